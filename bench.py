@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- train seq/s of the Transformer hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps (``ms_per_step``: wall milliseconds of one of them), writes the last
+timed step's outputs with ``--dump-outputs DIR`` and prints the result line.  ``--full`` adds everything else the
+benchmark measures or checks after the timed steps: the CPU-oracle parity of a held-out batch, the grid leg below,
+the per-kernel rooflines (dominant plane-GEMM launch inside and outside train steps, the large launch, fp8), the
+lockstep fits and the CPU baseline (``--no-grid`` / ``--no-cpu-baseline`` still drop those two).
 
 One "step" = one full training step (forward + CrossEntropyLoss + backward +
 clip_grad_norm_(0.5) + SGD-momentum) of BASELINE.json configs[1]
@@ -11,7 +17,8 @@ token ids that is already resident in HBM (hipGraph replay or plain stream launc
 whichever a short probe during warmup finds faster -- slnlp/launch.py).
 N>1: one process per GPU over RCCL (the driver launches the ranks with
 torch.distributed.run; run by hand without WORLD_SIZE, ``--gpus N`` spawns the N
-rank processes itself before anything touches the GPU).  Two legs per N:
+rank processes itself before anything touches the GPU).  Two legs per N (the
+second with ``--full``):
 
 * ``value``: every rank runs its own independent fit (the reference's only
   parallelism is the embarrassingly parallel (candidate x fold) grid, SURVEY.md
@@ -492,6 +499,24 @@ def cpu_baseline(c, sd, X, y, Ln, budget_s=14.0):
             "one_thread": {"value": round(v_one, 2), "cores": 1, "sample": f"{n3} steps ({dt3:.1f} s), dropout {c['dropout']}"}}
 
 
+DUMP_PARAM_SAMPLE = 1 << 20    # parameters written by --dump-outputs: a fixed sample (the cfg2 arena alone is 108 MB)
+
+
+def dump_outputs(out_dir, eng, logp):
+    """``--dump-outputs``: what a caller of the timed train step holds after the last timed step, as float32 .npy files --
+    ``logp`` (that step's log-probs [B, Vt]), ``loss`` and ``grad_norm`` (its scalars, shape [1]) and ``params_sample``
+    (DUMP_PARAM_SAMPLE elements of the updated parameter arena at sorted positions drawn with numpy seed 0, or the whole
+    arena if it is smaller).  The inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = eng.params.detach().cpu().numpy()
+    idx = np.arange(params.size)
+    if params.size > DUMP_PARAM_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(params.size, size=DUMP_PARAM_SAMPLE, replace=False))
+    arrays = {"logp": logp.detach().cpu().numpy(), "loss": [eng.loss], "grad_norm": [eng.grad_norm], "params_sample": params[idx]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def spawn_ranks(n):
     """``--gpus N`` run by hand (no WORLD_SIZE): start the N rank processes -- fresh children, before this parent has
     touched the GPU -- hand them the rendezvous through the environment torch.distributed.run would set, relay rank 0's
@@ -531,6 +556,12 @@ def main():
                     help="hipGraph replay, plain stream launches, or time both during warmup and keep the faster (default)")
     ap.add_argument("--eager", action="store_true", help="same as --launch eager")
     ap.add_argument("--dropout", type=float, default=None, help="override the workload's dropout rate (0: what the dropout epilogues cost)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (log-probs, loss, grad norm, a fixed sample of the updated parameters) "
+                         "to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU-oracle parity check, the grid leg, the per-kernel rooflines, the "
+                         "lockstep fits and the CPU baseline (a plain run reports the timed steps only)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -596,9 +627,11 @@ def main():
     pre_warmup = max(0, 2 + 2 * PROBE - args.warmup) if launch == "auto" else 0
 
     def run(k0, k):
+        logp = None
         for i in range(k0, k0 + k):
             j = (i % n_batches) * B
-            eng.step(Xd[j:j + B], yd[j:j + B], Ld[j:j + B], MOMENTUM, MAX_NORM, graph=launch)
+            logp = eng.step(Xd[j:j + B], yd[j:j + B], Ld[j:j + B], MOMENTUM, MAX_NORM, graph=launch)
+        return logp
 
     def barrier():
         torch.cuda.synchronize(dev)
@@ -614,12 +647,14 @@ def main():
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         ev0.record(stream)
-        run(args.warmup, args.steps)
+        logp_last = run(args.warmup, args.steps)
         ev1.record(stream)
         barrier()
         wall = time.perf_counter() - t0
     ev_ms = ev0.elapsed_time(ev1)
     loss_end = eng.loss
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, logp_last)      # before anything below steps the engine again
     rank_walls = [wall]
     if world > 1:
         t = torch.zeros(world, dtype=torch.float64, device="cpu" if shared else dev)
@@ -630,7 +665,7 @@ def main():
 
     # outside the timed region: the dominant kernel's launches timed inside eager train steps (rank 0; roofline.population)
     in_step = None
-    if rank == 0 and "rnn" not in c:
+    if args.full and rank == 0 and "rnn" not in c:
         def run_eager(k):
             with torch.cuda.stream(stream):
                 for i in range(k):
@@ -644,7 +679,7 @@ def main():
     # ---- leg 2: the sharded grid search, every rank takes part (collectives inside)
     chosen = eng._launch.mode((B, float(MOMENTUM), float(MAX_NORM))) if launch == "auto" else None
     grid = None
-    if "rnn" not in c and not args.no_grid:
+    if args.full and "rnn" not in c and not args.no_grid:
         del eng
         torch.cuda.empty_cache()
         grid = grid_folds_per_hour(dev, world, rank, fits_per_gpu=args.fits_per_gpu, lockstep=args.lockstep)
@@ -660,18 +695,20 @@ def main():
         step_flops = 3.0 * fwd_flops_per_seq(c) * B
         ms_event = ev_ms / args.steps           # HIP events on the launch stream, rank 0
         achieved = step_flops / (ms_event * 1e-3) / 1e12
-        # parity on a held-out batch (eval mode) against the CPU oracle
-        cfg0, sd0 = build_sd(c, seed=1)
-        Xe, ye, Le = torch.from_numpy(Xn[:B]), torch.from_numpy(yn[:B]), torch.from_numpy(Ln[:B])
-        if "rnn" in c:
-            e2 = re_.RnnEngine(cfg0, device=dev)
-            e2.load_state(sd0)
-            lp = e2.forward(Xe.to(dev), ye.to(dev), Le.to(dev)).cpu()
-        else:
-            e2 = te.TransformerEngine(cfg0, device=dev)
-            e2.load_state(sd0)
-            lp = e2.forward(Xe.to(dev), ye.to(dev)).cpu()
-        parity = cpu_parity(c, sd0, Xe, ye, Le, lp)
+        parity = None
+        if args.full:
+            # parity on a held-out batch (eval mode) against the CPU oracle
+            cfg0, sd0 = build_sd(c, seed=1)
+            Xe, ye, Le = torch.from_numpy(Xn[:B]), torch.from_numpy(yn[:B]), torch.from_numpy(Ln[:B])
+            if "rnn" in c:
+                e2 = re_.RnnEngine(cfg0, device=dev)
+                e2.load_state(sd0)
+                lp = e2.forward(Xe.to(dev), ye.to(dev), Le.to(dev)).cpu()
+            else:
+                e2 = te.TransformerEngine(cfg0, device=dev)
+                e2.load_state(sd0)
+                lp = e2.forward(Xe.to(dev), ye.to(dev)).cpu()
+            parity = cpu_parity(c, sd0, Xe, ye, Le, lp)
         out = {
             "metric": f"train seq/s (batch={B},len={S})", "value": round(seqs / wall, 1), "unit": "seq/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -691,11 +728,13 @@ def main():
                               "traffic": pmc_traffic(args.workload)[0], "traffic_source": pmc_traffic(args.workload)[1],
                               "launch": "one train step (all its kernels)", "flops_per_launch": step_flops,
                               "ms_per_launch_hip_events": round(ms_event, 4)},
-            "parity": parity, "final_loss": round(loss_end, 5),
+            "final_loss": round(loss_end, 5),
         }
+        if parity is not None:
+            out["parity"] = parity
         if grid is not None:
             out["grid"] = grid
-        if "rnn" not in c:
+        if args.full and "rnn" not in c:
             with torch.cuda.stream(stream):
                 dk = dominant_kernel_roofline(c, 3 if args.precision == 8 else args.precision, dev, args.workload, in_step)
                 if args.precision == 8:
@@ -704,10 +743,10 @@ def main():
                 out["roofline"] = dk
                 with torch.cuda.stream(stream):
                     out["roofline_large_launch"] = large_launch_roofline(3 if args.precision == 8 else args.precision, dev)
-        if world == 1 and not args.no_cpu_baseline and args.precision != 8:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.precision != 8:
             out["concurrent_fits"] = concurrent_fits(c, args.precision, dev)
         out.setdefault("roofline", dict(out["roofline_step"]))   # RNN workloads: no single dominant GEMM, the step is the unit
-        if not args.no_cpu_baseline and world == 1:       # reported at N = 1 only (the other ranks would just wait)
+        if args.full and not args.no_cpu_baseline and world == 1:       # reported at N = 1 only (the other ranks would just wait)
             out["cpu_baseline"] = cpu_baseline(c, sd0, torch.from_numpy(Xn), torch.from_numpy(yn), torch.from_numpy(Ln))
             out["gpu_over_cpu"] = round(out["value"] / world / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)

@@ -505,15 +505,16 @@ def test_one_rank_under_a_launcher_scores_like_one_rank_alone():
 
 
 def test_simulated_schedule_with_the_unit_duration_spread_measured_to_early_stopping():
-    """a grid run to EarlyStopping (profiles/r05_grid_long.json: 120 fits, max_epochs 80, patience 30; a third of the
-    fits stop early, 26 regroupings) says how far a unit's duration strays from its estimated cost: 0.70 ... 2.57 of the median
-    ratio.  The simulated 8-GPU schedule of the bench sample is re-run with every unit's work scaled by those measured ratios
-    (dealt out cyclically, several phases): the dynamic counter absorbs the spread -- strong-scaling efficiency stays >= 0.90 at
+    """a grid run to EarlyStopping (tests/golden/grid_long_unit_spread.json, the run these thresholds were set on:
+    120 fits, max_epochs 80, patience 30; a third of the fits stop early, 26 regroupings) says how far a unit's duration strays
+    from its estimated cost: 0.70 ... 2.57 of the median ratio.  A pinned record, not profiles/r05_grid_long.json: that file is
+    tools/bench_grid_long.py's output and is replaced by every new measurement.  The simulated 8-GPU schedule of the bench
+    sample is re-run with every unit's work scaled by those measured ratios (dealt out cyclically, several phases): the dynamic counter absorbs the spread -- strong-scaling efficiency stays >= 0.90 at
     8 GPUs and >= 0.93 at 2 / 4 -- while a static deal of the same units loses much more."""
     import json, os, bench
     from slnlp import grid_sim as gs
     cal = json.load(open(os.path.join(ROOT, "profiles", "r04_grid_calibration.json")))
-    long_run = json.load(open(os.path.join(ROOT, "profiles", "r05_grid_long.json")))
+    long_run = json.load(open(os.path.join(ROOT, "tests", "golden", "grid_long_unit_spread.json")))
     ratios = long_run["unit_seconds_over_estimated_cost_normalised"]["values"]
     assert len(ratios) >= 20 and min(ratios) < 0.8 and max(ratios) > 1.5
     per_fit = {}

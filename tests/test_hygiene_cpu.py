@@ -1,6 +1,6 @@
 """CPU checks of the host-side contract pieces around the hot path: the reference's ``model.util`` helpers against the
 golden masks, module copy / pickle keeping the parameter-arena aliasing, the skorch-callback translation, the scorer
-wrapper, the reference's ``fit(X=..., y=train.y().to_array())`` spelling, and bench.py's rank spawning."""
+wrapper, the reference's ``fit(X=..., y=train.y().to_array())`` spelling, and bench.py's rank spawning and output dump."""
 import copy
 import io
 import os
@@ -181,6 +181,27 @@ def test_bench_spawns_one_fresh_process_per_rank(monkeypatch):
     assert [env["RANK"] for _, env in started] == ["0", "1"] and [env["LOCAL_RANK"] for _, env in started] == ["0", "1"]
     assert all(cmd[0] == sys.executable and cmd[1].endswith("bench.py") and cmd[2:] == ["--gpus", "2", "--steps", "3"] for cmd, _ in started)
     assert not torch.cuda.is_initialized()                          # the parent never touched the GPU
+
+
+def test_bench_dump_outputs_are_float32_files_with_a_fixed_parameter_sample(tmp_path):
+    """bench.py --dump-outputs: the last timed step's log-probs, loss and grad norm and a seeded sample of the parameter arena,
+    float32, well inside 64 MB, and the same sample positions in every run (two builds compare file by file)."""
+    import bench
+
+    class FakeEngine:
+        params = torch.arange(3 << 20, dtype=torch.float32)
+        loss, grad_norm = 2.5, 0.75
+    logp = torch.randn(50, 202, generator=torch.Generator().manual_seed(0))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), FakeEngine(), logp)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad_norm.npy", "logp.npy", "loss.npy", "params_sample.npy"]
+    arrays = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype == np.float32 and np.array_equal(a, np.load(tmp_path / "b" / f"{n}.npy")) for n, a in arrays.items())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert np.array_equal(arrays["logp"], logp.numpy()) and arrays["loss"].tolist() == [2.5] and arrays["grad_norm"].tolist() == [0.75]
+    s = arrays["params_sample"]                                     # values of arange = the sampled positions
+    assert s.size == bench.DUMP_PARAM_SAMPLE and np.all(np.diff(s) > 0) and s[-1] < FakeEngine.params.numel()
 
 
 def test_product_package_never_imports_the_oracle():

@@ -1,7 +1,7 @@
 # rocprofv3 profiles of a round: kernel traces, HBM-traffic PMC passes, SQ counters.  One script for every round:
 #     bash tools/gpu/profile.sh <round tag, e.g. r04> <out dir> [section ...]
 # sections (default: all): trace traffic traffic_more sq big lockstep cfg5 cfg5p8 rnn
-#   trace     kernel trace of the default bench command -> <tag>_bench_cfg2_kernel_trace_summary.txt, <tag>_bench_cfg2_roofline_kernel.json
+#   trace     kernel trace of the bench command with --full (its roofline legs) -> <tag>_bench_cfg2_kernel_trace_summary.txt, <tag>_bench_cfg2_roofline_kernel.json
 #   traffic   FETCH_SIZE / WRITE_SIZE passes of the eager cfg2 step -> <tag>_pmc_cfg2_step_traffic.json
 #   traffic_more  the same for the other workloads' steps (TRAFFIC_WORKLOADS, default cfg5 cfg3 cfg1 e1024 cfg3gru) -> <tag>_pmc_<workload>_step_traffic.json
 #   sq        SQ counters of the cfg2 dgrad + wgrad group -> <tag>_mfma_util_sq.json, <tag>_pmc_plane_gemm_sq*_raw.txt
@@ -26,7 +26,7 @@ trace() {   # trace <name> <summary file> <program...>
   echo "[prof] $out"; head -14 $O/$out | cut -c1-160; tail -1 $O/$out
 }
 if has trace; then
-  trace bench ${TAG}_bench_cfg2_kernel_trace_summary.txt python3 bench.py --steps 20 --warmup 20 --no-cpu-baseline --no-grid || exit 1
+  trace bench ${TAG}_bench_cfg2_kernel_trace_summary.txt python3 bench.py --full --steps 20 --warmup 20 --no-cpu-baseline --no-grid || exit 1
   KT=$(ls $R/bench/*/*kernel_trace.csv | head -1)
   python3 tools/roofline_kernel_stats.py $KT 496 $O/${TAG}_bench_cfg2_roofline_kernel.json
   tail -1 $O/bench.stdout > $O/${TAG}_bench_cfg2_traced.json
@@ -68,10 +68,10 @@ if has traffic_more; then   # HBM traffic of the configs[4] and configs[2] steps
   done
   echo "[prof] traffic of the other workloads done"
 fi
-if has cfg5; then trace c5 ${TAG}_bench_cfg5_kernel_trace_summary.txt python3 bench.py --workload cfg5 --steps 8 --warmup 4 --no-cpu-baseline --no-grid; fi
-if has cfg5p8; then trace c5p8 ${TAG}_bench_cfg5_p8_kernel_trace_summary.txt python3 bench.py --workload cfg5 --precision 8 --steps 8 --warmup 4 --no-cpu-baseline --no-grid; fi
+if has cfg5; then trace c5 ${TAG}_bench_cfg5_kernel_trace_summary.txt python3 bench.py --full --workload cfg5 --steps 8 --warmup 4 --no-cpu-baseline --no-grid; fi
+if has cfg5p8; then trace c5p8 ${TAG}_bench_cfg5_p8_kernel_trace_summary.txt python3 bench.py --full --workload cfg5 --precision 8 --steps 8 --warmup 4 --no-cpu-baseline --no-grid; fi
 if has rnn; then
-  trace rnn ${TAG}_bench_cfg3_kernel_trace_summary.txt python3 bench.py --workload cfg3 --steps 10 --warmup 6 --no-cpu-baseline --no-grid
+  trace rnn ${TAG}_bench_cfg3_kernel_trace_summary.txt python3 bench.py --full --workload cfg3 --steps 10 --warmup 6 --no-cpu-baseline --no-grid
   trace rnnls ${TAG}_lockstep_cfg3_k8_kernel_trace_summary.txt python3 tools/bench_lockstep.py --workload cfg3 --ks 8 --steps 6
 fi
 ls -la $O | head -40

@@ -14,7 +14,7 @@
 #   net          estimator / lockstep / configs tests
 #   suite        the whole -m gpu suite
 #   bench        default bench line (cfg2) without grid / cpu baseline
-#   bench_full   the default bench.py run, exactly as the driver runs it
+#   bench_full   bench.py --full with its default arguments: every leg (grid, rooflines, lockstep fits, CPU baseline)
 #   records      every other workload's bench line with its cpu_baseline (cfg1, cfg3, cfg3gru, e1024, cfg5, cfg5 precision 8)
 #   bench_cfg5   cfg5 (configs[4] shape) line, precision 3
 #   bench_cfg5p8 ... precision 8
@@ -68,20 +68,20 @@ for spec in "$@"; do
       timeout -k 10 1100 python -m pytest $T -k "$KEXPR" -q -x > $O/$step.log 2>&1; rc=$?
       tail -3 $O/$step.log | cut -c1-300
       if [ $rc -ne 0 ]; then grep -E "^E |^FAILED|^ERROR" $O/$step.log | head -20 | cut -c1-300; exit $rc; fi ;;
-    bench)       timeout -k 10 300 python bench.py --steps 100 --warmup 20 --no-grid --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }; line $O/bench.json ;;
-    bench_full)  timeout -k 10 600 python bench.py > $O/bench_full.json 2> $O/bench_full.err || { tail -5 $O/bench_full.err; exit 1; }; line $O/bench_full.json ;;
-    bench_cfg5)  timeout -k 10 400 python bench.py --workload cfg5 --steps 20 --warmup 5 --no-grid --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err || { tail -5 $O/bench_cfg5.err; exit 1; }; line $O/bench_cfg5.json ;;
-    bench_cfg5p8) timeout -k 10 400 python bench.py --workload cfg5 --precision 8 --steps 20 --warmup 5 --no-grid --no-cpu-baseline > $O/bench_cfg5_p8.json 2> $O/bench_cfg5_p8.err || { tail -5 $O/bench_cfg5_p8.err; exit 1; }; line $O/bench_cfg5_p8.json ;;
-    bench_rnn)   for w in cfg3 cfg3gru; do timeout -k 10 400 python bench.py --workload $w --steps 40 --warmup 10 --no-grid --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || { tail -5 $O/bench_$w.err; exit 1; }; line $O/bench_$w.json; done ;;
+    bench)       timeout -k 10 300 python bench.py --full --steps 100 --warmup 20 --no-grid --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }; line $O/bench.json ;;
+    bench_full)  timeout -k 10 600 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err || { tail -5 $O/bench_full.err; exit 1; }; line $O/bench_full.json ;;
+    bench_cfg5)  timeout -k 10 400 python bench.py --full --workload cfg5 --steps 20 --warmup 5 --no-grid --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err || { tail -5 $O/bench_cfg5.err; exit 1; }; line $O/bench_cfg5.json ;;
+    bench_cfg5p8) timeout -k 10 400 python bench.py --full --workload cfg5 --precision 8 --steps 20 --warmup 5 --no-grid --no-cpu-baseline > $O/bench_cfg5_p8.json 2> $O/bench_cfg5_p8.err || { tail -5 $O/bench_cfg5_p8.err; exit 1; }; line $O/bench_cfg5_p8.json ;;
+    bench_rnn)   for w in cfg3 cfg3gru; do timeout -k 10 400 python bench.py --full --workload $w --steps 40 --warmup 10 --no-grid --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err || { tail -5 $O/bench_$w.err; exit 1; }; line $O/bench_$w.json; done ;;
     records)     # every workload's bench line WITH its cpu_baseline (the round's record-keeping runs -> profiles/<round>_bench_<workload>.json)
-                 for w in cfg1 cfg3 cfg3gru e1024 cfg5; do timeout -k 10 500 python bench.py --workload $w --steps 40 --warmup 10 --no-grid > $O/bench_$w.json 2> $O/bench_$w.err || { tail -5 $O/bench_$w.err; exit 1; }; line $O/bench_$w.json; done
-                 timeout -k 10 500 python bench.py --workload cfg5 --precision 8 --steps 40 --warmup 10 --no-grid > $O/bench_cfg5_p8.json 2> $O/bench_cfg5_p8.err || { tail -5 $O/bench_cfg5_p8.err; exit 1; }; line $O/bench_cfg5_p8.json ;;
+                 for w in cfg1 cfg3 cfg3gru e1024 cfg5; do timeout -k 10 500 python bench.py --full --workload $w --steps 40 --warmup 10 --no-grid > $O/bench_$w.json 2> $O/bench_$w.err || { tail -5 $O/bench_$w.err; exit 1; }; line $O/bench_$w.json; done
+                 timeout -k 10 500 python bench.py --full --workload cfg5 --precision 8 --steps 40 --warmup 10 --no-grid > $O/bench_cfg5_p8.json 2> $O/bench_cfg5_p8.err || { tail -5 $O/bench_cfg5_p8.err; exit 1; }; line $O/bench_cfg5_p8.json ;;
     lockstep)    timeout -k 10 400 python tools/bench_lockstep.py --workload cfg2 --ks 1,4,15 --steps 12 > $O/lockstep.json 2> $O/lockstep.err || { tail -5 $O/lockstep.err; exit 1; }
                  tail -1 $O/lockstep.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['workload'], [(r['K'], r['seq_per_s'], r['ms_per_lockstep_step']) for r in d['results']])" ;;
     lockstep_rnn) for w in cfg3 cfg3gru; do timeout -k 10 400 python tools/bench_lockstep.py --workload $w --ks 1,4,16 --steps 12 > $O/lockstep_$w.json 2> $O/lockstep_$w.err || { tail -5 $O/lockstep_$w.err; exit 1; }
                  tail -1 $O/lockstep_$w.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['workload'], [(r['K'], r['seq_per_s'], r['ms_per_lockstep_step']) for r in d['results']])"; done ;;
-    grid)        timeout -k 10 500 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/grid.json 2> $O/grid.err || { tail -5 $O/grid.err; exit 1; }; line $O/grid.json ;;
-    rehearsal)   timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/rehearsal.json 2> $O/rehearsal.err || { tail -5 $O/rehearsal.err; exit 1; }; line $O/rehearsal.json ;;
+    grid)        timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/grid.json 2> $O/grid.err || { tail -5 $O/grid.err; exit 1; }; line $O/grid.json ;;
+    rehearsal)   timeout -k 10 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/rehearsal.json 2> $O/rehearsal.err || { tail -5 $O/rehearsal.err; exit 1; }; line $O/rehearsal.json ;;
     smoke)       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail -5 $O/smoke.txt; exit 1; }; tail -2 $O/smoke.txt ;;
     fullgrid)    timeout -k 10 600 python tools/full_grid.py --lockstep 15 > $O/full_grid_324x5.json 2> $O/fullgrid.err || { tail -8 $O/fullgrid.err; exit 1; }; cut -c1-400 $O/full_grid_324x5.json ;;
     passerr)     timeout -k 10 400 python tools/backward_pass_errors.py ${PASSERR:-cfg1 cfg2 cfg5} > $O/passerr.jsonl 2> $O/passerr.err || { tail -5 $O/passerr.err; exit 1; }; cat $O/passerr.jsonl ;;

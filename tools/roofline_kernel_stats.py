@@ -1,5 +1,5 @@
 """In-step vs back-to-back durations of the `roofline` kernel (grouped plane GEMM of one dY) from a rocprofv3 --kernel-trace CSV
-of `python bench.py`: the trailing run of consecutive launches is bench.py's own HIP-event measurement, the rest ran inside
+of `python bench.py --full`: the trailing run of consecutive launches is bench.py's own HIP-event measurement, the rest ran inside
 train steps.  usage: roofline_kernel_stats.py <kernel_trace.csv> <workgroups> [out.json]"""
 import csv, json, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
