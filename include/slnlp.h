@@ -242,6 +242,13 @@ int slnlp_ln_param_reduce(const slnlp_ln_reduce_entry* table_dev, int n, int max
 int slnlp_lsm_nll(const float* logits, int64_t ld_logits, const int64_t* y, int B, int V,
                   int64_t ignore_index, float* logp, float* loss, float* dlogits, int64_t ld_dlogits,
                   float* row_scratch /* [B] */, void* stream);
+/* slnlp_lsm_nll with the rest of CrossEntropyLoss (torch's composition, on the log-probs):
+ * class_weight [V] (device, or NULL: all ones), label_smoothing in [0, 1], reduction 0 = "mean" (divided by the
+ * summed class weight of the kept rows; NaN when no row is kept) or 1 = "sum".  At (NULL, 0, 0) the result is
+ * bit-identical to slnlp_lsm_nll. */
+int slnlp_lsm_nll_ex(const float* logits, int64_t ld_logits, const int64_t* y, int B, int V, int64_t ignore_index,
+                     const float* class_weight, float label_smoothing, int reduction, float* logp, float* loss,
+                     float* dlogits, int64_t ld_dlogits, float* row_scratch /* [B] */, void* stream);
 /* backward of log_softmax alone, for callers that own the criterion (torch
  * autograd): dlogits = dlogp - exp(logp) * rowsum(dlogp). */
 int slnlp_lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dlogits,
@@ -257,6 +264,22 @@ int slnlp_clip_sgd_step(float* params, const float* grads, float* momentum_buf, 
                         const float* lr_dev, float momentum, float max_norm,
                         float* partials /* [1024] scratch */, float* norm_out,
                         unsigned long long* rng, void* stream);
+
+/* slnlp_clip_sgd_step with the rest of torch.optim.SGD (torch/optim/sgd.py _single_tensor_sgd): d = g' + weight_decay p;
+ * buf = d on the first step, m buf + (1 - dampening) d after; d = d + m buf (nesterov) or buf; p -= lr d.
+ * step_count[0] (float, device) counts the steps taken (0 before the first) and is advanced by one; required unless the
+ * settings are plain SGD-momentum.  Floats [skip_begin, skip_end) (multiples of 4; empty when skip_end <= skip_begin) are a
+ * parameter torch never steps and stay untouched.  nesterov needs momentum > 0 and dampening 0, as in torch. */
+int slnlp_clip_sgd_step_ex(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
+                           float momentum, float dampening, float weight_decay, int nesterov, float max_norm,
+                           float* partials /* [1024] scratch */, float* norm_out, float* step_count, int64_t skip_begin,
+                           int64_t skip_end, void* stream);
+/* clip_grad_norm_ + torch.optim.AdamW: p *= 1 - lr weight_decay, then the Adam update without an L2 term; the skip range
+ * as in slnlp_clip_sgd_step_ex; step_count as in slnlp_clip_adam_step. */
+int slnlp_clip_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                          float* partials /* [1024] scratch */, float* norm_out, float* step_count, int64_t skip_begin,
+                          int64_t skip_end, void* stream);
 
 /* clip_grad_norm_ + torch.optim.Adam (amsgrad False; torch/optim/adam.py _single_tensor_adam) over one flat arena:
  * step_count[0] (float, device) holds the number of steps taken so far and is advanced by one. */
@@ -410,7 +433,7 @@ typedef struct slnlp_tf_buffers {
     void* workspace;             /* slnlp_tf_workspace_bytes */
     unsigned long long* rng;     /* [2] = {seed, step} */
     float* lr;                   /* [1] */
-    float* scalars;              /* [4] = {loss, grad_norm, -, -} */
+    float* scalars;              /* [4] = {loss, grad_norm, Adam step count, SGD step count} */
 } slnlp_tf_buffers;
 
 typedef struct slnlp_tf_plan slnlp_tf_plan;
@@ -457,6 +480,22 @@ int slnlp_tf_debug_layout(const slnlp_tf_config* cfg, char* out, int64_t out_byt
  * a stream-ordered allocator on the stream the plan ran on (torch's caching allocator), where the device-wide wait stalls
  * every other host thread's queued work each time a fit ends. */
 int slnlp_tf_set_destroy_sync(slnlp_tf_plan* plan, int on);
+
+/* Criterion and update settings of a plan (default: CrossEntropyLoss(ignore_index=pad) and plain SGD-momentum).
+ * set_criterion: class_weight [Vt] in HOST memory (copied into device memory the plan owns, on `stream`; NULL: none),
+ * label_smoothing in [0, 1], reduction 0 = "mean" / 1 = "sum"; used by every forward (train and eval).
+ * set_update: kind SLNLP_UPDATE_SGD -- slnlp_tf_optim runs torch.optim.SGD with dampening / weight_decay / nesterov (the step
+ * count lives in scalars[3]); SLNLP_UPDATE_ADAM / _ADAMW -- slnlp_tf_optim_adam runs Adam / AdamW (AdamW: decoupled decay)
+ * with the weight_decay of that call, and a lockstep group's Adam update uses THIS weight_decay for the plan instead of the
+ * group's (slnlp_tf_lockstep_set_adam), so fits that differ in it step in one group; dampening and nesterov must be 0.
+ * A call that changes a setting drops the plan's captured graphs (re-capture with slnlp_tf_graph_capture_train), and a
+ * lockstep group drops its programs, hands their table space back and re-records before its next step; a call that changes
+ * nothing drops nothing. */
+#define SLNLP_UPDATE_SGD 0
+#define SLNLP_UPDATE_ADAM 1
+#define SLNLP_UPDATE_ADAMW 2
+int slnlp_tf_set_criterion(slnlp_tf_plan* plan, const float* class_weight, float label_smoothing, int reduction, void* stream);
+int slnlp_tf_set_update(slnlp_tf_plan* plan, int kind, float dampening, float weight_decay, int nesterov);
 
 /* One kernel sequence per device (default).  The step entry points (slnlp_{tf,rnn}_{forward,backward,optim*,train_step,
  * graph_launch}, slnlp_*_lockstep_{step,epoch}) serialise per device: host threads enqueue whole steps in turn, and a step issued
@@ -574,6 +613,10 @@ int slnlp_rnn_optim(slnlp_rnn_plan* plan, float momentum, float max_norm, void* 
 int slnlp_rnn_optim_adam(slnlp_rnn_plan* plan, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
                          float max_norm, void* stream);
 int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* plan, int on);   /* as slnlp_tf_set_destroy_sync */
+/* as slnlp_tf_set_criterion / slnlp_tf_set_update; the decoder's pre_output_layer (never given a gradient) is exempt from
+ * weight decay, as torch skips a parameter whose grad is None */
+int slnlp_rnn_set_criterion(slnlp_rnn_plan* plan, const float* class_weight, float label_smoothing, int reduction, void* stream);
+int slnlp_rnn_set_update(slnlp_rnn_plan* plan, int kind, float dampening, float weight_decay, int nesterov);
 int slnlp_rnn_train_step(slnlp_rnn_plan* plan, const int64_t* X, const int64_t* y, const int64_t* lengths, int B,
                          float momentum, float max_norm, float* logp, void* stream);
 int slnlp_rnn_graph_capture_train(slnlp_rnn_plan* plan, const int64_t* X, const int64_t* y, const int64_t* lengths,

@@ -1,5 +1,6 @@
 // Shared device/host helpers for the slnlp gfx950 kernels.
 #pragma once
+#include <vector>
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <mutex>
@@ -333,9 +334,16 @@ struct LnPartialEntry {
 int ln_param_partial(const LnPartialEntry* table_dev, const LnPartialEntry* single_host, int n, int E, int rows_enc, int rows_dec,
                      int full_rows_enc, int full_rows_dec, hipStream_t st);
 int ln_partial_chunk(int rows);
+// CrossEntropyLoss settings beyond ignore_index (default: weight None, label_smoothing 0, reduction "mean")
+struct LossOpts {
+    const float* class_weight = nullptr;   // [V] device, or nullptr
+    float label_smoothing = 0.f;
+    int reduction = 0;                     // 0 "mean", 1 "sum"
+};
 int lsm_nll(const float* logits, int64_t ld_logits, const int64_t* y, int B, int V, int64_t ignore_index, float* logp,
             float* loss, float* dlogits, int64_t ld_dlogits, float* row_scratch, hipStream_t st, hipStream_t loss_st,
-            float* logp2 = nullptr, const int* logp2_row = nullptr, float* loss_hist = nullptr, const int* hist_idx = nullptr);
+            float* logp2 = nullptr, const int* logp2_row = nullptr, float* loss_hist = nullptr, const int* hist_idx = nullptr,
+            LossOpts lo = {});
 int lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dlogits, int64_t ld_dlogits, hipStream_t st);
 int rnn_cell_fwd(int lstm, const slnlp_rnn_cell_dir* dirs, int ndir, int B, int Hd, const int64_t* lengths, float fill,
                  int64_t ld_out, float drop_p, int drop_site, const unsigned long long* rng, hipStream_t st);
@@ -358,12 +366,59 @@ int bahdanau_bwd(const float* q, const float* pk, const float* val, const float*
                  float* dwe, hipStream_t st);
 int add_rows(const float* in, int64_t ld_in, float* out, int64_t ld_out, int R, int C, int accumulate, hipStream_t st);
 int tanh_bwd(const float* dy, const float* y, float* out, int64_t n, hipStream_t st);
+// torch.optim.SGD settings beyond momentum (default: plain SGD-momentum).  steps: a device float the update advances every
+// step (the first-step rule of dampening); [skip_begin, skip_end): floats the general update leaves untouched (a parameter
+// whose grad torch leaves None), multiples of 4, empty by default.
+struct SgdOpts {
+    float dampening = 0.f, weight_decay = 0.f;
+    int nesterov = 0;
+    float* steps = nullptr;
+    int64_t skip_begin = 0, skip_end = 0;
+};
+// decoupled: torch.optim.AdamW (weight_decay applied as p *= 1 - lr wd, skip range honoured) instead of Adam's L2 term
+struct AdamOpts {
+    int decoupled = 0;
+    int64_t skip_begin = 0, skip_end = 0;
+};
 int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
                   float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
-                  hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1);   // planes written for floats [wp_begin, wp_end); -1: to the end
+                  hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,   // planes written for floats [wp_begin, wp_end); -1: to the end
+                  SgdOpts so = {});
 int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
                    float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
-                   unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1);
+                   unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,
+                   AdamOpts ao = {});
+// A plan's criterion and update settings (slnlp_{tf,rnn}_set_criterion / _set_update).  The class weights are copied into
+// device memory the plan owns, so recorded programs and captured graphs keep a valid pointer; `gen` moves on every change
+// (a lockstep group re-records its programs when a fit's generation moved).
+struct TrainOpts {
+    float* class_weight = nullptr;          // [V] device copy, or nullptr
+    std::vector<float> class_weight_host;   // what it holds (change detection)
+    float label_smoothing = 0.f;
+    int reduction = 0;
+    int kind = 0;                           // SLNLP_UPDATE_SGD / _ADAM / _ADAMW
+    float dampening = 0.f, weight_decay = 0.f;
+    int nesterov = 0;
+    unsigned gen = 0;
+    TrainOpts() = default;
+    TrainOpts(const TrainOpts&) = delete;
+    TrainOpts& operator=(const TrainOpts&) = delete;
+    ~TrainOpts();
+    LossOpts loss() const { return LossOpts{class_weight, label_smoothing, reduction}; }
+    SgdOpts sgd(float* steps, int64_t skip_begin, int64_t skip_end) const {
+        if (kind != 0) return SgdOpts{0.f, 0.f, 0, steps, skip_begin, skip_end};    // the settings are Adam's
+        return SgdOpts{dampening, weight_decay, nesterov, steps, skip_begin, skip_end};
+    }
+    AdamOpts adam(int64_t skip_begin, int64_t skip_end) const { return AdamOpts{kind == 2 ? 1 : 0, skip_begin, skip_end}; }
+    // the weight decay of a lockstep group's Adam update for this fit: the plan's own once its kind is Adam / AdamW (a
+    // per-fit setting), else the group's (slnlp_*_lockstep_set_adam)
+    float adam_weight_decay(float group) const { return kind == 0 ? group : weight_decay; }
+    // *changed: whether anything differs from before (the caller then drops what it recorded with the old settings).
+    // cw: host memory; uploaded to the plan's copy on `st`
+    int set_criterion(int V, const float* cw, float eps, int reduction, hipStream_t st, bool* changed);
+    int set_update(int kind, float dampening, float weight_decay, int nesterov, bool* changed);
+};
+
 // Which version of a parameter arena a plan's derived data (bf16 weight planes) was made from: every optimizer step and
 // every slnlp_*_params_changed() call moves the arena to a new generation (process-wide table keyed by the arena pointer,
 // because several plans -- one per sequence length -- may share one arena).

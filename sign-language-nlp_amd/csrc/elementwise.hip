@@ -717,14 +717,89 @@ constexpr int LOSS_MAXB = 1024;
 
 // grid = B rows, one wave each.  n_valid (targets != ignore_index) is recomputed by every row (B <= 1024
 // compares) so d loss/d logits needs no second pass; the scalar loss is summed by lsm_loss_reduce_kernel.
+// CrossEntropyLoss(weight=cw, label_smoothing=eps, reduction=sum ? "sum" : "mean") on the log-probs, rows with
+// y != ignore (torch's composition, kept = the rows counted in D):
+//   loss = [(1-eps) sum_i w[y_i] (-l[i,y_i]) + (eps/V) sum_i sum_c w[c] (-l[i,c])] / D,  l = log_softmax(logp)
+//   D = sum_i w[y_i] ("mean") or 1 ("sum"); w = 1 without class weights.
+// d loss / d l[i,c] = -a[c] / D with a[c] = (1-eps) w[y_i] [c == y_i] + (eps/V) w[c]; through the criterion's log_softmax
+// d loss / d logp[i,c] = (exp(l[i,c]) A - a[c]) / D with A = sum_c a[c].  Only called off the default settings: the plain
+// body below keeps today's arithmetic exactly.
+__device__ __forceinline__ void lsm_nll_general(const float* __restrict__ logits, long ld, const long* __restrict__ y,
+                                                int B, int V, long ignore, float* __restrict__ logp,
+                                                float* __restrict__ row_nll, float* __restrict__ dlogits, long ldd,
+                                                float* __restrict__ logp2, const float* __restrict__ cw, float eps,
+                                                int sum_red) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    float dsum = 0.f;
+    for (int i = lane; i < B; i += 64) {
+        const long t = y[i];
+        if (t != ignore && t >= 0 && t < V) dsum += cw ? cw[t] : 1.f;
+    }
+    const float D = wave_sum(dsum);
+    const float* xr = logits + (long)b * ld;
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, xr[v]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += expf(xr[v] - m);
+    const float lse = m + logf(wave_sum(s));
+    float m2 = -INFINITY;
+    for (int v = lane; v < V; v += 64) {
+        const float lp = xr[v] - lse;
+        logp[(long)b * V + v] = lp;
+        if (logp2) logp2[(long)b * V + v] = lp;
+        m2 = fmaxf(m2, lp);
+    }
+    m2 = wave_max(m2);
+    float s2 = 0.f;
+    for (int v = lane; v < V; v += 64) s2 += expf((xr[v] - lse) - m2);
+    const float lse2 = m2 + logf(wave_sum(s2));
+    // the smoothing term's two row sums: sum_c w[c] l[c] (loss) and sum_c w[c] (gradient)
+    float swl = 0.f, sw = 0.f;
+    for (int v = lane; v < V; v += 64) {
+        const float wc = cw ? cw[v] : 1.f;
+        swl += wc * ((xr[v] - lse) - lse2);
+        sw += wc;
+    }
+    swl = wave_sum(swl);
+    sw = wave_sum(sw);
+    const long t = y[b];
+    const bool valid = (t != ignore) && t >= 0 && t < V;
+    const float wt = valid ? (cw ? cw[t] : 1.f) : 0.f;
+    const float es = eps / (float)V, keep = 1.f - eps;
+    // NaN marks "ignored"; the reduce kernel divides by D
+    if (lane == 0) row_nll[b] = valid ? keep * wt * -((xr[t] - lse) - lse2) - es * swl : NAN;
+    if (!dlogits) return;
+    const float inv = valid ? (sum_red ? 1.f : 1.f / D) : 0.f;
+    const float A = keep * wt + es * sw;
+    float sum = 0.f;
+    for (int v = lane; v < V; v += 64) {
+        const float a = (v == t ? keep * wt : 0.f) + es * (cw ? cw[v] : 1.f);
+        sum += inv * (expf((xr[v] - lse) - lse2) * A - a);
+    }
+    sum = wave_sum(sum);
+    for (int v = lane; v < V; v += 64) {
+        const float lp = xr[v] - lse;
+        const float a = (v == t ? keep * wt : 0.f) + es * (cw ? cw[v] : 1.f);
+        const float dlp = inv * (expf(lp - lse2) * A - a);
+        dlogits[(long)b * ldd + v] = dlp - expf(lp) * sum;
+    }
+}
+
 __device__ __forceinline__ void lsm_nll_body(const float* __restrict__ logits, long ld, const long* __restrict__ y,
                                                      int B, int V, long ignore, float* __restrict__ logp,
                                                      float* __restrict__ row_nll, float* __restrict__ dlogits, long ldd,
-                                                     float* __restrict__ logp2, const int* __restrict__ logp2_row) {
+                                                     float* __restrict__ logp2, const int* __restrict__ logp2_row,
+                                                     const float* __restrict__ cw, float eps, int sum_red) {
     // logp2 (optional): a second copy of the log-probs for the caller, at row offset *logp2_row (a device scalar, so a
     // recorded launch can walk an epoch's output buffer) -- replaces a device-to-device copy per step
     const int lane = threadIdx.x, b = blockIdx.x;
     if (logp2) logp2 += (long)(logp2_row ? *logp2_row : 0) * V;
+    // class weights / label smoothing / sum: runtime arguments (lockstep merges fits that differ in them into one launch)
+    if (cw || eps != 0.f || sum_red) {
+        lsm_nll_general(logits, ld, y, B, V, ignore, logp, row_nll, dlogits, ldd, logp2, cw, eps, sum_red);
+        return;
+    }
     int cnt = 0;
     for (int i = lane; i < B; i += 64) {
         const long t = y[i];
@@ -768,14 +843,27 @@ __device__ __forceinline__ void lsm_nll_body(const float* __restrict__ logits, l
 SLNLP_ZKERNEL(lsm_nll_kernel, 64, lsm_nll_body)
 
 __device__ __forceinline__ void lsm_loss_reduce_body(const float* __restrict__ row_nll, int B, float* __restrict__ loss,
-                                                     float* __restrict__ loss_hist, const int* __restrict__ hist_idx) {
+                                                     float* __restrict__ loss_hist, const int* __restrict__ hist_idx,
+                                                     const long* __restrict__ y, int V, long ignore, const float* __restrict__ cw,
+                                                     int general, int sum_red) {
     float tot = 0.f, n = 0.f;
-    for (int b = threadIdx.x; b < B; b += 64) {
-        const float v = row_nll[b];
-        if (v == v) { tot += v; n += 1.f; }
+    if (general) {   // lsm_nll_general's rows: n = D (sum of the kept rows' class weights), or 1 for "sum"
+        for (int b = threadIdx.x; b < B; b += 64) {
+            const float v = row_nll[b];
+            if (v == v) tot += v;
+            const long t = y[b];
+            if (t != ignore && t >= 0 && t < V) n += cw ? cw[t] : 1.f;
+        }
+        tot = wave_sum(tot);
+        n = sum_red ? 1.f : wave_sum(n);
+    } else {
+        for (int b = threadIdx.x; b < B; b += 64) {
+            const float v = row_nll[b];
+            if (v == v) { tot += v; n += 1.f; }
+        }
+        tot = wave_sum(tot);
+        n = wave_sum(n);
     }
-    tot = wave_sum(tot);
-    n = wave_sum(n);
     if (threadIdx.x == 0) {
         loss[0] = tot / n;   // 0/0 = NaN when every target is ignored, as torch
         if (loss_hist) loss_hist[hist_idx ? *hist_idx : 0] = tot / n;    // per-batch losses of an epoch, no host round trip
@@ -798,15 +886,20 @@ SLNLP_ZKERNEL(lsm_bwd_kernel, 256, lsm_bwd_body)
 
 int lsm_nll(const float* logits, int64_t ld_logits, const int64_t* y, int B, int V, int64_t ignore_index, float* logp,
             float* loss, float* dlogits, int64_t ld_dlogits, float* row_scratch, hipStream_t st, hipStream_t loss_st,
-            float* logp2, const int* logp2_row, float* loss_hist, const int* hist_idx) {
+            float* logp2, const int* logp2_row, float* loss_hist, const int* hist_idx, LossOpts lo) {
     SLNLP_CHECK_ARG(logits && y && logp && loss && row_scratch, "lsm_nll: null pointer");
     SLNLP_CHECK_ARG(B > 0 && B <= LOSS_MAXB && V > 0 && ld_logits >= V, "lsm_nll: bad shape B=%d V=%d", B, V);
     SLNLP_CHECK_ARG(!dlogits || ld_dlogits >= V, "lsm_nll: ld_dlogits too small");
+    SLNLP_CHECK_ARG(lo.label_smoothing >= 0.f && lo.label_smoothing <= 1.f && (lo.reduction == 0 || lo.reduction == 1),
+                    "lsm_nll: label_smoothing %g outside [0, 1] or reduction %d not 0 (mean) / 1 (sum)", lo.label_smoothing,
+                    lo.reduction);
+    const int general = (lo.class_weight || lo.label_smoothing != 0.f || lo.reduction) ? 1 : 0;
     SLNLP_TRY(zlaunch(lsm_nll_kernel, dim3(B), 64, 0, st, "lsm_nll",
                       logits, (long)ld_logits, (const long*)y, B, V, (long)ignore_index, logp, row_scratch, dlogits, (long)ld_dlogits,
-                      logp2, logp2_row));
+                      logp2, logp2_row, lo.class_weight, lo.label_smoothing, lo.reduction));
     SLNLP_TRY(zlaunch(lsm_loss_reduce_kernel, dim3(1), 64, 0, loss_st ? loss_st : st, "lsm_loss_reduce",
-                      row_scratch, B, loss, loss_hist, hist_idx));
+                      row_scratch, B, loss, loss_hist, hist_idx, (const long*)y, V, (long)ignore_index, lo.class_weight, general,
+                      lo.reduction));
     return 0;
 }
 
@@ -821,7 +914,11 @@ int lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dlogits,
 // clip_grad_norm_(max_norm) + torch.optim.SGD(momentum) over one flat arena.
 constexpr int OPT_BLOCKS = 1024;
 
-__device__ __forceinline__ void sumsq_body(const float* __restrict__ g, long n4, float* __restrict__ partials) {
+__device__ __forceinline__ void sumsq_body(const float* __restrict__ g, long n4, float* __restrict__ partials,
+                                           float* __restrict__ sgd_steps) {
+    // sgd_steps (optional): the SGD step count, advanced HERE -- before the update launch, which only reads it (every block
+    // of sgd_kernel sees the same value: 1 on the first step)
+    if (sgd_steps && blockIdx.x == 0 && threadIdx.x == 0) sgd_steps[0] += 1.f;
     __shared__ float red[4];
     float s = 0.f;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)OPT_BLOCKS * 256) {
@@ -839,7 +936,9 @@ __device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __r
                                                   long n4, const float* __restrict__ lr_dev, float momentum,
                                                   float max_norm, const float* __restrict__ partials,
                                                   float* __restrict__ norm_out, unsigned long long* __restrict__ rng,
-                                                  PlaneOut wp, long wp_begin4, long wp_end4) {
+                                                  PlaneOut wp, long wp_begin4, long wp_end4, float dampening, float weight_decay,
+                                                  int nesterov, const float* __restrict__ sgd_steps, long skip_begin4,
+                                                  long skip_end4) {
     // wp (optional): the updated weights also leave as bf16 hi / lo planes (same offsets as the arena) -- the operand
     // form the plane GEMMs of the NEXT step stage by LDS-DMA -- instead of a separate pass that re-reads the arena.
     // Only float4 indices in [wp_begin4, wp_end4) are written: the plan passes the range of the weights that FEED plane GEMMs
@@ -855,6 +954,39 @@ __device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __r
     float coef = 1.f;
     if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
     const float lr = lr_dev[0];
+    if (dampening != 0.f || weight_decay != 0.f || nesterov) {
+        // torch/optim/sgd.py _single_tensor_sgd: d = g' + wd p; buf = d on the first step, else m buf + (1 - dampening) d;
+        // d = d + m buf (nesterov) or buf; p -= lr d.  Float indices [skip_begin4, skip_end4) are a parameter torch never
+        // steps (its grad is None): left untouched.  Kept apart from the plain loop below, whose arithmetic stays as it was.
+        const bool first = sgd_steps[0] == 1.f;
+        const float damp = first ? 0.f : 1.f - dampening, keep = first ? 0.f : momentum;
+        for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            float4 w = reinterpret_cast<float4*>(p)[i];
+            if (i < skip_begin4 || i >= skip_end4) {
+                const float4 gv = reinterpret_cast<const float4*>(g)[i];
+                float4 b = reinterpret_cast<float4*>(buf)[i];
+                float ge[4] = {gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef};
+                float be[4] = {b.x, b.y, b.z, b.w}, we[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float d = ge[e] + weight_decay * we[e];
+                    be[e] = first ? d : keep * be[e] + damp * d;
+                    d = nesterov ? d + momentum * be[e] : be[e];
+                    we[e] -= lr * d;
+                }
+                b = make_float4(be[0], be[1], be[2], be[3]);
+                w = make_float4(we[0], we[1], we[2], we[3]);
+                reinterpret_cast<float4*>(buf)[i] = b;
+                reinterpret_cast<float4*>(p)[i] = w;
+            }
+            if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, w);
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (norm_out) norm_out[0] = norm;
+            if (rng) rng[1] += 1ull;
+        }
+        return;
+    }
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 gv = reinterpret_cast<const float4*>(g)[i];
         float4 b = reinterpret_cast<float4*>(buf)[i];
@@ -873,20 +1005,37 @@ __device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __r
 }
 SLNLP_ZKERNEL(sgd_kernel, 256, sgd_body)
 
+// skip range [skip_begin, skip_end) in floats, 16-byte aligned (multiples of 4); empty when skip_end <= skip_begin
+static int check_skip(const char* what, int64_t n, int64_t skip_begin, int64_t skip_end) {
+    SLNLP_CHECK_ARG(skip_end <= skip_begin || (skip_begin >= 0 && skip_end <= n && skip_begin % 4 == 0 && skip_end % 4 == 0),
+                    "%s: skip range [%ld, %ld) must lie in [0, %ld) on multiples of 4", what, (long)skip_begin, (long)skip_end, (long)n);
+    return 0;
+}
+
 int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
                   float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
-                  hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end) {
+                  hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end, SgdOpts so) {
     SLNLP_CHECK_ARG(params && grads && momentum_buf && lr_dev && partials, "clip_sgd_step: null pointer");
     SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_sgd_step: n=%ld must be a positive multiple of 4", (long)n);
     SLNLP_CHECK_ARG(((uintptr_t)params & 15) == 0 && ((uintptr_t)grads & 15) == 0 && ((uintptr_t)momentum_buf & 15) == 0,
                     "clip_sgd_step: arenas must be 16-byte aligned");
+    // torch's argument rules (torch.optim.SGD.__init__); without momentum torch keeps no buffer, so dampening is moot
+    SLNLP_CHECK_ARG(so.dampening >= 0.f && so.weight_decay >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
+                    "clip_sgd_step: bad dampening %g / weight_decay %g / nesterov (needs momentum > 0 and dampening 0)",
+                    so.dampening, so.weight_decay);
+    SLNLP_TRY(check_skip("clip_sgd_step", n, so.skip_begin, so.skip_end));
+    const float damp = momentum != 0.f ? so.dampening : 0.f;
+    const bool general = damp != 0.f || so.weight_decay != 0.f || so.nesterov;
+    SLNLP_CHECK_ARG(!general || so.steps, "clip_sgd_step: dampening / weight decay / nesterov need the step counter");
     SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq",
-                      grads, (long)(n / 4), partials));
+                      grads, (long)(n / 4), partials, so.steps));
     int grid = ceil_div(n / 4, 256);
     if (grid > 2048) grid = 2048;
+    const long sb4 = so.skip_end > so.skip_begin ? (long)(so.skip_begin / 4) : 0, se4 = so.skip_end > so.skip_begin ? (long)(so.skip_end / 4) : 0;
     SLNLP_TRY(zlaunch(sgd_kernel, dim3(grid), 256, 0, st, "sgd",
                       params, grads, momentum_buf, (long)(n / 4), lr_dev, momentum, max_norm, partials, norm_out, rng, wp,
-                      (long)(wp_begin / 4), (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4)));
+                      (long)(wp_begin / 4), (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4), damp, so.weight_decay,
+                      so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4));
     return 0;
 }
 
@@ -900,7 +1049,9 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
                                           float beta2, float eps, float weight_decay, float max_norm,
                                           const float* __restrict__ partials, float* __restrict__ norm_out,
                                           unsigned long long* __restrict__ rng, float* __restrict__ step_f, PlaneOut wp,
-                                          long wp_begin4, long wp_end4) {
+                                          long wp_begin4, long wp_end4, int decoupled, long skip_begin4, long skip_end4) {
+    // decoupled (torch.optim.AdamW): p *= 1 - lr wd first, then the Adam update with no L2 term; float indices
+    // [skip_begin4, skip_end4) (a parameter torch never steps) are left untouched.  Plain Adam ignores the skip range.
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < OPT_BLOCKS; i += 256) s += partials[i];
@@ -914,14 +1065,20 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
     const float t = step_f[0] + 1.f;                       // every block reads the OLD count (adam_count_kernel advances it afterwards)
     const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(beta2, t);
     const float step_size = lr / bc1, rsq_bc2 = 1.f / sqrtf(bc2);
+    const float l2 = decoupled ? 0.f : weight_decay, decay = 1.f - lr * weight_decay;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        if (decoupled && i >= skip_begin4 && i < skip_end4) {
+            if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, reinterpret_cast<const float4*>(p)[i]);
+            continue;
+        }
         const float4 gv = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i], w = reinterpret_cast<float4*>(p)[i];
         float ge[4] = {gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef};
         float me[4] = {mm.x, mm.y, mm.z, mm.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w}, we[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if (weight_decay != 0.f) ge[e] += weight_decay * we[e];
+            if (decoupled) we[e] *= decay;
+            if (l2 != 0.f) ge[e] += l2 * we[e];
             me[e] += (1.f - beta1) * (ge[e] - me[e]);
             ve[e] = beta2 * ve[e] + (1.f - beta2) * ge[e] * ge[e];
             we[e] -= step_size * (me[e] / (sqrtf(ve[e]) * rsq_bc2 + eps));
@@ -945,19 +1102,70 @@ SLNLP_ZKERNEL(adam_count_kernel, 64, adam_count_body)
 
 int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
                    float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
-                   unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end) {
+                   unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end,
+                   AdamOpts ao) {
     SLNLP_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && lr_dev && partials && step_f, "clip_adam_step: null pointer");
+    SLNLP_TRY(check_skip("clip_adam_step", n, ao.skip_begin, ao.skip_end));
+    SLNLP_CHECK_ARG(weight_decay >= 0.f, "clip_adam_step: weight_decay %g < 0", weight_decay);
     SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_adam_step: n=%ld must be a positive multiple of 4", (long)n);
     SLNLP_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
                     "clip_adam_step: arenas must be 16-byte aligned");
     SLNLP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "clip_adam_step: bad betas / eps");
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials));
+    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials, (float*)nullptr));
     int grid = ceil_div(n / 4, 256);
     if (grid > 2048) grid = 2048;
+    const long sb4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_begin / 4) : 0, se4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_end / 4) : 0;
     SLNLP_TRY(zlaunch(adam_kernel, dim3(grid), 256, 0, st, "adam", params, grads, exp_avg, exp_avg_sq, (long)(n / 4), lr_dev, beta1, beta2,
                       eps, weight_decay, max_norm, partials, norm_out, rng, step_f, wp, (long)(wp_begin / 4),
-                      (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4)));
+                      (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4), ao.decoupled ? 1 : 0, sb4, se4));
     SLNLP_TRY(zlaunch(adam_count_kernel, dim3(1), 64, 0, st, "adam_count", step_f));
+    return 0;
+}
+
+// ============================================================ plan settings
+TrainOpts::~TrainOpts() {
+    if (class_weight) (void)hipFree(class_weight);
+}
+
+int TrainOpts::set_criterion(int V, const float* cw, float eps, int red, hipStream_t st, bool* changed) {
+    SLNLP_CHECK_ARG(V > 0 && eps >= 0.f && eps <= 1.f && (red == 0 || red == 1),
+                    "set_criterion: label_smoothing %g outside [0, 1] or reduction %d not 0 (mean) / 1 (sum)", eps, red);
+    std::vector<float> host;
+    if (cw) host.assign(cw, cw + V);   // host memory
+    *changed = host != class_weight_host || eps != label_smoothing || red != reduction;
+    if (!*changed) return 0;
+    if (cw && !class_weight && hipMalloc(&class_weight, (size_t)V * sizeof(float)) != hipSuccess) {
+        class_weight = nullptr;
+        set_error("set_criterion: allocating the class weights failed");
+        return SLNLP_ERR_LAUNCH;
+    }
+    class_weight_host.swap(host);
+    // from the plan's own host copy (alive until the next change), ordered on the fit's stream before its next step
+    if (cw && hipMemcpyAsync(class_weight, class_weight_host.data(), (size_t)V * sizeof(float), hipMemcpyHostToDevice, st) !=
+                  hipSuccess) {
+        set_error("set_criterion: copying the class weights failed");
+        return SLNLP_ERR_LAUNCH;
+    }
+    if (!cw && class_weight) {
+        (void)hipFree(class_weight);
+        class_weight = nullptr;
+    }
+    label_smoothing = eps;
+    reduction = red;
+    ++gen;
+    return 0;
+}
+
+int TrainOpts::set_update(int k, float damp, float wd, int nest, bool* changed) {
+    SLNLP_CHECK_ARG(k == SLNLP_UPDATE_SGD || k == SLNLP_UPDATE_ADAM || k == SLNLP_UPDATE_ADAMW, "set_update: unknown kind %d", k);
+    SLNLP_CHECK_ARG(damp >= 0.f && wd >= 0.f, "set_update: dampening %g / weight_decay %g must be >= 0", damp, wd);
+    SLNLP_CHECK_ARG(!nest || damp == 0.f, "set_update: Nesterov momentum requires zero dampening");
+    SLNLP_CHECK_ARG(k == SLNLP_UPDATE_SGD || (damp == 0.f && !nest), "set_update: dampening / nesterov are SGD's");
+    nest = nest ? 1 : 0;
+    *changed = k != kind || damp != dampening || wd != weight_decay || nest != nesterov;
+    if (!*changed) return 0;
+    kind = k; dampening = damp; weight_decay = wd; nesterov = nest;
+    ++gen;
     return 0;
 }
 
@@ -1004,6 +1212,13 @@ int slnlp_lsm_nll(const float* logits, int64_t ld_logits, const int64_t* y, int 
     return slnlp::lsm_nll(logits, ld_logits, y, B, V, ignore_index, logp, loss, dlogits, ld_dlogits, row_scratch,
                           (hipStream_t)stream, nullptr);
 }
+int slnlp_lsm_nll_ex(const float* logits, int64_t ld_logits, const int64_t* y, int B, int V, int64_t ignore_index,
+                     const float* class_weight, float label_smoothing, int reduction, float* logp, float* loss, float* dlogits,
+                     int64_t ld_dlogits, float* row_scratch, void* stream) {
+    return slnlp::lsm_nll(logits, ld_logits, y, B, V, ignore_index, logp, loss, dlogits, ld_dlogits, row_scratch,
+                          (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          slnlp::LossOpts{class_weight, label_smoothing, reduction});
+}
 int slnlp_lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dlogits, int64_t ld_dlogits,
                   void* stream) {
     return slnlp::lsm_bwd(logp, dlogp, B, V, dlogits, ld_dlogits, (hipStream_t)stream);
@@ -1013,6 +1228,20 @@ int slnlp_clip_sgd_step(float* params, const float* grads, float* momentum_buf, 
                         void* stream) {
     return slnlp::clip_sgd_step(params, grads, momentum_buf, n, lr_dev, momentum, max_norm, partials, norm_out, rng,
                                 (hipStream_t)stream);
+}
+int slnlp_clip_sgd_step_ex(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
+                           float momentum, float dampening, float weight_decay, int nesterov, float max_norm, float* partials,
+                           float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
+    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
+                                (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
+                                slnlp::SgdOpts{dampening, weight_decay, nesterov, step_count, skip_begin, skip_end});
+}
+int slnlp_clip_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
+                          float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
+                          float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
+    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
+                                 norm_out, nullptr, step_count, (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
+                                 slnlp::AdamOpts{1, skip_begin, skip_end});
 }
 int slnlp_clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
                          float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,

@@ -42,6 +42,7 @@ int rnn_ls_record(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, const 
 void rnn_ls_outputs(slnlp_rnn_plan* pl, float* logp, float* loss, const int* dyn);
 void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train);
 const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl);
+unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl);
 
 struct GatherArgs {
     const int64_t* const* X;     // [K] dataset pointers (device table)
@@ -102,6 +103,7 @@ struct LsFit {
                   const LsAdam* adam, float* exp_avg_sq, hipStream_t st);   // the ordinary step code, run under a Recorder
     void (*outputs)(void* plan, float* logp, float* loss, const int* dyn);
     void (*replayed)(void* plan, int B, int train);         // host bookkeeping after the step's launches were issued
+    unsigned (*opts_gen)(void* plan);                       // generation of the plan's criterion / update settings (TrainOpts)
 };
 
 struct LockstepGroup {
@@ -126,6 +128,9 @@ struct LockstepGroup {
         std::vector<float*> logp, loss;             // per-fit output buffers (device, caller-owned)
     } slot[LS_SLOTS];
     std::map<std::tuple<int, int, int>, Program> programs;   // (slot, B, train)
+    // each fit's settings generation when the programs were recorded: the criterion and update settings ride every fit's
+    // argument packs, so a fit whose settings changed since makes every program stale
+    std::vector<unsigned> rec_gen;
     // the optimizer constants a train program baked into its recorded update launches: every later call must pass the same
     bool have_opt = false;
     float opt_momentum = 0.f, opt_max_norm = 0.f;
@@ -393,6 +398,18 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
                         "(%g / %g); set new data (which drops the programs) or use another group",
                         momentum, max_norm, ls->opt_momentum, ls->opt_max_norm);
     }
+    std::vector<unsigned> gen(ls->K);
+    for (int f = 0; f < ls->K; ++f) gen[f] = ls->fits[f].opts_gen(ls->fits[f].plan);
+    if (gen != ls->rec_gen) {
+        // no program is left to read the table space: hand it back and put the slots' pointer tables at its start again
+        // (as set_data does), ordered on `st` behind every launch that read the old tables
+        ls->programs.clear();
+        ls->have_opt = false;
+        ls->rec_gen = gen;
+        ls->ws_used = ls->ws_mark;
+        for (int k = 0; k < LS_SLOTS; ++k)
+            if (ls->slot[k].set) SLNLP_TRY(upload_slot_tables(ls, ls->slot[k], st));
+    }
     for (LsFit& f : ls->fits) SLNLP_TRY(f.prepare(f.plan, B, st));
     const auto key = std::make_tuple(slot, B, train ? 1 : 0);
     auto it = ls->programs.find(key);
@@ -473,7 +490,9 @@ static int tf_record(void* p, const int64_t* X, const int64_t* y, const int64_t*
     SLNLP_TRY(pl->forward_impl(X, y, B, train, nullptr, st));
     if (!train) return 0;
     SLNLP_TRY(slnlp_tf_backward(pl, st));
-    if (adam) return slnlp_tf_optim_adam(pl, exp_avg_sq, adam->beta1, adam->beta2, adam->eps, adam->weight_decay, max_norm, st);
+    if (adam)
+        return slnlp_tf_optim_adam(pl, exp_avg_sq, adam->beta1, adam->beta2, adam->eps, pl->opts.adam_weight_decay(adam->weight_decay),
+                                   max_norm, st);
     return slnlp_tf_optim(pl, momentum, max_norm, st);
 }
 static void tf_outputs(void* p, float* logp, float* loss, const int* dyn) {
@@ -495,6 +514,8 @@ static int rnn_record(void* p, const int64_t* X, const int64_t* y, const int64_t
 }
 static void rnn_outputs(void* p, float* logp, float* loss, const int* dyn) { rnn_ls_outputs((slnlp_rnn_plan*)p, logp, loss, dyn); }
 static void rnn_replayed(void* p, int B, int train) { rnn_ls_replayed((slnlp_rnn_plan*)p, B, train); }
+static unsigned rnn_opts_gen(void* p) { return rnn_ls_opts_gen((slnlp_rnn_plan*)p); }
+static unsigned tf_opts_gen(void* p) { return ((slnlp_tf_plan*)p)->opts.gen; }
 
 extern "C" {
 
@@ -531,7 +552,7 @@ int slnlp_tf_lockstep_create(slnlp_tf_plan** plans, int K, void* workspace, int6
         for (int g = 0; g < f; ++g) SLNLP_CHECK_ARG(plans[g] != plans[f], "lockstep_create: plan %d listed twice", f);
     }
     slnlp_tf_lockstep* ls = new slnlp_tf_lockstep();
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed});
+    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed, tf_opts_gen});
     const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;
@@ -594,7 +615,7 @@ int slnlp_rnn_lockstep_create(slnlp_rnn_plan** plans, int K, void* workspace, in
     }
     slnlp_rnn_lockstep* ls = new slnlp_rnn_lockstep();
     ls->has_len = true;
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed});
+    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed, rnn_opts_gen});
     const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;

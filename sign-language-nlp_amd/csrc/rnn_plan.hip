@@ -262,6 +262,7 @@ struct slnlp_rnn_plan {
     float last_p = 0.f;
     const int64_t *last_X = nullptr, *last_y = nullptr, *last_len = nullptr;
     std::map<int, hipGraphExec_t> graphs;
+    TrainOpts opts;           // slnlp_rnn_set_criterion / slnlp_rnn_set_update
     bool use_planes = false;  // E, Hd multiples of 64: the M = S*B GEMMs run on pre-split bf16 planes (gemm_planes.hip)
     int planes_B = -1;        // batch size the activation planes' zero padding is valid for
     int destroy_sync = 1;     // slnlp_rnn_set_destroy_sync: wait for the device before the plan goes away (launch.hpp)
@@ -556,7 +557,7 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
     SLNLP_TRY(pl->lin(x_prev, Hd, B, Hd, pl->P(L.gen_w), Hd, c.Vt, nullptr, w.logits, Vp, 0, nullptr, st));
     SLNLP_TRY(lsm_nll(w.logits, Vp, y, B, c.Vt, c.pad_tgt, w.logp, pl->buf.scalars, train ? w.dlogits : nullptr, Vp,
                       w.row_nll, st, nullptr, logp_out ? nullptr : pl->ls_logp, logp_out ? nullptr : pl->ls_dyn,
-                      logp_out ? nullptr : pl->ls_loss, (!logp_out && pl->ls_dyn) ? pl->ls_dyn + 1 : nullptr));
+                      logp_out ? nullptr : pl->ls_loss, (!logp_out && pl->ls_dyn) ? pl->ls_dyn + 1 : nullptr, pl->opts.loss()));
     if (logp_out &&
         hipMemcpyAsync(logp_out, w.logp, (size_t)B * c.Vt * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
         set_error("rnn_forward: copy of log-probs failed");
@@ -758,12 +759,20 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
     return 0;
 }
 
+// end of the decoder's pre_output_layer in the arena, rounded up to 16 bytes (the padding after it is never written): the
+// range the weight-decaying updates leave alone -- torch skips the parameter, its grad stays None (rnn_plan.hip header)
+static int64_t rnn_pre_out_end(const slnlp_rnn_plan* pl) {
+    const int64_t Hd = pl->cfg.Hd, E = pl->cfg.E;
+    return (pl->L.pre_out + Hd * (3 * Hd + E) + 3) / 4 * 4;
+}
+
 int slnlp_rnn_optim(slnlp_rnn_plan* pl, float momentum, float max_norm, void* stream) {
     SLNLP_CHECK_ARG(pl, "rnn_optim: null plan");
     StepScope scope((hipStream_t)stream);
     SLNLP_TRY(scope.rc);
     return clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
-                         pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream);
+                         pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream, PlaneOut{}, 0, -1,
+                         pl->opts.sgd(pl->buf.scalars + 3, pl->L.pre_out, rnn_pre_out_end(pl)));
 }
 
 // clip_grad_norm_ + torch.optim.Adam on the arena (any torch optimizer is reachable in the reference through
@@ -776,7 +785,30 @@ int slnlp_rnn_optim_adam(slnlp_rnn_plan* pl, float* exp_avg_sq, float beta1, flo
     SLNLP_TRY(scope.rc);
     return clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
                           weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
-                          (hipStream_t)stream);
+                          (hipStream_t)stream, PlaneOut{}, 0, -1, pl->opts.adam(pl->L.pre_out, rnn_pre_out_end(pl)));
+}
+
+static void rnn_drop_graphs(slnlp_rnn_plan* pl) {
+    if (pl->graphs.empty()) return;
+    (void)hipDeviceSynchronize();   // an exec may still be running
+    for (auto& kv : pl->graphs) (void)hipGraphExecDestroy(kv.second);
+    pl->graphs.clear();
+}
+
+int slnlp_rnn_set_criterion(slnlp_rnn_plan* pl, const float* class_weight, float label_smoothing, int reduction, void* stream) {
+    SLNLP_CHECK_ARG(pl, "rnn_set_criterion: null plan");
+    bool changed = false;
+    SLNLP_TRY(pl->opts.set_criterion(pl->cfg.Vt, class_weight, label_smoothing, reduction, (hipStream_t)stream, &changed));
+    if (changed) rnn_drop_graphs(pl);
+    return 0;
+}
+
+int slnlp_rnn_set_update(slnlp_rnn_plan* pl, int kind, float dampening, float weight_decay, int nesterov) {
+    SLNLP_CHECK_ARG(pl, "rnn_set_update: null plan");
+    bool changed = false;
+    SLNLP_TRY(pl->opts.set_update(kind, dampening, weight_decay, nesterov, &changed));
+    if (changed) rnn_drop_graphs(pl);
+    return 0;
 }
 
 int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* pl, int on) {
@@ -880,7 +912,9 @@ int rnn_ls_record(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, const 
     SLNLP_TRY(slnlp_rnn_forward(pl, X, y, len, B, train, nullptr, st));
     if (!train) return 0;
     SLNLP_TRY(slnlp_rnn_backward(pl, st));
-    if (adam) return slnlp_rnn_optim_adam(pl, exp_avg_sq, adam->beta1, adam->beta2, adam->eps, adam->weight_decay, max_norm, st);
+    if (adam)
+        return slnlp_rnn_optim_adam(pl, exp_avg_sq, adam->beta1, adam->beta2, adam->eps, pl->opts.adam_weight_decay(adam->weight_decay),
+                                    max_norm, st);
     return slnlp_rnn_optim(pl, momentum, max_norm, st);
 }
 void rnn_ls_outputs(slnlp_rnn_plan* pl, float* logp, float* loss, const int* dyn) {
@@ -891,4 +925,5 @@ void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train) {
     pl->last_p = train ? pl->cfg.dropout : 0.f;
 }
 const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl) { return &pl->cfg; }
+unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl) { return pl->opts.gen; }
 }  // namespace slnlp

@@ -269,7 +269,7 @@ int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int t
     // in the epoch buffer at the batch's row offset and the loss in the epoch's loss history
     SLNLP_TRY(lsm_nll(w.logits, Vp, y, B, c.Vt, c.pad_tgt, w.logp, pl->buf.scalars, train ? w.dlogits : nullptr, Vp,
                       w.row_nll, st, nullptr, logp_out ? logp_out : ls_logp, logp_out ? nullptr : ls_dyn,
-                      logp_out ? nullptr : ls_loss, (!logp_out && ls_dyn) ? ls_dyn + 1 : nullptr));
+                      logp_out ? nullptr : ls_loss, (!logp_out && ls_dyn) ? ls_dyn + 1 : nullptr, pl->opts.loss()));
     return 0;
 }
 
@@ -460,7 +460,8 @@ int slnlp_tf_optim(slnlp_tf_plan* pl, float momentum, float max_norm, void* stre
     SLNLP_TRY(scope.rc);
     SLNLP_TRY(clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
                             pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
-                            pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end()));
+                            pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
+                            pl->opts.sgd(pl->buf.scalars + 3, 0, 0)));
     if (!recording()) pl->params_stepped();      // (a lockstep replay does this per step itself)
     return 0;
 }
@@ -474,7 +475,8 @@ int slnlp_tf_optim_adam(slnlp_tf_plan* pl, float* exp_avg_sq, float beta1, float
     SLNLP_TRY(scope.rc);
     SLNLP_TRY(clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
                              weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
-                             (hipStream_t)stream, pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end()));
+                             (hipStream_t)stream, pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
+                             pl->opts.adam(0, 0)));
     if (!recording()) pl->params_stepped();
     return 0;
 }
@@ -482,6 +484,30 @@ int slnlp_tf_optim_adam(slnlp_tf_plan* pl, float* exp_avg_sq, float beta1, float
 int slnlp_tf_set_destroy_sync(slnlp_tf_plan* pl, int on) {
     SLNLP_CHECK_ARG(pl, "tf_set_destroy_sync: null plan");
     pl->destroy_sync = on ? 1 : 0;
+    return 0;
+}
+
+// A settings change: the captured graphs baked the old settings into their launches -- drop them (the caller re-captures)
+static void tf_drop_graphs(slnlp_tf_plan* pl) {
+    if (pl->graphs.empty()) return;
+    (void)hipDeviceSynchronize();   // an exec may still be running
+    for (auto& kv : pl->graphs) (void)hipGraphExecDestroy(kv.second);
+    pl->graphs.clear();
+}
+
+int slnlp_tf_set_criterion(slnlp_tf_plan* pl, const float* class_weight, float label_smoothing, int reduction, void* stream) {
+    SLNLP_CHECK_ARG(pl, "tf_set_criterion: null plan");
+    bool changed = false;
+    SLNLP_TRY(pl->opts.set_criterion(pl->cfg.Vt, class_weight, label_smoothing, reduction, (hipStream_t)stream, &changed));
+    if (changed) tf_drop_graphs(pl);
+    return 0;
+}
+
+int slnlp_tf_set_update(slnlp_tf_plan* pl, int kind, float dampening, float weight_decay, int nesterov) {
+    SLNLP_CHECK_ARG(pl, "tf_set_update: null plan");
+    bool changed = false;
+    SLNLP_TRY(pl->opts.set_update(kind, dampening, weight_decay, nesterov, &changed));
+    if (changed) tf_drop_graphs(pl);
     return 0;
 }
 

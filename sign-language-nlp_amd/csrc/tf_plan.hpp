@@ -359,7 +359,8 @@ struct slnlp_tf_plan {
     float last_p = 0.f;   // dropout used by the last forward (0 in eval)
     const int64_t* last_X = nullptr;
     const int64_t* last_y = nullptr;
-    std::map<int, hipGraphExec_t> graphs;   // one captured train step per batch size, kept until destroy
+    std::map<int, hipGraphExec_t> graphs;   // one captured train step per batch size, kept until destroy (or a settings change)
+    TrainOpts opts;                         // slnlp_tf_set_criterion / slnlp_tf_set_update
     int nbE = 0, nbD = 0;  // (dgamma, dbeta) chunk counts of the FULL batch (fixed: the reduce table is static)
     int destroy_sync = 1;  // slnlp_tf_set_destroy_sync: wait for the device before the plan goes away (launch.hpp)
     // Lockstep (lockstep.hip): where this fit's per-step outputs go while it advances as one of K fits -- an epoch-long

@@ -181,12 +181,33 @@ class ArenaModule(nn.Module):
         if eng is None or eng.cfg.B < B:
             old = eng
             eng = self._make_engine(max(B, old.cfg.B if old is not None else 0), S, self._shared_state())
+            self._apply_train_options(eng)
             self._engines[S] = eng
         return eng
 
     def engine(self, B, S):
         """Public handle for the fused-step estimator (slnlp.net)."""
         return self._engine_for(B, S)
+
+    def set_train_options(self, criterion=None, update=None):
+        """Criterion and update settings of the fused step, for every plan of the module (now and created later):
+        ``criterion`` {weight, label_smoothing, reduction}, ``update`` {kind, dampening, weight_decay, nesterov} -- the
+        keywords of the engines' ``set_criterion`` / ``set_update``.  None leaves that part as it is."""
+        opts = dict(getattr(self, "_train_opts", None) or {})
+        if criterion is not None:
+            opts["criterion"] = dict(criterion)
+        if update is not None:
+            opts["update"] = dict(update)
+        self._train_opts = opts
+        for eng in self._engines.values():
+            self._apply_train_options(eng)
+
+    def _apply_train_options(self, eng):
+        opts = getattr(self, "_train_opts", None) or {}
+        if "criterion" in opts:
+            eng.set_criterion(**opts["criterion"])
+        if "update" in opts:
+            eng.set_update(**opts["update"])
 
     def _run(self, inputs):
         if self.training and torch.is_grad_enabled():

@@ -111,9 +111,12 @@ SIGNATURES = {
     "slnlp_layernorm_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32), vp]),
     "slnlp_ln_param_reduce": (i32, [vp, i32, i32, vp]),
     "slnlp_lsm_nll": (i32, [vp, i64, vp, i32, i32, i64, vp, vp, vp, i64, vp, vp]),
+    "slnlp_lsm_nll_ex": (i32, [vp, i64, vp, i32, i32, i64, vp, f32, i32, vp, vp, vp, i64, vp, vp]),
     "slnlp_lsm_bwd": (i32, [vp, vp, i32, i32, vp, i64, vp]),
     "slnlp_clip_sgd_step": (i32, [vp, vp, vp, i64, vp, f32, f32, vp, vp, vp, vp]),
     "slnlp_clip_adam_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    "slnlp_clip_sgd_step_ex": (i32, [vp, vp, vp, i64, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
+    "slnlp_clip_adamw_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_rnn_cell_fwd": (i32, [i32, C.POINTER(RnnCellDir), i32, i32, i32, vp, f32, i64, f32, i32, vp, vp]),
     "slnlp_rnn_layer_fwd": (i32, [i32, C.POINTER(RnnLayerDir), i32, i32, i32, i32, vp, f32, i64, f32, i32, vp, i32, vp,
@@ -136,6 +139,8 @@ SIGNATURES = {
     "slnlp_rnn_optim": (i32, [vp, f32, f32, vp]),
     "slnlp_rnn_optim_adam": (i32, [vp, vp, f32, f32, f32, f32, f32, vp]),
     "slnlp_rnn_set_destroy_sync": (i32, [vp, i32]),
+    "slnlp_rnn_set_criterion": (i32, [vp, vp, f32, i32, vp]),
+    "slnlp_rnn_set_update": (i32, [vp, i32, f32, f32, i32]),
     "slnlp_rnn_train_step": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp]),
     "slnlp_rnn_graph_capture_train": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp]),
     "slnlp_rnn_graph_launch": (i32, [vp, i32, vp]),
@@ -162,6 +167,8 @@ SIGNATURES = {
     "slnlp_tf_optim_adam": (i32, [vp, vp, f32, f32, f32, f32, f32, vp]),
     "slnlp_tf_debug_layout": (i32, [vp, C.c_char_p, i64]),
     "slnlp_tf_set_destroy_sync": (i32, [vp, i32]),
+    "slnlp_tf_set_criterion": (i32, [vp, vp, f32, i32, vp]),
+    "slnlp_tf_set_update": (i32, [vp, i32, f32, f32, i32]),
     "slnlp_set_stream_policy": (i32, [i32]),
     "slnlp_set_thread_stream_policy": (i32, [i32]),
     "slnlp_set_backward_passes": (i32, [i32, i32]),
@@ -222,6 +229,10 @@ def require_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError("slnlp: no MI355X visible -- the HIP path is the only compute path "
                            "(there is deliberately no CPU fallback)")
+
+
+REDUCTIONS = {"mean": 0, "sum": 1}             # CrossEntropyLoss reductions the fused criterion implements
+UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 
 
 def ptr(t):

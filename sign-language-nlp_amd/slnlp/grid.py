@@ -80,7 +80,10 @@ def build_tasks(param_grid, y, cv, seq_len=48, defaults=None):
     return cands, folds, tasks, order
 
 
-SHAPE_KEYS_EXCLUDED = ("lr", "module__dropout")
+# per-fit settings that change no launch sequence: candidates that differ only in these share a lockstep unit (the criterion
+# settings, SGD's settings and the Adam / AdamW weight decay ride each fit's own argument packs, csrc/lockstep.hip)
+SHAPE_KEYS_EXCLUDED = ("lr", "module__dropout", "criterion__label_smoothing", "optimizer__weight_decay", "optimizer__dampening",
+                       "optimizer__nesterov")
 
 
 def estimate_fit_bytes(params, seq_len, defaults=None, lockstep=1):

@@ -128,13 +128,15 @@ LOCKSTEP_MODULES = ("Transformer", "EncoderDecoderLSTMAttn", "EncoderDecoderGRUA
 def lockstep_supported(net):
     """A fused update (SGD-momentum or Adam) + CrossEntropyLoss on one of the path's three modules: what the lockstep launch
     sequences implement."""
-    return getattr(net, "_fused_kind", None) in ("sgd", "adam") and type(net.module_).__name__ in LOCKSTEP_MODULES
+    return getattr(net, "_fused_kind", None) in ("sgd", "adam", "adamw") and type(net.module_).__name__ in LOCKSTEP_MODULES
 
 
 def _adam_key(net):
-    ok = net._opt_kwargs
-    return (net._fused_kind,) + ((tuple(ok.get("betas", (0.9, 0.999))), float(ok.get("eps", 1e-8)), float(ok.get("weight_decay", 0.0)))
-                                 if net._fused_kind == "adam" else ())
+    """What the fits of one group must share about their update: the kind and, for Adam / AdamW, the constants the group passes
+    to every fit (betas, eps).  The weight decay (each plan's own once its kind is Adam / AdamW: slnlp_*_set_update), SGD's
+    dampening / weight decay / nesterov and the criterion settings are each fit's own (they ride its argument packs)."""
+    from .net import adam_args
+    return (net._fused_kind,) + (adam_args(net)[:2] if net._fused_kind in ("adam", "adamw") else ())
 
 
 def fit_lockstep(nets, datasets):
@@ -165,10 +167,10 @@ def _fit_lockstep_gated(nets, datasets):
     with torch.cuda.stream(stream):
         runs = [_FitRun(n, d) for n, d in zip(nets, datasets)]
     r0 = runs[0]
-    assert all(lockstep_supported(n) for n in nets), "lockstep: fused SGD / Adam + CrossEntropyLoss on the model.* modules only"
+    assert all(lockstep_supported(n) for n in nets), "lockstep: fused SGD / Adam / AdamW + CrossEntropyLoss on the model.* modules only"
     assert len({type(n.module_) for n in nets}) == 1, "lockstep: one module class per group"
     assert len({_adam_key(n) for n in nets}) == 1, "lockstep: one optimizer (and one set of Adam constants) per group"
-    adam = _adam_key(nets[0]) if nets[0]._fused_kind == "adam" else None
+    adam = _adam_key(nets[0]) if nets[0]._fused_kind in ("adam", "adamw") else None
     assert all((r.bs, r.momentum, r.max_norm, len(r.tr), (len(r.va) if r.va is not None else 0)) ==
                (r0.bs, r0.momentum, r0.max_norm, len(r0.tr), (len(r0.va) if r0.va is not None else 0)) for r in runs), \
         "lockstep: the fits of a group share batch size, momentum, clipping and split sizes"
@@ -187,7 +189,8 @@ def _fit_lockstep_gated(nets, datasets):
                         log["regroups"] += 1
                 group = LockstepGroup([engines[i] for i in active])
                 if adam is not None:
-                    group.set_adam([nets[i].module_.adam_second_moment() for i in active], adam[1], adam[2], adam[3])
+                    # weight_decay: each plan's own (NeuralNetClassifier.initialize set its update kind), not the group's
+                    group.set_adam([nets[i].module_.adam_second_moment() for i in active], adam[1], adam[2], 0.0)
                 group.set_data(TRAIN, [runs[i].Xtr for i in active], [runs[i].ytr for i in active], r0.bs,
                                [runs[i].Ltr for i in active])
                 if r0.va is not None:

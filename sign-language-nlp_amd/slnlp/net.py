@@ -192,6 +192,60 @@ def _resolve(obj):
     return found
 
 
+def fused_kind(criterion, opt_cls, opt_kwargs, module_cls):
+    """Which fused clip + update kernel replaces the torch optimizer of a fit: "sgd", "adam", "adamw", or None (the fit steps
+    through torch).  ``criterion`` is the constructed criterion; a ``CrossEntropyLoss`` argument the fused criterion does not
+    implement (``reduction="none"``) sends the fit to the torch path -- it is never dropped.  The optimizer arguments are
+    checked by constructing the torch optimizer on a dummy parameter, so bad ones raise torch's own error here."""
+    if not isinstance(criterion, torch.nn.CrossEntropyLoss) or not hasattr(module_cls, "engine"):
+        return None
+    if criterion_options(criterion) is None:
+        return None
+    kinds = {torch.optim.SGD: "sgd", torch.optim.Adam: "adam", torch.optim.AdamW: "adamw"}
+    kind = kinds.get(opt_cls)
+    if kind is None:
+        return None
+    d = optimizer_defaults(opt_cls, opt_kwargs)
+    if d.get("maximize", False) or (kind != "sgd" and d.get("amsgrad", False)):
+        return None
+    return kind
+
+
+def criterion_options(criterion):
+    """The fused criterion's settings of a ``CrossEntropyLoss`` ({weight, label_smoothing, reduction}, the keywords of the
+    engines' ``set_criterion``), or None when it asks for something the fused criterion does not implement.  ``ignore_index``
+    is the vocabulary's pad index on the fused path, as the reference always passes it."""
+    if not isinstance(criterion, torch.nn.CrossEntropyLoss) or criterion.reduction not in ("mean", "sum"):
+        return None
+    w = criterion.weight
+    if w is not None and (w.dim() != 1 or not w.is_floating_point()):
+        return None
+    return {"weight": None if w is None else w.detach().float().cpu(), "label_smoothing": float(criterion.label_smoothing),
+            "reduction": criterion.reduction}
+
+
+def optimizer_defaults(opt_cls, opt_kwargs):
+    """The optimizer's settings with torch's defaults filled in (AdamW's weight_decay is 1e-2, Adam's 0): construct it on a
+    dummy parameter -- which also raises torch's own error for an invalid combination (nesterov with dampening)."""
+    kw = dict(opt_kwargs)
+    kw.setdefault("lr", 0.01)
+    return dict(opt_cls([torch.nn.Parameter(torch.zeros(1))], **kw).defaults)
+
+
+def update_options(kind, defaults):
+    """The engines' ``set_update`` keywords for a fused fit."""
+    if kind == "sgd":
+        return {"kind": "sgd", "dampening": float(defaults.get("dampening", 0.0)), "weight_decay": float(defaults.get("weight_decay", 0.0)),
+                "nesterov": bool(defaults.get("nesterov", False))}
+    return {"kind": kind, "weight_decay": float(defaults.get("weight_decay", 0.0))}     # the fit's own in a lockstep group
+
+
+def adam_args(net):
+    """(betas, eps, weight_decay) of a fused Adam / AdamW fit, torch's defaults filled in."""
+    d = net._opt_defaults
+    return tuple(float(b) for b in d["betas"]), float(d["eps"]), float(d["weight_decay"])
+
+
 class ScoringWrapper:
     """Named sklearn scorer with the extra keyword the reference gives each metric (helper.py:529-554): log-loss is told
     the full label set (a fold may miss classes), the precision / recall / F1 family gets ``zero_division=0``, accuracy
@@ -421,23 +475,27 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         kw = self._sub("module")
         kw.setdefault("device", dev)
         self.criterion_ = _resolve(self.criterion)(**self._sub("criterion"))
+        if isinstance(self.criterion_, torch.nn.Module):
+            self.criterion_ = self.criterion_.to(dev)    # class weights on the device of the torch-stepped path's log-probs
+            # (criterion.pt is written from a host copy: save_params)
         self._opt_cls = _resolve(self.optimizer)
         ok = self._opt_kwargs = self._sub("optimizer")
         mod_cls = _resolve(self.module)
-        ce = isinstance(self.criterion_, torch.nn.CrossEntropyLoss) and hasattr(mod_cls, "engine")
-        self._fused_kind = None                   # which fused clip + update kernel replaces the torch optimizer
-        if ce and self._opt_cls is torch.optim.SGD and not ok.get("nesterov", False) and not ok.get("weight_decay", 0) \
-                and not ok.get("dampening", 0) and not ok.get("maximize", False):
-            self._fused_kind = "sgd"
-        elif ce and self._opt_cls is torch.optim.Adam and not ok.get("amsgrad", False) and not ok.get("maximize", False):
-            self._fused_kind = "adam"
+        # which fused clip + update kernel replaces the torch optimizer (None: the fit steps through torch)
+        self._fused_kind = fused_kind(self.criterion_, self._opt_cls, ok, mod_cls)
         self._fused = self._fused_kind is not None
+        self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
+        # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
+        self._crit_opts = criterion_options(self.criterion_) if hasattr(mod_cls, "engine") else None
         # a fused fit may take this host thread's own stream; one that steps through torch kernels stays on the device's shared
         # stream and holds the device exclusively while it runs (see STREAM_MODE above)
         self._stream = device_stream(dev, per_thread=(STREAM_MODE == "thread" and self._fused))
         self._gate = device_gate(dev)
         with torch.cuda.stream(self._stream):            # the weight draw / upload too: nothing of a fit runs on another queue
             self.module_ = mod_cls(**kw).to(dev)
+        if hasattr(self.module_, "set_train_options"):
+            self.module_.set_train_options(criterion=self._crit_opts,
+                                           update=update_options(self._fused_kind, self._opt_defaults) if self._fused else None)
         if not self._fused:
             self.optimizer_ = self._opt_cls(self.module_.parameters(), lr=self.lr, **ok)
         self.lr_ = float(self.lr)
@@ -524,10 +582,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             if train and self._fused:
                 eng = self.module_.engine(xb.shape[0], xb.shape[1])
                 eng.set_lr(self.lr_)
-                if self._fused_kind == "adam":
-                    ok = self._opt_kwargs
-                    logp = eng.train_step_adam(xb, yb, self.module_.adam_second_moment(), tuple(ok.get("betas", (0.9, 0.999))),
-                                               float(ok.get("eps", 1e-8)), float(ok.get("weight_decay", 0.0)), max_norm, lengths=lb)
+                if self._fused_kind in ("adam", "adamw"):
+                    betas, eps, wd = adam_args(self)
+                    logp = eng.train_step_adam(xb, yb, self.module_.adam_second_moment(), betas, eps, wd, max_norm, lengths=lb)
                 else:
                     logp = eng.step(xb, yb, lb, momentum, max_norm, graph=self.use_graph if self.use_graph == "auto" else bool(self.use_graph))
                 losses.append(eng.scalars[0].clone())
@@ -543,7 +600,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             else:
                 with torch.no_grad():
                     logp = self.module_(X=xb, y=yb, lengths=lb)
-                    if hasattr(self.module_, "engine") and isinstance(self.criterion_, torch.nn.CrossEntropyLoss):
+                    if hasattr(self.module_, "engine") and self._crit_opts is not None:
                         losses.append(self.module_.engine(xb.shape[0], xb.shape[1]).scalars[0].clone())
                     else:
                         losses.append(self.criterion_(logp, yb))
@@ -595,7 +652,10 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         opt = self._opt_cls([p for n, p in params.items()], lr=self.lr_, **self._opt_kwargs)
         st = self.module_._shared_state()
         mom = st["momentum"]
-        adam = self._fused_kind == "adam"
+        adam = self._fused_kind in ("adam", "adamw")
+        # torch.optim.SGD keeps no momentum buffer before its first step (the first-step rule of dampening reads that): the
+        # library's SGD step count (scalars[3]) says whether there was one
+        sgd_started = adam or float(st["scalars"][3]) > 0
         step = None
         if adam:
             step = float(st["scalars"][2])
@@ -609,7 +669,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             view = lambda arena: arena[off:off + n].view(*shape).detach().cpu().clone()
             if adam:
                 opt.state[params[name]].update(step=torch.tensor(step), exp_avg=view(mom), exp_avg_sq=view(v2))
-            else:
+            elif sgd_started:
                 opt.state[params[name]]["momentum_buffer"] = view(mom)
         return opt.state_dict()
 
@@ -618,9 +678,11 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         ent = {n: (shape, off) for n, shape, off in self.module_._entries}
         st = self.module_._shared_state()
         step = None
+        started = False
         for idx, state in sd.get("state", {}).items():
             shape, off = ent[names[int(idx)]]
             buf = state.get("momentum_buffer", state.get("exp_avg"))
+            started = started or state.get("momentum_buffer") is not None
             if buf is not None:
                 st["momentum"][off:off + buf.numel()].copy_(buf.reshape(-1).to(st["momentum"].device, torch.float32))
             if state.get("exp_avg_sq") is not None:
@@ -629,6 +691,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 step = float(state.get("step", 0.0))
         if step is not None:                           # the device-side Adam step count (shared by every plan of the module)
             st["scalars"][2] = step
+        if self._fused_kind == "sgd":                  # SGD: whether the first step (no dampening) is behind us
+            st["scalars"][3] = 1.0 if started else 0.0
         groups = sd.get("param_groups") or [{}]
         if "lr" in groups[0]:
             self._set_lr(groups[0]["lr"])
@@ -639,7 +703,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         os.makedirs(dirname, exist_ok=True)
         torch.save({k: v.detach().cpu() for k, v in self.module_.state_dict().items()}, os.path.join(dirname, "params.pt"))
         torch.save(self._sgd_state_dict() if self._fused else self.optimizer_.state_dict(), os.path.join(dirname, "optimizer.pt"))
-        torch.save(self.criterion_.state_dict(), os.path.join(dirname, "criterion.pt"))
+        torch.save({k: v.detach().cpu() if torch.is_tensor(v) else v for k, v in self.criterion_.state_dict().items()},
+                   os.path.join(dirname, "criterion.pt"))       # host tensors, like params.pt
         with open(os.path.join(dirname, "history.json"), "w") as f:
             json.dump(self.history, f, indent=1)
 

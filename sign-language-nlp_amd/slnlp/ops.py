@@ -309,6 +309,21 @@ def lsm_nll(logits, y, ignore_index, *, want_grad=True):
     return logp, loss, dl
 
 
+def lsm_nll_ex(logits, y, ignore_index, *, weight=None, label_smoothing=0.0, reduction="mean", want_grad=True):
+    """``lsm_nll`` with CrossEntropyLoss's ``weight`` ([V] fp32 on the device, or None), ``label_smoothing`` and
+    ``reduction`` ("mean" / "sum") -> (logp [B,V], loss [1], dlogits [B,V] | None)"""
+    _lib.require_gpu()
+    B, V = logits.shape
+    logp = torch.empty(B, V, dtype=torch.float32, device=logits.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dl = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_grad else None
+    rows = torch.empty(B, dtype=torch.float32, device=logits.device)
+    w = None if weight is None else weight.to(logits.device, torch.float32).contiguous()
+    check(load().slnlp_lsm_nll_ex(ptr(logits), logits.stride(0), ptr(y), B, V, ignore_index, ptr(w), float(label_smoothing),
+                                  _lib.REDUCTIONS[reduction], ptr(logp), ptr(loss), ptr(dl), V, ptr(rows), stream_ptr()), "lsm_nll_ex")
+    return logp, loss, dl
+
+
 def lsm_bwd(logp, dlogp):
     _lib.require_gpu()
     B, V = logp.shape
@@ -334,6 +349,31 @@ def clip_adam_step(params, grads, exp_avg, exp_avg_sq, lr_dev, step_count, *, be
     norm = torch.empty(1, dtype=torch.float32, device=params.device)
     check(load().slnlp_clip_adam_step(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), ptr(lr_dev), betas[0], betas[1],
                                       eps, weight_decay, max_norm, ptr(partials), ptr(norm), ptr(step_count), stream_ptr()), "clip_adam_step")
+    return norm
+
+
+def clip_sgd_step_ex(params, grads, buf, lr_dev, step_count, *, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False,
+                     max_norm=0.5, skip=(0, 0)):
+    """clip + torch.optim.SGD with dampening / weight decay / Nesterov; ``step_count`` [1] float (device) counts the steps
+    (0 before the first) and is advanced; floats [skip[0], skip[1]) stay untouched.  Returns the pre-clip norm [1]."""
+    _lib.require_gpu()
+    partials = torch.empty(1024, dtype=torch.float32, device=params.device)
+    norm = torch.empty(1, dtype=torch.float32, device=params.device)
+    check(load().slnlp_clip_sgd_step_ex(ptr(params), ptr(grads), ptr(buf), params.numel(), ptr(lr_dev), momentum, dampening,
+                                        weight_decay, int(bool(nesterov)), max_norm, ptr(partials), ptr(norm), ptr(step_count),
+                                        skip[0], skip[1], stream_ptr()), "clip_sgd_step_ex")
+    return norm
+
+
+def clip_adamw_step(params, grads, exp_avg, exp_avg_sq, lr_dev, step_count, *, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                    max_norm=0.5, skip=(0, 0)):
+    """clip + torch.optim.AdamW on flat fp32 arenas (floats [skip[0], skip[1]) untouched).  Returns the pre-clip norm [1]."""
+    _lib.require_gpu()
+    partials = torch.empty(1024, dtype=torch.float32, device=params.device)
+    norm = torch.empty(1, dtype=torch.float32, device=params.device)
+    check(load().slnlp_clip_adamw_step(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), ptr(lr_dev), betas[0],
+                                       betas[1], eps, weight_decay, max_norm, ptr(partials), ptr(norm), ptr(step_count), skip[0], skip[1],
+                                       stream_ptr()), "clip_adamw_step")
     return norm
 
 

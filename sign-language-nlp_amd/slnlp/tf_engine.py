@@ -132,6 +132,24 @@ class TransformerEngine:
         for k, t in v.items():
             t.copy_(torch.as_tensor(sd[k]).to(self.device, torch.float32))
 
+    def set_criterion(self, weight=None, label_smoothing=0.0, reduction="mean"):
+        """CrossEntropyLoss settings of every later forward (train and eval): ``weight`` [Vt] or None, ``label_smoothing``,
+        ``reduction`` "mean" / "sum".  A change drops the plan's captured graphs (re-captured on the next graph step)."""
+        w = None if weight is None else torch.as_tensor(weight).detach().to("cpu", torch.float32).contiguous()   # host memory
+        if w is not None and w.shape != (self.cfg.Vt,):
+            raise ValueError(f"set_criterion: weight of shape {tuple(w.shape)}, expected ({self.cfg.Vt},) -- one per target class")
+        check(load().slnlp_tf_set_criterion(self.handle, ptr(w), float(label_smoothing), _lib.REDUCTIONS[reduction], self._sp()),
+              "tf_set_criterion")
+        self._graph_keys = {}
+
+    def set_update(self, kind="sgd", dampening=0.0, weight_decay=0.0, nesterov=False):
+        """Update rule of the fused step: "sgd" (``optim`` / ``step`` run torch.optim.SGD with these settings), "adam" or
+        "adamw" (``optim_adam`` runs Adam / AdamW with the weight decay of that call; ``weight_decay`` here is the fit's own in
+        a lockstep group, slnlp.lockstep)."""
+        check(load().slnlp_tf_set_update(self.handle, _lib.UPDATE_KINDS[kind], float(dampening), float(weight_decay),
+                                             int(bool(nesterov))), "tf_set_update")
+        self._graph_keys = {}
+
     def set_lr(self, lr):
         self.lr.fill_(float(lr))
 
