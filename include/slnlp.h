@@ -566,6 +566,13 @@ int slnlp_tf_lockstep_num_launches(slnlp_tf_lockstep* group, int slot, int B, in
  * step), step count = each plan's scalars[2]; `momentum` of the step calls is then ignored.  Drops recorded train programs. */
 int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* group, float* const* exp_avg_sq, float beta1, float beta2, float eps,
                                float weight_decay);
+/* per-fit learning-rate tables for per-batch schedules: table[f] = n_steps floats in device memory of the caller (kept alive
+ * while set), the rate of fit f by batch index; a NULL entry leaves that fit's rate alone, a NULL `table` clears the setting.
+ * From then on a TRAIN step with batch index step_index first stores table[f][step_index] into plan f's buf.lr -- inside the
+ * gather launch every step already issues, so num_launches does not change -- and then runs the recorded program;
+ * step_index >= n_steps is an argument error (nothing is launched).  Eval steps never touch buf.lr.  Drops no recorded program.
+ * The pointer table's upload is ordered on `stream`, as set_data's. */
+int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* group, const float* const* table, int n_steps, void* stream);
 int slnlp_tf_lockstep_set_destroy_sync(slnlp_tf_lockstep* group, int on);   /* as slnlp_tf_set_destroy_sync, for the group's tables */
 
 
@@ -645,6 +652,7 @@ int slnlp_rnn_lockstep_epoch(slnlp_rnn_lockstep* group, int slot, int batch, int
 int slnlp_rnn_lockstep_num_launches(slnlp_rnn_lockstep* group, int slot, int B, int train);
 int slnlp_rnn_lockstep_set_adam(slnlp_rnn_lockstep* group, float* const* exp_avg_sq, float beta1, float beta2, float eps,
                                 float weight_decay);
+int slnlp_rnn_lockstep_set_lr_table(slnlp_rnn_lockstep* group, const float* const* table, int n_steps, void* stream);
 int slnlp_rnn_lockstep_set_destroy_sync(slnlp_rnn_lockstep* group, int on);
 
 #ifdef __cplusplus

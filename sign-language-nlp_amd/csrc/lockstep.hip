@@ -22,6 +22,10 @@
 // programs read, and publishes {row0, batch index} as device scalars: lsm_nll writes the batch's log-probs at row
 // row0 of the fit's epoch-long output buffer and the loss into the fit's per-batch loss history, so a whole epoch
 // needs no host synchronisation and no per-step device-to-device copies.
+//
+// Learning-rate tables (slnlp_*_lockstep_set_lr_table): a per-batch schedule cannot come from the host inside an epoch that
+// never synchronises, so the same gather launch also stores table[f][batch index] into fit f's lr scalar (the float the
+// recorded update launches read through the pointer they always had) ahead of every TRAIN step.
 #include <map>
 #include <tuple>
 
@@ -43,6 +47,7 @@ void rnn_ls_outputs(slnlp_rnn_plan* pl, float* logp, float* loss, const int* dyn
 void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train);
 const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl);
 unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl);
+float* rnn_ls_lr(slnlp_rnn_plan* pl);
 
 struct GatherArgs {
     const int64_t* const* X;     // [K] dataset pointers (device table)
@@ -52,6 +57,8 @@ struct GatherArgs {
     int64_t* const* yst;
     int64_t* const* Lst;
     int* dyn;                    // {row0, batch index}
+    const float* const* lr_table;   // [K] per-fit learning rates by batch index (device table; entries may be nullptr), or nullptr
+    float* const* lr;               // [K] each fit's lr scalar (device table)
     int S, row0, B, step;
 };
 
@@ -73,6 +80,10 @@ __global__ __launch_bounds__(256) void ls_gather_kernel(const GatherArgs a) {
         if (f == 0 && threadIdx.x == 0) {
             a.dyn[0] = a.row0;
             a.dyn[1] = a.step;
+        }
+        if (a.lr_table && threadIdx.x == 0) {       // train steps of a group with tables: this batch's rate, before the program runs
+            const float* t = a.lr_table[f];
+            if (t) *a.lr[f] = t[a.step];
         }
     }
 }
@@ -104,6 +115,7 @@ struct LsFit {
     void (*outputs)(void* plan, float* logp, float* loss, const int* dyn);
     void (*replayed)(void* plan, int B, int train);         // host bookkeeping after the step's launches were issued
     unsigned (*opts_gen)(void* plan);                       // generation of the plan's criterion / update settings (TrainOpts)
+    float* (*lr)(void* plan);                               // the device float the plan's update launches read the learning rate from
 };
 
 struct LockstepGroup {
@@ -118,6 +130,10 @@ struct LockstepGroup {
     int64_t** d_yst = nullptr;
     int64_t** d_Lst = nullptr;
     int* dyn = nullptr;
+    // slnlp_*_lockstep_set_lr_table: both pointer tables sit below ws_mark (never reclaimed); d_lr_table is rewritten in place
+    float** d_lr = nullptr;                         // device table [K]: each fit's lr scalar
+    const float** d_lr_table = nullptr;             // device table [K]: the caller's per-fit tables (nullptr: leave that fit alone)
+    int lr_steps = 0;                               // floats per table; 0: no tables set
     struct Slot {
         bool set = false;
         int64_t rows = 0;
@@ -333,6 +349,11 @@ static int ls_init(LockstepGroup* ls, int B, int S, void* workspace, int64_t wor
     SLNLP_TRY(upload(ls, ls->Xst.data(), K * sizeof(void*), (void**)&ls->d_Xst, st));
     SLNLP_TRY(upload(ls, ls->yst.data(), K * sizeof(void*), (void**)&ls->d_yst, st));
     if (ls->has_len) SLNLP_TRY(upload(ls, ls->Lst.data(), K * sizeof(void*), (void**)&ls->d_Lst, st));
+    std::vector<float*> lr(K);
+    for (int f = 0; f < K; ++f) lr[f] = ls->fits[f].lr(ls->fits[f].plan);
+    SLNLP_TRY(upload(ls, lr.data(), K * sizeof(void*), (void**)&ls->d_lr, st));
+    ls->d_lr_table = (const float**)ls->take(K * sizeof(void*));
+    SLNLP_CHECK_ARG(ls->d_lr_table, "lockstep_create: workspace too small");
     ls->ws_mark = ls->ws_used;
     return 0;
 }
@@ -381,6 +402,26 @@ static int ls_set_data(LockstepGroup* ls, int slot, const int64_t* const* X, con
     return upload_slot_tables(ls, s, st);
 }
 
+// table[f]: n_steps learning rates of fit f by batch index (device memory of the caller), nullptr: that fit keeps whatever its
+// lr scalar holds; table == nullptr: no tables any more.  The recorded programs read the lr scalar through the pointer they
+// always had, so none is dropped.  The copy is ordered on `st` behind every gather launch that read the old table.
+static int ls_set_lr_table(LockstepGroup* ls, const float* const* table, int n_steps, hipStream_t st) {
+    SLNLP_CHECK_ARG(ls, "lockstep_set_lr_table: null group");
+    if (!table) {
+        ls->lr_steps = 0;
+        return 0;
+    }
+    SLNLP_CHECK_ARG(n_steps > 0, "lockstep_set_lr_table: n_steps %d", n_steps);
+    if (hipMemcpyAsync(ls->d_lr_table, table, ls->K * sizeof(void*), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {       // pageable host memory: as upload()
+        set_error("lockstep_set_lr_table: table upload failed: %s", hipGetErrorString(hipGetLastError()));
+        ls->lr_steps = 0;
+        return SLNLP_ERR_LAUNCH;
+    }
+    ls->lr_steps = n_steps;
+    return 0;
+}
+
 // One lockstep step of every fit on rows [row0, row0 + B) of slot `slot`: train != 0 -> forward + criterion + backward +
 // clip + SGD (what slnlp_{tf,rnn}_train_step does for one fit), else an eval-mode forward + criterion.
 static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_index, int train, float momentum, float max_norm,
@@ -389,6 +430,8 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     LockstepGroup::Slot& s = ls->slot[slot];
     SLNLP_CHECK_ARG(B > 0 && B <= ls->maxB && row0 >= 0 && row0 + B <= s.rows, "lockstep_step: rows [%ld, %ld) outside 0..%ld or batch > %d",
                     (long)row0, (long)(row0 + B), (long)s.rows, ls->maxB);
+    SLNLP_CHECK_ARG(!train || !ls->lr_steps || (step_index >= 0 && step_index < ls->lr_steps),
+                    "lockstep_step: batch index %d outside the learning-rate tables' %d steps", step_index, ls->lr_steps);
     StepScope scope(st);               // one kernel sequence per device (launch.hpp)
     SLNLP_TRY(scope.rc);
     if (train) {
@@ -433,6 +476,8 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     GatherArgs g;
     g.X = s.d_X; g.y = s.d_y; g.len = ls->has_len ? s.d_len : nullptr;
     g.Xst = ls->d_Xst; g.yst = ls->d_yst; g.Lst = ls->d_Lst; g.dyn = ls->dyn;
+    g.lr_table = train && ls->lr_steps ? ls->d_lr_table : nullptr;      // eval steps never touch the learning rate
+    g.lr = ls->d_lr;
     g.S = ls->S; g.row0 = (int)row0; g.B = B; g.step = step_index;
     int gx = (B * ls->S + 255) / 256;
     if (gx > 64) gx = 64;
@@ -516,12 +561,17 @@ static void rnn_outputs(void* p, float* logp, float* loss, const int* dyn) { rnn
 static void rnn_replayed(void* p, int B, int train) { rnn_ls_replayed((slnlp_rnn_plan*)p, B, train); }
 static unsigned rnn_opts_gen(void* p) { return rnn_ls_opts_gen((slnlp_rnn_plan*)p); }
 static unsigned tf_opts_gen(void* p) { return ((slnlp_tf_plan*)p)->opts.gen; }
+static float* rnn_lr(void* p) { return rnn_ls_lr((slnlp_rnn_plan*)p); }
+static float* tf_lr(void* p) { return ((slnlp_tf_plan*)p)->buf.lr; }
+
+// the two learning-rate pointer tables of ls_init, each on a 256-byte boundary of the bump allocator
+static size_t ls_lr_table_bytes(int K) { return 2 * (((size_t)K * sizeof(void*) + 255) & ~(size_t)255); }
 
 extern "C" {
 
 int64_t slnlp_tf_lockstep_workspace_bytes(const slnlp_tf_config* cfg, int K) {
     if (!cfg || K < 1 || K > LS_MAX_FITS) return -1;
-    // staging + pointer tables + argument / job tables of the cached programs (<= 8: train / eval x full / tail batch x
+    // staging + pointer tables (staging, slots, learning rates) + argument / job tables of the cached programs (<= 8: train / eval x full / tail batch x
     // data slots).  Per fit a program holds, for each of its ~45 + 55 N call sites, either a <= 256-byte argument pack, or
     // -- the 8 N plane-GEMM sites -- up to 2 jobs and a block map of 4 B per workgroup (the dgrad's tiles plus the wgrad's
     // tiles x split-K, jobs padded to multiples of 8 blocks), or -- ~16 N + 4 fp32-operand group sites -- up to 4 jobs and
@@ -534,7 +584,7 @@ int64_t slnlp_tf_lockstep_workspace_bytes(const slnlp_tf_config* cfg, int K) {
     const size_t brow = cd((size_t)cfg->B, 64) * cd(wide > (size_t)cfg->Vt ? wide : (size_t)cfg->Vt, 16) * (size_t)cfg->H;
     const size_t per_fit = (45 + 55 * N) * 256 + 8 * N * (2 * sizeof(PlaneJob) + 4 * plane_blocks) +
                            (16 * N + 4) * (4 * sizeof(GemmJob) + 4 * 4 * brow);
-    return (int64_t)(staging + 65536 + 8 * ((45 + 55 * N) * 512 + (size_t)K * per_fit * 3 / 2));
+    return (int64_t)(staging + ls_lr_table_bytes(K) + 65536 + 8 * ((45 + 55 * N) * 512 + (size_t)K * per_fit * 3 / 2));
 }
 
 int slnlp_tf_lockstep_create(slnlp_tf_plan** plans, int K, void* workspace, int64_t workspace_bytes, void* stream,
@@ -552,7 +602,7 @@ int slnlp_tf_lockstep_create(slnlp_tf_plan** plans, int K, void* workspace, int6
         for (int g = 0; g < f; ++g) SLNLP_CHECK_ARG(plans[g] != plans[f], "lockstep_create: plan %d listed twice", f);
     }
     slnlp_tf_lockstep* ls = new slnlp_tf_lockstep();
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed, tf_opts_gen});
+    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed, tf_opts_gen, tf_lr});
     const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;
@@ -582,6 +632,9 @@ int slnlp_tf_lockstep_num_launches(slnlp_tf_lockstep* ls, int slot, int B, int t
 int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* ls, float* const* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay) {
     return ls_set_adam(ls, exp_avg_sq, beta1, beta2, eps, weight_decay);
 }
+int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* ls, const float* const* table, int n_steps, void* stream) {
+    return ls_set_lr_table(ls, table, n_steps, (hipStream_t)stream);
+}
 int slnlp_tf_lockstep_set_destroy_sync(slnlp_tf_lockstep* ls, int on) {
     SLNLP_CHECK_ARG(ls, "lockstep_set_destroy_sync: null group");
     ls->destroy_sync = on ? 1 : 0;
@@ -596,7 +649,7 @@ int64_t slnlp_rnn_lockstep_workspace_bytes(const slnlp_rnn_config* cfg, int K) {
     // of ~400 B + a block map: budget 6 KiB on average, for 6 programs (train / eval x full / tail batch, test).
     const size_t staging = (size_t)K * ((size_t)cfg->B * cfg->S + 2 * cfg->B + 64) * sizeof(int64_t);
     const size_t sites = 64 + (size_t)cfg->N * (3 * (size_t)cfg->S + 24);
-    return (int64_t)(staging + 65536 + 6 * sites * (size_t)K * 6144);
+    return (int64_t)(staging + ls_lr_table_bytes(K) + 65536 + 6 * sites * (size_t)K * 6144);
 }
 
 int slnlp_rnn_lockstep_create(slnlp_rnn_plan** plans, int K, void* workspace, int64_t workspace_bytes, void* stream,
@@ -615,7 +668,7 @@ int slnlp_rnn_lockstep_create(slnlp_rnn_plan** plans, int K, void* workspace, in
     }
     slnlp_rnn_lockstep* ls = new slnlp_rnn_lockstep();
     ls->has_len = true;
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed, rnn_opts_gen});
+    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed, rnn_opts_gen, rnn_lr});
     const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;
@@ -643,6 +696,9 @@ int slnlp_rnn_lockstep_epoch(slnlp_rnn_lockstep* ls, int slot, int batch, int tr
 int slnlp_rnn_lockstep_num_launches(slnlp_rnn_lockstep* ls, int slot, int B, int train) { return ls_num_launches(ls, slot, B, train); }
 int slnlp_rnn_lockstep_set_adam(slnlp_rnn_lockstep* ls, float* const* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay) {
     return ls_set_adam(ls, exp_avg_sq, beta1, beta2, eps, weight_decay);
+}
+int slnlp_rnn_lockstep_set_lr_table(slnlp_rnn_lockstep* ls, const float* const* table, int n_steps, void* stream) {
+    return ls_set_lr_table(ls, table, n_steps, (hipStream_t)stream);
 }
 int slnlp_rnn_lockstep_set_destroy_sync(slnlp_rnn_lockstep* ls, int on) {
     SLNLP_CHECK_ARG(ls, "rnn_lockstep_set_destroy_sync: null group");

@@ -926,4 +926,5 @@ void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train) {
 }
 const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl) { return &pl->cfg; }
 unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl) { return pl->opts.gen; }
+float* rnn_ls_lr(slnlp_rnn_plan* pl) { return pl->buf.lr; }
 }  // namespace slnlp

@@ -186,6 +186,7 @@ SIGNATURES = {
     "slnlp_tf_lockstep_epoch": (i32, [vp, i32, i32, i32, C.c_float, C.c_float, vp]),
     "slnlp_tf_lockstep_num_launches": (i32, [vp, i32, i32, i32]),
     "slnlp_tf_lockstep_set_adam": (i32, [vp, vp, f32, f32, f32, f32]),
+    "slnlp_tf_lockstep_set_lr_table": (i32, [vp, vp, i32, vp]),
     "slnlp_tf_lockstep_set_destroy_sync": (i32, [vp, i32]),
     "slnlp_rnn_lockstep_workspace_bytes": (i64, [vp, i32]),
     "slnlp_rnn_lockstep_create": (i32, [vp, i32, vp, i64, vp, vp]),
@@ -195,6 +196,7 @@ SIGNATURES = {
     "slnlp_rnn_lockstep_epoch": (i32, [vp, i32, i32, i32, C.c_float, C.c_float, vp]),
     "slnlp_rnn_lockstep_num_launches": (i32, [vp, i32, i32, i32]),
     "slnlp_rnn_lockstep_set_adam": (i32, [vp, vp, f32, f32, f32, f32]),
+    "slnlp_rnn_lockstep_set_lr_table": (i32, [vp, vp, i32, vp]),
     "slnlp_rnn_lockstep_set_destroy_sync": (i32, [vp, i32]),
 }
 

@@ -93,6 +93,22 @@ class LockstepGroup:
         self._v2 = list(exp_avg_sq)                      # keep the tensors alive: the C side holds raw pointers
         check(self._fn("set_adam")(self.handle, _ptr_array(self._v2), betas[0], betas[1], eps, weight_decay), f"{self.kind}_lockstep_set_adam")
 
+    def set_lr_tables(self, tables):
+        """Per-fit learning rates by train-batch index: a list with, per fit, a contiguous float32 device tensor [n_steps] or None
+        (that fit keeps the rate its engine's ``set_lr`` gave it); None (or no tensor at all) clears the setting.  From then on every
+        TRAIN step first stores ``tables[f][step_index]`` into fit f's learning rate, inside the launch that stages the batch."""
+        given = [t for t in (tables or []) if t is not None]
+        if not given:
+            self._lr_tables = None
+            check(self._fn("set_lr_table")(self.handle, None, 0, self._sp()), f"{self.kind}_lockstep_set_lr_table")
+            return
+        n = int(given[0].numel())
+        assert len(tables) == self.K and all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == given[0].device
+                                             for t in given), "lockstep: one float32 device tensor [n_steps] (or None) per fit"
+        self._lr_tables = list(tables)                   # keep the tensors alive: the gather launch reads them
+        arr = (C.c_void_p * self.K)(*[None if t is None else ptr(t) for t in tables])
+        check(self._fn("set_lr_table")(self.handle, arr, n, self._sp()), f"{self.kind}_lockstep_set_lr_table")
+
     def _sync_versions(self):
         for e in self.engines:                           # Transformer: weight planes follow outside writes to the fp32 arena
             if hasattr(e, "sync_params_version"):
@@ -197,10 +213,22 @@ def _fit_lockstep_gated(nets, datasets):
                     group.set_data(VALID, [runs[i].Xva for i in active], [runs[i].yva for i in active], r0.bs,
                                    [runs[i].Lva for i in active])
                 members = list(active)
+            # every fit's rates for this epoch, before anything is queued (a scheduler stepped past its end raises here)
+            tables = [runs[i].lr_table() for i in active]
             for i in active:
                 engines[i].set_lr(nets[i].lr_)
                 nets[i].module_.train()
                 runs[i].begin_epoch()
+            pb = [j for j, (i, t) in enumerate(zip(active, tables)) if t is not None and runs[i].schedule.per_batch]
+            if pb:
+                # the epoch runs without coming back to the host: per-batch rates go to the device as one [fits, batches] tensor
+                # (a host-to-device copy on the fit's stream, alive in the group until the next epoch replaces it), and each
+                # step's gather launch hands every such fit its row's next entry; the other fits keep the rate set above
+                dev_tab = torch.tensor([tables[j] for j in pb], dtype=torch.float32).to(group.device)
+                per_fit = [None] * len(active)
+                for r, j in enumerate(pb):
+                    per_fit[j] = dev_tab[r]
+                group.set_lr_tables(per_fit)
             t_epoch = time.perf_counter()
             group.epoch(TRAIN, r0.bs, True, r0.momentum, r0.max_norm)
             if r0.va is not None:

@@ -14,7 +14,8 @@ semantics:
 * per batch: forward -> CrossEntropyLoss(ignore_index=pad) -> backward ->
   clip_grad_norm_(gradient_clip_value) -> SGD(momentum)  == ONE hipGraph replay;
 * per epoch: valid pass, ``EpochScoring`` metrics for train/valid, ``lr`` scoring,
-  ``LRScheduler(ReduceLROnPlateau)`` on valid_loss, ``EarlyStopping`` (patience,
+  ``LRScheduler`` (``ReduceLROnPlateau`` on valid_loss, or any other ``torch.optim.lr_scheduler`` policy stepped per
+  epoch or per batch: slnlp/schedule.py), ``EarlyStopping`` (patience,
   relative threshold), ``Checkpoint`` on ``valid_loss_best`` (helper.py:197-273).
 
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
@@ -28,7 +29,7 @@ import importlib
 import numpy as np
 import torch
 
-from . import metrics
+from . import metrics, schedule
 from .data import TokenDataset
 
 
@@ -289,7 +290,7 @@ class _CachedPredictor(ClassifierMixin, BaseEstimator):
 
 class _FitRun:
     """One estimator's fit between epochs: the internal split, the device-resident data, and skorch's per-epoch callbacks
-    (EpochScoring on the cached predictions, Checkpoint, LRScheduler(ReduceLROnPlateau), EarlyStopping; helper.py:197-273).
+    (EpochScoring on the cached predictions, Checkpoint, LRScheduler, EarlyStopping; helper.py:197-273).
     ``partial_fit`` drives one of these with its own batch loop; ``slnlp.lockstep`` drives K of them with one launch
     sequence per step -- the epoch bookkeeping is this one piece of code either way."""
 
@@ -309,9 +310,12 @@ class _FitRun:
         self.es = es
         self.max_norm = float(clip["gradient_clip_value"]) if clip and clip.get("gradient_clip_value") else 0.0
         self.momentum = float(net._opt_kwargs.get("momentum", 0.0))
-        self.plateau = None
-        if sched:
-            assert sched.get("policy", "ReduceLROnPlateau") == "ReduceLROnPlateau", "only ReduceLROnPlateau is wired"
+        self.plateau, self.schedule, self.epoch_lrs = None, None, None
+        if sched and not schedule.is_plateau(sched):
+            # the schedule's position is a function of the history: built from scratch and replayed up to where the fit stands
+            self.schedule = schedule.LRSchedule.from_setting(sched, net.lr).fast_forward(net.history)
+            net._set_lr(self.schedule.current)
+        elif sched:
             dummy = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=net.lr_)
             self.plateau = torch.optim.lr_scheduler.ReduceLROnPlateau(
                 dummy, **{k: v for k, v in sched.items() if k not in ("policy", "monitor", "step_every")})
@@ -323,14 +327,28 @@ class _FitRun:
     def begin_epoch(self):
         self.t0 = time.time()
 
+    def lr_table(self):
+        """The learning rates of the coming epoch's train batches, in order (None: no schedule, every batch runs at ``net.lr_``).
+        Call once per epoch, before any of its work is queued: a scheduler stepped past its end raises here."""
+        if self.schedule is None:
+            return None
+        self.epoch_lrs = self.schedule.epoch_table((len(self.tr) + self.bs - 1) // self.bs)
+        return self.epoch_lrs
+
     def end_epoch(self, tr, va):
         """tr / va: (sample-weighted mean loss, log-probs [n, V] on the device, [(batch loss, batch size)]) of the epoch's
         train and valid passes (va None without a valid split).  Returns True when the fit is over."""
         net = self.net
         tr_loss, tr_logp, tr_batches = tr
         epoch = len(net.history) + 1
+        if self.schedule is not None:
+            # what the reference's lr scoring reads at epoch end: with batch stepping the rate after the epoch's last step
+            net._set_lr(self.schedule.current)
         row = {"epoch": epoch, "train_loss": tr_loss, "lr": net.lr_,
                "batches": [{"train_loss": l, "train_batch_size": n} for l, n in tr_batches]}   # skorch history layout
+        if self.schedule is not None and self.schedule.per_batch:
+            for b, lr in zip(row["batches"], self.epoch_lrs):
+                b["event_lr"] = lr                           # the rate this batch used
         if va is not None:
             va_loss, va_logp, va_batches = va
             row["batches"] += [{"valid_loss": l, "valid_batch_size": n} for l, n in va_batches]
@@ -361,6 +379,9 @@ class _FitRun:
         if self.plateau is not None:                         # LRScheduler(monitor=valid_loss, step_every=epoch)
             self.plateau.step(monitor)
             net._set_lr(self.plateau.optimizer.param_groups[0]["lr"])
+        if self.schedule is not None:                        # LRScheduler(step_every=epoch); a no-op with batch stepping
+            self.schedule.epoch_end()
+            net._set_lr(self.schedule.current)
         self.epochs_left -= 1
         if self.es:                                          # skorch EarlyStopping, lower_is_better
             es = self.es
@@ -421,11 +442,11 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             elif kind == "GradientNormClipping":
                 self._params["gradient_clipping"] = {"gradient_clip_value": get("gradient_clip_value")}
             elif kind == "LRScheduler":
-                pol = get("policy", "ReduceLROnPlateau")
-                pol = pol if isinstance(pol, str) else getattr(pol, "__name__", str(pol))
-                if pol != "ReduceLROnPlateau" or get("monitor", "valid_loss") != "valid_loss":
-                    raise ValueError("LRScheduler: only ReduceLROnPlateau on valid_loss is implemented")
-                self._params["lr_scheduler"] = {"policy": pol, **dict(get("kwargs", {}) or {})}
+                setting = schedule.from_callback(obj)
+                if schedule.is_plateau(setting) and get("monitor", "valid_loss") != "valid_loss":
+                    raise ValueError("LRScheduler: ReduceLROnPlateau is implemented on monitor='valid_loss' only")
+                schedule.check_setting(setting, self._params["lr"])
+                self._params["lr_scheduler"] = setting
             elif kind == "Checkpoint":
                 if get("monitor", "valid_loss_best") != "valid_loss_best":
                     raise ValueError("Checkpoint: only monitor='valid_loss_best' is implemented")
@@ -469,6 +490,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
 
     # ------------------------------------------------------------- lifecycle
     def initialize(self):
+        schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
         dev = torch.device(self.device)
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("slnlp.net: device %r -- the HIP path is the only compute path (no CPU fallback)" % (self.device,))
@@ -544,7 +566,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             for _ in range(int(self.max_epochs)):
                 run.begin_epoch()
                 self.module_.train()
-                tr = self._run_epoch(run.Xtr, run.Ltr, run.ytr, run.bs, True, run.momentum, run.max_norm)
+                tr = self._run_epoch(run.Xtr, run.Ltr, run.ytr, run.bs, True, run.momentum, run.max_norm, lrs=run.lr_table())
                 va = None
                 if run.va is not None:
                     self.module_.eval()
@@ -572,13 +594,15 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             for g in self.optimizer_.param_groups:
                 g["lr"] = self.lr_
 
-    def _run_epoch(self, X, L, y, bs, train, momentum, max_norm):
-        """One pass in dataset order.  Returns (sample-weighted mean loss, log-probs [N,V] on the device,
-        [(batch loss, batch size)])."""
+    def _run_epoch(self, X, L, y, bs, train, momentum, max_norm, lrs=None):
+        """One pass in dataset order; ``lrs``: the learning rate of each train batch (``_FitRun.lr_table``; None: ``lr_``
+        throughout).  Returns (sample-weighted mean loss, log-probs [N,V] on the device, [(batch loss, batch size)])."""
         n = X.shape[0]
         losses, sizes, outs = [], [], []
-        for i in range(0, n, bs):
+        for k, i in enumerate(range(0, n, bs)):
             xb, lb, yb = X[i:i + bs], L[i:i + bs], y[i:i + bs]
+            if train and lrs is not None:
+                self._set_lr(lrs[k])                        # one schedule for the fused and the torch-stepped path
             if train and self._fused:
                 eng = self.module_.engine(xb.shape[0], xb.shape[1])
                 eng.set_lr(self.lr_)
