@@ -466,7 +466,9 @@ int slnlp_tf_train_step(slnlp_tf_plan* plan, const int64_t* X, const int64_t* y,
 int slnlp_tf_graph_capture_train(slnlp_tf_plan* plan, const int64_t* X, const int64_t* y, int B,
                                  float momentum, float max_norm, float* logp, void* stream);
 int slnlp_tf_graph_launch(slnlp_tf_plan* plan, int B, void* stream);
-/* test helper: copy a named activation tap ("enc0", "memory", "dec1", "logits", ...) */
+/* test helper: copy a named activation tap ("enc0", "memory", "dec1", "logits", ...); "enc<l>.<planes>" (d2p, hp, ghp, x1p, d1p,
+ * ctxp, gqkvp, x2p, xinp): an operand of the layer's gradient GEMMs as its bf16 planes -- the hi plane's [rows, cols] 16-bit words,
+ * then the lo plane's, in rows * cols floats */
 int slnlp_tf_tap(slnlp_tf_plan* plan, const char* name, float* out, int64_t max_floats,
                  int64_t* n_out, void* stream);
 /* The parameter arena was written from outside the library (load_state_dict, a torch optimizer, an in-place edit):

@@ -281,6 +281,9 @@ constexpr int WD_MAX_SPLITK = 8;
 struct WdPlan { int split, separate; };
 WdPlan gemm_planes_wd_plan(const slnlp_gemm_args& wgrad, const slnlp_gemm_args& dgrad);
 int gemm_planes_wd(const slnlp_gemm_args& wgrad, const slnlp_gemm_args& dgrad, void* scratch, size_t scratch_bytes, hipStream_t s);
+// a pair whose launch waits for its weight gradient: the split factor that launch gives it (a caller may then run dX alone and dW
+// later with that split: same sums), or 0: keep the pair in one launch.  Decided from the shapes alone
+int gemm_planes_wd_defer(const slnlp_gemm_args& wgrad, const slnlp_gemm_args& dgrad);
 struct QuantRow { long off; int K, pad; };   // one weight row of a precision-8 plan: offset into the arena (floats), length
 int quant_rows_fp8(const float* x, int64_t ld, int R, int K, unsigned char* q, int64_t ldq, float* scale, const void* row_table,
                    hipStream_t st);   // row_table: device array of {long offset (floats); int K; int pad} or null

@@ -74,4 +74,20 @@ void plane_merge_geometry(const void* recorded_fn, PlaneJob* jobs, int njobs, co
 // -1: more jobs / units than a map entry can name)
 int plane_merge_place(const void* merged_fn, const PlaneJob* jobs, int njobs, std::vector<int>& map);
 
+// A batch of independent plane-GEMM jobs as ONE table-driven launch whose tables the caller keeps on the device (the solo
+// Transformer plan's deferred weight gradients): host images of the job table and the block map, the kernel and its geometry.
+struct PlaneBatch {
+    std::vector<PlaneJob> jobs;
+    std::vector<int> map;
+    const void* fn = nullptr;
+    size_t lds = 0;
+    int geo = 0;
+};
+size_t plane_batch_scratch_bytes(const slnlp_gemm_args* jobs, const int* split_k, int njobs);      // zero-initialised, 16-byte aligned
+size_t plane_batch_map_capacity(const slnlp_gemm_args* jobs, const int* split_k, int njobs);       // block-map entries, any geometry
+int plane_batch_build(const slnlp_gemm_args* jobs, const int* split_k, int njobs, void* scratch, size_t scratch_bytes, size_t map_capacity,
+                      PlaneBatch& out);
+int plane_batch_launch(const PlaneBatch& b, const PlaneJob* dev_tab, const int* dev_map, hipStream_t s);   // tables = copies of b.jobs / b.map
+int plane_geo_forced();   // slnlp_set_plane_tile's geometry (-1: automatic): a built batch is stale once it changes
+
 }  // namespace slnlp

@@ -1090,6 +1090,30 @@ size_t gemm_group_scratch_bytes(const slnlp_gemm_args* jobs, const int* split_k,
     return GROUP_COUNTERS * sizeof(int) + floats * sizeof(float);
 }
 
+// The launch-independent part of a job descriptor: epilogue constants, K-loop variant, tile grid at `geo`, K slices (clamped)
+static void fill_plane_job(PlaneJob& j, const slnlp_gemm_args& a, int nks, int geo) {
+    j.a = a;
+    j.drop_thr = dropout_threshold(a.drop_p);
+    j.drop_scale = 1.f / (1.f - a.drop_p);
+    j.variant = a.precision == 8 ? 3 : (a.a_kmajor && a.b_kmajor) ? 0 : a.a_kmajor ? 1 : 2;
+    if (a.precision == 2) j.variant = a.a_kmajor ? 3 : 4;
+    j.hand_off = splitk_mode() >= 2 ? splitk_mode() : 0;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    j.vec_out = a.N % 4 == 0 && (!a.C || (a.ldc % 4 == 0 && al16(a.C))) && (!a.resid || (a.ldr % 4 == 0 && al16(a.resid))) &&
+                (!a.C_hi || (a.ldc_p % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C_hi) & 7) == 0 &&
+                             (!a.C_lo || (reinterpret_cast<uintptr_t>(a.C_lo) & 7) == 0)));
+    j.tiles_x = ceil_div(a.N, GEO[geo].bn);
+    j.tiles_y = ceil_div(a.M, GEO[geo].bm);
+    const int ktiles = ceil_div(a.K, PT);
+    if (nks < 1 || splitk_mode() == 1) nks = 1;          // (probe mode 1: no split-K at all)
+    if (nks > ktiles) nks = ktiles;
+    j.nks = nks;
+    j.block_begin = 0;
+    j.part = nullptr;
+    j.part_rs = nullptr;
+    j.counters = nullptr;
+}
+
 int gemm_planes_group(const slnlp_gemm_args* jobs, const int* split_k, int njobs, void* scratch, size_t scratch_bytes,
                       hipStream_t s, bool defer_reduce) {
     SLNLP_CHECK_ARG(jobs && njobs >= 1 && njobs <= MAX_JOBS, "gemm_group: 1..%d jobs", MAX_JOBS);
@@ -1105,24 +1129,9 @@ int gemm_planes_group(const slnlp_gemm_args* jobs, const int* split_k, int njobs
         auto family = [](int p) { return p == 2 ? 3 : p; };
         SLNLP_CHECK_ARG(family(a.precision) == family(jobs[0].precision), "gemm_group: jobs of one launch share the precision family");
         PlaneJob& j = P.job[i];
-        j.a = a;
-        j.drop_thr = dropout_threshold(a.drop_p);
-        j.drop_scale = 1.f / (1.f - a.drop_p);
-        j.variant = a.precision == 8 ? 3 : (a.a_kmajor && a.b_kmajor) ? 0 : a.a_kmajor ? 1 : 2;
-        if (a.precision == 2) j.variant = a.a_kmajor ? 3 : 4;
-        j.hand_off = splitk_mode() >= 2 ? splitk_mode() : 0;
-        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-        j.vec_out = a.N % 4 == 0 && (!a.C || (a.ldc % 4 == 0 && al16(a.C))) && (!a.resid || (a.ldr % 4 == 0 && al16(a.resid))) &&
-                    (!a.C_hi || (a.ldc_p % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C_hi) & 7) == 0 &&
-                                 (!a.C_lo || (reinterpret_cast<uintptr_t>(a.C_lo) & 7) == 0)));
         if (a.precision == 8) SLNLP_CHECK_ARG(!split_k || split_k[i] <= 1, "gemm_group: fp8 jobs do not split K");
-        j.tiles_x = ceil_div(a.N, GEO[geo].bn);
-        j.tiles_y = ceil_div(a.M, GEO[geo].bm);
-        const int ktiles = ceil_div(a.K, PT);
-        int nks = split_k ? split_k[i] : 1;
-        if (nks < 1 || splitk_mode() == 1) nks = 1;          // (probe mode 1: no split-K at all)
-        if (nks > ktiles) nks = ktiles;
-        j.nks = nks;
+        fill_plane_job(j, a, split_k ? split_k[i] : 1, geo);
+        const int nks = j.nks;
         j.block_begin = blocks;
         j.part = nullptr;
         j.part_rs = nullptr;
@@ -1210,13 +1219,17 @@ static int wd_split_grouped(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg
 // profiles/r05_pmc_plane_pair.txt), and alone each takes the tile and the split that suit it: the data gradient one full round of
 // 256-wide tiles, the weight gradient as many K slices as fill one round of them (48 tiles x 5).  Measured on one box
 // (profiles/r05_plane_pair_sweep.txt): 480 us grouped (128-wide tiles, 6 slices) -> 192 + 236 us.
+static bool wd_both_large(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg) {
+    const long d128 = (long)ceil_div(dg.M, 128) * ceil_div(dg.N, 128), w256 = (long)ceil_div(wg.M, 256) * ceil_div(wg.N, 256);
+    return d128 >= 1024 && dg.K >= 1024 && w256 >= 24 && w256 <= 256 && wg.K >= 4096;
+}
 WdPlan gemm_planes_wd_plan(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg) {
     WdPlan p;
     p.separate = 0;
     p.split = wd_split_grouped(wg, dg);
-    const long d128 = (long)ceil_div(dg.M, 128) * ceil_div(dg.N, 128), w256 = (long)ceil_div(wg.M, 256) * ceil_div(wg.N, 256);
+    const long w256 = (long)ceil_div(wg.M, 256) * ceil_div(wg.N, 256);
     static const bool allow_separate = [] { const char* e = getenv("SLNLP_WD_SEPARATE"); return !(e && atoi(e) == 0); }();   // (A / B measurements)
-    if (allow_separate && g_plane_geo.load(std::memory_order_relaxed) < 0 && wg.precision != 8 && d128 >= 1024 && dg.K >= 1024 && w256 >= 24 && w256 <= 256 && wg.K >= 4096) {
+    if (allow_separate && g_plane_geo.load(std::memory_order_relaxed) < 0 && wg.precision != 8 && wd_both_large(wg, dg)) {
         p.separate = 1;
         int n = (int)(256 / w256);                          // K slices that fill one round of 256-wide tiles
         n = std::min(n, std::min(WD_MAX_SPLITK, ceil_div(wg.K, 2048)));
@@ -1235,6 +1248,21 @@ int gemm_planes_wd(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg, void* s
     const slnlp_gemm_args jobs[2] = {wg, dg};
     const int split[2] = {p.split, 1};
     return gemm_planes_group(jobs, split, 2, scratch, scratch_bytes, st);
+}
+
+// The other end: a pair whose ONE launch is a single round of workgroups (all of them resident at once, two per CU) lasts as long
+// as its longest workgroup, and when that is a weight-gradient slice -- 13 K-steps + the meeting against the data gradient's 8 at
+// cfg2's E x E pairs, 38 against 24 at its in_proj -- whatever reads dX waits for a dW nobody reads before the optimizer.  A plan that
+// can run the weight gradient later (tf_plan.hip: all of a backward's in one batched launch, plane_batch_*) asks here: the split
+// factor the pair's launch would give the weight gradient -- kept, so the sums keep their order -- or 0: leave the pair together
+// (several rounds of workgroups: the weight gradient's fill the data gradient's tail, and pairing is work-conserving).
+// A rule of the shapes alone: what a plan sizes its scratch by must not move with a tuning knob.
+int gemm_planes_wd_defer(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg) {
+    if (wg.precision == 8 || wd_both_large(wg, dg)) return 0;
+    const int n = wd_split_grouped(wg, dg);
+    const long tw = (long)ceil_div(wg.M, 64) * ceil_div(wg.N, 64), td = (long)ceil_div(dg.M, 64) * ceil_div(dg.N, 64);
+    const int len = ceil_div(ceil_div(wg.K, 64), n) + (n > 1 ? 1 : 0);
+    return (tw * n + td <= 512 && len > ceil_div(dg.K, 64)) ? n : 0;
 }
 
 // A recorded job re-tiled for a merged launch (lockstep.hip): only the tile grid changes -- the K partition (nks) and the
@@ -1333,6 +1361,79 @@ int plane_merge_place(const void* merged_fn, const PlaneJob* jobs, int njobs, st
         for (size_t i = 0; i < units[k].size(); ++i) map[i * 8 + k] = units[k][i];
     return 1;
 }
+
+// ---- a batch of independent jobs as ONE table-driven launch (the solo Transformer plan's deferred weight gradients, tf_plan.hip):
+// the job table and block map a merged lockstep launch builds per recorded program, here built by the plan that owns every pointer
+// in them.  Geometry for all the batch's tiles (plane_merge_geometry), units placed on the XCDs (plane_merge_place); each job keeps
+// the K slices it is given, so its sums keep their order whatever the tile.
+// Scratch of a batch: one arrival counter per (job, 64 x 64 tile) -- the most any geometry needs; a batch is not bound by
+// GROUP_COUNTERS and is always one launch -- then per split-K job the regions gemm_group_scratch_bytes() describes.
+static size_t batch_counters(const slnlp_gemm_args* jobs, const int* split_k, int njobs) {
+    size_t n = 0;
+    for (int i = 0; i < njobs; ++i)
+        if (split_k[i] > 1) n += (size_t)ceil_div(jobs[i].M, 64) * ceil_div(jobs[i].N, 64);
+    return (n + 63) & ~(size_t)63;
+}
+size_t plane_batch_scratch_bytes(const slnlp_gemm_args* jobs, const int* split_k, int njobs) {
+    return batch_counters(jobs, split_k, njobs) * sizeof(int) + gemm_group_scratch_bytes(jobs, split_k, njobs) - GROUP_COUNTERS * sizeof(int);
+}
+// block-map entries a batch of these jobs can need at any geometry (an XCD's run is never longer than all units together)
+size_t plane_batch_map_capacity(const slnlp_gemm_args* jobs, const int* split_k, int njobs) {
+    size_t units = 0;
+    for (int i = 0; i < njobs; ++i) units += (size_t)ceil_div(jobs[i].M, 64) * ceil_div(jobs[i].N, 64) * std::max(split_k[i], 1);
+    return 8 * units + 8 * (size_t)njobs;
+}
+int plane_batch_build(const slnlp_gemm_args* jobs, const int* split_k, int njobs, void* scratch, size_t scratch_bytes, size_t map_capacity,
+                      PlaneBatch& out) {
+    out = PlaneBatch{};
+    if (njobs == 0) return 0;
+    SLNLP_CHECK_ARG(jobs && split_k && njobs > 0 && njobs <= PLACE_JOBS, "plane_batch: 1..%d jobs", PLACE_JOBS);
+    SLNLP_CHECK_ARG(scratch && (((uintptr_t)scratch) & 15) == 0, "plane_batch: needs a 16-byte aligned scratch buffer");
+    out.jobs.resize(njobs);
+    size_t ctr = 0, off = batch_counters(jobs, split_k, njobs) * sizeof(int);
+    auto family = [](int p) { return p == 2 ? 3 : p; };
+    for (int i = 0; i < njobs; ++i) {
+        const slnlp_gemm_args& a = jobs[i];
+        SLNLP_TRY(check_plane_job(a));
+        SLNLP_CHECK_ARG(a.precision != 8 && family(a.precision) == family(jobs[0].precision), "plane_batch: jobs of one launch share the precision family (not fp8)");
+        PlaneJob& j = out.jobs[i];
+        fill_plane_job(j, a, split_k[i], 0);
+        if (j.nks > 1) {
+            j.counters = reinterpret_cast<int*>(scratch) + ctr;
+            ctr += (size_t)j.tiles_x * j.tiles_y;
+            const size_t n256 = (size_t)ceil_div(a.N, 256) * 256, m256 = (size_t)ceil_div(a.M, 256) * 256;
+            j.part = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + off);
+            off += n256 * m256 * j.nks * sizeof(float);
+            j.part_rs = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + off);
+            off += m256 * j.nks * sizeof(float);
+        }
+    }
+    SLNLP_CHECK_ARG(off <= scratch_bytes, "plane_batch: scratch too small (%zu > %zu bytes)", off, scratch_bytes);
+    SLNLP_TRY(gemm_planes_init());
+    plane_merge_geometry(gemm_planes_kernel_ptr(jobs[0].precision, 0), out.jobs.data(), njobs, &out.fn, &out.lds);
+    for (int g = 0; g < NGEO; ++g)
+        if (out.fn == gemm_planes_kernel_ptr(jobs[0].precision, g)) out.geo = g;
+    const int placed = plane_merge_place(out.fn, out.jobs.data(), njobs, out.map);
+    SLNLP_CHECK_ARG(placed == 1, "plane_batch: more units than a block map entry can name");
+    SLNLP_CHECK_ARG(out.map.size() <= map_capacity, "plane_batch: block map of %zu entries, room for %zu", out.map.size(), map_capacity);
+    return 0;
+}
+int plane_batch_launch(const PlaneBatch& b, const PlaneJob* dev_tab, const int* dev_map, hipStream_t s) {
+    if (b.jobs.empty()) return 0;
+    SLNLP_CHECK_ARG(dev_tab && dev_map && !recording(), "plane_batch: needs its device tables; not for a lockstep recorder");
+    static const PlaneGroupParams none{};                     // (a table-driven launch reads no by-value job)
+    void* args[3];
+    args[0] = const_cast<PlaneGroupParams*>(&none); args[1] = &dev_tab; args[2] = &dev_map;
+    const int blocks = (int)b.map.size();
+    const int timed = launch_timer_begin(s);
+    if (hipLaunchKernel(b.fn, dim3(blocks), dim3(PTHREADS), args, b.lds, s) != hipSuccess) {
+        set_error("gemm_planes (batch): %s", hipGetErrorString(hipGetLastError()));
+        return SLNLP_ERR_LAUNCH;
+    }
+    if (timed >= 0) launch_timer_end(timed, s, blocks, (int)b.jobs.size(), b.geo);
+    return 0;
+}
+int plane_geo_forced() { return g_plane_geo.load(std::memory_order_relaxed); }
 
 template <int NSPLIT>
 static const void* kernel_of(int geo) {

@@ -302,7 +302,8 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
     const unsigned long long* rng = pl->buf.rng;
     const int64_t *X = pl->last_X, *y = pl->last_y;
     const bool up = pl->use_planes;
-    // Everything runs on the caller's stream; the weight gradient of each dY shares a launch with its data gradient.
+    // Everything runs on the caller's stream; the weight gradient of each dY shares a launch with its data gradient -- but the
+    // encoder's where the pair's launch would wait for it: those run in one batched launch behind the layer loop (tf_plan.hpp).
 
     // generator: logits = tfin lin_w^T + lin_b
     SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(w.dlogits, Vp, B, c.Vt, w.tfin, E, pl->G(L.lin_w), pl->G(L.lin_b)),
@@ -407,7 +408,6 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
         const EncP& q = L.enc[l];
         const EncA& a = w.enc[l];
         const float* x_in = l > 0 ? w.enc[l - 1].x2 : w.x0;
-        const PP& xp_in = l > 0 ? w.enc[l - 1].x2p : w.x0p;
         const PlaneOut none{};
         // LayerNorm backward also emits the bf16 planes of the gradient that feeds the sub-layer's GEMMs
         // (the dropout-masked copy when dropout is on, else dx itself)
@@ -418,10 +418,8 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
                                 (up && p > 0.f) ? a.d2p.out() : none));
         const float* d2 = p > 0.f ? a.gB2 : a.gA2;
         if (up) {
-            SLNLP_TRY(pl->wd_group(pl->wgrad_p_args(a.d2p, E, M, E, a.hp, F, pl->G(q.l2_w), pl->G(q.l2_b)),
-                                   pl->dgrad_p_args(a.d2p, E, M, E, q.l2_w, F, nullptr, a.h, ik, nullptr, &a.ghp), 0, st));
-            SLNLP_TRY(pl->wd_group(pl->wgrad_p_args(a.ghp, F, M, F, a.x1p, E, pl->G(q.l1_w), pl->G(q.l1_b)),
-                                   pl->dgrad_p_args(a.ghp, F, M, F, q.l1_w, E, a.gx1, nullptr, 0.f, a.gA2, nullptr), 0, st));
+            SLNLP_TRY(pl->enc_pair_launch(l, 0, B, ik, st));     // linear2: d h (ReLU-gated, planes only)
+            SLNLP_TRY(pl->enc_pair_launch(l, 1, B, ik, st));     // linear1: d x1 (+ the residual branch)
         } else {
             SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d2, E, M, E, a.h, F, pl->G(q.l2_w), pl->G(q.l2_b)),
                                      pl->dgrad_args(d2, E, M, E, pl->P(q.l2_w), F, a.gh, a.h, ik, nullptr), st));
@@ -433,11 +431,9 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
                                 (up && p > 0.f) ? a.d1p.out() : none));
         const float* d1 = p > 0.f ? a.gB1 : a.gA1;
         if (up) {
-            SLNLP_TRY(pl->wd_group(pl->wgrad_p_args(a.d1p, E, M, E, a.ctxp, E, pl->G(q.out_w), pl->G(q.out_b)),
-                                   pl->dgrad_p_args(a.d1p, E, M, E, q.out_w, E, a.gctx, nullptr, 0.f, nullptr, nullptr), 0, st));
+            SLNLP_TRY(pl->enc_pair_launch(l, 2, B, ik, st));     // out_proj: d ctx
             SLNLP_TRY(attn_self_bwd(a.qkv, a.probs, a.gctx, B, S, H, dh, S <= 64 ? nullptr : a.gqkv, p, pl->enc_site(l, 0), rng, st, a.gqkvp.out(), w.attn_scratch));
-            SLNLP_TRY(pl->wd_group(pl->wgrad_p_args(a.gqkvp, 3 * E, M, 3 * E, xp_in, E, pl->G(q.in_w), pl->G(q.in_b)),
-                                   pl->dgrad_p_args(a.gqkvp, 3 * E, M, 3 * E, q.in_w, E, a.gx0, nullptr, 0.f, a.gA1, nullptr), 0, st));
+            SLNLP_TRY(pl->enc_pair_launch(l, 3, B, ik, st));     // in_proj: d x0 (+ the residual branch)
         } else {
             SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d1, E, M, E, a.ctx, E, pl->G(q.out_w), pl->G(q.out_b)),
                                      pl->dgrad_args(d1, E, M, E, pl->P(q.out_w), E, a.gctx, nullptr, 0.f, nullptr), st));
@@ -447,6 +443,8 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
         }
         dx = a.gx0;
     }
+    // the weight gradients the loop left behind (tf_plan.hpp: enc_pair_launch), all in one launch; nothing below reads a dW
+    if (up && !recording()) SLNLP_TRY(plane_batch_launch(pl->wbatch, w.wb_tab, w.wb_map, st));
     SLNLP_TRY(embed_bwd(X, S, B, S, E, c.Vs, dx, pl->G(L.src_emb), sqrtf((float)E), -1, p, SITE_SRC_EMB, rng, w.emb_scratch_src, st, w.emb_keep));
     // every LayerNorm's (dgamma, dbeta): chunk sums in one launch, then the chunks added in order
     SLNLP_TRY(ln_param_partial(w.ln_ptable, nullptr, 5 * c.N + 2, E, M, B, c.B * c.S, c.B, st));
@@ -640,6 +638,27 @@ int slnlp_tf_tap(slnlp_tf_plan* pl, const char* name, float* out, int64_t max_fl
     else if (n == "memory") { src = pl->w.mem; rows = M; }
     else if (n == "logits") { src = pl->w.logits; rows = B; cols = c.Vt; ld = Vp; }
     else if (n == "dlogits") { src = pl->w.dlogits; rows = B; cols = c.Vt; ld = Vp; }
+    else if (n.rfind("enc", 0) == 0 && n.find('.') != std::string::npos) {
+        // "enc<l>.<planes>": an operand of the layer's gradient GEMMs as the bf16 planes the kernels read -- the hi plane's [rows, cols]
+        // 16-bit words, then the lo plane's, packed into rows * cols floats
+        const int l = atoi(name + 3);
+        SLNLP_CHECK_ARG(l >= 0 && l < c.N && pl->use_planes, "tf_tap: %s", name);
+        const EncA& a = pl->w.enc[l];
+        const std::string f = n.substr(n.find('.') + 1);
+        const PP* q = f == "d2p" ? &a.d2p : f == "hp" ? &a.hp : f == "ghp" ? &a.ghp : f == "x1p" ? &a.x1p : f == "d1p" ? &a.d1p : f == "ctxp" ? &a.ctxp :
+                      f == "gqkvp" ? &a.gqkvp : f == "x2p" ? &a.x2p : f == "xinp" ? (l > 0 ? &pl->w.enc[l - 1].x2p : &pl->w.x0p) : nullptr;
+        SLNLP_CHECK_ARG(q, "tf_tap: unknown tap '%s'", name);
+        cols = (f == "hp" || f == "ghp") ? c.F : f == "gqkvp" ? 3 * E : E;
+        const int64_t words = (int64_t)M * cols;
+        SLNLP_CHECK_ARG(words <= max_floats, "tf_tap: buffer too small (%ld needed)", (long)words);
+        if (hipMemcpyAsync(out, q->hi, words * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
+            hipMemcpyAsync(reinterpret_cast<char*>(out) + words * 2, q->lo, words * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+            set_error("tf_tap: copy failed");
+            return SLNLP_ERR_LAUNCH;
+        }
+        if (n_out) *n_out = words;
+        return 0;
+    }
     else if (n.rfind("enc", 0) == 0) { int l = atoi(name + 3); SLNLP_CHECK_ARG(l >= 0 && l < c.N, "tf_tap: %s", name); src = pl->w.enc[l].x2; rows = M; }
     else if (n.rfind("dec", 0) == 0) { int l = atoi(name + 3); SLNLP_CHECK_ARG(l >= 0 && l < c.N, "tf_tap: %s", name); src = pl->w.dec[l].t3; rows = B; }
     SLNLP_CHECK_ARG(src, "tf_tap: unknown tap '%s'", name);

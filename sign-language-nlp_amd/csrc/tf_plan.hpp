@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "gemm_jobs.hpp"
 #include "launch.hpp"
 
 namespace slnlp {
@@ -176,6 +177,13 @@ struct Ws {
     float* attn_scratch;    // S > 64: dS of one self-attention backward ([B,H,S,S], shared by all layers)
     char* gscr[1];          // split-K scratch of the grouped GEMM launches (one stream: one scratch)
     size_t gscr_bytes;
+    // the encoder's deferred weight gradients (one batched launch per backward, slnlp_tf_plan::wbatch): device job table and block
+    // map, and the batch's own split-K scratch (a region per job: all of them are in flight at once)
+    PlaneJob* wb_tab;
+    int* wb_map;
+    size_t wb_map_cap;
+    char* wb_scr;
+    size_t wb_scr_bytes;
     slnlp_ln_reduce_entry* ln_table;
     LnPartialEntry* ln_ptable;   // the same LayerNorms' (dy, x, stats, partial) for the one ln_param_partial launch of a backward
     size_t bytes;
@@ -186,6 +194,16 @@ constexpr int MAX_SPLITK = WD_MAX_SPLITK;
 static int splitk_for(int T) {
     const int n = ((T + 63) / 64 + 5) / 10;
     return n < 1 ? 1 : n > MAX_SPLITK ? MAX_SPLITK : n;
+}
+
+// The four Linear layers of an encoder layer in the order backward meets them (linear2, linear1, out_proj, in_proj): the shapes of
+// the gradient pair of dY [tokens, nout] against x [tokens, kin] -- all the deferral rule (gemm_planes_wd_defer) looks at
+static void enc_pair_shapes(const slnlp_tf_config& c, int k, int tokens, slnlp_gemm_args* wg, slnlp_gemm_args* dg) {
+    const int nout = k == 1 ? c.F : k == 3 ? 3 * c.E : c.E, kin = k == 0 ? c.F : c.E;
+    memset(wg, 0, sizeof(*wg));
+    memset(dg, 0, sizeof(*dg));
+    wg->M = nout; wg->N = kin; wg->K = tokens; wg->precision = 3;
+    dg->M = tokens; dg->N = kin; dg->K = nout; dg->precision = 3;
 }
 
 static Ws carve(const slnlp_tf_config& c, void* base) {
@@ -288,6 +306,22 @@ static Ws carve(const slnlp_tf_config& c, void* base) {
     w.attn_scratch = c.S > 64 ? (float*)b.take<char>(attn_long_scratch_bytes(c.B, c.S, c.H)) : nullptr;
     w.ln_table = b.take<slnlp_ln_reduce_entry>(5 * c.N + 2);
     w.ln_ptable = b.take<LnPartialEntry>(5 * c.N + 2);
+    // the batched weight-gradient launch: every (layer, Linear) whose pair defers its weight gradient at SOME batch size 1..B, with
+    // the largest split factor it takes there -- room for the tables and the scratch of whichever batch size comes
+    std::vector<slnlp_gemm_args> wb_jobs;
+    std::vector<int> wb_split;
+    for (int k = 0; k < 4 && (E % 64 == 0) && (F % 64 == 0); ++k) {
+        slnlp_gemm_args wg, dg;
+        int split = 0;
+        for (size_t bb = 1; bb <= B; ++bb) {
+            enc_pair_shapes(c, k, (int)(bb * S), &wg, &dg);
+            split = std::max(split, gemm_planes_wd_defer(wg, dg));
+        }
+        for (int i = 0; i < c.N && split > 0; ++i) { wb_jobs.push_back(wg); wb_split.push_back(split); }
+    }
+    w.wb_map_cap = wb_jobs.empty() ? 0 : plane_batch_map_capacity(wb_jobs.data(), wb_split.data(), (int)wb_jobs.size());
+    w.wb_tab = b.take<PlaneJob>(wb_jobs.size());
+    w.wb_map = b.take<int>(w.wb_map_cap);
     // ---- bf16 operand planes (only used when E and F are multiples of 64)
     const size_t Mp = (M + 63) / 64 * 64;
     const bool q8 = c.precision == 8;
@@ -336,6 +370,8 @@ static Ws carve(const slnlp_tf_config& c, void* base) {
         w.gscr_bytes = 16384 + nx * ny * MAX_SPLITK * sizeof(float) + ny * MAX_SPLITK * sizeof(float);
         w.gscr_bytes = (w.gscr_bytes + 255) & ~(size_t)255;
         w.gscr[0] = b.take<char>(w.gscr_bytes);
+        w.wb_scr_bytes = wb_jobs.empty() ? 0 : (plane_batch_scratch_bytes(wb_jobs.data(), wb_split.data(), (int)wb_jobs.size()) + 255) & ~(size_t)255;
+        w.wb_scr = b.take<char>(w.wb_scr_bytes);
     }
     b.cur = (b.cur + 255) & ~(size_t)255;
     w.planes_end = b.base + b.cur;
@@ -613,14 +649,83 @@ struct slnlp_tf_plan {
     int wd_group(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg, int which_scratch, hipStream_t st) const {
         return gemm_planes_wd(wg, dg, w.gscr[which_scratch], w.gscr_bytes, st);      // (split factor, one launch or two: gemm_planes.hip)
     }
-    // zero padding of the activation planes is per batch size: re-zero when it changes (outside any capture)
-    int prepare_planes(int B, hipStream_t st) {
-        if (!use_planes || B == planes_B) return 0;
-        if (hipMemsetAsync(w.planes_begin, 0, (size_t)(w.planes_end - w.planes_begin), st) != hipSuccess) {
-            set_error("tf: zeroing operand planes failed");
+    // ---- the encoder's weight gradients off the chain.  Backward is one dependent chain of launches, and a pair's launch ends with
+    // its longest workgroup: at these shapes a weight-gradient slice, whose result nothing reads before the optimizer.  Where the
+    // shapes say so (gemm_planes_wd_defer) the chain carries the data gradient alone and the layer loop is followed by ONE launch
+    // of all deferred weight gradients (plane_batch_*): throughput-sized tiles, a job's panels in one XCD's L2, the split factor --
+    // hence every sum -- of the pair's launch.  Every operand is still intact then (each gradient buffer is written once per
+    // step).  Under a lockstep recorder the pairs stay together: merged launches are throughput-sized already.
+    // Pair k (linear2, linear1, out_proj, in_proj: the order backward meets them) of encoder layer l at batch size B
+    void enc_pair(int l, int k, int B, float ik, slnlp_gemm_args* wg, slnlp_gemm_args* dg) const {
+        const int E = cfg.E, F = cfg.F, M = cfg.S * B;
+        const EncP& q = L.enc[l];
+        const EncA& a = w.enc[l];
+        if (k == 0) {
+            *wg = wgrad_p_args(a.d2p, E, M, E, a.hp, F, G(q.l2_w), G(q.l2_b));
+            *dg = dgrad_p_args(a.d2p, E, M, E, q.l2_w, F, nullptr, a.h, ik, nullptr, &a.ghp);
+        } else if (k == 1) {
+            *wg = wgrad_p_args(a.ghp, F, M, F, a.x1p, E, G(q.l1_w), G(q.l1_b));
+            *dg = dgrad_p_args(a.ghp, F, M, F, q.l1_w, E, a.gx1, nullptr, 0.f, a.gA2, nullptr);
+        } else if (k == 2) {
+            *wg = wgrad_p_args(a.d1p, E, M, E, a.ctxp, E, G(q.out_w), G(q.out_b));
+            *dg = dgrad_p_args(a.d1p, E, M, E, q.out_w, E, a.gctx, nullptr, 0.f, nullptr, nullptr);
+        } else {
+            *wg = wgrad_p_args(a.gqkvp, 3 * E, M, 3 * E, l > 0 ? w.enc[l - 1].x2p : w.x0p, E, G(q.in_w), G(q.in_b));
+            *dg = dgrad_p_args(a.gqkvp, 3 * E, M, 3 * E, q.in_w, E, a.gx0, nullptr, 0.f, a.gA1, nullptr);
+        }
+    }
+    PlaneBatch wbatch;                  // the deferred jobs of a backward at batch size wbatch_B (device copies: w.wb_tab, w.wb_map)
+    std::vector<char> wb_deferred;      // [4 l + k]: the pair's weight gradient is a job of the batch
+    std::vector<int> wb_map_host;       // the block map as uploaded (padded to the device map's size)
+    int wbatch_B = -1, wbatch_geo = -2; // batch size / forced tile geometry (plane_geo_forced) the tables were built for
+    // every pointer in the tables is the plan's own: they change with the batch size alone (K = tokens, hence split factors and
+    // scratch regions) -- rebuilt where the planes' padding is re-zeroed, outside any capture
+    int build_wbatch(int B, hipStream_t st) {
+        std::vector<slnlp_gemm_args> jobs;
+        std::vector<int> split;
+        wb_deferred.assign(4 * (size_t)cfg.N, 0);
+        for (int l = cfg.N - 1; l >= 0; --l)
+            for (int k = 0; k < 4; ++k) {
+                slnlp_gemm_args wg, dg;
+                enc_pair(l, k, B, 1.f, &wg, &dg);
+                const int n = gemm_planes_wd_defer(wg, dg);
+                if (n == 0) continue;
+                wb_deferred[4 * l + k] = 1;
+                jobs.push_back(wg);
+                split.push_back(n);
+            }
+        SLNLP_TRY(plane_batch_build(jobs.data(), split.data(), (int)jobs.size(), w.wb_scr, w.wb_scr_bytes, w.wb_map_cap, wbatch));
+        wbatch_B = B;
+        wbatch_geo = plane_geo_forced();
+        if (wbatch.jobs.empty()) return 0;
+        // the whole map travels, padding (-1: no work) to its end: a launch sized for another geometry's map stays inside it
+        wb_map_host = wbatch.map;
+        wb_map_host.resize(w.wb_map_cap, -1);
+        if (hipMemcpyAsync(w.wb_tab, wbatch.jobs.data(), wbatch.jobs.size() * sizeof(PlaneJob), hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(w.wb_map, wb_map_host.data(), wb_map_host.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) {
+            set_error("tf: uploading the weight-gradient batch tables failed: %s", hipGetErrorString(hipGetLastError()));
             return SLNLP_ERR_LAUNCH;
         }
-        planes_B = B;
+        return 0;
+    }
+    bool wb_defers(int l, int k) const { return !recording() && !wb_deferred.empty() && wb_deferred[4 * l + k]; }
+    // pair k of encoder layer l on the chain: the data gradient alone where the weight gradient is a job of the batch
+    int enc_pair_launch(int l, int k, int B, float ik, hipStream_t st) const {
+        slnlp_gemm_args wg, dg;
+        enc_pair(l, k, B, ik, &wg, &dg);
+        return wb_defers(l, k) ? gemm(dg, st) : wd_group(wg, dg, 0, st);
+    }
+    // zero padding of the activation planes is per batch size: re-zero when it changes (outside any capture)
+    int prepare_planes(int B, hipStream_t st) {
+        if (!use_planes) return 0;
+        if (B != planes_B) {
+            if (hipMemsetAsync(w.planes_begin, 0, (size_t)(w.planes_end - w.planes_begin), st) != hipSuccess) {
+                set_error("tf: zeroing operand planes failed");
+                return SLNLP_ERR_LAUNCH;
+            }
+            planes_B = B;
+        }
+        if (B != wbatch_B || plane_geo_forced() != wbatch_geo) SLNLP_TRY(build_wbatch(B, st));
         return 0;
     }
     int forward_impl(const int64_t* X, const int64_t* y, int B, int train, float* logp_out, hipStream_t st);
