@@ -287,6 +287,16 @@ int slnlp_clip_adam_step(float* params, const float* grads, float* exp_avg, floa
                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                          float* partials /* [1024] scratch */, float* norm_out, float* step_count, void* stream);
 
+/* -------------------------------------------------------------- batch gather --
+ * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
+ * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.
+ * lengths and len_out are both NULL or both given.  B x S ids to X_out, B entries to len_out / y_out.  One launch: a wave
+ * moves a row, so loads and stores are whole lines.  The indices (and row0 + B against the order's length) are the
+ * caller's contract, like every pointer here.  Everything a fit stages that is not a lockstep group goes through this:
+ * the eager step, the staging buffers of a captured graph, the torch-stepped loop. */
+int slnlp_gather_batch(const int64_t* X, const int64_t* lengths, const int64_t* y, const int64_t* order, int64_t row0,
+                       int B, int S, int64_t* X_out, int64_t* len_out, int64_t* y_out, void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);
@@ -575,6 +585,15 @@ int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* group, float* const* exp_avg_s
  * step_index >= n_steps is an argument error (nothing is launched).  Eval steps never touch buf.lr.  Drops no recorded program.
  * The pointer table's upload is ordered on `stream`, as set_data's. */
 int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* group, const float* const* table, int n_steps, void* stream);
+/* per-fit visit order of one data slot (a shuffled epoch): order[f] = n_visit int64 row indices into fit f's dataset of that
+ * slot, in device memory of the caller (kept alive while set); a NULL entry leaves that fit in dataset order, a NULL `order`
+ * clears the setting for the slot.  n_visit (1 .. rows) is one number for the group.  From then on a step of that slot stages
+ * row order[f][row0 + i] instead of row row0 + i -- ids, label and, for RNN fits, length -- with row0 + B <= n_visit, and
+ * slnlp_tf_lockstep_epoch walks [0, n_visit).  Log-probs and batch losses keep landing at VISIT position (logp[f][row0 ..],
+ * loss[f][step_index]).  Only the gather launch reads the table: no recorded program is dropped or re-recorded and
+ * num_launches does not change.  The indices are the caller's contract.  set_data on the slot clears its order.  The pointer
+ * table's upload is ordered on `stream`, as set_lr_table's. */
+int slnlp_tf_lockstep_set_order(slnlp_tf_lockstep* group, int slot, const int64_t* const* order, int64_t n_visit, void* stream);
 int slnlp_tf_lockstep_set_destroy_sync(slnlp_tf_lockstep* group, int on);   /* as slnlp_tf_set_destroy_sync, for the group's tables */
 
 
@@ -655,6 +674,7 @@ int slnlp_rnn_lockstep_num_launches(slnlp_rnn_lockstep* group, int slot, int B, 
 int slnlp_rnn_lockstep_set_adam(slnlp_rnn_lockstep* group, float* const* exp_avg_sq, float beta1, float beta2, float eps,
                                 float weight_decay);
 int slnlp_rnn_lockstep_set_lr_table(slnlp_rnn_lockstep* group, const float* const* table, int n_steps, void* stream);
+int slnlp_rnn_lockstep_set_order(slnlp_rnn_lockstep* group, int slot, const int64_t* const* order, int64_t n_visit, void* stream);
 int slnlp_rnn_lockstep_set_destroy_sync(slnlp_rnn_lockstep* group, int on);
 
 #ifdef __cplusplus

@@ -83,6 +83,26 @@ __device__ __forceinline__ void probe_kernel_end() {
 #endif
 }
 
+// ------------------------------------------------- batches through an order table ----
+// Stage B rows of an int64 [rows, S] dataset in visit order (a shuffled epoch: slnlp_gather_batch, ls_gather_kernel):
+// out[r] = X[order ? order[r] : first + r].  The unit of contiguity is a row (384 bytes at S = 48), so ONE WAVE takes a row:
+// consecutive lanes move consecutive ids (whole-line loads and stores) and order[r] -- wave-uniform, the wave index comes from
+// readfirstlane -- is read once per row.  Blocks of 256 threads, any grid.x; `order` already points at the batch's first
+// entry.  The indices are the caller's contract (the host wrappers check them before upload).
+__device__ __forceinline__ void gather_id_rows(const int64_t* __restrict__ X, const int64_t* __restrict__ order, long first, int B, int S,
+                                               int64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int nwaves = gridDim.x * 4;
+    for (int r = wave; r < B; r += nwaves) {
+        const int64_t* src = X + (order ? order[r] : first + r) * S;
+        int64_t* dst = out + (long)r * S;
+        for (int c = lane; c < S; c += 64) dst[c] = src[c];
+    }
+}
+// blocks of 256 threads that give every row of a B-row batch a wave of its own (at most 64 of them: the waves loop)
+static inline int gather_rows_grid(int B) { return B >= 256 ? 64 : (B + 3) / 4; }
+
 // ------------------------------------------------------------- dropout ------
 // Counter-based Threefry4x32-12 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11 -- the
 // 12-round form is the shortest Threefry-4x32 the paper reports as passing BigCrush; known-answer vectors of the 20-round form

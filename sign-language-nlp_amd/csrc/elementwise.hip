@@ -1178,6 +1178,23 @@ __global__ void dropout_mask_kernel(float* out, int R, int C, unsigned thr, int 
     }
 }
 
+// ============================================================== batch gather
+// One batch of a solo fit in visit order: the row kernel of common.hpp for the ids, block 0 for the labels and lengths.
+__global__ __launch_bounds__(256) void gather_batch_kernel(const int64_t* __restrict__ X, const int64_t* __restrict__ lengths,
+                                                           const int64_t* __restrict__ y, const int64_t* __restrict__ order, long row0,
+                                                           int B, int S, int64_t* __restrict__ X_out, int64_t* __restrict__ len_out,
+                                                           int64_t* __restrict__ y_out) {
+    if (order) order += row0;
+    gather_id_rows(X, order, row0, B, S, X_out);
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < B; i += 256) {
+            const int64_t r = order ? order[i] : row0 + i;
+            y_out[i] = y[r];
+            if (lengths) len_out[i] = lengths[r];
+        }
+    }
+}
+
 }  // namespace slnlp
 
 extern "C" {
@@ -1248,6 +1265,16 @@ int slnlp_clip_adam_step(float* params, const float* grads, float* exp_avg, floa
                          float* step_count, void* stream) {
     return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
                                  norm_out, nullptr, step_count, (hipStream_t)stream);
+}
+int slnlp_gather_batch(const int64_t* X, const int64_t* lengths, const int64_t* y, const int64_t* order, int64_t row0, int B, int S,
+                       int64_t* X_out, int64_t* len_out, int64_t* y_out, void* stream) {
+    SLNLP_CHECK_ARG(X && y && X_out && y_out, "slnlp_gather_batch: null X, y, X_out or y_out");
+    SLNLP_CHECK_ARG((lengths != nullptr) == (len_out != nullptr), "slnlp_gather_batch: lengths and len_out go together");
+    SLNLP_CHECK_ARG(B > 0 && S > 0 && row0 >= 0, "slnlp_gather_batch: B %d, S %d, row0 %ld", B, S, (long)row0);
+    hipLaunchKernelGGL(slnlp::gather_batch_kernel, dim3(slnlp::gather_rows_grid(B)), dim3(256), 0, (hipStream_t)stream, X, lengths, y, order,
+                       (long)row0, B, S, X_out, len_out, y_out);
+    SLNLP_CHECK_LAUNCH("slnlp_gather_batch");
+    return 0;
 }
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site, const unsigned long long* rng, void* stream) {
     if (!out || !rng || R <= 0 || C <= 0 || p < 0.f || p >= 1.f) {

@@ -26,6 +26,11 @@
 // Learning-rate tables (slnlp_*_lockstep_set_lr_table): a per-batch schedule cannot come from the host inside an epoch that
 // never synchronises, so the same gather launch also stores table[f][batch index] into fit f's lr scalar (the float the
 // recorded update launches read through the pointer they always had) ahead of every TRAIN step.
+//
+// Order tables (slnlp_*_lockstep_set_order): a shuffled epoch visits the rows of a slot in an order the host drew before the
+// epoch (torch's RandomSampler, slnlp/sampler.py).  The gather launch then stages row order[f][row0 + i] instead of row
+// row0 + i -- ids, label and length -- and everything behind it (the recorded programs, where log-probs and losses land) is
+// what it was: outputs stay at VISIT position row0, so the caller pairs them with the labels in visit order.
 #include <map>
 #include <tuple>
 
@@ -59,11 +64,12 @@ struct GatherArgs {
     int* dyn;                    // {row0, batch index}
     const float* const* lr_table;   // [K] per-fit learning rates by batch index (device table; entries may be nullptr), or nullptr
     float* const* lr;               // [K] each fit's lr scalar (device table)
+    const int64_t* const* order;    // [K] per-fit visit order of the slot, n_visit row indices (device table; entries may be nullptr), or nullptr
     int S, row0, B, step;
 };
 
-__global__ __launch_bounds__(256) void ls_gather_kernel(const GatherArgs a) {
-    const int f = blockIdx.z;
+// rows [row0, row0 + B) of fit f's dataset, as they lie: one thread per int64, consecutive threads walk one contiguous block
+__device__ __forceinline__ void ls_gather_dataset_order(const GatherArgs& a, int f) {
     const int64_t* X = a.X[f] + (long)a.row0 * a.S;
     int64_t* Xs = a.Xst[f];
     const int n = a.B * a.S;
@@ -77,6 +83,32 @@ __global__ __launch_bounds__(256) void ls_gather_kernel(const GatherArgs a) {
             int64_t* ls = a.Lst[f];
             for (int i = threadIdx.x; i < a.B; i += 256) ls[i] = l[i];
         }
+    }
+}
+
+// rows ord[0 .. B) of fit f's dataset (ord: the fit's order table at the batch's first visit): a wave per row (common.hpp)
+__device__ __forceinline__ void ls_gather_visit_order(const GatherArgs& a, int f, const int64_t* __restrict__ ord) {
+    gather_id_rows(a.X[f], ord, 0, a.B, a.S, a.Xst[f]);
+    if (blockIdx.x == 0) {
+        const int64_t* y = a.y[f];
+        int64_t* ys = a.yst[f];
+        for (int i = threadIdx.x; i < a.B; i += 256) ys[i] = y[ord[i]];
+        if (a.len) {
+            const int64_t* l = a.len[f];
+            int64_t* ls = a.Lst[f];
+            for (int i = threadIdx.x; i < a.B; i += 256) ls[i] = l[ord[i]];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ls_gather_kernel(const GatherArgs a) {
+    const int f = blockIdx.z;
+    const int64_t* ord = a.order ? a.order[f] : nullptr;
+    if (ord)
+        ls_gather_visit_order(a, f, ord + a.row0);
+    else
+        ls_gather_dataset_order(a, f);
+    if (blockIdx.x == 0) {
         if (f == 0 && threadIdx.x == 0) {
             a.dyn[0] = a.row0;
             a.dyn[1] = a.step;
@@ -137,6 +169,9 @@ struct LockstepGroup {
     struct Slot {
         bool set = false;
         int64_t rows = 0;
+        // slnlp_*_lockstep_set_order: the slot's pointer table [K] (below ws_mark, rewritten in place) and how many rows a pass visits
+        const int64_t** d_order = nullptr;
+        int64_t n_visit = 0;                        // 0: no order set, a pass walks the slot's rows as they lie
         const int64_t** d_X = nullptr;              // device tables [K]
         const int64_t** d_y = nullptr;
         const int64_t** d_len = nullptr;
@@ -354,6 +389,10 @@ static int ls_init(LockstepGroup* ls, int B, int S, void* workspace, int64_t wor
     SLNLP_TRY(upload(ls, lr.data(), K * sizeof(void*), (void**)&ls->d_lr, st));
     ls->d_lr_table = (const float**)ls->take(K * sizeof(void*));
     SLNLP_CHECK_ARG(ls->d_lr_table, "lockstep_create: workspace too small");
+    for (int k = 0; k < LS_SLOTS; ++k) {
+        ls->slot[k].d_order = (const int64_t**)ls->take(K * sizeof(void*));
+        SLNLP_CHECK_ARG(ls->slot[k].d_order, "lockstep_create: workspace too small");
+    }
     ls->ws_mark = ls->ws_used;
     return 0;
 }
@@ -378,6 +417,7 @@ static int ls_set_data(LockstepGroup* ls, int slot, const int64_t* const* X, con
     for (auto it = ls->programs.begin(); it != ls->programs.end();)     // programs of this slot baked the old output pointers
         it = std::get<0>(it->first) == slot ? ls->programs.erase(it) : std::next(it);
     s.rows = rows;
+    s.n_visit = 0;                                  // an order table indexes the data it was set for
     s.logp.assign(logp, logp + ls->K);
     s.loss.assign(loss, loss + ls->K);
     s.hX.assign(X, X + ls->K);
@@ -422,14 +462,38 @@ static int ls_set_lr_table(LockstepGroup* ls, const float* const* table, int n_s
     return 0;
 }
 
+// order[f]: n_visit row indices of fit f's dataset in slot `slot` (device memory of the caller), the rows a pass visits and in
+// which order; nullptr: that fit walks its rows as they lie; order == nullptr: no order for the slot any more.  No recorded
+// program is touched: only the gather launch reads the table.  The copy is ordered on `st` as ls_set_lr_table's is.
+static int ls_set_order(LockstepGroup* ls, int slot, const int64_t* const* order, int64_t n_visit, hipStream_t st) {
+    SLNLP_CHECK_ARG(ls && slot >= 0 && slot < LS_SLOTS, "lockstep_set_order: bad group or slot %d", slot);
+    LockstepGroup::Slot& s = ls->slot[slot];
+    if (!order) {
+        s.n_visit = 0;
+        return 0;
+    }
+    SLNLP_CHECK_ARG(s.set, "lockstep_set_order: slot %d has no data", slot);
+    SLNLP_CHECK_ARG(n_visit >= 1 && n_visit <= s.rows, "lockstep_set_order: n_visit %ld outside 1..%ld (the slot's rows)", (long)n_visit,
+                    (long)s.rows);
+    if (hipMemcpyAsync(s.d_order, order, ls->K * sizeof(void*), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {       // pageable host memory: as upload()
+        set_error("lockstep_set_order: table upload failed: %s", hipGetErrorString(hipGetLastError()));
+        s.n_visit = 0;
+        return SLNLP_ERR_LAUNCH;
+    }
+    s.n_visit = n_visit;
+    return 0;
+}
+
 // One lockstep step of every fit on rows [row0, row0 + B) of slot `slot`: train != 0 -> forward + criterion + backward +
 // clip + SGD (what slnlp_{tf,rnn}_train_step does for one fit), else an eval-mode forward + criterion.
 static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_index, int train, float momentum, float max_norm,
                    hipStream_t st) {
     SLNLP_CHECK_ARG(ls && slot >= 0 && slot < LS_SLOTS && ls->slot[slot].set, "lockstep_step: slot %d has no data", slot);
     LockstepGroup::Slot& s = ls->slot[slot];
-    SLNLP_CHECK_ARG(B > 0 && B <= ls->maxB && row0 >= 0 && row0 + B <= s.rows, "lockstep_step: rows [%ld, %ld) outside 0..%ld or batch > %d",
-                    (long)row0, (long)(row0 + B), (long)s.rows, ls->maxB);
+    const int64_t visit = s.n_visit ? s.n_visit : s.rows;      // with an order table row0 counts visits
+    SLNLP_CHECK_ARG(B > 0 && B <= ls->maxB && row0 >= 0 && row0 + B <= visit, "lockstep_step: rows [%ld, %ld) outside 0..%ld or batch > %d",
+                    (long)row0, (long)(row0 + B), (long)visit, ls->maxB);
     SLNLP_CHECK_ARG(!train || !ls->lr_steps || (step_index >= 0 && step_index < ls->lr_steps),
                     "lockstep_step: batch index %d outside the learning-rate tables' %d steps", step_index, ls->lr_steps);
     StepScope scope(st);               // one kernel sequence per device (launch.hpp)
@@ -478,9 +542,11 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     g.Xst = ls->d_Xst; g.yst = ls->d_yst; g.Lst = ls->d_Lst; g.dyn = ls->dyn;
     g.lr_table = train && ls->lr_steps ? ls->d_lr_table : nullptr;      // eval steps never touch the learning rate
     g.lr = ls->d_lr;
+    g.order = s.n_visit ? s.d_order : nullptr;
     g.S = ls->S; g.row0 = (int)row0; g.B = B; g.step = step_index;
     int gx = (B * ls->S + 255) / 256;
     if (gx > 64) gx = 64;
+    if (g.order) gx = std::max(gx, gather_rows_grid(B));                // a wave per row for the fits that have a table
     hipLaunchKernelGGL(ls_gather_kernel, dim3(gx, 1, ls->K), dim3(256), 0, st, g);
     SLNLP_CHECK_LAUNCH("lockstep gather");
     SLNLP_TRY(replay(it->second, st));
@@ -488,10 +554,11 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     return 0;
 }
 
-// One pass over slot `slot` in dataset order, batches of `batch` rows (the last one may be shorter).
+// One pass over slot `slot` -- in dataset order, or the n_visit rows of the slot's order tables -- in batches of `batch` rows
+// (the last one may be shorter).
 static int ls_epoch(LockstepGroup* ls, int slot, int batch, int train, float momentum, float max_norm, hipStream_t st) {
     SLNLP_CHECK_ARG(ls && slot >= 0 && slot < LS_SLOTS && ls->slot[slot].set && batch > 0, "lockstep_epoch: bad arguments");
-    const int64_t rows = ls->slot[slot].rows;
+    const int64_t rows = ls->slot[slot].n_visit ? ls->slot[slot].n_visit : ls->slot[slot].rows;
     int step = 0;
     for (int64_t r = 0; r < rows; r += batch, ++step) {
         const int B = (int)(rows - r < batch ? rows - r : batch);
@@ -564,8 +631,8 @@ static unsigned tf_opts_gen(void* p) { return ((slnlp_tf_plan*)p)->opts.gen; }
 static float* rnn_lr(void* p) { return rnn_ls_lr((slnlp_rnn_plan*)p); }
 static float* tf_lr(void* p) { return ((slnlp_tf_plan*)p)->buf.lr; }
 
-// the two learning-rate pointer tables of ls_init, each on a 256-byte boundary of the bump allocator
-static size_t ls_lr_table_bytes(int K) { return 2 * (((size_t)K * sizeof(void*) + 255) & ~(size_t)255); }
+// the two learning-rate pointer tables of ls_init and the slots' order tables, each on a 256-byte boundary of the bump allocator
+static size_t ls_lr_table_bytes(int K) { return (2 + LS_SLOTS) * (((size_t)K * sizeof(void*) + 255) & ~(size_t)255); }
 
 extern "C" {
 
@@ -635,6 +702,9 @@ int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* ls, float* const* exp_avg_sq, 
 int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* ls, const float* const* table, int n_steps, void* stream) {
     return ls_set_lr_table(ls, table, n_steps, (hipStream_t)stream);
 }
+int slnlp_tf_lockstep_set_order(slnlp_tf_lockstep* ls, int slot, const int64_t* const* order, int64_t n_visit, void* stream) {
+    return ls_set_order(ls, slot, order, n_visit, (hipStream_t)stream);
+}
 int slnlp_tf_lockstep_set_destroy_sync(slnlp_tf_lockstep* ls, int on) {
     SLNLP_CHECK_ARG(ls, "lockstep_set_destroy_sync: null group");
     ls->destroy_sync = on ? 1 : 0;
@@ -699,6 +769,9 @@ int slnlp_rnn_lockstep_set_adam(slnlp_rnn_lockstep* ls, float* const* exp_avg_sq
 }
 int slnlp_rnn_lockstep_set_lr_table(slnlp_rnn_lockstep* ls, const float* const* table, int n_steps, void* stream) {
     return ls_set_lr_table(ls, table, n_steps, (hipStream_t)stream);
+}
+int slnlp_rnn_lockstep_set_order(slnlp_rnn_lockstep* ls, int slot, const int64_t* const* order, int64_t n_visit, void* stream) {
+    return ls_set_order(ls, slot, order, n_visit, (hipStream_t)stream);
 }
 int slnlp_rnn_lockstep_set_destroy_sync(slnlp_rnn_lockstep* ls, int on) {
     SLNLP_CHECK_ARG(ls, "rnn_lockstep_set_destroy_sync: null group");

@@ -118,6 +118,7 @@ SIGNATURES = {
     "slnlp_clip_sgd_step_ex": (i32, [vp, vp, vp, i64, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_clip_adamw_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
+    "slnlp_gather_batch": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
     "slnlp_rnn_cell_fwd": (i32, [i32, C.POINTER(RnnCellDir), i32, i32, i32, vp, f32, i64, f32, i32, vp, vp]),
     "slnlp_rnn_layer_fwd": (i32, [i32, C.POINTER(RnnLayerDir), i32, i32, i32, i32, vp, f32, i64, f32, i32, vp, i32, vp,
                                   C.POINTER(i32), vp]),
@@ -187,6 +188,7 @@ SIGNATURES = {
     "slnlp_tf_lockstep_num_launches": (i32, [vp, i32, i32, i32]),
     "slnlp_tf_lockstep_set_adam": (i32, [vp, vp, f32, f32, f32, f32]),
     "slnlp_tf_lockstep_set_lr_table": (i32, [vp, vp, i32, vp]),
+    "slnlp_tf_lockstep_set_order": (i32, [vp, i32, vp, i64, vp]),
     "slnlp_tf_lockstep_set_destroy_sync": (i32, [vp, i32]),
     "slnlp_rnn_lockstep_workspace_bytes": (i64, [vp, i32]),
     "slnlp_rnn_lockstep_create": (i32, [vp, i32, vp, i64, vp, vp]),
@@ -197,6 +199,7 @@ SIGNATURES = {
     "slnlp_rnn_lockstep_num_launches": (i32, [vp, i32, i32, i32]),
     "slnlp_rnn_lockstep_set_adam": (i32, [vp, vp, f32, f32, f32, f32]),
     "slnlp_rnn_lockstep_set_lr_table": (i32, [vp, vp, i32, vp]),
+    "slnlp_rnn_lockstep_set_order": (i32, [vp, i32, vp, i64, vp]),
     "slnlp_rnn_lockstep_set_destroy_sync": (i32, [vp, i32]),
 }
 

@@ -16,7 +16,9 @@ artefacts into ``workdir``:
 What replaces what: dask workers -> one process per GPU (``ShardedGridSearchCV``); commons-python's argument loader
 -> PyYAML + argparse; torchtext / imblearn -> ``slnlp.ingest`` / ``slnlp.balance``; the torch profiler dump is not
 reproduced.  ``dataset_args.synthetic: {n: ..}`` (not in the reference) generates an ASL-Phono-shaped dataset when
-the corpus is not on the machine.
+the corpus is not on the machine.  ``iterator_train_args: {shuffle: true, drop_last: false}`` (the reference hard-codes its
+iterator arguments, helper.py:73-83, with ``shuffle`` commented out) becomes ``iterator_train__*``; in ``grid_args`` it is a grid
+axis.  Configs without the key behave as before.
 """
 import argparse
 import copy
@@ -28,7 +30,7 @@ import os
 import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
-             "criterion_args", "grid_args")
+             "criterion_args", "iterator_train_args", "grid_args")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -85,12 +87,13 @@ def prefix_args(prefix, ensure_list=False, output=None, **kwargs):
 
 def build_param_grid(grid_args):
     """helper.py:108-180 ``build_grid_params``: model_args -> module__*, optimizer_args -> optimizer__*,
-    criterion_args -> criterion__*, everything else (lr, ...) by its own name."""
+    criterion_args -> criterion__*, iterator_train_args -> iterator_train__*, everything else (lr, ...) by its own name."""
     g = dict(grid_args or {})
     grid = {}
     grid.update(prefix_args("module", ensure_list=True, **(g.pop("model_args", None) or {})))
     grid.update(prefix_args("optimizer", ensure_list=True, **(g.pop("optimizer_args", None) or {})))
     grid.update(prefix_args("criterion", ensure_list=True, **(g.pop("criterion_args", None) or {})))
+    grid.update(prefix_args("iterator_train", ensure_list=True, **(g.pop("iterator_train_args", None) or {})))
     g.pop("training_args", None)
     grid.update(prefix_args(None, ensure_list=True, **g))
     return grid
@@ -115,6 +118,7 @@ def build_net_params(args, dataset, device):
     p.update(prefix_args("module", batch_first=True, src_vocab=dataset.vocab_X, tgt_vocab=dataset.vocab_y, **model_args))
     p.update(prefix_args("optimizer", **(args.get("optimizer_args") or {})))
     p.update(prefix_args("criterion", **crit))
+    p.update(prefix_args("iterator_train", **(args.get("iterator_train_args") or {})))
     return p
 
 

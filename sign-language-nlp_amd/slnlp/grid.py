@@ -82,9 +82,11 @@ def build_tasks(param_grid, y, cv, seq_len=48, defaults=None):
 
 # per-fit settings that change no launch sequence: candidates that differ only in these share a lockstep unit (the criterion
 # settings, SGD's settings and the Adam / AdamW weight decay ride each fit's own argument packs, csrc/lockstep.hip; a learning-rate
-# schedule is host work per epoch, and per batch a device table per fit that the step's gather launch reads: slnlp/schedule.py)
+# schedule is host work per epoch, and per batch a device table per fit that the step's gather launch reads: slnlp/schedule.py;
+# a shuffled visit order is such a table too: slnlp/sampler.py -- iterator_train__drop_last changes the number of steps and stays
+# shape-defining)
 SHAPE_KEYS_EXCLUDED = ("lr", "module__dropout", "criterion__label_smoothing", "optimizer__weight_decay", "optimizer__dampening",
-                       "optimizer__nesterov", "lr_scheduler")
+                       "optimizer__nesterov", "lr_scheduler", "iterator_train__shuffle")
 
 
 def estimate_fit_bytes(params, seq_len, defaults=None, lockstep=1):

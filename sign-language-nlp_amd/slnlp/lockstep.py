@@ -46,7 +46,7 @@ class LockstepGroup:
         check(self._fn("create")(handles, self.K, ptr(self.workspace), nbytes, self._sp(), C.byref(out)), f"{self.kind}_lockstep_create")
         self.handle = out
         check(self._fn("set_destroy_sync")(out, 0), "lockstep_set_destroy_sync")   # torch-allocated tables: see tf_engine.py
-        self.data, self.logp, self.loss, self.rows = {}, {}, {}, {}
+        self.data, self.logp, self.loss, self.rows, self.n_visit, self._orders = {}, {}, {}, {}, {}, {}
 
     def _fn(self, name):                                 # a method, not a closure over self: no reference cycle
         return getattr(load(), f"slnlp_{self.kind}_lockstep_{name}")
@@ -76,6 +76,8 @@ class LockstepGroup:
         self.logp[slot] = [torch.empty(rows, Vt, dtype=torch.float32, device=self.device) for _ in range(self.K)]
         self.loss[slot] = [torch.zeros(nb, dtype=torch.float32, device=self.device) for _ in range(self.K)]
         self.rows[slot] = rows
+        self.n_visit.pop(slot, None)                     # the C side drops the slot's order with its old data
+        self._orders.pop(slot, None)
         if self.kind == "rnn":
             assert lengths is not None and len(lengths) == self.K, "lockstep: RNN fits need the sequence lengths"
             lengths = [l.contiguous() for l in lengths]
@@ -109,6 +111,27 @@ class LockstepGroup:
         arr = (C.c_void_p * self.K)(*[None if t is None else ptr(t) for t in tables])
         check(self._fn("set_lr_table")(self.handle, arr, n, self._sp()), f"{self.kind}_lockstep_set_lr_table")
 
+    def set_order(self, slot, orders, n_visit=None):
+        """Per-fit visit order of a slot (a shuffled epoch): a list with, per fit, a contiguous int64 device tensor [n_visit] of row
+        indices into that fit's dataset or None (that fit stays in dataset order); ``orders`` None clears the setting.  ``n_visit``
+        (default: the tensors' length) is the number of rows a pass visits, one number for the group -- with every entry None it
+        only shortens the pass (drop_last).  From then on ``step`` / ``epoch`` stage row ``orders[f][row0 + i]`` for visit
+        ``row0 + i``; log-probs and losses land at visit position, and ``results`` covers ``n_visit`` rows.  The indices are the
+        caller's contract: check the host array (``slnlp.sampler.check_order``) before uploading it."""
+        if orders is None:
+            self.n_visit.pop(slot, None)
+            self._orders.pop(slot, None)
+            check(self._fn("set_order")(self.handle, slot, None, 0, self._sp()), f"{self.kind}_lockstep_set_order")
+            return
+        given = [t for t in orders if t is not None]
+        n = int(given[0].numel()) if n_visit is None else int(n_visit)
+        assert len(orders) == self.K and all(t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n and t.device == self.device
+                                             for t in given), "lockstep: one int64 device tensor [n_visit] (or None) per fit"
+        arr = (C.c_void_p * self.K)(*[None if t is None else ptr(t) for t in orders])
+        check(self._fn("set_order")(self.handle, slot, arr, n, self._sp()), f"{self.kind}_lockstep_set_order")
+        self._orders[slot] = list(orders)                # keep the tensors alive: the gather launch reads them
+        self.n_visit[slot] = n
+
     def _sync_versions(self):
         for e in self.engines:                           # Transformer: weight planes follow outside writes to the fp32 arena
             if hasattr(e, "sync_params_version"):
@@ -120,7 +143,8 @@ class LockstepGroup:
               f"{self.kind}_lockstep_step")
 
     def epoch(self, slot, batch, train, momentum=0.9, max_norm=0.5):
-        """One pass over the slot in dataset order; no host synchronisation.  Results: ``logp[slot]``, ``loss[slot]``."""
+        """One pass over the slot in dataset order (or the slot's order tables: ``set_order``); no host synchronisation.
+        Results: ``logp[slot]``, ``loss[slot]``."""
         self._sync_versions()
         check(self._fn("epoch")(self.handle, slot, batch, int(train), momentum, max_norm, self._sp()), f"{self.kind}_lockstep_epoch")
 
@@ -129,13 +153,17 @@ class LockstepGroup:
 
     def results(self, slot, f, batch):
         """What ``NeuralNetClassifier._run_epoch`` returns for fit ``f``: (batch-size weighted mean loss, log-probs [rows, Vt],
-        [(batch loss, batch size)]).  Call after a synchronisation point."""
-        rows = self.rows[slot]
+        [(batch loss, batch size)]) -- over the ``n_visit`` rows of a pass, in visit order, when the slot has an order.  Call
+        after a synchronisation point."""
+        rows = self.n_visit.get(slot, self.rows[slot])
         sizes = [min(batch, rows - r) for r in range(0, rows, batch)]
-        per_batch = self.loss[slot][f].float().cpu()
+        per_batch, logp = self.loss[slot][f], self.logp[slot][f]
+        if rows != self.rows[slot]:
+            per_batch, logp = per_batch[:len(sizes)], logp[:rows]
+        per_batch = per_batch.float().cpu()
         w = torch.tensor(sizes, dtype=torch.float32)
         mean = float((per_batch * w).sum() / w.sum())
-        return mean, self.logp[slot][f], list(zip(per_batch.tolist(), sizes))
+        return mean, logp, list(zip(per_batch.tolist(), sizes))
 
 
 LOCKSTEP_MODULES = ("Transformer", "EncoderDecoderLSTMAttn", "EncoderDecoderGRUAttn")
@@ -187,9 +215,9 @@ def _fit_lockstep_gated(nets, datasets):
     assert len({type(n.module_) for n in nets}) == 1, "lockstep: one module class per group"
     assert len({_adam_key(n) for n in nets}) == 1, "lockstep: one optimizer (and one set of Adam constants) per group"
     adam = _adam_key(nets[0]) if nets[0]._fused_kind in ("adam", "adamw") else None
-    assert all((r.bs, r.momentum, r.max_norm, len(r.tr), (len(r.va) if r.va is not None else 0)) ==
-               (r0.bs, r0.momentum, r0.max_norm, len(r0.tr), (len(r0.va) if r0.va is not None else 0)) for r in runs), \
-        "lockstep: the fits of a group share batch size, momentum, clipping and split sizes"
+    assert all((r.bs, r.momentum, r.max_norm, len(r.tr), r.n_visit, (len(r.va) if r.va is not None else 0)) ==
+               (r0.bs, r0.momentum, r0.max_norm, len(r0.tr), r0.n_visit, (len(r0.va) if r0.va is not None else 0)) for r in runs), \
+        "lockstep: the fits of a group share batch size, momentum, clipping, split sizes and drop_last"
     S = r0.Xtr.shape[1]
     with torch.cuda.stream(stream):
         engines = [n.module_.engine(r0.bs, S) for n in nets]
@@ -215,6 +243,7 @@ def _fit_lockstep_gated(nets, datasets):
                 members = list(active)
             # every fit's rates for this epoch, before anything is queued (a scheduler stepped past its end raises here)
             tables = [runs[i].lr_table() for i in active]
+            orders = [runs[i].order() for i in active]  # shuffled fits: the epoch's visit order (host), drawn before anything is queued
             for i in active:
                 engines[i].set_lr(nets[i].lr_)
                 nets[i].module_.train()
@@ -229,6 +258,19 @@ def _fit_lockstep_gated(nets, datasets):
                 for r, j in enumerate(pb):
                     per_fit[j] = dev_tab[r]
                 group.set_lr_tables(per_fit)
+            sh = [j for j, o in enumerate(orders) if o is not None]
+            if sh or r0.n_visit != len(r0.tr):
+                # the orders go to the device the same way: ONE [fits, 2, n_visit] tensor per epoch -- each shuffled fit's order and
+                # its labels in visit order (what train scoring pairs the log-probs with) -- and every step's gather launch stages
+                # the rows its fit's table names; unshuffled fits of the group keep dataset order (no table), and with drop_last
+                # the group only visits the full batches.  A new group (after a regroup) gets its tables here like the first.
+                per_fit = [None] * len(active)
+                if sh:
+                    dev_ord = torch.from_numpy(np.stack([runs[active[j]].visit_table() for j in sh])).to(group.device)
+                    for r, j in enumerate(sh):
+                        per_fit[j] = dev_ord[r, 0]
+                        runs[active[j]].set_visit(dev_ord[r, 0], dev_ord[r, 1])
+                group.set_order(TRAIN, per_fit, r0.n_visit)
             t_epoch = time.perf_counter()
             group.epoch(TRAIN, r0.bs, True, r0.momentum, r0.max_norm)
             if r0.va is not None:

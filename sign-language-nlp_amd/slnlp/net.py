@@ -10,7 +10,8 @@ reference configures, with the same parameter names
 semantics:
 
 * internal 80/20 stratified split, first fold of ``StratifiedKFold(5)`` (skorch ``CVSplit(5)``);
-* batches in dataset order (``shuffle`` is commented out, helper.py:75-76);
+* batches in dataset order (``shuffle`` is commented out, helper.py:75-76), or -- ``iterator_train__shuffle=True`` -- in the
+  order torch's ``RandomSampler`` draws per epoch (slnlp/sampler.py); ``iterator_train__drop_last`` drops the short last batch;
 * per batch: forward -> CrossEntropyLoss(ignore_index=pad) -> backward ->
   clip_grad_norm_(gradient_clip_value) -> SGD(momentum)  == ONE hipGraph replay;
 * per epoch: valid pass, ``EpochScoring`` metrics for train/valid, ``lr`` scoring,
@@ -29,7 +30,7 @@ import importlib
 import numpy as np
 import torch
 
-from . import metrics, schedule
+from . import metrics, ops, sampler, schedule
 from .data import TokenDataset
 
 
@@ -321,6 +322,22 @@ class _FitRun:
                 dummy, **{k: v for k, v in sched.items() if k not in ("policy", "monitor", "step_every")})
         self.best_valid, self.misses, self.dyn_thr = float("inf"), 0, float("inf")
         self.bs = int(net.batch_size)
+        # the train iterator: which rows an epoch visits (all, or the full batches) and in which order (dataset order, or a
+        # fresh draw of torch's RandomSampler per epoch); valid and test passes stay in dataset order
+        self.shuffle, self.drop_last = net._iterator_train()
+        self.n_visit = sampler.n_visit(len(self.tr), self.bs, self.drop_last)
+        if self.n_visit < 1:
+            raise ValueError(f"iterator_train__drop_last=True with {len(self.tr)} train rows and batch_size {self.bs}: no full batch, "
+                             "nothing to train on")
+        self.sampler = None
+        if self.shuffle:
+            # the order's position is a function of the history, like a schedule's: the seed rides the epoch rows
+            seed = sampler.seed_from_history(net.history)
+            if seed is None:                                 # (shuffling switched on after initialize(): drawn now)
+                seed = net.shuffle_seed_ if getattr(net, "shuffle_seed_", None) is not None else sampler.draw_seed()
+            net.shuffle_seed_ = seed
+            self.sampler = sampler.EpochOrder(len(self.tr), self.bs, net.shuffle_seed_, self.drop_last).fast_forward(len(net.history))
+        self.epoch_order, self.order_dev, self.y_visit_dev = None, None, None
         self.epochs_left = int(net.max_epochs)
         self.done = self.epochs_left <= 0
 
@@ -332,8 +349,33 @@ class _FitRun:
         Call once per epoch, before any of its work is queued: a scheduler stepped past its end raises here."""
         if self.schedule is None:
             return None
-        self.epoch_lrs = self.schedule.epoch_table((len(self.tr) + self.bs - 1) // self.bs)
+        self.epoch_lrs = self.schedule.epoch_table((self.n_visit + self.bs - 1) // self.bs)
         return self.epoch_lrs
+
+    def order(self):
+        """The coming epoch's visit order of the train rows: int64 host array [n_visit], or None (dataset order).  Call once
+        per epoch, before any of its work is queued, next to ``lr_table``."""
+        self.epoch_order = self.sampler.next_epoch() if self.sampler is not None else None
+        self.order_dev = self.y_visit_dev = None
+        return self.epoch_order
+
+    def visit_table(self):
+        """What a shuffled epoch needs on the device, as one host array int64 [2, n_visit]: the order (range-checked) and the
+        labels in visit order -- the epoch's log-probs land at visit position, so that is what train scoring pairs them with."""
+        order = sampler.check_order(self.epoch_order, len(self.tr), self.n_visit)
+        return np.stack([order, self.tr.y[order].astype(np.int64)])
+
+    def set_visit(self, order_dev, y_visit_dev):
+        """The device copies of ``visit_table``'s two rows (uploaded by whoever drives the epoch: one copy per lockstep group)."""
+        self.order_dev, self.y_visit_dev = order_dev, y_visit_dev
+
+    def train_labels(self):
+        """(device, host) labels of the rows the epoch's train log-probs belong to, in visit order."""
+        if self.epoch_order is not None:
+            return self.y_visit_dev, self.tr.y[self.epoch_order]
+        if self.n_visit != len(self.tr):
+            return self.ytr[:self.n_visit], self.tr.y[:self.n_visit]
+        return self.ytr, self.tr.y
 
     def end_epoch(self, tr, va):
         """tr / va: (sample-weighted mean loss, log-probs [n, V] on the device, [(batch loss, batch size)]) of the epoch's
@@ -346,6 +388,8 @@ class _FitRun:
             net._set_lr(self.schedule.current)
         row = {"epoch": epoch, "train_loss": tr_loss, "lr": net.lr_,
                "batches": [{"train_loss": l, "train_batch_size": n} for l, n in tr_batches]}   # skorch history layout
+        if self.sampler is not None:
+            row["shuffle_seed"] = self.sampler.seed          # a resumed fit rebuilds the order from it (slnlp/sampler.py)
         if self.schedule is not None and self.schedule.per_batch:
             for b, lr in zip(row["batches"], self.epoch_lrs):
                 b["event_lr"] = lr                           # the rate this batch used
@@ -357,18 +401,19 @@ class _FitRun:
             self.best_valid = min(self.best_valid, va_loss)
         # EpochScoring on the epoch's cached predictions: the reference's five metrics from one device-side
         # reduction (slnlp/metrics.py, same numbers as the sklearn scorers); anything else through sklearn
-        splits = [("train", tr_logp, self.ytr, self.tr)] + ([("valid", va_logp, self.yva, self.va)] if va is not None else [])
+        # (train: paired with the labels in VISIT order, what skorch's cached predictions give EpochScoring under a shuffling loader)
+        splits = [("train", tr_logp) + self.train_labels()] + ([("valid", va_logp, self.yva, self.va.y)] if va is not None else [])
         names = [wr.score for wr in self.wrappers]
-        fast = {sp: metrics.epoch_scores(names, lp, yd, part.y) if self.fast_ok and names else {} for sp, lp, yd, part in splits}
+        fast = {sp: metrics.epoch_scores(names, lp, yd, yh) if self.fast_ok and names else {} for sp, lp, yd, yh in splits}
         proba = {}
         for wr in self.wrappers:
-            for sp, lp, yd, part in splits:
+            for sp, lp, yd, yh in splits:
                 if wr.score in fast[sp]:
                     row[f"{sp}_{wr.score}"] = fast[sp][wr.score]
                     continue
                 if sp not in proba:
                     proba[sp] = np.exp(lp.cpu().numpy())
-                row[f"{sp}_{wr.score}"] = float(wr(_CachedPredictor(proba[sp], net.classes_), None, part.y))
+                row[f"{sp}_{wr.score}"] = float(wr(_CachedPredictor(proba[sp], net.classes_), None, yh))
         row["dur"] = time.time() - self.t0
         net.history.append(row)
         if net.verbose:
@@ -489,8 +534,20 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         return {k[n:]: v for k, v in self._params.items() if k.startswith(prefix + "__")}
 
     # ------------------------------------------------------------- lifecycle
+    def _iterator_train(self):
+        """(shuffle, drop_last) of the train iterator: the two ``iterator_train__*`` keys the fit loop honours."""
+        it = self._sub("iterator_train")
+        out = []
+        for k in sampler.HONOURED:
+            v = it.get(k, False)
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"iterator_train__{k}={v!r}: expected True or False")
+            out.append(bool(v))
+        return tuple(out)
+
     def initialize(self):
         schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
+        shuffle, _ = self._iterator_train()
         dev = torch.device(self.device)
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("slnlp.net: device %r -- the HIP path is the only compute path (no CPU fallback)" % (self.device,))
@@ -522,6 +579,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             self.optimizer_ = self._opt_cls(self.module_.parameters(), lr=self.lr, **ok)
         self.lr_ = float(self.lr)
         self.history = []
+        # the seed of the shuffled order, drawn the way RandomSampler draws one without a generator -- AFTER the module's
+        # weights and only when shuffling is on, so the initial weights of every other configuration keep their bits
+        self.shuffle_seed_ = sampler.draw_seed() if shuffle else None
         self.initialized_ = True
         return self
 
@@ -566,7 +626,11 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             for _ in range(int(self.max_epochs)):
                 run.begin_epoch()
                 self.module_.train()
-                tr = self._run_epoch(run.Xtr, run.Ltr, run.ytr, run.bs, True, run.momentum, run.max_norm, lrs=run.lr_table())
+                lrs, order = run.lr_table(), run.order()
+                if order is not None:                       # one upload per epoch: the order and the labels in visit order
+                    run.set_visit(*torch.from_numpy(run.visit_table()).to(run.Xtr.device))
+                tr = self._run_epoch(run.Xtr, run.Ltr, run.ytr, run.bs, True, run.momentum, run.max_norm, lrs=lrs,
+                                     order=run.order_dev, n_visit=run.n_visit)
                 va = None
                 if run.va is not None:
                     self.module_.eval()
@@ -594,13 +658,22 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             for g in self.optimizer_.param_groups:
                 g["lr"] = self.lr_
 
-    def _run_epoch(self, X, L, y, bs, train, momentum, max_norm, lrs=None):
-        """One pass in dataset order; ``lrs``: the learning rate of each train batch (``_FitRun.lr_table``; None: ``lr_``
-        throughout).  Returns (sample-weighted mean loss, log-probs [N,V] on the device, [(batch loss, batch size)])."""
-        n = X.shape[0]
+    def _run_epoch(self, X, L, y, bs, train, momentum, max_norm, lrs=None, order=None, n_visit=None):
+        """One pass in dataset order, or -- ``order``: int64 device tensor [n_visit] -- over rows ``order[0], order[1], ...``
+        (a shuffled train epoch: every batch is staged by the library's gather launch, whichever way the fit steps, so no
+        torch indexing kernel joins the stream); ``n_visit``: rows visited (None: all; fewer with drop_last).  ``lrs``: the
+        learning rate of each train batch (``_FitRun.lr_table``; None: ``lr_`` throughout).  Returns (sample-weighted mean
+        loss, log-probs [n_visit, V] on the device in visit order, [(batch loss, batch size)])."""
+        n = X.shape[0] if n_visit is None else int(n_visit)
         losses, sizes, outs = [], [], []
         for k, i in enumerate(range(0, n, bs)):
-            xb, lb, yb = X[i:i + bs], L[i:i + bs], y[i:i + bs]
+            stop = min(i + bs, n)
+            if order is not None:
+                # fused fits gather straight into their plan's fixed staging buffers (the ones a captured graph reads)
+                stage = self.module_.engine(stop - i, X.shape[1]).staging() if train and self._fused else None
+                xb, lb, yb = ops.gather_batch(X, L, y, order, i, stop - i, out=stage)
+            else:
+                xb, lb, yb = X[i:stop], L[i:stop], y[i:stop]
             if train and lrs is not None:
                 self._set_lr(lrs[k])                        # one schedule for the fused and the torch-stepped path
             if train and self._fused:
@@ -750,4 +823,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         if os.path.exists(hist):
             with open(hist) as f:
                 self.history = json.load(f)
+            seed = sampler.seed_from_history(self.history)
+            if seed is not None:                         # the resumed fit continues the checkpoint's order (slnlp/sampler.py)
+                self.shuffle_seed_ = seed
         return self

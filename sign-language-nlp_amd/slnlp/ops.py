@@ -382,3 +382,30 @@ def dropout_mask(R, C_, p, site, rng):
     out = torch.empty(R, C_, dtype=torch.float32, device=rng.device)
     check(load().slnlp_dropout_mask(ptr(out), R, C_, p, site, ptr(rng), stream_ptr()), "dropout_mask")
     return out
+
+
+def gather_batch(X, lengths, y, order, row0, B, out=None):
+    """One batch in visit order: rows ``order[row0 : row0 + B]`` of the device-resident dataset ``X`` int64 [rows, S] /
+    ``lengths`` int64 [rows] or None / ``y`` int64 [rows]; ``order`` None: rows ``row0 : row0 + B``.  ``out``: staging buffers
+    ``(X_out [>= B, S], len_out [>= B] or None, y_out [>= B])`` to fill (a captured graph's, a fit's); None allocates them.
+    Returns the filled ``(X_out[:B], len_out[:B] or None, y_out[:B])``.  The order's indices are the caller's contract
+    (``slnlp.sampler.check_order`` checks a host order before it is uploaded)."""
+    _lib.require_gpu()
+    rows, S = X.shape
+    row0, B = int(row0), int(B)
+    limit = rows if order is None else int(order.numel())
+    if B < 1 or row0 < 0 or row0 + B > limit:
+        raise ValueError(f"gather_batch: rows [{row0}, {row0 + B}) outside 0..{limit}")
+    if out is None:
+        out = (torch.empty(B, S, dtype=torch.int64, device=X.device),
+               None if lengths is None else torch.empty(B, dtype=torch.int64, device=X.device),
+               torch.empty(B, dtype=torch.int64, device=X.device))
+    Xo, Lo, yo = out
+    if lengths is None:
+        Lo = None
+    for t in (X, lengths, y, order, Xo, Lo, yo):
+        assert t is None or (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()), "gather_batch: contiguous int64 device tensors"
+    assert Xo.shape[0] >= B and Xo.shape[1] == S and yo.shape[0] >= B and (Lo is None or Lo.shape[0] >= B) and y.shape[0] == rows
+    check(load().slnlp_gather_batch(ptr(X), ptr(lengths), ptr(y), ptr(order), row0, B, S, ptr(Xo), ptr(Lo), ptr(yo), stream_ptr()),
+          "gather_batch")
+    return Xo[:B], (None if Lo is None else Lo[:B]), yo[:B]

@@ -150,16 +150,25 @@ class RnnEngine:
                                           self._sp()), "rnn_train_step")
         return self.logp[:B]
 
-    def train_step_graph(self, X, y, lengths, momentum=0.9, max_norm=0.5):
-        B = X.shape[0]
-        key = (B, float(momentum), float(max_norm))
+    def staging(self):
+        """The plan's fixed staging buffers ``(X [B, S], lengths [B], y [B])``: what a captured graph reads.  A shuffled fit
+        gathers its batches straight into them (``ops.gather_batch(..., out=engine.staging())``) and steps on the views it gets
+        back."""
         if self._xbuf is None:
             dev = self.device
             self._xbuf = torch.empty(self.cfg.B, self.cfg.S, dtype=torch.int64, device=dev)
             self._ybuf = torch.empty(self.cfg.B, dtype=torch.int64, device=dev)
             self._lbuf = torch.empty(self.cfg.B, dtype=torch.int64, device=dev)
+        return self._xbuf, self._lbuf, self._ybuf
+
+    def train_step_graph(self, X, y, lengths, momentum=0.9, max_norm=0.5):
+        B = X.shape[0]
+        key = (B, float(momentum), float(max_norm))
+        self.staging()
         xb, yb, lb = self._xbuf[:B], self._ybuf[:B], self._lbuf[:B]
-        xb.copy_(X); yb.copy_(y); lb.copy_(lengths)
+        for dst, src in ((xb, X), (yb, y), (lb, lengths)):
+            if src.data_ptr() != dst.data_ptr():          # a shuffled fit's batch was gathered here already
+                dst.copy_(src)
         st = self._sp()
         if st == 0:
             raise RuntimeError("train_step_graph needs a non-default stream (use torch.cuda.stream(...))")

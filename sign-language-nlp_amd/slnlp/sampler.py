@@ -1,0 +1,81 @@
+"""The visit order of a fit's train rows: torch's own ``RandomSampler`` / ``BatchSampler``, wrapped.
+
+skorch hands ``iterator_train__shuffle`` / ``iterator_train__drop_last`` to ``torch.utils.data.DataLoader``, which builds a
+``BatchSampler(RandomSampler(dataset, generator=...), batch_size, drop_last)``.  ``EpochOrder`` owns exactly those two objects
+(over ``range(n)``), so every index of every epoch is torch's own draw -- nothing about how ``RandomSampler`` uses its
+generator is restated here.  The fit loop asks for a whole epoch's order ahead of the epoch (``next_epoch``), because a
+lockstep unit runs the epoch without coming back to the host: the order travels to the device as a table (slnlp.lockstep),
+and every other path stages its batches through the same table (``slnlp_gather_batch``).
+
+As for schedules (slnlp/schedule.py), the position is a function of the fit's history: a new fit run builds the sampler from
+the seed and draws the epochs the history accounts for (``fast_forward``), so a resumed fit needs no extra checkpoint file --
+the seed rides every epoch row of a shuffled fit (``"shuffle_seed"``).
+"""
+import numpy as np
+import torch
+from torch.utils.data import BatchSampler, RandomSampler
+
+# the ``iterator_train__*`` keys the fit loop honours (every other ``iterator_*`` key is accepted and has no effect, as the
+# reference's ``collate_fn``)
+HONOURED = ("shuffle", "drop_last")
+
+
+def draw_seed():
+    """A fresh seed from torch's global CPU generator, the way ``RandomSampler`` draws one when it is given no generator."""
+    return int(torch.empty((), dtype=torch.int64).random_().item())
+
+
+def seed_from_history(history):
+    """The ``shuffle_seed`` of the last epoch row that carries one, or None."""
+    for row in reversed(history or []):
+        if row.get("shuffle_seed") is not None:
+            return int(row["shuffle_seed"])
+    return None
+
+
+def n_visit(n, batch_size, drop_last=False):
+    """Rows one epoch visits."""
+    return (n // batch_size) * batch_size if drop_last else n
+
+
+def check_order(order, rows, n_visit=None):
+    """A host order as contiguous int64, after the checks the device side leaves to its caller: one dimension, the expected
+    length, every index a row of the dataset."""
+    order = np.ascontiguousarray(order, dtype=np.int64)
+    if order.ndim != 1 or order.size < 1 or (n_visit is not None and order.size != n_visit):
+        raise ValueError(f"order table of shape {order.shape}, expected ({n_visit},)")
+    if int(order.min()) < 0 or int(order.max()) >= rows:
+        raise ValueError(f"order table indexes rows {int(order.min())}..{int(order.max())} of a dataset of {rows}")
+    return order
+
+
+class EpochOrder:
+    """Epoch ``e`` (0-based) of the object is the ``e``-th iteration of
+    ``BatchSampler(RandomSampler(range(n), generator=torch.Generator().manual_seed(seed)), batch_size, drop_last)``, flattened."""
+
+    def __init__(self, n, batch_size, seed, drop_last=False):
+        n, batch_size = int(n), int(batch_size)
+        if n < 1 or batch_size < 1:
+            raise ValueError(f"EpochOrder: n={n}, batch_size={batch_size}")
+        self.n, self.batch_size, self.seed, self.drop_last = n, batch_size, int(seed), bool(drop_last)
+        self.n_visit = n_visit(n, batch_size, self.drop_last)
+        if self.n_visit < 1:
+            raise ValueError(f"iterator_train__drop_last=True with {n} train rows and batch_size {batch_size}: no full batch, "
+                             "nothing to train on")
+        self.epochs_drawn = 0
+        self._gen = torch.Generator().manual_seed(self.seed)
+        self._batches = BatchSampler(RandomSampler(range(n), generator=self._gen), batch_size, self.drop_last)
+
+    def next_epoch(self):
+        """The coming epoch's visit order: int64 numpy array of ``n_visit`` row indices."""
+        # the iteration is run to its end, as a DataLoader would: what RandomSampler draws after its last index is part of the stream
+        order = np.array([i for batch in self._batches for i in batch], dtype=np.int64)
+        assert order.shape == (self.n_visit,)
+        self.epochs_drawn += 1
+        return order
+
+    def fast_forward(self, epochs_done):
+        """Draw (and drop) the epochs a history of ``epochs_done`` rows accounts for."""
+        for _ in range(int(epochs_done)):
+            self.next_epoch()
+        return self

@@ -84,7 +84,7 @@ class TransformerEngine:
         check(load().slnlp_tf_set_destroy_sync(handle, 0), "tf_set_destroy_sync")
         self._graph_keys = {}
         self._launch = LaunchPolicy()
-        self._xbuf = self._ybuf = None
+        self._xbuf = self._ybuf = self._lbuf = None
         self._pv = None
 
     def sync_params_version(self):
@@ -199,9 +199,20 @@ class TransformerEngine:
                                          self._sp()), "tf_train_step")
         return self.logp[:B]
 
+    def staging(self):
+        """The plan's fixed staging buffers ``(X [B, S], lengths [B], y [B])``: what a captured graph reads.  A shuffled fit
+        gathers its batches straight into them (``ops.gather_batch(..., out=engine.staging())``) and steps on the views it gets
+        back; the lengths buffer is there for the uniform call, the Transformer never reads it."""
+        if self._xbuf is None:
+            self._xbuf = torch.empty(self.cfg.B, self.cfg.S, dtype=torch.int64, device=self.device)
+            self._ybuf = torch.empty(self.cfg.B, dtype=torch.int64, device=self.device)
+        if self._lbuf is None:
+            self._lbuf = torch.empty(self.cfg.B, dtype=torch.int64, device=self.device)
+        return self._xbuf, self._lbuf, self._ybuf
+
     def train_step_graph(self, X, y, momentum=0.9, max_norm=0.5):
         """Same step replayed from a captured hipGraph (one per batch size):
-        the batch is copied into fixed staging buffers, then one graph launch."""
+        the batch is copied into fixed staging buffers (unless it was gathered there), then one graph launch."""
         self.sync_params_version()
         B = X.shape[0]
         key = (B, float(momentum), float(max_norm))
@@ -209,8 +220,10 @@ class TransformerEngine:
             self._xbuf = torch.empty(self.cfg.B, self.cfg.S, dtype=torch.int64, device=self.device)
             self._ybuf = torch.empty(self.cfg.B, dtype=torch.int64, device=self.device)
         xb, yb = self._xbuf[:B], self._ybuf[:B]
-        xb.copy_(X)
-        yb.copy_(y)
+        if X.data_ptr() != xb.data_ptr():
+            xb.copy_(X)
+        if y.data_ptr() != yb.data_ptr():
+            yb.copy_(y)
         st = self._sp()
         if st == 0:
             raise RuntimeError("train_step_graph needs a non-default stream (use torch.cuda.stream(...))")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Aggregate train seq/s of K fits advancing in lockstep (one launch sequence) vs one fit alone.
 
-    python tools/bench_lockstep.py [--workload cfg2] [--ks 1,2,4,8] [--steps 30]
+    python tools/bench_lockstep.py [--workload cfg2] [--ks 1,2,4,8] [--steps 30] [--shuffle]
+        --shuffle: every fit stages its batches through an order table of its own (a shuffled epoch, slnlp_*_lockstep_set_order)
 """
 import argparse
 import json
@@ -24,6 +25,7 @@ def main():
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--precision", type=int, default=3)
+    ap.add_argument("--shuffle", action="store_true", help="an order table (a random permutation of the rows) on every fit")
     args = ap.parse_args()
     from slnlp import synth, tf_engine as te, rnn_engine as re_
     from slnlp.lockstep import LockstepGroup
@@ -46,6 +48,9 @@ def main():
         with torch.cuda.stream(st):
             grp = LockstepGroup(engs)
             grp.set_data(0, [d[0] for d in data], [d[1] for d in data], B, [d[2] for d in data])
+            if args.shuffle:
+                gen = torch.Generator().manual_seed(1)
+                grp.set_order(0, [torch.randperm(rows, generator=gen).to(dev) for _ in range(K)])
             grp.epoch(0, B, True, 0.9, 0.5)              # warm-up pass (records the program)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -55,7 +60,7 @@ def main():
             n = grp.num_launches(0, B, True)
             grp.close()
         r = {"K": K, "seq_per_s": round(K * rows / dt, 1), "ms_per_lockstep_step": round(dt / args.steps * 1e3, 3),
-             "launches_per_step": n}
+             "launches_per_step": n, "shuffle": bool(args.shuffle)}
         out["results"].append(r)
         print(json.dumps(r), flush=True)
         del engs, data, grp
