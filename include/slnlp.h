@@ -476,7 +476,8 @@ int slnlp_tf_train_step(slnlp_tf_plan* plan, const int64_t* X, const int64_t* y,
 int slnlp_tf_graph_capture_train(slnlp_tf_plan* plan, const int64_t* X, const int64_t* y, int B,
                                  float momentum, float max_norm, float* logp, void* stream);
 int slnlp_tf_graph_launch(slnlp_tf_plan* plan, int B, void* stream);
-/* test helper: copy a named activation tap ("enc0", "memory", "dec1", "logits", ...); "enc<l>.<planes>" (d2p, hp, ghp, x1p, d1p,
+/* test helper: copy a named activation tap ("enc0", "memory", "dec1", "logits", ...; "dmemory": the gradient with respect to
+ * the encoder memory, [S*B, E], after a backward); "enc<l>.<planes>" (d2p, hp, ghp, x1p, d1p,
  * ctxp, gqkvp, x2p, xinp): an operand of the layer's gradient GEMMs as its bf16 planes -- the hi plane's [rows, cols] 16-bit words,
  * then the lo plane's, in rows * cols floats */
 int slnlp_tf_tap(slnlp_tf_plan* plan, const char* name, float* out, int64_t max_floats,
@@ -508,6 +509,12 @@ int slnlp_tf_set_destroy_sync(slnlp_tf_plan* plan, int on);
 #define SLNLP_UPDATE_ADAMW 2
 int slnlp_tf_set_criterion(slnlp_tf_plan* plan, const float* class_weight, float label_smoothing, int reduction, void* stream);
 int slnlp_tf_set_update(slnlp_tf_plan* plan, int kind, float dampening, float weight_decay, int nesterov);
+/* Where backward forms the gradient with respect to the encoder memory (and the cross-attention value biases' gradients).
+ * on (default): one launch for all decoder layers behind the decoder's layer loop -- nothing on that chain reads the sum;
+ * off: a launch per layer inside the loop, each adding onto the sum.  Same bits either way (the same fp32 operations in the
+ * same order); the switch exists for A / B measurements and tests.  A change drops the plan's captured graphs and makes a
+ * lockstep group re-record, as slnlp_tf_set_update does. */
+int slnlp_tf_set_dmem_batched(slnlp_tf_plan* plan, int on);
 
 /* One kernel sequence per device (default).  The step entry points (slnlp_{tf,rnn}_{forward,backward,optim*,train_step,
  * graph_launch}, slnlp_*_lockstep_{step,epoch}) serialise per device: host threads enqueue whole steps in turn, and a step issued

@@ -181,6 +181,61 @@ constexpr int XMEM_MAX_HEADS = 64;      // heads per sequence the d-memory kerne
 // streams, so one row per workgroup read them S times per sequence (77 MB through the L2 per launch, 1.2 GB for 15 fits in
 // lockstep); eight rows share one pass.  A thread holds 4 columns of its rows; the sum over h runs in head order per row as before.
 constexpr int DMEM_ROWS = 8;
+// the three pieces of the per-layer work, shared by the per-layer kernel and the all-layers kernel below so that both compile the
+// same expressions (the same FMA contraction): nothing moves by a bit between them
+// p_s (after dropout) and d score_s of (sequence b, head h, memory row s_); zeros past the end of the sequence
+__device__ __forceinline__ void dmem_stage(const float* __restrict__ probs, const float* __restrict__ dsc, int b, int h, int s_, int S, int H,
+                                           float drop_p, unsigned drop_thr, int drop_site, const unsigned long long* __restrict__ rng,
+                                           float& p, float& d) {
+    const long bh = (long)b * H + h;
+    p = 0.f;
+    d = 0.f;
+    if (s_ < S) {
+        p = probs[bh * S + s_];
+        if (drop_p > 0.f) p = dropout_keep(rng, drop_site, (unsigned)bh, (unsigned)s_, drop_thr) ? p / (1.f - drop_p) : 0.f;
+        d = dsc[bh * S + s_];
+    }
+}
+// a[i] += sum_h p(r_i, h) d mbar(b, h, e..e+3) + d score(r_i, h) qk(b, h, e..e+3), heads in order; ph / dh_: LDS tables [row][ld].
+// DMEM_HEADS heads' vectors are requested together, before anything waits for one.  Two heads (four loads in flight) keep the
+// kernels at 96 / 100 VGPRs; four heads measured the same step times at 112 / 116, eight put them at 144 / 148 and one wave per
+// SIMD fewer.  Row r_i = set + i sets exists for i < ni (the same in every thread) and, where sets does not divide DMEM_ROWS,
+// for some threads only: the others add zeros into an accumulator that is never stored.
+constexpr int DMEM_HEADS = 2;
+__device__ __forceinline__ void dmem_add_heads(float4 (&a)[DMEM_ROWS], const float* __restrict__ dmbar, const float* __restrict__ qk,
+                                               const float* ph, const float* dh_, int ld, int b, int H, int E, int e, int set, int sets) {
+    const int ni = (DMEM_ROWS + sets - 1) / sets;
+    for (int h0 = 0; h0 < H; h0 += DMEM_HEADS) {
+        float4 g[DMEM_HEADS], k[DMEM_HEADS];
+#pragma unroll
+        for (int u = 0; u < DMEM_HEADS; ++u) {
+            const long bh = (long)b * H + (h0 + u < H ? h0 + u : H - 1);       // (past the last head: a repeat, never used)
+            g[u] = *reinterpret_cast<const float4*>(dmbar + bh * E + e);
+            k[u] = *reinterpret_cast<const float4*>(qk + bh * E + e);
+        }
+#pragma unroll
+        for (int u = 0; u < DMEM_HEADS; ++u) {
+            if (h0 + u >= H) break;
+#pragma unroll
+            for (int i = 0; i < DMEM_ROWS; ++i) {
+                if (i >= ni) break;
+                const int r = set + i * sets;
+                const bool ok = r < DMEM_ROWS;
+                const float p = ok ? ph[r * ld + h0 + u] : 0.f, d = ok ? dh_[r * ld + h0 + u] : 0.f;
+                a[i].x += p * g[u].x + d * k[u].x; a[i].y += p * g[u].y + d * k[u].y; a[i].z += p * g[u].z + d * k[u].z; a[i].w += p * g[u].w + d * k[u].w;
+            }
+        }
+    }
+}
+// d bv[c] = column sum of dcp [B, E] in row order
+__device__ __forceinline__ void dmem_colsum(const float* __restrict__ dcp, int B, int E, int c, float* __restrict__ dbv) {
+    if (c >= E) return;
+    float a = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < B; ++r) a += dcp[(long)r * E + c];
+    dbv[c] = a;
+}
+
 __device__ __forceinline__ void xmem_dmem_body(const float* __restrict__ probs, const float* __restrict__ dsc, const float* __restrict__ dmbar,
                                                const float* __restrict__ qk, int B, int S, int H, int E, float* __restrict__ dmem,
                                                int accumulate, float drop_p, unsigned drop_thr, int drop_site,
@@ -189,25 +244,14 @@ __device__ __forceinline__ void xmem_dmem_body(const float* __restrict__ probs, 
     __shared__ float ph[DMEM_ROWS][XMEM_MAX_HEADS], dh_[DMEM_ROWS][XMEM_MAX_HEADS];   // p_s (after dropout), d score_s per (row, head)
     const int chunks = (S + DMEM_ROWS - 1) / DMEM_ROWS, tid = threadIdx.x;
     if ((int)blockIdx.x >= chunks * B) {                 // the launch's last ceil(E / 256) workgroups: d bv = column sums of dcp, in row
-        const int c = ((int)blockIdx.x - chunks * B) * 256 + tid;      // order (was a launch of its own: 5 us of dispatch for 100 KB)
-        if (c < E) {
-            float a = 0.f;
-#pragma unroll 8
-            for (int r = 0; r < B; ++r) a += dcp[(long)r * E + c];
-            dbv[c] = a;
-        }
+        dmem_colsum(dcp, B, E, ((int)blockIdx.x - chunks * B) * 256 + tid, dbv);   // order (was a launch of its own: 5 us of dispatch for 100 KB)
         return;
     }
     const int b = blockIdx.x / chunks, s0 = (blockIdx.x % chunks) * DMEM_ROWS;
     for (int i = tid; i < DMEM_ROWS * H; i += 256) {
-        const int r = i / H, h = i - r * H, s_ = s0 + r;
-        const long bh = (long)b * H + h;
-        float p = 0.f, d = 0.f;
-        if (s_ < S) {
-            p = probs[bh * S + s_];
-            if (drop_p > 0.f) p = dropout_keep(rng, drop_site, (unsigned)bh, (unsigned)s_, drop_thr) ? p / (1.f - drop_p) : 0.f;
-            d = dsc[bh * S + s_];
-        }
+        const int r = i / H, h = i - r * H;
+        float p, d;
+        dmem_stage(probs, dsc, b, h, s0 + r, S, H, drop_p, drop_thr, drop_site, rng, p, d);
         ph[r][h] = p;
         dh_[r][h] = d;
     }
@@ -224,19 +268,7 @@ __device__ __forceinline__ void xmem_dmem_body(const float* __restrict__ probs, 
             a[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (accumulate && r < DMEM_ROWS && s_ < S) a[i] = *reinterpret_cast<const float4*>(dmem + ((long)s_ * B + b) * E + e);
         }
-#pragma unroll 8                                         // (all eight heads' vectors requested together: 16 loads in flight, not 4 x 4 round trips)
-        for (int h = 0; h < H; ++h) {
-            const long bh = (long)b * H + h;
-            const float4 g = *reinterpret_cast<const float4*>(dmbar + bh * E + e), k = *reinterpret_cast<const float4*>(qk + bh * E + e);
-#pragma unroll
-            for (int i = 0; i < DMEM_ROWS; ++i) {
-                const int r = set + i * sets;
-                if (r < DMEM_ROWS) {
-                    const float p = ph[r][h], d = dh_[r][h];
-                    a[i].x += p * g.x + d * k.x; a[i].y += p * g.y + d * k.y; a[i].z += p * g.z + d * k.z; a[i].w += p * g.w + d * k.w;
-                }
-            }
-        }
+        dmem_add_heads(a, dmbar, qk, &ph[0][0], &dh_[0][0], XMEM_MAX_HEADS, b, H, E, e, set, sets);
 #pragma unroll
         for (int i = 0; i < DMEM_ROWS; ++i) {
             const int r = set + i * sets, s_ = s0 + r;
@@ -245,6 +277,73 @@ __device__ __forceinline__ void xmem_dmem_body(const float* __restrict__ probs, 
     }
 }
 SLNLP_ZKERNEL(xmem_dmem_kernel, 256, xmem_dmem_body)
+
+// ------------------------------------------------------------------- backward, per memory row, ALL decoder layers ----
+// Nothing on the decoder's backward chain reads d memory, and every input of the kernel above is a per-layer buffer that stays
+// intact until the end of backward.  So the N launches inside the layer loop -- N - 1 of them a read-modify-write of the whole
+// [S*B, E] sum -- become ONE launch behind it: same workgroup / thread decomposition, accumulators start at zero, the layers are
+// walked N-1 ... 0 (the order the loop visits them) and the heads 0 ... H-1 inside each, and every row is stored once.  Per
+// element that is the sequence of fp32 operations the N launches perform: same bits.  The launch's trailing N ceil(E / 256)
+// workgroups (layer-major) are the layers' d bv column sums.
+// Per-layer pointers come from a device table the plan uploads once (tf_plan.hip).  The (p_s, d score_s) tables of up to
+// DMEM_STAGE_LAYERS layers are staged in LDS together, a wave per layer, so the staging costs one round trip and one barrier per
+// group of layers rather than one per layer; the head loops then follow each other with nothing but their own loads to wait for.
+constexpr int DMEM_STAGE_LAYERS = 8;
+// a table entry's pointer: the same in every lane (the layer index is wave-uniform), said so to the compiler, then global
+template <class T>
+__device__ __forceinline__ T* dmem_ptr(T* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return as_global((T*)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ void xmem_dmem_all_body(const XmemDmemLayer* __restrict__ tab, int N, int B, int S, int H, int E,
+                                                   float* __restrict__ dmem, float drop_p, unsigned drop_thr,
+                                                   const unsigned long long* __restrict__ rng) {
+    extern __shared__ __attribute__((aligned(16))) float xm_lds[];   // [staged layer][p | d][DMEM_ROWS][H]
+    const int chunks = (S + DMEM_ROWS - 1) / DMEM_ROWS, tid = threadIdx.x;
+    if ((int)blockIdx.x >= chunks * B) {
+        const int cb = (E + 255) / 256, i = (int)blockIdx.x - chunks * B, l = i / cb;
+        if (l < N) dmem_colsum(dmem_ptr(tab[l].dcp), B, E, (i - l * cb) * 256 + tid, dmem_ptr(tab[l].dbv));
+        return;
+    }
+    const int b = blockIdx.x / chunks, s0 = (blockIdx.x % chunks) * DMEM_ROWS;
+    const int per = E >> 2, sets = per >= 256 ? 1 : 256 / per;
+    const int set = sets == 1 ? 0 : tid / per, c0 = sets == 1 ? tid : tid - set * per, e = c0 * 4;
+    const bool active = set < sets && e < E;             // (E <= 1024, xmem_check: a thread has at most one column chunk)
+    const int lf = DMEM_ROWS * H, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    float4 a[DMEM_ROWS];
+#pragma unroll
+    for (int i = 0; i < DMEM_ROWS; ++i) a[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int l1 = N; l1 > 0; l1 -= DMEM_STAGE_LAYERS) {  // layers l1 - 1 ... l1 - n of this trip
+        const int n = l1 < DMEM_STAGE_LAYERS ? l1 : DMEM_STAGE_LAYERS;
+        if (l1 != N) __syncthreads();                    // (the previous trip's tables are still being read)
+        for (int j = wave; j < n; j += 4) {
+            const XmemDmemLayer L = tab[l1 - 1 - j];
+            const float* __restrict__ probs = dmem_ptr(L.probs);
+            const float* __restrict__ dsc = dmem_ptr(L.dsc);
+            for (int i = lane; i < lf; i += 64) {
+                const int r = i / H, h = i - r * H;
+                float p, d;
+                dmem_stage(probs, dsc, b, h, s0 + r, S, H, drop_p, drop_thr, L.drop_site, rng, p, d);
+                xm_lds[2 * j * lf + i] = p;
+                xm_lds[(2 * j + 1) * lf + i] = d;
+            }
+        }
+        __syncthreads();
+        if (active)
+            for (int j = 0; j < n; ++j) {
+                const XmemDmemLayer L = tab[l1 - 1 - j];
+                dmem_add_heads(a, dmem_ptr(L.dmbar), dmem_ptr(L.qk), xm_lds + 2 * j * lf, xm_lds + (2 * j + 1) * lf, H, b, H, E, e, set, sets);
+            }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int i = 0; i < DMEM_ROWS; ++i) {
+        const int r = set + i * sets, s_ = s0 + r;
+        if (r < DMEM_ROWS && s_ < S) *reinterpret_cast<float4*>(dmem + ((long)s_ * B + b) * E + e) = a[i];
+    }
+}
+SLNLP_ZKERNEL(xmem_dmem_all_kernel, 256, xmem_dmem_all_body)
 
 // out[c] = sum_r in[r, c] in row order (d bv)
 __device__ __forceinline__ void xmem_colsum_body(const float* __restrict__ in, int R, int C, float* __restrict__ out) {
@@ -515,12 +614,13 @@ int xmem_fwd(const float* qk, const float* mem, const float* bv, int B, int S, i
                    dropout_threshold(drop_p), drop_site, rng);
 }
 
-// from d mbar = Wv_h^T d ctx_h: d scores, d qk, d ctx * sum_s p_s; then d memory (+= over the decoder layers) and d bv
+// from d mbar = Wv_h^T d ctx_h: d scores, d qk, d ctx * sum_s p_s; then d memory (+= over the decoder layers) and d bv --
+// unless dmem is null: the caller then runs xmem_dmem_all behind its layer loop (d memory of all layers and every d bv)
 int xmem_bwd(const float* mem, const float* bv, const float* probs, const float* psum, const float* qk, const float* dmbar,
              const float* dctx, int B, int S, int H, int dh, float* dsc, float* dqk, float* dcp, float* dbv, float* dmem, int accumulate,
              float drop_p, int drop_site, const unsigned long long* rng, hipStream_t st) {
     SLNLP_TRY(xmem_check("xmem_bwd", B, S, H, dh));
-    SLNLP_CHECK_ARG(mem && bv && probs && psum && qk && dmbar && dctx && dsc && dqk && dcp && dbv && dmem, "xmem_bwd: null pointer");
+    SLNLP_CHECK_ARG(mem && bv && probs && psum && qk && dmbar && dctx && dsc && dqk && dcp && dbv, "xmem_bwd: null pointer");
     SLNLP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || rng), "xmem_bwd: bad dropout args");
     const int E = H * dh;
     if (const int hp = xmem_heads_per_wg(B, S, H, dh); hp > 1) {
@@ -535,8 +635,22 @@ int xmem_bwd(const float* mem, const float* bv, const float* probs, const float*
         SLNLP_TRY(zlaunch(xmem_bwd_kernel, dim3(B * H), 256, lds, st, "xmem_bwd", mem, bv, probs, psum, dmbar, dctx, B, S, H, dh, dsc, dqk, dcp,
                           drop_p, dropout_threshold(drop_p), drop_site, rng));
     }
+    if (!dmem) return 0;
     return zlaunch(xmem_dmem_kernel, dim3(ceil_div(S, DMEM_ROWS) * B + ceil_div(E, 256)), 256, 0, st, "xmem_dmem", probs, (const float*)dsc, dmbar, qk, B, S, H, E, dmem,
                    accumulate, drop_p, dropout_threshold(drop_p), drop_site, rng, (const float*)dcp, dbv);
+}
+
+// d memory [S*B, E] = the sum over the N decoder layers (N - 1 ... 0) of what xmem_bwd's d-memory launch adds, and every layer's
+// d bv, in one launch; tab: device table [N] of the layers' buffers (all written by xmem_bwd(dmem = nullptr) calls before)
+int xmem_dmem_all(const XmemDmemLayer* tab, int N, int B, int S, int H, int dh, float* dmem, float drop_p, const unsigned long long* rng,
+                  hipStream_t st) {
+    SLNLP_TRY(xmem_check("xmem_dmem_all", B, S, H, dh));
+    SLNLP_CHECK_ARG(tab && dmem && N > 0, "xmem_dmem_all: null pointer / no layers");
+    SLNLP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || rng), "xmem_dmem_all: bad dropout args");
+    const int E = H * dh, n = N < DMEM_STAGE_LAYERS ? N : DMEM_STAGE_LAYERS;
+    const size_t lds = (size_t)n * 2 * DMEM_ROWS * H * sizeof(float);        // <= 8 x 2 x 8 x 64 floats = 32 KiB
+    return zlaunch(xmem_dmem_all_kernel, dim3(ceil_div(S, DMEM_ROWS) * B + N * ceil_div(E, 256)), 256, lds, st, "xmem_dmem_all", tab, N, B, S, H, E,
+                   dmem, drop_p, dropout_threshold(drop_p), rng);
 }
 
 }  // namespace slnlp

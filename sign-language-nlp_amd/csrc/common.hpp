@@ -334,6 +334,15 @@ int xmem_fwd(const float* qk, const float* mem, const float* bv, int B, int S, i
 int xmem_bwd(const float* mem, const float* bv, const float* probs, const float* psum, const float* qk, const float* dmbar,
              const float* dctx, int B, int S, int H, int dh, float* dsc, float* dqk, float* dcp, float* dbv, float* dmem, int accumulate,
              float drop_p, int drop_site, const unsigned long long* rng, hipStream_t st);
+// one decoder layer's buffers as xmem_dmem_all reads them (a device table the plan uploads once)
+struct XmemDmemLayer {
+    const float *probs, *dsc, *dmbar, *qk, *dcp;
+    float* dbv;
+    int drop_site;
+    int pad;
+};
+int xmem_dmem_all(const XmemDmemLayer* tab, int N, int B, int S, int H, int dh, float* dmem, float drop_p, const unsigned long long* rng,
+                  hipStream_t st);
 int layernorm_fwd(const float* x, const float* gamma, const float* beta, int rows, int E, float eps, float* y,
                   float* stats, hipStream_t st, PlaneOut po = {});
 int ln_bwd_blocks(int rows);

@@ -131,6 +131,16 @@ int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, sln
         }
         ent(w.lnp_fin, p->L.decn_w, p->L.decn_b, 1, w.gfin, w.dec[N - 1].t3, w.st_fin);
     }
+    // the decoder layers' cross-attention gradient buffers (xmem_dmem_all): pointers of the plan's own, uploaded once
+    std::vector<XmemDmemLayer> dtab;
+    for (int i = 0; i < cfg->N; ++i) {
+        const DecA& a = p->w.dec[i];
+        XmemDmemLayer e;
+        e.probs = a.xprobs; e.dsc = a.dsc; e.dmbar = a.dmbar; e.qk = a.qk; e.dcp = a.dcp;
+        e.dbv = p->G(p->L.dec[i].cin_b) + 2 * cfg->E; e.drop_site = p->dec_site(i, 2); e.pad = 0;
+        dtab.push_back(e);
+    }
+    ok = ok && hipMemcpy(p->w.dmem_tab, dtab.data(), dtab.size() * sizeof(dtab[0]), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(p->w.ln_table, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(p->w.ln_ptable, ptab.data(), ptab.size() * sizeof(ptab[0]), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemset(buf->grads, 0, p->L.total * sizeof(float)) == hipSuccess &&
@@ -311,6 +321,8 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
     SLNLP_TRY(layernorm_bwd(w.gfin, w.dec[c.N - 1].t3, pl->P(L.decn_w), w.st_fin, B, E, nullptr, w.gtl, nullptr, 0.f, 0,
                             rng, nullptr, nullptr, 0, st));
     const float* dt = w.gtl;  // gradient w.r.t. the current decoder layer's output
+    // d memory has no reader before the encoder's final LayerNorm: the layers leave it (and d bv) to one launch behind the loop
+    float* const gmem_l = pl->dmem_batched ? nullptr : w.gmem;
     for (int l = c.N - 1; l >= 0; --l) {
         const DecP& q = L.dec[l];
         const DecA& a = w.dec[l];
@@ -332,7 +344,7 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
                 const slnlp_gemm_args j1 = pl->head_expand(a.gxctx, Wv, a.dmbar, B, H, dh);
                 SLNLP_TRY(gemm_group(&j1, 1, st));
                 SLNLP_TRY(xmem_bwd(w.mem, pl->P(q.cin_b) + 2 * E, a.xprobs, a.psum, a.qk, a.dmbar, a.gxctx, B, S, H, dh, a.dsc, a.dqk, a.dcp,
-                                   pl->G(q.cin_b) + 2 * E, w.gmem, l == c.N - 1 ? 0 : 1, p, pl->dec_site(l, 2), rng, st));
+                                   pl->G(q.cin_b) + 2 * E, gmem_l, l == c.N - 1 ? 0 : 1, p, pl->dec_site(l, 2), rng, st));
                 slnlp_gemm_args jobs[3] = {pl->head_reduce(a.dqk, Wk, a.gq, nullptr, B, H, dh),
                                            pl->head_wgrad(a.q, a.dqk, pl->G(q.cin_w) + (long)E * E, B, H, dh),
                                            pl->head_wgrad(a.gxctx, a.mbar, pl->G(q.cin_w) + 2L * E * E, B, H, dh)};
@@ -363,15 +375,15 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
         const float* d2 = p > 0.f ? a.gB2 : a.gA2;
         SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d2, E, B, E, a.xctx, E, pl->G(q.cout_w), pl->G(q.cout_b)),
                                  pl->dgrad_args(d2, E, B, E, pl->P(q.cout_w), E, a.gxctx, nullptr, 0.f, nullptr), st));
-        // d ctx -> d mbar = Wv_h^T d ctx_h (batched GEMM) -> d scores, d qk, d memory (accumulated over the decoder layers in
-        // layer order), d bv -> ONE launch of three batched jobs: d q_h = Wk_h d qk, d Wk_h = q_h^T (x) d qk, d Wv_h = d ctx_h^T (x) mbar.
+        // d ctx -> d mbar = Wv_h^T d ctx_h (batched GEMM) -> d scores, d qk (d memory, accumulated over the decoder layers in
+        // layer order, and d bv: here per layer, or for all layers behind the loop -- dmem_batched) -> ONE launch of three batched jobs: d q_h = Wk_h d qk, d Wk_h = q_h^T (x) d qk, d Wv_h = d ctx_h^T (x) mbar.
         // d bk is exactly zero (a shift of all scores): nothing writes it, the gradient arena was zeroed at plan creation.
         {
             const float *Wk = pl->P(q.cin_w) + (long)E * E, *Wv = pl->P(q.cin_w) + 2L * E * E;
             const slnlp_gemm_args j1 = pl->head_expand(a.gxctx, Wv, a.dmbar, B, H, dh);
             SLNLP_TRY(gemm_group(&j1, 1, st));
             SLNLP_TRY(xmem_bwd(w.mem, pl->P(q.cin_b) + 2 * E, a.xprobs, a.psum, a.qk, a.dmbar, a.gxctx, B, S, H, dh, a.dsc, a.dqk, a.dcp,
-                               pl->G(q.cin_b) + 2 * E, w.gmem, l == c.N - 1 ? 0 : 1, p, pl->dec_site(l, 2), rng, st));
+                               pl->G(q.cin_b) + 2 * E, gmem_l, l == c.N - 1 ? 0 : 1, p, pl->dec_site(l, 2), rng, st));
             const slnlp_gemm_args jobs[3] = {pl->head_reduce(a.dqk, Wk, a.gq, nullptr, B, H, dh),
                                              pl->head_wgrad(a.q, a.dqk, pl->G(q.cin_w) + (long)E * E, B, H, dh),
                                              pl->head_wgrad(a.gxctx, a.mbar, pl->G(q.cin_w) + 2L * E * E, B, H, dh)};
@@ -395,6 +407,7 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
                                  pl->dgrad_args(a.gv, E, B, E, pl->P(q.sin_w) + 2L * E * E, E, a.gt0, nullptr, 0.f, a.gA1), sb));
         dt = a.gt0;
     }
+    if (pl->dmem_batched) SLNLP_TRY(xmem_dmem_all(w.dmem_tab, c.N, B, S, H, dh, w.gmem, p, rng, st));
     SLNLP_TRY(embed_bwd(y, 1, B, 1, E, c.Vt, dt, pl->G(L.tgt_emb), sqrtf((float)E), -1, p, SITE_TGT_EMB, rng, w.emb_scratch_tgt, st));
 
     // encoder: needs the complete d memory
@@ -491,6 +504,15 @@ static void tf_drop_graphs(slnlp_tf_plan* pl) {
     (void)hipDeviceSynchronize();   // an exec may still be running
     for (auto& kv : pl->graphs) (void)hipGraphExecDestroy(kv.second);
     pl->graphs.clear();
+}
+
+int slnlp_tf_set_dmem_batched(slnlp_tf_plan* pl, int on) {
+    SLNLP_CHECK_ARG(pl, "tf_set_dmem_batched: null plan");
+    if (pl->dmem_batched == (on != 0)) return 0;
+    pl->dmem_batched = on != 0;
+    ++pl->opts.gen;            // a lockstep group re-records its programs: the launch sequence changed
+    tf_drop_graphs(pl);
+    return 0;
 }
 
 int slnlp_tf_set_criterion(slnlp_tf_plan* pl, const float* class_weight, float label_smoothing, int reduction, void* stream) {
@@ -636,6 +658,7 @@ int slnlp_tf_tap(slnlp_tf_plan* pl, const char* name, float* out, int64_t max_fl
     if (n == "src_embed") { src = pl->w.x0; rows = M; }
     else if (n == "tgt_embed") { src = pl->w.t0; rows = B; }
     else if (n == "memory") { src = pl->w.mem; rows = M; }
+    else if (n == "dmemory") { src = pl->w.gmem; rows = M; }
     else if (n == "logits") { src = pl->w.logits; rows = B; cols = c.Vt; ld = Vp; }
     else if (n == "dlogits") { src = pl->w.dlogits; rows = B; cols = c.Vt; ld = Vp; }
     else if (n.rfind("enc", 0) == 0 && n.find('.') != std::string::npos) {

@@ -186,6 +186,7 @@ struct Ws {
     size_t wb_scr_bytes;
     slnlp_ln_reduce_entry* ln_table;
     LnPartialEntry* ln_ptable;   // the same LayerNorms' (dy, x, stats, partial) for the one ln_param_partial launch of a backward
+    XmemDmemLayer* dmem_tab;     // [N] the decoder layers' cross-attention gradient buffers for the one xmem_dmem_all launch of a backward
     size_t bytes;
 };
 
@@ -306,6 +307,7 @@ static Ws carve(const slnlp_tf_config& c, void* base) {
     w.attn_scratch = c.S > 64 ? (float*)b.take<char>(attn_long_scratch_bytes(c.B, c.S, c.H)) : nullptr;
     w.ln_table = b.take<slnlp_ln_reduce_entry>(5 * c.N + 2);
     w.ln_ptable = b.take<LnPartialEntry>(5 * c.N + 2);
+    w.dmem_tab = b.take<XmemDmemLayer>(c.N);
     // the batched weight-gradient launch: every (layer, Linear) whose pair defers its weight gradient at SOME batch size 1..B, with
     // the largest split factor it takes there -- room for the tables and the scratch of whichever batch size comes
     std::vector<slnlp_gemm_args> wb_jobs;
@@ -399,6 +401,9 @@ struct slnlp_tf_plan {
     TrainOpts opts;                         // slnlp_tf_set_criterion / slnlp_tf_set_update
     int nbE = 0, nbD = 0;  // (dgamma, dbeta) chunk counts of the FULL batch (fixed: the reduce table is static)
     int destroy_sync = 1;  // slnlp_tf_set_destroy_sync: wait for the device before the plan goes away (launch.hpp)
+    // slnlp_tf_set_dmem_batched: d memory of all decoder layers (and their d bv) in ONE launch behind the decoder's layer loop
+    // (attention_mem.hip: xmem_dmem_all) instead of a launch per layer inside it -- nothing on the decoder's chain reads d memory
+    bool dmem_batched = true;
     // Lockstep (lockstep.hip): where this fit's per-step outputs go while it advances as one of K fits -- an epoch-long
     // log-prob buffer and a per-batch loss history, indexed through two device scalars the driver updates per step
     float* ls_logp = nullptr;       // [rows of the epoch, Vt]

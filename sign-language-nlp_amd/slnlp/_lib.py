@@ -170,6 +170,7 @@ SIGNATURES = {
     "slnlp_tf_set_destroy_sync": (i32, [vp, i32]),
     "slnlp_tf_set_criterion": (i32, [vp, vp, f32, i32, vp]),
     "slnlp_tf_set_update": (i32, [vp, i32, f32, f32, i32]),
+    "slnlp_tf_set_dmem_batched": (i32, [vp, i32]),
     "slnlp_set_stream_policy": (i32, [i32]),
     "slnlp_set_thread_stream_policy": (i32, [i32]),
     "slnlp_set_backward_passes": (i32, [i32, i32]),

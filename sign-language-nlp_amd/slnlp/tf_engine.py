@@ -150,6 +150,12 @@ class TransformerEngine:
                                              int(bool(nesterov))), "tf_set_update")
         self._graph_keys = {}
 
+    def set_dmem_batched(self, on=True):
+        """d memory of all decoder layers in one launch behind the decoder's backward loop (default) or a launch per layer
+        inside it: same bits, an A / B switch."""
+        check(load().slnlp_tf_set_dmem_batched(self.handle, int(bool(on))), "tf_set_dmem_batched")
+        self._graph_keys = {}
+
     def set_lr(self, lr):
         self.lr.fill_(float(lr))
 
