@@ -287,6 +287,28 @@ int slnlp_clip_adam_step(float* params, const float* grads, float* exp_avg, floa
                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                          float* partials /* [1024] scratch */, float* norm_out, float* step_count, void* stream);
 
+/* Per-parameter-group learning rate and weight decay (torch's optimizer param_groups) for the two updates above.  The
+ * arena of n floats is cut into n_segments segments: segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last
+ * one runs to n -- and belongs to group seg_group[s] in [0, n_groups).  seg_begin[0] is 0, the entries are multiples of 4
+ * and strictly increasing; at most 1024 segments (SLNLP_ERR_INVALID_ARG above that).  seg_begin, seg_group and
+ * weight_decay [n_groups] are HOST arrays, copied into device memory the handle owns (the upload is ordered on stream).
+ * The groups' learning rates are not part of the table: every step reads them from lr_dev [n_groups] in device memory. */
+typedef struct slnlp_param_groups slnlp_param_groups;
+int slnlp_param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
+                              const float* weight_decay, void* stream, slnlp_param_groups** out);
+void slnlp_param_groups_destroy(slnlp_param_groups* groups);
+/* slnlp_clip_sgd_step_ex / slnlp_clip_adam_step / slnlp_clip_adamw_step (decoupled != 0) with lr and weight decay taken per
+ * element from its group: same two launches, same norm, same clip, same counters.  One segment that covers the arena gives
+ * the bits of the one-group entry points. */
+int slnlp_clip_sgd_step_groups(float* params, const float* grads, float* momentum_buf, int64_t n,
+                               const slnlp_param_groups* groups, const float* lr_dev /* [n_groups] */, float momentum,
+                               float dampening, int nesterov, float max_norm, float* partials /* [1024] scratch */,
+                               float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream);
+int slnlp_clip_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                const slnlp_param_groups* groups, const float* lr_dev /* [n_groups] */, float beta1,
+                                float beta2, float eps, int decoupled, float max_norm, float* partials /* [1024] scratch */,
+                                float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.
@@ -509,6 +531,12 @@ int slnlp_tf_set_destroy_sync(slnlp_tf_plan* plan, int on);
 #define SLNLP_UPDATE_ADAMW 2
 int slnlp_tf_set_criterion(slnlp_tf_plan* plan, const float* class_weight, float label_smoothing, int reduction, void* stream);
 int slnlp_tf_set_update(slnlp_tf_plan* plan, int kind, float dampening, float weight_decay, int nesterov);
+/* Per-group lr / weight decay of the plan's update (arguments as slnlp_param_groups_create, over the plan's arena):
+ * slnlp_tf_optim / slnlp_tf_optim_adam then step group g with lr_dev[g] (device memory, [n_groups], the caller's, read
+ * every step) and weight_decay[g] instead of the plan's one lr and the one weight decay.  n_segments == 0 clears the table:
+ * the one-group update again.  Drops the captured graphs and makes a lockstep group re-record, as slnlp_tf_set_update. */
+int slnlp_tf_set_param_groups(slnlp_tf_plan* plan, int n_segments, const int64_t* seg_begin, const int32_t* seg_group,
+                              int n_groups, const float* weight_decay, const float* lr_dev, void* stream);
 /* Where backward forms the gradient with respect to the encoder memory (and the cross-attention value biases' gradients).
  * on (default): one launch for all decoder layers behind the decoder's layer loop -- nothing on that chain reads the sum;
  * off: a launch per layer inside the loop, each adding onto the sum.  Same bits either way (the same fp32 operations in the
@@ -590,6 +618,10 @@ int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* group, float* const* exp_avg_s
  * From then on a TRAIN step with batch index step_index first stores table[f][step_index] into plan f's buf.lr -- inside the
  * gather launch every step already issues, so num_launches does not change -- and then runs the recorded program;
  * step_index >= n_steps is an argument error (nothing is launched).  Eval steps never touch buf.lr.  Drops no recorded program.
+ * A plan with param groups (slnlp_tf_set_param_groups, G groups) has G rates per step: its table is n_steps x G floats, row
+ * step_index goes to its lr_dev[0..G).  Fits with different groups, or with none, share a group: as soon as one fit has
+ * groups every fit's update is recorded through the grouped kernel -- one launch per call site -- the fits without groups
+ * with a one-segment table over their arena (their own buf.lr and weight decay: the one-group kernel's bits).
  * The pointer table's upload is ordered on `stream`, as set_data's. */
 int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* group, const float* const* table, int n_steps, void* stream);
 /* per-fit visit order of one data slot (a shuffled epoch): order[f] = n_visit int64 row indices into fit f's dataset of that
@@ -652,6 +684,9 @@ int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* plan, int on);   /* as slnlp_tf_s
  * weight decay, as torch skips a parameter whose grad is None */
 int slnlp_rnn_set_criterion(slnlp_rnn_plan* plan, const float* class_weight, float label_smoothing, int reduction, void* stream);
 int slnlp_rnn_set_update(slnlp_rnn_plan* plan, int kind, float dampening, float weight_decay, int nesterov);
+/* as slnlp_tf_set_param_groups */
+int slnlp_rnn_set_param_groups(slnlp_rnn_plan* plan, int n_segments, const int64_t* seg_begin, const int32_t* seg_group,
+                               int n_groups, const float* weight_decay, const float* lr_dev, void* stream);
 int slnlp_rnn_train_step(slnlp_rnn_plan* plan, const int64_t* X, const int64_t* y, const int64_t* lengths, int B,
                          float momentum, float max_norm, float* logp, void* stream);
 int slnlp_rnn_graph_capture_train(slnlp_rnn_plan* plan, const int64_t* X, const int64_t* y, const int64_t* lengths,

@@ -420,7 +420,45 @@ int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp
                    float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
                    unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,
                    AdamOpts ao = {});
-// A plan's criterion and update settings (slnlp_{tf,rnn}_set_criterion / _set_update).  The class weights are copied into
+// Per-parameter-group lr / weight decay of the fused update (optimizer__param_groups).  The arena is cut into segments
+// on float4 boundaries (arena entries are 16-byte aligned: a float4 never straddles two parameters); segment s covers
+// float4 indices [seg_begin4[s], seg_begin4[s + 1]) -- the last one runs to the arena's end -- and belongs to group
+// seg_group[s]; group g steps with lr[g] and wd[g].  All four arrays are device memory; lr is the caller's (schedules
+// write it between steps: captured graphs and recorded lockstep programs read it, they never bake it in).
+constexpr int GROUPS_MAX_SEGMENTS = 1024;
+struct GroupTab {
+    const int* seg_begin4 = nullptr;
+    const int* seg_group = nullptr;
+    const float* wd = nullptr;
+    const float* lr = nullptr;
+    int n_seg = 0;
+};
+}  // namespace slnlp
+// the device copy of a segment table (slnlp_param_groups_create); any_wd: whether a group decays (SGD: the general update)
+struct slnlp_param_groups {
+    int* dev = nullptr;                     // one allocation: seg_begin4 [n_seg] | seg_group [n_seg] | wd [n_groups]
+    std::vector<int> host;                  // what it holds (the upload's source, alive as long as the table)
+    int n_seg = 0, n_groups = 0;
+    int64_t n = 0;
+    bool any_wd = false;
+    slnlp::GroupTab tab(const float* lr_dev) const {
+        return slnlp::GroupTab{dev, dev + n_seg, reinterpret_cast<const float*>(dev + 2 * n_seg), lr_dev, n_seg};
+    }
+};
+namespace slnlp {
+int param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
+                        const float* weight_decay, hipStream_t st, slnlp_param_groups** out);
+void param_groups_destroy(slnlp_param_groups* pg);
+// the grouped forms of clip_sgd_step / clip_adam_step: lr and weight decay per element from its group, the rest as there
+int clip_sgd_step_groups(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* pg,
+                         const float* lr_dev, float momentum, float max_norm, float* partials, float* norm_out,
+                         unsigned long long* rng, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,
+                         SgdOpts so = {});
+int clip_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                          const slnlp_param_groups* pg, const float* lr_dev, float beta1, float beta2, float eps, float max_norm,
+                          float* partials, float* norm_out, unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {},
+                          int64_t wp_begin = 0, int64_t wp_end = -1, AdamOpts ao = {});
+// A plan's criterion and update settings (slnlp_{tf,rnn}_set_criterion / _set_update / _set_param_groups).  The class weights are copied into
 // device memory the plan owns, so recorded programs and captured graphs keep a valid pointer; `gen` moves on every change
 // (a lockstep group re-records its programs when a fit's generation moved).
 struct TrainOpts {
@@ -431,6 +469,15 @@ struct TrainOpts {
     int kind = 0;                           // SLNLP_UPDATE_SGD / _ADAM / _ADAMW
     float dampening = 0.f, weight_decay = 0.f;
     int nesterov = 0;
+    slnlp_param_groups* groups = nullptr;   // per-group lr / weight decay (owned), or nullptr: one lr, one weight decay
+    const float* groups_lr = nullptr;       // [n_groups] device rates of `groups` (the caller's)
+    // A lockstep group that holds a fit WITH groups records every fit's update through the grouped kernel (one kernel per call
+    // site): a fit without groups then steps with a one-segment table over its arena -- its own lr scalar, its own weight
+    // decay: the one-group kernel's bits.  `force_groups` is up only while the group records; `one` is that table (owned).
+    bool force_groups = false;
+    slnlp_param_groups* one = nullptr;
+    int one_segment(int64_t n, float wd, hipStream_t st, const slnlp_param_groups** out);
+    int n_groups() const { return groups ? groups->n_groups : 0; }
     unsigned gen = 0;
     TrainOpts() = default;
     TrainOpts(const TrainOpts&) = delete;
@@ -449,6 +496,9 @@ struct TrainOpts {
     // cw: host memory; uploaded to the plan's copy on `st`
     int set_criterion(int V, const float* cw, float eps, int reduction, hipStream_t st, bool* changed);
     int set_update(int kind, float dampening, float weight_decay, int nesterov, bool* changed);
+    // n: the plan's arena floats; n_segments == 0 clears the table (the one-group update again).  Always counts as a change.
+    int set_param_groups(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
+                         const float* weight_decay, const float* lr_dev, hipStream_t st);
 };
 
 // Which version of a parameter arena a plan's derived data (bf16 weight planes) was made from: every optimizer step and

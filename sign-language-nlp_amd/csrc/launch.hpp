@@ -60,6 +60,14 @@ __device__ __forceinline__ PlaneOut as_global(PlaneOut po) {
     return po;
 }
 
+__device__ __forceinline__ GroupTab as_global(GroupTab gt) {
+    gt.seg_begin4 = as_global(gt.seg_begin4);
+    gt.seg_group = as_global(gt.seg_group);
+    gt.wd = as_global(gt.wd);
+    gt.lr = as_global(gt.lr);
+    return gt;
+}
+
 // the per-direction argument structs travel inside kernel argument packs: their pointers get the same global
 // address-space treatment as bare pointer arguments (declared before PackOf so its calls see them)
 __device__ __forceinline__ slnlp_rnn_cell_dir as_global(slnlp_rnn_cell_dir d) {

@@ -25,7 +25,8 @@
 //
 // Learning-rate tables (slnlp_*_lockstep_set_lr_table): a per-batch schedule cannot come from the host inside an epoch that
 // never synchronises, so the same gather launch also stores table[f][batch index] into fit f's lr scalar (the float the
-// recorded update launches read through the pointer they always had) ahead of every TRAIN step.
+// recorded update launches read through the pointer they always had) ahead of every TRAIN step.  A fit with per-parameter-group
+// rates (slnlp_*_set_param_groups, G groups) has G floats there -- its plan's lr_dev -- and its table row is [n_steps][G].
 //
 // Order tables (slnlp_*_lockstep_set_order): a shuffled epoch visits the rows of a slot in an order the host drew before the
 // epoch (torch's RandomSampler, slnlp/sampler.py).  The gather launch then stages row order[f][row0 + i] instead of row
@@ -53,6 +54,7 @@ void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train);
 const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl);
 unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl);
 float* rnn_ls_lr(slnlp_rnn_plan* pl);
+int rnn_ls_groups(slnlp_rnn_plan* pl, int force);
 
 struct GatherArgs {
     const int64_t* const* X;     // [K] dataset pointers (device table)
@@ -63,7 +65,8 @@ struct GatherArgs {
     int64_t* const* Lst;
     int* dyn;                    // {row0, batch index}
     const float* const* lr_table;   // [K] per-fit learning rates by batch index (device table; entries may be nullptr), or nullptr
-    float* const* lr;               // [K] each fit's lr scalar (device table)
+    float* const* lr;               // [K] each fit's lr scalar, or its G group rates (device table)
+    const int* lr_width;            // [K] floats per step of fit f's table: 1, or G with param groups (device table)
     const int64_t* const* order;    // [K] per-fit visit order of the slot, n_visit row indices (device table; entries may be nullptr), or nullptr
     int S, row0, B, step;
 };
@@ -113,9 +116,11 @@ __global__ __launch_bounds__(256) void ls_gather_kernel(const GatherArgs a) {
             a.dyn[0] = a.row0;
             a.dyn[1] = a.step;
         }
-        if (a.lr_table && threadIdx.x == 0) {       // train steps of a group with tables: this batch's rate, before the program runs
+        if (a.lr_table) {                           // train steps of a group with tables: this batch's rate(s), before the program runs
             const float* t = a.lr_table[f];
-            if (t) *a.lr[f] = t[a.step];
+            const int w = a.lr_width[f];
+            if (t)
+                for (int g = threadIdx.x; g < w; g += 256) a.lr[f][g] = t[(long)a.step * w + g];
         }
     }
 }
@@ -147,7 +152,8 @@ struct LsFit {
     void (*outputs)(void* plan, float* logp, float* loss, const int* dyn);
     void (*replayed)(void* plan, int B, int train);         // host bookkeeping after the step's launches were issued
     unsigned (*opts_gen)(void* plan);                       // generation of the plan's criterion / update settings (TrainOpts)
-    float* (*lr)(void* plan);                               // the device float the plan's update launches read the learning rate from
+    float* (*lr)(void* plan);                               // the device float(s) the plan's update launches read the learning rate from
+    int (*groups)(void* plan, int force);                   // the plan's param-group count (0: none); force >= 0 sets TrainOpts::force_groups
 };
 
 struct LockstepGroup {
@@ -163,7 +169,8 @@ struct LockstepGroup {
     int64_t** d_Lst = nullptr;
     int* dyn = nullptr;
     // slnlp_*_lockstep_set_lr_table: both pointer tables sit below ws_mark (never reclaimed); d_lr_table is rewritten in place
-    float** d_lr = nullptr;                         // device table [K]: each fit's lr scalar
+    float** d_lr = nullptr;                         // device table [K]: each fit's lr scalar / group rates
+    int* d_lr_width = nullptr;                      // device table [K]: floats per step of each fit's table
     const float** d_lr_table = nullptr;             // device table [K]: the caller's per-fit tables (nullptr: leave that fit alone)
     int lr_steps = 0;                               // floats per table; 0: no tables set
     struct Slot {
@@ -366,6 +373,7 @@ static int replay(const Program& prog, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------ generic driver ----
+static int upload_lr_targets(LockstepGroup* ls, hipStream_t st);
 static int ls_init(LockstepGroup* ls, int B, int S, void* workspace, int64_t workspace_bytes, hipStream_t st) {
     const int K = (int)ls->fits.size();
     ls->K = K; ls->S = S; ls->maxB = B;
@@ -384,9 +392,10 @@ static int ls_init(LockstepGroup* ls, int B, int S, void* workspace, int64_t wor
     SLNLP_TRY(upload(ls, ls->Xst.data(), K * sizeof(void*), (void**)&ls->d_Xst, st));
     SLNLP_TRY(upload(ls, ls->yst.data(), K * sizeof(void*), (void**)&ls->d_yst, st));
     if (ls->has_len) SLNLP_TRY(upload(ls, ls->Lst.data(), K * sizeof(void*), (void**)&ls->d_Lst, st));
-    std::vector<float*> lr(K);
-    for (int f = 0; f < K; ++f) lr[f] = ls->fits[f].lr(ls->fits[f].plan);
-    SLNLP_TRY(upload(ls, lr.data(), K * sizeof(void*), (void**)&ls->d_lr, st));
+    ls->d_lr = (float**)ls->take(K * sizeof(void*));
+    ls->d_lr_width = (int*)ls->take(K * sizeof(int));
+    SLNLP_CHECK_ARG(ls->d_lr && ls->d_lr_width, "lockstep_create: workspace too small");
+    SLNLP_TRY(upload_lr_targets(ls, st));
     ls->d_lr_table = (const float**)ls->take(K * sizeof(void*));
     SLNLP_CHECK_ARG(ls->d_lr_table, "lockstep_create: workspace too small");
     for (int k = 0; k < LS_SLOTS; ++k) {
@@ -394,6 +403,25 @@ static int ls_init(LockstepGroup* ls, int B, int S, void* workspace, int64_t wor
         SLNLP_CHECK_ARG(ls->slot[k].d_order, "lockstep_create: workspace too small");
     }
     ls->ws_mark = ls->ws_used;
+    return 0;
+}
+
+// where each fit's update reads its rate(s) and how many there are: follows the plans' param-group settings (re-uploaded in place
+// when a fit's settings generation moved)
+static int upload_lr_targets(LockstepGroup* ls, hipStream_t st) {
+    std::vector<float*> lr(ls->K);
+    std::vector<int> width(ls->K);
+    for (int f = 0; f < ls->K; ++f) {
+        lr[f] = ls->fits[f].lr(ls->fits[f].plan);
+        const int g = ls->fits[f].groups(ls->fits[f].plan, -1);
+        width[f] = g > 0 ? g : 1;
+    }
+    if (hipMemcpyAsync(ls->d_lr, lr.data(), ls->K * sizeof(void*), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(ls->d_lr_width, width.data(), ls->K * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {       // pageable host memory: as upload()
+        set_error("lockstep: learning-rate target upload failed: %s", hipGetErrorString(hipGetLastError()));
+        return SLNLP_ERR_LAUNCH;
+    }
     return 0;
 }
 
@@ -516,6 +544,7 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
         ls->ws_used = ls->ws_mark;
         for (int k = 0; k < LS_SLOTS; ++k)
             if (ls->slot[k].set) SLNLP_TRY(upload_slot_tables(ls, ls->slot[k], st));
+        SLNLP_TRY(upload_lr_targets(ls, st));          // a fit's param groups may have come or gone
     }
     for (LsFit& f : ls->fits) SLNLP_TRY(f.prepare(f.plan, B, st));
     const auto key = std::make_tuple(slot, B, train ? 1 : 0);
@@ -523,6 +552,11 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     if (it == ls->programs.end()) {
         std::vector<Recorder> recs(ls->K);
         int rc = 0;
+        // one kernel per call site: as soon as one fit has param groups, every fit records the grouped update (the others with a
+        // one-segment table: the one-group kernel's bits)
+        bool any_groups = false;
+        for (LsFit& f : ls->fits) any_groups = any_groups || f.groups(f.plan, -1) > 0;
+        for (LsFit& f : ls->fits) f.groups(f.plan, any_groups ? 1 : 0);
         for (int f = 0; f < ls->K && !rc; ++f) {
             LsFit& fit = ls->fits[f];
             fit.outputs(fit.plan, s.logp[f], s.loss[f], ls->dyn);
@@ -531,6 +565,7 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
                             ls->use_adam ? ls->v2[f] : nullptr, st);
             set_recorder(nullptr);
         }
+        for (LsFit& f : ls->fits) f.groups(f.plan, 0);      // a solo step of such a plan takes its own kernel again
         if (rc) return rc;
         Program prog;
         SLNLP_TRY(merge(ls, recs, prog, st));
@@ -542,6 +577,7 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     g.Xst = ls->d_Xst; g.yst = ls->d_yst; g.Lst = ls->d_Lst; g.dyn = ls->dyn;
     g.lr_table = train && ls->lr_steps ? ls->d_lr_table : nullptr;      // eval steps never touch the learning rate
     g.lr = ls->d_lr;
+    g.lr_width = ls->d_lr_width;
     g.order = s.n_visit ? s.d_order : nullptr;
     g.S = ls->S; g.row0 = (int)row0; g.B = B; g.step = step_index;
     int gx = (B * ls->S + 255) / 256;
@@ -629,10 +665,19 @@ static void rnn_replayed(void* p, int B, int train) { rnn_ls_replayed((slnlp_rnn
 static unsigned rnn_opts_gen(void* p) { return rnn_ls_opts_gen((slnlp_rnn_plan*)p); }
 static unsigned tf_opts_gen(void* p) { return ((slnlp_tf_plan*)p)->opts.gen; }
 static float* rnn_lr(void* p) { return rnn_ls_lr((slnlp_rnn_plan*)p); }
-static float* tf_lr(void* p) { return ((slnlp_tf_plan*)p)->buf.lr; }
+static float* tf_lr(void* p) {
+    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
+    return pl->opts.groups ? const_cast<float*>(pl->opts.groups_lr) : pl->buf.lr;
+}
+static int tf_groups(void* p, int force) {
+    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
+    if (force >= 0) pl->opts.force_groups = force != 0;
+    return pl->opts.n_groups();
+}
+static int rnn_groups(void* p, int force) { return rnn_ls_groups((slnlp_rnn_plan*)p, force); }
 
 // the two learning-rate pointer tables of ls_init and the slots' order tables, each on a 256-byte boundary of the bump allocator
-static size_t ls_lr_table_bytes(int K) { return (2 + LS_SLOTS) * (((size_t)K * sizeof(void*) + 255) & ~(size_t)255); }
+static size_t ls_lr_table_bytes(int K) { return (3 + LS_SLOTS) * (((size_t)K * sizeof(void*) + 255) & ~(size_t)255); }
 
 extern "C" {
 
@@ -669,7 +714,7 @@ int slnlp_tf_lockstep_create(slnlp_tf_plan** plans, int K, void* workspace, int6
         for (int g = 0; g < f; ++g) SLNLP_CHECK_ARG(plans[g] != plans[f], "lockstep_create: plan %d listed twice", f);
     }
     slnlp_tf_lockstep* ls = new slnlp_tf_lockstep();
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed, tf_opts_gen, tf_lr});
+    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed, tf_opts_gen, tf_lr, tf_groups});
     const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;
@@ -738,7 +783,7 @@ int slnlp_rnn_lockstep_create(slnlp_rnn_plan** plans, int K, void* workspace, in
     }
     slnlp_rnn_lockstep* ls = new slnlp_rnn_lockstep();
     ls->has_len = true;
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed, rnn_opts_gen, rnn_lr});
+    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed, rnn_opts_gen, rnn_lr, rnn_groups});
     const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;

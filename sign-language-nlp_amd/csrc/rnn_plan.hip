@@ -770,6 +770,16 @@ int slnlp_rnn_optim(slnlp_rnn_plan* pl, float momentum, float max_norm, void* st
     SLNLP_CHECK_ARG(pl, "rnn_optim: null plan");
     StepScope scope((hipStream_t)stream);
     SLNLP_TRY(scope.rc);
+    const slnlp_param_groups* pg = pl->opts.groups;
+    const float* pg_lr = pl->opts.groups_lr;
+    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
+        SLNLP_TRY(pl->opts.one_segment(pl->L.total, pl->opts.sgd(nullptr, 0, 0).weight_decay, (hipStream_t)stream, &pg));
+        pg_lr = pl->buf.lr;
+    }
+    if (pg)
+        return clip_sgd_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pg, pg_lr,
+                                    momentum, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
+                                    PlaneOut{}, 0, -1, pl->opts.sgd(pl->buf.scalars + 3, pl->L.pre_out, rnn_pre_out_end(pl)));
     return clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
                          pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream, PlaneOut{}, 0, -1,
                          pl->opts.sgd(pl->buf.scalars + 3, pl->L.pre_out, rnn_pre_out_end(pl)));
@@ -783,6 +793,17 @@ int slnlp_rnn_optim_adam(slnlp_rnn_plan* pl, float* exp_avg_sq, float beta1, flo
     SLNLP_CHECK_ARG(pl && exp_avg_sq, "rnn_optim_adam: null argument");
     StepScope scope((hipStream_t)stream);
     SLNLP_TRY(scope.rc);
+    const slnlp_param_groups* pg = pl->opts.groups;
+    const float* pg_lr = pl->opts.groups_lr;
+    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
+        SLNLP_TRY(pl->opts.one_segment(pl->L.total, weight_decay, (hipStream_t)stream, &pg));
+        pg_lr = pl->buf.lr;
+    }
+    if (pg)                   // weight decay per group: the call's one value is not read
+        return clip_adam_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pg,
+                                     pg_lr, beta1, beta2, eps, max_norm, pl->w.opt_partials, pl->buf.scalars + 1,
+                                     pl->buf.rng, pl->buf.scalars + 2, (hipStream_t)stream, PlaneOut{}, 0, -1,
+                                     pl->opts.adam(pl->L.pre_out, rnn_pre_out_end(pl)));
     return clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
                           weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
                           (hipStream_t)stream, PlaneOut{}, 0, -1, pl->opts.adam(pl->L.pre_out, rnn_pre_out_end(pl)));
@@ -809,6 +830,15 @@ int slnlp_rnn_set_update(slnlp_rnn_plan* pl, int kind, float dampening, float we
     SLNLP_TRY(pl->opts.set_update(kind, dampening, weight_decay, nesterov, &changed));
     if (changed) rnn_drop_graphs(pl);
     return 0;
+}
+
+int slnlp_rnn_set_param_groups(slnlp_rnn_plan* pl, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
+                               const float* weight_decay, const float* lr_dev, void* stream) {
+    SLNLP_CHECK_ARG(pl, "rnn_set_param_groups: null plan");
+    SLNLP_CHECK_ARG(n_segments >= 0, "rnn_set_param_groups: %d segments", n_segments);
+    if (n_segments == 0 && !pl->opts.groups) return 0;
+    rnn_drop_graphs(pl);           // before the old table goes away: a captured update holds its pointers
+    return pl->opts.set_param_groups(pl->L.total, n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
 }
 
 int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* pl, int on) {
@@ -926,5 +956,9 @@ void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train) {
 }
 const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl) { return &pl->cfg; }
 unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl) { return pl->opts.gen; }
-float* rnn_ls_lr(slnlp_rnn_plan* pl) { return pl->buf.lr; }
+float* rnn_ls_lr(slnlp_rnn_plan* pl) { return pl->opts.groups ? const_cast<float*>(pl->opts.groups_lr) : pl->buf.lr; }
+int rnn_ls_groups(slnlp_rnn_plan* pl, int force) {
+    if (force >= 0) pl->opts.force_groups = force != 0;
+    return pl->opts.n_groups();
+}
 }  // namespace slnlp

@@ -469,10 +469,22 @@ int slnlp_tf_optim(slnlp_tf_plan* pl, float momentum, float max_norm, void* stre
     SLNLP_CHECK_ARG(pl, "tf_optim: null plan");
     StepScope scope((hipStream_t)stream);
     SLNLP_TRY(scope.rc);
-    SLNLP_TRY(clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
-                            pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
-                            pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
-                            pl->opts.sgd(pl->buf.scalars + 3, 0, 0)));
+    const slnlp_param_groups* pg = pl->opts.groups;
+    const float* pg_lr = pl->opts.groups_lr;
+    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
+        SLNLP_TRY(pl->opts.one_segment(pl->L.total, pl->opts.sgd(nullptr, 0, 0).weight_decay, (hipStream_t)stream, &pg));
+        pg_lr = pl->buf.lr;
+    }
+    if (pg)
+        SLNLP_TRY(clip_sgd_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pg, pg_lr,
+                                       momentum, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
+                                       pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
+                                       pl->opts.sgd(pl->buf.scalars + 3, 0, 0)));
+    else
+        SLNLP_TRY(clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
+                                pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
+                                pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
+                                pl->opts.sgd(pl->buf.scalars + 3, 0, 0)));
     if (!recording()) pl->params_stepped();      // (a lockstep replay does this per step itself)
     return 0;
 }
@@ -484,10 +496,23 @@ int slnlp_tf_optim_adam(slnlp_tf_plan* pl, float* exp_avg_sq, float beta1, float
     SLNLP_CHECK_ARG(pl && exp_avg_sq, "tf_optim_adam: null argument");
     StepScope scope((hipStream_t)stream);
     SLNLP_TRY(scope.rc);
-    SLNLP_TRY(clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
-                             weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
-                             (hipStream_t)stream, pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
-                             pl->opts.adam(0, 0)));
+    const slnlp_param_groups* pg = pl->opts.groups;
+    const float* pg_lr = pl->opts.groups_lr;
+    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
+        SLNLP_TRY(pl->opts.one_segment(pl->L.total, weight_decay, (hipStream_t)stream, &pg));
+        pg_lr = pl->buf.lr;
+    }
+    if (pg)                   // weight decay per group: the call's one value is not read
+        SLNLP_TRY(clip_adam_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pg,
+                                        pg_lr, beta1, beta2, eps, max_norm, pl->w.opt_partials, pl->buf.scalars + 1,
+                                        pl->buf.rng, pl->buf.scalars + 2, (hipStream_t)stream,
+                                        pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
+                                        pl->opts.adam(0, 0)));
+    else
+        SLNLP_TRY(clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
+                                 weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
+                                 (hipStream_t)stream, pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
+                                 pl->opts.adam(0, 0)));
     if (!recording()) pl->params_stepped();
     return 0;
 }
@@ -529,6 +554,15 @@ int slnlp_tf_set_update(slnlp_tf_plan* pl, int kind, float dampening, float weig
     SLNLP_TRY(pl->opts.set_update(kind, dampening, weight_decay, nesterov, &changed));
     if (changed) tf_drop_graphs(pl);
     return 0;
+}
+
+int slnlp_tf_set_param_groups(slnlp_tf_plan* pl, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
+                              const float* weight_decay, const float* lr_dev, void* stream) {
+    SLNLP_CHECK_ARG(pl, "tf_set_param_groups: null plan");
+    SLNLP_CHECK_ARG(n_segments >= 0, "tf_set_param_groups: %d segments", n_segments);
+    if (n_segments == 0 && !pl->opts.groups) return 0;
+    tf_drop_graphs(pl);            // before the old table goes away: a captured update holds its pointers
+    return pl->opts.set_param_groups(pl->L.total, n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
 }
 
 // The parameter arena was written from outside the library (load_state_dict, a torch optimizer, an in-place edit):

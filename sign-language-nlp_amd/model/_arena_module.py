@@ -189,11 +189,16 @@ class ArenaModule(nn.Module):
         """Public handle for the fused-step estimator (slnlp.net)."""
         return self._engine_for(B, S)
 
-    def set_train_options(self, criterion=None, update=None):
+    def set_train_options(self, criterion=None, update=None, param_groups=None):
         """Criterion and update settings of the fused step, for every plan of the module (now and created later):
         ``criterion`` {weight, label_smoothing, reduction}, ``update`` {kind, dampening, weight_decay, nesterov} -- the
-        keywords of the engines' ``set_criterion`` / ``set_update``.  None leaves that part as it is."""
+        keywords of the engines' ``set_criterion`` / ``set_update``; ``param_groups`` {seg_begin, seg_group, weight_decay}
+        (``slnlp.param_groups.segments``; the engines' ``set_param_groups``) or False: no groups.  None leaves that part as
+        it is."""
         opts = dict(getattr(self, "_train_opts", None) or {})
+        if param_groups is not None:
+            opts["param_groups"] = dict(param_groups) if param_groups else False
+            self._group_lr_host = None
         if criterion is not None:
             opts["criterion"] = dict(criterion)
         if update is not None:
@@ -208,6 +213,34 @@ class ArenaModule(nn.Module):
             eng.set_criterion(**opts["criterion"])
         if "update" in opts:
             eng.set_update(**opts["update"])
+        if "param_groups" in opts:
+            tab = opts["param_groups"]
+            eng.set_param_groups(tab or None, self._group_lr(len(tab["weight_decay"])) if tab else None)
+
+    def _group_lr(self, n):
+        """The groups' learning rates on the device, [n] float32: ONE tensor per module, read by every plan's update."""
+        st = self._shared_state()
+        t = st.get("group_lr")
+        if t is None or t.numel() != n:
+            t = st["group_lr"] = torch.zeros(n, dtype=torch.float32, device=self._arena.device)
+            self._group_lr_host = None
+        return t
+
+    def set_group_lrs(self, lrs):
+        """Write the groups' current rates: a fill launch per rate that moved, queued on the fit's stream like the one-group
+        ``lr.fill_`` -- the host never waits for the stream, so a per-batch schedule costs no synchronisation."""
+        lrs = [float(v) for v in lrs]
+        t = self._group_lr(len(lrs))
+        have = getattr(self, "_group_lr_host", None)
+        for i, v in enumerate(lrs):
+            if have is None or have[i] != v:
+                t[i:i + 1].fill_(v)
+        self._group_lr_host = lrs
+
+    def forget_group_lrs(self):
+        """The device copy of the rates is about to be written from elsewhere (a lockstep group's rate tables): the next
+        ``set_group_lrs`` writes every rate."""
+        self._group_lr_host = None
 
     def _run(self, inputs):
         if self.training and torch.is_grad_enabled():

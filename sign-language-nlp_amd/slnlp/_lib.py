@@ -117,6 +117,10 @@ SIGNATURES = {
     "slnlp_clip_adam_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
     "slnlp_clip_sgd_step_ex": (i32, [vp, vp, vp, i64, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_clip_adamw_step": (i32, [vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, i64, i64, vp]),
+    "slnlp_param_groups_create": (i32, [i64, i32, vp, vp, i32, vp, vp, C.POINTER(vp)]),
+    "slnlp_param_groups_destroy": (None, [vp]),
+    "slnlp_clip_sgd_step_groups": (i32, [vp, vp, vp, i64, vp, vp, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
+    "slnlp_clip_adam_step_groups": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_gather_batch": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
     "slnlp_rnn_cell_fwd": (i32, [i32, C.POINTER(RnnCellDir), i32, i32, i32, vp, f32, i64, f32, i32, vp, vp]),
@@ -142,6 +146,7 @@ SIGNATURES = {
     "slnlp_rnn_set_destroy_sync": (i32, [vp, i32]),
     "slnlp_rnn_set_criterion": (i32, [vp, vp, f32, i32, vp]),
     "slnlp_rnn_set_update": (i32, [vp, i32, f32, f32, i32]),
+    "slnlp_rnn_set_param_groups": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
     "slnlp_rnn_train_step": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp]),
     "slnlp_rnn_graph_capture_train": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp]),
     "slnlp_rnn_graph_launch": (i32, [vp, i32, vp]),
@@ -170,6 +175,7 @@ SIGNATURES = {
     "slnlp_tf_set_destroy_sync": (i32, [vp, i32]),
     "slnlp_tf_set_criterion": (i32, [vp, vp, f32, i32, vp]),
     "slnlp_tf_set_update": (i32, [vp, i32, f32, f32, i32]),
+    "slnlp_tf_set_param_groups": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
     "slnlp_tf_set_dmem_batched": (i32, [vp, i32]),
     "slnlp_set_stream_policy": (i32, [i32]),
     "slnlp_set_thread_stream_policy": (i32, [i32]),

@@ -86,7 +86,7 @@ def build_tasks(param_grid, y, cv, seq_len=48, defaults=None):
 # a shuffled visit order is such a table too: slnlp/sampler.py -- iterator_train__drop_last changes the number of steps and stays
 # shape-defining)
 SHAPE_KEYS_EXCLUDED = ("lr", "module__dropout", "criterion__label_smoothing", "optimizer__weight_decay", "optimizer__dampening",
-                       "optimizer__nesterov", "lr_scheduler", "iterator_train__shuffle")
+                       "optimizer__nesterov", "lr_scheduler", "iterator_train__shuffle", "optimizer__param_groups")
 
 
 def estimate_fit_bytes(params, seq_len, defaults=None, lockstep=1):

@@ -95,18 +95,23 @@ class LockstepGroup:
         self._v2 = list(exp_avg_sq)                      # keep the tensors alive: the C side holds raw pointers
         check(self._fn("set_adam")(self.handle, _ptr_array(self._v2), betas[0], betas[1], eps, weight_decay), f"{self.kind}_lockstep_set_adam")
 
-    def set_lr_tables(self, tables):
+    def set_lr_tables(self, tables, n_steps=None):
         """Per-fit learning rates by train-batch index: a list with, per fit, a contiguous float32 device tensor [n_steps] or None
         (that fit keeps the rate its engine's ``set_lr`` gave it); None (or no tensor at all) clears the setting.  From then on every
-        TRAIN step first stores ``tables[f][step_index]`` into fit f's learning rate, inside the launch that stages the batch."""
+        TRAIN step first stores ``tables[f][step_index]`` into fit f's learning rate, inside the launch that stages the batch.
+        A fit whose engine has param groups (``set_param_groups``, G groups) gives [n_steps, G]: row ``step_index`` goes to its G
+        group rates; ``n_steps`` (default: the first tensor's length) is then the one number the tensors share."""
         given = [t for t in (tables or []) if t is not None]
         if not given:
             self._lr_tables = None
             check(self._fn("set_lr_table")(self.handle, None, 0, self._sp()), f"{self.kind}_lockstep_set_lr_table")
             return
-        n = int(given[0].numel())
-        assert len(tables) == self.K and all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == given[0].device
-                                             for t in given), "lockstep: one float32 device tensor [n_steps] (or None) per fit"
+        n = int(given[0].shape[0]) if n_steps is None else int(n_steps)
+        width = [1 if getattr(e, "_group_lr", None) is None else int(e._group_lr.numel()) for e in self.engines]
+        assert len(tables) == self.K and all(t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n * w and
+                                                           t.device == given[0].device)
+                                             for t, w in zip(tables, width)), \
+            "lockstep: one float32 device tensor [n_steps] ([n_steps, groups] with param groups) or None per fit"
         self._lr_tables = list(tables)                   # keep the tensors alive: the gather launch reads them
         arr = (C.c_void_p * self.K)(*[None if t is None else ptr(t) for t in tables])
         check(self._fn("set_lr_table")(self.handle, arr, n, self._sp()), f"{self.kind}_lockstep_set_lr_table")
@@ -178,7 +183,8 @@ def lockstep_supported(net):
 def _adam_key(net):
     """What the fits of one group must share about their update: the kind and, for Adam / AdamW, the constants the group passes
     to every fit (betas, eps).  The weight decay (each plan's own once its kind is Adam / AdamW: slnlp_*_set_update), SGD's
-    dampening / weight decay / nesterov and the criterion settings are each fit's own (they ride its argument packs)."""
+    dampening / weight decay / nesterov, the criterion settings and the param groups (``optimizer__param_groups``: the table
+    pointer and the rates' pointer) are each fit's own (they ride its argument packs)."""
     from .net import adam_args
     return (net._fused_kind,) + (adam_args(net)[:2] if net._fused_kind in ("adam", "adamw") else ())
 
@@ -246,6 +252,8 @@ def _fit_lockstep_gated(nets, datasets):
             orders = [runs[i].order() for i in active]  # shuffled fits: the epoch's visit order (host), drawn before anything is queued
             for i in active:
                 engines[i].set_lr(nets[i].lr_)
+                if nets[i]._groups is not None:
+                    nets[i].module_.set_group_lrs(nets[i]._lrs)     # what a grouped fit's update reads instead
                 nets[i].module_.train()
                 runs[i].begin_epoch()
             pb = [j for j, (i, t) in enumerate(zip(active, tables)) if t is not None and runs[i].schedule.per_batch]
@@ -253,11 +261,16 @@ def _fit_lockstep_gated(nets, datasets):
                 # the epoch runs without coming back to the host: per-batch rates go to the device as one [fits, batches] tensor
                 # (a host-to-device copy on the fit's stream, alive in the group until the next epoch replaces it), and each
                 # step's gather launch hands every such fit its row's next entry; the other fits keep the rate set above
-                dev_tab = torch.tensor([tables[j] for j in pb], dtype=torch.float32).to(group.device)
-                per_fit = [None] * len(active)
-                for r, j in enumerate(pb):
-                    per_fit[j] = dev_tab[r]
-                group.set_lr_tables(per_fit)
+                # (a fit with param groups has G rates per step: its row is [batches, G], flattened)
+                flat = [[v for row in tables[j] for v in (row if isinstance(row, list) else [row])] for j in pb]
+                dev_tab = torch.tensor([v for f in flat for v in f], dtype=torch.float32).to(group.device)
+                per_fit, at = [None] * len(active), 0
+                for f, j in zip(flat, pb):
+                    per_fit[j] = dev_tab[at:at + len(f)]
+                    at += len(f)
+                    if nets[active[j]]._groups is not None:
+                        nets[active[j]].module_.forget_group_lrs()      # the device writes them from here on
+                group.set_lr_tables(per_fit, n_steps=len(tables[pb[0]]))
             sh = [j for j, o in enumerate(orders) if o is not None]
             if sh or r0.n_visit != len(r0.tr):
                 # the orders go to the device the same way: ONE [fits, 2, n_visit] tensor per epoch -- each shuffled fit's order and

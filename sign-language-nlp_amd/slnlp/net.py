@@ -30,7 +30,7 @@ import importlib
 import numpy as np
 import torch
 
-from . import metrics, ops, sampler, schedule
+from . import metrics, ops, param_groups, sampler, schedule
 from .data import TokenDataset
 
 
@@ -194,11 +194,17 @@ def _resolve(obj):
     return found
 
 
-def fused_kind(criterion, opt_cls, opt_kwargs, module_cls):
+def fused_kind(criterion, opt_cls, opt_kwargs, module_cls, groups=None):
     """Which fused clip + update kernel replaces the torch optimizer of a fit: "sgd", "adam", "adamw", or None (the fit steps
     through torch).  ``criterion`` is the constructed criterion; a ``CrossEntropyLoss`` argument the fused criterion does not
     implement (``reduction="none"``) sends the fit to the torch path -- it is never dropped.  The optimizer arguments are
-    checked by constructing the torch optimizer on a dummy parameter, so bad ones raise torch's own error here."""
+    checked by constructing the torch optimizer on a dummy parameter, so bad ones raise torch's own error here.
+    ``groups``: the ``optimizer__param_groups`` pairs (``optimizer_kwargs`` splits them off): every pair's settings are
+    checked the same way; the fit stays fused while they only name ``lr`` / ``weight_decay`` -- any other per-group key
+    (``momentum``, ``betas``, ...) sends it to the torch path, like ``reduction="none"``."""
+    groups = param_groups.as_pairs(groups)
+    for _, settings in groups:
+        optimizer_defaults(opt_cls, {**opt_kwargs, **settings})
     if not isinstance(criterion, torch.nn.CrossEntropyLoss) or not hasattr(module_cls, "engine"):
         return None
     if criterion_options(criterion) is None:
@@ -209,6 +215,8 @@ def fused_kind(criterion, opt_cls, opt_kwargs, module_cls):
         return None
     d = optimizer_defaults(opt_cls, opt_kwargs)
     if d.get("maximize", False) or (kind != "sgd" and d.get("amsgrad", False)):
+        return None
+    if not param_groups.fused_ok(groups):
         return None
     return kind
 
@@ -224,6 +232,13 @@ def criterion_options(criterion):
         return None
     return {"weight": None if w is None else w.detach().float().cpu(), "label_smoothing": float(criterion.label_smoothing),
             "reduction": criterion.reduction}
+
+
+def optimizer_kwargs(opt_kwargs):
+    """(constructor keywords, ``param_groups`` pairs) of the ``optimizer__*`` settings: ``param_groups`` is skorch's, not a
+    keyword of any torch optimizer."""
+    kw = dict(opt_kwargs)
+    return kw, param_groups.as_pairs(kw.pop("param_groups", None))
 
 
 def optimizer_defaults(opt_cls, opt_kwargs):
@@ -314,10 +329,11 @@ class _FitRun:
         self.plateau, self.schedule, self.epoch_lrs = None, None, None
         if sched and not schedule.is_plateau(sched):
             # the schedule's position is a function of the history: built from scratch and replayed up to where the fit stands
-            self.schedule = schedule.LRSchedule.from_setting(sched, net.lr).fast_forward(net.history)
-            net._set_lr(self.schedule.current)
+            self.schedule = schedule.LRSchedule.from_setting(sched, net._base_lrs()).fast_forward(net.history)
+            net._set_lr(self.schedule.rates)
         elif sched:
-            dummy = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=net.lr_)
+            # one dummy group per param group, at the groups' current rates (min_lr / factor lists apply per group, as in torch)
+            dummy = torch.optim.SGD([{"params": [torch.nn.Parameter(torch.zeros(1))], "lr": v} for v in net.lrs_], lr=net.lr_)
             self.plateau = torch.optim.lr_scheduler.ReduceLROnPlateau(
                 dummy, **{k: v for k, v in sched.items() if k not in ("policy", "monitor", "step_every")})
         self.best_valid, self.misses, self.dyn_thr = float("inf"), 0, float("inf")
@@ -385,14 +401,14 @@ class _FitRun:
         epoch = len(net.history) + 1
         if self.schedule is not None:
             # what the reference's lr scoring reads at epoch end: with batch stepping the rate after the epoch's last step
-            net._set_lr(self.schedule.current)
+            net._set_lr(self.schedule.rates)
         row = {"epoch": epoch, "train_loss": tr_loss, "lr": net.lr_,
                "batches": [{"train_loss": l, "train_batch_size": n} for l, n in tr_batches]}   # skorch history layout
         if self.sampler is not None:
             row["shuffle_seed"] = self.sampler.seed          # a resumed fit rebuilds the order from it (slnlp/sampler.py)
         if self.schedule is not None and self.schedule.per_batch:
             for b, lr in zip(row["batches"], self.epoch_lrs):
-                b["event_lr"] = lr                           # the rate this batch used
+                b["event_lr"] = lr[0] if isinstance(lr, list) else lr     # the rate this batch used (param groups: group 0's)
         if va is not None:
             va_loss, va_logp, va_batches = va
             row["batches"] += [{"valid_loss": l, "valid_batch_size": n} for l, n in va_batches]
@@ -423,10 +439,10 @@ class _FitRun:
         monitor = row.get("valid_loss", tr_loss)
         if self.plateau is not None:                         # LRScheduler(monitor=valid_loss, step_every=epoch)
             self.plateau.step(monitor)
-            net._set_lr(self.plateau.optimizer.param_groups[0]["lr"])
+            net._set_lr([g["lr"] for g in self.plateau.optimizer.param_groups] if net._groups else self.plateau.optimizer.param_groups[0]["lr"])
         if self.schedule is not None:                        # LRScheduler(step_every=epoch); a no-op with batch stepping
             self.schedule.epoch_end()
-            net._set_lr(self.schedule.current)
+            net._set_lr(self.schedule.rates)
         self.epochs_left -= 1
         if self.es:                                          # skorch EarlyStopping, lower_is_better
             es = self.es
@@ -490,7 +506,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 setting = schedule.from_callback(obj)
                 if schedule.is_plateau(setting) and get("monitor", "valid_loss") != "valid_loss":
                     raise ValueError("LRScheduler: ReduceLROnPlateau is implemented on monitor='valid_loss' only")
-                schedule.check_setting(setting, self._params["lr"])
+                if not self._params.get("optimizer__param_groups"):     # (with groups: checked per group in initialize())
+                    schedule.check_setting(setting, self._params["lr"])
                 self._params["lr_scheduler"] = setting
             elif kind == "Checkpoint":
                 if get("monitor", "valid_loss_best") != "valid_loss_best":
@@ -546,7 +563,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         return tuple(out)
 
     def initialize(self):
-        schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
+        ok, pairs = optimizer_kwargs(self._sub("optimizer"))
+        if not pairs:
+            schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
         shuffle, _ = self._iterator_train()
         dev = torch.device(self.device)
         if dev.type != "cuda" or not torch.cuda.is_available():
@@ -558,10 +577,10 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             self.criterion_ = self.criterion_.to(dev)    # class weights on the device of the torch-stepped path's log-probs
             # (criterion.pt is written from a host copy: save_params)
         self._opt_cls = _resolve(self.optimizer)
-        ok = self._opt_kwargs = self._sub("optimizer")
+        self._opt_kwargs = ok                            # the constructor's keywords; optimizer__param_groups travels apart
         mod_cls = _resolve(self.module)
         # which fused clip + update kernel replaces the torch optimizer (None: the fit steps through torch)
-        self._fused_kind = fused_kind(self.criterion_, self._opt_cls, ok, mod_cls)
+        self._fused_kind = fused_kind(self.criterion_, self._opt_cls, ok, mod_cls, pairs)
         self._fused = self._fused_kind is not None
         self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
         # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
@@ -572,12 +591,24 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         self._gate = device_gate(dev)
         with torch.cuda.stream(self._stream):            # the weight draw / upload too: nothing of a fit runs on another queue
             self.module_ = mod_cls(**kw).to(dev)
+        # optimizer__param_groups: the groups (slnlp/param_groups.py) feed the torch optimizer or the fused update's table
+        self._groups = param_groups.build([n for n, _ in self.module_.named_parameters()], pairs) if pairs else None
+        if self._groups is not None and all(g.pattern is None for g in self._groups):
+            self._groups = None                          # no pattern matched anything: one group with the defaults, as without
         if hasattr(self.module_, "set_train_options"):
             self.module_.set_train_options(criterion=self._crit_opts,
-                                           update=update_options(self._fused_kind, self._opt_defaults) if self._fused else None)
+                                           update=update_options(self._fused_kind, self._opt_defaults) if self._fused else None,
+                                           param_groups=self._group_table() if self._fused else None)
         if not self._fused:
-            self.optimizer_ = self._opt_cls(self.module_.parameters(), lr=self.lr, **ok)
+            what = (param_groups.torch_groups(self._groups, self.module_.named_parameters()) if self._groups is not None
+                    else self.module_.parameters())
+            self.optimizer_ = self._opt_cls(what, lr=self.lr, **ok)
         self.lr_ = float(self.lr)
+        self._set_lr(self._base_lrs())
+        if pairs:
+            # the schedule's per-group arguments against the real group count -- known only once the module's parameter names
+            # are (a pattern that matches nothing makes no group), so with groups this check comes after the module is built
+            schedule.check_setting(self.lr_scheduler, self._base_lrs())
         self.history = []
         # the seed of the shuffled order, drawn the way RandomSampler draws one without a generator -- AFTER the module's
         # weights and only when shuffling is on, so the initial weights of every other configuration keep their bits
@@ -652,7 +683,36 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             tr, va = next(iter(KFold(n_splits=int(ts)).split(idx)))
         return tr, va
 
+    def _base_lrs(self):
+        """The configured rate: ``lr``, or with param groups the list of every group's (its own ``lr``, else ``lr``)."""
+        if getattr(self, "_groups", None) is None:
+            return float(self.lr)
+        return param_groups.resolved(self._groups, {"lr": self.lr}, "lr")
+
+    def _group_table(self):
+        """The fused update's device table of the groups (False: none), for ``module_.set_train_options``."""
+        if self._groups is None:
+            return False
+        begin, group = param_groups.segments(self._groups, self.module_._entries, self.module_._arena.numel())
+        return {"seg_begin": begin, "seg_group": group,
+                "weight_decay": param_groups.resolved(self._groups, self._opt_defaults, "weight_decay")}
+
+    @property
+    def lrs_(self):
+        """The current rate of every param group (``lr_`` is group 0's, what the history's ``lr`` records)."""
+        return list(self._lrs) if getattr(self, "_groups", None) is not None else [self.lr_]
+
     def _set_lr(self, lr):
+        """``lr``: one rate, or with param groups the list of the groups' rates."""
+        if getattr(self, "_groups", None) is not None:
+            if not isinstance(lr, (list, tuple)) or len(lr) != len(self._groups):
+                raise ValueError(f"_set_lr: {len(self._groups)} param groups need a list of {len(self._groups)} rates, got {lr!r}")
+            self._lrs = [float(v) for v in lr]
+            self.lr_ = self._lrs[0]
+            if not self._fused:
+                for g, v in zip(self.optimizer_.param_groups, self._lrs):
+                    g["lr"] = v
+            return
         self.lr_ = float(lr)
         if not self._fused:
             for g in self.optimizer_.param_groups:
@@ -679,6 +739,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             if train and self._fused:
                 eng = self.module_.engine(xb.shape[0], xb.shape[1])
                 eng.set_lr(self.lr_)
+                if self._groups is not None:
+                    self.module_.set_group_lrs(self._lrs)    # what the grouped update reads instead
                 if self._fused_kind in ("adam", "adamw"):
                     betas, eps, wd = adam_args(self)
                     logp = eng.train_step_adam(xb, yb, self.module_.adam_second_moment(), betas, eps, wd, max_norm, lengths=lb)
@@ -746,7 +808,13 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         in ``module.parameters()`` order, plus the param group with the current lr -- what skorch's Checkpoint writes as
         optimizer.pt (helper.py:211-213) and what ``torch.optim.SGD.load_state_dict`` reads back."""
         params = dict(self.module_.named_parameters())
-        opt = self._opt_cls([p for n, p in params.items()], lr=self.lr_, **self._opt_kwargs)
+        if self._groups is not None:
+            # the same groups the torch-stepped path would build: torch numbers the state by position across them
+            opt = self._opt_cls(param_groups.torch_groups(self._groups, params.items()), lr=float(self.lr), **self._opt_kwargs)
+            for g, v in zip(opt.param_groups, self._lrs):
+                g["lr"] = v
+        else:
+            opt = self._opt_cls([p for n, p in params.items()], lr=self.lr_, **self._opt_kwargs)
         st = self.module_._shared_state()
         mom = st["momentum"]
         adam = self._fused_kind in ("adam", "adamw")
@@ -771,7 +839,13 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         return opt.state_dict()
 
     def _load_sgd_state_dict(self, sd):
-        names = [n for n, _ in self.module_.named_parameters()]
+        groups = sd.get("param_groups") or [{}]
+        if self._groups is not None and (len(groups) != len(self._groups) or
+                                         [len(g.get("params", ())) for g in groups] != [len(g.names) for g in self._groups]):
+            raise ValueError(f"optimizer.pt holds {len(groups)} param groups that are not this estimator's {len(self._groups)}: "
+                             "load it with the optimizer__param_groups it was written with")
+        # torch numbers the state by position across the param groups, in group order
+        names = param_groups.positions(self._groups) if self._groups is not None else [n for n, _ in self.module_.named_parameters()]
         ent = {n: (shape, off) for n, shape, off in self.module_._entries}
         st = self.module_._shared_state()
         step = None
@@ -790,8 +864,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             st["scalars"][2] = step
         if self._fused_kind == "sgd":                  # SGD: whether the first step (no dampening) is behind us
             st["scalars"][3] = 1.0 if started else 0.0
-        groups = sd.get("param_groups") or [{}]
-        if "lr" in groups[0]:
+        if self._groups is not None:
+            self._set_lr([g["lr"] for g in groups])
+        elif "lr" in groups[0]:
             self._set_lr(groups[0]["lr"])
 
     def save_params(self, dirname):
@@ -819,6 +894,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             else:
                 self.optimizer_.load_state_dict(sd)
                 self.lr_ = float(self.optimizer_.param_groups[0]["lr"])
+                if self._groups is not None:
+                    self._lrs = [float(g["lr"]) for g in self.optimizer_.param_groups]
         hist = os.path.join(dirname, "history.json")
         if os.path.exists(hist):
             with open(hist) as f:

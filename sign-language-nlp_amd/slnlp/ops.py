@@ -377,6 +377,58 @@ def clip_adamw_step(params, grads, exp_avg, exp_avg_sq, lr_dev, step_count, *, b
     return norm
 
 
+class ParamGroupTable:
+    """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
+    segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
+    with weight_decay[g].  The groups' learning rates are a device tensor given to each step."""
+
+    def __init__(self, n, seg_begin, seg_group, weight_decay):
+        import ctypes as C
+        _lib.require_gpu()
+        self.n, self.n_groups, self.handle = int(n), len(weight_decay), C.c_void_p()
+        check(load().slnlp_param_groups_create(self.n, len(seg_begin), (C.c_int64 * len(seg_begin))(*seg_begin),
+                                               (C.c_int32 * len(seg_group))(*seg_group), len(weight_decay),
+                                               (C.c_float * len(weight_decay))(*weight_decay), stream_ptr(), C.byref(self.handle)),
+              "param_groups_create")
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                load().slnlp_param_groups_destroy(h)
+            except Exception:                            # interpreter shutdown: the module globals are already gone
+                pass
+            self.handle = None
+
+
+def clip_sgd_step_groups(params, grads, buf, table, lr_dev, step_count, *, momentum=0.9, dampening=0.0, nesterov=False, max_norm=0.5,
+                         skip=(0, 0)):
+    """``clip_sgd_step_ex`` with lr (``lr_dev`` [groups], device) and weight decay per parameter group (``table``: a
+    ``ParamGroupTable``).  Returns the pre-clip norm [1]."""
+    _lib.require_gpu()
+    partials = torch.empty(1024, dtype=torch.float32, device=params.device)
+    norm = torch.empty(1, dtype=torch.float32, device=params.device)
+    assert lr_dev.numel() == table.n_groups
+    check(load().slnlp_clip_sgd_step_groups(ptr(params), ptr(grads), ptr(buf), params.numel(), table.handle, ptr(lr_dev), momentum,
+                                            dampening, int(bool(nesterov)), max_norm, ptr(partials), ptr(norm), ptr(step_count),
+                                            skip[0], skip[1], stream_ptr()), "clip_sgd_step_groups")
+    return norm
+
+
+def clip_adam_step_groups(params, grads, exp_avg, exp_avg_sq, table, lr_dev, step_count, *, betas=(0.9, 0.999), eps=1e-8,
+                          decoupled=False, max_norm=0.5, skip=(0, 0)):
+    """``clip_adam_step`` (``decoupled``: ``clip_adamw_step``) with lr and weight decay per parameter group, as
+    ``clip_sgd_step_groups``.  Returns the pre-clip norm [1]."""
+    _lib.require_gpu()
+    partials = torch.empty(1024, dtype=torch.float32, device=params.device)
+    norm = torch.empty(1, dtype=torch.float32, device=params.device)
+    assert lr_dev.numel() == table.n_groups
+    check(load().slnlp_clip_adam_step_groups(ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), table.handle,
+                                             ptr(lr_dev), betas[0], betas[1], eps, int(bool(decoupled)), max_norm, ptr(partials),
+                                             ptr(norm), ptr(step_count), skip[0], skip[1], stream_ptr()), "clip_adam_step_groups")
+    return norm
+
+
 def dropout_mask(R, C_, p, site, rng):
     _lib.require_gpu()
     out = torch.empty(R, C_, dtype=torch.float32, device=rng.device)

@@ -2,8 +2,8 @@
 
 skorch's ``LRScheduler`` callback takes a policy (a name in ``torch.optim.lr_scheduler`` or the class), ``step_every`` and the
 policy's keyword arguments (the reference configures ``ReduceLROnPlateau``, helper.py:226-238).  ``LRSchedule`` is that for
-the fused fit loop: it owns a dummy optimizer (one zero parameter, ``lr`` = the estimator's) and a real scheduler instance on
-it, so every value is torch's own arithmetic -- nothing is restated in closed form.  The loop asks it for the rates of an
+the fused fit loop: it owns a dummy optimizer (one zero parameter per param group, ``lr`` = the estimator's, or each group's
+base rate with ``optimizer__param_groups``) and a real scheduler instance on it, so every value is torch's own arithmetic -- nothing is restated in closed form.  The loop asks it for the rates of an
 epoch's train batches ahead of the epoch (``epoch_table``), because a lockstep unit runs the whole epoch without coming back
 to the host: per-batch rates travel to the device as a table (slnlp.lockstep).
 
@@ -58,7 +58,10 @@ def _resolve_policy(policy):
 
 
 class LRSchedule:
-    """One fit's schedule.  ``current`` is the rate the next train batch uses."""
+    """One fit's schedule.  ``current`` is the rate the next train batch uses (group 0's with param groups, what the history's
+    ``lr`` and ``event_lr`` record); ``lr`` a list of G base rates: one dummy group each, ``current_all`` and the rows of
+    ``epoch_table`` are then lists of G rates, every one torch's own for that group (per-group ``max_lr`` lists,
+    ``lr_lambda`` lists, ... included)."""
 
     def __init__(self, policy, lr, step_every="epoch", **kwargs):
         if step_every not in STEP_EVERY:
@@ -71,7 +74,9 @@ class LRSchedule:
             raise ValueError(f"lr_scheduler: {cls.__name__} cycles the momentum by default, which the fused update does not implement "
                              f"-- pass cycle_momentum=False")
         self.policy, self.step_every, self.kwargs = cls, step_every, dict(kwargs)
-        self._opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=float(lr))
+        self.grouped = isinstance(lr, (list, tuple))
+        base = [float(v) for v in lr] if self.grouped else [float(lr)]
+        self._opt = torch.optim.SGD([{"params": [torch.nn.Parameter(torch.zeros(1))], "lr": v} for v in base], lr=base[0])
         try:
             self._sched = cls(self._opt, **kwargs)
         except Exception as e:
@@ -92,19 +97,31 @@ class LRSchedule:
     def current(self):
         return float(self._opt.param_groups[0]["lr"])
 
+    @property
+    def current_all(self):
+        return [float(g["lr"]) for g in self._opt.param_groups]
+
+    @property
+    def rates(self):
+        """What the estimator's ``_set_lr`` takes: ``current``, or with param groups ``current_all``."""
+        return self._row()
+
+    def _row(self):
+        return self.current_all if self.grouped else self.current
+
     def _step(self):                                       # skorch: optimizer.step() per batch, then the scheduler
         self._opt.step()
         self._sched.step()
 
     def epoch_table(self, n):
-        """The rates of the next ``n`` train batches (Python floats).  Per-batch stepping advances the scheduler by ``n``
+        """The rates of the next ``n`` train batches (Python floats; with param groups a list of G floats each).  Per-batch stepping advances the scheduler by ``n``
         (a scheduler stepped past its end raises torch's own error here, before anything is queued); per-epoch stepping
         returns ``n`` copies of the current value and leaves the advance to ``epoch_end``."""
         if not self.per_batch:
-            return [self.current] * n
+            return [self._row() for _ in range(n)]
         out = []
         for _ in range(n):
-            out.append(self.current)
+            out.append(self._row())
             self._step()
         return out
 

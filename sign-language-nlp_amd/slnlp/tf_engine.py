@@ -156,6 +156,23 @@ class TransformerEngine:
         check(load().slnlp_tf_set_dmem_batched(self.handle, int(bool(on))), "tf_set_dmem_batched")
         self._graph_keys = {}
 
+    def set_param_groups(self, table=None, lr=None):
+        """Per-parameter-group lr / weight decay of the fused update (``optimizer__param_groups``): ``table`` {seg_begin,
+        seg_group, weight_decay} as ``slnlp.param_groups.segments`` builds it, ``lr`` the float32 device tensor [groups] the
+        update reads every step (the caller writes the rates there; ``set_lr`` is then not read by the update).  None clears
+        the table: the one-group update again.  A change drops the plan's captured graphs."""
+        if not table:
+            check(load().slnlp_tf_set_param_groups(self.handle, 0, None, None, 0, None, None, self._sp()), "tf_set_param_groups")
+            self._group_lr = None
+        else:
+            begin, group, wd = list(table["seg_begin"]), list(table["seg_group"]), list(table["weight_decay"])
+            if lr is None or not lr.is_cuda or lr.dtype != torch.float32 or lr.numel() != len(wd) or not lr.is_contiguous():
+                raise ValueError(f"set_param_groups: lr must be a contiguous float32 device tensor of {len(wd)} rates")
+            check(load().slnlp_tf_set_param_groups(self.handle, len(begin), (C.c_int64 * len(begin))(*begin), (C.c_int32 * len(group))(*group),
+                                                   len(wd), (C.c_float * len(wd))(*wd), ptr(lr), self._sp()), "tf_set_param_groups")
+            self._group_lr = lr                  # kept alive: the update kernels read it
+        self._graph_keys = {}
+
     def set_lr(self, lr):
         self.lr.fill_(float(lr))
 
