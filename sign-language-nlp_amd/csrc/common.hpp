@@ -412,14 +412,6 @@ struct AdamOpts {
     int decoupled = 0;
     int64_t skip_begin = 0, skip_end = 0;
 };
-int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
-                  float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
-                  hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,   // planes written for floats [wp_begin, wp_end); -1: to the end
-                  SgdOpts so = {});
-int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
-                   float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
-                   unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,
-                   AdamOpts ao = {});
 // Per-parameter-group lr / weight decay of the fused update (optimizer__param_groups).  The arena is cut into segments
 // on float4 boundaries (arena entries are 16-byte aligned: a float4 never straddles two parameters); segment s covers
 // float4 indices [seg_begin4[s], seg_begin4[s + 1]) -- the last one runs to the arena's end -- and belongs to group
@@ -449,15 +441,16 @@ namespace slnlp {
 int param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
                         const float* weight_decay, hipStream_t st, slnlp_param_groups** out);
 void param_groups_destroy(slnlp_param_groups* pg);
-// the grouped forms of clip_sgd_step / clip_adam_step: lr and weight decay per element from its group, the rest as there
-int clip_sgd_step_groups(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* pg,
-                         const float* lr_dev, float momentum, float max_norm, float* partials, float* norm_out,
-                         unsigned long long* rng, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,
-                         SgdOpts so = {});
-int clip_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
-                          const slnlp_param_groups* pg, const float* lr_dev, float beta1, float beta2, float eps, float max_norm,
-                          float* partials, float* norm_out, unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {},
-                          int64_t wp_begin = 0, int64_t wp_end = -1, AdamOpts ao = {});
+// pg (optional): per-parameter-group lr / weight decay -- lr_dev then holds the groups' rates, and each group decays with the
+// table's weight decay (so.weight_decay / weight_decay are not read); the rest as for one group
+int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* pg, const float* lr_dev,
+                  float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
+                  hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0, int64_t wp_end = -1,   // planes written for floats [wp_begin, wp_end); -1: to the end
+                  SgdOpts so = {});
+int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const slnlp_param_groups* pg,
+                   const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials,
+                   float* norm_out, unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp = {}, int64_t wp_begin = 0,
+                   int64_t wp_end = -1, AdamOpts ao = {});
 // A plan's criterion and update settings (slnlp_{tf,rnn}_set_criterion / _set_update / _set_param_groups).  The class weights are copied into
 // device memory the plan owns, so recorded programs and captured graphs keep a valid pointer; `gen` moves on every change
 // (a lockstep group re-records its programs when a fit's generation moved).

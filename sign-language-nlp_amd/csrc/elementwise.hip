@@ -1005,40 +1005,6 @@ __device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __r
 }
 SLNLP_ZKERNEL(sgd_kernel, 256, sgd_body)
 
-// skip range [skip_begin, skip_end) in floats, 16-byte aligned (multiples of 4); empty when skip_end <= skip_begin
-static int check_skip(const char* what, int64_t n, int64_t skip_begin, int64_t skip_end) {
-    SLNLP_CHECK_ARG(skip_end <= skip_begin || (skip_begin >= 0 && skip_end <= n && skip_begin % 4 == 0 && skip_end % 4 == 0),
-                    "%s: skip range [%ld, %ld) must lie in [0, %ld) on multiples of 4", what, (long)skip_begin, (long)skip_end, (long)n);
-    return 0;
-}
-
-int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
-                  float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
-                  hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end, SgdOpts so) {
-    SLNLP_CHECK_ARG(params && grads && momentum_buf && lr_dev && partials, "clip_sgd_step: null pointer");
-    SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_sgd_step: n=%ld must be a positive multiple of 4", (long)n);
-    SLNLP_CHECK_ARG(((uintptr_t)params & 15) == 0 && ((uintptr_t)grads & 15) == 0 && ((uintptr_t)momentum_buf & 15) == 0,
-                    "clip_sgd_step: arenas must be 16-byte aligned");
-    // torch's argument rules (torch.optim.SGD.__init__); without momentum torch keeps no buffer, so dampening is moot
-    SLNLP_CHECK_ARG(so.dampening >= 0.f && so.weight_decay >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
-                    "clip_sgd_step: bad dampening %g / weight_decay %g / nesterov (needs momentum > 0 and dampening 0)",
-                    so.dampening, so.weight_decay);
-    SLNLP_TRY(check_skip("clip_sgd_step", n, so.skip_begin, so.skip_end));
-    const float damp = momentum != 0.f ? so.dampening : 0.f;
-    const bool general = damp != 0.f || so.weight_decay != 0.f || so.nesterov;
-    SLNLP_CHECK_ARG(!general || so.steps, "clip_sgd_step: dampening / weight decay / nesterov need the step counter");
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq",
-                      grads, (long)(n / 4), partials, so.steps));
-    int grid = ceil_div(n / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const long sb4 = so.skip_end > so.skip_begin ? (long)(so.skip_begin / 4) : 0, se4 = so.skip_end > so.skip_begin ? (long)(so.skip_end / 4) : 0;
-    SLNLP_TRY(zlaunch(sgd_kernel, dim3(grid), 256, 0, st, "sgd",
-                      params, grads, momentum_buf, (long)(n / 4), lr_dev, momentum, max_norm, partials, norm_out, rng, wp,
-                      (long)(wp_begin / 4), (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4), damp, so.weight_decay,
-                      so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4));
-    return 0;
-}
-
 // torch.optim.Adam (amsgrad False, maximize False) fused with clip_grad_norm_, same two-launch shape as clip + SGD:
 //   g' = g * clip_coef (+ weight_decay * p);  m += (1 - b1)(g' - m);  v = b2 v + (1 - b2) g'^2;
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)            (torch/optim/adam.py _single_tensor_adam)
@@ -1099,28 +1065,6 @@ SLNLP_ZKERNEL(adam_kernel, 256, adam_body)
 // the count is advanced by its own one-thread launch AFTER the update (every block of adam_kernel must read the same old value)
 __device__ __forceinline__ void adam_count_body(float* __restrict__ step_f) { if (threadIdx.x == 0 && blockIdx.x == 0) step_f[0] += 1.f; }
 SLNLP_ZKERNEL(adam_count_kernel, 64, adam_count_body)
-
-int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
-                   float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
-                   unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end,
-                   AdamOpts ao) {
-    SLNLP_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && lr_dev && partials && step_f, "clip_adam_step: null pointer");
-    SLNLP_TRY(check_skip("clip_adam_step", n, ao.skip_begin, ao.skip_end));
-    SLNLP_CHECK_ARG(weight_decay >= 0.f, "clip_adam_step: weight_decay %g < 0", weight_decay);
-    SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_adam_step: n=%ld must be a positive multiple of 4", (long)n);
-    SLNLP_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
-                    "clip_adam_step: arenas must be 16-byte aligned");
-    SLNLP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "clip_adam_step: bad betas / eps");
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials, (float*)nullptr));
-    int grid = ceil_div(n / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const long sb4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_begin / 4) : 0, se4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_end / 4) : 0;
-    SLNLP_TRY(zlaunch(adam_kernel, dim3(grid), 256, 0, st, "adam", params, grads, exp_avg, exp_avg_sq, (long)(n / 4), lr_dev, beta1, beta2,
-                      eps, weight_decay, max_norm, partials, norm_out, rng, step_f, wp, (long)(wp_begin / 4),
-                      (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4), ao.decoupled ? 1 : 0, sb4, se4));
-    SLNLP_TRY(zlaunch(adam_count_kernel, dim3(1), 64, 0, st, "adam_count", step_f));
-    return 0;
-}
 
 // ------------------------------------------------ per-parameter-group update (optimizer__param_groups) ----
 // The same two launches as above (sumsq_kernel, then the update); the update reads lr and weight decay per float4 from
@@ -1275,6 +1219,86 @@ __device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const fl
 }
 SLNLP_ZKERNEL(adam_groups_kernel, 256, adam_groups_body)
 
+// skip range [skip_begin, skip_end) in floats, 16-byte aligned (multiples of 4); empty when skip_end <= skip_begin
+static int check_skip(const char* what, int64_t n, int64_t skip_begin, int64_t skip_end) {
+    SLNLP_CHECK_ARG(skip_end <= skip_begin || (skip_begin >= 0 && skip_end <= n && skip_begin % 4 == 0 && skip_end % 4 == 0),
+                    "%s: skip range [%ld, %ld) must lie in [0, %ld) on multiples of 4", what, (long)skip_begin, (long)skip_end, (long)n);
+    return 0;
+}
+
+// pg (optional): lr_dev holds the groups' rates and each group decays with its own weight decay (so.weight_decay is not read)
+int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* pg, const float* lr_dev,
+                  float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
+                  hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end, SgdOpts so) {
+    const char* what = pg ? "clip_sgd_step_groups" : "clip_sgd_step";
+    SLNLP_CHECK_ARG(params && grads && momentum_buf && lr_dev && partials, "%s: null pointer", what);
+    if (pg)
+        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n == pg->n, "clip_sgd_step_groups: n=%ld must be the table's (%ld), a positive multiple of 4",
+                        (long)n, (long)pg->n);
+    else
+        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_sgd_step: n=%ld must be a positive multiple of 4", (long)n);
+    SLNLP_CHECK_ARG(((uintptr_t)params & 15) == 0 && ((uintptr_t)grads & 15) == 0 && ((uintptr_t)momentum_buf & 15) == 0,
+                    "%s: arenas must be 16-byte aligned", what);
+    // torch's argument rules (torch.optim.SGD.__init__); without momentum torch keeps no buffer, so dampening is moot
+    if (pg)
+        SLNLP_CHECK_ARG(so.dampening >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
+                        "clip_sgd_step_groups: bad dampening %g / nesterov (needs momentum > 0 and dampening 0)", so.dampening);
+    else
+        SLNLP_CHECK_ARG(so.dampening >= 0.f && so.weight_decay >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
+                        "clip_sgd_step: bad dampening %g / weight_decay %g / nesterov (needs momentum > 0 and dampening 0)",
+                        so.dampening, so.weight_decay);
+    SLNLP_TRY(check_skip(what, n, so.skip_begin, so.skip_end));
+    const float damp = momentum != 0.f ? so.dampening : 0.f;
+    const bool general = damp != 0.f || (pg ? pg->any_wd : so.weight_decay != 0.f) || so.nesterov;
+    SLNLP_CHECK_ARG(!general || so.steps, "%s: dampening / weight decay / nesterov need the step counter", what);
+    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq",
+                      grads, (long)(n / 4), partials, so.steps));
+    int grid = ceil_div(n / 4, 256);
+    if (grid > 2048) grid = 2048;
+    const long sb4 = so.skip_end > so.skip_begin ? (long)(so.skip_begin / 4) : 0, se4 = so.skip_end > so.skip_begin ? (long)(so.skip_end / 4) : 0;
+    const long wb4 = (long)(wp_begin / 4), we4 = (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4);
+    if (pg)
+        return zlaunch(sgd_groups_kernel, dim3(grid), 256, 0, st, "sgd_groups",
+                       params, grads, momentum_buf, (long)(n / 4), pg->tab(lr_dev), momentum, max_norm, partials, norm_out, rng, wp,
+                       wb4, we4, damp, general ? 1 : 0, so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4);
+    return zlaunch(sgd_kernel, dim3(grid), 256, 0, st, "sgd",
+                   params, grads, momentum_buf, (long)(n / 4), lr_dev, momentum, max_norm, partials, norm_out, rng, wp,
+                   wb4, we4, damp, so.weight_decay, so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4);
+}
+
+// pg (optional): lr_dev holds the groups' rates and each group decays with its own weight decay (weight_decay is not read)
+int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const slnlp_param_groups* pg,
+                   const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials,
+                   float* norm_out, unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end,
+                   AdamOpts ao) {
+    const char* what = pg ? "clip_adam_step_groups" : "clip_adam_step";
+    SLNLP_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && lr_dev && partials && step_f, "%s: null pointer", what);
+    SLNLP_TRY(check_skip(what, n, ao.skip_begin, ao.skip_end));
+    if (pg) {
+        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n == pg->n, "clip_adam_step_groups: n=%ld must be the table's (%ld), a positive multiple of 4",
+                        (long)n, (long)pg->n);
+    } else {
+        SLNLP_CHECK_ARG(weight_decay >= 0.f, "clip_adam_step: weight_decay %g < 0", weight_decay);
+        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_adam_step: n=%ld must be a positive multiple of 4", (long)n);
+    }
+    SLNLP_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
+                    "%s: arenas must be 16-byte aligned", what);
+    SLNLP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "%s: bad betas / eps", what);
+    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials, (float*)nullptr));
+    int grid = ceil_div(n / 4, 256);
+    if (grid > 2048) grid = 2048;
+    const long sb4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_begin / 4) : 0, se4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_end / 4) : 0;
+    const long wb4 = (long)(wp_begin / 4), we4 = (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4);
+    if (pg)
+        SLNLP_TRY(zlaunch(adam_groups_kernel, dim3(grid), 256, 0, st, "adam_groups", params, grads, exp_avg, exp_avg_sq, (long)(n / 4),
+                          pg->tab(lr_dev), beta1, beta2, eps, max_norm, partials, norm_out, rng, step_f, wp, wb4, we4,
+                          ao.decoupled ? 1 : 0, sb4, se4));
+    else
+        SLNLP_TRY(zlaunch(adam_kernel, dim3(grid), 256, 0, st, "adam", params, grads, exp_avg, exp_avg_sq, (long)(n / 4), lr_dev, beta1,
+                          beta2, eps, weight_decay, max_norm, partials, norm_out, rng, step_f, wp, wb4, we4, ao.decoupled ? 1 : 0, sb4, se4));
+    return zlaunch(adam_count_kernel, dim3(1), 64, 0, st, "adam_count", step_f);
+}
+
 int param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
                         const float* weight_decay, hipStream_t st, slnlp_param_groups** out) {
     SLNLP_CHECK_ARG(out && seg_begin && seg_group && weight_decay, "param_groups_create: null pointer");
@@ -1318,53 +1342,6 @@ void param_groups_destroy(slnlp_param_groups* pg) {
     if (!pg) return;
     if (pg->dev) (void)hipFree(pg->dev);
     delete pg;
-}
-
-int clip_sgd_step_groups(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* pg,
-                         const float* lr_dev, float momentum, float max_norm, float* partials, float* norm_out,
-                         unsigned long long* rng, hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end, SgdOpts so) {
-    SLNLP_CHECK_ARG(params && grads && momentum_buf && lr_dev && partials && pg, "clip_sgd_step_groups: null pointer");
-    SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n == pg->n, "clip_sgd_step_groups: n=%ld must be the table's (%ld), a positive multiple of 4",
-                    (long)n, (long)pg->n);
-    SLNLP_CHECK_ARG(((uintptr_t)params & 15) == 0 && ((uintptr_t)grads & 15) == 0 && ((uintptr_t)momentum_buf & 15) == 0,
-                    "clip_sgd_step_groups: arenas must be 16-byte aligned");
-    SLNLP_CHECK_ARG(so.dampening >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
-                    "clip_sgd_step_groups: bad dampening %g / nesterov (needs momentum > 0 and dampening 0)", so.dampening);
-    SLNLP_TRY(check_skip("clip_sgd_step_groups", n, so.skip_begin, so.skip_end));
-    const float damp = momentum != 0.f ? so.dampening : 0.f;
-    const bool general = damp != 0.f || pg->any_wd || so.nesterov;
-    SLNLP_CHECK_ARG(!general || so.steps, "clip_sgd_step_groups: dampening / weight decay / nesterov need the step counter");
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials, so.steps));
-    int grid = ceil_div(n / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const long sb4 = so.skip_end > so.skip_begin ? (long)(so.skip_begin / 4) : 0, se4 = so.skip_end > so.skip_begin ? (long)(so.skip_end / 4) : 0;
-    SLNLP_TRY(zlaunch(sgd_groups_kernel, dim3(grid), 256, 0, st, "sgd_groups",
-                      params, grads, momentum_buf, (long)(n / 4), pg->tab(lr_dev), momentum, max_norm, partials, norm_out, rng, wp,
-                      (long)(wp_begin / 4), (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4), damp, general ? 1 : 0,
-                      so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4));
-    return 0;
-}
-
-int clip_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
-                          const slnlp_param_groups* pg, const float* lr_dev, float beta1, float beta2, float eps, float max_norm,
-                          float* partials, float* norm_out, unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp,
-                          int64_t wp_begin, int64_t wp_end, AdamOpts ao) {
-    SLNLP_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && lr_dev && partials && step_f && pg, "clip_adam_step_groups: null pointer");
-    SLNLP_TRY(check_skip("clip_adam_step_groups", n, ao.skip_begin, ao.skip_end));
-    SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n == pg->n, "clip_adam_step_groups: n=%ld must be the table's (%ld), a positive multiple of 4",
-                    (long)n, (long)pg->n);
-    SLNLP_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
-                    "clip_adam_step_groups: arenas must be 16-byte aligned");
-    SLNLP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "clip_adam_step_groups: bad betas / eps");
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials, (float*)nullptr));
-    int grid = ceil_div(n / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const long sb4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_begin / 4) : 0, se4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_end / 4) : 0;
-    SLNLP_TRY(zlaunch(adam_groups_kernel, dim3(grid), 256, 0, st, "adam_groups", params, grads, exp_avg, exp_avg_sq, (long)(n / 4),
-                      pg->tab(lr_dev), beta1, beta2, eps, max_norm, partials, norm_out, rng, step_f, wp, (long)(wp_begin / 4),
-                      (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4), ao.decoupled ? 1 : 0, sb4, se4));
-    SLNLP_TRY(zlaunch(adam_count_kernel, dim3(1), 64, 0, st, "adam_count", step_f));
-    return 0;
 }
 
 // ============================================================ plan settings
@@ -1522,27 +1499,27 @@ int slnlp_lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dl
 int slnlp_clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
                         float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
                         void* stream) {
-    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, lr_dev, momentum, max_norm, partials, norm_out, rng,
+    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, nullptr, lr_dev, momentum, max_norm, partials, norm_out, rng,
                                 (hipStream_t)stream);
 }
 int slnlp_clip_sgd_step_ex(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
                            float momentum, float dampening, float weight_decay, int nesterov, float max_norm, float* partials,
                            float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
-    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
+    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, nullptr, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
                                 (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
                                 slnlp::SgdOpts{dampening, weight_decay, nesterov, step_count, skip_begin, skip_end});
 }
 int slnlp_clip_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
                           float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
                           float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
-    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
+    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, nullptr, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
                                  norm_out, nullptr, step_count, (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
                                  slnlp::AdamOpts{1, skip_begin, skip_end});
 }
 int slnlp_clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
                          float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
                          float* step_count, void* stream) {
-    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
+    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, nullptr, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
                                  norm_out, nullptr, step_count, (hipStream_t)stream);
 }
 int slnlp_param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
@@ -1553,17 +1530,19 @@ void slnlp_param_groups_destroy(slnlp_param_groups* groups) { slnlp::param_group
 int slnlp_clip_sgd_step_groups(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* groups,
                                const float* lr_dev, float momentum, float dampening, int nesterov, float max_norm, float* partials,
                                float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
-    return slnlp::clip_sgd_step_groups(params, grads, momentum_buf, n, groups, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
-                                       (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
-                                       slnlp::SgdOpts{dampening, 0.f, nesterov, step_count, skip_begin, skip_end});
+    SLNLP_CHECK_ARG(groups, "clip_sgd_step_groups: null pointer");
+    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, groups, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
+                                (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
+                                slnlp::SgdOpts{dampening, 0.f, nesterov, step_count, skip_begin, skip_end});
 }
 int slnlp_clip_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                                 const slnlp_param_groups* groups, const float* lr_dev, float beta1, float beta2, float eps,
                                 int decoupled, float max_norm, float* partials, float* norm_out, float* step_count,
                                 int64_t skip_begin, int64_t skip_end, void* stream) {
-    return slnlp::clip_adam_step_groups(params, grads, exp_avg, exp_avg_sq, n, groups, lr_dev, beta1, beta2, eps, max_norm, partials,
-                                        norm_out, nullptr, step_count, (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
-                                        slnlp::AdamOpts{decoupled ? 1 : 0, skip_begin, skip_end});
+    SLNLP_CHECK_ARG(groups, "clip_adam_step_groups: null pointer");
+    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, groups, lr_dev, beta1, beta2, eps, 0.f, max_norm, partials,
+                                 norm_out, nullptr, step_count, (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
+                                 slnlp::AdamOpts{decoupled ? 1 : 0, skip_begin, skip_end});
 }
 int slnlp_gather_batch(const int64_t* X, const int64_t* lengths, const int64_t* y, const int64_t* order, int64_t row0, int B, int S,
                        int64_t* X_out, int64_t* len_out, int64_t* y_out, void* stream) {

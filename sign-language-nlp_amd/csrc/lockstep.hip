@@ -45,17 +45,6 @@ namespace slnlp {
 constexpr int LS_MAX_FITS = 64;
 constexpr int LS_SLOTS = 4;
 
-// hooks of the RNN plan (its struct is private to rnn_plan.hip)
-int rnn_ls_prepare(slnlp_rnn_plan* pl, int B, hipStream_t st);
-int rnn_ls_record(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, const int64_t* len, int B, int train, float momentum,
-                  float max_norm, const LsAdam* adam, float* exp_avg_sq, hipStream_t st);
-void rnn_ls_outputs(slnlp_rnn_plan* pl, float* logp, float* loss, const int* dyn);
-void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train);
-const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl);
-unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl);
-float* rnn_ls_lr(slnlp_rnn_plan* pl);
-int rnn_ls_groups(slnlp_rnn_plan* pl, int force);
-
 struct GatherArgs {
     const int64_t* const* X;     // [K] dataset pointers (device table)
     const int64_t* const* y;
@@ -143,21 +132,8 @@ struct Program {
 
 using namespace slnlp;
 
-// What the driver needs from one fit, whatever its plan type.
-struct LsFit {
-    void* plan;
-    int (*prepare)(void* plan, int B, hipStream_t st);      // work that must stay outside a recorded program (memsets, re-splits)
-    int (*record)(void* plan, const int64_t* X, const int64_t* y, const int64_t* len, int B, int train, float momentum, float max_norm,
-                  const LsAdam* adam, float* exp_avg_sq, hipStream_t st);   // the ordinary step code, run under a Recorder
-    void (*outputs)(void* plan, float* logp, float* loss, const int* dyn);
-    void (*replayed)(void* plan, int B, int train);         // host bookkeeping after the step's launches were issued
-    unsigned (*opts_gen)(void* plan);                       // generation of the plan's criterion / update settings (TrainOpts)
-    float* (*lr)(void* plan);                               // the device float(s) the plan's update launches read the learning rate from
-    int (*groups)(void* plan, int force);                   // the plan's param-group count (0: none); force >= 0 sets TrainOpts::force_groups
-};
-
 struct LockstepGroup {
-    std::vector<LsFit> fits;
+    std::vector<PlanCore*> fits;                    // what the driver needs from a fit, whatever its plan type (plan_core.hpp)
     bool has_len = false;
     int K = 0, S = 0, maxB = 0;
     int destroy_sync = 1;                           // slnlp_*_lockstep_set_destroy_sync (launch.hpp)
@@ -412,8 +388,8 @@ static int upload_lr_targets(LockstepGroup* ls, hipStream_t st) {
     std::vector<float*> lr(ls->K);
     std::vector<int> width(ls->K);
     for (int f = 0; f < ls->K; ++f) {
-        lr[f] = ls->fits[f].lr(ls->fits[f].plan);
-        const int g = ls->fits[f].groups(ls->fits[f].plan, -1);
+        lr[f] = ls->fits[f]->lr_target();
+        const int g = ls->fits[f]->opts.n_groups();
         width[f] = g > 0 ? g : 1;
     }
     if (hipMemcpyAsync(ls->d_lr, lr.data(), ls->K * sizeof(void*), hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -434,7 +410,7 @@ static int upload_slot_tables(LockstepGroup* ls, LockstepGroup::Slot& s, hipStre
 
 static void ls_destroy(LockstepGroup* ls) {
     destroy_sync(ls->destroy_sync);    // tables live in caller memory that may be freed next
-    for (LsFit& f : ls->fits) f.outputs(f.plan, nullptr, nullptr, nullptr);
+    for (PlanCore* f : ls->fits) f->ls_logp = f->ls_loss = nullptr, f->ls_dyn = nullptr;
 }
 
 static int ls_set_data(LockstepGroup* ls, int slot, const int64_t* const* X, const int64_t* const* y, const int64_t* const* len,
@@ -534,7 +510,7 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
                         momentum, max_norm, ls->opt_momentum, ls->opt_max_norm);
     }
     std::vector<unsigned> gen(ls->K);
-    for (int f = 0; f < ls->K; ++f) gen[f] = ls->fits[f].opts_gen(ls->fits[f].plan);
+    for (int f = 0; f < ls->K; ++f) gen[f] = ls->fits[f]->opts.gen;
     if (gen != ls->rec_gen) {
         // no program is left to read the table space: hand it back and put the slots' pointer tables at its start again
         // (as set_data does), ordered on `st` behind every launch that read the old tables
@@ -546,7 +522,7 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
             if (ls->slot[k].set) SLNLP_TRY(upload_slot_tables(ls, ls->slot[k], st));
         SLNLP_TRY(upload_lr_targets(ls, st));          // a fit's param groups may have come or gone
     }
-    for (LsFit& f : ls->fits) SLNLP_TRY(f.prepare(f.plan, B, st));
+    for (PlanCore* f : ls->fits) SLNLP_TRY(f->prepare(B, st));
     const auto key = std::make_tuple(slot, B, train ? 1 : 0);
     auto it = ls->programs.find(key);
     if (it == ls->programs.end()) {
@@ -555,17 +531,17 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
         // one kernel per call site: as soon as one fit has param groups, every fit records the grouped update (the others with a
         // one-segment table: the one-group kernel's bits)
         bool any_groups = false;
-        for (LsFit& f : ls->fits) any_groups = any_groups || f.groups(f.plan, -1) > 0;
-        for (LsFit& f : ls->fits) f.groups(f.plan, any_groups ? 1 : 0);
+        for (PlanCore* f : ls->fits) any_groups = any_groups || f->opts.n_groups() > 0;
+        for (PlanCore* f : ls->fits) f->opts.force_groups = any_groups;
         for (int f = 0; f < ls->K && !rc; ++f) {
-            LsFit& fit = ls->fits[f];
-            fit.outputs(fit.plan, s.logp[f], s.loss[f], ls->dyn);
+            PlanCore* fit = ls->fits[f];
+            fit->ls_logp = s.logp[f]; fit->ls_loss = s.loss[f]; fit->ls_dyn = ls->dyn;
             set_recorder(&recs[f]);
-            rc = fit.record(fit.plan, ls->Xst[f], ls->yst[f], ls->Lst[f], B, train, momentum, max_norm, ls->use_adam ? &ls->adam : nullptr,
-                            ls->use_adam ? ls->v2[f] : nullptr, st);
+            rc = fit->record(ls->Xst[f], ls->yst[f], ls->Lst[f], B, train, momentum, max_norm, ls->use_adam ? &ls->adam : nullptr,
+                             ls->use_adam ? ls->v2[f] : nullptr, st);
             set_recorder(nullptr);
         }
-        for (LsFit& f : ls->fits) f.groups(f.plan, 0);      // a solo step of such a plan takes its own kernel again
+        for (PlanCore* f : ls->fits) f->opts.force_groups = false;      // a solo step of such a plan takes its own kernel again
         if (rc) return rc;
         Program prog;
         SLNLP_TRY(merge(ls, recs, prog, st));
@@ -586,7 +562,7 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
     hipLaunchKernelGGL(ls_gather_kernel, dim3(gx, 1, ls->K), dim3(256), 0, st, g);
     SLNLP_CHECK_LAUNCH("lockstep gather");
     SLNLP_TRY(replay(it->second, st));
-    for (LsFit& f : ls->fits) f.replayed(f.plan, B, train);
+    for (PlanCore* f : ls->fits) f->replayed(B, train);
     return 0;
 }
 
@@ -625,56 +601,19 @@ static int ls_num_launches(LockstepGroup* ls, int slot, int B, int train) {
     return it == ls->programs.end() ? -1 : (int)it->second.ops.size() + 1;
 }
 
-// ---------------------------------------------------------------------------------------------- Transformer hooks ----
-static int tf_prepare(void* p, int B, hipStream_t st) {
-    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
-    SLNLP_TRY(pl->prepare_planes(B, st));      // re-zero plane padding when B changes
-    SLNLP_TRY(pl->ensure_wplanes(st));         // never part of a recorded program: the update kernel keeps the planes current
-    return pl->ensure_wq(st);                  // precision 8: re-quantised weights, likewise outside the program
+// K plans of one type and shape become the fits of `ls`.  `what`: the entry point's name, the prefix of its error texts
+static int ls_create(const char* what, LockstepGroup* ls, PlanCore* const* plans, int K, bool has_len, void* workspace,
+                     int64_t workspace_bytes, hipStream_t st) {
+    for (int f = 0; f < K; ++f) {
+        SLNLP_CHECK_ARG(plans[f]->same_shape(*plans[0]),
+                        "%s: plan %d does not have the shape of plan 0 (lr, dropout rate and seed may differ; "
+                        "dropout on/off may not)", what, f);
+        for (int g = 0; g < f; ++g) SLNLP_CHECK_ARG(plans[g] != plans[f], "%s: plan %d listed twice", what, f);
+    }
+    ls->has_len = has_len;
+    ls->fits.assign(plans, plans + K);
+    return ls_init(ls, plans[0]->max_B, plans[0]->S, workspace, workspace_bytes, st);
 }
-static int tf_record(void* p, const int64_t* X, const int64_t* y, const int64_t*, int B, int train, float momentum, float max_norm,
-                     const LsAdam* adam, float* exp_avg_sq, hipStream_t st) {
-    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
-    SLNLP_TRY(pl->forward_impl(X, y, B, train, nullptr, st));
-    if (!train) return 0;
-    SLNLP_TRY(slnlp_tf_backward(pl, st));
-    if (adam)
-        return slnlp_tf_optim_adam(pl, exp_avg_sq, adam->beta1, adam->beta2, adam->eps, pl->opts.adam_weight_decay(adam->weight_decay),
-                                   max_norm, st);
-    return slnlp_tf_optim(pl, momentum, max_norm, st);
-}
-static void tf_outputs(void* p, float* logp, float* loss, const int* dyn) {
-    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
-    pl->ls_logp = logp; pl->ls_loss = loss; pl->ls_dyn = dyn;
-}
-static void tf_replayed(void* p, int B, int train) {
-    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
-    pl->last_B = B;
-    pl->last_p = train ? pl->cfg.dropout : 0.f;
-    if (train) pl->params_stepped();
-}
-
-// ------------------------------------------------------------------------------------------------------ RNN hooks ----
-static int rnn_prepare(void* p, int B, hipStream_t st) { return rnn_ls_prepare((slnlp_rnn_plan*)p, B, st); }
-static int rnn_record(void* p, const int64_t* X, const int64_t* y, const int64_t* len, int B, int train, float momentum, float max_norm,
-                      const LsAdam* adam, float* exp_avg_sq, hipStream_t st) {
-    return rnn_ls_record((slnlp_rnn_plan*)p, X, y, len, B, train, momentum, max_norm, adam, exp_avg_sq, st);
-}
-static void rnn_outputs(void* p, float* logp, float* loss, const int* dyn) { rnn_ls_outputs((slnlp_rnn_plan*)p, logp, loss, dyn); }
-static void rnn_replayed(void* p, int B, int train) { rnn_ls_replayed((slnlp_rnn_plan*)p, B, train); }
-static unsigned rnn_opts_gen(void* p) { return rnn_ls_opts_gen((slnlp_rnn_plan*)p); }
-static unsigned tf_opts_gen(void* p) { return ((slnlp_tf_plan*)p)->opts.gen; }
-static float* rnn_lr(void* p) { return rnn_ls_lr((slnlp_rnn_plan*)p); }
-static float* tf_lr(void* p) {
-    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
-    return pl->opts.groups ? const_cast<float*>(pl->opts.groups_lr) : pl->buf.lr;
-}
-static int tf_groups(void* p, int force) {
-    slnlp_tf_plan* pl = (slnlp_tf_plan*)p;
-    if (force >= 0) pl->opts.force_groups = force != 0;
-    return pl->opts.n_groups();
-}
-static int rnn_groups(void* p, int force) { return rnn_ls_groups((slnlp_rnn_plan*)p, force); }
 
 // the two learning-rate pointer tables of ls_init and the slots' order tables, each on a 256-byte boundary of the bump allocator
 static size_t ls_lr_table_bytes(int K) { return (3 + LS_SLOTS) * (((size_t)K * sizeof(void*) + 255) & ~(size_t)255); }
@@ -703,19 +642,13 @@ int slnlp_tf_lockstep_create(slnlp_tf_plan** plans, int K, void* workspace, int6
                              slnlp_tf_lockstep** out) {
     SLNLP_CHECK_ARG(plans && out && K >= 1 && K <= LS_MAX_FITS, "lockstep_create: 1..%d plans", LS_MAX_FITS);
     SLNLP_CHECK_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "lockstep_create: workspace must be 256-byte aligned");
-    const slnlp_tf_config& c0 = plans[0]->cfg;
+    std::vector<PlanCore*> cores(K);
     for (int f = 0; f < K; ++f) {
         SLNLP_CHECK_ARG(plans[f], "lockstep_create: null plan %d", f);
-        const slnlp_tf_config& c = plans[f]->cfg;
-        SLNLP_CHECK_ARG(c.E == c0.E && c.H == c0.H && c.N == c0.N && c.F == c0.F && c.Vs == c0.Vs && c.Vt == c0.Vt && c.B == c0.B &&
-                            c.S == c0.S && c.precision == c0.precision && (c.dropout > 0.f) == (c0.dropout > 0.f),
-                        "lockstep_create: plan %d does not have the shape of plan 0 (lr, dropout rate and seed may differ; "
-                        "dropout on/off may not)", f);
-        for (int g = 0; g < f; ++g) SLNLP_CHECK_ARG(plans[g] != plans[f], "lockstep_create: plan %d listed twice", f);
+        cores[f] = plans[f];
     }
     slnlp_tf_lockstep* ls = new slnlp_tf_lockstep();
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], tf_prepare, tf_record, tf_outputs, tf_replayed, tf_opts_gen, tf_lr, tf_groups});
-    const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
+    const int rc = ls_create("lockstep_create", ls, cores.data(), K, false, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;
     return 0;
@@ -771,20 +704,13 @@ int slnlp_rnn_lockstep_create(slnlp_rnn_plan** plans, int K, void* workspace, in
                               slnlp_rnn_lockstep** out) {
     SLNLP_CHECK_ARG(plans && out && K >= 1 && K <= LS_MAX_FITS, "rnn_lockstep_create: 1..%d plans", LS_MAX_FITS);
     SLNLP_CHECK_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "rnn_lockstep_create: workspace must be 256-byte aligned");
-    for (int f = 0; f < K; ++f) SLNLP_CHECK_ARG(plans[f], "rnn_lockstep_create: null plan %d", f);
-    const slnlp_rnn_config& c0 = *rnn_ls_cfg(plans[0]);
+    std::vector<PlanCore*> cores(K);
     for (int f = 0; f < K; ++f) {
-        const slnlp_rnn_config& c = *rnn_ls_cfg(plans[f]);
-        SLNLP_CHECK_ARG(c.lstm == c0.lstm && c.E == c0.E && c.Hd == c0.Hd && c.N == c0.N && c.Vs == c0.Vs && c.Vt == c0.Vt && c.B == c0.B &&
-                            c.S == c0.S && c.precision == c0.precision && (c.dropout > 0.f) == (c0.dropout > 0.f),
-                        "rnn_lockstep_create: plan %d does not have the shape of plan 0 (lr, dropout rate and seed may differ; "
-                        "dropout on/off may not)", f);
-        for (int g = 0; g < f; ++g) SLNLP_CHECK_ARG(plans[g] != plans[f], "rnn_lockstep_create: plan %d listed twice", f);
+        SLNLP_CHECK_ARG(plans[f], "rnn_lockstep_create: null plan %d", f);
+        cores[f] = rnn_core(plans[f]);
     }
     slnlp_rnn_lockstep* ls = new slnlp_rnn_lockstep();
-    ls->has_len = true;
-    for (int f = 0; f < K; ++f) ls->fits.push_back(LsFit{plans[f], rnn_prepare, rnn_record, rnn_outputs, rnn_replayed, rnn_opts_gen, rnn_lr, rnn_groups});
-    const int rc = ls_init(ls, c0.B, c0.S, workspace, workspace_bytes, (hipStream_t)stream);
+    const int rc = ls_create("rnn_lockstep_create", ls, cores.data(), K, true, workspace, workspace_bytes, (hipStream_t)stream);
     if (rc) { delete ls; return rc; }
     *out = ls;
     return 0;

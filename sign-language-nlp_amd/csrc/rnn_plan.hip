@@ -16,11 +16,10 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "plan_core.hpp"
 #include <cstring>
 
 namespace slnlp {
-
-static inline long align_up_r(long v, long a) { return (v + a - 1) / a * a; }
 
 // K-slices of the recurrent data gradient (see slnlp_rnn_plan::kslices).  SLNLP_RNN_KSLICE=gate: one per gate (A / B measurements)
 static int rnn_kslices(const slnlp_rnn_config& c) {
@@ -55,7 +54,7 @@ static RLayout build_rlayout(const slnlp_rnn_config& c) {
         e.name = n; e.shape[0] = d0; e.shape[1] = d1; e.ndim = d1 > 0 ? 2 : 1;
         e.numel = d1 > 0 ? d0 * d1 : d0;
         e.off = cur;
-        cur = align_up_r(cur + e.numel, 4);
+        cur = align_up(cur + e.numel, 4);
         L.ents.push_back(e);
         return e.off;
     };
@@ -155,7 +154,7 @@ struct RWs {
 static RWs rcarve(const slnlp_rnn_config& c, void* base) {
     RWs w;
     RBump b(base);
-    const size_t B = c.B, S = c.S, E = c.E, Hd = c.Hd, M = B * S, G = c.lstm ? 4 : 3, Vp = align_up_r(c.Vt, 4);
+    const size_t B = c.B, S = c.S, E = c.E, Hd = c.Hd, M = B * S, G = c.lstm ? 4 : 3, Vp = align_up(c.Vt, 4);
     w.emb = b.take<float>(M * E);
     w.demb = b.take<float>(M * E);
     // states that start every step at zero sit together: ONE memset per pass instead of one per (layer, direction)
@@ -253,19 +252,13 @@ using namespace slnlp;
 
 enum { RSITE_ENC0 = 32, RSITE_DEC0 = 64 };
 
-struct slnlp_rnn_plan {
+// What is not the model -- buffers, settings, captured graphs, the update call, the lockstep outputs -- is PlanCore's
+struct slnlp_rnn_plan : PlanCore {
     slnlp_rnn_config cfg;
-    slnlp_tf_buffers buf;
     RLayout L;
     RWs w;
-    int last_B = 0;
-    float last_p = 0.f;
     const int64_t *last_X = nullptr, *last_y = nullptr, *last_len = nullptr;
-    std::map<int, hipGraphExec_t> graphs;
-    TrainOpts opts;           // slnlp_rnn_set_criterion / slnlp_rnn_set_update
     bool use_planes = false;  // E, Hd multiples of 64: the M = S*B GEMMs run on pre-split bf16 planes (gemm_planes.hip)
-    int planes_B = -1;        // batch size the activation planes' zero padding is valid for
-    int destroy_sync = 1;     // slnlp_rnn_set_destroy_sync: wait for the device before the plan goes away (launch.hpp)
     int wgrad_p = 2, dgrad_p = 2;   // split-bf16 passes of the plane gradient products: the process default AT CREATION, fixed for the plan's life
     bool persistent = false;  // opt-in: all timesteps of an encoder layer in one launch (not yet faster; needs one fit per GPU)
     // backward through time: the cell kernel + K-sliced grouped GEMM pair per timestep (default), or ONE launch per timestep
@@ -274,10 +267,28 @@ struct slnlp_rnn_plan {
     // 7.73 vs 7.27): its G K-slices share one CU's LDS-write and conversion bandwidth where the K-sliced launch spreads them over
     // 256 CUs, and a timestep is a latency chain either way.  16 GRU fits in lockstep gain 4 % from it.
     bool unfused_bwd = [] { const char* e = getenv("SLNLP_RNN_FUSED_BWD"); return !(e && atoi(e) != 0); }();
-    // lockstep (lockstep.hip): where lsm_nll also puts the batch's log-probs / loss (device row and batch index in ls_dyn)
-    float* ls_logp = nullptr;
-    float* ls_loss = nullptr;
-    const int* ls_dyn = nullptr;
+
+    int forward(const int64_t* X, const int64_t* y, const int64_t* lengths, int B, int train, float* logp, hipStream_t st) override {
+        return slnlp_rnn_forward(this, X, y, lengths, B, train, logp, st);
+    }
+    int backward(hipStream_t st) override { return slnlp_rnn_backward(this, st); }
+    // no weight planes leave the update; the decaying updates leave the decoder's dead pre_output_layer alone -- torch skips the
+    // parameter, its grad stays None (file header) -- up to its end rounded up to 16 bytes (the padding after it is never written)
+    UpdateRanges update_ranges() const override {
+        UpdateRanges r;
+        r.skip_begin = L.pre_out;
+        r.skip_end = (L.pre_out + (int64_t)cfg.Hd * (3 * (int64_t)cfg.Hd + cfg.E) + 3) / 4 * 4;
+        return r;
+    }
+    int check_recordable() const override {
+        SLNLP_CHECK_ARG(!persistent, "lockstep: the persistent RNN layer kernel needs the GPU to itself -- switch it off");
+        return 0;
+    }
+    bool same_shape(const PlanCore& other) const override {
+        const slnlp_rnn_config &c = cfg, &c0 = static_cast<const slnlp_rnn_plan&>(other).cfg;
+        return c.lstm == c0.lstm && c.E == c0.E && c.Hd == c0.Hd && c.N == c0.N && c.Vs == c0.Vs && c.Vt == c0.Vt && c.B == c0.B &&
+               c.S == c0.S && c.precision == c0.precision && (c.dropout > 0.f) == (c0.dropout > 0.f);
+    }
 
     float* P(long off) const { return buf.params + off; }
     float* Gd(long off) const { return buf.grads + off; }
@@ -315,7 +326,7 @@ struct slnlp_rnn_plan {
         return gemm(dgr_args(dy, ldy, M, Nout, W, ldw, Kin, dx, ldx, resid), st);
     }
     // zero padding of the activation planes is per batch size: re-zero when it changes (outside any capture)
-    int prepare_planes(int B, hipStream_t st) {
+    int prepare_planes(int B, hipStream_t st) override {
         if (!use_planes || B == planes_B) return 0;
         if (hipMemsetAsync(w.planes_begin, 0, (size_t)(w.planes_end - w.planes_begin), st) != hipSuccess) {
             set_error("rnn: zeroing operand planes failed");
@@ -401,11 +412,7 @@ int64_t slnlp_rnn_workspace_bytes(const slnlp_rnn_config* cfg) {
 }
 
 void slnlp_rnn_destroy(slnlp_rnn_plan* plan) {
-    if (!plan) return;
-    if (!plan->graphs.empty()) (void)hipDeviceSynchronize();   // graph execs are torn down below
-    else destroy_sync(plan->destroy_sync);
-    for (auto& kv : plan->graphs) (void)hipGraphExecDestroy(kv.second);
-    delete plan;
+    if (plan) plan->destroy();
 }
 
 int slnlp_rnn_create(const slnlp_rnn_config* cfg, const slnlp_tf_buffers* buf, slnlp_rnn_plan** out) {
@@ -423,6 +430,8 @@ int slnlp_rnn_create(const slnlp_rnn_config* cfg, const slnlp_tf_buffers* buf, s
     p->buf = *buf;
     p->L = build_rlayout(*cfg);
     p->w = rcarve(*cfg, buf->workspace);
+    p->arena = p->L.total; p->opt_partials = p->w.opt_partials;
+    p->max_B = cfg->B; p->S = cfg->S; p->Vt = cfg->Vt; p->dropout = cfg->dropout;
     p->use_planes = (cfg->E % 64 == 0) && (cfg->Hd % 64 == 0);
     std::vector<int64_t> bos(cfg->B, (int64_t)cfg->bos_idx);
     if (hipMemcpy(p->w.bos_ids, bos.data(), bos.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess ||
@@ -449,7 +458,7 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
     const RWs& w = pl->w;
     const RLayout& L = pl->L;
     const int lstm = c.lstm, G = lstm ? 4 : 3, E = c.E, Hd = c.Hd, S = c.S, N = c.N, M = S * B, GH = G * Hd;
-    const int Vp = (int)align_up_r(c.Vt, 4);
+    const int Vp = (int)align_up(c.Vt, 4);
     const float p = train ? c.dropout : 0.f;
     const unsigned long long* rng = pl->buf.rng;
     pl->last_B = B; pl->last_p = p; pl->last_X = X; pl->last_y = y; pl->last_len = lengths;
@@ -596,7 +605,7 @@ int slnlp_rnn_health(slnlp_rnn_plan* pl, int* status) {
 
 int slnlp_rnn_seed_dlogp(slnlp_rnn_plan* pl, const float* dlogp, void* stream) {
     SLNLP_CHECK_ARG(pl && dlogp && pl->last_B > 0, "rnn_seed_dlogp: needs a prior forward");
-    return lsm_bwd(pl->w.logp, dlogp, pl->last_B, pl->cfg.Vt, pl->w.dlogits, align_up_r(pl->cfg.Vt, 4), (hipStream_t)stream);
+    return lsm_bwd(pl->w.logp, dlogp, pl->last_B, pl->cfg.Vt, pl->w.dlogits, align_up(pl->cfg.Vt, 4), (hipStream_t)stream);
 }
 
 int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
@@ -608,7 +617,7 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
     const RWs& w = pl->w;
     const RLayout& L = pl->L;
     const int B = pl->last_B, lstm = c.lstm, G = lstm ? 4 : 3, E = c.E, Hd = c.Hd, S = c.S, N = c.N, M = S * B;
-    const int GH = G * Hd, Vp = (int)align_up_r(c.Vt, 4);
+    const int GH = G * Hd, Vp = (int)align_up(c.Vt, 4);
     const float p = pl->last_p;
     const unsigned long long* rng = pl->buf.rng;
     const int64_t *X = pl->last_X, *lengths = pl->last_len;
@@ -759,86 +768,32 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
     return 0;
 }
 
-// end of the decoder's pre_output_layer in the arena, rounded up to 16 bytes (the padding after it is never written): the
-// range the weight-decaying updates leave alone -- torch skips the parameter, its grad stays None (rnn_plan.hip header)
-static int64_t rnn_pre_out_end(const slnlp_rnn_plan* pl) {
-    const int64_t Hd = pl->cfg.Hd, E = pl->cfg.E;
-    return (pl->L.pre_out + Hd * (3 * Hd + E) + 3) / 4 * 4;
-}
-
 int slnlp_rnn_optim(slnlp_rnn_plan* pl, float momentum, float max_norm, void* stream) {
     SLNLP_CHECK_ARG(pl, "rnn_optim: null plan");
-    StepScope scope((hipStream_t)stream);
-    SLNLP_TRY(scope.rc);
-    const slnlp_param_groups* pg = pl->opts.groups;
-    const float* pg_lr = pl->opts.groups_lr;
-    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
-        SLNLP_TRY(pl->opts.one_segment(pl->L.total, pl->opts.sgd(nullptr, 0, 0).weight_decay, (hipStream_t)stream, &pg));
-        pg_lr = pl->buf.lr;
-    }
-    if (pg)
-        return clip_sgd_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pg, pg_lr,
-                                    momentum, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
-                                    PlaneOut{}, 0, -1, pl->opts.sgd(pl->buf.scalars + 3, pl->L.pre_out, rnn_pre_out_end(pl)));
-    return clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
-                         pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream, PlaneOut{}, 0, -1,
-                         pl->opts.sgd(pl->buf.scalars + 3, pl->L.pre_out, rnn_pre_out_end(pl)));
+    return pl->update_sgd(momentum, max_norm, (hipStream_t)stream);
 }
 
-// clip_grad_norm_ + torch.optim.Adam on the arena (any torch optimizer is reachable in the reference through
-// pydoc.locate, /root/reference/helper.py:91-104): exp_avg = buf.momentum, exp_avg_sq = the caller's arena-shaped buffer,
-// step count = scalars[2] (advanced on the device) -- the same fused kernel as slnlp_tf_optim_adam.
+// (any torch optimizer is reachable in the reference through pydoc.locate, /root/reference/helper.py:91-104)
 int slnlp_rnn_optim_adam(slnlp_rnn_plan* pl, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
                          float max_norm, void* stream) {
     SLNLP_CHECK_ARG(pl && exp_avg_sq, "rnn_optim_adam: null argument");
-    StepScope scope((hipStream_t)stream);
-    SLNLP_TRY(scope.rc);
-    const slnlp_param_groups* pg = pl->opts.groups;
-    const float* pg_lr = pl->opts.groups_lr;
-    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
-        SLNLP_TRY(pl->opts.one_segment(pl->L.total, weight_decay, (hipStream_t)stream, &pg));
-        pg_lr = pl->buf.lr;
-    }
-    if (pg)                   // weight decay per group: the call's one value is not read
-        return clip_adam_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pg,
-                                     pg_lr, beta1, beta2, eps, max_norm, pl->w.opt_partials, pl->buf.scalars + 1,
-                                     pl->buf.rng, pl->buf.scalars + 2, (hipStream_t)stream, PlaneOut{}, 0, -1,
-                                     pl->opts.adam(pl->L.pre_out, rnn_pre_out_end(pl)));
-    return clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
-                          weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
-                          (hipStream_t)stream, PlaneOut{}, 0, -1, pl->opts.adam(pl->L.pre_out, rnn_pre_out_end(pl)));
-}
-
-static void rnn_drop_graphs(slnlp_rnn_plan* pl) {
-    if (pl->graphs.empty()) return;
-    (void)hipDeviceSynchronize();   // an exec may still be running
-    for (auto& kv : pl->graphs) (void)hipGraphExecDestroy(kv.second);
-    pl->graphs.clear();
+    return pl->update_adam(exp_avg_sq, beta1, beta2, eps, weight_decay, max_norm, (hipStream_t)stream);
 }
 
 int slnlp_rnn_set_criterion(slnlp_rnn_plan* pl, const float* class_weight, float label_smoothing, int reduction, void* stream) {
     SLNLP_CHECK_ARG(pl, "rnn_set_criterion: null plan");
-    bool changed = false;
-    SLNLP_TRY(pl->opts.set_criterion(pl->cfg.Vt, class_weight, label_smoothing, reduction, (hipStream_t)stream, &changed));
-    if (changed) rnn_drop_graphs(pl);
-    return 0;
+    return pl->set_criterion(class_weight, label_smoothing, reduction, (hipStream_t)stream);
 }
 
 int slnlp_rnn_set_update(slnlp_rnn_plan* pl, int kind, float dampening, float weight_decay, int nesterov) {
     SLNLP_CHECK_ARG(pl, "rnn_set_update: null plan");
-    bool changed = false;
-    SLNLP_TRY(pl->opts.set_update(kind, dampening, weight_decay, nesterov, &changed));
-    if (changed) rnn_drop_graphs(pl);
-    return 0;
+    return pl->set_update(kind, dampening, weight_decay, nesterov);
 }
 
 int slnlp_rnn_set_param_groups(slnlp_rnn_plan* pl, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
                                const float* weight_decay, const float* lr_dev, void* stream) {
     SLNLP_CHECK_ARG(pl, "rnn_set_param_groups: null plan");
-    SLNLP_CHECK_ARG(n_segments >= 0, "rnn_set_param_groups: %d segments", n_segments);
-    if (n_segments == 0 && !pl->opts.groups) return 0;
-    rnn_drop_graphs(pl);           // before the old table goes away: a captured update holds its pointers
-    return pl->opts.set_param_groups(pl->L.total, n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
+    return pl->set_param_groups("rnn_set_param_groups", n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
 }
 
 int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* pl, int on) {
@@ -849,68 +804,25 @@ int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* pl, int on) {
 
 int slnlp_rnn_train_step(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, const int64_t* lengths, int B,
                          float momentum, float max_norm, float* logp, void* stream) {
-    StepScope scope((hipStream_t)stream);        // one scope for the whole step (the nested entry points re-enter it)
-    SLNLP_TRY(scope.rc);
-    SLNLP_TRY(slnlp_rnn_forward(pl, X, y, lengths, B, 1, logp, stream));
-    SLNLP_TRY(slnlp_rnn_backward(pl, stream));
-    return slnlp_rnn_optim(pl, momentum, max_norm, stream);
+    SLNLP_CHECK_ARG(pl, "rnn_forward: X, y and lengths are required");      // (what the step's forward says about a null plan)
+    return pl->train_step(X, y, lengths, B, momentum, max_norm, logp, (hipStream_t)stream);
 }
 
 int slnlp_rnn_graph_capture_train(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, const int64_t* lengths, int B,
                                   float momentum, float max_norm, float* logp, void* stream) {
-    SLNLP_CHECK_ARG(pl && stream, "rnn_graph_capture_train: needs a plan and a non-default stream");
-    hipStream_t st = (hipStream_t)stream;
-    SLNLP_TRY(pl->prepare_planes(B, (hipStream_t)stream));   // must not be captured: it runs once per batch-size change
-    auto old = pl->graphs.find(B);
-    if (old != pl->graphs.end()) {
-        (void)hipStreamSynchronize(st);
-        (void)hipGraphExecDestroy(old->second);
-        pl->graphs.erase(old);
-    }
-    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        set_error("rnn_graph_capture_train: begin capture failed: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    int rc = slnlp_rnn_train_step(pl, X, y, lengths, B, momentum, max_norm, logp, stream);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(st, &g);
-    if (rc != 0) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-    }
-    if (e != hipSuccess || !g) {
-        set_error("rnn_graph_capture_train: end capture failed: %s", hipGetErrorString(e));
-        return SLNLP_ERR_LAUNCH;
-    }
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-        set_error("rnn_graph_capture_train: instantiate failed: %s", hipGetErrorString(e));
-        return SLNLP_ERR_LAUNCH;
-    }
-    pl->graphs[B] = exec;
-    return 0;
+    SLNLP_CHECK_ARG(pl, "rnn_graph_capture_train: needs a plan and a non-default stream");
+    return pl->graph_capture_train("rnn_graph_capture_train", X, y, lengths, B, momentum, max_norm, logp, (hipStream_t)stream);
 }
 
 int slnlp_rnn_graph_launch(slnlp_rnn_plan* pl, int B, void* stream) {
     SLNLP_CHECK_ARG(pl, "rnn_graph_launch: null plan");
-    auto it = pl->graphs.find(B);
-    SLNLP_CHECK_ARG(it != pl->graphs.end(), "rnn_graph_launch: no captured graph for batch %d", B);
-    StepScope scope((hipStream_t)stream);
-    SLNLP_TRY(scope.rc);
-    SLNLP_TRY(pl->prepare_planes(B, (hipStream_t)stream));
-    if (hipGraphLaunch(it->second, (hipStream_t)stream) != hipSuccess) {
-        set_error("rnn_graph_launch: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    return 0;
+    return pl->graph_launch("rnn_graph_launch", B, (hipStream_t)stream);
 }
 
 int slnlp_rnn_tap(slnlp_rnn_plan* pl, const char* name, float* out, int64_t max_floats, int64_t* n_out, void* stream) {
     SLNLP_CHECK_ARG(pl && name && out && pl->last_B > 0, "rnn_tap: bad args / no forward yet");
     const slnlp_rnn_config& c = pl->cfg;
-    const int B = pl->last_B, M = B * c.S, Hd = c.Hd, Vp = (int)align_up_r(c.Vt, 4);
+    const int B = pl->last_B, M = B * c.S, Hd = c.Hd, Vp = (int)align_up(c.Vt, 4);
     const std::string n(name);
     const float* src = nullptr;
     int64_t rows = 0, cols = 0, ld = 0;
@@ -933,32 +845,7 @@ int slnlp_rnn_tap(slnlp_rnn_plan* pl, const char* name, float* out, int64_t max_
 
 }  // extern "C"
 
-// ---- hooks of the lockstep driver (lockstep.hip): the plan struct stays private to this file
+// the lockstep driver (lockstep.hip) sees the plan as its PlanCore: the struct stays private to this file
 namespace slnlp {
-int rnn_ls_prepare(slnlp_rnn_plan* pl, int B, hipStream_t st) { return pl->prepare_planes(B, st); }
-int rnn_ls_record(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, const int64_t* len, int B, int train, float momentum,
-                  float max_norm, const LsAdam* adam, float* exp_avg_sq, hipStream_t st) {
-    SLNLP_CHECK_ARG(!pl->persistent, "lockstep: the persistent RNN layer kernel needs the GPU to itself -- switch it off");
-    SLNLP_TRY(slnlp_rnn_forward(pl, X, y, len, B, train, nullptr, st));
-    if (!train) return 0;
-    SLNLP_TRY(slnlp_rnn_backward(pl, st));
-    if (adam)
-        return slnlp_rnn_optim_adam(pl, exp_avg_sq, adam->beta1, adam->beta2, adam->eps, pl->opts.adam_weight_decay(adam->weight_decay),
-                                    max_norm, st);
-    return slnlp_rnn_optim(pl, momentum, max_norm, st);
-}
-void rnn_ls_outputs(slnlp_rnn_plan* pl, float* logp, float* loss, const int* dyn) {
-    pl->ls_logp = logp; pl->ls_loss = loss; pl->ls_dyn = dyn;
-}
-void rnn_ls_replayed(slnlp_rnn_plan* pl, int B, int train) {
-    pl->last_B = B;
-    pl->last_p = train ? pl->cfg.dropout : 0.f;
-}
-const slnlp_rnn_config* rnn_ls_cfg(slnlp_rnn_plan* pl) { return &pl->cfg; }
-unsigned rnn_ls_opts_gen(slnlp_rnn_plan* pl) { return pl->opts.gen; }
-float* rnn_ls_lr(slnlp_rnn_plan* pl) { return pl->opts.groups ? const_cast<float*>(pl->opts.groups_lr) : pl->buf.lr; }
-int rnn_ls_groups(slnlp_rnn_plan* pl, int force) {
-    if (force >= 0) pl->opts.force_groups = force != 0;
-    return pl->opts.n_groups();
-}
+PlanCore* rnn_core(slnlp_rnn_plan* pl) { return pl; }
 }  // namespace slnlp

@@ -56,11 +56,7 @@ int64_t slnlp_tf_workspace_bytes(const slnlp_tf_config* cfg) {
 }
 
 void slnlp_tf_destroy(slnlp_tf_plan* plan) {
-    if (!plan) return;
-    if (!plan->graphs.empty()) (void)hipDeviceSynchronize();   // graph execs are torn down below
-    else destroy_sync(plan->destroy_sync);    // nothing of this plan may still be in flight when its buffers go
-    for (auto& kv : plan->graphs) (void)hipGraphExecDestroy(kv.second);
-    delete plan;
+    if (plan) plan->destroy();
 }
 
 int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, slnlp_tf_plan** out) {
@@ -77,6 +73,8 @@ int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, sln
     p->buf = *buf;
     p->L = build_layout(*cfg);
     p->w = carve(*cfg, buf->workspace);
+    p->arena = p->L.total; p->opt_partials = p->w.opt_partials;
+    p->max_B = cfg->B; p->S = cfg->S; p->Vt = cfg->Vt; p->dropout = cfg->dropout;
     bool ok = attn_init() == 0 && gemm_planes_init() == 0;
     p->use_planes = (cfg->E % 64 == 0) && (cfg->F % 64 == 0);
     p->wgrad_np = wgrad_passes();
@@ -467,54 +465,13 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
 
 int slnlp_tf_optim(slnlp_tf_plan* pl, float momentum, float max_norm, void* stream) {
     SLNLP_CHECK_ARG(pl, "tf_optim: null plan");
-    StepScope scope((hipStream_t)stream);
-    SLNLP_TRY(scope.rc);
-    const slnlp_param_groups* pg = pl->opts.groups;
-    const float* pg_lr = pl->opts.groups_lr;
-    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
-        SLNLP_TRY(pl->opts.one_segment(pl->L.total, pl->opts.sgd(nullptr, 0, 0).weight_decay, (hipStream_t)stream, &pg));
-        pg_lr = pl->buf.lr;
-    }
-    if (pg)
-        SLNLP_TRY(clip_sgd_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pg, pg_lr,
-                                       momentum, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
-                                       pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
-                                       pl->opts.sgd(pl->buf.scalars + 3, 0, 0)));
-    else
-        SLNLP_TRY(clip_sgd_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, pl->L.total, pl->buf.lr, momentum, max_norm,
-                                pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, (hipStream_t)stream,
-                                pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
-                                pl->opts.sgd(pl->buf.scalars + 3, 0, 0)));
-    if (!recording()) pl->params_stepped();      // (a lockstep replay does this per step itself)
-    return 0;
+    return pl->update_sgd(momentum, max_norm, (hipStream_t)stream);
 }
 
-// clip_grad_norm_ + torch.optim.Adam on the arena: exp_avg = buf.momentum, exp_avg_sq = the caller's arena-shaped
-// buffer, step count = scalars[2] (advanced on the device).
 int slnlp_tf_optim_adam(slnlp_tf_plan* pl, float* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay,
                         float max_norm, void* stream) {
     SLNLP_CHECK_ARG(pl && exp_avg_sq, "tf_optim_adam: null argument");
-    StepScope scope((hipStream_t)stream);
-    SLNLP_TRY(scope.rc);
-    const slnlp_param_groups* pg = pl->opts.groups;
-    const float* pg_lr = pl->opts.groups_lr;
-    if (!pg && pl->opts.force_groups) {      // beside a grouped fit of a lockstep group: the same kernel, a one-segment table
-        SLNLP_TRY(pl->opts.one_segment(pl->L.total, weight_decay, (hipStream_t)stream, &pg));
-        pg_lr = pl->buf.lr;
-    }
-    if (pg)                   // weight decay per group: the call's one value is not read
-        SLNLP_TRY(clip_adam_step_groups(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pg,
-                                        pg_lr, beta1, beta2, eps, max_norm, pl->w.opt_partials, pl->buf.scalars + 1,
-                                        pl->buf.rng, pl->buf.scalars + 2, (hipStream_t)stream,
-                                        pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
-                                        pl->opts.adam(0, 0)));
-    else
-        SLNLP_TRY(clip_adam_step(pl->buf.params, pl->buf.grads, pl->buf.momentum, exp_avg_sq, pl->L.total, pl->buf.lr, beta1, beta2, eps,
-                                 weight_decay, max_norm, pl->w.opt_partials, pl->buf.scalars + 1, pl->buf.rng, pl->buf.scalars + 2,
-                                 (hipStream_t)stream, pl->use_planes ? pl->w.wp.out() : PlaneOut{}, pl->wplane_begin(), pl->wplane_end(),
-                                 pl->opts.adam(0, 0)));
-    if (!recording()) pl->params_stepped();
-    return 0;
+    return pl->update_adam(exp_avg_sq, beta1, beta2, eps, weight_decay, max_norm, (hipStream_t)stream);
 }
 
 int slnlp_tf_set_destroy_sync(slnlp_tf_plan* pl, int on) {
@@ -523,46 +480,29 @@ int slnlp_tf_set_destroy_sync(slnlp_tf_plan* pl, int on) {
     return 0;
 }
 
-// A settings change: the captured graphs baked the old settings into their launches -- drop them (the caller re-captures)
-static void tf_drop_graphs(slnlp_tf_plan* pl) {
-    if (pl->graphs.empty()) return;
-    (void)hipDeviceSynchronize();   // an exec may still be running
-    for (auto& kv : pl->graphs) (void)hipGraphExecDestroy(kv.second);
-    pl->graphs.clear();
-}
-
 int slnlp_tf_set_dmem_batched(slnlp_tf_plan* pl, int on) {
     SLNLP_CHECK_ARG(pl, "tf_set_dmem_batched: null plan");
     if (pl->dmem_batched == (on != 0)) return 0;
     pl->dmem_batched = on != 0;
     ++pl->opts.gen;            // a lockstep group re-records its programs: the launch sequence changed
-    tf_drop_graphs(pl);
+    pl->drop_graphs();
     return 0;
 }
 
 int slnlp_tf_set_criterion(slnlp_tf_plan* pl, const float* class_weight, float label_smoothing, int reduction, void* stream) {
     SLNLP_CHECK_ARG(pl, "tf_set_criterion: null plan");
-    bool changed = false;
-    SLNLP_TRY(pl->opts.set_criterion(pl->cfg.Vt, class_weight, label_smoothing, reduction, (hipStream_t)stream, &changed));
-    if (changed) tf_drop_graphs(pl);
-    return 0;
+    return pl->set_criterion(class_weight, label_smoothing, reduction, (hipStream_t)stream);
 }
 
 int slnlp_tf_set_update(slnlp_tf_plan* pl, int kind, float dampening, float weight_decay, int nesterov) {
     SLNLP_CHECK_ARG(pl, "tf_set_update: null plan");
-    bool changed = false;
-    SLNLP_TRY(pl->opts.set_update(kind, dampening, weight_decay, nesterov, &changed));
-    if (changed) tf_drop_graphs(pl);
-    return 0;
+    return pl->set_update(kind, dampening, weight_decay, nesterov);
 }
 
 int slnlp_tf_set_param_groups(slnlp_tf_plan* pl, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
                               const float* weight_decay, const float* lr_dev, void* stream) {
     SLNLP_CHECK_ARG(pl, "tf_set_param_groups: null plan");
-    SLNLP_CHECK_ARG(n_segments >= 0, "tf_set_param_groups: %d segments", n_segments);
-    if (n_segments == 0 && !pl->opts.groups) return 0;
-    tf_drop_graphs(pl);            // before the old table goes away: a captured update holds its pointers
-    return pl->opts.set_param_groups(pl->L.total, n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
+    return pl->set_param_groups("tf_set_param_groups", n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
 }
 
 // The parameter arena was written from outside the library (load_state_dict, a torch optimizer, an in-place edit):
@@ -575,68 +515,19 @@ int slnlp_tf_params_changed(slnlp_tf_plan* pl) {
 
 int slnlp_tf_train_step(slnlp_tf_plan* pl, const int64_t* X, const int64_t* y, int B, float momentum, float max_norm,
                         float* logp, void* stream) {
-    StepScope scope((hipStream_t)stream);        // one scope for the whole step (the nested entry points re-enter it)
-    SLNLP_TRY(scope.rc);
-    SLNLP_TRY(slnlp_tf_forward(pl, X, y, B, 1, logp, stream));
-    SLNLP_TRY(slnlp_tf_backward(pl, stream));
-    return slnlp_tf_optim(pl, momentum, max_norm, stream);
+    SLNLP_CHECK_ARG(pl, "tf_forward: `X` and `y` are required parameters");      // (what the step's forward says about a null plan)
+    return pl->train_step(X, y, nullptr, B, momentum, max_norm, logp, (hipStream_t)stream);
 }
 
-// Capture one train step (fixed X / y / logp device buffers and batch size) into
-// a hipGraph and keep the executable graph in the plan; replay with
-// slnlp_tf_graph_launch.  lr, rng step and the data are read from device memory,
-// so the same graph serves every step of a fit.
 int slnlp_tf_graph_capture_train(slnlp_tf_plan* pl, const int64_t* X, const int64_t* y, int B, float momentum,
                                  float max_norm, float* logp, void* stream) {
-    SLNLP_CHECK_ARG(pl && stream, "tf_graph_capture_train: needs a plan and a non-default stream");
-    hipStream_t st = (hipStream_t)stream;
-    SLNLP_TRY(pl->prepare_planes(B, st));   // must not be captured: it runs once per batch-size change
-    auto old = pl->graphs.find(B);
-    if (old != pl->graphs.end()) {          // re-capture for this batch size: the old exec may still be running
-        (void)hipStreamSynchronize(st);
-        (void)hipGraphExecDestroy(old->second);
-        pl->graphs.erase(old);
-    }
-    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        set_error("tf_graph_capture_train: begin capture failed: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    pl->wplanes_gen = 0;      // the captured step always re-splits the weights: a replay cannot check the arena's generation
-    int rc = slnlp_tf_train_step(pl, X, y, B, momentum, max_norm, logp, stream);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(st, &g);
-    if (rc != 0) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-    }
-    if (e != hipSuccess || !g) {
-        set_error("tf_graph_capture_train: end capture failed: %s", hipGetErrorString(e));
-        return SLNLP_ERR_LAUNCH;
-    }
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (e != hipSuccess) {
-        set_error("tf_graph_capture_train: instantiate failed: %s", hipGetErrorString(e));
-        return SLNLP_ERR_LAUNCH;
-    }
-    pl->graphs[B] = exec;
-    return 0;
+    SLNLP_CHECK_ARG(pl, "tf_graph_capture_train: needs a plan and a non-default stream");
+    return pl->graph_capture_train("tf_graph_capture_train", X, y, nullptr, B, momentum, max_norm, logp, (hipStream_t)stream);
 }
 
 int slnlp_tf_graph_launch(slnlp_tf_plan* pl, int B, void* stream) {
     SLNLP_CHECK_ARG(pl, "tf_graph_launch: null plan");
-    auto it = pl->graphs.find(B);
-    SLNLP_CHECK_ARG(it != pl->graphs.end(), "tf_graph_launch: no captured graph for batch %d", B);
-    StepScope scope((hipStream_t)stream);
-    SLNLP_TRY(scope.rc);
-    SLNLP_TRY(pl->prepare_planes(B, (hipStream_t)stream));
-    if (hipGraphLaunch(it->second, (hipStream_t)stream) != hipSuccess) {
-        set_error("tf_graph_launch: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    pl->params_stepped();
-    return 0;
+    return pl->graph_launch("tf_graph_launch", B, (hipStream_t)stream);
 }
 
 // Debug helper: "name offset" lines (byte offsets into the workspace, in carve order) of every fp32 activation /

@@ -8,10 +8,9 @@
 #include "common.hpp"
 #include "gemm_jobs.hpp"
 #include "launch.hpp"
+#include "plan_core.hpp"
 
 namespace slnlp {
-
-static inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
 
 struct ParamEnt {
     std::string name;
@@ -388,27 +387,17 @@ using namespace slnlp;   // internal header, included only by the plan translati
 // dropout site ids
 enum { SITE_SRC_EMB = 1, SITE_TGT_EMB = 2, SITE_LAYER0 = 16, SITE_PER_LAYER = 8 };
 
-struct slnlp_tf_plan {
+// What is not the model -- buffers, settings, captured graphs, the update call, the lockstep outputs -- is PlanCore's
+struct slnlp_tf_plan : PlanCore {
     slnlp_tf_config cfg;
-    slnlp_tf_buffers buf;
     Layout L;
     Ws w;
-    int last_B = 0;       // batch of the last forward
-    float last_p = 0.f;   // dropout used by the last forward (0 in eval)
     const int64_t* last_X = nullptr;
     const int64_t* last_y = nullptr;
-    std::map<int, hipGraphExec_t> graphs;   // one captured train step per batch size, kept until destroy (or a settings change)
-    TrainOpts opts;                         // slnlp_tf_set_criterion / slnlp_tf_set_update
     int nbE = 0, nbD = 0;  // (dgamma, dbeta) chunk counts of the FULL batch (fixed: the reduce table is static)
-    int destroy_sync = 1;  // slnlp_tf_set_destroy_sync: wait for the device before the plan goes away (launch.hpp)
     // slnlp_tf_set_dmem_batched: d memory of all decoder layers (and their d bv) in ONE launch behind the decoder's layer loop
     // (attention_mem.hip: xmem_dmem_all) instead of a launch per layer inside it -- nothing on the decoder's chain reads d memory
     bool dmem_batched = true;
-    // Lockstep (lockstep.hip): where this fit's per-step outputs go while it advances as one of K fits -- an epoch-long
-    // log-prob buffer and a per-batch loss history, indexed through two device scalars the driver updates per step
-    float* ls_logp = nullptr;       // [rows of the epoch, Vt]
-    float* ls_loss = nullptr;       // [batches of the epoch]
-    const int* ls_dyn = nullptr;    // {first row of the batch, index of the batch}
     // precision 8: the forward products run on the fp8 MFMA (e4m3 activations, scale 1; e4m3 weights with one scale per
     // output row, re-quantised from the fp32 master weights whenever the arena has moved); the backward stays split-bf16
     int prec3() const { return cfg.precision == 8 ? 3 : cfg.precision; }
@@ -446,16 +435,40 @@ struct slnlp_tf_plan {
     static constexpr int ROWS_MAX_B = 64;
     bool rows_for(int B, int drop_head_dim) const { return B <= ROWS_MAX_B || drop_head_dim != 0; }   // (per-head dropout is not built into the plane GEMM)
     // the optimizer just rewrote the arena (and, with planes, the planes with it)
-    void params_stepped() {
+    void params_stepped() override {
         const unsigned long long g = bump_params_generation(buf.params);
         if (use_planes) wplanes_gen = g;
     }
+    // the captured step always re-splits the weights: a replay cannot check the arena's generation
+    void before_capture() override { wplanes_gen = 0; }
+    UpdateRanges update_ranges() const override {
+        UpdateRanges r;
+        if (use_planes) r.wp = w.wp.out();
+        r.wp_begin = wplane_begin();
+        r.wp_end = wplane_end();
+        return r;
+    }
+    // outside a recorded lockstep program: re-zeroed plane padding when B changes; the weight planes (the update kernel keeps
+    // them current) and, precision 8, the re-quantised weights
+    int prepare(int B, hipStream_t st) override {
+        SLNLP_TRY(prepare_planes(B, st));
+        SLNLP_TRY(ensure_wplanes(st));
+        return ensure_wq(st);
+    }
+    bool same_shape(const PlanCore& other) const override {
+        const slnlp_tf_config &c = cfg, &c0 = static_cast<const slnlp_tf_plan&>(other).cfg;
+        return c.E == c0.E && c.H == c0.H && c.N == c0.N && c.F == c0.F && c.Vs == c0.Vs && c.Vt == c0.Vt && c.B == c0.B && c.S == c0.S &&
+               c.precision == c0.precision && (c.dropout > 0.f) == (c0.dropout > 0.f);
+    }
+    int forward(const int64_t* X, const int64_t* y, const int64_t*, int B, int train, float* logp, hipStream_t st) override {
+        return slnlp_tf_forward(this, X, y, B, train, logp, st);
+    }
+    int backward(hipStream_t st) override { return slnlp_tf_backward(this, st); }
     bool use_planes = false;   // E, F multiples of 64: M = S*B GEMMs run on pre-split bf16 planes (gemm_planes.hip)
     bool use_rows = false;     // ... and the decoder's B-row products on planes, register-direct (gemm_rows.hip; K <= 1024)
     // split-bf16 passes of the plane GEMM's gradient products: the process default AT CREATION (slnlp_set_backward_passes), fixed for the
     // plan's life -- a captured graph, a recorded lockstep program and every host thread that steps this plan issue the same products
     int wgrad_np = 2, dgrad_np = 2;
-    int planes_B = -1;         // batch size the activation planes' zero padding is valid for
 
     float* P(long off) const { return buf.params + off; }
     float* G(long off) const { return buf.grads + off; }
@@ -721,7 +734,7 @@ struct slnlp_tf_plan {
         return wb_defers(l, k) ? gemm(dg, st) : wd_group(wg, dg, 0, st);
     }
     // zero padding of the activation planes is per batch size: re-zero when it changes (outside any capture)
-    int prepare_planes(int B, hipStream_t st) {
+    int prepare_planes(int B, hipStream_t st) override {
         if (!use_planes) return 0;
         if (B != planes_B) {
             if (hipMemsetAsync(w.planes_begin, 0, (size_t)(w.planes_end - w.planes_begin), st) != hipSuccess) {

@@ -34,7 +34,7 @@ class LockstepGroup:
     def __init__(self, engines):
         cfg = engines[0].cfg
         self.engines, self.K, self.device = list(engines), len(engines), engines[0].device
-        self.kind = "rnn" if type(engines[0]).__name__ == "RnnEngine" else "tf"
+        self.kind = engines[0].prefix                    # "tf" / "rnn": the C family
         assert all(type(e) is type(engines[0]) for e in engines), "lockstep: one engine type per group"
         nbytes = int(self._fn("workspace_bytes")(C.byref(cfg), self.K))
         if nbytes < 0:
@@ -45,7 +45,7 @@ class LockstepGroup:
         out = C.c_void_p()
         check(self._fn("create")(handles, self.K, ptr(self.workspace), nbytes, self._sp(), C.byref(out)), f"{self.kind}_lockstep_create")
         self.handle = out
-        check(self._fn("set_destroy_sync")(out, 0), "lockstep_set_destroy_sync")   # torch-allocated tables: see tf_engine.py
+        check(self._fn("set_destroy_sync")(out, 0), "lockstep_set_destroy_sync")   # torch-allocated tables: see _engine.py
         self.data, self.logp, self.loss, self.rows, self.n_visit, self._orders = {}, {}, {}, {}, {}, {}
 
     def _fn(self, name):                                 # a method, not a closure over self: no reference cycle
@@ -60,7 +60,7 @@ class LockstepGroup:
         if h:
             ls, al = getattr(self, "_last_stream", None), getattr(self, "_alloc_stream", None)
             if ls is not None and al is not None and ls != al:
-                ls.synchronize()                         # the tables go back to another stream's pool (tf_engine.__del__)
+                ls.synchronize()                         # the tables go back to another stream's pool (_engine.PlanEngine.__del__)
             self._fn("destroy")(h)
 
     __del__ = close
