@@ -5,6 +5,8 @@
 // virtual methods, called a few times per step on the host, never per launch.
 #pragma once
 #include <map>
+#include <string>
+#include <vector>
 
 #include "common.hpp"
 #include "launch.hpp"
@@ -12,6 +14,52 @@
 namespace slnlp {
 
 static inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
+
+// ---- what both plan types lay out the same way
+// one tensor of the flat parameter arena (names / shapes = the reference state_dict)
+struct ParamEnt {
+    std::string name;
+    int64_t shape[2];
+    int ndim;
+    int64_t off, numel;
+};
+// the body of slnlp_{tf,rnn}_param_info; `what` is the entry point's name, the prefix of its error text
+static inline int param_info(const std::vector<ParamEnt>& ents, int i, const char* what, char* name, int64_t shape[2], int* ndim, int64_t* offset) {
+    SLNLP_CHECK_ARG(i >= 0 && i < (int)ents.size(), "%s: index %d out of range", what, i);
+    const ParamEnt& e = ents[i];
+    if (name) {
+        strncpy(name, e.name.c_str(), 127);
+        name[127] = 0;
+    }
+    if (shape) {
+        shape[0] = e.shape[0];
+        shape[1] = e.shape[1];
+    }
+    if (ndim) *ndim = e.ndim;
+    if (offset) *offset = e.off;
+    return 0;
+}
+// the workspace carver: every buffer on a 256-byte boundary
+struct Bump {
+    char* base;
+    size_t cur = 0;
+    explicit Bump(void* b) : base((char*)b) {}
+    template <typename T>
+    T* take(size_t n) {
+        cur = (cur + 255) & ~(size_t)255;
+        T* p = (T*)(base + cur);
+        cur += n * sizeof(T);
+        return p;
+    }
+};
+// bf16 hi/lo planes of a GEMM operand (same logical shape / row stride as its fp32 twin, rows
+// zero-padded to a multiple of 64): written once by the producer, read by gemm_planes.hip
+struct PP {
+    unsigned short *hi = nullptr, *lo = nullptr;
+    unsigned char* q8 = nullptr;        // precision 8: forward operands also as an e4m3 plane
+    PlaneOut out() const { PlaneOut o; o.hi = hi; o.lo = lo; o.q8 = q8; return o; }
+    PP at(long off) const { PP q; q.hi = hi + off; q.lo = lo + off; return q; }    // planes of a whole arena: the tensor at float offset `off`
+};
 
 struct PlanCore {
     slnlp_tf_buffers buf{};
@@ -21,6 +69,11 @@ struct PlanCore {
     int last_B = 0;                         // batch of the last forward
     float last_p = 0.f;                     // dropout used by the last forward (0 in eval)
     int planes_B = -1;                      // batch size the activation planes' zero padding is valid for
+    // split-bf16 passes of the plane GEMM's gradient products: the process default AT CREATION (slnlp_set_backward_passes), fixed for the
+    // plan's life -- a captured graph, a recorded lockstep program and every host thread that steps this plan issue the same products
+    int wgrad_np = wgrad_passes(), dgrad_np = dgrad_passes();
+    int wgrad_prec(int precision) const { return precision == 3 ? wgrad_np : precision; }
+    int dgrad_prec(int precision) const { return precision == 3 ? dgrad_np : precision; }     // (dY's bf16 head only)
     // Lockstep (lockstep.hip): where this fit's per-step outputs go while it advances as one of K fits -- an epoch-long
     // log-prob buffer and a per-batch loss history, indexed through two device scalars the driver updates per step
     float* ls_logp = nullptr;               // [rows of the epoch, Vt]

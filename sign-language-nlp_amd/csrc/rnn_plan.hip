@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "linear_jobs.hpp"
 #include "plan_core.hpp"
 #include <cstring>
 
@@ -30,15 +31,9 @@ static int rnn_kslices(const slnlp_rnn_config& c) {
 }
 static bool rnn_kslice_wide() { static const bool w = [] { const char* e = getenv("SLNLP_RNN_KSLICE"); return e && strchr(e, 'w'); }(); return w; }
 
-struct RParam {
-    std::string name;
-    int64_t shape[2];
-    int ndim;
-    int64_t off, numel;
-};
 struct RnnW { long w_ih, w_hh, b_ih, b_hh; int in; };
 struct RLayout {
-    std::vector<RParam> ents;
+    std::vector<ParamEnt> ents;
     std::vector<RnnW> enc[2];   // [direction][layer]
     std::vector<RnnW> dec;
     long key_w, query_w, energy_w, bridge_w, bridge_b, pre_out, src_emb, trg_emb, gen_w, total;
@@ -50,7 +45,7 @@ static RLayout build_rlayout(const slnlp_rnn_config& c) {
     RLayout L;
     long cur = 0;
     auto add = [&](const std::string& n, long d0, long d1) -> long {
-        RParam e;
+        ParamEnt e;
         e.name = n; e.shape[0] = d0; e.shape[1] = d1; e.ndim = d1 > 0 ? 2 : 1;
         e.numel = d1 > 0 ? d0 * d1 : d0;
         e.off = cur;
@@ -110,28 +105,11 @@ static int check_rcfg(const slnlp_rnn_config* c) {
     return 0;
 }
 
-struct RBump {
-    char* base;
-    size_t cur = 0;
-    explicit RBump(void* b) : base((char*)b) {}
-    template <typename T>
-    T* take(size_t n) {
-        cur = (cur + 255) & ~(size_t)255;
-        T* p = (T*)(base + cur);
-        cur += n * sizeof(T);
-        return p;
-    }
-};
-
 struct EncDirA {   // per (layer, direction)
     float *xproj, *acts, *hprev, *cprev, *hn, *h, *c;
     float *dgx, *dgh, *dh, *dc, *carry, *dhx;   // dhx: partial products of the K-sliced recurrent dgrad
 };
-struct RPP {               // bf16 hi / lo planes of a GEMM operand (gemm_planes.hip)
-    unsigned short *hi = nullptr, *lo = nullptr;
-    PlaneOut out() const { PlaneOut o; o.hi = hi; o.lo = lo; return o; }
-};
-struct EncLayerA { EncDirA d[2]; float *out, *dout; RPP xinp; };    // out [M,2Hd]; dout = grad w.r.t. out; xinp = planes of the layer input
+struct EncLayerA { EncDirA d[2]; float *out, *dout; PP xinp; };    // out [M,2Hd]; dout = grad w.r.t. out; xinp = planes of the layer input
 struct DecLayerA {
     float *xproj, *hproj, *acts, *hprev, *cprev, *hn, *h, *c, *out;
     float *dgx, *dgh, *dh, *dc, *carry, *dout;
@@ -142,8 +120,8 @@ struct RWs {
         *demb_bos, *dwe_part, *logits, *dlogits, *logp, *row_nll, *opt_partials;
     int64_t* bos_ids;
     unsigned* sync;          // {barrier count, generation, error flag} of the persistent layer kernel
-    RPP wp;                  // planes of the encoder's RNN weights (arena prefix [0, key_w)), split once per forward
-    RPP dgxp[2], dghp[2], hprevp[2];   // per direction, reused by every layer's backward
+    PP wp;                  // planes of the encoder's RNN weights (arena prefix [0, key_w)), split once per forward
+    PP dgxp[2], dghp[2], hprevp[2];   // per direction, reused by every layer's backward
     char *planes_begin, *planes_end;   // activation planes: zero padding rows, re-zeroed when the batch size changes
     void *emb_scratch_src, *emb_scratch_tgt;
     std::vector<EncLayerA> enc;
@@ -153,7 +131,7 @@ struct RWs {
 
 static RWs rcarve(const slnlp_rnn_config& c, void* base) {
     RWs w;
-    RBump b(base);
+    Bump b(base);
     const size_t B = c.B, S = c.S, E = c.E, Hd = c.Hd, M = B * S, G = c.lstm ? 4 : 3, Vp = align_up(c.Vt, 4);
     w.emb = b.take<float>(M * E);
     w.demb = b.take<float>(M * E);
@@ -232,7 +210,7 @@ static RWs rcarve(const slnlp_rnn_config& c, void* base) {
         w.wp.lo = b.take<unsigned short>(wlen);
         b.cur = (b.cur + 255) & ~(size_t)255;
         w.planes_begin = b.base + b.cur;
-        auto pp = [&](size_t cols) { RPP q; q.hi = b.take<unsigned short>(Mp * cols); q.lo = b.take<unsigned short>(Mp * cols); return q; };
+        auto pp = [&](size_t cols) { PP q; q.hi = b.take<unsigned short>(Mp * cols); q.lo = b.take<unsigned short>(Mp * cols); return q; };
         for (int l = 0; l < c.N; ++l) w.enc[l].xinp = pp(l == 0 ? E : 2 * Hd);
         for (int d = 0; d < 2; ++d) {
             w.dgxp[d] = pp(GH);
@@ -259,7 +237,6 @@ struct slnlp_rnn_plan : PlanCore {
     RWs w;
     const int64_t *last_X = nullptr, *last_y = nullptr, *last_len = nullptr;
     bool use_planes = false;  // E, Hd multiples of 64: the M = S*B GEMMs run on pre-split bf16 planes (gemm_planes.hip)
-    int wgrad_p = 2, dgrad_p = 2;   // split-bf16 passes of the plane gradient products: the process default AT CREATION, fixed for the plan's life
     bool persistent = false;  // opt-in: all timesteps of an encoder layer in one launch (not yet faster; needs one fit per GPU)
     // backward through time: the cell kernel + K-sliced grouped GEMM pair per timestep (default), or ONE launch per timestep
     // (gemm.hip rnn_step_bwd_kernel; slnlp_rnn_set_fused_backward(plan, 1), env SLNLP_RNN_FUSED_BWD=1).  Round 4 built the
@@ -293,38 +270,10 @@ struct slnlp_rnn_plan : PlanCore {
     float* P(long off) const { return buf.params + off; }
     float* Gd(long off) const { return buf.grads + off; }
 
-    // y[M,N] = x[M,K](lda) W[N,K](ldb)^T + bias, act (0 none / 2 tanh), + resid
-    slnlp_gemm_args lin_args(const float* x, long lda, int M, int K, const float* W, long ldb, int N, const float* bias,
-                             float* y, long ldy, int act, const float* resid) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.lda = lda; a.a_kmajor = 1;
-        a.B = W; a.ldb = ldb; a.b_kmajor = 1;
-        a.C = y; a.ldc = ldy; a.M = M; a.N = N; a.K = K;
-        a.bias = bias; a.relu = act; a.resid = resid; a.ldr = ldy;
-        a.precision = cfg.precision;
-        return a;
-    }
-    int lin(const float* x, long lda, int M, int K, const float* W, long ldb, int N, const float* bias, float* y, long ldy,
-            int act, const float* resid, hipStream_t st) const {
-        return gemm(lin_args(x, lda, M, K, W, ldb, N, bias, y, ldy, act, resid), st);
-    }
-    // dx[M,Kin](ldx) = dy[M,Nout](ldy) W[Nout,Kin](ldw)  (+resid, same ld as dx)
-    slnlp_gemm_args dgr_args(const float* dy, long ldy, int M, int Nout, const float* W, long ldw, int Kin, float* dx,
-                             long ldx, const float* resid) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = dy; a.lda = ldy; a.a_kmajor = 1;
-        a.B = W; a.ldb = ldw; a.b_kmajor = 0;
-        a.C = dx; a.ldc = ldx; a.M = M; a.N = Kin; a.K = Nout;
-        a.resid = resid; a.ldr = ldx;
-        a.precision = cfg.precision;
-        return a;
-    }
-    int dgr(const float* dy, long ldy, int M, int Nout, const float* W, long ldw, int Kin, float* dx, long ldx,
-            const float* resid, hipStream_t st) const {
-        return gemm(dgr_args(dy, ldy, M, Nout, W, ldw, Kin, dx, ldx, resid), st);
-    }
+    // the three products of a Linear on fp32 operands (linear_jobs.hpp), one launch each
+    int lin(const Mat& x, const Mat& W, int M, int N, int K, float* y, const Epi& e, hipStream_t st) const { return gemm(linear_job(x, W, M, N, K, y, e, cfg.precision), st); }
+    int dgr(const Mat& dy, const Mat& W, int M, int Nout, int Kin, float* dx, const float* resid, hipStream_t st) const { return gemm(dgrad_job(dy, W, M, Nout, Kin, dx, Epi().plus(resid), cfg.precision), st); }
+    int wgr(const Mat& dy, const Mat& x, int T, int Nout, int Kin, float* dW, float* db, hipStream_t st, long ldw = 0) const { return gemm(wgrad_job(dy, x, T, Nout, Kin, dW, db, cfg.precision, ldw), st); }
     // zero padding of the activation planes is per batch size: re-zero when it changes (outside any capture)
     int prepare_planes(int B, hipStream_t st) override {
         if (!use_planes || B == planes_B) return 0;
@@ -335,53 +284,11 @@ struct slnlp_rnn_plan : PlanCore {
         planes_B = B;
         return 0;
     }
-    // plane GEMM argument builders (weights: planes of the arena at offset woff)
-    slnlp_gemm_args lin_p(const RPP& x, int M, int K, long woff, int N, const float* bias, float* y) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A_hi = x.hi; a.A_lo = x.lo; a.lda_p = K; a.a_kmajor = 1;
-        a.B_hi = w.wp.hi + woff; a.B_lo = w.wp.lo + woff; a.ldb_p = K; a.b_kmajor = 1;
-        a.C = y; a.ldc = N; a.M = M; a.N = N; a.K = K; a.bias = bias;
-        a.precision = cfg.precision;
-        return a;
-    }
-    slnlp_gemm_args dgr_p(const RPP& dy, int M, int Nout, long woff, int Kin, float* dx, const float* resid) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A_hi = dy.hi; a.A_lo = dy.lo; a.lda_p = Nout; a.a_kmajor = 1;
-        a.B_hi = w.wp.hi + woff; a.B_lo = w.wp.lo + woff; a.ldb_p = Kin; a.b_kmajor = 0;
-        a.C = dx; a.ldc = Kin; a.M = M; a.N = Kin; a.K = Nout;
-        a.resid = resid; a.ldr = Kin;
-        a.precision = cfg.precision == 3 ? dgrad_p : cfg.precision;     // (slnlp_set_backward_passes: dY's bf16 head only)
-        return a;
-    }
-    slnlp_gemm_args wgr_p(const RPP& dy, int T, int Nout, const RPP& x, int Kin, float* dW, float* db) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A_hi = dy.hi; a.A_lo = dy.lo; a.lda_p = Nout; a.a_kmajor = 0;
-        a.B_hi = x.hi; a.B_lo = x.lo; a.ldb_p = Kin; a.b_kmajor = 0;
-        a.C = dW; a.ldc = Kin; a.M = Nout; a.N = Kin; a.K = T;
-        a.rowsum_a = db;
-        a.precision = cfg.precision == 3 ? wgrad_p : cfg.precision;
-        return a;
-    }
     // the recurrent dgrad dh(t-1) = dgh W_hh + carry contracts over the G*Hd gate columns, cut into K-slices (each its own GEMM job or
     // one GEMM of a batched job; partial products summed by the next cell kernel).  Rounds 1-4: one slice per gate on 64 x 16 tiles --
     // 256 workgroups of 160 KB (64 rows x 512 k of dgh, re-read by each of the 32 column tiles, + 512 k x 16 columns of W_hh).  Round 5:
     // slices of 128 on 64 x 64 tiles -- the same 256 workgroups, 64 KB each (32 + 32): a launch lasts as long as one workgroup loads.
     int kslices() const { return rnn_kslices(cfg); }
-    // dW[Nout,Kin](ldw) = dy[T,Nout](ldy)^T x[T,Kin](ldx);  db = colsum(dy)
-    int wgr(const float* dy, long ldy, int T, int Nout, const float* x, long ldx, int Kin, float* dW, long ldw, float* db,
-            hipStream_t st) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = dy; a.lda = ldy; a.a_kmajor = 0;
-        a.B = x; a.ldb = ldx; a.b_kmajor = 0;
-        a.C = dW; a.ldc = ldw; a.M = Nout; a.N = Kin; a.K = T;
-        a.rowsum_a = db;
-        a.precision = cfg.precision;
-        return gemm(a, st);
-    }
 };
 
 
@@ -393,14 +300,7 @@ int slnlp_rnn_num_params(const slnlp_rnn_config* cfg) {
 }
 int slnlp_rnn_param_info(const slnlp_rnn_config* cfg, int i, char* name, int64_t shape[2], int* ndim, int64_t* offset) {
     SLNLP_TRY(check_rcfg(cfg));
-    RLayout L = build_rlayout(*cfg);
-    SLNLP_CHECK_ARG(i >= 0 && i < (int)L.ents.size(), "rnn_param_info: index %d out of range", i);
-    const RParam& e = L.ents[i];
-    if (name) { strncpy(name, e.name.c_str(), 127); name[127] = 0; }
-    if (shape) { shape[0] = e.shape[0]; shape[1] = e.shape[1]; }
-    if (ndim) *ndim = e.ndim;
-    if (offset) *offset = e.off;
-    return 0;
+    return param_info(build_rlayout(*cfg).ents, i, "rnn_param_info", name, shape, ndim, offset);
 }
 int64_t slnlp_rnn_arena_floats(const slnlp_rnn_config* cfg) {
     if (check_rcfg(cfg)) return -1;
@@ -425,8 +325,6 @@ int slnlp_rnn_create(const slnlp_rnn_config* cfg, const slnlp_tf_buffers* buf, s
                     "rnn_create: arenas / workspace must be 256-byte aligned");
     slnlp_rnn_plan* p = new slnlp_rnn_plan();
     p->cfg = *cfg;
-    p->wgrad_p = wgrad_passes();
-    p->dgrad_p = dgrad_passes();
     p->buf = *buf;
     p->L = build_rlayout(*cfg);
     p->w = rcarve(*cfg, buf->workspace);
@@ -478,13 +376,13 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
         const int in = L.enc[0][l].in;
         if (up) {   // x W_ih^T + b_ih of both directions over all timesteps: one grouped plane-GEMM launch
             if (l > 0) SLNLP_TRY(split_planes(x_in, in, M, in, a.xinp.hi, a.xinp.lo, in, st));
-            const slnlp_gemm_args xj[2] = {pl->lin_p(a.xinp, M, in, L.enc[0][l].w_ih, GH, pl->P(L.enc[0][l].b_ih), a.d[0].xproj),
-                                           pl->lin_p(a.xinp, M, in, L.enc[1][l].w_ih, GH, pl->P(L.enc[1][l].b_ih), a.d[1].xproj)};
+            const slnlp_gemm_args xj[2] = {linear_job(planes(a.xinp, in), planes(w.wp.at(L.enc[0][l].w_ih), in), M, GH, in, a.d[0].xproj, Epi().biased(pl->P(L.enc[0][l].b_ih)), c.precision),
+                                           linear_job(planes(a.xinp, in), planes(w.wp.at(L.enc[1][l].w_ih), in), M, GH, in, a.d[1].xproj, Epi().biased(pl->P(L.enc[1][l].b_ih)), c.precision)};
             SLNLP_TRY(gemm_planes_group(xj, nullptr, 2, nullptr, 0, st));
         }
         for (int d = 0; d < 2; ++d) {
             const RnnW& q = L.enc[d][l];
-            if (!up) SLNLP_TRY(pl->lin(x_in, in, M, in, pl->P(q.w_ih), in, GH, pl->P(q.b_ih), a.d[d].xproj, GH, 0, nullptr, st));
+            if (!up) SLNLP_TRY(pl->lin(f32(x_in, in), f32(pl->P(q.w_ih), in), M, GH, in, a.d[d].xproj, Epi().biased(pl->P(q.b_ih)), st));
             // the state chain lives in the per-timestep `hprev` slots: slot of the first processed timestep = h_0 = 0
             const int t0 = d == 0 ? 0 : S - 1;
             SLNLP_TRY(fill_zero(a.d[d].hprev + (long)t0 * B * Hd, (size_t)B * Hd * sizeof(float), st));
@@ -533,11 +431,10 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
     }
     const float* enc_out = w.enc[N - 1].out;
     // Decoder.init_hidden :268-280: tanh(bridge(enc_final)); LSTM uses (h, h) as (h0, c0)
-    SLNLP_TRY(pl->lin(w.enc_final, 2 * Hd, N * B, 2 * Hd, pl->P(L.bridge_w), 2 * Hd, Hd, pl->P(L.bridge_b), w.h0, Hd, 2,
-                      nullptr, st));
-    SLNLP_TRY(pl->lin(enc_out, 2 * Hd, M, 2 * Hd, pl->P(L.key_w), 2 * Hd, Hd, nullptr, w.pk, Hd, 0, nullptr, st));   // :246
+    SLNLP_TRY(pl->lin(f32(w.enc_final, 2 * Hd), f32(pl->P(L.bridge_w), 2 * Hd), N * B, Hd, 2 * Hd, w.h0, Epi().biased(pl->P(L.bridge_b), 2), st));
+    SLNLP_TRY(pl->lin(f32(enc_out, 2 * Hd), f32(pl->P(L.key_w), 2 * Hd), M, Hd, 2 * Hd, w.pk, Epi(), st));   // :246
     const float* h_top = w.h0 + (long)(N - 1) * B * Hd;                                                              // get_query
-    SLNLP_TRY(pl->lin(h_top, Hd, B, Hd, pl->P(L.query_w), Hd, Hd, nullptr, w.q, Hd, 0, nullptr, st));
+    SLNLP_TRY(pl->lin(f32(h_top, Hd), f32(pl->P(L.query_w), Hd), B, Hd, Hd, w.q, Epi(), st));
     SLNLP_TRY(bahdanau_fwd(w.q, w.pk, enc_out, pl->P(L.energy_w), X, S, c.pad_src, B, S, Hd, w.alphas, w.ctx, st));
     // prev_embed = trg_embed(<bos>)  :254 with max_len = 1
     SLNLP_TRY(embed_fwd(w.bos_ids, 1, B, 1, E, c.Vt, pl->P(L.trg_emb), nullptr, w.emb_bos, 1.f, 0.f, 0, rng, -1, st));
@@ -546,13 +443,13 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
         const RnnW& q = L.dec[l];
         const DecLayerA& a = w.dec[l];
         if (l == 0) {   // rnn_input = cat[prev_embed, context]  -> two K-slices of W_ih, no concat buffer
-            SLNLP_TRY(pl->lin(w.emb_bos, E, B, E, pl->P(q.w_ih), q.in, GH, pl->P(q.b_ih), a.xproj, GH, 0, nullptr, st));
-            SLNLP_TRY(pl->lin(w.ctx, 2 * Hd, B, 2 * Hd, pl->P(q.w_ih) + E, q.in, GH, nullptr, a.xproj, GH, 0, a.xproj, st));
+            SLNLP_TRY(pl->lin(f32(w.emb_bos, E), f32(pl->P(q.w_ih), q.in), B, GH, E, a.xproj, Epi().biased(pl->P(q.b_ih)), st));
+            SLNLP_TRY(pl->lin(f32(w.ctx, 2 * Hd), f32(pl->P(q.w_ih) + E, q.in), B, GH, 2 * Hd, a.xproj, Epi().plus(a.xproj), st));
         } else {
-            SLNLP_TRY(pl->lin(x_prev, Hd, B, Hd, pl->P(q.w_ih), Hd, GH, pl->P(q.b_ih), a.xproj, GH, 0, nullptr, st));
+            SLNLP_TRY(pl->lin(f32(x_prev, Hd), f32(pl->P(q.w_ih), Hd), B, GH, Hd, a.xproj, Epi().biased(pl->P(q.b_ih)), st));
         }
         const float* h0l = w.h0 + (long)l * B * Hd;
-        SLNLP_TRY(pl->lin(h0l, Hd, B, Hd, pl->P(q.w_hh), Hd, GH, pl->P(q.b_hh), a.hproj, GH, 0, nullptr, st));
+        SLNLP_TRY(pl->lin(f32(h0l, Hd), f32(pl->P(q.w_hh), Hd), B, GH, Hd, a.hproj, Epi().biased(pl->P(q.b_hh)), st));
         SLNLP_TRY(add_rows(h0l, Hd, a.h, Hd, B, Hd, 0, st));
         if (lstm) SLNLP_TRY(add_rows(h0l, Hd, a.c, Hd, B, Hd, 0, st));
         slnlp_rnn_cell_dir k;
@@ -563,7 +460,7 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
         x_prev = a.out;
     }
     // generator on the decoder state (bkp.py:40-46,69-76) + criterion
-    SLNLP_TRY(pl->lin(x_prev, Hd, B, Hd, pl->P(L.gen_w), Hd, c.Vt, nullptr, w.logits, Vp, 0, nullptr, st));
+    SLNLP_TRY(pl->lin(f32(x_prev, Hd), f32(pl->P(L.gen_w), Hd), B, c.Vt, Hd, w.logits, Epi().stride(Vp), st));
     SLNLP_TRY(lsm_nll(w.logits, Vp, y, B, c.Vt, c.pad_tgt, w.logp, pl->buf.scalars, train ? w.dlogits : nullptr, Vp,
                       w.row_nll, st, nullptr, logp_out ? nullptr : pl->ls_logp, logp_out ? nullptr : pl->ls_dyn,
                       logp_out ? nullptr : pl->ls_loss, (!logp_out && pl->ls_dyn) ? pl->ls_dyn + 1 : nullptr, pl->opts.loss()));
@@ -626,8 +523,8 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
     SLNLP_TRY(fill_zero(w.zero_bwd, (size_t)4 * N * c.B * Hd * sizeof(float), st));   // dc / dh seeds
     // generator (no bias)
     const float* dec_out = w.dec[N - 1].out;
-    SLNLP_TRY(pl->wgr(w.dlogits, Vp, B, c.Vt, dec_out, Hd, Hd, pl->Gd(L.gen_w), Hd, nullptr, st));
-    SLNLP_TRY(pl->dgr(w.dlogits, Vp, B, c.Vt, pl->P(L.gen_w), Hd, Hd, w.dec[N - 1].dout, Hd, nullptr, st));
+    SLNLP_TRY(pl->wgr(f32(w.dlogits, Vp), f32(dec_out, Hd), B, c.Vt, Hd, pl->Gd(L.gen_w), nullptr, st));
+    SLNLP_TRY(pl->dgr(f32(w.dlogits, Vp), f32(pl->P(L.gen_w), Hd), B, c.Vt, Hd, w.dec[N - 1].dout, nullptr, st));
     // decoder RNN, one step, top layer first
     for (int l = N - 1; l >= 0; --l) {
         const RnnW& q = L.dec[l];
@@ -638,17 +535,17 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
         k.t = 0; k.out_row0 = 0; k.out_col0 = 0;
         SLNLP_TRY(rnn_cell_bwd(lstm, &k, 1, B, Hd, nullptr, Hd, l == N - 1 ? 0.f : p, RSITE_DEC0 + l, rng, st));
         float* dh0l = w.dh0 + (long)l * B * Hd;
-        SLNLP_TRY(pl->dgr(a.dgh, GH, B, GH, pl->P(q.w_hh), Hd, Hd, dh0l, Hd, a.carry, st));        // d h0[l]
+        SLNLP_TRY(pl->dgr(f32(a.dgh, GH), f32(pl->P(q.w_hh), Hd), B, GH, Hd, dh0l, a.carry, st));        // d h0[l]
         if (lstm) SLNLP_TRY(add_rows(a.dc, Hd, dh0l, Hd, B, Hd, 1, st));                             // c0 = h0 too
-        SLNLP_TRY(pl->wgr(a.dgh, GH, B, GH, a.hprev, Hd, Hd, pl->Gd(q.w_hh), Hd, pl->Gd(q.b_hh), st));
+        SLNLP_TRY(pl->wgr(f32(a.dgh, GH), f32(a.hprev, Hd), B, GH, Hd, pl->Gd(q.w_hh), pl->Gd(q.b_hh), st));
         if (l > 0) {
-            SLNLP_TRY(pl->wgr(a.dgx, GH, B, GH, w.dec[l - 1].out, Hd, Hd, pl->Gd(q.w_ih), Hd, pl->Gd(q.b_ih), st));
-            SLNLP_TRY(pl->dgr(a.dgx, GH, B, GH, pl->P(q.w_ih), Hd, Hd, w.dec[l - 1].dout, Hd, nullptr, st));
+            SLNLP_TRY(pl->wgr(f32(a.dgx, GH), f32(w.dec[l - 1].out, Hd), B, GH, Hd, pl->Gd(q.w_ih), pl->Gd(q.b_ih), st));
+            SLNLP_TRY(pl->dgr(f32(a.dgx, GH), f32(pl->P(q.w_ih), Hd), B, GH, Hd, w.dec[l - 1].dout, nullptr, st));
         } else {
-            SLNLP_TRY(pl->wgr(a.dgx, GH, B, GH, w.emb_bos, E, E, pl->Gd(q.w_ih), q.in, pl->Gd(q.b_ih), st));
-            SLNLP_TRY(pl->wgr(a.dgx, GH, B, GH, w.ctx, 2 * Hd, 2 * Hd, pl->Gd(q.w_ih) + E, q.in, nullptr, st));
-            SLNLP_TRY(pl->dgr(a.dgx, GH, B, GH, pl->P(q.w_ih) + E, q.in, 2 * Hd, w.dctx, 2 * Hd, nullptr, st));
-            SLNLP_TRY(pl->dgr(a.dgx, GH, B, GH, pl->P(q.w_ih), q.in, E, w.demb_bos, E, nullptr, st));
+            SLNLP_TRY(pl->wgr(f32(a.dgx, GH), f32(w.emb_bos, E), B, GH, E, pl->Gd(q.w_ih), pl->Gd(q.b_ih), st, q.in));
+            SLNLP_TRY(pl->wgr(f32(a.dgx, GH), f32(w.ctx, 2 * Hd), B, GH, 2 * Hd, pl->Gd(q.w_ih) + E, nullptr, st, q.in));
+            SLNLP_TRY(pl->dgr(f32(a.dgx, GH), f32(pl->P(q.w_ih) + E, q.in), B, GH, 2 * Hd, w.dctx, nullptr, st));
+            SLNLP_TRY(pl->dgr(f32(a.dgx, GH), f32(pl->P(q.w_ih), q.in), B, GH, E, w.demb_bos, nullptr, st));
         }
     }
     // trg_embed: only the <bos> row sees gradient; padding_idx row gets none (bkp.py:377-379)
@@ -660,14 +557,14 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
                            w.dwe_part, pl->Gd(L.energy_w), st));
     const float* h_top = w.h0 + (long)(N - 1) * B * Hd;
     float* dh_top = w.dh0 + (long)(N - 1) * B * Hd;
-    SLNLP_TRY(pl->wgr(w.dq, Hd, B, Hd, h_top, Hd, Hd, pl->Gd(L.query_w), Hd, nullptr, st));
-    SLNLP_TRY(pl->dgr(w.dq, Hd, B, Hd, pl->P(L.query_w), Hd, Hd, dh_top, Hd, dh_top, st));
-    SLNLP_TRY(pl->wgr(w.dpk, Hd, M, Hd, enc_out, 2 * Hd, 2 * Hd, pl->Gd(L.key_w), 2 * Hd, nullptr, st));
-    SLNLP_TRY(pl->dgr(w.dpk, Hd, M, Hd, pl->P(L.key_w), 2 * Hd, 2 * Hd, denc_out, 2 * Hd, denc_out, st));
+    SLNLP_TRY(pl->wgr(f32(w.dq, Hd), f32(h_top, Hd), B, Hd, Hd, pl->Gd(L.query_w), nullptr, st));
+    SLNLP_TRY(pl->dgr(f32(w.dq, Hd), f32(pl->P(L.query_w), Hd), B, Hd, Hd, dh_top, dh_top, st));
+    SLNLP_TRY(pl->wgr(f32(w.dpk, Hd), f32(enc_out, 2 * Hd), M, Hd, 2 * Hd, pl->Gd(L.key_w), nullptr, st));
+    SLNLP_TRY(pl->dgr(f32(w.dpk, Hd), f32(pl->P(L.key_w), 2 * Hd), M, Hd, 2 * Hd, denc_out, denc_out, st));
     // bridge: h0 = tanh(z)
     SLNLP_TRY(tanh_bwd(w.dh0, w.h0, w.dz, (int64_t)N * B * Hd, st));
-    SLNLP_TRY(pl->wgr(w.dz, Hd, N * B, Hd, w.enc_final, 2 * Hd, 2 * Hd, pl->Gd(L.bridge_w), 2 * Hd, pl->Gd(L.bridge_b), st));
-    SLNLP_TRY(pl->dgr(w.dz, Hd, N * B, Hd, pl->P(L.bridge_w), 2 * Hd, 2 * Hd, w.denc_final, 2 * Hd, nullptr, st));
+    SLNLP_TRY(pl->wgr(f32(w.dz, Hd), f32(w.enc_final, 2 * Hd), N * B, Hd, 2 * Hd, pl->Gd(L.bridge_w), pl->Gd(L.bridge_b), st));
+    SLNLP_TRY(pl->dgr(f32(w.dz, Hd), f32(pl->P(L.bridge_w), 2 * Hd), N * B, Hd, 2 * Hd, w.denc_final, nullptr, st));
 
     // encoder, backward through time, top layer first
     for (int l = N - 1; l >= 0; --l) {
@@ -724,16 +621,15 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
                 const RnnW& q = L.enc[d][l];
                 if (nsl <= 4 && !rnn_kslice_wide()) {
                     for (int sl = 0; sl < nsl; ++sl)
-                        rec[nj++] = pl->dgr_args(dirs[d].dgh + sl * Ks, GH, B, Ks, pl->P(q.w_hh) + (long)sl * Ks * Hd, Hd, Hd,
-                                                 sl == 0 ? a.d[d].dh : a.d[d].dhx + (long)(sl - 1) * B * Hd, Hd,
-                                                 sl == 0 ? a.d[d].carry : nullptr);
+                        rec[nj++] = dgrad_job(f32(dirs[d].dgh + sl * Ks, GH), f32(pl->P(q.w_hh) + (long)sl * Ks * Hd, Hd), B, Ks, Hd,
+                                              sl == 0 ? a.d[d].dh : a.d[d].dhx + (long)(sl - 1) * B * Hd, Epi().plus(sl == 0 ? a.d[d].carry : nullptr), c.precision);
                     continue;
                 }
                 // slice 0 (+ carry) -> dh; slices 1 .. nsl-1 as ONE batched job -> dhx[0 .. nsl-2]; 64-column tiles
-                rec[nj] = pl->dgr_args(dirs[d].dgh, GH, B, Ks, pl->P(q.w_hh), Hd, Hd, a.d[d].dh, Hd, a.d[d].carry);
+                rec[nj] = dgrad_job(f32(dirs[d].dgh, GH), f32(pl->P(q.w_hh), Hd), B, Ks, Hd, a.d[d].dh, Epi().plus(a.d[d].carry), c.precision);
                 if (rnn_kslice_wide()) wide |= 1u << nj;
                 ++nj;
-                rec[nj] = pl->dgr_args(dirs[d].dgh + Ks, GH, B, Ks, pl->P(q.w_hh) + (long)Ks * Hd, Hd, Hd, a.d[d].dhx, Hd, nullptr);
+                rec[nj] = dgrad_job(f32(dirs[d].dgh + Ks, GH), f32(pl->P(q.w_hh) + (long)Ks * Hd, Hd), B, Ks, Hd, a.d[d].dhx, Epi(), c.precision);
                 rec[nj].batch = nsl - 1;
                 rec[nj].batch_stride_a = Ks; rec[nj].batch_stride_b = (long)Ks * Hd; rec[nj].batch_stride_c = (long)B * Hd;
                 if (rnn_kslice_wide()) wide |= 1u << nj;
@@ -752,15 +648,15 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
                 if (!lstm) SLNLP_TRY(split_planes(e.dgh, GH, M, GH, w.dghp[d].hi, w.dghp[d].lo, GH, st));
                 SLNLP_TRY(split_planes(e.hprev, Hd, M, Hd, w.hprevp[d].hi, w.hprevp[d].lo, Hd, st));
                 const slnlp_gemm_args jobs[3] = {
-                    pl->wgr_p(w.dgxp[d], M, GH, a.xinp, in, pl->Gd(q.w_ih), pl->Gd(q.b_ih)),
-                    pl->wgr_p(w.dghp[d], M, GH, w.hprevp[d], Hd, pl->Gd(q.w_hh), pl->Gd(q.b_hh)),
-                    pl->dgr_p(w.dgxp[d], M, GH, q.w_ih, in, dx, d == 0 ? nullptr : dx)};
+                    wgrad_job(planes(w.dgxp[d], GH), planes(a.xinp, in), M, GH, in, pl->Gd(q.w_ih), pl->Gd(q.b_ih), pl->wgrad_prec(c.precision)),
+                    wgrad_job(planes(w.dghp[d], GH), planes(w.hprevp[d], Hd), M, GH, Hd, pl->Gd(q.w_hh), pl->Gd(q.b_hh), pl->wgrad_prec(c.precision)),
+                    dgrad_job(planes(w.dgxp[d], GH), planes(w.wp.at(q.w_ih), in), M, GH, in, dx, Epi().plus(d == 0 ? nullptr : dx), pl->dgrad_prec(c.precision))};
                 SLNLP_TRY(gemm_planes_group(jobs, nullptr, 3, nullptr, 0, st));
                 continue;
             }
-            SLNLP_TRY(pl->wgr(e.dgx, GH, M, GH, x_in, in, in, pl->Gd(q.w_ih), in, pl->Gd(q.b_ih), st));
-            SLNLP_TRY(pl->wgr(e.dgh, GH, M, GH, e.hprev, Hd, Hd, pl->Gd(q.w_hh), Hd, pl->Gd(q.b_hh), st));
-            SLNLP_TRY(pl->dgr(e.dgx, GH, M, GH, pl->P(q.w_ih), in, in, dx, in, d == 0 ? nullptr : dx, st));
+            SLNLP_TRY(pl->wgr(f32(e.dgx, GH), f32(x_in, in), M, GH, in, pl->Gd(q.w_ih), pl->Gd(q.b_ih), st));
+            SLNLP_TRY(pl->wgr(f32(e.dgh, GH), f32(e.hprev, Hd), M, GH, Hd, pl->Gd(q.w_hh), pl->Gd(q.b_hh), st));
+            SLNLP_TRY(pl->dgr(f32(e.dgx, GH), f32(pl->P(q.w_ih), in), M, GH, in, dx, d == 0 ? nullptr : dx, st));
         }
     }
     // src_embed: padding_idx row gets no gradient (bkp.py:374-376)

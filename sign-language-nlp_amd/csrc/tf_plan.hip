@@ -29,20 +29,7 @@ int slnlp_tf_num_params(const slnlp_tf_config* cfg) {
 
 int slnlp_tf_param_info(const slnlp_tf_config* cfg, int i, char* name, int64_t shape[2], int* ndim, int64_t* offset) {
     SLNLP_TRY(check_cfg(cfg));
-    Layout L = build_layout(*cfg);
-    SLNLP_CHECK_ARG(i >= 0 && i < (int)L.ents.size(), "tf_param_info: index %d out of range", i);
-    const ParamEnt& e = L.ents[i];
-    if (name) {
-        strncpy(name, e.name.c_str(), 127);
-        name[127] = 0;
-    }
-    if (shape) {
-        shape[0] = e.shape[0];
-        shape[1] = e.shape[1];
-    }
-    if (ndim) *ndim = e.ndim;
-    if (offset) *offset = e.off;
-    return 0;
+    return param_info(build_layout(*cfg).ents, i, "tf_param_info", name, shape, ndim, offset);
 }
 
 int64_t slnlp_tf_arena_floats(const slnlp_tf_config* cfg) {
@@ -77,8 +64,6 @@ int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, sln
     p->max_B = cfg->B; p->S = cfg->S; p->Vt = cfg->Vt; p->dropout = cfg->dropout;
     bool ok = attn_init() == 0 && gemm_planes_init() == 0;
     p->use_planes = (cfg->E % 64 == 0) && (cfg->F % 64 == 0);
-    p->wgrad_np = wgrad_passes();
-    p->dgrad_np = dgrad_passes();
     {   // SLNLP_DEC_ROWS=0: the decoder's products on gemm.hip's fp32-operand kernel again (A / B measurements; another arithmetic:
         // that kernel splits its operands itself, with a truncated head)
         const char* e = getenv("SLNLP_DEC_ROWS");
@@ -160,32 +145,23 @@ int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, sln
 // Decoder layer l up to its cross-attention query: self-attention over ONE key (softmax == 1 -> out_proj(v_proj(t));
 // the q/k rows of in_proj are dead; in train mode the weight-1 "attention" is still dropped per (row, head) -- fused into
 // the V projection), residual + norm1, then q = in_proj_q(t1) (transformer.py:82-87).
-int slnlp_tf_plan::dec_self_block(int l, const float* t, const PP* tp, int B, float p, hipStream_t st) const {
-    const slnlp_tf_plan* pl = this;
+int slnlp_tf_plan::dec_self_block(int l, const Mat& t, int B, float p, hipStream_t st) const {
     const int E = cfg.E, dh = E / cfg.H;
     const DecP& q = L.dec[l];
     const DecA& a = w.dec[l];
-    if (use_rows) {        // B-row products on planes (gemm_rows.hip): every producer also emits its output as the next product's operand
-        SLNLP_TRY(pl->linear_r(*tp, B, E, q.sin_w + 2L * E * E, E, pl->P(q.sin_b) + 2 * E, a.v, E, 0, p, pl->dec_site(l, 0), nullptr, &a.vp, st, dh));
-        SLNLP_TRY(pl->linear_r(a.vp, B, E, q.sout_w, E, pl->P(q.sout_b), a.y1, E, 0, p, pl->dec_site(l, 1), t, nullptr, st));
-        SLNLP_TRY(layernorm_fwd(a.y1, pl->P(q.n1_w), pl->P(q.n1_b), B, E, 1e-5f, a.t1, a.st1, st, a.t1p.out()));
-        SLNLP_TRY(pl->linear_r(a.t1p, B, E, q.cin_w, E, pl->P(q.cin_b), a.q, E, 0, 0.f, 0, nullptr, nullptr, st));
-        return 0;
-    }
-    SLNLP_TRY(pl->linear(t, B, E, pl->P(q.sin_w) + 2L * E * E, E, pl->P(q.sin_b) + 2 * E, a.v, E, 0, p, pl->dec_site(l, 0), nullptr, st, dh));
-    SLNLP_TRY(pl->linear(a.v, B, E, pl->P(q.sout_w), E, pl->P(q.sout_b), a.y1, E, 0, p, pl->dec_site(l, 1), t, st));
-    SLNLP_TRY(layernorm_fwd(a.y1, pl->P(q.n1_w), pl->P(q.n1_b), B, E, 1e-5f, a.t1, a.st1, st));
-    SLNLP_TRY(pl->linear(a.t1, B, E, pl->P(q.cin_w), E, pl->P(q.cin_b), a.q, E, 0, 0.f, 0, nullptr, st));
-    return 0;
+    // (B-row products on planes, gemm_rows.hip: every producer also emits its output as the next product's operand)
+    SLNLP_TRY(linear(t, q.sin_w + 2L * E * E, q.sin_b + 2 * E, B, E, E, a.v, Epi().dropped(p, dec_site(l, 0), dh).also(a.vp), st));
+    SLNLP_TRY(linear(rview(a.v, a.vp, E), q.sout_w, q.sout_b, B, E, E, a.y1, Epi().dropped(p, dec_site(l, 1)).plus(t.f), st));
+    SLNLP_TRY(layernorm_fwd(a.y1, P(q.n1_w), P(q.n1_b), B, E, 1e-5f, a.t1, a.st1, st, rout(a.t1p)));
+    return linear(rview(a.t1, a.t1p, E), q.cin_w, q.cin_b, B, E, E, a.q, Epi(), st);
 }
 
 int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int train, float* logp_out, hipStream_t st) {
-    slnlp_tf_plan* pl = this;
-    const slnlp_tf_config& c = pl->cfg;
+    const slnlp_tf_config& c = cfg;
     const int E = c.E, F = c.F, H = c.H, S = c.S, dh = E / H, M = S * B, Vp = (int)align_up(c.Vt, 4);
     const float p = train ? c.dropout : 0.f;
-    const unsigned long long* rng = pl->buf.rng;
-    pl->last_B = B; pl->last_p = p; pl->last_X = X; pl->last_y = y;
+    const unsigned long long* rng = buf.rng;
+    last_B = B; last_p = p; last_X = X; last_y = y;
 
     // The target side up to the first cross-attention (embedding, layer 0's single-key self-attention block and its
     // query projection: five B-row launches) depends on nothing the encoder computes; everything runs on the caller's
@@ -196,88 +172,57 @@ int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int t
         SLNLP_TRY(ensure_wplanes(st));
         SLNLP_TRY(ensure_wq(st));
     }
-    SLNLP_TRY(embed_fwd(y, 1, B, 1, E, c.Vt, pl->P(L.tgt_emb), pl->buf.pe, w.t0, sqrtf((float)E), p, SITE_TGT_EMB, rng, c.pad_tgt, st,
-                        use_rows ? w.t0p.out() : PlaneOut{}));
-    SLNLP_TRY(dec_self_block(0, w.t0, &w.t0p, B, p, st));
-    SLNLP_TRY(embed_fwd(X, S, B, S, E, c.Vs, pl->P(L.src_emb), pl->buf.pe, w.x0, sqrtf((float)E), p, SITE_SRC_EMB, rng, -1, st,
-                        up ? w.x0p.out() : PlaneOut{}, w.emb_keep));
+    SLNLP_TRY(embed_fwd(y, 1, B, 1, E, c.Vt, P(L.tgt_emb), buf.pe, w.t0, sqrtf((float)E), p, SITE_TGT_EMB, rng, c.pad_tgt, st, rout(w.t0p)));
+    SLNLP_TRY(dec_self_block(0, rview(w.t0, w.t0p, E), B, p, st));
+    SLNLP_TRY(embed_fwd(X, S, B, S, E, c.Vs, P(L.src_emb), buf.pe, w.x0, sqrtf((float)E), p, SITE_SRC_EMB, rng, -1, st, pout(w.x0p), w.emb_keep));
 
-    const float* x = w.x0;
-    const PP* xp = &w.x0p;
+    Mat x = view(w.x0, w.x0p, E);
     for (int l = 0; l < c.N; ++l) {
         const EncP& q = L.enc[l];
         const EncA& a = w.enc[l];
-        if (up) {
-            SLNLP_TRY(pl->linear_p(*xp, M, E, q.in_w, 3 * E, pl->P(q.in_b), a.qkv, 3 * E, 0, 0.f, 0, nullptr, nullptr, st));
-            // (ctx and, in backward, d qkv leave the attention kernels as planes only when the sequence fits the single-tile kernels:
-            //  their fp32 copies have no reader in the plane path)
-            SLNLP_TRY(attn_self_fwd(a.qkv, X, S, c.pad_src, 1, B, S, H, dh, S <= 64 ? nullptr : a.ctx, a.probs, p, pl->enc_site(l, 0), rng, st, a.ctxp.out()));
-            SLNLP_TRY(pl->linear_p(a.ctxp, M, E, q.out_w, E, pl->P(q.out_b), a.y1, E, 0, p, pl->enc_site(l, 1), x, nullptr, st));
-            SLNLP_TRY(layernorm_fwd(a.y1, pl->P(q.n1_w), pl->P(q.n1_b), M, E, 1e-5f, a.x1, a.st1, st, a.x1p.out()));
-            SLNLP_TRY(pl->linear_p(a.x1p, M, E, q.l1_w, F, pl->P(q.l1_b), a.h, F, 1, p, pl->enc_site(l, 2), nullptr, &a.hp, st));
-            SLNLP_TRY(pl->linear_p(a.hp, M, F, q.l2_w, E, pl->P(q.l2_b), a.y2, E, 0, p, pl->enc_site(l, 3), a.x1, nullptr, st));
-            SLNLP_TRY(layernorm_fwd(a.y2, pl->P(q.n2_w), pl->P(q.n2_b), M, E, 1e-5f, a.x2, a.st2, st, a.x2p.out()));
-        } else {
-            SLNLP_TRY(pl->linear(x, M, E, pl->P(q.in_w), 3 * E, pl->P(q.in_b), a.qkv, 3 * E, 0, 0.f, 0, nullptr, st));
-            SLNLP_TRY(attn_self_fwd(a.qkv, X, S, c.pad_src, 1, B, S, H, dh, a.ctx, a.probs, p, pl->enc_site(l, 0), rng, st));
-            SLNLP_TRY(pl->linear(a.ctx, M, E, pl->P(q.out_w), E, pl->P(q.out_b), a.y1, E, 0, p, pl->enc_site(l, 1), x, st));
-            SLNLP_TRY(layernorm_fwd(a.y1, pl->P(q.n1_w), pl->P(q.n1_b), M, E, 1e-5f, a.x1, a.st1, st));
-            SLNLP_TRY(pl->linear(a.x1, M, E, pl->P(q.l1_w), F, pl->P(q.l1_b), a.h, F, 1, p, pl->enc_site(l, 2), nullptr, st));
-            SLNLP_TRY(pl->linear(a.h, M, F, pl->P(q.l2_w), E, pl->P(q.l2_b), a.y2, E, 0, p, pl->enc_site(l, 3), a.x1, st));
-            SLNLP_TRY(layernorm_fwd(a.y2, pl->P(q.n2_w), pl->P(q.n2_b), M, E, 1e-5f, a.x2, a.st2, st));
-        }
-        x = a.x2;
-        xp = &a.x2p;
+        SLNLP_TRY(linear(x, q.in_w, q.in_b, M, 3 * E, E, a.qkv, Epi(), st));
+        // (ctx and, in backward, d qkv leave the attention kernels as planes only when the sequence fits the single-tile kernels:
+        //  their fp32 copies have no reader in the plane path)
+        SLNLP_TRY(attn_self_fwd(a.qkv, X, S, c.pad_src, 1, B, S, H, dh, (up && S <= 64) ? nullptr : a.ctx, a.probs, p, enc_site(l, 0), rng, st, pout(a.ctxp)));
+        SLNLP_TRY(linear(view(a.ctx, a.ctxp, E), q.out_w, q.out_b, M, E, E, a.y1, Epi().dropped(p, enc_site(l, 1)).plus(x.f), st));
+        SLNLP_TRY(layernorm_fwd(a.y1, P(q.n1_w), P(q.n1_b), M, E, 1e-5f, a.x1, a.st1, st, pout(a.x1p)));
+        SLNLP_TRY(linear(view(a.x1, a.x1p, E), q.l1_w, q.l1_b, M, F, E, a.h, Epi().relu().dropped(p, enc_site(l, 2)).also(a.hp), st));
+        SLNLP_TRY(linear(view(a.h, a.hp, F), q.l2_w, q.l2_b, M, E, F, a.y2, Epi().dropped(p, enc_site(l, 3)).plus(a.x1), st));
+        SLNLP_TRY(layernorm_fwd(a.y2, P(q.n2_w), P(q.n2_b), M, E, 1e-5f, a.x2, a.st2, st, pout(a.x2p)));
+        x = view(a.x2, a.x2p, E);
     }
-    SLNLP_TRY(layernorm_fwd(x, pl->P(L.encn_w), pl->P(L.encn_b), M, E, 1e-5f, w.mem, w.st_mem, st, up ? w.memp.out() : PlaneOut{}));
+    SLNLP_TRY(layernorm_fwd(x.f, P(L.encn_w), P(L.encn_b), M, E, 1e-5f, w.mem, w.st_mem, st, pout(w.memp)));
 
-    const float* t = w.t0;
-    const PP* tp = &w.t0p;
+    Mat t = rview(w.t0, w.t0p, E);
     for (int l = 0; l < c.N; ++l) {
         const DecP& q = L.dec[l];
         const DecA& a = w.dec[l];
-        if (l > 0) SLNLP_TRY(dec_self_block(l, t, tp, B, p, st));   // (layer 0's block ran ahead of the encoder, above)
+        if (l > 0) SLNLP_TRY(dec_self_block(l, t, B, p, st));   // (layer 0's block ran ahead of the encoder, above)
         // cross-attention over the memory itself: with ONE query per sequence the K / V projections of the S memory rows
         // re-associate into B-row products (attention_mem.hip) -- no [S*B, 2E] projection, no K|V gradient GEMMs:
         // qk = Wk_h^T q_h (batched GEMM) -> scores / softmax / dropout / mbar (+ ctx0 = bv sum_s p_s) -> ctx = Wv_h mbar + ctx0
-        {
-            const float *Wk = pl->P(q.cin_w) + (long)E * E, *Wv = pl->P(q.cin_w) + 2L * E * E;
-            const slnlp_gemm_args j1 = pl->head_expand(a.q, Wk, a.qk, B, H, dh);
-            SLNLP_TRY(gemm_group(&j1, 1, st));
-            SLNLP_TRY(xmem_fwd(a.qk, w.mem, pl->P(q.cin_b) + 2 * E, B, S, H, dh, a.mbar, a.psum, a.xprobs, a.xctx, p, pl->dec_site(l, 2), rng, st));
-            slnlp_gemm_args j2 = pl->head_reduce(a.mbar, Wv, a.xctx, a.xctx, B, H, dh);
-            if (use_rows) { j2.C_hi = a.xctxp.hi; j2.C_lo = a.xctxp.lo; j2.ldc_p = E; }      // ... and as planes, for the out projection
-            SLNLP_TRY(gemm_group(&j2, 1, st));
-        }
-        if (use_rows) {
-            SLNLP_TRY(pl->linear_r(a.xctxp, B, E, q.cout_w, E, pl->P(q.cout_b), a.y2, E, 0, p, pl->dec_site(l, 3), a.t1, nullptr, st));
-            SLNLP_TRY(layernorm_fwd(a.y2, pl->P(q.n2_w), pl->P(q.n2_b), B, E, 1e-5f, a.t2, a.st2, st, a.t2p.out()));
-            SLNLP_TRY(pl->linear_r(a.t2p, B, E, q.l1_w, F, pl->P(q.l1_b), a.h, F, 1, p, pl->dec_site(l, 4), nullptr, &a.hp, st));
-            SLNLP_TRY(pl->linear_r(a.hp, B, F, q.l2_w, E, pl->P(q.l2_b), a.y3, E, 0, p, pl->dec_site(l, 5), a.t2, nullptr, st));
-            SLNLP_TRY(layernorm_fwd(a.y3, pl->P(q.n3_w), pl->P(q.n3_b), B, E, 1e-5f, a.t3, a.st3, st, a.t3p.out()));
-        } else {
-            SLNLP_TRY(pl->linear(a.xctx, B, E, pl->P(q.cout_w), E, pl->P(q.cout_b), a.y2, E, 0, p, pl->dec_site(l, 3), a.t1, st));
-            SLNLP_TRY(layernorm_fwd(a.y2, pl->P(q.n2_w), pl->P(q.n2_b), B, E, 1e-5f, a.t2, a.st2, st));
-            SLNLP_TRY(pl->linear(a.t2, B, E, pl->P(q.l1_w), F, pl->P(q.l1_b), a.h, F, 1, p, pl->dec_site(l, 4), nullptr, st));
-            SLNLP_TRY(pl->linear(a.h, B, F, pl->P(q.l2_w), E, pl->P(q.l2_b), a.y3, E, 0, p, pl->dec_site(l, 5), a.t2, st));
-            SLNLP_TRY(layernorm_fwd(a.y3, pl->P(q.n3_w), pl->P(q.n3_b), B, E, 1e-5f, a.t3, a.st3, st));
-        }
-        t = a.t3;
-        tp = &a.t3p;
+        // (... and as planes, for the out projection)
+        const float *Wk = P(q.cin_w) + (long)E * E, *Wv = P(q.cin_w) + 2L * E * E;
+        const slnlp_gemm_args j1 = head_expand(a.q, Wk, a.qk, B, H, dh, prec3());
+        SLNLP_TRY(gemm_group(&j1, 1, st));
+        SLNLP_TRY(xmem_fwd(a.qk, w.mem, P(q.cin_b) + 2 * E, B, S, H, dh, a.mbar, a.psum, a.xprobs, a.xctx, p, dec_site(l, 2), rng, st));
+        const slnlp_gemm_args j2 = head_reduce(a.mbar, Wv, a.xctx, a.xctx, use_rows ? &a.xctxp : nullptr, B, H, dh, prec3());
+        SLNLP_TRY(gemm_group(&j2, 1, st));
+        SLNLP_TRY(linear(rview(a.xctx, a.xctxp, E), q.cout_w, q.cout_b, B, E, E, a.y2, Epi().dropped(p, dec_site(l, 3)).plus(a.t1), st));
+        SLNLP_TRY(layernorm_fwd(a.y2, P(q.n2_w), P(q.n2_b), B, E, 1e-5f, a.t2, a.st2, st, rout(a.t2p)));
+        SLNLP_TRY(linear(rview(a.t2, a.t2p, E), q.l1_w, q.l1_b, B, F, E, a.h, Epi().relu().dropped(p, dec_site(l, 4)).also(a.hp), st));
+        SLNLP_TRY(linear(rview(a.h, a.hp, F), q.l2_w, q.l2_b, B, E, F, a.y3, Epi().dropped(p, dec_site(l, 5)).plus(a.t2), st));
+        SLNLP_TRY(layernorm_fwd(a.y3, P(q.n3_w), P(q.n3_b), B, E, 1e-5f, a.t3, a.st3, st, rout(a.t3p)));
+        t = rview(a.t3, a.t3p, E);
     }
-    if (use_rows) {
-        SLNLP_TRY(layernorm_fwd(t, pl->P(L.decn_w), pl->P(L.decn_b), B, E, 1e-5f, w.tfin, w.st_fin, st, w.tfinp.out()));
-        SLNLP_TRY(pl->linear_r(w.tfinp, B, E, L.lin_w, c.Vt, pl->P(L.lin_b), w.logits, Vp, 0, 0.f, 0, nullptr, nullptr, st));
-    } else {
-        SLNLP_TRY(layernorm_fwd(t, pl->P(L.decn_w), pl->P(L.decn_b), B, E, 1e-5f, w.tfin, w.st_fin, st));
-        SLNLP_TRY(pl->linear(w.tfin, B, E, pl->P(L.lin_w), c.Vt, pl->P(L.lin_b), w.logits, Vp, 0, 0.f, 0, nullptr, st));
-    }
+    SLNLP_TRY(layernorm_fwd(t.f, P(L.decn_w), P(L.decn_b), B, E, 1e-5f, w.tfin, w.st_fin, st, rout(w.tfinp)));
+    SLNLP_TRY(linear(rview(w.tfin, w.tfinp, E), L.lin_w, L.lin_b, B, c.Vt, E, w.logits, Epi().stride(Vp), st));
     // log_softmax (transformer.py:88-89) + the criterion skorch applies to it (helper.py:61-70)
     // the caller's copy of the log-probs is written by the same kernel (no device-to-device copy); in lockstep it lands
     // in the epoch buffer at the batch's row offset and the loss in the epoch's loss history
-    SLNLP_TRY(lsm_nll(w.logits, Vp, y, B, c.Vt, c.pad_tgt, w.logp, pl->buf.scalars, train ? w.dlogits : nullptr, Vp,
+    SLNLP_TRY(lsm_nll(w.logits, Vp, y, B, c.Vt, c.pad_tgt, w.logp, buf.scalars, train ? w.dlogits : nullptr, Vp,
                       w.row_nll, st, nullptr, logp_out ? logp_out : ls_logp, logp_out ? nullptr : ls_dyn,
-                      logp_out ? nullptr : ls_loss, (!logp_out && ls_dyn) ? ls_dyn + 1 : nullptr, pl->opts.loss()));
+                      logp_out ? nullptr : ls_loss, (!logp_out && ls_dyn) ? ls_dyn + 1 : nullptr, opts.loss()));
     return 0;
 }
 
@@ -313,96 +258,51 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
     // Everything runs on the caller's stream; the weight gradient of each dY shares a launch with its data gradient -- but the
     // encoder's where the pair's launch would wait for it: those run in one batched launch behind the layer loop (tf_plan.hpp).
 
-    // generator: logits = tfin lin_w^T + lin_b
-    SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(w.dlogits, Vp, B, c.Vt, w.tfin, E, pl->G(L.lin_w), pl->G(L.lin_b)),
-                             pl->dgrad_args(w.dlogits, Vp, B, c.Vt, pl->P(L.lin_w), E, w.gfin, nullptr, 0.f, nullptr), st));
+    // generator: logits = tfin lin_w^T + lin_b (fp32 operands in every mode)
+    SLNLP_TRY(pl->linear_bwd(f32(w.dlogits, Vp), L.lin_w, L.lin_b, f32(w.tfin, E), B, c.Vt, E, w.gfin, Epi(), st));
     SLNLP_TRY(layernorm_bwd(w.gfin, w.dec[c.N - 1].t3, pl->P(L.decn_w), w.st_fin, B, E, nullptr, w.gtl, nullptr, 0.f, 0,
                             rng, nullptr, nullptr, 0, st));
     const float* dt = w.gtl;  // gradient w.r.t. the current decoder layer's output
     // d memory has no reader before the encoder's final LayerNorm: the layers leave it (and d bv) to one launch behind the loop
     float* const gmem_l = pl->dmem_batched ? nullptr : w.gmem;
+    const bool ur = pl->use_rows;
     for (int l = c.N - 1; l >= 0; --l) {
         const DecP& q = L.dec[l];
         const DecA& a = w.dec[l];
-        const float* t_in = l > 0 ? w.dec[l - 1].t3 : w.t0;
-        if (pl->use_rows) {
-            // the same chain on plane operands: LayerNorm backward emits the sub-layer's dY as planes (the dropout-masked copy when
-            // dropout is on), every Linear's backward pair is ONE gemm_rows_bwd launch, whose data gradient emits the next dY
-            const PlaneOut none{};
-            const PP& t_inp = l > 0 ? w.dec[l - 1].t3p : w.t0p;
-            SLNLP_TRY(layernorm_bwd(dt, a.y3, pl->P(q.n3_w), a.st3, B, E, nullptr, a.gA3, nullptr, p, pl->dec_site(l, 5), rng, nullptr, nullptr, 0, st,
-                                    p == 0.f ? a.d3p.out() : none, p > 0.f ? a.d3p.out() : none));
-            SLNLP_TRY(pl->wd_rows(a.d3p, B, E, q.l2_w, F, nullptr, &a.ghp, a.h, ik, nullptr, a.hp, q.l2_w, q.l2_b, st));
-            SLNLP_TRY(pl->wd_rows(a.ghp, B, F, q.l1_w, E, a.gt2, nullptr, nullptr, 0.f, a.gA3, a.t2p, q.l1_w, q.l1_b, st));
-            SLNLP_TRY(layernorm_bwd(a.gt2, a.y2, pl->P(q.n2_w), a.st2, B, E, nullptr, a.gA2, nullptr, p, pl->dec_site(l, 3), rng, nullptr, nullptr, 0, st,
-                                    p == 0.f ? a.d2p.out() : none, p > 0.f ? a.d2p.out() : none));
-            SLNLP_TRY(pl->wd_rows(a.d2p, B, E, q.cout_w, E, a.gxctx, nullptr, nullptr, 0.f, nullptr, a.xctxp, q.cout_w, q.cout_b, st));
-            {
-                const float *Wk = pl->P(q.cin_w) + (long)E * E, *Wv = pl->P(q.cin_w) + 2L * E * E;
-                const slnlp_gemm_args j1 = pl->head_expand(a.gxctx, Wv, a.dmbar, B, H, dh);
-                SLNLP_TRY(gemm_group(&j1, 1, st));
-                SLNLP_TRY(xmem_bwd(w.mem, pl->P(q.cin_b) + 2 * E, a.xprobs, a.psum, a.qk, a.dmbar, a.gxctx, B, S, H, dh, a.dsc, a.dqk, a.dcp,
-                                   pl->G(q.cin_b) + 2 * E, gmem_l, l == c.N - 1 ? 0 : 1, p, pl->dec_site(l, 2), rng, st));
-                slnlp_gemm_args jobs[3] = {pl->head_reduce(a.dqk, Wk, a.gq, nullptr, B, H, dh),
-                                           pl->head_wgrad(a.q, a.dqk, pl->G(q.cin_w) + (long)E * E, B, H, dh),
-                                           pl->head_wgrad(a.gxctx, a.mbar, pl->G(q.cin_w) + 2L * E * E, B, H, dh)};
-                jobs[0].C_hi = a.gqp.hi; jobs[0].C_lo = a.gqp.lo; jobs[0].ldc_p = E;
-                SLNLP_TRY(gemm_group(jobs, 3, st));
-            }
-            SLNLP_TRY(pl->wd_rows(a.gqp, B, E, q.cin_w, E, a.gt1, nullptr, nullptr, 0.f, a.gA2, a.t1p, q.cin_w, q.cin_b, st));
-            SLNLP_TRY(layernorm_bwd(a.gt1, a.y1, pl->P(q.n1_w), a.st1, B, E, nullptr, a.gA1, nullptr, p, pl->dec_site(l, 1), rng, nullptr, nullptr, 0, st,
-                                    p == 0.f ? a.d1p.out() : none, p > 0.f ? a.d1p.out() : none));
-            // (the single-key self-attention's per-(row, head) dropout: the same mask as the forward V projection)
-            SLNLP_TRY(pl->wd_rows(a.d1p, B, E, q.sout_w, E, nullptr, &a.gvp, nullptr, 0.f, nullptr, a.vp, q.sout_w, q.sout_b, st, p, pl->dec_site(l, 0), p > 0.f ? dh : 0));
-            // softmax over one element has zero gradient: the q/k rows of in_proj (weight and bias) get exactly 0 -- nothing writes them
-            SLNLP_TRY(pl->wd_rows(a.gvp, B, E, q.sin_w + 2L * E * E, E, a.gt0, nullptr, nullptr, 0.f, a.gA1, t_inp, q.sin_w + 2L * E * E, q.sin_b + 2 * E, st));
-            dt = a.gt0;
-            continue;
-        }
+        const Mat t_in = l > 0 ? pl->rview(w.dec[l - 1].t3, w.dec[l - 1].t3p, E) : pl->rview(w.t0, w.t0p, E);
+        // Each LayerNorm backward emits the sub-layer's dY the way the pair reads it; every Linear's backward pair is ONE launch, whose
+        // data gradient emits the next dY (B-row products: as planes; d h and d v then have no fp32 copy)
         // norm3 / FFN
-        SLNLP_TRY(layernorm_bwd(dt, a.y3, pl->P(q.n3_w), a.st3, B, E, nullptr, a.gA3, p > 0.f ? a.gB3 : nullptr, p,
-                                pl->dec_site(l, 5), rng, nullptr, nullptr, 0, st));
-        const float* d3 = p > 0.f ? a.gB3 : a.gA3;
-        SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d3, E, B, E, a.h, F, pl->G(q.l2_w), pl->G(q.l2_b)),
-                                 pl->dgrad_args(d3, E, B, E, pl->P(q.l2_w), F, a.gh, a.h, ik, nullptr), st));
-        SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(a.gh, F, B, F, a.t2, E, pl->G(q.l1_w), pl->G(q.l1_b)),
-                                 pl->dgrad_args(a.gh, F, B, F, pl->P(q.l1_w), E, a.gt2, nullptr, 0.f, a.gA3), st));
+        SLNLP_TRY(pl->ln_bwd_dy(ur, dt, a.y3, q.n3_w, a.st3, B, a.gA3, a.gB3, a.d3p, p, pl->dec_site(l, 5), nullptr, 0, st));
+        SLNLP_TRY(pl->linear_bwd(pl->rview(p > 0.f ? a.gB3 : a.gA3, a.d3p, E), q.l2_w, q.l2_b, pl->rview(a.h, a.hp, F), B, E, F, ur ? nullptr : a.gh,
+                                 Epi().gated(a.h, ik).also(a.ghp), st));
+        SLNLP_TRY(pl->linear_bwd(pl->rview(a.gh, a.ghp, F), q.l1_w, q.l1_b, pl->rview(a.t2, a.t2p, E), B, F, E, a.gt2, Epi().plus(a.gA3), st));
         // norm2 / cross-attention
-        SLNLP_TRY(layernorm_bwd(a.gt2, a.y2, pl->P(q.n2_w), a.st2, B, E, nullptr, a.gA2, p > 0.f ? a.gB2 : nullptr, p,
-                                pl->dec_site(l, 3), rng, nullptr, nullptr, 0, st));
-        const float* d2 = p > 0.f ? a.gB2 : a.gA2;
-        SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d2, E, B, E, a.xctx, E, pl->G(q.cout_w), pl->G(q.cout_b)),
-                                 pl->dgrad_args(d2, E, B, E, pl->P(q.cout_w), E, a.gxctx, nullptr, 0.f, nullptr), st));
+        SLNLP_TRY(pl->ln_bwd_dy(ur, a.gt2, a.y2, q.n2_w, a.st2, B, a.gA2, a.gB2, a.d2p, p, pl->dec_site(l, 3), nullptr, 0, st));
+        SLNLP_TRY(pl->linear_bwd(pl->rview(p > 0.f ? a.gB2 : a.gA2, a.d2p, E), q.cout_w, q.cout_b, pl->rview(a.xctx, a.xctxp, E), B, E, E, a.gxctx, Epi(), st));
         // d ctx -> d mbar = Wv_h^T d ctx_h (batched GEMM) -> d scores, d qk (d memory, accumulated over the decoder layers in
         // layer order, and d bv: here per layer, or for all layers behind the loop -- dmem_batched) -> ONE launch of three batched jobs: d q_h = Wk_h d qk, d Wk_h = q_h^T (x) d qk, d Wv_h = d ctx_h^T (x) mbar.
         // d bk is exactly zero (a shift of all scores): nothing writes it, the gradient arena was zeroed at plan creation.
         {
             const float *Wk = pl->P(q.cin_w) + (long)E * E, *Wv = pl->P(q.cin_w) + 2L * E * E;
-            const slnlp_gemm_args j1 = pl->head_expand(a.gxctx, Wv, a.dmbar, B, H, dh);
+            const int pr = pl->prec3();
+            const slnlp_gemm_args j1 = head_expand(a.gxctx, Wv, a.dmbar, B, H, dh, pr);
             SLNLP_TRY(gemm_group(&j1, 1, st));
             SLNLP_TRY(xmem_bwd(w.mem, pl->P(q.cin_b) + 2 * E, a.xprobs, a.psum, a.qk, a.dmbar, a.gxctx, B, S, H, dh, a.dsc, a.dqk, a.dcp,
                                pl->G(q.cin_b) + 2 * E, gmem_l, l == c.N - 1 ? 0 : 1, p, pl->dec_site(l, 2), rng, st));
-            const slnlp_gemm_args jobs[3] = {pl->head_reduce(a.dqk, Wk, a.gq, nullptr, B, H, dh),
-                                             pl->head_wgrad(a.q, a.dqk, pl->G(q.cin_w) + (long)E * E, B, H, dh),
-                                             pl->head_wgrad(a.gxctx, a.mbar, pl->G(q.cin_w) + 2L * E * E, B, H, dh)};
+            const slnlp_gemm_args jobs[3] = {head_reduce(a.dqk, Wk, a.gq, nullptr, ur ? &a.gqp : nullptr, B, H, dh, pr),
+                                             head_wgrad(a.q, a.dqk, pl->G(q.cin_w) + (long)E * E, B, H, dh, pr),
+                                             head_wgrad(a.gxctx, a.mbar, pl->G(q.cin_w) + 2L * E * E, B, H, dh, pr)};
             SLNLP_TRY(gemm_group(jobs, 3, st));
         }
-        SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(a.gq, E, B, E, a.t1, E, pl->G(q.cin_w), pl->G(q.cin_b)),
-                                 pl->dgrad_args(a.gq, E, B, E, pl->P(q.cin_w), E, a.gt1, nullptr, 0.f, a.gA2), st));
-        // norm1 / self-attention (single key)
-        hipStream_t sb = st;
-        SLNLP_TRY(layernorm_bwd(a.gt1, a.y1, pl->P(q.n1_w), a.st1, B, E, nullptr, a.gA1, p > 0.f ? a.gB1 : nullptr, p,
-                                pl->dec_site(l, 1), rng, nullptr, nullptr, 0, sb));
-        const float* d1 = p > 0.f ? a.gB1 : a.gA1;
-        {
-            slnlp_gemm_args dg = pl->dgrad_args(d1, E, B, E, pl->P(q.sout_w), E, a.gv, nullptr, 0.f, nullptr);
-            if (p > 0.f) { dg.drop_p = p; dg.drop_site = pl->dec_site(l, 0); dg.rng = rng; dg.drop_head_dim = dh; }   // same mask as forward
-            SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d1, E, B, E, a.v, E, pl->G(q.sout_w), pl->G(q.sout_b)), dg, sb));
-        }
+        SLNLP_TRY(pl->linear_bwd(pl->rview(a.gq, a.gqp, E), q.cin_w, q.cin_b, pl->rview(a.t1, a.t1p, E), B, E, E, a.gt1, Epi().plus(a.gA2), st));
+        // norm1 / self-attention (single key; its per-(row, head) dropout: the same mask as the forward V projection)
+        SLNLP_TRY(pl->ln_bwd_dy(ur, a.gt1, a.y1, q.n1_w, a.st1, B, a.gA1, a.gB1, a.d1p, p, pl->dec_site(l, 1), nullptr, 0, st));
+        SLNLP_TRY(pl->linear_bwd(pl->rview(p > 0.f ? a.gB1 : a.gA1, a.d1p, E), q.sout_w, q.sout_b, pl->rview(a.v, a.vp, E), B, E, E, ur ? nullptr : a.gv,
+                                 Epi().dropped(p, pl->dec_site(l, 0), p > 0.f ? dh : 0).also(a.gvp), st));
         // softmax over one element has zero gradient: the q/k rows of in_proj (weight and bias) get exactly 0.
         // Nothing ever writes them, and the gradient arena is zeroed at plan creation, so they stay zero.
-        SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(a.gv, E, B, E, t_in, E, pl->G(q.sin_w) + 2L * E * E, pl->G(q.sin_b) + 2 * E),
-                                 pl->dgrad_args(a.gv, E, B, E, pl->P(q.sin_w) + 2L * E * E, E, a.gt0, nullptr, 0.f, a.gA1), sb));
+        SLNLP_TRY(pl->linear_bwd(pl->rview(a.gv, a.gvp, E), q.sin_w + 2L * E * E, q.sin_b + 2 * E, t_in, B, E, E, a.gt0, Epi().plus(a.gA1), st));
         dt = a.gt0;
     }
     if (pl->dmem_batched) SLNLP_TRY(xmem_dmem_all(w.dmem_tab, c.N, B, S, H, dh, w.gmem, p, rng, st));
@@ -418,40 +318,17 @@ int slnlp_tf_backward(slnlp_tf_plan* pl, void* stream) {
     for (int l = c.N - 1; l >= 0; --l) {
         const EncP& q = L.enc[l];
         const EncA& a = w.enc[l];
-        const float* x_in = l > 0 ? w.enc[l - 1].x2 : w.x0;
-        const PlaneOut none{};
         // LayerNorm backward also emits the bf16 planes of the gradient that feeds the sub-layer's GEMMs
         // (the dropout-masked copy when dropout is on, else dx itself)
         // (plane path: the sub-layer's GEMMs read the planes only, so neither the masked fp32 copy nor the fp32 ReLU-gated
         //  gradient of the FFN hidden layer is stored)
-        SLNLP_TRY(layernorm_bwd(dx, a.y2, pl->P(q.n2_w), a.st2, M, E, nullptr, a.gA2, (p > 0.f && !up) ? a.gB2 : nullptr, p,
-                                pl->enc_site(l, 3), rng, lnf ? a.lnp2 : nullptr, nullptr, Mfull, st, (up && p == 0.f) ? a.d2p.out() : none,
-                                (up && p > 0.f) ? a.d2p.out() : none));
-        const float* d2 = p > 0.f ? a.gB2 : a.gA2;
-        if (up) {
-            SLNLP_TRY(pl->enc_pair_launch(l, 0, B, ik, st));     // linear2: d h (ReLU-gated, planes only)
-            SLNLP_TRY(pl->enc_pair_launch(l, 1, B, ik, st));     // linear1: d x1 (+ the residual branch)
-        } else {
-            SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d2, E, M, E, a.h, F, pl->G(q.l2_w), pl->G(q.l2_b)),
-                                     pl->dgrad_args(d2, E, M, E, pl->P(q.l2_w), F, a.gh, a.h, ik, nullptr), st));
-            SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(a.gh, F, M, F, a.x1, E, pl->G(q.l1_w), pl->G(q.l1_b)),
-                                     pl->dgrad_args(a.gh, F, M, F, pl->P(q.l1_w), E, a.gx1, nullptr, 0.f, a.gA2), st));
-        }
-        SLNLP_TRY(layernorm_bwd(a.gx1, a.y1, pl->P(q.n1_w), a.st1, M, E, nullptr, a.gA1, (p > 0.f && !up) ? a.gB1 : nullptr, p,
-                                pl->enc_site(l, 1), rng, lnf ? a.lnp1 : nullptr, nullptr, Mfull, st, (up && p == 0.f) ? a.d1p.out() : none,
-                                (up && p > 0.f) ? a.d1p.out() : none));
-        const float* d1 = p > 0.f ? a.gB1 : a.gA1;
-        if (up) {
-            SLNLP_TRY(pl->enc_pair_launch(l, 2, B, ik, st));     // out_proj: d ctx
-            SLNLP_TRY(attn_self_bwd(a.qkv, a.probs, a.gctx, B, S, H, dh, S <= 64 ? nullptr : a.gqkv, p, pl->enc_site(l, 0), rng, st, a.gqkvp.out(), w.attn_scratch));
-            SLNLP_TRY(pl->enc_pair_launch(l, 3, B, ik, st));     // in_proj: d x0 (+ the residual branch)
-        } else {
-            SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(d1, E, M, E, a.ctx, E, pl->G(q.out_w), pl->G(q.out_b)),
-                                     pl->dgrad_args(d1, E, M, E, pl->P(q.out_w), E, a.gctx, nullptr, 0.f, nullptr), st));
-            SLNLP_TRY(attn_self_bwd(a.qkv, a.probs, a.gctx, B, S, H, dh, a.gqkv, p, pl->enc_site(l, 0), rng, st, PlaneOut{}, w.attn_scratch));
-            SLNLP_TRY(pl->wd_group_f(pl->wgrad_args(a.gqkv, 3 * E, M, 3 * E, x_in, E, pl->G(q.in_w), pl->G(q.in_b)),
-                                     pl->dgrad_args(a.gqkv, 3 * E, M, 3 * E, pl->P(q.in_w), E, a.gx0, nullptr, 0.f, a.gA1), st));
-        }
+        SLNLP_TRY(pl->ln_bwd_dy(up, dx, a.y2, q.n2_w, a.st2, M, a.gA2, a.gB2, a.d2p, p, pl->enc_site(l, 3), lnf ? a.lnp2 : nullptr, Mfull, st));
+        SLNLP_TRY(pl->enc_pair_launch(l, 0, B, st));     // linear2: d h (ReLU-gated)
+        SLNLP_TRY(pl->enc_pair_launch(l, 1, B, st));     // linear1: d x1 (+ the residual branch)
+        SLNLP_TRY(pl->ln_bwd_dy(up, a.gx1, a.y1, q.n1_w, a.st1, M, a.gA1, a.gB1, a.d1p, p, pl->enc_site(l, 1), lnf ? a.lnp1 : nullptr, Mfull, st));
+        SLNLP_TRY(pl->enc_pair_launch(l, 2, B, st));     // out_proj: d ctx
+        SLNLP_TRY(attn_self_bwd(a.qkv, a.probs, a.gctx, B, S, H, dh, (up && S <= 64) ? nullptr : a.gqkv, p, pl->enc_site(l, 0), rng, st, pl->pout(a.gqkvp), w.attn_scratch));
+        SLNLP_TRY(pl->enc_pair_launch(l, 3, B, st));     // in_proj: d x0 (+ the residual branch)
         dx = a.gx0;
     }
     // the weight gradients the loop left behind (tf_plan.hpp: enc_pair_launch), all in one launch; nothing below reads a dW

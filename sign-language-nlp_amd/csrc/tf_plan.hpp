@@ -1,5 +1,7 @@
-// tf_plan.hpp -- the Transformer plan object: arena layout, workspace carving and the per-launch helpers.  Shared by
-// tf_plan.hip (the single-fit entry points) and lockstep.hip (K plans advancing through one launch sequence).
+// tf_plan.hpp -- the Transformer plan object: arena layout, workspace carving, and the two operations a layer is written in:
+// linear() and linear_bwd(), which pick the kernel family (fp32-operand, plane, B-row, fp8) from the operand views of the plan's
+// mode and take their jobs from linear_jobs.hpp.  Shared by tf_plan.hip (the single-fit entry points) and lockstep.hip (K plans
+// advancing through one launch sequence).
 #pragma once
 #include <map>
 #include <string>
@@ -8,16 +10,11 @@
 #include "common.hpp"
 #include "gemm_jobs.hpp"
 #include "launch.hpp"
+#include "linear_jobs.hpp"
 #include "plan_core.hpp"
 
 namespace slnlp {
 
-struct ParamEnt {
-    std::string name;
-    int64_t shape[2];
-    int ndim;
-    int64_t off, numel;
-};
 struct EncP { long in_w, in_b, out_w, out_b, l1_w, l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b; };
 struct DecP {
     long sin_w, sin_b, sout_w, sout_b, cin_w, cin_b, cout_w, cout_b, l1_w, l1_b, l2_w, l2_b;
@@ -123,28 +120,8 @@ static int check_cfg(const slnlp_tf_config* c) {
 }
 
 // ------------------------------------------------------------- workspace ----
-struct Bump {
-    char* base;
-    size_t cur = 0;
-    explicit Bump(void* b) : base((char*)b) {}
-    template <typename T>
-    T* take(size_t n) {
-        cur = (cur + 255) & ~(size_t)255;
-        T* p = (T*)(base + cur);
-        cur += n * sizeof(T);
-        return p;
-    }
-};
-
 // forward activations kept for backward + this layer's gradient buffers.  Every gradient buffer is
 // written exactly once per step: there is nothing to overwrite until the next step.
-// bf16 hi/lo planes of a GEMM operand (same logical shape / row stride as its fp32 twin, rows
-// zero-padded to a multiple of 64): written once by the producer, read by gemm_planes.hip
-struct PP {
-    unsigned short *hi = nullptr, *lo = nullptr;
-    unsigned char* q8 = nullptr;        // precision 8: forward operands also as an e4m3 plane
-    PlaneOut out() const { PlaneOut o; o.hi = hi; o.lo = lo; o.q8 = q8; return o; }
-};
 struct EncA {
     float *qkv, *probs, *ctx, *y1, *st1, *x1, *h, *y2, *st2, *x2, *lnp1, *lnp2;
     float *gA2, *gB2, *gh, *gx1, *gA1, *gB1, *gctx, *gqkv, *gx0;
@@ -466,206 +443,75 @@ struct slnlp_tf_plan : PlanCore {
     int backward(hipStream_t st) override { return slnlp_tf_backward(this, st); }
     bool use_planes = false;   // E, F multiples of 64: M = S*B GEMMs run on pre-split bf16 planes (gemm_planes.hip)
     bool use_rows = false;     // ... and the decoder's B-row products on planes, register-direct (gemm_rows.hip; K <= 1024)
-    // split-bf16 passes of the plane GEMM's gradient products: the process default AT CREATION (slnlp_set_backward_passes), fixed for the
-    // plan's life -- a captured graph, a recorded lockstep program and every host thread that steps this plan issue the same products
-    int wgrad_np = 2, dgrad_np = 2;
-
     float* P(long off) const { return buf.params + off; }
     float* G(long off) const { return buf.grads + off; }
     int enc_site(int l, int k) const { return SITE_LAYER0 + l * SITE_PER_LAYER + k; }
     int dec_site(int l, int k) const { return SITE_LAYER0 + (cfg.N + l) * SITE_PER_LAYER + k; }
 
-    int dec_self_block(int l, const float* t, const PP* tp, int B, float p, hipStream_t st) const;
+    int dec_self_block(int l, const Mat& t, int B, float p, hipStream_t st) const;
 
-    // y[M,N] = x[M,K] W[N,K]^T + b  (+relu) (+dropout) (+resid)
-    int linear(const float* x, int M, int K, const float* W, int N, const float* bias, float* y, long ldy, int relu,
-               float p, int site, const float* resid, hipStream_t st, int drop_head_dim = 0) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.lda = K; a.a_kmajor = 1;
-        a.B = W; a.ldb = K; a.b_kmajor = 1;
-        a.C = y; a.ldc = ldy; a.M = M; a.N = N; a.K = K;
-        a.bias = bias; a.relu = relu;
-        a.drop_p = p; a.drop_site = site; a.rng = buf.rng;
-        a.resid = resid; a.ldr = ldy;
-        a.precision = prec3();
-        a.drop_head_dim = drop_head_dim;
-        return gemm(a, st);
+    // ---- an activation as the operand of the plan's mode: the encoder's S*B-row products read planes when use_planes, the decoder's
+    // B-row products when use_rows; else both read fp32.  (The fp32 pointer travels along: residuals and LayerNorms read it.)
+    Mat view(const float* f, const PP& p, long ld) const { return use_planes ? planes(p, ld, Mat::PLANES, f) : f32(f, ld); }
+    Mat rview(const float* f, const PP& p, long ld) const { return use_rows ? planes(p, ld, Mat::ROWS, f) : f32(f, ld); }
+    PlaneOut pout(const PP& p) const { return use_planes ? p.out() : PlaneOut{}; }     // ... and what their producers emit beside fp32
+    PlaneOut rout(const PP& p) const { return use_rows ? p.out() : PlaneOut{}; }
+
+    // y[M, N] = x[M, K] W^T + b with the epilogue `e`; W, b at arena offsets woff, boff.  The family follows x's view: fp32 operands
+    // (gemm.hip); B-row planes against fp32 weights, register-direct (gemm_rows.hip) where rows_for says so; else the plane GEMM --
+    // for the encoder at precision 8 on e4m3 planes with per-row weight scales.  Only a product of planes also emits planes.
+    int linear(const Mat& x, long woff, long boff, int M, int N, int K, float* y, Epi e, hipStream_t st) const {
+        e.bias = P(boff);
+        e.rng = buf.rng;
+        if (x.kind == Mat::F32) {
+            e.out = nullptr;
+            return gemm(linear_job(x, f32(P(woff), K), M, N, K, y, e, prec3()), st);
+        }
+        if (x.kind == Mat::ROWS) {
+            const bool rows = rows_for(M, e.drop_head_dim);
+            const slnlp_gemm_args a = linear_job(x, rows ? f32(P(woff), K) : planes(w.wp.at(woff), K), M, N, K, y, e, prec3());
+            return rows ? gemm_rows(a, st) : gemm(a, st);
+        }
+        if (cfg.precision != 8) return gemm(linear_job(x, planes(w.wp.at(woff), K), M, N, K, y, e, prec3()), st);
+        PP wq;
+        wq.q8 = w.wq + woff;
+        e.col_scale = w.wscale + qrow0.at(woff);
+        return gemm(linear_job(planes(x.p, K, Mat::Q8), planes(wq, K, Mat::Q8), M, N, K, y, e, 8), st);
     }
-    // dx[M,Kin] = dy[M,Nout] W[Nout,Kin]  (*gate) (+resid)
-    slnlp_gemm_args dgrad_args(const float* dy, long ldy, int M, int Nout, const float* W, int Kin, float* dx,
-                               const float* gate, float gate_scale, const float* resid) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = dy; a.lda = ldy; a.a_kmajor = 1;
-        a.B = W; a.ldb = Kin; a.b_kmajor = 0;
-        a.C = dx; a.ldc = Kin; a.M = M; a.N = Kin; a.K = Nout;
-        a.gate = gate; a.ldg = Kin; a.gate_scale = gate_scale;
-        a.resid = resid; a.ldr = Kin;
-        a.precision = prec3();
-        return a;
+    // The gradient pair of that Linear: wg: dW = dY^T x, db = colsum(dY) into the gradient arena at woff, boff; dg: dX = dY W with the
+    // epilogue `e` (gate, per-head dropout, residual; fp32 and / or planes out).  Same family rule, from dY's view.  A data gradient
+    // without a mask carries no dropout fields; the B-row kernel's always names the rng.
+    void linear_bwd_jobs(const Mat& dy, long woff, long boff, const Mat& x, int T, int Nout, int Kin, float* dx, Epi e,
+                         slnlp_gemm_args* wg, slnlp_gemm_args* dg) const {
+        const bool f = dy.kind == Mat::F32, rows = dy.kind == Mat::ROWS && rows_for(T, e.drop_head_dim), pg = !f && !rows;
+        if (f) e.out = nullptr;
+        if (!rows && e.drop_p == 0.f) e.drop_site = e.drop_head_dim = 0;
+        if (rows || e.drop_p > 0.f) e.rng = buf.rng;
+        *wg = wgrad_job(dy, x, T, Nout, Kin, G(woff), G(boff), pg ? wgrad_prec(prec3()) : prec3());
+        *dg = dgrad_job(dy, pg ? planes(w.wp.at(woff), Kin) : f32(P(woff), Kin), T, Nout, Kin, dx, e, pg ? dgrad_prec(prec3()) : prec3());
     }
-    int dgrad(const float* dy, long ldy, int M, int Nout, const float* W, int Kin, float* dx, const float* gate,
-              float gate_scale, const float* resid, hipStream_t st) const {
-        return gemm(dgrad_args(dy, ldy, M, Nout, W, Kin, dx, gate, gate_scale, resid), st);
-    }
-    // dW[Nout,Kin] = dy[T,Nout]^T x[T,Kin];  db[Nout] = colsum(dy)
-    slnlp_gemm_args wgrad_args(const float* dy, long ldy, int T, int Nout, const float* x, int Kin, float* dW, float* db) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = dy; a.lda = ldy; a.a_kmajor = 0;
-        a.B = x; a.ldb = Kin; a.b_kmajor = 0;
-        a.C = dW; a.ldc = Kin; a.M = Nout; a.N = Kin; a.K = T;
-        a.rowsum_a = db;
-        a.precision = prec3();
-        return a;
-    }
-    int wgrad(const float* dy, long ldy, int T, int Nout, const float* x, int Kin, float* dW, float* db,
-              hipStream_t st) const {
-        return gemm(wgrad_args(dy, ldy, T, Nout, x, Kin, dW, db), st);
-    }
-    // `H` GEMMs of one shape in one job (gemm.hip, batched jobs): GEMM h reads A + h*sa, B + h*sb and writes C + h*sc
-    static slnlp_gemm_args batched(slnlp_gemm_args a, int H, long sa, long sb, long sc) {
-        a.batch = H; a.batch_stride_a = sa; a.batch_stride_b = sb; a.batch_stride_c = sc;
-        return a;
-    }
-    // per-head products of the decoder's cross-attention (attention_mem.hip); W = rows h*dh.. of a [E, E] block of in_proj
-    // x[B, H*dh] (columns h*dh..) -> out[B, H, E]:  out_h = x_h W_h      (qk = Wk_h^T q_h;  d mbar = Wv_h^T d ctx_h)
-    slnlp_gemm_args head_expand(const float* x, const float* W, float* out, int B, int H, int dh) const {
-        const int E = H * dh;
-        slnlp_gemm_args a = dgrad_args(x, E, B, dh, W, E, out, nullptr, 0.f, nullptr);
-        a.ldc = (long)H * E;
-        return batched(a, H, dh, (long)dh * E, E);
-    }
-    // x[B, H, E] -> out[B, H*dh] (columns h*dh..):  out_h = x_h W_h^T (+ resid in place)      (ctx_h = Wv_h mbar;  d q_h = Wk_h d qk)
-    slnlp_gemm_args head_reduce(const float* x, const float* W, float* out, const float* resid, int B, int H, int dh) const {
-        const int E = H * dh;
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.lda = (long)H * E; a.a_kmajor = 1;
-        a.B = W; a.ldb = E; a.b_kmajor = 1;
-        a.C = out; a.ldc = E; a.M = B; a.N = dh; a.K = E;
-        a.resid = resid; a.ldr = E;
-        a.precision = prec3();
-        return batched(a, H, E, (long)dh * E, dh);
-    }
-    // dW_h[dh, E] = dy_h^T x_h:  dy[B, H*dh] (columns h*dh..), x[B, H, E], dW = rows h*dh.. of an [E, E] gradient block
-    slnlp_gemm_args head_wgrad(const float* dy, const float* x, float* dW, int B, int H, int dh) const {
-        const int E = H * dh;
-        slnlp_gemm_args a = wgrad_args(dy, E, B, dh, x, E, dW, nullptr);
-        a.ldb = (long)H * E;
-        return batched(a, H, dh, E, (long)dh * E);
-    }
-    // weight- and data-gradient of one dY (fp32 operands) in one launch
-    int wd_group_f(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg, hipStream_t st) const {
+    // ... in ONE launch: the grouped fp32-operand kernel; gemm_rows_bwd; or the plane GEMM's pair, whose weight gradient (split-K over
+    // the tokens) fills the CUs the data gradient leaves idle -- no cross-queue edge to pay for (measured 4-10 us each; split factor,
+    // one launch or two: gemm_planes.hip).  dgrad_alone: the weight gradient runs elsewhere (wb_defers)
+    int launch_pair(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg, bool dgrad_alone, hipStream_t st) const {
+        if (dgrad_alone) return gemm(dg, st);
+        if (dg.A_hi && dg.B_hi) return gemm_planes_wd(wg, dg, w.gscr[0], w.gscr_bytes, st);
+        if (dg.A_hi) return gemm_rows_bwd(dg, wg, st);
         const slnlp_gemm_args jobs[2] = {wg, dg};
         return gemm_group(jobs, 2, st);
     }
-    // ---- the same three GEMM roles over pre-split planes; weights: planes of the arena at offset woff
-    int linear_p(const PP& x, int M, int K, long woff, int N, const float* bias, float* y, long ldy, int relu, float p,
-                 int site, const float* resid, const PP* outp, hipStream_t st) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        if (cfg.precision == 8) {       // fp8 forward product: e4m3 planes, per-row weight scales
-            a.A_hi = reinterpret_cast<const uint16_t*>(x.q8); a.lda_p = K; a.a_kmajor = 1;
-            a.B_hi = reinterpret_cast<const uint16_t*>(w.wq + woff); a.ldb_p = K; a.b_kmajor = 1;
-            a.col_scale = w.wscale + qrow0.at(woff);
-            a.C = y; a.ldc = ldy; a.M = M; a.N = N; a.K = K;
-            a.bias = bias; a.relu = relu;
-            a.drop_p = p; a.drop_site = site; a.rng = buf.rng;
-            a.resid = resid; a.ldr = ldy;
-            if (outp) { a.C_hi = outp->hi; a.C_lo = outp->lo; a.C_q8 = outp->q8; a.ldc_p = N; }
-            a.precision = 8;
-            return gemm(a, st);
-        }
-        a.A_hi = x.hi; a.A_lo = x.lo; a.lda_p = K; a.a_kmajor = 1;
-        a.B_hi = w.wp.hi + woff; a.B_lo = w.wp.lo + woff; a.ldb_p = K; a.b_kmajor = 1;
-        a.C = y; a.ldc = ldy; a.M = M; a.N = N; a.K = K;
-        a.bias = bias; a.relu = relu;
-        a.drop_p = p; a.drop_site = site; a.rng = buf.rng;
-        a.resid = resid; a.ldr = ldy;
-        if (outp) { a.C_hi = outp->hi; a.C_lo = outp->lo; a.ldc_p = N; }
-        a.precision = prec3();
-        return gemm(a, st);
+    int linear_bwd(const Mat& dy, long woff, long boff, const Mat& x, int T, int Nout, int Kin, float* dx, const Epi& e, hipStream_t st) const {
+        slnlp_gemm_args wg, dg;
+        linear_bwd_jobs(dy, woff, boff, x, T, Nout, Kin, dx, e, &wg, &dg);
+        return launch_pair(wg, dg, false, st);
     }
-    // the same product for the decoder's B rows: x as planes, W as fp32 (split in registers), both register-direct (gemm_rows.hip)
-    int linear_r(const PP& x, int M, int K, long woff, int N, const float* bias, float* y, long ldy, int relu, float p, int site,
-                 const float* resid, const PP* outp, hipStream_t st, int drop_head_dim = 0) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A_hi = x.hi; a.A_lo = x.lo; a.lda_p = K; a.a_kmajor = 1;
-        const bool rows = rows_for(M, drop_head_dim);
-        if (rows) { a.B = P(woff); a.ldb = K; }
-        else { a.B_hi = w.wp.hi + woff; a.B_lo = w.wp.lo + woff; a.ldb_p = K; }
-        a.b_kmajor = 1;
-        a.C = y; a.ldc = ldy; a.M = M; a.N = N; a.K = K;
-        a.bias = bias; a.relu = relu;
-        a.drop_p = p; a.drop_site = site; a.rng = buf.rng;
-        a.resid = resid; a.ldr = ldy;
-        if (outp) { a.C_hi = outp->hi; a.C_lo = outp->lo; a.ldc_p = N; }
-        a.precision = prec3();
-        a.drop_head_dim = drop_head_dim;
-        return rows ? gemm_rows(a, st) : gemm(a, st);
-    }
-    // the backward pair of a decoder Linear y[B, Nout] = x[B, Kin] W^T + b in ONE launch (gemm_rows.hip: gemm_rows_bwd): dX = dY W with
-    // its epilogue (gate, per-head dropout, residual; fp32 and / or planes out) and dW = dY^T x, db = colsum(dY)
-    int wd_rows(const PP& dy, int B, int Nout, long woff, int Kin, float* dx, const PP* dxp, const float* gate, float gate_scale,
-                const float* resid, const PP& x, long gw, long gb, hipStream_t st, float drop_p = 0.f, int drop_site = 0, int drop_head_dim = 0) const {
-        if (!rows_for(B, drop_head_dim))       // the plane GEMM's gradient pair, as in the encoder
-            return wd_group(wgrad_p_args(dy, Nout, B, Nout, x, Kin, G(gw), G(gb)),
-                            dgrad_p_args(dy, Nout, B, Nout, woff, Kin, dx, gate, gate_scale, resid, dxp), 0, st);
-        slnlp_gemm_args d, g;
-        memset(&d, 0, sizeof(d));
-        memset(&g, 0, sizeof(g));
-        d.A_hi = dy.hi; d.A_lo = dy.lo; d.lda_p = Nout; d.a_kmajor = 1;
-        d.B = P(woff); d.ldb = Kin; d.b_kmajor = 0;
-        d.C = dx; d.ldc = Kin; d.M = B; d.N = Kin; d.K = Nout;
-        d.gate = gate; d.ldg = Kin; d.gate_scale = gate_scale;
-        d.resid = resid; d.ldr = Kin;
-        if (dxp) { d.C_hi = dxp->hi; d.C_lo = dxp->lo; d.ldc_p = Kin; }
-        d.drop_p = drop_p; d.drop_site = drop_site; d.rng = buf.rng; d.drop_head_dim = drop_head_dim;
-        d.precision = prec3();
-        g.A_hi = dy.hi; g.A_lo = dy.lo; g.lda_p = Nout; g.a_kmajor = 0;
-        g.B_hi = x.hi; g.B_lo = x.lo; g.ldb_p = Kin; g.b_kmajor = 0;
-        g.C = G(gw); g.ldc = Kin; g.M = Nout; g.N = Kin; g.K = B;
-        g.rowsum_a = G(gb);
-        g.precision = prec3();
-        return gemm_rows_bwd(d, g, st);
-    }
-    slnlp_gemm_args dgrad_p_args(const PP& dy, long ldy, int M, int Nout, long woff, int Kin, float* dx, const float* gate,
-                                 float gate_scale, const float* resid, const PP* outp) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A_hi = dy.hi; a.A_lo = dy.lo; a.lda_p = ldy; a.a_kmajor = 1;
-        a.B_hi = w.wp.hi + woff; a.B_lo = w.wp.lo + woff; a.ldb_p = Kin; a.b_kmajor = 0;
-        a.C = dx; a.ldc = Kin; a.M = M; a.N = Kin; a.K = Nout;
-        a.gate = gate; a.ldg = Kin; a.gate_scale = gate_scale;
-        a.resid = resid; a.ldr = Kin;
-        if (outp) { a.C_hi = outp->hi; a.C_lo = outp->lo; a.ldc_p = Kin; }
-        a.precision = prec3() == 3 ? dgrad_np : prec3();
-        return a;
-    }
-    int dgrad_p(const PP& dy, long ldy, int M, int Nout, long woff, int Kin, float* dx, const float* gate,
-                float gate_scale, const float* resid, const PP* outp, hipStream_t st) const {
-        return gemm(dgrad_p_args(dy, ldy, M, Nout, woff, Kin, dx, gate, gate_scale, resid, outp), st);
-    }
-    slnlp_gemm_args wgrad_p_args(const PP& dy, long ldy, int T, int Nout, const PP& x, int Kin, float* dW, float* db) const {
-        slnlp_gemm_args a;
-        memset(&a, 0, sizeof(a));
-        a.A_hi = dy.hi; a.A_lo = dy.lo; a.lda_p = ldy; a.a_kmajor = 0;
-        a.B_hi = x.hi; a.B_lo = x.lo; a.ldb_p = Kin; a.b_kmajor = 0;
-        a.C = dW; a.ldc = Kin; a.M = Nout; a.N = Kin; a.K = T;
-        a.rowsum_a = db;
-        a.precision = prec3() == 3 ? wgrad_np : prec3();
-        return a;
-    }
-    int wgrad_p(const PP& dy, long ldy, int T, int Nout, const PP& x, int Kin, float* dW, float* db, hipStream_t st) const {
-        return gemm(wgrad_p_args(dy, ldy, T, Nout, x, Kin, dW, db), st);
-    }
-    // weight gradient (split-K over the tokens) and data gradient of one dY in ONE launch: the wgrad's workgroups
-    // fill the CUs the dgrad leaves idle, and there is no cross-queue edge to pay for (measured 4-10 us each)
-    int wd_group(const slnlp_gemm_args& wg, const slnlp_gemm_args& dg, int which_scratch, hipStream_t st) const {
-        return gemm_planes_wd(wg, dg, w.gscr[which_scratch], w.gscr_bytes, st);      // (split factor, one launch or two: gemm_planes.hip)
+    // LayerNorm backward in front of a sub-layer's gradient pair: dx -> gA, and the pair's dY -- dx, dropout-masked when p > 0 -- as
+    // what the pair reads: planes dyp (`as_planes`), or fp32 (gA itself at p = 0, else the masked copy gB)
+    int ln_bwd_dy(bool as_planes, const float* dy, const float* y, long gamma, const float* stats, int rows, float* gA, float* gB, const PP& dyp,
+                  float p, int site, float* partial, int full_rows, hipStream_t st) const {
+        const PlaneOut none{}, out = as_planes ? dyp.out() : none;
+        return layernorm_bwd(dy, y, P(gamma), stats, rows, cfg.E, nullptr, gA, (p > 0.f && !as_planes) ? gB : nullptr, p, site, buf.rng,
+                             partial, nullptr, full_rows, st, p == 0.f ? out : none, p > 0.f ? out : none);
     }
     // ---- the encoder's weight gradients off the chain.  Backward is one dependent chain of launches, and a pair's launch ends with
     // its longest workgroup: at these shapes a weight-gradient slice, whose result nothing reads before the optimizer.  Where the
@@ -673,24 +519,23 @@ struct slnlp_tf_plan : PlanCore {
     // of all deferred weight gradients (plane_batch_*): throughput-sized tiles, a job's panels in one XCD's L2, the split factor --
     // hence every sum -- of the pair's launch.  Every operand is still intact then (each gradient buffer is written once per
     // step).  Under a lockstep recorder the pairs stay together: merged launches are throughput-sized already.
-    // Pair k (linear2, linear1, out_proj, in_proj: the order backward meets them) of encoder layer l at batch size B
-    void enc_pair(int l, int k, int B, float ik, slnlp_gemm_args* wg, slnlp_gemm_args* dg) const {
+    // Pair k (linear2, linear1, out_proj, in_proj: the order backward meets them) of encoder layer l at batch size B, after a forward
+    // with dropout last_p.  (Plane path: the sub-layer's GEMMs read planes only -- d h has no fp32 copy.)
+    void enc_pair(int l, int k, int B, slnlp_gemm_args* wg, slnlp_gemm_args* dg) const {
         const int E = cfg.E, F = cfg.F, M = cfg.S * B;
+        const float p = last_p;
         const EncP& q = L.enc[l];
         const EncA& a = w.enc[l];
-        if (k == 0) {
-            *wg = wgrad_p_args(a.d2p, E, M, E, a.hp, F, G(q.l2_w), G(q.l2_b));
-            *dg = dgrad_p_args(a.d2p, E, M, E, q.l2_w, F, nullptr, a.h, ik, nullptr, &a.ghp);
-        } else if (k == 1) {
-            *wg = wgrad_p_args(a.ghp, F, M, F, a.x1p, E, G(q.l1_w), G(q.l1_b));
-            *dg = dgrad_p_args(a.ghp, F, M, F, q.l1_w, E, a.gx1, nullptr, 0.f, a.gA2, nullptr);
-        } else if (k == 2) {
-            *wg = wgrad_p_args(a.d1p, E, M, E, a.ctxp, E, G(q.out_w), G(q.out_b));
-            *dg = dgrad_p_args(a.d1p, E, M, E, q.out_w, E, a.gctx, nullptr, 0.f, nullptr, nullptr);
-        } else {
-            *wg = wgrad_p_args(a.gqkvp, 3 * E, M, 3 * E, l > 0 ? w.enc[l - 1].x2p : w.x0p, E, G(q.in_w), G(q.in_b));
-            *dg = dgrad_p_args(a.gqkvp, 3 * E, M, 3 * E, q.in_w, E, a.gx0, nullptr, 0.f, a.gA1, nullptr);
-        }
+        if (k == 0)
+            linear_bwd_jobs(view(p > 0.f ? a.gB2 : a.gA2, a.d2p, E), q.l2_w, q.l2_b, view(a.h, a.hp, F), M, E, F, use_planes ? nullptr : a.gh,
+                            Epi().gated(a.h, 1.f / (1.f - p)).also(a.ghp), wg, dg);
+        else if (k == 1)
+            linear_bwd_jobs(view(a.gh, a.ghp, F), q.l1_w, q.l1_b, view(a.x1, a.x1p, E), M, F, E, a.gx1, Epi().plus(a.gA2), wg, dg);
+        else if (k == 2)
+            linear_bwd_jobs(view(p > 0.f ? a.gB1 : a.gA1, a.d1p, E), q.out_w, q.out_b, view(a.ctx, a.ctxp, E), M, E, E, a.gctx, Epi(), wg, dg);
+        else
+            linear_bwd_jobs(view(a.gqkv, a.gqkvp, 3 * E), q.in_w, q.in_b, l > 0 ? view(w.enc[l - 1].x2, w.enc[l - 1].x2p, E) : view(w.x0, w.x0p, E),
+                            M, 3 * E, E, a.gx0, Epi().plus(a.gA1), wg, dg);
     }
     PlaneBatch wbatch;                  // the deferred jobs of a backward at batch size wbatch_B (device copies: w.wb_tab, w.wb_map)
     std::vector<char> wb_deferred;      // [4 l + k]: the pair's weight gradient is a job of the batch
@@ -705,7 +550,7 @@ struct slnlp_tf_plan : PlanCore {
         for (int l = cfg.N - 1; l >= 0; --l)
             for (int k = 0; k < 4; ++k) {
                 slnlp_gemm_args wg, dg;
-                enc_pair(l, k, B, 1.f, &wg, &dg);
+                enc_pair(l, k, B, &wg, &dg);
                 const int n = gemm_planes_wd_defer(wg, dg);
                 if (n == 0) continue;
                 wb_deferred[4 * l + k] = 1;
@@ -728,10 +573,10 @@ struct slnlp_tf_plan : PlanCore {
     }
     bool wb_defers(int l, int k) const { return !recording() && !wb_deferred.empty() && wb_deferred[4 * l + k]; }
     // pair k of encoder layer l on the chain: the data gradient alone where the weight gradient is a job of the batch
-    int enc_pair_launch(int l, int k, int B, float ik, hipStream_t st) const {
+    int enc_pair_launch(int l, int k, int B, hipStream_t st) const {
         slnlp_gemm_args wg, dg;
-        enc_pair(l, k, B, ik, &wg, &dg);
-        return wb_defers(l, k) ? gemm(dg, st) : wd_group(wg, dg, 0, st);
+        enc_pair(l, k, B, &wg, &dg);
+        return launch_pair(wg, dg, wb_defers(l, k), st);
     }
     // zero padding of the activation planes is per batch size: re-zero when it changes (outside any capture)
     int prepare_planes(int B, hipStream_t st) override {
