@@ -241,6 +241,11 @@ def attn_self_fwd(qkv, ids, pad_idx, *, B, S, H, dh, causal=True, drop_p=0.0, dr
 def attn_self_bwd(qkv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None):
     _lib.require_gpu()
     dqkv = torch.empty_like(qkv)
+    if S > 64:      # the wave-per-row kernels keep dS between their row pass and their column pass
+        scratch = torch.empty(int(load().slnlp_attn_long_scratch_bytes(B, S, H)), dtype=torch.uint8, device=qkv.device)
+        check(load().slnlp_attn_self_bwd_long(ptr(qkv), ptr(probs), ptr(dctx), B, S, H, dh, ptr(dqkv), ptr(scratch), drop_p,
+                                              drop_site, ptr(rng), stream_ptr()), "attn_self_bwd_long")
+        return dqkv
     check(load().slnlp_attn_self_bwd(ptr(qkv), ptr(probs), ptr(dctx), B, S, H, dh, ptr(dqkv), drop_p, drop_site,
                                      ptr(rng), stream_ptr()), "attn_self_bwd")
     return dqkv
@@ -256,10 +261,12 @@ def attn_cross_fwd(q, kv, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None):
     return ctx, probs
 
 
-def attn_cross_bwd(q, kv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None):
+def attn_cross_bwd(q, kv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None, dkv=None):
+    """``kv`` / ``dkv`` may be column views of wider buffers (row strides ld_kv / ld_dkv); ``dkv`` None allocates it."""
     _lib.require_gpu()
     dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv)
+    if dkv is None:
+        dkv = torch.empty(kv.shape, dtype=torch.float32, device=kv.device)
     check(load().slnlp_attn_cross_bwd(ptr(q), ptr(kv), kv.stride(0), ptr(probs), ptr(dctx), B, S, H, dh, ptr(dq),
                                       ptr(dkv), dkv.stride(0), drop_p, drop_site, ptr(rng), stream_ptr()),
           "attn_cross_bwd")
@@ -434,6 +441,68 @@ def dropout_mask(R, C_, p, site, rng):
     out = torch.empty(R, C_, dtype=torch.float32, device=rng.device)
     check(load().slnlp_dropout_mask(ptr(out), R, C_, p, site, ptr(rng), stream_ptr()), "dropout_mask")
     return out
+
+
+def dir_struct(cls, **fields):
+    """One direction's argument struct of the recurrent entry points (``_lib.RnnCellDir``, ``RnnStepDir``, ``RnnLayerDir``,
+    ``RnnCellBwdDir``): tensors (views included) become their device pointers, None a null pointer, numbers stay."""
+    return cls(**{k: (v.data_ptr() if torch.is_tensor(v) else v) for k, v in fields.items()})
+
+
+def _dirs(cls, dirs):
+    assert len(dirs) in (1, 2) and all(isinstance(d, cls) for d in dirs)
+    return (cls * len(dirs))(*dirs)
+
+
+def rnn_cell_fwd(lstm, dirs, *, B, Hd, lengths=None, fill=0.0, ld_out=0, drop_p=0.0, drop_site=0, rng=None):
+    """One timestep of the point-wise cell for 1 or 2 directions (``dirs``: ``_lib.RnnCellDir``), in place on their buffers."""
+    _lib.require_gpu()
+    check(load().slnlp_rnn_cell_fwd(int(lstm), _dirs(_lib.RnnCellDir, dirs), len(dirs), B, Hd, ptr(lengths), fill, ld_out, drop_p,
+                                    drop_site, ptr(rng), stream_ptr()), "rnn_cell_fwd")
+
+
+def rnn_cell_bwd(lstm, dirs, *, B, Hd, lengths=None, ld_dout=0, drop_p=0.0, drop_site=0, rng=None):
+    """Backward of one timestep of the cell (``dirs``: ``_lib.RnnCellBwdDir``): writes dgx, dgh, carry, updates dc_state."""
+    _lib.require_gpu()
+    check(load().slnlp_rnn_cell_bwd(int(lstm), _dirs(_lib.RnnCellBwdDir, dirs), len(dirs), B, Hd, ptr(lengths), ld_dout, drop_p,
+                                    drop_site, ptr(rng), stream_ptr()), "rnn_cell_bwd")
+
+
+def rnn_step_fwd(lstm, dirs, *, B, Hd, lengths=None, fill=0.0, ld_out=0, drop_p=0.0, drop_site=0, rng=None, precision=3):
+    """Recurrent product + cell of one timestep in one launch (``dirs``: ``_lib.RnnStepDir``)."""
+    _lib.require_gpu()
+    check(load().slnlp_rnn_step_fwd(int(lstm), _dirs(_lib.RnnStepDir, dirs), len(dirs), B, Hd, ptr(lengths), fill, ld_out, drop_p,
+                                    drop_site, ptr(rng), precision, stream_ptr()), "rnn_step_fwd")
+
+
+def rnn_step_bwd(lstm, dirs, *, B, Hd, lengths=None, ld_dout=0, drop_p=0.0, drop_site=0, rng=None, precision=3):
+    """Recurrent data gradient of the step before + this step's cell backward in one launch (``dirs``: ``_lib.RnnStepBwdDir``)."""
+    _lib.require_gpu()
+    check(load().slnlp_rnn_step_bwd(int(lstm), _dirs(_lib.RnnStepBwdDir, dirs), len(dirs), B, Hd, ptr(lengths), ld_dout, drop_p,
+                                    drop_site, ptr(rng), precision, stream_ptr()), "rnn_step_bwd")
+
+
+def bahdanau_fwd(q, proj_key, value, w_energy, ids, pad_idx, *, B, S, Hd):
+    """-> (alphas [B, S], ctx [B, 2 Hd]); proj_key [S*B, Hd] / value [S*B, 2 Hd] rows time-major, ids int64 [B, S]."""
+    _lib.require_gpu()
+    alphas = torch.empty(B, S, dtype=torch.float32, device=q.device)
+    ctx = torch.empty(B, 2 * Hd, dtype=torch.float32, device=q.device)
+    check(load().slnlp_bahdanau_fwd(ptr(q), ptr(proj_key), ptr(value), ptr(w_energy), ptr(ids), ids.stride(0), pad_idx, B, S, Hd,
+                                    ptr(alphas), ptr(ctx), stream_ptr()), "bahdanau_fwd")
+    return alphas, ctx
+
+
+def bahdanau_bwd(q, proj_key, value, w_energy, alphas, dctx, *, B, S, Hd):
+    """-> (dq [B, Hd], dproj_key [S*B, Hd], dvalue [S*B, 2 Hd], dw_energy [Hd])"""
+    _lib.require_gpu()
+    dq = torch.empty_like(q)
+    dpk = torch.empty_like(proj_key)
+    dval = torch.empty_like(value)
+    part = torch.empty(B, Hd, dtype=torch.float32, device=q.device)
+    dwe = torch.empty(Hd, dtype=torch.float32, device=q.device)
+    check(load().slnlp_bahdanau_bwd(ptr(q), ptr(proj_key), ptr(value), ptr(w_energy), ptr(alphas), ptr(dctx), B, S, Hd, ptr(dq),
+                                    ptr(dpk), ptr(dval), ptr(part), ptr(dwe), stream_ptr()), "bahdanau_bwd")
+    return dq, dpk, dval, dwe
 
 
 def gather_batch(X, lengths, y, order, row0, B, out=None):

@@ -159,27 +159,37 @@ def _mha_ref(qkv, ids, pad, B, S, H, dh, causal, mask=None, p=0.0):
     return ctx, pr
 
 
-@pytest.mark.parametrize("B,S,H,dh", [(50, 48, 8, 64), (4, 12, 4, 8), (50, 48, 4, 32), (9, 64, 4, 256), (50, 48, 8, 16),
-                                      (3, 37, 2, 128), (5, 37, 3, 32), (6, 20, 2, 64), (2, 64, 2, 48)])
+_SELF_MASKED = [(50, 48, 8, 64), (4, 12, 4, 8), (50, 48, 4, 32), (9, 64, 4, 256), (50, 48, 8, 16), (3, 37, 2, 128), (5, 37, 3, 32),
+                (6, 20, 2, 64), (2, 64, 2, 48)]
+# causal = 0 and ids = NULL (no key-padding mask) at two of the shapes above
+_SELF_VARIANTS = [(shape, c, i) for shape in [(4, 12, 4, 8), (9, 64, 4, 256)] for c, i in [(False, True), (True, False), (False, False)]]
+
+
+@pytest.mark.parametrize("B,S,H,dh,causal,use_ids",
+                         [pytest.param(*s, True, True, id="-".join(map(str, s))) for s in _SELF_MASKED] +
+                         [pytest.param(*s, c, i, id="-".join(map(str, s)) + f"-causal{int(c)}-ids{int(i)}") for s, c, i in _SELF_VARIANTS])
 @pytest.mark.parametrize("p", [0.0, 0.2])
-def test_attn_self(ops, B, S, H, dh, p):
+def test_attn_self(ops, B, S, H, dh, causal, use_ids, p):
     E = H * dh
     qkv = rnd(S * B, 3 * E, seed=1).double().requires_grad_(True)
     lengths = torch.randint(max(1, S // 6), S + 1, (B,), generator=torch.Generator().manual_seed(3))
     ids = torch.full((B, S), 5, dtype=torch.long)
     ids[torch.arange(S)[None, :] >= lengths[:, None]] = 1
+    if not use_ids:
+        ids = None
     rng = ops.make_rng(seed=5, step=2)
     mask = ops.dropout_mask(B * H * S, S, p, 17, rng).cpu().double().view(B, H, S, S) if p > 0 else None
-    ctx_ref, pr_ref = _mha_ref(qkv, ids, 1, B, S, H, dh, True, mask, p)
+    ctx_ref, pr_ref = _mha_ref(qkv, ids, 1, B, S, H, dh, causal, mask, p)
     dctx = rnd(S * B, E, seed=2)
     ctx_ref.backward(dctx.double())
     qc = qkv.detach().float().cuda()
-    ctx, probs = ops.attn_self_fwd(qc, ids.cuda(), 1, B=B, S=S, H=H, dh=dh, causal=True, drop_p=p, drop_site=17, rng=rng)
+    ctx, probs = ops.attn_self_fwd(qc, None if ids is None else ids.cuda(), 1, B=B, S=S, H=H, dh=dh, causal=causal, drop_p=p, drop_site=17,
+                                   rng=rng)
     # split-bf16 MFMA (3 passes, ~2^-16 per product); head dims above 64 in chunks of 64
     e_p, e_c = rel(probs, pr_ref), rel(ctx, ctx_ref)
     dqkv = ops.attn_self_bwd(qc, probs, dctx.cuda(), B=B, S=S, H=H, dh=dh, drop_p=p, drop_site=17, rng=rng)
     e_g = rel(dqkv, qkv.grad)
-    print(f"attn_self B{B} S{S} H{H} dh{dh} p{p}: probs {e_p:.2e} ctx {e_c:.2e} dqkv {e_g:.2e}")
+    print(f"attn_self B{B} S{S} H{H} dh{dh} p{p} causal{int(causal)} ids{int(use_ids)}: probs {e_p:.2e} ctx {e_c:.2e} dqkv {e_g:.2e}")
     assert e_p < 5e-5 and e_c < 5e-5 and e_g < 1e-4
 
 
