@@ -319,6 +319,36 @@ int slnlp_clip_adam_step_groups(float* params, const float* grads, float* exp_av
 int slnlp_gather_batch(const int64_t* X, const int64_t* lengths, const int64_t* y, const int64_t* order, int64_t row0,
                        int B, int S, int64_t* X_out, int64_t* len_out, int64_t* y_out, void* stream);
 
+/* ------------------------------------------------------ class-balanced epochs --
+ * The visit order of a class-balanced train epoch (iterator_train__balance), drawn on the device straight into an order
+ * table (slnlp_gather_batch, slnlp_*_lockstep_set_order).  Labels y [n] in [0, n_classes); a class that is present, with n_c
+ * rows, keeps u_c of them and is visited t_c times: the reference's smoothed targets around the mean size u of the present
+ * classes, smooth(v) = round-half-even(u + ln v), u_c = min(n_c, smooth(n_c)), t_c = max(u_c, smooth(u_c)).  An epoch
+ * visits n_bal = sum t_c rows, the same number every epoch.
+ * Random words: Threefry-4x32, the dropout masks' 12 rounds, key (seed low word, seed high word, 0, 0), counter
+ * (index, epoch, stage, 0).  Of the output words X0..X3 a 64-bit key is X1 << 32 | X0, the over-sampling word is X0.
+ *   stage 0, index = row i: the rows of a class are ranked by (key, i) ascending; the u_c lowest ranks are kept,
+ *            kept_c[r] = the row of rank r;
+ *   stage 1, index = base_c + j: extra j in [0, t_c - u_c) of class c (base_c: the class's first slot) takes
+ *            kept_c[(X0 * u_c) >> 32];
+ *   stage 2, index = slot: the slots -- class after class in ascending id, each class's kept rows then its extras -- are
+ *            ranked by (key, slot) ascending; order_out[rank] = the slot's row.
+ * The result is a function of (y, seed, epoch) alone: no atomics, nothing depends on the grid or on timing.
+ * slnlp_balance_plan_create reads the labels from HOST memory and keeps the per-class tables (and the scratch of a draw) in
+ * device memory it owns; the upload is ordered on stream.  Errors (SLNLP_ERR_INVALID_ARG, with a message): null pointers,
+ * n < 1, a label outside [0, n_classes), n or n_bal above SLNLP_BALANCE_MAX_ROWS (the ranks are counted, which is quadratic).
+ * slnlp_balanced_order: two launches on stream, no host synchronisation, no allocation.  y_dev: the same labels on the
+ * device, read only for y_out [n_bal] = the labels in visit order (both may be NULL); epoch in [0, 2^32).  A plan serves one
+ * draw at a time (its scratch links the two launches): draws of one plan on several streams need an order between them. */
+#define SLNLP_BALANCE_MAX_ROWS 65536
+typedef struct slnlp_balance_plan slnlp_balance_plan;
+int slnlp_balance_plan_create(const int64_t* y_host, int64_t n, int n_classes, void* stream, slnlp_balance_plan** out);
+int64_t slnlp_balance_plan_rows(const slnlp_balance_plan* plan);          /* n_bal */
+void slnlp_balance_plan_destroy(slnlp_balance_plan* plan);
+int slnlp_balanced_order(const slnlp_balance_plan* plan, const int64_t* y_dev, uint64_t seed, int64_t epoch,
+                         int64_t* order_out /* [n_bal] */, int64_t* y_out /* [n_bal] or NULL: labels in visit order */,
+                         void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);
@@ -626,7 +656,9 @@ int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* group, float* const* exp_avg_s
 int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* group, const float* const* table, int n_steps, void* stream);
 /* per-fit visit order of one data slot (a shuffled epoch): order[f] = n_visit int64 row indices into fit f's dataset of that
  * slot, in device memory of the caller (kept alive while set); a NULL entry leaves that fit in dataset order, a NULL `order`
- * clears the setting for the slot.  n_visit (1 .. rows) is one number for the group.  From then on a step of that slot stages
+ * clears the setting for the slot.  n_visit is one number for the group: 1 .. rows, or -- when EVERY fit has a table (a
+ * class-balanced epoch visits rows more than once) -- any length up to 2^31 - 1, and the slot's logp[f] / loss[f] buffers then
+ * hold n_visit rows / ceil(n_visit / batch) losses (the caller's contract, like every pointer here).  From then on a step of that slot stages
  * row order[f][row0 + i] instead of row row0 + i -- ids, label and, for RNN fits, length -- with row0 + B <= n_visit, and
  * slnlp_tf_lockstep_epoch walks [0, n_visit).  Log-probs and batch losses keep landing at VISIT position (logp[f][row0 ..],
  * loss[f][step_index]).  Only the gather launch reads the table: no recorded program is dropped or re-recorded and

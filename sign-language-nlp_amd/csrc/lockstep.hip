@@ -477,8 +477,14 @@ static int ls_set_order(LockstepGroup* ls, int slot, const int64_t* const* order
         return 0;
     }
     SLNLP_CHECK_ARG(s.set, "lockstep_set_order: slot %d has no data", slot);
-    SLNLP_CHECK_ARG(n_visit >= 1 && n_visit <= s.rows, "lockstep_set_order: n_visit %ld outside 1..%ld (the slot's rows)", (long)n_visit,
-                    (long)s.rows);
+    // a fit without a table walks its rows as they lie, so a pass cannot be longer than the data; when every fit has one the
+    // tables may name rows more than once (a class-balanced epoch) and the pass is as long as they are -- the slot's output
+    // buffers then hold n_visit rows, the caller's contract (slnlp.h)
+    bool all_tables = true;
+    for (int f = 0; f < ls->K; ++f) all_tables = all_tables && order[f] != nullptr;
+    const int64_t longest = all_tables ? 0x7fffffffLL : s.rows;
+    SLNLP_CHECK_ARG(n_visit >= 1 && n_visit <= longest, "lockstep_set_order: n_visit %ld outside 1..%ld (the slot's rows%s)", (long)n_visit,
+                    (long)longest, all_tables ? ", or the tables' length when every fit has one" : "");
     if (hipMemcpyAsync(s.d_order, order, ls->K * sizeof(void*), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) {       // pageable host memory: as upload()
         set_error("lockstep_set_order: table upload failed: %s", hipGetErrorString(hipGetLastError()));

@@ -122,6 +122,10 @@ SIGNATURES = {
     "slnlp_clip_sgd_step_groups": (i32, [vp, vp, vp, i64, vp, vp, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_clip_adam_step_groups": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
+    "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
+    "slnlp_balance_plan_rows": (i64, [vp]),
+    "slnlp_balance_plan_destroy": (None, [vp]),
+    "slnlp_balanced_order": (i32, [vp, vp, C.c_uint64, i64, vp, vp, vp]),
     "slnlp_gather_batch": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
     "slnlp_rnn_cell_fwd": (i32, [i32, C.POINTER(RnnCellDir), i32, i32, i32, vp, f32, i64, f32, i32, vp, vp]),
     "slnlp_rnn_layer_fwd": (i32, [i32, C.POINTER(RnnLayerDir), i32, i32, i32, i32, vp, f32, i64, f32, i32, vp, i32, vp,

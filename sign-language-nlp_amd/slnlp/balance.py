@@ -12,6 +12,11 @@ class -- also one that keeps all its rows, whose rows come back permuted -- and 
 order; the over-sampler appends, per class, ``choice(rows of c, size=needed_c, replace=True)`` (the same stream as
 ``randint(0, n_c, needed_c)``) after all rows of the under-sampled set.  imbalanced-learn is not installed in the build
 image: tests/test_pipeline_cpu.py pins the order with indices worked out from that published algorithm by hand.
+
+Balancing a dataset here, before it is split, lets an over-sampled row land in a fit's train part AND in its valid part.
+``NeuralNetClassifier(iterator_train__balance=True)`` applies the same ``sampling_targets`` inside a fit instead: to the fit's
+own train split, redrawn every epoch on the device (slnlp/sampler.py, csrc/balance.hip).  This module's
+behaviour is unchanged.
 """
 import collections
 import math

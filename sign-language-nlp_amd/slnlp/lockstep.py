@@ -47,6 +47,7 @@ class LockstepGroup:
         self.handle = out
         check(self._fn("set_destroy_sync")(out, 0), "lockstep_set_destroy_sync")   # torch-allocated tables: see _engine.py
         self.data, self.logp, self.loss, self.rows, self.n_visit, self._orders = {}, {}, {}, {}, {}, {}
+        self.cap = {}                                    # rows the slot's output buffers hold (set_data: visit_rows)
 
     def _fn(self, name):                                 # a method, not a closure over self: no reference cycle
         return getattr(load(), f"slnlp_{self.kind}_lockstep_{name}")
@@ -65,17 +66,19 @@ class LockstepGroup:
 
     __del__ = close
 
-    def set_data(self, slot, Xs, ys, batch, lengths=None):
+    def set_data(self, slot, Xs, ys, batch, lengths=None, visit_rows=None):
         """Per-fit datasets of one slot (device int64 [rows, S] / [rows], the same number of rows for every fit; RNN fits also
         pass the sequence lengths [rows]).  Allocates the slot's output buffers: ``logp[slot][f]`` [rows, Vt] and
-        ``loss[slot][f]`` [ceil(rows / batch)]."""
+        ``loss[slot][f]`` [ceil(rows / batch)] -- for ``max(rows, visit_rows)`` rows when a pass will visit more rows than the
+        data has (class-balanced epochs: ``set_order`` with a table per fit)."""
         rows = int(Xs[0].shape[0])
         assert len(Xs) == len(ys) == self.K and all(x.shape[0] == rows and x.is_contiguous() for x in Xs)
         Vt = self.engines[0].cfg.Vt
-        nb = (rows + batch - 1) // batch
-        self.logp[slot] = [torch.empty(rows, Vt, dtype=torch.float32, device=self.device) for _ in range(self.K)]
+        cap = max(rows, int(visit_rows or 0))
+        nb = (cap + batch - 1) // batch
+        self.logp[slot] = [torch.empty(cap, Vt, dtype=torch.float32, device=self.device) for _ in range(self.K)]
         self.loss[slot] = [torch.zeros(nb, dtype=torch.float32, device=self.device) for _ in range(self.K)]
-        self.rows[slot] = rows
+        self.rows[slot], self.cap[slot] = rows, cap
         self.n_visit.pop(slot, None)                     # the C side drops the slot's order with its old data
         self._orders.pop(slot, None)
         if self.kind == "rnn":
@@ -132,6 +135,10 @@ class LockstepGroup:
         n = int(given[0].numel()) if n_visit is None else int(n_visit)
         assert len(orders) == self.K and all(t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n and t.device == self.device
                                              for t in given), "lockstep: one int64 device tensor [n_visit] (or None) per fit"
+        # a pass longer than the data (tables that name rows more than once) writes n rows of log-probs: set_data(visit_rows=)
+        # (only when every fit has a table: otherwise the library itself refuses a pass longer than the data)
+        if len(given) == self.K and slot in self.cap and n > self.cap[slot]:
+            raise ValueError(f"lockstep: n_visit {n} beyond the {self.cap[slot]} rows of the slot's output buffers")
         arr = (C.c_void_p * self.K)(*[None if t is None else ptr(t) for t in orders])
         check(self._fn("set_order")(self.handle, slot, arr, n, self._sp()), f"{self.kind}_lockstep_set_order")
         self._orders[slot] = list(orders)                # keep the tensors alive: the gather launch reads them
@@ -163,7 +170,7 @@ class LockstepGroup:
         rows = self.n_visit.get(slot, self.rows[slot])
         sizes = [min(batch, rows - r) for r in range(0, rows, batch)]
         per_batch, logp = self.loss[slot][f], self.logp[slot][f]
-        if rows != self.rows[slot]:
+        if rows != self.cap[slot]:
             per_batch, logp = per_batch[:len(sizes)], logp[:rows]
         per_batch = per_batch.float().cpu()
         w = torch.tensor(sizes, dtype=torch.float32)
@@ -242,7 +249,7 @@ def _fit_lockstep_gated(nets, datasets):
                     # weight_decay: each plan's own (NeuralNetClassifier.initialize set its update kind), not the group's
                     group.set_adam([nets[i].module_.adam_second_moment() for i in active], adam[1], adam[2], 0.0)
                 group.set_data(TRAIN, [runs[i].Xtr for i in active], [runs[i].ytr for i in active], r0.bs,
-                               [runs[i].Ltr for i in active])
+                               [runs[i].Ltr for i in active], visit_rows=r0.n_visit)
                 if r0.va is not None:
                     group.set_data(VALID, [runs[i].Xva for i in active], [runs[i].yva for i in active], r0.bs,
                                    [runs[i].Lva for i in active])
@@ -272,7 +279,8 @@ def _fit_lockstep_gated(nets, datasets):
                         nets[active[j]].module_.forget_group_lrs()      # the device writes them from here on
                 group.set_lr_tables(per_fit, n_steps=len(tables[pb[0]]))
             sh = [j for j, o in enumerate(orders) if o is not None]
-            if sh or r0.n_visit != len(r0.tr):
+            bal = [j for j, i in enumerate(active) if runs[i].balance is not None]
+            if sh or bal or r0.n_visit != len(r0.tr):
                 # the orders go to the device the same way: ONE [fits, 2, n_visit] tensor per epoch -- each shuffled fit's order and
                 # its labels in visit order (what train scoring pairs the log-probs with) -- and every step's gather launch stages
                 # the rows its fit's table names; unshuffled fits of the group keep dataset order (no table), and with drop_last
@@ -283,6 +291,8 @@ def _fit_lockstep_gated(nets, datasets):
                     for r, j in enumerate(sh):
                         per_fit[j] = dev_ord[r, 0]
                         runs[active[j]].set_visit(dev_ord[r, 0], dev_ord[r, 1])
+                for j in bal:                           # balanced fits: order() drew the table on the device, nothing to upload
+                    per_fit[j] = runs[active[j]].order_dev
                 group.set_order(TRAIN, per_fit, r0.n_visit)
             t_epoch = time.perf_counter()
             group.epoch(TRAIN, r0.bs, True, r0.momentum, r0.max_norm)
@@ -357,7 +367,9 @@ def fit_and_score_group(estimator_factory, params_list, trains, tests, scoring="
             net.initialize()
         nets.append(net)
     if not all(lockstep_supported(n) for n in nets) or len({type(n.module_) for n in nets}) != 1 or len({_adam_key(n) for n in nets}) != 1 or \
-            len({len(t) for t in trains}) != 1 or len({len(t) for t in tests}) != 1:
+            len({len(t) for t in trains}) != 1 or len({len(t) for t in tests}) != 1 or \
+            (any(n._iterator_train_balance() for n in nets) and len({n._epoch_rows(t) for n, t in zip(nets, trains)}) != 1):
+        # (the last one: a balanced epoch's length follows the fold's labels, and a group shares its batch count)
         del nets
         # concurrent=True: no hipGraph capture -- other host threads may be launching on the device's shared stream
         return [default_fit_and_score(estimator_factory, p, tr, te, scoring, seed=s, concurrent=True)

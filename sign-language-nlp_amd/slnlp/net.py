@@ -12,6 +12,8 @@ semantics:
 * internal 80/20 stratified split, first fold of ``StratifiedKFold(5)`` (skorch ``CVSplit(5)``);
 * batches in dataset order (``shuffle`` is commented out, helper.py:75-76), or -- ``iterator_train__shuffle=True`` -- in the
   order torch's ``RandomSampler`` draws per epoch (slnlp/sampler.py); ``iterator_train__drop_last`` drops the short last batch;
+  ``iterator_train__balance=True`` makes every train epoch a class-balanced resample of the fit's own train split, drawn on
+  the device (csrc/balance.hip) -- the valid split is never touched, and ``iterator_train__shuffle`` has nothing left to do;
 * per batch: forward -> CrossEntropyLoss(ignore_index=pad) -> backward ->
   clip_grad_norm_(gradient_clip_value) -> SGD(momentum)  == ONE hipGraph replay;
 * per epoch: valid pass, ``EpochScoring`` metrics for train/valid, ``lr`` scoring,
@@ -346,7 +348,25 @@ class _FitRun:
             raise ValueError(f"iterator_train__drop_last=True with {len(self.tr)} train rows and batch_size {self.bs}: no full batch, "
                              "nothing to train on")
         self.sampler = None
-        if self.shuffle:
+        # iterator_train__balance: a class-balanced resample of the train rows per epoch, drawn on the device into the order
+        # table (slnlp_balanced_order).  The plan holds the class tables of THIS fit's train labels; the epoch length -- the same
+        # every epoch -- is the plan's.  The draw permutes, so the shuffling sampler is not built beside it.
+        self.balance = None
+        if net._iterator_train_balance():
+            self.balance = ops.BalancePlan(self.tr.y, max(len(net.classes_), int(self.tr.y.max()) + 1))
+            self.n_visit = sampler.n_visit(self.balance.rows, self.bs, self.drop_last)
+            if self.n_visit < 1:
+                raise ValueError(f"iterator_train__drop_last=True with {self.balance.rows} balanced train rows and batch_size {self.bs}: "
+                                 "no full batch, nothing to train on")
+            # the draw is a function of (seed, epoch number): the seed rides the epoch rows, a resumed fit needs nothing else
+            seed = sampler.seed_of(net.history, "balance_seed")
+            if seed is None:                                 # (balancing switched on after initialize(): drawn now)
+                seed = net.balance_seed_ if getattr(net, "balance_seed_", None) is not None else sampler.draw_seed()
+            net.balance_seed_ = seed
+            dev = self.ytr.device
+            self._bal_out = (torch.empty(self.balance.rows, dtype=torch.int64, device=dev),
+                             torch.empty(self.balance.rows, dtype=torch.int64, device=dev))
+        elif self.shuffle:
             # the order's position is a function of the history, like a schedule's: the seed rides the epoch rows
             seed = sampler.seed_from_history(net.history)
             if seed is None:                                 # (shuffling switched on after initialize(): drawn now)
@@ -373,6 +393,11 @@ class _FitRun:
         per epoch, before any of its work is queued, next to ``lr_table``."""
         self.epoch_order = self.sampler.next_epoch() if self.sampler is not None else None
         self.order_dev = self.y_visit_dev = None
+        if self.balance is not None:
+            # a balanced epoch's order never exists on the host: drawn on the fit's stream, in front of the epoch's work, into
+            # the run's two device tables (order, labels in visit order); with drop_last the epoch visits their full batches
+            order, y_visit = self.balance.order(self.ytr, self.net.balance_seed_, len(self.net.history), out=self._bal_out)
+            self.set_visit(order[:self.n_visit], y_visit[:self.n_visit])
         return self.epoch_order
 
     def visit_table(self):
@@ -389,6 +414,9 @@ class _FitRun:
         """(device, host) labels of the rows the epoch's train log-probs belong to, in visit order."""
         if self.epoch_order is not None:
             return self.y_visit_dev, self.tr.y[self.epoch_order]
+        if self.balance is not None:
+            # the one device-to-host copy a balanced epoch adds, taken after the epoch's synchronisation point
+            return self.y_visit_dev, self.y_visit_dev.cpu().numpy()
         if self.n_visit != len(self.tr):
             return self.ytr[:self.n_visit], self.tr.y[:self.n_visit]
         return self.ytr, self.tr.y
@@ -406,6 +434,8 @@ class _FitRun:
                "batches": [{"train_loss": l, "train_batch_size": n} for l, n in tr_batches]}   # skorch history layout
         if self.sampler is not None:
             row["shuffle_seed"] = self.sampler.seed          # a resumed fit rebuilds the order from it (slnlp/sampler.py)
+        if self.balance is not None:
+            row["balance_seed"] = net.balance_seed_          # with the epoch number, all a resumed fit needs to go on drawing
         if self.schedule is not None and self.schedule.per_batch:
             for b, lr in zip(row["batches"], self.epoch_lrs):
                 b["event_lr"] = lr[0] if isinstance(lr, list) else lr     # the rate this batch used (param groups: group 0's)
@@ -562,11 +592,30 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             out.append(bool(v))
         return tuple(out)
 
+    def _iterator_train_balance(self):
+        """``iterator_train__balance``: class-balanced train epochs drawn on the device (slnlp/sampler.py); default False."""
+        v = self._sub("iterator_train").get(sampler.BALANCE, False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"iterator_train__{sampler.BALANCE}={v!r}: expected True or False")
+        return bool(v)
+
+    def _epoch_rows(self, ds):
+        """Rows a train epoch on ``ds`` visits before drop_last: the train split's, or a balanced epoch's."""
+        y = ds.y[self._train_split(ds)[0]]
+        return sampler.balanced_rows(y) if self._iterator_train_balance() else len(y)
+
+    def _draw_iterator_seeds(self, shuffle, balance):
+        """``shuffle_seed_`` / ``balance_seed_``: each drawn from torch's global CPU generator only when its option is on (None
+        otherwise), the shuffle seed first -- a configuration without the option consumes what it always did."""
+        self.shuffle_seed_ = sampler.draw_seed() if shuffle else None
+        self.balance_seed_ = sampler.draw_seed() if balance else None
+
     def initialize(self):
         ok, pairs = optimizer_kwargs(self._sub("optimizer"))
         if not pairs:
             schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
         shuffle, _ = self._iterator_train()
+        balance = self._iterator_train_balance()
         dev = torch.device(self.device)
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("slnlp.net: device %r -- the HIP path is the only compute path (no CPU fallback)" % (self.device,))
@@ -612,7 +661,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         self.history = []
         # the seed of the shuffled order, drawn the way RandomSampler draws one without a generator -- AFTER the module's
         # weights and only when shuffling is on, so the initial weights of every other configuration keep their bits
-        self.shuffle_seed_ = sampler.draw_seed() if shuffle else None
+        self._draw_iterator_seeds(shuffle, balance)
         self.initialized_ = True
         return self
 
@@ -659,6 +708,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 self.module_.train()
                 lrs, order = run.lr_table(), run.order()
                 if order is not None:                       # one upload per epoch: the order and the labels in visit order
+                    # (a balanced epoch has no host order: run.order() drew its tables on the device)
                     run.set_visit(*torch.from_numpy(run.visit_table()).to(run.Xtr.device))
                 tr = self._run_epoch(run.Xtr, run.Ltr, run.ytr, run.bs, True, run.momentum, run.max_norm, lrs=lrs,
                                      order=run.order_dev, n_visit=run.n_visit)
@@ -903,4 +953,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             seed = sampler.seed_from_history(self.history)
             if seed is not None:                         # the resumed fit continues the checkpoint's order (slnlp/sampler.py)
                 self.shuffle_seed_ = seed
+            seed = sampler.seed_of(self.history, "balance_seed")
+            if seed is not None:                         # ... and the checkpoint's balanced draws, at epoch len(history)
+                self.balance_seed_ = seed
         return self

@@ -530,3 +530,44 @@ def gather_batch(X, lengths, y, order, row0, B, out=None):
     check(load().slnlp_gather_batch(ptr(X), ptr(lengths), ptr(y), ptr(order), row0, B, S, ptr(Xo), ptr(Lo), ptr(yo), stream_ptr()),
           "gather_batch")
     return Xo[:B], (None if Lo is None else Lo[:B]), yo[:B]
+
+
+class BalancePlan:
+    """The per-class tables of a class-balanced epoch draw over the labels ``y`` (host int64 [n], values in
+    ``[0, n_classes)``), in device memory the handle owns (``slnlp_balance_plan_create``).  ``rows``: the ``n_bal`` rows every
+    epoch visits.  ``order(y_dev, seed, epoch)`` draws one epoch's visit order on the current stream: two launches, no host
+    synchronisation, no upload.  A plan serves one draw at a time (include/slnlp.h)."""
+
+    def __init__(self, y, n_classes):
+        import ctypes as C
+        import numpy as np
+        _lib.require_gpu()
+        y = np.ascontiguousarray(y, dtype=np.int64)
+        if y.ndim != 1:
+            raise ValueError(f"BalancePlan: labels of shape {y.shape}, expected one dimension")
+        self.n, self.handle = int(y.size), C.c_void_p()
+        check(load().slnlp_balance_plan_create(y.ctypes.data, self.n, int(n_classes), stream_ptr(), C.byref(self.handle)),
+              "balance_plan_create")
+        self.rows = int(load().slnlp_balance_plan_rows(self.handle))
+
+    def order(self, y_dev, seed, epoch, out=None, want_labels=True):
+        """-> (order int64 [rows], labels in visit order int64 [rows] or None), device tensors; ``out``: the pair to fill."""
+        dev = y_dev.device
+        assert y_dev.is_cuda and y_dev.dtype == torch.int64 and y_dev.is_contiguous() and y_dev.numel() == self.n, \
+            "BalancePlan.order: the plan's labels as a contiguous int64 device tensor"
+        order, y_out = out if out is not None else (torch.empty(self.rows, dtype=torch.int64, device=dev),
+                                                    torch.empty(self.rows, dtype=torch.int64, device=dev) if want_labels else None)
+        for t in (order, y_out):
+            assert t is None or (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == self.rows)
+        check(load().slnlp_balanced_order(self.handle, ptr(y_dev), int(seed) % (1 << 64), int(epoch), ptr(order), ptr(y_out), stream_ptr()),
+              "balanced_order")
+        return order, y_out
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                load().slnlp_balance_plan_destroy(h)
+            except Exception:                            # interpreter shutdown: the module globals are already gone
+                pass
+            self.handle = None

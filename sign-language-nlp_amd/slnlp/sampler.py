@@ -7,6 +7,13 @@ generator is restated here.  The fit loop asks for a whole epoch's order ahead o
 lockstep unit runs the epoch without coming back to the host: the order travels to the device as a table (slnlp.lockstep),
 and every other path stages its batches through the same table (``slnlp_gather_batch``).
 
+``iterator_train__balance=True`` replaces that order by a class-balanced resample of the fit's own train rows, drawn afresh
+every epoch ON THE DEVICE (``slnlp_balanced_order``, csrc/balance.hip; targets: ``slnlp.balance.sampling_targets``) straight into
+the same table: the epoch then visits ``balanced_rows(y)`` rows, some of them more than once, and nothing is uploaded.  The draw
+is a function of (labels, ``balance_seed``, epoch number), so a resumed fit needs no fast-forward; it already permutes, which
+leaves ``iterator_train__shuffle`` nothing to do beside it (accepted, no effect).  ``HONOURED`` keeps naming the two keys this
+module draws for on the host; ``BALANCE`` is the third honoured key.
+
 As for schedules (slnlp/schedule.py), the position is a function of the fit's history: a new fit run builds the sampler from
 the seed and draws the epochs the history accounts for (``fast_forward``), so a resumed fit needs no extra checkpoint file --
 the seed rides every epoch row of a shuffled fit (``"shuffle_seed"``).
@@ -31,6 +38,25 @@ def seed_from_history(history):
         if row.get("shuffle_seed") is not None:
             return int(row["shuffle_seed"])
     return None
+
+
+BALANCE = "balance"
+
+
+def seed_of(history, key):
+    """The ``key`` ("shuffle_seed" / "balance_seed") of the last epoch row that carries one, or None."""
+    for row in reversed(history or []):
+        if row.get(key) is not None:
+            return int(row[key])
+    return None
+
+
+def balanced_rows(y):
+    """Rows a class-balanced epoch over the labels ``y`` visits: the sum of the over-sampling targets (what
+    ``slnlp_balance_plan_rows`` returns for the same labels)."""
+    import collections
+    from .balance import sampling_targets
+    return int(sum(sampling_targets(dict(collections.Counter(np.asarray(y).tolist())))[1].values()))
 
 
 def n_visit(n, batch_size, drop_last=False):
