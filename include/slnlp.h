@@ -309,6 +309,24 @@ int slnlp_clip_adam_step_groups(float* params, const float* grads, float* exp_av
                                 float beta2, float eps, int decoupled, float max_norm, float* partials /* [1024] scratch */,
                                 float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream);
 
+/* ---------------------------------------------------------- weight averaging --
+ * A running average of a parameter arena, kept on the device: torch.optim.swa_utils.AveragedModel without the host.
+ * slnlp_average_step feeds `params` (n floats, a multiple of 4; 16-byte aligned, like avg) into `avg`.  count[0] is a device
+ * float, the number of models averaged so far; with c its value BEFORE the call:
+ *   c == 0            avg = params, bit for bit
+ *   SLNLP_AVG_SWA     avg += (params - avg) / (c + 1)          AveragedModel's default avg_fn
+ *   SLNLP_AVG_EMA     avg += (params - avg) * (1 - decay)      get_ema_multi_avg_fn(decay), 0 < decay < 1
+ * and count[0] = c + 1 afterwards (its own one-thread launch behind the update, so every block read the same c).  Floats
+ * [skip_begin, skip_end) (multiples of 4; empty: none) are copied, never averaged: a parameter torch never steps stays equal to
+ * the model's.  Two launches, no host wait; capturable.
+ * slnlp_swap_arenas exchanges two arenas of n floats in place, in one launch; two swaps restore every bit.  After a swap into
+ * a plan's parameter arena tell the plan (slnlp_tf_params_changed). */
+#define SLNLP_AVG_SWA 0
+#define SLNLP_AVG_EMA 1
+int slnlp_average_step(float* avg, const float* params, int64_t n, float* count, int kind, float decay, int64_t skip_begin,
+                       int64_t skip_end, void* stream);
+int slnlp_swap_arenas(float* a, float* b, int64_t n, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.
@@ -567,6 +585,11 @@ int slnlp_tf_set_update(slnlp_tf_plan* plan, int kind, float dampening, float we
  * the one-group update again.  Drops the captured graphs and makes a lockstep group re-record, as slnlp_tf_set_update. */
 int slnlp_tf_set_param_groups(slnlp_tf_plan* plan, int n_segments, const int64_t* seg_begin, const int32_t* seg_group,
                               int n_groups, const float* weight_decay, const float* lr_dev, void* stream);
+/* Weight averaging riding the train step: with a non-NULL avg (arena-shaped, the caller's) every update of the plan -- slnlp_tf_optim,
+ * slnlp_tf_optim_adam, slnlp_tf_train_step, a captured graph, a recorded lockstep program -- is followed by slnlp_average_step's
+ * two launches on (avg, the plan's arena, count, kind, decay); the update kernels themselves are untouched.  NULL removes them.
+ * A call that changes the setting drops the captured graphs and makes a lockstep group re-record, as slnlp_tf_set_update. */
+int slnlp_tf_set_averaging(slnlp_tf_plan* plan, float* avg, float* count, int kind, float decay);
 /* Where backward forms the gradient with respect to the encoder memory (and the cross-attention value biases' gradients).
  * on (default): one launch for all decoder layers behind the decoder's layer loop -- nothing on that chain reads the sum;
  * off: a launch per layer inside the loop, each adding onto the sum.  Same bits either way (the same fp32 operations in the
@@ -665,6 +688,11 @@ int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* group, const float* const*
  * num_launches does not change.  The indices are the caller's contract.  set_data on the slot clears its order.  The pointer
  * table's upload is ordered on `stream`, as set_lr_table's. */
 int slnlp_tf_lockstep_set_order(slnlp_tf_lockstep* group, int slot, const int64_t* const* order, int64_t n_visit, void* stream);
+/* weight averaging for the group's train steps (slnlp_tf_set_averaging for K fits): avg[f] / count[f] per fit, one (kind, decay)
+ * for the group.  The two launches run once per step over the K arenas; a fit whose avg[f] is NULL is not averaging yet and its
+ * part of the launch does nothing.  While set, the group's setting stands in for the plans' own.  avg == NULL: off.  A call that
+ * changes something drops the recorded programs (re-recorded by the next step); num_launches of a train step grows by 2. */
+int slnlp_tf_lockstep_set_averaging(slnlp_tf_lockstep* group, float* const* avg, float* const* count, int kind, float decay);
 int slnlp_tf_lockstep_set_destroy_sync(slnlp_tf_lockstep* group, int on);   /* as slnlp_tf_set_destroy_sync, for the group's tables */
 
 
@@ -719,6 +747,8 @@ int slnlp_rnn_set_update(slnlp_rnn_plan* plan, int kind, float dampening, float 
 /* as slnlp_tf_set_param_groups */
 int slnlp_rnn_set_param_groups(slnlp_rnn_plan* plan, int n_segments, const int64_t* seg_begin, const int32_t* seg_group,
                                int n_groups, const float* weight_decay, const float* lr_dev, void* stream);
+/* as slnlp_tf_set_averaging; the pre_output_layer (never stepped) is copied into the average, not averaged */
+int slnlp_rnn_set_averaging(slnlp_rnn_plan* plan, float* avg, float* count, int kind, float decay);
 int slnlp_rnn_train_step(slnlp_rnn_plan* plan, const int64_t* X, const int64_t* y, const int64_t* lengths, int B,
                          float momentum, float max_norm, float* logp, void* stream);
 int slnlp_rnn_graph_capture_train(slnlp_rnn_plan* plan, const int64_t* X, const int64_t* y, const int64_t* lengths,
@@ -749,6 +779,7 @@ int slnlp_rnn_lockstep_set_adam(slnlp_rnn_lockstep* group, float* const* exp_avg
                                 float weight_decay);
 int slnlp_rnn_lockstep_set_lr_table(slnlp_rnn_lockstep* group, const float* const* table, int n_steps, void* stream);
 int slnlp_rnn_lockstep_set_order(slnlp_rnn_lockstep* group, int slot, const int64_t* const* order, int64_t n_visit, void* stream);
+int slnlp_rnn_lockstep_set_averaging(slnlp_rnn_lockstep* group, float* const* avg, float* const* count, int kind, float decay);
 int slnlp_rnn_lockstep_set_destroy_sync(slnlp_rnn_lockstep* group, int on);
 
 #ifdef __cplusplus

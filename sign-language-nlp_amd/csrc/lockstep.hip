@@ -172,6 +172,12 @@ struct LockstepGroup {
     bool use_adam = false;
     LsAdam adam{};
     std::vector<float*> v2;                         // per-fit exp_avg_sq arenas (device, caller-owned)
+    // slnlp_*_lockstep_set_averaging: the group's train programs end in the averaging launches (average.hip), one launch over the K
+    // arenas; a fit whose entry is null is not averaging yet (its part of the launch returns at once)
+    bool use_avg = false;
+    std::vector<float*> avg, avg_count;             // per-fit accumulators and their counts (device, caller-owned)
+    int avg_kind = 0;
+    float avg_decay = 0.f;
 
     void* take(size_t bytes) {
         ws_used = (ws_used + 255) & ~(size_t)255;
@@ -542,10 +548,13 @@ static int ls_step(LockstepGroup* ls, int slot, int64_t row0, int B, int step_in
         for (int f = 0; f < ls->K && !rc; ++f) {
             PlanCore* fit = ls->fits[f];
             fit->ls_logp = s.logp[f]; fit->ls_loss = s.loss[f]; fit->ls_dyn = ls->dyn;
+            const PlanCore::Averaging own = fit->averaging;         // the group's setting stands in for the plan's while it records
+            if (ls->use_avg) fit->averaging = PlanCore::Averaging{ls->avg[f], ls->avg_count[f], ls->avg_kind, ls->avg_decay, true};
             set_recorder(&recs[f]);
             rc = fit->record(ls->Xst[f], ls->yst[f], ls->Lst[f], B, train, momentum, max_norm, ls->use_adam ? &ls->adam : nullptr,
                              ls->use_adam ? ls->v2[f] : nullptr, st);
             set_recorder(nullptr);
+            fit->averaging = own;
         }
         for (PlanCore* f : ls->fits) f->opts.force_groups = false;      // a solo step of such a plan takes its own kernel again
         if (rc) return rc;
@@ -598,6 +607,37 @@ static int ls_set_adam(LockstepGroup* ls, float* const* exp_avg_sq, float beta1,
     ls->have_opt = false;
     // (the dropped train programs' tables stay in the bump-allocated workspace until every program is gone -- set_data on the
     //  last slot hands the space back; set_adam is called once per group, before its first train epoch, when there is nothing to drop)
+    return 0;
+}
+
+// Train steps feed a running average of every fit's arena from now on (what slnlp_*_set_averaging does for one plan): avg[f] /
+// count[f] per fit, a null avg[f] for a fit that is not averaging yet, one (kind, decay) for the group; avg == nullptr: no averaging.
+// A call that changes something drops every recorded program and hands the table space back before the next step, as a
+// settings change of a fit does (the accumulators' pointers ride the recorded argument packs).
+static int ls_set_averaging(LockstepGroup* ls, float* const* avg, float* const* count, int kind, float decay) {
+    SLNLP_CHECK_ARG(ls, "lockstep_set_averaging: null group");
+    std::vector<float*> a(ls->K, nullptr), c(ls->K, nullptr);
+    bool on = false;
+    if (avg) {
+        SLNLP_CHECK_ARG(count, "lockstep_set_averaging: averaging needs the device counts");
+        SLNLP_CHECK_ARG(kind == SLNLP_AVG_SWA || (kind == SLNLP_AVG_EMA && decay > 0.f && decay < 1.f),
+                        "lockstep_set_averaging: kind %d / decay %g (SLNLP_AVG_SWA, or SLNLP_AVG_EMA with 0 < decay < 1)", kind, decay);
+        if (kind == SLNLP_AVG_SWA) decay = 0.f;
+        for (int f = 0; f < ls->K; ++f) {
+            if (!avg[f]) continue;
+            const PlanCore* fit = ls->fits[f];
+            SLNLP_CHECK_ARG(count[f], "lockstep_set_averaging: null count for fit %d", f);
+            SLNLP_CHECK_ARG(((uintptr_t)avg[f] & 15) == 0 && (avg[f] + fit->arena <= fit->buf.params || fit->buf.params + fit->arena <= avg[f]),
+                            "lockstep_set_averaging: avg of fit %d must be a 16-byte aligned arena of its own", f);
+            a[f] = avg[f]; c[f] = count[f];
+            on = true;
+        }
+    }
+    if (!on) kind = 0, decay = 0.f;
+    if (on == ls->use_avg && (!on || (a == ls->avg && c == ls->avg_count && kind == ls->avg_kind && decay == ls->avg_decay))) return 0;
+    ls->use_avg = on;
+    ls->avg = a; ls->avg_count = c; ls->avg_kind = kind; ls->avg_decay = decay;
+    ls->rec_gen.clear();            // the next step finds its programs stale: drops them, reclaims their tables, records again
     return 0;
 }
 
@@ -683,6 +723,9 @@ int slnlp_tf_lockstep_num_launches(slnlp_tf_lockstep* ls, int slot, int B, int t
 int slnlp_tf_lockstep_set_adam(slnlp_tf_lockstep* ls, float* const* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay) {
     return ls_set_adam(ls, exp_avg_sq, beta1, beta2, eps, weight_decay);
 }
+int slnlp_tf_lockstep_set_averaging(slnlp_tf_lockstep* ls, float* const* avg, float* const* count, int kind, float decay) {
+    return ls_set_averaging(ls, avg, count, kind, decay);
+}
 int slnlp_tf_lockstep_set_lr_table(slnlp_tf_lockstep* ls, const float* const* table, int n_steps, void* stream) {
     return ls_set_lr_table(ls, table, n_steps, (hipStream_t)stream);
 }
@@ -743,6 +786,9 @@ int slnlp_rnn_lockstep_epoch(slnlp_rnn_lockstep* ls, int slot, int batch, int tr
 int slnlp_rnn_lockstep_num_launches(slnlp_rnn_lockstep* ls, int slot, int B, int train) { return ls_num_launches(ls, slot, B, train); }
 int slnlp_rnn_lockstep_set_adam(slnlp_rnn_lockstep* ls, float* const* exp_avg_sq, float beta1, float beta2, float eps, float weight_decay) {
     return ls_set_adam(ls, exp_avg_sq, beta1, beta2, eps, weight_decay);
+}
+int slnlp_rnn_lockstep_set_averaging(slnlp_rnn_lockstep* ls, float* const* avg, float* const* count, int kind, float decay) {
+    return ls_set_averaging(ls, avg, count, kind, decay);
 }
 int slnlp_rnn_lockstep_set_lr_table(slnlp_rnn_lockstep* ls, const float* const* table, int n_steps, void* stream) {
     return ls_set_lr_table(ls, table, n_steps, (hipStream_t)stream);

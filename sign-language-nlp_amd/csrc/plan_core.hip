@@ -14,6 +14,7 @@ int PlanCore::update_sgd(float momentum, float max_norm, hipStream_t st) {
     const UpdateRanges r = update_ranges();
     SLNLP_TRY(clip_sgd_step(buf.params, buf.grads, buf.momentum, arena, pg, lr, momentum, max_norm, opt_partials, buf.scalars + 1,
                             buf.rng, st, r.wp, r.wp_begin, r.wp_end, opts.sgd(buf.scalars + 3, r.skip_begin, r.skip_end)));
+    SLNLP_TRY(average_after_update(st));
     if (!recording()) params_stepped();      // (a lockstep replay does this per step itself)
     return 0;
 }
@@ -31,6 +32,7 @@ int PlanCore::update_adam(float* exp_avg_sq, float beta1, float beta2, float eps
     SLNLP_TRY(clip_adam_step(buf.params, buf.grads, buf.momentum, exp_avg_sq, arena, pg, lr, beta1, beta2, eps, weight_decay, max_norm,
                              opt_partials, buf.scalars + 1, buf.rng, buf.scalars + 2, st, r.wp, r.wp_begin, r.wp_end,
                              opts.adam(r.skip_begin, r.skip_end)));
+    SLNLP_TRY(average_after_update(st));
     if (!recording()) params_stepped();
     return 0;
 }

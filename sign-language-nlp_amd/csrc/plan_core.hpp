@@ -83,6 +83,16 @@ struct PlanCore {
     // shared code reads
     int64_t arena = 0;
     float* opt_partials = nullptr;
+    // slnlp_*_set_averaging (average.hip): the running average of the arena a train step feeds behind its update; `forced` is up
+    // only while a lockstep group with averaging records (every fit then issues the two launches, with a null avg if it is not
+    // averaging yet: one kernel per call site)
+    struct Averaging {
+        float* avg = nullptr;
+        float* count = nullptr;
+        int kind = 0;
+        float decay = 0.f;
+        bool forced = false;
+    } averaging;
     int max_B = 0, S = 0, Vt = 0;
     float dropout = 0.f;
 
@@ -115,6 +125,8 @@ struct PlanCore {
     int set_update(int kind, float dampening, float weight_decay, int nesterov);
     int set_param_groups(const char* what, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
                          const float* weight_decay, const float* lr_dev, hipStream_t st);
+    int set_averaging(const char* what, float* avg, float* count, int kind, float decay);
+    int average_after_update(hipStream_t st);
     int train_step(const int64_t* X, const int64_t* y, const int64_t* lengths, int B, float momentum, float max_norm, float* logp,
                    hipStream_t st);
     int graph_capture_train(const char* what, const int64_t* X, const int64_t* y, const int64_t* lengths, int B, float momentum,
@@ -128,6 +140,11 @@ struct PlanCore {
     void replayed(int B, int train);
     float* lr_target() const { return opts.groups ? const_cast<float*>(opts.groups_lr) : buf.lr; }
 };
+
+// average.hip: the accumulator's two launches (the average, then its count) and the in-place exchange of two arenas
+int average_step(float* avg, const float* params, int64_t n, float* count, int kind, float decay, int64_t skip_begin, int64_t skip_end,
+                 hipStream_t st);
+int swap_arenas(float* a, float* b, int64_t n, hipStream_t st);
 
 // the RNN plan as its PlanCore (its struct is private to rnn_plan.hip)
 PlanCore* rnn_core(slnlp_rnn_plan* plan);

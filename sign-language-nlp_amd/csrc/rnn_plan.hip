@@ -692,6 +692,11 @@ int slnlp_rnn_set_param_groups(slnlp_rnn_plan* pl, int n_segments, const int64_t
     return pl->set_param_groups("rnn_set_param_groups", n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
 }
 
+int slnlp_rnn_set_averaging(slnlp_rnn_plan* pl, float* avg, float* count, int kind, float decay) {
+    SLNLP_CHECK_ARG(pl, "rnn_set_averaging: null plan");
+    return pl->set_averaging("rnn_set_averaging", avg, count, kind, decay);
+}
+
 int slnlp_rnn_set_destroy_sync(slnlp_rnn_plan* pl, int on) {
     SLNLP_CHECK_ARG(pl, "rnn_set_destroy_sync: null plan");
     pl->destroy_sync = on ? 1 : 0;

@@ -382,6 +382,11 @@ int slnlp_tf_set_param_groups(slnlp_tf_plan* pl, int n_segments, const int64_t* 
     return pl->set_param_groups("tf_set_param_groups", n_segments, seg_begin, seg_group, n_groups, weight_decay, lr_dev, (hipStream_t)stream);
 }
 
+int slnlp_tf_set_averaging(slnlp_tf_plan* pl, float* avg, float* count, int kind, float decay) {
+    SLNLP_CHECK_ARG(pl, "tf_set_averaging: null plan");
+    return pl->set_averaging("tf_set_averaging", avg, count, kind, decay);
+}
+
 // The parameter arena was written from outside the library (load_state_dict, a torch optimizer, an in-place edit):
 // derived data is stale.  The Python engines call this when the arena tensor's version counter has moved.
 int slnlp_tf_params_changed(slnlp_tf_plan* pl) {

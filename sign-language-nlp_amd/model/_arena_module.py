@@ -120,6 +120,68 @@ class ArenaModule(nn.Module):
             st["exp_avg_sq"] = torch.zeros_like(st["momentum"])
         return st["exp_avg_sq"]
 
+    def averaged_arena(self):
+        """(avg, count): the arena-shaped running average of the weights and the number of models averaged so far, a device
+        float (allocated on first use, zero: the first update copies)."""
+        st = self._shared_state()
+        if "averaged" not in st:
+            st["averaged"] = torch.zeros_like(st["momentum"])
+            st["n_averaged"] = torch.zeros(1, dtype=torch.float32, device=st["momentum"].device)
+        return st["averaged"], st["n_averaged"]
+
+    def has_averaged(self):
+        st = self._opt_state
+        return st is not None and "averaged" in st and st["averaged"].device == self._arena.device
+
+    def set_averaging(self, kind=None, decay=0.0):
+        """Weight averaging riding every train step (``kind`` "swa" / "ema"; None: off), for every plan of the module, now and
+        created later -- as ``set_train_options``."""
+        new = None if kind is None else (str(kind), float(decay))
+        if new == getattr(self, "_averaging", None):
+            return
+        self._averaging = new
+        for eng in self._engines.values():
+            self._apply_averaging(eng)
+
+    def _apply_averaging(self, eng):
+        av = getattr(self, "_averaging", None)
+        if av is None:
+            if getattr(eng, "_averaging", (None, None))[0] is not None:
+                eng.set_averaging(None)
+        else:
+            eng.set_averaging(*self.averaged_arena(), kind=av[0], decay=av[1])
+
+    def average_skip(self):
+        """Floats [begin, end) of the arena the accumulator copies instead of averaging: the parameters torch never steps
+        (``_dead_params``), when they lie in one run -- what the plans' own averaging launches skip."""
+        dead = [(off, shape) for name, shape, off in self._entries if name in self._dead_params]
+        if not dead:
+            return 0, 0
+        end = 0
+        for off, shape in dead:
+            n = 1
+            for d in shape:
+                n *= d
+            end = max(end, off + n)
+        return min(off for off, _ in dead), (end + 3) // 4 * 4
+
+    def average_now(self, kind, decay=0.0):
+        """One update of the running average from the weights as they stand (the epoch cadence): two launches on the current
+        stream, no host wait."""
+        from slnlp import ops
+        self._materialize()
+        avg, count = self.averaged_arena()
+        ops.average_step(avg, self._arena, count, kind=kind, decay=decay, skip=self.average_skip())
+
+    def swap_averaged(self):
+        """Exchange the weights with their running average in place (one launch) and tell the plans, so the next forward reads
+        planes of the weights it is given.  Twice restores every bit."""
+        from slnlp import ops
+        self._materialize()
+        ops.swap_arenas(self._arena, self.averaged_arena()[0])
+        for eng in self._engines.values():
+            eng.params_changed()
+
     def _state_order(self, views):
         raise NotImplementedError
 
@@ -182,6 +244,7 @@ class ArenaModule(nn.Module):
             old = eng
             eng = self._make_engine(max(B, old.cfg.B if old is not None else 0), S, self._shared_state())
             self._apply_train_options(eng)
+            self._apply_averaging(eng)
             self._engines[S] = eng
         return eng
 

@@ -15,7 +15,7 @@ from .launch import LaunchPolicy
 from ._lib import TfBuffers, check, load, ptr
 
 # every slnlp_<prefix>_<name> a PlanEngine calls through _call (tests/test_engine_cpu.py holds them against _lib.SIGNATURES)
-CALLS = ("create", "destroy", "set_destroy_sync", "set_criterion", "set_update", "set_param_groups", "forward", "seed_dlogp",
+CALLS = ("create", "destroy", "set_destroy_sync", "set_criterion", "set_update", "set_param_groups", "set_averaging", "forward", "seed_dlogp",
          "backward", "optim", "optim_adam", "train_step", "graph_capture_train", "graph_launch", "tap")
 LAYOUT_CALLS = ("num_params", "param_info", "arena_floats", "workspace_bytes")
 
@@ -99,6 +99,8 @@ class PlanEngine:
                 pass
             self.handle = None
 
+    _pv = None
+
     def sync_params_version(self):
         """Before a launch that reads data derived from the arena (the Transformer's weight planes); nothing to do here."""
 
@@ -150,6 +152,24 @@ class PlanEngine:
                        len(wd), (C.c_float * len(wd))(*wd), ptr(lr), self._sp())
             self._group_lr = lr                  # kept alive: the update kernels read it
         self._graph_keys = {}
+
+    def set_averaging(self, avg=None, count=None, kind="swa", decay=0.0):
+        """Weight averaging riding the train step: every update of this plan is followed by the accumulator's two launches on
+        ``avg`` (arena-shaped float32 device tensor) and ``count`` ([1] float32, the models averaged so far) -- "swa" or "ema"
+        with ``decay`` (``ops.average_step``).  ``avg`` None removes them.  A change drops the plan's captured graphs."""
+        if avg is None:
+            self._call("set_averaging", None, None, 0, 0.0)
+        else:
+            if not (avg.is_cuda and avg.dtype == torch.float32 and avg.numel() == self.arena_floats and avg.is_contiguous()):
+                raise ValueError("set_averaging: avg must be a contiguous float32 device tensor of the arena's size")
+            self._call("set_averaging", ptr(avg), ptr(count), _lib.AVERAGE_KINDS[kind], float(decay))
+        self._averaging = (avg, count)       # kept alive: the step's launches write them
+        self._graph_keys = {}
+
+    def params_changed(self):
+        """The arena was rewritten by a launch through its raw pointer (``ops.swap_arenas``), which moves no tensor version
+        counter: the next ``sync_params_version`` tells the plan whatever the counter says."""
+        self._pv = None
 
     def set_lr(self, lr):
         self.lr.fill_(float(lr))

@@ -121,6 +121,8 @@ SIGNATURES = {
     "slnlp_param_groups_destroy": (None, [vp]),
     "slnlp_clip_sgd_step_groups": (i32, [vp, vp, vp, i64, vp, vp, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_clip_adam_step_groups": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
+    "slnlp_average_step": (i32, [vp, vp, i64, vp, i32, f32, i64, i64, vp]),
+    "slnlp_swap_arenas": (i32, [vp, vp, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -151,6 +153,7 @@ SIGNATURES = {
     "slnlp_rnn_set_criterion": (i32, [vp, vp, f32, i32, vp]),
     "slnlp_rnn_set_update": (i32, [vp, i32, f32, f32, i32]),
     "slnlp_rnn_set_param_groups": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
+    "slnlp_rnn_set_averaging": (i32, [vp, vp, vp, i32, f32]),
     "slnlp_rnn_train_step": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp]),
     "slnlp_rnn_graph_capture_train": (i32, [vp, vp, vp, vp, i32, f32, f32, vp, vp]),
     "slnlp_rnn_graph_launch": (i32, [vp, i32, vp]),
@@ -180,6 +183,7 @@ SIGNATURES = {
     "slnlp_tf_set_criterion": (i32, [vp, vp, f32, i32, vp]),
     "slnlp_tf_set_update": (i32, [vp, i32, f32, f32, i32]),
     "slnlp_tf_set_param_groups": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
+    "slnlp_tf_set_averaging": (i32, [vp, vp, vp, i32, f32]),
     "slnlp_tf_set_dmem_batched": (i32, [vp, i32]),
     "slnlp_set_stream_policy": (i32, [i32]),
     "slnlp_set_thread_stream_policy": (i32, [i32]),
@@ -200,6 +204,7 @@ SIGNATURES = {
     "slnlp_tf_lockstep_set_adam": (i32, [vp, vp, f32, f32, f32, f32]),
     "slnlp_tf_lockstep_set_lr_table": (i32, [vp, vp, i32, vp]),
     "slnlp_tf_lockstep_set_order": (i32, [vp, i32, vp, i64, vp]),
+    "slnlp_tf_lockstep_set_averaging": (i32, [vp, vp, vp, i32, f32]),
     "slnlp_tf_lockstep_set_destroy_sync": (i32, [vp, i32]),
     "slnlp_rnn_lockstep_workspace_bytes": (i64, [vp, i32]),
     "slnlp_rnn_lockstep_create": (i32, [vp, i32, vp, i64, vp, vp]),
@@ -211,6 +216,7 @@ SIGNATURES = {
     "slnlp_rnn_lockstep_set_adam": (i32, [vp, vp, f32, f32, f32, f32]),
     "slnlp_rnn_lockstep_set_lr_table": (i32, [vp, vp, i32, vp]),
     "slnlp_rnn_lockstep_set_order": (i32, [vp, i32, vp, i64, vp]),
+    "slnlp_rnn_lockstep_set_averaging": (i32, [vp, vp, vp, i32, f32]),
     "slnlp_rnn_lockstep_set_destroy_sync": (i32, [vp, i32]),
 }
 
@@ -249,6 +255,7 @@ def require_gpu():
 
 REDUCTIONS = {"mean": 0, "sum": 1}             # CrossEntropyLoss reductions the fused criterion implements
 UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
+AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
 
 
 def ptr(t):

@@ -98,6 +98,26 @@ class LockstepGroup:
         self._v2 = list(exp_avg_sq)                      # keep the tensors alive: the C side holds raw pointers
         check(self._fn("set_adam")(self.handle, _ptr_array(self._v2), betas[0], betas[1], eps, weight_decay), f"{self.kind}_lockstep_set_adam")
 
+    def set_averaging(self, avgs=None, kind="swa", decay=0.0):
+        """Weight averaging riding the group's train steps: ``avgs`` holds, per fit, ``(avg, count)`` -- the arena-shaped running
+        average and its [1] float count (``ArenaModule.averaged_arena``) -- or None for a fit that is not averaging yet; one
+        ``(kind, decay)`` for the group.  One launch over the K arenas per step.  ``avgs`` None (or all None): off.  A change makes
+        the group record its programs again."""
+        from ._lib import AVERAGE_KINDS
+        given = [a for a in (avgs or []) if a is not None]
+        if not given:
+            self._avgs = None
+            check(self._fn("set_averaging")(self.handle, None, None, 0, 0.0), f"{self.kind}_lockstep_set_averaging")
+            return
+        assert len(avgs) == self.K and all(a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and a.numel() == e.arena_floats
+                                           for (a, _), e in zip([x for x in avgs if x is not None],
+                                                                [e for x, e in zip(avgs, self.engines) if x is not None])), \
+            "lockstep: one (arena-shaped float32 device tensor, count) pair or None per fit"
+        self._avgs = list(avgs)                          # keep the tensors alive: the step's launches write them
+        a = (C.c_void_p * self.K)(*[None if x is None else ptr(x[0]) for x in avgs])
+        c = (C.c_void_p * self.K)(*[None if x is None else ptr(x[1]) for x in avgs])
+        check(self._fn("set_averaging")(self.handle, a, c, AVERAGE_KINDS[kind], float(decay)), f"{self.kind}_lockstep_set_averaging")
+
     def set_lr_tables(self, tables, n_steps=None):
         """Per-fit learning rates by train-batch index: a list with, per fit, a contiguous float32 device tensor [n_steps] or None
         (that fit keeps the rate its engine's ``set_lr`` gave it); None (or no tensor at all) clears the setting.  From then on every
@@ -196,6 +216,14 @@ def _adam_key(net):
     return (net._fused_kind,) + (adam_args(net)[:2] if net._fused_kind in ("adam", "adamw") else ())
 
 
+def _avg_key(net):
+    """What the fits of one group must share about weight averaging (``weight_averaging``): one (kind, decay, every) per group,
+    or None for all.  ``start_epoch`` and ``predict`` are each fit's own: a fit whose epoch has not come rides the group's
+    averaging launch with a null entry."""
+    av = getattr(net, "_avg_opts", None)
+    return None if av is None else (av["kind"], av["decay"], av["every"])
+
+
 def fit_lockstep(nets, datasets):
     """``net.partial_fit(ds)`` for every (net, ds) pair, all fits advancing together.  The nets must be initialised,
     of one shape (lr and dropout rate may differ) and their datasets of one size; fits that stop early (EarlyStopping)
@@ -227,7 +255,9 @@ def _fit_lockstep_gated(nets, datasets):
     assert all(lockstep_supported(n) for n in nets), "lockstep: fused SGD / Adam / AdamW + CrossEntropyLoss on the model.* modules only"
     assert len({type(n.module_) for n in nets}) == 1, "lockstep: one module class per group"
     assert len({_adam_key(n) for n in nets}) == 1, "lockstep: one optimizer (and one set of Adam constants) per group"
+    assert len({_avg_key(n) for n in nets}) == 1, "lockstep: one weight_averaging (kind, decay, every) per group"
     adam = _adam_key(nets[0]) if nets[0]._fused_kind in ("adam", "adamw") else None
+    avg = _avg_key(nets[0])
     assert all((r.bs, r.momentum, r.max_norm, len(r.tr), r.n_visit, (len(r.va) if r.va is not None else 0)) ==
                (r0.bs, r0.momentum, r0.max_norm, len(r0.tr), r0.n_visit, (len(r0.va) if r0.va is not None else 0)) for r in runs), \
         "lockstep: the fits of a group share batch size, momentum, clipping, split sizes and drop_last"
@@ -294,8 +324,17 @@ def _fit_lockstep_gated(nets, datasets):
                 for j in bal:                           # balanced fits: order() drew the table on the device, nothing to upload
                     per_fit[j] = runs[active[j]].order_dev
                 group.set_order(TRAIN, per_fit, r0.n_visit)
+            averaging = [nets[i]._averaging_epoch() for i in active]   # per fit: has its start_epoch come?
+            if avg is not None and avg[2] == "batch":
+                # the accumulator rides every train step, one launch over the group's arenas; a fit that is not averaging yet has a
+                # null entry (a call that changes nothing costs nothing: the group re-records only when an entry moved)
+                group.set_averaging([nets[i].module_.averaged_arena() if on else None for i, on in zip(active, averaging)], avg[0], avg[1])
             t_epoch = time.perf_counter()
             group.epoch(TRAIN, r0.bs, True, r0.momentum, r0.max_norm)
+            if avg is not None and avg[2] == "epoch":
+                for i, on in zip(active, averaging):    # behind the epoch's last step, in front of the valid pass; no host wait
+                    if on:
+                        nets[i].module_.average_now(avg[0], avg[1])
             if r0.va is not None:
                 group.epoch(VALID, r0.bs, False, r0.momentum, r0.max_norm)
             stream_sync(stream)                         # one host sync per epoch for all K fits
@@ -339,7 +378,14 @@ def _predict_proba_lockstep_gated(nets, datasets, bs, stream_sync):
             n.module_.eval()
         group = LockstepGroup(engines)
         group.set_data(TEST, [d[0] for d in dev], [d[2] for d in dev], bs, [d[1] for d in dev])
-        group.epoch(TEST, bs, False)
+        swapped = [n for n in nets if n._predict_averaged()]
+        for n in swapped:
+            n.module_.swap_averaged()                   # weight_averaging predict: the averaged weights stand in for the forward
+        try:
+            group.epoch(TEST, bs, False)
+        finally:
+            for n in swapped:
+                n.module_.swap_averaged()               # ... and the live weights come back bit for bit
         out = [lp.clone() for lp in group.logp[TEST]]
         stream_sync(nets[0]._stream)
         # softmax on the host copies (torch's CPU op, as in NeuralNetClassifier.predict_proba: no torch arithmetic kernel runs
@@ -367,7 +413,7 @@ def fit_and_score_group(estimator_factory, params_list, trains, tests, scoring="
             net.initialize()
         nets.append(net)
     if not all(lockstep_supported(n) for n in nets) or len({type(n.module_) for n in nets}) != 1 or len({_adam_key(n) for n in nets}) != 1 or \
-            len({len(t) for t in trains}) != 1 or len({len(t) for t in tests}) != 1 or \
+            len({_avg_key(n) for n in nets}) != 1 or len({len(t) for t in trains}) != 1 or len({len(t) for t in tests}) != 1 or \
             (any(n._iterator_train_balance() for n in nets) and len({n._epoch_rows(t) for n, t in zip(nets, trains)}) != 1):
         # (the last one: a balanced epoch's length follows the fold's labels, and a group shares its batch count)
         del nets

@@ -19,7 +19,9 @@ semantics:
 * per epoch: valid pass, ``EpochScoring`` metrics for train/valid, ``lr`` scoring,
   ``LRScheduler`` (``ReduceLROnPlateau`` on valid_loss, or any other ``torch.optim.lr_scheduler`` policy stepped per
   epoch or per batch: slnlp/schedule.py), ``EarlyStopping`` (patience,
-  relative threshold), ``Checkpoint`` on ``valid_loss_best`` (helper.py:197-273).
+  relative threshold), ``Checkpoint`` on ``valid_loss_best`` (helper.py:197-273);
+* ``weight_averaging={...}``: a running average of the weights (SWA / EMA, ``torch.optim.swa_utils``) kept on the device beside
+  the model, fed per epoch or per batch, and -- ``predict`` -- what ``predict_proba`` / ``predict`` / ``score`` evaluate with.
 
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
@@ -259,6 +261,49 @@ def update_options(kind, defaults):
     return {"kind": kind, "weight_decay": float(defaults.get("weight_decay", 0.0))}     # the fit's own in a lockstep group
 
 
+AVERAGING_KEYS = ("kind", "decay", "every", "start_epoch", "predict")
+
+
+def averaging_options(setting):
+    """The ``weight_averaging`` setting with its defaults filled in -- {kind "swa" | "ema", decay (ema only; 0.999), every
+    "epoch" | "batch", start_epoch >= 1, predict} -- or None (off).  Anything the fit loop could not honour raises ValueError here."""
+    if setting is None or setting is False:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"weight_averaging={setting!r}: expected a dict with keys among {AVERAGING_KEYS} or None")
+    unknown = sorted(set(setting) - set(AVERAGING_KEYS))
+    if unknown:
+        raise ValueError(f"weight_averaging: unknown keys {unknown} (known: {AVERAGING_KEYS})")
+    kind = setting.get("kind", "swa")
+    if kind not in ("swa", "ema"):
+        raise ValueError(f"weight_averaging: kind={kind!r}, expected 'swa' or 'ema'")
+    decay = setting.get("decay", 0.999 if kind == "ema" else 0.0)
+    if kind == "ema" or "decay" in setting:
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating)) or not 0.0 < float(decay) < 1.0:
+            raise ValueError(f"weight_averaging: decay={decay!r} outside (0, 1)")
+    every = setting.get("every", "epoch")
+    if every not in ("epoch", "batch"):
+        raise ValueError(f"weight_averaging: every={every!r}, expected 'epoch' or 'batch'")
+    start = setting.get("start_epoch", 1)
+    if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or int(start) < 1:
+        raise ValueError(f"weight_averaging: start_epoch={start!r}, expected an integer >= 1")
+    predict = setting.get("predict", True)
+    if not isinstance(predict, (bool, np.bool_)):
+        raise ValueError(f"weight_averaging: predict={predict!r}, expected True or False")
+    return {"kind": kind, "decay": float(decay) if kind == "ema" else 0.0, "every": every, "start_epoch": int(start),
+            "predict": bool(predict)}
+
+
+def next_n_averaged(opts, history, n_batches):
+    """``n_averaged`` of the epoch about to join ``history``: the models in the average once that epoch is over, from the cadence
+    and the rows alone (no device read) -- the last row's count plus, from ``start_epoch`` on, one per epoch or one per train
+    batch.  A resumed fit goes on from the count its loaded history ends with."""
+    have = int(history[-1].get("n_averaged", 0)) if history else 0
+    if len(history) + 1 < opts["start_epoch"]:
+        return have
+    return have + (1 if opts["every"] == "epoch" else int(n_batches))
+
+
 def adam_args(net):
     """(betas, eps, weight_decay) of a fused Adam / AdamW fit, torch's defaults filled in."""
     d = net._opt_defaults
@@ -460,6 +505,8 @@ class _FitRun:
                 if sp not in proba:
                     proba[sp] = np.exp(lp.cpu().numpy())
                 row[f"{sp}_{wr.score}"] = float(wr(_CachedPredictor(proba[sp], net.classes_), None, yh))
+        if getattr(net, "_avg_opts", None) is not None:
+            row["n_averaged"] = next_n_averaged(net._avg_opts, net.history, len(tr_batches))
         row["dur"] = time.time() - self.t0
         net.history.append(row)
         if net.verbose:
@@ -494,13 +541,13 @@ class _FitRun:
 class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
     _OWN = ("module", "criterion", "optimizer", "lr", "max_epochs", "batch_size", "device", "warm_start", "verbose",
             "predict_nonlinearity", "scoring", "labels", "early_stopping", "gradient_clipping", "lr_scheduler",
-            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset")
+            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging")
 
     def __init__(self, module, criterion="torch.nn.CrossEntropyLoss", optimizer="torch.optim.SGD", lr=0.01,
                  max_epochs=10, batch_size=128, device="cuda", warm_start=False, verbose=0,
                  predict_nonlinearity="auto", scoring=None, labels=None, early_stopping=None,
                  gradient_clipping=None, lr_scheduler=None, checkpoint_dir=None, train_split=5, use_graph="auto",
-                 callbacks=None, dataset=None, **kwargs):
+                 callbacks=None, dataset=None, weight_averaging=None, **kwargs):
         loc = locals()
         self._params = {k: loc[k] for k in self._OWN}
         for k, v in kwargs.items():
@@ -611,6 +658,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         self.balance_seed_ = sampler.draw_seed() if balance else None
 
     def initialize(self):
+        avg_opts = averaging_options(self._params.get("weight_averaging"))   # a bad setting: here, not in the middle of a fit
         ok, pairs = optimizer_kwargs(self._sub("optimizer"))
         if not pairs:
             schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
@@ -631,6 +679,11 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         # which fused clip + update kernel replaces the torch optimizer (None: the fit steps through torch)
         self._fused_kind = fused_kind(self.criterion_, self._opt_cls, ok, mod_cls, pairs)
         self._fused = self._fused_kind is not None
+        if avg_opts is not None and not self._fused:
+            raise ValueError("weight_averaging: the average is kept on the device by the fused train step, and this fit steps through "
+                             f"torch (optimizer {self._opt_cls.__name__}, criterion {type(self.criterion_).__name__}); it is "
+                             "implemented for fused fits only (SGD / Adam / AdamW with CrossEntropyLoss on the model.* modules)")
+        self._avg_opts = avg_opts
         self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
         # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
         self._crit_opts = criterion_options(self.criterion_) if hasattr(mod_cls, "engine") else None
@@ -710,8 +763,15 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 if order is not None:                       # one upload per epoch: the order and the labels in visit order
                     # (a balanced epoch has no host order: run.order() drew its tables on the device)
                     run.set_visit(*torch.from_numpy(run.visit_table()).to(run.Xtr.device))
+                averaging = self._averaging_epoch()
+                if self._avg_opts is not None and self._avg_opts["every"] == "batch":
+                    # the accumulator's launches ride every train step from start_epoch on: switched between epochs, once
+                    self.module_.set_averaging(*((self._avg_opts["kind"], self._avg_opts["decay"]) if averaging else (None,)))
                 tr = self._run_epoch(run.Xtr, run.Ltr, run.ytr, run.bs, True, run.momentum, run.max_norm, lrs=lrs,
                                      order=run.order_dev, n_visit=run.n_visit)
+                if averaging and self._avg_opts["every"] == "epoch":
+                    # behind the epoch's last step, in front of the valid pass (which reads the live weights), on the fit's stream
+                    self.module_.average_now(self._avg_opts["kind"], self._avg_opts["decay"])
                 va = None
                 if run.va is not None:
                     self.module_.eval()
@@ -720,6 +780,34 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                     break
         stream_sync(self._stream)
         return self
+
+    # ------------------------------------------------------- weight averaging
+    def _averaging_epoch(self):
+        """Whether the epoch about to run feeds the average (the option is on and ``start_epoch`` is reached)."""
+        av = getattr(self, "_avg_opts", None)
+        return av is not None and len(self.history) + 1 >= av["start_epoch"]
+
+    @property
+    def n_averaged_(self):
+        """Models in the running average, from the history (no device read)."""
+        return int(self.history[-1].get("n_averaged", 0)) if self.history else 0
+
+    def _predict_averaged(self):
+        av = getattr(self, "_avg_opts", None)
+        return av is not None and av["predict"] and self.n_averaged_ > 0
+
+    def averaged_state_dict(self):
+        """The module's ``state_dict`` with every parameter replaced by its running average (buffers as they are)."""
+        if getattr(self, "_avg_opts", None) is None:
+            raise RuntimeError("averaged_state_dict: this estimator has no weight_averaging option")
+        sd = dict(self.module_.state_dict())
+        avg = self.module_.averaged_arena()[0]
+        for name, shape, off in self.module_._entries:
+            n = 1
+            for d in shape:
+                n *= d
+            sd[name] = avg[off:off + n].view(*shape).clone()
+        return sd
 
     def _train_split(self, ds):
         ts = self.train_split
@@ -834,8 +922,15 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             self._enter_stream()
             with torch.cuda.stream(self._stream), torch.no_grad():
                 Xd, Ld, yd = self._device_data(ds)
-                for i in range(0, len(ds), int(self.batch_size)):
-                    outs.append(self.module_(X=Xd[i:i + self.batch_size], y=yd[i:i + self.batch_size], lengths=Ld[i:i + self.batch_size]))
+                swapped = self._predict_averaged()
+                if swapped:
+                    self.module_.swap_averaged()         # the averaged weights stand in for the forward passes ...
+                try:
+                    for i in range(0, len(ds), int(self.batch_size)):
+                        outs.append(self.module_(X=Xd[i:i + self.batch_size], y=yd[i:i + self.batch_size], lengths=Ld[i:i + self.batch_size]))
+                finally:
+                    if swapped:
+                        self.module_.swap_averaged()     # ... and the live weights come back bit for bit
                 out = torch.cat(outs)
             stream_sync(self._stream)
         finally:
@@ -929,6 +1024,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                    os.path.join(dirname, "criterion.pt"))       # host tensors, like params.pt
         with open(os.path.join(dirname, "history.json"), "w") as f:
             json.dump(self.history, f, indent=1)
+        if getattr(self, "_avg_opts", None) is not None:  # the running average and how many models it holds: a resumed fit goes on
+            torch.save({"state_dict": {k: v.detach().cpu() for k, v in self.averaged_state_dict().items()}, "n_averaged": self.n_averaged_},
+                       os.path.join(dirname, "averaged.pt"))
 
     def load_params(self, dirname):
         """Restore what ``save_params`` / skorch's Checkpoint wrote: weights, optimizer state (momentum buffers + lr) and,
@@ -946,6 +1044,14 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 self.lr_ = float(self.optimizer_.param_groups[0]["lr"])
                 if self._groups is not None:
                     self._lrs = [float(g["lr"]) for g in self.optimizer_.param_groups]
+        avg_file = os.path.join(dirname, "averaged.pt")
+        if getattr(self, "_avg_opts", None) is not None and os.path.exists(avg_file):
+            saved = torch.load(avg_file)
+            avg, count = self.module_.averaged_arena()
+            for name, shape, off in self.module_._entries:
+                t = saved["state_dict"][name]
+                avg[off:off + t.numel()].copy_(t.reshape(-1).to(avg.device, torch.float32))
+            count.fill_(float(saved["n_averaged"]))
         hist = os.path.join(dirname, "history.json")
         if os.path.exists(hist):
             with open(hist) as f:

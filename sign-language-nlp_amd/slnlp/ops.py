@@ -384,6 +384,21 @@ def clip_adamw_step(params, grads, exp_avg, exp_avg_sq, lr_dev, step_count, *, b
     return norm
 
 
+def average_step(avg, params, count, *, kind="swa", decay=0.0, skip=(0, 0)):
+    """Feed ``params`` into the running average ``avg`` (flat fp32 arenas, in place): a bit copy while ``count`` [1] float
+    (device) is 0, then ``kind`` "swa" (``AveragedModel``'s default ``avg_fn``) or "ema" (``get_ema_multi_avg_fn(decay)``);
+    floats ``skip`` [begin, end) are copied.  ``count`` is advanced on the device; no host wait."""
+    _lib.require_gpu()
+    check(load().slnlp_average_step(ptr(avg), ptr(params), params.numel(), ptr(count), _lib.AVERAGE_KINDS[kind], float(decay),
+                                    int(skip[0]), int(skip[1]), stream_ptr()), "average_step")
+
+
+def swap_arenas(a, b):
+    """Exchange two flat fp32 arenas in place (one launch); two swaps restore every bit."""
+    _lib.require_gpu()
+    check(load().slnlp_swap_arenas(ptr(a), ptr(b), a.numel(), stream_ptr()), "swap_arenas")
+
+
 class ParamGroupTable:
     """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
     segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
