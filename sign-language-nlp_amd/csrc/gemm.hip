@@ -29,13 +29,9 @@
 
 #include "common.hpp"
 #include "gemm_jobs.hpp"
+#include "mfma_tile.hpp"
 
 namespace slnlp {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #if SLNLP_PROBE_FENCES == 256
 // timeline probe build (tools/probes/probe_gemm_timeline.py): every workgroup records 100 MHz timestamps of its phases
@@ -46,148 +42,6 @@ __device__ unsigned g_gts_n;
 #else
 #define GTS_MARK(slot) do { } while (0)
 #endif
-
-constexpr int BM = 64, BKT = 64;
-constexpr int KLD = BKT;      // [row][k] image: 64 bf16 = 128-B rows, 16-B slots XOR-swizzled by (row & 7)
-
-// element offset of (row, k) in the k-major image.  The mixed-row lane groups of ds_read_b128
-// ({0-3,12-15,20-27}, ...) hit 16 distinct 16-B slots of the 256-B bank row with this swizzle;
-// a padded stride cannot do that (the g=1 slots are the g=0 slots shifted by one).
-__device__ __forceinline__ int kmaj_off(int row, int k) { return row * KLD + ((((k >> 3) ^ (row & 7)) << 3) | (k & 7)); }
-
-
-__device__ __forceinline__ unsigned short f2bf(float x) {
-    __bf16 b = (__bf16)x;
-    return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-
-// One operand tile = ROWS x 64(k) fp32.  NV float4 per thread.
-//  KMAJOR: element (row,k) at P + row*ld + k; float4 runs along k; 16 float4 per row.
-// !KMAJOR: element (row,k) at P + k*ld + row; float4 runs along row; ROWS/4 float4 per k.
-template <bool KMAJOR, int ROWS>
-struct TileIO {
-    static constexpr int NV = ROWS * BKT / 4 / 256;       // 4 (ROWS=64), 2 (ROWS=32) or 1 (ROWS=16)
-    static constexpr int MLD = ROWS + 8;                  // [k][row] image row stride (bf16)
-    static constexpr int PLANE = KMAJOR ? ROWS * KLD : BKT * MLD;
-
-    __device__ static __forceinline__ void coords(int idx, int& row, int& k) {
-        if (KMAJOR) { row = idx >> 4; k = (idx & 15) << 2; }
-        else { k = idx / (ROWS / 4); row = (idx % (ROWS / 4)) << 2; }
-    }
-
-    // Issue the loads of one K-tile.  Branch-free and with NO use of the loaded values: any use here
-    // (even zeroing a tail lane) makes hipcc wait vmcnt(0) right behind each load and serialises the
-    // whole prefetch.  Out-of-range coordinates are clamped to a valid address; stash() zeroes them.
-    template <bool VEC>
-    __device__ static __forceinline__ void fetch(const float* __restrict__ P, long ld, int row0, int nrows,
-                                                 int k0, int K, int tid, float4 (&r)[NV]) {
-#pragma unroll
-        for (int u = 0; u < NV; ++u) {
-            int row, k;
-            coords(tid + 256 * u, row, k);
-            row += row0;
-            k += k0;
-            if (VEC) {   // compile-time: the hot kernel has no control flow around its loads
-                const int rc = row < nrows ? row : 0, kc = k < K ? k : 0;
-                r[u] = *reinterpret_cast<const float4*>(KMAJOR ? P + (long)rc * ld + kc : P + (long)kc * ld + rc);
-            } else {
-                float x[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    int rr = KMAJOR ? row : row + e, kk = KMAJOR ? k + e : k;
-                    rr = rr < nrows ? rr : 0;
-                    kk = kk < K ? kk : 0;
-                    x[e] = KMAJOR ? P[(long)rr * ld + kk] : P[(long)kk * ld + rr];
-                }
-                r[u] = make_float4(x[0], x[1], x[2], x[3]);
-            }
-        }
-    }
-
-    // fp32 -> bf16 hi (+ lo) and store into the LDS image.  hi is the TRUNCATED upper half of the
-    // fp32 word (1 VALU op instead of a round-to-nearest convert); x - hi is exact in fp32 and
-    // lo = rne_bf16(x - hi) absorbs the truncation, so hi + lo still represents x to ~2^-16.
-    // EDGE = false: interior tile, no bounds masks at all.
-    template <int NSPLIT, bool EDGE>
-    __device__ static __forceinline__ void stash(unsigned short* __restrict__ T, int tid, const float4 (&r)[NV],
-                                                 int row0, int nrows, int k0, int K) {
-        typedef __attribute__((ext_vector_type(2))) float f32x2;
-        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-#pragma unroll
-        for (int u = 0; u < NV; ++u) {
-            int row, k;
-            coords(tid + 256 * u, row, k);
-            float x[4] = {r[u].x, r[u].y, r[u].z, r[u].w};
-            if (EDGE) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int rr = row0 + (KMAJOR ? row : row + e), kk = k0 + (KMAJOR ? k + e : k);
-                    if (!(rr < nrows && kk < K)) x[e] = 0.f;      // edge / K-tail zero fill (v_cndmask)
-                }
-            }
-            const int off = KMAJOR ? kmaj_off(row, k) : k * MLD + row;   // both 8-B aligned
-            unsigned ub[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ub[e] = __float_as_uint(x[e]);
-            uint2 w;
-            if (NSPLIT == 3) {
-                w.x = (ub[0] >> 16) | (ub[1] & 0xFFFF0000u);
-                w.y = (ub[2] >> 16) | (ub[3] & 0xFFFF0000u);
-                *reinterpret_cast<uint2*>(T + off) = w;
-                float lo[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) lo[e] = x[e] - __uint_as_float(ub[e] & 0xFFFF0000u);
-                const bf16x2 l01 = __builtin_convertvector(f32x2{lo[0], lo[1]}, bf16x2);
-                const bf16x2 l23 = __builtin_convertvector(f32x2{lo[2], lo[3]}, bf16x2);
-                w.x = __builtin_bit_cast(unsigned, l01);
-                w.y = __builtin_bit_cast(unsigned, l23);
-                *reinterpret_cast<uint2*>(T + PLANE + off) = w;
-            } else {   // single pass: round to nearest
-                const bf16x2 h01 = __builtin_convertvector(f32x2{x[0], x[1]}, bf16x2);
-                const bf16x2 h23 = __builtin_convertvector(f32x2{x[2], x[3]}, bf16x2);
-                w.x = __builtin_bit_cast(unsigned, h01);
-                w.y = __builtin_bit_cast(unsigned, h23);
-                *reinterpret_cast<uint2*>(T + off) = w;
-            }
-        }
-    }
-
-    // MFMA 16x16x32 operand fragment of tile rows [r0, r0+16), k in [kk*32, kk*32+32):
-    // lane l holds (row r0 + (l&15), k = kk*32 + 8*(l>>4) + j), j = 0..7.
-    __device__ static __forceinline__ bf16x8 frag(const unsigned short* __restrict__ T, int r0, int kk, int lane) {
-        if (KMAJOR) {
-            return *reinterpret_cast<const bf16x8*>(T + kmaj_off(r0 + (lane & 15), kk * 32 + ((lane >> 4) << 3)));
-        } else {
-            // transposing read: lane (i = l&15; q = i>>2, p = i&3) addresses k-row q, columns 4p..4p+3 of a
-            // 4(k) x 16(row) block and receives the 4 k-values of column i.
-            const int i = lane & 15, kb = kk * 32 + ((lane >> 4) << 3) + (i >> 2);
-            const unsigned short* p0 = T + kb * MLD + r0 + ((i & 3) << 2);
-            typedef __attribute__((address_space(3))) s16x4* lds_p;
-            const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0));
-            const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0 + 4 * MLD));
-            const s16x8 v = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            return __builtin_bit_cast(bf16x8, v);
-        }
-    }
-
-    // bf16(hi)+bf16(lo) value of tile element (row, k) -- for the fused bias-gradient row sums
-    template <int NSPLIT>
-    __device__ static __forceinline__ float value(const unsigned short* __restrict__ T, int row, int k) {
-        const int off = KMAJOR ? kmaj_off(row, k) : k * MLD + row;
-        float v = bf2f(T[off]);
-        if (NSPLIT == 3) v += bf2f(T[PLANE + off]);
-        return v;
-    }
-};
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also emits s_waitcnt vmcnt(0),
-// which would drain the register prefetch of the next two K-tiles at every step.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // LDS of one tile job: A planes, B planes, 4 x 64 row-sum scratch
 template <int NSPLIT, bool AK, bool BK, int BNT>
@@ -590,10 +444,6 @@ static void launch(const GemmParams& p, hipStream_t s) {
     else launch2<NSPLIT, AK, BK, false>(p, s);
 }
 
-static bool vec_ok(const float* ptr, long ld) {
-    return (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(ptr) & 15) == 0);
-}
-
 static int fill_params(const slnlp_gemm_args& a, GemmParams& p) {
     SLNLP_CHECK_ARG(a.A && a.B && a.C, "gemm: null operand");
     SLNLP_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0, "gemm: bad shape M=%d N=%d K=%d", a.M, a.N, a.K);
@@ -702,948 +552,7 @@ const void* gemm_group_kernel_ptr(int precision, int ks) {
     return ks == 2 ? (const void*)gemm_group_kernel<1, 2> : (const void*)gemm_group_kernel<1, 1>;
 }
 
-// ------------------------------------------------------------- fused recurrent step ---
-// One forward timestep of an LSTM / GRU layer (up to two directions) in ONE launch: the recurrent GEMM
-// h_{t-1} W_hh^T and the point-wise cell (rnn.hip rnn_cell_fwd_kernel) that consumes it.  A workgroup owns 16 hidden
-// units: it computes their G gate pre-activations for all B rows (G B-tiles of 16 weight rows, one shared A tile per
-// K-step, same split-bf16 K order as gemm_tile, so results are bit-identical to GEMM + cell) and applies the cell in
-// the accumulator layout -- every lane holds all G gates of its (row, unit) pairs.  The new state goes to a DIFFERENT
-// buffer than the one read (other workgroups still read h_{t-1}): the caller chains the per-timestep `hprev` slots.
-struct RnnStepParams {
-    slnlp_rnn_step_dir d[2];
-    int B, Hd, ndir;
-    const long* lengths;
-    float fill;
-    long ld_out;
-    float drop_p;
-    unsigned drop_thr;
-    int drop_site;
-    const unsigned long long* rng;
-};
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ __forceinline__ slnlp_rnn_step_dir as_global(slnlp_rnn_step_dir d) {
-    d.h_in = as_global(d.h_in); d.h_out = as_global(d.h_out); d.w_hh = as_global(d.w_hh); d.b_hh = as_global(d.b_hh);
-    d.xproj = as_global(d.xproj); d.c = as_global(d.c); d.cprev_save = as_global(d.cprev_save); d.acts = as_global(d.acts);
-    d.hn_save = as_global(d.hn_save); d.out = as_global(d.out);
-    return d;
-}
-
-// ------------------------------------------------------------------------------------------ fused backward timestep ---
-// One launch per backward timestep (rounds 1-3: a cell kernel + a grouped K-sliced GEMM launch, 192 + 192 launches per cfg3 step):
-//   dh(t) = dgh(t+1) W_hh + carry(t+1)            [B, Hd]     recurrent data gradient of the step processed just before
-//   cell backward of step t (rnn.hip, rnn_cell_bwd_body: same arithmetic, same order)  ->  dgx(t), dgh(t), dc, carry(t)
-// A workgroup owns 16 hidden units (output columns of the GEMM) of one direction and 64 batch rows.  The contraction runs over
-// the G * Hd gate columns: G groups of 256 threads, group g contracting gate g's Hd columns with its own stage images (all G K
-// loops in flight together: the dependent chain is Hd / 64 steps, as in the K-sliced launch it replaces); the groups' partial
-// sums meet in LDS and are added in gate order -- ((P0 + carry) + P1) + P2 (+ P3), the order of the unfused path -- and group 0
-// applies the cell in the accumulator layout.  dgh_next == NULL: first step of a layer, dh = dh_state (no product).
-struct RnnStepBwdParams {
-    slnlp_rnn_step_bwd_dir d[2];
-    int B, Hd, ndir;
-    const long* lengths;
-    long ld_dout;
-    float drop_p;
-    unsigned drop_thr;
-    int drop_site;
-    const unsigned long long* rng;
-};
-__device__ __forceinline__ slnlp_rnn_step_bwd_dir as_global(slnlp_rnn_step_bwd_dir d) {
-    d.cell = as_global(d.cell);
-    d.dgh_next = as_global(d.dgh_next); d.w_hh = as_global(d.w_hh);
-    return d;
-}
-template <int NSPLIT, bool LSTM>
-constexpr int rnn_step_bwd_group_elems() {
-    return (NSPLIT == 3 ? 2 : 1) * (TileIO<true, BM>::PLANE + TileIO<false, 16>::PLANE);
-}
-template <int NSPLIT, bool LSTM>
-constexpr size_t rnn_step_bwd_lds() {
-    constexpr int G = LSTM ? 4 : 3;
-    return (size_t)G * rnn_step_bwd_group_elems<NSPLIT, LSTM>() * sizeof(unsigned short) + (size_t)(G - 1) * 256 * sizeof(f32x4);
-}
-
-template <int NSPLIT, bool LSTM>
-__global__ __launch_bounds__(LSTM ? 1024 : 768) void rnn_step_bwd_kernel(const RnnStepBwdParams P0, const RnnStepBwdParams* __restrict__ tab) {
-    extern __shared__ __attribute__((aligned(16))) unsigned short bsm[];
-    RnnStepBwdParams P;
-    if (tab) P = tab[blockIdx.z];
-    else P = P0;
-    P.lengths = as_global(P.lengths);
-    P.rng = as_global(P.rng);
-    constexpr int G = LSTM ? 4 : 3;
-    constexpr int NP = NSPLIT == 3 ? 2 : 1;
-    using TA = TileIO<true, BM>;
-    using TB = TileIO<false, 16>;
-    const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-    unsigned short* As = bsm + grp * rnn_step_bwd_group_elems<NSPLIT, LSTM>();
-    unsigned short* Bs = As + NP * TA::PLANE;
-    f32x4* red = reinterpret_cast<f32x4*>(bsm + G * rnn_step_bwd_group_elems<NSPLIT, LSTM>());
-    const int dir = blockIdx.y % P.ndir;
-    const slnlp_rnn_step_bwd_dir sd = as_global(dir == 0 ? P.d[0] : P.d[1]);
-    const slnlp_rnn_cell_bwd_dir& d = sd.cell;
-    const int B = P.B, Hd = P.Hd, GH = G * Hd, j0 = blockIdx.x * 16, bm0 = (blockIdx.y / P.ndir) * BM;
-    const bool product = sd.dgh_next != nullptr;       // (launch-uniform per direction)
-
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (product) {
-        const int ktiles = Hd / BKT, kg = grp * Hd;    // this group's gate columns [kg, kg + Hd)
-        float4 ra0[TA::NV], ra1[TA::NV], rb0[TB::NV], rb1[TB::NV];
-        auto fetch = [&](int kt, float4 (&ra)[TA::NV], float4 (&rb)[TB::NV]) {
-            const int kc = kt < ktiles ? kt : 0;           // past-the-end prefetch: a valid tile, never stashed
-            TA::template fetch<true>(sd.dgh_next, GH, bm0, B, kg + kc * BKT, GH, tid, ra);
-            TB::template fetch<true>(sd.w_hh, Hd, j0, Hd, kg + kc * BKT, GH, tid, rb);
-        };
-        auto stash = [&](int kt, const float4 (&ra)[TA::NV], const float4 (&rb)[TB::NV]) {
-            // rows >= B hold a clamped row's data and only feed accumulator rows that are never used (no masks: Hd % 64 == 0)
-            TA::template stash<NSPLIT, false>(As, tid, ra, bm0, B, kg + kt * BKT, GH);
-            TB::template stash<NSPLIT, false>(Bs, tid, rb, j0, Hd, kg + kt * BKT, GH);
-        };
-        auto consume = [&]() {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const bf16x8 ah = TA::frag(As, wave * 16, kk, lane);
-                const bf16x8 bh = TB::frag(Bs, 0, kk, lane);
-                if (NSPLIT == 3) {
-                    const bf16x8 al = TA::frag(As + TA::PLANE, wave * 16, kk, lane);
-                    const bf16x8 bl = TB::frag(Bs + TB::PLANE, 0, kk, lane);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
-                }
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
-            }
-        };
-        fetch(0, ra0, rb0);
-        fetch(1, ra1, rb1);
-        for (int kt = 0; kt < ktiles; kt += 2) {
-            lds_barrier();
-            stash(kt, ra0, rb0);
-            lds_barrier();
-            fetch(kt + 2, ra0, rb0);
-            consume();
-            if (kt + 1 >= ktiles) break;
-            lds_barrier();
-            stash(kt + 1, ra1, rb1);
-            lds_barrier();
-            fetch(kt + 3, ra1, rb1);
-            consume();
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the dummy prefetches
-        if (grp > 0) red[(grp - 1) * 256 + tid] = acc;
-        __syncthreads();
-    }
-    if (grp != 0) return;
-
-    // ---- the cell backward of this timestep in the accumulator layout (rnn.hip rnn_cell_bwd_body: same arithmetic and order)
-    const int j = j0 + (lane & 15);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = bm0 + wave * 16 + ((lane >> 4) << 2) + r;
-        if (b >= B) break;
-        const long idx = (long)b * Hd + j;
-        const bool valid = P.lengths ? (d.t < P.lengths[b]) : true;
-        float dh;
-        if (product) {
-            dh = acc[r] + d.carry[idx];                      // (the unfused path adds carry as the first job's residual)
-#pragma unroll
-            for (int e = 0; e < G - 1; ++e) dh += red[e * 256 + tid][r];
-        } else {
-            dh = d.dh_state[idx];
-        }
-        float* gx = d.dgx + (long)b * GH;
-        float* gh = LSTM ? gx : d.dgh + (long)b * GH;
-        if (!valid) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                gx[g * Hd + j] = 0.f;
-                if (!LSTM) gh[g * Hd + j] = 0.f;
-            }
-            d.carry[idx] = dh;
-            continue;
-        }
-        if (d.dout) {
-            float g = d.dout[(long)b * P.ld_dout + j];
-            if (P.drop_p > 0.f)
-                g = dropout_keep(P.rng, P.drop_site, (unsigned)(d.out_row0 + b), (unsigned)(d.out_col0 + j), P.drop_thr)
-                        ? g / (1.f - P.drop_p) : 0.f;
-            dh += g;
-        }
-        const float* a = d.acts + (long)b * GH;
-        if constexpr (LSTM) {
-            const float gi = a[j], gf = a[Hd + j], gg = a[2 * Hd + j], go = a[3 * Hd + j];
-            const float cprev = d.cprev_save[idx];
-            const float tc = tanhf(gf * cprev + gi * gg);
-            const float dc = d.dc_state[idx] + dh * go * (1.f - tc * tc);
-            gx[j] = dc * gg * gi * (1.f - gi);
-            gx[Hd + j] = dc * cprev * gf * (1.f - gf);
-            gx[2 * Hd + j] = dc * gi * (1.f - gg * gg);
-            gx[3 * Hd + j] = dh * tc * go * (1.f - go);
-            d.dc_state[idx] = dc * gf;
-            d.carry[idx] = 0.f;
-        } else {
-            const float rr = a[j], z = a[Hd + j], nn = a[2 * Hd + j];
-            const float hprev = d.hprev_save[idx], hn = d.hn_save[idx];
-            const float dn_pre = dh * (1.f - z) * (1.f - nn * nn);
-            const float dr_pre = dn_pre * hn * rr * (1.f - rr);
-            const float dz_pre = dh * (hprev - nn) * z * (1.f - z);
-            gx[j] = dr_pre; gx[Hd + j] = dz_pre; gx[2 * Hd + j] = dn_pre;
-            gh[j] = dr_pre; gh[Hd + j] = dz_pre; gh[2 * Hd + j] = dn_pre * rr;
-            d.carry[idx] = dh * z;
-        }
-    }
-}
-
-template <int NSPLIT, bool LSTM>
-static const void* rnn_step_bwd_fn() { return (const void*)rnn_step_bwd_kernel<NSPLIT, LSTM>; }
-
-// raise the kernels' dynamic LDS limit once per device (plan creation: never inside a graph capture)
-int rnn_step_bwd_init() {
-    static DeviceOnce once;
-    return once.run([]() -> int {
-        const bool ok =
-            hipFuncSetAttribute(rnn_step_bwd_fn<3, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rnn_step_bwd_lds<3, true>()) == hipSuccess &&
-            hipFuncSetAttribute(rnn_step_bwd_fn<3, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rnn_step_bwd_lds<3, false>()) == hipSuccess &&
-            hipFuncSetAttribute(rnn_step_bwd_fn<1, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rnn_step_bwd_lds<1, true>()) == hipSuccess &&
-            hipFuncSetAttribute(rnn_step_bwd_fn<1, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rnn_step_bwd_lds<1, false>()) == hipSuccess;
-        if (!ok) {
-            set_error("rnn_step_bwd_init: cannot raise dynamic LDS limit: %s", hipGetErrorString(hipGetLastError()));
-            return SLNLP_ERR_LAUNCH;
-        }
-        return 0;
-    });
-}
-
-bool rnn_step_bwd_covers(int B, int Hd) { return Hd % 64 == 0 && B > 0; }
-
-int rnn_step_bwd(int lstm, const slnlp_rnn_step_bwd_dir* dirs, int ndir, int B, int Hd, const int64_t* lengths, int64_t ld_dout,
-                 float drop_p, int drop_site, const unsigned long long* rng, int precision, hipStream_t st) {
-    SLNLP_CHECK_ARG(dirs && (ndir == 1 || ndir == 2) && rnn_step_bwd_covers(B, Hd), "rnn_step_bwd: bad args (Hd %% 64 == 0)");
-    SLNLP_CHECK_ARG(precision == 1 || precision == 3, "rnn_step_bwd: precision must be 1 or 3");
-    SLNLP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || rng), "rnn_step_bwd: bad dropout args");
-    const int G = lstm ? 4 : 3;
-    RnnStepBwdParams P;
-    for (int k = 0; k < ndir; ++k) {
-        const slnlp_rnn_step_bwd_dir& d = dirs[k];
-        SLNLP_CHECK_ARG(d.cell.dc_state || !lstm, "rnn_step_bwd: dc_state missing in direction %d", k);
-        SLNLP_CHECK_ARG(d.cell.acts && d.cell.dgx && d.cell.carry && (lstm ? d.cell.cprev_save != nullptr : (d.cell.hprev_save && d.cell.hn_save && d.cell.dgh)),
-                        "rnn_step_bwd: null pointer in direction %d", k);
-        SLNLP_CHECK_ARG(d.dgh_next ? (d.w_hh && vec_ok(d.dgh_next, (long)G * Hd) && vec_ok(d.w_hh, Hd)) : d.cell.dh_state != nullptr,
-                        "rnn_step_bwd: direction %d needs {dgh_next, w_hh} (16-byte aligned) or dh_state", k);
-        SLNLP_CHECK_ARG((dirs[0].dgh_next != nullptr) == (d.dgh_next != nullptr), "rnn_step_bwd: the directions of a launch are both first steps or both not");
-        P.d[k] = d;
-    }
-    if (ndir == 1) P.d[1] = P.d[0];
-    P.B = B; P.Hd = Hd; P.ndir = ndir; P.lengths = (const long*)lengths; P.ld_dout = ld_dout;
-    P.drop_p = drop_p; P.drop_thr = dropout_threshold(drop_p); P.drop_site = drop_site; P.rng = rng;
-    SLNLP_TRY(rnn_step_bwd_init());
-    const dim3 grid(Hd / 16, ndir * ceil_div(B, BM));
-    const dim3 block(G * 256);
-    const void* fn = precision == 3 ? (lstm ? rnn_step_bwd_fn<3, true>() : rnn_step_bwd_fn<3, false>())
-                                    : (lstm ? rnn_step_bwd_fn<1, true>() : rnn_step_bwd_fn<1, false>());
-    const size_t lds = precision == 3 ? (lstm ? rnn_step_bwd_lds<3, true>() : rnn_step_bwd_lds<3, false>())
-                                      : (lstm ? rnn_step_bwd_lds<1, true>() : rnn_step_bwd_lds<1, false>());
-    if (recording()) return record_op(fn, grid, block, lds, REC_Z, &P, sizeof(P), "rnn_step_bwd");
-    const RnnStepBwdParams* tab = nullptr;
-    void* args[2] = {&P, &tab};
-    if (hipLaunchKernel(fn, grid, block, args, lds, st) != hipSuccess) {
-        set_error("rnn_step_bwd: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    return SLNLP_OK;
-}
-
-// grid (Hd / 16, ndir x row tiles, fit): `tab` != nullptr is a lockstep launch, fit z takes tab[z] (launch.hpp)
-// KS = 2: two groups of 256 threads, one half of the K tiles each (gemm_tile's scheme: the K sum is two halves by definition, so the
-// bits do not depend on KS) -- a solo fit's 64-workgroup launch is a chain of 8 K steps, a merged lockstep launch takes KS = 1.
-template <int NSPLIT, bool LSTM, bool EDGE, int KS = 1>
-__global__ __launch_bounds__(256 * KS) void rnn_step_fwd_kernel(const RnnStepParams P0, const RnnStepParams* __restrict__ tab) {
-    RnnStepParams P;
-    if (tab) P = tab[blockIdx.z];
-    else P = P0;
-    P.lengths = as_global(P.lengths);
-    P.rng = as_global(P.rng);
-    constexpr int G = LSTM ? 4 : 3;
-    constexpr int NP = NSPLIT == 3 ? 2 : 1;
-    using TA = TileIO<true, BM>;
-    using TB = TileIO<true, 16>;
-    __shared__ __attribute__((aligned(16))) unsigned short As_all[KS * NP * TA::PLANE];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs_all[KS * G * NP * TB::PLANE];
-    __shared__ f32x4 red[KS == 2 ? G * 256 : 1];               // group 1's half of the K sum on its way to group 0
-    const int grp = KS == 2 ? (int)(threadIdx.x >> 8) : 0;
-    unsigned short* As = As_all + grp * NP * TA::PLANE;
-    unsigned short* Bs = Bs_all + grp * G * NP * TB::PLANE;
-    const int dir = blockIdx.y % P.ndir;
-    const slnlp_rnn_step_dir d = as_global(dir == 0 ? P.d[0] : P.d[1]);
-    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-    const int B = P.B, Hd = P.Hd, j0 = blockIdx.x * 16, bm0 = (blockIdx.y / P.ndir) * BM;
-    const int K = Hd, ktiles = (K + BKT - 1) / BKT;
-
-    f32x4 acc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 ra0[TA::NV], ra1[TA::NV], rb0[G][TB::NV], rb1[G][TB::NV];
-    auto fetch = [&](int kt, float4 (&ra)[TA::NV], float4 (&rb)[G][TB::NV]) {
-        TA::template fetch<true>(d.h_in, Hd, bm0, B, kt * BKT, K, tid, ra);
-#pragma unroll
-        for (int g = 0; g < G; ++g) TB::template fetch<true>(d.w_hh + (long)g * Hd * Hd, Hd, j0, Hd, kt * BKT, K, tid, rb[g]);
-    };
-    auto stash = [&](int kt, const float4 (&ra)[TA::NV], const float4 (&rb)[G][TB::NV]) {
-        // EDGE = false (Hd % 64 == 0): no masks at all -- rows >= B hold a clamped row's data and only feed accumulator
-        // rows that are never stored
-        TA::template stash<NSPLIT, EDGE>(As, tid, ra, bm0, B, kt * BKT, K);
-#pragma unroll
-        for (int g = 0; g < G; ++g) TB::template stash<NSPLIT, EDGE>(Bs + g * NP * TB::PLANE, tid, rb[g], j0, Hd, kt * BKT, K);
-    };
-    auto consume = [&]() {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const bf16x8 ah = TA::frag(As, wave * 16, kk, lane);
-            bf16x8 al = ah;
-            if (NSPLIT == 3) al = TA::frag(As + TA::PLANE, wave * 16, kk, lane);
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const unsigned short* bt = Bs + g * NP * TB::PLANE;
-                const bf16x8 bh = TB::frag(bt, 0, kk, lane);
-                if (NSPLIT == 3) {
-                    const bf16x8 bl = TB::frag(bt + TB::PLANE, 0, kk, lane);
-                    acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc[g], 0, 0, 0);
-                    acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc[g], 0, 0, 0);
-                }
-                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[g], 0, 0, 0);
-            }
-        }
-    };
-    // the cell's own operands are requested first, so their latency hides behind the K loop
-    const int j = j0 + (lane & 15), jj = j < Hd ? j : 0;
-    float bh[G], xpv[4][G], hpv[4], cpv[4];
-#pragma unroll
-    for (int g = 0; g < G; ++g) bh[g] = d.b_hh ? d.b_hh[g * Hd + jj] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = bm0 + wave * 16 + ((lane >> 4) << 2) + r, bb = b < B ? b : 0;
-#pragma unroll
-        for (int g = 0; g < G; ++g) xpv[r][g] = d.xproj[(long)bb * G * Hd + g * Hd + jj];
-        hpv[r] = d.h_in[(long)bb * Hd + jj];
-        cpv[r] = LSTM ? d.c[(long)bb * Hd + jj] : 0.f;
-    }
-    // the K sum in two halves, tiles [0, T) and [T, ktiles), first + second: gemm_tile's definition (bit-identical to GEMM + cell)
-    const int half = (ktiles + 1) / 2;
-    if constexpr (KS == 1) {
-        f32x4 acc_first[G];
-        auto park = [&]() {
-#pragma unroll
-            for (int g = 0; g < G; ++g) { acc_first[g] = acc[g]; acc[g] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        };
-        fetch(0, ra0, rb0);
-        fetch(1, ra1, rb1);
-        for (int kt = 0; kt < ktiles; kt += 2) {
-            if (kt == half) park();
-            lds_barrier();
-            stash(kt, ra0, rb0);
-            lds_barrier();
-            fetch(kt + 2, ra0, rb0);
-            consume();
-            if (kt + 1 >= ktiles) break;
-            if (kt + 1 == half) park();
-            lds_barrier();
-            stash(kt + 1, ra1, rb1);
-            lds_barrier();
-            fetch(kt + 3, ra1, rb1);
-            consume();
-        }
-        if (ktiles <= half) park();
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[g] = acc_first[g] + acc[g];
-    } else {
-        // group g: tiles [k0, k1); both groups make `half` steps (the barriers are the workgroup's), group 1 idles in its last one
-        // when the number of tiles is odd; past-the-end prefetches read a clamped, valid tile and are never stashed
-        const int k0 = grp * half, k1 = grp == 0 ? half : ktiles;
-        fetch(k0, ra0, rb0);
-        fetch(k0 + 1, ra1, rb1);
-        for (int it = 0; it < half; it += 2) {
-            const int kt = k0 + it;
-            lds_barrier();
-            if (kt < k1) stash(kt, ra0, rb0);
-            lds_barrier();
-            fetch(kt + 2, ra0, rb0);
-            if (kt < k1) consume();
-            if (it + 1 >= half) break;
-            lds_barrier();
-            if (kt + 1 < k1) stash(kt + 1, ra1, rb1);
-            lds_barrier();
-            fetch(kt + 3, ra1, rb1);
-            if (kt + 1 < k1) consume();
-        }
-        if (grp == 1) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) red[g * 256 + tid] = acc[g];
-        }
-        __syncthreads();
-        if (grp == 1) return;
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[g] = acc[g] + red[g * 256 + tid];
-    }
-
-    // ---- cell (same arithmetic and order as rnn_cell_fwd_kernel)
-    if (j >= Hd) return;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = bm0 + wave * 16 + ((lane >> 4) << 2) + r;
-        if (b >= B) break;
-        const long idx = (long)b * Hd + j;
-        const bool valid = P.lengths ? (d.t < P.lengths[b]) : true;
-        float* a = d.acts + (long)b * G * Hd;
-        const float hprev = hpv[r];
-        float hnew;
-        if constexpr (LSTM) {
-            const float cprev = cpv[r];
-            const float gi = sigm(xpv[r][0] + (acc[0][r] + bh[0]));
-            const float gf = sigm(xpv[r][1] + (acc[1][r] + bh[1]));
-            const float gg = tanhf(xpv[r][2] + (acc[2][r] + bh[2]));
-            const float go = sigm(xpv[r][3] + (acc[3][r] + bh[3]));
-            const float cnew = gf * cprev + gi * gg;
-            hnew = go * tanhf(cnew);
-            a[j] = gi; a[Hd + j] = gf; a[2 * Hd + j] = gg; a[3 * Hd + j] = go;
-            d.cprev_save[idx] = cprev;
-            d.c[idx] = valid ? cnew : cprev;
-        } else {
-            const float hn = acc[2][r] + bh[2];
-            const float rr = sigm(xpv[r][0] + (acc[0][r] + bh[0]));
-            const float z = sigm(xpv[r][1] + (acc[1][r] + bh[1]));
-            const float nn = tanhf(xpv[r][2] + rr * hn);
-            hnew = (1.f - z) * nn + z * hprev;
-            a[j] = rr; a[Hd + j] = z; a[2 * Hd + j] = nn;
-            d.hn_save[idx] = hn;
-        }
-        d.h_out[idx] = valid ? hnew : hprev;
-        if (d.out) {
-            float o = valid ? hnew : P.fill;
-            if (P.drop_p > 0.f && valid)
-                o = dropout_keep(P.rng, P.drop_site, (unsigned)(d.out_row0 + b), (unsigned)(d.out_col0 + j), P.drop_thr)
-                        ? o / (1.f - P.drop_p) : 0.f;
-            d.out[(long)b * P.ld_out + j] = o;
-        }
-    }
-}
-
-// The same timestep RE-TILED for a solo fit's launch: a workgroup owns 16 batch rows x 16 hidden units x all G gates (grid Hd / 16 x
-// ndir x row tiles of 16: 256 workgroups at B = 50, Hd = 512, two directions -- every CU -- instead of 64), WAVE g computes gate g's
-// 16 x 16 tile, and wave 0 applies the cell once the gates have met in LDS.  Why: such a launch lasts as long as one workgroup takes
-// to LOAD its operands (gemm_rows.hip measured the same for the decoder's products: ~33 GB/s per compute unit), and the 64-row
-// tile above pulls 128 KB of h beside its 128 KB of W_hh per workgroup where this one pulls 32 + 128.  Same K order, same halves,
-// same cell arithmetic per element: bit-identical to rnn_step_fwd_kernel (tests/test_rnn_gpu.py), so a merged lockstep launch --
-// which pays for total bytes, not for one workgroup's -- keeps the 64-row kernel (rnn_step_fwd_for_blocks).
-template <int NSPLIT, bool LSTM, bool EDGE, int KS = 1>
-__global__ __launch_bounds__(256 * KS) void rnn_step_fwd_rt_kernel(const RnnStepParams P0, const RnnStepParams* __restrict__ tab) {
-    RnnStepParams P;
-    if (tab) P = tab[blockIdx.z];
-    else P = P0;
-    P.lengths = as_global(P.lengths);
-    P.rng = as_global(P.rng);
-    constexpr int G = LSTM ? 4 : 3;
-    constexpr int NP = NSPLIT == 3 ? 2 : 1;
-    using TA = TileIO<true, 16>;
-    using TB = TileIO<true, 16>;
-    __shared__ __attribute__((aligned(16))) unsigned short As_all[KS * NP * TA::PLANE];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs_all[KS * G * NP * TB::PLANE];
-    __shared__ f32x4 red[(KS == 2 ? 4 : 0) * 64 + 4 * 64];     // group 1's half of the K sum; then the gates on their way to wave 0
-    const int grp = KS == 2 ? (int)(threadIdx.x >> 8) : 0;
-    unsigned short* As = As_all + grp * NP * TA::PLANE;
-    unsigned short* Bs = Bs_all + grp * G * NP * TB::PLANE;
-    const int dir = blockIdx.y % P.ndir;
-    const slnlp_rnn_step_dir d = as_global(dir == 0 ? P.d[0] : P.d[1]);
-    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;      // wave = gate
-    const int B = P.B, Hd = P.Hd, j0 = blockIdx.x * 16, bm0 = (blockIdx.y / P.ndir) * 16;
-    const int K = Hd, ktiles = (K + BKT - 1) / BKT;
-
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 ra0[TA::NV], ra1[TA::NV], rb0[G][TB::NV], rb1[G][TB::NV];
-    auto fetch = [&](int kt, float4 (&ra)[TA::NV], float4 (&rb)[G][TB::NV]) {
-        TA::template fetch<true>(d.h_in, Hd, bm0, B, kt * BKT, K, tid, ra);
-#pragma unroll
-        for (int g = 0; g < G; ++g) TB::template fetch<true>(d.w_hh + (long)g * Hd * Hd, Hd, j0, Hd, kt * BKT, K, tid, rb[g]);
-    };
-    auto stash = [&](int kt, const float4 (&ra)[TA::NV], const float4 (&rb)[G][TB::NV]) {
-        TA::template stash<NSPLIT, EDGE>(As, tid, ra, bm0, B, kt * BKT, K);
-#pragma unroll
-        for (int g = 0; g < G; ++g) TB::template stash<NSPLIT, EDGE>(Bs + g * NP * TB::PLANE, tid, rb[g], j0, Hd, kt * BKT, K);
-    };
-    auto consume = [&]() {
-        if (wave >= G) return;                                     // (GRU: three gates, the fourth wave only stages)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const bf16x8 ah = TA::frag(As, 0, kk, lane);
-            bf16x8 al = ah;
-            if (NSPLIT == 3) al = TA::frag(As + TA::PLANE, 0, kk, lane);
-            const unsigned short* bt = Bs + wave * NP * TB::PLANE;
-            const bf16x8 bh = TB::frag(bt, 0, kk, lane);
-            if (NSPLIT == 3) {
-                const bf16x8 bl = TB::frag(bt + TB::PLANE, 0, kk, lane);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
-            }
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
-        }
-    };
-    // the cell's own operands are requested first (by the wave that will apply it), so their latency hides behind the K loop
-    const int j = j0 + (lane & 15), jj = j < Hd ? j : 0;
-    float bh[G], xpv[4][G], hpv[4], cpv[4];
-    if (grp == 0 && wave == 0) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) bh[g] = d.b_hh ? d.b_hh[g * Hd + jj] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = bm0 + ((lane >> 4) << 2) + r, bb = b < B ? b : 0;
-#pragma unroll
-            for (int g = 0; g < G; ++g) xpv[r][g] = d.xproj[(long)bb * G * Hd + g * Hd + jj];
-            hpv[r] = d.h_in[(long)bb * Hd + jj];
-            cpv[r] = LSTM ? d.c[(long)bb * Hd + jj] : 0.f;
-        }
-    }
-    // the K sum in two halves, tiles [0, T) and [T, ktiles), first + second: gemm_tile's definition
-    const int half = (ktiles + 1) / 2;
-    if constexpr (KS == 1) {
-        f32x4 acc_first = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto park = [&]() { acc_first = acc; acc = f32x4{0.f, 0.f, 0.f, 0.f}; };
-        fetch(0, ra0, rb0);
-        fetch(1, ra1, rb1);
-        for (int kt = 0; kt < ktiles; kt += 2) {
-            if (kt == half) park();
-            lds_barrier();
-            stash(kt, ra0, rb0);
-            lds_barrier();
-            fetch(kt + 2, ra0, rb0);
-            consume();
-            if (kt + 1 >= ktiles) break;
-            if (kt + 1 == half) park();
-            lds_barrier();
-            stash(kt + 1, ra1, rb1);
-            lds_barrier();
-            fetch(kt + 3, ra1, rb1);
-            consume();
-        }
-        if (ktiles <= half) park();
-        acc = acc_first + acc;
-    } else {
-        const int k0 = grp * half, k1 = grp == 0 ? half : ktiles;
-        fetch(k0, ra0, rb0);
-        fetch(k0 + 1, ra1, rb1);
-        for (int it = 0; it < half; it += 2) {
-            const int kt = k0 + it;
-            lds_barrier();
-            if (kt < k1) stash(kt, ra0, rb0);
-            lds_barrier();
-            fetch(kt + 2, ra0, rb0);
-            if (kt < k1) consume();
-            if (it + 1 >= half) break;
-            lds_barrier();
-            if (kt + 1 < k1) stash(kt + 1, ra1, rb1);
-            lds_barrier();
-            fetch(kt + 3, ra1, rb1);
-            if (kt + 1 < k1) consume();
-        }
-        if (grp == 1) red[4 * 64 + wave * 64 + lane] = acc;
-        __syncthreads();
-        if (grp == 1) return;
-        acc = acc + red[4 * 64 + wave * 64 + lane];
-    }
-    // the gates meet: wave g -> LDS -> wave 0
-    red[wave * 64 + lane] = acc;
-    lds_barrier();                                 // (KS = 2: group 1 has left; the barrier counts the waves that remain)
-    if (wave != 0) return;
-    f32x4 ga[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) ga[g] = red[g * 64 + lane];
-
-    // ---- cell (same arithmetic and order as rnn_cell_fwd_kernel)
-    if (j >= Hd) return;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = bm0 + ((lane >> 4) << 2) + r;
-        if (b >= B) break;
-        const long idx = (long)b * Hd + j;
-        const bool valid = P.lengths ? (d.t < P.lengths[b]) : true;
-        float* a = d.acts + (long)b * G * Hd;
-        const float hprev = hpv[r];
-        float hnew;
-        if constexpr (LSTM) {
-            const float cprev = cpv[r];
-            const float gi = sigm(xpv[r][0] + (ga[0][r] + bh[0]));
-            const float gf = sigm(xpv[r][1] + (ga[1][r] + bh[1]));
-            const float gg = tanhf(xpv[r][2] + (ga[2][r] + bh[2]));
-            const float go = sigm(xpv[r][3] + (ga[3][r] + bh[3]));
-            const float cnew = gf * cprev + gi * gg;
-            hnew = go * tanhf(cnew);
-            a[j] = gi; a[Hd + j] = gf; a[2 * Hd + j] = gg; a[3 * Hd + j] = go;
-            d.cprev_save[idx] = cprev;
-            d.c[idx] = valid ? cnew : cprev;
-        } else {
-            const float hn = ga[2][r] + bh[2];
-            const float rr = sigm(xpv[r][0] + (ga[0][r] + bh[0]));
-            const float z = sigm(xpv[r][1] + (ga[1][r] + bh[1]));
-            const float nn = tanhf(xpv[r][2] + rr * hn);
-            hnew = (1.f - z) * nn + z * hprev;
-            a[j] = rr; a[Hd + j] = z; a[2 * Hd + j] = nn;
-            d.hn_save[idx] = hn;
-        }
-        d.h_out[idx] = valid ? hnew : hprev;
-        if (d.out) {
-            float o = valid ? hnew : P.fill;
-            if (P.drop_p > 0.f && valid)
-                o = dropout_keep(P.rng, P.drop_site, (unsigned)(d.out_row0 + b), (unsigned)(d.out_col0 + j), P.drop_thr)
-                        ? o / (1.f - P.drop_p) : 0.f;
-            d.out[(long)b * P.ld_out + j] = o;
-        }
-    }
-}
-
-// The kernel a MERGED launch of `blocks` workgroups runs in place of the recorded forward-step kernel `fn` (nullptr: `fn` is not one
-// of them, or is the right one already): same results, the thread-group count of the merged size.
-// kernel table: [precision 3 / 1][LSTM / GRU][EDGE][16-row re-tiled?][KS - 1]
-static const void* rnn_step_kernel(int ns, bool lstm, bool edge, bool rt, int ks) {
-#define SLNLP_RS(NS, L, E) (rt ? (ks == 2 ? (const void*)rnn_step_fwd_rt_kernel<NS, L, E, 2> : (const void*)rnn_step_fwd_rt_kernel<NS, L, E, 1>) \
-                               : (ks == 2 ? (const void*)rnn_step_fwd_kernel<NS, L, E, 2> : (const void*)rnn_step_fwd_kernel<NS, L, E, 1>))
-    if (ns == 3) {
-        if (lstm) return edge ? SLNLP_RS(3, true, true) : SLNLP_RS(3, true, false);
-        return edge ? SLNLP_RS(3, false, true) : SLNLP_RS(3, false, false);
-    }
-    if (lstm) return edge ? SLNLP_RS(1, true, true) : SLNLP_RS(1, true, false);
-    return edge ? SLNLP_RS(1, false, true) : SLNLP_RS(1, false, false);
-#undef SLNLP_RS
-}
-// slnlp_set_rnn_step_tile / SLNLP_RNN_STEP_RT=0: the 64-row tile for solo launches too (tests, A / B measurements; same bits)
-static std::atomic<int> g_rnn_step_rt{[] { const char* e = getenv("SLNLP_RNN_STEP_RT"); return (e && atoi(e) == 0) ? 0 : 1; }()};
-static bool rnn_step_rt_enabled() { return g_rnn_step_rt.load(std::memory_order_relaxed) != 0; }
-// which tiling / thread groups a launch of `fits` timesteps [B x Hd, ndir directions] takes: the 16-row tile while it still fits the
-// chip about twice over (a launch-latency chain: one fit), the 64-row tile (a third of the operand bytes in total) beyond
-static void rnn_step_shape(int B, int Hd, int ndir, int fits, bool* rt, int* ks, dim3* grid) {
-    const int gx = ceil_div(Hd, 16), rt_blocks = gx * ndir * ceil_div(B, 16) * fits;
-    *rt = rnn_step_rt_enabled() && B > 16 && rt_blocks <= 512;
-    *grid = dim3(gx, ndir * ceil_div(B, *rt ? 16 : BM));
-    *ks = gemm_group_ks((int)(grid->x * grid->y) * fits, ceil_div(Hd, BKT));
-}
-// The kernel a MERGED launch of `fits` fits runs in place of the recorded forward-step kernel `fn` (nullptr: `fn` is not one of them):
-// same results, the tiling and thread-group count of the merged size.  `grid`: in = the recorded (x, y), out = the merged one.
-const void* rnn_step_fwd_for_blocks(const void* fn, const void* recorded_args, int fits, int* threads, dim3* grid) {
-    for (int ns = 1; ns <= 3; ns += 2)
-        for (int l = 0; l < 2; ++l)
-            for (int e = 0; e < 2; ++e)
-                for (int rt = 0; rt < 2; ++rt)
-                    for (int ks = 1; ks <= 2; ++ks)
-                        if (fn == rnn_step_kernel(ns, l != 0, e != 0, rt != 0, ks)) {
-                            const RnnStepParams& P = *static_cast<const RnnStepParams*>(recorded_args);
-                            bool mrt;
-                            int mks;
-                            rnn_step_shape(P.B, P.Hd, P.ndir, fits, &mrt, &mks, grid);
-                            *threads = 256 * mks;
-                            return rnn_step_kernel(ns, l != 0, e != 0, mrt, mks);
-                        }
-    return nullptr;
-}
-
-int rnn_step_fwd(int lstm, const slnlp_rnn_step_dir* dirs, int ndir, int B, int Hd, const int64_t* lengths, float fill,
-                 int64_t ld_out, float drop_p, int drop_site, const unsigned long long* rng, int precision, hipStream_t st) {
-    SLNLP_CHECK_ARG(dirs && (ndir == 1 || ndir == 2) && B > 0 && Hd > 0 && Hd % 4 == 0, "rnn_step_fwd: bad args (Hd %% 4 == 0)");
-    SLNLP_CHECK_ARG(precision == 1 || precision == 3, "rnn_step_fwd: precision must be 1 or 3");
-    SLNLP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || rng), "rnn_step_fwd: bad dropout args");
-    RnnStepParams P;
-    for (int k = 0; k < ndir; ++k) {
-        const slnlp_rnn_step_dir& d = dirs[k];
-        SLNLP_CHECK_ARG(d.h_in && d.h_out && d.h_in != d.h_out && d.w_hh && d.xproj && d.acts &&
-                            (lstm ? (d.c && d.cprev_save) : (d.hn_save != nullptr)),
-                        "rnn_step_fwd: null pointer (or h_in == h_out) in direction %d", k);
-        SLNLP_CHECK_ARG(vec_ok(d.h_in, Hd) && vec_ok(d.w_hh, Hd), "rnn_step_fwd: h_in / w_hh must be 16-byte aligned");
-        P.d[k] = d;
-    }
-    if (ndir == 1) P.d[1] = P.d[0];
-    P.B = B; P.Hd = Hd; P.ndir = ndir; P.lengths = (const long*)lengths; P.fill = fill; P.ld_out = ld_out;
-    P.drop_p = drop_p; P.drop_thr = dropout_threshold(drop_p); P.drop_site = drop_site; P.rng = rng;
-    const bool edge = (Hd % BKT) != 0;
-    // tile and thread groups for ONE fit's launch (a merged lockstep launch picks again for its size: rnn_step_fwd_for_blocks)
-    bool rt;
-    int ks;
-    dim3 grid;
-    rnn_step_shape(B, Hd, ndir, 1, &rt, &ks, &grid);
-    const void* fn = rnn_step_kernel(precision, lstm != 0, edge, rt, ks);
-    if (recording()) return record_op(fn, grid, dim3(256 * ks), 0, REC_Z, &P, sizeof(P), "rnn_step_fwd");
-    const RnnStepParams* no_tab = nullptr;
-    void* args[2] = {&P, &no_tab};
-    if (hipLaunchKernel(fn, grid, dim3(256 * ks), args, 0, st) != hipSuccess) {
-        set_error("rnn_step_fwd: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    return SLNLP_OK;
-}
-
-// ------------------------------------------------------- persistent recurrent layer ---
-// ALL S timesteps of one bidirectional LSTM / GRU layer in ONE launch.  The per-timestep kernel above is ~5 us of
-// launch latency plus a K loop that re-reads and re-converts the same W_hh slice 48 times; here a workgroup keeps its
-// slice of W_hh (the G x 16 rows of its 16 hidden units, all K) in LDS as bf16 hi/lo for the whole sequence
-// (128 KiB at Hd = 512) and only streams h_{t-1} per step.  The Hd/16 x ndir co-resident workgroups meet at a
-// device-wide barrier between steps (sense-reversing counter, agent-scope atomics, bounded spin: 1.35 us for 64
-// workgroups, tools/micro/grid_barrier.hip); the new state is written with sc1 (write-through) stores and drained
-// before the barrier, and every h slot is written once and read only afterwards, so no workgroup can see a stale
-// L1 / L2 line -- no fences (an agent-scope fence is a whole-L2 write-back on this part).
-// Same K order and split as rnn_step_fwd_kernel -> bit-identical results.
-// Measured (round 1): 13.9 us per timestep, no faster than the per-timestep launches (13.4 us) -- with one wave per SIMD
-// the K loop (convert h_{t-1}, two block barriers per K tile, LDS fragment reads exposed in front of every MFMA group)
-// costs ~8 us, and h_{t-1} arrives from the memory side.  It is therefore OPT-IN (slnlp_rnn_set_persistent); the plan
-// for it: 8 waves (two per SIMD, gates split over wave pairs) and the state exchanged as bf16 planes via LDS-DMA.
-struct RnnLayerParams {
-    slnlp_rnn_layer_dir d[2];
-    int B, Hd, S;
-    const long* lengths;
-    float fill;
-    long ld_out;
-    float drop_p;
-    unsigned drop_thr;
-    int drop_site;
-    const unsigned long long* rng;
-    unsigned* bar;      // {count, generation}
-    int* err;
-};
-
-__device__ __forceinline__ void grid_barrier_sr(unsigned* bar, int* err, unsigned nblocks) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's sc1 stores have reached the memory side
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned gen = __hip_atomic_load(bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblocks - 1) {
-            __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the reset lands before anyone is released
-            __hip_atomic_fetch_add(bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            long spins = 0;
-            while (__hip_atomic_load(bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > 4000000) { *err = 1; break; }     // never hang: flag the step as invalid and move on
-            }
-        }
-    }
-    __syncthreads();
-}
-
-template <int NSPLIT, bool LSTM>
-__global__ __launch_bounds__(256) void rnn_layer_fwd_kernel(const RnnLayerParams P) {
-    constexpr int G = LSTM ? 4 : 3;
-    constexpr int NP = NSPLIT == 3 ? 2 : 1;
-    using TA = TileIO<true, BM>;
-    using TB = TileIO<true, 16>;
-    extern __shared__ __attribute__((aligned(16))) unsigned short lsm[];
-    const slnlp_rnn_layer_dir& d = P.d[blockIdx.y];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int B = P.B, Hd = P.Hd, S = P.S, j0 = blockIdx.x * 16, GH = G * Hd;
-    const int K = Hd, ktiles = K / BKT;                          // host guarantees Hd % 64 == 0, B <= 64
-    unsigned short* Wl = lsm;                                    // [ktile][gate][plane][16 x 64]
-    unsigned short* As = lsm + (size_t)ktiles * G * NP * TB::PLANE;
-    const unsigned nblocks = gridDim.x * gridDim.y;
-
-    // ---- resident weight slice: rows g*Hd + j0 .. +15 of W_hh, every K tile, split once
-    for (int kt = 0; kt < ktiles; ++kt)
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            float4 rw[TB::NV];
-            TB::template fetch<true>(d.w_hh + (long)g * Hd * Hd, Hd, j0, Hd, kt * BKT, K, tid, rw);
-            TB::template stash<NSPLIT, false>(Wl + ((size_t)kt * G + g) * NP * TB::PLANE, tid, rw, j0, Hd, kt * BKT, K);
-        }
-    const int j = j0 + (lane & 15);
-    float bh[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) bh[g] = d.b_hh ? d.b_hh[g * Hd + j] : 0.f;
-    const bool rev = d.reverse != 0;
-
-    for (int step = 0; step < S; ++step) {
-        const int t = rev ? S - 1 - step : step, tn = rev ? t - 1 : t + 1;
-        const float* h_in = d.hprev + (long)t * B * Hd;
-        float* h_out = step + 1 < S ? d.hprev + (long)tn * B * Hd : d.h_final;
-        const float* xproj = d.xproj + (long)t * B * GH;
-        // the cell's own operands first: their latency hides behind the K loop
-        float xpv[4][G], hpv[4], cpv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = wave * 16 + ((lane >> 4) << 2) + r, bb = b < B ? b : 0;
-#pragma unroll
-            for (int g = 0; g < G; ++g) xpv[r][g] = xproj[(long)bb * GH + g * Hd + j];
-            hpv[r] = h_in[(long)bb * Hd + j];
-            cpv[r] = LSTM ? d.c[(long)bb * Hd + j] : 0.f;
-        }
-        f32x4 acc[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float4 ra0[TA::NV], ra1[TA::NV];
-        TA::template fetch<true>(h_in, Hd, 0, B, 0, K, tid, ra0);
-        TA::template fetch<true>(h_in, Hd, 0, B, BKT, K, tid, ra1);
-        auto consume = [&](int kt) {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const bf16x8 ah = TA::frag(As, wave * 16, kk, lane);
-                bf16x8 al = ah;
-                if (NSPLIT == 3) al = TA::frag(As + TA::PLANE, wave * 16, kk, lane);
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    const unsigned short* bt = Wl + ((size_t)kt * G + g) * NP * TB::PLANE;
-                    const bf16x8 bhf = TB::frag(bt, 0, kk, lane);
-                    if (NSPLIT == 3) {
-                        const bf16x8 blf = TB::frag(bt + TB::PLANE, 0, kk, lane);
-                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bhf, acc[g], 0, 0, 0);
-                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, blf, acc[g], 0, 0, 0);
-                    }
-                    acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bhf, acc[g], 0, 0, 0);
-                }
-            }
-        };
-        // the K sum in two halves, tiles [0, T) and [T, ktiles), first + second: gemm_tile's definition
-        const int half = (ktiles + 1) / 2;
-        f32x4 acc_first[G];
-        auto park = [&]() {
-#pragma unroll
-            for (int g = 0; g < G; ++g) { acc_first[g] = acc[g]; acc[g] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        };
-        for (int kt = 0; kt < ktiles; kt += 2) {
-            if (kt == half) park();
-            lds_barrier();
-            TA::template stash<NSPLIT, false>(As, tid, ra0, 0, B, kt * BKT, K);
-            lds_barrier();
-            TA::template fetch<true>(h_in, Hd, 0, B, (kt + 2) * BKT, K, tid, ra0);
-            consume(kt);
-            if (kt + 1 >= ktiles) break;
-            if (kt + 1 == half) park();
-            lds_barrier();
-            TA::template stash<NSPLIT, false>(As, tid, ra1, 0, B, (kt + 1) * BKT, K);
-            lds_barrier();
-            TA::template fetch<true>(h_in, Hd, 0, B, (kt + 3) * BKT, K, tid, ra1);
-            consume(kt + 1);
-        }
-        if (ktiles <= half) park();
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[g] = acc_first[g] + acc[g];
-        // ---- cell (same arithmetic and order as rnn_cell_fwd_kernel)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = wave * 16 + ((lane >> 4) << 2) + r;
-            if (b >= B) break;
-            const long idx = (long)b * Hd + j;
-            const bool valid = P.lengths ? (t < P.lengths[b]) : true;
-            float* a = d.acts + (long)t * B * GH + (long)b * GH;
-            const float hprev = hpv[r];
-            float hnew;
-            if constexpr (LSTM) {
-                const float cprev = cpv[r];
-                const float gi = sigm(xpv[r][0] + (acc[0][r] + bh[0]));
-                const float gf = sigm(xpv[r][1] + (acc[1][r] + bh[1]));
-                const float gg = tanhf(xpv[r][2] + (acc[2][r] + bh[2]));
-                const float go = sigm(xpv[r][3] + (acc[3][r] + bh[3]));
-                const float cnew = gf * cprev + gi * gg;
-                hnew = go * tanhf(cnew);
-                a[j] = gi; a[Hd + j] = gf; a[2 * Hd + j] = gg; a[3 * Hd + j] = go;
-                d.cprev[(long)t * B * Hd + idx] = cprev;
-                d.c[idx] = valid ? cnew : cprev;
-            } else {
-                const float hn = acc[2][r] + bh[2];
-                const float rr = sigm(xpv[r][0] + (acc[0][r] + bh[0]));
-                const float z = sigm(xpv[r][1] + (acc[1][r] + bh[1]));
-                const float nn = tanhf(xpv[r][2] + rr * hn);
-                hnew = (1.f - z) * nn + z * hprev;
-                a[j] = rr; a[Hd + j] = z; a[2 * Hd + j] = nn;
-                d.hn[(long)t * B * Hd + idx] = hn;
-            }
-            // the next step's workgroups (other XCDs) read this: write-through store
-            __hip_atomic_store(h_out + idx, valid ? hnew : hprev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (d.out) {
-                float o = valid ? hnew : P.fill;
-                if (P.drop_p > 0.f && valid)
-                    o = dropout_keep(P.rng, P.drop_site, (unsigned)(t * B + b), (unsigned)(d.out_col0 + j), P.drop_thr)
-                            ? o / (1.f - P.drop_p) : 0.f;
-                d.out[((long)t * B + b) * P.ld_out + j] = o;
-            }
-        }
-        if (step + 1 < S) grid_barrier_sr(P.bar, P.err, nblocks);
-    }
-}
-
-// one-time opt-in to > 64 KiB dynamic LDS; called from plan creation so it never lands inside a graph capture
-int rnn_layer_init() {
-    static DeviceOnce once;                     // hipFuncSetAttribute applies per device
-    return once.run([]() -> int {
-    const int lim = 156 * 1024;
-    const bool ok =
-        hipFuncSetAttribute((const void*)rnn_layer_fwd_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess &&
-        hipFuncSetAttribute((const void*)rnn_layer_fwd_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess &&
-        hipFuncSetAttribute((const void*)rnn_layer_fwd_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess &&
-        hipFuncSetAttribute((const void*)rnn_layer_fwd_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) == hipSuccess;
-    if (!ok) {
-        set_error("rnn_layer_init: cannot raise dynamic LDS limit: %s", hipGetErrorString(hipGetLastError()));
-        return SLNLP_ERR_LAUNCH;
-    }
-    return 0;
-    });
-}
-
-static size_t rnn_layer_lds(int G, int Hd, int precision) {
-    const int NP = precision == 3 ? 2 : 1;
-    return ((size_t)(Hd / BKT) * G * NP * TileIO<true, 16>::PLANE + (size_t)NP * TileIO<true, BM>::PLANE) * sizeof(unsigned short);
-}
-
-// 0 = launched; 1 = shape not covered by the persistent kernel (caller uses the per-timestep path)
-int rnn_layer_fwd(int lstm, const slnlp_rnn_layer_dir* dirs, int ndir, int B, int Hd, int S, const int64_t* lengths,
-                  float fill, int64_t ld_out, float drop_p, int drop_site, const unsigned long long* rng, int precision,
-                  unsigned* bar, int* err, int* launched, hipStream_t st) {
-    SLNLP_CHECK_ARG(dirs && (ndir == 1 || ndir == 2) && B > 0 && Hd > 0 && S > 0 && bar && err && launched, "rnn_layer_fwd: bad args");
-    SLNLP_CHECK_ARG(precision == 1 || precision == 3, "rnn_layer_fwd: precision must be 1 or 3");
-    SLNLP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || rng), "rnn_layer_fwd: bad dropout args");
-    const int G = lstm ? 4 : 3;
-    const size_t lds = rnn_layer_lds(G, Hd, precision);
-    *launched = 0;
-    if (B > BM || Hd % BKT != 0 || lds > 156 * 1024 || (Hd / 16) * ndir > 128) return SLNLP_OK;   // not covered
-    RnnLayerParams P;
-    for (int k = 0; k < ndir; ++k) {
-        const slnlp_rnn_layer_dir& d = dirs[k];
-        SLNLP_CHECK_ARG(d.hprev && d.h_final && d.w_hh && d.xproj && d.acts && (lstm ? (d.c && d.cprev) : (d.hn != nullptr)),
-                        "rnn_layer_fwd: null pointer in direction %d", k);
-        SLNLP_CHECK_ARG(vec_ok(d.hprev, Hd) && vec_ok(d.w_hh, Hd) && ((long)B * Hd) % 4 == 0, "rnn_layer_fwd: hprev / w_hh must be 16-byte aligned");
-        P.d[k] = d;
-    }
-    if (ndir == 1) P.d[1] = P.d[0];
-    P.B = B; P.Hd = Hd; P.S = S; P.lengths = (const long*)lengths; P.fill = fill; P.ld_out = ld_out;
-    P.drop_p = drop_p; P.drop_thr = dropout_threshold(drop_p); P.drop_site = drop_site; P.rng = rng;
-    P.bar = bar; P.err = err;
-    const dim3 grid(Hd / 16, ndir);
-    SLNLP_TRY(rnn_layer_init());
-#define SLNLP_LAYER(NS, L) hipLaunchKernelGGL((rnn_layer_fwd_kernel<NS, L>), grid, dim3(256), lds, st, P)
-    if (precision == 3) { if (lstm) SLNLP_LAYER(3, true); else SLNLP_LAYER(3, false); }
-    else { if (lstm) SLNLP_LAYER(1, true); else SLNLP_LAYER(1, false); }
-#undef SLNLP_LAYER
-    SLNLP_CHECK_LAUNCH("rnn_layer_fwd");
-    *launched = 1;
-    return SLNLP_OK;
-}
-
 }  // namespace slnlp
-
-extern "C" int slnlp_rnn_layer_fwd(int lstm, const slnlp_rnn_layer_dir* dirs, int ndir, int B, int Hd, int S,
-                                   const int64_t* lengths, float fill, int64_t ld_out, float drop_p, int drop_site,
-                                   const unsigned long long* rng, int precision, uint32_t* sync, int* launched, void* stream) {
-    if (!sync) {
-        slnlp::set_error("slnlp_rnn_layer_fwd: sync words required");
-        return SLNLP_ERR_INVALID_ARG;
-    }
-    return slnlp::rnn_layer_fwd(lstm, dirs, ndir, B, Hd, S, lengths, fill, ld_out, drop_p, drop_site, rng, precision, sync,
-                                reinterpret_cast<int*>(sync + 2), launched, (hipStream_t)stream);
-}
-
-extern "C" int slnlp_rnn_step_bwd(int lstm, const slnlp_rnn_step_bwd_dir* dirs, int ndir, int B, int Hd, const int64_t* lengths,
-                                  int64_t ld_dout, float drop_p, int drop_site, const unsigned long long* rng, int precision,
-                                  void* stream) {
-    return slnlp::rnn_step_bwd(lstm, dirs, ndir, B, Hd, lengths, ld_dout, drop_p, drop_site, rng, precision, (hipStream_t)stream);
-}
-
-extern "C" int slnlp_rnn_step_fwd(int lstm, const slnlp_rnn_step_dir* dirs, int ndir, int B, int Hd, const int64_t* lengths,
-                                  float fill, int64_t ld_out, float drop_p, int drop_site, const unsigned long long* rng,
-                                  int precision, void* stream) {
-    return slnlp::rnn_step_fwd(lstm, dirs, ndir, B, Hd, lengths, fill, ld_out, drop_p, drop_site, rng, precision,
-                               (hipStream_t)stream);
-}
 
 extern "C" int slnlp_gemm(const slnlp_gemm_args* args, void* stream) {
     if (!args) {
@@ -1674,10 +583,5 @@ extern "C" int slnlp_set_gemm_ks(int ks) {
         return SLNLP_ERR_INVALID_ARG;
     }
     slnlp::g_gemm_ks.store(ks == 0 ? -1 : ks, std::memory_order_relaxed);
-    return 0;
-}
-
-extern "C" int slnlp_set_rnn_step_tile(int rows16) {
-    slnlp::g_rnn_step_rt.store(rows16 ? 1 : 0, std::memory_order_relaxed);
     return 0;
 }

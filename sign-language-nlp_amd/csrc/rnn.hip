@@ -4,13 +4,13 @@
 //
 // The matmuls around the cell (x W_ih^T for all timesteps at once, h_{t-1} W_hh^T per step, and
 // every dgrad / wgrad) run on the MFMA GEMM (gemm.hip); these kernels are the fp32 glue between
-// them.  Gate order follows torch.nn.LSTM (i,f,g,o) / torch.nn.GRU (r,z,n), which the reference
-// instantiates at bkp.py:95-100,186-190.
+// them.  The cell arithmetic itself is in rnn_cell.hpp, shared with the fused kernels of
+// rnn_step.hip.  Gate order follows torch.nn.LSTM (i,f,g,o) / torch.nn.GRU (r,z,n), which the
+// reference instantiates at bkp.py:95-100,186-190.
 #include "launch.hpp"
+#include "rnn_cell.hpp"
 
 namespace slnlp {
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ------------------------------------------------------------------- forward
 // One launch = one timestep of up to two directions (blockIdx.y).  Sequence b advances only while
@@ -21,46 +21,32 @@ __device__ __forceinline__ void rnn_cell_fwd_body(slnlp_rnn_cell_dir d0, slnlp_r
                                                   const long* __restrict__ lengths, float fill, long ld_out, float drop_p,
                                                   unsigned drop_thr, int drop_site, const unsigned long long* __restrict__ rng) {
     const slnlp_rnn_cell_dir d = blockIdx.y == 0 ? d0 : d1;
-    const int G = LSTM ? 4 : 3;
+    constexpr int G = LSTM ? 4 : 3;
     const long n = (long)B * Hd;
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
         const int b = (int)(idx / Hd), j = (int)(idx % Hd);
         const bool valid = lengths ? (d.t < lengths[b]) : true;
         const float* xp = d.xproj + (long)b * G * Hd;
         const float* hp = d.hproj + (long)b * G * Hd;
-        const float hprev = d.h[idx];
-        float hnew;
+        const float hprev = d.h[idx], cprev = LSTM ? d.c[idx] : 0.f;
+        float xg[G], hg[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) { xg[g] = xp[g * Hd + j]; hg[g] = hp[g * Hd + j]; }
+        const RnnCellFwd<LSTM> o = rnn_cell_fwd_elem<LSTM>(xg, hg, hprev, cprev);
+        float* a = d.acts + (long)b * G * Hd;
+#pragma unroll
+        for (int g = 0; g < G; ++g) a[g * Hd + j] = o.act[g];
         if (LSTM) {
-            const float cprev = d.c[idx];
-            const float gi = sigmoidf_(xp[j] + hp[j]);
-            const float gf = sigmoidf_(xp[Hd + j] + hp[Hd + j]);
-            const float gg = tanhf(xp[2 * Hd + j] + hp[2 * Hd + j]);
-            const float go = sigmoidf_(xp[3 * Hd + j] + hp[3 * Hd + j]);
-            const float cnew = gf * cprev + gi * gg;
-            hnew = go * tanhf(cnew);
-            float* a = d.acts + (long)b * G * Hd;
-            a[j] = gi; a[Hd + j] = gf; a[2 * Hd + j] = gg; a[3 * Hd + j] = go;
             d.cprev_save[idx] = cprev;
-            d.c[idx] = valid ? cnew : cprev;
+            d.c[idx] = valid ? o.cnew : cprev;
         } else {
-            const float hn = hp[2 * Hd + j];
-            const float r = sigmoidf_(xp[j] + hp[j]);
-            const float z = sigmoidf_(xp[Hd + j] + hp[Hd + j]);
-            const float nn = tanhf(xp[2 * Hd + j] + r * hn);
-            hnew = (1.f - z) * nn + z * hprev;
-            float* a = d.acts + (long)b * G * Hd;
-            a[j] = r; a[Hd + j] = z; a[2 * Hd + j] = nn;
-            d.hn_save[idx] = hn;
+            d.hn_save[idx] = o.hn;
         }
         d.hprev_save[idx] = hprev;
-        d.h[idx] = valid ? hnew : hprev;
-        if (d.out) {
-            float o = valid ? hnew : fill;
-            if (drop_p > 0.f && valid)
-                o = dropout_keep(rng, drop_site, (unsigned)(d.out_row0 + b), (unsigned)(d.out_col0 + j), drop_thr)
-                        ? o / (1.f - drop_p) : 0.f;
-            d.out[(long)b * ld_out + j] = o;
-        }
+        d.h[idx] = valid ? o.hnew : hprev;
+        if (d.out)
+            d.out[(long)b * ld_out + j] = rnn_cell_out(valid, o.hnew, fill, drop_p, drop_thr, drop_site, rng, (unsigned)(d.out_row0 + b),
+                                                       (unsigned)(d.out_col0 + j));
     }
 }
 
@@ -86,7 +72,7 @@ __device__ __forceinline__ void rnn_cell_bwd_body(slnlp_rnn_cell_bwd_dir d0, sln
                                                   const long* __restrict__ lengths, long ld_dout, float drop_p, unsigned drop_thr,
                                                   int drop_site, const unsigned long long* __restrict__ rng) {
     const slnlp_rnn_cell_bwd_dir d = blockIdx.y == 0 ? d0 : d1;
-    const int G = LSTM ? 4 : 3;
+    constexpr int G = LSTM ? 4 : 3;
     const long n = (long)B * Hd;
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
         const int b = (int)(idx / Hd), j = (int)(idx % Hd);
@@ -129,10 +115,12 @@ __device__ __forceinline__ void rnn_cell_bwd_body(slnlp_rnn_cell_bwd_dir d0, sln
                         ? g / (1.f - drop_p) : 0.f;
             dh += g;
         }
+        // rnn_cell_bwd_elem's formulas (rnn_cell.hpp), kept in place: through the shared function this kernel, which lives at
+        // the edge of its scalar registers, compiles to another allocation with more waits
         if (LSTM) {
             const float gi = a0, gf = a1, gg = a2, go = a3;
             const float cprev = s0;
-            const float tc = tanhf(gf * cprev + gi * gg);
+            const float tc = tanhf(lstm_cnew(gi, gf, gg, cprev));
             const float dc = s1 + dh * go * (1.f - tc * tc);
             gx[j] = dc * gg * gi * (1.f - gi);
             gx[Hd + j] = dc * cprev * gf * (1.f - gf);

@@ -239,7 +239,7 @@ struct slnlp_rnn_plan : PlanCore {
     bool use_planes = false;  // E, Hd multiples of 64: the M = S*B GEMMs run on pre-split bf16 planes (gemm_planes.hip)
     bool persistent = false;  // opt-in: all timesteps of an encoder layer in one launch (not yet faster; needs one fit per GPU)
     // backward through time: the cell kernel + K-sliced grouped GEMM pair per timestep (default), or ONE launch per timestep
-    // (gemm.hip rnn_step_bwd_kernel; slnlp_rnn_set_fused_backward(plan, 1), env SLNLP_RNN_FUSED_BWD=1).  Round 4 built the
+    // (rnn_step.hip rnn_step_bwd_kernel; slnlp_rnn_set_fused_backward(plan, 1), env SLNLP_RNN_FUSED_BWD=1).  Round 4 built the
     // fused kernel to halve the 384 dependent launches of a cfg3 backward and measured it SLOWER solo (LSTM 9.11 vs 8.09 ms, GRU
     // 7.73 vs 7.27): its G K-slices share one CU's LDS-write and conversion bandwidth where the K-sliced launch spreads them over
     // 256 CUs, and a timestep is a latency chain either way.  16 GRU fits in lockstep gain 4 % from it.
@@ -391,7 +391,7 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
         // inter-layer dropout (not after the last layer); padded outputs of the LAST layer = float(pad_idx)
         const float fill = last ? (float)c.pad_src : 0.f, pdrop = last ? 0.f : p;
         int launched = 0;
-        if (pl->persistent) {   // all S timesteps of both directions in ONE launch (gemm.hip rnn_layer_fwd_kernel)
+        if (pl->persistent) {   // all S timesteps of both directions in ONE launch (rnn_step.hip rnn_layer_fwd_kernel)
             slnlp_rnn_layer_dir ld[2];
             for (int d = 0; d < 2; ++d) {
                 const RnnW& q = L.enc[d][l];
@@ -472,7 +472,7 @@ int slnlp_rnn_forward(slnlp_rnn_plan* pl, const int64_t* X, const int64_t* y, co
     return 0;
 }
 
-// on = 1: all timesteps of an encoder layer in ONE persistent launch (gemm.hip rnn_layer_fwd_kernel) instead of one
+// on = 1: all timesteps of an encoder layer in ONE persistent launch (rnn_step.hip rnn_layer_fwd_kernel) instead of one
 // launch per timestep.  Off by default: measured no faster yet, and its workgroups must all be resident at once, so it
 // must not be used when several fits share the GPU.
 int slnlp_rnn_set_fused_backward(slnlp_rnn_plan* pl, int on) {
@@ -576,7 +576,7 @@ int slnlp_rnn_backward(slnlp_rnn_plan* pl, void* stream) {
             SLNLP_TRY(add_rows(w.denc_final + (long)l * B * 2 * Hd + d * Hd, 2 * Hd, a.d[d].dh, Hd, B, Hd, 0, st));
         }
         const int nsl = pl->kslices(), Ks = GH / nsl;
-        // one launch per timestep (gemm.hip rnn_step_bwd_kernel: the recurrent dgrad of the step before + this step's cell
+        // one launch per timestep (rnn_step.hip rnn_step_bwd_kernel: the recurrent dgrad of the step before + this step's cell
         // backward); shapes it does not cover -- and SLNLP_RNN_UNFUSED_BWD=1, the comparison path of the tests -- take the
         // cell kernel + K-sliced grouped GEMM pair
         const bool fused_bwd = rnn_step_bwd_covers(B, Hd) && !pl->unfused_bwd;

@@ -175,11 +175,14 @@ def test_fused_backward_step_equals_cell_plus_ksliced_gemm(rnn_type, name):
 
 
 @pytest.mark.parametrize("lstm", [1, 0])
-@pytest.mark.parametrize("B,Hd,ndir", [(50, 512, 2), (50, 512, 1), (33, 256, 2), (70, 64, 2), (20, 40, 1)])
+@pytest.mark.parametrize("B,Hd,ndir", [(50, 512, 2), (50, 512, 1), (33, 256, 2), (70, 64, 2), (20, 40, 1), (17, 192, 1)])
 def test_recurrent_step_tiles_return_the_same_bits(lstm, B, Hd, ndir):
     """The fused forward timestep on its two tiles -- 16 batch rows per workgroup with the gates on four waves (one fit's launch:
     every CU gets a workgroup) and 64 rows with the gates in one wave's accumulators (merged lockstep launches) -- must agree bit
-    for bit (slnlp_set_rnn_step_tile): same K order, same halves, same cell arithmetic per element."""
+    for bit (slnlp_set_rnn_step_tile): same K order, same halves, same cell arithmetic per element.  So must the two schedules of
+    the K halves on either tile (slnlp_set_gemm_ks: one thread group that parks the first half, or one group per half): all four
+    (tile, ks) combinations return the same bits.  (17, 192, 1): three K tiles, the smallest odd count above one -- group 1 of a
+    two-group workgroup idles in its last trip -- with B just above 16 so that the 16-row tile is taken."""
     import ctypes as C
     from slnlp import ops
     from slnlp._lib import RnnStepDir, check, load, ptr, stream_ptr
@@ -192,8 +195,9 @@ def test_recurrent_step_tiles_return_the_same_bits(lstm, B, Hd, ndir):
     t, p, site, fill, ld_out = 2, 0.2, 40, 1.0, 2 * Hd
     res = []
     try:
-        for tile in (1, 0):
+        for tile, ks in ((1, 1), (0, 1), (1, 2), (0, 2)):
             load().slnlp_set_rnn_step_tile(tile)
+            check(load().slnlp_set_gemm_ks(ks), "set_gemm_ks")
             bufs = dict(acts=torch.zeros(ndir, B, G * Hd).cuda(), cprev=torch.zeros(ndir, B, Hd).cuda(), hn=torch.zeros(ndir, B, Hd).cuda(),
                         out=torch.zeros(B, ld_out).cuda(), c=c.clone(), h_out=torch.zeros(ndir, B, Hd).cuda())
             dirs = (RnnStepDir * ndir)(*[RnnStepDir(ptr(h[k]), ptr(bufs["h_out"][k]), ptr(W[k]), ptr(bh[k]), ptr(xp[k]), ptr(bufs["c"][k]), ptr(bufs["cprev"][k]),
@@ -202,9 +206,11 @@ def test_recurrent_step_tiles_return_the_same_bits(lstm, B, Hd, ndir):
             torch.cuda.synchronize()
             res.append(bufs)
     finally:
+        load().slnlp_set_gemm_ks(0)
         load().slnlp_set_rnn_step_tile(1)
-    for k in ("h_out", "acts", "out", "c", "cprev", "hn"):
-        assert torch.equal(res[0][k], res[1][k]), k
+    for other in res[1:]:
+        for k in ("h_out", "acts", "out", "c", "cprev", "hn"):
+            assert torch.equal(res[0][k], other[k]), k
     assert float(res[0]["h_out"].abs().max()) > 0
 
 
