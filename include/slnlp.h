@@ -327,6 +327,21 @@ int slnlp_average_step(float* avg, const float* params, int64_t n, float* count,
                        int64_t skip_end, void* stream);
 int slnlp_swap_arenas(float* a, float* b, int64_t n, void* stream);
 
+/* ------------------------------------------------------------ epoch scoring --
+ * An epoch's log-probs reduced to what the scoring metrics are functions of (slnlp/metrics.py forms the scores on the host).
+ * logp float32 [N, ld], V <= ld columns used; y int64 [N].  Per row i, with v = logp[i, y[i]]:
+ *   pred[i]    index of the first maximum (np.argmax: a NaN is larger than everything, the first NaN wins)
+ *   picked[i]  v, bit for bit
+ *   rank[i]    #{j : logp[i, j] > v} + #{j > y[i] : logp[i, j] == v}: where sklearn's top_k_accuracy_score finds the true class
+ *              (0 = first); V, never a hit, when the row holds a NaN
+ *   counts     int32 [3 V + 1]: true_sum [V], pred_sum [V], tp_sum [V] (rows with y = c, with pred = c, with both), then n_bad
+ * A label outside [0, V) is not used as an index: picked[i] = NaN, rank[i] = V, n_bad += 1, and the row enters pred_sum only.
+ * counts is zeroed by the call, on the stream; the sums are integer atomics, so the result does not depend on scheduling.
+ * Two launches, no host wait.  Invalid arguments -- a null pointer, N < 1, V < 1, ld < V, N above INT32_MAX or 3 V + 1 above it,
+ * an output overlapping an input or another output -- return SLNLP_ERR_INVALID_ARG before anything is launched. */
+int slnlp_score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V, int32_t* pred, float* picked,
+                     int32_t* rank, int32_t* counts, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

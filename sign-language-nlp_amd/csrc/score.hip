@@ -1,0 +1,158 @@
+// score.hip -- an epoch's log-probs reduced to what the scoring metrics need, on the device (slnlp/metrics.py).
+//
+// Accuracy, log-loss, the precision / recall / F1 family (weighted or macro), balanced accuracy and top-k accuracy are all
+// functions of three values per sample and three counts per class.  One pass over logp [N, ld] (V columns used) and y [N]:
+//
+//   pred[i]    the index of the row's first maximum (np.argmax: a NaN is larger than everything, the first NaN wins)
+//   picked[i]  v = logp[i, y[i]], bit for bit
+//   rank[i]    #{j : logp[i, j] > v} + #{j > y[i] : logp[i, j] == v} -- the position of the true class in a stable ascending
+//              argsort read backwards (sklearn's top_k_accuracy_score: among equal scores the higher index comes first);
+//              V -- never a hit -- when the row holds a NaN
+//   counts     true_sum [V] | pred_sum [V] | tp_sum [V] | n_bad: the per-class sums of a confusion matrix's row, column and
+//              diagonal, and the number of labels outside [0, V)
+//
+// A label outside [0, V) is never used as an index: its row gets picked = NaN and rank = V, counts as one n_bad and enters
+// pred_sum only.  tests/score_ref.py is the numpy restatement.
+//
+// One wave per row, four rows per block, rows over a grid-stride loop: lanes stride the columns (coalesced), v is read first,
+// so the maximum, its index and the two rank counts come out of the same pass.  The wave-level combines are DPP exchanges and
+// v_readlane over all 64 lanes (common.hpp); the arg-max rule -- larger value wins, equal values: lower index, NaN beats all -- is
+// a total order on (value, index), so every lane of a pair computes the same winner.  The class counts are integer atomics, one
+// lane per row: sums of integers, the same whatever the order of arrival.  Both kernels take the argument-pack form of launch.hpp.
+#include <limits.h>
+#include <math.h>
+
+#include <algorithm>
+
+#include "common.hpp"
+#include "launch.hpp"
+
+namespace slnlp {
+
+constexpr int SCORE_MAX_BLOCKS = 2048;  // x 4 rows: epochs past 8192 rows wrap the stride loop
+
+// whether (x, j) comes before (bv, bi) in the arg-max order
+__device__ __forceinline__ bool score_beats(float x, int j, float bv, int bi) {
+    const bool xn = x != x, bn = bv != bv;
+    if (xn || bn) return xn && (!bn || j < bi);
+    return x > bv || (x == bv && j < bi);
+}
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+
+template <int CTRL>
+__device__ __forceinline__ void score_best_step(float& bv, int& bi) {
+    const float ov = dpp_mov<CTRL>(bv);
+    const int oi = dpp_mov_i<CTRL>(bi);
+    if (score_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+}
+// over the whole wave (all 64 lanes active); every lane gets the result
+__device__ __forceinline__ void wave_best(float& bv, int& bi) {
+    score_best_step<DPP_XOR1>(bv, bi);
+    score_best_step<DPP_XOR2>(bv, bi);
+    score_best_step<DPP_HALF_MIRROR>(bv, bi);
+    score_best_step<DPP_MIRROR>(bv, bi);
+    float rv = lane_bcast(bv, 0);
+    int ri = __builtin_amdgcn_readlane(bi, 0);
+#pragma unroll
+    for (int l = 16; l < 64; l += 16) {
+        const float ov = lane_bcast(bv, l);
+        const int oi = __builtin_amdgcn_readlane(bi, l);
+        if (score_beats(ov, oi, rv, ri)) { rv = ov; ri = oi; }
+    }
+    bv = rv; bi = ri;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+    v += dpp_mov_i<DPP_XOR1>(v);
+    v += dpp_mov_i<DPP_XOR2>(v);
+    v += dpp_mov_i<DPP_HALF_MIRROR>(v);
+    v += dpp_mov_i<DPP_MIRROR>(v);
+    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
+           (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
+
+__device__ __forceinline__ void score_zero_body(int* __restrict__ counts, int n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) counts[i] = 0;
+}
+SLNLP_ZKERNEL(score_zero_kernel, 256, score_zero_body)
+
+__device__ __forceinline__ void score_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
+                                                int* __restrict__ pred, float* __restrict__ picked, int* __restrict__ rank,
+                                                int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int nwaves = gridDim.x * 4;
+    const float qnan = __builtin_bit_cast(float, 0x7fc00000);
+    for (long r = wave; r < N; r += nwaves) {
+        const float* row = logp + r * ld;
+        const int64_t label = y[r];
+        const bool ok = label >= 0 && label < V;
+        const float v = ok ? row[label] : qnan;
+        float bv = -INFINITY;                            // (any column beats this start: -inf at column j ties and j < INT_MAX)
+        int bi = INT_MAX, gt = 0, eq = 0, nans = 0;
+        for (int j = lane; j < V; j += 64) {
+            const float x = row[j];
+            if (score_beats(x, j, bv, bi)) { bv = x; bi = j; }
+            gt += x > v ? 1 : 0;
+            eq += (x == v && j > label) ? 1 : 0;
+            nans += x != x ? 1 : 0;
+        }
+        wave_best(bv, bi);                               // bi in [0, V): V >= 1, lane 0 read column 0
+        gt = wave_sum_i(gt);
+        eq = wave_sum_i(eq);
+        nans = wave_sum_i(nans);
+        if (lane == 0) {
+            pred[r] = bi;
+            picked[r] = v;
+            rank[r] = (ok && nans == 0) ? gt + eq : V;
+            atomicAdd(&counts[(long)V + bi], 1);
+            if (ok) {
+                atomicAdd(&counts[label], 1);
+                if (bi == label) atomicAdd(&counts[2L * V + label], 1);
+            } else {
+                atomicAdd(&counts[3L * V], 1);
+            }
+        }
+    }
+}
+SLNLP_ZKERNEL(score_rows_kernel, 256, score_rows_body)
+
+struct ScoreSpan { const void* p; size_t bytes; const char* name; };
+static bool spans_overlap(const ScoreSpan& a, const ScoreSpan& b) {
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+int score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V, int32_t* pred, float* picked, int32_t* rank,
+               int32_t* counts, hipStream_t st) {
+    SLNLP_CHECK_ARG(logp && y && pred && picked && rank && counts, "score_rows: null pointer");
+    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "score_rows: N=%ld outside 1..%d", (long)N, INT_MAX);
+    // counts holds 3 V + 1 int32 entries and is indexed with int32 class ids
+    SLNLP_CHECK_ARG(V >= 1 && V <= (INT_MAX - 1) / 3, "score_rows: V=%d outside 1..%d", V, (INT_MAX - 1) / 3);
+    SLNLP_CHECK_ARG(ld >= V, "score_rows: ld=%ld is less than V=%d", (long)ld, V);
+    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "score_rows: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
+    SLNLP_CHECK_ARG((((uintptr_t)logp | (uintptr_t)pred | (uintptr_t)picked | (uintptr_t)rank | (uintptr_t)counts) & 3) == 0 &&
+                        ((uintptr_t)y & 7) == 0,
+                    "score_rows: misaligned pointer");
+    const size_t n = (size_t)N, n_counts = 3 * (size_t)V + 1;
+    const ScoreSpan in[2] = {{logp, ((n - 1) * (size_t)ld + (size_t)V) * 4, "logp"}, {y, n * 8, "y"}};
+    const ScoreSpan out[4] = {{pred, n * 4, "pred"}, {picked, n * 4, "picked"}, {rank, n * 4, "rank"}, {counts, n_counts * 4, "counts"}};
+    for (int o = 0; o < 4; ++o) {
+        for (int i = 0; i < 2; ++i)
+            SLNLP_CHECK_ARG(!spans_overlap(out[o], in[i]), "score_rows: output %s overlaps input %s", out[o].name, in[i].name);
+        for (int q = 0; q < o; ++q)
+            SLNLP_CHECK_ARG(!spans_overlap(out[o], out[q]), "score_rows: outputs %s and %s overlap", out[q].name, out[o].name);
+    }
+    const int zero_blocks = (int)std::min<size_t>((n_counts + 255) / 256, SCORE_MAX_BLOCKS);
+    SLNLP_TRY(zlaunch(score_zero_kernel, dim3(zero_blocks), 256, 0, st, "score_zero", counts, (int)n_counts));
+    const int blocks = (int)std::min<int64_t>((N + 3) / 4, SCORE_MAX_BLOCKS);
+    return zlaunch(score_rows_kernel, dim3(blocks), 256, 0, st, "score_rows", logp, (long)ld, y, (int)N, V, pred, picked, rank, counts);
+}
+
+}  // namespace slnlp
+
+extern "C" int slnlp_score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V, int32_t* pred, float* picked,
+                                int32_t* rank, int32_t* counts, void* stream) {
+    return slnlp::score_rows(logp, ld, y, N, V, pred, picked, rank, counts, (hipStream_t)stream);
+}

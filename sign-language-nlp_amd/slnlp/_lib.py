@@ -123,6 +123,7 @@ SIGNATURES = {
     "slnlp_clip_adam_step_groups": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, i32, f32, vp, vp, vp, i64, i64, vp]),
     "slnlp_average_step": (i32, [vp, vp, i64, vp, i32, f32, i64, i64, vp]),
     "slnlp_swap_arenas": (i32, [vp, vp, i64, vp]),
+    "slnlp_score_rows": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),

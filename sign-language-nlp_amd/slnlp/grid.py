@@ -404,7 +404,7 @@ def default_fit_and_score(estimator_factory, params, train, test, scoring="neg_l
         # themselves: concurrent fits must use the per-timestep launches
         net.module_.persistent_kernels = False
     net.partial_fit(train)
-    return float(ScoringWrapper(scoring, train.labels() if scoring == "neg_log_loss" else None)(net, test, test.y))
+    return float(ScoringWrapper(scoring, train.labels() if ScoringWrapper.needs_labels(scoring) else None)(net, test, test.y))
 
 
 def _recipe_init_factory(factory):

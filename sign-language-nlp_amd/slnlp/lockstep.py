@@ -424,6 +424,6 @@ def fit_and_score_group(estimator_factory, params_list, trains, tests, scoring="
     probas = predict_proba_lockstep(nets, tests)
     scores = []
     for net, train, test, proba in zip(nets, trains, tests, probas):
-        wr = ScoringWrapper(scoring, train.labels() if scoring == "neg_log_loss" else None)
+        wr = ScoringWrapper(scoring, train.labels() if ScoringWrapper.needs_labels(scoring) else None)
         scores.append(float(wr(_CachedPredictor(proba, net.classes_), None, test.y)))
     return scores

@@ -313,20 +313,34 @@ def adam_args(net):
 class ScoringWrapper:
     """Named sklearn scorer with the extra keyword the reference gives each metric (helper.py:529-554): log-loss is told
     the full label set (a fold may miss classes), the precision / recall / F1 family gets ``zero_division=0``, accuracy
-    takes nothing.  Exposes ``score`` (the name) and ``greater_is_better`` -- what the reference's EpochScoring and
-    GridSearchCV wiring read (helper.py:255-268, 183-194)."""
+    takes nothing.  Beyond the reference's names: ``balanced_accuracy`` takes nothing either, and the top-k family --
+    ``top_k_accuracy`` (sklearn's k = 2) and ``top<k>_accuracy`` for any k >= 1, a ``top_k_accuracy_score`` scorer with that
+    k -- is told the label set like log-loss.  Exposes ``score`` (the name) and ``greater_is_better`` -- what the reference's
+    EpochScoring and GridSearchCV wiring read (helper.py:255-268, 183-194)."""
 
-    _EXTRA = {"neg_log_loss": lambda labels: {"labels": labels}, "accuracy": lambda labels: {}}
+    _EXTRA = {"neg_log_loss": lambda labels: {"labels": labels}, "accuracy": lambda labels: {},
+              "balanced_accuracy": lambda labels: {}, "top_k_accuracy": lambda labels: {"labels": labels}}
 
     def __init__(self, score_func, labels=None):
-        from sklearn.metrics import get_scorer
+        from sklearn.metrics import get_scorer, make_scorer, top_k_accuracy_score
         self.score = score_func
-        base = get_scorer(score_func)
-        extra = self._EXTRA.get(score_func, lambda labels: {"zero_division": 0})(labels)
+        k = metrics.top_k_of(score_func)
+        if k is not None and score_func != "top_k_accuracy":
+            # what sklearn's own "top_k_accuracy" scorer is, with the name's k
+            base = make_scorer(top_k_accuracy_score, greater_is_better=True, response_method=("decision_function", "predict_proba"), k=k)
+            extra = {"labels": labels}
+        else:
+            base = get_scorer(score_func)
+            extra = self._EXTRA.get(score_func, lambda labels: {"zero_division": 0})(labels)
         self.greater_is_better = base._sign > 0
         # a scorer object of the same kind with the merged keywords (get_scorer hands out a fresh copy per call)
         base._kwargs = {**base._kwargs, **extra}
         self.scorer = base
+
+    @staticmethod
+    def needs_labels(score_func):
+        """Whether the scorer must be told the full label set: a test fold may miss classes the probability columns stand for."""
+        return score_func == "neg_log_loss" or metrics.top_k_of(score_func) is not None
 
     def __call__(self, estimator, X, y_true, sample_weight=None):
         return self.scorer(estimator, X, y_true, sample_weight)
@@ -369,6 +383,7 @@ class _FitRun:
         self.wrappers = [ScoringWrapper(s, labels) for s in (net.scoring or [])]
         # the fast metrics index the probability columns by class id: valid when the labels are exactly the columns
         self.fast_ok = labels is not None and list(labels) == list(range(len(net.classes_)))
+        self._score_out = {}                                 # split -> the reduction's device buffers (ops.score_rows)
         es, clip, sched = net.early_stopping, net.gradient_clipping, net.lr_scheduler
         self.es = es
         self.max_norm = float(clip["gradient_clip_value"]) if clip and clip.get("gradient_clip_value") else 0.0
@@ -466,6 +481,12 @@ class _FitRun:
             return self.ytr[:self.n_visit], self.tr.y[:self.n_visit]
         return self.ytr, self.tr.y
 
+    def _reduced_scores(self, names, split, logp, y_dev, y_host):
+        """``metrics.epoch_scores`` into this fit's own device buffers for ``split`` (allocated once, not every epoch)."""
+        if logp.is_cuda and split not in self._score_out:
+            self._score_out[split] = ops.score_buffers(logp.shape[0], logp.shape[1], logp.device)
+        return metrics.epoch_scores(names, logp, y_dev, y_host, split=split, out=self._score_out.get(split))
+
     def end_epoch(self, tr, va):
         """tr / va: (sample-weighted mean loss, log-probs [n, V] on the device, [(batch loss, batch size)]) of the epoch's
         train and valid passes (va None without a valid split).  Returns True when the fit is over."""
@@ -490,12 +511,12 @@ class _FitRun:
             row["valid_loss"] = va_loss
             row["valid_loss_best"] = bool(va_loss < self.best_valid)
             self.best_valid = min(self.best_valid, va_loss)
-        # EpochScoring on the epoch's cached predictions: the reference's five metrics from one device-side
-        # reduction (slnlp/metrics.py, same numbers as the sklearn scorers); anything else through sklearn
+        # EpochScoring on the epoch's cached predictions: the reference's five metrics, the macro family, balanced and top-k
+        # accuracy from one device-side reduction (slnlp/metrics.py, same numbers as the sklearn scorers); anything else through sklearn
         # (train: paired with the labels in VISIT order, what skorch's cached predictions give EpochScoring under a shuffling loader)
         splits = [("train", tr_logp) + self.train_labels()] + ([("valid", va_logp, self.yva, self.va.y)] if va is not None else [])
         names = [wr.score for wr in self.wrappers]
-        fast = {sp: metrics.epoch_scores(names, lp, yd, yh) if self.fast_ok and names else {} for sp, lp, yd, yh in splits}
+        fast = {sp: self._reduced_scores(names, sp, lp, yd, yh) if self.fast_ok and names else {} for sp, lp, yd, yh in splits}
         proba = {}
         for wr in self.wrappers:
             for sp, lp, yd, yh in splits:

@@ -399,6 +399,51 @@ def swap_arenas(a, b):
     check(load().slnlp_swap_arenas(ptr(a), ptr(b), a.numel(), stream_ptr()), "swap_arenas")
 
 
+def score_buffers(N, V, device):
+    """The four output tensors of ``score_rows`` for an [N, V] epoch: slices of ONE allocation, so ``score_download`` is one copy."""
+    flat = torch.empty(3 * N + 3 * V + 1, dtype=torch.int32, device=device)
+    return flat[:N], flat[N:2 * N].view(torch.float32), flat[2 * N:3 * N], flat[3 * N:]
+
+
+def score_download(out):
+    """``score_rows``' four tensors as numpy arrays: one device-to-host copy when they are ``score_buffers``' slices of one
+    allocation, four otherwise."""
+    import numpy as np
+    pred, picked, rank, counts = out
+    N, base = pred.numel(), pred._base
+    if (base is not None and base.dtype == torch.int32 and base.dim() == 1 and base.is_contiguous()
+            and base.numel() == 3 * N + counts.numel() and pred.data_ptr() == base.data_ptr()
+            and picked.data_ptr() == base.data_ptr() + 4 * N and rank.data_ptr() == base.data_ptr() + 8 * N
+            and counts.data_ptr() == base.data_ptr() + 12 * N):
+        h = base.cpu().numpy()
+        return h[:N], h[N:2 * N].view(np.float32), h[2 * N:3 * N], h[3 * N:]
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def score_rows(logp, y, out=None):
+    """An epoch's log-probs ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) and labels ``y`` int64 [N] reduced to
+    ``(pred int32 [N], picked float32 [N], rank int32 [N], counts int32 [3 V + 1])``, device tensors (``slnlp_score_rows``,
+    include/slnlp.h); ``out``: such a 4-tuple to fill.  Runs on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    if not (logp.is_cuda and logp.dtype == torch.float32 and logp.dim() == 2 and (logp.stride(1) == 1 or logp.shape[1] == 1)):
+        raise ValueError(f"score_rows: logp must be a float32 [N, V] device tensor with unit column stride, got {logp.dtype} "
+                         f"{tuple(logp.shape)} strides {logp.stride()} on {logp.device}")
+    N, V = int(logp.shape[0]), int(logp.shape[1])
+    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"score_rows: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    ld = int(logp.stride(0)) if N > 1 else max(V, int(logp.stride(0)))
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = score_buffers(N, V, logp.device)
+        pred, picked, rank, counts = out
+        for t, dt, n in ((pred, torch.int32, N), (picked, torch.float32, N), (rank, torch.int32, N), (counts, torch.int32, 3 * V + 1)):
+            if not (t.device == logp.device and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous()):
+                raise ValueError(f"score_rows: out must be (int32 [{N}], float32 [{N}], int32 [{N}], int32 [{3 * V + 1}]) on {logp.device}")
+        check(load().slnlp_score_rows(ptr(logp), ld, ptr(y), N, V, ptr(pred), ptr(picked), ptr(rank), ptr(counts), stream_ptr()),
+              "score_rows")
+    return out
+
+
 class ParamGroupTable:
     """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
     segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
