@@ -382,6 +382,24 @@ int slnlp_balanced_order(const slnlp_balance_plan* plan, const int64_t* y_dev, u
                          int64_t* order_out /* [n_bal] */, int64_t* y_out /* [n_bal] or NULL: labels in visit order */,
                          void* stream);
 
+/* ------------------------------------------------- train-time input augmentation --
+ * One epoch's augmented copy of a train split (iterator_train__augment): frame dropping deletes random timesteps, token
+ * masking replaces random tokens by unk.  X int64 [n, S], L int64 [n]; row i has len = clamp(L[i], 0, S).  Every position
+ * t < len makes one Threefry-4x32 call, the dropout masks' 12 rounds, key (seed low word, seed high word, 0, 0), counter
+ * (i, epoch, t, 0); of the output words only X0 is used:
+ *   the position draws drop iff (X0 & 0xFFFF) < thr16(p_drop), and mask iff (X0 >> 16) < thr16(p_mask),
+ *   thr16(p) = min(floor(p * 65536 + 0.5), 65535), the dropout masks' threshold rule.
+ * When every position t < len of a row drew drop, none is dropped: a row never loses all of its frames.  The kept positions,
+ * in ascending t, are written compacted to X_out[i, 0 .. len'): unk where the position drew mask, X[i, t] otherwise;
+ * X_out[i, len' .. S) = pad; L_out[i] = len'.  Positions >= len of X are never read.  The result is a function of the
+ * arguments alone: no atomics, nothing depends on the grid or on timing.  One launch on stream, no host synchronisation, no
+ * allocation.  Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer, n < 1, S < 1,
+ * epoch outside [0, 2^32), a probability outside [0, 1), an output buffer overlapping an input (the kernel is not in-place)
+ * or the other output. */
+int slnlp_augment_rows(const int64_t* X, const int64_t* L, int64_t n, int64_t S, int64_t pad, int64_t unk, float p_drop,
+                       float p_mask, uint64_t seed, int64_t epoch, int64_t* X_out /* [n, S] */, int64_t* L_out /* [n] */,
+                       void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);

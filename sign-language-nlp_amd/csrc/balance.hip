@@ -41,38 +41,9 @@ struct slnlp_balance_plan {
 
 namespace slnlp {
 
-struct BalanceKey { unsigned ks[5]; unsigned epoch; };
-
-// Threefry-4x32 at counter (index, epoch, stage, 0): common.hpp's threefry4x32 with all four counter words (same rounds)
-__device__ __forceinline__ uint4 balance_words(unsigned index, unsigned stage, const BalanceKey& K) {
-    constexpr int ROT[8][2] = {{10, 26}, {11, 21}, {13, 27}, {23, 5}, {6, 20}, {17, 11}, {25, 10}, {18, 20}};
-    unsigned x0 = index + K.ks[0], x1 = K.epoch + K.ks[1], x2 = stage + K.ks[2], x3 = K.ks[3];
-#pragma unroll
-    for (int r = 0; r < SLNLP_THREEFRY_ROUNDS; ++r) {
-        if ((r & 1) == 0) {
-            x0 += x1; x1 = __builtin_rotateleft32(x1, ROT[r & 7][0]) ^ x0;
-            x2 += x3; x3 = __builtin_rotateleft32(x3, ROT[r & 7][1]) ^ x2;
-        } else {
-            x0 += x3; x3 = __builtin_rotateleft32(x3, ROT[r & 7][0]) ^ x0;
-            x2 += x1; x1 = __builtin_rotateleft32(x1, ROT[r & 7][1]) ^ x2;
-        }
-        if ((r & 3) == 3) {
-            const int s = (r + 1) >> 2;
-            x0 += K.ks[s % 5]; x1 += K.ks[(s + 1) % 5]; x2 += K.ks[(s + 2) % 5]; x3 += K.ks[(s + 3) % 5] + (unsigned)s;
-        }
-    }
-    return make_uint4(x0, x1, x2, x3);
-}
-__device__ __forceinline__ unsigned long long balance_key64(unsigned index, unsigned stage, const BalanceKey& K) {
-    const uint4 w = balance_words(index, stage, K);
+__device__ __forceinline__ unsigned long long balance_key64(unsigned index, unsigned stage, const SeedKey& K) {
+    const uint4 w = seed_words(index, stage, K);
     return ((unsigned long long)w.y << 32) | w.x;
-}
-__device__ __forceinline__ BalanceKey balance_key(unsigned long long seed, unsigned epoch) {
-    BalanceKey K;
-    K.ks[0] = (unsigned)seed; K.ks[1] = (unsigned)(seed >> 32); K.ks[2] = 0u; K.ks[3] = 0u;
-    K.ks[4] = 0x1BD11BDAu ^ K.ks[0] ^ K.ks[1];
-    K.epoch = epoch;
-    return K;
 }
 
 // Launch 1.  Blocks [0, rank_blocks): thread p takes members[p] = row i of class c, counts the class's rows with a smaller
@@ -87,7 +58,7 @@ __device__ __forceinline__ void balance_rank_body(const int* __restrict__ cls, c
                                                   unsigned long long* __restrict__ key2) {
     __shared__ unsigned long long tile_key[256];
     __shared__ int tile_row[256];
-    const BalanceKey K = balance_key(seed, epoch);
+    const SeedKey K = seed_key(seed, epoch);
     if ((int)blockIdx.x >= rank_blocks) {
         const int s = ((int)blockIdx.x - rank_blocks) * 256 + (int)threadIdx.x;
         if (s < n_bal) key2[s] = balance_key64((unsigned)s, 2u, K);
@@ -158,8 +129,8 @@ __device__ __forceinline__ void balance_fill_body(const int* __restrict__ cls, c
     const int j = s - c[BC_BASE], keep = c[BC_KEEP];
     int r = j;
     if (j >= keep) {
-        const BalanceKey K = balance_key(seed, epoch);
-        const unsigned w = balance_words((unsigned)(c[BC_BASE] + (j - keep)), 1u, K).x;
+        const SeedKey K = seed_key(seed, epoch);
+        const unsigned w = seed_words((unsigned)(c[BC_BASE] + (j - keep)), 1u, K).x;
         r = (int)(((unsigned long long)w * (unsigned)keep) >> 32);           // mulhi32: in [0, keep)
     }
     const int row = kept[c[BC_KEPT] + r];

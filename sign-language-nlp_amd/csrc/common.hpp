@@ -161,6 +161,37 @@ __device__ __forceinline__ uint4 threefry4x32(unsigned c0, unsigned c1, const Dr
     return make_uint4(x0, x1, x2, x3);
 }
 
+// The same generator for draws that are no dropout masks and take their seed as an argument (a class-balanced epoch's order,
+// balance.hip; an epoch's input augmentation, augment.hip): key (seed_lo, seed_hi, 0, 0), counter (index, epoch, word2, 0) --
+// three counter words, same rounds.
+struct SeedKey { unsigned ks[5]; unsigned epoch; };
+__device__ __forceinline__ SeedKey seed_key(unsigned long long seed, unsigned epoch) {
+    SeedKey K;
+    K.ks[0] = (unsigned)seed; K.ks[1] = (unsigned)(seed >> 32); K.ks[2] = 0u; K.ks[3] = 0u;
+    K.ks[4] = 0x1BD11BDAu ^ K.ks[0] ^ K.ks[1];
+    K.epoch = epoch;
+    return K;
+}
+__device__ __forceinline__ uint4 seed_words(unsigned index, unsigned word2, const SeedKey& K) {
+    constexpr int ROT[8][2] = {{10, 26}, {11, 21}, {13, 27}, {23, 5}, {6, 20}, {17, 11}, {25, 10}, {18, 20}};
+    unsigned x0 = index + K.ks[0], x1 = K.epoch + K.ks[1], x2 = word2 + K.ks[2], x3 = K.ks[3];
+#pragma unroll
+    for (int r = 0; r < SLNLP_THREEFRY_ROUNDS; ++r) {
+        if ((r & 1) == 0) {
+            x0 += x1; x1 = __builtin_rotateleft32(x1, ROT[r & 7][0]) ^ x0;
+            x2 += x3; x3 = __builtin_rotateleft32(x3, ROT[r & 7][1]) ^ x2;
+        } else {
+            x0 += x3; x3 = __builtin_rotateleft32(x3, ROT[r & 7][0]) ^ x0;
+            x2 += x1; x1 = __builtin_rotateleft32(x1, ROT[r & 7][1]) ^ x2;
+        }
+        if ((r & 3) == 3) {
+            const int s = (r + 1) >> 2;
+            x0 += K.ks[s % 5]; x1 += K.ks[(s + 1) % 5]; x2 += K.ks[(s + 2) % 5]; x3 += K.ks[(s + 3) % 5] + (unsigned)s;
+        }
+    }
+    return make_uint4(x0, x1, x2, x3);
+}
+
 // the call's column coordinate of column c (bit 4 of c removed) and which half of the call's lots c takes (bit 4 of c)
 __device__ __forceinline__ unsigned drop_cc(unsigned c) { return ((c >> 5) << 4) | (c & 15u); }
 __device__ __forceinline__ int drop_half(unsigned c) { return (int)((c >> 4) & 1u); }

@@ -129,6 +129,7 @@ SIGNATURES = {
     "slnlp_balance_plan_rows": (i64, [vp]),
     "slnlp_balance_plan_destroy": (None, [vp]),
     "slnlp_balanced_order": (i32, [vp, vp, C.c_uint64, i64, vp, vp, vp]),
+    "slnlp_augment_rows": (i32, [vp, vp, i64, i64, i64, i64, f32, f32, C.c_uint64, i64, vp, vp, vp]),
     "slnlp_gather_batch": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
     "slnlp_rnn_cell_fwd": (i32, [i32, C.POINTER(RnnCellDir), i32, i32, i32, vp, f32, i64, f32, i32, vp, vp]),
     "slnlp_rnn_layer_fwd": (i32, [i32, C.POINTER(RnnLayerDir), i32, i32, i32, i32, vp, f32, i64, f32, i32, vp, i32, vp,

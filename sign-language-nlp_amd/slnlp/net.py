@@ -14,6 +14,9 @@ semantics:
   order torch's ``RandomSampler`` draws per epoch (slnlp/sampler.py); ``iterator_train__drop_last`` drops the short last batch;
   ``iterator_train__balance=True`` makes every train epoch a class-balanced resample of the fit's own train split, drawn on
   the device (csrc/balance.hip) -- the valid split is never touched, and ``iterator_train__shuffle`` has nothing left to do;
+  ``iterator_train__augment={"frame_drop": p, "token_mask": p}`` shows every train epoch a freshly augmented copy of the train
+  rows, drawn on the device (csrc/augment.hip): random timesteps deleted, random tokens replaced by ``<unk>`` -- valid, test and
+  predict data are never augmented, and the train scores are the training pass's (augmented inputs), as under dropout;
 * per batch: forward -> CrossEntropyLoss(ignore_index=pad) -> backward ->
   clip_grad_norm_(gradient_clip_value) -> SGD(momentum)  == ONE hipGraph replay;
 * per epoch: valid pass, ``EpochScoring`` metrics for train/valid, ``lr`` scoring,
@@ -434,6 +437,18 @@ class _FitRun:
             net.shuffle_seed_ = seed
             self.sampler = sampler.EpochOrder(len(self.tr), self.bs, net.shuffle_seed_, self.drop_last).fast_forward(len(net.history))
         self.epoch_order, self.order_dev, self.y_visit_dev = None, None, None
+        # iterator_train__augment: the pristine device copy of the train split stays here; Xtr / Ltr become two buffers of the same
+        # shapes, allocated once, that order() refills every epoch (slnlp_augment_rows) -- dataset-order slices, gather launches,
+        # captured graphs and a lockstep group's data pointers all keep reading the same addresses
+        self.augment = net._iterator_train_augment()
+        if self.augment is not None:
+            seed = sampler.seed_of(net.history, "augment_seed")
+            if seed is None:                                 # (the option switched on after initialize(): drawn now)
+                seed = net.augment_seed_ if getattr(net, "augment_seed_", None) is not None else sampler.draw_seed()
+            net.augment_seed_ = seed
+            self._aug_ids = net._augment_ids()
+            self._aug_src = (self.Xtr, self.Ltr)
+            self.Xtr, self.Ltr = torch.empty_like(self.Xtr), torch.empty_like(self.Ltr)
         self.epochs_left = int(net.max_epochs)
         self.done = self.epochs_left <= 0
 
@@ -458,6 +473,12 @@ class _FitRun:
             # the run's two device tables (order, labels in visit order); with drop_last the epoch visits their full batches
             order, y_visit = self.balance.order(self.ytr, self.net.balance_seed_, len(self.net.history), out=self._bal_out)
             self.set_visit(order[:self.n_visit], y_visit[:self.n_visit])
+        if self.augment is not None:
+            # the epoch's augmented train rows: a function of (rows, seed, epoch number) per dataset row, queued on the fit's
+            # stream in front of the epoch's work (and behind the previous epoch's, which read the same two buffers)
+            pad, unk = self._aug_ids
+            ops.augment_rows(*self._aug_src, pad, unk, self.augment["frame_drop"], self.augment["token_mask"], self.net.augment_seed_,
+                             len(self.net.history), out=(self.Xtr, self.Ltr))
         return self.epoch_order
 
     def visit_table(self):
@@ -502,6 +523,8 @@ class _FitRun:
             row["shuffle_seed"] = self.sampler.seed          # a resumed fit rebuilds the order from it (slnlp/sampler.py)
         if self.balance is not None:
             row["balance_seed"] = net.balance_seed_          # with the epoch number, all a resumed fit needs to go on drawing
+        if self.augment is not None:
+            row["augment_seed"] = net.augment_seed_          # likewise: the draw of epoch e is a function of (rows, seed, e)
         if self.schedule is not None and self.schedule.per_batch:
             for b, lr in zip(row["batches"], self.epoch_lrs):
                 b["event_lr"] = lr[0] if isinstance(lr, list) else lr     # the rate this batch used (param groups: group 0's)
@@ -667,16 +690,30 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             raise ValueError(f"iterator_train__{sampler.BALANCE}={v!r}: expected True or False")
         return bool(v)
 
+    def _iterator_train_augment(self):
+        """``iterator_train__augment``: {frame_drop, token_mask} with the defaults filled in, or None (off); slnlp/sampler.py."""
+        return sampler.augment_options(self._sub("iterator_train").get(sampler.AUGMENT))
+
+    def _augment_ids(self):
+        """(pad, unk) of the module's source vocabulary: what fills an augmented row's tail and what a masked token becomes."""
+        vocab = self._sub("module").get("src_vocab")
+        if vocab is None or not hasattr(vocab, "stoi"):
+            raise ValueError("iterator_train__augment: the <pad> and <unk> ids come from the module's source vocabulary, and "
+                             f"module__src_vocab is {vocab!r}")
+        from model.util import UNK_WORD, get_pad_idx
+        return int(get_pad_idx(vocab)), int(vocab.stoi[UNK_WORD])
+
     def _epoch_rows(self, ds):
         """Rows a train epoch on ``ds`` visits before drop_last: the train split's, or a balanced epoch's."""
         y = ds.y[self._train_split(ds)[0]]
         return sampler.balanced_rows(y) if self._iterator_train_balance() else len(y)
 
-    def _draw_iterator_seeds(self, shuffle, balance):
-        """``shuffle_seed_`` / ``balance_seed_``: each drawn from torch's global CPU generator only when its option is on (None
-        otherwise), the shuffle seed first -- a configuration without the option consumes what it always did."""
+    def _draw_iterator_seeds(self, shuffle, balance, augment=False):
+        """``shuffle_seed_`` / ``balance_seed_`` / ``augment_seed_``: each drawn from torch's global CPU generator only when its
+        option is on (None otherwise), in this order -- a configuration without an option consumes what it always did."""
         self.shuffle_seed_ = sampler.draw_seed() if shuffle else None
         self.balance_seed_ = sampler.draw_seed() if balance else None
+        self.augment_seed_ = sampler.draw_seed() if augment else None
 
     def initialize(self):
         avg_opts = averaging_options(self._params.get("weight_averaging"))   # a bad setting: here, not in the middle of a fit
@@ -685,6 +722,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
         shuffle, _ = self._iterator_train()
         balance = self._iterator_train_balance()
+        augment = self._iterator_train_augment()             # a bad setting: here, not in the middle of a fit
+        if augment is not None:
+            self._augment_ids()
         dev = torch.device(self.device)
         if dev.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("slnlp.net: device %r -- the HIP path is the only compute path (no CPU fallback)" % (self.device,))
@@ -735,7 +775,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         self.history = []
         # the seed of the shuffled order, drawn the way RandomSampler draws one without a generator -- AFTER the module's
         # weights and only when shuffling is on, so the initial weights of every other configuration keep their bits
-        self._draw_iterator_seeds(shuffle, balance)
+        self._draw_iterator_seeds(shuffle, balance, augment is not None)
         self.initialized_ = True
         return self
 
@@ -1083,4 +1123,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             seed = sampler.seed_of(self.history, "balance_seed")
             if seed is not None:                         # ... and the checkpoint's balanced draws, at epoch len(history)
                 self.balance_seed_ = seed
+            seed = sampler.seed_of(self.history, "augment_seed")
+            if seed is not None:                         # ... and its augmentation draws, likewise
+                self.augment_seed_ = seed
         return self

@@ -592,6 +592,25 @@ def gather_batch(X, lengths, y, order, row0, B, out=None):
     return Xo[:B], (None if Lo is None else Lo[:B]), yo[:B]
 
 
+def augment_rows(X, L, pad, unk, p_drop, p_mask, seed, epoch, out=None):
+    """One epoch's augmented copy of the device-resident rows ``X`` int64 [n, S] / ``L`` int64 [n] (``slnlp_augment_rows``,
+    csrc/augment.hip): every position below a row's length is dropped with probability ``p_drop`` (the rest closes up; a row
+    never loses all of its positions) and, when kept, replaced by ``unk`` with probability ``p_mask``; the tail is ``pad``.  A
+    function of (X, L, seed, epoch) alone, drawn on the current stream: one launch, no host synchronisation.  ``out``: the
+    pair ``(X_out [n, S], L_out [n])`` to fill -- never ``X`` / ``L`` themselves; None allocates it.  Returns the pair."""
+    _lib.require_gpu()
+    n, S = X.shape
+    if out is None:
+        out = (torch.empty_like(X), torch.empty_like(L))
+    Xo, Lo = out
+    for t in (X, L, Xo, Lo):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous(), "augment_rows: contiguous int64 device tensors"
+    assert L.shape == (n,) and Xo.shape == (n, S) and Lo.shape == (n,), "augment_rows: X [n, S], L [n] and outputs of the same shapes"
+    check(load().slnlp_augment_rows(ptr(X), ptr(L), n, S, int(pad), int(unk), float(p_drop), float(p_mask), int(seed) % (1 << 64),
+                                    int(epoch), ptr(Xo), ptr(Lo), stream_ptr()), "augment_rows")
+    return Xo, Lo
+
+
 class BalancePlan:
     """The per-class tables of a class-balanced epoch draw over the labels ``y`` (host int64 [n], values in
     ``[0, n_classes)``), in device memory the handle owns (``slnlp_balance_plan_create``).  ``rows``: the ``n_bal`` rows every

@@ -14,6 +14,15 @@ is a function of (labels, ``balance_seed``, epoch number), so a resumed fit need
 leaves ``iterator_train__shuffle`` nothing to do beside it (accepted, no effect).  ``HONOURED`` keeps naming the two keys this
 module draws for on the host; ``BALANCE`` is the third honoured key.
 
+``iterator_train__augment={"frame_drop": p, "token_mask": p}`` regularises the INPUTS instead of the order: every train epoch
+sees a freshly augmented copy of the fit's own train rows, drawn ON THE DEVICE (``slnlp_augment_rows``, csrc/augment.hip) into
+the two buffers every consumer of the train split already reads -- frame dropping deletes random timesteps (the row closes up
+and gets shorter, never empty), token masking replaces random tokens by ``<unk>``.  The draw is a function of (rows,
+``augment_seed``, epoch number), per dataset row: a resumed fit needs no fast-forward, it composes with shuffling and balancing
+(which only choose the rows' order), and a row a balanced epoch visits twice is seen in the same augmented form both times
+within that epoch.  Valid, test and predict data are never augmented.  ``AUGMENT`` is the fourth honoured key,
+``augment_options`` its validation.
+
 As for schedules (slnlp/schedule.py), the position is a function of the fit's history: a new fit run builds the sampler from
 the seed and draws the epochs the history accounts for (``fast_forward``), so a resumed fit needs no extra checkpoint file --
 the seed rides every epoch row of a shuffled fit (``"shuffle_seed"``).
@@ -22,8 +31,8 @@ import numpy as np
 import torch
 from torch.utils.data import BatchSampler, RandomSampler
 
-# the ``iterator_train__*`` keys the fit loop honours (every other ``iterator_*`` key is accepted and has no effect, as the
-# reference's ``collate_fn``)
+# the ``iterator_train__*`` keys the fit loop honours beside ``balance`` and ``augment`` below (every other ``iterator_*`` key is
+# accepted and has no effect, as the reference's ``collate_fn``)
 HONOURED = ("shuffle", "drop_last")
 
 
@@ -44,11 +53,35 @@ BALANCE = "balance"
 
 
 def seed_of(history, key):
-    """The ``key`` ("shuffle_seed" / "balance_seed") of the last epoch row that carries one, or None."""
+    """The ``key`` ("shuffle_seed" / "balance_seed" / "augment_seed") of the last epoch row that carries one, or None."""
     for row in reversed(history or []):
         if row.get(key) is not None:
             return int(row[key])
     return None
+
+
+AUGMENT = "augment"
+AUGMENT_KEYS = ("frame_drop", "token_mask")
+
+
+def augment_options(setting):
+    """The ``iterator_train__augment`` setting with its defaults filled in -- {frame_drop, token_mask}, each a probability in
+    [0, 1), 0 when omitted -- or None (off: None, False or absent).  Anything else raises ValueError."""
+    if setting is None or setting is False:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"iterator_train__augment={setting!r}: expected a dict with keys among {AUGMENT_KEYS}, None or False")
+    unknown = sorted(set(setting) - set(AUGMENT_KEYS), key=repr)
+    if unknown:
+        raise ValueError(f"iterator_train__augment: unknown keys {unknown} (known: {AUGMENT_KEYS})")
+    out = {}
+    for k in AUGMENT_KEYS:
+        p = setting.get(k, 0.0)
+        # the library takes the probability as a float32 (the dropout masks' threshold rule): that value must stay below 1
+        if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(np.float32(p)) < 1.0:
+            raise ValueError(f"iterator_train__augment: {k}={p!r}, expected a real number in [0, 1)")
+        out[k] = float(p)
+    return out
 
 
 def balanced_rows(y):
