@@ -342,6 +342,47 @@ int slnlp_swap_arenas(float* a, float* b, int64_t n, void* stream);
 int slnlp_score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V, int32_t* pred, float* picked,
                      int32_t* rank, int32_t* counts, void* stream);
 
+/* ------------------------------------------------------ temperature calibration --
+ * One scalar T fitted on held-out log-probs and applied as softmax(z / T): the arg-max never moves, the log-loss does.
+ * logp float32 [N, ld], V <= ld columns used; y int64 [N]; beta = 1 / T.  Rows whose label lies outside [0, V) are counted
+ * and excluded (never used as an index); M rows remain.  Per row i, p = softmax(beta z_i):
+ *   f_i = logsumexp_c(beta z_ic) - beta z_iy       g_i = sum_c p_c z_ic - z_iy       h_i = sum_c p_c z_ic^2 - (sum_c p_c z_ic)^2
+ *   s_i = |sum_c p_c z_ic| + |z_iy|                f, g, h, s: their means over the M rows (g = df/dbeta, h = d2f/dbeta2 >= 0)
+ * slnlp_fit_temperature minimises f over beta in [2^-6, 2^6], in fp64 throughout (z itself is float32):
+ *   1. at beta = 2^-6: |g| <= 2^-44 s there AND at beta = 1 -> beta = 1, SLNLP_CAL_FLAT; else g >= 0 -> beta = 2^-6, SLNLP_CAL_BOUND
+ *   2. at beta = 2^6:  g <= 0 -> beta = 2^6, SLNLP_CAL_BOUND
+ *   3. lo = 2^-6, hi = 2^6, beta = 1; at most 32 times: evaluate at beta; |g| <= 2^-44 s -> SLNLP_CAL_GRADIENT (result beta);
+ *      g < 0 ? lo = beta : hi = beta; beta' = beta exp(-g / (g + beta h)) (the Newton step in ln beta) when g + beta h > 0
+ *      and lo < beta' < hi, else sqrt(lo hi); |ln(beta' / beta)| <= 2^-40 -> SLNLP_CAL_STEP (result beta'); after the 32nd
+ *      evaluation -> SLNLP_CAL_CAP (result beta'); else beta = beta'.
+ * M == 0 gives beta = 1, SLNLP_CAL_FLAT, both f = 0.
+ * state: SLNLP_CAL_STATE_BYTES of device memory, 8-byte aligned, written by the call (no need to clear it):
+ *   double [0] beta   [1] T = 1 / beta   [2] f at beta = 1   [3] f at the result   [4..7] the iteration's own
+ *   int64  [8] reason (SLNLP_CAL_*)   [9] iterations (evaluations of step 3; 0 for FLAT / BOUND)   [10] M   [11] labels out
+ *          of range   [12..15] the iteration's own
+ * scratch: slnlp_fit_temperature_scratch_bytes(N) bytes (-1 and a message for N outside 1..INT32_MAX), 32-byte aligned: the
+ * per-row terms of one evaluation.  The call queues a fixed sequence of 72 launches on stream (36 evaluations of two launches:
+ * beta = 1, the two bounds, 32 iterations, the result; once the reason is set the iteration launches return at once) and
+ * never waits for the host.  The result is a function of the arguments alone: the row terms are summed by one block in an
+ * order that depends on N only.  Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer,
+ * N or V outside 1..INT32_MAX, ld < V, scratch too small or misaligned, state or scratch overlapping an input or each other.
+ *
+ * slnlp_scale_logp: out[i, c] = beta z_ic - logsumexp_c'(beta z_ic'), the calibrated log-probs; beta = beta_dev[0] is read
+ * from device memory (a state's first double), so the call never waits for the host.  Per row in fp64 with the maximum
+ * subtracted, rounded once to float32.  out may be logp itself with ld_out == ld (in place: every column is re-read by the
+ * lane that stores it, after the row's logsumexp is complete); any other overlap is SLNLP_ERR_INVALID_ARG.  One launch. */
+#define SLNLP_CAL_STATE_BYTES 128
+#define SLNLP_CAL_FLAT 1
+#define SLNLP_CAL_BOUND 2
+#define SLNLP_CAL_GRADIENT 3
+#define SLNLP_CAL_STEP 4
+#define SLNLP_CAL_CAP 5
+int64_t slnlp_fit_temperature_scratch_bytes(int64_t N);
+int slnlp_fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, void* state, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+int slnlp_scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, float* out, int64_t ld_out,
+                     void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

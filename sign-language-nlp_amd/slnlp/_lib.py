@@ -124,6 +124,9 @@ SIGNATURES = {
     "slnlp_average_step": (i32, [vp, vp, i64, vp, i32, f32, i64, i64, vp]),
     "slnlp_swap_arenas": (i32, [vp, vp, i64, vp]),
     "slnlp_score_rows": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "slnlp_fit_temperature_scratch_bytes": (i64, [i64]),
+    "slnlp_fit_temperature": (i32, [vp, i64, vp, i64, i64, vp, vp, i64, vp]),
+    "slnlp_scale_logp": (i32, [vp, i64, i64, i64, vp, vp, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -258,6 +261,7 @@ def require_gpu():
 REDUCTIONS = {"mean": 0, "sum": 1}             # CrossEntropyLoss reductions the fused criterion implements
 UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
+CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_*
 
 
 def ptr(t):

@@ -18,7 +18,8 @@ What replaces what: dask workers -> one process per GPU (``ShardedGridSearchCV``
 reproduced.  ``dataset_args.synthetic: {n: ..}`` (not in the reference) generates an ASL-Phono-shaped dataset when
 the corpus is not on the machine.  ``iterator_train_args: {shuffle: true, drop_last: false}`` (the reference hard-codes its
 iterator arguments, helper.py:73-83, with ``shuffle`` commented out) becomes ``iterator_train__*``; in ``grid_args`` it is a grid
-axis.  Configs without the key behave as before.
+axis.  Configs without the key behave as before.  A top-level ``calibration: {method: temperature}`` goes to the estimator as it is
+(temperature calibration on the fit's valid split, slnlp/net.py); a list of such settings under ``grid_args`` is a grid axis.
 """
 import argparse
 import copy
@@ -30,7 +31,7 @@ import os
 import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
-             "criterion_args", "iterator_train_args", "grid_args")
+             "criterion_args", "iterator_train_args", "grid_args", "calibration")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -110,7 +111,7 @@ def build_net_params(args, dataset, device):
          "scoring": args.get("scoring"), "early_stopping": args.get("early_stopping"),
          "gradient_clipping": args.get("gradient_clipping"), "lr_scheduler": args.get("lr_scheduler"),
          "checkpoint_dir": args.get("workdir") or None}
-    for k in ("lr", "max_epochs", "batch_size", "verbose"):
+    for k in ("lr", "max_epochs", "batch_size", "verbose", "calibration"):     # (calibration: {method: temperature}, slnlp/net.py)
         if args.get(k) is not None:
             p[k] = args[k]
     if isinstance(p.get("scoring"), str):

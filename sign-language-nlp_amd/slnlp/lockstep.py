@@ -18,6 +18,7 @@ import time
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import check, load, ptr, stream_ptr
 
 TRAIN, VALID, TEST = 0, 1, 2
@@ -224,10 +225,49 @@ def _avg_key(net):
     return None if av is None else (av["kind"], av["decay"], av["every"])
 
 
+def _eval_pass(nets, data, bs):
+    """One lockstep eval pass (the TEST slot) of ``nets`` over ``data`` -- per fit (X, lengths, y) on the device -- under the
+    weights ``predict_proba`` evaluates with: the averaged ones stand in where ``weight_averaging`` predicts with them, and the
+    live weights come back bit for bit.  Returns (group, the fits' log-probs: the group's own buffers); the caller closes the
+    group.  No host wait."""
+    S = data[0][0].shape[1]
+    engines = [n.module_.engine(bs, S) for n in nets]
+    for n in nets:
+        n.module_.eval()
+    group = LockstepGroup(engines)
+    group.set_data(TEST, [d[0] for d in data], [d[2] for d in data], bs, [d[1] for d in data])
+    swapped = [n for n in nets if n._predict_averaged()]
+    for n in swapped:
+        n.module_.swap_averaged()
+    try:
+        group.epoch(TEST, bs, False)
+    finally:
+        for n in swapped:
+            n.module_.swap_averaged()
+    return group, group.logp[TEST]
+
+
+def _calibrate_lockstep(nets, runs, stream):
+    """``NeuralNetClassifier._calibrate`` for the fits of a group whose ``calibration`` option is on: one lockstep eval pass over
+    their valid splits, one ``fit_temperature`` per fit on the group's stream, then one sync and the downloads."""
+    from .net import stream_sync
+    todo = [(n, r) for n, r in zip(nets, runs) if getattr(n, "_cal_opts", None) is not None]
+    if not todo:
+        return
+    if any(r.va is None for _, r in todo):
+        raise ValueError("calibration: the fit has no valid split to fit the temperature on (train_split)")
+    group, logps = _eval_pass([n for n, _ in todo], [(r.Xva, r.Lva, r.yva) for _, r in todo], todo[0][1].bs)
+    states = [ops.fit_temperature(lp, r.yva) for lp, (_, r) in zip(logps, todo)]
+    stream_sync(stream)
+    group.close()
+    for (n, _), state in zip(todo, states):
+        n._set_calibration(ops.temperature_download(state), state)
+
+
 def fit_lockstep(nets, datasets):
     """``net.partial_fit(ds)`` for every (net, ds) pair, all fits advancing together.  The nets must be initialised,
     of one shape (lr and dropout rate may differ) and their datasets of one size; fits that stop early (EarlyStopping)
-    leave the group, the others go on."""
+    leave the group, the others go on.  Fits whose ``calibration`` option is on are calibrated after the last one has ended."""
     nets[0]._gate.enter(False)                          # fused fits share the device (slnlp.net: _DeviceGate)
     try:
         return _fit_lockstep_gated(nets, datasets)
@@ -249,6 +289,9 @@ def _fit_lockstep_gated(nets, datasets):
     stream = nets[0]._stream
     assert all(n._stream is stream for n in nets), "lockstep: the fits of a group share the device's stream"
     nets[0]._enter_stream()                             # the stream waits for whatever this thread queued elsewhere so far
+    for n in nets:
+        if getattr(n, "_cal_opts", None) is not None:
+            n._set_calibration(None)                    # as partial_fit: an earlier fit's temperature does not describe these weights
     with torch.cuda.stream(stream):
         runs = [_FitRun(n, d) for n, d in zip(nets, datasets)]
     r0 = runs[0]
@@ -350,6 +393,8 @@ def _fit_lockstep_gated(nets, datasets):
     stream_sync(stream)
     if group is not None:
         group.close()
+    with torch.cuda.stream(stream):
+        _calibrate_lockstep(nets, runs, stream)
     if log is not None:
         log["epochs_run"] = [len(n.history) for n in nets]
         EPOCH_LOG.append(log)
@@ -371,22 +416,11 @@ def predict_proba_lockstep(nets, datasets):
 def _predict_proba_lockstep_gated(nets, datasets, bs, stream_sync):
     nets[0]._enter_stream()
     with torch.cuda.stream(nets[0]._stream):
-        dev = [n._device_data(d) for n, d in zip(nets, datasets)]
-        S = dev[0][0].shape[1]
-        engines = [n.module_.engine(bs, S) for n in nets]
-        for n in nets:
-            n.module_.eval()
-        group = LockstepGroup(engines)
-        group.set_data(TEST, [d[0] for d in dev], [d[2] for d in dev], bs, [d[1] for d in dev])
-        swapped = [n for n in nets if n._predict_averaged()]
-        for n in swapped:
-            n.module_.swap_averaged()                   # weight_averaging predict: the averaged weights stand in for the forward
-        try:
-            group.epoch(TEST, bs, False)
-        finally:
-            for n in swapped:
-                n.module_.swap_averaged()               # ... and the live weights come back bit for bit
-        out = [lp.clone() for lp in group.logp[TEST]]
+        group, logps = _eval_pass(nets, [n._device_data(d) for n, d in zip(nets, datasets)], bs)
+        out = [lp.clone() for lp in logps]
+        for n, o in zip(nets, out):
+            if getattr(n, "calibration_", None) is not None:
+                ops.scale_logp(o, n._cal_state, out=o)  # a calibrated fit's log-probs become beta z - logsumexp(beta z), in place
         stream_sync(nets[0]._stream)
         # softmax on the host copies (torch's CPU op, as in NeuralNetClassifier.predict_proba: no torch arithmetic kernel runs
         # beside other fits on the GPU)

@@ -24,7 +24,9 @@ semantics:
   epoch or per batch: slnlp/schedule.py), ``EarlyStopping`` (patience,
   relative threshold), ``Checkpoint`` on ``valid_loss_best`` (helper.py:197-273);
 * ``weight_averaging={...}``: a running average of the weights (SWA / EMA, ``torch.optim.swa_utils``) kept on the device beside
-  the model, fed per epoch or per batch, and -- ``predict`` -- what ``predict_proba`` / ``predict`` / ``score`` evaluate with.
+  the model, fed per epoch or per batch, and -- ``predict`` -- what ``predict_proba`` / ``predict`` / ``score`` evaluate with;
+* ``calibration={"method": "temperature"}``: at the end of a fit one temperature is fitted on the valid split's log-probs, on
+  the device (csrc/calibration.hip), and ``predict_proba`` returns ``softmax(z / T)``; ``predict`` and the history never change.
 
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
@@ -295,6 +297,25 @@ def averaging_options(setting):
         raise ValueError(f"weight_averaging: predict={predict!r}, expected True or False")
     return {"kind": kind, "decay": float(decay) if kind == "ema" else 0.0, "every": every, "start_epoch": int(start),
             "predict": bool(predict)}
+
+
+CALIBRATION_KEYS = ("method",)
+
+
+def calibration_options(setting):
+    """The ``calibration`` setting with its defaults filled in -- {method "temperature"} -- or None (off).  Anything else raises
+    ValueError here."""
+    if setting is None or setting is False:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"calibration={setting!r}: expected a dict with keys among {CALIBRATION_KEYS} or None")
+    unknown = sorted(set(setting) - set(CALIBRATION_KEYS))
+    if unknown:
+        raise ValueError(f"calibration: unknown keys {unknown} (known: {CALIBRATION_KEYS})")
+    method = setting.get("method", "temperature")
+    if method != "temperature":
+        raise ValueError(f"calibration: method={method!r}, expected 'temperature'")
+    return {"method": "temperature"}
 
 
 def next_n_averaged(opts, history, n_batches):
@@ -585,13 +606,13 @@ class _FitRun:
 class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
     _OWN = ("module", "criterion", "optimizer", "lr", "max_epochs", "batch_size", "device", "warm_start", "verbose",
             "predict_nonlinearity", "scoring", "labels", "early_stopping", "gradient_clipping", "lr_scheduler",
-            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging")
+            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging", "calibration")
 
     def __init__(self, module, criterion="torch.nn.CrossEntropyLoss", optimizer="torch.optim.SGD", lr=0.01,
                  max_epochs=10, batch_size=128, device="cuda", warm_start=False, verbose=0,
                  predict_nonlinearity="auto", scoring=None, labels=None, early_stopping=None,
                  gradient_clipping=None, lr_scheduler=None, checkpoint_dir=None, train_split=5, use_graph="auto",
-                 callbacks=None, dataset=None, weight_averaging=None, **kwargs):
+                 callbacks=None, dataset=None, weight_averaging=None, calibration=None, **kwargs):
         loc = locals()
         self._params = {k: loc[k] for k in self._OWN}
         for k, v in kwargs.items():
@@ -717,6 +738,10 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
 
     def initialize(self):
         avg_opts = averaging_options(self._params.get("weight_averaging"))   # a bad setting: here, not in the middle of a fit
+        cal_opts = calibration_options(self._params.get("calibration"))
+        if cal_opts is not None and not self.train_split:
+            raise ValueError(f"calibration: the temperature is fitted on the fit's internal valid split, and train_split={self.train_split!r} "
+                             "holds nothing out")
         ok, pairs = optimizer_kwargs(self._sub("optimizer"))
         if not pairs:
             schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
@@ -745,6 +770,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                              f"torch (optimizer {self._opt_cls.__name__}, criterion {type(self.criterion_).__name__}); it is "
                              "implemented for fused fits only (SGD / Adam / AdamW with CrossEntropyLoss on the model.* modules)")
         self._avg_opts = avg_opts
+        self._cal_opts = cal_opts
+        self._set_calibration(None)
         self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
         # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
         self._crit_opts = criterion_options(self.criterion_) if hasattr(mod_cls, "engine") else None
@@ -815,6 +842,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
 
     def _partial_fit_gated(self, X, y):
         self._enter_stream()
+        if getattr(self, "_cal_opts", None) is not None:
+            self._set_calibration(None)                      # an earlier fit's temperature does not describe the weights to come
         with torch.cuda.stream(self._stream):
             run = _FitRun(self, self._as_dataset(X, y))
             for _ in range(int(self.max_epochs)):
@@ -839,8 +868,45 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                     va = self._run_epoch(run.Xva, run.Lva, run.yva, run.bs, False, run.momentum, run.max_norm)
                 if run.end_epoch(tr, va):
                     break
+            if getattr(self, "_cal_opts", None) is not None:
+                self._calibrate(run)
         stream_sync(self._stream)
         return self
+
+    # ------------------------------------------------------------ calibration
+    def _calibrate(self, run):
+        """Fit the temperature on the valid split's log-probs under the weights ``predict_proba`` evaluates with (the averaged
+        ones swapped in and back, as there); the [N, V] matrix stays on the device, only the state comes to the host."""
+        if run.va is None:
+            raise ValueError("calibration: the fit has no valid split to fit the temperature on (train_split)")
+        self.module_.eval()
+        swapped = self._predict_averaged()
+        if swapped:
+            self.module_.swap_averaged()
+        try:
+            logp = self._run_epoch(run.Xva, run.Lva, run.yva, run.bs, False, run.momentum, run.max_norm)[1]
+        finally:
+            if swapped:
+                self.module_.swap_averaged()
+        state = ops.fit_temperature(logp, run.yva)
+        self._set_calibration(ops.temperature_download(state), state)
+
+    def _set_calibration(self, info, state=None):
+        """``calibration_`` (``ops.temperature_download``'s dict), ``temperature_`` and the device state ``predict_proba`` scales with;
+        None removes them.  A fit that cannot stand raises here: labels outside the classes, the iteration cap."""
+        if info is None:
+            for k in ("calibration_", "temperature_", "_cal_state"):
+                self.__dict__.pop(k, None)
+            return
+        if info["bad_labels"] > 0:
+            raise ValueError(f"calibrating on the valid data: {info['bad_labels']} of {info['rows'] + info['bad_labels']} labels lie "
+                             "outside the classes of the log-probs")
+        if info["reason"] == "cap":
+            raise RuntimeError(f"calibration: the temperature search did not converge in {info['iterations']} iterations "
+                               f"(beta {info['beta']!r})")
+        dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
+        self._cal_state = state if state is not None else ops.temperature_state(info["beta"], dev)
+        self.calibration_, self.temperature_ = dict(info), info["temperature"]
 
     # ------------------------------------------------------- weight averaging
     def _averaging_epoch(self):
@@ -993,6 +1059,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                     if swapped:
                         self.module_.swap_averaged()     # ... and the live weights come back bit for bit
                 out = torch.cat(outs)
+                if getattr(self, "calibration_", None) is not None:
+                    ops.scale_logp(out, self._cal_state, out=out)    # softmax(z / T) below: the calibrated log-probs, in place
             stream_sync(self._stream)
         finally:
             self._gate.leave(not self._fused)
@@ -1085,6 +1153,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                    os.path.join(dirname, "criterion.pt"))       # host tensors, like params.pt
         with open(os.path.join(dirname, "history.json"), "w") as f:
             json.dump(self.history, f, indent=1)
+        if getattr(self, "calibration_", None) is not None:
+            with open(os.path.join(dirname, "calibration.json"), "w") as f:
+                json.dump(self.calibration_, f, indent=1)
         if getattr(self, "_avg_opts", None) is not None:  # the running average and how many models it holds: a resumed fit goes on
             torch.save({"state_dict": {k: v.detach().cpu() for k, v in self.averaged_state_dict().items()}, "n_averaged": self.n_averaged_},
                        os.path.join(dirname, "averaged.pt"))
@@ -1113,6 +1184,10 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 t = saved["state_dict"][name]
                 avg[off:off + t.numel()].copy_(t.reshape(-1).to(avg.device, torch.float32))
             count.fill_(float(saved["n_averaged"]))
+        cal_file = os.path.join(dirname, "calibration.json")
+        if getattr(self, "_cal_opts", None) is not None and os.path.exists(cal_file):
+            with open(cal_file) as f:
+                self._set_calibration(json.load(f))          # beta goes back to the device
         hist = os.path.join(dirname, "history.json")
         if os.path.exists(hist):
             with open(hist) as f:

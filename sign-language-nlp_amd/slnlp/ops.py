@@ -444,6 +444,78 @@ def score_rows(logp, y, out=None):
     return out
 
 
+CAL_STATE_DOUBLES = 16                       # SLNLP_CAL_STATE_BYTES / 8: eight doubles, then eight int64
+
+
+def _logp_matrix(what, logp):
+    if not (logp.is_cuda and logp.dtype == torch.float32 and logp.dim() == 2 and (logp.stride(1) == 1 or logp.shape[1] == 1)):
+        raise ValueError(f"{what}: logp must be a float32 [N, V] device tensor with unit column stride, got {logp.dtype} "
+                         f"{tuple(logp.shape)} strides {logp.stride()} on {logp.device}")
+    N, V = int(logp.shape[0]), int(logp.shape[1])
+    return N, V, (int(logp.stride(0)) if N > 1 else max(V, int(logp.stride(0))))
+
+
+def _cal_state(what, state, device):
+    if not (state.device == device and state.dtype == torch.float64 and state.dim() == 1 and state.numel() == CAL_STATE_DOUBLES
+            and state.is_contiguous()):
+        raise ValueError(f"{what}: state must be a contiguous float64 [{CAL_STATE_DOUBLES}] tensor on {device}")
+
+
+def fit_temperature(logp, y, state=None, scratch=None):
+    """Fit the temperature of ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) against the labels ``y`` int64 [N]
+    (``slnlp_fit_temperature``, include/slnlp.h).  Returns the device state, float64 [16] (``temperature_download`` reads it;
+    its first double is beta = 1 / T, what ``scale_logp`` takes); ``state`` / ``scratch`` (float64 [>= 4 N]): buffers to use.
+    Runs on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("fit_temperature", logp)
+    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"fit_temperature: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    with torch.cuda.device(logp.device):
+        if state is None:
+            state = torch.empty(CAL_STATE_DOUBLES, dtype=torch.float64, device=logp.device)
+        _cal_state("fit_temperature", state, logp.device)
+        if scratch is None:
+            scratch = torch.empty(4 * N, dtype=torch.float64, device=logp.device)
+        if not (scratch.device == logp.device and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.is_contiguous()):
+            raise ValueError(f"fit_temperature: scratch must be a contiguous float64 [>= {4 * N}] tensor on {logp.device}")
+        check(load().slnlp_fit_temperature(ptr(logp), ld, ptr(y), N, V, ptr(state), ptr(scratch), scratch.numel() * 8, stream_ptr()),
+              "fit_temperature")
+    return state
+
+
+def temperature_state(beta, device):
+    """A device state that holds only beta (and T): what ``scale_logp`` needs of a calibration read back from a checkpoint."""
+    state = torch.zeros(CAL_STATE_DOUBLES, dtype=torch.float64)
+    state[0], state[1] = float(beta), 1.0 / float(beta)
+    return state.to(device)
+
+
+def temperature_download(state):
+    """``fit_temperature``'s state as a dict: {temperature, beta, nll_before, nll_after, reason ("flat" | "bound" | "gradient" |
+    "step" | "cap"), iterations, rows, bad_labels}.  One device-to-host copy (it waits for the fit's launches)."""
+    h = state.cpu().numpy()
+    q = h.view("int64")[8:]
+    return {"temperature": float(h[1]), "beta": float(h[0]), "nll_before": float(h[2]), "nll_after": float(h[3]),
+            "reason": _lib.CALIBRATION_REASONS[int(q[0])], "iterations": int(q[1]), "rows": int(q[2]), "bad_labels": int(q[3])}
+
+
+def scale_logp(logp, state, out=None):
+    """The calibrated log-probs ``beta logp - logsumexp(beta logp)`` per row, beta read on the device from ``state``'s first double
+    (``slnlp_scale_logp``).  ``out``: a float32 [N, V] tensor to fill -- ``logp`` itself for in place; default a new one.  Runs on
+    the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("scale_logp", logp)
+    _cal_state("scale_logp", state, logp.device)
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = torch.empty(N, V, dtype=torch.float32, device=logp.device)
+        if out.device != logp.device or tuple(out.shape) != (N, V):
+            raise ValueError(f"scale_logp: out must be a float32 [{N}, {V}] tensor on {logp.device}")
+        _, _, ld_out = _logp_matrix("scale_logp (out)", out)
+        check(load().slnlp_scale_logp(ptr(logp), ld, N, V, ptr(state), ptr(out), ld_out, stream_ptr()), "scale_logp")
+    return out
+
+
 class ParamGroupTable:
     """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
     segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
