@@ -8,7 +8,7 @@
 //                         avg += (params - avg) / (count[0] + 1)    SLNLP_AVG_SWA  (AveragedModel's default avg_fn)
 //                         avg += (params - avg) * (1 - decay)       SLNLP_AVG_EMA  (get_ema_multi_avg_fn: a lerp)
 //   average_count_kernel  count[0] += 1, one thread, behind the update: every block of average_kernel reads the OLD count
-//                         (the Adam step count's rule, elementwise.hip).
+//                         (the Adam step count's rule, update.hip).
 //
 // Floats [skip_begin, skip_end) -- a parameter torch never steps -- are copied, so the average equals the model there.  The
 // update kernels are not touched: the accumulator reads the arena they leave behind (4 B / parameter more than a fused form

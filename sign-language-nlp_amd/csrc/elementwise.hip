@@ -1,5 +1,5 @@
 // elementwise.hip -- HBM-bound pieces of the step: embedding gather + positional
-// add, LayerNorm, log-softmax / NLL criterion, grad-norm clip + SGD-momentum.
+// add, LayerNorm, log-softmax / NLL criterion, dropout mask, batch gather (the clip + update: update.hip).
 // All fp32, 16-B vector accesses, one wave per row for the row-wise reductions.
 #include "common.hpp"
 #include "launch.hpp"
@@ -910,521 +910,6 @@ int lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dlogits,
     return 0;
 }
 
-// ================================================================= optimizer
-// clip_grad_norm_(max_norm) + torch.optim.SGD(momentum) over one flat arena.
-constexpr int OPT_BLOCKS = 1024;
-
-__device__ __forceinline__ void sumsq_body(const float* __restrict__ g, long n4, float* __restrict__ partials,
-                                           float* __restrict__ sgd_steps) {
-    // sgd_steps (optional): the SGD step count, advanced HERE -- before the update launch, which only reads it (every block
-    // of sgd_kernel sees the same value: 1 on the first step)
-    if (sgd_steps && blockIdx.x == 0 && threadIdx.x == 0) sgd_steps[0] += 1.f;
-    __shared__ float red[4];
-    float s = 0.f;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)OPT_BLOCKS * 256) {
-        const float4 v = reinterpret_cast<const float4*>(g)[i];
-        s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-SLNLP_ZKERNEL(sumsq_kernel, 256, sumsq_body)
-
-__device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  long n4, const float* __restrict__ lr_dev, float momentum,
-                                                  float max_norm, const float* __restrict__ partials,
-                                                  float* __restrict__ norm_out, unsigned long long* __restrict__ rng,
-                                                  PlaneOut wp, long wp_begin4, long wp_end4, float dampening, float weight_decay,
-                                                  int nesterov, const float* __restrict__ sgd_steps, long skip_begin4,
-                                                  long skip_end4) {
-    // wp (optional): the updated weights also leave as bf16 hi / lo planes (same offsets as the arena) -- the operand
-    // form the plane GEMMs of the NEXT step stage by LDS-DMA -- instead of a separate pass that re-reads the arena.
-    // Only float4 indices in [wp_begin4, wp_end4) are written: the plan passes the range of the weights that FEED plane GEMMs
-    // (the encoder layers: a third of a Transformer's parameters), the rest of the plane arena has no reader
-    __shared__ float red[4];
-    // every block re-derives the total in the same fixed order: deterministic, no third launch
-    float s = 0.f;
-    for (int i = threadIdx.x; i < OPT_BLOCKS; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
-    float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-    const float lr = lr_dev[0];
-    if (dampening != 0.f || weight_decay != 0.f || nesterov) {
-        // torch/optim/sgd.py _single_tensor_sgd: d = g' + wd p; buf = d on the first step, else m buf + (1 - dampening) d;
-        // d = d + m buf (nesterov) or buf; p -= lr d.  Float indices [skip_begin4, skip_end4) are a parameter torch never
-        // steps (its grad is None): left untouched.  Kept apart from the plain loop below, whose arithmetic stays as it was.
-        const bool first = sgd_steps[0] == 1.f;
-        const float damp = first ? 0.f : 1.f - dampening, keep = first ? 0.f : momentum;
-        for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-            float4 w = reinterpret_cast<float4*>(p)[i];
-            if (i < skip_begin4 || i >= skip_end4) {
-                const float4 gv = reinterpret_cast<const float4*>(g)[i];
-                float4 b = reinterpret_cast<float4*>(buf)[i];
-                float ge[4] = {gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef};
-                float be[4] = {b.x, b.y, b.z, b.w}, we[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float d = ge[e] + weight_decay * we[e];
-                    be[e] = first ? d : keep * be[e] + damp * d;
-                    d = nesterov ? d + momentum * be[e] : be[e];
-                    we[e] -= lr * d;
-                }
-                b = make_float4(be[0], be[1], be[2], be[3]);
-                w = make_float4(we[0], we[1], we[2], we[3]);
-                reinterpret_cast<float4*>(buf)[i] = b;
-                reinterpret_cast<float4*>(p)[i] = w;
-            }
-            if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, w);
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            if (norm_out) norm_out[0] = norm;
-            if (rng) rng[1] += 1ull;
-        }
-        return;
-    }
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 b = reinterpret_cast<float4*>(buf)[i];
-        float4 w = reinterpret_cast<float4*>(p)[i];
-        b.x = momentum * b.x + gv.x * coef; b.y = momentum * b.y + gv.y * coef;
-        b.z = momentum * b.z + gv.z * coef; b.w = momentum * b.w + gv.w * coef;
-        w.x -= lr * b.x; w.y -= lr * b.y; w.z -= lr * b.z; w.w -= lr * b.w;
-        reinterpret_cast<float4*>(buf)[i] = b;
-        reinterpret_cast<float4*>(p)[i] = w;
-        if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, w);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (norm_out) norm_out[0] = norm;
-        if (rng) rng[1] += 1ull;
-    }
-}
-SLNLP_ZKERNEL(sgd_kernel, 256, sgd_body)
-
-// torch.optim.Adam (amsgrad False, maximize False) fused with clip_grad_norm_, same two-launch shape as clip + SGD:
-//   g' = g * clip_coef (+ weight_decay * p);  m += (1 - b1)(g' - m);  v = b2 v + (1 - b2) g'^2;
-//   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)            (torch/optim/adam.py _single_tensor_adam)
-// The step count t lives in device memory (step_f[0], a float: exact to 2^24 steps) and is advanced here, so a captured
-// or recorded step needs no host-side argument that changes per step.
-__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, long n4, const float* __restrict__ lr_dev, float beta1,
-                                          float beta2, float eps, float weight_decay, float max_norm,
-                                          const float* __restrict__ partials, float* __restrict__ norm_out,
-                                          unsigned long long* __restrict__ rng, float* __restrict__ step_f, PlaneOut wp,
-                                          long wp_begin4, long wp_end4, int decoupled, long skip_begin4, long skip_end4) {
-    // decoupled (torch.optim.AdamW): p *= 1 - lr wd first, then the Adam update with no L2 term; float indices
-    // [skip_begin4, skip_end4) (a parameter torch never steps) are left untouched.  Plain Adam ignores the skip range.
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < OPT_BLOCKS; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
-    float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-    const float lr = lr_dev[0];
-    const float t = step_f[0] + 1.f;                       // every block reads the OLD count (adam_count_kernel advances it afterwards)
-    const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(beta2, t);
-    const float step_size = lr / bc1, rsq_bc2 = 1.f / sqrtf(bc2);
-    const float l2 = decoupled ? 0.f : weight_decay, decay = 1.f - lr * weight_decay;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        if (decoupled && i >= skip_begin4 && i < skip_end4) {
-            if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, reinterpret_cast<const float4*>(p)[i]);
-            continue;
-        }
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i], w = reinterpret_cast<float4*>(p)[i];
-        float ge[4] = {gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef};
-        float me[4] = {mm.x, mm.y, mm.z, mm.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w}, we[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (decoupled) we[e] *= decay;
-            if (l2 != 0.f) ge[e] += l2 * we[e];
-            me[e] += (1.f - beta1) * (ge[e] - me[e]);
-            ve[e] = beta2 * ve[e] + (1.f - beta2) * ge[e] * ge[e];
-            we[e] -= step_size * (me[e] / (sqrtf(ve[e]) * rsq_bc2 + eps));
-        }
-        reinterpret_cast<float4*>(m)[i] = make_float4(me[0], me[1], me[2], me[3]);
-        reinterpret_cast<float4*>(v)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
-        const float4 wn = make_float4(we[0], we[1], we[2], we[3]);
-        reinterpret_cast<float4*>(p)[i] = wn;
-        if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, wn);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (norm_out) norm_out[0] = norm;
-        if (rng) rng[1] += 1ull;
-    }
-}
-SLNLP_ZKERNEL(adam_kernel, 256, adam_body)
-
-// the count is advanced by its own one-thread launch AFTER the update (every block of adam_kernel must read the same old value)
-__device__ __forceinline__ void adam_count_body(float* __restrict__ step_f) { if (threadIdx.x == 0 && blockIdx.x == 0) step_f[0] += 1.f; }
-SLNLP_ZKERNEL(adam_count_kernel, 64, adam_count_body)
-
-// ------------------------------------------------ per-parameter-group update (optimizer__param_groups) ----
-// The same two launches as above (sumsq_kernel, then the update); the update reads lr and weight decay per float4 from
-// the segment its index falls in.  The table is staged in LDS once per block with the group's settings resolved per
-// segment, so the loop does one short binary search over LDS (no global reads) per float4; segment boundaries are
-// float4 indices, so the four floats of a vector always share a group.  The arithmetic per element is the ungrouped
-// bodies', expression for expression: a one-segment table gives the ungrouped kernels' bits.
-struct GroupLds {
-    int begin[GROUPS_MAX_SEGMENTS];
-    float lr[GROUPS_MAX_SEGMENTS], wd[GROUPS_MAX_SEGMENTS];
-};
-
-__device__ __forceinline__ void groups_stage(GroupLds& t, const GroupTab& gt) {    // the caller's barrier publishes it
-    for (int s = threadIdx.x; s < gt.n_seg; s += 256) {
-        const int gi = gt.seg_group[s];
-        t.begin[s] = gt.seg_begin4[s];
-        t.lr[s] = gt.lr[gi];
-        t.wd[s] = gt.wd[gi];
-    }
-}
-
-// the segment of float4 index i: the last s with begin[s] <= i (begin[0] == 0)
-__device__ __forceinline__ int groups_find(const GroupLds& t, int n_seg, long i) {
-    int lo = 0, hi = n_seg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long)t.begin[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ void sgd_groups_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                long n4, GroupTab gt, float momentum, float max_norm,
-                                                const float* __restrict__ partials, float* __restrict__ norm_out,
-                                                unsigned long long* __restrict__ rng, PlaneOut wp, long wp_begin4, long wp_end4,
-                                                float dampening, int general, int nesterov, const float* __restrict__ sgd_steps,
-                                                long skip_begin4, long skip_end4) {
-    // general: dampening, nesterov or ANY group's weight decay (decided on the host, as clip_sgd_step decides it for one group)
-    __shared__ float red[4];
-    __shared__ GroupLds tab;
-    groups_stage(tab, gt);
-    float s = 0.f;
-    for (int i = threadIdx.x; i < OPT_BLOCKS; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
-    float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-    if (general) {
-        const bool first = sgd_steps[0] == 1.f;
-        const float damp = first ? 0.f : 1.f - dampening, keep = first ? 0.f : momentum;
-        for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-            float4 w = reinterpret_cast<float4*>(p)[i];
-            if (i < skip_begin4 || i >= skip_end4) {
-                const int sg = groups_find(tab, gt.n_seg, i);
-                const float lr = tab.lr[sg], weight_decay = tab.wd[sg];
-                const float4 gv = reinterpret_cast<const float4*>(g)[i];
-                float4 b = reinterpret_cast<float4*>(buf)[i];
-                float ge[4] = {gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef};
-                float be[4] = {b.x, b.y, b.z, b.w}, we[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float d = ge[e] + weight_decay * we[e];
-                    be[e] = first ? d : keep * be[e] + damp * d;
-                    d = nesterov ? d + momentum * be[e] : be[e];
-                    we[e] -= lr * d;
-                }
-                b = make_float4(be[0], be[1], be[2], be[3]);
-                w = make_float4(we[0], we[1], we[2], we[3]);
-                reinterpret_cast<float4*>(buf)[i] = b;
-                reinterpret_cast<float4*>(p)[i] = w;
-            }
-            if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, w);
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            if (norm_out) norm_out[0] = norm;
-            if (rng) rng[1] += 1ull;
-        }
-        return;
-    }
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const float lr = tab.lr[groups_find(tab, gt.n_seg, i)];
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 b = reinterpret_cast<float4*>(buf)[i];
-        float4 w = reinterpret_cast<float4*>(p)[i];
-        b.x = momentum * b.x + gv.x * coef; b.y = momentum * b.y + gv.y * coef;
-        b.z = momentum * b.z + gv.z * coef; b.w = momentum * b.w + gv.w * coef;
-        w.x -= lr * b.x; w.y -= lr * b.y; w.z -= lr * b.z; w.w -= lr * b.w;
-        reinterpret_cast<float4*>(buf)[i] = b;
-        reinterpret_cast<float4*>(p)[i] = w;
-        if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, w);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (norm_out) norm_out[0] = norm;
-        if (rng) rng[1] += 1ull;
-    }
-}
-SLNLP_ZKERNEL(sgd_groups_kernel, 256, sgd_groups_body)
-
-__device__ __forceinline__ void adam_groups_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                 float* __restrict__ v, long n4, GroupTab gt, float beta1, float beta2, float eps,
-                                                 float max_norm, const float* __restrict__ partials, float* __restrict__ norm_out,
-                                                 unsigned long long* __restrict__ rng, float* __restrict__ step_f, PlaneOut wp,
-                                                 long wp_begin4, long wp_end4, int decoupled, long skip_begin4, long skip_end4) {
-    __shared__ float red[4];
-    __shared__ GroupLds tab;
-    groups_stage(tab, gt);
-    float s = 0.f;
-    for (int i = threadIdx.x; i < OPT_BLOCKS; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
-    float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-    const float t = step_f[0] + 1.f;                       // the OLD count, as adam_body reads it
-    const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(beta2, t);
-    const float rsq_bc2 = 1.f / sqrtf(bc2);
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        if (decoupled && i >= skip_begin4 && i < skip_end4) {
-            if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, reinterpret_cast<const float4*>(p)[i]);
-            continue;
-        }
-        const int sg = groups_find(tab, gt.n_seg, i);
-        const float lr = tab.lr[sg], weight_decay = tab.wd[sg];
-        const float step_size = lr / bc1;
-        const float l2 = decoupled ? 0.f : weight_decay, decay = 1.f - lr * weight_decay;
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i], w = reinterpret_cast<float4*>(p)[i];
-        float ge[4] = {gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef};
-        float me[4] = {mm.x, mm.y, mm.z, mm.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w}, we[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (decoupled) we[e] *= decay;
-            if (l2 != 0.f) ge[e] += l2 * we[e];
-            me[e] += (1.f - beta1) * (ge[e] - me[e]);
-            ve[e] = beta2 * ve[e] + (1.f - beta2) * ge[e] * ge[e];
-            we[e] -= step_size * (me[e] / (sqrtf(ve[e]) * rsq_bc2 + eps));
-        }
-        reinterpret_cast<float4*>(m)[i] = make_float4(me[0], me[1], me[2], me[3]);
-        reinterpret_cast<float4*>(v)[i] = make_float4(ve[0], ve[1], ve[2], ve[3]);
-        const float4 wn = make_float4(we[0], we[1], we[2], we[3]);
-        reinterpret_cast<float4*>(p)[i] = wn;
-        if (i >= wp_begin4 && i < wp_end4) store_planes4(wp, i * 4, wn);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (norm_out) norm_out[0] = norm;
-        if (rng) rng[1] += 1ull;
-    }
-}
-SLNLP_ZKERNEL(adam_groups_kernel, 256, adam_groups_body)
-
-// skip range [skip_begin, skip_end) in floats, 16-byte aligned (multiples of 4); empty when skip_end <= skip_begin
-static int check_skip(const char* what, int64_t n, int64_t skip_begin, int64_t skip_end) {
-    SLNLP_CHECK_ARG(skip_end <= skip_begin || (skip_begin >= 0 && skip_end <= n && skip_begin % 4 == 0 && skip_end % 4 == 0),
-                    "%s: skip range [%ld, %ld) must lie in [0, %ld) on multiples of 4", what, (long)skip_begin, (long)skip_end, (long)n);
-    return 0;
-}
-
-// pg (optional): lr_dev holds the groups' rates and each group decays with its own weight decay (so.weight_decay is not read)
-int clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* pg, const float* lr_dev,
-                  float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
-                  hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end, SgdOpts so) {
-    const char* what = pg ? "clip_sgd_step_groups" : "clip_sgd_step";
-    SLNLP_CHECK_ARG(params && grads && momentum_buf && lr_dev && partials, "%s: null pointer", what);
-    if (pg)
-        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n == pg->n, "clip_sgd_step_groups: n=%ld must be the table's (%ld), a positive multiple of 4",
-                        (long)n, (long)pg->n);
-    else
-        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_sgd_step: n=%ld must be a positive multiple of 4", (long)n);
-    SLNLP_CHECK_ARG(((uintptr_t)params & 15) == 0 && ((uintptr_t)grads & 15) == 0 && ((uintptr_t)momentum_buf & 15) == 0,
-                    "%s: arenas must be 16-byte aligned", what);
-    // torch's argument rules (torch.optim.SGD.__init__); without momentum torch keeps no buffer, so dampening is moot
-    if (pg)
-        SLNLP_CHECK_ARG(so.dampening >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
-                        "clip_sgd_step_groups: bad dampening %g / nesterov (needs momentum > 0 and dampening 0)", so.dampening);
-    else
-        SLNLP_CHECK_ARG(so.dampening >= 0.f && so.weight_decay >= 0.f && (!so.nesterov || (momentum > 0.f && so.dampening == 0.f)),
-                        "clip_sgd_step: bad dampening %g / weight_decay %g / nesterov (needs momentum > 0 and dampening 0)",
-                        so.dampening, so.weight_decay);
-    SLNLP_TRY(check_skip(what, n, so.skip_begin, so.skip_end));
-    const float damp = momentum != 0.f ? so.dampening : 0.f;
-    const bool general = damp != 0.f || (pg ? pg->any_wd : so.weight_decay != 0.f) || so.nesterov;
-    SLNLP_CHECK_ARG(!general || so.steps, "%s: dampening / weight decay / nesterov need the step counter", what);
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq",
-                      grads, (long)(n / 4), partials, so.steps));
-    int grid = ceil_div(n / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const long sb4 = so.skip_end > so.skip_begin ? (long)(so.skip_begin / 4) : 0, se4 = so.skip_end > so.skip_begin ? (long)(so.skip_end / 4) : 0;
-    const long wb4 = (long)(wp_begin / 4), we4 = (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4);
-    if (pg)
-        return zlaunch(sgd_groups_kernel, dim3(grid), 256, 0, st, "sgd_groups",
-                       params, grads, momentum_buf, (long)(n / 4), pg->tab(lr_dev), momentum, max_norm, partials, norm_out, rng, wp,
-                       wb4, we4, damp, general ? 1 : 0, so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4);
-    return zlaunch(sgd_kernel, dim3(grid), 256, 0, st, "sgd",
-                   params, grads, momentum_buf, (long)(n / 4), lr_dev, momentum, max_norm, partials, norm_out, rng, wp,
-                   wb4, we4, damp, so.weight_decay, so.nesterov ? 1 : 0, (const float*)so.steps, sb4, se4);
-}
-
-// pg (optional): lr_dev holds the groups' rates and each group decays with its own weight decay (weight_decay is not read)
-int clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const slnlp_param_groups* pg,
-                   const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials,
-                   float* norm_out, unsigned long long* rng, float* step_f, hipStream_t st, PlaneOut wp, int64_t wp_begin, int64_t wp_end,
-                   AdamOpts ao) {
-    const char* what = pg ? "clip_adam_step_groups" : "clip_adam_step";
-    SLNLP_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && lr_dev && partials && step_f, "%s: null pointer", what);
-    SLNLP_TRY(check_skip(what, n, ao.skip_begin, ao.skip_end));
-    if (pg) {
-        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n == pg->n, "clip_adam_step_groups: n=%ld must be the table's (%ld), a positive multiple of 4",
-                        (long)n, (long)pg->n);
-    } else {
-        SLNLP_CHECK_ARG(weight_decay >= 0.f, "clip_adam_step: weight_decay %g < 0", weight_decay);
-        SLNLP_CHECK_ARG(n > 0 && n % 4 == 0, "clip_adam_step: n=%ld must be a positive multiple of 4", (long)n);
-    }
-    SLNLP_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
-                    "%s: arenas must be 16-byte aligned", what);
-    SLNLP_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "%s: bad betas / eps", what);
-    SLNLP_TRY(zlaunch(sumsq_kernel, dim3(OPT_BLOCKS), 256, 0, st, "sumsq", grads, (long)(n / 4), partials, (float*)nullptr));
-    int grid = ceil_div(n / 4, 256);
-    if (grid > 2048) grid = 2048;
-    const long sb4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_begin / 4) : 0, se4 = ao.skip_end > ao.skip_begin ? (long)(ao.skip_end / 4) : 0;
-    const long wb4 = (long)(wp_begin / 4), we4 = (long)(wp_end < 0 ? n / 4 : (wp_end + 3) / 4);
-    if (pg)
-        SLNLP_TRY(zlaunch(adam_groups_kernel, dim3(grid), 256, 0, st, "adam_groups", params, grads, exp_avg, exp_avg_sq, (long)(n / 4),
-                          pg->tab(lr_dev), beta1, beta2, eps, max_norm, partials, norm_out, rng, step_f, wp, wb4, we4,
-                          ao.decoupled ? 1 : 0, sb4, se4));
-    else
-        SLNLP_TRY(zlaunch(adam_kernel, dim3(grid), 256, 0, st, "adam", params, grads, exp_avg, exp_avg_sq, (long)(n / 4), lr_dev, beta1,
-                          beta2, eps, weight_decay, max_norm, partials, norm_out, rng, step_f, wp, wb4, we4, ao.decoupled ? 1 : 0, sb4, se4));
-    return zlaunch(adam_count_kernel, dim3(1), 64, 0, st, "adam_count", step_f);
-}
-
-int param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
-                        const float* weight_decay, hipStream_t st, slnlp_param_groups** out) {
-    SLNLP_CHECK_ARG(out && seg_begin && seg_group && weight_decay, "param_groups_create: null pointer");
-    *out = nullptr;
-    SLNLP_CHECK_ARG(n > 0 && n % 4 == 0 && n / 4 < 0x7fffffffL, "param_groups_create: n=%ld must be a positive multiple of 4", (long)n);
-    SLNLP_CHECK_ARG(n_segments >= 1 && n_segments <= GROUPS_MAX_SEGMENTS && n_groups >= 1 && n_groups <= n_segments,
-                    "param_groups_create: %d segments (1..%d) in %d groups (1..segments)", n_segments, GROUPS_MAX_SEGMENTS, n_groups);
-    SLNLP_CHECK_ARG(seg_begin[0] == 0, "param_groups_create: the first segment must begin at 0");
-    for (int s = 0; s < n_segments; ++s) {
-        SLNLP_CHECK_ARG(seg_begin[s] % 4 == 0 && seg_begin[s] < n && (s == 0 || seg_begin[s] > seg_begin[s - 1]),
-                        "param_groups_create: segment %d begins at %ld: must be a multiple of 4 in [0, %ld), strictly increasing", s,
-                        (long)seg_begin[s], (long)n);
-        SLNLP_CHECK_ARG(seg_group[s] >= 0 && seg_group[s] < n_groups, "param_groups_create: segment %d in group %d of %d", s, seg_group[s],
-                        n_groups);
-    }
-    bool any = false;
-    for (int gi = 0; gi < n_groups; ++gi) {
-        SLNLP_CHECK_ARG(weight_decay[gi] >= 0.f, "param_groups_create: weight_decay %g of group %d < 0", weight_decay[gi], gi);
-        any = any || weight_decay[gi] != 0.f;
-    }
-    slnlp_param_groups* pg = new slnlp_param_groups;
-    pg->n = n; pg->n_seg = n_segments; pg->n_groups = n_groups; pg->any_wd = any;
-    pg->host.resize(2 * (size_t)n_segments + n_groups);
-    for (int s = 0; s < n_segments; ++s) {
-        pg->host[s] = (int)(seg_begin[s] / 4);
-        pg->host[n_segments + s] = seg_group[s];
-    }
-    memcpy(pg->host.data() + 2 * (size_t)n_segments, weight_decay, (size_t)n_groups * sizeof(float));
-    const size_t bytes = pg->host.size() * sizeof(int);
-    if (hipMalloc(&pg->dev, bytes) != hipSuccess ||
-        hipMemcpyAsync(pg->dev, pg->host.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
-        set_error("param_groups_create: allocating / uploading the table failed: %s", hipGetErrorString(hipGetLastError()));
-        param_groups_destroy(pg);
-        return SLNLP_ERR_LAUNCH;
-    }
-    *out = pg;
-    return 0;
-}
-
-void param_groups_destroy(slnlp_param_groups* pg) {
-    if (!pg) return;
-    if (pg->dev) (void)hipFree(pg->dev);
-    delete pg;
-}
-
-// ============================================================ plan settings
-TrainOpts::~TrainOpts() {
-    if (class_weight) (void)hipFree(class_weight);
-    param_groups_destroy(groups);
-    param_groups_destroy(one);
-}
-
-int TrainOpts::one_segment(int64_t n, float wd, hipStream_t st, const slnlp_param_groups** out) {
-    float have = 0.f;
-    if (one) memcpy(&have, &one->host[2], sizeof(float));
-    if (!one || one->n != n || have != wd) {
-        // (a changed weight decay moved the settings generation: no recorded program reads the old table any more, and
-        //  hipFree waits for the device)
-        param_groups_destroy(one);
-        one = nullptr;
-        const int64_t begin = 0;
-        const int group = 0;
-        SLNLP_TRY(param_groups_create(n, 1, &begin, &group, 1, &wd, st, &one));
-    }
-    *out = one;
-    return 0;
-}
-
-int TrainOpts::set_criterion(int V, const float* cw, float eps, int red, hipStream_t st, bool* changed) {
-    SLNLP_CHECK_ARG(V > 0 && eps >= 0.f && eps <= 1.f && (red == 0 || red == 1),
-                    "set_criterion: label_smoothing %g outside [0, 1] or reduction %d not 0 (mean) / 1 (sum)", eps, red);
-    std::vector<float> host;
-    if (cw) host.assign(cw, cw + V);   // host memory
-    *changed = host != class_weight_host || eps != label_smoothing || red != reduction;
-    if (!*changed) return 0;
-    if (cw && !class_weight && hipMalloc(&class_weight, (size_t)V * sizeof(float)) != hipSuccess) {
-        class_weight = nullptr;
-        set_error("set_criterion: allocating the class weights failed");
-        return SLNLP_ERR_LAUNCH;
-    }
-    class_weight_host.swap(host);
-    // from the plan's own host copy (alive until the next change), ordered on the fit's stream before its next step
-    if (cw && hipMemcpyAsync(class_weight, class_weight_host.data(), (size_t)V * sizeof(float), hipMemcpyHostToDevice, st) !=
-                  hipSuccess) {
-        set_error("set_criterion: copying the class weights failed");
-        return SLNLP_ERR_LAUNCH;
-    }
-    if (!cw && class_weight) {
-        (void)hipFree(class_weight);
-        class_weight = nullptr;
-    }
-    label_smoothing = eps;
-    reduction = red;
-    ++gen;
-    return 0;
-}
-
-int TrainOpts::set_update(int k, float damp, float wd, int nest, bool* changed) {
-    SLNLP_CHECK_ARG(k == SLNLP_UPDATE_SGD || k == SLNLP_UPDATE_ADAM || k == SLNLP_UPDATE_ADAMW, "set_update: unknown kind %d", k);
-    SLNLP_CHECK_ARG(damp >= 0.f && wd >= 0.f, "set_update: dampening %g / weight_decay %g must be >= 0", damp, wd);
-    SLNLP_CHECK_ARG(!nest || damp == 0.f, "set_update: Nesterov momentum requires zero dampening");
-    SLNLP_CHECK_ARG(k == SLNLP_UPDATE_SGD || (damp == 0.f && !nest), "set_update: dampening / nesterov are SGD's");
-    nest = nest ? 1 : 0;
-    *changed = k != kind || damp != dampening || wd != weight_decay || nest != nesterov;
-    if (!*changed) return 0;
-    kind = k; dampening = damp; weight_decay = wd; nesterov = nest;
-    ++gen;
-    return 0;
-}
-
-int TrainOpts::set_param_groups(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
-                                const float* wd, const float* lr_dev, hipStream_t st) {
-    slnlp_param_groups* pg = nullptr;
-    if (n_segments != 0) {
-        SLNLP_CHECK_ARG(lr_dev, "set_param_groups: null lr_dev");
-        SLNLP_TRY(param_groups_create(n, n_segments, seg_begin, seg_group, n_groups, wd, st, &pg));
-    }
-    // the old table may still be read by queued work: the caller drops its graphs (a device-wide wait) before this returns;
-    // freeing goes through hipFree, which waits for the device itself
-    param_groups_destroy(groups);
-    groups = pg;
-    groups_lr = pg ? lr_dev : nullptr;
-    ++gen;
-    return 0;
-}
-
 // ============================================================== dropout mask
 __global__ void dropout_mask_kernel(float* out, int R, int C, unsigned thr, int site, const unsigned long long* rng) {
     const long total = (long)R * C;
@@ -1495,54 +980,6 @@ int slnlp_lsm_nll_ex(const float* logits, int64_t ld_logits, const int64_t* y, i
 int slnlp_lsm_bwd(const float* logp, const float* dlogp, int B, int V, float* dlogits, int64_t ld_dlogits,
                   void* stream) {
     return slnlp::lsm_bwd(logp, dlogp, B, V, dlogits, ld_dlogits, (hipStream_t)stream);
-}
-int slnlp_clip_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
-                        float momentum, float max_norm, float* partials, float* norm_out, unsigned long long* rng,
-                        void* stream) {
-    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, nullptr, lr_dev, momentum, max_norm, partials, norm_out, rng,
-                                (hipStream_t)stream);
-}
-int slnlp_clip_sgd_step_ex(float* params, const float* grads, float* momentum_buf, int64_t n, const float* lr_dev,
-                           float momentum, float dampening, float weight_decay, int nesterov, float max_norm, float* partials,
-                           float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
-    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, nullptr, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
-                                (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
-                                slnlp::SgdOpts{dampening, weight_decay, nesterov, step_count, skip_begin, skip_end});
-}
-int slnlp_clip_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
-                          float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
-                          float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
-    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, nullptr, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
-                                 norm_out, nullptr, step_count, (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
-                                 slnlp::AdamOpts{1, skip_begin, skip_end});
-}
-int slnlp_clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* lr_dev,
-                         float beta1, float beta2, float eps, float weight_decay, float max_norm, float* partials, float* norm_out,
-                         float* step_count, void* stream) {
-    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, nullptr, lr_dev, beta1, beta2, eps, weight_decay, max_norm, partials,
-                                 norm_out, nullptr, step_count, (hipStream_t)stream);
-}
-int slnlp_param_groups_create(int64_t n, int n_segments, const int64_t* seg_begin, const int32_t* seg_group, int n_groups,
-                              const float* weight_decay, void* stream, slnlp_param_groups** out) {
-    return slnlp::param_groups_create(n, n_segments, seg_begin, seg_group, n_groups, weight_decay, (hipStream_t)stream, out);
-}
-void slnlp_param_groups_destroy(slnlp_param_groups* groups) { slnlp::param_groups_destroy(groups); }
-int slnlp_clip_sgd_step_groups(float* params, const float* grads, float* momentum_buf, int64_t n, const slnlp_param_groups* groups,
-                               const float* lr_dev, float momentum, float dampening, int nesterov, float max_norm, float* partials,
-                               float* norm_out, float* step_count, int64_t skip_begin, int64_t skip_end, void* stream) {
-    SLNLP_CHECK_ARG(groups, "clip_sgd_step_groups: null pointer");
-    return slnlp::clip_sgd_step(params, grads, momentum_buf, n, groups, lr_dev, momentum, max_norm, partials, norm_out, nullptr,
-                                (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
-                                slnlp::SgdOpts{dampening, 0.f, nesterov, step_count, skip_begin, skip_end});
-}
-int slnlp_clip_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                const slnlp_param_groups* groups, const float* lr_dev, float beta1, float beta2, float eps,
-                                int decoupled, float max_norm, float* partials, float* norm_out, float* step_count,
-                                int64_t skip_begin, int64_t skip_end, void* stream) {
-    SLNLP_CHECK_ARG(groups, "clip_adam_step_groups: null pointer");
-    return slnlp::clip_adam_step(params, grads, exp_avg, exp_avg_sq, n, groups, lr_dev, beta1, beta2, eps, 0.f, max_norm, partials,
-                                 norm_out, nullptr, step_count, (hipStream_t)stream, slnlp::PlaneOut{}, 0, -1,
-                                 slnlp::AdamOpts{decoupled ? 1 : 0, skip_begin, skip_end});
 }
 int slnlp_gather_batch(const int64_t* X, const int64_t* lengths, const int64_t* y, const int64_t* order, int64_t row0, int B, int S,
                        int64_t* X_out, int64_t* len_out, int64_t* y_out, void* stream) {

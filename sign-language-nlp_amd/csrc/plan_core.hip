@@ -3,6 +3,87 @@
 
 namespace slnlp {
 
+// A plan's criterion / update / param-group settings (TrainOpts, common.hpp)
+TrainOpts::~TrainOpts() {
+    if (class_weight) (void)hipFree(class_weight);
+    param_groups_destroy(groups);
+    param_groups_destroy(one);
+}
+
+int TrainOpts::one_segment(int64_t n, float wd, hipStream_t st, const slnlp_param_groups** out) {
+    float have = 0.f;
+    if (one) memcpy(&have, &one->host[2], sizeof(float));
+    if (!one || one->n != n || have != wd) {
+        // (a changed weight decay moved the settings generation: no recorded program reads the old table any more, and
+        //  hipFree waits for the device)
+        param_groups_destroy(one);
+        one = nullptr;
+        const int64_t begin = 0;
+        const int group = 0;
+        SLNLP_TRY(param_groups_create(n, 1, &begin, &group, 1, &wd, st, &one));
+    }
+    *out = one;
+    return 0;
+}
+
+int TrainOpts::set_criterion(int V, const float* cw, float eps, int red, hipStream_t st, bool* changed) {
+    SLNLP_CHECK_ARG(V > 0 && eps >= 0.f && eps <= 1.f && (red == 0 || red == 1),
+                    "set_criterion: label_smoothing %g outside [0, 1] or reduction %d not 0 (mean) / 1 (sum)", eps, red);
+    std::vector<float> host;
+    if (cw) host.assign(cw, cw + V);   // host memory
+    *changed = host != class_weight_host || eps != label_smoothing || red != reduction;
+    if (!*changed) return 0;
+    if (cw && !class_weight && hipMalloc(&class_weight, (size_t)V * sizeof(float)) != hipSuccess) {
+        class_weight = nullptr;
+        set_error("set_criterion: allocating the class weights failed");
+        return SLNLP_ERR_LAUNCH;
+    }
+    class_weight_host.swap(host);
+    // from the plan's own host copy (alive until the next change), ordered on the fit's stream before its next step
+    if (cw && hipMemcpyAsync(class_weight, class_weight_host.data(), (size_t)V * sizeof(float), hipMemcpyHostToDevice, st) !=
+                  hipSuccess) {
+        set_error("set_criterion: copying the class weights failed");
+        return SLNLP_ERR_LAUNCH;
+    }
+    if (!cw && class_weight) {
+        (void)hipFree(class_weight);
+        class_weight = nullptr;
+    }
+    label_smoothing = eps;
+    reduction = red;
+    ++gen;
+    return 0;
+}
+
+int TrainOpts::set_update(int k, float damp, float wd, int nest, bool* changed) {
+    SLNLP_CHECK_ARG(k == SLNLP_UPDATE_SGD || k == SLNLP_UPDATE_ADAM || k == SLNLP_UPDATE_ADAMW, "set_update: unknown kind %d", k);
+    SLNLP_CHECK_ARG(damp >= 0.f && wd >= 0.f, "set_update: dampening %g / weight_decay %g must be >= 0", damp, wd);
+    SLNLP_CHECK_ARG(!nest || damp == 0.f, "set_update: Nesterov momentum requires zero dampening");
+    SLNLP_CHECK_ARG(k == SLNLP_UPDATE_SGD || (damp == 0.f && !nest), "set_update: dampening / nesterov are SGD's");
+    nest = nest ? 1 : 0;
+    *changed = k != kind || damp != dampening || wd != weight_decay || nest != nesterov;
+    if (!*changed) return 0;
+    kind = k; dampening = damp; weight_decay = wd; nesterov = nest;
+    ++gen;
+    return 0;
+}
+
+int TrainOpts::set_param_groups(int64_t n, int n_segments, const int64_t* seg_begin, const int* seg_group, int n_groups,
+                                const float* wd, const float* lr_dev, hipStream_t st) {
+    slnlp_param_groups* pg = nullptr;
+    if (n_segments != 0) {
+        SLNLP_CHECK_ARG(lr_dev, "set_param_groups: null lr_dev");
+        SLNLP_TRY(param_groups_create(n, n_segments, seg_begin, seg_group, n_groups, wd, st, &pg));
+    }
+    // the old table may still be read by queued work: the caller drops its graphs (a device-wide wait) before this returns;
+    // freeing goes through hipFree, which waits for the device itself
+    param_groups_destroy(groups);
+    groups = pg;
+    groups_lr = pg ? lr_dev : nullptr;
+    ++gen;
+    return 0;
+}
+
 // clip_grad_norm_ + torch.optim.SGD on the arena.  Beside a grouped fit of a lockstep group a plan without groups records the
 // same kernel with a one-segment table: its own lr scalar, its own weight decay
 int PlanCore::update_sgd(float momentum, float max_norm, hipStream_t st) {

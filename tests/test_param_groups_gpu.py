@@ -118,11 +118,17 @@ def test_clip_adam_groups_vs_torch(decoupled):
         assert torch.equal(P[SKIP[0]:SKIP[1]].cpu(), p0[SKIP[0]:SKIP[1]])
 
 
-@pytest.mark.parametrize("case", ["sgd_plain", "sgd_general", "adam", "adamw"])
-def test_one_group_is_the_ungrouped_kernel_bit_for_bit(case):
+# the update's grid is capped at 2048 blocks of 256 float4: 1 << 18 floats is one trip of the grid-stride loop; the second size
+# takes a second trip with a ragged tail, its skip range straddling the float4 index where that trip begins
+ONE_GROUP_SIZES = {"one_trip": (1 << 18, (4096, 8192)), "two_trips": (4 * (2048 * 256 + 517), (4 * (2048 * 256 - 300), 4 * (2048 * 256 + 200)))}
+
+
+@pytest.mark.parametrize("case,size", [pytest.param(c, s, id=c if s == "one_trip" else f"{c}-{s}")          # (the first size keeps its ids)
+                                       for s in ONE_GROUP_SIZES for c in ("sgd_plain", "sgd_general", "adam", "adamw")])
+def test_one_group_is_the_ungrouped_kernel_bit_for_bit(case, size):
     """One segment covering the arena with the fit's own lr / weight decay: weights and state equal the one-group entry point's."""
     from slnlp import ops
-    n = 1 << 18
+    n, skip = ONE_GROUP_SIZES[size]
     p0, b0, v0 = rnd(n, seed=1), rnd(n, seed=3, scale=1e-3), rnd(n, seed=4, scale=1e-3).abs()
     wd = {"sgd_plain": 0.0, "sgd_general": 1e-3, "adam": 1e-3, "adamw": 1e-2}[case]
     table = ops.ParamGroupTable(n, [0], [0], [wd])
@@ -135,15 +141,14 @@ def test_one_group_is_the_ungrouped_kernel_bit_for_bit(case):
             na = ops.clip_sgd_step_ex(a["P"], g, a["B"], lr, a["cnt"], momentum=0.9, max_norm=0.5)
             nb = ops.clip_sgd_step_groups(b["P"], g, b["B"], table, lr, b["cnt"], momentum=0.9, max_norm=0.5)
         elif case == "sgd_general":
-            na = ops.clip_sgd_step_ex(a["P"], g, a["B"], lr, a["cnt"], momentum=0.9, dampening=0.3, weight_decay=wd, max_norm=0.5, skip=(4096, 8192))
-            nb = ops.clip_sgd_step_groups(b["P"], g, b["B"], table, lr, b["cnt"], momentum=0.9, dampening=0.3, max_norm=0.5, skip=(4096, 8192))
+            na = ops.clip_sgd_step_ex(a["P"], g, a["B"], lr, a["cnt"], momentum=0.9, dampening=0.3, weight_decay=wd, max_norm=0.5, skip=skip)
+            nb = ops.clip_sgd_step_groups(b["P"], g, b["B"], table, lr, b["cnt"], momentum=0.9, dampening=0.3, max_norm=0.5, skip=skip)
         elif case == "adam":
             na = ops.clip_adam_step(a["P"], g, a["B"], a["V"], lr, a["cnt"], betas=(0.9, 0.99), weight_decay=wd, max_norm=0.5)
             nb = ops.clip_adam_step_groups(b["P"], g, b["B"], b["V"], table, lr, b["cnt"], betas=(0.9, 0.99), max_norm=0.5)
         else:
-            na = ops.clip_adamw_step(a["P"], g, a["B"], a["V"], lr, a["cnt"], betas=(0.9, 0.99), weight_decay=wd, max_norm=0.5, skip=(4096, 8192))
-            nb = ops.clip_adam_step_groups(b["P"], g, b["B"], b["V"], table, lr, b["cnt"], betas=(0.9, 0.99), decoupled=True, max_norm=0.5,
-                                           skip=(4096, 8192))
+            na = ops.clip_adamw_step(a["P"], g, a["B"], a["V"], lr, a["cnt"], betas=(0.9, 0.99), weight_decay=wd, max_norm=0.5, skip=skip)
+            nb = ops.clip_adam_step_groups(b["P"], g, b["B"], b["V"], table, lr, b["cnt"], betas=(0.9, 0.99), decoupled=True, max_norm=0.5, skip=skip)
         assert torch.equal(na, nb)
         for k in a:
             assert torch.equal(a[k], b[k]), (case, step, k)

@@ -21,9 +21,10 @@ for p in (ROOT, os.path.join(ROOT, "sign-language-nlp_amd")):
 TF1 = dict(E=128, H=4, N=2, F=256, Vs=3000, Vt=202, B=50, S=48, dropout=0.1)
 RNN3 = dict(E=512, Hd=512, N=4, Vs=3000, Vt=202, B=50, S=48, dropout=0.1)
 RNN0 = dict(E=24, Hd=32, N=2, Vs=300, Vt=40, B=8, S=10, dropout=0.1)
-# name -> (config, options: steps / graph / lockstep K / adam / env)
+TF0 = dict(E=32, H=4, N=2, F=64, Vs=300, Vt=40, B=8, S=12, dropout=0.1)
+# name -> (config, options: steps / graph / lockstep K / adam / update (set_update's arguments) / groups (per fit: a table?) / env)
 CASES = {
-    "tf_tiny": (dict(E=32, H=4, N=2, F=64, Vs=300, Vt=40, B=8, S=12, dropout=0.1), {}),          # fp32-operand path everywhere
+    "tf_tiny": (TF0, {}),                                                                        # fp32-operand path everywhere
     "tf_cfg1_d0": (dict(TF1, dropout=0.0), {}),                                                  # planes + B-row products
     "tf_cfg1": (TF1, {}),                                                                        # ... masked LayerNorm planes, per-head dropout
     "tf_cfg1_decrows0": (TF1, dict(env={"SLNLP_DEC_ROWS": "0"})),                                # plane encoder, fp32-operand decoder
@@ -38,7 +39,22 @@ CASES = {
     "rnn_lstm_cfg3_d0": (dict(RNN3, rnn="lstm", dropout=0.0), dict(steps=3)), "rnn_lstm_cfg3": (dict(RNN3, rnn="lstm"), dict(steps=3)),   # planes path
     "rnn_gru_cfg3_d0": (dict(RNN3, rnn="gru", dropout=0.0), dict(steps=3)), "rnn_gru_cfg3": (dict(RNN3, rnn="gru"), dict(steps=3)),
     "rnn_lstm_cfg3_ls3": (dict(RNN3, rnn="lstm"), dict(steps=3, lockstep=3)),                    # RNN recorder path
+    # the fused update's dispatch branches (csrc/update.hip)
+    "tf_tiny_sgd_damp_wd": (TF0, dict(update=dict(dampening=0.3, weight_decay=1e-2))),           # SGD's general loop
+    "tf_tiny_sgd_nesterov": (TF0, dict(update=dict(nesterov=True))),
+    "rnn_lstm_tiny_adamw": (dict(RNN0, rnn="lstm"), dict(adam=True, update=dict(kind="adamw", weight_decay=1e-2))),   # a skip range (the dead pre-output bias)
+    "tf_tiny_groups_sgd": (TF0, dict(groups=(True,), update=dict(weight_decay=1e-2))),           # the table kernels
+    "tf_tiny_groups_adamw": (TF0, dict(groups=(True,), adam=True, update=dict(kind="adamw", weight_decay=1e-2))),
+    "tf_cfg1_groups": (TF1, dict(groups=(True,))),                                               # ... writing the weight planes
+    "tf_tiny_ls3_groups": (TF0, dict(lockstep=3, groups=(True, True, False), update=dict(weight_decay=1e-2))),   # the ungrouped fit on a one-segment table
 }
+
+
+def group_table(e, f, torch):
+    """One segment per arena entry, dealt over 3 groups (fit f starts at group f) with their own weight decay and rate."""
+    begin = sorted({off for _, _, off in e.entries})
+    table = {"seg_begin": begin, "seg_group": [(i + f) % 3 for i in range(len(begin))], "weight_decay": [1e-2, 0.0, 1e-3]}
+    return table, torch.tensor([0.01 * (1 + f), 0.02, 0.005], device=e.device)
 
 
 def crc(*tensors):
@@ -66,6 +82,10 @@ def main():
         e = (re_.RnnEngine if rnn else te.TransformerEngine)(cfg, device=dev, seed=1 + f)
         e.load_state(sd)
         e.set_lr(0.01 * (1 + f))
+        if o.get("update"):
+            e.set_update(**o["update"])
+        if f < len(o.get("groups", ())) and o["groups"][f]:
+            e.set_param_groups(*group_table(e, f, torch))
         X, L, y = (torch.from_numpy(a).to(dev) for a in synth.make_batch(steps * B, S, c["Vs"], c["Vt"], seed=1 + f))
         engs.append(e)
         data.append((X, y, L))
@@ -86,7 +106,8 @@ def main():
             v2 = torch.zeros_like(e.params) if o.get("adam") else None
             for i in range(steps):
                 if v2 is not None:
-                    logp = e.train_step_adam(*batch(i)[:2], v2, lengths=batch(i)[2] if rnn else None)
+                    logp = e.train_step_adam(*batch(i)[:2], v2, weight_decay=o.get("update", {}).get("weight_decay", 0.0),
+                                             lengths=batch(i)[2] if rnn else None)
                 else:
                     logp = (e.train_step_graph if o.get("graph") else e.train_step)(*batch(i))
             out["logp"] = crc(logp, *([v2] if v2 is not None else []))
