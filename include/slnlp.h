@@ -383,6 +383,33 @@ int slnlp_fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64
 int slnlp_scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, float* out, int64_t ld_out,
                      void* stream);
 
+/* ------------------------------------------------------ reliability diagnostics --
+ * What expected / maximum calibration error (ECE, MCE), the multiclass Brier score and the log-loss of a set of log-probs are
+ * functions of (slnlp/ops.py forms the scores on the host).  logp float32 [N, ld], V <= ld columns used; y int64 [N]; bins = B
+ * in 1..SLNLP_REL_MAX_BINS; beta = beta_dev ? beta_dev[0] : 1 exactly -- beta_dev is device memory (a calibration state's
+ * first double), so the call never waits for the host; p = softmax(beta z_i) is never materialised.  Per row i, in fp64
+ * throughout (z itself is float32), with zmax the float32 row maximum, a = beta zmax, e_c = exp(beta z_c - a), k the number
+ * of columns at the maximum (e = 1 exactly: counted, not summed), rest = sum_{c not at max} e_c + (k - 1), s0 = 1 + rest:
+ *   pred    index of the first maximum (slnlp_score_rows' order)          correct = (pred == y_i)
+ *   conf    1 / s0, the probability of the arg-max class
+ *   brier   sum_c (p_c - 1[c = y_i])^2 = (k + sum_{c not at max} e_c^2) / s0^2 - 2 exp(beta z_y - a) / s0 + 1
+ *   nll     log1p(rest) - (beta z_y - a)                                   (slnlp_fit_temperature's f_i)
+ *   bin     clamp(ceil(conf B) - 1, 0, B - 1), from the conf that is stored: equal-width bins (b / B, (b + 1) / B], closed on
+ *           the right (Guo et al. 2017), so conf = 1 and conf one ulp below 1 both land in bin B - 1
+ * rows  double [N, 4]:     (conf, brier, nll, code); code = 2 bin + correct for a scored row; code = -1 and three zeros for a
+ *                          label outside [0, V) (looked at first, never used as an index); code = -2 and three NaN for a row
+ *                          that holds a NaN or whose maximum is not finite
+ * table double [B + 1, 4]: row b < B = (count, sum conf, sum correct, 0) over the scored rows of bin b; row B = (sum brier,
+ *                          sum nll, n_bad_label, n_nan), the two sums over the scored rows only
+ * Two launches: the rows (a wave per row, no LDS), then B + 1 blocks of 256 threads, block b summing bin b (block B the totals):
+ * thread t adds rows t, t + 256, ... in increasing order, then a fixed binary tree over the 256 partial sums.  No atomics: the
+ * result is a function of the arguments alone.  rows and table are 32-byte aligned.  Errors (SLNLP_ERR_INVALID_ARG with a
+ * message, before anything is launched): a null pointer (beta_dev may be null), N or V outside 1..INT32_MAX, bins outside
+ * 1..SLNLP_REL_MAX_BINS, ld < V, a misaligned pointer, an output overlapping an input or the other output. */
+#define SLNLP_REL_MAX_BINS 64
+int slnlp_reliability_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int bins, const double* beta_dev,
+                           double* rows, double* table, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

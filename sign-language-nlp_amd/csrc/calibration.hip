@@ -54,23 +54,7 @@ constexpr double CAL_BETA_MIN = 0.015625, CAL_BETA_MAX = 64.0;                  
 constexpr double CAL_GRAD_TOL = 5.6843418860808015e-14;                           // 2^-44
 constexpr double CAL_STEP_TOL = 9.094947017729282e-13;                            // 2^-40
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_bcast_d(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-// over the whole wave (all 64 lanes active), in one fixed order; every lane gets the result
-__device__ __forceinline__ double wave_sum_d(double v) {
-    v += dpp_mov_d<DPP_XOR1>(v);
-    v += dpp_mov_d<DPP_XOR2>(v);
-    v += dpp_mov_d<DPP_HALF_MIRROR>(v);
-    v += dpp_mov_d<DPP_MIRROR>(v);
-    return (lane_bcast_d(v, 0) + lane_bcast_d(v, 16)) + (lane_bcast_d(v, 32) + lane_bcast_d(v, 48));
-}
+// (the fp64 wave reductions dpp_mov_d / lane_bcast_d / wave_sum_d: common.hpp, shared with reliability.hip)
 
 // whether evaluation `eval` of the sequence has nothing left to do (evaluation 0 initialises the state: it reads no flag)
 __device__ __forceinline__ bool cal_settled(const int64_t* q, int eval) {

@@ -311,6 +311,57 @@ __device__ __forceinline__ float wave_max(float v) {
     v = row16_max(v);
     return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
 }
+// the same exchanges on doubles (calibration.hip, reliability.hip): two 32-bit moves per value
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov_d(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane_bcast_d(double v, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+// over the whole wave (all 64 lanes active), in one fixed order; every lane gets the result
+__device__ __forceinline__ double wave_sum_d(double v) {
+    v += dpp_mov_d<DPP_XOR1>(v);
+    v += dpp_mov_d<DPP_XOR2>(v);
+    v += dpp_mov_d<DPP_HALF_MIRROR>(v);
+    v += dpp_mov_d<DPP_MIRROR>(v);
+    return (lane_bcast_d(v, 0) + lane_bcast_d(v, 16)) + (lane_bcast_d(v, 32) + lane_bcast_d(v, 48));
+}
+
+// The arg-max of a row of float32 scores (score.hip, reliability.hip): larger value wins, equal values: lower index, a NaN beats
+// all (np.argmax) -- a total order on (value, index), so every lane of a pair computes the same winner.
+// whether (x, j) comes before (bv, bi) in that order
+__device__ __forceinline__ bool score_beats(float x, int j, float bv, int bi) {
+    const bool xn = x != x, bn = bv != bv;
+    if (xn || bn) return xn && (!bn || j < bi);
+    return x > bv || (x == bv && j < bi);
+}
+template <int CTRL>
+__device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+template <int CTRL>
+__device__ __forceinline__ void score_best_step(float& bv, int& bi) {
+    const float ov = dpp_mov<CTRL>(bv);
+    const int oi = dpp_mov_i<CTRL>(bi);
+    if (score_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+}
+// over the whole wave (all 64 lanes active); every lane gets the result
+__device__ __forceinline__ void wave_best(float& bv, int& bi) {
+    score_best_step<DPP_XOR1>(bv, bi);
+    score_best_step<DPP_XOR2>(bv, bi);
+    score_best_step<DPP_HALF_MIRROR>(bv, bi);
+    score_best_step<DPP_MIRROR>(bv, bi);
+    float rv = lane_bcast(bv, 0);
+    int ri = __builtin_amdgcn_readlane(bi, 0);
+#pragma unroll
+    for (int l = 16; l < 64; l += 16) {
+        const float ov = lane_bcast(bv, l);
+        const int oi = __builtin_amdgcn_readlane(bi, l);
+        if (score_beats(ov, oi, rv, ri)) { rv = ov; ri = oi; }
+    }
+    bv = rv; bi = ri;
+}
 
 }  // namespace slnlp
 

@@ -31,38 +31,7 @@ namespace slnlp {
 
 constexpr int SCORE_MAX_BLOCKS = 2048;  // x 4 rows: epochs past 8192 rows wrap the stride loop
 
-// whether (x, j) comes before (bv, bi) in the arg-max order
-__device__ __forceinline__ bool score_beats(float x, int j, float bv, int bi) {
-    const bool xn = x != x, bn = bv != bv;
-    if (xn || bn) return xn && (!bn || j < bi);
-    return x > bv || (x == bv && j < bi);
-}
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-
-template <int CTRL>
-__device__ __forceinline__ void score_best_step(float& bv, int& bi) {
-    const float ov = dpp_mov<CTRL>(bv);
-    const int oi = dpp_mov_i<CTRL>(bi);
-    if (score_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-}
-// over the whole wave (all 64 lanes active); every lane gets the result
-__device__ __forceinline__ void wave_best(float& bv, int& bi) {
-    score_best_step<DPP_XOR1>(bv, bi);
-    score_best_step<DPP_XOR2>(bv, bi);
-    score_best_step<DPP_HALF_MIRROR>(bv, bi);
-    score_best_step<DPP_MIRROR>(bv, bi);
-    float rv = lane_bcast(bv, 0);
-    int ri = __builtin_amdgcn_readlane(bi, 0);
-#pragma unroll
-    for (int l = 16; l < 64; l += 16) {
-        const float ov = lane_bcast(bv, l);
-        const int oi = __builtin_amdgcn_readlane(bi, l);
-        if (score_beats(ov, oi, rv, ri)) { rv = ov; ri = oi; }
-    }
-    bv = rv; bi = ri;
-}
+// (the arg-max order score_beats and its wave reduction wave_best: common.hpp, shared with reliability.hip)
 __device__ __forceinline__ int wave_sum_i(int v) {
     v += dpp_mov_i<DPP_XOR1>(v);
     v += dpp_mov_i<DPP_XOR2>(v);

@@ -127,6 +127,7 @@ SIGNATURES = {
     "slnlp_fit_temperature_scratch_bytes": (i64, [i64]),
     "slnlp_fit_temperature": (i32, [vp, i64, vp, i64, i64, vp, vp, i64, vp]),
     "slnlp_scale_logp": (i32, [vp, i64, i64, i64, vp, vp, i64, vp]),
+    "slnlp_reliability_rows": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -262,6 +263,7 @@ REDUCTIONS = {"mean": 0, "sum": 1}             # CrossEntropyLoss reductions the
 UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
 CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_*
+REL_MAX_BINS = 64                               # SLNLP_REL_MAX_BINS
 
 
 def ptr(t):

@@ -12,12 +12,23 @@ formed on the host with the arithmetic sklearn uses, so the numbers are the ones
 * ``REDUCED``: macro precision / recall / F1, balanced accuracy and ``top_k_accuracy`` (k = 2, sklearn's default), plus
   ``top<k>_accuracy`` for any integer 1 <= k < V (``top5_accuracy``).
 
-Log-probs on the CPU are reduced by a numpy expression instead (``reduce_rows``); a scorer name outside the two families
-goes through sklearn as before.
+* ``CALIBRATION``: ``neg_ece`` (expected calibration error over 15 equal-width bins of the top-class probability; ``neg_ece<B>``
+  for 1 <= B <= 64 bins), ``neg_mce`` (the largest bin's gap, 15 bins) and ``neg_brier`` (the multiclass Brier score
+  sum_c (p_c - 1[c = y])^2, mean over the samples) -- from ``slnlp_reliability_rows`` (csrc/reliability.hip), one call per
+  distinct bin count and only when such a name is asked for.  The bins are (b / B, (b + 1) / B], closed on the right (Guo et
+  al. 2017).  sklearn has no scorer of these names (its ``neg_brier_score`` is binary only).
+
+Log-probs on the CPU are reduced by a numpy expression instead (``reduce_rows``, ``reliability_numpy``); a scorer name outside
+the three families goes through sklearn as before.
 
 One documented difference: the rank is taken among the float32 LOG-PROBS.  An sklearn scorer fed ``exp(logp)`` can see
 extra ties where two different log-probs round to the same probability, and then orders those classes by index; the
 top-k numbers here are sklearn's on the log-probs themselves (which is what the tests compare with).
+
+Another, of the same kind: the history's ``CALIBRATION`` numbers are taken on the float32 LOG-PROBS, in fp64 (softmax of the row,
+maximum subtracted).  A ``ScoringWrapper`` of the same name is fed ``predict_proba``'s float32 PROBABILITIES, which it
+renormalises per row in fp64: the two agree to about float32 rounding of a probability (1e-7), not bit for bit, and a
+sample whose confidence sits within that distance of a bin edge may change bins.
 """
 import re
 
@@ -26,7 +37,10 @@ import torch
 
 FAST = ("accuracy", "precision_weighted", "recall_weighted", "f1_weighted", "neg_log_loss")
 REDUCED = ("precision_macro", "recall_macro", "f1_macro", "balanced_accuracy", "top_k_accuracy")
+CALIBRATION = ("neg_ece", "neg_mce", "neg_brier")
+DEFAULT_BINS, MAX_BINS = 15, 64                             # MAX_BINS: SLNLP_REL_MAX_BINS
 _TOP_K = re.compile(r"top([1-9][0-9]*)_accuracy\Z")
+_ECE_B = re.compile(r"neg_ece([0-9]+)\Z")
 
 
 def top_k_of(name):
@@ -37,9 +51,29 @@ def top_k_of(name):
     return int(m.group(1)) if m else None
 
 
+def calibration_metric_of(name):
+    """(kind, bins) of a ``CALIBRATION`` name -- ("ece", 15), ("ece", B) for ``neg_ece<B>``, ("mce", 15), ("brier", None) -- and
+    None for any other name.  ``neg_ece<B>`` with B outside 1..64 raises ValueError."""
+    if name == "neg_ece":
+        return "ece", DEFAULT_BINS
+    if name == "neg_mce":
+        return "mce", DEFAULT_BINS
+    if name == "neg_brier":
+        return "brier", None
+    m = _ECE_B.match(name) if isinstance(name, str) else None
+    if not m:
+        return None
+    bins = int(m.group(1))
+    if not 1 <= bins <= MAX_BINS or m.group(1) != str(bins):
+        raise ValueError(f"{name}: the number of bins must be an integer in 1..{MAX_BINS}, written without leading zeros")
+    return "ece", bins
+
+
 def is_reduced(name):
-    """Whether ``name`` is scored from the device-side reduction: ``FAST``, ``REDUCED`` or a ``top<k>_accuracy``."""
-    return name in FAST or name in REDUCED or top_k_of(name) is not None
+    """Whether ``name`` is scored from the device-side reductions: ``FAST``, ``REDUCED``, a ``top<k>_accuracy`` or ``CALIBRATION``
+    (``neg_ece<B>`` included).  Not a pure predicate: a ``neg_ece<B>`` whose B lies outside 1..64 raises ValueError
+    (``calibration_metric_of``), so that a misspelt bin count fails with its own message wherever the name is first looked at."""
+    return name in FAST or name in REDUCED or top_k_of(name) is not None or calibration_metric_of(name) is not None
 
 
 def reduce_epoch(logp, y):
@@ -159,15 +193,139 @@ def scores_from_rows(names, y_true, pred, picked, rank, counts, n_classes):
     return _scores(names, y_true, pred, picked, n_classes, lambda: _prf_counts(counts, n_classes), rank=rank)
 
 
-def epoch_scores(names, logp, y, y_host=None, split=None, out=None):
+def reliability_from_table(table):
+    """The table of ``slnlp_reliability_rows`` (include/slnlp.h), float64 [B + 1, 4] on the host, as a dict.  With M = the sum
+    of the counts: ``ece`` = sum_b |sum_correct_b - sum_conf_b| / M, ``mce`` = the largest |accuracy_b - confidence_b| over the
+    non-empty bins, ``brier`` / ``nll`` / ``accuracy`` / ``confidence`` = means over the M scored rows; ``rows`` = M;
+    ``bins``: {count int64 [B], confidence [B], accuracy [B]} (NaN in an empty bin).  A row that holds a NaN (``nan_rows``) makes
+    ece, mce, brier and nll NaN, as it does ``neg_log_loss``; so does M = 0."""
+    table = np.asarray(table, dtype=np.float64)
+    B = table.shape[0] - 1
+    count, sum_conf, sum_correct = table[:B, 0], table[:B, 1], table[:B, 2]
+    M, bad, nans = float(count.sum()), int(table[B, 2]), int(table[B, 3])
+    filled = count > 0
+    safe = np.where(filled, count, 1.0)
+    conf_b = np.where(filled, sum_conf / safe, np.nan)
+    acc_b = np.where(filled, sum_correct / safe, np.nan)
+    nan = float("nan")
+    out = {"ece": nan, "mce": nan, "brier": nan, "nll": nan, "accuracy": nan, "confidence": nan, "rows": int(M), "bad_labels": bad,
+           "nan_rows": nans, "bins": {"count": count.astype(np.int64), "confidence": conf_b, "accuracy": acc_b}}
+    if M > 0:
+        out["accuracy"], out["confidence"] = float(sum_correct.sum() / M), float(sum_conf.sum() / M)
+    if M > 0 and nans == 0:
+        out["ece"] = float(np.abs(sum_correct - sum_conf).sum() / M)
+        out["mce"] = float(np.abs(acc_b[filled] - conf_b[filled]).max())
+        out["brier"], out["nll"] = float(table[B, 0] / M), float(table[B, 1] / M)
+    return out
+
+
+def reliability_numpy(proba, y, bins=DEFAULT_BINS):
+    """(rows float64 [N, 4], table float64 [bins + 1, 4]) as ``slnlp_reliability_rows`` defines them, from PROBABILITIES
+    ``proba`` [N, V] on the host: every row is renormalised in fp64 (p = proba_i / sum proba_i), then conf = p at the first
+    maximum, brier = sum_c (p_c - 1[c = y])^2, nll = -log p_y, and the same bin rule and row codes."""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= MAX_BINS:
+        raise ValueError(f"reliability: bins={bins!r}, expected an integer in 1..{MAX_BINS}")
+    bins = int(bins)
+    p = np.asarray(proba).astype(np.float64)
+    yy = np.asarray(y).astype(np.int64)
+    N, V = p.shape
+    idx = np.arange(N)
+    rows = np.zeros((N, 4))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p = p / p.sum(axis=1, keepdims=True)
+        bad = (yy < 0) | (yy >= V)
+        broken = ~bad & ~np.isfinite(p).all(axis=1)
+        fine = ~bad & ~broken
+        pred = p.argmax(axis=1)
+        onehot = np.zeros((N, V))
+        onehot[idx[fine], yy[fine]] = 1.0
+        rows[:, 0] = p[idx, pred]
+        rows[:, 1] = ((p - onehot) ** 2).sum(axis=1)
+        rows[:, 2] = -np.log(p[idx, np.where(fine, yy, 0)])
+        rows[:, 3] = 2.0 * np.clip(np.ceil(rows[:, 0] * bins) - 1.0, 0.0, bins - 1.0) + (pred == yy)
+    rows[bad] = (0.0, 0.0, 0.0, -1.0)
+    rows[broken] = (np.nan, np.nan, np.nan, -2.0)
+    return rows, reliability_table_numpy(rows, bins)
+
+
+def reliability_table_numpy(rows, bins):
+    """The table of ``rows`` [N, 4] (numpy's summation order, not the device's)."""
+    code = rows[:, 3].astype(np.int64)
+    ok = code >= 0
+    b = code[ok] >> 1
+    table = np.zeros((bins + 1, 4))
+    table[:bins, 0] = np.bincount(b, minlength=bins)
+    table[:bins, 1] = np.bincount(b, weights=rows[ok, 0], minlength=bins)
+    table[:bins, 2] = np.bincount(b, weights=(code[ok] & 1).astype(np.float64), minlength=bins)
+    table[bins] = (rows[ok, 1].sum(), rows[ok, 2].sum(), float((code == -1).sum()), float((code == -2).sum()))
+    return table
+
+
+def reliability_summary(logp, y, bins, out=None):
+    """``reliability_from_table`` of one epoch's log-probs at beta = 1: on a GPU one ``ops.reliability_rows`` call (``out``: its
+    buffers) and one small download; on the CPU ``reliability_numpy`` of exp(log-prob), taken in fp64."""
+    if logp.is_cuda:
+        from . import ops
+        return ops.reliability_download(ops.reliability_rows(logp if logp.dtype == torch.float32 else logp.float(), y, bins=bins, out=out))
+    with np.errstate(over="ignore"):
+        proba = np.exp(logp.detach().float().numpy().astype(np.float64))
+    return reliability_from_table(reliability_numpy(proba, y.detach().numpy(), bins)[1])
+
+
+def calibration_score(name, summary):
+    """The score ``name`` (a ``CALIBRATION`` name: the NEGATED quantity, greater is better) from ``reliability_from_table``'s dict."""
+    return -summary[calibration_metric_of(name)[0]]
+
+
+def calibration_error(y_true, proba, *, kind, bins=None, labels=None):
+    """The POSITIVE quantity behind a ``CALIBRATION`` scorer (``ScoringWrapper`` negates it): ``kind`` "ece" | "mce" | "brier" of
+    the probabilities ``proba`` [N, V], whose column c stands for class ``labels[c]`` (None: class c).  With two classes
+    sklearn's ``predict_proba`` scorers hand over the second column alone, as a 1-D array: the two columns are rebuilt as
+    [1 - p, p], which is what ``log_loss`` does with such input."""
+    y_true = np.asarray(y_true)
+    proba = np.asarray(proba)
+    if proba.ndim == 1:
+        proba = np.stack([1.0 - proba.astype(np.float64), proba.astype(np.float64)], axis=1)
+    if labels is not None:
+        labels = np.asarray(labels)
+        if len(labels) != proba.shape[1]:
+            raise ValueError(f"neg_{kind}: {len(labels)} labels for {proba.shape[1]} probability columns")
+        order = np.argsort(labels, kind="stable")
+        pos = np.clip(np.searchsorted(labels[order], y_true), 0, len(labels) - 1)
+        y_true = np.where(labels[order][pos] == y_true, order[pos], -1)
+    summary = reliability_from_table(reliability_numpy(proba, y_true, bins or DEFAULT_BINS)[1])
+    if summary["bad_labels"] > 0:
+        raise ValueError(f"neg_{kind}: {summary['bad_labels']} of {len(y_true)} labels lie outside the {proba.shape[1]} classes of the "
+                         "probabilities")
+    return summary[kind]
+
+
+def epoch_scores(names, logp, y, y_host=None, split=None, out=None, rel_out=None):
     """{name: score} for the names among ``names`` that ``is_reduced``; ``logp`` / ``y`` are device tensors of one epoch.
-    ``split`` names the data in the error a label outside the columns raises; ``out``: ``reduce_rows``' device buffers."""
+    ``split`` names the data in the error a label outside the columns raises; ``out``: ``reduce_rows``' device buffers;
+    ``rel_out``: {bins: ``ops.reliability_rows``' device buffers}, one entry per bin count the ``CALIBRATION`` names ask for."""
     names = [n for n in names if is_reduced(n)]
     if not names:
         return {}
-    pred, picked, rank, counts = reduce_rows(logp, y, out=out)
-    if counts[-1] > 0:
-        raise ValueError(f"scoring the {split or 'epoch'} data: {int(counts[-1])} of {len(pred)} labels lie outside the "
-                         f"{int(logp.shape[1])} classes of the log-probs")
-    y_true = np.asarray(y_host if y_host is not None else y.cpu().numpy()).astype(np.int64)
-    return scores_from_rows(names, y_true, pred, picked, rank, counts, int(logp.shape[1]))
+    cal = [n for n in names if calibration_metric_of(n) is not None]
+    names = [n for n in names if n not in cal]
+
+    def bad_labels(count):
+        return ValueError(f"scoring the {split or 'epoch'} data: {int(count)} of {int(logp.shape[0])} labels lie outside the "
+                          f"{int(logp.shape[1])} classes of the log-probs")
+    scores = {}
+    if names:
+        pred, picked, rank, counts = reduce_rows(logp, y, out=out)
+        if counts[-1] > 0:
+            raise bad_labels(counts[-1])
+        y_true = np.asarray(y_host if y_host is not None else y.cpu().numpy()).astype(np.int64)
+        scores = scores_from_rows(names, y_true, pred, picked, rank, counts, int(logp.shape[1]))
+    summaries = {}
+    for name in cal:                                        # history rows are uncalibrated by construction: beta = 1
+        bins = calibration_metric_of(name)[1] or DEFAULT_BINS
+        if bins not in summaries:
+            summaries[bins] = reliability_summary(logp, y, bins, out=(rel_out or {}).get(bins))
+            if summaries[bins]["bad_labels"] > 0:
+                raise bad_labels(summaries[bins]["bad_labels"])
+        scores[name] = calibration_score(name, summaries[bins])
+    return scores

@@ -339,8 +339,11 @@ class ScoringWrapper:
     the full label set (a fold may miss classes), the precision / recall / F1 family gets ``zero_division=0``, accuracy
     takes nothing.  Beyond the reference's names: ``balanced_accuracy`` takes nothing either, and the top-k family --
     ``top_k_accuracy`` (sklearn's k = 2) and ``top<k>_accuracy`` for any k >= 1, a ``top_k_accuracy_score`` scorer with that
-    k -- is told the label set like log-loss.  Exposes ``score`` (the name) and ``greater_is_better`` -- what the reference's
-    EpochScoring and GridSearchCV wiring read (helper.py:255-268, 183-194)."""
+    k -- is told the label set like log-loss.  The calibration family (``metrics.CALIBRATION``: ``neg_ece``, ``neg_ece<B>``,
+    ``neg_mce``, ``neg_brier``), which sklearn does not have, is a ``make_scorer`` of ``metrics.calibration_error`` on
+    ``predict_proba`` with ``greater_is_better=False`` -- sign -1, like ``neg_log_loss`` -- and is told the label set too.
+    Exposes ``score`` (the name) and ``greater_is_better`` -- what the reference's EpochScoring and GridSearchCV wiring read
+    (helper.py:255-268, 183-194)."""
 
     _EXTRA = {"neg_log_loss": lambda labels: {"labels": labels}, "accuracy": lambda labels: {},
               "balanced_accuracy": lambda labels: {}, "top_k_accuracy": lambda labels: {"labels": labels}}
@@ -349,7 +352,11 @@ class ScoringWrapper:
         from sklearn.metrics import get_scorer, make_scorer, top_k_accuracy_score
         self.score = score_func
         k = metrics.top_k_of(score_func)
-        if k is not None and score_func != "top_k_accuracy":
+        cal = metrics.calibration_metric_of(score_func)
+        if cal is not None:
+            base = make_scorer(metrics.calibration_error, greater_is_better=False, response_method="predict_proba", kind=cal[0], bins=cal[1])
+            extra = {"labels": labels}
+        elif k is not None and score_func != "top_k_accuracy":
             # what sklearn's own "top_k_accuracy" scorer is, with the name's k
             base = make_scorer(top_k_accuracy_score, greater_is_better=True, response_method=("decision_function", "predict_proba"), k=k)
             extra = {"labels": labels}
@@ -364,7 +371,8 @@ class ScoringWrapper:
     @staticmethod
     def needs_labels(score_func):
         """Whether the scorer must be told the full label set: a test fold may miss classes the probability columns stand for."""
-        return score_func == "neg_log_loss" or metrics.top_k_of(score_func) is not None
+        return (score_func == "neg_log_loss" or metrics.top_k_of(score_func) is not None
+                or metrics.calibration_metric_of(score_func) is not None)
 
     def __call__(self, estimator, X, y_true, sample_weight=None):
         return self.scorer(estimator, X, y_true, sample_weight)
@@ -408,6 +416,7 @@ class _FitRun:
         # the fast metrics index the probability columns by class id: valid when the labels are exactly the columns
         self.fast_ok = labels is not None and list(labels) == list(range(len(net.classes_)))
         self._score_out = {}                                 # split -> the reduction's device buffers (ops.score_rows)
+        self._rel_out = {}                                   # split -> {bins: ops.reliability_rows' device buffers}
         es, clip, sched = net.early_stopping, net.gradient_clipping, net.lr_scheduler
         self.es = es
         self.max_norm = float(clip["gradient_clip_value"]) if clip and clip.get("gradient_clip_value") else 0.0
@@ -527,7 +536,12 @@ class _FitRun:
         """``metrics.epoch_scores`` into this fit's own device buffers for ``split`` (allocated once, not every epoch)."""
         if logp.is_cuda and split not in self._score_out:
             self._score_out[split] = ops.score_buffers(logp.shape[0], logp.shape[1], logp.device)
-        return metrics.epoch_scores(names, logp, y_dev, y_host, split=split, out=self._score_out.get(split))
+        if logp.is_cuda and split not in self._rel_out:
+            cal = [metrics.calibration_metric_of(n) for n in names]
+            self._rel_out[split] = {bins: ops.reliability_buffers(logp.shape[0], bins, logp.device)
+                                    for bins in sorted({c[1] or metrics.DEFAULT_BINS for c in cal if c is not None})}
+        return metrics.epoch_scores(names, logp, y_dev, y_host, split=split, out=self._score_out.get(split),
+                                    rel_out=self._rel_out.get(split))
 
     def end_epoch(self, tr, va):
         """tr / va: (sample-weighted mean loss, log-probs [n, V] on the device, [(batch loss, batch size)]) of the epoch's
@@ -1041,7 +1055,20 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         ``predict_nonlinearity='auto'`` applies softmax for CrossEntropyLoss."""
         if not self.initialized_:
             raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        ds = self._as_dataset(X)
+
+        def scaled(out, yd):
+            if getattr(self, "calibration_", None) is not None:
+                ops.scale_logp(out, self._cal_state, out=out)        # softmax(z / T) below: the calibrated log-probs, in place
+            return out
+        out = self._forward_logp(self._as_dataset(X), scaled).cpu()
+        # the nonlinearity on the host copy (torch's CPU softmax -- the op the reference's CPU path runs): torch's GPU kernels
+        # are built with packed fp32 and must not run beside other fits' kernels (STREAM_MODE above); [N, V] is tiny
+        return (torch.softmax(out, dim=-1) if self.predict_nonlinearity == "auto" else out).numpy()
+
+    def _forward_logp(self, ds, then):
+        """The module's float32 log-probs [len(ds), V] of ``ds`` on the device -- the forward passes of ``predict_proba``: under
+        the gate, on the fit's stream, the averaged weights swapped in where the fit predicts with them and back afterwards --
+        handed, still on that stream, to ``then(logp, y_dev)``; returns what ``then`` returns once the stream has drained."""
         self.module_.eval()
         outs = []
         self._gate.enter(not self._fused)
@@ -1058,19 +1085,42 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 finally:
                     if swapped:
                         self.module_.swap_averaged()     # ... and the live weights come back bit for bit
-                out = torch.cat(outs)
-                if getattr(self, "calibration_", None) is not None:
-                    ops.scale_logp(out, self._cal_state, out=out)    # softmax(z / T) below: the calibrated log-probs, in place
+                res = then(torch.cat(outs), yd)
             stream_sync(self._stream)
         finally:
             self._gate.leave(not self._fused)
-        out = out.cpu()
-        # the nonlinearity on the host copy (torch's CPU softmax -- the op the reference's CPU path runs): torch's GPU kernels
-        # are built with packed fp32 and must not run beside other fits' kernels (STREAM_MODE above); [N, V] is tiny
-        return (torch.softmax(out, dim=-1) if self.predict_nonlinearity == "auto" else out).numpy()
+        return res
 
     def predict(self, X):
         return self.classes_[self.predict_proba(X).argmax(-1)]
+
+    def reliability(self, X, y=None, bins=15, calibrated=True):
+        """Reliability diagnostics of this fit's predictions on ``X`` (``y``: the labels; None: the dataset's), all formed from one
+        ``ops.reliability_rows`` call on the device log-probs of ``predict_proba``'s forward passes: ``ops.reliability_download``'s
+        dict -- ece, mce (``bins`` equal-width right-closed bins of the top-class probability, 1..64), brier, nll, accuracy,
+        confidence, rows, bad_labels, nan_rows, bins {count, confidence, accuracy} -- plus ``temperature``: the T the
+        probabilities were taken at, softmax(z / T) -- ``temperature_`` for a calibrated fit unless ``calibrated=False``, else 1.0
+        (the device then reads no state)."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= metrics.MAX_BINS:
+            raise ValueError(f"reliability: bins={bins!r}, expected an integer in 1..{metrics.MAX_BINS}")
+        ds = self._as_dataset(X)
+        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
+        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
+        if labels is not None and labels.shape != (len(ds),):
+            raise ValueError(f"reliability: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
+
+        def rows(logp, yd):
+            yd = yd if labels is None else labels.to(logp.device)
+            return ops.reliability_rows(logp if logp.dtype == torch.float32 else logp.float(), yd.contiguous(), bins=int(bins),
+                                        state=self._cal_state if use else None)
+        res = ops.reliability_download(self._forward_logp(ds, rows))
+        if res["bad_labels"] > 0:
+            raise ValueError(f"reliability: {res['bad_labels']} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the "
+                             "log-probs")
+        res["temperature"] = float(self.temperature_) if use else 1.0
+        return res
 
     def score(self, X, y=None):
         ds = self._as_dataset(X)

@@ -2,6 +2,7 @@
 parity tests and by the RNN host code).  Every function launches on torch's
 current stream and fails loudly without a GPU / without the built library."""
 import ctypes as C
+import numbers
 
 import torch
 
@@ -514,6 +515,48 @@ def scale_logp(logp, state, out=None):
         _, _, ld_out = _logp_matrix("scale_logp (out)", out)
         check(load().slnlp_scale_logp(ptr(logp), ld, N, V, ptr(state), ptr(out), ld_out, stream_ptr()), "scale_logp")
     return out
+
+
+def reliability_buffers(N, bins, device):
+    """The two output tensors of ``reliability_rows`` for N rows and ``bins`` bins -- rows float64 [N, 4], table float64
+    [bins + 1, 4] -- as slices of ONE allocation, so ``reliability_download`` is one copy."""
+    flat = torch.empty(4 * (N + bins + 1), dtype=torch.float64, device=device)
+    return flat[:4 * N].view(N, 4), flat[4 * N:].view(bins + 1, 4)
+
+
+def reliability_rows(logp, y, bins=15, state=None, out=None):
+    """The reliability terms of ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) against the labels ``y`` int64 [N]
+    (``slnlp_reliability_rows``, include/slnlp.h): ``(rows float64 [N, 4], table float64 [bins + 1, 4])``, device tensors that are
+    slices of one allocation.  ``state``: a calibration state (``fit_temperature`` / ``temperature_state``) whose beta is read on
+    the device, so the terms are those of softmax(beta logp); None: beta = 1.  ``out``: such a pair to fill.  Runs on the current
+    stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("reliability_rows", logp)
+    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"reliability_rows: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    if isinstance(bins, bool) or not isinstance(bins, numbers.Integral) or not 1 <= bins <= _lib.REL_MAX_BINS:
+        raise ValueError(f"reliability_rows: bins={bins!r}, expected an integer in 1..{_lib.REL_MAX_BINS}")
+    bins = int(bins)
+    if state is not None:
+        _cal_state("reliability_rows", state, logp.device)
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = reliability_buffers(N, bins, logp.device)
+        rows, table = out
+        for t, shape in ((rows, (N, 4)), (table, (bins + 1, 4))):
+            if not (t.device == logp.device and t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"reliability_rows: out must be (float64 [{N}, 4], float64 [{bins + 1}, 4]) on {logp.device}")
+        check(load().slnlp_reliability_rows(ptr(logp), ld, ptr(y), N, V, bins, ptr(state) if state is not None else None, ptr(rows),
+                                            ptr(table), stream_ptr()), "reliability_rows")
+    return out
+
+
+def reliability_download(out):
+    """``reliability_rows``' result as a dict (``metrics.reliability_from_table`` forms it on the host, in fp64, from the table):
+    {ece, mce, brier, nll, accuracy, confidence, rows, bad_labels, nan_rows, bins: {count, confidence, accuracy}}.  ONE
+    device-to-host copy, of the table (it waits for the two launches); the per-row terms stay on the device."""
+    from . import metrics
+    return metrics.reliability_from_table(out[1].cpu().numpy())
 
 
 class ParamGroupTable:
