@@ -410,6 +410,46 @@ int slnlp_scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const 
 int slnlp_reliability_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int bins, const double* beta_dev,
                            double* rows, double* table, void* stream);
 
+/* ----------------------------------------------------------------- error analysis --
+ * Which classes are wrong and what they were mistaken for: the top-k classes of every row, the confusion matrix and its
+ * most-confused pairs (slnlp/ops.py and slnlp/metrics.py form the report on the host; NeuralNetClassifier.error_analysis).
+ *
+ * slnlp_topk_rows: logp float32 [N, ld], V <= ld columns used; k in 1..min(V, SLNLP_TOPK_MAX); beta as for
+ * slnlp_reliability_rows (beta_dev may be null: beta = 1).  idx int32 [N, k]: per row the first k columns in the total order of
+ * slnlp_score_rows' arg-max on the float32 values -- a NaN comes before everything (several NaNs by ascending index), then
+ * larger values first, equal values by ascending index; -inf is an ordinary value.  Column 0 is therefore slnlp_score_rows'
+ * pred and np.argmax.  NOT sklearn's top-k tie order (top_k_accuracy_score puts the HIGHER index first among equal scores;
+ * rank[] of slnlp_score_rows follows sklearn, this list follows the arg-max).  prob float64 [N, k]: prob[i, j] =
+ * exp(beta z_c - a) / s0 for c = idx[i, j], with slnlp_reliability_rows' fp64 decomposition (zmax the float32 row maximum,
+ * a = beta zmax, columns at the maximum counted and not exponentiated, s0 = 1 + rest): prob[i, 0] is that call's conf bit for
+ * bit.  A row that holds a NaN or whose maximum is not finite gets NaN probabilities; its indices still follow the order.
+ * One launch (a wave per row, k - 1 selection rounds over the row, no LDS, no atomics); the result is a function of the
+ * arguments alone.  Errors: a null pointer (but beta_dev), N or V outside 1..INT32_MAX, k out of range, ld < V, a misaligned
+ * pointer (idx 4, prob and beta_dev 8 bytes), an output overlapping an input or the other output.
+ *
+ * slnlp_confusion_matrix: pred int32 [N] (what slnlp_score_rows wrote), y int64 [N], V in 1..SLNLP_CONFUSION_MAX_V; counts
+ * int32 [V V + 1] is zeroed by the call, on the stream, then counts[y_i V + pred_i] += 1 for every row whose label and
+ * prediction both lie in [0, V) -- rows true, columns predicted -- and counts[V V] += 1 for every other row (a value outside
+ * [0, V) is never used as an index).  Integer atomics: the result does not depend on scheduling.  Two launches.
+ *
+ * slnlp_confusion_pairs: counts int32 [V V] as above (the tail entry is not read); pairs int32 [M, 3], M in
+ * 1..SLNLP_PAIRS_MAX: the M largest off-diagonal cells with a count above 0, ordered by count descending, then true class
+ * ascending, then predicted class ascending (the last two: the flat index ascending); row m = (true, predicted, count), unused
+ * rows = (-1, -1, 0).  work: slnlp_confusion_pairs_workspace_bytes(V, M) bytes of device memory (-1 and a message for V or M out
+ * of range), 8-byte aligned, written by the call (no need to clear it; more than needed changes nothing).  Two launches: blocks
+ * select the first M cells of a contiguous slice each, one block merges their lists; the order is total, so the result is the
+ * same however the cells are sliced.
+ *
+ * All three return SLNLP_ERR_INVALID_ARG with a message before anything is launched. */
+#define SLNLP_TOPK_MAX 64
+#define SLNLP_CONFUSION_MAX_V 4096
+#define SLNLP_PAIRS_MAX 64
+int slnlp_topk_rows(const float* logp, int64_t ld, int64_t N, int64_t V, int k, const double* beta_dev, int32_t* idx, double* prob,
+                    void* stream);
+int slnlp_confusion_matrix(const int32_t* pred, const int64_t* y, int64_t N, int64_t V, int32_t* counts, void* stream);
+int64_t slnlp_confusion_pairs_workspace_bytes(int64_t V, int M);
+int slnlp_confusion_pairs(const int32_t* counts, int64_t V, int M, int32_t* pairs, void* work, int64_t work_bytes, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

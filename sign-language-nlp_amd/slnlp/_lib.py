@@ -128,6 +128,10 @@ SIGNATURES = {
     "slnlp_fit_temperature": (i32, [vp, i64, vp, i64, i64, vp, vp, i64, vp]),
     "slnlp_scale_logp": (i32, [vp, i64, i64, i64, vp, vp, i64, vp]),
     "slnlp_reliability_rows": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp]),
+    "slnlp_topk_rows": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp]),
+    "slnlp_confusion_matrix": (i32, [vp, vp, i64, i64, vp, vp]),
+    "slnlp_confusion_pairs_workspace_bytes": (i64, [i64, i32]),
+    "slnlp_confusion_pairs": (i32, [vp, i64, i32, vp, vp, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -264,6 +268,9 @@ UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
 CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_*
 REL_MAX_BINS = 64                               # SLNLP_REL_MAX_BINS
+TOPK_MAX = 64                                   # SLNLP_TOPK_MAX
+CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
+PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 
 
 def ptr(t):

@@ -20,9 +20,18 @@ the corpus is not on the machine.  ``iterator_train_args: {shuffle: true, drop_l
 iterator arguments, helper.py:73-83, with ``shuffle`` commented out) becomes ``iterator_train__*``; in ``grid_args`` it is a grid
 axis.  Configs without the key behave as before.  A top-level ``calibration: {method: temperature}`` goes to the estimator as it is
 (temperature calibration on the fit's valid split, slnlp/net.py); a list of such settings under ``grid_args`` is a grid axis.
+A top-level ``error_analysis: {pairs: 20, top_k: 5}`` (both optional, these defaults) makes rank 0 write, next to test_output.json,
+what ``NeuralNetClassifier.error_analysis`` finds on the test split:
+
+    test_class_report.csv          precision / recall / f1 / support / predicted per class, then the macro row
+    test_confused_pairs.csv        the most-confused (true, predicted) pairs, largest count first
+    test_topk.csv                  per test sample its label and the top_k classes with their probabilities
+
+Without the key the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
+import csv
 import datetime
 import itertools
 import json
@@ -31,7 +40,7 @@ import os
 import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
-             "criterion_args", "iterator_train_args", "grid_args", "calibration")
+             "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -164,6 +173,58 @@ def save_cv_results(cv_results, phase, workdir):
         os.path.join(workdir, f"{phase}_results.csv"))
 
 
+ERROR_ANALYSIS_DEFAULTS = {"pairs": 20, "top_k": 5}
+ERROR_ANALYSIS_MAX = {"pairs": 64, "top_k": 64}                                 # SLNLP_PAIRS_MAX, SLNLP_TOPK_MAX
+
+
+def error_analysis_options(setting):
+    """The ``error_analysis`` key with its defaults filled in -- {pairs 20, top_k 5} -- or None when the key is absent.  Anything
+    but a dict over these two keys ({}: all defaults) with integer values in 1..64 raises ValueError (``top_k`` above the number of
+    classes is cut to it when the files are written)."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"error_analysis={setting!r}: expected a dict with keys among {tuple(ERROR_ANALYSIS_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(ERROR_ANALYSIS_DEFAULTS))
+    if unknown:
+        raise ValueError(f"error_analysis: unknown keys {unknown} (known: {tuple(ERROR_ANALYSIS_DEFAULTS)})")
+    opts = dict(ERROR_ANALYSIS_DEFAULTS, **setting)
+    for k, v in opts.items():
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= ERROR_ANALYSIS_MAX[k]:
+            raise ValueError(f"error_analysis: {k}={v!r}, expected an integer in 1..{ERROR_ANALYSIS_MAX[k]}")
+    return opts
+
+
+def save_error_analysis(est, test_data, opts, workdir):
+    """``est.error_analysis(test_data, **opts)`` as three CSV files in ``workdir`` (floats written with ``repr``: they read back
+    bit for bit).  A class is written as its id and, where the dataset has a label vocabulary, its name.  Returns the result."""
+    names = test_data.vocab_y.itos if getattr(test_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    res = est.error_analysis(test_data, pairs=opts["pairs"], top_k=min(opts["top_k"], len(est.classes_)), matrix=False)
+    rep = res["report"]
+    with open(os.path.join(workdir, "test_class_report.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["class", "name", "precision", "recall", "f1", "support", "predicted"])
+        for i, c in enumerate(res["classes"]):
+            w.writerow([int(c), name(c), *(repr(float(rep[k][i])) for k in ("precision", "recall", "f1")), int(rep["support"][i]),
+                        int(rep["predicted"][i])])
+        w.writerow(["macro", "", *(repr(res["macro"][k]) for k in ("precision", "recall", "f1")), int(rep["support"].sum()),
+                    int(rep["predicted"].sum())])
+    with open(os.path.join(workdir, "test_confused_pairs.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["true", "true_name", "predicted", "predicted_name", "count"])
+        for t, p, c in res["pairs"]:
+            w.writerow([int(t), name(t), int(p), name(p), int(c)])
+    labels, proba = res["topk"]
+    k = labels.shape[1]
+    with open(os.path.join(workdir, "test_topk.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["row", "true", *(f"top{j + 1}" for j in range(k)), *(f"p{j + 1}" for j in range(k))])
+        for i in range(len(labels)):
+            w.writerow([i, int(test_data.y[i]), *(int(c) for c in labels[i]), *(repr(float(p)) for p in proba[i])])
+    return res
+
+
 def run(args):
     """main.run + tune_hyperparams + test_model.  Returns (grid search object, test metrics); rank 0 writes files."""
     import random
@@ -190,6 +251,7 @@ def run(args):
             # the default 10-minute watchdog would abort ranks that wait for a slower one
             dist.init_process_group("nccl", device_id=torch.device(device), timeout=datetime.timedelta(hours=48))
     workdir = args.get("workdir") or "."
+    analysis = error_analysis_options(args.get("error_analysis"))               # a bad key fails before the grid search, not after
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -227,6 +289,8 @@ def run(args):
         est = gs.best_estimator_
         test_output = {f"test_{m}": float(ScoringWrapper(m, test_data.labels())(est, test_data, test_data.y)) for m in metrics}
         save_json(test_output, os.path.join(workdir, "test_output.json"))
+        if analysis is not None:
+            save_error_analysis(est, test_data, analysis, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

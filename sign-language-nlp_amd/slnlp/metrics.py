@@ -193,6 +193,23 @@ def scores_from_rows(names, y_true, pred, picked, rank, counts, n_classes):
     return _scores(names, y_true, pred, picked, n_classes, lambda: _prf_counts(counts, n_classes), rank=rank)
 
 
+def class_report(true_sum, pred_sum, tp_sum):
+    """The per-class table of an error analysis from the integer class counts ``slnlp_score_rows`` produces (a confusion
+    matrix's row sums, column sums and diagonal), in fp64: ``(report, macro)``.  ``report``: {precision, recall, f1 float64 [V],
+    support int64 [V] (rows with that label), predicted int64 [V] (rows with that prediction)} -- sklearn's
+    ``precision_recall_fscore_support(labels=all V classes, average=None, zero_division=0)``, the keyword the reference's
+    ``ScoringWrapper`` passes: a class that is never predicted has precision 0, one that never occurs recall 0.  ``macro``:
+    {precision, recall, f1}: the plain means over ALL V classes (``average="macro"`` with the same labels)."""
+    ts, ps, tp = (np.asarray(a) for a in (true_sum, pred_sum, tp_sum))
+    if not (ts.ndim == 1 and ts.size >= 1 and ts.shape == ps.shape == tp.shape and all(a.dtype.kind in "iu" for a in (ts, ps, tp))):
+        raise ValueError(f"class_report: expected three integer arrays of one length, got shapes {ts.shape}, {ps.shape}, {tp.shape}")
+    ts, ps, tp = ts.astype(np.int64), ps.astype(np.int64), tp.astype(np.int64)
+    report = {kind: _per_class(kind, tp, ps, ts) for kind in ("precision", "recall", "f1")}
+    macro = {kind: float(np.average(v)) for kind, v in report.items()}
+    report.update(support=ts, predicted=ps)
+    return report, macro
+
+
 def reliability_from_table(table):
     """The table of ``slnlp_reliability_rows`` (include/slnlp.h), float64 [B + 1, 4] on the host, as a dict.  With M = the sum
     of the counts: ``ece`` = sum_b |sum_correct_b - sum_conf_b| / M, ``mce`` = the largest |accuracy_b - confidence_b| over the

@@ -28,6 +28,9 @@ semantics:
 * ``calibration={"method": "temperature"}``: at the end of a fit one temperature is fitted on the valid split's log-probs, on
   the device (csrc/calibration.hip), and ``predict_proba`` returns ``softmax(z / T)``; ``predict`` and the history never change.
 
+Beyond skorch: ``reliability`` (ECE / MCE / Brier, csrc/reliability.hip), ``predict_topk`` and ``error_analysis`` (top-k classes,
+confusion matrix, most-confused pairs, per-class report: csrc/confusion.hip) reduce a fitted estimator's log-probs on the device.
+
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
 import threading
@@ -1121,6 +1124,68 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                              "log-probs")
         res["temperature"] = float(self.temperature_) if use else 1.0
         return res
+
+    @staticmethod
+    def _int_option(what, name, value, lo, hi):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+            raise ValueError(f"{what}: {name}={value!r}, expected an integer in {lo}..{hi}")
+        return int(value)
+
+    def predict_topk(self, X, k=5, calibrated=True):
+        """The ``k`` most probable classes of every sample of ``X`` and their probabilities: ``(labels [N, k] from classes_, proba
+        float64 [N, k])``, most probable first, from one ``ops.topk_rows`` call on the device log-probs of ``predict_proba``'s
+        forward passes (k in 1..min(classes, 64)).  The order is the arg-max's -- equal log-probs by ascending class -- so
+        ``labels[:, 0]`` is ``predict(X)``; the probabilities are softmax(z / T) in fp64, ``temperature_`` for a calibrated fit
+        unless ``calibrated=False``, else T = 1."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        k = self._int_option("predict_topk", "k", k, 1, min(len(self.classes_), ops._lib.TOPK_MAX))
+        ds = self._as_dataset(X)
+        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
+
+        def rows(logp, yd):
+            return ops.topk_rows(logp if logp.dtype == torch.float32 else logp.float(), k, state=self._cal_state if use else None)
+        idx, prob = ops.topk_download(self._forward_logp(ds, rows))
+        return self.classes_[idx], prob
+
+    def error_analysis(self, X, y=None, pairs=20, top_k=None, matrix=True, calibrated=True):
+        """Which classes this fit gets wrong on ``X`` (``y``: the labels; None: the dataset's) and what it takes them for, formed
+        on the device from the log-probs of ``predict_proba``'s forward passes (``ops.error_analysis_rows``: the arg-max and class
+        counts, the confusion matrix, its most-confused pairs, the top-k lists) and downloaded in one copy.  A dict:
+        ``classes`` (``classes_``); ``confusion`` int64 [V, V], rows true and columns predicted -- None with ``matrix=False``,
+        and then the V x V counts never leave the device; ``report`` {precision, recall, f1, support, predicted} per class and
+        ``macro`` {precision, recall, f1} (``metrics.class_report``: zero_division = 0, means over all V classes); ``accuracy``;
+        ``pairs``: up to ``pairs`` (1..64) tuples (true label, predicted label, count) over the off-diagonal cells, largest
+        count first, ties by true then predicted class; ``topk``: ``predict_topk(X, top_k, calibrated)``'s pair from the same
+        forward passes, None without ``top_k``; ``rows``: the number of samples."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        V = len(self.classes_)
+        M = self._int_option("error_analysis", "pairs", pairs, 1, ops._lib.PAIRS_MAX)
+        k = 0 if top_k is None else self._int_option("error_analysis", "top_k", top_k, 1, min(V, ops._lib.TOPK_MAX))
+        if V > ops._lib.CONFUSION_MAX_V:
+            raise ValueError(f"error_analysis: {V} classes, the confusion matrix is formed for at most {ops._lib.CONFUSION_MAX_V}")
+        ds = self._as_dataset(X)
+        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
+        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
+        if labels is not None and labels.shape != (len(ds),):
+            raise ValueError(f"error_analysis: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
+
+        def rows(logp, yd):
+            yd = yd if labels is None else labels.to(logp.device)
+            buf = ops.error_analysis_buffers(logp.shape[0], logp.shape[1], k, M, logp.device)
+            return ops.error_analysis_rows(logp if logp.dtype == torch.float32 else logp.float(), yd.contiguous(), buf,
+                                           state=self._cal_state if use else None)
+        got = ops.error_analysis_download(self._forward_logp(ds, rows), matrix=bool(matrix), topk=k > 0)
+        counts = got["counts"]
+        V = (counts.size - 1) // 3                           # the columns of the log-probs
+        if counts[3 * V] > 0:
+            raise ValueError(f"error_analysis: {int(counts[3 * V])} of {len(ds)} labels lie outside the {V} classes of the log-probs")
+        report, macro = metrics.class_report(counts[:V], counts[V:2 * V], counts[2 * V:3 * V])
+        return {"classes": self.classes_, "confusion": got["confusion"], "report": report, "macro": macro,
+                "accuracy": float(counts[2 * V:3 * V].sum() / len(ds)),
+                "pairs": [(self.classes_[t], self.classes_[p], int(c)) for t, p, c in got["pairs"] if c > 0],
+                "topk": (self.classes_[got["topk_idx"]], got["topk_prob"]) if k else None, "rows": len(ds)}
 
     def score(self, X, y=None):
         ds = self._as_dataset(X)

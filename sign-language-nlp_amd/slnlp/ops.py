@@ -559,6 +559,175 @@ def reliability_download(out):
     return metrics.reliability_from_table(out[1].cpu().numpy())
 
 
+def _int_in(what, name, value, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
+        raise ValueError(f"{what}: {name}={value!r}, expected an integer in {lo}..{hi}")
+    return int(value)
+
+
+def error_analysis_buffers(N, V, k, M, device):
+    """Every device buffer of one error analysis of an [N, V] set of log-probs -- ``k`` top classes per row (0: none), ``M``
+    most-confused pairs -- as slices of ONE int32 allocation, laid out so that whatever is asked for afterwards is one contiguous
+    piece of it (``error_analysis_download``):
+
+        confusion [V V + 1] | pairs [M, 3] | counts [3 V + 1] | topk_idx [N, k] | topk_prob float64 [N, k] |
+        pred [N] | picked float32 [N] | rank [N] | work
+
+    (one pad entry in front of topk_idx, topk_prob or work where that keeps them 8-byte aligned).  ``score`` = (pred, picked, rank,
+    counts) is ``score_rows``' ``out``, ``topk`` = (topk_idx, topk_prob) ``topk_rows``'; the pieces after topk_prob never leave
+    the device."""
+    what = "error_analysis_buffers"
+    N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
+    k, M = _int_in(what, "k", k or 0, 0, min(V, _lib.TOPK_MAX)), _int_in(what, "M", M, 1, _lib.PAIRS_MAX)
+    work_bytes = load().slnlp_confusion_pairs_workspace_bytes(V, M)
+    at, off = {}, 0
+    for name, n, align8 in (("confusion", V * V + 1, False), ("pairs", 3 * M, False), ("counts", 3 * V + 1, False),
+                            ("topk_idx", N * k, True), ("topk_prob", 2 * N * k, True), ("pred", N, False), ("picked", N, False),
+                            ("rank", N, False), ("work", work_bytes // 4, True)):
+        if align8:                                           # an even int32 offset: 8-byte aligned (one pad entry where needed)
+            off += off & 1
+        at[name] = (off, n)
+        off += n
+    flat = torch.empty(off, dtype=torch.int32, device=device)
+    buf = {name: flat[begin:begin + n] for name, (begin, n) in at.items()}
+    buf["pairs"] = buf["pairs"].view(M, 3)
+    buf["picked"] = buf["picked"].view(torch.float32)
+    buf["topk_idx"] = buf["topk_idx"].view(N, k) if k else None
+    buf["topk_prob"] = buf["topk_prob"].view(torch.float64).view(N, k) if k else None
+    buf["work"] = buf["work"].view(torch.uint8)
+    buf.update(flat=flat, at=at, score=(buf["pred"], buf["picked"], buf["rank"], buf["counts"]),
+               topk=(buf["topk_idx"], buf["topk_prob"]) if k else None, shape=(N, V, k, M))
+    return buf
+
+
+def error_analysis_download(buf, matrix=True, topk=False):
+    """What an error analysis hands to the host, in ONE device-to-host copy of only the pieces asked for: the pairs and the class
+    counts always, the V x V matrix with ``matrix``, the top-k lists with ``topk``.  Returns a dict of numpy arrays: ``pairs``
+    int32 [M, 3], ``counts`` int64 [3 V + 1], ``confusion`` int64 [V, V] and ``skipped`` (the matrix' tail entry) or None,
+    ``topk_idx`` int32 [N, k] and ``topk_prob`` float64 [N, k] or None."""
+    import numpy as np
+    N, V, k, M = buf["shape"]
+    at = buf["at"]
+    begin = at["confusion"][0] if matrix else at["pairs"][0]
+    end = sum(at["topk_prob"]) if topk and k else sum(at["counts"])
+    h = buf["flat"][begin:end].cpu().numpy()
+    piece = lambda name: h[at[name][0] - begin:at[name][0] - begin + at[name][1]]
+    out = {"pairs": piece("pairs").reshape(M, 3), "counts": piece("counts").astype(np.int64), "confusion": None, "skipped": None,
+           "topk_idx": None, "topk_prob": None}
+    if matrix:
+        out["confusion"], out["skipped"] = piece("confusion")[:V * V].reshape(V, V).astype(np.int64), int(piece("confusion")[V * V])
+    if topk and k:
+        out["topk_idx"] = piece("topk_idx").reshape(N, k)
+        out["topk_prob"] = piece("topk_prob").copy().view(np.float64).reshape(N, k)    # (the copy: 8-byte aligned on the host too)
+    return out
+
+
+def topk_buffers(N, k, device):
+    """The two output tensors of ``topk_rows`` -- idx int32 [N, k], prob float64 [N, k] -- as slices of ONE allocation (the
+    probabilities first: they need the 8-byte alignment), so ``topk_download`` is one copy."""
+    flat = torch.empty(3 * N * k, dtype=torch.int32, device=device)
+    return flat[2 * N * k:].view(N, k), flat[:2 * N * k].view(torch.float64).view(N, k)
+
+
+def topk_download(out):
+    """``topk_rows``' two tensors as numpy arrays (idx int32 [N, k], prob float64 [N, k]): one device-to-host copy when they are
+    ``topk_buffers``' slices of one allocation, two otherwise."""
+    import numpy as np
+    idx, prob = out
+    n = idx.numel()
+    if (idx.is_contiguous() and prob.is_contiguous() and idx.untyped_storage().data_ptr() == prob.untyped_storage().data_ptr()
+            and idx.storage_offset() == 2 * prob.storage_offset() + 2 * n):
+        flat = torch.empty(0, dtype=torch.int32, device=idx.device).set_(idx.untyped_storage(), 2 * prob.storage_offset(), (3 * n,))
+        h = flat.cpu().numpy()
+        return h[2 * n:].reshape(idx.shape), h[:2 * n].view(np.float64).reshape(prob.shape)
+    return idx.cpu().numpy(), prob.cpu().numpy()
+
+
+def topk_rows(logp, k, state=None, out=None):
+    """The ``k`` most probable classes of every row of ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) and their
+    probabilities under softmax(beta logp) (``slnlp_topk_rows``, include/slnlp.h): ``(idx int32 [N, k], prob float64 [N, k])``,
+    device tensors.  The order is the arg-max's (a NaN first, larger values first, equal values by ascending index), so
+    ``idx[:, 0]`` is ``score_rows``' ``pred`` and ``prob[:, 0]`` is ``reliability_rows``' conf.  ``state``: a calibration state
+    whose beta is read on the device; None: beta = 1.  ``out``: such a pair to fill.  Runs on the current stream of ``logp``'s
+    device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("topk_rows", logp)
+    k = _int_in("topk_rows", "k", k, 1, min(V, _lib.TOPK_MAX))
+    if state is not None:
+        _cal_state("topk_rows", state, logp.device)
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = topk_buffers(N, k, logp.device)
+        idx, prob = out
+        for t, dt in ((idx, torch.int32), (prob, torch.float64)):
+            if not (t.device == logp.device and t.dtype == dt and tuple(t.shape) == (N, k) and t.is_contiguous()):
+                raise ValueError(f"topk_rows: out must be (int32 [{N}, {k}], float64 [{N}, {k}]) on {logp.device}")
+        check(load().slnlp_topk_rows(ptr(logp), ld, N, V, k, ptr(state) if state is not None else None, ptr(idx), ptr(prob),
+                                     stream_ptr()), "topk_rows")
+    return out
+
+
+def confusion_matrix(pred, y, V, out=None):
+    """The confusion matrix of the predictions ``pred`` int32 [N] (``score_rows``' first output) against the labels ``y`` int64
+    [N] over ``V`` classes (``slnlp_confusion_matrix``): int32 [V V + 1] on the device -- cell ``y V + pred`` counts the rows with
+    that label and that prediction, the last entry the rows whose label or prediction lies outside [0, V).  ``out``: such a tensor
+    to fill.  Runs on the current stream of ``pred``'s device; no host wait."""
+    _lib.require_gpu()
+    if not (pred.is_cuda and pred.dtype == torch.int32 and pred.dim() == 1 and pred.numel() >= 1 and pred.is_contiguous()):
+        raise ValueError(f"confusion_matrix: pred must be a contiguous int32 [N] device tensor, got {pred.dtype} {tuple(pred.shape)} on "
+                         f"{pred.device}")
+    N = pred.numel()
+    if not (y.device == pred.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"confusion_matrix: y must be a contiguous int64 [{N}] tensor on {pred.device}")
+    V = _int_in("confusion_matrix", "V", V, 1, _lib.CONFUSION_MAX_V)
+    with torch.cuda.device(pred.device):
+        if out is None:
+            out = torch.empty(V * V + 1, dtype=torch.int32, device=pred.device)
+        if not (out.device == pred.device and out.dtype == torch.int32 and out.dim() == 1 and out.numel() == V * V + 1 and out.is_contiguous()):
+            raise ValueError(f"confusion_matrix: out must be a contiguous int32 [{V * V + 1}] tensor on {pred.device}")
+        check(load().slnlp_confusion_matrix(ptr(pred), ptr(y), N, V, ptr(out), stream_ptr()), "confusion_matrix")
+    return out
+
+
+def confusion_pairs(counts, V, M, out=None, work=None):
+    """The ``M`` most-confused pairs of ``confusion_matrix``'s ``counts`` (``slnlp_confusion_pairs``): int32 [M, 3] on the device,
+    rows ``(true, predicted, count)`` over the off-diagonal cells with a count above 0, by count descending, then true class,
+    then predicted class ascending; unused rows are (-1, -1, 0).  ``out``: such a tensor to fill; ``work``: a contiguous uint8
+    scratch tensor of at least ``slnlp_confusion_pairs_workspace_bytes(V, M)`` bytes (default: a new one).  Runs on the current
+    stream of ``counts``' device; no host wait."""
+    _lib.require_gpu()
+    V = _int_in("confusion_pairs", "V", V, 1, _lib.CONFUSION_MAX_V)
+    M = _int_in("confusion_pairs", "M", M, 1, _lib.PAIRS_MAX)
+    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.dim() == 1 and counts.numel() in (V * V, V * V + 1)
+            and counts.is_contiguous()):
+        raise ValueError(f"confusion_pairs: counts must be a contiguous int32 [{V * V + 1}] device tensor, got {counts.dtype} "
+                         f"{tuple(counts.shape)} on {counts.device}")
+    with torch.cuda.device(counts.device):
+        if out is None:
+            out = torch.empty(M, 3, dtype=torch.int32, device=counts.device)
+        if not (out.device == counts.device and out.dtype == torch.int32 and tuple(out.shape) == (M, 3) and out.is_contiguous()):
+            raise ValueError(f"confusion_pairs: out must be a contiguous int32 [{M}, 3] tensor on {counts.device}")
+        if work is None:
+            work = torch.empty(load().slnlp_confusion_pairs_workspace_bytes(V, M), dtype=torch.uint8, device=counts.device)
+        if not (work.device == counts.device and work.dtype == torch.uint8 and work.dim() == 1 and work.is_contiguous()):
+            raise ValueError(f"confusion_pairs: work must be a contiguous uint8 tensor on {counts.device}")
+        check(load().slnlp_confusion_pairs(ptr(counts), V, M, ptr(out), ptr(work), work.numel(), stream_ptr()), "confusion_pairs")
+    return out
+
+
+def error_analysis_rows(logp, y, buf, state=None):
+    """One error analysis on the device, into ``error_analysis_buffers``' slices: ``score_rows`` (arg-max and class counts), then
+    ``confusion_matrix`` on its ``pred``, ``confusion_pairs`` on the matrix and, when the buffers hold top-k lists,
+    ``topk_rows``.  Runs on the current stream of ``logp``'s device; no host wait.  Returns ``buf``."""
+    N, V, k, M = buf["shape"]
+    score_rows(logp, y, out=buf["score"])
+    confusion_matrix(buf["pred"], y, V, out=buf["confusion"])
+    confusion_pairs(buf["confusion"], V, M, out=buf["pairs"], work=buf["work"])
+    if k:
+        topk_rows(logp, k, state=state, out=buf["topk"])
+    return buf
+
+
 class ParamGroupTable:
     """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
     segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
