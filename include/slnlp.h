@@ -450,6 +450,50 @@ int slnlp_confusion_matrix(const int32_t* pred, const int64_t* y, int64_t N, int
 int64_t slnlp_confusion_pairs_workspace_bytes(int64_t V, int M);
 int slnlp_confusion_pairs(const int32_t* counts, int64_t V, int M, int32_t* pairs, void* work, int64_t work_bytes, void* stream);
 
+/* ------------------------------------------------------ bootstrap of the scores --
+ * B bootstrap replicates of the scoring metrics of one set of predictions: every replicate draws N rows with replacement
+ * from the per-row results that are already on the device and reduces them to the metrics (slnlp/metrics.py summarises the
+ * replicates on the host: bootstrap_intervals, bootstrap_difference; NeuralNetClassifier.score_interval / compare).
+ * y int64 [N], pred int32 [N] and rank int32 [N] as slnlp_score_rows takes / leaves them (rank may be null iff top_k == 0);
+ * values double [N, ldv], Q <= ldv columns used (null iff Q == 0) -- slnlp_reliability_rows' rows directly with ldv = 4,
+ * Q = 3: conf, brier, nll.  V in 1..SLNLP_CONFUSION_MAX_V; top_k = 0 or in [1, V); B in 1..SLNLP_BOOT_MAX_REPLICATES.
+ *
+ * The draw.  Random words: Threefry-4x32, the dropout masks' 12 rounds, key (seed low word, seed high word, 0, 0).  Draw j in
+ * [0, N) of replicate b: q = j >> 2, w = j & 3, X0..X3 the output words at counter (q, b, SLNLP_BOOT_STAGE, 0); the row is
+ * (X_w * N) >> 32.  All four words of a call are used (the last call of a replicate may use fewer).  The draw is a function of
+ * (seed, b, j, N) alone, not of the predictions: two calls with one seed on two fits' outputs see the same resamples (a paired
+ * bootstrap), and replicate b does not depend on B.
+ *
+ * Per replicate, over its N drawn rows r (a value outside [0, V) is never used as an index -- slnlp_score_rows' rule):
+ *   true_sum[y_r] += 1 when the label is in range, else n_bad += 1;  pred_sum[pred_r] += 1 when the prediction is in range;
+ *   tp_sum[y_r] += 1 when both are in range and equal;  hits += 1 when the label is in range and rank_r < top_k;
+ *   for each value column its fp64 sum (a NaN propagates).
+ * stats double [B, SLNLP_BOOT_FIXED + Q], row b, with the definitions of slnlp/metrics.py (sklearn's, zero_division = 0):
+ *   [0] accuracy = sum tp_sum / N         [1..3] precision, recall, f1 macro        [4..6] precision, recall, f1 weighted
+ *   [7] balanced_accuracy                 [8] top_k_accuracy = hits / N (NaN when top_k == 0)       [9..] the Q column means
+ * Per class precision = tp / pred_sum, recall = tp / true_sum, f1 = 2 tp / (true_sum + pred_sum), 0 where the denominator is 0.
+ * The macro scores are their means and the weighted scores their true_sum-weighted means (0 when no label is in range) over
+ * the classes PRESENT IN THE REPLICATE (true_sum + pred_sum > 0); balanced_accuracy is the mean recall over the classes with
+ * true_sum > 0 (NaN when there is none): a replicate that loses a rare class changes the denominators.
+ * One difference from metrics._scores, for callers that pass values outside the classes (slnlp_score_rows' pred never is one):
+ * accuracy is sum tp_sum / N, so a row counts as correct only when its label is a class -- a label and a prediction that are the
+ * SAME value outside [0, V) are not a correct row here, while mean(y == pred) would count them.
+ * counts int32 [B, 3 V + 1] or null: row b = true_sum | pred_sum | tp_sum | n_bad, slnlp_score_rows' layout.
+ *
+ * One launch: a block of 256 threads per replicate, the class counts in LDS (integer atomics: sums of integers do not depend
+ * on the order of arrival).  Every fp64 sum is formed in a fixed order -- thread t adds draws (classes) t, t + 256, ... in
+ * increasing order, then a fixed binary tree over the 256 partial sums -- so the result is a function of the arguments alone.
+ * No global atomics.  Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer other than
+ * the nullable ones, N outside 1..INT32_MAX, V outside 1..SLNLP_CONFUSION_MAX_V, B outside 1..SLNLP_BOOT_MAX_REPLICATES, Q
+ * outside 0..SLNLP_BOOT_MAX_VALUES, ldv < Q, top_k < 0 or >= V when nonzero, a misaligned pointer (y, values, stats 8 bytes;
+ * pred, rank, counts 4), an output overlapping an input or the other output. */
+#define SLNLP_BOOT_MAX_REPLICATES 65536
+#define SLNLP_BOOT_MAX_VALUES 8
+#define SLNLP_BOOT_FIXED 9              /* the count-derived columns of stats */
+#define SLNLP_BOOT_STAGE 0x626f6f74u    /* the draw's counter word 2; slnlp_balanced_order uses 0, 1, 2 */
+int slnlp_bootstrap_scores(const int64_t* y, const int32_t* pred, const int32_t* rank, const double* values, int64_t ldv, int Q,
+                           int64_t N, int V, int top_k, int B, uint64_t seed, double* stats, int32_t* counts, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

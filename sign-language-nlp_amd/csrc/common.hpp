@@ -163,7 +163,9 @@ __device__ __forceinline__ uint4 threefry4x32(unsigned c0, unsigned c1, const Dr
 
 // The same generator for draws that are no dropout masks and take their seed as an argument (a class-balanced epoch's order,
 // balance.hip; an epoch's input augmentation, augment.hip): key (seed_lo, seed_hi, 0, 0), counter (index, epoch, word2, 0) --
-// three counter words, same rounds.
+// three counter words, same rounds.  Counter word 2 tells the draws of one (seed, epoch) apart: balance.hip's stages 0, 1, 2,
+// augment.hip's timestep, and bootstrap.hip's resampling draws (counter (draw >> 2, replicate, SEED_STAGE_BOOTSTRAP, 0)).
+constexpr unsigned SEED_STAGE_BOOTSTRAP = SLNLP_BOOT_STAGE;      // "boot": no stage of balance.hip, no timestep
 struct SeedKey { unsigned ks[5]; unsigned epoch; };
 __device__ __forceinline__ SeedKey seed_key(unsigned long long seed, unsigned epoch) {
     SeedKey K;

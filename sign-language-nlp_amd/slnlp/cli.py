@@ -27,7 +27,13 @@ what ``NeuralNetClassifier.error_analysis`` finds on the test split:
     test_confused_pairs.csv        the most-confused (true, predicted) pairs, largest count first
     test_topk.csv                  per test sample its label and the top_k classes with their probabilities
 
-Without the key the workdir holds exactly the files listed above.
+A top-level ``confidence_intervals: {replicates: 1000, level: 0.95, seed: 0}`` (all three optional, these defaults) makes rank 0
+write, next to test_output.json, what ``NeuralNetClassifier.score_interval`` finds on the test split:
+
+    test_intervals.json            point, bootstrap mean / std and the percentile bounds of every scoring name of the run that
+                                   has an interval (ECE and MCE have none), plus replicates, level, seed and rows
+
+Without the two keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -40,7 +46,7 @@ import os
 import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
-             "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis")
+             "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -225,6 +231,55 @@ def save_error_analysis(est, test_data, opts, workdir):
     return res
 
 
+INTERVAL_DEFAULTS = {"replicates": 1000, "level": 0.95, "seed": 0}
+INTERVAL_MAX_REPLICATES = 65536                                                 # SLNLP_BOOT_MAX_REPLICATES
+
+
+def confidence_interval_options(setting):
+    """The ``confidence_intervals`` key with its defaults filled in -- {replicates 1000, level 0.95, seed 0} -- or None when the key
+    is absent.  Anything but a dict over these three keys ({}: all defaults) with ``replicates`` an integer in 2..65536 (one
+    replicate has no standard deviation, and the file holds numbers only), ``level`` a number in (0, 1) and ``seed`` an integer in
+    [0, 2^64) raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"confidence_intervals={setting!r}: expected a dict with keys among {tuple(INTERVAL_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(INTERVAL_DEFAULTS))
+    if unknown:
+        raise ValueError(f"confidence_intervals: unknown keys {unknown} (known: {tuple(INTERVAL_DEFAULTS)})")
+    opts = dict(INTERVAL_DEFAULTS, **setting)
+    whole = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if not whole(opts["replicates"]) or not 2 <= opts["replicates"] <= INTERVAL_MAX_REPLICATES:
+        raise ValueError(f"confidence_intervals: replicates={opts['replicates']!r}, expected an integer in 2..{INTERVAL_MAX_REPLICATES}")
+    if isinstance(opts["level"], bool) or not isinstance(opts["level"], (int, float)) or not 0.0 < opts["level"] < 1.0:
+        raise ValueError(f"confidence_intervals: level={opts['level']!r}, expected a number in (0, 1)")
+    if not whole(opts["seed"]) or not 0 <= opts["seed"] < 2 ** 64:
+        raise ValueError(f"confidence_intervals: seed={opts['seed']!r}, expected an integer in [0, 2^64)")
+    return opts
+
+
+def save_intervals(est, test_data, opts, names, workdir):
+    """``est.score_interval(test_data, **opts)`` for the scoring names among ``names`` that have an interval, as
+    ``test_intervals.json`` in ``workdir``: {replicates, level, seed, rows, intervals: {test_<name>: {point, mean, std, lower, upper,
+    n_nan}}}.  One call serves one top-k, so names with different k take a call each, under the same seed; a ``top<k>_accuracy``
+    whose k is not below the number of classes has no value (``test_output.json`` could not hold it either) and is left out, like the
+    names without an interval.  Returns what it wrote."""
+    from . import metrics
+    by_k = {}                                                                   # k of the top-k column (None: not used) -> names
+    for n in dict.fromkeys(names):
+        found = metrics.bootstrap_metric_of(n) if isinstance(n, str) else None
+        if found is not None and (found[2] is None or 1 <= found[2] < len(est.classes_)):
+            by_k.setdefault(found[2], []).append(n)
+    plain, ks = by_k.pop(None, []), sorted(by_k)
+    groups = [g for g in [plain + (by_k[ks[0]] if ks else []), *(by_k[k] for k in ks[1:])] if g]
+    out = {"replicates": opts["replicates"], "level": opts["level"], "seed": opts["seed"], "rows": len(test_data), "intervals": {}}
+    for group in groups:
+        res = est.score_interval(test_data, scoring=group, **opts)
+        out["intervals"].update({f"test_{n}": res[n] for n in group})
+    save_json(out, os.path.join(workdir, "test_intervals.json"))
+    return out
+
+
 def run(args):
     """main.run + tune_hyperparams + test_model.  Returns (grid search object, test metrics); rank 0 writes files."""
     import random
@@ -252,6 +307,7 @@ def run(args):
             dist.init_process_group("nccl", device_id=torch.device(device), timeout=datetime.timedelta(hours=48))
     workdir = args.get("workdir") or "."
     analysis = error_analysis_options(args.get("error_analysis"))               # a bad key fails before the grid search, not after
+    intervals = confidence_interval_options(args.get("confidence_intervals"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -291,6 +347,8 @@ def run(args):
         save_json(test_output, os.path.join(workdir, "test_output.json"))
         if analysis is not None:
             save_error_analysis(est, test_data, analysis, workdir)
+        if intervals is not None:
+            save_intervals(est, test_data, intervals, metrics, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

@@ -346,3 +346,83 @@ def epoch_scores(names, logp, y, y_host=None, split=None, out=None, rel_out=None
                 raise bad_labels(summaries[bins]["bad_labels"])
         scores[name] = calibration_score(name, summaries[bins])
     return scores
+
+
+# ------------------------------------------------------------------------------------------------------ bootstrap ----
+# The fixed columns of ``slnlp_bootstrap_scores``' stats (include/slnlp.h, SLNLP_BOOT_FIXED of them), in order; the value columns
+# follow.  ``BOOT_VALUES``: what ``NeuralNetClassifier.score_interval`` forms from ``reliability_rows``' (conf, brier, nll) columns:
+# (name, column, sign).
+BOOT_COLUMNS = ("accuracy", "precision_macro", "recall_macro", "f1_macro", "precision_weighted", "recall_weighted", "f1_weighted",
+                "balanced_accuracy", "top_k_accuracy")
+BOOT_VALUES = (("confidence", 0, 1.0), ("neg_brier", 1, -1.0), ("neg_log_loss", 2, -1.0))
+
+
+def bootstrap_metric_of(name):
+    """Where the replicates of the score ``name`` are found in ``slnlp_bootstrap_scores``' stats: ``(column, sign, k)`` -- the
+    score is ``sign * stats[:, column]``; ``k`` is the top-k column's k (``top_k_accuracy``: 2, ``top<k>_accuracy``: k), else
+    None; the value columns (``BOOT_VALUES``) are counted from ``len(BOOT_COLUMNS)``.  None for a name without an interval
+    (ECE and MCE among them: they are no means over rows)."""
+    if name in BOOT_COLUMNS[:-1]:
+        return BOOT_COLUMNS.index(name), 1.0, None
+    k = top_k_of(name)
+    if k is not None:
+        return len(BOOT_COLUMNS) - 1, 1.0, k
+    for value, column, sign in BOOT_VALUES:
+        if name == value:
+            return len(BOOT_COLUMNS) + column, sign, None
+    return None
+
+
+def _boot_level(what, level):
+    if isinstance(level, (bool, np.bool_)) or not isinstance(level, (int, float, np.integer, np.floating)) or not 0.0 < level < 1.0:
+        raise ValueError(f"{what}: level={level!r}, expected a number in (0, 1)")
+    return float(level)
+
+
+def _boot_matrix(what, stats, names):
+    stats = np.asarray(stats, dtype=np.float64)
+    names = list(names)
+    if stats.ndim != 2 or stats.shape[0] < 1 or stats.shape[1] != len(names):
+        raise ValueError(f"{what}: expected a [replicates, {len(names)}] array for the names {names}, got shape {stats.shape}")
+    return stats, names
+
+
+def _boot_summary(x, level):
+    """{mean, std (ddof = 1), lower, upper, n_nan} of the replicates ``x`` that are not NaN (all NaN when there is none)."""
+    kept = x[~np.isnan(x)]
+    nan = float("nan")
+    out = {"mean": nan, "std": nan, "lower": nan, "upper": nan, "n_nan": int(x.size - kept.size)}
+    if kept.size:
+        alpha = 1.0 - level
+        lower, upper = np.quantile(kept, [alpha / 2.0, 1.0 - alpha / 2.0])
+        out.update(mean=float(kept.mean()), std=float(kept.std(ddof=1)) if kept.size > 1 else nan, lower=float(lower), upper=float(upper))
+    return out
+
+
+def bootstrap_intervals(stats, names, level=0.95):
+    """Percentile bootstrap intervals.  ``stats`` [replicates, len(names)]: one column of replicates per name
+    (``ops.bootstrap_scores``' stats, or columns of it).  Per name {mean, std (ddof = 1), lower, upper, n_nan}: ``lower`` and
+    ``upper`` are ``np.quantile(x, [alpha / 2, 1 - alpha / 2])``, alpha = 1 - ``level``, over the replicates that are not NaN (a
+    replicate without any scored class has no balanced accuracy); ``n_nan`` counts the others.  No replicate left: all four NaN."""
+    level = _boot_level("bootstrap_intervals", level)
+    stats, names = _boot_matrix("bootstrap_intervals", stats, names)
+    return {name: _boot_summary(stats[:, i], level) for i, name in enumerate(names)}
+
+
+def bootstrap_difference(stats_a, stats_b, names, level=0.95):
+    """The paired bootstrap of two fits scored on the SAME resamples (two ``ops.bootstrap_scores`` calls with one seed): per name
+    {mean, std, lower, upper, n_nan, p_not_better} of the replicates of ``a - b`` -- ``bootstrap_intervals`` of the difference, plus
+    ``p_not_better``: the share of the replicates that are not NaN with ``a - b <= 0`` (all names are scores, greater is better:
+    near 0, a beats b by more than resampling noise; 1 for two equal fits).  Raises ValueError when the shapes differ."""
+    level = _boot_level("bootstrap_difference", level)
+    a, names = _boot_matrix("bootstrap_difference", stats_a, names)
+    b, _ = _boot_matrix("bootstrap_difference", stats_b, names)
+    if a.shape != b.shape:
+        raise ValueError(f"bootstrap_difference: the two sets of replicates differ in shape, {a.shape} and {b.shape}: a paired comparison "
+                         "needs the same replicates of the same names")
+    out = {}
+    for i, name in enumerate(names):
+        d = a[:, i] - b[:, i]
+        kept = d[~np.isnan(d)]
+        out[name] = dict(_boot_summary(d, level), p_not_better=float(np.mean(kept <= 0.0)) if kept.size else float("nan"))
+    return out

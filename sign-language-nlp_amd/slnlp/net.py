@@ -1187,6 +1187,115 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                 "pairs": [(self.classes_[t], self.classes_[p], int(c)) for t, p, c in got["pairs"] if c > 0],
                 "topk": (self.classes_[got["topk_idx"]], got["topk_prob"]) if k else None, "rows": len(ds)}
 
+    def _interval_request(self, what, scoring, replicates, level, seed):
+        """The checked arguments of ``score_interval`` / ``compare``: ``(names, top_k, replicates, level, seed)``."""
+        V = len(self.classes_)
+        if V > ops._lib.CONFUSION_MAX_V:
+            raise ValueError(f"{what}: {V} classes, the bootstrap counts at most {ops._lib.CONFUSION_MAX_V}")
+        if scoring is None:                                  # everything that has an interval (top_k_accuracy: k = 2, needs V > 2)
+            names = [n for n in metrics.BOOT_COLUMNS if n != "top_k_accuracy" or V > 2] + [v[0] for v in metrics.BOOT_VALUES]
+        else:
+            names = [scoring] if isinstance(scoring, str) else list(scoring) if isinstance(scoring, (list, tuple)) else []
+            if not names or not all(isinstance(n, str) for n in names) or len(set(names)) != len(names):
+                raise ValueError(f"{what}: scoring={scoring!r}, expected None, a name or a list of distinct names")
+        ks = set()
+        for n in names:
+            if n in metrics.CALIBRATION[:2] or n.startswith("neg_ece"):
+                raise ValueError(f"{what}: {n} has no bootstrap interval here: ECE and MCE are no means over rows, a replicate would need "
+                                 "its own bin sums; neg_brier, neg_log_loss and confidence have one")
+            found = metrics.bootstrap_metric_of(n)
+            if found is None:
+                raise ValueError(f"{what}: {n!r} has no bootstrap interval; known: {metrics.BOOT_COLUMNS[:-1]}, top_k_accuracy, "
+                                 f"top<k>_accuracy, {tuple(v[0] for v in metrics.BOOT_VALUES)}")
+            if found[2] is not None:
+                if not 1 <= found[2] < V:
+                    raise ValueError(f"{what}: {n}: k={found[2]} must lie in [1, {V}) for {V} classes")
+                ks.add(found[2])
+        if len(ks) > 1:
+            raise ValueError(f"{what}: top-k accuracies for k in {sorted(ks)} asked for, one call resamples one k")
+        B = self._int_option(what, "replicates", replicates, 1, ops._lib.BOOT_MAX_REPLICATES)
+        seed = self._int_option(what, "seed", seed, 0, 2 ** 64 - 1)
+        return names, (ks.pop() if ks else 0), B, metrics._boot_level(what, level), seed
+
+    def _bootstrap(self, what, X, y, names, top_k, B, seed, calibrated):
+        """One forward pass over ``X``, then ``ops.score_interval_rows`` and one download: ``(point {name: full-sample score},
+        replicates float64 [B, len(names)], rows)``."""
+        ds = self._as_dataset(X)
+        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
+        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
+        if labels is not None and labels.shape != (len(ds),):
+            raise ValueError(f"{what}: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
+
+        def rows(logp, yd):
+            yd = yd if labels is None else labels.to(logp.device)
+            buf = ops.score_interval_buffers(logp.shape[0], logp.shape[1], B, logp.device)
+            return ops.score_interval_rows(logp if logp.dtype == torch.float32 else logp.float(), yd.contiguous(), buf, top_k=top_k,
+                                           seed=seed, state=self._cal_state if use else None)
+        got = ops.score_interval_download(self._forward_logp(ds, rows))
+        counts = got["counts"]
+        V = (counts.size - 1) // 3                           # the columns of the log-probs
+        if counts[3 * V] > 0:
+            raise ValueError(f"{what}: {int(counts[3 * V])} of {len(ds)} labels lie outside the {V} classes of the log-probs")
+        y_true = (np.asarray(ds.y) if labels is None else labels.numpy()).astype(np.int64)
+        where = {n: metrics.bootstrap_metric_of(n) for n in names}
+        counted = [n for n in names if where[n][0] < len(metrics.BOOT_COLUMNS)]
+        point = metrics.scores_from_rows(counted, y_true, got["pred"], None, got["rank"], counts, V)
+        table = metrics.reliability_from_table(got["table"])
+        for name, column, sign in metrics.BOOT_VALUES:       # the reliability table's means: confidence, brier, nll
+            if name in where:
+                point[name] = sign * table[("confidence", "brier", "nll")[column]]
+        reps = np.stack([where[n][1] * got["stats"][:, where[n][0]] for n in names], axis=1)
+        return point, reps, len(ds)
+
+    def score_interval(self, X, y=None, scoring=None, replicates=1000, level=0.95, seed=0, calibrated=True, return_replicates=False):
+        """Percentile bootstrap confidence intervals of this fit's scores on ``X`` (``y``: the labels; None: the dataset's), drawn
+        on the device: one forward pass, ``ops.score_rows``, ``ops.reliability_rows`` (at ``temperature_`` for a calibrated fit
+        unless ``calibrated=False``), then ``replicates`` resamples of the per-row results (``ops.bootstrap_scores``) and ONE
+        download.  ``scoring``: a name or a list of names among accuracy, precision / recall / f1 _macro and _weighted,
+        balanced_accuracy, ``top_k_accuracy`` (k = 2) or ``top<k>_accuracy`` (one k per call), ``neg_log_loss``, ``neg_brier`` and
+        ``confidence`` (the mean top-class probability); None: all of them.  ``neg_ece`` / ``neg_mce`` are rejected: they are no
+        means over rows.  Returns {name: {point, mean, std, lower, upper, n_nan}} plus ``replicates``, ``level``, ``seed`` and
+        ``rows``: ``point`` is the full-sample score from the existing paths (``metrics.scores_from_rows``, the reliability
+        table); mean, std (ddof = 1) and the ``level`` percentile bounds are ``metrics.bootstrap_intervals`` of the replicates.
+        A replicate scores the classes present IN IT, as sklearn would score that resample.  ``neg_log_loss`` here is minus the
+        mean of ``reliability_rows``' fp64 nll -- the UNCLIPPED fp64 log-loss of softmax(z / T), not sklearn's float32-clipped
+        one that the history's ``neg_log_loss`` restates; its ``point`` is formed the same way.  The resamples depend on
+        ``(seed, len(X))`` alone.  ``return_replicates=True`` adds ``names`` and ``replicate_scores`` float64 [replicates,
+        len(names)].  Raises ValueError when a label lies outside the classes."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        names, top_k, B, level, seed = self._interval_request("score_interval", scoring, replicates, level, seed)
+        point, reps, n = self._bootstrap("score_interval", X, y, names, top_k, B, seed, calibrated)
+        summary = metrics.bootstrap_intervals(reps, names, level)
+        out = {name: dict(point=float(point[name]), **summary[name]) for name in names}
+        out.update(replicates=B, level=level, seed=seed, rows=n)
+        if return_replicates:
+            out.update(names=names, replicate_scores=reps)
+        return out
+
+    def compare(self, other, X, y=None, scoring=None, replicates=1000, level=0.95, seed=0, calibrated=True, return_replicates=False):
+        """The paired bootstrap of this fit against ``other`` on ``X``: both fits are scored as ``score_interval`` does, with ONE
+        seed -- so replicate b holds the same rows for both -- and the replicates of ``self - other`` are summarised
+        (``metrics.bootstrap_difference``).  Returns {name: {point, mean, std, lower, upper, n_nan, p_not_better}} plus
+        ``replicates``, ``level``, ``seed`` and ``rows``: ``point`` is the difference of the full-sample scores,
+        ``p_not_better`` the share of replicates in which ``self`` does not beat ``other`` (every name is a score: greater is
+        better).  ``return_replicates=True`` adds ``names`` and ``replicate_scores`` (of the difference).  Raises ValueError when
+        the two fits' ``classes_`` differ."""
+        if not self.initialized_ or not getattr(other, "initialized_", False):
+            raise RuntimeError("compare: both NeuralNetClassifier instances must be initialized.")
+        if not np.array_equal(np.asarray(self.classes_), np.asarray(other.classes_)):
+            raise ValueError(f"compare: the two fits have different classes_ ({len(self.classes_)} and {len(other.classes_)} classes): "
+                             "their scores are not comparable")
+        names, top_k, B, level, seed = self._interval_request("compare", scoring, replicates, level, seed)
+        point_a, reps_a, n = self._bootstrap("compare", X, y, names, top_k, B, seed, calibrated)
+        point_b, reps_b, _ = other._bootstrap("compare", X, y, names, top_k, B, seed, calibrated)
+        summary = metrics.bootstrap_difference(reps_a, reps_b, names, level)
+        out = {name: dict(point=float(point_a[name] - point_b[name]), **summary[name]) for name in names}
+        out.update(replicates=B, level=level, seed=seed, rows=n)
+        if return_replicates:
+            out.update(names=names, replicate_scores=reps_a - reps_b)
+        return out
+
     def score(self, X, y=None):
         ds = self._as_dataset(X)
         return float((self.predict(ds) == (ds.y if y is None else np.asarray(y))).mean())

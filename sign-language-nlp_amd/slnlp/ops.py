@@ -728,6 +728,128 @@ def error_analysis_rows(logp, y, buf, state=None):
     return buf
 
 
+def bootstrap_buffers(B, V, Q, counts, device):
+    """The output tensors of ``bootstrap_scores`` for ``B`` replicates over ``V`` classes with ``Q`` value columns -- stats
+    float64 [B, 9 + Q] and, with ``counts``, counts int32 [B, 3 V + 1] (else None) -- as slices of ONE allocation, so
+    ``bootstrap_download`` is one copy."""
+    n_stats, n_counts = B * (_lib.BOOT_FIXED + Q), B * (3 * V + 1) if counts else 0
+    flat = torch.empty(n_stats + (n_counts + 1) // 2, dtype=torch.float64, device=device)
+    return flat[:n_stats].view(B, _lib.BOOT_FIXED + Q), (flat[n_stats:].view(torch.int32)[:n_counts].view(B, 3 * V + 1) if counts else None)
+
+
+def bootstrap_download(out):
+    """``bootstrap_scores``' result as numpy arrays ``(stats float64 [B, 9 + Q], counts int32 [B, 3 V + 1] or None)``: one
+    device-to-host copy when they are ``bootstrap_buffers``' slices of one allocation (it waits for the launch), two otherwise."""
+    import numpy as np
+    stats, counts = out
+    if counts is None:
+        return stats.cpu().numpy(), None
+    n, words = stats.numel(), (counts.numel() + 1) // 2
+    if (stats.is_contiguous() and counts.is_contiguous() and stats.untyped_storage().data_ptr() == counts.untyped_storage().data_ptr()
+            and counts.storage_offset() == 2 * (stats.storage_offset() + n)
+            and stats.untyped_storage().nbytes() >= 8 * (stats.storage_offset() + n + words)):
+        flat = torch.empty(0, dtype=torch.float64, device=stats.device).set_(stats.untyped_storage(), stats.storage_offset(), (n + words,))
+        h = flat.cpu().numpy()
+        return h[:n].reshape(stats.shape), h[n:].view(np.int32)[:counts.numel()].reshape(counts.shape)
+    return stats.cpu().numpy(), counts.cpu().numpy()
+
+
+def bootstrap_scores(y, pred, rank, values=None, *, n_classes, top_k=0, replicates, seed, counts=False, out=None):
+    """``replicates`` bootstrap replicates of the scoring metrics of one set of predictions (``slnlp_bootstrap_scores``,
+    include/slnlp.h): the labels ``y`` int64 [N], ``score_rows``' ``pred`` and ``rank`` int32 [N] (``rank`` may be None when
+    ``top_k`` is 0) and ``values`` float64 [N, Q] with unit column stride, Q <= 8 (rows may be padded: ``stride(0) >= Q`` --
+    ``reliability_rows``' ``rows[:, :3]`` directly: conf, brier, nll; None: Q = 0) are resampled with replacement, every replicate
+    from N draws that depend on ``(seed, replicate, N)`` alone -- two calls with one seed resample two fits alike.  Returns
+    ``(stats float64 [replicates, 9 + Q], counts)``, device tensors sliced from one allocation: the columns of ``stats`` are
+    ``metrics.BOOT_COLUMNS`` (``top_k_accuracy`` is NaN with ``top_k=0``, else top-``top_k`` accuracy, k in [1, n_classes)), then
+    the means of the value columns; ``counts`` is int32 [replicates, 3 V + 1] (``score_rows``' layout per replicate) with
+    ``counts=True``, else None.  ``out``: such a pair to fill.  Runs on the current stream of ``y``'s device; no host wait."""
+    _lib.require_gpu()
+    what = "bootstrap_scores"
+    if not (y.is_cuda and y.dtype == torch.int64 and y.dim() == 1 and y.numel() >= 1 and y.is_contiguous()):
+        raise ValueError(f"{what}: y must be a contiguous int64 [N] device tensor, got {y.dtype} {tuple(y.shape)} on {y.device}")
+    N = y.numel()
+    V = _int_in(what, "n_classes", n_classes, 1, _lib.CONFUSION_MAX_V)
+    B = _int_in(what, "replicates", replicates, 1, _lib.BOOT_MAX_REPLICATES)
+    seed = _int_in(what, "seed", seed, 0, 2 ** 64 - 1)
+    top_k = _int_in(what, "top_k", top_k, 0, max(V - 1, 0))
+    for name, t in (("pred", pred), ("rank", rank)):
+        if t is None and name == "rank" and top_k == 0:
+            continue
+        if t is None or not (t.device == y.device and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == N and t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous int32 [{N}] tensor on {y.device}")
+    Q, ldv = 0, 0
+    if values is not None:
+        if not (values.device == y.device and values.dtype == torch.float64 and values.dim() == 2 and values.shape[0] == N
+                and 1 <= values.shape[1] <= _lib.BOOT_MAX_VALUES and (values.stride(1) == 1 or values.shape[1] == 1)
+                and (N == 1 or values.stride(0) >= values.shape[1])):
+            raise ValueError(f"{what}: values must be a float64 [{N}, 1..{_lib.BOOT_MAX_VALUES}] tensor on {y.device} with unit column "
+                             f"stride, got {values.dtype} {tuple(values.shape)} strides {values.stride()} on {values.device}")
+        Q = int(values.shape[1])
+        ldv = int(values.stride(0)) if N > 1 else max(Q, int(values.stride(0)))
+    with torch.cuda.device(y.device):
+        if out is None:
+            out = bootstrap_buffers(B, V, Q, bool(counts), y.device)
+        stats, cnt = out
+        ok = stats.device == y.device and stats.dtype == torch.float64 and tuple(stats.shape) == (B, _lib.BOOT_FIXED + Q) and stats.is_contiguous()
+        if cnt is not None:
+            ok = ok and cnt.device == y.device and cnt.dtype == torch.int32 and tuple(cnt.shape) == (B, 3 * V + 1) and cnt.is_contiguous()
+        if not ok:
+            raise ValueError(f"{what}: out must be (float64 [{B}, {_lib.BOOT_FIXED + Q}], int32 [{B}, {3 * V + 1}] or None) on {y.device}")
+        check(load().slnlp_bootstrap_scores(ptr(y), ptr(pred), ptr(rank) if top_k else None, ptr(values), ldv, Q, N, V, top_k, B, seed,
+                                            ptr(stats), ptr(cnt), stream_ptr()), what)
+    return out
+
+
+def score_interval_buffers(N, V, B, device, bins=15):
+    """Every device buffer of one bootstrap of an [N, V] set of log-probs (``NeuralNetClassifier.score_interval``) as slices of ONE
+    float64 allocation, what the host reads first:
+
+        stats [B, 9 + 3] | table [bins + 1, 4] | pred [N] | picked float32 [N] | rank [N] | counts [3 V + 1] | rows [N, 4]
+
+    (pad entries keep table and rows 32-byte aligned).  ``score`` = (pred, picked, rank, counts) is ``score_rows``' ``out``,
+    ``reliability`` = (rows, table) ``reliability_rows``', ``boot`` = (stats, None) ``bootstrap_scores``'; the per-row terms never
+    leave the device (``score_interval_download``)."""
+    what = "score_interval_buffers"
+    N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
+    B, bins = _int_in(what, "B", B, 1, _lib.BOOT_MAX_REPLICATES), _int_in(what, "bins", bins, 1, _lib.REL_MAX_BINS)
+    pad4 = lambda n: (n + 3) // 4 * 4
+    n_stats, n_ints = B * (_lib.BOOT_FIXED + 3), 3 * N + 3 * V + 1
+    o_table = pad4(n_stats)
+    o_ints = o_table + 4 * (bins + 1)
+    o_rows = pad4(o_ints + (n_ints + 1) // 2)
+    flat = torch.empty(o_rows + 4 * N, dtype=torch.float64, device=device)
+    ints = flat[o_ints:o_rows].view(torch.int32)
+    score = (ints[:N], ints[N:2 * N].view(torch.float32), ints[2 * N:3 * N], ints[3 * N:n_ints])
+    return {"flat": flat, "shape": (N, V, B, bins), "head": o_ints + (n_ints + 1) // 2, "at": (o_table, o_ints), "score": score,
+            "reliability": (flat[o_rows:].view(N, 4), flat[o_table:o_ints].view(bins + 1, 4)),
+            "boot": (flat[:n_stats].view(B, _lib.BOOT_FIXED + 3), None)}
+
+
+def score_interval_rows(logp, y, buf, *, top_k=0, seed=0, state=None):
+    """One bootstrap on the device, into ``score_interval_buffers``' slices: ``score_rows``, ``reliability_rows`` (at ``state``'s
+    beta; None: 1) and ``bootstrap_scores`` on what the two left -- pred, rank and the (conf, brier, nll) columns.  Runs on the
+    current stream of ``logp``'s device; no host wait.  Returns ``buf``."""
+    N, V, B, bins = buf["shape"]
+    pred, _, rank, _ = score_rows(logp, y, out=buf["score"])
+    rows, _ = reliability_rows(logp, y, bins=bins, state=state, out=buf["reliability"])
+    bootstrap_scores(y, pred, rank, rows[:, :3], n_classes=V, top_k=top_k, replicates=B, seed=seed, out=buf["boot"])
+    return buf
+
+
+def score_interval_download(buf):
+    """What ``score_interval_rows`` hands to the host, in ONE device-to-host copy (it waits for the launches): a dict of numpy
+    arrays -- ``stats`` float64 [B, 12], ``table`` float64 [bins + 1, 4], ``pred`` int32 [N], ``rank`` int32 [N], ``counts`` int64
+    [3 V + 1]."""
+    import numpy as np
+    N, V, B, bins = buf["shape"]
+    o_table, o_ints = buf["at"]
+    h = buf["flat"][:buf["head"]].cpu().numpy()
+    ints = h[o_ints:].view(np.int32)
+    return {"stats": h[:B * (_lib.BOOT_FIXED + 3)].reshape(B, _lib.BOOT_FIXED + 3), "table": h[o_table:o_ints].reshape(bins + 1, 4),
+            "pred": ints[:N], "rank": ints[2 * N:3 * N], "counts": ints[3 * N:3 * N + 3 * V + 1].astype(np.int64)}
+
+
 class ParamGroupTable:
     """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
     segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
