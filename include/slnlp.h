@@ -494,6 +494,50 @@ int slnlp_confusion_pairs(const int32_t* counts, int64_t V, int M, int32_t* pair
 int slnlp_bootstrap_scores(const int64_t* y, const int32_t* pred, const int32_t* rank, const double* values, int64_t ldv, int Q,
                            int64_t N, int V, int top_k, int B, uint64_t seed, double* stats, int32_t* counts, void* stream);
 
+/* ------------------------------------------------------ ensembles of log-probs --
+ * K fits' log-probs combined into one set of log-probs in the layout every row entry point above reads, and in the same pass
+ * the per-row uncertainty decomposition (slnlp/ops.py's ensemble_rows; slnlp/ensemble.py's VotingEnsemble).
+ * logp: a HOST array of K device pointers, K in 1..SLNLP_ENSEMBLE_MAX_MEMBERS; member k is float32 [N, ld[k]], V <= ld[k]
+ * columns used; ld: a host array.  beta_dev: a host array of K device pointers, or null; an entry may be null.  A null entry (or
+ * a null array) means beta_k = 1 exactly, otherwise beta_k = beta_dev[k][0] is read on the device (a calibration state's first
+ * double, as slnlp_reliability_rows takes it), so the call never waits for the host.  weights: a host array of K finite doubles
+ * > 0, or null; the call normalises them in fp64, w_k = weights[k] / (their sum in increasing k); null: w_k = 1 / K.  The
+ * members travel to the kernel by value in its argument struct: no device table is uploaded, and the host arrays may be freed
+ * as soon as the call returns.  out float32 [N, ld_out]; rows double [N, 4] or null (then no diagnostics are formed).
+ *
+ * Per row i, in fp64 throughout (z itself is float32):
+ *   member term   slnlp_scale_logp's expression before its rounding: zmax_k the float32 row maximum, a_k = beta_k zmax_k, the
+ *                 columns at the maximum counted and not exponentiated:
+ *                 l_kc = (beta_k z_kc - a_k) - log1p(rest_k + (n_at_max_k - 1)),  p_kc = exp(l_kc); a -inf column is an ordinary
+ *                 value with p = 0
+ *   mixture       (every mode) m_c = max_k l_kc, mix_c = m_c + log(sum_k w_k exp(l_kc - m_c)) with k increasing, -inf when m_c is
+ *   SLNLP_VOTE_SOFT   out_c = (float) mix_c: the arithmetic mean of the members' probabilities
+ *   SLNLP_VOTE_LOG    u_c = sum_k w_k l_kc with k increasing, out_c = (float)((u_c - umax) - log(sum_c exp(u_c - umax))): the
+ *                 weighted geometric mean, renormalised (a product of experts)
+ *   rows[i]       with pbar_c = exp(mix_c) whatever the mode:
+ *     [0] H_total = -sum_c pbar_c mix_c                              the entropy of the mixture
+ *     [1] H_mean  = sum_k w_k (-sum_c p_kc l_kc)                     the expected entropy of a member
+ *     [2] MI      = sum_k w_k sum_c p_kc (l_kc - mix_c)              their difference, the mutual information -- summed directly
+ *                   and not formed as [0] - [1], so nothing cancels: MI >= 0 up to rounding, MI <= -sum_k w_k log w_k
+ *     [3] n_disagree: the members whose own arg-max -- the first maximum of their float32 row, slnlp_score_rows' order, which
+ *                   beta > 0 does not move -- is not the first maximum of the float32 out row as stored
+ *     terms with a zero probability are 0.
+ * A row in which a member holds a NaN or has a row maximum that is not finite, or (SLNLP_VOTE_LOG) whose every u_c is -inf, gets
+ * NaN in every out column and rows = (NaN, NaN, NaN, -2): slnlp_reliability_rows' NaN-row convention.
+ *
+ * One launch: 256 threads, a wave per row, lanes stride the columns; no LDS, no atomics.  Every sum is formed in a fixed order
+ * (a lane's columns ascending, the members ascending within a column, then the wave butterfly), so the result is a function of
+ * the arguments alone.  The second pass re-reads the K rows, every column by the lane that uses it: out may alias NO input.
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null logp, ld or out, or a null member pointer;
+ * K outside 1..SLNLP_ENSEMBLE_MAX_MEMBERS; N or V outside 1..INT32_MAX; an unknown mode; ld[k] < V or ld_out < V; a weight that
+ * is not finite or not > 0; a misaligned pointer (members and out 4 bytes, betas 8, rows 32); out or rows overlapping a
+ * member, a beta or each other. */
+#define SLNLP_ENSEMBLE_MAX_MEMBERS 32
+#define SLNLP_VOTE_SOFT 0     /* arithmetic mean of the members' probabilities */
+#define SLNLP_VOTE_LOG  1     /* weighted geometric mean, renormalised (product of experts) */
+int slnlp_ensemble_rows(const float* const* logp, const int64_t* ld, const double* const* beta_dev, const double* weights,
+                        int K, int64_t N, int64_t V, int mode, float* out, int64_t ld_out, double* rows, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

@@ -1,0 +1,10 @@
+"""slnlp: the MI355X path of the sign-language gloss classifier.  The submodules are imported on demand (``slnlp.net``,
+``slnlp.ops``, ...); ``slnlp.VotingEnsemble`` is resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
+__all__ = ["VotingEnsemble"]
+
+
+def __getattr__(name):
+    if name == "VotingEnsemble":
+        from .ensemble import VotingEnsemble
+        return VotingEnsemble
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

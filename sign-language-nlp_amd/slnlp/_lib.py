@@ -133,6 +133,7 @@ SIGNATURES = {
     "slnlp_confusion_pairs_workspace_bytes": (i64, [i64, i32]),
     "slnlp_confusion_pairs": (i32, [vp, i64, i32, vp, vp, i64, vp]),
     "slnlp_bootstrap_scores": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, C.c_uint64, vp, vp, vp]),
+    "slnlp_ensemble_rows": (i32, [vp, vp, vp, vp, i32, i64, i64, i32, vp, i64, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -276,6 +277,8 @@ BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES
 BOOT_MAX_VALUES = 8                             # SLNLP_BOOT_MAX_VALUES
 BOOT_FIXED = 9                                  # SLNLP_BOOT_FIXED
 BOOT_STAGE = 0x626F6F74                         # SLNLP_BOOT_STAGE
+ENSEMBLE_MAX_MEMBERS = 32                       # SLNLP_ENSEMBLE_MAX_MEMBERS
+VOTING = {"soft": 0, "log": 1}                  # SLNLP_VOTE_*
 
 
 def ptr(t):

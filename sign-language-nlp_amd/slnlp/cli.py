@@ -33,7 +33,17 @@ write, next to test_output.json, what ``NeuralNetClassifier.score_interval`` fin
     test_intervals.json            point, bootstrap mean / std and the percentile bounds of every scoring name of the run that
                                    has an interval (ECE and MCE have none), plus replicates, level, seed and rows
 
-Without the two keys the workdir holds exactly the files listed above.
+A top-level ``ensemble: {members: 5, voting: soft}`` (both optional, these defaults; ``voting``: soft or log; ``members`` in 2..32)
+makes rank 0, after the refit, fit ``members - 1`` more estimators with the best parameters on the train data -- member i after
+``torch.manual_seed(seed + i)``, without checkpoints of its own, saved under ``workdir/ensemble/member<i>/`` -- and combine them with
+the refit (member 0) into a ``slnlp.ensemble.VotingEnsemble``, and write, next to test_output.json:
+
+    test_ensemble.json             the ensemble's and every member's test scores for the run's metrics, the ensemble's
+                                   ``uncertainty`` on the test split, and ``best_estimator_.compare(ensemble, test_data)``: the
+                                   paired bootstrap of the single refit against the ensemble (with the ``confidence_intervals``
+                                   options when that key is present, else its defaults)
+
+Without the three keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -46,7 +56,8 @@ import os
 import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
-             "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals")
+             "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
+             "ensemble")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -280,6 +291,60 @@ def save_intervals(est, test_data, opts, names, workdir):
     return out
 
 
+ENSEMBLE_DEFAULTS = {"members": 5, "voting": "soft"}
+ENSEMBLE_MAX_MEMBERS = 32                                                       # SLNLP_ENSEMBLE_MAX_MEMBERS
+ENSEMBLE_VOTING = ("soft", "log")
+
+
+def ensemble_options(setting):
+    """The ``ensemble`` key with its defaults filled in -- {members 5, voting soft} -- or None when the key is absent.  Anything but
+    a dict over these two keys ({}: all defaults) with ``members`` an integer in 2..32 (one member is the refit itself) and
+    ``voting`` "soft" or "log" raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"ensemble={setting!r}: expected a dict with keys among {tuple(ENSEMBLE_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(ENSEMBLE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"ensemble: unknown keys {unknown} (known: {tuple(ENSEMBLE_DEFAULTS)})")
+    opts = dict(ENSEMBLE_DEFAULTS, **setting)
+    if isinstance(opts["members"], bool) or not isinstance(opts["members"], int) or not 2 <= opts["members"] <= ENSEMBLE_MAX_MEMBERS:
+        raise ValueError(f"ensemble: members={opts['members']!r}, expected an integer in 2..{ENSEMBLE_MAX_MEMBERS}")
+    if opts["voting"] not in ENSEMBLE_VOTING:
+        raise ValueError(f"ensemble: voting={opts['voting']!r}, expected one of {ENSEMBLE_VOTING}")
+    return opts
+
+
+def save_ensemble(gs, factory, train_data, test_data, opts, intervals, names, seed, workdir):
+    """The refit (member 0) and ``opts["members"] - 1`` further fits of ``gs.best_params_`` on ``train_data`` -- member i after
+    ``torch.manual_seed(seed + i)``, ``checkpoint_dir=None``, saved under ``workdir/ensemble/member<i>/`` -- as a
+    ``VotingEnsemble``; ``test_ensemble.json`` in ``workdir``: {members, voting, scores: {ensemble, members}, uncertainty,
+    single_vs_ensemble}.  Names whose top-k is not below the number of classes have no value and are left out, as in
+    ``save_intervals``.  Returns (the ensemble, what it wrote)."""
+    import torch
+
+    from . import metrics
+    from .ensemble import VotingEnsemble
+    members = [gs.best_estimator_]
+    for i in range(1, opts["members"]):
+        net = factory().set_params(**gs.best_params_).set_params(checkpoint_dir=None)
+        torch.manual_seed(seed + i)
+        net.fit(train_data)
+        net.save_params(os.path.join(workdir, "ensemble", f"member{i}"))
+        members.append(net)
+    ens = VotingEnsemble(members, voting=opts["voting"])
+    V = len(ens.classes_)
+    names = [n for n in dict.fromkeys(names) if metrics.top_k_of(n) is None or 1 <= metrics.top_k_of(n) < V]
+    scores = ens.member_scores(test_data, names)
+    out = {"members": len(members), "voting": opts["voting"],
+           "scores": {"ensemble": {f"test_{n}": v for n, v in scores["ensemble"].items()},
+                      "members": [{f"test_{n}": v for n, v in m.items()} for m in scores["members"]]},
+           "uncertainty": ens.uncertainty(test_data),
+           "single_vs_ensemble": gs.best_estimator_.compare(ens, test_data, **(intervals or {}))}
+    save_json(out, os.path.join(workdir, "test_ensemble.json"))
+    return ens, out
+
+
 def run(args):
     """main.run + tune_hyperparams + test_model.  Returns (grid search object, test metrics); rank 0 writes files."""
     import random
@@ -308,6 +373,7 @@ def run(args):
     workdir = args.get("workdir") or "."
     analysis = error_analysis_options(args.get("error_analysis"))               # a bad key fails before the grid search, not after
     intervals = confidence_interval_options(args.get("confidence_intervals"))
+    ensemble = ensemble_options(args.get("ensemble"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -349,6 +415,8 @@ def run(args):
             save_error_analysis(est, test_data, analysis, workdir)
         if intervals is not None:
             save_intervals(est, test_data, intervals, metrics, workdir)
+        if ensemble is not None:
+            save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

@@ -426,3 +426,19 @@ def bootstrap_difference(stats_a, stats_b, names, level=0.95):
         kept = d[~np.isnan(d)]
         out[name] = dict(_boot_summary(d, level), p_not_better=float(np.mean(kept <= 0.0)) if kept.size else float("nan"))
     return out
+
+
+def uncertainty_summary(rows):
+    """An ensemble's per-row uncertainty decomposition -- ``ops.ensemble_rows``' rows float64 [N, 4] = (total entropy, expected
+    member entropy, mutual information, disagreeing members), code -2 in the last column for a row that held a NaN -- reduced
+    on the host, in fp64, to means over the scored rows: {total_entropy, expected_entropy, mutual_information,
+    disagreement_rate (the share of rows on which some member's arg-max is not the ensemble's), mean_disagreement (members per
+    row), rows, nan_rows}.  No scored row: the means are NaN."""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != 4:
+        raise ValueError(f"uncertainty_summary: rows has shape {rows.shape}, expected [N, 4]")
+    ok = rows[:, 3] >= 0
+    n = int(ok.sum())
+    mean = (lambda v: float(np.sum(v) / n)) if n else (lambda v: float("nan"))
+    return {"total_entropy": mean(rows[ok, 0]), "expected_entropy": mean(rows[ok, 1]), "mutual_information": mean(rows[ok, 2]),
+            "disagreement_rate": mean(rows[ok, 3] > 0), "mean_disagreement": mean(rows[ok, 3]), "rows": n, "nan_rows": int((~ok).sum())}

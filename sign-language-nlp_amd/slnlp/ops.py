@@ -850,6 +850,69 @@ def score_interval_download(buf):
             "pred": ints[:N], "rank": ints[2 * N:3 * N], "counts": ints[3 * N:3 * N + 3 * V + 1].astype(np.int64)}
 
 
+def ensemble_rows(logps, states=None, weights=None, voting="soft", diagnostics=True, out=None):
+    """K fits' log-probs combined on the device (``slnlp_ensemble_rows``, include/slnlp.h): ``logps`` is a list of 1..32 float32
+    [N, V] device tensors (rows may be padded: ``stride(0) >= V``), ``states`` a list of calibration states (``fit_temperature`` /
+    ``temperature_state``) or Nones -- member k enters as softmax(beta_k logp_k), beta_k read on the device, None: 1 --
+    ``weights`` K finite numbers > 0 (normalised by the call) or None: equal; ``voting`` "soft", the mean of the probabilities, or
+    "log", their weighted geometric mean renormalised.  Returns ``(out float32 [N, V], rows float64 [N, 4] or None)``: the
+    combined log-probs, in the layout every row op here reads, and per row (total entropy, expected member entropy, mutual
+    information, number of members whose arg-max is not the ensemble's) -- (NaN, NaN, NaN, -2) and a NaN ``out`` row where a
+    member's row holds a NaN.  ``diagnostics=False`` forms no rows.  ``out``: a float32 [N, V] tensor to fill, no member's memory.
+    Runs on the current stream of the members' device; no host wait."""
+    _lib.require_gpu()
+    what = "ensemble_rows"
+    logps = list(logps) if isinstance(logps, (list, tuple)) else []
+    K = len(logps)
+    if not 1 <= K <= _lib.ENSEMBLE_MAX_MEMBERS:
+        raise ValueError(f"{what}: logps must be a list of 1..{_lib.ENSEMBLE_MAX_MEMBERS} tensors")
+    if voting not in _lib.VOTING:
+        raise ValueError(f"{what}: voting={voting!r}, expected one of {tuple(_lib.VOTING)}")
+    N, V, _ = _logp_matrix(what, logps[0])
+    dev = logps[0].device
+    lds = []
+    for k, z in enumerate(logps):
+        n, v, ld = _logp_matrix(f"{what} (member {k})", z)
+        if (n, v) != (N, V) or z.device != dev:
+            raise ValueError(f"{what}: member {k} is {tuple(z.shape)} on {z.device}, member 0 is {(N, V)} on {dev}")
+        lds.append(ld)
+    states = [None] * K if states is None else list(states)
+    if len(states) != K:
+        raise ValueError(f"{what}: {len(states)} states for {K} members")
+    for st in states:
+        if st is not None:
+            _cal_state(what, st, dev)
+    if weights is not None:
+        weights = [float(w) for w in weights]
+        if len(weights) != K or not all(0.0 < w < float("inf") for w in weights):
+            raise ValueError(f"{what}: weights={weights!r}, expected {K} finite numbers above 0")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(N, V, dtype=torch.float32, device=dev)
+        if out.device != dev or tuple(out.shape) != (N, V):
+            raise ValueError(f"{what}: out must be a float32 [{N}, {V}] tensor on {dev}")
+        _, _, ld_out = _logp_matrix(f"{what} (out)", out)
+        rows = torch.empty(N, 4, dtype=torch.float64, device=dev) if diagnostics else None
+        check(load().slnlp_ensemble_rows((C.c_void_p * K)(*[ptr(z) for z in logps]), (C.c_int64 * K)(*lds),
+                                         (C.c_void_p * K)(*[ptr(st) for st in states]),
+                                         (C.c_double * K)(*weights) if weights is not None else None, K, N, V, _lib.VOTING[voting],
+                                         ptr(out), ld_out, ptr(rows), stream_ptr()), what)
+    return out, rows
+
+
+def ensemble_download(res, per_row=False):
+    """``ensemble_rows``' diagnostics as ``metrics.uncertainty_summary``'s dict; ``per_row=True`` adds ``per_row``, the float64
+    [N, 4] rows.  ONE device-to-host copy, of the rows (it waits for the launch); the combined log-probs stay on the device."""
+    from . import metrics
+    if res[1] is None:
+        raise ValueError("ensemble_download: the call formed no diagnostics (diagnostics=False)")
+    rows = res[1].cpu().numpy()
+    got = metrics.uncertainty_summary(rows)
+    if per_row:
+        got["per_row"] = rows
+    return got
+
+
 class ParamGroupTable:
     """Device copy of a per-parameter-group segment table over an arena of ``n`` floats (``slnlp_param_groups_create``):
     segment s covers floats [seg_begin[s], seg_begin[s + 1]) -- the last one to ``n`` -- in group seg_group[s]; group g decays
