@@ -538,6 +538,33 @@ int slnlp_bootstrap_scores(const int64_t* y, const int32_t* pred, const int32_t*
 int slnlp_ensemble_rows(const float* const* logp, const int64_t* ld, const double* const* beta_dev, const double* weights,
                         int K, int64_t N, int64_t V, int mode, float* out, int64_t ld_out, double* rows, void* stream);
 
+/* ------------------------------------------------------------ ranking metrics --
+ * What the one-vs-rest ROC AUC and the average precision of every class are functions of (slnlp/metrics.py forms the scores on
+ * the host: auc_macro, auc_weighted, ap_macro, ap_weighted; NeuralNetClassifier.ranking).  logp float32 [N, ld], V <= ld columns
+ * used; y int64 [N].  For class c the rows with y = c are its positives (P_c), every other row with a label in [0, V) is a
+ * negative (Q_c); the score of row j for class c is z[j, c], the float32 log-prob as stored: ties are ties of the float32 values
+ * (slnlp_score_rows' rank convention), -0.0 equals +0.0, -inf is an ordinary value.  Per row i, with c = y_i and x = z[i, c]:
+ *   gt_neg = #{negatives j: z[j, c] > x}   eq_neg = #{negatives j: z[j, c] == x}   ge_pos = #{positives j: z[j, c] >= x} (i itself counts)
+ * rows  int32 [N, 4] or null: (gt_neg, eq_neg, ge_pos, code).  code 0: counted; -1: a label outside [0, V) (looked at first, never
+ *       used as an index; neither a positive nor a negative of any class; the counts are 0); -2: column c holds a NaN in some row
+ *       with a valid label, which leaves class c undefined (the counts are 0).
+ * table double [V + 1, 4]: row c < V = (P_c, the NaN entries of column c over the rows with a valid label,
+ *       sum_{i in c} (2 (Q_c - gt_neg) - eq_neg), sum_{i in c} ge_pos / (ge_pos + gt_neg + eq_neg)); the two sums are 0 for a class
+ *       with a NaN; row V = (rows with a valid label, rows with a bad label, 0, 0).  The third column is an exact integer
+ *       (N <= SLNLP_RANK_MAX_ROWS keeps 2 N^2 below 2^53).  AUC_c = table[c][2] / (2 P_c Q_c): Mann-Whitney with half credit for
+ *       ties, sklearn's trapezoid.  AP_c = table[c][3] / P_c: sklearn's step-wise average_precision_score (tied positives share a
+ *       threshold and contribute the same term).  Both are undefined for P_c = 0, Q_c = 0 or a NaN in the column.
+ * One launch, one block of 256 threads per class: the class's positives are compacted into LDS in ascending row order (ballots,
+ * no cursor), sorted there, and the column is streamed against them with two binary searches per row and integer LDS atomics on
+ * three histograms; suffix sums give the counts.  More than SLNLP_RANK_CHUNK positives: the same per chunk.  The sums are formed
+ * in a fixed order (sorted position, fixed tree, chunks ascending) and no global atomics are used: the result is a function of
+ * the arguments alone.  Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null logp, y or table; N
+ * outside 1..SLNLP_RANK_MAX_ROWS; V outside 1..INT32_MAX - 1; ld < V; a misaligned pointer (logp 4 bytes, y 8, rows 16, table
+ * 32); an output overlapping an input or the other output. */
+#define SLNLP_RANK_CHUNK 2048
+#define SLNLP_RANK_MAX_ROWS 67108863    /* 2^26 - 1 */
+int slnlp_ranking_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int32_t* rows, double* table, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

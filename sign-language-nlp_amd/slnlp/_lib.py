@@ -134,6 +134,7 @@ SIGNATURES = {
     "slnlp_confusion_pairs": (i32, [vp, i64, i32, vp, vp, i64, vp]),
     "slnlp_bootstrap_scores": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, C.c_uint64, vp, vp, vp]),
     "slnlp_ensemble_rows": (i32, [vp, vp, vp, vp, i32, i64, i64, i32, vp, i64, vp, vp]),
+    "slnlp_ranking_rows": (i32, [vp, i64, vp, i64, i64, vp, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -270,6 +271,8 @@ UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
 CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_*
 REL_MAX_BINS = 64                               # SLNLP_REL_MAX_BINS
+RANK_CHUNK = 2048                               # SLNLP_RANK_CHUNK
+RANK_MAX_ROWS = 67108863                        # SLNLP_RANK_MAX_ROWS
 TOPK_MAX = 64                                   # SLNLP_TOPK_MAX
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX

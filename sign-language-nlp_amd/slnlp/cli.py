@@ -43,7 +43,14 @@ the refit (member 0) into a ``slnlp.ensemble.VotingEnsemble``, and write, next t
                                    paired bootstrap of the single refit against the ensemble (with the ``confidence_intervals``
                                    options when that key is present, else its defaults)
 
-Without the three keys the workdir holds exactly the files listed above.
+A top-level ``ranking: {}`` (no options yet) makes rank 0 write, next to test_output.json, what ``NeuralNetClassifier.ranking``
+finds on the test split:
+
+    test_ranking.json              auc_macro, auc_weighted, ap_macro, ap_weighted and classes_scored
+    test_ranking_classes.csv       class, name, support, one-vs-rest ROC AUC and average precision per class (an empty cell
+                                   for a class without a positive or a negative test row)
+
+Without the four keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -57,7 +64,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble")
+             "ensemble", "ranking")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -242,6 +249,40 @@ def save_error_analysis(est, test_data, opts, workdir):
     return res
 
 
+RANKING_KEYS = ()                                                               # no options yet
+
+
+def ranking_options(setting):
+    """The ``ranking`` key -- {} -- or None when the key is absent.  Anything but a dict without keys raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"ranking={setting!r}: expected a dict with keys among {RANKING_KEYS}")
+    unknown = sorted(set(setting) - set(RANKING_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"ranking: unknown keys {unknown} (known: {RANKING_KEYS})")
+    return {}
+
+
+def save_ranking(est, test_data, opts, workdir):
+    """``est.ranking(test_data)`` as ``test_ranking.json`` (the four scores and ``classes_scored``) and
+    ``test_ranking_classes.csv`` (class, name, support, auc, ap) in ``workdir``; floats are written with ``repr`` (they read back
+    bit for bit), a NaN as an empty cell.  Returns the result."""
+    from . import metrics
+    names = test_data.vocab_y.itos if getattr(test_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    cell = lambda v: "" if v != v else repr(float(v))
+    res = est.ranking(test_data, **opts)
+    save_json({**{k: float(res[k]) for k in metrics.RANKING}, "classes_scored": int(res["classes_scored"])},
+              os.path.join(workdir, "test_ranking.json"))
+    with open(os.path.join(workdir, "test_ranking_classes.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["class", "name", "support", "auc", "ap"])
+        for i, c in enumerate(res["classes"]):
+            w.writerow([int(c), name(c), int(res["support"][i]), cell(res["auc"][i]), cell(res["ap"][i])])
+    return res
+
+
 INTERVAL_DEFAULTS = {"replicates": 1000, "level": 0.95, "seed": 0}
 INTERVAL_MAX_REPLICATES = 65536                                                 # SLNLP_BOOT_MAX_REPLICATES
 
@@ -374,6 +415,7 @@ def run(args):
     analysis = error_analysis_options(args.get("error_analysis"))               # a bad key fails before the grid search, not after
     intervals = confidence_interval_options(args.get("confidence_intervals"))
     ensemble = ensemble_options(args.get("ensemble"))
+    ranking = ranking_options(args.get("ranking"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -415,6 +457,8 @@ def run(args):
             save_error_analysis(est, test_data, analysis, workdir)
         if intervals is not None:
             save_intervals(est, test_data, intervals, metrics, workdir)
+        if ranking is not None:
+            save_ranking(est, test_data, ranking, workdir)
         if ensemble is not None:
             save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch

@@ -4,7 +4,7 @@
 member runs its own forward passes (``NeuralNetClassifier._forward_logp``: under its gate, on its stream, with its averaged
 weights where it predicts with them), ONE ``ops.ensemble_rows`` launch combines the members' device log-probs, each at its own
 temperature, into one set of float32 log-probs, and everything that judges one fit's log-probs -- ``predict_proba``,
-``reliability``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare`` -- then works on the ensemble through the
+``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare`` -- then works on the ensemble through the
 same ``_forward_logp(ds, then)`` hook: those methods are ``NeuralNetClassifier``'s own functions, bound here, not copies.  The
 same launch gives, per sample, how much the members disagree (``uncertainty``): the entropy of the mixture, the expected entropy
 of a member and their difference, the mutual information.  Nothing is averaged on the host and no torch arithmetic runs on the
@@ -98,6 +98,7 @@ class VotingEnsemble(ClassifierMixin, BaseEstimator):
     predict = NeuralNetClassifier.predict
     score = NeuralNetClassifier.score
     reliability = NeuralNetClassifier.reliability
+    ranking = NeuralNetClassifier.ranking
     predict_topk = NeuralNetClassifier.predict_topk
     error_analysis = NeuralNetClassifier.error_analysis
     _interval_request = NeuralNetClassifier._interval_request

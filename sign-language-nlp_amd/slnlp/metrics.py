@@ -18,12 +18,25 @@ formed on the host with the arithmetic sklearn uses, so the numbers are the ones
   distinct bin count and only when such a name is asked for.  The bins are (b / B, (b + 1) / B], closed on the right (Guo et
   al. 2017).  sklearn has no scorer of these names (its ``neg_brier_score`` is binary only).
 
-Log-probs on the CPU are reduced by a numpy expression instead (``reduce_rows``, ``reliability_numpy``); a scorer name outside
-the three families goes through sklearn as before.
+* ``RANKING``: ``auc_macro`` / ``auc_weighted`` (one-vs-rest ROC AUC per class) and ``ap_macro`` / ``ap_weighted`` (average
+  precision per class), averaged over the DEFINED classes -- plainly, or weighted by the class's support -- from
+  ``slnlp_ranking_rows`` (csrc/ranking.hip), one call and only when such a name is asked for.  A class is undefined when it has
+  no positive or no negative row (a fold of a long-tailed label set lacks classes: sklearn's ``roc_auc_ovr`` is NaN or raises
+  there) or when its column holds a NaN; it is left out of both averages, and the score is NaN when no class is defined.
+  Per class the numbers are sklearn's binary ``roc_auc_score`` (Mann-Whitney, half credit for ties) and
+  ``average_precision_score`` (step-wise; tied positives share a threshold).  They are no means over rows and have no
+  bootstrap interval.  ``roc_auc_ovr`` itself stays an sklearn name.
+
+Log-probs on the CPU are reduced by a numpy expression instead (``reduce_rows``, ``reliability_numpy``, ``ranking_numpy``); a
+scorer name outside the four families goes through sklearn as before.
 
 One documented difference: the rank is taken among the float32 LOG-PROBS.  An sklearn scorer fed ``exp(logp)`` can see
 extra ties where two different log-probs round to the same probability, and then orders those classes by index; the
 top-k numbers here are sklearn's on the log-probs themselves (which is what the tests compare with).
+
+The ``RANKING`` numbers follow the same convention: the score of a sample for class c is the float32 LOG-PROB z[:, c] as stored,
+and ties are ties of those float32 values (-0.0 equals +0.0, -inf is an ordinary value).  A ``ScoringWrapper`` of the same name
+ranks ``predict_proba``'s float32 probabilities, where two different log-probs may round to one probability.
 
 Another, of the same kind: the history's ``CALIBRATION`` numbers are taken on the float32 LOG-PROBS, in fp64 (softmax of the row,
 maximum subtracted).  A ``ScoringWrapper`` of the same name is fed ``predict_proba``'s float32 PROBABILITIES, which it
@@ -38,6 +51,7 @@ import torch
 FAST = ("accuracy", "precision_weighted", "recall_weighted", "f1_weighted", "neg_log_loss")
 REDUCED = ("precision_macro", "recall_macro", "f1_macro", "balanced_accuracy", "top_k_accuracy")
 CALIBRATION = ("neg_ece", "neg_mce", "neg_brier")
+RANKING = ("auc_macro", "auc_weighted", "ap_macro", "ap_weighted")
 DEFAULT_BINS, MAX_BINS = 15, 64                             # MAX_BINS: SLNLP_REL_MAX_BINS
 _TOP_K = re.compile(r"top([1-9][0-9]*)_accuracy\Z")
 _ECE_B = re.compile(r"neg_ece([0-9]+)\Z")
@@ -70,10 +84,11 @@ def calibration_metric_of(name):
 
 
 def is_reduced(name):
-    """Whether ``name`` is scored from the device-side reductions: ``FAST``, ``REDUCED``, a ``top<k>_accuracy`` or ``CALIBRATION``
-    (``neg_ece<B>`` included).  Not a pure predicate: a ``neg_ece<B>`` whose B lies outside 1..64 raises ValueError
+    """Whether ``name`` is scored from the device-side reductions: ``FAST``, ``REDUCED``, a ``top<k>_accuracy``, ``CALIBRATION``
+    (``neg_ece<B>`` included) or ``RANKING``.  Not a pure predicate: a ``neg_ece<B>`` whose B lies outside 1..64 raises ValueError
     (``calibration_metric_of``), so that a misspelt bin count fails with its own message wherever the name is first looked at."""
-    return name in FAST or name in REDUCED or top_k_of(name) is not None or calibration_metric_of(name) is not None
+    return (name in FAST or name in REDUCED or name in RANKING or top_k_of(name) is not None
+            or calibration_metric_of(name) is not None)
 
 
 def reduce_epoch(logp, y):
@@ -317,15 +332,118 @@ def calibration_error(y_true, proba, *, kind, bins=None, labels=None):
     return summary[kind]
 
 
-def epoch_scores(names, logp, y, y_host=None, split=None, out=None, rel_out=None):
+def ranking_from_table(table):
+    """The table of ``slnlp_ranking_rows`` (include/slnlp.h), float64 [V + 1, 4] on the host, as a dict.  Per class, with P its
+    positives and Q = (valid rows) - P its negatives: ``auc`` = table[c, 2] / (2 P Q), ``ap`` = table[c, 3] / P, ``support`` = P;
+    a class with P = 0, Q = 0 or a NaN in its column is undefined: NaN in ``auc`` and ``ap``.  ``auc_macro`` / ``ap_macro``: the
+    plain means over the defined classes, ``auc_weighted`` / ``ap_weighted``: weighted by P over the defined classes, all NaN
+    when ``classes_scored`` (their number) is 0.  ``rows``: the rows with a valid label, ``bad_labels``: the others,
+    ``nan_classes``: the classes whose column holds a NaN."""
+    table = np.asarray(table, dtype=np.float64)
+    if table.ndim != 2 or table.shape[0] < 2 or table.shape[1] != 4:
+        raise ValueError(f"ranking_from_table: table has shape {table.shape}, expected [V + 1, 4]")
+    V = table.shape[0] - 1
+    P, nans = table[:V, 0], table[:V, 1]
+    rows, bad = int(table[V, 0]), int(table[V, 1])
+    Q = table[V, 0] - P
+    defined = (P > 0) & (Q > 0) & (nans == 0)
+    auc = np.full(V, np.nan)
+    ap = np.full(V, np.nan)
+    auc[defined] = table[:V, 2][defined] / (2.0 * P[defined] * Q[defined])
+    ap[defined] = table[:V, 3][defined] / P[defined]
+    n = int(defined.sum())
+    nan = float("nan")
+    out = {name: nan for name in RANKING}
+    if n:
+        w = P[defined]
+        out = {"auc_macro": float(auc[defined].sum() / n), "auc_weighted": float((auc[defined] * w).sum() / w.sum()),
+               "ap_macro": float(ap[defined].sum() / n), "ap_weighted": float((ap[defined] * w).sum() / w.sum())}
+    out.update(classes_scored=n, auc=auc, ap=ap, support=P.astype(np.int64), rows=rows, bad_labels=bad,
+               nan_classes=int((nans > 0).sum()))
+    return out
+
+
+def ranking_numpy(scores, y):
+    """(rows int32 [N, 4], table float64 [V + 1, 4]) as ``slnlp_ranking_rows`` defines them, from ``scores`` [N, V] on the host
+    (any float dtype: ties are ties of the values as given) and labels ``y`` [N]: per class one sort of the column and two
+    ``searchsorted`` per group of rows."""
+    z = np.asarray(scores)
+    yy = np.asarray(y).astype(np.int64)
+    if z.ndim != 2 or yy.shape != (z.shape[0],):
+        raise ValueError(f"ranking: scores has shape {z.shape} and y {yy.shape}, expected [N, V] and [N]")
+    N, V = z.shape
+    ok = (yy >= 0) & (yy < V)
+    rows = np.zeros((N, 4), dtype=np.int32)
+    rows[~ok, 3] = -1
+    table = np.zeros((V + 1, 4))
+    nvalid = int(ok.sum())
+    table[V, :2] = (nvalid, N - nvalid)
+    for c in range(V):
+        col = z[ok, c]
+        pos = np.flatnonzero(ok & (yy == c))
+        P = pos.size
+        n_nan = int(np.isnan(col).sum())
+        table[c, :2] = (P, n_nan)
+        if n_nan:
+            rows[pos, 3] = -2
+            continue
+        if P == 0:
+            continue
+        x = z[pos, c]
+        neg = np.sort(col[yy[ok] != c])
+        own = np.sort(x)
+        gt = neg.size - np.searchsorted(neg, x, side="right")
+        eq = np.searchsorted(neg, x, side="right") - np.searchsorted(neg, x, side="left")
+        ge = P - np.searchsorted(own, x, side="left")
+        rows[pos, 0], rows[pos, 1], rows[pos, 2] = gt, eq, ge
+        Q = nvalid - P
+        table[c, 2] = float((2 * (Q - gt.astype(np.int64)) - eq).sum())
+        table[c, 3] = float((ge / (ge + gt + eq).astype(np.float64)).sum())
+    return rows, table
+
+
+def ranking_summary(logp, y, out=None):
+    """``ranking_from_table`` of one set of log-probs: on a GPU one ``ops.ranking_rows`` call without per-row output (``out``:
+    its buffers) and one download of V + 1 rows of four doubles; on the CPU ``ranking_numpy`` of the float32 log-probs."""
+    if logp.is_cuda:
+        from . import ops
+        return ops.ranking_download(ops.ranking_rows(logp if logp.dtype == torch.float32 else logp.float(), y, out=out, per_row=False))
+    return ranking_from_table(ranking_numpy(logp.detach().float().numpy(), y.detach().numpy())[1])
+
+
+def ranking_score(y_true, proba, *, name, labels=None):
+    """The ``RANKING`` score ``name`` of the probabilities ``proba`` [N, V], whose column c stands for class ``labels[c]`` (None:
+    class c) -- what a ``ScoringWrapper`` of that name calls; a 1-D ``proba`` is the second of two columns, as in
+    ``calibration_error``.  Ties are ties of the probabilities as given."""
+    y_true = np.asarray(y_true)
+    proba = np.asarray(proba)
+    if proba.ndim == 1:
+        proba = np.stack([1.0 - proba.astype(np.float64), proba.astype(np.float64)], axis=1)
+    if labels is not None:
+        labels = np.asarray(labels)
+        if len(labels) != proba.shape[1]:
+            raise ValueError(f"{name}: {len(labels)} labels for {proba.shape[1]} probability columns")
+        order = np.argsort(labels, kind="stable")
+        pos = np.clip(np.searchsorted(labels[order], y_true), 0, len(labels) - 1)
+        y_true = np.where(labels[order][pos] == y_true, order[pos], -1)
+    summary = ranking_from_table(ranking_numpy(proba, y_true)[1])
+    if summary["bad_labels"] > 0:
+        raise ValueError(f"{name}: {summary['bad_labels']} of {len(y_true)} labels lie outside the {proba.shape[1]} classes of the "
+                         "probabilities")
+    return summary[name]
+
+
+def epoch_scores(names, logp, y, y_host=None, split=None, out=None, rel_out=None, rank_out=None):
     """{name: score} for the names among ``names`` that ``is_reduced``; ``logp`` / ``y`` are device tensors of one epoch.
     ``split`` names the data in the error a label outside the columns raises; ``out``: ``reduce_rows``' device buffers;
-    ``rel_out``: {bins: ``ops.reliability_rows``' device buffers}, one entry per bin count the ``CALIBRATION`` names ask for."""
+    ``rel_out``: {bins: ``ops.reliability_rows``' device buffers}, one entry per bin count the ``CALIBRATION`` names ask for;
+    ``rank_out``: ``ops.ranking_rows``' device buffers (its rows may be None), used when a ``RANKING`` name is asked for."""
     names = [n for n in names if is_reduced(n)]
     if not names:
         return {}
     cal = [n for n in names if calibration_metric_of(n) is not None]
-    names = [n for n in names if n not in cal]
+    ranking = [n for n in names if n in RANKING]
+    names = [n for n in names if n not in cal and n not in ranking]
 
     def bad_labels(count):
         return ValueError(f"scoring the {split or 'epoch'} data: {int(count)} of {int(logp.shape[0])} labels lie outside the "
@@ -345,6 +463,11 @@ def epoch_scores(names, logp, y, y_host=None, split=None, out=None, rel_out=None
             if summaries[bins]["bad_labels"] > 0:
                 raise bad_labels(summaries[bins]["bad_labels"])
         scores[name] = calibration_score(name, summaries[bins])
+    if ranking:                                             # one call, whatever the number of names; uncalibrated like the rest
+        summary = ranking_summary(logp, y, out=rank_out)
+        if summary["bad_labels"] > 0:
+            raise bad_labels(summary["bad_labels"])
+        scores.update({name: summary[name] for name in ranking})
     return scores
 
 

@@ -29,7 +29,8 @@ semantics:
   the device (csrc/calibration.hip), and ``predict_proba`` returns ``softmax(z / T)``; ``predict`` and the history never change.
 
 Beyond skorch: ``reliability`` (ECE / MCE / Brier, csrc/reliability.hip), ``predict_topk`` and ``error_analysis`` (top-k classes,
-confusion matrix, most-confused pairs, per-class report: csrc/confusion.hip) reduce a fitted estimator's log-probs on the device.
+confusion matrix, most-confused pairs, per-class report: csrc/confusion.hip) and ``ranking`` (one-vs-rest ROC AUC and average
+precision per class, csrc/ranking.hip) reduce a fitted estimator's log-probs on the device.
 
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
@@ -345,6 +346,8 @@ class ScoringWrapper:
     k -- is told the label set like log-loss.  The calibration family (``metrics.CALIBRATION``: ``neg_ece``, ``neg_ece<B>``,
     ``neg_mce``, ``neg_brier``), which sklearn does not have, is a ``make_scorer`` of ``metrics.calibration_error`` on
     ``predict_proba`` with ``greater_is_better=False`` -- sign -1, like ``neg_log_loss`` -- and is told the label set too.
+    The ranking family (``metrics.RANKING``: ``auc_macro``, ``auc_weighted``, ``ap_macro``, ``ap_weighted``) is a ``make_scorer``
+    of ``metrics.ranking_score`` on ``predict_proba``, greater is better, told the label set as well.
     Exposes ``score`` (the name) and ``greater_is_better`` -- what the reference's EpochScoring and GridSearchCV wiring read
     (helper.py:255-268, 183-194)."""
 
@@ -358,6 +361,9 @@ class ScoringWrapper:
         cal = metrics.calibration_metric_of(score_func)
         if cal is not None:
             base = make_scorer(metrics.calibration_error, greater_is_better=False, response_method="predict_proba", kind=cal[0], bins=cal[1])
+            extra = {"labels": labels}
+        elif score_func in metrics.RANKING:
+            base = make_scorer(metrics.ranking_score, greater_is_better=True, response_method="predict_proba", name=score_func)
             extra = {"labels": labels}
         elif k is not None and score_func != "top_k_accuracy":
             # what sklearn's own "top_k_accuracy" scorer is, with the name's k
@@ -375,7 +381,7 @@ class ScoringWrapper:
     def needs_labels(score_func):
         """Whether the scorer must be told the full label set: a test fold may miss classes the probability columns stand for."""
         return (score_func == "neg_log_loss" or metrics.top_k_of(score_func) is not None
-                or metrics.calibration_metric_of(score_func) is not None)
+                or metrics.calibration_metric_of(score_func) is not None or score_func in metrics.RANKING)
 
     def __call__(self, estimator, X, y_true, sample_weight=None):
         return self.scorer(estimator, X, y_true, sample_weight)
@@ -420,6 +426,7 @@ class _FitRun:
         self.fast_ok = labels is not None and list(labels) == list(range(len(net.classes_)))
         self._score_out = {}                                 # split -> the reduction's device buffers (ops.score_rows)
         self._rel_out = {}                                   # split -> {bins: ops.reliability_rows' device buffers}
+        self._rank_out = {}                                  # split -> ops.ranking_rows' device buffers (the table alone)
         es, clip, sched = net.early_stopping, net.gradient_clipping, net.lr_scheduler
         self.es = es
         self.max_norm = float(clip["gradient_clip_value"]) if clip and clip.get("gradient_clip_value") else 0.0
@@ -543,8 +550,10 @@ class _FitRun:
             cal = [metrics.calibration_metric_of(n) for n in names]
             self._rel_out[split] = {bins: ops.reliability_buffers(logp.shape[0], bins, logp.device)
                                     for bins in sorted({c[1] or metrics.DEFAULT_BINS for c in cal if c is not None})}
+        if logp.is_cuda and split not in self._rank_out and any(n in metrics.RANKING for n in names):
+            self._rank_out[split] = ops.ranking_buffers(logp.shape[0], logp.shape[1], logp.device, per_row=False)
         return metrics.epoch_scores(names, logp, y_dev, y_host, split=split, out=self._score_out.get(split),
-                                    rel_out=self._rel_out.get(split))
+                                    rel_out=self._rel_out.get(split), rank_out=self._rank_out.get(split))
 
     def end_epoch(self, tr, va):
         """tr / va: (sample-weighted mean loss, log-probs [n, V] on the device, [(batch loss, batch size)]) of the epoch's
@@ -1122,6 +1131,36 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         if res["bad_labels"] > 0:
             raise ValueError(f"reliability: {res['bad_labels']} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the "
                              "log-probs")
+        res["temperature"] = float(self.temperature_) if use else 1.0
+        return res
+
+    def ranking(self, X, y=None, calibrated=True):
+        """Ranking metrics of this fit's predictions on ``X`` (``y``: the labels; None: the dataset's): per class the one-vs-rest
+        ROC AUC and the average precision, and their averages over the defined classes, from one ``ops.ranking_rows`` call on the
+        device log-probs of ``predict_proba``'s forward passes: ``ops.ranking_download``'s dict -- auc_macro, auc_weighted,
+        ap_macro, ap_weighted, classes_scored, auc / ap / support per class (NaN for a class without a positive or a negative
+        row), rows, bad_labels, nan_classes -- plus ``classes`` (``classes_``) and ``temperature``.  A temperature changes the
+        order of a class's scores ACROSS rows, so a calibrated fit is ranked on its calibrated float32 log-probs
+        (``ops.scale_logp`` first) unless ``calibrated=False``; ``temperature`` is then ``temperature_``, else 1.0."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        ds = self._as_dataset(X)
+        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
+        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
+        if labels is not None and labels.shape != (len(ds),):
+            raise ValueError(f"ranking: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
+
+        def rows(logp, yd):
+            yd = yd if labels is None else labels.to(logp.device)
+            logp = logp if logp.dtype == torch.float32 else logp.float()
+            if use:
+                ops.scale_logp(logp, self._cal_state, out=logp)      # in place: the ranks are those of the calibrated log-probs
+            return ops.ranking_rows(logp, yd.contiguous(), per_row=False)
+        res = ops.ranking_download(self._forward_logp(ds, rows))
+        if res["bad_labels"] > 0:
+            raise ValueError(f"ranking: {res['bad_labels']} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the "
+                             "log-probs")
+        res["classes"] = self.classes_
         res["temperature"] = float(self.temperature_) if use else 1.0
         return res
 

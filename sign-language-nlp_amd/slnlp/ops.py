@@ -559,6 +559,55 @@ def reliability_download(out):
     return metrics.reliability_from_table(out[1].cpu().numpy())
 
 
+def ranking_buffers(N, V, device, per_row=True):
+    """The two output tensors of ``ranking_rows`` for an [N, V] set of log-probs -- rows int32 [N, 4] (None with
+    ``per_row=False``), table float64 [V + 1, 4] -- as slices of ONE allocation: the table comes first, so it is 32-byte aligned
+    and ``ranking_download`` copies it alone."""
+    flat = torch.empty(4 * (V + 1) + (2 * N if per_row else 0), dtype=torch.float64, device=device)
+    table = flat[:4 * (V + 1)].view(V + 1, 4)
+    return (flat[4 * (V + 1):].view(torch.int32).view(N, 4) if per_row else None), table
+
+
+def ranking_rows(logp, y, out=None, per_row=True):
+    """What the one-vs-rest ROC AUC and average precision of every class are functions of, from ``logp`` float32 [N, V] (rows may
+    be padded: ``stride(0) >= V``) and the labels ``y`` int64 [N] (``slnlp_ranking_rows``, include/slnlp.h): ``(rows int32 [N, 4],
+    table float64 [V + 1, 4])``, device tensors; rows = (negatives above, negatives tied, positives at or above, code) per
+    sample, None with ``per_row=False`` (the kernel then writes the table alone).  ``out``: such a pair to fill (its rows may be
+    None, whatever ``per_row`` says).  Runs on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("ranking_rows", logp)
+    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"ranking_rows: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    if N > _lib.RANK_MAX_ROWS:
+        raise ValueError(f"ranking_rows: {N} rows, the pair counts are exact for at most {_lib.RANK_MAX_ROWS}")
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = ranking_buffers(N, V, logp.device, per_row=bool(per_row))
+        rows, table = out
+        ok = table.device == logp.device and table.dtype == torch.float64 and tuple(table.shape) == (V + 1, 4) and table.is_contiguous()
+        if rows is not None:
+            ok = ok and rows.device == logp.device and rows.dtype == torch.int32 and tuple(rows.shape) == (N, 4) and rows.is_contiguous()
+        if not ok:
+            raise ValueError(f"ranking_rows: out must be (int32 [{N}, 4] or None, float64 [{V + 1}, 4]) on {logp.device}")
+        check(load().slnlp_ranking_rows(ptr(logp), ld, ptr(y), N, V, ptr(rows) if rows is not None else None, ptr(table), stream_ptr()),
+              "ranking_rows")
+    return out
+
+
+def ranking_download(out, per_row=False):
+    """``ranking_rows``' result as a dict (``metrics.ranking_from_table`` forms it on the host, in fp64, from the table):
+    {auc_macro, auc_weighted, ap_macro, ap_weighted, classes_scored, auc [V], ap [V], support [V], rows, bad_labels, nan_classes}.
+    ONE device-to-host copy, of the table (it waits for the launch); ``per_row=True`` adds ``per_row``, the int32 [N, 4] rows (a
+    second copy)."""
+    from . import metrics
+    res = metrics.ranking_from_table(out[1].cpu().numpy())
+    if per_row:
+        if out[0] is None:
+            raise ValueError("ranking_download: per_row=True, but the call formed no rows (ranking_rows(per_row=False))")
+        res["per_row"] = out[0].cpu().numpy()
+    return res
+
+
 def _int_in(what, name, value, lo, hi):
     if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
         raise ValueError(f"{what}: {name}={value!r}, expected an integer in {lo}..{hi}")
