@@ -565,6 +565,65 @@ int slnlp_ensemble_rows(const float* const* logp, const int64_t* ld, const doubl
 #define SLNLP_RANK_MAX_ROWS 67108863    /* 2^26 - 1 */
 int slnlp_ranking_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int32_t* rows, double* table, void* stream);
 
+/* -------------------------------------------------- conformal prediction sets --
+ * Split conformal prediction on a set of log-probs (NeuralNetClassifier.conformalize / predict_set / coverage; slnlp/metrics.py's
+ * conformal_report): per sample the set of classes that holds the true one with probability 1 - alpha, given a threshold that
+ * is an order statistic of the scores of held-out rows.  tests/conformal_ref.py restates everything below in numpy.
+ *
+ * Probabilities.  logp float32 [N, ld], V <= ld columns used; beta = beta_dev ? beta_dev[0] : 1.  p_c = exp(beta z_c - a) / s0
+ * with slnlp_topk_rows' / slnlp_reliability_rows' fp64 decomposition (zmax the float32 row maximum, a = beta zmax, the columns
+ * at the maximum counted, the others summed, s0 = 1 + rest): p of the arg-max is slnlp_reliability_rows' conf bit for bit.
+ * Order.  Within a row the classes stand in the arg-max's total order: larger value first, equal values by ascending column;
+ * -0.0 equals +0.0; -inf is an ordinary value with p = 0.  rank(c) is 1-based in that order; before(c) is the sum of p over the
+ * classes in front of c, added in ascending rank order in fp64 (a lane adds its contiguous run of ranks, the 64 lane totals are
+ * added from lane 0 upwards): a fixed order that depends on neither grid nor timing.
+ * Score of class c.  method SLNLP_CONFORMAL_LAC: s(c) = 1 - p_c.  method SLNLP_CONFORMAL_APS: s(c) = before(c) + u p_c +
+ * lam max(0, rank(c) - k_reg); lam = 0 is APS (Romano, Sesia, Candes 2020), lam > 0 RAPS (Angelopoulos et al. 2021).
+ * u = 1 unless `randomized`; then ONE u per row, shared by its classes: u = (w + 0.5) 2^-32 with w word 0 of the Threefry
+ * call at counter (row, draw, SLNLP_CONFORMAL_STAGE, 0) under key (seed low word, seed high word, 0, 0), the 12 rounds of the
+ * dropout masks -- a counter no other draw of the library uses with that key (slnlp_balanced_order: stages 0, 1, 2; the
+ * augmentation: the timestep; the bootstrap: SLNLP_BOOT_STAGE).  `draw` tells calibration draws from prediction draws.
+ * Codes.  0 an ordinary row.  -2 a row that holds a NaN or whose maximum is not finite (looked at first): no sort, size 0,
+ * every set word 0, rank 0, score NaN.  -1: y given and the label outside [0, V) (never used as an index): the set and its
+ * size are formed, rank and covered are 0, the score is NaN.
+ *
+ * slnlp_conformal_rows.  y int64 [N] or null.  qhat_dev: null, or a device double read on the device (state[0] of
+ * slnlp_conformal_quantile: no host round trip between calibrating and predicting); the set of a row is {c : s(c) <= qhat}
+ * and may be empty (LAC, or deterministic APS when the top probability exceeds qhat): reported, not patched.
+ *   score double [N] or null (needs y): s(y_i), NaN for a code other than 0
+ *   rows  int32 [N, 4] or null: (set size, rank(y_i) or 0 without y, covered 0 / 1, code); size and covered 0 without qhat_dev
+ *   sets  uint32 [N, W] or null (needs qhat_dev), W = ceil(V / 32): bit c & 31 of word c >> 5 is set iff c is in the set; the
+ *         padding bits of the last word are 0
+ * One launch, one wave per row: the row is sorted in LDS as 64-bit keys (~order key of the value << 32 | column, ascending)
+ * by one bitonic network over the next power of two >= max(V, 64); every lane then owns a contiguous run of ranks, decodes
+ * the values, forms p, before and the scores and sets its bits in an LDS mask with integer ORs; the words leave in whole
+ * stores.  No global atomics: the result is a function of the arguments alone.
+ *
+ * slnlp_conformal_quantile.  Over the n rows with code 0 (rows[i][3]): k = ceil((double)(n + 1) * (1.0 - alpha)) in fp64 and
+ * qhat the k-th smallest score, +inf when k > n (n = 0 included).  state double [4] = (qhat, n, k, rows with a code other than
+ * 0).  One block: an exact radix select over order-preserving uint64 keys of the scores, 8 passes over 256-bin integer
+ * histograms in LDS (correct, not fast, for large N).
+ *
+ * slnlp_conformal_summary.  table int64 [V + 1, 4], zeroed by the call on the stream; over the rows with code 0 whose label
+ * lies in [0, V): row c < V, columns 0..2 = (rows of class c, covered rows, sum of their set sizes); column 3 of row s = the
+ * rows whose set has size s, s = 0..V; table[V][0] = every other row.  Integer atomics.  Two launches.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null logp / score and rows of the quantile /
+ * rows, y and table of the summary / state; V outside 1..SLNLP_CONFORMAL_MAX_V; ld < V; N outside 1..INT32_MAX; alpha outside
+ * (0, 1); lam negative or not finite; k_reg < 0; an unknown method; score without y; sets without qhat_dev; a misaligned
+ * pointer (logp, sets 4 bytes; y, beta_dev, qhat_dev, score 8; rows 16; state, table 32); an output overlapping an input or
+ * another output. */
+#define SLNLP_CONFORMAL_MAX_V 1024
+#define SLNLP_CONFORMAL_LAC 0
+#define SLNLP_CONFORMAL_APS 1
+#define SLNLP_CONFORMAL_STAGE 0x636f6e66u   /* the draw's counter word 2 ("conf") */
+#define SLNLP_CONFORMAL_STATE_BYTES 32      /* double[4] */
+int slnlp_conformal_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, const double* beta_dev, int method,
+                         double lam, int k_reg, int randomized, uint64_t seed, uint32_t draw, const double* qhat_dev, double* score,
+                         int32_t* rows, uint32_t* sets, void* stream);
+int slnlp_conformal_quantile(const double* score, const int32_t* rows, int64_t N, double alpha, double* state, void* stream);
+int slnlp_conformal_summary(const int32_t* rows, const int64_t* y, int64_t N, int64_t V, int64_t* table, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

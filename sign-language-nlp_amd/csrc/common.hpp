@@ -340,6 +340,12 @@ __device__ __forceinline__ bool score_beats(float x, int j, float bv, int bi) {
     if (xn || bn) return xn && (!bn || j < bi);
     return x > bv || (x == bv && j < bi);
 }
+// float -> uint32 with the floats' order; -0.0 and +0.0 share a key.  No NaN comes here (ranking.hip, conformal.hip).
+__device__ __forceinline__ unsigned rank_key(float x) {
+    if (x == 0.0f) x = 0.0f;
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 template <int CTRL>
 __device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
 template <int CTRL>

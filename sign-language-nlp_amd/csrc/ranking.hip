@@ -43,13 +43,6 @@ static_assert(RANK_PER_THREAD * 256 == RANK_CHUNK && (RANK_CHUNK & (RANK_CHUNK -
 constexpr unsigned RANK_KEY_NAN = 0xFFFFFFFEu;  // a positive whose own value is a NaN: behind every real key (+inf is 0xFF800000)
 constexpr unsigned RANK_KEY_PAD = 0xFFFFFFFFu;  // the sort's padding
 
-// float -> uint32 with the floats' order; -0.0 and +0.0 share a key.  No NaN comes here.
-__device__ __forceinline__ unsigned rank_key(float x) {
-    if (x == 0.0f) x = 0.0f;
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
                                                   int* __restrict__ rows, double* __restrict__ table) {
     __shared__ unsigned keys[RANK_CHUNK];

@@ -135,6 +135,9 @@ SIGNATURES = {
     "slnlp_bootstrap_scores": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, C.c_uint64, vp, vp, vp]),
     "slnlp_ensemble_rows": (i32, [vp, vp, vp, vp, i32, i64, i64, i32, vp, i64, vp, vp]),
     "slnlp_ranking_rows": (i32, [vp, i64, vp, i64, i64, vp, vp, vp]),
+    "slnlp_conformal_rows": (i32, [vp, i64, vp, i64, i64, vp, i32, C.c_double, i32, i32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]),
+    "slnlp_conformal_quantile": (i32, [vp, vp, i64, C.c_double, vp, vp]),
+    "slnlp_conformal_summary": (i32, [vp, vp, i64, i64, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -274,6 +277,9 @@ REL_MAX_BINS = 64                               # SLNLP_REL_MAX_BINS
 RANK_CHUNK = 2048                               # SLNLP_RANK_CHUNK
 RANK_MAX_ROWS = 67108863                        # SLNLP_RANK_MAX_ROWS
 TOPK_MAX = 64                                   # SLNLP_TOPK_MAX
+CONFORMAL_MAX_V = 1024                          # SLNLP_CONFORMAL_MAX_V
+CONFORMAL_METHODS = {"lac": 0, "aps": 1}        # SLNLP_CONFORMAL_LAC / _APS
+CONFORMAL_STAGE = 0x636F6E66                    # SLNLP_CONFORMAL_STAGE
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

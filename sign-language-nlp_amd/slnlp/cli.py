@@ -50,7 +50,16 @@ finds on the test split:
     test_ranking_classes.csv       class, name, support, one-vs-rest ROC AUC and average precision per class (an empty cell
                                    for a class without a positive or a negative test row)
 
-Without the four keys the workdir holds exactly the files listed above.
+A top-level ``conformal: {alpha: 0.1, method: aps, randomized: true, lam: 0.0, k_reg: 0, seed: 0}`` (all optional, these defaults;
+``method``: lac or aps, ``lam`` > 0 makes it RAPS) goes to the estimator as it is (every fit takes its threshold on its valid
+split, slnlp/net.py) and makes rank 0 write, next to test_output.json, what the refit's ``coverage`` finds on the test split:
+
+    test_conformal.json            coverage, mean_size, median_size, empty_rate, singleton_rate, worst_class_coverage, rows,
+                                   excluded, and the threshold: alpha, qhat, n, k
+    test_conformal_classes.csv     class, name, support, coverage and mean set size per class (an empty cell for a class
+                                   without a test row)
+
+Without the five keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -64,7 +73,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking")
+             "ensemble", "ranking", "conformal")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -144,7 +153,7 @@ def build_net_params(args, dataset, device):
          "scoring": args.get("scoring"), "early_stopping": args.get("early_stopping"),
          "gradient_clipping": args.get("gradient_clipping"), "lr_scheduler": args.get("lr_scheduler"),
          "checkpoint_dir": args.get("workdir") or None}
-    for k in ("lr", "max_epochs", "batch_size", "verbose", "calibration"):     # (calibration: {method: temperature}, slnlp/net.py)
+    for k in ("lr", "max_epochs", "batch_size", "verbose", "calibration", "conformal"):     # (calibration: {method: temperature}, conformal: {alpha: ...}, slnlp/net.py)
         if args.get(k) is not None:
             p[k] = args[k]
     if isinstance(p.get("scoring"), str):
@@ -283,6 +292,28 @@ def save_ranking(est, test_data, opts, workdir):
     return res
 
 
+CONFORMAL_SCALARS = ("coverage", "mean_size", "median_size", "empty_rate", "singleton_rate", "worst_class_coverage", "rows", "excluded")
+
+
+def save_conformal(est, test_data, workdir):
+    """``est.coverage(test_data)`` as ``test_conformal.json`` (the report's scalars, alpha, qhat, n, k) and
+    ``test_conformal_classes.csv`` (class, name, support, coverage, mean_size) in ``workdir``; floats are written with ``repr``, a
+    NaN as an empty cell.  Returns the result."""
+    names = test_data.vocab_y.itos if getattr(test_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    cell = lambda v: "" if v != v else repr(float(v))
+    res = est.coverage(test_data)
+    out = {k: (int(res[k]) if k in ("median_size", "rows", "excluded") and res[k] == res[k] else float(res[k])) for k in CONFORMAL_SCALARS}
+    out.update(alpha=float(res["alpha"]), qhat=float(res["qhat"]), n=int(res["calibration_rows"]), k=int(res["k"]))
+    save_json(out, os.path.join(workdir, "test_conformal.json"))
+    with open(os.path.join(workdir, "test_conformal_classes.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["class", "name", "support", "coverage", "mean_size"])
+        for i, c in enumerate(res["classes"]):
+            w.writerow([int(c), name(c), int(res["support"][i]), cell(res["class_coverage"][i]), cell(res["class_mean_size"][i])])
+    return res
+
+
 INTERVAL_DEFAULTS = {"replicates": 1000, "level": 0.95, "seed": 0}
 INTERVAL_MAX_REPLICATES = 65536                                                 # SLNLP_BOOT_MAX_REPLICATES
 
@@ -394,7 +425,7 @@ def run(args):
 
     from . import grid as G
     from .balance import balance_dataset
-    from .net import NeuralNetClassifier, ScoringWrapper
+    from .net import NeuralNetClassifier, ScoringWrapper, conformal_options
 
     seed = int(args.get("seed", 1))
     torch.manual_seed(seed); random.seed(seed); np.random.seed(seed)            # helper.setup_seed
@@ -416,6 +447,7 @@ def run(args):
     intervals = confidence_interval_options(args.get("confidence_intervals"))
     ensemble = ensemble_options(args.get("ensemble"))
     ranking = ranking_options(args.get("ranking"))
+    conformal = conformal_options(args.get("conformal"))                         # (the estimator's own check: slnlp/net.py)
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -459,6 +491,8 @@ def run(args):
             save_intervals(est, test_data, intervals, metrics, workdir)
         if ranking is not None:
             save_ranking(est, test_data, ranking, workdir)
+        if conformal is not None:
+            save_conformal(est, test_data, workdir)
         if ensemble is not None:
             save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch

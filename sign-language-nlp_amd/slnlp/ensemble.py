@@ -4,7 +4,8 @@
 member runs its own forward passes (``NeuralNetClassifier._forward_logp``: under its gate, on its stream, with its averaged
 weights where it predicts with them), ONE ``ops.ensemble_rows`` launch combines the members' device log-probs, each at its own
 temperature, into one set of float32 log-probs, and everything that judges one fit's log-probs -- ``predict_proba``,
-``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare`` -- then works on the ensemble through the
+``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare``, ``conformalize``, ``predict_set``,
+``coverage`` -- then works on the ensemble through the
 same ``_forward_logp(ds, then)`` hook: those methods are ``NeuralNetClassifier``'s own functions, bound here, not copies.  The
 same launch gives, per sample, how much the members disagree (``uncertainty``): the entropy of the mixture, the expected entropy
 of a member and their difference, the mutual information.  Nothing is averaged on the host and no torch arithmetic runs on the
@@ -105,6 +106,13 @@ class VotingEnsemble(ClassifierMixin, BaseEstimator):
     _bootstrap = NeuralNetClassifier._bootstrap
     score_interval = NeuralNetClassifier.score_interval
     compare = NeuralNetClassifier.compare
+    # conformal sets of the ensemble's log-probs: the threshold is the ensemble's own (``conformal_``), taken by ``conformalize``
+    _conformal_calibrate = NeuralNetClassifier._conformal_calibrate
+    _conformal_rows = NeuralNetClassifier._conformal_rows
+    _set_conformal = NeuralNetClassifier._set_conformal
+    conformalize = NeuralNetClassifier.conformalize
+    predict_set = NeuralNetClassifier.predict_set
+    coverage = NeuralNetClassifier.coverage
 
     def uncertainty(self, X, per_row=False):
         """How much the members disagree on ``X``: ``metrics.uncertainty_summary`` of ``ops.ensemble_rows``' per-row terms --

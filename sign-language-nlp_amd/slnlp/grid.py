@@ -85,10 +85,11 @@ def build_tasks(param_grid, y, cv, seq_len=48, defaults=None):
 # schedule is host work per epoch, and per batch a device table per fit that the step's gather launch reads: slnlp/schedule.py;
 # a shuffled visit order is such a table too: slnlp/sampler.py -- iterator_train__drop_last changes the number of steps and stays
 # shape-defining; iterator_train__augment refills a fit's own train buffers between epochs, outside the group's launches;
-# calibration is fitted per fit after the group's last epoch and applied per fit to the predictions: slnlp/lockstep.py)
+# calibration is fitted per fit after the group's last epoch and applied per fit to the predictions, and so is the conformal
+# threshold: slnlp/lockstep.py)
 SHAPE_KEYS_EXCLUDED = ("lr", "module__dropout", "criterion__label_smoothing", "optimizer__weight_decay", "optimizer__dampening",
                        "optimizer__nesterov", "lr_scheduler", "iterator_train__shuffle", "optimizer__param_groups",
-                       "iterator_train__augment", "calibration")
+                       "iterator_train__augment", "calibration", "conformal")
 
 
 def estimate_fit_bytes(params, seq_len, defaults=None, lockstep=1):

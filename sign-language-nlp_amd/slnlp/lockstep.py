@@ -249,25 +249,36 @@ def _eval_pass(nets, data, bs):
 
 def _calibrate_lockstep(nets, runs, stream):
     """``NeuralNetClassifier._calibrate`` for the fits of a group whose ``calibration`` option is on: one lockstep eval pass over
-    their valid splits, one ``fit_temperature`` per fit on the group's stream, then one sync and the downloads."""
+    their valid splits, one ``fit_temperature`` per fit on the group's stream, then one sync and the downloads.  The fits whose
+    ``conformal`` option is on then take their threshold on the same log-probs, at their temperature (``_conformalize_fit``)."""
     from .net import stream_sync
-    todo = [(n, r) for n, r in zip(nets, runs) if getattr(n, "_cal_opts", None) is not None]
+    on = lambda n, key: getattr(n, key, None) is not None
+    todo = [(n, r) for n, r in zip(nets, runs) if on(n, "_cal_opts") or on(n, "_conf_opts")]
     if not todo:
         return
-    if any(r.va is None for _, r in todo):
+    if any(r.va is None for n, r in todo if on(n, "_cal_opts")):
         raise ValueError("calibration: the fit has no valid split to fit the temperature on (train_split)")
+    if any(r.va is None for _, r in todo):
+        raise ValueError("conformal: the fit has no valid split to take the threshold on (train_split)")
     group, logps = _eval_pass([n for n, _ in todo], [(r.Xva, r.Lva, r.yva) for _, r in todo], todo[0][1].bs)
-    states = [ops.fit_temperature(lp, r.yva) for lp, (_, r) in zip(logps, todo)]
+    states = [ops.fit_temperature(lp, r.yva) if on(n, "_cal_opts") else None for lp, (n, r) in zip(logps, todo)]
+    stream_sync(stream)
+    for (n, _), state in zip(todo, states):
+        if state is not None:
+            n._set_calibration(ops.temperature_download(state), state)
+    # the conformal option, as NeuralNetClassifier._conformalize_fit: after the temperature, on the same log-probs
+    conf = [(n, r, n._conformal_calibrate(lp, r.yva, n._conf_opts, True)) for lp, (n, r) in zip(logps, todo) if on(n, "_conf_opts")]
     stream_sync(stream)
     group.close()
-    for (n, _), state in zip(todo, states):
-        n._set_calibration(ops.temperature_download(state), state)
+    for n, r, (state, use) in conf:
+        n._set_conformal(n._conf_opts, state, use, labels=r.va.y, where="the valid data")
 
 
 def fit_lockstep(nets, datasets):
     """``net.partial_fit(ds)`` for every (net, ds) pair, all fits advancing together.  The nets must be initialised,
     of one shape (lr and dropout rate may differ) and their datasets of one size; fits that stop early (EarlyStopping)
-    leave the group, the others go on.  Fits whose ``calibration`` option is on are calibrated after the last one has ended."""
+    leave the group, the others go on.  Fits whose ``calibration`` / ``conformal`` option is on are calibrated / conformalised after
+    the last one has ended."""
     nets[0]._gate.enter(False)                          # fused fits share the device (slnlp.net: _DeviceGate)
     try:
         return _fit_lockstep_gated(nets, datasets)
@@ -292,6 +303,8 @@ def _fit_lockstep_gated(nets, datasets):
     for n in nets:
         if getattr(n, "_cal_opts", None) is not None:
             n._set_calibration(None)                    # as partial_fit: an earlier fit's temperature does not describe these weights
+        if getattr(n, "_conf_opts", None) is not None:
+            n._set_conformal(None)
     with torch.cuda.stream(stream):
         runs = [_FitRun(n, d) for n, d in zip(nets, datasets)]
     r0 = runs[0]

@@ -363,6 +363,40 @@ def ranking_from_table(table):
     return out
 
 
+def conformal_report(table, state=None, min_support=5):
+    """The table of ``slnlp_conformal_summary`` (include/slnlp.h), int64 [V + 1, 4] on the host, as a dict, over the n rows that
+    were scored: ``coverage`` (the share whose set holds the label), ``mean_size``, ``median_size`` (the lower median),
+    ``empty_rate``, ``singleton_rate``, ``size_hist`` int64 [V + 1]; per class ``support``, ``class_coverage`` and
+    ``class_mean_size`` (NaN for a class without rows); ``worst_class_coverage``: the minimum over the classes with at least
+    ``min_support`` rows (NaN without one); ``rows`` = n and ``excluded``, the rows left out (a NaN row, a label outside the
+    classes).  ``state``: ``slnlp_conformal_quantile``'s four doubles, whose qhat / n / k are passed on as ``qhat``,
+    ``calibration_rows`` and ``k``."""
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[0] < 2 or table.shape[1] != 4:
+        raise ValueError(f"conformal_report: table has shape {table.shape}, expected [V + 1, 4]")
+    if isinstance(min_support, (bool, np.bool_)) or not isinstance(min_support, (int, np.integer)) or min_support < 1:
+        raise ValueError(f"conformal_report: min_support={min_support!r}, expected an integer >= 1")
+    table = table.astype(np.int64)
+    V = table.shape[0] - 1
+    support, covered, sizes = table[:V, 0], table[:V, 1], table[:V, 2]
+    hist = table[:, 3].copy()
+    n = int(support.sum())
+    nan = float("nan")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        class_cov = np.where(support > 0, covered / support, np.nan)
+        class_size = np.where(support > 0, sizes / support, np.nan)
+    enough = support >= min_support
+    out = {"coverage": float(covered.sum() / n) if n else nan, "mean_size": float(sizes.sum() / n) if n else nan,
+           "median_size": int(np.searchsorted(np.cumsum(hist), (n + 1) // 2)) if n else nan,
+           "empty_rate": float(hist[0] / n) if n else nan, "singleton_rate": float(hist[1] / n) if n else nan,
+           "size_hist": hist, "support": support.copy(), "class_coverage": class_cov, "class_mean_size": class_size,
+           "worst_class_coverage": float(class_cov[enough].min()) if enough.any() else nan, "rows": n, "excluded": int(table[V, 0])}
+    if state is not None:
+        state = np.asarray(state, dtype=np.float64)
+        out.update(qhat=float(state[0]), calibration_rows=int(state[1]), k=int(state[2]))
+    return out
+
+
 def ranking_numpy(scores, y):
     """(rows int32 [N, 4], table float64 [V + 1, 4]) as ``slnlp_ranking_rows`` defines them, from ``scores`` [N, V] on the host
     (any float dtype: ties are ties of the values as given) and labels ``y`` [N]: per class one sort of the column and two

@@ -26,16 +26,24 @@ semantics:
 * ``weight_averaging={...}``: a running average of the weights (SWA / EMA, ``torch.optim.swa_utils``) kept on the device beside
   the model, fed per epoch or per batch, and -- ``predict`` -- what ``predict_proba`` / ``predict`` / ``score`` evaluate with;
 * ``calibration={"method": "temperature"}``: at the end of a fit one temperature is fitted on the valid split's log-probs, on
-  the device (csrc/calibration.hip), and ``predict_proba`` returns ``softmax(z / T)``; ``predict`` and the history never change.
+  the device (csrc/calibration.hip), and ``predict_proba`` returns ``softmax(z / T)``; ``predict`` and the history never change;
+* ``conformal={"alpha": 0.1, ...}``: at the end of a fit, after the temperature, the threshold of split conformal prediction sets
+  (LAC / APS / RAPS, csrc/conformal.hip) is taken on the valid split's log-probs, on the device; ``predict_set`` then returns per
+  sample the set of classes that holds the true one with probability about 1 - alpha.  About: the valid split also chose the
+  temperature and the stopping epoch, so the guarantee is approximate there; it is exact only with ``conformalize`` on rows the
+  fit never saw (``coverage`` reports what the sets achieve on labelled data).
 
 Beyond skorch: ``reliability`` (ECE / MCE / Brier, csrc/reliability.hip), ``predict_topk`` and ``error_analysis`` (top-k classes,
 confusion matrix, most-confused pairs, per-class report: csrc/confusion.hip) and ``ranking`` (one-vs-rest ROC AUC and average
-precision per class, csrc/ranking.hip) reduce a fitted estimator's log-probs on the device.
+precision per class, csrc/ranking.hip) reduce a fitted estimator's log-probs on the device; ``conformalize`` / ``predict_set`` /
+``coverage`` (csrc/conformal.hip) say something about a single sample.
 
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
 import threading
 import json
+import math
+import warnings
 import os
 import time
 import importlib
@@ -320,6 +328,51 @@ def calibration_options(setting):
     if method != "temperature":
         raise ValueError(f"calibration: method={method!r}, expected 'temperature'")
     return {"method": "temperature"}
+
+
+CONFORMAL_DEFAULTS = {"alpha": 0.1, "method": "aps", "randomized": True, "lam": 0.0, "k_reg": 0, "seed": 0}
+CONFORMAL_METHODS = tuple(ops._lib.CONFORMAL_METHODS)
+
+
+def conformal_options(setting):
+    """The ``conformal`` setting with its defaults filled in -- {alpha 0.1, method "aps", randomized True, lam 0.0, k_reg 0,
+    seed 0} -- or None (off).  ``method``: "lac" (1 - p of the class) or "aps" (the mass in front of the class plus u times its
+    own; ``lam`` > 0 with ``k_reg`` adds RAPS' penalty lam max(0, rank - k_reg)).  Anything else raises ValueError here."""
+    if setting is None or setting is False:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"conformal={setting!r}: expected a dict with keys among {tuple(CONFORMAL_DEFAULTS)} or None")
+    unknown = sorted(set(setting) - set(CONFORMAL_DEFAULTS))
+    if unknown:
+        raise ValueError(f"conformal: unknown keys {unknown} (known: {tuple(CONFORMAL_DEFAULTS)})")
+    o = {**CONFORMAL_DEFAULTS, **setting}
+    real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not real(o["alpha"]) or not 0.0 < float(o["alpha"]) < 1.0:
+        raise ValueError(f"conformal: alpha={o['alpha']!r}, expected a number in (0, 1)")
+    if o["method"] not in CONFORMAL_METHODS:
+        raise ValueError(f"conformal: method={o['method']!r}, expected one of {CONFORMAL_METHODS}")
+    if not isinstance(o["randomized"], (bool, np.bool_)):
+        raise ValueError(f"conformal: randomized={o['randomized']!r}, expected True or False")
+    if not real(o["lam"]) or not 0.0 <= float(o["lam"]) < float("inf"):
+        raise ValueError(f"conformal: lam={o['lam']!r}, expected a finite number >= 0")
+    if not whole(o["k_reg"]) or not 0 <= o["k_reg"] < 2 ** 31:
+        raise ValueError(f"conformal: k_reg={o['k_reg']!r}, expected an integer >= 0")
+    if not whole(o["seed"]) or not 0 <= o["seed"] < 2 ** 64:
+        raise ValueError(f"conformal: seed={o['seed']!r}, expected an integer in 0..2^64 - 1")
+    return {"alpha": float(o["alpha"]), "method": o["method"], "randomized": bool(o["randomized"]), "lam": float(o["lam"]),
+            "k_reg": int(o["k_reg"]), "seed": int(o["seed"])}
+
+
+def conformal_least_rows(alpha):
+    """The least number n of calibration rows with ceil((n + 1)(1 - alpha)) <= n: fewer give an infinite threshold."""
+    n = max(1, int(math.ceil((1.0 - alpha) / alpha)) - 2)
+    while math.ceil(float(n + 1) * (1.0 - alpha)) > n:
+        n += 1
+    return n
+
+
+CONFORMAL_DRAW_CALIBRATE, CONFORMAL_DRAW_PREDICT = 0, 1    # the u of a row at prediction time is independent of the calibration draws
 
 
 def next_n_averaged(opts, history, n_batches):
@@ -632,13 +685,13 @@ class _FitRun:
 class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
     _OWN = ("module", "criterion", "optimizer", "lr", "max_epochs", "batch_size", "device", "warm_start", "verbose",
             "predict_nonlinearity", "scoring", "labels", "early_stopping", "gradient_clipping", "lr_scheduler",
-            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging", "calibration")
+            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging", "calibration", "conformal")
 
     def __init__(self, module, criterion="torch.nn.CrossEntropyLoss", optimizer="torch.optim.SGD", lr=0.01,
                  max_epochs=10, batch_size=128, device="cuda", warm_start=False, verbose=0,
                  predict_nonlinearity="auto", scoring=None, labels=None, early_stopping=None,
                  gradient_clipping=None, lr_scheduler=None, checkpoint_dir=None, train_split=5, use_graph="auto",
-                 callbacks=None, dataset=None, weight_averaging=None, calibration=None, **kwargs):
+                 callbacks=None, dataset=None, weight_averaging=None, calibration=None, conformal=None, **kwargs):
         loc = locals()
         self._params = {k: loc[k] for k in self._OWN}
         for k, v in kwargs.items():
@@ -768,6 +821,10 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         if cal_opts is not None and not self.train_split:
             raise ValueError(f"calibration: the temperature is fitted on the fit's internal valid split, and train_split={self.train_split!r} "
                              "holds nothing out")
+        conf_opts = conformal_options(self._params.get("conformal"))
+        if conf_opts is not None and not self.train_split:
+            raise ValueError(f"conformal: the threshold is taken on the fit's internal valid split, and train_split={self.train_split!r} "
+                             "holds nothing out (conformalize(X, y) takes it on data of yours)")
         ok, pairs = optimizer_kwargs(self._sub("optimizer"))
         if not pairs:
             schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
@@ -798,6 +855,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         self._avg_opts = avg_opts
         self._cal_opts = cal_opts
         self._set_calibration(None)
+        self._conf_opts = conf_opts
+        self._set_conformal(None)
         self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
         # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
         self._crit_opts = criterion_options(self.criterion_) if hasattr(mod_cls, "engine") else None
@@ -870,6 +929,8 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         self._enter_stream()
         if getattr(self, "_cal_opts", None) is not None:
             self._set_calibration(None)                      # an earlier fit's temperature does not describe the weights to come
+        if getattr(self, "_conf_opts", None) is not None:
+            self._set_conformal(None)                        # nor does its threshold
         with torch.cuda.stream(self._stream):
             run = _FitRun(self, self._as_dataset(X, y))
             for _ in range(int(self.max_epochs)):
@@ -894,8 +955,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
                     va = self._run_epoch(run.Xva, run.Lva, run.yva, run.bs, False, run.momentum, run.max_norm)
                 if run.end_epoch(tr, va):
                     break
-            if getattr(self, "_cal_opts", None) is not None:
-                self._calibrate(run)
+            logp = self._calibrate(run) if getattr(self, "_cal_opts", None) is not None else None
+            if getattr(self, "_conf_opts", None) is not None:
+                self._conformalize_fit(run, logp)
         stream_sync(self._stream)
         return self
 
@@ -905,17 +967,22 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         ones swapped in and back, as there); the [N, V] matrix stays on the device, only the state comes to the host."""
         if run.va is None:
             raise ValueError("calibration: the fit has no valid split to fit the temperature on (train_split)")
+        logp = self._valid_logp(run)
+        state = ops.fit_temperature(logp, run.yva)
+        self._set_calibration(ops.temperature_download(state), state)
+        return logp
+
+    def _valid_logp(self, run):
+        """The valid split's device log-probs under the weights ``predict_proba`` evaluates with."""
         self.module_.eval()
         swapped = self._predict_averaged()
         if swapped:
             self.module_.swap_averaged()
         try:
-            logp = self._run_epoch(run.Xva, run.Lva, run.yva, run.bs, False, run.momentum, run.max_norm)[1]
+            return self._run_epoch(run.Xva, run.Lva, run.yva, run.bs, False, run.momentum, run.max_norm)[1]
         finally:
             if swapped:
                 self.module_.swap_averaged()
-        state = ops.fit_temperature(logp, run.yva)
-        self._set_calibration(ops.temperature_download(state), state)
 
     def _set_calibration(self, info, state=None):
         """``calibration_`` (``ops.temperature_download``'s dict), ``temperature_`` and the device state ``predict_proba`` scales with;
@@ -933,6 +1000,164 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
         self._cal_state = state if state is not None else ops.temperature_state(info["beta"], dev)
         self.calibration_, self.temperature_ = dict(info), info["temperature"]
+
+    # ------------------------------------------------------ conformal sets
+    def _conformalize_fit(self, run, logp=None):
+        """The ``conformal`` option at the end of a fit: the threshold on the valid split's log-probs (``logp``: those the
+        temperature was just fitted on; None: a forward pass under the weights ``predict_proba`` uses), at the fit's
+        temperature when it has one.  This split also chose the temperature and the stopping epoch, so the 1 - alpha guarantee
+        is approximate here; it is exact only with ``conformalize`` on rows the fit never saw."""
+        if run.va is None:
+            raise ValueError("conformal: the fit has no valid split to take the threshold on (train_split)")
+        if logp is None:
+            logp = self._valid_logp(run)
+        self._set_conformal(self._conf_opts, *self._conformal_calibrate(logp, run.yva, self._conf_opts, True), labels=run.va.y,
+                            where="the valid data")
+
+    def _conformal_calibrate(self, logp, yd, opts, calibrated):
+        """Scores at the calibration draw, then the threshold, on the current stream: ``(device state float64 [4], whether the
+        temperature was used)``.  No host wait."""
+        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
+        logp = logp if logp.dtype == torch.float32 else logp.float()
+        buf = ops.conformal_buffers(logp.shape[0], logp.shape[1], logp.device, sets=False)
+        ops.conformal_rows(logp, yd.contiguous(), buf, method=opts["method"], lam=opts["lam"], k_reg=opts["k_reg"],
+                           randomized=opts["randomized"], seed=opts["seed"], draw=CONFORMAL_DRAW_CALIBRATE,
+                           state=self._cal_state if use else None)
+        state = torch.empty(4, dtype=torch.float64, device=logp.device)
+        return ops.conformal_quantile(buf, opts["alpha"], state=state), use
+
+    def _set_conformal(self, opts, state=None, calibrated=False, labels=None, where="the calibration data", info=None):
+        """``conformal_`` -- the options plus ``calibrated``, ``qhat``, ``n``, ``k`` and ``excluded`` -- and the device state
+        ``predict_set`` reads its threshold from; None removes them.  ``state``: ``ops.conformal_quantile``'s (one download of
+        its four doubles, which waits for the launches); ``info``: a ``conformal_`` read back from a checkpoint instead (qhat
+        goes back to the device).  Labels outside the classes raise, as in ``_set_calibration``."""
+        if opts is None:
+            for k in ("conformal_", "_conf_state"):
+                self.__dict__.pop(k, None)
+            return
+        if info is None:
+            if labels is not None:
+                bad = int(((np.asarray(labels) < 0) | (np.asarray(labels) >= len(self.classes_))).sum())
+                if bad:
+                    raise ValueError(f"conformalizing on {where}: {bad} of {len(labels)} labels lie outside the classes of the log-probs")
+            h = state.cpu().numpy()
+            info = {**opts, "calibrated": bool(calibrated), "qhat": float(h[0]), "n": int(h[1]), "k": int(h[2]), "excluded": int(h[3])}
+            if math.isinf(info["qhat"]):
+                warnings.warn(f"conformal: {info['n']} calibration rows are too few for alpha={info['alpha']}: the threshold is infinite "
+                              f"and every set holds every class; at least {conformal_least_rows(info['alpha'])} rows are needed",
+                              RuntimeWarning, stacklevel=3)
+        else:
+            dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
+            state = torch.tensor([float(info["qhat"]), float(info["n"]), float(info["k"]), float(info["excluded"])],
+                                 dtype=torch.float64).to(dev)
+        self._conf_state, self.conformal_ = state, dict(info)
+
+    def conformalize(self, X, y=None, alpha=0.1, method="aps", randomized=True, lam=0.0, k_reg=0, seed=0, calibrated=True):
+        """Take the threshold of split conformal prediction sets on ``X`` (``y``: the labels; None: the dataset's) -- rows the fit
+        has not seen, for the guarantee to hold: with exchangeable rows, ``predict_set`` then covers the true class with
+        probability at least 1 - alpha (and, randomised, at most 1 - alpha + 1 / (n + 1)).  One forward pass,
+        ``ops.conformal_rows`` at draw 0 and ``ops.conformal_quantile``, all on the device; only the four doubles of the state
+        come to the host.  ``method`` "lac": s = 1 - p of the class (the smallest sets on average, may be empty); "aps": the
+        probability mass in front of the class plus u times its own (adaptive: larger sets where the model is lost); ``lam`` > 0
+        with ``k_reg`` adds RAPS' penalty lam max(0, rank - k_reg), which shortens the tails.  ``randomized``: u is one draw
+        per row of the counter-based generator under ``seed``; False: u = 1 (conservative, sets never empty for APS).
+        ``calibrated``: the probabilities are softmax(z / T) with ``temperature_`` when the fit has one.  Sets ``conformal_``
+        (the options, ``calibrated``, ``qhat``, ``n``, ``k``, ``excluded``: rows left out for a NaN) and returns self.  Fewer than
+        about (1 - alpha) / alpha rows give an infinite threshold: kept and reported, with a warning."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        opts = conformal_options({"alpha": alpha, "method": method, "randomized": randomized, "lam": lam, "k_reg": k_reg, "seed": seed})
+        ds = self._as_dataset(X)
+        labels = ds.y if y is None else np.ascontiguousarray(np.asarray(y), dtype=np.int64)
+        if labels.shape != (len(ds),):
+            raise ValueError(f"conformalize: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
+        bad = int(((labels < 0) | (labels >= len(self.classes_))).sum())
+        if bad:                                              # before the forward passes, as coverage does
+            raise ValueError(f"conformalize: {bad} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the log-probs")
+
+        def rows(logp, yd):
+            yd = yd if y is None else torch.from_numpy(labels).to(logp.device)
+            return self._conformal_calibrate(logp, yd, opts, calibrated)
+        state, use = self._forward_logp(ds, rows)
+        self._set_conformal(opts, state, use, labels=labels)
+        return self
+
+    def _conformal_rows(self, what, logp, yd, sets):
+        """``ops.conformal_rows`` at the prediction draw under ``conformal_``'s options and the device threshold."""
+        c = self.conformal_
+        use = c["calibrated"] and getattr(self, "calibration_", None) is not None
+        logp = logp if logp.dtype == torch.float32 else logp.float()
+        buf = ops.conformal_buffers(logp.shape[0], logp.shape[1], logp.device, sets=sets)
+        return ops.conformal_rows(logp, yd, buf, method=c["method"], lam=c["lam"], k_reg=c["k_reg"], randomized=c["randomized"],
+                                  seed=c["seed"], draw=CONFORMAL_DRAW_PREDICT, state=self._cal_state if use else None,
+                                  qhat=self._conf_state)
+
+    def predict_set(self, X, return_mask=False):
+        """The conformal prediction set of every sample of ``X`` under ``conformal_``'s options and threshold (draw 1: a row's u
+        is independent of the calibration draws): ``{"sets": ..., "sizes": int array [N]}``.  ``sets``: a list of N label
+        arrays (from ``classes_``), most probable first -- every score here grows with the rank, so a set is the first ``size``
+        classes of the row's order; the order comes from ``ops.topk_rows`` on the same forward passes, and the members beyond
+        rank 64 follow by ascending class -- or, with ``return_mask=True``, a bool [N, V] mask.  A set may be empty (LAC, or
+        APS without randomisation when the top probability exceeds the threshold); a row with a NaN gets an empty set.  The
+        [N, V] log-probs stay on the device: the set words, the sizes and (for the lists) the top indices come over."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        if getattr(self, "conformal_", None) is None:
+            raise RuntimeError("predict_set: this estimator has no threshold yet: fit it with the conformal option or call conformalize(X, y)")
+        ds = self._as_dataset(X)
+        V = len(self.classes_)
+        k = min(V, ops._lib.TOPK_MAX)
+
+        def rows(logp, yd):
+            buf = self._conformal_rows("predict_set", logp, None, True)
+            top = None if return_mask else ops.topk_rows(logp if logp.dtype == torch.float32 else logp.float(), k)[0]
+            return buf, top
+        buf, top = self._forward_logp(ds, rows)
+        got = ops.conformal_download(buf, rows=True, sets=True)
+        sizes = got["rows"][:, 0].astype(np.int64)
+        mask = np.unpackbits(got["sets"].view(np.uint8), axis=1, bitorder="little")[:, :V].astype(bool)
+        if return_mask:
+            return {"sets": mask, "sizes": sizes}
+        top = top.cpu().numpy()
+        sets = []
+        for i in range(len(ds)):
+            head = top[i, :min(int(sizes[i]), k)]
+            if sizes[i] > k:                                 # the members past rank 64, by ascending class
+                rest = mask[i].copy()
+                rest[head] = False
+                head = np.concatenate([head, np.flatnonzero(rest)])
+            sets.append(self.classes_[head])
+        return {"sets": sets, "sizes": sizes}
+
+    def coverage(self, X, y=None, min_support=5):
+        """What the sets of ``predict_set`` achieve on labelled data ``X`` (``y``: the labels; None: the dataset's), reduced on the
+        device (``ops.conformal_summary``) and downloaded in one copy: ``metrics.conformal_report``'s dict -- coverage,
+        mean_size, median_size, empty_rate, singleton_rate, size_hist, per class support / class_coverage / class_mean_size
+        (NaN for a class without rows), worst_class_coverage over the classes with at least ``min_support`` rows, rows,
+        excluded -- plus ``qhat``, ``calibration_rows``, ``k``, ``alpha`` and ``classes``.  The per-class table shows whether
+        one threshold serves every class."""
+        if not self.initialized_:
+            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
+        if getattr(self, "conformal_", None) is None:
+            raise RuntimeError("coverage: this estimator has no threshold yet: fit it with the conformal option or call conformalize(X, y)")
+        ds = self._as_dataset(X)
+        labels = ds.y if y is None else np.ascontiguousarray(np.asarray(y), dtype=np.int64)
+        if labels.shape != (len(ds),):
+            raise ValueError(f"coverage: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
+        bad = int(((labels < 0) | (labels >= len(self.classes_))).sum())
+        if bad:
+            raise ValueError(f"coverage: {bad} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the log-probs")
+
+        def rows(logp, yd):
+            yd = (yd if y is None else torch.from_numpy(labels).to(logp.device)).contiguous()
+            buf = self._conformal_rows("coverage", logp, yd, False)
+            ops.conformal_summary(buf, yd)
+            return buf
+        got = ops.conformal_download(self._forward_logp(ds, rows))
+        c = self.conformal_
+        res = metrics.conformal_report(got["table"], min_support=min_support)
+        res.update(qhat=c["qhat"], calibration_rows=c["n"], k=c["k"], alpha=c["alpha"], classes=self.classes_)
+        return res
 
     # ------------------------------------------------------- weight averaging
     def _averaging_epoch(self):
@@ -1408,7 +1633,7 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
 
     def save_params(self, dirname):
         """skorch ``Checkpoint`` artefacts: params.pt (state_dict), optimizer.pt (a torch.optim state_dict in either
-        mode), criterion.pt, history.json."""
+        mode), criterion.pt, history.json; calibration.json and conformal.json when the fit has a temperature / a conformal threshold."""
         os.makedirs(dirname, exist_ok=True)
         torch.save({k: v.detach().cpu() for k, v in self.module_.state_dict().items()}, os.path.join(dirname, "params.pt"))
         torch.save(self._sgd_state_dict() if self._fused else self.optimizer_.state_dict(), os.path.join(dirname, "optimizer.pt"))
@@ -1419,6 +1644,9 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         if getattr(self, "calibration_", None) is not None:
             with open(os.path.join(dirname, "calibration.json"), "w") as f:
                 json.dump(self.calibration_, f, indent=1)
+        if getattr(self, "conformal_", None) is not None:
+            with open(os.path.join(dirname, "conformal.json"), "w") as f:
+                json.dump(self.conformal_, f, indent=1)      # (an infinite qhat is written as Infinity, which json.load reads back)
         if getattr(self, "_avg_opts", None) is not None:  # the running average and how many models it holds: a resumed fit goes on
             torch.save({"state_dict": {k: v.detach().cpu() for k, v in self.averaged_state_dict().items()}, "n_averaged": self.n_averaged_},
                        os.path.join(dirname, "averaged.pt"))
@@ -1451,6 +1679,11 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         if getattr(self, "_cal_opts", None) is not None and os.path.exists(cal_file):
             with open(cal_file) as f:
                 self._set_calibration(json.load(f))          # beta goes back to the device
+        conf_file = os.path.join(dirname, "conformal.json")
+        if os.path.exists(conf_file):
+            with open(conf_file) as f:
+                info = json.load(f)
+            self._set_conformal(conformal_options({k: info[k] for k in CONFORMAL_DEFAULTS}), info=info)     # qhat goes back to the device
         hist = os.path.join(dirname, "history.json")
         if os.path.exists(hist):
             with open(hist) as f:

@@ -614,6 +614,119 @@ def _int_in(what, name, value, lo, hi):
     return int(value)
 
 
+def conformal_buffers(N, V, device, sets=True):
+    """Every device buffer of one conformal pass over an [N, V] set of log-probs, as slices of ONE int64 allocation:
+
+        state float64 [4] | table int64 [V + 1, 4] | score float64 [N] | rows int32 [N, 4] | sets int32 [N, ceil(V / 32)]
+
+    (one pad entry in front of rows where that keeps them 16-byte aligned; ``sets`` None with ``sets=False``).  The state and
+    the table come first, so ``conformal_download`` copies them alone; the set words are uint32 bit masks held in int32."""
+    what = "conformal_buffers"
+    N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFORMAL_MAX_V)
+    W = (V + 31) // 32
+    head = 4 + 4 * (V + 1)
+    at_rows = head + N + (N & 1)
+    at_sets = at_rows + 2 * N
+    flat = torch.empty(at_sets + ((N * W + 1) // 2 if sets else 0), dtype=torch.int64, device=device)
+    return {"flat": flat, "shape": (N, V), "state": flat[:4].view(torch.float64), "table": flat[4:head].view(V + 1, 4),
+            "score": flat[head:head + N].view(torch.float64), "rows": flat[at_rows:at_sets].view(torch.int32).view(N, 4),
+            "sets": flat[at_sets:].view(torch.int32)[:N * W].view(N, W) if sets else None}
+
+
+def _conformal_buf(what, buf, logp_or_device, N, V):
+    device = logp_or_device
+    if not (isinstance(buf, dict) and buf.get("shape") == (N, V) and buf["flat"].device == device):
+        raise ValueError(f"{what}: buf must be conformal_buffers({N}, {V}, {device!r})")
+
+
+def _conformal_state(what, name, t, device):
+    if not (t.device == device and t.dtype == torch.float64 and t.dim() == 1 and t.numel() == 4 and t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous float64 [4] tensor on {device}")
+
+
+def conformal_rows(logp, y=None, buf=None, *, method="aps", lam=0.0, k_reg=0, randomized=True, seed=0, draw=0, state=None, qhat=None):
+    """The conformal scores and prediction sets of ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``; V <= 1024)
+    (``slnlp_conformal_rows``, include/slnlp.h), into ``buf`` (``conformal_buffers``; default a new one, which is returned).
+    ``y`` int64 [N] or None: with labels ``buf["score"]`` holds s(y_i) and ``buf["rows"]`` the label's rank and whether the set
+    covers it.  ``method`` "lac" | "aps"; ``lam`` / ``k_reg``: the RAPS penalty; ``randomized`` / ``seed`` / ``draw``: one u per
+    row from the counter-based generator.  ``state``: a calibration state whose beta is read on the device (None: beta = 1).
+    ``qhat``: a float64 [4] device tensor whose first entry is the threshold (``conformal_quantile``'s state), read on the
+    device; None: scores and ranks only, ``buf["sets"]`` is not written.  Runs on the current stream of ``logp``'s device; no
+    host wait."""
+    _lib.require_gpu()
+    what = "conformal_rows"
+    N, V, ld = _logp_matrix(what, logp)
+    if V > _lib.CONFORMAL_MAX_V:
+        raise ValueError(f"{what}: {V} classes, a row is sorted for at most {_lib.CONFORMAL_MAX_V}")
+    if y is not None and not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"{what}: y must be a contiguous int64 [{N}] tensor on {logp.device} or None")
+    if method not in _lib.CONFORMAL_METHODS:
+        raise ValueError(f"{what}: method={method!r}, expected one of {tuple(_lib.CONFORMAL_METHODS)}")
+    seed, draw = _int_in(what, "seed", seed, 0, 2 ** 64 - 1), _int_in(what, "draw", draw, 0, 2 ** 32 - 1)
+    k_reg = _int_in(what, "k_reg", k_reg, 0, 2 ** 31 - 1)
+    if state is not None:
+        _cal_state(what, state, logp.device)
+    if qhat is not None:
+        _conformal_state(what, "qhat", qhat, logp.device)
+    with torch.cuda.device(logp.device):
+        if buf is None:
+            buf = conformal_buffers(N, V, logp.device, sets=qhat is not None)
+        _conformal_buf(what, buf, logp.device, N, V)
+        sets = buf["sets"] if qhat is not None else None
+        check(load().slnlp_conformal_rows(ptr(logp), ld, ptr(y) if y is not None else None, N, V, ptr(state) if state is not None else None,
+                                          _lib.CONFORMAL_METHODS[method], float(lam), k_reg, 1 if randomized else 0, seed, draw,
+                                          ptr(qhat) if qhat is not None else None, ptr(buf["score"]) if y is not None else None,
+                                          ptr(buf["rows"]), ptr(sets) if sets is not None else None, stream_ptr()), what)
+    return buf
+
+
+def conformal_quantile(buf, alpha, state=None):
+    """The threshold of ``buf``'s scores (``conformal_rows`` with labels): ``state`` float64 [4] = (qhat, n, k, rows left out) --
+    qhat the ceil((n + 1)(1 - alpha))-th smallest score of the n rows with code 0, +inf when there are too few
+    (``slnlp_conformal_quantile``).  ``state``: the tensor to fill, default ``buf["state"]``; returned.  No host wait."""
+    _lib.require_gpu()
+    N, _ = buf["shape"]
+    state = buf["state"] if state is None else state
+    _conformal_state("conformal_quantile", "state", state, buf["flat"].device)
+    with torch.cuda.device(state.device):
+        check(load().slnlp_conformal_quantile(ptr(buf["score"]), ptr(buf["rows"]), N, float(alpha), ptr(state), stream_ptr()),
+              "conformal_quantile")
+    return state
+
+
+def conformal_summary(buf, y):
+    """The coverage / set-size table of ``buf``'s rows against the labels ``y`` int64 [N] (``slnlp_conformal_summary``): fills and
+    returns ``buf["table"]``, int64 [V + 1, 4].  No host wait."""
+    _lib.require_gpu()
+    N, V = buf["shape"]
+    dev = buf["flat"].device
+    if not (y.device == dev and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"conformal_summary: y must be a contiguous int64 [{N}] tensor on {dev}")
+    with torch.cuda.device(dev):
+        check(load().slnlp_conformal_summary(ptr(buf["rows"]), ptr(y), N, V, ptr(buf["table"]), stream_ptr()), "conformal_summary")
+    return buf["table"]
+
+
+def conformal_download(buf, rows=False, sets=False, score=False):
+    """What a conformal pass hands to the host: ONE device-to-host copy of the state and the table -- {qhat, n, k, excluded,
+    state float64 [4], table int64 [V + 1, 4]} (a piece no call has written yet holds whatever the allocation held) -- and, only
+    on request, one further copy each for ``rows`` int32 [N, 4], ``sets`` uint32 [N, W] and ``score`` float64 [N]."""
+    import numpy as np
+    N, V = buf["shape"]
+    h = buf["flat"][:4 + 4 * (V + 1)].cpu().numpy()
+    st = h[:4].view(np.float64)
+    out = {"state": st, "table": h[4:].reshape(V + 1, 4), "qhat": float(st[0]), "n": st[1], "k": st[2], "excluded": st[3]}
+    if rows:
+        out["rows"] = buf["rows"].cpu().numpy()
+    if sets:
+        if buf["sets"] is None:
+            raise ValueError("conformal_download: sets=True, but the buffers hold none (conformal_buffers(sets=False))")
+        out["sets"] = buf["sets"].cpu().numpy().view(np.uint32)
+    if score:
+        out["score"] = buf["score"].cpu().numpy()
+    return out
+
+
 def error_analysis_buffers(N, V, k, M, device):
     """Every device buffer of one error analysis of an [N, V] set of log-probs -- ``k`` top classes per row (0: none), ``M``
     most-confused pairs -- as slices of ONE int32 allocation, laid out so that whatever is asked for afterwards is one contiguous
