@@ -140,6 +140,15 @@ int slnlp_gemm_wd_plan(const slnlp_gemm_args* wgrad, const slnlp_gemm_args* dgra
  * gate, dropout incl. drop_head_dim, resid, C and / or C_hi / C_lo); the K sum is per 64-k tile: partial products from zero, added
  * in tile order.  Meant for up to 64 rows (one block of rows; more work, the plans use the plane GEMM there). */
 int slnlp_gemm_rows(const slnlp_gemm_args* args, void* stream);
+/* slnlp_layernorm_fwd followed by slnlp_gemm_rows on its output, in ONE launch and with their bits: x [M, K] (row stride ldx) is
+ * the LayerNorm's INPUT; every 16 x 16-tile workgroup normalises its 16 rows itself (the stand-alone kernel's row arithmetic),
+ * splits them and contracts them with W as slnlp_gemm_rows does.  args as for slnlp_gemm_rows, A_hi / A_lo / lda_p not read.
+ * The first column tile's workgroups also store what the LayerNorm launch stores, for rows < M: y [M, K] (row stride K), (mean,
+ * rstd) to stats [M, 2] (or NULL) and y as planes y_hi / y_lo (row stride ldp; both or neither) -- rows >= M of the planes stay
+ * as they are.  K a multiple of 64, at most 1024; the launch must be one that takes the 16 x 16 tile (slnlp_set_rows_tile -1 or
+ * 0); x and y (and resid / gate and y) must not overlap -- other workgroups still read while the first column tile's write. */
+int slnlp_gemm_rows_ln(const slnlp_gemm_args* args, const float* x, int64_t ldx, const float* gamma, const float* beta, float eps,
+                       float* y, float* stats, uint16_t* y_hi, uint16_t* y_lo, int64_t ldp, void* stream);
 /* The backward pair of such a product in ONE launch (autograd's two mm calls for nn.Linear at batch rows):
  *   dgrad: dX[B rows, Kin] = dY[B rows, Nout] W[Nout, Kin] (+ the slnlp_gemm epilogue: gate, dropout, residual, planes out) --
  *          A = dY planes k-major, B = W as fp32 (B / ldb), NOT k-major (m-major: k = W's row; Nout a multiple of 64, Kin of 4);
@@ -911,6 +920,12 @@ int slnlp_tf_set_averaging(slnlp_tf_plan* plan, float* avg, float* count, int ki
  * same order); the switch exists for A / B measurements and tests.  A change drops the plan's captured graphs and makes a
  * lockstep group re-record, as slnlp_tf_set_update does. */
 int slnlp_tf_set_dmem_batched(slnlp_tf_plan* plan, int on);
+/* The decoder's LayerNorms that feed exactly one B-row product on the chain (norm1 -> the cross-attention query projection,
+ * norm2 -> linear1, norm3 -> the next layer's V projection, the final norm -> the generator).  on (default; a new plan starts
+ * from the environment knob SLNLP_DEC_LN_FUSED=0|1): the LayerNorm is that product's prologue (slnlp_gemm_rows_ln), one launch
+ * instead of two, wherever the product is a solo fit's 16 x 16-tile B-row launch; off: a launch each.  Same bits either way.
+ * Recorded lockstep programs always hold the two launches.  A change drops the plan's captured graphs, as slnlp_tf_set_update. */
+int slnlp_tf_set_dec_ln_fused(slnlp_tf_plan* plan, int on);
 
 /* One kernel sequence per device (default).  The step entry points (slnlp_{tf,rnn}_{forward,backward,optim*,train_step,
  * graph_launch}, slnlp_*_lockstep_{step,epoch}) serialise per device: host threads enqueue whole steps in turn, and a step issued

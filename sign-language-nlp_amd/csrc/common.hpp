@@ -380,6 +380,20 @@ int gemm_group(const slnlp_gemm_args* jobs, int njobs, hipStream_t s, unsigned w
 int gemm_planes(const slnlp_gemm_args& a, hipStream_t s);
 int gemm_rows(const slnlp_gemm_args& a, hipStream_t s);
 int gemm_rows_bwd(const slnlp_gemm_args& dgrad, const slnlp_gemm_args& wgrad, hipStream_t s);   // dX = dY W and dW = dY^T x, db in one launch     // B-row products on k-major planes, register-direct (gemm_rows.hip)
+// a B-row product whose A operand is the output of a LayerNorm that the product's own launch computes (gemm_rows.hip:
+// gemm_rows_ln_kernel): x [M, K] un-normalised (row stride ldx) -> y [M, K] (row stride K), (mean, rstd) to stats [M, 2] (or null),
+// y as planes y_hi / y_lo (row stride ldp; both or neither) -- what layernorm_fwd would have stored, bit for bit.  x and y apart.
+struct RowsLn {
+    const float* x = nullptr;
+    long ldx = 0;
+    const float *gamma = nullptr, *beta = nullptr;
+    float eps = 0.f;
+    float *y = nullptr, *stats = nullptr;
+    unsigned short *y_hi = nullptr, *y_lo = nullptr;
+    long ldp = 0;
+};
+int gemm_rows_ln(const slnlp_gemm_args& a, const RowsLn& ln, hipStream_t s);   // `a` as for gemm_rows; its A operand fields are not read
+bool gemm_rows_ln_covers(int M, int N, int K);   // the launch would take the 16 x 16 tile and K fits the prologue
 int gemm_planes_init();
 // up to 4 independent plane GEMMs in ONE launch, optional deterministic split-K per job (gemm_planes.hip)
 int gemm_planes_group(const slnlp_gemm_args* jobs, const int* split_k, int njobs, void* scratch, size_t scratch_bytes,

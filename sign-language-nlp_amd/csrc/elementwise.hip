@@ -3,6 +3,7 @@
 // All fp32, 16-B vector accesses, one wave per row for the row-wise reductions.
 #include "common.hpp"
 #include "launch.hpp"
+#include "layernorm_row.hpp"
 
 namespace slnlp {
 
@@ -313,7 +314,7 @@ int embed_bwd(const int64_t* ids, int64_t ld_ids, int B, int S, int E, int V, co
 }
 
 // ================================================================= layernorm
-constexpr int LN_MAXU = 4;  // float4 per lane -> E <= 1024 in the backward (register-resident columns)
+// (LN_MAXU = 4 float4 per lane -> E <= 1024, forward and backward: layernorm_row.hpp)
 
 __device__ __forceinline__ void layernorm_fwd_body(const float* __restrict__ x,
                                                             const float* __restrict__ gamma,
@@ -334,30 +335,11 @@ __device__ __forceinline__ void layernorm_fwd_body(const float* __restrict__ x,
         g[u] = in ? *reinterpret_cast<const float4*>(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         bt[u] = in ? *reinterpret_cast<const float4*>(beta + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float s = 0.f;
-#pragma unroll
-    for (int u = 0; u < LN_MAXU; ++u) s += v[u].x + v[u].y + v[u].z + v[u].w;      // out-of-range slots hold zeros
-    const float mean = wave_sum(s) / (float)E;
-    float q = 0.f;
-#pragma unroll
-    for (int u = 0; u < LN_MAXU; ++u) {
-        if (lane * 4 + u * 256 < E) {
-            const float a = v[u].x - mean, b = v[u].y - mean, cc = v[u].z - mean, d = v[u].w - mean;
-            q += a * a + b * b + cc * cc + d * d;
-        }
-    }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)E + eps);
-#pragma unroll
-    for (int u = 0; u < LN_MAXU; ++u) {
-        const int c = lane * 4 + u * 256;
-        if (c < E) {
-            float4 o;
-            o.x = (v[u].x - mean) * rstd * g[u].x + bt[u].x; o.y = (v[u].y - mean) * rstd * g[u].y + bt[u].y;
-            o.z = (v[u].z - mean) * rstd * g[u].z + bt[u].z; o.w = (v[u].w - mean) * rstd * g[u].w + bt[u].w;
-            *reinterpret_cast<float4*>(y + (long)row * E + c) = o;
-            store_planes4(po, (long)row * E + c, o);
-        }
-    }
+    float mean, rstd;
+    layernorm_row(v, g, bt, E, eps, lane, mean, rstd, [&](int, int c, const float4& o) {      // (the arithmetic: layernorm_row.hpp)
+        *reinterpret_cast<float4*>(y + (long)row * E + c) = o;
+        store_planes4(po, (long)row * E + c, o);
+    });
     if (lane == 0 && stats) {
         stats[2 * row] = mean;
         stats[2 * row + 1] = rstd;

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "gemm_jobs.hpp"
 #include "launch.hpp"
+#include "layernorm_row.hpp"
 
 namespace slnlp {
 
@@ -129,6 +130,62 @@ __device__ __forceinline__ void rows_img_col8(const float* img, int kk, int lane
     const float* p = img + (kk * 32 + ((lane >> 4) << 3)) * 16 + (lane & 15);
 #pragma unroll
     for (int e = 0; e < 8; ++e) x[e] = p[e * 16];
+}
+
+// rows_tile's epilogue of one MFMA tile (accumulator layout: the lane holds rows gm0 .. gm0 + 3 of column gn) as two functions, for
+// gemm_rows_ln_body: what it reads is requested early (rows_epilogue_loads, by the lanes whose rows and column exist) and used
+// behind the K sum (rows_epilogue).  rows_tile keeps its own text of the same statements: called from there, these functions
+// move the instruction streams of every kernel above, which are held fixed (tools/diff_kernel_isa.py).
+struct RowsEpi {
+    float bias = 0.f, gt[4] = {0.f, 0.f, 0.f, 0.f}, rs[4] = {0.f, 0.f, 0.f, 0.f};
+    DropKey dkey = {};
+};
+__device__ __forceinline__ void rows_epilogue_loads(const slnlp_gemm_args& g, int gm0, int gn, RowsEpi& e) {
+    if (g.bias) e.bias = g.bias[gn];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int gm = gm0 + r < g.M ? gm0 + r : gm0;
+        if (g.gate) e.gt[r] = g.gate[(long)gm * g.ldg + gn];
+        if (g.resid) e.rs[r] = g.resid[(long)gm * g.ldr + gn];
+    }
+    if (g.drop_p > 0.f) e.dkey = dropout_key(g.rng, g.drop_site);
+}
+__device__ __forceinline__ void rows_epilogue(const RowsParams& p, const f32x4& acc, int gm0, int gn, const RowsEpi& e) {
+    const slnlp_gemm_args& g = p.a;
+    const int M = g.M, N = g.N;
+    unsigned lot[4] = {0u, 0u, 0u, 0u};
+    if (g.drop_p > 0.f) {
+        if (g.drop_head_dim == 0) {
+            const uint4 bits = dropout_bits8(e.dkey, (unsigned)gm0 >> 2, drop_cc((unsigned)gn));
+            const int h = drop_half((unsigned)gn);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lot[r] = pick_lot(bits, h, r);
+        } else {                                  // one keep / drop decision per (row, head), see slnlp.h
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned rh = (unsigned)(gm0 + r) * (unsigned)(N / g.drop_head_dim) + (unsigned)(gn / g.drop_head_dim);
+                lot[r] = pick_lot(dropout_bits8(e.dkey, rh >> 2, 0u), 0, (int)(rh & 3u));
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int gm = gm0 + r;
+        if (gm >= M) break;
+        float v = acc[r] + e.bias;
+        if (g.relu == 1) v = fmaxf(v, 0.f);
+        else if (g.relu == 2) v = tanhf(v);
+        if (g.gate) v = g.gate_mode == 1 ? v * (1.f - e.gt[r] * e.gt[r]) : (e.gt[r] > 0.f ? v * g.gate_scale : 0.f);
+        if (g.drop_p > 0.f) v = (lot[r] >= p.drop_thr) ? v * p.drop_scale : 0.f;
+        if (g.resid) v += e.rs[r];
+        if (g.C) g.C[(long)gm * g.ldc + gn] = v;
+        if (g.C_hi) {
+            unsigned short h, l;
+            split_bf16(v, h, l);
+            g.C_hi[(long)gm * g.ldc_p + gn] = h;
+            if (g.C_lo) g.C_lo[(long)gm * g.ldc_p + gn] = l;
+        }
+    }
 }
 
 // One product unit: output tile (bx, by) of 16 MT rows x 16 NT columns.  BK: the B operand is k-major (forward products: fragments
@@ -421,6 +478,161 @@ __device__ __forceinline__ void gemm_rows_body(RowsParams p) {
     rows_tile<NSPLIT, MT, NT, true>(p, blockIdx.x, blockIdx.y, part);
 }
 
+// ---- The forward product whose operand is the output of a LayerNorm that has not run yet (the decoder's norm1 / norm2 / norm3 and
+// final norm each feed exactly one B-row product on the chain: 4.6 us of launch for 13 workgroups of work).  A kernel of its own for
+// the 16 x 16 tile of a solo fit's launch -- the kernels above, which merged lockstep launches also take, keep their registers.
+// The workgroup takes UN-NORMALISED fp32 rows where rows_tile takes planes: wave w normalises rows 2 w and 2 w + 1 of its 16 with
+// layernorm_row -- the stand-alone kernel's lane-to-column mapping and reductions, hence its bits -- splits them (split_bf16: the
+// bits LayerNorm's plane output holds) into an LDS image, and after one barrier every wave reads the A fragments of its K tiles
+// from that image; weight fragments, MFMA order, K sum and epilogue are rows_tile's.  The weight fragments of the wave's first
+// tile and the epilogue's operands are requested in front of the arithmetic: one memory round trip covers all of them.
+// The workgroups of column tile 0 also store what the LayerNorm launch stored (y, its planes, (mean, rstd); rows < M only), as
+// each wave's last instructions.  Measured at the bench shape: 7.4 us per launch against 6.0 + 3.9 for the two it replaces.
+struct RowsLnParams {
+    RowsParams r;
+    RowsLn ln;
+};
+__device__ __forceinline__ RowsLnParams as_global(RowsLnParams p) {
+    launder(p.r.a);
+    p.ln.x = as_global(p.ln.x); p.ln.gamma = as_global(p.ln.gamma); p.ln.beta = as_global(p.ln.beta);
+    p.ln.y = as_global(p.ln.y); p.ln.stats = as_global(p.ln.stats); p.ln.y_hi = as_global(p.ln.y_hi); p.ln.y_lo = as_global(p.ln.y_lo);
+    return p;
+}
+// The image: [16 rows][K] bf16 per plane, rows unpadded, the 16-byte slots of a row XOR-ed with the row number.  A fragment read
+// is ds_read_b128 by lane (row l & 15, k-octet l >> 4): banks (a / 4) % 64, i.e. 16 slots per 256 bytes, and each of its 16-lane
+// groups holds 8 rows at one octet and the other 8 at the next ({0-3, 12-15, 20-27}, ...).  Unswizzled, a 1024-byte row puts
+// all 16 rows on one slot; no padding separates them all (rows r, r' at octets o, o + 1 meet whenever (r' - r) stride = 1 in
+// slots mod 16, and every difference occurs); slot ^ row maps a group onto 16 different slots.  (K not a multiple of 128: rows
+// of 8 n slots, XOR with 3 bits of the row, 2-way.)  Returns the element offset of columns c .. c + 7, c a multiple of 8.
+__device__ __forceinline__ int rows_ln_off(int r, int c, int K) { return r * K + (((c >> 3) ^ (r & ((K & 127) ? 7 : 15))) << 3); }
+
+template <int NSPLIT>
+__device__ __forceinline__ void gemm_rows_ln_body(RowsLnParams p) {
+    extern __shared__ __attribute__((aligned(16))) float part[];      // [ktiles][64 lanes][4] | the image [hi, lo][16 rows][K]
+    const slnlp_gemm_args& g = p.r.a;
+    const RowsLn& n = p.ln;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bx = blockIdx.x, bn0 = bx * 16, bm0 = blockIdx.y * 16;
+    const int M = g.M, N = g.N, K = g.K, ktiles = K >> 6;
+    unsigned short* img = reinterpret_cast<unsigned short*>(part + ktiles * 256);
+    const int koct = 8 * (lane >> 4);
+
+    // requests first, every one of them, then one wait: this wave's two rows, gamma and beta ...  No lane-dependent control
+    // flow around a load and nothing that reads a loaded value between them: a slot past K reads the row's last float4 and a
+    // row past M repeats row M - 1 (zeros are selected in below; such a row is normalised like any other and never stored).
+    const int r0 = bm0 + 2 * wave;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v[2][LN_MAXU], ga[LN_MAXU], bt[LN_MAXU];
+#pragma unroll
+    for (int u = 0; u < LN_MAXU; ++u) {
+        v[0][u] = v[1][u] = ga[u] = bt[u] = zero4;
+        if (u * 256 < K) {                                   // (wave-uniform)
+            const int cl = min(lane * 4 + u * 256, K - 4);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) v[i][u] = *reinterpret_cast<const float4*>(n.x + (long)min(r0 + i, M - 1) * n.ldx + cl);
+            ga[u] = *reinterpret_cast<const float4*>(n.gamma + cl);
+            bt[u] = *reinterpret_cast<const float4*>(n.beta + cl);
+        }
+    }
+    // ... the weight fragments of its first K tile (a row past N is a repeat of row N - 1: never stored; a wave without a tile
+    // repeats the last one's) ...
+    const float* bw = g.B + (long)min(bn0 + (lane & 15), N - 1) * g.ldb + koct;
+    float xb[2][8];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) rows_load8(bw + min(wave, ktiles - 1) * 64 + kk * 32, xb[kk]);
+    // ... and what the epilogue wants (wave 0 runs it: the lane holds rows gm0 .. gm0 + 3 of column gn)
+    const int gm0 = bm0 + ((lane >> 4) << 2), gn = bn0 + (lane & 15);
+    const bool live = wave == 0 && gn < N && gm0 < M;
+    RowsEpi epi;
+    if (live) rows_epilogue_loads(g, gm0, gn, epi);
+
+    // everything has been requested: zeros into the slots past K, and the first tile's weight fragments split
+#pragma unroll
+    for (int u = 0; u < LN_MAXU; ++u)
+        if (lane * 4 + u * 256 >= K) v[0][u] = v[1][u] = ga[u] = bt[u] = zero4;
+    bf16x8 fb0[2], lb0[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) rows_split8<NSPLIT>(xb[kk], fb0[kk], lb0[kk]);
+
+    // the prologue: rows 2 w, 2 w + 1 -> the image.  What column tile 0 owes memory (y, its planes, the statistics) stays in
+    // registers until the wave's last instruction: a store in front of a counted wait is waited for with the loads
+    float4 on[2][LN_MAXU];
+    float mean[2], rstd[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int rl = 2 * wave + i;
+        layernorm_row(v[i], ga, bt, K, n.eps, lane, mean[i], rstd[i], [&](int u, int c, const float4& o) {
+            unsigned short h[4], l[4];
+            split_bf16(o.x, h[0], l[0]); split_bf16(o.y, h[1], l[1]); split_bf16(o.z, h[2], l[2]); split_bf16(o.w, h[3], l[3]);
+            const int off = rows_ln_off(rl, c & ~7, K) + (c & 4);
+            *reinterpret_cast<uint2*>(img + off) = make_uint2(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16));
+            if (NSPLIT == 3) *reinterpret_cast<uint2*>(img + 16 * K + off) = make_uint2(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16));
+            on[i][u] = o;
+        });
+    }
+    auto store_rows = [&]() {
+        if (bx != 0) return;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int row = r0 + i;
+            if (row >= M) break;
+#pragma unroll
+            for (int u = 0; u < LN_MAXU; ++u) {
+                const int c = lane * 4 + u * 256;
+                if (c < K) {
+                    *reinterpret_cast<float4*>(n.y + (long)row * K + c) = on[i][u];
+                    store_planes4(PlaneOut{n.y_hi, n.y_lo, nullptr}, (long)row * n.ldp + c, on[i][u]);
+                }
+            }
+            if (lane == 0 && n.stats) {
+                n.stats[2 * row] = mean[i];
+                n.stats[2 * row + 1] = rstd[i];
+            }
+        }
+    };
+    __syncthreads();
+
+    for (int t = wave; t < ktiles; t += RT_WAVES) {
+        bf16x8 fa[2], la[2], fb[2], lb[2];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const int k = t * 64 + kk * 32;
+            if (t != wave) {
+                rows_load8(bw + k, xb[kk]);
+                rows_split8<NSPLIT>(xb[kk], fb[kk], lb[kk]);
+            } else {
+                fb[kk] = fb0[kk];
+                if (NSPLIT == 3) lb[kk] = lb0[kk];
+            }
+            const int off = rows_ln_off(lane & 15, k + koct, K);
+            fa[kk] = *reinterpret_cast<const bf16x8*>(img + off);
+            if (NSPLIT == 3) la[kk] = *reinterpret_cast<const bf16x8*>(img + 16 * K + off);
+        }
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {                      // (rows_tile's order)
+            if (NSPLIT == 3) {
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(la[kk], fb[kk], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk], lb[kk], acc, 0, 0, 0);
+            }
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk], fb[kk], acc, 0, 0, 0);
+        }
+        *reinterpret_cast<f32x4*>(part + (t * 64 + lane) * 4) = acc;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        // the K sum in tile order, then the epilogue
+        f32x4 acc = *reinterpret_cast<const f32x4*>(part + lane * 4);
+        for (int t = 1; t < ktiles; ++t) acc += *reinterpret_cast<const f32x4*>(part + (t * 64 + lane) * 4);
+        if (live) rows_epilogue(p.r, acc, gm0, gn, epi);
+    }
+    store_rows();
+}
+__device__ __forceinline__ void gemm_rows_ln_body_3(RowsLnParams p) { gemm_rows_ln_body<3>(p); }
+__device__ __forceinline__ void gemm_rows_ln_body_1(RowsLnParams p) { gemm_rows_ln_body<1>(p); }
+SLNLP_ZKERNEL(gemm_rows_ln_kernel_3, RT_THREADS, gemm_rows_ln_body_3)
+SLNLP_ZKERNEL(gemm_rows_ln_kernel_1, RT_THREADS, gemm_rows_ln_body_1)
+
 // The backward pair of one dY in ONE launch: blocks [0, nd) are the data gradient's tiles (dX = dY W, W m-major), the rest the weight
 // gradient's units (dW = dY^T x, db = column sums of dY).  Both read the same dY planes.
 struct RowsBwdParams {
@@ -474,6 +686,8 @@ static size_t rows_bwd_lds(int geo, int K) {
     const size_t w = (size_t)(RT_GEO[geo].mt + RT_WAVES) * 2 * RT_IMG * sizeof(unsigned short);      // the workgroup's dY images + the waves' x images
     return d > w ? d : w;
 }
+// the LayerNorm-prologue kernel: the partial tiles + the image of the 16 normalised rows, hi and lo (K = 512: 8 + 32 KiB; 1024: 16 + 64)
+static size_t rows_ln_lds(int K) { return rows_lds(0, K) + (size_t)2 * 16 * K * sizeof(unsigned short); }
 static dim3 rows_grid(int geo, int M, int N) { return dim3(ceil_div(N, 16 * RT_GEO[geo].nt), ceil_div(M, 16 * RT_GEO[geo].mt)); }
 static int rows_wgrad_units(const slnlp_gemm_args& w, int geo) { return ceil_div(w.M, 16 * RT_GEO[geo].mt) * ceil_div(w.N, 128); }
 
@@ -511,6 +725,8 @@ static int rows_init() {
                                                (int)std::min(rows_lds(geo, 64 * RT_MAX_KTILES), RT_LDS_MAX)) == hipSuccess &&
                      hipFuncSetAttribute((const void*)rows_bwd_kernel(prec, geo), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)std::min(rows_bwd_lds(geo, 64 * RT_MAX_KTILES), RT_LDS_MAX)) == hipSuccess;
+        ok = ok && hipFuncSetAttribute((const void*)gemm_rows_ln_kernel_3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_ln_lds(64 * RT_MAX_KTILES)) == hipSuccess &&
+             hipFuncSetAttribute((const void*)gemm_rows_ln_kernel_1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_ln_lds(64 * RT_MAX_KTILES)) == hipSuccess;
         if (!ok) {
             set_error("gemm_rows: cannot raise dynamic LDS limit: %s", hipGetErrorString(hipGetLastError()));
             return SLNLP_ERR_LAUNCH;
@@ -602,6 +818,47 @@ int gemm_rows(const slnlp_gemm_args& a, hipStream_t st) {
     return zlaunch(rows_kernel(a.precision, geo), rows_grid(geo, a.M, a.N), RT_THREADS, rows_lds(geo, a.K), st, "gemm_rows", p);
 }
 
+// whether a solo launch of this product takes the 16 x 16 tile, the only one the LayerNorm prologue is built for (a forced
+// SLNLP_ROWS_TILE other than 0 says no), and the row fits the prologue's registers
+bool gemm_rows_ln_covers(int M, int N, int K) {
+    return K % 64 == 0 && K <= LN_MAXU * 256 && ceil_div(K, 64) <= RT_MAX_KTILES && rows_geo(M, N, K, 1, false) == 0;
+}
+
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// C = epilogue( LayerNorm(x) W^T ) in one launch (gemm_rows_ln_body): `a` as for gemm_rows without its A operand, which is ln.x here
+int gemm_rows_ln(const slnlp_gemm_args& a, const RowsLn& ln, hipStream_t st) {
+    SLNLP_CHECK_ARG(!recording(), "gemm_rows_ln: a solo launch only (a lockstep program keeps layernorm_fwd and gemm_rows)");
+    SLNLP_CHECK_ARG(ln.x && ln.gamma && ln.beta && ln.y, "gemm_rows_ln: null pointer (x, gamma, beta and y are required)");
+    SLNLP_CHECK_ARG((ln.y_hi == nullptr) == (ln.y_lo == nullptr), "gemm_rows_ln: y's planes come as a pair (hi and lo), or not at all");
+    slnlp_gemm_args c = a;                                   // (the shared checks see x in the A operand's place)
+    c.A_hi = c.A_lo = reinterpret_cast<const uint16_t*>(ln.x);
+    c.lda_p = a.K;
+    SLNLP_TRY(check_rows_job(c, true, "gemm_rows_ln"));
+    SLNLP_CHECK_ARG(gemm_rows_ln_covers(a.M, a.N, a.K), "gemm_rows_ln: M=%d N=%d K=%d is not a 16 x 16-tile launch with K <= %d (or another tile is forced)",
+                    a.M, a.N, a.K, LN_MAXU * 256);
+    SLNLP_CHECK_ARG(ln.ldx >= a.K && ln.ldx % 4 == 0 && (!ln.y_hi || (ln.ldp >= a.K && ln.ldp % 4 == 0)), "gemm_rows_ln: row strides must cover K and be multiples of 4");
+    SLNLP_CHECK_ARG((((uintptr_t)ln.x | (uintptr_t)ln.gamma | (uintptr_t)ln.beta | (uintptr_t)ln.y) & 15) == 0 &&
+                        (((uintptr_t)ln.y_hi | (uintptr_t)ln.y_lo) & 7) == 0,
+                    "gemm_rows_ln: x, gamma, beta and y must be 16-byte aligned, y's planes 8-byte aligned");
+    // other workgroups of the launch still read x (and the epilogue's operands) while the first column tile's write y
+    const size_t x_bytes = ((size_t)(a.M - 1) * ln.ldx + a.K) * sizeof(float), y_bytes = (size_t)a.M * a.K * sizeof(float);
+    SLNLP_CHECK_ARG(!ranges_overlap(ln.x, x_bytes, ln.y, y_bytes), "gemm_rows_ln: x and y overlap");
+    SLNLP_CHECK_ARG(!a.resid || !ranges_overlap(a.resid, ((size_t)(a.M - 1) * a.ldr + a.N) * sizeof(float), ln.y, y_bytes), "gemm_rows_ln: resid and y overlap");
+    SLNLP_CHECK_ARG(!a.gate || !ranges_overlap(a.gate, ((size_t)(a.M - 1) * a.ldg + a.N) * sizeof(float), ln.y, y_bytes), "gemm_rows_ln: gate and y overlap");
+    RowsLnParams p;
+    p.r.a = a;
+    p.r.a.A_hi = p.r.a.A_lo = nullptr;
+    p.r.drop_thr = dropout_threshold(a.drop_p);
+    p.r.drop_scale = 1.f / (1.f - a.drop_p);
+    p.ln = ln;
+    SLNLP_TRY(rows_init());
+    return zlaunch(a.precision == 3 ? gemm_rows_ln_kernel_3 : gemm_rows_ln_kernel_1, rows_grid(0, a.M, a.N), RT_THREADS, rows_ln_lds(a.K), st, "gemm_rows_ln", p);
+}
+
 }  // namespace slnlp
 
 #if SLNLP_PROBE_FENCES == 256
@@ -634,6 +891,17 @@ extern "C" int slnlp_set_rows_tile(int tile) {
     }
     slnlp::g_rows_geo.store(tile, std::memory_order_relaxed);
     return 0;
+}
+
+extern "C" int slnlp_gemm_rows_ln(const slnlp_gemm_args* args, const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, float* y,
+                                  float* stats, uint16_t* y_hi, uint16_t* y_lo, int64_t ldp, void* stream) {
+    if (!args) {
+        slnlp::set_error("gemm_rows_ln: null args");
+        return SLNLP_ERR_INVALID_ARG;
+    }
+    slnlp::RowsLn ln;
+    ln.x = x; ln.ldx = ldx; ln.gamma = gamma; ln.beta = beta; ln.eps = eps; ln.y = y; ln.stats = stats; ln.y_hi = y_hi; ln.y_lo = y_lo; ln.ldp = ldp;
+    return slnlp::gemm_rows_ln(*args, ln, (hipStream_t)stream);
 }
 
 extern "C" int slnlp_gemm_rows(const slnlp_gemm_args* args, void* stream) {

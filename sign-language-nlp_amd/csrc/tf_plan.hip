@@ -69,6 +69,10 @@ int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, sln
         const char* e = getenv("SLNLP_DEC_ROWS");
         p->use_rows = p->use_planes && cfg->E <= 1024 && cfg->F <= 1024 && !(e && atoi(e) == 0);
     }
+    {   // SLNLP_DEC_LN_FUSED=0: a new plan starts with the decoder's LayerNorms as launches of their own (A / B of one build)
+        const char* e = getenv("SLNLP_DEC_LN_FUSED");
+        p->dec_ln_fused = !(e && atoi(e) == 0);
+    }
     if (ok && cfg->precision == 8) {     // rows the fp8 forward products read: one {offset, K} entry each, uploaded once
         std::vector<QuantRow> rows;
         auto block = [&](long off, int nrows, int K) {
@@ -144,16 +148,24 @@ int slnlp_tf_create(const slnlp_tf_config* cfg, const slnlp_tf_buffers* buf, sln
 
 // Decoder layer l up to its cross-attention query: self-attention over ONE key (softmax == 1 -> out_proj(v_proj(t));
 // the q/k rows of in_proj are dead; in train mode the weight-1 "attention" is still dropped per (row, head) -- fused into
-// the V projection), residual + norm1, then q = in_proj_q(t1) (transformer.py:82-87).
-int slnlp_tf_plan::dec_self_block(int l, const Mat& t, int B, float p, hipStream_t st) const {
+// the V projection), residual + norm1, then q = in_proj_q(t1) (transformer.py:82-87).  The layer's input t is the target
+// embedding or the layer below's norm3 output -- that LayerNorm runs here, with the V projection that alone reads it on the chain.
+int slnlp_tf_plan::dec_self_block(int l, int B, float p, hipStream_t st) const {
     const int E = cfg.E, dh = E / cfg.H;
     const DecP& q = L.dec[l];
     const DecA& a = w.dec[l];
     // (B-row products on planes, gemm_rows.hip: every producer also emits its output as the next product's operand)
-    SLNLP_TRY(linear(t, q.sin_w + 2L * E * E, q.sin_b + 2 * E, B, E, E, a.v, Epi().dropped(p, dec_site(l, 0), dh).also(a.vp), st));
-    SLNLP_TRY(linear(rview(a.v, a.vp, E), q.sout_w, q.sout_b, B, E, E, a.y1, Epi().dropped(p, dec_site(l, 1)).plus(t.f), st));
-    SLNLP_TRY(layernorm_fwd(a.y1, P(q.n1_w), P(q.n1_b), B, E, 1e-5f, a.t1, a.st1, st, rout(a.t1p)));
-    return linear(rview(a.t1, a.t1p, E), q.cin_w, q.cin_b, B, E, E, a.q, Epi(), st);
+    const Epi ev = Epi().dropped(p, dec_site(l, 0), dh).also(a.vp);
+    const float* t = l == 0 ? w.t0 : w.dec[l - 1].t3;
+    if (l == 0) {
+        SLNLP_TRY(linear(rview(w.t0, w.t0p, E), q.sin_w + 2L * E * E, q.sin_b + 2 * E, B, E, E, a.v, ev, st));
+    } else {
+        const DecP& qb = L.dec[l - 1];
+        const DecA& b = w.dec[l - 1];
+        SLNLP_TRY(ln_linear(b.y3, qb.n3_w, qb.n3_b, b.t3, b.st3, b.t3p, q.sin_w + 2L * E * E, q.sin_b + 2 * E, B, E, a.v, ev, st));
+    }
+    SLNLP_TRY(linear(rview(a.v, a.vp, E), q.sout_w, q.sout_b, B, E, E, a.y1, Epi().dropped(p, dec_site(l, 1)).plus(t), st));
+    return ln_linear(a.y1, q.n1_w, q.n1_b, a.t1, a.st1, a.t1p, q.cin_w, q.cin_b, B, E, a.q, Epi(), st);
 }
 
 int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int train, float* logp_out, hipStream_t st) {
@@ -173,7 +185,7 @@ int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int t
         SLNLP_TRY(ensure_wq(st));
     }
     SLNLP_TRY(embed_fwd(y, 1, B, 1, E, c.Vt, P(L.tgt_emb), buf.pe, w.t0, sqrtf((float)E), p, SITE_TGT_EMB, rng, c.pad_tgt, st, rout(w.t0p)));
-    SLNLP_TRY(dec_self_block(0, rview(w.t0, w.t0p, E), B, p, st));
+    SLNLP_TRY(dec_self_block(0, B, p, st));
     SLNLP_TRY(embed_fwd(X, S, B, S, E, c.Vs, P(L.src_emb), buf.pe, w.x0, sqrtf((float)E), p, SITE_SRC_EMB, rng, -1, st, pout(w.x0p), w.emb_keep));
 
     Mat x = view(w.x0, w.x0p, E);
@@ -193,11 +205,14 @@ int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int t
     }
     SLNLP_TRY(layernorm_fwd(x.f, P(L.encn_w), P(L.encn_b), M, E, 1e-5f, w.mem, w.st_mem, st, pout(w.memp)));
 
-    Mat t = rview(w.t0, w.t0p, E);
+    // The decoder's LayerNorms go through ln_linear with the one product that reads them on the chain (one launch for both where
+    // gemm_rows.hip's prologue kernel covers it): norm1 + the query projection and, for l > 0, the layer below's norm3 + the V
+    // projection in dec_self_block; norm2 + linear1 here; the final norm + the generator behind the loop.  Only the last layer's
+    // norm3 feeds a LayerNorm, not a product, and keeps its launch.
     for (int l = 0; l < c.N; ++l) {
         const DecP& q = L.dec[l];
         const DecA& a = w.dec[l];
-        if (l > 0) SLNLP_TRY(dec_self_block(l, t, B, p, st));   // (layer 0's block ran ahead of the encoder, above)
+        if (l > 0) SLNLP_TRY(dec_self_block(l, B, p, st));   // (layer 0's block ran ahead of the encoder, above)
         // cross-attention over the memory itself: with ONE query per sequence the K / V projections of the S memory rows
         // re-associate into B-row products (attention_mem.hip) -- no [S*B, 2E] projection, no K|V gradient GEMMs:
         // qk = Wk_h^T q_h (batched GEMM) -> scores / softmax / dropout / mbar (+ ctx0 = bv sum_s p_s) -> ctx = Wv_h mbar + ctx0
@@ -209,14 +224,11 @@ int slnlp_tf_plan::forward_impl(const int64_t* X, const int64_t* y, int B, int t
         const slnlp_gemm_args j2 = head_reduce(a.mbar, Wv, a.xctx, a.xctx, use_rows ? &a.xctxp : nullptr, B, H, dh, prec3());
         SLNLP_TRY(gemm_group(&j2, 1, st));
         SLNLP_TRY(linear(rview(a.xctx, a.xctxp, E), q.cout_w, q.cout_b, B, E, E, a.y2, Epi().dropped(p, dec_site(l, 3)).plus(a.t1), st));
-        SLNLP_TRY(layernorm_fwd(a.y2, P(q.n2_w), P(q.n2_b), B, E, 1e-5f, a.t2, a.st2, st, rout(a.t2p)));
-        SLNLP_TRY(linear(rview(a.t2, a.t2p, E), q.l1_w, q.l1_b, B, F, E, a.h, Epi().relu().dropped(p, dec_site(l, 4)).also(a.hp), st));
+        SLNLP_TRY(ln_linear(a.y2, q.n2_w, q.n2_b, a.t2, a.st2, a.t2p, q.l1_w, q.l1_b, B, F, a.h, Epi().relu().dropped(p, dec_site(l, 4)).also(a.hp), st));
         SLNLP_TRY(linear(rview(a.h, a.hp, F), q.l2_w, q.l2_b, B, E, F, a.y3, Epi().dropped(p, dec_site(l, 5)).plus(a.t2), st));
-        SLNLP_TRY(layernorm_fwd(a.y3, P(q.n3_w), P(q.n3_b), B, E, 1e-5f, a.t3, a.st3, st, rout(a.t3p)));
-        t = rview(a.t3, a.t3p, E);
+        if (l == c.N - 1) SLNLP_TRY(layernorm_fwd(a.y3, P(q.n3_w), P(q.n3_b), B, E, 1e-5f, a.t3, a.st3, st, rout(a.t3p)));
     }
-    SLNLP_TRY(layernorm_fwd(t.f, P(L.decn_w), P(L.decn_b), B, E, 1e-5f, w.tfin, w.st_fin, st, rout(w.tfinp)));
-    SLNLP_TRY(linear(rview(w.tfin, w.tfinp, E), L.lin_w, L.lin_b, B, c.Vt, E, w.logits, Epi().stride(Vp), st));
+    SLNLP_TRY(ln_linear(w.dec[c.N - 1].t3, L.decn_w, L.decn_b, w.tfin, w.st_fin, w.tfinp, L.lin_w, L.lin_b, B, c.Vt, w.logits, Epi().stride(Vp), st));
     // log_softmax (transformer.py:88-89) + the criterion skorch applies to it (helper.py:61-70)
     // the caller's copy of the log-probs is written by the same kernel (no device-to-device copy); in lockstep it lands
     // in the epoch buffer at the batch's row offset and the loss in the epoch's loss history
@@ -362,6 +374,15 @@ int slnlp_tf_set_dmem_batched(slnlp_tf_plan* pl, int on) {
     if (pl->dmem_batched == (on != 0)) return 0;
     pl->dmem_batched = on != 0;
     ++pl->opts.gen;            // a lockstep group re-records its programs: the launch sequence changed
+    pl->drop_graphs();
+    return 0;
+}
+
+int slnlp_tf_set_dec_ln_fused(slnlp_tf_plan* pl, int on) {
+    SLNLP_CHECK_ARG(pl, "tf_set_dec_ln_fused: null plan");
+    if (pl->dec_ln_fused == (on != 0)) return 0;
+    pl->dec_ln_fused = on != 0;
+    ++pl->opts.gen;            // (as every switch of the launch sequence; a recorded program itself never holds the fused launch)
     pl->drop_graphs();
     return 0;
 }

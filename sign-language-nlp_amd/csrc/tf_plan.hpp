@@ -375,6 +375,10 @@ struct slnlp_tf_plan : PlanCore {
     // slnlp_tf_set_dmem_batched: d memory of all decoder layers (and their d bv) in ONE launch behind the decoder's layer loop
     // (attention_mem.hip: xmem_dmem_all) instead of a launch per layer inside it -- nothing on the decoder's chain reads d memory
     bool dmem_batched = true;
+    // slnlp_tf_set_dec_ln_fused (initial value: SLNLP_DEC_LN_FUSED=0|1, default 1): a decoder LayerNorm that feeds exactly one B-row
+    // product on the chain (norm1 -> the cross-attention query projection, norm2 -> linear1, norm3 -> the next layer's V projection,
+    // the final norm -> the generator) runs as that product's prologue instead of a launch of its own (ln_linear)
+    bool dec_ln_fused = true;
     // precision 8: the forward products run on the fp8 MFMA (e4m3 activations, scale 1; e4m3 weights with one scale per
     // output row, re-quantised from the fp32 master weights whenever the arena has moved); the backward stays split-bf16
     int prec3() const { return cfg.precision == 8 ? 3 : cfg.precision; }
@@ -448,7 +452,7 @@ struct slnlp_tf_plan : PlanCore {
     int enc_site(int l, int k) const { return SITE_LAYER0 + l * SITE_PER_LAYER + k; }
     int dec_site(int l, int k) const { return SITE_LAYER0 + (cfg.N + l) * SITE_PER_LAYER + k; }
 
-    int dec_self_block(int l, const Mat& t, int B, float p, hipStream_t st) const;
+    int dec_self_block(int l, int B, float p, hipStream_t st) const;
 
     // ---- an activation as the operand of the plan's mode: the encoder's S*B-row products read planes when use_planes, the decoder's
     // B-row products when use_rows; else both read fp32.  (The fp32 pointer travels along: residuals and LayerNorms read it.)
@@ -477,6 +481,23 @@ struct slnlp_tf_plan : PlanCore {
         wq.q8 = w.wq + woff;
         e.col_scale = w.wscale + qrow0.at(woff);
         return gemm(linear_job(planes(x.p, K, Mat::Q8), planes(wq, K, Mat::Q8), M, N, K, y, e, 8), st);
+    }
+    // t = LayerNorm(xin) (gamma, beta at arena offsets gw, gb; fp32, planes tp and stats out) followed by the Linear y[M, N] = t W^T + b
+    // that alone reads t on the chain.  One launch (gemm_rows.hip: the LayerNorm is the product's prologue, same bits) where the
+    // product is a solo fit's 16 x 16-tile B-row launch; otherwise the two launches.  A recorder always sees the two: lockstep
+    // programs keep their length, and their merged launches never take the prologue's kernel.
+    int ln_linear(const float* xin, long gw, long gb, float* t, float* stats, const PP& tp, long woff, long boff, int M, int N, float* y, Epi e,
+                  hipStream_t st) const {
+        const int E = cfg.E;
+        if (dec_ln_fused && use_rows && rows_for(M, e.drop_head_dim) && gemm_rows_ln_covers(M, N, E) && !recording()) {
+            e.bias = P(boff);
+            e.rng = buf.rng;
+            RowsLn ln;
+            ln.x = xin; ln.ldx = E; ln.gamma = P(gw); ln.beta = P(gb); ln.eps = 1e-5f; ln.y = t; ln.stats = stats; ln.y_hi = tp.hi; ln.y_lo = tp.lo; ln.ldp = E;
+            return gemm_rows_ln(linear_job(rview(t, tp, E), f32(P(woff), E), M, N, E, y, e, prec3()), ln, st);
+        }
+        SLNLP_TRY(layernorm_fwd(xin, P(gw), P(gb), M, E, 1e-5f, t, stats, st, rout(tp)));
+        return linear(rview(t, tp, E), woff, boff, M, N, E, y, e, st);
     }
     // The gradient pair of that Linear: wg: dW = dY^T x, db = colsum(dY) into the gradient arena at woff, boff; dg: dX = dY W with the
     // epilogue `e` (gate, per-head dropout, residual; fp32 and / or planes out).  Same family rule, from dY's view.  A data gradient

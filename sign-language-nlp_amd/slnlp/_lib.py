@@ -94,6 +94,7 @@ SIGNATURES = {
     "slnlp_gemm_wd": (i32, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), vp, i64, vp]),
     "slnlp_gemm_wd_plan": (i32, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "slnlp_gemm_rows": (i32, [C.POINTER(GemmArgs), vp]),
+    "slnlp_gemm_rows_ln": (i32, [C.POINTER(GemmArgs), vp, i64, vp, vp, f32, vp, vp, vp, vp, i64, vp]),
     "slnlp_gemm_rows_bwd": (i32, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), vp]),
     "slnlp_set_rows_tile": (i32, [i32]),
     "slnlp_quant_rows_fp8": (i32, [vp, i64, i32, i32, vp, i64, vp, vp]),
@@ -201,6 +202,7 @@ SIGNATURES = {
     "slnlp_tf_set_param_groups": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),
     "slnlp_tf_set_averaging": (i32, [vp, vp, vp, i32, f32]),
     "slnlp_tf_set_dmem_batched": (i32, [vp, i32]),
+    "slnlp_tf_set_dec_ln_fused": (i32, [vp, i32]),
     "slnlp_set_stream_policy": (i32, [i32]),
     "slnlp_set_thread_stream_policy": (i32, [i32]),
     "slnlp_set_backward_passes": (i32, [i32, i32]),
@@ -250,6 +252,8 @@ def load():
                                "only compute path (no CPU fallback)")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if os.environ.get("SLNLP_PROBE_LIB") and not hasattr(lib, name):
+                continue              # an A / B library built from an older tree (tools/ab_bench.py) lacks the newer entry points
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

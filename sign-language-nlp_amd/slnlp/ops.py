@@ -177,6 +177,29 @@ def gemm_rows(Ap, W, *, M, N, K, out=None, precision=3, bias=None, relu=0, gate=
     return (out, cp) if want_planes else out
 
 
+def gemm_rows_ln(x, gamma, beta, W, *, M, N, K, y, stats=None, y_planes=None, eps=1e-5, out=None, precision=3, bias=None, relu=0,
+                 drop_p=0.0, drop_site=0, rng=None, drop_head_dim=0, resid=None, out_planes=None):
+    """C = epilogue(LayerNorm(x) W^T) in one launch (slnlp_gemm_rows_ln): x [M, K] fp32 is the LayerNorm's input; the normalised
+    rows go to ``y`` [M, K], (mean, rstd) to ``stats`` [M, 2] and, as (hi, lo) planes, to ``y_planes`` -- what layernorm_fwd
+    followed by gemm_rows would have left, bit for bit.  ``out_planes``: also emit C as (hi, lo) planes."""
+    _lib.require_gpu()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    a = GemmArgs()
+    a.C, a.ldc, a.M, a.N, a.K = ptr(out), out.stride(0), M, N, K
+    a.a_kmajor, a.b_kmajor, a.precision = 1, 1, precision
+    a.B, a.ldb = ptr(W), W.stride(0)
+    a.bias, a.relu = ptr(bias), int(relu)
+    a.drop_p, a.drop_site, a.rng, a.drop_head_dim = drop_p, drop_site, ptr(rng), drop_head_dim
+    a.resid, a.ldr = ptr(resid), (resid.stride(0) if resid is not None else 0)
+    if out_planes is not None:
+        a.C_hi, a.C_lo, a.ldc_p = ptr(out_planes[0]), ptr(out_planes[1]), out_planes[0].stride(0)
+    yh, yl = y_planes if y_planes is not None else (None, None)
+    check(load().slnlp_gemm_rows_ln(C.byref(a), ptr(x), x.stride(0), ptr(gamma), ptr(beta), eps, ptr(y), ptr(stats), ptr(yh), ptr(yl),
+                                    yh.stride(0) if yh is not None else 0, stream_ptr()), "gemm_rows_ln")
+    return out
+
+
 def gemm_rows_bwd(dYp, W, Xp, *, B, Nout, Kin, precision=3, gate=None, gate_scale=1.0, gate_mode=0, drop_p=0.0, drop_site=0, rng=None,
                   drop_head_dim=0, resid=None, want_planes=False, want_db=True):
     """dX = dY W (+ epilogue), dW = dY^T x, db = colsum(dY) in one launch (slnlp_gemm_rows_bwd): dYp [B, Nout] and Xp [B, Kin] as

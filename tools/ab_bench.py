@@ -2,7 +2,7 @@
 library under sign-language-nlp_amd/lib/ (libslnlp.so, or libslnlp_probe<name>.so picked through SLNLP_PROBE_LIB=<name>); the
 workloads run in fresh child processes, variants interleaved, `--rounds` times.
 
-    python tools/ab_bench.py --variants ,old --workloads cfg2,cfg5,ls15 [--rounds 2]
+    python tools/ab_bench.py --variants ,old --workloads cfg2,cfg5,ls15 [--rounds 2] [--json out.json]
         ""    = the product library;  old = lib/libslnlp_probeold.so (make VARIANT=old in a checkout of the old tree);
         NAME=VALUE = the product library with that environment knob (e.g. SLNLP_DEC_ROWS=0); join with "+"
 workloads: cfg2 / cfg5 / cfg3 / cfg3gru (bench.py lines, ms per step), ls4 / ls15 (tools/bench_lockstep.py, ms per lockstep step),
@@ -15,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--variants", default=",old")
 ap.add_argument("--workloads", default="cfg2,cfg5,ls15")
 ap.add_argument("--rounds", type=int, default=2)
+ap.add_argument("--json", default=None, help="also write every round's value and each build's spread between rounds to this file")
 a = ap.parse_args()
 
 
@@ -54,3 +55,11 @@ print("--- ms per step: min over rounds (all)")
 for (wl, v), ms in res.items():
     ok = [m for m in ms if m is not None]
     print(f"{wl:8s} {v or 'product':10s} {min(ok) if ok else None}   {ms}")
+if a.json:      # every round's value, and each build's own spread between rounds: (max - min) / min, in per cent
+    out = {}
+    for (wl, v), ms in res.items():
+        ok = [m for m in ms if m is not None]
+        out.setdefault(wl, {})[v or "product"] = {"ms": ms, "spread_pct": round(100.0 * (max(ok) - min(ok)) / min(ok), 3) if ok else None}
+    with open(a.json, "w") as f:
+        json.dump({"rounds": a.rounds, "variants": [v or "product" for v in a.variants.split(",")], "ms_per_step": out}, f, indent=1)
+        f.write("\n")
