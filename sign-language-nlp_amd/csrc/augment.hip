@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -69,11 +70,6 @@ __device__ __forceinline__ void augment_rows_body(const int64_t* __restrict__ X,
 }
 SLNLP_ZKERNEL(augment_rows_kernel, 256, augment_rows_body)
 
-static bool augment_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 int augment_rows(const int64_t* X, const int64_t* L, int64_t n, int64_t S, int64_t pad, int64_t unk, float p_drop, float p_mask,
                  uint64_t seed, int64_t epoch, int64_t* X_out, int64_t* L_out, hipStream_t st) {
     SLNLP_CHECK_ARG(X && L && X_out && L_out, "augment_rows: null pointer");
@@ -85,11 +81,10 @@ int augment_rows(const int64_t* X, const int64_t* L, int64_t n, int64_t S, int64
     SLNLP_CHECK_ARG(p_mask >= 0.0f && p_mask < 1.0f, "augment_rows: p_mask=%g outside [0, 1)", (double)p_mask);
     const size_t x_bytes = (size_t)n * (size_t)S * 8, l_bytes = (size_t)n * 8;
     // not in-place: a row's stores would run ahead of another chunk's loads, and L is read while L_out is written
-    SLNLP_CHECK_ARG(!augment_overlap(X_out, x_bytes, X, x_bytes), "augment_rows: X_out overlaps X (the kernel is not in-place)");
-    SLNLP_CHECK_ARG(!augment_overlap(L_out, l_bytes, L, l_bytes), "augment_rows: L_out overlaps L (the kernel is not in-place)");
-    SLNLP_CHECK_ARG(!augment_overlap(X_out, x_bytes, L, l_bytes) && !augment_overlap(L_out, l_bytes, X, x_bytes) &&
-                        !augment_overlap(X_out, x_bytes, L_out, l_bytes),
-                    "augment_rows: the id and length buffers overlap");
+    const Span x = {X, x_bytes, "X"}, l = {L, l_bytes, "L"}, xo = {X_out, x_bytes, "X_out"}, lo = {L_out, l_bytes, "L_out"};
+    SLNLP_CHECK_ARG(!spans_overlap(xo, x), "augment_rows: X_out overlaps X (the kernel is not in-place)");
+    SLNLP_CHECK_ARG(!spans_overlap(lo, l), "augment_rows: L_out overlaps L (the kernel is not in-place)");
+    SLNLP_CHECK_ARG(!spans_overlap(xo, l) && !spans_overlap(lo, x) && !spans_overlap(xo, lo), "augment_rows: the id and length buffers overlap");
     const int blocks = (int)std::min<int64_t>((n + 3) / 4, AUGMENT_MAX_BLOCKS);
     return zlaunch(augment_rows_kernel, dim3(blocks), 256, 0, st, "augment_rows", X, L, (int)n, (int)S, pad, unk, dropout_threshold(p_drop),
                    dropout_threshold(p_mask), (unsigned long long)seed, (unsigned)epoch, X_out, L_out);

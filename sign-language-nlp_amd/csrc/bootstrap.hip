@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -158,12 +159,6 @@ __device__ __forceinline__ void bootstrap_body(const int64_t* __restrict__ y, co
 }
 SLNLP_ZKERNEL(bootstrap_kernel, 256, bootstrap_body)
 
-struct BootSpan { const void* p; size_t bytes; const char* name; };
-static bool boot_overlap(const BootSpan& a, const BootSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a.p && b.p && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int bootstrap_scores(const int64_t* y, const int32_t* pred, const int32_t* rank, const double* values, int64_t ldv, int Q, int64_t N, int V,
                      int top_k, int B, uint64_t seed, double* stats, int32_t* counts, hipStream_t st) {
     SLNLP_CHECK_ARG(Q >= 0 && Q <= SLNLP_BOOT_MAX_VALUES, "bootstrap_scores: Q=%d outside 0..%d", Q, SLNLP_BOOT_MAX_VALUES);
@@ -178,13 +173,10 @@ int bootstrap_scores(const int64_t* y, const int32_t* pred, const int32_t* rank,
                         (((uintptr_t)y | (uintptr_t)values | (uintptr_t)stats) & 7) == 0,
                     "bootstrap_scores: misaligned pointer");
     const size_t n = (size_t)N, b = (size_t)B;
-    const BootSpan in[4] = {{y, n * 8, "y"}, {pred, n * 4, "pred"}, {top_k ? rank : nullptr, n * 4, "rank"},
+    const Span in[4] = {{y, n * 8, "y"}, {pred, n * 4, "pred"}, {top_k ? rank : nullptr, n * 4, "rank"},
                             {Q ? values : nullptr, Q ? ((n - 1) * (size_t)ldv + (size_t)Q) * 8 : 0, "values"}};
-    const BootSpan out[2] = {{stats, b * (size_t)(SLNLP_BOOT_FIXED + Q) * 8, "stats"}, {counts, b * (3 * (size_t)V + 1) * 4, "counts"}};
-    for (int o = 0; o < 2; ++o)
-        for (int i = 0; i < 4; ++i)
-            SLNLP_CHECK_ARG(!boot_overlap(out[o], in[i]), "bootstrap_scores: output %s overlaps input %s", out[o].name, in[i].name);
-    SLNLP_CHECK_ARG(!boot_overlap(out[0], out[1]), "bootstrap_scores: outputs stats and counts overlap");
+    const Span out[2] = {{stats, b * (size_t)(SLNLP_BOOT_FIXED + Q) * 8, "stats"}, {counts, b * (3 * (size_t)V + 1) * 4, "counts"}};
+    SLNLP_TRY(check_no_overlap("bootstrap_scores", out, in));
     return zlaunch(bootstrap_kernel, dim3(B), 256, 3 * (size_t)V * sizeof(int), st, "bootstrap_scores", y, pred, top_k ? rank : nullptr,
                    Q ? values : nullptr, (long)(Q ? ldv : 0), Q, (int)N, V, top_k, (unsigned long long)seed, stats, counts);
 }

@@ -41,6 +41,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -222,12 +223,6 @@ __device__ __forceinline__ void scale_logp_body(const float* logp, long ld, int 
 }
 SLNLP_ZKERNEL(scale_logp_kernel, 256, scale_logp_body)
 
-static bool cal_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-static size_t cal_matrix_bytes(int64_t N, int64_t ld, int64_t V) { return ((size_t)(N - 1) * (size_t)ld + (size_t)V) * 4; }
-
 int64_t fit_temperature_scratch_bytes(int64_t N) {
     if (N < 1 || N > INT_MAX) {
         set_error("fit_temperature_scratch_bytes: N=%ld outside 1..%d", (long)N, INT_MAX);
@@ -239,18 +234,14 @@ int64_t fit_temperature_scratch_bytes(int64_t N) {
 int fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, void* state, void* scratch,
                     int64_t scratch_bytes, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && y && state && scratch, "fit_temperature: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "fit_temperature: N=%ld outside 1..%d", (long)N, INT_MAX);
-    SLNLP_CHECK_ARG(V >= 1 && V <= INT_MAX, "fit_temperature: V=%ld outside 1..%d", (long)V, INT_MAX);
-    SLNLP_CHECK_ARG(ld >= V, "fit_temperature: ld=%ld is less than V=%ld", (long)ld, (long)V);
-    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "fit_temperature: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
+    Span z;
+    SLNLP_TRY(check_logp_matrix("fit_temperature", logp, N, INT_MAX, V, INT_MAX, ld, &z));
     SLNLP_CHECK_ARG(scratch_bytes >= N * 32, "fit_temperature: scratch of %ld bytes is too small, %ld rows need %ld",
                     (long)scratch_bytes, (long)N, (long)(N * 32));
     SLNLP_CHECK_ARG(((uintptr_t)scratch & 31) == 0, "fit_temperature: scratch is not 32-byte aligned");
     SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0 && (((uintptr_t)y | (uintptr_t)state) & 7) == 0, "fit_temperature: misaligned pointer");
-    const size_t z_bytes = cal_matrix_bytes(N, ld, V), y_bytes = (size_t)N * 8, t_bytes = (size_t)N * 32;
-    SLNLP_CHECK_ARG(!cal_overlap(state, SLNLP_CAL_STATE_BYTES, logp, z_bytes) && !cal_overlap(state, SLNLP_CAL_STATE_BYTES, y, y_bytes) &&
-                        !cal_overlap(scratch, t_bytes, logp, z_bytes) && !cal_overlap(scratch, t_bytes, y, y_bytes) &&
-                        !cal_overlap(scratch, t_bytes, state, SLNLP_CAL_STATE_BYTES),
+    const Span labels = {y, (size_t)N * 8, "y"}, s = {state, SLNLP_CAL_STATE_BYTES, "state"}, t = {scratch, (size_t)N * 32, "scratch"};
+    SLNLP_CHECK_ARG(!spans_overlap(s, z) && !spans_overlap(s, labels) && !spans_overlap(t, z) && !spans_overlap(t, labels) && !spans_overlap(t, s),
                     "fit_temperature: state or scratch overlaps an input or each other");
     const int blocks = (int)std::min<int64_t>((N + 3) / 4, CAL_MAX_BLOCKS);
     for (int eval = 0; eval < CAL_EVALS; ++eval) {
@@ -270,11 +261,11 @@ int scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double
     SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N && ld_out <= INT64_MAX / 8 / N, "scale_logp: ld=%ld / ld_out=%ld times N=%ld is no addressable matrix",
                     (long)ld, (long)ld_out, (long)N);
     SLNLP_CHECK_ARG((((uintptr_t)logp | (uintptr_t)out) & 3) == 0 && ((uintptr_t)beta_dev & 7) == 0, "scale_logp: misaligned pointer");
-    const size_t in_bytes = cal_matrix_bytes(N, ld, V), out_bytes = cal_matrix_bytes(N, ld_out, V);
+    const Span z = {logp, matrix_bytes(N, ld, V), "logp"}, o = {out, matrix_bytes(N, ld_out, V), "out"};
     const bool in_place = (const float*)out == logp && ld_out == ld;
-    SLNLP_CHECK_ARG(in_place || !cal_overlap(out, out_bytes, logp, in_bytes),
+    SLNLP_CHECK_ARG(in_place || !spans_overlap(o, z),
                     "scale_logp: out overlaps logp without being logp itself (in place means the same pointer and the same row stride)");
-    SLNLP_CHECK_ARG(!cal_overlap(out, out_bytes, beta_dev, 8), "scale_logp: out overlaps beta");
+    SLNLP_CHECK_ARG(!spans_overlap(o, Span{beta_dev, 8, "beta"}), "scale_logp: out overlaps beta");
     const int blocks = (int)std::min<int64_t>((N + 3) / 4, CAL_MAX_BLOCKS);
     return zlaunch(scale_logp_kernel, dim3(blocks), 256, 0, st, "scale_logp", logp, (long)ld, (int)N, (int)V, beta_dev, out, (long)ld_out);
 }

@@ -4,9 +4,8 @@
 // tests/conformal_ref.py restates them in numpy.
 //
 // conformal_rows: z float32 log-probs [N, ld] (V columns used), beta = beta_dev ? beta_dev[0] : 1, p_c = exp(beta z_c - a) / s0 with
-// topk_rows' two passes statement by statement (same loop, same expression, same reduction order: p of the arg-max is that
-// kernel's prob[i, 0] bit for bit).  One wave per row, one row per 64-thread block (rows over a grid-stride loop), so every
-// barrier is the wave's own:
+// a and s0 from the row head of logp_row.hpp, which topk_rows shares (p of the arg-max is that kernel's prob[i, 0] bit for bit).
+// One wave per row, one row per 64-thread block (rows over a grid-stride loop), so every barrier is the wave's own:
 //   1. the row goes to LDS as 64-bit keys, ~rank_key(value) << 32 | column -- ascending keys are score_beats' order, equal values
 //      by ascending column for free; the padding up to M, the next power of two >= max(V, 64), is ~0 and sorts last; one bitonic
 //      network over M, every lane taking M / 128 compare-exchanges per step;
@@ -27,6 +26,8 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "logp_row.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -58,14 +59,9 @@ __device__ __forceinline__ void conformal_rows_body(const float* __restrict__ lo
         int64_t label = -1;
         if (y) label = y[r];
         const bool label_ok = label >= 0 && label < V;   // a label outside the columns is never used as an index
-        float zmax = -INFINITY;                          // (any column beats this start: -inf at column j ties and j < INT_MAX)
-        int pred = INT_MAX;
-        for (int j = lane; j < V; j += 64) {
-            const float x = row[j];
-            if (score_beats(x, j, zmax, pred)) { zmax = x; pred = j; }
-        }
-        wave_best(zmax, pred);                           // a NaN anywhere in the row wins: zmax is then no finite number
-        if (!(fabsf(zmax) < INFINITY)) {                 // wave-uniform: no set can be formed
+        const LogpRowMax top = logp_row_argmax(row, V, lane);
+        const float zmax = top.zmax;
+        if (!top.finite) {                                   // wave-uniform: no set can be formed
             if (lane == 0) {
                 if (score) score[r] = qnan;
                 if (rows) *(int4*)(rows + 4 * r) = int4{0, 0, 0, -2};
@@ -73,20 +69,8 @@ __device__ __forceinline__ void conformal_rows_body(const float* __restrict__ lo
             if (sets && lane < W) sets[r * W + lane] = 0u;
             continue;
         }
-        const double a = beta * (double)zmax;            // beta > 0: the maximum of beta z
-        double rest = 0.0, at_max = 0.0;                 // as in topk_rows: sum e - 1 without the 1 ever entering a sum
-        for (int j = lane; j < V; j += 64) {
-            const float zf = row[j];
-            if (zf == zmax) {
-                at_max += 1.0;
-            } else {
-                const double e = exp(beta * (double)zf - a);
-                rest += e;
-            }
-        }
-        const double n_max = wave_sum_d(at_max);         // whole numbers, summed exactly
-        rest = wave_sum_d(rest) + (n_max - 1.0);
-        const double s0 = 1.0 + rest;
+        const LogpRowSums h = logp_row_sums(row, V, lane, beta, zmax);
+        const double a = h.a, s0 = h.s0;
         // 1. the keys and their sort
         for (int j = lane; j < M; j += 64)
             keys[j] = j < V ? ((unsigned long long)(~rank_key(row[j])) << 32) | (unsigned)j : ~0ull;
@@ -243,21 +227,12 @@ __device__ __forceinline__ void conformal_count_body(const int* __restrict__ row
 SLNLP_ZKERNEL(conformal_count_kernel, 256, conformal_count_body)
 
 // ------------------------------------------------------------------------------------------------------- host side ----
-struct CfSpan { const void* p; size_t bytes; const char* name; };
-static bool cf_overlap(const CfSpan& a, const CfSpan& b) {
-    if (!a.p || !b.p) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int conformal_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, const double* beta_dev, int method, double lam,
                    int k_reg, int randomized, uint64_t seed, uint32_t draw, const double* qhat_dev, double* score, int32_t* rows,
                    uint32_t* sets, hipStream_t st) {
     SLNLP_CHECK_ARG(logp, "conformal_rows: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "conformal_rows: N=%ld outside 1..%d", (long)N, INT_MAX);
-    SLNLP_CHECK_ARG(V >= 1 && V <= SLNLP_CONFORMAL_MAX_V, "conformal_rows: V=%ld outside 1..%d", (long)V, SLNLP_CONFORMAL_MAX_V);
-    SLNLP_CHECK_ARG(ld >= V, "conformal_rows: ld=%ld is less than V=%ld", (long)ld, (long)V);
-    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "conformal_rows: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
+    Span z;
+    SLNLP_TRY(check_logp_matrix("conformal_rows", logp, N, INT_MAX, V, SLNLP_CONFORMAL_MAX_V, ld, &z));
     SLNLP_CHECK_ARG(method == SLNLP_CONFORMAL_LAC || method == SLNLP_CONFORMAL_APS, "conformal_rows: method=%d, expected %d (LAC) or %d (APS)",
                     method, SLNLP_CONFORMAL_LAC, SLNLP_CONFORMAL_APS);
     SLNLP_CHECK_ARG(lam >= 0.0 && lam < (double)INFINITY, "conformal_rows: lam=%g, expected a finite number >= 0", lam);
@@ -269,14 +244,9 @@ int conformal_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, i
                     "conformal_rows: misaligned pointer");
     SLNLP_CHECK_ARG(((uintptr_t)rows & 15) == 0, "conformal_rows: rows is not 16-byte aligned");
     const size_t n = (size_t)N, W = ((size_t)V + 31) / 32;
-    const CfSpan in[4] = {{logp, ((n - 1) * (size_t)ld + (size_t)V) * 4, "logp"}, {y, n * 8, "y"}, {beta_dev, 8, "beta"}, {qhat_dev, 8, "qhat"}};
-    const CfSpan out[3] = {{score, n * 8, "score"}, {rows, n * 16, "rows"}, {sets, n * W * 4, "sets"}};
-    for (int o = 0; o < 3; ++o) {
-        for (int i = 0; i < 4; ++i)
-            SLNLP_CHECK_ARG(!cf_overlap(out[o], in[i]), "conformal_rows: output %s overlaps input %s", out[o].name, in[i].name);
-        for (int p = 0; p < o; ++p)
-            SLNLP_CHECK_ARG(!cf_overlap(out[o], out[p]), "conformal_rows: outputs %s and %s overlap", out[p].name, out[o].name);
-    }
+    const Span in[4] = {z, {y, n * 8, "y"}, {beta_dev, 8, "beta"}, {qhat_dev, 8, "qhat"}};
+    const Span out[3] = {{score, n * 8, "score"}, {rows, n * 16, "rows"}, {sets, n * W * 4, "sets"}};
+    SLNLP_TRY(check_no_overlap("conformal_rows", out, in));
     const int blocks = (int)std::min<int64_t>(N, CONFORMAL_MAX_BLOCKS);
     return zlaunch(conformal_rows_kernel, dim3(blocks), 64, 0, st, "conformal_rows", logp, (long)ld, y, (int)N, (int)V, beta_dev, method, lam,
                    k_reg, randomized ? 1 : 0, (unsigned long long)seed, (unsigned)draw, qhat_dev, score, (int*)rows, (unsigned*)sets);
@@ -290,8 +260,8 @@ int conformal_quantile(const double* score, const int32_t* rows, int64_t N, doub
     SLNLP_CHECK_ARG(((uintptr_t)rows & 15) == 0, "conformal_quantile: rows is not 16-byte aligned");
     SLNLP_CHECK_ARG(((uintptr_t)state & 31) == 0, "conformal_quantile: state is not 32-byte aligned");
     const size_t n = (size_t)N;
-    const CfSpan in[2] = {{score, n * 8, "score"}, {rows, n * 16, "rows"}}, out = {state, SLNLP_CONFORMAL_STATE_BYTES, "state"};
-    for (int i = 0; i < 2; ++i) SLNLP_CHECK_ARG(!cf_overlap(out, in[i]), "conformal_quantile: output state overlaps input %s", in[i].name);
+    const Span in[2] = {{score, n * 8, "score"}, {rows, n * 16, "rows"}}, out[1] = {{state, SLNLP_CONFORMAL_STATE_BYTES, "state"}};
+    SLNLP_TRY(check_no_overlap("conformal_quantile", out, in));
     return zlaunch(conformal_quantile_kernel, dim3(1), 256, 0, st, "conformal_quantile", score, (const int*)rows, (int)N, alpha, state);
 }
 
@@ -303,8 +273,8 @@ int conformal_summary(const int32_t* rows, const int64_t* y, int64_t N, int64_t 
     SLNLP_CHECK_ARG(((uintptr_t)rows & 15) == 0, "conformal_summary: rows is not 16-byte aligned");
     SLNLP_CHECK_ARG(((uintptr_t)table & 31) == 0, "conformal_summary: table is not 32-byte aligned");
     const size_t n = (size_t)N, cells = ((size_t)V + 1) * 4;
-    const CfSpan in[2] = {{rows, n * 16, "rows"}, {y, n * 8, "y"}}, out = {table, cells * 8, "table"};
-    for (int i = 0; i < 2; ++i) SLNLP_CHECK_ARG(!cf_overlap(out, in[i]), "conformal_summary: output table overlaps input %s", in[i].name);
+    const Span in[2] = {{rows, n * 16, "rows"}, {y, n * 8, "y"}}, out[1] = {{table, cells * 8, "table"}};
+    SLNLP_TRY(check_no_overlap("conformal_summary", out, in));
     const int zero_blocks = (int)std::min<size_t>((cells + 255) / 256, CONFORMAL_MAX_BLOCKS);
     SLNLP_TRY(zlaunch(conformal_zero_kernel, dim3(zero_blocks), 256, 0, st, "conformal_zero", (unsigned long long*)table, (long)cells));
     const int blocks = (int)std::min<int64_t>((N + 255) / 256, CONFORMAL_MAX_BLOCKS);

@@ -4,10 +4,8 @@
 //
 // topk_rows: z float32 log-probs [N, ld] (V columns used), beta = beta_dev ? beta_dev[0] : 1.  Per row the first k columns in
 // score_beats' total order on the float32 values (common.hpp: a NaN first, then larger values, equal values by ascending index) and
-// prob = exp(beta z_c - a) / s0 with reliability.hip's decomposition -- zmax the float32 row maximum, a = beta zmax, the columns AT
-// the maximum counted, the others summed: rest = sum e + (n_max - 1), s0 = 1 + rest.  The two passes that lead to s0 are
-// reliability_rows_body's, statement by statement (same loop, same expression, same reduction order), so prob[i, 0] = 1 / s0 is
-// that kernel's conf bit for bit.  Then k - 1 rounds: a wave arg-max over the elements that come strictly AFTER the previous winner
+// prob = exp(beta z_c - a) / s0 with a and s0 from the row head of logp_row.hpp, which reliability_rows shares: prob[i, 0] = 1 / s0
+// is that kernel's conf bit for bit.  Then k - 1 rounds: a wave arg-max over the elements that come strictly AFTER the previous winner
 // in the order; nothing is stored in between (a row stays in L2), lane m keeps winner m and the k results leave in one store.
 // One wave per row, four rows per block, rows over a grid-stride loop, lanes stride the columns; no LDS.
 //
@@ -26,6 +24,8 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "logp_row.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -43,30 +43,12 @@ __device__ __forceinline__ void topk_rows_body(const float* __restrict__ logp, l
     const double qnan = __builtin_bit_cast(double, 0x7ff8000000000000ull);
     for (long r = wave; r < N; r += nwaves) {            // r: the same in every lane, so every lane reaches the reductions
         const float* row = logp + r * ld;
-        float zmax = -INFINITY;                          // (any column beats this start: -inf at column j ties and j < INT_MAX)
-        int pred = INT_MAX;
-        for (int j = lane; j < V; j += 64) {
-            const float x = row[j];
-            if (score_beats(x, j, zmax, pred)) { zmax = x; pred = j; }
-        }
-        wave_best(zmax, pred);                           // a NaN anywhere in the row wins: zmax is then no finite number
-        const bool finite = fabsf(zmax) < INFINITY;
-        const double a = beta * (double)zmax;            // beta > 0: the maximum of beta z
-        double rest = 0.0, at_max = 0.0;                 // as in reliability_rows: sum e - 1 without the 1 ever entering a sum
-        for (int j = lane; j < V; j += 64) {
-            const float zf = row[j];
-            if (zf == zmax) {
-                at_max += 1.0;
-            } else {
-                const double e = exp(beta * (double)zf - a);
-                rest += e;
-            }
-        }
-        const double n_max = wave_sum_d(at_max);         // whole numbers, summed exactly
-        rest = wave_sum_d(rest) + (n_max - 1.0);
-        const double s0 = 1.0 + rest;
+        const LogpRowMax top = logp_row_argmax(row, V, lane);
+        const float zmax = top.zmax;
+        const LogpRowSums h = logp_row_sums(row, V, lane, beta, zmax);
+        const double a = h.a, s0 = h.s0;
         float pv = zmax, mine_v = zmax;                  // (pv, pi): the previous winner; lane m keeps winner m (k <= 64)
-        int pi = pred, mine_i = pred;
+        int pi = top.pred, mine_i = top.pred;
         for (int m = 1; m < k; ++m) {                    // k <= V: every round has an element left
             float bv = -INFINITY;
             int bi = INT_MAX;
@@ -81,7 +63,7 @@ __device__ __forceinline__ void topk_rows_body(const float* __restrict__ logp, l
         if (lane < k) {
             idx[r * k + lane] = mine_i;
             double p = qnan;                             // a row that holds a NaN or whose maximum is not finite
-            if (finite) p = mine_v == zmax ? 1.0 / s0 : exp(beta * (double)mine_v - a) / s0;
+            if (top.finite) p = mine_v == zmax ? 1.0 / s0 : exp(beta * (double)mine_v - a) / s0;
             prob[r * k + lane] = p;
         }
     }
@@ -196,29 +178,18 @@ __device__ __forceinline__ void pairs_merge_body(const pair_key* __restrict__ li
 SLNLP_ZKERNEL(pairs_merge_kernel, 256, pairs_merge_body)
 
 // ------------------------------------------------------------------------------------------------------ host side ----
-struct ConfSpan { const void* p; size_t bytes; const char* name; };
-static bool conf_overlap(const ConfSpan& a, const ConfSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int topk_rows(const float* logp, int64_t ld, int64_t N, int64_t V, int k, const double* beta_dev, int32_t* idx, double* prob, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && idx && prob, "topk_rows: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "topk_rows: N=%ld outside 1..%d", (long)N, INT_MAX);
-    SLNLP_CHECK_ARG(V >= 1 && V <= INT_MAX, "topk_rows: V=%ld outside 1..%d", (long)V, INT_MAX);
+    Span z;
+    SLNLP_TRY(check_logp_matrix("topk_rows", logp, N, INT_MAX, V, INT_MAX, ld, &z));
     const int k_max = (int)std::min<int64_t>(V, SLNLP_TOPK_MAX);
     SLNLP_CHECK_ARG(k >= 1 && k <= k_max, "topk_rows: k=%d outside 1..%d", k, k_max);
-    SLNLP_CHECK_ARG(ld >= V, "topk_rows: ld=%ld is less than V=%ld", (long)ld, (long)V);
-    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "topk_rows: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
     SLNLP_CHECK_ARG((((uintptr_t)logp | (uintptr_t)idx) & 3) == 0 && (((uintptr_t)prob | (uintptr_t)beta_dev) & 7) == 0,
                     "topk_rows: misaligned pointer");
     const size_t n = (size_t)N;
-    const ConfSpan in[2] = {{logp, ((n - 1) * (size_t)ld + (size_t)V) * 4, "logp"}, {beta_dev, 8, "beta"}};
-    const ConfSpan out[2] = {{idx, n * k * 4, "idx"}, {prob, n * k * 8, "prob"}};
-    for (int o = 0; o < 2; ++o)
-        for (int i = 0; i < (beta_dev ? 2 : 1); ++i)
-            SLNLP_CHECK_ARG(!conf_overlap(out[o], in[i]), "topk_rows: output %s overlaps input %s", out[o].name, in[i].name);
-    SLNLP_CHECK_ARG(!conf_overlap(out[0], out[1]), "topk_rows: outputs idx and prob overlap");
+    const Span in[2] = {z, {beta_dev, 8, "beta"}};
+    const Span out[2] = {{idx, n * k * 4, "idx"}, {prob, n * k * 8, "prob"}};
+    SLNLP_TRY(check_no_overlap("topk_rows", out, in));
     const int blocks = (int)std::min<int64_t>((N + 3) / 4, CONF_MAX_BLOCKS);
     return zlaunch(topk_rows_kernel, dim3(blocks), 256, 0, st, "topk_rows", logp, (long)ld, (int)N, (int)V, k, beta_dev, idx, prob);
 }
@@ -229,8 +200,8 @@ int confusion_matrix(const int32_t* pred, const int64_t* y, int64_t N, int64_t V
     SLNLP_CHECK_ARG(V >= 1 && V <= SLNLP_CONFUSION_MAX_V, "confusion_matrix: V=%ld outside 1..%d", (long)V, SLNLP_CONFUSION_MAX_V);
     SLNLP_CHECK_ARG((((uintptr_t)pred | (uintptr_t)counts) & 3) == 0 && ((uintptr_t)y & 7) == 0, "confusion_matrix: misaligned pointer");
     const size_t n = (size_t)N, n_counts = (size_t)V * (size_t)V + 1;
-    const ConfSpan in[2] = {{pred, n * 4, "pred"}, {y, n * 8, "y"}}, out = {counts, n_counts * 4, "counts"};
-    for (int i = 0; i < 2; ++i) SLNLP_CHECK_ARG(!conf_overlap(out, in[i]), "confusion_matrix: output counts overlaps input %s", in[i].name);
+    const Span in[2] = {{pred, n * 4, "pred"}, {y, n * 8, "y"}}, out[1] = {{counts, n_counts * 4, "counts"}};
+    SLNLP_TRY(check_no_overlap("confusion_matrix", out, in));
     const int zero_blocks = (int)std::min<size_t>((n_counts + 255) / 256, CONF_MAX_BLOCKS);
     SLNLP_TRY(zlaunch(confusion_zero_kernel, dim3(zero_blocks), 256, 0, st, "confusion_zero", counts, (long)n_counts));
     const int blocks = (int)std::min<int64_t>((N + 255) / 256, CONF_MAX_BLOCKS);
@@ -258,10 +229,9 @@ int confusion_pairs(const int32_t* counts, int64_t V, int M, int32_t* pairs, voi
     SLNLP_CHECK_ARG(work_bytes >= need, "confusion_pairs: work_bytes=%ld is too small, V=%ld and M=%d need %ld", (long)work_bytes, (long)V, M,
                     (long)need);
     SLNLP_CHECK_ARG((((uintptr_t)counts | (uintptr_t)pairs) & 3) == 0 && ((uintptr_t)work & 7) == 0, "confusion_pairs: misaligned pointer");
-    const ConfSpan in = {counts, (size_t)V * (size_t)V * 4, "counts"};
-    const ConfSpan out[2] = {{pairs, (size_t)M * 12, "pairs"}, {work, (size_t)need, "work"}};
-    for (int o = 0; o < 2; ++o) SLNLP_CHECK_ARG(!conf_overlap(out[o], in), "confusion_pairs: output %s overlaps input counts", out[o].name);
-    SLNLP_CHECK_ARG(!conf_overlap(out[0], out[1]), "confusion_pairs: outputs pairs and work overlap");
+    const Span in[1] = {{counts, (size_t)V * (size_t)V * 4, "counts"}};
+    const Span out[2] = {{pairs, (size_t)M * 12, "pairs"}, {work, (size_t)need, "work"}};
+    SLNLP_TRY(check_no_overlap("confusion_pairs", out, in));
     const int slices = pairs_slices(V);
     const long slice = (long)((V * V + slices - 1) / slices);
     SLNLP_TRY(zlaunch(pairs_slice_kernel, dim3(slices), 256, 0, st, "confusion_pairs_slice", counts, (int)V, M, slice, (pair_key*)work));

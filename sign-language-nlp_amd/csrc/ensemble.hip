@@ -3,8 +3,8 @@
 //
 // Member k: z_k float32 log-probs [N, ld_k] (V columns used), beta_k = beta_dev[k] ? beta_dev[k][0] : 1 (a calibration state's first
 // double, read on the device), w_k > 0 with sum w_k = 1 (normalised on the host in fp64).  Per row, all in fp64 but z itself:
-//   member term   scale_logp's expression before its rounding: zmax_k the float32 row maximum, a_k = beta_k zmax_k, the columns AT the
-//                 maximum counted and not exponentiated:  l_kc = (beta_k z_kc - a_k) - log1p(rest_k + (n_at_max_k - 1)),  p_kc = exp(l_kc)
+//   member term   scale_logp's expression before its rounding, with a_k and rest_k = sum e - 1 from the row head of logp_row.hpp:
+//                 l_kc = (beta_k z_kc - a_k) - log1p(rest_k),  p_kc = exp(l_kc)
 //   mixture       m_c = max_k l_kc,  mix_c = m_c + log(sum_k w_k exp(l_kc - m_c)),  -inf when m_c is;  pbar_c = exp(mix_c)
 //   SOFT          out_c = (float) mix_c
 //   LOG           u_c = sum_k w_k l_kc,  out_c = (float)((u_c - umax) - log(sum_c exp(u_c - umax)))
@@ -33,6 +33,8 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "logp_row.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -110,22 +112,11 @@ __device__ __forceinline__ void ensemble_rows_body(EnsMembers m, int K, int N, i
         for (int k = 0; k < K; ++k) {                    // pass 1: member k's maximum, arg-max and logsumexp
             const ens_gf row = (ens_gf)lane_bcast_u64(me.row, k);
             const double beta = lane_bcast_d(me.beta, k);
-            float zmax = -INFINITY;                      // (any column beats this start: -inf at column j ties and j < INT_MAX)
-            int pred = INT_MAX;
-            for (int j = lane; j < V; j += 64) {
-                const float x = row[j];
-                if (score_beats(x, j, zmax, pred)) { zmax = x; pred = j; }
-            }
-            wave_best(zmax, pred);                       // a NaN anywhere in the row wins: zmax is then no finite number
-            bad = bad || !(fabsf(zmax) < INFINITY);
-            const double a = beta * (double)zmax;
-            double rest = 0.0, at_max = 0.0;             // as in scale_logp: sum e - 1 without the 1 ever entering a sum
-            for (int j = lane; j < V; j += 64) {
-                const float zf = row[j];
-                if (zf == zmax) at_max += 1.0; else rest += exp(beta * (double)zf - a);
-            }
-            const double l1p = log1p(wave_sum_d(rest) + (wave_sum_d(at_max) - 1.0));
-            if (lane == k) { me.a = a; me.l1p = l1p; my_arg = pred; }
+            const LogpRowMax top = logp_row_argmax(row, V, lane);
+            bad = bad || !top.finite;
+            const LogpRowSums h = logp_row_sums(row, V, lane, beta, top.zmax);
+            const double l1p = log1p(h.rest);
+            if (lane == k) { me.a = h.a; me.l1p = l1p; my_arg = top.pred; }
         }
         // from here on the column loops run the same number of rounds in every lane (a lane past the row's end works on column 0
         // and adds nothing), so that every v_readlane of the k loops is issued with the whole wave active
@@ -209,12 +200,6 @@ __device__ __forceinline__ void ensemble_rows_body(EnsMembers m, int K, int N, i
 }
 SLNLP_ZKERNEL(ensemble_rows_kernel, 256, ensemble_rows_body)
 
-struct EnsSpan { const void* p; size_t bytes; };
-static bool ens_overlap(const EnsSpan& a, const EnsSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int ensemble_rows(const float* const* logp, const int64_t* ld, const double* const* beta_dev, const double* weights, int K, int64_t N,
                   int64_t V, int mode, float* out, int64_t ld_out, double* rows, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && ld && out, "ensemble_rows: null pointer");
@@ -247,18 +232,14 @@ int ensemble_rows(const float* const* logp, const int64_t* ld, const double* con
     }
     SLNLP_CHECK_ARG(wsum < INFINITY, "ensemble_rows: the weights' sum is not finite");
     for (int k = 0; k < K; ++k) m.w[k] = weights ? m.w[k] / wsum : 1.0 / (double)K;
-    const size_t n = (size_t)N, v = (size_t)V;
-    const EnsSpan outs[2] = {{out, ((n - 1) * (size_t)ld_out + v) * 4}, {rows, n * 32}};
-    for (int o = 0; o < (rows ? 2 : 1); ++o) {
-        const char* name = o ? "rows" : "out";
+    const Span outs[2] = {{out, matrix_bytes(N, ld_out, V), "out"}, {rows, (size_t)N * 32, "rows"}};
+    for (const Span& o : outs) {                         // its own wording: the inputs are numbered members
         for (int k = 0; k < K; ++k) {
-            SLNLP_CHECK_ARG(!ens_overlap(outs[o], EnsSpan{m.z[k], ((n - 1) * (size_t)m.ld[k] + v) * 4}), "ensemble_rows: %s overlaps member %d",
-                            name, k);
-            SLNLP_CHECK_ARG(!m.beta[k] || !ens_overlap(outs[o], EnsSpan{m.beta[k], 8}), "ensemble_rows: %s overlaps the beta of member %d",
-                            name, k);
+            SLNLP_CHECK_ARG(!spans_overlap(o, Span{m.z[k], matrix_bytes(N, m.ld[k], V), ""}), "ensemble_rows: %s overlaps member %d", o.name, k);
+            SLNLP_CHECK_ARG(!spans_overlap(o, Span{m.beta[k], 8, ""}), "ensemble_rows: %s overlaps the beta of member %d", o.name, k);
         }
     }
-    SLNLP_CHECK_ARG(!rows || !ens_overlap(outs[0], outs[1]), "ensemble_rows: out and rows overlap");
+    SLNLP_CHECK_ARG(!spans_overlap(outs[0], outs[1]), "ensemble_rows: out and rows overlap");
     const int blocks = (int)std::min<int64_t>((N + 3) / 4, ENS_MAX_BLOCKS);
     return zlaunch(ensemble_rows_kernel, dim3(blocks), 256, 0, st, "ensemble_rows", m, K, (int)N, (int)V, mode, out, (long)ld_out, rows);
 }

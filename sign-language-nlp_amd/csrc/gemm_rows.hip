@@ -27,6 +27,7 @@
 #include "gemm_jobs.hpp"
 #include "launch.hpp"
 #include "layernorm_row.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -824,11 +825,6 @@ bool gemm_rows_ln_covers(int M, int N, int K) {
     return K % 64 == 0 && K <= LN_MAXU * 256 && ceil_div(K, 64) <= RT_MAX_KTILES && rows_geo(M, N, K, 1, false) == 0;
 }
 
-static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // C = epilogue( LayerNorm(x) W^T ) in one launch (gemm_rows_ln_body): `a` as for gemm_rows without its A operand, which is ln.x here
 int gemm_rows_ln(const slnlp_gemm_args& a, const RowsLn& ln, hipStream_t st) {
     SLNLP_CHECK_ARG(!recording(), "gemm_rows_ln: a solo launch only (a lockstep program keeps layernorm_fwd and gemm_rows)");
@@ -845,10 +841,10 @@ int gemm_rows_ln(const slnlp_gemm_args& a, const RowsLn& ln, hipStream_t st) {
                         (((uintptr_t)ln.y_hi | (uintptr_t)ln.y_lo) & 7) == 0,
                     "gemm_rows_ln: x, gamma, beta and y must be 16-byte aligned, y's planes 8-byte aligned");
     // other workgroups of the launch still read x (and the epilogue's operands) while the first column tile's write y
-    const size_t x_bytes = ((size_t)(a.M - 1) * ln.ldx + a.K) * sizeof(float), y_bytes = (size_t)a.M * a.K * sizeof(float);
-    SLNLP_CHECK_ARG(!ranges_overlap(ln.x, x_bytes, ln.y, y_bytes), "gemm_rows_ln: x and y overlap");
-    SLNLP_CHECK_ARG(!a.resid || !ranges_overlap(a.resid, ((size_t)(a.M - 1) * a.ldr + a.N) * sizeof(float), ln.y, y_bytes), "gemm_rows_ln: resid and y overlap");
-    SLNLP_CHECK_ARG(!a.gate || !ranges_overlap(a.gate, ((size_t)(a.M - 1) * a.ldg + a.N) * sizeof(float), ln.y, y_bytes), "gemm_rows_ln: gate and y overlap");
+    const Span y = {ln.y, matrix_bytes(a.M, a.K, a.K), "y"};
+    const Span read[3] = {{ln.x, matrix_bytes(a.M, ln.ldx, a.K), "x"}, {a.resid, matrix_bytes(a.M, a.ldr, a.N), "resid"},
+                          {a.gate, matrix_bytes(a.M, a.ldg, a.N), "gate"}};
+    for (const Span& s : read) SLNLP_CHECK_ARG(!spans_overlap(s, y), "gemm_rows_ln: %s and y overlap", s.name);
     RowsLnParams p;
     p.r.a = a;
     p.r.a.A_hi = p.r.a.A_lo = nullptr;

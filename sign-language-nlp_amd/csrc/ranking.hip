@@ -34,6 +34,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -209,28 +210,17 @@ __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp
 }
 SLNLP_ZKERNEL(ranking_rows_kernel, 256, ranking_rows_body)
 
-struct RankSpan { const void* p; size_t bytes; const char* name; };
-static bool rank_overlap(const RankSpan& a, const RankSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int ranking_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int32_t* rows, double* table, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && y && table, "ranking_rows: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= SLNLP_RANK_MAX_ROWS, "ranking_rows: N=%ld outside 1..%d", (long)N, SLNLP_RANK_MAX_ROWS);
-    SLNLP_CHECK_ARG(V >= 1 && V <= INT_MAX - 1, "ranking_rows: V=%ld outside 1..%d", (long)V, INT_MAX - 1);
-    SLNLP_CHECK_ARG(ld >= V, "ranking_rows: ld=%ld is less than V=%ld", (long)ld, (long)V);
-    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "ranking_rows: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
+    Span z;
+    SLNLP_TRY(check_logp_matrix("ranking_rows", logp, N, SLNLP_RANK_MAX_ROWS, V, INT_MAX - 1, ld, &z));
     SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0 && ((uintptr_t)y & 7) == 0, "ranking_rows: misaligned pointer");
     SLNLP_CHECK_ARG(((uintptr_t)rows & 15) == 0, "ranking_rows: rows is not 16-byte aligned");
     SLNLP_CHECK_ARG(((uintptr_t)table & 31) == 0, "ranking_rows: table is not 32-byte aligned");
     const size_t n = (size_t)N;
-    const RankSpan in[2] = {{logp, ((n - 1) * (size_t)ld + (size_t)V) * 4, "logp"}, {y, n * 8, "y"}};
-    const RankSpan out[2] = {{table, ((size_t)V + 1) * 32, "table"}, {rows, n * 16, "rows"}};
-    for (int o = 0; o < (rows ? 2 : 1); ++o)
-        for (int i = 0; i < 2; ++i)
-            SLNLP_CHECK_ARG(!rank_overlap(out[o], in[i]), "ranking_rows: output %s overlaps input %s", out[o].name, in[i].name);
-    SLNLP_CHECK_ARG(!rows || !rank_overlap(out[0], out[1]), "ranking_rows: outputs rows and table overlap");
+    const Span in[2] = {z, {y, n * 8, "y"}};
+    const Span out[2] = {{rows, n * 16, "rows"}, {table, ((size_t)V + 1) * 32, "table"}};
+    SLNLP_TRY(check_no_overlap("ranking_rows", out, in));
     return zlaunch(ranking_rows_kernel, dim3((unsigned)V), 256, 0, st, "ranking_rows", logp, (long)ld, y, (int)N, (int)V, (int*)rows, table);
 }
 

@@ -3,10 +3,9 @@
 // neg_brier, NeuralNetClassifier.reliability).
 //
 // z float32 log-probs [N, ld] (V columns used), y int64 [N], B bins, beta = beta_dev ? beta_dev[0] : 1 (a calibration state's
-// first double), p = softmax(beta z_i) -- never materialised.  Per row, all in fp64 but z itself, with calibration.hip's
-// decomposition: zmax the float32 row maximum, a = beta zmax, e_c = exp(beta z_c - a); the k columns AT the maximum have e = 1
-// exactly and are counted, the others summed: rest = sum e + (k - 1), s0 = 1 + rest.
-//   pred    the first maximum in score.hip's order on the float32 values        correct = (pred == y_i)
+// first double), p = softmax(beta z_i) -- never materialised.  Per row, all in fp64 but z itself, from the row head of
+// logp_row.hpp: pred / zmax, a = beta zmax, e_c = exp(beta z_c - a), the k columns at the maximum, rest = sum e - 1, s0 = 1 + rest.
+//   pred    the first maximum in score_beats' order on the float32 values       correct = (pred == y_i)
 //   conf    1 / s0: the probability of the arg-max class
 //   brier   sum_c (p_c - 1[c = y_i])^2 = (k + sum_{c not at max} e_c^2) / s0^2 - 2 exp(beta z_y - a) / s0 + 1
 //   nll     log1p(rest) - (beta z_y - a): fit_rows' f_i
@@ -30,6 +29,8 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "logp_row.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -46,41 +47,22 @@ __device__ __forceinline__ void reliability_rows_body(const float* __restrict__ 
         const float* row = logp + r * ld;
         const int64_t label = y[r];
         const bool ok = label >= 0 && label < V;         // a label outside the columns is never used as an index
-        float zmax = -INFINITY;                          // (any column beats this start: -inf at column j ties and j < INT_MAX)
-        int pred = INT_MAX;
-        for (int j = lane; j < V; j += 64) {
-            const float x = row[j];
-            if (score_beats(x, j, zmax, pred)) { zmax = x; pred = j; }
-        }
-        wave_best(zmax, pred);                           // a NaN anywhere in the row wins: zmax is then no finite number
-        const bool finite = fabsf(zmax) < INFINITY;
-        const double a = beta * (double)zmax;            // beta > 0: the maximum of beta z
-        double rest = 0.0, at_max = 0.0, sq = 0.0;       // as in fit_rows: sum e - 1 without the 1 ever entering a sum
-        for (int j = lane; j < V; j += 64) {
-            const float zf = row[j];
-            if (zf == zmax) {
-                at_max += 1.0;
-            } else {
-                const double e = exp(beta * (double)zf - a);
-                rest += e;
-                sq += e * e;
-            }
-        }
-        const double k = wave_sum_d(at_max);             // whole numbers, summed exactly (k >= 1 for a finite maximum)
-        rest = wave_sum_d(rest) + (k - 1.0);
+        const LogpRowMax top = logp_row_argmax(row, V, lane);
+        double sq = 0.0;                                 // sum e^2 over the columns not at the maximum
+        const LogpRowSums h = logp_row_sums(row, V, lane, beta, top.zmax, [&](double e) { sq += e * e; });
         sq = wave_sum_d(sq);
         if (lane == 0) {
             double4 t = {0.0, 0.0, 0.0, -1.0};           // a label out of range: nothing to score
-            if (ok && !finite) {
+            if (ok && !top.finite) {
                 t = {qnan, qnan, qnan, -2.0};
             } else if (ok) {
-                const double s0 = 1.0 + rest;
-                const double by = beta * (double)row[label] - a;
+                const double s0 = h.s0;
+                const double by = beta * (double)row[label] - h.a;
                 t.x = 1.0 / s0;
-                t.y = (k + sq) / (s0 * s0) - 2.0 * exp(by) / s0 + 1.0;
-                t.z = log1p(rest) - by;
+                t.y = (h.n_max + sq) / (s0 * s0) - 2.0 * exp(by) / s0 + 1.0;
+                t.z = log1p(h.rest) - by;
                 const double bin = fmin(fmax(ceil(t.x * (double)bins) - 1.0, 0.0), (double)(bins - 1));
-                t.w = 2.0 * bin + (pred == label ? 1.0 : 0.0);
+                t.w = 2.0 * bin + (top.pred == label ? 1.0 : 0.0);
             }
             *(double4*)(rows + 4 * r) = t;
         }
@@ -118,29 +100,18 @@ __device__ __forceinline__ void reliability_table_body(const double* __restrict_
 }
 SLNLP_ZKERNEL(reliability_table_kernel, 256, reliability_table_body)
 
-struct RelSpan { const void* p; size_t bytes; const char* name; };
-static bool rel_overlap(const RelSpan& a, const RelSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int reliability_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int bins, const double* beta_dev, double* rows,
                      double* table, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && y && rows && table, "reliability_rows: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "reliability_rows: N=%ld outside 1..%d", (long)N, INT_MAX);
-    SLNLP_CHECK_ARG(V >= 1 && V <= INT_MAX, "reliability_rows: V=%ld outside 1..%d", (long)V, INT_MAX);
+    Span z;
+    SLNLP_TRY(check_logp_matrix("reliability_rows", logp, N, INT_MAX, V, INT_MAX, ld, &z));
     SLNLP_CHECK_ARG(bins >= 1 && bins <= SLNLP_REL_MAX_BINS, "reliability_rows: bins=%d outside 1..%d", bins, SLNLP_REL_MAX_BINS);
-    SLNLP_CHECK_ARG(ld >= V, "reliability_rows: ld=%ld is less than V=%ld", (long)ld, (long)V);
-    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "reliability_rows: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
     SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0 && (((uintptr_t)y | (uintptr_t)beta_dev) & 7) == 0, "reliability_rows: misaligned pointer");
     SLNLP_CHECK_ARG((((uintptr_t)rows | (uintptr_t)table) & 31) == 0, "reliability_rows: rows or table is not 32-byte aligned");
     const size_t n = (size_t)N;
-    const RelSpan in[3] = {{logp, ((n - 1) * (size_t)ld + (size_t)V) * 4, "logp"}, {y, n * 8, "y"}, {beta_dev, 8, "beta"}};
-    const RelSpan out[2] = {{rows, n * 32, "rows"}, {table, ((size_t)bins + 1) * 32, "table"}};
-    for (int o = 0; o < 2; ++o)
-        for (int i = 0; i < (beta_dev ? 3 : 2); ++i)
-            SLNLP_CHECK_ARG(!rel_overlap(out[o], in[i]), "reliability_rows: output %s overlaps input %s", out[o].name, in[i].name);
-    SLNLP_CHECK_ARG(!rel_overlap(out[0], out[1]), "reliability_rows: outputs rows and table overlap");
+    const Span in[3] = {z, {y, n * 8, "y"}, {beta_dev, 8, "beta"}};
+    const Span out[2] = {{rows, n * 32, "rows"}, {table, ((size_t)bins + 1) * 32, "table"}};
+    SLNLP_TRY(check_no_overlap("reliability_rows", out, in));
     const int blocks = (int)std::min<int64_t>((N + 3) / 4, REL_MAX_BLOCKS);
     SLNLP_TRY(zlaunch(reliability_rows_kernel, dim3(blocks), 256, 0, st, "reliability_rows", logp, (long)ld, y, (int)N, (int)V, bins, beta_dev,
                       rows));

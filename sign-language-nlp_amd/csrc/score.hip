@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "spans.hpp"
 
 namespace slnlp {
 
@@ -87,32 +88,18 @@ __device__ __forceinline__ void score_rows_body(const float* __restrict__ logp, 
 }
 SLNLP_ZKERNEL(score_rows_kernel, 256, score_rows_body)
 
-struct ScoreSpan { const void* p; size_t bytes; const char* name; };
-static bool spans_overlap(const ScoreSpan& a, const ScoreSpan& b) {
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-
 int score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V, int32_t* pred, float* picked, int32_t* rank,
                int32_t* counts, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && y && pred && picked && rank && counts, "score_rows: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "score_rows: N=%ld outside 1..%d", (long)N, INT_MAX);
-    // counts holds 3 V + 1 int32 entries and is indexed with int32 class ids
-    SLNLP_CHECK_ARG(V >= 1 && V <= (INT_MAX - 1) / 3, "score_rows: V=%d outside 1..%d", V, (INT_MAX - 1) / 3);
-    SLNLP_CHECK_ARG(ld >= V, "score_rows: ld=%ld is less than V=%d", (long)ld, V);
-    SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N, "score_rows: ld=%ld times N=%ld is no addressable matrix", (long)ld, (long)N);
+    Span z;                                              // counts holds 3 V + 1 int32 entries and is indexed with int32 class ids
+    SLNLP_TRY(check_logp_matrix("score_rows", logp, N, INT_MAX, V, (INT_MAX - 1) / 3, ld, &z));
     SLNLP_CHECK_ARG((((uintptr_t)logp | (uintptr_t)pred | (uintptr_t)picked | (uintptr_t)rank | (uintptr_t)counts) & 3) == 0 &&
                         ((uintptr_t)y & 7) == 0,
                     "score_rows: misaligned pointer");
     const size_t n = (size_t)N, n_counts = 3 * (size_t)V + 1;
-    const ScoreSpan in[2] = {{logp, ((n - 1) * (size_t)ld + (size_t)V) * 4, "logp"}, {y, n * 8, "y"}};
-    const ScoreSpan out[4] = {{pred, n * 4, "pred"}, {picked, n * 4, "picked"}, {rank, n * 4, "rank"}, {counts, n_counts * 4, "counts"}};
-    for (int o = 0; o < 4; ++o) {
-        for (int i = 0; i < 2; ++i)
-            SLNLP_CHECK_ARG(!spans_overlap(out[o], in[i]), "score_rows: output %s overlaps input %s", out[o].name, in[i].name);
-        for (int q = 0; q < o; ++q)
-            SLNLP_CHECK_ARG(!spans_overlap(out[o], out[q]), "score_rows: outputs %s and %s overlap", out[q].name, out[o].name);
-    }
+    const Span in[2] = {z, {y, n * 8, "y"}};
+    const Span out[4] = {{pred, n * 4, "pred"}, {picked, n * 4, "picked"}, {rank, n * 4, "rank"}, {counts, n_counts * 4, "counts"}};
+    SLNLP_TRY(check_no_overlap("score_rows", out, in));
     const int zero_blocks = (int)std::min<size_t>((n_counts + 255) / 256, SCORE_MAX_BLOCKS);
     SLNLP_TRY(zlaunch(score_zero_kernel, dim3(zero_blocks), 256, 0, st, "score_zero", counts, (int)n_counts));
     const int blocks = (int)std::min<int64_t>((N + 3) / 4, SCORE_MAX_BLOCKS);

@@ -6,7 +6,7 @@ weights where it predicts with them), ONE ``ops.ensemble_rows`` launch combines 
 temperature, into one set of float32 log-probs, and everything that judges one fit's log-probs -- ``predict_proba``,
 ``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare``, ``conformalize``, ``predict_set``,
 ``coverage`` -- then works on the ensemble through the
-same ``_forward_logp(ds, then)`` hook: those methods are ``NeuralNetClassifier``'s own functions, bound here, not copies.  The
+same ``_forward_logp(ds, then)`` hook: both classes inherit those methods from ``slnlp.judge.LogProbJudge``.  The
 same launch gives, per sample, how much the members disagree (``uncertainty``): the entropy of the mixture, the expected entropy
 of a member and their difference, the mutual information.  Nothing is averaged on the host and no torch arithmetic runs on the
 device."""
@@ -15,12 +15,13 @@ import torch
 from sklearn.base import BaseEstimator, ClassifierMixin
 
 from . import _lib, ops
+from .judge import LogProbJudge
 from .net import NeuralNetClassifier, ScoringWrapper, _CachedPredictor, stream_sync
 
 VOTING = tuple(_lib.VOTING)
 
 
-class VotingEnsemble(ClassifierMixin, BaseEstimator):
+class VotingEnsemble(LogProbJudge, ClassifierMixin, BaseEstimator):
     """``members``: 1..32 initialised ``NeuralNetClassifier``s on one device with equal ``classes_``.  ``voting``: "soft", the
     weighted arithmetic mean of the members' probabilities, or "log", their weighted geometric mean renormalised (a product of
     experts).  ``weights``: one finite number > 0 per member (normalised on the way in), None: equal.  ``calibrated``: a member
@@ -62,9 +63,6 @@ class VotingEnsemble(ClassifierMixin, BaseEstimator):
         dev = torch.device(net.device)
         return torch.device("cuda", torch.cuda.current_device()) if dev.type == "cuda" and dev.index is None else dev
 
-    _as_dataset = staticmethod(NeuralNetClassifier._as_dataset)
-    _int_option = staticmethod(NeuralNetClassifier._int_option)
-
     def _states(self):
         """Per member its device calibration state, or None: beta = 1."""
         return [m._cal_state if self.calibrated and getattr(m, "calibration_", None) is not None else None for m in self.members]
@@ -94,25 +92,8 @@ class VotingEnsemble(ClassifierMixin, BaseEstimator):
         log-prob consumer of ``NeuralNetClassifier`` goes through."""
         return self._combine(ds, lambda out, yd, rows: then(out, yd), False)
 
-    # one fit's log-prob consumers, bound: they read ``self._forward_logp``, ``classes_``, ``calibration_`` (None here: T = 1)
-    predict_proba = NeuralNetClassifier.predict_proba
-    predict = NeuralNetClassifier.predict
-    score = NeuralNetClassifier.score
-    reliability = NeuralNetClassifier.reliability
-    ranking = NeuralNetClassifier.ranking
-    predict_topk = NeuralNetClassifier.predict_topk
-    error_analysis = NeuralNetClassifier.error_analysis
-    _interval_request = NeuralNetClassifier._interval_request
-    _bootstrap = NeuralNetClassifier._bootstrap
-    score_interval = NeuralNetClassifier.score_interval
-    compare = NeuralNetClassifier.compare
-    # conformal sets of the ensemble's log-probs: the threshold is the ensemble's own (``conformal_``), taken by ``conformalize``
-    _conformal_calibrate = NeuralNetClassifier._conformal_calibrate
-    _conformal_rows = NeuralNetClassifier._conformal_rows
-    _set_conformal = NeuralNetClassifier._set_conformal
-    conformalize = NeuralNetClassifier.conformalize
-    predict_set = NeuralNetClassifier.predict_set
-    coverage = NeuralNetClassifier.coverage
+    # the log-prob consumers are LogProbJudge's: they read ``self._forward_logp``, ``classes_``, ``calibration_`` (None here: T = 1);
+    # the conformal threshold is the ensemble's own (``conformal_``), taken by ``conformalize``
 
     def uncertainty(self, X, per_row=False):
         """How much the members disagree on ``X``: ``metrics.uncertainty_summary`` of ``ops.ensemble_rows``' per-row terms --

@@ -42,8 +42,6 @@ The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
 import threading
 import json
-import math
-import warnings
 import os
 import time
 import importlib
@@ -52,7 +50,7 @@ import numpy as np
 import torch
 
 from . import metrics, ops, param_groups, sampler, schedule
-from .data import TokenDataset
+from .judge import CONFORMAL_DEFAULTS, LogProbJudge, conformal_least_rows, conformal_options  # noqa: F401  (part of this module's names)
 
 
 # module construction consumes torch's global CPU generator (initial weights): concurrent fits take turns
@@ -328,51 +326,6 @@ def calibration_options(setting):
     if method != "temperature":
         raise ValueError(f"calibration: method={method!r}, expected 'temperature'")
     return {"method": "temperature"}
-
-
-CONFORMAL_DEFAULTS = {"alpha": 0.1, "method": "aps", "randomized": True, "lam": 0.0, "k_reg": 0, "seed": 0}
-CONFORMAL_METHODS = tuple(ops._lib.CONFORMAL_METHODS)
-
-
-def conformal_options(setting):
-    """The ``conformal`` setting with its defaults filled in -- {alpha 0.1, method "aps", randomized True, lam 0.0, k_reg 0,
-    seed 0} -- or None (off).  ``method``: "lac" (1 - p of the class) or "aps" (the mass in front of the class plus u times its
-    own; ``lam`` > 0 with ``k_reg`` adds RAPS' penalty lam max(0, rank - k_reg)).  Anything else raises ValueError here."""
-    if setting is None or setting is False:
-        return None
-    if not isinstance(setting, dict):
-        raise ValueError(f"conformal={setting!r}: expected a dict with keys among {tuple(CONFORMAL_DEFAULTS)} or None")
-    unknown = sorted(set(setting) - set(CONFORMAL_DEFAULTS))
-    if unknown:
-        raise ValueError(f"conformal: unknown keys {unknown} (known: {tuple(CONFORMAL_DEFAULTS)})")
-    o = {**CONFORMAL_DEFAULTS, **setting}
-    real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-    if not real(o["alpha"]) or not 0.0 < float(o["alpha"]) < 1.0:
-        raise ValueError(f"conformal: alpha={o['alpha']!r}, expected a number in (0, 1)")
-    if o["method"] not in CONFORMAL_METHODS:
-        raise ValueError(f"conformal: method={o['method']!r}, expected one of {CONFORMAL_METHODS}")
-    if not isinstance(o["randomized"], (bool, np.bool_)):
-        raise ValueError(f"conformal: randomized={o['randomized']!r}, expected True or False")
-    if not real(o["lam"]) or not 0.0 <= float(o["lam"]) < float("inf"):
-        raise ValueError(f"conformal: lam={o['lam']!r}, expected a finite number >= 0")
-    if not whole(o["k_reg"]) or not 0 <= o["k_reg"] < 2 ** 31:
-        raise ValueError(f"conformal: k_reg={o['k_reg']!r}, expected an integer >= 0")
-    if not whole(o["seed"]) or not 0 <= o["seed"] < 2 ** 64:
-        raise ValueError(f"conformal: seed={o['seed']!r}, expected an integer in 0..2^64 - 1")
-    return {"alpha": float(o["alpha"]), "method": o["method"], "randomized": bool(o["randomized"]), "lam": float(o["lam"]),
-            "k_reg": int(o["k_reg"]), "seed": int(o["seed"])}
-
-
-def conformal_least_rows(alpha):
-    """The least number n of calibration rows with ceil((n + 1)(1 - alpha)) <= n: fewer give an infinite threshold."""
-    n = max(1, int(math.ceil((1.0 - alpha) / alpha)) - 2)
-    while math.ceil(float(n + 1) * (1.0 - alpha)) > n:
-        n += 1
-    return n
-
-
-CONFORMAL_DRAW_CALIBRATE, CONFORMAL_DRAW_PREDICT = 0, 1    # the u of a row at prediction time is independent of the calibration draws
 
 
 def next_n_averaged(opts, history, n_batches):
@@ -682,7 +635,7 @@ class _FitRun:
         return self.done
 
 
-class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
+class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
     _OWN = ("module", "criterion", "optimizer", "lr", "max_epochs", "batch_size", "device", "warm_start", "verbose",
             "predict_nonlinearity", "scoring", "labels", "early_stopping", "gradient_clipping", "lr_scheduler",
             "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging", "calibration", "conformal")
@@ -896,16 +849,6 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         ``initialize``, the dataset upload): ``self._stream`` is a non-blocking stream, nothing else makes it wait."""
         self._stream.wait_stream(torch.cuda.current_stream(self._stream.device))
 
-    # ------------------------------------------------------------------ data
-    @staticmethod
-    def _as_dataset(X, y=None):
-        if isinstance(X, TokenDataset):
-            return X
-        if isinstance(X, dict):
-            return TokenDataset(X["X"], X["lengths"], X["y"] if y is None else y)
-        raise TypeError("X must be a slnlp.data.TokenDataset (ids, lengths and labels travel together: the "
-                        "Transformer consumes y as decoder input, transformer.py:65)")
-
     def _device_data(self, ds):
         dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
         return (torch.from_numpy(ds.ids).to(dev), torch.from_numpy(ds.lengths).to(dev), torch.from_numpy(ds.y).to(dev))
@@ -1013,151 +956,6 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
             logp = self._valid_logp(run)
         self._set_conformal(self._conf_opts, *self._conformal_calibrate(logp, run.yva, self._conf_opts, True), labels=run.va.y,
                             where="the valid data")
-
-    def _conformal_calibrate(self, logp, yd, opts, calibrated):
-        """Scores at the calibration draw, then the threshold, on the current stream: ``(device state float64 [4], whether the
-        temperature was used)``.  No host wait."""
-        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
-        logp = logp if logp.dtype == torch.float32 else logp.float()
-        buf = ops.conformal_buffers(logp.shape[0], logp.shape[1], logp.device, sets=False)
-        ops.conformal_rows(logp, yd.contiguous(), buf, method=opts["method"], lam=opts["lam"], k_reg=opts["k_reg"],
-                           randomized=opts["randomized"], seed=opts["seed"], draw=CONFORMAL_DRAW_CALIBRATE,
-                           state=self._cal_state if use else None)
-        state = torch.empty(4, dtype=torch.float64, device=logp.device)
-        return ops.conformal_quantile(buf, opts["alpha"], state=state), use
-
-    def _set_conformal(self, opts, state=None, calibrated=False, labels=None, where="the calibration data", info=None):
-        """``conformal_`` -- the options plus ``calibrated``, ``qhat``, ``n``, ``k`` and ``excluded`` -- and the device state
-        ``predict_set`` reads its threshold from; None removes them.  ``state``: ``ops.conformal_quantile``'s (one download of
-        its four doubles, which waits for the launches); ``info``: a ``conformal_`` read back from a checkpoint instead (qhat
-        goes back to the device).  Labels outside the classes raise, as in ``_set_calibration``."""
-        if opts is None:
-            for k in ("conformal_", "_conf_state"):
-                self.__dict__.pop(k, None)
-            return
-        if info is None:
-            if labels is not None:
-                bad = int(((np.asarray(labels) < 0) | (np.asarray(labels) >= len(self.classes_))).sum())
-                if bad:
-                    raise ValueError(f"conformalizing on {where}: {bad} of {len(labels)} labels lie outside the classes of the log-probs")
-            h = state.cpu().numpy()
-            info = {**opts, "calibrated": bool(calibrated), "qhat": float(h[0]), "n": int(h[1]), "k": int(h[2]), "excluded": int(h[3])}
-            if math.isinf(info["qhat"]):
-                warnings.warn(f"conformal: {info['n']} calibration rows are too few for alpha={info['alpha']}: the threshold is infinite "
-                              f"and every set holds every class; at least {conformal_least_rows(info['alpha'])} rows are needed",
-                              RuntimeWarning, stacklevel=3)
-        else:
-            dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
-            state = torch.tensor([float(info["qhat"]), float(info["n"]), float(info["k"]), float(info["excluded"])],
-                                 dtype=torch.float64).to(dev)
-        self._conf_state, self.conformal_ = state, dict(info)
-
-    def conformalize(self, X, y=None, alpha=0.1, method="aps", randomized=True, lam=0.0, k_reg=0, seed=0, calibrated=True):
-        """Take the threshold of split conformal prediction sets on ``X`` (``y``: the labels; None: the dataset's) -- rows the fit
-        has not seen, for the guarantee to hold: with exchangeable rows, ``predict_set`` then covers the true class with
-        probability at least 1 - alpha (and, randomised, at most 1 - alpha + 1 / (n + 1)).  One forward pass,
-        ``ops.conformal_rows`` at draw 0 and ``ops.conformal_quantile``, all on the device; only the four doubles of the state
-        come to the host.  ``method`` "lac": s = 1 - p of the class (the smallest sets on average, may be empty); "aps": the
-        probability mass in front of the class plus u times its own (adaptive: larger sets where the model is lost); ``lam`` > 0
-        with ``k_reg`` adds RAPS' penalty lam max(0, rank - k_reg), which shortens the tails.  ``randomized``: u is one draw
-        per row of the counter-based generator under ``seed``; False: u = 1 (conservative, sets never empty for APS).
-        ``calibrated``: the probabilities are softmax(z / T) with ``temperature_`` when the fit has one.  Sets ``conformal_``
-        (the options, ``calibrated``, ``qhat``, ``n``, ``k``, ``excluded``: rows left out for a NaN) and returns self.  Fewer than
-        about (1 - alpha) / alpha rows give an infinite threshold: kept and reported, with a warning."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        opts = conformal_options({"alpha": alpha, "method": method, "randomized": randomized, "lam": lam, "k_reg": k_reg, "seed": seed})
-        ds = self._as_dataset(X)
-        labels = ds.y if y is None else np.ascontiguousarray(np.asarray(y), dtype=np.int64)
-        if labels.shape != (len(ds),):
-            raise ValueError(f"conformalize: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
-        bad = int(((labels < 0) | (labels >= len(self.classes_))).sum())
-        if bad:                                              # before the forward passes, as coverage does
-            raise ValueError(f"conformalize: {bad} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the log-probs")
-
-        def rows(logp, yd):
-            yd = yd if y is None else torch.from_numpy(labels).to(logp.device)
-            return self._conformal_calibrate(logp, yd, opts, calibrated)
-        state, use = self._forward_logp(ds, rows)
-        self._set_conformal(opts, state, use, labels=labels)
-        return self
-
-    def _conformal_rows(self, what, logp, yd, sets):
-        """``ops.conformal_rows`` at the prediction draw under ``conformal_``'s options and the device threshold."""
-        c = self.conformal_
-        use = c["calibrated"] and getattr(self, "calibration_", None) is not None
-        logp = logp if logp.dtype == torch.float32 else logp.float()
-        buf = ops.conformal_buffers(logp.shape[0], logp.shape[1], logp.device, sets=sets)
-        return ops.conformal_rows(logp, yd, buf, method=c["method"], lam=c["lam"], k_reg=c["k_reg"], randomized=c["randomized"],
-                                  seed=c["seed"], draw=CONFORMAL_DRAW_PREDICT, state=self._cal_state if use else None,
-                                  qhat=self._conf_state)
-
-    def predict_set(self, X, return_mask=False):
-        """The conformal prediction set of every sample of ``X`` under ``conformal_``'s options and threshold (draw 1: a row's u
-        is independent of the calibration draws): ``{"sets": ..., "sizes": int array [N]}``.  ``sets``: a list of N label
-        arrays (from ``classes_``), most probable first -- every score here grows with the rank, so a set is the first ``size``
-        classes of the row's order; the order comes from ``ops.topk_rows`` on the same forward passes, and the members beyond
-        rank 64 follow by ascending class -- or, with ``return_mask=True``, a bool [N, V] mask.  A set may be empty (LAC, or
-        APS without randomisation when the top probability exceeds the threshold); a row with a NaN gets an empty set.  The
-        [N, V] log-probs stay on the device: the set words, the sizes and (for the lists) the top indices come over."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        if getattr(self, "conformal_", None) is None:
-            raise RuntimeError("predict_set: this estimator has no threshold yet: fit it with the conformal option or call conformalize(X, y)")
-        ds = self._as_dataset(X)
-        V = len(self.classes_)
-        k = min(V, ops._lib.TOPK_MAX)
-
-        def rows(logp, yd):
-            buf = self._conformal_rows("predict_set", logp, None, True)
-            top = None if return_mask else ops.topk_rows(logp if logp.dtype == torch.float32 else logp.float(), k)[0]
-            return buf, top
-        buf, top = self._forward_logp(ds, rows)
-        got = ops.conformal_download(buf, rows=True, sets=True)
-        sizes = got["rows"][:, 0].astype(np.int64)
-        mask = np.unpackbits(got["sets"].view(np.uint8), axis=1, bitorder="little")[:, :V].astype(bool)
-        if return_mask:
-            return {"sets": mask, "sizes": sizes}
-        top = top.cpu().numpy()
-        sets = []
-        for i in range(len(ds)):
-            head = top[i, :min(int(sizes[i]), k)]
-            if sizes[i] > k:                                 # the members past rank 64, by ascending class
-                rest = mask[i].copy()
-                rest[head] = False
-                head = np.concatenate([head, np.flatnonzero(rest)])
-            sets.append(self.classes_[head])
-        return {"sets": sets, "sizes": sizes}
-
-    def coverage(self, X, y=None, min_support=5):
-        """What the sets of ``predict_set`` achieve on labelled data ``X`` (``y``: the labels; None: the dataset's), reduced on the
-        device (``ops.conformal_summary``) and downloaded in one copy: ``metrics.conformal_report``'s dict -- coverage,
-        mean_size, median_size, empty_rate, singleton_rate, size_hist, per class support / class_coverage / class_mean_size
-        (NaN for a class without rows), worst_class_coverage over the classes with at least ``min_support`` rows, rows,
-        excluded -- plus ``qhat``, ``calibration_rows``, ``k``, ``alpha`` and ``classes``.  The per-class table shows whether
-        one threshold serves every class."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        if getattr(self, "conformal_", None) is None:
-            raise RuntimeError("coverage: this estimator has no threshold yet: fit it with the conformal option or call conformalize(X, y)")
-        ds = self._as_dataset(X)
-        labels = ds.y if y is None else np.ascontiguousarray(np.asarray(y), dtype=np.int64)
-        if labels.shape != (len(ds),):
-            raise ValueError(f"coverage: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
-        bad = int(((labels < 0) | (labels >= len(self.classes_))).sum())
-        if bad:
-            raise ValueError(f"coverage: {bad} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the log-probs")
-
-        def rows(logp, yd):
-            yd = (yd if y is None else torch.from_numpy(labels).to(logp.device)).contiguous()
-            buf = self._conformal_rows("coverage", logp, yd, False)
-            ops.conformal_summary(buf, yd)
-            return buf
-        got = ops.conformal_download(self._forward_logp(ds, rows))
-        c = self.conformal_
-        res = metrics.conformal_report(got["table"], min_support=min_support)
-        res.update(qhat=c["qhat"], calibration_rows=c["n"], k=c["k"], alpha=c["alpha"], classes=self.classes_)
-        return res
 
     # ------------------------------------------------------- weight averaging
     def _averaging_epoch(self):
@@ -1287,21 +1085,6 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         return mean, torch.cat(outs), list(zip(per_batch.tolist(), sizes))
 
     # --------------------------------------------------------------- predict
-    def predict_proba(self, X):
-        """softmax of the module output -- the module returns log-probs and skorch's
-        ``predict_nonlinearity='auto'`` applies softmax for CrossEntropyLoss."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-
-        def scaled(out, yd):
-            if getattr(self, "calibration_", None) is not None:
-                ops.scale_logp(out, self._cal_state, out=out)        # softmax(z / T) below: the calibrated log-probs, in place
-            return out
-        out = self._forward_logp(self._as_dataset(X), scaled).cpu()
-        # the nonlinearity on the host copy (torch's CPU softmax -- the op the reference's CPU path runs): torch's GPU kernels
-        # are built with packed fp32 and must not run beside other fits' kernels (STREAM_MODE above); [N, V] is tiny
-        return (torch.softmax(out, dim=-1) if self.predict_nonlinearity == "auto" else out).numpy()
-
     def _forward_logp(self, ds, then):
         """The module's float32 log-probs [len(ds), V] of ``ds`` on the device -- the forward passes of ``predict_proba``: under
         the gate, on the fit's stream, the averaged weights swapped in where the fit predicts with them and back afterwards --
@@ -1327,242 +1110,6 @@ class NeuralNetClassifier(ClassifierMixin, BaseEstimator):
         finally:
             self._gate.leave(not self._fused)
         return res
-
-    def predict(self, X):
-        return self.classes_[self.predict_proba(X).argmax(-1)]
-
-    def reliability(self, X, y=None, bins=15, calibrated=True):
-        """Reliability diagnostics of this fit's predictions on ``X`` (``y``: the labels; None: the dataset's), all formed from one
-        ``ops.reliability_rows`` call on the device log-probs of ``predict_proba``'s forward passes: ``ops.reliability_download``'s
-        dict -- ece, mce (``bins`` equal-width right-closed bins of the top-class probability, 1..64), brier, nll, accuracy,
-        confidence, rows, bad_labels, nan_rows, bins {count, confidence, accuracy} -- plus ``temperature``: the T the
-        probabilities were taken at, softmax(z / T) -- ``temperature_`` for a calibrated fit unless ``calibrated=False``, else 1.0
-        (the device then reads no state)."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= metrics.MAX_BINS:
-            raise ValueError(f"reliability: bins={bins!r}, expected an integer in 1..{metrics.MAX_BINS}")
-        ds = self._as_dataset(X)
-        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
-        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
-        if labels is not None and labels.shape != (len(ds),):
-            raise ValueError(f"reliability: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
-
-        def rows(logp, yd):
-            yd = yd if labels is None else labels.to(logp.device)
-            return ops.reliability_rows(logp if logp.dtype == torch.float32 else logp.float(), yd.contiguous(), bins=int(bins),
-                                        state=self._cal_state if use else None)
-        res = ops.reliability_download(self._forward_logp(ds, rows))
-        if res["bad_labels"] > 0:
-            raise ValueError(f"reliability: {res['bad_labels']} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the "
-                             "log-probs")
-        res["temperature"] = float(self.temperature_) if use else 1.0
-        return res
-
-    def ranking(self, X, y=None, calibrated=True):
-        """Ranking metrics of this fit's predictions on ``X`` (``y``: the labels; None: the dataset's): per class the one-vs-rest
-        ROC AUC and the average precision, and their averages over the defined classes, from one ``ops.ranking_rows`` call on the
-        device log-probs of ``predict_proba``'s forward passes: ``ops.ranking_download``'s dict -- auc_macro, auc_weighted,
-        ap_macro, ap_weighted, classes_scored, auc / ap / support per class (NaN for a class without a positive or a negative
-        row), rows, bad_labels, nan_classes -- plus ``classes`` (``classes_``) and ``temperature``.  A temperature changes the
-        order of a class's scores ACROSS rows, so a calibrated fit is ranked on its calibrated float32 log-probs
-        (``ops.scale_logp`` first) unless ``calibrated=False``; ``temperature`` is then ``temperature_``, else 1.0."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        ds = self._as_dataset(X)
-        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
-        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
-        if labels is not None and labels.shape != (len(ds),):
-            raise ValueError(f"ranking: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
-
-        def rows(logp, yd):
-            yd = yd if labels is None else labels.to(logp.device)
-            logp = logp if logp.dtype == torch.float32 else logp.float()
-            if use:
-                ops.scale_logp(logp, self._cal_state, out=logp)      # in place: the ranks are those of the calibrated log-probs
-            return ops.ranking_rows(logp, yd.contiguous(), per_row=False)
-        res = ops.ranking_download(self._forward_logp(ds, rows))
-        if res["bad_labels"] > 0:
-            raise ValueError(f"ranking: {res['bad_labels']} of {len(ds)} labels lie outside the {len(self.classes_)} classes of the "
-                             "log-probs")
-        res["classes"] = self.classes_
-        res["temperature"] = float(self.temperature_) if use else 1.0
-        return res
-
-    @staticmethod
-    def _int_option(what, name, value, lo, hi):
-        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
-            raise ValueError(f"{what}: {name}={value!r}, expected an integer in {lo}..{hi}")
-        return int(value)
-
-    def predict_topk(self, X, k=5, calibrated=True):
-        """The ``k`` most probable classes of every sample of ``X`` and their probabilities: ``(labels [N, k] from classes_, proba
-        float64 [N, k])``, most probable first, from one ``ops.topk_rows`` call on the device log-probs of ``predict_proba``'s
-        forward passes (k in 1..min(classes, 64)).  The order is the arg-max's -- equal log-probs by ascending class -- so
-        ``labels[:, 0]`` is ``predict(X)``; the probabilities are softmax(z / T) in fp64, ``temperature_`` for a calibrated fit
-        unless ``calibrated=False``, else T = 1."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        k = self._int_option("predict_topk", "k", k, 1, min(len(self.classes_), ops._lib.TOPK_MAX))
-        ds = self._as_dataset(X)
-        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
-
-        def rows(logp, yd):
-            return ops.topk_rows(logp if logp.dtype == torch.float32 else logp.float(), k, state=self._cal_state if use else None)
-        idx, prob = ops.topk_download(self._forward_logp(ds, rows))
-        return self.classes_[idx], prob
-
-    def error_analysis(self, X, y=None, pairs=20, top_k=None, matrix=True, calibrated=True):
-        """Which classes this fit gets wrong on ``X`` (``y``: the labels; None: the dataset's) and what it takes them for, formed
-        on the device from the log-probs of ``predict_proba``'s forward passes (``ops.error_analysis_rows``: the arg-max and class
-        counts, the confusion matrix, its most-confused pairs, the top-k lists) and downloaded in one copy.  A dict:
-        ``classes`` (``classes_``); ``confusion`` int64 [V, V], rows true and columns predicted -- None with ``matrix=False``,
-        and then the V x V counts never leave the device; ``report`` {precision, recall, f1, support, predicted} per class and
-        ``macro`` {precision, recall, f1} (``metrics.class_report``: zero_division = 0, means over all V classes); ``accuracy``;
-        ``pairs``: up to ``pairs`` (1..64) tuples (true label, predicted label, count) over the off-diagonal cells, largest
-        count first, ties by true then predicted class; ``topk``: ``predict_topk(X, top_k, calibrated)``'s pair from the same
-        forward passes, None without ``top_k``; ``rows``: the number of samples."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        V = len(self.classes_)
-        M = self._int_option("error_analysis", "pairs", pairs, 1, ops._lib.PAIRS_MAX)
-        k = 0 if top_k is None else self._int_option("error_analysis", "top_k", top_k, 1, min(V, ops._lib.TOPK_MAX))
-        if V > ops._lib.CONFUSION_MAX_V:
-            raise ValueError(f"error_analysis: {V} classes, the confusion matrix is formed for at most {ops._lib.CONFUSION_MAX_V}")
-        ds = self._as_dataset(X)
-        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
-        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
-        if labels is not None and labels.shape != (len(ds),):
-            raise ValueError(f"error_analysis: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
-
-        def rows(logp, yd):
-            yd = yd if labels is None else labels.to(logp.device)
-            buf = ops.error_analysis_buffers(logp.shape[0], logp.shape[1], k, M, logp.device)
-            return ops.error_analysis_rows(logp if logp.dtype == torch.float32 else logp.float(), yd.contiguous(), buf,
-                                           state=self._cal_state if use else None)
-        got = ops.error_analysis_download(self._forward_logp(ds, rows), matrix=bool(matrix), topk=k > 0)
-        counts = got["counts"]
-        V = (counts.size - 1) // 3                           # the columns of the log-probs
-        if counts[3 * V] > 0:
-            raise ValueError(f"error_analysis: {int(counts[3 * V])} of {len(ds)} labels lie outside the {V} classes of the log-probs")
-        report, macro = metrics.class_report(counts[:V], counts[V:2 * V], counts[2 * V:3 * V])
-        return {"classes": self.classes_, "confusion": got["confusion"], "report": report, "macro": macro,
-                "accuracy": float(counts[2 * V:3 * V].sum() / len(ds)),
-                "pairs": [(self.classes_[t], self.classes_[p], int(c)) for t, p, c in got["pairs"] if c > 0],
-                "topk": (self.classes_[got["topk_idx"]], got["topk_prob"]) if k else None, "rows": len(ds)}
-
-    def _interval_request(self, what, scoring, replicates, level, seed):
-        """The checked arguments of ``score_interval`` / ``compare``: ``(names, top_k, replicates, level, seed)``."""
-        V = len(self.classes_)
-        if V > ops._lib.CONFUSION_MAX_V:
-            raise ValueError(f"{what}: {V} classes, the bootstrap counts at most {ops._lib.CONFUSION_MAX_V}")
-        if scoring is None:                                  # everything that has an interval (top_k_accuracy: k = 2, needs V > 2)
-            names = [n for n in metrics.BOOT_COLUMNS if n != "top_k_accuracy" or V > 2] + [v[0] for v in metrics.BOOT_VALUES]
-        else:
-            names = [scoring] if isinstance(scoring, str) else list(scoring) if isinstance(scoring, (list, tuple)) else []
-            if not names or not all(isinstance(n, str) for n in names) or len(set(names)) != len(names):
-                raise ValueError(f"{what}: scoring={scoring!r}, expected None, a name or a list of distinct names")
-        ks = set()
-        for n in names:
-            if n in metrics.CALIBRATION[:2] or n.startswith("neg_ece"):
-                raise ValueError(f"{what}: {n} has no bootstrap interval here: ECE and MCE are no means over rows, a replicate would need "
-                                 "its own bin sums; neg_brier, neg_log_loss and confidence have one")
-            found = metrics.bootstrap_metric_of(n)
-            if found is None:
-                raise ValueError(f"{what}: {n!r} has no bootstrap interval; known: {metrics.BOOT_COLUMNS[:-1]}, top_k_accuracy, "
-                                 f"top<k>_accuracy, {tuple(v[0] for v in metrics.BOOT_VALUES)}")
-            if found[2] is not None:
-                if not 1 <= found[2] < V:
-                    raise ValueError(f"{what}: {n}: k={found[2]} must lie in [1, {V}) for {V} classes")
-                ks.add(found[2])
-        if len(ks) > 1:
-            raise ValueError(f"{what}: top-k accuracies for k in {sorted(ks)} asked for, one call resamples one k")
-        B = self._int_option(what, "replicates", replicates, 1, ops._lib.BOOT_MAX_REPLICATES)
-        seed = self._int_option(what, "seed", seed, 0, 2 ** 64 - 1)
-        return names, (ks.pop() if ks else 0), B, metrics._boot_level(what, level), seed
-
-    def _bootstrap(self, what, X, y, names, top_k, B, seed, calibrated):
-        """One forward pass over ``X``, then ``ops.score_interval_rows`` and one download: ``(point {name: full-sample score},
-        replicates float64 [B, len(names)], rows)``."""
-        ds = self._as_dataset(X)
-        use = bool(calibrated) and getattr(self, "calibration_", None) is not None
-        labels = None if y is None else torch.from_numpy(np.ascontiguousarray(np.asarray(y), dtype=np.int64))
-        if labels is not None and labels.shape != (len(ds),):
-            raise ValueError(f"{what}: y has shape {tuple(labels.shape)}, expected ({len(ds)},)")
-
-        def rows(logp, yd):
-            yd = yd if labels is None else labels.to(logp.device)
-            buf = ops.score_interval_buffers(logp.shape[0], logp.shape[1], B, logp.device)
-            return ops.score_interval_rows(logp if logp.dtype == torch.float32 else logp.float(), yd.contiguous(), buf, top_k=top_k,
-                                           seed=seed, state=self._cal_state if use else None)
-        got = ops.score_interval_download(self._forward_logp(ds, rows))
-        counts = got["counts"]
-        V = (counts.size - 1) // 3                           # the columns of the log-probs
-        if counts[3 * V] > 0:
-            raise ValueError(f"{what}: {int(counts[3 * V])} of {len(ds)} labels lie outside the {V} classes of the log-probs")
-        y_true = (np.asarray(ds.y) if labels is None else labels.numpy()).astype(np.int64)
-        where = {n: metrics.bootstrap_metric_of(n) for n in names}
-        counted = [n for n in names if where[n][0] < len(metrics.BOOT_COLUMNS)]
-        point = metrics.scores_from_rows(counted, y_true, got["pred"], None, got["rank"], counts, V)
-        table = metrics.reliability_from_table(got["table"])
-        for name, column, sign in metrics.BOOT_VALUES:       # the reliability table's means: confidence, brier, nll
-            if name in where:
-                point[name] = sign * table[("confidence", "brier", "nll")[column]]
-        reps = np.stack([where[n][1] * got["stats"][:, where[n][0]] for n in names], axis=1)
-        return point, reps, len(ds)
-
-    def score_interval(self, X, y=None, scoring=None, replicates=1000, level=0.95, seed=0, calibrated=True, return_replicates=False):
-        """Percentile bootstrap confidence intervals of this fit's scores on ``X`` (``y``: the labels; None: the dataset's), drawn
-        on the device: one forward pass, ``ops.score_rows``, ``ops.reliability_rows`` (at ``temperature_`` for a calibrated fit
-        unless ``calibrated=False``), then ``replicates`` resamples of the per-row results (``ops.bootstrap_scores``) and ONE
-        download.  ``scoring``: a name or a list of names among accuracy, precision / recall / f1 _macro and _weighted,
-        balanced_accuracy, ``top_k_accuracy`` (k = 2) or ``top<k>_accuracy`` (one k per call), ``neg_log_loss``, ``neg_brier`` and
-        ``confidence`` (the mean top-class probability); None: all of them.  ``neg_ece`` / ``neg_mce`` are rejected: they are no
-        means over rows.  Returns {name: {point, mean, std, lower, upper, n_nan}} plus ``replicates``, ``level``, ``seed`` and
-        ``rows``: ``point`` is the full-sample score from the existing paths (``metrics.scores_from_rows``, the reliability
-        table); mean, std (ddof = 1) and the ``level`` percentile bounds are ``metrics.bootstrap_intervals`` of the replicates.
-        A replicate scores the classes present IN IT, as sklearn would score that resample.  ``neg_log_loss`` here is minus the
-        mean of ``reliability_rows``' fp64 nll -- the UNCLIPPED fp64 log-loss of softmax(z / T), not sklearn's float32-clipped
-        one that the history's ``neg_log_loss`` restates; its ``point`` is formed the same way.  The resamples depend on
-        ``(seed, len(X))`` alone.  ``return_replicates=True`` adds ``names`` and ``replicate_scores`` float64 [replicates,
-        len(names)].  Raises ValueError when a label lies outside the classes."""
-        if not self.initialized_:
-            raise RuntimeError("This NeuralNetClassifier instance is not initialized yet.")
-        names, top_k, B, level, seed = self._interval_request("score_interval", scoring, replicates, level, seed)
-        point, reps, n = self._bootstrap("score_interval", X, y, names, top_k, B, seed, calibrated)
-        summary = metrics.bootstrap_intervals(reps, names, level)
-        out = {name: dict(point=float(point[name]), **summary[name]) for name in names}
-        out.update(replicates=B, level=level, seed=seed, rows=n)
-        if return_replicates:
-            out.update(names=names, replicate_scores=reps)
-        return out
-
-    def compare(self, other, X, y=None, scoring=None, replicates=1000, level=0.95, seed=0, calibrated=True, return_replicates=False):
-        """The paired bootstrap of this fit against ``other`` on ``X``: both fits are scored as ``score_interval`` does, with ONE
-        seed -- so replicate b holds the same rows for both -- and the replicates of ``self - other`` are summarised
-        (``metrics.bootstrap_difference``).  Returns {name: {point, mean, std, lower, upper, n_nan, p_not_better}} plus
-        ``replicates``, ``level``, ``seed`` and ``rows``: ``point`` is the difference of the full-sample scores,
-        ``p_not_better`` the share of replicates in which ``self`` does not beat ``other`` (every name is a score: greater is
-        better).  ``return_replicates=True`` adds ``names`` and ``replicate_scores`` (of the difference).  Raises ValueError when
-        the two fits' ``classes_`` differ."""
-        if not self.initialized_ or not getattr(other, "initialized_", False):
-            raise RuntimeError("compare: both NeuralNetClassifier instances must be initialized.")
-        if not np.array_equal(np.asarray(self.classes_), np.asarray(other.classes_)):
-            raise ValueError(f"compare: the two fits have different classes_ ({len(self.classes_)} and {len(other.classes_)} classes): "
-                             "their scores are not comparable")
-        names, top_k, B, level, seed = self._interval_request("compare", scoring, replicates, level, seed)
-        point_a, reps_a, n = self._bootstrap("compare", X, y, names, top_k, B, seed, calibrated)
-        point_b, reps_b, _ = other._bootstrap("compare", X, y, names, top_k, B, seed, calibrated)
-        summary = metrics.bootstrap_difference(reps_a, reps_b, names, level)
-        out = {name: dict(point=float(point_a[name] - point_b[name]), **summary[name]) for name in names}
-        out.update(replicates=B, level=level, seed=seed, rows=n)
-        if return_replicates:
-            out.update(names=names, replicate_scores=reps_a - reps_b)
-        return out
-
-    def score(self, X, y=None):
-        ds = self._as_dataset(X)
-        return float((self.predict(ds) == (ds.y if y is None else np.asarray(y))).mean())
 
     # ------------------------------------------------------------ checkpoint
     def _sgd_state_dict(self):

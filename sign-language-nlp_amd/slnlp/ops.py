@@ -449,13 +449,8 @@ def score_rows(logp, y, out=None):
     ``(pred int32 [N], picked float32 [N], rank int32 [N], counts int32 [3 V + 1])``, device tensors (``slnlp_score_rows``,
     include/slnlp.h); ``out``: such a 4-tuple to fill.  Runs on the current stream of ``logp``'s device; no host wait."""
     _lib.require_gpu()
-    if not (logp.is_cuda and logp.dtype == torch.float32 and logp.dim() == 2 and (logp.stride(1) == 1 or logp.shape[1] == 1)):
-        raise ValueError(f"score_rows: logp must be a float32 [N, V] device tensor with unit column stride, got {logp.dtype} "
-                         f"{tuple(logp.shape)} strides {logp.stride()} on {logp.device}")
-    N, V = int(logp.shape[0]), int(logp.shape[1])
-    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"score_rows: y must be a contiguous int64 [{N}] tensor on {logp.device}")
-    ld = int(logp.stride(0)) if N > 1 else max(V, int(logp.stride(0)))
+    N, V, ld = _logp_matrix("score_rows", logp)
+    _labels("score_rows", y, logp.device, N)
     with torch.cuda.device(logp.device):
         if out is None:
             out = score_buffers(N, V, logp.device)
@@ -479,6 +474,11 @@ def _logp_matrix(what, logp):
     return N, V, (int(logp.stride(0)) if N > 1 else max(V, int(logp.stride(0))))
 
 
+def _labels(what, y, device, N, or_none=""):
+    if not (y.device == device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
+        raise ValueError(f"{what}: y must be a contiguous int64 [{N}] tensor on {device}{or_none}")
+
+
 def _cal_state(what, state, device):
     if not (state.device == device and state.dtype == torch.float64 and state.dim() == 1 and state.numel() == CAL_STATE_DOUBLES
             and state.is_contiguous()):
@@ -492,8 +492,7 @@ def fit_temperature(logp, y, state=None, scratch=None):
     Runs on the current stream of ``logp``'s device; no host wait."""
     _lib.require_gpu()
     N, V, ld = _logp_matrix("fit_temperature", logp)
-    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"fit_temperature: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    _labels("fit_temperature", y, logp.device, N)
     with torch.cuda.device(logp.device):
         if state is None:
             state = torch.empty(CAL_STATE_DOUBLES, dtype=torch.float64, device=logp.device)
@@ -555,8 +554,7 @@ def reliability_rows(logp, y, bins=15, state=None, out=None):
     stream of ``logp``'s device; no host wait."""
     _lib.require_gpu()
     N, V, ld = _logp_matrix("reliability_rows", logp)
-    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"reliability_rows: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    _labels("reliability_rows", y, logp.device, N)
     if isinstance(bins, bool) or not isinstance(bins, numbers.Integral) or not 1 <= bins <= _lib.REL_MAX_BINS:
         raise ValueError(f"reliability_rows: bins={bins!r}, expected an integer in 1..{_lib.REL_MAX_BINS}")
     bins = int(bins)
@@ -599,8 +597,7 @@ def ranking_rows(logp, y, out=None, per_row=True):
     None, whatever ``per_row`` says).  Runs on the current stream of ``logp``'s device; no host wait."""
     _lib.require_gpu()
     N, V, ld = _logp_matrix("ranking_rows", logp)
-    if not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"ranking_rows: y must be a contiguous int64 [{N}] tensor on {logp.device}")
+    _labels("ranking_rows", y, logp.device, N)
     if N > _lib.RANK_MAX_ROWS:
         raise ValueError(f"ranking_rows: {N} rows, the pair counts are exact for at most {_lib.RANK_MAX_ROWS}")
     with torch.cuda.device(logp.device):
@@ -681,8 +678,8 @@ def conformal_rows(logp, y=None, buf=None, *, method="aps", lam=0.0, k_reg=0, ra
     N, V, ld = _logp_matrix(what, logp)
     if V > _lib.CONFORMAL_MAX_V:
         raise ValueError(f"{what}: {V} classes, a row is sorted for at most {_lib.CONFORMAL_MAX_V}")
-    if y is not None and not (y.device == logp.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"{what}: y must be a contiguous int64 [{N}] tensor on {logp.device} or None")
+    if y is not None:
+        _labels(what, y, logp.device, N, " or None")
     if method not in _lib.CONFORMAL_METHODS:
         raise ValueError(f"{what}: method={method!r}, expected one of {tuple(_lib.CONFORMAL_METHODS)}")
     seed, draw = _int_in(what, "seed", seed, 0, 2 ** 64 - 1), _int_in(what, "draw", draw, 0, 2 ** 32 - 1)
@@ -723,8 +720,7 @@ def conformal_summary(buf, y):
     _lib.require_gpu()
     N, V = buf["shape"]
     dev = buf["flat"].device
-    if not (y.device == dev and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"conformal_summary: y must be a contiguous int64 [{N}] tensor on {dev}")
+    _labels("conformal_summary", y, dev, N)
     with torch.cuda.device(dev):
         check(load().slnlp_conformal_summary(ptr(buf["rows"]), ptr(y), N, V, ptr(buf["table"]), stream_ptr()), "conformal_summary")
     return buf["table"]
@@ -862,8 +858,7 @@ def confusion_matrix(pred, y, V, out=None):
         raise ValueError(f"confusion_matrix: pred must be a contiguous int32 [N] device tensor, got {pred.dtype} {tuple(pred.shape)} on "
                          f"{pred.device}")
     N = pred.numel()
-    if not (y.device == pred.device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"confusion_matrix: y must be a contiguous int64 [{N}] tensor on {pred.device}")
+    _labels("confusion_matrix", y, pred.device, N)
     V = _int_in("confusion_matrix", "V", V, 1, _lib.CONFUSION_MAX_V)
     with torch.cuda.device(pred.device):
         if out is None:
