@@ -392,6 +392,56 @@ int slnlp_fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64
 int slnlp_scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, float* out, int64_t ld_out,
                      void* stream);
 
+/* -------------------------------------------------------- label-shift adaptation --
+ * A classifier trained under the class priors pi_s and used under pi_t is corrected exactly by p_t(c | x) ~ p_s(c | x)
+ * pi_t(c) / pi_s(c).  slnlp_fit_priors estimates pi_t from UNLABELLED rows by the EM of Saerens, Latinne and Decaestecker (2002),
+ * slnlp_shift_logp applies a log-ratio to log-probs (slnlp.PriorShift).  logp float32 [N, ld], V <= ld columns used; beta =
+ * beta_dev ? beta_dev[0] : 1 exactly, device memory as for slnlp_reliability_rows; log_source double [V] in device memory,
+ * the FINITE values ln pi_s(c); everything but z itself is fp64.
+ *
+ * slnlp_fit_priors: a row that holds a NaN or whose maximum is not finite (slnlp_reliability_rows' code -2 rows) is excluded
+ * and counted; M rows remain.  With lw^0 = 0 and pi^0_c = exp(log_source_c), for t = 0, 1, ...:
+ *   a_ic = beta z_ic + lw^t_c (the product rounded, then the sum)      lse_i = max_c a_ic + log sum_c exp(a_ic - max_c a_ic)
+ *   S_c = sum_i exp(a_ic - lse_i) over the M rows                      pi^{t+1}_c = S_c / M
+ *   d^t = max_c |pi^{t+1}_c - pi^t_c|;   d^t <= tol -> SLNLP_PRIOR_TOL;   else t == max_iter -> SLNLP_PRIOR_CAP;
+ *   else lw^{t+1}_c = ln max(pi^{t+1}_c, 2^-1022) - log_source_c
+ * (a row's responsibilities sum to 1, so pi needs no normalisation across classes).  The result is pi = pi^{t+1}, log_w_c =
+ * ln max(pi_c, 2^-1022) - log_source_c, iterations = t + 1; one more evaluation at log_w gives gain = (1 / M) sum_i (lse_i(log_w)
+ * - lse_i(0)), the log-likelihood per row that the rows gain from the new priors (>= 0 up to rounding; EM never lowers it).
+ * max_iter in 0..SLNLP_PRIOR_MAX_ITER (0: one evaluation, pi = the mean prediction), tol finite and >= 0.
+ * M == 0 gives table rows 0 and 1 = pi^0, log_w = 0, gain = 0, d = 0, iterations = 0 and SLNLP_PRIOR_EMPTY.
+ *   table double [3, V]: row 0 = pi^1, the mean of softmax(beta z_i) over the M rows (the model's own mean prediction);
+ *                        row 1 = pi; row 2 = log_w
+ *   state: SLNLP_PRIOR_STATE_BYTES of device memory, 8-byte aligned, written by the call (no need to clear it):
+ *     double [0] gain   [1] the last d   [2..7] zero
+ *     int64  [8] reason (SLNLP_PRIOR_*)   [9] iterations   [10] M   [11] excluded rows   [12..15] zero
+ *   scratch: slnlp_fit_priors_scratch_bytes(N, V) bytes (-1 and a message for N or V outside 1..INT32_MAX), 8-byte aligned.
+ * The call queues a fixed sequence of 3 (max_iter + 1) + 2 launches on stream -- per iteration the rows' lse_i (a wave per row),
+ * S_c (a block per class: thread t adds rows t, t + 256, ... in increasing order, then a fixed binary tree over the 256 partial
+ * sums) and one block that forms pi, log_w, d and takes the stop decision; then the evaluation at the result and the gain --
+ * and never waits for the host: once the reason is set, the iteration launches read it and return at once.  No atomics: the
+ * result is a function of the arguments alone.
+ *
+ * slnlp_shift_logp: out[i, c] = (beta z_ic + log_w_c) - logsumexp_c'(beta z_ic' + log_w_c'), log_w double [V] in device memory
+ * (table row 2), per row in fp64 with the maximum subtracted, rounded once to float32.  log_w_c = -inf is legal and gives -inf in
+ * that column; a row that holds a NaN, whose maximum is not finite, or whose largest beta z_ic + log_w_c is not finite gets NaN
+ * in every column.  out may be logp itself with ld_out == ld (slnlp_scale_logp's rule); any other overlap is an error.  One
+ * launch.
+ *
+ * Errors of both (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer (beta_dev may be null), N
+ * or V outside 1..INT32_MAX, ld or ld_out < V, max_iter or tol out of range, scratch too small, a misaligned pointer (logp and
+ * out 4 bytes, the others 8), an output overlapping an input or another output. */
+#define SLNLP_PRIOR_MAX_ITER 1024
+#define SLNLP_PRIOR_STATE_BYTES 128
+#define SLNLP_PRIOR_TOL 1
+#define SLNLP_PRIOR_CAP 2
+#define SLNLP_PRIOR_EMPTY 3
+int64_t slnlp_fit_priors_scratch_bytes(int64_t N, int64_t V);
+int slnlp_fit_priors(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, const double* log_source,
+                     int max_iter, double tol, double* table, void* state, void* scratch, int64_t scratch_bytes, void* stream);
+int slnlp_shift_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, const double* log_w, float* out,
+                     int64_t ld_out, void* stream);
+
 /* ------------------------------------------------------ reliability diagnostics --
  * What expected / maximum calibration error (ECE, MCE), the multiclass Brier score and the log-loss of a set of log-probs are
  * functions of (slnlp/ops.py forms the scores on the host).  logp float32 [N, ld], V <= ld columns used; y int64 [N]; bins = B

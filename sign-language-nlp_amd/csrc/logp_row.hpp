@@ -16,6 +16,7 @@
 //   fit_rows / scale_logp (calibration.hip) take the maximum with fmaxf / wave_max: another NaN rule (a NaN is skipped) and no arg-max.
 //   fit_rows also evaluates exp for the columns AT the maximum, its s1 and s2 need it: folding it in would change bits.
 //   score_rows (score.hip) fuses its arg-max with three other counts in one pass over the row.
+//   prior_rows / shift_logp (prior_shift.hip) take logp_row_argmax's `finite` alone from here: their maximum is that of beta z + lw.
 #pragma once
 #include <limits.h>
 #include <math.h>

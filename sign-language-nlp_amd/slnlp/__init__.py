@@ -1,10 +1,13 @@
 """slnlp: the MI355X path of the sign-language gloss classifier.  The submodules are imported on demand (``slnlp.net``,
-``slnlp.ops``, ...); ``slnlp.VotingEnsemble`` is resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
-__all__ = ["VotingEnsemble"]
+``slnlp.ops``, ...); ``slnlp.VotingEnsemble`` and ``slnlp.PriorShift`` are resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
+__all__ = ["VotingEnsemble", "PriorShift"]
 
 
 def __getattr__(name):
     if name == "VotingEnsemble":
         from .ensemble import VotingEnsemble
         return VotingEnsemble
+    if name == "PriorShift":
+        from .prior_shift import PriorShift
+        return PriorShift
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -128,6 +128,9 @@ SIGNATURES = {
     "slnlp_fit_temperature_scratch_bytes": (i64, [i64]),
     "slnlp_fit_temperature": (i32, [vp, i64, vp, i64, i64, vp, vp, i64, vp]),
     "slnlp_scale_logp": (i32, [vp, i64, i64, i64, vp, vp, i64, vp]),
+    "slnlp_fit_priors_scratch_bytes": (i64, [i64, i64]),
+    "slnlp_fit_priors": (i32, [vp, i64, i64, i64, vp, vp, i32, C.c_double, vp, vp, vp, i64, vp]),
+    "slnlp_shift_logp": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp]),
     "slnlp_reliability_rows": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp]),
     "slnlp_topk_rows": (i32, [vp, i64, i64, i64, i32, vp, vp, vp, vp]),
     "slnlp_confusion_matrix": (i32, [vp, vp, i64, i64, vp, vp]),
@@ -277,6 +280,8 @@ REDUCTIONS = {"mean": 0, "sum": 1}             # CrossEntropyLoss reductions the
 UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
 CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_*
+PRIOR_REASONS = {1: "tol", 2: "cap", 3: "empty"}   # SLNLP_PRIOR_*
+PRIOR_MAX_ITER = 1024                           # SLNLP_PRIOR_MAX_ITER
 REL_MAX_BINS = 64                               # SLNLP_REL_MAX_BINS
 RANK_CHUNK = 2048                               # SLNLP_RANK_CHUNK
 RANK_MAX_ROWS = 67108863                        # SLNLP_RANK_MAX_ROWS

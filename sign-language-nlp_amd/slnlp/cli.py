@@ -59,7 +59,18 @@ split, slnlp/net.py) and makes rank 0 write, next to test_output.json, what the 
     test_conformal_classes.csv     class, name, support, coverage and mean set size per class (an empty cell for a class
                                    without a test row)
 
-Without the five keys the workdir holds exactly the files listed above.
+A top-level ``prior_shift: {max_iter: 200, tol: 1e-6, source: train}`` (all optional, these defaults) makes rank 0 wrap the refit in
+a ``slnlp.PriorShift``, estimate the class priors of the test split from its UNLABELLED rows by EM on the device and write, next to
+test_output.json:
+
+    test_prior_shift.json          gain, d, reason, iterations, rows, nan_rows of the EM, and accuracy, balanced_accuracy and
+                                   log_loss on the test split before and after the re-weighting
+    test_prior_shift_classes.csv   class, name, source prior, estimated prior and test frequency per class
+
+``source``: ``train`` -- the refit's mean predicted probability on the train data, what it learned as priors whatever the sampler
+drew -- or ``train_labels`` -- the train labels' frequencies, with 1 added to every count.
+
+Without the six keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -73,7 +84,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal")
+             "ensemble", "ranking", "conformal", "prior_shift")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -314,6 +325,71 @@ def save_conformal(est, test_data, workdir):
     return res
 
 
+PRIOR_SHIFT_DEFAULTS = {"max_iter": 200, "tol": 1e-6, "source": "train"}
+PRIOR_SHIFT_MAX_ITER = 1024                                                     # SLNLP_PRIOR_MAX_ITER
+PRIOR_SHIFT_SOURCES = ("train", "train_labels")
+PRIOR_SHIFT_SCORES = ("accuracy", "balanced_accuracy", "neg_log_loss")
+
+
+def prior_shift_options(setting):
+    """The ``prior_shift`` key with its defaults filled in -- {max_iter 200, tol 1e-6, source train} -- or None when the key is
+    absent.  Anything but a dict over these three keys ({}: all defaults) with ``max_iter`` an integer in 0..1024, ``tol`` a finite
+    number >= 0 and ``source`` "train" or "train_labels" raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"prior_shift={setting!r}: expected a dict with keys among {tuple(PRIOR_SHIFT_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(PRIOR_SHIFT_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"prior_shift: unknown keys {unknown} (known: {tuple(PRIOR_SHIFT_DEFAULTS)})")
+    opts = dict(PRIOR_SHIFT_DEFAULTS, **setting)
+    if isinstance(opts["tol"], str):                                            # YAML 1.1 reads ``1e-6`` (no dot) as a string
+        try:
+            opts["tol"] = float(opts["tol"])
+        except ValueError:
+            pass
+    if isinstance(opts["max_iter"], bool) or not isinstance(opts["max_iter"], int) or not 0 <= opts["max_iter"] <= PRIOR_SHIFT_MAX_ITER:
+        raise ValueError(f"prior_shift: max_iter={opts['max_iter']!r}, expected an integer in 0..{PRIOR_SHIFT_MAX_ITER}")
+    if isinstance(opts["tol"], bool) or not isinstance(opts["tol"], (int, float)) or not 0.0 <= opts["tol"] < float("inf"):
+        raise ValueError(f"prior_shift: tol={opts['tol']!r}, expected a finite number >= 0")
+    if opts["source"] not in PRIOR_SHIFT_SOURCES:
+        raise ValueError(f"prior_shift: source={opts['source']!r}, expected one of {PRIOR_SHIFT_SOURCES}")
+    return {"max_iter": int(opts["max_iter"]), "tol": float(opts["tol"]), "source": opts["source"]}
+
+
+def save_prior_shift(est, train_data, test_data, opts, workdir):
+    """``PriorShift(est, source).fit(test_data)`` -- ``source`` the train data itself or its smoothed label frequencies -- as
+    ``test_prior_shift.json`` (the EM's scalars and {accuracy, balanced_accuracy, log_loss} on the test split ``before`` and
+    ``after``) and ``test_prior_shift_classes.csv`` (class, name, source_prior, estimated_prior, test_frequency) in ``workdir``;
+    floats are written with ``repr``.  Returns (the wrapper, what it wrote)."""
+    from .net import ScoringWrapper, _CachedPredictor
+    from .prior_shift import PriorShift, class_frequencies
+    V = len(est.classes_)
+    source = train_data if opts["source"] == "train" else class_frequencies(train_data.y, V, smoothing=1.0)
+    shifted = PriorShift(est, source).fit(test_data, max_iter=opts["max_iter"], tol=opts["tol"])
+    labels = np.arange(V)
+
+    def scores(e):                                                              # one forward pass per estimator
+        cached = _CachedPredictor(e.predict_proba(test_data), e.classes_)
+        got = {n: float(ScoringWrapper(n, labels)(cached, test_data, test_data.y)) for n in PRIOR_SHIFT_SCORES}
+        return {"accuracy": got["accuracy"], "balanced_accuracy": got["balanced_accuracy"], "log_loss": -got["neg_log_loss"]}
+    info = shifted.prior_shift_
+    out = {"gain": float(info["gain"]), "d": float(info["d"]), "reason": info["reason"], "iterations": int(info["iterations"]),
+           "rows": int(info["rows"]), "nan_rows": int(info["nan_rows"]), "source": opts["source"], "max_iter": opts["max_iter"],
+           "tol": opts["tol"], "before": scores(est), "after": scores(shifted)}
+    save_json(out, os.path.join(workdir, "test_prior_shift.json"))
+    names = test_data.vocab_y.itos if getattr(test_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    y = np.asarray(test_data.y)
+    freq = np.bincount(y[(y >= 0) & (y < V)], minlength=V) / max(1, len(y))
+    with open(os.path.join(workdir, "test_prior_shift_classes.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["class", "name", "source_prior", "estimated_prior", "test_frequency"])
+        for i, c in enumerate(shifted.classes_):
+            w.writerow([int(c), name(c), repr(float(shifted.source_priors_[i])), repr(float(shifted.priors_[i])), repr(float(freq[i]))])
+    return shifted, out
+
+
 INTERVAL_DEFAULTS = {"replicates": 1000, "level": 0.95, "seed": 0}
 INTERVAL_MAX_REPLICATES = 65536                                                 # SLNLP_BOOT_MAX_REPLICATES
 
@@ -448,6 +524,7 @@ def run(args):
     ensemble = ensemble_options(args.get("ensemble"))
     ranking = ranking_options(args.get("ranking"))
     conformal = conformal_options(args.get("conformal"))                         # (the estimator's own check: slnlp/net.py)
+    prior_shift = prior_shift_options(args.get("prior_shift"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -495,6 +572,8 @@ def run(args):
             save_conformal(est, test_data, workdir)
         if ensemble is not None:
             save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
+        if prior_shift is not None:
+            save_prior_shift(est, train_data, test_data, prior_shift, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

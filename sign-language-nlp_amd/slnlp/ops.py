@@ -539,6 +539,77 @@ def scale_logp(logp, state, out=None):
     return out
 
 
+PRIOR_STATE_DOUBLES = 16                     # SLNLP_PRIOR_STATE_BYTES / 8: eight doubles, then eight int64
+
+
+def _prior_vector(what, name, t, device, V):
+    if not (t.device == device and t.dtype == torch.float64 and t.dim() == 1 and t.numel() == V and t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous float64 [{V}] tensor on {device}")
+
+
+def fit_priors(logp, log_source, state=None, max_iter=200, tol=1e-6, out=None, scratch=None):
+    """Re-estimate the class priors of the UNLABELLED rows ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) by EM
+    (``slnlp_fit_priors``, include/slnlp.h).  ``log_source``: float64 [V] on the device, ln of the priors the log-probs were
+    trained under (finite).  ``state``: a calibration state whose beta is read on the device, so the EM runs on softmax(beta
+    logp); None: beta = 1.  ``max_iter`` in 0..1024 (0: one evaluation, the priors are the mean prediction), ``tol`` finite and
+    >= 0.  Returns ONE float64 [3 V + 16] device tensor (``priors_download`` reads it): the table -- the mean prediction, the
+    priors, the log-ratio ln(priors / source) that ``shift_logp`` takes, ``out[2 * V:3 * V]`` -- then the 16 words of the fit's
+    state.  ``out`` / ``scratch`` (float64 [>= 2 N + V]): buffers to use.  Runs on the current stream of ``logp``'s device; no
+    host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("fit_priors", logp)
+    _prior_vector("fit_priors", "log_source", log_source, logp.device, V)
+    max_iter = _int_in("fit_priors", "max_iter", max_iter, 0, _lib.PRIOR_MAX_ITER)
+    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0.0 <= float(tol) < float("inf"):
+        raise ValueError(f"fit_priors: tol={tol!r}, expected a finite number >= 0")
+    if state is not None:
+        _cal_state("fit_priors", state, logp.device)
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = torch.empty(3 * V + PRIOR_STATE_DOUBLES, dtype=torch.float64, device=logp.device)
+        _prior_vector("fit_priors", "out", out, logp.device, 3 * V + PRIOR_STATE_DOUBLES)
+        if scratch is None:
+            scratch = torch.empty(2 * N + V, dtype=torch.float64, device=logp.device)
+        if not (scratch.device == logp.device and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.is_contiguous()):
+            raise ValueError(f"fit_priors: scratch must be a contiguous float64 [>= {2 * N + V}] tensor on {logp.device}")
+        check(load().slnlp_fit_priors(ptr(logp), ld, N, V, ptr(state) if state is not None else None, ptr(log_source), max_iter,
+                                      float(tol), ptr(out), ptr(out[3 * V:]), ptr(scratch), scratch.numel() * 8, stream_ptr()),
+              "fit_priors")
+    return out
+
+
+def priors_download(out):
+    """``fit_priors``' result as a dict: {priors, mean_proba, log_ratio (float64 [V] each), gain, d, reason ("tol" | "cap" |
+    "empty"), iterations, rows, nan_rows}.  ONE device-to-host copy (it waits for the fit's launches)."""
+    h = out.cpu().numpy()
+    V = (h.size - PRIOR_STATE_DOUBLES) // 3
+    s = h[3 * V:]
+    q = s.view("int64")[8:]
+    return {"priors": h[V:2 * V].copy(), "mean_proba": h[:V].copy(), "log_ratio": h[2 * V:3 * V].copy(), "gain": float(s[0]),
+            "d": float(s[1]), "reason": _lib.PRIOR_REASONS[int(q[0])], "iterations": int(q[1]), "rows": int(q[2]), "nan_rows": int(q[3])}
+
+
+def shift_logp(logp, log_w, state=None, out=None):
+    """The log-probs under other class priors, ``(beta logp + log_w) - logsumexp(beta logp + log_w)`` per row (``slnlp_shift_logp``):
+    ``log_w`` float64 [V] on the device, ln(target prior / source prior) -- ``fit_priors``' ``out[2 * V:3 * V]``; ``state``: a
+    calibration state whose beta is read on the device (None: beta = 1).  ``out``: a float32 [N, V] tensor to fill -- ``logp``
+    itself for in place; default a new one.  Runs on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("shift_logp", logp)
+    _prior_vector("shift_logp", "log_w", log_w, logp.device, V)
+    if state is not None:
+        _cal_state("shift_logp", state, logp.device)
+    with torch.cuda.device(logp.device):
+        if out is None:
+            out = torch.empty(N, V, dtype=torch.float32, device=logp.device)
+        if out.device != logp.device or tuple(out.shape) != (N, V):
+            raise ValueError(f"shift_logp: out must be a float32 [{N}, {V}] tensor on {logp.device}")
+        _, _, ld_out = _logp_matrix("shift_logp (out)", out)
+        check(load().slnlp_shift_logp(ptr(logp), ld, N, V, ptr(state) if state is not None else None, ptr(log_w), ptr(out), ld_out,
+                                      stream_ptr()), "shift_logp")
+    return out
+
+
 def reliability_buffers(N, bins, device):
     """The two output tensors of ``reliability_rows`` for N rows and ``bins`` bins -- rows float64 [N, 4], table float64
     [bins + 1, 4] -- as slices of ONE allocation, so ``reliability_download`` is one copy."""
