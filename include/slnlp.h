@@ -683,6 +683,67 @@ int slnlp_conformal_rows(const float* logp, int64_t ld, const int64_t* y, int64_
 int slnlp_conformal_quantile(const double* score, const int32_t* rows, int64_t N, double alpha, double* state, void* stream);
 int slnlp_conformal_summary(const int32_t* rows, const int64_t* y, int64_t N, int64_t V, int64_t* table, void* stream);
 
+/* ------------------------------------------------------- selective prediction --
+ * Whether the confidence of a set of log-probs ranks its own errors, and where to cut when the model may decline to answer
+ * (NeuralNetClassifier.risk_coverage / fit_rejection / predict_selective; slnlp/metrics.py's selective_report): the risk-coverage
+ * curve, its area (AURC, Geifman & El-Yaniv) and the reject option.  tests/selective_ref.py restates everything below in numpy.
+ *
+ * Per row.  logp float32 [N, ld], V <= ld columns used; y int64 [N] or null; beta = beta_dev ? beta_dev[0] : 1.  zmax, a = beta zmax,
+ * n_max, rest and s0 = 1 + rest are slnlp_topk_rows' / slnlp_reliability_rows' fp64 decomposition (e_c = exp(beta z_c - a) over the
+ * columns NOT at the maximum, those at the maximum counted).
+ *   pred   the arg-max in slnlp_score_rows' order (a NaN first, larger values first, equal values by ascending column)
+ *   code   -2: the row holds a NaN or its maximum is not finite (looked at first); -1: y given and the label outside [0, V) (never
+ *          used as an index); else 0.  Rows with another code than 0 are EXCLUDED: they take part in no count below.
+ *   wrong  1 iff y is given, the code is 0 and pred != y_i
+ *   kappa  the confidence, fp64; the order of kappa is the order of acceptance.  NaN for code -2; formed for code -1.
+ *          SLNLP_SEL_MAX_PROB     1 / s0: slnlp_topk_rows' prob[i][0] and slnlp_reliability_rows' conf bit for bit
+ *          SLNLP_SEL_MARGIN       p(1) - p(2): 0 when n_max >= 2, else (1 - e2) / s0 with e2 the largest e_c (V = 1: e2 = 0, kappa 1)
+ *          SLNLP_SEL_NEG_ENTROPY  sum_c p_c ln p_c = (sum_c e_c t_c) / s0 - log1p(rest), t_c = beta z_c - a; a term with e_c == 0
+ *                                 counts as 0; each lane adds its columns in ascending order, the lanes meet in a fixed tree
+ *   accepted  kappa >= tau with tau = tau_dev[0] (a device double[4] whose first entry is the threshold, like the conformal state:
+ *          no host round trip between choosing and applying it); 0 without tau_dev and for code -2
+ * slnlp_selective_rows writes kappa double [N] and rows int32 [N, 4] = (pred, wrong, accepted, code).  One launch, one wave per row.
+ *
+ * Per included row.  slnlp_selective_counts takes kappa and rows as above (or as a caller made them); a row is included when its
+ * code is 0 and its kappa is no NaN (a code-0 row with a NaN kappa is counted with the -2 rows).  With n the included rows:
+ *   ge_i = #{included j: kappa_j >= kappa_i}        ge_wrong_i = #{included j with wrong_j != 0: kappa_j >= kappa_i}
+ * exact integers; ties are ties of the fp64 values and -0.0 equals +0.0.  The threshold tau = kappa_i accepts ge_i rows at
+ * selective risk ge_wrong_i / ge_i and coverage ge_i / n.  counts int32 [N, 2] = (ge, ge_wrong); (0, 0) for an excluded row.
+ * table double [SLNLP_SEL_TABLE_HEAD + ceil(N / SLNLP_SEL_CHUNK)]:
+ *   [0..7]   n, E = the included wrong rows, rows with code -1, every other excluded row, S = sum_i ge_wrong_i / ge_i, AURC = S / n
+ *            (NaN for n = 0), 0, 0.  AURC is the mean of the prefix risks when no two rows tie and, unlike it, a function of the
+ *            multiset of rows.
+ *   [8 + 2 l], [9 + 2 l], l < 8    coverage at risk: (ge, ge_wrong) of the largest ge_i with (double)ge_wrong_i <= risks[l] * (double)ge_i,
+ *            (0, 0) when there is none and for l >= nr
+ *   [24 + 2 l], [25 + 2 l], l < 8  risk at coverage: (ge, ge_wrong) of the smallest ge_i >= ceil(coverages[l] * (double)n), (0, 0)
+ *            for n = 0 and for l >= nc
+ *   [40 + b]  the sum of ge_wrong_i / ge_i over chunk b of included rows (0 for a chunk that holds none): S adds them ascending
+ * risks / coverages are HOST arrays of nr / nc <= SLNLP_SEL_MAX_LEVELS numbers in [0, 1], copied by the call.
+ * Three launches on the stream, no host wait: the level cells take their neutral elements; one block of 256 threads per chunk of
+ * SLNLP_SEL_CHUNK included rows (chunked by included ordinal in ascending row order: ballots, no cursor) sorts its chunk's
+ * order-preserving 64-bit keys in LDS, streams all N rows against them with a binary search and integer LDS atomics on two
+ * histograms, takes suffix sums, adds its terms in a fixed order and reduces the levels with 64-bit integer atomic max / min on
+ * (ge << 32 | ge_wrong), which commute; one block adds the chunk sums in ascending order and writes the table.  No float atomics:
+ * the result is a function of the arguments alone.  Every chunk's block reads all N rows, so the work is O(N^2 / SLNLP_SEL_CHUNK x
+ * log SLNLP_SEL_CHUNK); SLNLP_SEL_MAX_ROWS bounds that work (and keeps the counts in int32): it is NOT a measured limit.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null logp, kappa, rows, counts or table, null
+ * risks / coverages with a count above 0; N outside 1..SLNLP_SEL_MAX_ROWS; V outside 1..INT32_MAX - 1; ld < V; an unknown score;
+ * nr or nc outside 0..SLNLP_SEL_MAX_LEVELS; a level outside [0, 1] (a NaN included); a misaligned pointer (logp 4 bytes; y,
+ * beta_dev, tau_dev, kappa, counts 8; rows 16; table 32); an output overlapping an input or the other output. */
+#define SLNLP_SEL_MAX_PROB 0
+#define SLNLP_SEL_MARGIN 1
+#define SLNLP_SEL_NEG_ENTROPY 2
+#define SLNLP_SEL_CHUNK 2048
+#define SLNLP_SEL_MAX_LEVELS 8
+#define SLNLP_SEL_TABLE_HEAD 40
+#define SLNLP_SEL_MAX_ROWS 1048576      /* 2^20: 512 chunks; bounds the quadratic work, not a measured limit */
+#define SLNLP_SEL_STATE_BYTES 32        /* double[4]: tau first */
+int slnlp_selective_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, int score, const double* beta_dev,
+                         const double* tau_dev, double* kappa, int32_t* rows, void* stream);
+int slnlp_selective_counts(const double* kappa, const int32_t* rows, int64_t N, const double* risks, int nr, const double* coverages,
+                           int nc, int32_t* counts, double* table, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

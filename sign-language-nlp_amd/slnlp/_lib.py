@@ -142,6 +142,8 @@ SIGNATURES = {
     "slnlp_conformal_rows": (i32, [vp, i64, vp, i64, i64, vp, i32, C.c_double, i32, i32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]),
     "slnlp_conformal_quantile": (i32, [vp, vp, i64, C.c_double, vp, vp]),
     "slnlp_conformal_summary": (i32, [vp, vp, i64, i64, vp, vp]),
+    "slnlp_selective_rows": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp, vp]),
+    "slnlp_selective_counts": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -289,6 +291,11 @@ TOPK_MAX = 64                                   # SLNLP_TOPK_MAX
 CONFORMAL_MAX_V = 1024                          # SLNLP_CONFORMAL_MAX_V
 CONFORMAL_METHODS = {"lac": 0, "aps": 1}        # SLNLP_CONFORMAL_LAC / _APS
 CONFORMAL_STAGE = 0x636F6E66                    # SLNLP_CONFORMAL_STAGE
+SEL_SCORES = {"max_prob": 0, "margin": 1, "neg_entropy": 2}    # SLNLP_SEL_MAX_PROB / _MARGIN / _NEG_ENTROPY
+SEL_CHUNK = 2048                                # SLNLP_SEL_CHUNK
+SEL_MAX_LEVELS = 8                              # SLNLP_SEL_MAX_LEVELS
+SEL_TABLE_HEAD = 40                             # SLNLP_SEL_TABLE_HEAD
+SEL_MAX_ROWS = 1048576                          # SLNLP_SEL_MAX_ROWS
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

@@ -70,7 +70,15 @@ test_output.json:
 ``source``: ``train`` -- the refit's mean predicted probability on the train data, what it learned as priors whatever the sampler
 drew -- or ``train_labels`` -- the train labels' frequencies, with 1 added to every count.
 
-Without the six keys the workdir holds exactly the files listed above.
+A top-level ``selective: {score: max_prob, risks: [0.01, 0.05, 0.1], coverages: [0.5, 0.8, 0.9, 1.0]}`` (all optional, these
+defaults; ``score``: max_prob, margin or neg_entropy; up to 8 levels each) makes rank 0 write, next to test_output.json, what the
+refit's ``risk_coverage`` finds on the test split -- how wrong the fit is on what it answers when it may decline to answer:
+
+    test_selective.json            rows, errors, accuracy, excluded_labels, excluded_nan, aurc, aurc_oracle, e_aurc, score,
+                                   temperature, coverage_at_risk and risk_at_coverage (one entry per level; empirical, no guarantee)
+    test_risk_coverage.csv         threshold, accepted, wrong, coverage and risk per distinct confidence threshold, descending
+
+Without the seven keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -84,7 +92,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -325,6 +333,54 @@ def save_conformal(est, test_data, workdir):
     return res
 
 
+SELECTIVE_DEFAULTS = {"score": "max_prob", "risks": [0.01, 0.05, 0.1], "coverages": [0.5, 0.8, 0.9, 1.0]}
+SELECTIVE_SCORES = ("max_prob", "margin", "neg_entropy")                        # slnlp/judge.py: SELECTIVE_SCORES
+SELECTIVE_MAX_LEVELS = 8                                                        # SLNLP_SEL_MAX_LEVELS
+SELECTIVE_SCALARS = ("rows", "errors", "accuracy", "excluded_labels", "excluded_nan", "aurc", "aurc_oracle", "e_aurc")
+
+
+def selective_options(setting):
+    """The ``selective`` key with its defaults filled in -- {score max_prob, risks [0.01, 0.05, 0.1], coverages [0.5, 0.8, 0.9,
+    1.0]} -- or None when the key is absent.  Anything but a dict over these three keys ({}: all defaults) with ``score`` one of
+    max_prob / margin / neg_entropy and ``risks`` / ``coverages`` lists of at most 8 numbers in [0, 1] raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"selective={setting!r}: expected a dict with keys among {tuple(SELECTIVE_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(SELECTIVE_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"selective: unknown keys {unknown} (known: {tuple(SELECTIVE_DEFAULTS)})")
+    opts = dict(SELECTIVE_DEFAULTS, **setting)
+    if opts["score"] not in SELECTIVE_SCORES:
+        raise ValueError(f"selective: score={opts['score']!r}, expected one of {SELECTIVE_SCORES}")
+    for key in ("risks", "coverages"):
+        v = opts[key]
+        if not isinstance(v, (list, tuple)) or len(v) > SELECTIVE_MAX_LEVELS or \
+                not all(isinstance(x, (int, float)) and not isinstance(x, bool) and 0.0 <= x <= 1.0 for x in v):
+            raise ValueError(f"selective: {key}={v!r}, expected a list of at most {SELECTIVE_MAX_LEVELS} numbers in [0, 1]")
+    return {"score": opts["score"], "risks": [float(x) for x in opts["risks"]], "coverages": [float(x) for x in opts["coverages"]]}
+
+
+def save_selective(est, test_data, opts, workdir):
+    """``est.risk_coverage(test_data, **opts)`` as ``test_selective.json`` (rows, errors, accuracy, the excluded rows, aurc,
+    aurc_oracle, e_aurc, score, temperature and the two level tables) and ``test_risk_coverage.csv`` (threshold, accepted, wrong,
+    coverage, risk per distinct threshold, descending) in ``workdir``; floats are written with ``repr`` (they read back bit for
+    bit).  Returns the result."""
+    res = est.risk_coverage(test_data, **opts)
+    out = {k: (int(res[k]) if k in ("rows", "errors", "excluded_labels", "excluded_nan") else float(res[k])) for k in SELECTIVE_SCALARS}
+    out.update(score=res["score"], temperature=float(res["temperature"]), coverage_at_risk=res["coverage_at_risk"],
+               risk_at_coverage=res["risk_at_coverage"])
+    save_json(out, os.path.join(workdir, "test_selective.json"))
+    curve = res["curve"]
+    with open(os.path.join(workdir, "test_risk_coverage.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["threshold", "accepted", "wrong", "coverage", "risk"])
+        for i in range(len(curve["threshold"])):
+            w.writerow([repr(float(curve["threshold"][i])), int(curve["accepted"][i]), int(curve["wrong"][i]),
+                        repr(float(curve["coverage"][i])), repr(float(curve["risk"][i]))])
+    return res
+
+
 PRIOR_SHIFT_DEFAULTS = {"max_iter": 200, "tol": 1e-6, "source": "train"}
 PRIOR_SHIFT_MAX_ITER = 1024                                                     # SLNLP_PRIOR_MAX_ITER
 PRIOR_SHIFT_SOURCES = ("train", "train_labels")
@@ -525,6 +581,7 @@ def run(args):
     ranking = ranking_options(args.get("ranking"))
     conformal = conformal_options(args.get("conformal"))                         # (the estimator's own check: slnlp/net.py)
     prior_shift = prior_shift_options(args.get("prior_shift"))
+    selective = selective_options(args.get("selective"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -570,6 +627,8 @@ def run(args):
             save_ranking(est, test_data, ranking, workdir)
         if conformal is not None:
             save_conformal(est, test_data, workdir)
+        if selective is not None:
+            save_selective(est, test_data, selective, workdir)
         if ensemble is not None:
             save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
         if prior_shift is not None:

@@ -5,7 +5,7 @@ member runs its own forward passes (``NeuralNetClassifier._forward_logp``: under
 weights where it predicts with them), ONE ``ops.ensemble_rows`` launch combines the members' device log-probs, each at its own
 temperature, into one set of float32 log-probs, and everything that judges one fit's log-probs -- ``predict_proba``,
 ``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare``, ``conformalize``, ``predict_set``,
-``coverage`` -- then works on the ensemble through the
+``coverage``, ``risk_coverage``, ``fit_rejection``, ``predict_selective`` -- then works on the ensemble through the
 same ``_forward_logp(ds, then)`` hook: both classes inherit those methods from ``slnlp.judge.LogProbJudge``.  The
 same launch gives, per sample, how much the members disagree (``uncertainty``): the entropy of the mixture, the expected entropy
 of a member and their difference, the mutual information.  Nothing is averaged on the host and no torch arithmetic runs on the
@@ -93,7 +93,8 @@ class VotingEnsemble(LogProbJudge, ClassifierMixin, BaseEstimator):
         return self._combine(ds, lambda out, yd, rows: then(out, yd), False)
 
     # the log-prob consumers are LogProbJudge's: they read ``self._forward_logp``, ``classes_``, ``calibration_`` (None here: T = 1);
-    # the conformal threshold is the ensemble's own (``conformal_``), taken by ``conformalize``
+    # the conformal threshold is the ensemble's own (``conformal_``), taken by ``conformalize``; so is the rejection threshold
+    # (``rejection_``, ``fit_rejection``)
 
     def uncertainty(self, X, per_row=False):
         """How much the members disagree on ``X``: ``metrics.uncertainty_summary`` of ``ops.ensemble_rows``' per-row terms --

@@ -7,7 +7,8 @@ here exists on both.  The mixin is written against one hook and a few attributes
   ``then(logp, y_dev)``; returns what ``then`` returns once that stream has drained;
 * ``classes_``, ``initialized_``, ``predict_nonlinearity``;
 * ``calibration_`` / ``_cal_state`` / ``temperature_``: a fitted temperature and its device state (absent or None: T = 1);
-* ``conformal_`` / ``_conf_state``: the conformal options and the device threshold, set here by ``_set_conformal``.
+* ``conformal_`` / ``_conf_state``: the conformal options and the device threshold, set here by ``_set_conformal``;
+* ``rejection_`` / ``_rej_state``: the reject option's threshold and its device state, set here by ``_set_rejection``.
 
 What needs the fit itself and not its log-probs (the valid split, the weights, the checkpoint) stays in slnlp/net.py."""
 import math
@@ -22,6 +23,7 @@ from .data import TokenDataset
 
 CONFORMAL_DEFAULTS = {"alpha": 0.1, "method": "aps", "randomized": True, "lam": 0.0, "k_reg": 0, "seed": 0}
 CONFORMAL_METHODS = tuple(ops._lib.CONFORMAL_METHODS)
+SELECTIVE_SCORES = tuple(ops._lib.SEL_SCORES)
 
 
 def conformal_options(setting):
@@ -450,3 +452,108 @@ class LogProbJudge:
         res.update(qhat=c["qhat"], calibration_rows=c["n"], k=c["k"], alpha=c["alpha"], classes=self.classes_)
         return res
 
+    # ------------------------------------------------ selective prediction
+    def _selective_pass(self, what, ds, labels_on_device, score, calibrated, risks=(), coverages=()):
+        """One forward pass, ``ops.selective_rows`` and ``ops.selective_counts`` on the device log-probs, ONE download (32 bytes a
+        row): ``(ops.selective_download's dict, whether the temperature was used, the device)``."""
+        use = self._uses_temperature(calibrated)
+
+        def rows(logp, yd):
+            buf = ops.selective_rows(logp, labels_on_device(logp, yd), score=score, state=self._cal_state if use else None)
+            ops.selective_counts(buf, risks, coverages)
+            return buf
+        buf = self._judge(ds, rows)
+        return ops.selective_download(buf), use, buf["flat"].device
+
+    def risk_coverage(self, X, y=None, score="max_prob", calibrated=True, risks=(0.01, 0.05, 0.1), coverages=(0.5, 0.8, 0.9, 1.0), curve=True):
+        """Whether this fit's confidence ranks its own errors on ``X`` (``y``: the labels; None: the dataset's): if it may decline
+        to answer below a confidence threshold, how wrong is it on what it does answer.  One forward pass, ``ops.selective_rows``
+        and ``ops.selective_counts`` on the device log-probs and one download of 32 bytes a row; ``metrics.selective_report``'s
+        dict -- rows, errors, accuracy, excluded_labels, excluded_nan, risk_sum, aurc (the area under the risk-coverage curve,
+        Geifman & El-Yaniv), aurc_oracle, e_aurc, coverage_at_risk (per level of ``risks``, up to 8), risk_at_coverage (per level
+        of ``coverages``, up to 8), curve (the distinct thresholds in descending order with accepted, wrong, coverage, risk; None
+        with ``curve=False``) -- plus ``score``, ``classes`` and ``temperature``.  ``score``: the confidence, "max_prob" (the
+        top-class probability), "margin" (the gap to the runner-up) or "neg_entropy".  The probabilities are softmax(z / T) with
+        ``temperature_`` for a calibrated fit unless ``calibrated=False``; a temperature changes the order of the confidences
+        ACROSS rows, so it changes the curve.  The levels are empirical: they carry no guarantee (``fit_rejection`` gives one).
+        Raises ValueError when a label lies outside the classes."""
+        self._require_initialized()
+        if score not in SELECTIVE_SCORES:
+            raise ValueError(f"risk_coverage: score={score!r}, expected one of {SELECTIVE_SCORES}")
+        risks, coverages = ops._selective_levels("risk_coverage", "risks", risks), ops._selective_levels("risk_coverage", "coverages", coverages)
+        ds = self._as_dataset(X)
+        _, on_device = self._labels("risk_coverage", ds, y, check=True)
+        got, use, _ = self._selective_pass("risk_coverage", ds, on_device, score, calibrated, risks, coverages)
+        res = metrics.selective_report(got["kappa"], got["rows"], got["counts"], got["table"], risks, coverages, curve=bool(curve))
+        res.update(score=score, classes=self.classes_, temperature=float(self.temperature_) if use else 1.0)
+        return res
+
+    def _set_rejection(self, info, device=None):
+        """``rejection_`` and the device state ``predict_selective`` reads its threshold from (float64 [4]: tau, n, accepted,
+        excluded); None removes them.  ``device``: where the state goes (default: where the fit's weights are)."""
+        if info is None:
+            for k in ("rejection_", "_rej_state"):
+                self.__dict__.pop(k, None)
+            return
+        if device is None:
+            device = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
+        self._rej_state = torch.tensor([float(info["threshold"]), float(info["n"]), float(info["accepted"]), float(info["excluded"])],
+                                       dtype=torch.float64).to(device)
+        self.rejection_ = dict(info)
+
+    def fit_rejection(self, X, y=None, target_risk=0.05, delta=0.05, score="max_prob", calibrated=True):
+        """Turn a target error rate into a rejection threshold on ``X`` (``y``: the labels; None: the dataset's) -- rows the fit
+        NEVER SAW, neither in training nor for early stopping, the temperature or a conformal threshold, and drawn like the rows
+        ``predict_selective`` will meet: only then does the guarantee hold.  One forward pass, the risk-coverage curve on the
+        device (``risk_coverage``'s), then ``metrics.guaranteed_threshold``: with ``delta`` the SGR search of Geifman and El-Yaniv
+        (2017), after which the selective risk on new rows exceeds ``target_risk`` with probability at most ``delta`` over the
+        draw of ``X``; ``delta=None``: the ``empirical`` rule, the largest coverage whose empirical risk is at most the target,
+        which carries no guarantee.  Sets ``rejection_`` = {score, rule, target_risk, delta, threshold, bound, accepted, wrong,
+        coverage, risk, n, excluded, calibrated}; the threshold is one of the device's own confidences bit for bit and goes
+        back into a device state that ``predict_selective`` reads.  Returns self.
+
+        The search probes about log2(n) thresholds and the bound is not monotone in the number of accepted rows, so at small n
+        it can miss a threshold that exists: on the population of tests/test_selective_cpu.py (confidence uniform, P[wrong] =
+        (1 - confidence)^2), target 0.05, delta 0.05, 137 of 400 draws of n = 1000 rows found nothing (about a third: 146 of 400
+        under another seed) and none of 400 draws of n = 4000.
+        When nothing qualifies the threshold is +inf and nothing is accepted: kept and reported, with a RuntimeWarning."""
+        self._require_initialized()
+        if score not in SELECTIVE_SCORES:
+            raise ValueError(f"fit_rejection: score={score!r}, expected one of {SELECTIVE_SCORES}")
+        ds = self._as_dataset(X)
+        _, on_device = self._labels("fit_rejection", ds, y, check=True)
+        empty = {"threshold": [], "accepted": [], "wrong": [], "coverage": [], "risk": []}
+        metrics.guaranteed_threshold(empty, target_risk, delta)                  # the options' own checks, before the forward passes
+        got, use, device = self._selective_pass("fit_rejection", ds, on_device, score, calibrated)
+        rep = metrics.selective_report(got["kappa"], got["rows"], got["counts"], got["table"])
+        pick = metrics.guaranteed_threshold(rep["curve"], target_risk, delta)
+        info = {"score": score, "rule": "empirical" if delta is None else "sgr", "target_risk": float(target_risk),
+                "delta": None if delta is None else float(delta), "threshold": float("inf"), "bound": None, "accepted": 0, "wrong": 0,
+                "coverage": 0.0, "risk": float("nan"), "n": rep["rows"], "excluded": rep["excluded_labels"] + rep["excluded_nan"],
+                "calibrated": bool(use)}
+        if pick is None:
+            warnings.warn(f"fit_rejection: no threshold on these {rep['rows']} rows holds the selective risk at {float(target_risk):g}"
+                          + ("" if delta is None else f" with confidence {1.0 - float(delta):g}")
+                          + ": the threshold is infinite and nothing is accepted; more rows, a larger target or a larger delta may find one",
+                          RuntimeWarning, stacklevel=2)
+        else:
+            info.update({k: pick[k] for k in ("threshold", "bound", "accepted", "wrong", "coverage", "risk")})
+        self._set_rejection(info, device)
+        return self
+
+    def predict_selective(self, X):
+        """Predict with the reject option at ``rejection_``'s threshold: ``{"labels": from classes_ [N], "accepted": bool [N],
+        "confidence": float64 [N]}`` -- a row is accepted when its confidence (``rejection_["score"]``, at the temperature the
+        threshold was taken at) is at least the threshold, compared on the device against the device state; a row that holds a
+        NaN has a NaN confidence and is rejected.  ``labels`` are ``predict``'s whether accepted or not.  One forward pass, one
+        download of 24 bytes a row."""
+        self._require_initialized()
+        if getattr(self, "rejection_", None) is None:
+            raise RuntimeError("predict_selective: this estimator has no rejection threshold yet: call fit_rejection(X, y) first")
+        r = self.rejection_
+        use = self._uses_temperature(r["calibrated"])
+
+        def rows(logp, yd):
+            return ops.selective_rows(logp, None, score=r["score"], state=self._cal_state if use else None, tau=self._rej_state)
+        got = ops.selective_download(self._judge(self._as_dataset(X), rows), counts=False)
+        return {"labels": self.classes_[got["rows"][:, 0]], "accepted": got["rows"][:, 2] != 0, "confidence": got["kappa"]}

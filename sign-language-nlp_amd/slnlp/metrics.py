@@ -27,6 +27,10 @@ formed on the host with the arithmetic sklearn uses, so the numbers are the ones
   ``average_precision_score`` (step-wise; tied positives share a threshold).  They are no means over rows and have no
   bootstrap interval.  ``roc_auc_ovr`` itself stays an sklearn name.
 
+Beside the scorers: ``selective_report`` (the risk-coverage curve, AURC and the level tables from ``slnlp_selective_rows`` /
+``_counts``, csrc/selective.hip), ``binomial_upper`` and ``guaranteed_threshold`` (a rejection threshold for a target error rate)
+serve ``LogProbJudge.risk_coverage`` / ``fit_rejection``; they are no ``scoring`` names.
+
 Log-probs on the CPU are reduced by a numpy expression instead (``reduce_rows``, ``reliability_numpy``, ``ranking_numpy``); a
 scorer name outside the four families goes through sklearn as before.
 
@@ -43,6 +47,7 @@ maximum subtracted).  A ``ScoringWrapper`` of the same name is fed ``predict_pro
 renormalises per row in fp64: the two agree to about float32 rounding of a probability (1e-7), not bit for bit, and a
 sample whose confidence sits within that distance of a bin edge may change bins.
 """
+import math
 import re
 
 import numpy as np
@@ -395,6 +400,143 @@ def conformal_report(table, state=None, min_support=5):
         state = np.asarray(state, dtype=np.float64)
         out.update(qhat=float(state[0]), calibration_rows=int(state[1]), k=int(state[2]))
     return out
+
+
+SEL_TABLE_HEAD, SEL_MAX_LEVELS = 40, 8                        # SLNLP_SEL_TABLE_HEAD, SLNLP_SEL_MAX_LEVELS
+
+
+def aurc_oracle(n, errors):
+    """AURC of the best possible confidence for ``errors`` wrong rows among ``n``: every wrong row behind every right one, no two
+    rows tied -- (1 / n) sum_{k = n - E + 1 .. n} (k - n + E) / k; NaN for n = 0."""
+    n, E = int(n), int(errors)
+    return math.fsum((k - n + E) / k for k in range(n - E + 1, n + 1)) / n if n else float("nan")
+
+
+def selective_report(kappa, rows, counts, table, risks=(), coverages=(), curve=True):
+    """``ops.selective_download``'s pieces (``slnlp_selective_rows`` / ``_counts``, include/slnlp.h) as a dict, over the n included
+    rows: ``rows`` = n, ``errors`` = E, ``accuracy``, ``excluded_labels`` / ``excluded_nan`` (rows left out for a label outside the
+    classes / for a NaN), ``risk_sum``, ``aurc`` (the mean over the rows of the selective risk at the row's own threshold),
+    ``aurc_oracle`` (``aurc_oracle(n, E)``) and ``e_aurc``, their difference; ``coverage_at_risk``: per level of ``risks`` {risk,
+    accepted, wrong, coverage, selective_risk, threshold} -- the largest acceptance whose empirical risk is at most the level,
+    accepted 0 and a NaN threshold when there is none -- and ``risk_at_coverage``: per level of ``coverages`` {coverage, accepted,
+    wrong, achieved_coverage, risk, threshold} -- the smallest acceptance that reaches the level; ``curve`` (None with
+    ``curve=False``): the distinct thresholds in descending order as arrays ``threshold``, ``accepted``, ``wrong``, ``coverage``,
+    ``risk``.  Every threshold is one of ``kappa``'s values bit for bit.  The empirical levels carry no guarantee
+    (``guaranteed_threshold`` gives one)."""
+    kappa, rows, counts = np.asarray(kappa, dtype=np.float64), np.asarray(rows), np.asarray(counts)
+    table = np.asarray(table, dtype=np.float64)
+    if len(risks) > SEL_MAX_LEVELS or len(coverages) > SEL_MAX_LEVELS or table.ndim != 1 or table.size < SEL_TABLE_HEAD:
+        raise ValueError(f"selective_report: at most {SEL_MAX_LEVELS} levels each and a table of at least {SEL_TABLE_HEAD} doubles")
+    n, E = int(table[0]), int(table[1])
+    nan = float("nan")
+    inc = np.flatnonzero(counts[:, 0] > 0)                   # the included rows: a row counts itself
+    ge, first = np.unique(counts[inc, 0], return_index=True)  # ascending acceptance: descending thresholds
+    thr, gw = kappa[inc[first]], counts[inc[first], 1]
+    where = {int(g): i for i, g in enumerate(ge)}
+
+    def level(at):
+        g, w = int(table[at]), int(table[at + 1])
+        return g, w, (float(thr[where[g]]) if g else nan)
+    at_risk, at_cov = [], []
+    for l, r in enumerate(risks):
+        g, w, t = level(8 + 2 * l)
+        at_risk.append({"risk": float(r), "accepted": g, "wrong": w, "coverage": g / n if n else nan, "selective_risk": w / g if g else nan,
+                        "threshold": t})
+    for l, c in enumerate(coverages):
+        g, w, t = level(8 + 2 * SEL_MAX_LEVELS + 2 * l)
+        at_cov.append({"coverage": float(c), "accepted": g, "wrong": w, "achieved_coverage": g / n if n else nan,
+                       "risk": w / g if g else nan, "threshold": t})
+    out = {"rows": n, "errors": E, "accuracy": 1.0 - E / n if n else nan, "excluded_labels": int(table[2]), "excluded_nan": int(table[3]),
+           "risk_sum": float(table[4]), "aurc": float(table[5]), "aurc_oracle": aurc_oracle(n, E), "coverage_at_risk": at_risk,
+           "risk_at_coverage": at_cov, "curve": None}
+    out["e_aurc"] = out["aurc"] - out["aurc_oracle"]
+    if curve:
+        out["curve"] = {"threshold": thr, "accepted": ge.astype(np.int64), "wrong": gw.astype(np.int64),
+                        "coverage": ge / n if n else ge.astype(np.float64), "risk": gw / ge}
+    return out
+
+
+_LOG_FACTORIAL = [0.0]                                        # ln i!, grown on demand with math.lgamma
+
+
+def _log_factorials(k):
+    while len(_LOG_FACTORIAL) <= k:
+        _LOG_FACTORIAL.append(math.lgamma(len(_LOG_FACTORIAL) + 1.0))
+    return np.asarray(_LOG_FACTORIAL[:k + 1])
+
+
+def binomial_upper(e, k, delta):
+    """The Clopper-Pearson upper confidence bound of a binomial proportion: the b with P[Bin(k, b) <= e] = delta -- having seen
+    ``e`` errors in ``k`` trials, the error rate is above b with probability at most ``delta`` -- by bisection on the CDF, which
+    is summed in log space from ``math.lgamma``'s log-factorials.  1.0 for e >= k."""
+    if isinstance(e, (bool, np.bool_)) or isinstance(k, (bool, np.bool_)) or not isinstance(e, (int, np.integer)) or \
+            not isinstance(k, (int, np.integer)) or k < 1 or e < 0:
+        raise ValueError(f"binomial_upper: e={e!r}, k={k!r}, expected integers with k >= 1 and e >= 0")
+    if not isinstance(delta, (int, float, np.integer, np.floating)) or isinstance(delta, (bool, np.bool_)) or not 0.0 < float(delta) < 1.0:
+        raise ValueError(f"binomial_upper: delta={delta!r}, expected a number in (0, 1)")
+    e, k, delta = int(e), int(k), float(delta)
+    if e >= k:
+        return 1.0
+    lf = _log_factorials(k)
+    i = np.arange(e + 1, dtype=np.float64)
+    coef = lf[k] - lf[:e + 1] - lf[k - e:][::-1]              # ln C(k, i), i = 0 .. e
+    log_delta = math.log(delta)
+
+    def log_cdf(b):
+        t = coef + i * math.log(b) + (k - i) * math.log1p(-b)
+        m = float(t.max())
+        return m + math.log(float(np.exp(t - m).sum()))
+    lo, hi = 0.0, 1.0                                         # the CDF falls from 1 at b = 0 to 0 at b = 1
+    while True:
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            return hi
+        if log_cdf(mid) > log_delta:
+            lo = mid
+        else:
+            hi = mid
+
+
+def guaranteed_threshold(curve, target_risk, delta=0.05):
+    """Pick the rejection threshold of a risk-coverage ``curve`` (``selective_report``'s: distinct thresholds in descending
+    order with ``accepted`` and ``wrong``) for a target selective risk.  With ``delta``: the SGR search of Geifman and El-Yaniv
+    (2017) -- a binary search over the m distinct thresholds of at most ``steps = max(1, ceil(log2 m))`` probes, each tested with
+    ``binomial_upper(wrong, accepted, delta / steps)``; a probe whose bound is at most ``target_risk`` is kept and the search moves
+    towards more coverage, another moves it towards less.  On rows drawn like the ones the threshold will be used on, and that the
+    fit never saw, the true selective risk at the returned threshold exceeds ``target_risk`` with probability at most ``delta``.
+    ``delta=None`` selects the ``empirical`` rule instead: the largest coverage whose empirical risk is at most the target; it
+    carries NO guarantee (it overshoots the target about every other time).  Returns {rule, index, threshold, accepted, wrong,
+    coverage, risk, bound (None for the empirical rule), steps}, or None when no probe / no threshold qualifies."""
+    if not isinstance(target_risk, (int, float, np.integer, np.floating)) or isinstance(target_risk, (bool, np.bool_)) or \
+            not 0.0 < float(target_risk) < 1.0:
+        raise ValueError(f"guaranteed_threshold: target_risk={target_risk!r}, expected a number in (0, 1)")
+    if delta is not None and (not isinstance(delta, (int, float, np.integer, np.floating)) or isinstance(delta, (bool, np.bool_))
+                              or not 0.0 < float(delta) < 1.0):
+        raise ValueError(f"guaranteed_threshold: delta={delta!r}, expected a number in (0, 1) or None")
+    accepted, wrong = np.asarray(curve["accepted"]), np.asarray(curve["wrong"])
+    m = int(accepted.size)
+    target = float(target_risk)
+    pick, bound, steps = None, None, 0
+    if delta is None:
+        ok = np.flatnonzero(wrong <= target * accepted)
+        pick = int(ok[-1]) if ok.size else None              # accepted ascends along the curve
+    elif m:
+        steps = max(1, int(math.ceil(math.log2(m))))
+        lo, hi = 0, m - 1
+        for _ in range(steps):
+            if lo > hi:
+                break
+            mid = (lo + hi) // 2
+            b = binomial_upper(int(wrong[mid]), int(accepted[mid]), float(delta) / steps)
+            if b <= target:
+                pick, bound, lo = mid, b, mid + 1
+            else:
+                hi = mid - 1
+    if pick is None:
+        return None
+    return {"rule": "empirical" if delta is None else "sgr", "index": pick, "threshold": float(curve["threshold"][pick]),
+            "accepted": int(accepted[pick]), "wrong": int(wrong[pick]), "coverage": float(curve["coverage"][pick]),
+            "risk": float(curve["risk"][pick]), "bound": bound, "steps": steps}
 
 
 def ranking_numpy(scores, y):

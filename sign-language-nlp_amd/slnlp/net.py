@@ -36,7 +36,8 @@ semantics:
 Beyond skorch: ``reliability`` (ECE / MCE / Brier, csrc/reliability.hip), ``predict_topk`` and ``error_analysis`` (top-k classes,
 confusion matrix, most-confused pairs, per-class report: csrc/confusion.hip) and ``ranking`` (one-vs-rest ROC AUC and average
 precision per class, csrc/ranking.hip) reduce a fitted estimator's log-probs on the device; ``conformalize`` / ``predict_set`` /
-``coverage`` (csrc/conformal.hip) say something about a single sample.
+``coverage`` (csrc/conformal.hip) say something about a single sample; ``risk_coverage`` / ``fit_rejection`` /
+``predict_selective`` (csrc/selective.hip) let the fit decline to answer below a confidence threshold.
 
 The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
@@ -810,6 +811,7 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         self._set_calibration(None)
         self._conf_opts = conf_opts
         self._set_conformal(None)
+        self._set_rejection(None)
         self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
         # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
         self._crit_opts = criterion_options(self.criterion_) if hasattr(mod_cls, "engine") else None
@@ -874,6 +876,7 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
             self._set_calibration(None)                      # an earlier fit's temperature does not describe the weights to come
         if getattr(self, "_conf_opts", None) is not None:
             self._set_conformal(None)                        # nor does its threshold
+        self._set_rejection(None)                            # nor a rejection threshold taken with fit_rejection
         with torch.cuda.stream(self._stream):
             run = _FitRun(self, self._as_dataset(X, y))
             for _ in range(int(self.max_epochs)):
@@ -1180,7 +1183,8 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
 
     def save_params(self, dirname):
         """skorch ``Checkpoint`` artefacts: params.pt (state_dict), optimizer.pt (a torch.optim state_dict in either
-        mode), criterion.pt, history.json; calibration.json and conformal.json when the fit has a temperature / a conformal threshold."""
+        mode), criterion.pt, history.json; calibration.json, conformal.json and rejection.json when the fit has a temperature / a conformal threshold /
+        a rejection threshold."""
         os.makedirs(dirname, exist_ok=True)
         torch.save({k: v.detach().cpu() for k, v in self.module_.state_dict().items()}, os.path.join(dirname, "params.pt"))
         torch.save(self._sgd_state_dict() if self._fused else self.optimizer_.state_dict(), os.path.join(dirname, "optimizer.pt"))
@@ -1194,6 +1198,9 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         if getattr(self, "conformal_", None) is not None:
             with open(os.path.join(dirname, "conformal.json"), "w") as f:
                 json.dump(self.conformal_, f, indent=1)      # (an infinite qhat is written as Infinity, which json.load reads back)
+        if getattr(self, "rejection_", None) is not None:
+            with open(os.path.join(dirname, "rejection.json"), "w") as f:
+                json.dump(self.rejection_, f, indent=1)      # (repr round-trips the threshold bit for bit; Infinity and NaN as above)
         if getattr(self, "_avg_opts", None) is not None:  # the running average and how many models it holds: a resumed fit goes on
             torch.save({"state_dict": {k: v.detach().cpu() for k, v in self.averaged_state_dict().items()}, "n_averaged": self.n_averaged_},
                        os.path.join(dirname, "averaged.pt"))
@@ -1231,6 +1238,10 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
             with open(conf_file) as f:
                 info = json.load(f)
             self._set_conformal(conformal_options({k: info[k] for k in CONFORMAL_DEFAULTS}), info=info)     # qhat goes back to the device
+        rej_file = os.path.join(dirname, "rejection.json")
+        if os.path.exists(rej_file):
+            with open(rej_file) as f:
+                self._set_rejection(json.load(f))            # the threshold goes back to the device
         hist = os.path.join(dirname, "history.json")
         if os.path.exists(hist):
             with open(hist) as f:

@@ -817,6 +817,105 @@ def conformal_download(buf, rows=False, sets=False, score=False):
     return out
 
 
+def selective_buffers(N, device):
+    """Every device buffer of one selective-prediction pass over N rows, as slices of ONE float64 allocation:
+
+        table float64 [40 + ceil(N / 2048)] | kappa float64 [N] | rows int32 [N, 4] | counts int32 [N, 2]
+
+    (one pad entry in front of rows where that keeps them 16-byte aligned): 32 bytes a row, which ``selective_download`` brings
+    over in one copy."""
+    N = _int_in("selective_buffers", "N", N, 1, _lib.SEL_MAX_ROWS)
+    head = _lib.SEL_TABLE_HEAD + (N + _lib.SEL_CHUNK - 1) // _lib.SEL_CHUNK
+    at_rows = head + N + ((head + N) & 1)
+    at_counts = at_rows + 2 * N
+    flat = torch.empty(at_counts + N, dtype=torch.float64, device=device)
+    return {"flat": flat, "shape": (N,), "at": (head, at_rows, at_counts), "table": flat[:head], "kappa": flat[head:head + N],
+            "rows": flat[at_rows:at_counts].view(torch.int32).view(N, 4), "counts": flat[at_counts:].view(torch.int32).view(N, 2),
+            "levels": None}
+
+
+def _selective_buf(what, buf, device, N):
+    if not (isinstance(buf, dict) and buf.get("shape") == (N,) and buf["flat"].device == device):
+        raise ValueError(f"{what}: buf must be selective_buffers({N}, {device!r})")
+
+
+def _selective_levels(what, name, values):
+    try:
+        v = [float(x) for x in values]
+    except (TypeError, ValueError):
+        v = None
+    if v is None or len(v) > _lib.SEL_MAX_LEVELS or not all(0.0 <= x <= 1.0 for x in v):
+        raise ValueError(f"{what}: {name}={values!r}, expected at most {_lib.SEL_MAX_LEVELS} numbers in [0, 1]")
+    return v
+
+
+def selective_rows(logp, y=None, buf=None, *, score="max_prob", state=None, tau=None):
+    """Per row of ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) the arg-max, whether it is wrong, the confidence
+    and whether a threshold accepts the row (``slnlp_selective_rows``, include/slnlp.h), into ``buf`` (``selective_buffers``;
+    default a new one, which is returned): ``buf["kappa"]`` float64 [N], ``buf["rows"]`` int32 [N, 4] = (pred, wrong, accepted,
+    code).  ``y`` int64 [N] or None: without labels no row is wrong.  ``score``: "max_prob" (the top-class probability, ``topk_rows``'
+    bits), "margin" (p(1) - p(2)) or "neg_entropy" (sum p ln p).  ``state``: a calibration state whose beta is read on the device
+    (None: beta = 1).  ``tau``: a float64 [4] device tensor whose first entry is the threshold, read on the device; None: nothing
+    is accepted.  Runs on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    what = "selective_rows"
+    N, V, ld = _logp_matrix(what, logp)
+    if N > _lib.SEL_MAX_ROWS:
+        raise ValueError(f"{what}: {N} rows, the counts are formed for at most {_lib.SEL_MAX_ROWS}")
+    if y is not None:
+        _labels(what, y, logp.device, N, " or None")
+    if score not in _lib.SEL_SCORES:
+        raise ValueError(f"{what}: score={score!r}, expected one of {tuple(_lib.SEL_SCORES)}")
+    if state is not None:
+        _cal_state(what, state, logp.device)
+    if tau is not None:
+        _conformal_state(what, "tau", tau, logp.device)
+    with torch.cuda.device(logp.device):
+        if buf is None:
+            buf = selective_buffers(N, logp.device)
+        _selective_buf(what, buf, logp.device, N)
+        check(load().slnlp_selective_rows(ptr(logp), ld, ptr(y) if y is not None else None, N, V, _lib.SEL_SCORES[score],
+                                          ptr(state) if state is not None else None, ptr(tau) if tau is not None else None,
+                                          ptr(buf["kappa"]), ptr(buf["rows"]), stream_ptr()), what)
+    return buf
+
+
+def selective_counts(buf, risks=(), coverages=()):
+    """Per included row of ``buf`` (``selective_rows``' kappa and rows, or ones copied in) how many rows, and how many wrong rows,
+    are at least as confident -- ``buf["counts"]`` int32 [N, 2] -- and the summary ``buf["table"]``: n, E, the excluded rows, the
+    sum of the selective risks, AURC, coverage at each of ``risks`` and risk at each of ``coverages`` (up to 8 numbers in [0, 1]
+    each; ``slnlp_selective_counts``, include/slnlp.h).  Returns the table.  Three queued launches; no host wait."""
+    _lib.require_gpu()
+    what = "selective_counts"
+    if not (isinstance(buf, dict) and "kappa" in buf and "counts" in buf):
+        raise ValueError(f"{what}: buf must be selective_buffers(N, device)")
+    N, = buf["shape"]
+    risks, coverages = _selective_levels(what, "risks", risks), _selective_levels(what, "coverages", coverages)
+    r, c = (C.c_double * max(1, len(risks)))(*risks), (C.c_double * max(1, len(coverages)))(*coverages)
+    with torch.cuda.device(buf["flat"].device):
+        check(load().slnlp_selective_counts(ptr(buf["kappa"]), ptr(buf["rows"]), N, r, len(risks), c, len(coverages), ptr(buf["counts"]),
+                                            ptr(buf["table"]), stream_ptr()), what)
+    buf["levels"] = (risks, coverages)
+    return buf["table"]
+
+
+def selective_download(buf, counts=True):
+    """What a selective-prediction pass hands to the host in ONE device-to-host copy, 32 bytes a row -- the log-probs stay on the
+    device: {kappa float64 [N], rows int32 [N, 4], counts int32 [N, 2], table float64 [40 + chunks], risks, coverages} (a piece no
+    call has written yet holds whatever the allocation held).  ``counts=False``: kappa and rows alone, 24 bytes a row (what
+    ``selective_rows`` by itself writes)."""
+    import numpy as np
+    N, = buf["shape"]
+    head, at_rows, at_counts = buf["at"]
+    if not counts:
+        h = buf["flat"][head:at_counts].cpu().numpy()
+        return {"kappa": h[:N], "rows": h[at_rows - head:].view(np.int32).reshape(N, 4)}
+    h = buf["flat"].cpu().numpy()
+    risks, coverages = buf["levels"] if buf["levels"] is not None else ([], [])
+    return {"table": h[:head], "kappa": h[head:head + N], "rows": h[at_rows:at_counts].view(np.int32).reshape(N, 4),
+            "counts": h[at_counts:].view(np.int32).reshape(N, 2), "risks": list(risks), "coverages": list(coverages)}
+
+
 def error_analysis_buffers(N, V, k, M, device):
     """Every device buffer of one error analysis of an [N, V] set of log-probs -- ``k`` top classes per row (0: none), ``M``
     most-confused pairs -- as slices of ONE int32 allocation, laid out so that whatever is asked for afterwards is one contiguous

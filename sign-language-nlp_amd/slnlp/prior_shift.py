@@ -8,7 +8,8 @@ Saerens, Latinne and Decaestecker (2002) (``ops.fit_priors``: the maximum-likeli
 method to beat, Alexandari et al. 2020, so the base's fitted temperature is folded in) and re-weights the base's device log-probs
 in place (``ops.shift_logp``) before they reach whatever judges them: the wrapper is a ``slnlp.judge.LogProbJudge``, so
 ``predict_proba``, ``predict``, ``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare``,
-``conformalize``, ``predict_set`` and ``coverage`` all see the adapted predictions.  No torch arithmetic runs on the device.
+``conformalize``, ``predict_set``, ``coverage``, ``risk_coverage``, ``fit_rejection`` and ``predict_selective`` all see the adapted
+predictions.  No torch arithmetic runs on the device.
 
 "Unlabelled" is honest for the two RNN models only: the reference Transformer feeds the gold label to its decoder (SURVEY.md
 section 3.4 quirk 1, reproduced for parity), so its log-probs of a row already depend on that row's label.  The adaptation works on
@@ -128,6 +129,7 @@ class PriorShift(LogProbJudge, ClassifierMixin, BaseEstimator):
             self.log_ratio_ = info["log_ratio"] if info is not None else np.log(priors) - np.log(self.source_priors_)
         self.__dict__.pop("conformal_", None)                # a threshold taken under other priors does not carry over
         self.__dict__.pop("_conf_state", None)
+        self._set_rejection(None)                            # nor does a rejection threshold
         return self
 
     # --------------------------------------------------------------- fitting
