@@ -331,6 +331,14 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     v += dpp_mov_d<DPP_MIRROR>(v);
     return (lane_bcast_d(v, 0) + lane_bcast_d(v, 16)) + (lane_bcast_d(v, 32) + lane_bcast_d(v, 48));
 }
+// all 64 lanes active, no NaN among the values (fmax would drop it); every lane gets the result
+__device__ __forceinline__ double wave_max_d(double v) {
+    v = fmax(v, dpp_mov_d<DPP_XOR1>(v));
+    v = fmax(v, dpp_mov_d<DPP_XOR2>(v));
+    v = fmax(v, dpp_mov_d<DPP_HALF_MIRROR>(v));
+    v = fmax(v, dpp_mov_d<DPP_MIRROR>(v));
+    return fmax(fmax(lane_bcast_d(v, 0), lane_bcast_d(v, 16)), fmax(lane_bcast_d(v, 32), lane_bcast_d(v, 48)));
+}
 
 // The arg-max of a row of float32 scores (score.hip, reliability.hip): larger value wins, equal values: lower index, a NaN beats
 // all (np.argmax) -- a total order on (value, index), so every lane of a pair computes the same winner.
@@ -346,8 +354,31 @@ __device__ __forceinline__ unsigned rank_key(float x) {
     const unsigned u = __builtin_bit_cast(unsigned, x);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// the float a key was made from (+0.0 for either zero)
+__device__ __forceinline__ float rank_key_inv(unsigned key) {
+    return __builtin_bit_cast(float, (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+// double -> uint64 with the order of the doubles' bits (-0.0 in front of +0.0), and back: the very double that went in.  No NaN
+// comes here.  Whether the zeros are one value is the CALLER's decision: selective.hip counts ties of the values and turns -0.0
+// into +0.0 before it asks; conformal_quantile hands back the decoded bits of the winning score and must not.
+__device__ __forceinline__ unsigned long long order_key_d(double x) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double order_key_d_inv(unsigned long long key) {
+    return __builtin_bit_cast(double, (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key);
+}
 template <int CTRL>
 __device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+// over the whole wave (all 64 lanes active); every lane gets the result
+__device__ __forceinline__ int wave_sum_i(int v) {
+    v += dpp_mov_i<DPP_XOR1>(v);
+    v += dpp_mov_i<DPP_XOR2>(v);
+    v += dpp_mov_i<DPP_HALF_MIRROR>(v);
+    v += dpp_mov_i<DPP_MIRROR>(v);
+    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
+           (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
 template <int CTRL>
 __device__ __forceinline__ void score_best_step(float& bv, int& bi) {
     const float ov = dpp_mov<CTRL>(bv);

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
 #include "launch.hpp"
 #include "logp_row.hpp"
@@ -93,8 +94,7 @@ __device__ __forceinline__ void conformal_rows_body(const float* __restrict__ lo
             const int pos = p0 + q;
             double p = 0.0;                              // the padding: positions V .. M - 1
             if (pos < V) {
-                const unsigned kv = ~(unsigned)(keys[pos] >> 32);                      // rank_key of the value, undone below
-                const float x = __builtin_bit_cast(float, (kv & 0x80000000u) ? (kv & 0x7FFFFFFFu) : ~kv);
+                const float x = rank_key_inv(~(unsigned)(keys[pos] >> 32));
                 p = x == zmax ? 1.0 / s0 : exp(beta * (double)x - a) / s0;
             }
             prob[pos] = p;
@@ -140,12 +140,7 @@ __device__ __forceinline__ void conformal_rows_body(const float* __restrict__ lo
 SLNLP_ZKERNEL(conformal_rows_kernel, 64, conformal_rows_body)
 
 // -------------------------------------------------------------------------------------------------------- quantile ----
-// double -> uint64 with the doubles' order
-__device__ __forceinline__ unsigned long long conformal_score_key(double s) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, s);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
+// (the keys are order_key_d's of the scores as stored, -0.0 apart from +0.0: the answer is decoded from the winning key)
 __device__ __forceinline__ void conformal_quantile_body(const double* __restrict__ score, const int* __restrict__ rows, int N, double alpha,
                                                         double* __restrict__ state) {
     __shared__ int hist[256];
@@ -155,11 +150,7 @@ __device__ __forceinline__ void conformal_quantile_body(const double* __restrict
     int mine = 0;
     for (long i = tid; i < N; i += 256) mine += rows[4 * i + 3] == 0 ? 1 : 0;
     hist[tid] = mine;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) hist[tid] += hist[tid + w];
-        __syncthreads();
-    }
+    block_tree<1>(&hist, tid, TreeSum{});
     const int n = hist[0];
     __syncthreads();                                     // hist is rewritten below
     const double kd = ceil((double)((long)n + 1) * (1.0 - alpha));
@@ -175,7 +166,7 @@ __device__ __forceinline__ void conformal_quantile_body(const double* __restrict
         __syncthreads();
         for (long i = tid; i < N; i += 256) {
             if (rows[4 * i + 3] != 0) continue;
-            const unsigned long long key = conformal_score_key(score[i]);
+            const unsigned long long key = order_key_d(score[i]);
             if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255ull)], 1);
         }
         __syncthreads();
@@ -195,10 +186,7 @@ __device__ __forceinline__ void conformal_quantile_body(const double* __restrict
         k = found_k;
         __syncthreads();                                 // found_* and hist are rewritten by the next pass
     }
-    if (tid == 0) {
-        const unsigned long long bits = (prefix >> 63) ? (prefix & 0x7FFFFFFFFFFFFFFFull) : ~prefix;
-        *(double4*)state = double4{__builtin_bit_cast(double, bits), (double)n, kd, (double)(N - n)};
-    }
+    if (tid == 0) *(double4*)state = double4{order_key_d_inv(prefix), (double)n, kd, (double)(N - n)};
 }
 SLNLP_ZKERNEL(conformal_quantile_kernel, 256, conformal_quantile_body)
 

@@ -55,14 +55,6 @@ __device__ __forceinline__ unsigned long long lane_bcast_u64(unsigned long long 
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
     return ((unsigned long long)hi << 32) | lo;
 }
-// over the whole wave (all 64 lanes active, no NaN among the values); every lane gets the result
-__device__ __forceinline__ double wave_max_d(double v) {
-    v = fmax(v, dpp_mov_d<DPP_XOR1>(v));
-    v = fmax(v, dpp_mov_d<DPP_XOR2>(v));
-    v = fmax(v, dpp_mov_d<DPP_HALF_MIRROR>(v));
-    v = fmax(v, dpp_mov_d<DPP_MIRROR>(v));
-    return fmax(fmax(lane_bcast_d(v, 0), lane_bcast_d(v, 16)), fmax(lane_bcast_d(v, 32), lane_bcast_d(v, 48)));
-}
 
 // what lane k holds of member k for the row in hand; the k loops read it with readlane
 struct EnsLane {

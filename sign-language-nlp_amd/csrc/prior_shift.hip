@@ -39,6 +39,7 @@
 
 #include <algorithm>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
 #include "launch.hpp"
 #include "logp_row.hpp"
@@ -57,14 +58,6 @@ enum { PRIOR_GAIN = 0, PRIOR_D = 1 };
 enum { PRIOR_REASON = 0, PRIOR_ITERATIONS = 1, PRIOR_ROWS = 2, PRIOR_NAN = 3 };
 // the evaluation a launch belongs to: 0 .. max_iter are the iterations, PRIOR_FINAL the one at the result
 constexpr int PRIOR_FINAL = -1;
-
-__device__ __forceinline__ double wave_max_d(double v) {  // all 64 lanes active; every lane gets the result
-    v = fmax(v, dpp_mov_d<DPP_XOR1>(v));
-    v = fmax(v, dpp_mov_d<DPP_XOR2>(v));
-    v = fmax(v, dpp_mov_d<DPP_HALF_MIRROR>(v));
-    v = fmax(v, dpp_mov_d<DPP_MIRROR>(v));
-    return fmax(fmax(lane_bcast_d(v, 0), lane_bcast_d(v, 16)), fmax(lane_bcast_d(v, 32), lane_bcast_d(v, 48)));
-}
 
 // whether iteration `eval` has nothing left to do (iteration 0 initialises the state and the final evaluation always runs:
 // neither reads the flag)
@@ -95,15 +88,6 @@ __device__ __forceinline__ void prior_rows_body(const float* __restrict__ logp, 
 }
 SLNLP_ZKERNEL(prior_rows_kernel, 256, prior_rows_body)
 
-// the sum of 256 partial sums by a fixed binary tree; the result in red[0]
-__device__ __forceinline__ void prior_tree(double* red, int tid) {
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-}
-
 // S_c = sum_i exp(a_ic - lse_i) over the rows that count: block c
 __device__ __forceinline__ void prior_classes_body(const float* __restrict__ logp, long ld, int N, const double* __restrict__ beta_dev,
                                                    const double* __restrict__ lw, const double* __restrict__ state,
@@ -120,7 +104,7 @@ __device__ __forceinline__ void prior_classes_body(const float* __restrict__ log
         if (l == l) s += exp((beta * (double)logp[r * ld + c] + lwc) - l);
     }
     red[tid] = s;
-    prior_tree(red, tid);
+    block_tree<1>(&red, tid, TreeSum{});
     if (tid == 0) S[c] = red[0];
 }
 SLNLP_ZKERNEL(prior_classes_kernel, 256, prior_classes_body)
@@ -139,11 +123,7 @@ __device__ __forceinline__ void prior_update_body(const double* __restrict__ S, 
         int bad = 0;
         for (long r = tid; r < N; r += 256) bad += lse0[r] != lse0[r] ? 1 : 0;
         bad_red[tid] = bad;
-        __syncthreads();
-        for (int w = 128; w >= 1; w >>= 1) {
-            if (tid < w) bad_red[tid] += bad_red[tid + w];
-            __syncthreads();
-        }
+        block_tree<1>(&bad_red, tid, TreeSum{});
         M = (long)N - bad_red[0];
     } else {
         M = q[PRIOR_ROWS];
@@ -162,14 +142,7 @@ __device__ __forceinline__ void prior_update_body(const double* __restrict__ S, 
         lw[c] = M > 0 ? log(fmax(now, PRIOR_FLOOR)) - log_source[c] : 0.0;
     }
     red[tid] = d;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) {
-            const double o = red[tid + w], m = red[tid];
-            red[tid] = o > m || o != o ? o : m;
-        }
-        __syncthreads();
-    }
+    block_tree<1>(&red, tid, [](double m, double o) { return o > m || o != o ? o : m; });   // the larger, or a NaN, wins
     if (tid != 0) return;
     if (eval == 0) {
         for (int k = 0; k < 8; ++k) state[k] = 0.0;
@@ -200,7 +173,7 @@ __device__ __forceinline__ void prior_gain_body(const double* __restrict__ lse, 
         if (l0 == l0) s += lse[r] - l0;
     }
     red[tid] = s;
-    prior_tree(red, tid);
+    block_tree<1>(&red, tid, TreeSum{});
     if (tid != 0) return;
     const int64_t M = ((const int64_t*)(state + 8))[PRIOR_ROWS];
     state[PRIOR_GAIN] = M > 0 ? red[0] / (double)M : 0.0;

@@ -13,17 +13,17 @@
 // ties), AP_c = table[c][3] / P (the step-wise average precision).  tests/ranking_ref.py restates all of it.
 //
 // HOW IT RUNS.  One launch, V blocks of 256 threads, block c takes class c; no global atomics, nothing that depends on the grid.
-//   1. the block scans y in tiles of 256 rows and compacts its positives -- row index and an order-preserving uint32 key of the
-//      value -- into LDS in ascending row order: a ballot per wave and a prefix over the four wave totals give every positive its
-//      ordinal, so which positives form a chunk (RANK_CHUNK of them) does not depend on timing;
-//   2. a bitonic network in LDS sorts the chunk by key (equal keys give equal counts and equal terms: their order is immaterial);
-//   3. the block streams the N values of column c: per valid row two binary searches in the sorted keys (lower bound lb, upper
-//      bound ub) and integer LDS atomics on three histograms: a negative adds 1 at lo[lb] and at up[ub], a positive at pos[ub].
-//      Integer adds commute: the histograms are a function of the arguments alone;
-//   4. strict suffix sums S turn them into the counts of the positive at sorted position p: gt_neg = S_lo[p], eq_neg =
-//      S_up[p] - S_lo[p], ge_pos = S_pos[p]; they go to rows by original row index;
-//   5. the two table sums: a thread adds its 8 sorted positions in ascending order, a fixed binary tree adds the 256 threads,
-//      thread 0 adds the chunks in ascending order.  The third column is an exact integer (2 N^2 < 2^53 is checked).
+// The chunk_* steps are rank_chunk.hpp's, block_tree is block_reduce.hpp's.
+//   1. chunk_ordinal: the block scans y in tiles of 256 rows and compacts its positives -- row index and rank_key of the value, an
+//      order-preserving uint32 -- into LDS in ascending row order, so which positives form a chunk (RANK_CHUNK of them) does not
+//      depend on timing; the valid rows are counted in the same round.  chunk_pad_and_clear: padding, zeroed histograms;
+//   2. chunk_bitonic_sort: the chunk by key (equal keys give equal counts and equal terms: their order is immaterial);
+//   3. the block streams the N values of column c: per valid row chunk_lower_bound (lb) and chunk_upper_bound (ub) and integer
+//      LDS atomics on three histograms: a negative adds 1 at lo[lb] and at up[ub], a positive at pos[ub].  Integer adds commute;
+//   4. chunk_suffix / chunk_step: strict suffix sums S give the counts of the positive at sorted position p: gt_neg = S_lo[p],
+//      eq_neg = S_up[p] - S_lo[p], ge_pos = S_pos[p]; they go to rows by original row index;
+//   5. the two table sums: a thread adds its 8 sorted positions in ascending order, block_tree adds the 256 threads, thread 0
+//      adds the chunks in ascending order.  The third column is an exact integer (2 N^2 < 2^53 is checked).
 // A class with more than RANK_CHUNK positives repeats 1-5 per chunk (the column is streamed once per chunk: correct, not fast; the
 // data set has about 20 positives per class).  NaNs are counted per column and take part in no search.  The column reads are
 // strided (ld x 4 bytes apart); 32 neighbouring classes share each line out of L2.
@@ -32,8 +32,10 @@
 
 #include <algorithm>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
 #include "launch.hpp"
+#include "rank_chunk.hpp"
 #include "spans.hpp"
 
 namespace slnlp {
@@ -52,7 +54,7 @@ __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp
     __shared__ int part[3][256];
     __shared__ double red[2][256];
     __shared__ int wtot[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int c = blockIdx.x;                            // < V
     const float* col = logp + c;
     double sum_u = 0.0, sum_ap = 0.0;                    // thread 0: the table's two sums over the chunks so far
@@ -67,52 +69,24 @@ __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp
             if (r < N) label = y[r];
             const bool valid = label >= 0 && label < V;  // a label outside the columns is never used as an index
             const bool mine = valid && label == c;
-            const unsigned long long bm = __ballot(mine), bv = __ballot(valid);
-            if (lane == 0) { wtot[0][wave] = __popcll(bm); wtot[1][wave] = __popcll(bv); }
-            __syncthreads();
-            int before = 0, all = 0, allv = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int t = wtot[0][w];
-                if (w < wave) before += t;
-                all += t;
-                allv += wtot[1][w];
-            }
-            const int ord = pos_base + before + __popcll(bm & ((1ull << lane) - 1ull));
+            const bool flags[2] = {mine, valid};
+            int all[2];                                  // the tile's positives, its valid rows
+            const int ord = pos_base + chunk_ordinal(flags, wtot, tid, all);
             if (mine && ord >= first && ord - first < RANK_CHUNK) {
                 const float x = col[r * ld];
                 keys[ord - first] = x != x ? RANK_KEY_NAN : rank_key(x);
                 idx[ord - first] = (int)r;
             }
             if (first == 0 && c == 0 && rows && r < N && !valid) *(int4*)(rows + 4 * r) = int4{0, 0, 0, -1};
-            pos_base += all;
-            valid_base += allv;
-            __syncthreads();                             // wtot is rewritten by the next round
+            pos_base += all[0];
+            valid_base += all[1];
         }
         P = pos_base;
         nvalid = valid_base;
         const int n = min(P - first, RANK_CHUNK);        // 0 only when P == 0
-        int m = 1;
-        while (m < n) m <<= 1;                           // <= RANK_CHUNK
-        for (int i = n + tid; i < m; i += 256) { keys[i] = RANK_KEY_PAD; idx[i] = -1; }
-        for (int i = tid; i <= RANK_CHUNK; i += 256) { hist[0][i] = 0; hist[1][i] = 0; hist[2][i] = 0; }
-        __syncthreads();
-        // 2. bitonic sort of keys[0, m) (idx follows)
-        for (int k = 2; k <= m; k <<= 1) {
-            for (int j = k >> 1; j >= 1; j >>= 1) {
-                for (int i = tid; i < m; i += 256) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const unsigned a = keys[i], b = keys[l];
-                        if ((a > b) == ((i & k) == 0)) {
-                            keys[i] = b; keys[l] = a;
-                            const int t = idx[i]; idx[i] = idx[l]; idx[l] = t;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        const int m = chunk_pad_and_clear(keys, idx, hist, n, RANK_KEY_PAD, tid);
+        // 2. the chunk by key
+        chunk_bitonic_sort(keys, idx, m, tid);
         // 3. the column against the sorted keys
         int nans = 0;
         for (long r = tid; r < N; r += 256) {
@@ -121,17 +95,8 @@ __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp
             const float x = col[r * ld];
             if (x != x) { ++nans; continue; }
             const unsigned key = rank_key(x);
-            int lb = 0, hi = n;
-            while (lb < hi) {                            // the first position whose key is >= key
-                const int mid = (lb + hi) >> 1;
-                if (keys[mid] < key) lb = mid + 1; else hi = mid;
-            }
-            int ub = lb;
-            hi = n;
-            while (ub < hi) {                            // the first position whose key is > key
-                const int mid = (ub + hi) >> 1;
-                if (keys[mid] <= key) ub = mid + 1; else hi = mid;
-            }
+            const int lb = chunk_lower_bound(keys, n, key);
+            const int ub = chunk_upper_bound(keys, n, key, lb);
             if (label == c) {
                 atomicAdd(&hist[2][ub], 1);
             } else {
@@ -140,38 +105,13 @@ __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp
             }
         }
         part[0][tid] = nans;
-        __syncthreads();
-        for (int w = 128; w >= 1; w >>= 1) {
-            if (tid < w) part[0][tid] += part[0][tid + w];
-            __syncthreads();
-        }
+        block_tree<1>(part, tid, TreeSum{});
         nan_c = part[0][0];
-        __syncthreads();
-        // 4. strict suffix sums: S[p] = sum of hist over the positions p + 1 .. RANK_CHUNK
-        const int p0 = tid * RANK_PER_THREAD;
-        int tot[3];
-#pragma unroll
-        for (int h = 0; h < 3; ++h) {
-            int s = tid == 255 ? hist[h][RANK_CHUNK] : 0;
-#pragma unroll
-            for (int q = 0; q < RANK_PER_THREAD; ++q) s += hist[h][p0 + q];
-            tot[h] = s;
-            part[h][tid] = s;
-        }
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {              // inclusive suffix scan over the threads' totals
-            int add[3];
-#pragma unroll
-            for (int h = 0; h < 3; ++h) add[h] = tid + d < 256 ? part[h][tid + d] : 0;
-            __syncthreads();
-#pragma unroll
-            for (int h = 0; h < 3; ++h) part[h][tid] += add[h];
-            __syncthreads();
-        }
+        __syncthreads();                                 // part is rewritten below; the histograms are complete
+        // 4. strict suffix sums; the thread's positions from the last to the first, the terms kept to be added in ascending order
         int run[3];
-#pragma unroll
-        for (int h = 0; h < 3; ++h) run[h] = part[h][tid] - tot[h] + (tid == 255 ? hist[h][RANK_CHUNK] : 0);
-        // the thread's positions from the last to the first; the terms are kept to be added in ascending order
+        chunk_suffix(hist, part, tid, run);
+        const int p0 = tid * RANK_PER_THREAD;
         const double Q = (double)(nvalid - P);
         double tu[RANK_PER_THREAD], ta[RANK_PER_THREAD];
 #pragma unroll
@@ -186,19 +126,14 @@ __device__ __forceinline__ void ranking_rows_body(const float* __restrict__ logp
                 }
                 if (rows) *(int4*)(rows + 4 * (long)idx[p]) = nan_c == 0 ? int4{gt, eq, ge, 0} : int4{0, 0, 0, -2};
             }
-#pragma unroll
-            for (int h = 0; h < 3; ++h) run[h] += hist[h][p];
+            chunk_step(run, hist, p);
         }
         // 5. the chunk's two sums
         double su = 0.0, sa = 0.0;
 #pragma unroll
         for (int q = 0; q < RANK_PER_THREAD; ++q) { su += tu[q]; sa += ta[q]; }
         red[0][tid] = su; red[1][tid] = sa;
-        __syncthreads();
-        for (int w = 128; w >= 1; w >>= 1) {
-            if (tid < w) { red[0][tid] += red[0][tid + w]; red[1][tid] += red[1][tid + w]; }
-            __syncthreads();
-        }
+        block_tree<2>(red, tid, TreeSum{});
         if (tid == 0) { sum_u += red[0][0]; sum_ap += red[1][0]; }
         __syncthreads();                                 // the next chunk rewrites everything
         first += RANK_CHUNK;

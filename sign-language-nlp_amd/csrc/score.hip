@@ -32,15 +32,7 @@ namespace slnlp {
 
 constexpr int SCORE_MAX_BLOCKS = 2048;  // x 4 rows: epochs past 8192 rows wrap the stride loop
 
-// (the arg-max order score_beats and its wave reduction wave_best: common.hpp, shared with reliability.hip)
-__device__ __forceinline__ int wave_sum_i(int v) {
-    v += dpp_mov_i<DPP_XOR1>(v);
-    v += dpp_mov_i<DPP_XOR2>(v);
-    v += dpp_mov_i<DPP_HALF_MIRROR>(v);
-    v += dpp_mov_i<DPP_MIRROR>(v);
-    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-           (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
+// (the arg-max order score_beats, its wave reduction wave_best and wave_sum_i: common.hpp)
 
 __device__ __forceinline__ void score_zero_body(int* __restrict__ counts, int n) {
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) counts[i] = 0;

@@ -12,7 +12,9 @@
 // selective_counts: kappa float64 [N] and rows int32 [N, 4] as selective_rows wrote them (or as a caller made them: ties are ties of
 // the fp64 values).  A row is INCLUDED when its code is 0 and its kappa is no NaN.  Three launches on the stream:
 //   init    one block: the level cells of the table take the neutral element of their reduction (0 for a maximum, ~0 for a minimum);
-//   chunks  ceil(N / SEL_CHUNK) blocks of 256 threads, ranking_rows' scheme with a block per chunk of included rows.  Block b
+//   chunks  ceil(N / SEL_CHUNK) blocks of 256 threads, ranking_rows' scheme with a block per chunk of included rows -- written out
+//           here and NOT on rank_chunk.hpp's helpers: on them every output bit was the same, but selective_counts at N = 4000
+//           measured 0.4 % above this body's spread in each of three runs, so this body stays.  Block b
 //     1. scans rows in tiles of 256 and compacts the included rows with ordinal in [b C, (b + 1) C) -- row index and an order-
 //        preserving uint64 key of kappa -- into LDS in ascending row order: a ballot per wave and a prefix over the four wave totals
 //        give every included row its ordinal, so a chunk's membership does not depend on timing; the scan also yields n;
@@ -33,6 +35,7 @@
 
 #include <algorithm>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
 #include "launch.hpp"
 #include "logp_row.hpp"
@@ -56,14 +59,6 @@ struct SelLevels {
 };
 
 // ------------------------------------------------------------------------------------------------------------ rows ----
-__device__ __forceinline__ double sel_wave_max_d(double v) {    // over the whole wave (all 64 lanes active), no NaN comes here
-    v = fmax(v, dpp_mov_d<DPP_XOR1>(v));
-    v = fmax(v, dpp_mov_d<DPP_XOR2>(v));
-    v = fmax(v, dpp_mov_d<DPP_HALF_MIRROR>(v));
-    v = fmax(v, dpp_mov_d<DPP_MIRROR>(v));
-    return fmax(fmax(lane_bcast_d(v, 0), lane_bcast_d(v, 16)), fmax(lane_bcast_d(v, 32), lane_bcast_d(v, 48)));
-}
-
 __device__ __forceinline__ void selective_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
                                                     int score, const double* __restrict__ beta_dev, const double* __restrict__ tau_dev,
                                                     double* __restrict__ kappa, int* __restrict__ rows) {
@@ -93,7 +88,7 @@ __device__ __forceinline__ void selective_rows_body(const float* __restrict__ lo
         if (score == SLNLP_SEL_MAX_PROB) {
             k = 1.0 / s0;
         } else if (score == SLNLP_SEL_MARGIN) {
-            e2 = sel_wave_max_d(e2);
+            e2 = wave_max_d(e2);                         // (e >= 0: no NaN)
             k = h.n_max >= 2.0 ? 0.0 : (1.0 - e2) / s0;
         } else {                                         // sum p ln p = (sum e_c t_c) / s0 - log1p(rest); t = 0 at the maximum
             double et = 0.0;
@@ -116,11 +111,10 @@ __device__ __forceinline__ void selective_rows_body(const float* __restrict__ lo
 SLNLP_ZKERNEL(selective_rows_kernel, 64, selective_rows_body)
 
 // ---------------------------------------------------------------------------------------------------------- counts ----
-// double -> uint64 with the doubles' order; -0.0 and +0.0 share a key.  No NaN comes here.
+// double -> uint64 with the doubles' order; ties are ties of the fp64 values, so -0.0 takes +0.0's key.  No NaN comes here.
 __device__ __forceinline__ unsigned long long sel_key(double k) {
     if (k == 0.0) k = 0.0;
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, k);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    return order_key_d(k);
 }
 __device__ __forceinline__ bool sel_included(int code, double k) { return code == 0 && k == k; }
 
@@ -301,14 +295,7 @@ __device__ __forceinline__ void selective_final_body(const double* __restrict__ 
     }
 #pragma unroll
     for (int h = 0; h < 4; ++h) part[h][tid] = c[h];
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) part[h][tid] += part[h][tid + w];
-        }
-        __syncthreads();
-    }
+    block_tree<4>(part, tid, TreeSum{});
     const int n = part[0][0];
     if (tid == 0) {
         const int chunks = (n + SEL_CHUNK - 1) / SEL_CHUNK;

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""The four kernels that call csrc/logp_row.hpp, timed against another build of the library on ONE box: each feature's existing
-timer (tools/time_reliability.py, time_error_analysis.py, time_conformal.py: their own shapes, samples and HIP events) and, for the
-ensemble, HIP events around ``ops.ensemble_rows`` at 4000 x 202 with K = 5 -- every one in a fresh child process, the two libraries
-alternating, `--rounds` times.
+"""The log-prob judging kernels that share a header of csrc/ (logp_row.hpp, block_reduce.hpp, rank_chunk.hpp), timed against another
+build of the library on ONE box: each feature's existing timer (tools/time_reliability.py, time_error_analysis.py, time_conformal.py,
+time_ranking.py, time_selective.py, time_prior_shift.py, time_calibration.py: their own shapes, samples and HIP events) and, for
+the ensemble, HIP events around ``ops.ensemble_rows`` at 4000 x 202 with K = 5 -- every one in a fresh child process, the two
+libraries alternating, `--rounds` times.
 
-    python tools/ab_logp_row.py --variant parent [--rounds 5] [--out profiles/logp_row_ab.json]
+    python tools/ab_logp_row.py --variant parent [--rounds 5] [--workloads ranking selective ...] [--out profiles/logp_row_ab.json]
         parent = lib/libslnlp_probeparent.so (make VARIANT=parent in a checkout of the old tree)
+        --workloads: a subset of the eight (default: all)
 
 Per figure (median microseconds of one child): every round's value for both builds, the parent's min..max over its rounds, the new
 build's median over its rounds and whether that lies inside the parent's spread -- the only yardstick there is for kernels nobody
@@ -21,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "sign-language-nlp_amd"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
-WORKLOADS = ("reliability", "topk", "conformal", "ensemble")
+WORKLOADS = ("reliability", "topk", "conformal", "ensemble", "ranking", "selective", "prior_shift", "calibration")
 
 
 def child(workload):
@@ -43,6 +45,26 @@ def child(workload):
         res = t.time_kernel_and_routes()
         return {f"conformal_{k}{suffix}": res[part][k]["median_us"] for k in ("rows_scores", "rows_sets")
                 for part, suffix in (("kernel", ""), ("kernel_batched", "_batched"))}
+    if workload == "ranking":
+        import time_ranking as t
+        res = t.time_kernel_and_routes()
+        return {f"ranking_rows_{k}{suffix}": res[part][k]["median_us"] for k in ("table_only", "with_rows")
+                for part, suffix in (("kernel", ""), ("kernel_batched", "_batched"))}
+    if workload == "selective":
+        import time_selective as t
+        out = {}
+        for N in t.SIZES:
+            res = t.time_size(N)
+            for part, suffix in (("kernel", ""), ("kernel_batched", "_batched")):
+                out.update({f"selective_{k}_{N}{suffix}": v["median_us"] for k, v in res[part].items()})
+        return out
+    if workload == "prior_shift":
+        import time_prior_shift as t
+        res = t.measure()
+        return {f"{k}_{t.N}x{t.V}": res[k]["median_us"] for k in ("fit_priors_early_stop", "fit_priors_to_the_cap", "shift_logp")}
+    if workload == "calibration":
+        import time_calibration as t
+        return {f"{k}_{N}x{V}": t.time_shape(N, V)[k]["median_us"] for N, V in t.SHAPES for k in ("fit_temperature",)}
     from slnlp import ops
     from time_error_analysis import make_logp, timed
     zs = [make_logp(4000, 202, 1 + k)[0] for k in range(5)]
@@ -59,6 +81,7 @@ def main():
     ap.add_argument("--variant", default="parent")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--workloads", nargs="+", choices=WORKLOADS, default=list(WORKLOADS))
     ap.add_argument("--child", choices=WORKLOADS)
     a = ap.parse_args()
     if a.child:
@@ -66,7 +89,7 @@ def main():
         return 0
     us = {}
     for r in range(a.rounds):
-        for wl in WORKLOADS:
+        for wl in a.workloads:
             for lib in (a.variant, ""):                      # parent, new, parent, new, ...
                 env = dict(os.environ)
                 env.pop("SLNLP_PROBE_LIB", None)
@@ -86,8 +109,9 @@ def main():
         print(f"{k:44s} parent {s['parent_min']:9.2f} .. {s['parent_max']:9.2f} (median {s['parent_median']:9.2f})   new median {s['new_median']:9.2f}"
               f"   {'within' if s['new_median_within_parent_spread'] else 'below' if s['new_median'] < s['parent_min'] else 'ABOVE'}")
     if a.out:
+        command = f"python tools/ab_logp_row.py --variant {a.variant} --rounds {a.rounds} --workloads {' '.join(a.workloads)}"
         with open(a.out, "w") as f:
-            json.dump({"command": f"python tools/ab_logp_row.py --variant {a.variant} --rounds {a.rounds}", "rounds": a.rounds,
+            json.dump({"command": command, "rounds": a.rounds,
                        "unit": "us: the median of one fresh process's samples, per round", "figures": us}, f, indent=1)
             f.write("\n")
     return 0

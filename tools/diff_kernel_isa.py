@@ -7,7 +7,8 @@
 Per kernel (matched by substring of the mangled name; a name that matches several symbols must be one's exact demangled
 base name, e.g. sgd_kernel does not match sgd_groups_kernel):
   (a) resources: next_free_vgpr / next_free_sgpr / group_segment_fixed_size / private_segment_fixed_size / scratch lines;
-  (b) the instruction stream between the kernel's label and its s_endpgm, `.LBB<n>_<k>` function numbers normalised;
+  (b) the instruction stream between the kernel's label and the function's end (every exit, not only the first s_endpgm),
+      `.LBB<n>_<k>` function numbers normalised;
   (c) the multiset of opcodes.
 Exit status 0: (a) equal for every kernel; 1 otherwise.  A differing stream with equal resources is reported, not an error.
 """
@@ -37,13 +38,14 @@ def parse(path):
         if body is not None:
             if re.match(r"^\.LBB\d+_\d+:$", s):
                 body.append(re.sub(r"\.LBB\d+_", ".LBB_", s))
+            elif s.startswith((".section", ".Lfunc_end")):   # the function's end (its descriptor's section follows the last
+                                                             # instruction): an early-exit s_endpgm does not end the stream
+                out.setdefault(cur, {})["stream"] = body
+                body = None
             elif s.startswith("."):
                 pass                                # directives inside a body (.p2align ...)
             else:
                 body.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", s)))
-                if s.startswith("s_endpgm"):
-                    out.setdefault(cur, {})["stream"] = body
-                    body = None
             continue
         m = re.match(r"^\.amdhsa_kernel\s+(\S+)", s)
         if m:

@@ -13,6 +13,12 @@ scale_logp and score_rows.  Each at beta absent, beta = 1 and beta = 1 / 6 (wher
 and N in {1, 5, 37}, rows padded to a stride of V + 3.  Row i of a matrix is of kind (i + the index of V) mod 6: two columns tied at
 the maximum, all V tied, -inf columns, a NaN, a maximum of +inf, plain -- so that N = 1 meets every special kind once over the five
 V; its label is 0, V - 1, -1, V or a random class by the same rule mod 5.
+
+On the same grid, the kernels that share csrc/block_reduce.hpp and csrc/rank_chunk.hpp: ranking_rows (rows and table) and
+fit_temperature (state) where beta is absent; selective_rows for each of the three scores with and without a threshold,
+selective_counts with two risk and two coverage levels (counts and table), conformal_quantile (state) and fit_priors (table and
+state, 5 iterations) at every beta.  Then ranking_rows and selective_counts alone at N = 2049 and N = 4133 with V = 3
+(make_chunked): more members than one LDS chunk of 2048 holds, ties across the chunk boundaries.
 """
 import json
 import os
@@ -25,6 +31,8 @@ for p in (ROOT, os.path.join(ROOT, "sign-language-nlp_amd")):
     sys.path.insert(0, p)
 
 VS, NS, BETAS = (1, 63, 64, 65, 202), (1, 5, 37), (None, 1.0, 1.0 / 6.0)
+CHUNK_NS = (2049, 4133)                                      # ranking_rows and selective_counts across their chunks of 2048
+LEVELS = ((0.1, 0.3), (0.5, 0.9))                            # selective_counts: risks, coverages
 
 
 def make(torch, N, V, vi, seed):
@@ -50,6 +58,34 @@ def make(torch, N, V, vi, seed):
     pad = torch.full((N, V + 3), 7.0)
     pad[:, :V] = z
     return pad, y
+
+
+def make_chunked(torch, N):
+    """-> (logp float32 [N, 3] with row stride 6, y int64 [N], kappa float64 [N], rows int32 [N, 4]) on the host: inputs whose
+    members fill more than one LDS chunk of 2048.  Every value is one of 17, -0.0 and +0.0 among them, so ties span the chunk
+    boundaries.  N = 2049: every row is a positive of class 0 and an included row (one member beyond the boundary leaves room
+    for no other kind).  Larger N: 5 labels out of range, 20 rows of the other two classes, and NaNs in 4 rows -- a kappa, and
+    column 1 of the matrix (class 1 is undefined; class 0 stays ranked over more than two chunks) -- at random rows, and one row
+    of class 1 and one label out of range right at the first chunk boundary (rows 2047 and 2050)."""
+    g = torch.Generator().manual_seed(77 + N)
+    vals = torch.tensor([-0.0, 0.0] + [-0.125 * k for k in range(1, 16)], dtype=torch.float64)
+    z = torch.full((N, 6), 7.0)
+    z[:, :3] = vals[torch.randint(0, 17, (N, 3), generator=g)].float()
+    kappa = vals[torch.randint(0, 17, (N,), generator=g)].clone()
+    y = torch.zeros(N, dtype=torch.int64)
+    rows = torch.zeros(N, 4, dtype=torch.int32)
+    rows[:, 0] = torch.randint(0, 3, (N,), generator=g).int()
+    rows[:, 1] = (torch.rand(N, generator=g) < 0.3).int()
+    if N > 2049:
+        at = torch.randperm(N, generator=g)[:29]
+        y[at[:5]] = torch.tensor([-1, 3, 4, -7, 1 << 40])
+        rows[at[:5], 3] = -1
+        y[at[5:25]] = 1 + (torch.arange(20) & 1)
+        y[2047], y[2050], rows[2050, 3] = 1, -1, -1          # a row of class 1 and a label out of range at the first chunk boundary
+        nan_at = at[[23, 25, 26, 27]]                        # at[23] is a row of class 1: a positive whose own value is a NaN
+        z[nan_at, 1] = float("nan")
+        kappa[nan_at] = float("nan")
+    return z, y, kappa, rows
 
 
 def crc(*tensors):
@@ -88,8 +124,30 @@ def lines():
                     out["scale_logp"] = crc(ops.scale_logp(z, state))
                 else:
                     out["score_rows"] = crc(*ops.score_rows(z, y))
+                    out["ranking_rows"] = crc(*ops.ranking_rows(z, y))
+                    out["fit_temperature"] = crc(ops.fit_temperature(z, y))
+                tau = torch.tensor([0.4, 0.0, 0.0, 0.0], dtype=torch.float64, device=dev)
+                for score in ("max_prob", "margin", "neg_entropy"):
+                    for name, t in ((score, None), (score + "_tau", tau)):
+                        sel = ops.selective_rows(z, y, score=score, state=state, tau=t)
+                        out["selective_" + name] = crc(sel["kappa"], sel["rows"])
+                sel = ops.selective_rows(z, y, score="max_prob", state=state)
+                out["selective_counts"] = crc(ops.selective_counts(sel, risks=LEVELS[0], coverages=LEVELS[1]), sel["counts"])
+                buf = ops.conformal_rows(z, y, state=state, method="aps", randomized=False)
+                out["conformal_quantile"] = crc(ops.conformal_quantile(buf, 0.1))
+                source = torch.log_softmax(torch.arange(V, dtype=torch.float64, device=dev) / V, dim=0)
+                out["fit_priors"] = crc(ops.fit_priors(z, source, state=state, max_iter=5))
                 torch.cuda.synchronize()
                 yield {"V": V, "N": N, "beta": beta, **out}
+    for N in CHUNK_NS:
+        z, y, kappa, rows = (t.to(dev) for t in make_chunked(torch, N))
+        sel = ops.selective_buffers(N, dev)
+        sel["kappa"].copy_(kappa)
+        sel["rows"].copy_(rows)
+        table = ops.selective_counts(sel, risks=LEVELS[0], coverages=LEVELS[1])
+        out = {"ranking_rows": crc(*ops.ranking_rows(z[:, :3], y)), "selective_counts": crc(table, sel["counts"])}
+        torch.cuda.synchronize()
+        yield {"V": 3, "N": N, "beta": None, **out}
 
 
 def compare(variant, dest):
