@@ -744,6 +744,59 @@ int slnlp_selective_rows(const float* logp, int64_t ld, const int64_t* y, int64_
 int slnlp_selective_counts(const double* kappa, const int32_t* rows, int64_t N, const double* risks, int nr, const double* coverages,
                            int nc, int32_t* counts, double* table, void* stream);
 
+/* --------------------------------------------------------------- label audit --
+ * Confident learning (Northcutt, Jiang and Chuang 2021) on a set of labelled log-probs (LogProbJudge.label_issues; slnlp/metrics.py's
+ * label_audit_report): which rows' labels are probably wrong, what they should probably be, and how noisy the labels are.  It is
+ * meaningful on log-probs of rows the model has NOT been fitted on (slnlp.OutOfFold).  tests/label_audit_ref.py restates everything
+ * below in numpy.
+ *
+ * logp float32 [N, ld], V <= ld columns used (padding is never read); y int64 [N]; beta = beta_dev ? beta_dev[0] : 1.  Everything
+ * but logp is fp64.  zmax, a = beta zmax and s0 are slnlp_topk_rows' / slnlp_reliability_rows' fp64 decomposition, and THE
+ * PROBABILITY of column c of row i is
+ *   p_ic = 1 / s0 for a column at the maximum, exp(beta z_ic - a) / s0 for any other
+ * -- slnlp_topk_rows' prob bit for bit -- wherever it is formed below: the same (row, column) gives the same bits in every pass.
+ *   code   -2: the row holds a NaN or its maximum is not finite (looked at first); -1: the label lies outside [0, V) (never used as
+ *          an index); else 0.  Only rows with code 0 are USABLE: the others enter no sum and no count but nan_rows / bad_labels.
+ *   pred   the arg-max in slnlp_score_rows' order (a NaN first, larger values first, equal values by ascending column)
+ *   s      p_{i, y_i}, the self-confidence             other  p of the first column other than y_i in that order; 0 for V = 1
+ *   m      s - other, the normalised margin            p_pred 1 / s0 (formed for code -1 too)
+ *          s, other and m are NaN for an unusable row, p_pred for code -2
+ *   n_c    the usable rows labelled c                  t_c    (sum of their s) / n_c; NaN for n_c = 0.  Thread t of a block of 256
+ *          adds its rows t, t + 256, ... ascending, a fixed binary tree adds the threads: the order depends on N alone.  With
+ *          n_c = 1 the division by 1.0 is exact and t_c is that row's s, so its own p >= t_c holds with equality
+ *   k      the first column c with p_ic >= t_c in the arg-max's order on z_i (a NaN t_c compares false); -1: none, or not usable
+ *   flags  bit 0: k >= 0 and k != y_i, the label issue; bit 1: pred != y_i; 0 for an unusable row
+ *   joint  int32 [V V + 1]: cell y_i V + k_i counts the usable rows with k_i >= 0, the last entry every other row
+ *          (slnlp_confusion_matrix on (k, y)); pairs int32 [M, 3] = (given, confident, count): slnlp_confusion_pairs of the joint
+ *
+ * buf, in bytes from its start, with e(x) = x rounded up to an even number (every piece is 8-byte aligned):
+ *   head    int64 [8]: usable rows, bad_labels, nan_rows, usable rows with k = -1, issues (bit 0), arg-max disagreements (bit 1), 0, 0
+ *   t       double [V]          s      double [N]           m      double [N]
+ *   n       int32 [e(V)]        joint  int32 [e(V V + 1)]   pairs  int32 [e(3 M)]
+ *   k       int32 [e(N)]        code   int32 [e(N)]         flags  int32 [e(N)]
+ *   pred    int32 [e(N)]        other  double [N]           p_pred double [N]
+ *   work    slnlp_confusion_pairs_workspace_bytes(V, M) bytes
+ * in this order, SLNLP_AUDIT_HEAD_BYTES first; buf_bytes must cover all of it.  What a report needs ends with flags.
+ *
+ * Eight launches on the stream, no host wait: the rows (a wave per row), the classes (a block per class), the confident classes
+ * (a wave per row), slnlp_confusion_matrix's two, slnlp_confusion_pairs' two, one block for the head.  No floating-point atomics:
+ * the result is a function of the arguments alone.
+ *
+ * slnlp_scatter_logp: out[rows[i], c] for i < n, c < V is row i of logp -- with beta_dev, slnlp_scale_logp's value for that row
+ * bit for bit (one row body serves both); with null, the float32 value itself.  rows int64 [n]; an index outside [0, N_out) is
+ * skipped and never used as an address; rows of out that no index names are left alone.  The indices must be distinct (the
+ * caller checks: two equal ones race).  out float32 [N_out, ld_out] must not overlap any input.  One launch, a wave per row.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null logp, y, buf, rows or out; N, n or N_out
+ * outside 1..INT32_MAX; V outside 1..SLNLP_CONFUSION_MAX_V (label_audit: the joint is V x V) or 1..INT32_MAX (scatter_logp); ld or
+ * ld_out < V; M outside 1..SLNLP_PAIRS_MAX; buf_bytes too small; a misaligned pointer (logp, out 4 bytes; y, beta_dev, buf, rows 8);
+ * an output overlapping an input. */
+#define SLNLP_AUDIT_HEAD_BYTES 64
+int slnlp_label_audit(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, const double* beta_dev, int M, void* buf,
+                      int64_t buf_bytes, void* stream);
+int slnlp_scatter_logp(const float* logp, int64_t ld, int64_t n, int64_t V, const double* beta_dev, const int64_t* rows, float* out,
+                       int64_t ld_out, int64_t N_out, void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

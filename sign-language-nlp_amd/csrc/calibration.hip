@@ -41,6 +41,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "scale_row.hpp"
 #include "spans.hpp"
 
 namespace slnlp {
@@ -197,29 +198,14 @@ __device__ __forceinline__ void fit_update_body(const double* __restrict__ terms
 }
 SLNLP_ZKERNEL(fit_update_kernel, 256, fit_update_body)
 
-// (no __restrict__: out may be logp itself)
+// (no __restrict__: out may be logp itself); the row itself is scale_row.hpp's, which scatter_logp (label_audit.hip) shares
 __device__ __forceinline__ void scale_logp_body(const float* logp, long ld, int N, int V, const double* __restrict__ beta_dev, float* out,
                                                 long ld_out) {
     const double beta = beta_dev[0];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     const int nwaves = gridDim.x * 4;
-    for (long r = wave; r < N; r += nwaves) {
-        const float* row = logp + r * ld;
-        float* dst = out + r * ld_out;
-        float zmax = -INFINITY;
-        for (int j = lane; j < V; j += 64) zmax = fmaxf(zmax, row[j]);
-        zmax = wave_max(zmax);
-        const double a = beta * (double)zmax;
-        double rest = 0.0, at_max = 0.0;                 // as in fit_rows: sum e - 1 without the 1 ever entering a sum
-        for (int j = lane; j < V; j += 64) {
-            const float zf = row[j];
-            if (zf == zmax) at_max += 1.0; else rest += exp(beta * (double)zf - a);
-        }
-        // lse - a; it depends on every load of the row: none is outstanding past here
-        const double l = log1p(wave_sum_d(rest) + (wave_sum_d(at_max) - 1.0));
-        for (int j = lane; j < V; j += 64) dst[j] = (float)((beta * (double)row[j] - a) - l);   // re-read, then stored, by its own lane
-    }
+    for (long r = wave; r < N; r += nwaves) scale_logp_row(logp + r * ld, out + r * ld_out, V, lane, beta);
 }
 SLNLP_ZKERNEL(scale_logp_kernel, 256, scale_logp_body)
 

@@ -1,6 +1,7 @@
 """slnlp: the MI355X path of the sign-language gloss classifier.  The submodules are imported on demand (``slnlp.net``,
-``slnlp.ops``, ...); ``slnlp.VotingEnsemble`` and ``slnlp.PriorShift`` are resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
-__all__ = ["VotingEnsemble", "PriorShift"]
+``slnlp.ops``, ...); ``slnlp.VotingEnsemble``, ``slnlp.PriorShift``, ``slnlp.OutOfFold`` and ``slnlp.cross_fit`` are resolved on first
+use, so that ``import slnlp`` stays free of torch and sklearn."""
+__all__ = ["VotingEnsemble", "PriorShift", "OutOfFold", "cross_fit"]
 
 
 def __getattr__(name):
@@ -10,4 +11,7 @@ def __getattr__(name):
     if name == "PriorShift":
         from .prior_shift import PriorShift
         return PriorShift
+    if name in ("OutOfFold", "cross_fit"):
+        from . import out_of_fold
+        return getattr(out_of_fold, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -144,6 +144,8 @@ SIGNATURES = {
     "slnlp_conformal_summary": (i32, [vp, vp, i64, i64, vp, vp]),
     "slnlp_selective_rows": (i32, [vp, i64, vp, i64, i64, i32, vp, vp, vp, vp, vp]),
     "slnlp_selective_counts": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp]),
+    "slnlp_label_audit": (i32, [vp, i64, vp, i64, i64, vp, i32, vp, i64, vp]),
+    "slnlp_scatter_logp": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -296,6 +298,7 @@ SEL_CHUNK = 2048                                # SLNLP_SEL_CHUNK
 SEL_MAX_LEVELS = 8                              # SLNLP_SEL_MAX_LEVELS
 SEL_TABLE_HEAD = 40                             # SLNLP_SEL_TABLE_HEAD
 SEL_MAX_ROWS = 1048576                          # SLNLP_SEL_MAX_ROWS
+AUDIT_HEAD_BYTES = 64                           # SLNLP_AUDIT_HEAD_BYTES
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

@@ -78,7 +78,19 @@ refit's ``risk_coverage`` finds on the test split -- how wrong the fit is on wha
                                    temperature, coverage_at_risk and risk_at_coverage (one entry per level; empirical, no guarantee)
     test_risk_coverage.csv         threshold, accepted, wrong, coverage and risk per distinct confidence threshold, descending
 
-Without the seven keys the workdir holds exactly the files listed above.
+A top-level ``label_audit: {cv: 5, rank_by: normalized_margin, pairs: 20, top: 200}`` (all optional, these defaults; ``rank_by``:
+normalized_margin or self_confidence) makes rank 0 cross-fit the refit's parameters on the TRAIN data (``slnlp.cross_fit``: ``cv``
+further fits, each predicting the fold it did not see) and write what ``label_issues`` finds on those out-of-fold log-probs --
+which train labels are probably wrong, by confident learning:
+
+    train_label_audit.json         rows, bad_labels, nan_rows, unconfident, argmax_disagrees, issues, noise_rate, rank_by, cv,
+                                   temperature, pairs (given, suggested, count: the likely label swaps) and per class support,
+                                   threshold, issues, confident_other and noise
+    train_label_issues.csv         row, given, suggested, self_confidence and margin of the first ``top`` issues, most suspicious first
+
+(For the Transformer, whose decoder reads the gold label, this is a statement about its log-probs, not about the labels.)
+
+Without the eight keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -92,7 +104,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift", "selective")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -381,6 +393,62 @@ def save_selective(est, test_data, opts, workdir):
     return res
 
 
+LABEL_AUDIT_DEFAULTS = {"cv": 5, "rank_by": "normalized_margin", "pairs": 20, "top": 200}
+LABEL_AUDIT_RANKINGS = ("normalized_margin", "self_confidence")                 # slnlp/metrics.py: LABEL_RANKINGS
+LABEL_AUDIT_MAX_CV, LABEL_AUDIT_MAX_PAIRS = 32, 64                              # SLNLP_ENSEMBLE_MAX_MEMBERS, SLNLP_PAIRS_MAX
+
+
+def label_audit_options(setting):
+    """The ``label_audit`` key with its defaults filled in -- {cv 5, rank_by normalized_margin, pairs 20, top 200} -- or None when the
+    key is absent.  Anything but a dict over these four keys ({}: all defaults) with ``cv`` an integer in 2..32, ``rank_by``
+    normalized_margin or self_confidence, ``pairs`` an integer in 1..64 and ``top`` an integer >= 0 raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"label_audit={setting!r}: expected a dict with keys among {tuple(LABEL_AUDIT_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(LABEL_AUDIT_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"label_audit: unknown keys {unknown} (known: {tuple(LABEL_AUDIT_DEFAULTS)})")
+    opts = dict(LABEL_AUDIT_DEFAULTS, **setting)
+    whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    if not whole(opts["cv"], 2, LABEL_AUDIT_MAX_CV):
+        raise ValueError(f"label_audit: cv={opts['cv']!r}, expected an integer in 2..{LABEL_AUDIT_MAX_CV}")
+    if opts["rank_by"] not in LABEL_AUDIT_RANKINGS:
+        raise ValueError(f"label_audit: rank_by={opts['rank_by']!r}, expected one of {LABEL_AUDIT_RANKINGS}")
+    if not whole(opts["pairs"], 1, LABEL_AUDIT_MAX_PAIRS):
+        raise ValueError(f"label_audit: pairs={opts['pairs']!r}, expected an integer in 1..{LABEL_AUDIT_MAX_PAIRS}")
+    if not whole(opts["top"], 0, 2 ** 31 - 1):
+        raise ValueError(f"label_audit: top={opts['top']!r}, expected an integer >= 0")
+    return opts
+
+
+def save_label_audit(gs, factory, train_data, opts, seed, workdir):
+    """``slnlp.cross_fit`` of ``gs.best_params_`` on ``train_data`` (``opts["cv"]`` fits, fold f after ``torch.manual_seed(seed + f)``,
+    ``checkpoint_dir=None``) and its ``label_issues`` as ``train_label_audit.json`` (the scalars, the pairs and the per-class table)
+    and ``train_label_issues.csv`` (row, given, suggested, self_confidence, margin of the first ``opts["top"]`` issues) in
+    ``workdir``; floats are written with ``repr``.  Returns (the ``OutOfFold``, the result)."""
+    from .out_of_fold import cross_fit
+    net = factory().set_params(**gs.best_params_).set_params(checkpoint_dir=None)
+    oof = cross_fit(net, train_data, cv=opts["cv"], seed=seed)
+    res = oof.label_issues(train_data, rank_by=opts["rank_by"], pairs=opts["pairs"])
+    issues, per = res["issues"], res["per_class"]
+    cell = lambda v: None if v != v else float(v)            # NaN: a class without rows
+    out = {k: int(res[k]) for k in ("rows", "bad_labels", "nan_rows", "unconfident", "argmax_disagrees")}
+    out.update(issues=int(len(issues["row"])), noise_rate=cell(res["noise_rate"]), rank_by=res["rank_by"], cv=opts["cv"],
+               temperature=float(res["temperature"]), pairs=[[int(g), int(c), int(n)] for g, c, n in res["pairs"]],
+               per_class=[{"class": int(c), "support": int(per["support"][i]), "threshold": cell(per["threshold"][i]),
+                           "issues": int(per["issues"][i]), "confident_other": int(per["confident_other"][i]), "noise": cell(per["noise"][i])}
+                          for i, c in enumerate(res["classes"])])
+    save_json(out, os.path.join(workdir, "train_label_audit.json"))
+    with open(os.path.join(workdir, "train_label_issues.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["row", "given", "suggested", "self_confidence", "margin"])
+        for i in range(min(opts["top"], len(issues["row"]))):
+            w.writerow([int(issues["row"][i]), int(issues["given"][i]), int(issues["suggested"][i]),
+                        repr(float(issues["self_confidence"][i])), repr(float(issues["margin"][i]))])
+    return oof, res
+
+
 PRIOR_SHIFT_DEFAULTS = {"max_iter": 200, "tol": 1e-6, "source": "train"}
 PRIOR_SHIFT_MAX_ITER = 1024                                                     # SLNLP_PRIOR_MAX_ITER
 PRIOR_SHIFT_SOURCES = ("train", "train_labels")
@@ -582,6 +650,7 @@ def run(args):
     conformal = conformal_options(args.get("conformal"))                         # (the estimator's own check: slnlp/net.py)
     prior_shift = prior_shift_options(args.get("prior_shift"))
     selective = selective_options(args.get("selective"))
+    label_audit = label_audit_options(args.get("label_audit"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -633,6 +702,8 @@ def run(args):
             save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
         if prior_shift is not None:
             save_prior_shift(est, train_data, test_data, prior_shift, workdir)
+        if label_audit is not None:
+            save_label_audit(gs, factory, train_data, label_audit, seed, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

@@ -1,7 +1,7 @@
 """Everything that judges an [N, V] matrix of log-probs, written once: ``LogProbJudge``.
 
-``NeuralNetClassifier`` (one fit) and ``VotingEnsemble`` (several, combined on the device) inherit these methods; a consumer added
-here exists on both.  The mixin is written against one hook and a few attributes of its host class:
+``NeuralNetClassifier`` (one fit), ``VotingEnsemble`` (several, combined on the device), ``PriorShift`` (re-weighted) and
+``OutOfFold`` (each row from the fit that did not see it) inherit these methods; a consumer added here exists on all of them.  The mixin is written against one hook and a few attributes of its host class:
 
 * ``self._forward_logp(ds, then)``: the log-probs [len(ds), V] of ``ds`` on the device, handed on the estimator's stream to
   ``then(logp, y_dev)``; returns what ``then`` returns once that stream has drained;
@@ -557,3 +557,44 @@ class LogProbJudge:
             return ops.selective_rows(logp, None, score=r["score"], state=self._cal_state if use else None, tau=self._rej_state)
         got = ops.selective_download(self._judge(self._as_dataset(X), rows), counts=False)
         return {"labels": self.classes_[got["rows"][:, 0]], "accepted": got["rows"][:, 2] != 0, "confidence": got["kappa"]}
+
+    # ------------------------------------------------------------ label audit
+    def label_issues(self, X, y=None, calibrated=True, rank_by="normalized_margin", pairs=20, per_row=False):
+        """Which labels of ``X`` (``y``: the labels; None: the dataset's) are probably wrong, by confident learning (Northcutt, Jiang
+        and Chuang 2021): a row is CONFIDENTLY class c when its probability of c reaches t_c, the mean self-confidence of the rows
+        labelled c; a row confidently another class than its given one is a label issue, and that class is the suggestion.  One
+        forward pass, ``ops.label_audit_rows`` on the device log-probs and one download; ``metrics.label_audit_report``'s dict --
+        issues {row, given, suggested, self_confidence, margin} most suspicious first under ``rank_by`` ("normalized_margin" |
+        "self_confidence"), joint, calibrated_joint, noise_rate, per_class {support, threshold, issues, confident_other, noise},
+        pairs (given, suggested, count: up to ``pairs`` likely label swaps, 1..64), rows, bad_labels, nan_rows, unconfident,
+        argmax_disagrees -- with ``given``, ``suggested`` and the pairs as ``classes_`` entries, plus ``classes`` and
+        ``temperature``.  ``per_row=True`` adds ``per_row``: k, code, flags, pred int32 [N], s, m, other, p_pred float64 [N].  The
+        probabilities are softmax(z / T) with ``temperature_`` for a calibrated fit unless ``calibrated=False``.
+
+        The audit judges labels only on log-probs of rows the model was NOT fitted on: a fit has memorised its own training
+        rows, so use ``slnlp.cross_fit`` / ``slnlp.OutOfFold`` for a training set.  And it is meaningful for the two RNN models
+        only: the reference Transformer feeds the gold label to its decoder, so its log-probs of a row already depend on that
+        row's label -- for it this is a statement about the log-probs, not about the labels.  Raises ValueError when a label lies
+        outside the classes."""
+        self._require_initialized()
+        if rank_by not in metrics.LABEL_RANKINGS:
+            raise ValueError(f"label_issues: rank_by={rank_by!r}, expected one of {metrics.LABEL_RANKINGS}")
+        M = ops._int_in("label_issues", "pairs", pairs, 1, ops._lib.PAIRS_MAX)
+        if len(self.classes_) > ops._lib.CONFUSION_MAX_V:
+            raise ValueError(f"label_issues: {len(self.classes_)} classes, the confident joint is formed for at most {ops._lib.CONFUSION_MAX_V}")
+        ds = self._as_dataset(X)
+        use = self._uses_temperature(calibrated)
+        labels, on_device = self._labels("label_issues", ds, y)
+
+        def rows(logp, yd):
+            return ops.label_audit_rows(logp, on_device(logp, yd), state=self._cal_state if use else None, pairs=M)
+        got = ops.label_audit_download(self._judge(ds, rows), per_row=bool(per_row))
+        self._refuse_labels("label_issues", got["head"][1], len(ds), len(self.classes_))
+        res = metrics.label_audit_report(got, labels, rank_by=rank_by)
+        res["issues"]["given"] = self.classes_[res["issues"]["given"]]
+        res["issues"]["suggested"] = self.classes_[res["issues"]["suggested"]]
+        res["pairs"] = [(self.classes_[g], self.classes_[c], cnt) for g, c, cnt in res["pairs"]]
+        res.update(classes=self.classes_, temperature=float(self.temperature_) if use else 1.0)
+        if per_row:
+            res["per_row"] = {q: got[q] for q in ("k", "code", "flags", "pred", "s", "m", "other", "p_pred")}
+        return res

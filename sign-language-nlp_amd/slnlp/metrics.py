@@ -456,7 +456,54 @@ def selective_report(kappa, rows, counts, table, risks=(), coverages=(), curve=T
     return out
 
 
-_LOG_FACTORIAL = [0.0]                                        # ln i!, grown on demand with math.lgamma
+LABEL_RANKINGS = ("normalized_margin", "self_confidence")
+
+
+def label_audit_report(rec, y, rank_by="normalized_margin"):
+    """``ops.label_audit_download``'s dict (``slnlp_label_audit``, include/slnlp.h) and the given labels ``y`` int [N] as the
+    confident-learning report (Northcutt, Jiang and Chuang 2021), everything from the exact integer joint and the per-row record in
+    fp64: ``issues``: the rows with a label issue -- confidently another class than the given one -- most suspicious first, as
+    arrays ``row``, ``given``, ``suggested``, ``self_confidence``, ``margin``; ``rank_by`` "normalized_margin" orders them by (m
+    ascending, row ascending), "self_confidence" by (s ascending, row ascending).  ``joint`` int64 [V, V], rows the given and
+    columns the confident class; ``calibrated_joint`` float64 [V, V]: with r_c the joint's row sums, row c scaled to the class's
+    support, joint[c][j] n_c / r_c, or n_c on the diagonal for a class with no confident row (no evidence of noise), all divided by
+    the usable rows, so it sums to 1 and its rows to n_c / n; ``noise_rate`` = 1 - its trace.  ``per_class``: arrays ``support``
+    (n_c), ``threshold`` (t_c, NaN without rows), ``issues`` (issues given c), ``confident_other`` (rows confidently c but
+    labelled otherwise) and ``noise`` (1 - the diagonal's share of row c; NaN without rows).  ``pairs``: the likely label swaps
+    (given, suggested, count), largest count first.  ``rows`` (the usable ones), ``bad_labels``, ``nan_rows``, ``unconfident`` (usable
+    rows without a confident class) and ``argmax_disagrees`` (usable rows whose arg-max is not the given label)."""
+    if rank_by not in LABEL_RANKINGS:
+        raise ValueError(f"label_audit_report: rank_by={rank_by!r}, expected one of {LABEL_RANKINGS}")
+    y = np.asarray(y).astype(np.int64)
+    flags, k = np.asarray(rec["flags"]), np.asarray(rec["k"]).astype(np.int64)
+    s, m = np.asarray(rec["s"], dtype=np.float64), np.asarray(rec["m"], dtype=np.float64)
+    if y.shape != flags.shape:
+        raise ValueError(f"label_audit_report: y has shape {tuple(y.shape)}, the record {tuple(flags.shape)} rows")
+    head = [int(v) for v in rec["head"]]
+    joint = np.asarray(rec["joint"]).astype(np.int64)
+    n = np.asarray(rec["n"]).astype(np.int64)
+    V = n.size
+    rows = np.flatnonzero(flags & 1)
+    rows = rows[np.lexsort((rows, (m if rank_by == "normalized_margin" else s)[rows]))]
+    r = joint.sum(axis=1)
+    total = int(n.sum())
+    scaled = np.zeros((V, V), dtype=np.float64)
+    seen = r > 0
+    scaled[seen] = joint[seen] * (n[seen] / r[seen])[:, None]
+    scaled[~seen, ~seen] = n[~seen]                          # no confident row: the support stays on the diagonal
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = scaled / float(total) if total else np.full((V, V), np.nan)
+        noise = 1.0 - np.diagonal(q) / q.sum(axis=1)
+    off = joint - np.diag(np.diagonal(joint))
+    return {"issues": {"row": rows, "given": y[rows], "suggested": k[rows], "self_confidence": s[rows], "margin": m[rows]},
+            "rank_by": rank_by, "joint": joint, "calibrated_joint": q, "noise_rate": float(1.0 - np.trace(q)) if total else float("nan"),
+            "per_class": {"support": n, "threshold": np.asarray(rec["t"], dtype=np.float64), "issues": off.sum(axis=1),
+                          "confident_other": off.sum(axis=0), "noise": noise},
+            "pairs": [(int(g), int(c), int(cnt)) for g, c, cnt in np.asarray(rec["pairs"]) if cnt > 0],
+            "rows": head[0], "bad_labels": head[1], "nan_rows": head[2], "unconfident": head[3], "argmax_disagrees": head[5]}
+
+
+_LOG_FACTORIAL = [0.0]                                     # ln i!, grown on demand with math.lgamma
 
 
 def _log_factorials(k):

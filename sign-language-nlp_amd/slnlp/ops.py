@@ -1078,6 +1078,99 @@ def error_analysis_rows(logp, y, buf, state=None):
     return buf
 
 
+_AUDIT_PIECES = ("t", "s", "m", "n", "joint", "pairs", "k", "code", "flags", "pred", "other", "p_pred", "work")
+
+
+def label_audit_buffers(N, V, pairs, device):
+    """The device buffer of one label audit of an [N, V] set of log-probs with ``pairs`` likely label swaps, ONE int32 allocation
+    laid out as include/slnlp.h states (every piece 8-byte aligned, int32 pieces padded to an even length):
+
+        head int64 [8] | t float64 [V] | s float64 [N] | m float64 [N] | n [V] | joint [V V + 1] | pairs [M, 3] | k [N] | code [N] |
+        flags [N] | pred [N] | other float64 [N] | p_pred float64 [N] | work
+
+    What a report needs ends with flags, so ``label_audit_download`` copies one contiguous piece either way."""
+    what = "label_audit_buffers"
+    N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
+    M = _int_in(what, "pairs", pairs, 1, _lib.PAIRS_MAX)
+    even = lambda n: n + (n & 1)
+    sizes = {"t": 2 * V, "s": 2 * N, "m": 2 * N, "n": even(V), "joint": even(V * V + 1), "pairs": even(3 * M), "k": even(N),
+             "code": even(N), "flags": even(N), "pred": even(N), "other": 2 * N, "p_pred": 2 * N,
+             "work": load().slnlp_confusion_pairs_workspace_bytes(V, M) // 4}
+    at, off = {}, _lib.AUDIT_HEAD_BYTES // 4                 # in int32 entries
+    for name in _AUDIT_PIECES:
+        at[name] = off
+        off += sizes[name]
+    flat = torch.empty(off, dtype=torch.int32, device=device)
+    return {"flat": flat, "at": at, "end": off, "shape": (N, V, M)}
+
+
+def label_audit_rows(logp, y, buf=None, *, state=None, pairs=20):
+    """One confident-learning audit of ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``) against the labels ``y``
+    int64 [N] on the device (``slnlp_label_audit``, include/slnlp.h): per class the threshold t_c (the mean self-confidence of its
+    rows), per row the class it is confidently predicted as, the confident joint and its ``pairs`` largest off-diagonal cells,
+    into ``buf`` (``label_audit_buffers``; default a new one, which is returned).  ``state``: a calibration state whose beta is read
+    on the device (None: beta = 1).  Eight queued launches on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    what = "label_audit_rows"
+    N, V, ld = _logp_matrix(what, logp)
+    if V > _lib.CONFUSION_MAX_V:
+        raise ValueError(f"{what}: {V} classes, the confident joint is formed for at most {_lib.CONFUSION_MAX_V}")
+    _labels(what, y, logp.device, N)
+    if state is not None:
+        _cal_state(what, state, logp.device)
+    with torch.cuda.device(logp.device):
+        if buf is None:
+            buf = label_audit_buffers(N, V, pairs, logp.device)
+        if not (isinstance(buf, dict) and buf.get("shape", (0, 0, 0))[:2] == (N, V) and buf["flat"].device == logp.device):
+            raise ValueError(f"{what}: buf must be label_audit_buffers({N}, {V}, pairs, {logp.device!r})")
+        check(load().slnlp_label_audit(ptr(logp), ld, ptr(y), N, V, ptr(state) if state is not None else None, buf["shape"][2],
+                                       ptr(buf["flat"]), buf["flat"].numel() * 4, stream_ptr()), what)
+    return buf
+
+
+def label_audit_download(buf, per_row=False):
+    """What a label audit hands to the host in ONE device-to-host copy -- the log-probs stay on the device: {head int64 [8] =
+    (usable rows, bad_labels, nan_rows, unconfident, issues, argmax_disagrees, 0, 0), t float64 [V], n int32 [V], joint int64
+    [V, V], overflow, pairs int32 [M, 3], k / code / flags int32 [N], s / m float64 [N]}: what ``metrics.label_audit_report`` reads.
+    ``per_row=True`` extends the copy by pred int32 [N], other and p_pred float64 [N]."""
+    import numpy as np
+    N, V, M = buf["shape"]
+    at = buf["at"]
+    end = at["work"] if per_row else at["pred"]
+    h = buf["flat"][:end].cpu().numpy()
+    ints = lambda name, n: h[at[name]:at[name] + n]
+    reals = lambda name, n: h[at[name]:at[name] + 2 * n].view(np.float64)
+    out = {"head": h[:_lib.AUDIT_HEAD_BYTES // 4].view(np.int64), "t": reals("t", V), "s": reals("s", N), "m": reals("m", N),
+           "n": ints("n", V), "joint": ints("joint", V * V).reshape(V, V).astype(np.int64), "overflow": int(ints("joint", V * V + 1)[-1]),
+           "pairs": ints("pairs", 3 * M).reshape(M, 3), "k": ints("k", N), "code": ints("code", N), "flags": ints("flags", N)}
+    if per_row:
+        out.update(pred=ints("pred", N), other=reals("other", N), p_pred=reals("p_pred", N))
+    return out
+
+
+def scatter_logp(logp, rows, out, state=None):
+    """``out[rows[i], :] = `` row i of ``logp`` float32 [n, V] (``slnlp_scatter_logp``): with ``state`` (a calibration state whose beta
+    is read on the device) the row ``scale_logp`` would write, bit for bit; with None the float32 values themselves.  ``rows``: a
+    contiguous int64 [n] device tensor of DISTINCT indices (the caller checks: this is how ``OutOfFold`` assembles its folds, which
+    it has validated as a partition); an index outside ``out``'s rows is skipped on the device.  ``out``: a float32 [N_out, V]
+    device tensor that does not overlap ``logp``; rows no index names keep what they held.  Runs on the current stream of
+    ``logp``'s device; no host wait.  Returns ``out``."""
+    _lib.require_gpu()
+    what = "scatter_logp"
+    n, V, ld = _logp_matrix(what, logp)
+    if not (rows.device == logp.device and rows.dtype == torch.int64 and rows.dim() == 1 and rows.numel() == n and rows.is_contiguous()):
+        raise ValueError(f"{what}: rows must be a contiguous int64 [{n}] tensor on {logp.device}")
+    if state is not None:
+        _cal_state(what, state, logp.device)
+    if not (torch.is_tensor(out) and out.device == logp.device and out.dim() == 2 and out.shape[1] == V and out.shape[0] >= 1):
+        raise ValueError(f"{what}: out must be a float32 [N_out, {V}] tensor on {logp.device}")
+    N_out, _, ld_out = _logp_matrix(what + " (out)", out)
+    with torch.cuda.device(logp.device):
+        check(load().slnlp_scatter_logp(ptr(logp), ld, n, V, ptr(state) if state is not None else None, ptr(rows), ptr(out), ld_out, N_out,
+                                        stream_ptr()), what)
+    return out
+
+
 def bootstrap_buffers(B, V, Q, counts, device):
     """The output tensors of ``bootstrap_scores`` for ``B`` replicates over ``V`` classes with ``Q`` value columns -- stats
     float64 [B, 9 + Q] and, with ``counts``, counts int32 [B, 3 V + 1] (else None) -- as slices of ONE allocation, so
