@@ -392,6 +392,46 @@ int slnlp_fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64
 int slnlp_scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, float* out, int64_t ld_out,
                      void* stream);
 
+/* ------------------------------------------- bias-corrected temperature calibration --
+ * A temperature AND a per-class bias fitted on held-out log-probs, applied as softmax(beta z + b) (Alexandari, Kundaje and
+ * Shrikumar 2020: BCTS) -- slnlp_shift_logp with log_w = b and a state's beta.  Unlike a temperature, the bias can move the
+ * arg-max: it removes a per-class offset such as ln(pi_valid / pi_train) of a fit trained under other class priors.
+ * logp, y, the excluded rows and M as for slnlp_fit_temperature; 1 <= V <= SLNLP_BIAS_CAL_MAX_V.  theta = (beta, b_0 .. b_{V-1});
+ * p_i = softmax(beta z_i + b), m_i = sum_c p_ic z_ic, n_c = the share of the M rows labelled c; in fp64 throughout (z is float32):
+ *   F(theta) = mean_i [ logsumexp_c(beta z_ic + b_c) - beta z_iy - b_y ] + (lambda / 2) sum_c b_c^2,  lambda = 1 / (bias_sd^2 M)
+ *   g_beta = mean_i (m_i - z_iy)                        g_b = mean_i p_i - n + lambda b
+ *   H_beta,beta = mean_i (sum_c p_ic z_ic^2 - m_i^2)    H_beta,b = mean_i p_i (z_i - m_i)    H_bb = diag(mean_i p_i + lambda) - P^T P / M
+ * -- the MAP estimate under a N(0, bias_sd^2) prior on every bias (bias_sd finite and > 0), jointly convex in (beta, b).
+ * slnlp_fit_bias_temperature minimises F over beta in [2^-6, 2^6] by a damped Newton iteration:
+ *   1. theta = (1, 0); evaluate F, g there (evaluation 1).  M == 0 or V == 1 -> theta = (1, 0), SLNLP_CAL_FLAT, 0 evaluations.
+ *   2. max |g| <= tol -> SLNLP_CAL_GRADIENT (result theta); 48 evaluations made -> SLNLP_CAL_CAP (result theta).
+ *   3. H = L L^T by Cholesky; a pivot <= 0 (or NaN) -> SLNLP_CAL_PIVOT (result theta: it cannot happen in exact arithmetic, so
+ *      it is reported, not patched).  d = -H^-1 g, t = 1.
+ *   4. halve t while the beta of theta + t d lies outside [2^-6, 2^6] (no evaluation); evaluate F', g' at theta + t d;
+ *      F' <= F + 1e-4 t g^T d -> theta = theta + t d, F = F', g = g', go to 2; else 48 evaluations made -> SLNLP_CAL_CAP (result
+ *      theta); else t = t / 2 and 4 again.  A rejected candidate counts as an evaluation.
+ * state: as slnlp_fit_temperature's -- double [0] beta  [1] T = 1 / beta  [2] the mean log-loss at (1, 0)  [3] the mean log-loss at
+ * the result (both WITHOUT the penalty)  [4..7] the iteration's own; int64 [8] reason  [9] evaluations  [10] M  [11] labels out of
+ * range  [12..15] the iteration's own (13: halvings, 14: Newton directions) -- so slnlp_scale_logp, slnlp_shift_logp and every
+ * beta_dev argument read it unchanged.  bias: double [V] device memory, b at the result (what slnlp_shift_logp takes as log_w).
+ * tol: finite and >= 0, an ABSOLUTE bound on max |g|.  scratch: slnlp_fit_bias_temperature_scratch_bytes(N, V) bytes (-1 and a
+ * message for N outside 1..INT32_MAX or V outside 1..SLNLP_BIAS_CAL_MAX_V), 32-byte aligned: p_i as fp64 [N, V rounded up to 16],
+ * the row terms, the column sums, theta, the candidate, g, d and the (V + 1)^2 system.
+ * The call queues a fixed sequence of 48 x 5 - 2 + 3 = 241 launches on stream and never waits for the host: per evaluation the
+ * rows (a wave per row), the column sums (a block per class: thread t adds rows t, t + 256, ... in increasing order, then a
+ * fixed binary tree), ONE block that forms F and g and takes the accept / halve / stop decision, P^T P over the lower
+ * triangle's 16 x 16 tiles (v_mfma_f64_16x16x4_f64, the rows in increasing order; nothing after a rejected candidate), and ONE
+ * block for the factorisation, the solves and the next candidate; then the evaluation at the result.  Once the reason is set
+ * the launches read it and return at once.  No atomics: the result is a function of the arguments alone.
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer, N outside 1..INT32_MAX, V outside
+ * 1..SLNLP_BIAS_CAL_MAX_V, ld < V, bias_sd or tol out of range, scratch too small or misaligned, a misaligned pointer, state,
+ * bias or scratch overlapping an input or each other. */
+#define SLNLP_BIAS_CAL_MAX_V 512
+#define SLNLP_CAL_PIVOT 6
+int64_t slnlp_fit_bias_temperature_scratch_bytes(int64_t N, int64_t V);
+int slnlp_fit_bias_temperature(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, double bias_sd, double tol,
+                               void* state, double* bias, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* -------------------------------------------------------- label-shift adaptation --
  * A classifier trained under the class priors pi_s and used under pi_t is corrected exactly by p_t(c | x) ~ p_s(c | x)
  * pi_t(c) / pi_s(c).  slnlp_fit_priors estimates pi_t from UNLABELLED rows by the EM of Saerens, Latinne and Decaestecker (2002),

@@ -128,6 +128,8 @@ SIGNATURES = {
     "slnlp_fit_temperature_scratch_bytes": (i64, [i64]),
     "slnlp_fit_temperature": (i32, [vp, i64, vp, i64, i64, vp, vp, i64, vp]),
     "slnlp_scale_logp": (i32, [vp, i64, i64, i64, vp, vp, i64, vp]),
+    "slnlp_fit_bias_temperature_scratch_bytes": (i64, [i64, i64]),
+    "slnlp_fit_bias_temperature": (i32, [vp, i64, vp, i64, i64, C.c_double, C.c_double, vp, vp, vp, i64, vp]),
     "slnlp_fit_priors_scratch_bytes": (i64, [i64, i64]),
     "slnlp_fit_priors": (i32, [vp, i64, i64, i64, vp, vp, i32, C.c_double, vp, vp, vp, i64, vp]),
     "slnlp_shift_logp": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp]),
@@ -283,7 +285,9 @@ def require_gpu():
 REDUCTIONS = {"mean": 0, "sum": 1}             # CrossEntropyLoss reductions the fused criterion implements
 UPDATE_KINDS = {"sgd": 0, "adam": 1, "adamw": 2}  # SLNLP_UPDATE_*
 AVERAGE_KINDS = {"swa": 0, "ema": 1}            # SLNLP_AVG_*
-CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_*
+CALIBRATION_REASONS = {1: "flat", 2: "bound", 3: "gradient", 4: "step", 5: "cap"}   # SLNLP_CAL_* of slnlp_fit_temperature
+BIAS_CALIBRATION_REASONS = {**CALIBRATION_REASONS, 6: "pivot"}   # ... of slnlp_fit_bias_temperature: SLNLP_CAL_PIVOT too
+BIAS_CAL_MAX_V = 512                            # SLNLP_BIAS_CAL_MAX_V
 PRIOR_REASONS = {1: "tol", 2: "cap", 3: "empty"}   # SLNLP_PRIOR_*
 PRIOR_MAX_ITER = 1024                           # SLNLP_PRIOR_MAX_ITER
 REL_MAX_BINS = 64                               # SLNLP_REL_MAX_BINS

@@ -19,7 +19,8 @@ reproduced.  ``dataset_args.synthetic: {n: ..}`` (not in the reference) generate
 the corpus is not on the machine.  ``iterator_train_args: {shuffle: true, drop_last: false}`` (the reference hard-codes its
 iterator arguments, helper.py:73-83, with ``shuffle`` commented out) becomes ``iterator_train__*``; in ``grid_args`` it is a grid
 axis.  Configs without the key behave as before.  A top-level ``calibration: {method: temperature}`` goes to the estimator as it is
-(temperature calibration on the fit's valid split, slnlp/net.py); a list of such settings under ``grid_args`` is a grid axis.
+(temperature calibration on the fit's valid split, slnlp/net.py; ``{method: bias_temperature, bias_sd: 2.0}`` fits a per-class bias
+beside the temperature); a list of such settings under ``grid_args`` is a grid axis.
 A top-level ``error_analysis: {pairs: 20, top_k: 5}`` (both optional, these defaults) makes rank 0 write, next to test_output.json,
 what ``NeuralNetClassifier.error_analysis`` finds on the test split:
 

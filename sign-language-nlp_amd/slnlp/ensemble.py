@@ -25,8 +25,9 @@ class VotingEnsemble(LogProbJudge, ClassifierMixin, BaseEstimator):
     """``members``: 1..32 initialised ``NeuralNetClassifier``s on one device with equal ``classes_``.  ``voting``: "soft", the
     weighted arithmetic mean of the members' probabilities, or "log", their weighted geometric mean renormalised (a product of
     experts).  ``weights``: one finite number > 0 per member (normalised on the way in), None: equal.  ``calibrated``: a member
-    that fitted a temperature enters as softmax(z / T_k); False: every member at T = 1.  The ensemble has no temperature of its
-    own: ``calibration_`` is None, and the methods that report one report 1.0."""
+    that fitted a temperature enters as softmax(z / T_k) -- one with a ``bias_temperature`` calibration as its shifted log-probs,
+    softmax(beta_k z + b_k), at beta = 1 (``LogProbJudge._calibrated_logp``); False: every member at T = 1.  The ensemble has no
+    temperature of its own: ``calibration_`` is None, and the methods that report one report 1.0."""
     calibration_ = None
     temperature_ = 1.0
     predict_nonlinearity = "auto"
@@ -63,23 +64,26 @@ class VotingEnsemble(LogProbJudge, ClassifierMixin, BaseEstimator):
         dev = torch.device(net.device)
         return torch.device("cuda", torch.cuda.current_device()) if dev.type == "cuda" and dev.index is None else dev
 
-    def _states(self):
-        """Per member its device calibration state, or None: beta = 1."""
-        return [m._cal_state if self.calibrated and getattr(m, "calibration_", None) is not None else None for m in self.members]
+    def _member_logp(self, member):
+        """The ``then`` of a member's forward pass: ``(float32 log-probs, y_dev, calibration state or None)`` as the member's own
+        ``_calibrated_logp`` hands them over -- a bias calibration is already in the log-probs, on the member's stream."""
+        def keep(logp, yd):
+            logp = logp if logp.dtype == torch.float32 else logp.float()
+            logp, state = member._calibrated_logp(logp, member._uses_temperature(self.calibrated))
+            return logp, yd, state
+        return keep
 
     def _combine(self, ds, then, diagnostics):
         """Every member's float32 log-probs of ``ds`` -- its own ``_forward_logp``: under its gate, on its stream, returned once
         that stream has drained -- then, on the first member's stream and under its gate, ``ops.ensemble_rows`` and
         ``then(out, y_dev, rows)``; returns what ``then`` returns once that stream has drained."""
-        def keep(logp, yd):
-            return (logp if logp.dtype == torch.float32 else logp.float()), yd
-        got = [m._forward_logp(ds, keep) for m in self.members]
+        got = [m._forward_logp(ds, self._member_logp(m)) for m in self.members]
         first = self.members[0]
         first._gate.enter(not first._fused)
         try:
             first._enter_stream()
             with torch.cuda.stream(first._stream), torch.no_grad():
-                out, rows = ops.ensemble_rows([g[0] for g in got], states=self._states(), weights=self.weights, voting=self.voting,
+                out, rows = ops.ensemble_rows([g[0] for g in got], states=[g[2] for g in got], weights=self.weights, voting=self.voting,
                                               diagnostics=diagnostics)
                 res = then(out, got[0][1], rows)
             stream_sync(first._stream)

@@ -6,7 +6,9 @@
 * ``self._forward_logp(ds, then)``: the log-probs [len(ds), V] of ``ds`` on the device, handed on the estimator's stream to
   ``then(logp, y_dev)``; returns what ``then`` returns once that stream has drained;
 * ``classes_``, ``initialized_``, ``predict_nonlinearity``;
-* ``calibration_`` / ``_cal_state`` / ``temperature_``: a fitted temperature and its device state (absent or None: T = 1);
+* ``calibration_`` / ``_cal_state`` / ``temperature_``: a fitted temperature and its device state (absent or None: T = 1); ``_cal_bias``:
+  the device bias of a ``bias_temperature`` calibration (absent or None: a temperature alone) -- ``_calibrated_logp`` is the one
+  place that decides how a consumer gets calibrated log-probs;
 * ``conformal_`` / ``_conf_state``: the conformal options and the device threshold, set here by ``_set_conformal``;
 * ``rejection_`` / ``_rej_state``: the reject option's threshold and its device state, set here by ``_set_rejection``.
 
@@ -77,6 +79,32 @@ class LogProbJudge:
         """Whether the probabilities are softmax(z / T) with the fit's temperature: it has one and the caller wants it."""
         return bool(calibrated) and getattr(self, "calibration_", None) is not None
 
+    def _calibrated_logp(self, logp, use):
+        """How a consumer gets calibrated log-probs, decided in ONE place: ``(logp, state)`` -- ``state`` is what the consumer passes
+        on to its ``ops`` call.  Not ``use``: ``(logp, None)``, T = 1.  A temperature: ``(logp, _cal_state)`` unchanged, the device
+        reads beta.  A ``bias_temperature`` calibration: the float32 log-probs become ``(beta z + b) - logsumexp(beta z + b)`` IN
+        PLACE (``ops.shift_logp``, on the current stream) and the consumer gets ``state=None``: beta = 1 on what is now calibrated."""
+        if not use:
+            return logp, None
+        bias = getattr(self, "_cal_bias", None)
+        if bias is None:
+            return logp, self._cal_state
+        ops.shift_logp(logp, bias, state=self._cal_state, out=logp)
+        return logp, None
+
+    def _calibrated_values(self, logp, use):
+        """The calibrated float32 log-probs themselves, in place, for a consumer of the values (``predict_proba``, ``ranking``)."""
+        logp, state = self._calibrated_logp(logp, use)
+        if state is not None:
+            ops.scale_logp(logp, state, out=logp)            # beta z - logsumexp(beta z)
+        return logp
+
+    def _report_calibration(self, res, use):
+        """``res["calibration"]`` = the method's name, only for a fit whose calibration is more than a temperature."""
+        if use and getattr(self, "_cal_bias", None) is not None:
+            res["calibration"] = self.calibration_["method"]
+        return res
+
     def _judge(self, ds, then):
         """``_forward_logp`` for the consumers: ``then`` receives float32 log-probs."""
         return self._forward_logp(ds, lambda logp, yd: then(logp if logp.dtype == torch.float32 else logp.float(), yd))
@@ -114,15 +142,16 @@ class LogProbJudge:
         self._require_initialized()
 
         def scaled(out, yd):
-            if getattr(self, "calibration_", None) is not None:
-                ops.scale_logp(out, self._cal_state, out=out)        # softmax(z / T) below: the calibrated log-probs, in place
-            return out
+            return self._calibrated_values(out, self._uses_temperature(True))    # softmax(z / T) below: the calibrated log-probs, in place
         out = self._forward_logp(self._as_dataset(X), scaled).cpu()
         # the nonlinearity on the host copy (torch's CPU softmax -- the op the reference's CPU path runs): torch's GPU kernels
         # are built with packed fp32 and must not run beside other fits' kernels (STREAM_MODE above); [N, V] is tiny
         return (torch.softmax(out, dim=-1) if self.predict_nonlinearity == "auto" else out).numpy()
 
     def predict(self, X):
+        """The arg-max of ``predict_proba``.  Under a temperature it is the uncalibrated arg-max; under a ``bias_temperature``
+        calibration it is the arg-max of the CALIBRATED probabilities -- consistent with ``predict_proba`` and ``predict_topk`` --
+        and can differ from the uncalibrated one: a per-class bias moves it."""
         return self.classes_[self.predict_proba(X).argmax(-1)]
 
     def reliability(self, X, y=None, bins=15, calibrated=True):
@@ -139,11 +168,12 @@ class LogProbJudge:
         _, on_device = self._labels("reliability", ds, y)
 
         def rows(logp, yd):
-            return ops.reliability_rows(logp, on_device(logp, yd), bins=bins, state=self._cal_state if use else None)
+            logp, state = self._calibrated_logp(logp, use)
+            return ops.reliability_rows(logp, on_device(logp, yd), bins=bins, state=state)
         res = ops.reliability_download(self._judge(ds, rows))
         self._refuse_labels("reliability", res["bad_labels"], len(ds), len(self.classes_))
         res["temperature"] = float(self.temperature_) if use else 1.0
-        return res
+        return self._report_calibration(res, use)
 
     def ranking(self, X, y=None, calibrated=True):
         """Ranking metrics of this fit's predictions on ``X`` (``y``: the labels; None: the dataset's): per class the one-vs-rest
@@ -159,14 +189,13 @@ class LogProbJudge:
         _, on_device = self._labels("ranking", ds, y)
 
         def rows(logp, yd):
-            if use:
-                ops.scale_logp(logp, self._cal_state, out=logp)      # in place: the ranks are those of the calibrated log-probs
+            logp = self._calibrated_values(logp, use)            # in place: the ranks are those of the calibrated log-probs
             return ops.ranking_rows(logp, on_device(logp, yd), per_row=False)
         res = ops.ranking_download(self._judge(ds, rows))
         self._refuse_labels("ranking", res["bad_labels"], len(ds), len(self.classes_))
         res["classes"] = self.classes_
         res["temperature"] = float(self.temperature_) if use else 1.0
-        return res
+        return self._report_calibration(res, use)
 
     def predict_topk(self, X, k=5, calibrated=True):
         """The ``k`` most probable classes of every sample of ``X`` and their probabilities: ``(labels [N, k] from classes_, proba
@@ -180,7 +209,8 @@ class LogProbJudge:
         use = self._uses_temperature(calibrated)
 
         def rows(logp, yd):
-            return ops.topk_rows(logp, k, state=self._cal_state if use else None)
+            logp, state = self._calibrated_logp(logp, use)
+            return ops.topk_rows(logp, k, state=state)
         idx, prob = ops.topk_download(self._judge(ds, rows))
         return self.classes_[idx], prob
 
@@ -205,17 +235,19 @@ class LogProbJudge:
         _, on_device = self._labels("error_analysis", ds, y)
 
         def rows(logp, yd):
+            logp, state = self._calibrated_logp(logp, use)
             buf = ops.error_analysis_buffers(logp.shape[0], logp.shape[1], k, M, logp.device)
-            return ops.error_analysis_rows(logp, on_device(logp, yd), buf, state=self._cal_state if use else None)
+            return ops.error_analysis_rows(logp, on_device(logp, yd), buf, state=state)
         got = ops.error_analysis_download(self._judge(ds, rows), matrix=bool(matrix), topk=k > 0)
         counts = got["counts"]
         V = (counts.size - 1) // 3                           # the columns of the log-probs
         self._refuse_labels("error_analysis", counts[3 * V], len(ds), V)
         report, macro = metrics.class_report(counts[:V], counts[V:2 * V], counts[2 * V:3 * V])
-        return {"classes": self.classes_, "confusion": got["confusion"], "report": report, "macro": macro,
-                "accuracy": float(counts[2 * V:3 * V].sum() / len(ds)),
-                "pairs": [(self.classes_[t], self.classes_[p], int(c)) for t, p, c in got["pairs"] if c > 0],
-                "topk": (self.classes_[got["topk_idx"]], got["topk_prob"]) if k else None, "rows": len(ds)}
+        return self._report_calibration(
+            {"classes": self.classes_, "confusion": got["confusion"], "report": report, "macro": macro,
+             "accuracy": float(counts[2 * V:3 * V].sum() / len(ds)),
+             "pairs": [(self.classes_[t], self.classes_[p], int(c)) for t, p, c in got["pairs"] if c > 0],
+             "topk": (self.classes_[got["topk_idx"]], got["topk_prob"]) if k else None, "rows": len(ds)}, use)
 
     def _interval_request(self, what, scoring, replicates, level, seed):
         """The checked arguments of ``score_interval`` / ``compare``: ``(names, top_k, replicates, level, seed)``."""
@@ -255,8 +287,9 @@ class LogProbJudge:
         labels, on_device = self._labels(what, ds, y)
 
         def rows(logp, yd):
+            logp, state = self._calibrated_logp(logp, use)
             buf = ops.score_interval_buffers(logp.shape[0], logp.shape[1], B, logp.device)
-            return ops.score_interval_rows(logp, on_device(logp, yd), buf, top_k=top_k, seed=seed, state=self._cal_state if use else None)
+            return ops.score_interval_rows(logp, on_device(logp, yd), buf, top_k=top_k, seed=seed, state=state)
         got = ops.score_interval_download(self._judge(ds, rows))
         counts = got["counts"]
         V = (counts.size - 1) // 3                           # the columns of the log-probs
@@ -295,7 +328,7 @@ class LogProbJudge:
         out.update(replicates=B, level=level, seed=seed, rows=n)
         if return_replicates:
             out.update(names=names, replicate_scores=reps)
-        return out
+        return self._report_calibration(out, self._uses_temperature(calibrated))
 
     def compare(self, other, X, y=None, scoring=None, replicates=1000, level=0.95, seed=0, calibrated=True, return_replicates=False):
         """The paired bootstrap of this fit against ``other`` on ``X``: both fits are scored as ``score_interval`` does, with ONE
@@ -330,10 +363,10 @@ class LogProbJudge:
         temperature was used)``.  No host wait."""
         use = self._uses_temperature(calibrated)
         logp = logp if logp.dtype == torch.float32 else logp.float()     # (a fit hands its valid split's log-probs over directly)
+        logp, cal = self._calibrated_logp(logp, use)
         buf = ops.conformal_buffers(logp.shape[0], logp.shape[1], logp.device, sets=False)
         ops.conformal_rows(logp, yd.contiguous(), buf, method=opts["method"], lam=opts["lam"], k_reg=opts["k_reg"],
-                           randomized=opts["randomized"], seed=opts["seed"], draw=CONFORMAL_DRAW_CALIBRATE,
-                           state=self._cal_state if use else None)
+                           randomized=opts["randomized"], seed=opts["seed"], draw=CONFORMAL_DRAW_CALIBRATE, state=cal)
         state = torch.empty(4, dtype=torch.float64, device=logp.device)
         return ops.conformal_quantile(buf, opts["alpha"], state=state), use
 
@@ -384,13 +417,13 @@ class LogProbJudge:
         return self
 
     def _conformal_rows(self, what, logp, yd, sets):
-        """``ops.conformal_rows`` at the prediction draw under ``conformal_``'s options and the device threshold."""
+        """``ops.conformal_rows`` at the prediction draw under ``conformal_``'s options and the device threshold (a bias calibration
+        is applied to ``logp`` in place first: what the caller reads of ``logp`` afterwards is calibrated too)."""
         c = self.conformal_
-        use = self._uses_temperature(c["calibrated"])
+        logp, state = self._calibrated_logp(logp, self._uses_temperature(c["calibrated"]))
         buf = ops.conformal_buffers(logp.shape[0], logp.shape[1], logp.device, sets=sets)
         return ops.conformal_rows(logp, yd, buf, method=c["method"], lam=c["lam"], k_reg=c["k_reg"], randomized=c["randomized"],
-                                  seed=c["seed"], draw=CONFORMAL_DRAW_PREDICT, state=self._cal_state if use else None,
-                                  qhat=self._conf_state)
+                                  seed=c["seed"], draw=CONFORMAL_DRAW_PREDICT, state=state, qhat=self._conf_state)
 
     def predict_set(self, X, return_mask=False):
         """The conformal prediction set of every sample of ``X`` under ``conformal_``'s options and threshold (draw 1: a row's u
@@ -459,7 +492,8 @@ class LogProbJudge:
         use = self._uses_temperature(calibrated)
 
         def rows(logp, yd):
-            buf = ops.selective_rows(logp, labels_on_device(logp, yd), score=score, state=self._cal_state if use else None)
+            logp, state = self._calibrated_logp(logp, use)
+            buf = ops.selective_rows(logp, labels_on_device(logp, yd), score=score, state=state)
             ops.selective_counts(buf, risks, coverages)
             return buf
         buf = self._judge(ds, rows)
@@ -486,7 +520,7 @@ class LogProbJudge:
         got, use, _ = self._selective_pass("risk_coverage", ds, on_device, score, calibrated, risks, coverages)
         res = metrics.selective_report(got["kappa"], got["rows"], got["counts"], got["table"], risks, coverages, curve=bool(curve))
         res.update(score=score, classes=self.classes_, temperature=float(self.temperature_) if use else 1.0)
-        return res
+        return self._report_calibration(res, use)
 
     def _set_rejection(self, info, device=None):
         """``rejection_`` and the device state ``predict_selective`` reads its threshold from (float64 [4]: tau, n, accepted,
@@ -554,7 +588,8 @@ class LogProbJudge:
         use = self._uses_temperature(r["calibrated"])
 
         def rows(logp, yd):
-            return ops.selective_rows(logp, None, score=r["score"], state=self._cal_state if use else None, tau=self._rej_state)
+            logp, state = self._calibrated_logp(logp, use)
+            return ops.selective_rows(logp, None, score=r["score"], state=state, tau=self._rej_state)
         got = ops.selective_download(self._judge(self._as_dataset(X), rows), counts=False)
         return {"labels": self.classes_[got["rows"][:, 0]], "accepted": got["rows"][:, 2] != 0, "confidence": got["kappa"]}
 
@@ -587,7 +622,8 @@ class LogProbJudge:
         labels, on_device = self._labels("label_issues", ds, y)
 
         def rows(logp, yd):
-            return ops.label_audit_rows(logp, on_device(logp, yd), state=self._cal_state if use else None, pairs=M)
+            logp, state = self._calibrated_logp(logp, use)
+            return ops.label_audit_rows(logp, on_device(logp, yd), state=state, pairs=M)
         got = ops.label_audit_download(self._judge(ds, rows), per_row=bool(per_row))
         self._refuse_labels("label_issues", got["head"][1], len(ds), len(self.classes_))
         res = metrics.label_audit_report(got, labels, rank_by=rank_by)
@@ -595,6 +631,7 @@ class LogProbJudge:
         res["issues"]["suggested"] = self.classes_[res["issues"]["suggested"]]
         res["pairs"] = [(self.classes_[g], self.classes_[c], cnt) for g, c, cnt in res["pairs"]]
         res.update(classes=self.classes_, temperature=float(self.temperature_) if use else 1.0)
+        self._report_calibration(res, use)
         if per_row:
             res["per_row"] = {q: got[q] for q in ("k", "code", "flags", "pred", "s", "m", "other", "p_pred")}
         return res

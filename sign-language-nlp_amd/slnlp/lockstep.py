@@ -249,9 +249,10 @@ def _eval_pass(nets, data, bs):
 
 def _calibrate_lockstep(nets, runs, stream):
     """``NeuralNetClassifier._calibrate`` for the fits of a group whose ``calibration`` option is on: one lockstep eval pass over
-    their valid splits, one ``fit_temperature`` per fit on the group's stream, then one sync and the downloads.  The fits whose
+    their valid splits, one ``fit_temperature`` / ``fit_bias_temperature`` call per fit on the group's stream (``fit_calibration``),
+    then one sync and the downloads.  The fits whose
     ``conformal`` option is on then take their threshold on the same log-probs, at their temperature (``_conformalize_fit``)."""
-    from .net import stream_sync
+    from .net import download_calibration, fit_calibration, stream_sync
     on = lambda n, key: getattr(n, key, None) is not None
     todo = [(n, r) for n, r in zip(nets, runs) if on(n, "_cal_opts") or on(n, "_conf_opts")]
     if not todo:
@@ -261,11 +262,11 @@ def _calibrate_lockstep(nets, runs, stream):
     if any(r.va is None for _, r in todo):
         raise ValueError("conformal: the fit has no valid split to take the threshold on (train_split)")
     group, logps = _eval_pass([n for n, _ in todo], [(r.Xva, r.Lva, r.yva) for _, r in todo], todo[0][1].bs)
-    states = [ops.fit_temperature(lp, r.yva) if on(n, "_cal_opts") else None for lp, (n, r) in zip(logps, todo)]
+    fitted = [fit_calibration(n._cal_opts, lp, r.yva) if on(n, "_cal_opts") else None for lp, (n, r) in zip(logps, todo)]
     stream_sync(stream)
-    for (n, _), state in zip(todo, states):
-        if state is not None:
-            n._set_calibration(ops.temperature_download(state), state)
+    for (n, _), got in zip(todo, fitted):
+        if got is not None:
+            n._set_calibration(*download_calibration(n._cal_opts, got))
     # the conformal option, as NeuralNetClassifier._conformalize_fit: after the temperature, on the same log-probs
     conf = [(n, r, n._conformal_calibrate(lp, r.yva, n._conf_opts, True)) for lp, (n, r) in zip(logps, todo) if on(n, "_conf_opts")]
     stream_sync(stream)
@@ -432,8 +433,7 @@ def _predict_proba_lockstep_gated(nets, datasets, bs, stream_sync):
         group, logps = _eval_pass(nets, [n._device_data(d) for n, d in zip(nets, datasets)], bs)
         out = [lp.clone() for lp in logps]
         for n, o in zip(nets, out):
-            if getattr(n, "calibration_", None) is not None:
-                ops.scale_logp(o, n._cal_state, out=o)  # a calibrated fit's log-probs become beta z - logsumexp(beta z), in place
+            n._calibrated_values(o, n._uses_temperature(True))   # a calibrated fit's log-probs become the calibrated ones, in place
         stream_sync(nets[0]._stream)
         # softmax on the host copies (torch's CPU op, as in NeuralNetClassifier.predict_proba: no torch arithmetic kernel runs
         # beside other fits on the GPU)

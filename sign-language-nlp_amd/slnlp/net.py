@@ -27,6 +27,8 @@ semantics:
   the model, fed per epoch or per batch, and -- ``predict`` -- what ``predict_proba`` / ``predict`` / ``score`` evaluate with;
 * ``calibration={"method": "temperature"}``: at the end of a fit one temperature is fitted on the valid split's log-probs, on
   the device (csrc/calibration.hip), and ``predict_proba`` returns ``softmax(z / T)``; ``predict`` and the history never change;
+  ``{"method": "bias_temperature", "bias_sd": 2.0}`` fits a shrunk per-class bias beside it (csrc/bias_calibration.hip) and
+  ``predict_proba`` returns ``softmax(beta z + b)``: the history never changes, ``predict`` is the calibrated arg-max and can;
 * ``conformal={"alpha": 0.1, ...}``: at the end of a fit, after the temperature, the threshold of split conformal prediction sets
   (LAC / APS / RAPS, csrc/conformal.hip) is taken on the valid split's log-probs, on the device; ``predict_set`` then returns per
   sample the set of classes that holds the true one with probability about 1 - alpha.  About: the valid split also chose the
@@ -43,6 +45,7 @@ The compute path is HIP only; with no GPU ``fit`` / ``predict`` raise.
 """
 import threading
 import json
+import warnings
 import os
 import time
 import importlib
@@ -311,22 +314,67 @@ def averaging_options(setting):
 
 
 CALIBRATION_KEYS = ("method",)
+BIAS_CALIBRATION_KEYS = ("method", "bias_sd")
+BIAS_SD_DEFAULT = 2.0
 
 
 def calibration_options(setting):
     """The ``calibration`` setting with its defaults filled in -- {method "temperature"} -- or None (off).  Anything else raises
-    ValueError here."""
+    ValueError here.
+
+    ``{"method": "bias_temperature", "bias_sd": 2.0}`` fits a per-class bias beside the temperature, softmax(beta z + b)
+    (``ops.fit_bias_temperature``: bias-corrected temperature scaling, which removes the per-class offset of a fit trained under
+    other class priors than it is judged under).  ``bias_sd``, a key of this method only, is the standard deviation of the
+    Gaussian prior on every bias: a finite number > 0, small values shrink the bias towards a temperature alone.  Its default 2.0
+    is a design choice, not a measurement -- e^2 is a prior ratio of about 7 to 1 within one standard deviation -- and the value
+    is a grid axis a search can rank on ``neg_log_loss``."""
     if setting is None or setting is False:
         return None
     if not isinstance(setting, dict):
         raise ValueError(f"calibration={setting!r}: expected a dict with keys among {CALIBRATION_KEYS} or None")
+    method = setting.get("method", "temperature")
+    if method == "bias_temperature":
+        unknown = sorted(set(setting) - set(BIAS_CALIBRATION_KEYS))
+        if unknown:
+            raise ValueError(f"calibration: unknown keys {unknown} (known for method 'bias_temperature': {BIAS_CALIBRATION_KEYS})")
+        sd = setting.get("bias_sd", BIAS_SD_DEFAULT)
+        if isinstance(sd, (bool, np.bool_)) or not isinstance(sd, (int, float, np.integer, np.floating)) or not 0.0 < float(sd) < float("inf"):
+            raise ValueError(f"calibration: bias_sd={sd!r}, expected a finite number > 0")
+        return {"method": "bias_temperature", "bias_sd": float(sd)}
     unknown = sorted(set(setting) - set(CALIBRATION_KEYS))
     if unknown:
         raise ValueError(f"calibration: unknown keys {unknown} (known: {CALIBRATION_KEYS})")
-    method = setting.get("method", "temperature")
     if method != "temperature":
         raise ValueError(f"calibration: method={method!r}, expected 'temperature'")
     return {"method": "temperature"}
+
+
+def calibration_to_json(info):
+    """``calibration_`` as ``calibration.json`` holds it: the bias of a ``bias_temperature`` fit as a list (repr round-trips a
+    double bit for bit); a temperature fit's dict as it is."""
+    return {k: (np.asarray(v, dtype=np.float64).tolist() if k == "bias" else v) for k, v in info.items()}
+
+
+def calibration_from_json(info):
+    """``calibration_to_json``'s inverse: the bias back as float64 [V]."""
+    return {k: (np.asarray(v, dtype=np.float64) if k == "bias" else v) for k, v in info.items()}
+
+
+def fit_calibration(opts, logp, y):
+    """Queue the fit of the ``calibration`` option ``opts`` on the device log-probs ``logp`` and labels ``y`` (current stream, no
+    host wait): what ``download_calibration`` takes."""
+    if opts["method"] == "bias_temperature":
+        return ops.fit_bias_temperature(logp, y, bias_sd=opts["bias_sd"])
+    return ops.fit_temperature(logp, y)
+
+
+def download_calibration(opts, fitted):
+    """``(info, state, bias)`` of ``fit_calibration``'s result: the host dict (it waits for the fit's launches), the device state
+    and the device bias (None for a temperature)."""
+    if opts["method"] == "bias_temperature":
+        state, bias = fitted
+        return ops.bias_temperature_download(state, bias, opts["bias_sd"]), state, bias
+    return ops.temperature_download(fitted), fitted, None
 
 
 def next_n_averaged(opts, history, n_batches):
@@ -914,8 +962,7 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         if run.va is None:
             raise ValueError("calibration: the fit has no valid split to fit the temperature on (train_split)")
         logp = self._valid_logp(run)
-        state = ops.fit_temperature(logp, run.yva)
-        self._set_calibration(ops.temperature_download(state), state)
+        self._set_calibration(*download_calibration(self._cal_opts, fit_calibration(self._cal_opts, logp, run.yva)))
         return logp
 
     def _valid_logp(self, run):
@@ -930,20 +977,34 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
             if swapped:
                 self.module_.swap_averaged()
 
-    def _set_calibration(self, info, state=None):
-        """``calibration_`` (``ops.temperature_download``'s dict), ``temperature_`` and the device state ``predict_proba`` scales with;
-        None removes them.  A fit that cannot stand raises here: labels outside the classes, the iteration cap."""
+    def _set_calibration(self, info, state=None, bias=None):
+        """``calibration_`` (``ops.temperature_download``'s dict, or ``ops.bias_temperature_download``'s), ``temperature_`` and the
+        device state -- and, for a ``bias_temperature`` fit, the device bias -- ``predict_proba`` calibrates with; None removes
+        them.  A fit that cannot stand raises here: labels outside the classes, the temperature search's iteration cap.  A
+        ``bias_temperature`` fit that ends at its evaluation cap or on a non-positive pivot stands -- every accepted step lowered
+        the objective -- and warns."""
         if info is None:
-            for k in ("calibration_", "temperature_", "_cal_state"):
+            for k in ("calibration_", "temperature_", "_cal_state", "_cal_bias"):
                 self.__dict__.pop(k, None)
             return
         if info["bad_labels"] > 0:
             raise ValueError(f"calibrating on the valid data: {info['bad_labels']} of {info['rows'] + info['bad_labels']} labels lie "
                              "outside the classes of the log-probs")
+        dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
+        if info.get("method") == "bias_temperature":
+            if info["reason"] in ("cap", "pivot"):
+                warnings.warn(f"calibration: the bias_temperature search ended with reason {info['reason']!r} after {info['iterations']} "
+                              f"evaluations (beta {info['beta']!r}): the result is the last accepted point, not a converged one",
+                              RuntimeWarning, stacklevel=3)
+            if state is None:
+                state, bias = ops.bias_temperature_state(info["beta"], info["bias"], dev)
+            self._cal_state, self._cal_bias = state, bias
+            self.calibration_, self.temperature_ = dict(info), info["temperature"]
+            return
         if info["reason"] == "cap":
             raise RuntimeError(f"calibration: the temperature search did not converge in {info['iterations']} iterations "
                                f"(beta {info['beta']!r})")
-        dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
+        self.__dict__.pop("_cal_bias", None)
         self._cal_state = state if state is not None else ops.temperature_state(info["beta"], dev)
         self.calibration_, self.temperature_ = dict(info), info["temperature"]
 
@@ -1194,7 +1255,7 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
             json.dump(self.history, f, indent=1)
         if getattr(self, "calibration_", None) is not None:
             with open(os.path.join(dirname, "calibration.json"), "w") as f:
-                json.dump(self.calibration_, f, indent=1)
+                json.dump(calibration_to_json(self.calibration_), f, indent=1)
         if getattr(self, "conformal_", None) is not None:
             with open(os.path.join(dirname, "conformal.json"), "w") as f:
                 json.dump(self.conformal_, f, indent=1)      # (an infinite qhat is written as Infinity, which json.load reads back)
@@ -1232,7 +1293,7 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         cal_file = os.path.join(dirname, "calibration.json")
         if getattr(self, "_cal_opts", None) is not None and os.path.exists(cal_file):
             with open(cal_file) as f:
-                self._set_calibration(json.load(f))          # beta goes back to the device
+                self._set_calibration(calibration_from_json(json.load(f)))      # beta (and the bias) go back to the device
         conf_file = os.path.join(dirname, "conformal.json")
         if os.path.exists(conf_file):
             with open(conf_file) as f:

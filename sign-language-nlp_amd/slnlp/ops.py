@@ -516,10 +516,69 @@ def temperature_state(beta, device):
 def temperature_download(state):
     """``fit_temperature``'s state as a dict: {temperature, beta, nll_before, nll_after, reason ("flat" | "bound" | "gradient" |
     "step" | "cap"), iterations, rows, bad_labels}.  One device-to-host copy (it waits for the fit's launches)."""
+    return _calibration_download(state, _lib.CALIBRATION_REASONS)
+
+
+def _calibration_download(state, reasons):
     h = state.cpu().numpy()
     q = h.view("int64")[8:]
     return {"temperature": float(h[1]), "beta": float(h[0]), "nll_before": float(h[2]), "nll_after": float(h[3]),
-            "reason": _lib.CALIBRATION_REASONS[int(q[0])], "iterations": int(q[1]), "rows": int(q[2]), "bad_labels": int(q[3])}
+            "reason": reasons[int(q[0])], "iterations": int(q[1]), "rows": int(q[2]), "bad_labels": int(q[3])}
+
+
+def _positive(what, name, v, zero_ok=False):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (0.0 <= float(v) if zero_ok else 0.0 < float(v)) or not float(v) < float("inf"):
+        raise ValueError(f"{what}: {name}={v!r}, expected a finite number {'>= 0' if zero_ok else '> 0'}")
+    return float(v)
+
+
+def fit_bias_temperature(logp, y, bias_sd=2.0, tol=1e-10, state=None, bias=None, scratch=None):
+    """Fit a temperature AND a per-class bias on ``logp`` float32 [N, V] (rows may be padded: ``stride(0) >= V``; V <= 512) against
+    the labels ``y`` int64 [N] -- bias-corrected temperature scaling, the MAP estimate under a N(0, ``bias_sd``^2) prior on every
+    bias (``slnlp_fit_bias_temperature``, include/slnlp.h states the damped Newton iteration).  ``tol``: the absolute bound on
+    max |gradient| the search stops at.  Returns ``(state, bias)``: the device state float64 [16], laid out as
+    ``fit_temperature``'s (its first double is beta), and the bias float64 [V] -- what ``shift_logp(logp, bias, state)`` takes.
+    ``state`` / ``bias`` / ``scratch`` (float64, ``slnlp_fit_bias_temperature_scratch_bytes`` / 8 doubles): buffers to use.  Runs
+    on the current stream of ``logp``'s device; no host wait."""
+    _lib.require_gpu()
+    N, V, ld = _logp_matrix("fit_bias_temperature", logp)
+    _labels("fit_bias_temperature", y, logp.device, N)
+    bias_sd, tol = _positive("fit_bias_temperature", "bias_sd", bias_sd), _positive("fit_bias_temperature", "tol", tol, zero_ok=True)
+    with torch.cuda.device(logp.device):
+        if state is None:
+            state = torch.empty(CAL_STATE_DOUBLES, dtype=torch.float64, device=logp.device)
+        _cal_state("fit_bias_temperature", state, logp.device)
+        if bias is None:
+            bias = torch.empty(V, dtype=torch.float64, device=logp.device)
+        _prior_vector("fit_bias_temperature", "bias", bias, logp.device, V)
+        if scratch is None:
+            need = load().slnlp_fit_bias_temperature_scratch_bytes(N, V)
+            check(0 if need >= 0 else 1, "fit_bias_temperature_scratch_bytes")
+            scratch = torch.empty(need // 8, dtype=torch.float64, device=logp.device)
+        if not (scratch.device == logp.device and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.is_contiguous()):
+            raise ValueError(f"fit_bias_temperature: scratch must be a contiguous float64 tensor on {logp.device}")
+        check(load().slnlp_fit_bias_temperature(ptr(logp), ld, ptr(y), N, V, bias_sd, tol, ptr(state), ptr(bias), ptr(scratch),
+                                                scratch.numel() * 8, stream_ptr()), "fit_bias_temperature")
+    return state, bias
+
+
+def bias_temperature_state(beta, bias, device):
+    """``(state, bias)`` on ``device`` holding only beta (and T) and the bias: what ``shift_logp`` needs of a bias calibration read
+    back from a checkpoint."""
+    import numpy as np
+    return temperature_state(beta, device), torch.from_numpy(np.ascontiguousarray(np.asarray(bias, dtype=np.float64))).to(device)
+
+
+def bias_temperature_download(state, bias, bias_sd):
+    """``fit_bias_temperature``'s result as a dict: ``temperature_download``'s -- ``iterations`` counts the evaluations, rejected
+    candidates included; ``nll_before`` / ``nll_after`` are the mean log-loss at (1, 0) and at the result, WITHOUT the penalty --
+    plus ``method`` "bias_temperature", ``bias_sd``, ``bias`` (float64 [V]) and ``penalty``, (1 / (2 bias_sd^2 rows)) sum bias^2.
+    Two device-to-host copies (the first waits for the fit's launches)."""
+    info = _calibration_download(state, _lib.BIAS_CALIBRATION_REASONS)
+    b = bias.cpu().numpy().copy()
+    info.update(method="bias_temperature", bias_sd=float(bias_sd), bias=b,
+                penalty=0.5 / (float(bias_sd) ** 2 * info["rows"]) * float((b * b).sum()) if info["rows"] else 0.0)
+    return info
 
 
 def scale_logp(logp, state, out=None):

@@ -50,7 +50,8 @@ class OutOfFold(LogProbJudge, ClassifierMixin, BaseEstimator):
     ``folds``: per member the indices of the rows it did NOT see -- together a partition of ``range(N)``, otherwise ValueError.
     ``dataset``: the ``TokenDataset`` the indices refer to; ``_forward_logp`` then refuses every other one (length, labels,
     lengths and ids are compared) -- without it only the length can be.  ``calibrated``: a member that fitted a temperature enters
-    as softmax(z / T_k); False: every member at T = 1.  It has no temperature of its own: ``calibration_`` is None,
+    as softmax(z / T_k), one with a ``bias_temperature`` calibration as softmax(beta_k z + b_k); False: every member at
+    T = 1.  It has no temperature of its own: ``calibration_`` is None,
     ``temperature_`` 1.0."""
     calibration_ = None
     temperature_ = 1.0
@@ -72,9 +73,6 @@ class OutOfFold(LogProbJudge, ClassifierMixin, BaseEstimator):
         """``VotingEnsemble(members, **kw)``: what to predict NEW rows with."""
         return VotingEnsemble(self.members, **kw)
 
-    def _states(self):
-        return [m._cal_state if self.calibrated and getattr(m, "calibration_", None) is not None else None for m in self.members]
-
     def _refuse_other_data(self, ds):
         own = self.dataset
         same = len(ds) == self.rows_ and (own is None or ds is own or (np.array_equal(ds.y, own.y) and np.array_equal(ds.lengths, own.lengths)
@@ -91,17 +89,20 @@ class OutOfFold(LogProbJudge, ClassifierMixin, BaseEstimator):
         its gate, one ``ops.scatter_logp`` per member into one buffer."""
         self._refuse_other_data(ds)
 
-        def keep(logp, yd):
-            return logp if logp.dtype == torch.float32 else logp.float()
-        got = [m._forward_logp(ds[idx], keep) for m, idx in zip(self.members, self.folds)]
+        def keep(member):                                    # (a bias calibration is already in the log-probs: VotingEnsemble's rule)
+            def then(logp, yd):
+                logp = logp if logp.dtype == torch.float32 else logp.float()
+                return member._calibrated_logp(logp, member._uses_temperature(self.calibrated))
+            return then
+        got = [m._forward_logp(ds[idx], keep(m)) for m, idx in zip(self.members, self.folds)]
         first = self.members[0]
         first._gate.enter(not first._fused)
         try:
             first._enter_stream()
             with torch.cuda.stream(first._stream), torch.no_grad():
-                dev = got[0].device
-                out = torch.empty(self.rows_, got[0].shape[1], dtype=torch.float32, device=dev)     # every row is written: a partition
-                for logp, idx, state in zip(got, self.folds, self._states()):
+                dev = got[0][0].device
+                out = torch.empty(self.rows_, got[0][0].shape[1], dtype=torch.float32, device=dev)     # every row is written: a partition
+                for (logp, state), idx in zip(got, self.folds):
                     ops.scatter_logp(logp, torch.from_numpy(idx).to(dev), out, state=state)
                 res = then(out, torch.from_numpy(np.asarray(ds.y)).to(dev))
             stream_sync(first._stream)

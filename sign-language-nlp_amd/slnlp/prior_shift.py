@@ -72,7 +72,8 @@ class PriorShift(LogProbJudge, ClassifierMixin, BaseEstimator):
     before they are normalised, and every class must end above 0), or a ``TokenDataset``: then the base's mean predicted
     probability on it, taken on the device at the first ``fit`` / ``set_priors`` (Alexandari et al.'s choice: always above 0, and
     the fixed point of the EM on the source data itself).  ``calibrated``: a base that fitted a temperature enters as
-    softmax(z / T); False: at T = 1.  The wrapper has no temperature of its own: ``calibration_`` is None, ``temperature_`` 1.0.
+    softmax(z / T), one with a ``bias_temperature`` calibration as softmax(beta z + b) -- the probabilities the EM is "hard to beat"
+    on (Alexandari et al. 2020); False: at T = 1.  The wrapper has no temperature of its own: ``calibration_`` is None, ``temperature_`` 1.0.
 
     ``fit(X)`` sets ``priors_`` (the estimated target priors), ``source_priors_``, ``log_ratio_`` (ln of their ratio, what the
     device adds to the log-probs) and ``prior_shift_`` (``ops.priors_download``'s dict); ``set_priors`` installs known priors
@@ -100,12 +101,15 @@ class PriorShift(LogProbJudge, ClassifierMixin, BaseEstimator):
     def _device(self):
         return VotingEnsemble._device_of(self.base.members[0] if isinstance(self.base, VotingEnsemble) else self.base)
 
-    def _state(self):
-        """The base's device calibration state, or None: beta = 1 (an ensemble's members' temperatures are already in its log-probs)."""
-        return self.base._cal_state if self.calibrated and getattr(self.base, "calibration_", None) is not None else None
-
     def _base_logp(self, ds, then):
-        return self.base._forward_logp(ds, lambda logp, yd: then(logp if logp.dtype == torch.float32 else logp.float(), yd))
+        """The base's float32 log-probs handed to ``then(logp, y_dev, state)`` as the base's own ``_calibrated_logp`` hands them over:
+        ``state`` is its device calibration state, or None: beta = 1 -- a ``bias_temperature`` calibration is then already in the
+        log-probs, and an ensemble's members' calibrations always are."""
+        def calibrated(logp, yd):
+            logp = logp if logp.dtype == torch.float32 else logp.float()
+            logp, state = self.base._calibrated_logp(logp, self.base._uses_temperature(self.calibrated))
+            return then(logp, yd, state)
+        return self.base._forward_logp(ds, calibrated)
 
     def _source_priors(self):
         """``source_priors_``, formed once: the checked vector, or the base's mean prediction on the source dataset -- table row 0
@@ -114,7 +118,7 @@ class PriorShift(LogProbJudge, ClassifierMixin, BaseEstimator):
             V = len(self.classes_)
             if isinstance(self.source, TokenDataset):
                 start = torch.zeros(V, dtype=torch.float64).to(self._device())
-                out = self._base_logp(self.source, lambda logp, yd: ops.fit_priors(logp, start, state=self._state(), max_iter=0, tol=0.0))
+                out = self._base_logp(self.source, lambda logp, yd, state: ops.fit_priors(logp, start, state=state, max_iter=0, tol=0.0))
                 got = ops.priors_download(out)
                 if got["reason"] == "empty":
                     raise ValueError(f"PriorShift: every one of the {len(self.source)} source rows holds a NaN or has no finite maximum")
@@ -144,7 +148,7 @@ class PriorShift(LogProbJudge, ClassifierMixin, BaseEstimator):
             raise ValueError(f"PriorShift.fit: tol={tol!r}, expected a finite number >= 0")
         ds = self._as_dataset(X)
         log_source = torch.from_numpy(np.log(self._source_priors())).to(self._device())
-        out = self._base_logp(ds, lambda logp, yd: ops.fit_priors(logp, log_source, state=self._state(), max_iter=max_iter, tol=float(tol)))
+        out = self._base_logp(ds, lambda logp, yd, state: ops.fit_priors(logp, log_source, state=state, max_iter=max_iter, tol=float(tol)))
         info = ops.priors_download(out)
         V = len(self.classes_)
         return self._install(out[2 * V:3 * V], info["priors"], info)
@@ -171,7 +175,7 @@ class PriorShift(LogProbJudge, ClassifierMixin, BaseEstimator):
         if getattr(self, "_log_w", None) is None:
             raise RuntimeError("PriorShift: no target priors yet: call fit(X) or set_priors(priors) first")
 
-        def shifted(logp, yd):
-            ops.shift_logp(logp, self._log_w, state=self._state(), out=logp)
+        def shifted(logp, yd, state):
+            ops.shift_logp(logp, self._log_w, state=state, out=logp)
             return then(logp, yd)
         return self._base_logp(ds, shifted)
