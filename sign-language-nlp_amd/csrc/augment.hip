@@ -13,7 +13,7 @@
 // to X_out[i, 0 .. len'): <unk> where the position drew mask, X[i, t] otherwise; X_out[i, len' .. S) = pad; L_out[i] = len'.
 // Positions >= len of the input are never read.  A pure function of the arguments: nothing depends on the grid or on timing.
 //
-// One wave per row, four rows per block, rows over a grid-stride loop (gather_id_rows' and score.hip's shape).  Lanes stride the
+// One wave per row, four rows per block, rows over a grid-stride loop (wave_rows, common.hpp: gather_id_rows' shape).  Lanes stride the
 // positions 64 at a time; within a chunk a kept position's slot is the running base plus the number of kept lanes below it (the
 // wave's keep ballot through v_mbcnt), and the base carries over the chunks.  The "everything dropped" rule needs the row's
 // total before any store, so a first pass over the chunks only counts ballots and the second draws the same words again and
@@ -21,15 +21,11 @@
 // arithmetic only, no atomics, no LDS.
 #include <limits.h>
 
-#include <algorithm>
-
 #include "common.hpp"
 #include "launch.hpp"
 #include "spans.hpp"
 
 namespace slnlp {
-
-constexpr int AUGMENT_MAX_BLOCKS = 2048;  // x 4 rows: more than 8192 rows wrap the stride loop
 
 // kept lanes below this one
 __device__ __forceinline__ int lanes_below(unsigned long long ballot) {
@@ -39,11 +35,8 @@ __device__ __forceinline__ int lanes_below(unsigned long long ballot) {
 __device__ __forceinline__ void augment_rows_body(const int64_t* __restrict__ X, const int64_t* __restrict__ L, int n, int S, int64_t pad,
                                                   int64_t unk, unsigned thr_drop, unsigned thr_mask, unsigned long long seed,
                                                   unsigned epoch, int64_t* __restrict__ X_out, int64_t* __restrict__ L_out) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
     const SeedKey K = seed_key(seed, epoch);
-    for (int r = wave; r < n; r += nwaves) {             // r, len: the same in every lane, so are the loops' trip counts
+    wave_rows<int>(n, [&](int r, int lane) {             // r, len: the same in every lane, so are the loops' trip counts
         const int64_t l64 = L[r];
         const int len = l64 < 0 ? 0 : (l64 > S ? S : (int)l64);
         const int64_t* src = X + (long)r * S;
@@ -66,7 +59,7 @@ __device__ __forceinline__ void augment_rows_body(const int64_t* __restrict__ X,
         }
         for (int c = base + lane; c < S; c += 64) dst[c] = pad;
         if (lane == 0) L_out[r] = base;
-    }
+    });
 }
 SLNLP_ZKERNEL(augment_rows_kernel, 256, augment_rows_body)
 
@@ -85,8 +78,7 @@ int augment_rows(const int64_t* X, const int64_t* L, int64_t n, int64_t S, int64
     SLNLP_CHECK_ARG(!spans_overlap(xo, x), "augment_rows: X_out overlaps X (the kernel is not in-place)");
     SLNLP_CHECK_ARG(!spans_overlap(lo, l), "augment_rows: L_out overlaps L (the kernel is not in-place)");
     SLNLP_CHECK_ARG(!spans_overlap(xo, l) && !spans_overlap(lo, x) && !spans_overlap(xo, lo), "augment_rows: the id and length buffers overlap");
-    const int blocks = (int)std::min<int64_t>((n + 3) / 4, AUGMENT_MAX_BLOCKS);
-    return zlaunch(augment_rows_kernel, dim3(blocks), 256, 0, st, "augment_rows", X, L, (int)n, (int)S, pad, unk, dropout_threshold(p_drop),
+    return zlaunch(augment_rows_kernel, dim3(wave_rows_grid(n)), 256, 0, st, "augment_rows", X, L, (int)n, (int)S, pad, unk, dropout_threshold(p_drop),
                    dropout_threshold(p_mask), (unsigned long long)seed, (unsigned)epoch, X_out, L_out);
 }
 

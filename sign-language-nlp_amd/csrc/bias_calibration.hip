@@ -14,7 +14,7 @@
 //
 // HOW IT RUNS.  The call queues a FIXED sequence of 48 evaluations plus the one at the result and never waits for the host.
 // Evaluation e is five launches (the last two are not queued behind evaluation 47, the final one has the first three):
-//   bias_rows     one wave per row, four rows per block, rows over a grid-stride loop (calibration.hip's shape): lanes stride the
+//   bias_rows     one wave per row, four rows per block, rows over a grid-stride loop (wave_rows, common.hpp): lanes stride the
 //                 columns; the maximum and the sums are wave reductions in a fixed order; the wave writes p_i as fp64 into scratch
 //                 [N, Vp] (Vp = V rounded up to 16, the padding zeros) and lane 0 the row terms (f_i, m_i - z_iy, h_i, m_i).  A row
 //                 whose label lies outside the columns writes zeros.
@@ -39,24 +39,22 @@
 #include <limits.h>
 #include <math.h>
 
-#include <algorithm>
-
 #include "block_reduce.hpp"
 #include "common.hpp"
+#include "fit_state.hpp"
 #include "launch.hpp"
 #include "spans.hpp"
 
 namespace slnlp {
 
-constexpr int BC_MAX_BLOCKS = 2048;    // x 4 rows: more than 8192 rows wrap the stride loop
 constexpr int BC_EVALS = 48;           // the evaluation cap (rejected candidates count)
 constexpr int BC_FINAL = BC_EVALS;     // the evaluation at the result
 constexpr int BC_MAX_V = SLNLP_BIAS_CAL_MAX_V;
 constexpr double BC_BETA_MIN = 0.015625, BC_BETA_MAX = 64.0;      // 2^-6, 2^6
 constexpr double BC_ARMIJO = 1e-4;
-// state: 8 doubles, then 8 int64 (include/slnlp.h documents the first four of each; the rest is the iteration's own)
-enum { BC_BETA = 0, BC_T = 1, BC_F_BEFORE = 2, BC_F_AFTER = 3, BC_F = 4, BC_STEP = 5, BC_GTD = 6, BC_LAMBDA = 7 };
-enum { BC_REASON = 0, BC_EVALUATIONS = 1, BC_ROWS = 2, BC_BAD = 3, BC_NEED_H = 4, BC_HALVINGS = 5, BC_NEWTON = 6 };
+// state (fit_state.hpp; FIT_ITERATIONS counts the evaluations): the iteration's own doubles and words
+enum { BC_F = 4, BC_STEP = 5, BC_GTD = 6, BC_LAMBDA = 7 };
+enum { BC_NEED_H = 4, BC_HALVINGS = 5, BC_NEWTON = 6 };
 
 typedef double bc_double4 __attribute__((ext_vector_type(4)));
 
@@ -82,33 +80,24 @@ struct BiasScratch {
     }
 };
 
-// whether evaluation `eval` of rows / classes / decide has nothing left to do (evaluation 0 initialises the state and the final
-// one always runs: neither reads the flag)
-__device__ __forceinline__ bool bc_settled(const double* state, int eval) {
-    return eval != 0 && eval != BC_FINAL && ((const int64_t*)(state + 8))[BC_REASON] != 0;
-}
-
 // a maximum that keeps a NaN (from arguments out of contract: the gradient test then fails)
 __device__ __forceinline__ double bc_max_nan(double m, double o) { return o > m || o != o ? o : m; }
 
 __device__ __forceinline__ void bias_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V, int Vp,
                                                const double* __restrict__ state, const double* __restrict__ cand, double* __restrict__ P,
                                                double* __restrict__ terms, int eval) {
-    if (bc_settled(state, eval)) return;
+    if (fit_settled(state, eval, 0, BC_FINAL)) return;
     const bool start = eval == 0;                        // the point (1, 0): cand holds nothing yet
     const double beta = start ? 1.0 : cand[0];
     const double* b = cand + 1;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
-    for (long r = wave; r < N; r += nwaves) {            // r: the same in every lane, so every lane reaches the reductions
+    wave_rows(N, [&](long r, int lane) {
         const float* row = logp + r * ld;
         double* prow = P + r * Vp;
         const int64_t label = y[r];
         if (label < 0 || label >= V) {                   // (wave-uniform) never used as an index: the row adds nothing to any sum
             for (int j = lane; j < Vp; j += 64) prow[j] = 0.0;
             if (lane == 0) *(double4*)(terms + 4 * r) = make_double4(0.0, 0.0, 0.0, 0.0);
-            continue;
+            return;
         }
         double amax = -INFINITY;
         for (int j = lane; j < V; j += 64) amax = fmax(amax, beta * (double)row[j] + (start ? 0.0 : b[j]));
@@ -134,7 +123,7 @@ __device__ __forceinline__ void bias_rows_body(const float* __restrict__ logp, l
             const double ay = beta * zy + (start ? 0.0 : b[label]);
             *(double4*)(terms + 4 * r) = make_double4(log1p(rest) - (ay - amax), mean - zy, s2 / s0 - mean * mean, mean);
         }
-    }
+    });
 }
 SLNLP_ZKERNEL(bias_rows_kernel, 256, bias_rows_body)
 
@@ -143,21 +132,18 @@ __device__ __forceinline__ void bias_classes_body(const float* __restrict__ logp
                                                   const double* __restrict__ state, const double* __restrict__ P,
                                                   const double* __restrict__ terms, double* __restrict__ colS, double* __restrict__ colC,
                                                   double* __restrict__ cnt, int eval) {
-    if (bc_settled(state, eval)) return;                 // (every thread reads the same flag: the block returns as one)
+    if (fit_settled(state, eval, 0, BC_FINAL)) return;                 // (every thread reads the same flag: the block returns as one)
     __shared__ double red[3][256];
     const int tid = threadIdx.x;
     const long c = blockIdx.x;
-    double s = 0.0, hz = 0.0, n = 0.0;
-    for (long r = tid; r < N; r += 256) {
+    block_sum_rows<3>(red, tid, N, [&](long r, double* acc) {
         const double p = P[r * Vp + c];
         if (p != 0.0) {                                  // (an excluded row, or a column at -inf)
-            s += p;
-            hz += p * ((double)logp[r * ld + c] - terms[4 * r + 3]);
+            acc[0] += p;
+            acc[1] += p * ((double)logp[r * ld + c] - terms[4 * r + 3]);
         }
-        if (eval == 0) n += y[r] == c ? 1.0 : 0.0;
-    }
-    red[0][tid] = s; red[1][tid] = hz; red[2][tid] = n;
-    block_tree<3>(red, tid, TreeSum{});
+        if (eval == 0) acc[2] += y[r] == c ? 1.0 : 0.0;
+    });
     if (tid != 0) return;
     colS[c] = red[0][0];
     colC[c] = red[1][0];
@@ -170,8 +156,8 @@ __device__ __forceinline__ void bias_decide_body(const double* __restrict__ term
                                                  const double* __restrict__ colC, const double* __restrict__ cnt, int N, int V, int W,
                                                  double bias_sd, double tol, double* __restrict__ state, double* cand, double* theta,
                                                  double* __restrict__ g, double* __restrict__ A, double* __restrict__ bias, int eval) {
-    if (bc_settled(state, eval)) return;
-    int64_t* q = (int64_t*)(state + 8);
+    if (fit_settled(state, eval, 0, BC_FINAL)) return;
+    int64_t* q = fit_words(state);
     __shared__ double red[3][256];
     __shared__ int bad_red[256];
     __shared__ int action;
@@ -179,7 +165,7 @@ __device__ __forceinline__ void bias_decide_body(const double* __restrict__ term
     const bool start = eval == 0;
     double f = 0.0, gb = 0.0, h = 0.0;
     int bad = 0;
-    for (long r = tid; r < N; r += 256) {
+    for (long r = tid; r < N; r += 256) {                // (the first evaluation counts the bad labels along with the sums)
         const double4 t = *(const double4*)(terms + 4 * r);
         f += t.x; gb += t.y; h += t.z;
         if (start) {
@@ -196,7 +182,7 @@ __device__ __forceinline__ void bias_decide_body(const double* __restrict__ term
         block_tree<1>(&bad_red, tid, TreeSum{});
         M = (long)N - bad_red[0];
     } else {
-        M = q[BC_ROWS];
+        M = q[FIT_ROWS];
     }
     __syncthreads();                                     // red is rewritten below: every thread has read it
     const double inv = M > 0 ? 1.0 / (double)M : 0.0;
@@ -219,7 +205,7 @@ __device__ __forceinline__ void bias_decide_body(const double* __restrict__ term
         int act;
         const double nll = f * inv;
         if (eval == BC_FINAL) {
-            state[BC_F_AFTER] = nll;
+            state[FIT_F_AFTER] = nll;
             act = 4;
         } else {
             const double F = nll + 0.5 * lam * red[1][0], gbeta = gb * inv;
@@ -227,27 +213,24 @@ __device__ __forceinline__ void bias_decide_body(const double* __restrict__ term
             g[0] = gbeta;
             A[0] = h * inv;
             if (start) {
-                for (int k = 0; k < 8; ++k) state[k] = 0.0;
-                for (int k = 0; k < 8; ++k) q[k] = 0;
-                q[BC_ROWS] = M;
-                q[BC_BAD] = (long)N - M;
-                state[BC_F_BEFORE] = nll;
+                fit_state_reset(state, M, (long)N - M);
+                state[FIT_F_BEFORE] = nll;
                 state[BC_LAMBDA] = lam;
             }
             if (start && (M == 0 || V == 1)) {           // nothing to fit: (1, 0)
-                q[BC_REASON] = SLNLP_CAL_FLAT;
+                q[FIT_REASON] = SLNLP_CAL_FLAT;
                 act = 2;
             } else {
-                q[BC_EVALUATIONS] = eval + 1;
+                q[FIT_ITERATIONS] = eval + 1;
                 const bool accept = start || F <= state[BC_F] + BC_ARMIJO * state[BC_STEP] * state[BC_GTD];     // (a NaN is rejected)
                 if (accept) {
                     state[BC_F] = F;
-                    if (gmax <= tol) { q[BC_REASON] = SLNLP_CAL_GRADIENT; act = 2; }
-                    else if (eval == BC_EVALS - 1) { q[BC_REASON] = SLNLP_CAL_CAP; act = 2; }
+                    if (gmax <= tol) { q[FIT_REASON] = SLNLP_CAL_GRADIENT; act = 2; }
+                    else if (eval == BC_EVALS - 1) { q[FIT_REASON] = SLNLP_CAL_CAP; act = 2; }
                     else { q[BC_NEED_H] = 1; act = 1; }
                 } else {
                     q[BC_HALVINGS] += 1;
-                    if (eval == BC_EVALS - 1) { q[BC_REASON] = SLNLP_CAL_CAP; act = 3; }
+                    if (eval == BC_EVALS - 1) { q[FIT_REASON] = SLNLP_CAL_CAP; act = 3; }
                     else { q[BC_NEED_H] = 0; act = 0; }
                 }
             }
@@ -262,12 +245,7 @@ __device__ __forceinline__ void bias_decide_body(const double* __restrict__ term
         theta[i] = v;
         if (act == 1) continue;
         cand[i] = v;                                     // the final evaluation runs at the result
-        if (i == 0) {
-            state[BC_BETA] = v;
-            state[BC_T] = 1.0 / v;
-        } else {
-            bias[i - 1] = v;
-        }
+        fit_result(state, bias, i, v);
     }
 }
 SLNLP_ZKERNEL(bias_decide_kernel, 256, bias_decide_body)
@@ -276,8 +254,8 @@ SLNLP_ZKERNEL(bias_decide_kernel, 256, bias_decide_body)
 // l & 15]; of the four results of a lane, register v is D[row (l >> 4) + 4 v][col l & 15] -- not the other shapes' layout.
 __device__ __forceinline__ void bias_hessian_body(const double* __restrict__ P, const double* __restrict__ colS, int N, int V, int Vp, int W,
                                                   const double* __restrict__ state, double* __restrict__ A) {
-    const int64_t* q = (const int64_t*)(state + 8);
-    if (q[BC_REASON] != 0 || q[BC_NEED_H] == 0) return;
+    const int64_t* q = fit_words(state);
+    if (fit_settled(state) || q[BC_NEED_H] == 0) return;
     int I = 0;
     while ((I + 1) * (I + 2) / 2 <= (int)blockIdx.x) ++I;
     const int J = (int)blockIdx.x - I * (I + 1) / 2;
@@ -302,7 +280,7 @@ __device__ __forceinline__ void bias_hessian_body(const double* __restrict__ P, 
         const double b = r < N ? pb[r * Vp] : 0.0;
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
     }
-    const double M = (double)q[BC_ROWS], inv = 1.0 / M, lam = state[BC_LAMBDA];
+    const double M = (double)q[FIT_ROWS], inv = 1.0 / M, lam = state[BC_LAMBDA];
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
         const int row = 16 * I + k + 4 * v, col = 16 * J + cc;
@@ -318,8 +296,8 @@ SLNLP_ZKERNEL(bias_hessian_kernel, 64, bias_hessian_body)
 constexpr int BC_NB = 8, BC_PAD = BC_NB + 1, BC_SYS_MAX = BC_MAX_V + 16;      // (the padded row keeps a tile's 16 rows off one bank)
 __device__ __forceinline__ void bias_solve_body(double* A, const double* __restrict__ g, const double* theta, double* cand, double* d, int V,
                                                 int W, double* __restrict__ state, double* __restrict__ bias) {
-    int64_t* q = (int64_t*)(state + 8);
-    if (q[BC_REASON] != 0) return;
+    int64_t* q = fit_words(state);
+    if (fit_settled(state)) return;
     __shared__ double pan[BC_SYS_MAX * BC_PAD], rhs[BC_SYS_MAX];
     __shared__ double red[256];
     __shared__ double step;
@@ -393,13 +371,8 @@ __device__ __forceinline__ void bias_solve_body(double* A, const double* __restr
             for (int i = tid; i <= V; i += 256) {
                 const double v = theta[i];
                 cand[i] = v;
-                if (i == 0) {
-                    state[BC_BETA] = v;
-                    state[BC_T] = 1.0 / v;
-                    q[BC_REASON] = SLNLP_CAL_PIVOT;
-                } else {
-                    bias[i - 1] = v;
-                }
+                fit_result(state, bias, i, v);
+                if (i == 0) q[FIT_REASON] = SLNLP_CAL_PIVOT;
             }
             return;
         }
@@ -464,10 +437,7 @@ int fit_bias_temperature(const float* logp, int64_t ld, const int64_t* y, int64_
     SLNLP_CHECK_ARG(tol >= 0.0 && tol < INFINITY, "fit_bias_temperature: tol=%g is not a finite number >= 0", tol);
     const BiasScratch L(N, V);
     const size_t need = (size_t)L.doubles * 8;
-    SLNLP_CHECK_ARG(scratch_bytes >= 0 && (size_t)scratch_bytes >= need,
-                    "fit_bias_temperature: scratch of %ld bytes is too small, %ld rows of %ld classes need %ld", (long)scratch_bytes, (long)N,
-                    (long)V, (long)need);
-    SLNLP_CHECK_ARG(((uintptr_t)scratch & 31) == 0, "fit_bias_temperature: scratch is not 32-byte aligned");
+    SLNLP_TRY(check_scratch("fit_bias_temperature", scratch, scratch_bytes, need, N, V, 32));
     SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0 && (((uintptr_t)y | (uintptr_t)state | (uintptr_t)bias) & 7) == 0,
                     "fit_bias_temperature: misaligned pointer (logp: 4 bytes; y, state, bias: 8 bytes)");
     const Span out[3] = {{state, SLNLP_CAL_STATE_BYTES, "state"}, {bias, (size_t)V * 8, "bias"}, {scratch, need, "scratch"}};
@@ -477,7 +447,7 @@ int fit_bias_temperature(const float* logp, int64_t ld, const int64_t* y, int64_
     double *P = s + L.P, *colS = s + L.colS, *colC = s + L.colC, *cnt = s + L.cnt, *theta = s + L.theta, *cand = s + L.cand, *g = s + L.g,
            *d = s + L.d, *A = s + L.A, *terms = s + L.terms;
     const int Vp = (int)L.Vp, W = (int)L.W, T = Vp / 16;
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, BC_MAX_BLOCKS);
+    const int blocks = wave_rows_grid(N);
     for (int eval = 0; eval <= BC_FINAL; ++eval) {
         SLNLP_TRY(zlaunch(bias_rows_kernel, dim3(blocks), 256, 0, st, "fit_bias_temperature_rows", logp, (long)ld, y, (int)N, (int)V, Vp,
                           (const double*)state, (const double*)cand, P, terms, eval));

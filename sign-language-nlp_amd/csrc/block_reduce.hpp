@@ -28,4 +28,15 @@ __device__ __forceinline__ void block_tree(T (*red)[256], int tid, Op op) {
     }
 }
 
+// "thread t adds rows t, t + 256, ... in increasing order, then the tree": f(r, acc) adds row r's terms to acc[0 .. H), and
+// red[h][0] is sum h afterwards -- an order that depends on n alone.  block_tree's barriers and rules.
+template <int H, class T, class F>
+__device__ __forceinline__ void block_sum_rows(T (*red)[256], int tid, long n, F f) {
+    T acc[H] = {};
+    for (long r = tid; r < n; r += 256) f(r, acc);
+#pragma unroll
+    for (int h = 0; h < H; ++h) red[h][tid] = acc[h];
+    block_tree<H>(red, tid, TreeSum{});
+}
+
 }  // namespace slnlp

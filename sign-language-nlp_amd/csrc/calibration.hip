@@ -14,8 +14,8 @@
 // HOW IT RUNS.  The call queues a FIXED sequence of 36 evaluations and never waits for the host:
 //   0: beta = 1 (nll_before, the flat test's second half)   1: beta = 2^-6   2: beta = 2^6   3 .. 34: the 32 iterations
 //   35: the result (nll_after)
-// One evaluation is two launches.  fit_rows: one wave per row, four rows per block, rows over a grid-stride loop (score.hip's
-// shape); lanes stride the columns, the row maximum and the sums sum e - 1, sum e z, sum e z^2 (e = exp(beta z - max)) are wave
+// One evaluation is two launches.  fit_rows: one wave per row, four rows per block, rows over a grid-stride loop (wave_rows,
+// common.hpp); lanes stride the columns, the row maximum and the sums sum e - 1, sum e z, sum e z^2 (e = exp(beta z - max)) are wave
 // reductions in a fixed order (DPP inside 16 lanes, v_readlane across the four rows), and lane 0 writes (f_i, g_i, h_i, s_i)
 // into scratch [N, 4].  fit_update: ONE block of 256 threads sums the row terms -- thread t rows t, t + 256, ... in increasing
 // order, then a fixed binary tree over the 256 partial sums in LDS: an order that depends on N alone -- and thread 0 applies
@@ -37,41 +37,30 @@
 #include <limits.h>
 #include <math.h>
 
-#include <algorithm>
-
 #include "common.hpp"
+#include "fit_state.hpp"
 #include "launch.hpp"
 #include "scale_row.hpp"
 #include "spans.hpp"
 
 namespace slnlp {
 
-constexpr int CAL_MAX_BLOCKS = 2048;   // x 4 rows: more than 8192 rows wrap the stride loop
 constexpr int CAL_ITERS = 32;          // the iteration cap
 constexpr int CAL_EVALS = CAL_ITERS + 4;   // beta = 1, the two bounds, the iterations, the result
-// state: 8 doubles, then 8 int64 (include/slnlp.h documents the first four of each; the rest is the iteration's own)
-enum { CAL_BETA = 0, CAL_T = 1, CAL_F_BEFORE = 2, CAL_F_AFTER = 3, CAL_LO = 4, CAL_HI = 5, CAL_NEXT = 6 };
-enum { CAL_REASON = 0, CAL_ITERATIONS = 1, CAL_ROWS = 2, CAL_BAD = 3, CAL_FLAT_AT_ONE = 4 };
+// state (fit_state.hpp): the iteration's own doubles and word
+enum { CAL_LO = 4, CAL_HI = 5, CAL_NEXT = 6 };
+enum { CAL_FLAT_AT_ONE = 4 };
 constexpr double CAL_BETA_MIN = 0.015625, CAL_BETA_MAX = 64.0;                    // 2^-6, 2^6
 constexpr double CAL_GRAD_TOL = 5.6843418860808015e-14;                           // 2^-44
 constexpr double CAL_STEP_TOL = 9.094947017729282e-13;                            // 2^-40
 
 // (the fp64 wave reductions dpp_mov_d / lane_bcast_d / wave_sum_d: common.hpp, shared with reliability.hip)
 
-// whether evaluation `eval` of the sequence has nothing left to do (evaluation 0 initialises the state: it reads no flag)
-__device__ __forceinline__ bool cal_settled(const int64_t* q, int eval) {
-    return eval != 0 && eval != CAL_EVALS - 1 && q[CAL_REASON] != 0;
-}
-
 __device__ __forceinline__ void fit_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
                                               const double* __restrict__ state, double* __restrict__ terms, int eval) {
-    const int64_t* q = (const int64_t*)(state + 8);
-    if (cal_settled(q, eval)) return;
+    if (fit_settled(state, eval, 0, CAL_EVALS - 1)) return;
     const double beta = eval == 0 ? 1.0 : state[CAL_NEXT];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
-    for (long r = wave; r < N; r += nwaves) {            // r: the same in every lane, so every lane reaches the reductions
+    wave_rows(N, [&](long r, int lane) {
         const float* row = logp + r * ld;
         const int64_t label = y[r];
         const bool ok = label >= 0 && label < V;         // a label outside the columns is never used as an index
@@ -105,23 +94,22 @@ __device__ __forceinline__ void fit_rows_body(const float* __restrict__ logp, lo
             }
             *(double4*)(terms + 4 * r) = t;
         }
-    }
+    });
 }
 SLNLP_ZKERNEL(fit_rows_kernel, 256, fit_rows_body)
 
 // the end of the search: the result, why, and after how many iterations; evaluation 35 then runs at the result
 __device__ __forceinline__ void cal_finish(double* state, int64_t* q, double beta, int reason, int iterations) {
-    state[CAL_BETA] = beta;
-    state[CAL_T] = 1.0 / beta;
+    fit_result(state, nullptr, 0, beta);
     state[CAL_NEXT] = beta;
-    q[CAL_ITERATIONS] = iterations;
-    q[CAL_REASON] = reason;
+    q[FIT_ITERATIONS] = iterations;
+    q[FIT_REASON] = reason;
 }
 
 __device__ __forceinline__ void fit_update_body(const double* __restrict__ terms, const int64_t* __restrict__ y, int N, int V,
                                                 double* __restrict__ state, int eval) {
-    int64_t* q = (int64_t*)(state + 8);
-    if (cal_settled(q, eval)) return;                    // (every thread reads the same flag: the block returns as one)
+    if (fit_settled(state, eval, 0, CAL_EVALS - 1)) return;
+    int64_t* q = fit_words(state);
     __shared__ double red[4][256];
     __shared__ int bad_red[256];
     const int tid = threadIdx.x;
@@ -136,8 +124,8 @@ __device__ __forceinline__ void fit_update_body(const double* __restrict__ terms
     red[0][tid] = f; red[1][tid] = g; red[2][tid] = h; red[3][tid] = s;
     bad_red[tid] = bad;
     __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) {
+    for (int w = 128; w >= 1; w >>= 1) {                 // block_reduce.hpp's tree over the four doubles AND the int: one pass of
+        if (tid < w) {                                   // nine barriers where two block_tree calls make two, 36 times a fit
 #pragma unroll
             for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + w];
             bad_red[tid] += bad_red[tid + w];
@@ -147,10 +135,7 @@ __device__ __forceinline__ void fit_update_body(const double* __restrict__ terms
     if (tid != 0) return;
     const long n_bad = bad_red[0], M = (long)N - n_bad;
     if (eval == 0) {
-        for (int k = 0; k < 8; ++k) state[k] = 0.0;
-        for (int k = 0; k < 8; ++k) q[k] = 0;
-        q[CAL_ROWS] = M;
-        q[CAL_BAD] = n_bad;
+        fit_state_reset(state, M, n_bad);
         if (M == 0) {                                    // nothing to fit on: T = 1 (the caller reads bad_labels)
             cal_finish(state, q, 1.0, SLNLP_CAL_FLAT, 0);
             return;
@@ -160,7 +145,7 @@ __device__ __forceinline__ void fit_update_body(const double* __restrict__ terms
     f = red[0][0] * inv; g = red[1][0] * inv; h = red[2][0] * inv; s = red[3][0] * inv;
     const bool flat = fabs(g) <= CAL_GRAD_TOL * s;
     if (eval == 0) {                                     // beta = 1
-        state[CAL_F_BEFORE] = f;
+        state[FIT_F_BEFORE] = f;
         q[CAL_FLAT_AT_ONE] = flat ? 1 : 0;
         state[CAL_NEXT] = CAL_BETA_MIN;
     } else if (eval == 1) {                              // beta = 2^-6
@@ -193,7 +178,7 @@ __device__ __forceinline__ void fit_update_body(const double* __restrict__ terms
         else if (it == CAL_ITERS) cal_finish(state, q, next, SLNLP_CAL_CAP, it);
         else state[CAL_NEXT] = next;
     } else {                                             // the result
-        state[CAL_F_AFTER] = f;
+        state[FIT_F_AFTER] = f;
     }
 }
 SLNLP_ZKERNEL(fit_update_kernel, 256, fit_update_body)
@@ -202,10 +187,7 @@ SLNLP_ZKERNEL(fit_update_kernel, 256, fit_update_body)
 __device__ __forceinline__ void scale_logp_body(const float* logp, long ld, int N, int V, const double* __restrict__ beta_dev, float* out,
                                                 long ld_out) {
     const double beta = beta_dev[0];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
-    for (long r = wave; r < N; r += nwaves) scale_logp_row(logp + r * ld, out + r * ld_out, V, lane, beta);
+    wave_rows(N, [&](long r, int lane) { scale_logp_row(logp + r * ld, out + r * ld_out, V, lane, beta); });
 }
 SLNLP_ZKERNEL(scale_logp_kernel, 256, scale_logp_body)
 
@@ -222,14 +204,12 @@ int fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64_t N, 
     SLNLP_CHECK_ARG(logp && y && state && scratch, "fit_temperature: null pointer");
     Span z;
     SLNLP_TRY(check_logp_matrix("fit_temperature", logp, N, INT_MAX, V, INT_MAX, ld, &z));
-    SLNLP_CHECK_ARG(scratch_bytes >= N * 32, "fit_temperature: scratch of %ld bytes is too small, %ld rows need %ld",
-                    (long)scratch_bytes, (long)N, (long)(N * 32));
-    SLNLP_CHECK_ARG(((uintptr_t)scratch & 31) == 0, "fit_temperature: scratch is not 32-byte aligned");
+    SLNLP_TRY(check_scratch("fit_temperature", scratch, scratch_bytes, (size_t)N * 32, N, 0, 32));
     SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0 && (((uintptr_t)y | (uintptr_t)state) & 7) == 0, "fit_temperature: misaligned pointer");
     const Span labels = {y, (size_t)N * 8, "y"}, s = {state, SLNLP_CAL_STATE_BYTES, "state"}, t = {scratch, (size_t)N * 32, "scratch"};
     SLNLP_CHECK_ARG(!spans_overlap(s, z) && !spans_overlap(s, labels) && !spans_overlap(t, z) && !spans_overlap(t, labels) && !spans_overlap(t, s),
                     "fit_temperature: state or scratch overlaps an input or each other");
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, CAL_MAX_BLOCKS);
+    const int blocks = wave_rows_grid(N);
     for (int eval = 0; eval < CAL_EVALS; ++eval) {
         SLNLP_TRY(zlaunch(fit_rows_kernel, dim3(blocks), 256, 0, st, "fit_temperature_rows", logp, (long)ld, y, (int)N, (int)V,
                           (const double*)state, (double*)scratch, eval));
@@ -241,18 +221,15 @@ int fit_temperature(const float* logp, int64_t ld, const int64_t* y, int64_t N, 
 
 int scale_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, float* out, int64_t ld_out, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && beta_dev && out, "scale_logp: null pointer");
-    SLNLP_CHECK_ARG(N >= 1 && N <= INT_MAX, "scale_logp: N=%ld outside 1..%d", (long)N, INT_MAX);
-    SLNLP_CHECK_ARG(V >= 1 && V <= INT_MAX, "scale_logp: V=%ld outside 1..%d", (long)V, INT_MAX);
+    SLNLP_TRY(check_logp_dims("scale_logp", N, INT_MAX, V, INT_MAX));
     SLNLP_CHECK_ARG(ld >= V && ld_out >= V, "scale_logp: ld=%ld or ld_out=%ld is less than V=%ld", (long)ld, (long)ld_out, (long)V);
     SLNLP_CHECK_ARG(ld <= INT64_MAX / 8 / N && ld_out <= INT64_MAX / 8 / N, "scale_logp: ld=%ld / ld_out=%ld times N=%ld is no addressable matrix",
                     (long)ld, (long)ld_out, (long)N);
     SLNLP_CHECK_ARG((((uintptr_t)logp | (uintptr_t)out) & 3) == 0 && ((uintptr_t)beta_dev & 7) == 0, "scale_logp: misaligned pointer");
     const Span z = {logp, matrix_bytes(N, ld, V), "logp"}, o = {out, matrix_bytes(N, ld_out, V), "out"};
-    const bool in_place = (const float*)out == logp && ld_out == ld;
-    SLNLP_CHECK_ARG(in_place || !spans_overlap(o, z),
-                    "scale_logp: out overlaps logp without being logp itself (in place means the same pointer and the same row stride)");
+    SLNLP_TRY(check_in_place("scale_logp", o, ld_out, z, ld));
     SLNLP_CHECK_ARG(!spans_overlap(o, Span{beta_dev, 8, "beta"}), "scale_logp: out overlaps beta");
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, CAL_MAX_BLOCKS);
+    const int blocks = wave_rows_grid(N);
     return zlaunch(scale_logp_kernel, dim3(blocks), 256, 0, st, "scale_logp", logp, (long)ld, (int)N, (int)V, beta_dev, out, (long)ld_out);
 }
 

@@ -103,6 +103,23 @@ __device__ __forceinline__ void gather_id_rows(const int64_t* __restrict__ X, co
 // blocks of 256 threads that give every row of a B-row batch a wave of its own (at most 64 of them: the waves loop)
 static inline int gather_rows_grid(int B) { return B >= 256 ? 64 : (B + 3) / 4; }
 
+// ------------------------------------------------- one wave per row ----
+// gather_id_rows' loop for the judging kernels: blocks of 256 threads, ONE WAVE takes a row, four rows per block, the rows over
+// a grid-stride loop; any grid.x.  f(r, lane) runs with r the same in every lane (the wave index comes from readfirstlane), so
+// every lane reaches f's wave reductions, and a load at an address made of r alone is one per wave.  A loop body's `continue` is
+// f's `return`.  Row is the type of r (long unless the site says otherwise); n keeps the site's own type.  (gather_id_rows keeps
+// its own copy: it is on the train step, and through this helper its kernels' instruction streams are not the same ones.)
+template <class Row = long, class Count, class F>
+__device__ __forceinline__ void wave_rows(Count n, F f) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int nwaves = gridDim.x * 4;
+    for (Row r = wave; r < n; r += nwaves) f(r, lane);
+}
+constexpr int WAVE_ROWS_MAX_BLOCKS = 2048;   // x 4 rows: more than 8192 rows wrap the stride loop
+// the blocks of 256 threads of a wave_rows launch over n rows
+static inline int wave_rows_grid(int64_t n) { return (int)((n + 3) / 4 < WAVE_ROWS_MAX_BLOCKS ? (n + 3) / 4 : WAVE_ROWS_MAX_BLOCKS); }
+
 // ------------------------------------------------------------- dropout ------
 // Counter-based Threefry4x32-12 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11 -- the
 // 12-round form is the shortest Threefry-4x32 the paper reports as passing BigCrush; known-answer vectors of the 20-round form

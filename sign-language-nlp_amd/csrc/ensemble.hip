@@ -16,7 +16,7 @@
 // A row in which a member holds a NaN or has a maximum that is not finite, or (LOG) whose every u_c is -inf, gets NaN in every out
 // column and rows = (NaN, NaN, NaN, -2): reliability.hip's NaN-row convention.  tests/ensemble_ref.py restates all of it.
 //
-// HOW IT RUNS.  One launch, scale_logp's shape: 256 threads, one wave per row, rows over a grid-stride loop, lane t takes columns
+// HOW IT RUNS.  One launch in wave_rows' shape (common.hpp): 256 threads, one wave per row, rows over a grid-stride loop, lane t takes columns
 // t, t + 64, ...  The members travel BY VALUE in the kernel's argument struct (K <= 32: no device table, nothing uploaded); at its
 // start lane k of every wave picks member k's pointer, stride, beta and weight out of it with 32 STATIC selects, and per row it
 // keeps member k's row constants (a_k, the log1p term, the arg-max) -- the loops over k then read lane k with v_readlane, k being
@@ -29,16 +29,12 @@
 #include <limits.h>
 #include <math.h>
 
-#include <algorithm>
-
 #include "common.hpp"
 #include "launch.hpp"
 #include "logp_row.hpp"
 #include "spans.hpp"
 
 namespace slnlp {
-
-constexpr int ENS_MAX_BLOCKS = 2048;   // x 4 rows: more than 8192 rows wrap the stride loop
 
 struct EnsMembers {                    // by value in the kernel arguments: 1 KiB
     const float* z[SLNLP_ENSEMBLE_MAX_MEMBERS];
@@ -75,6 +71,7 @@ __device__ __forceinline__ double ens_log_term(const EnsLane& me, int K, int j) 
 
 __device__ __forceinline__ void ensemble_rows_body(EnsMembers m, int K, int N, int V, int mode, float* __restrict__ out, long ld_out,
                                                    double* __restrict__ rows) {
+    // (wave_rows' loop, written out: through the helper this kernel's register counts change -- profiles/judging_shell_isa.txt)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     const int nwaves = gridDim.x * 4;
@@ -232,8 +229,7 @@ int ensemble_rows(const float* const* logp, const int64_t* ld, const double* con
         }
     }
     SLNLP_CHECK_ARG(!spans_overlap(outs[0], outs[1]), "ensemble_rows: out and rows overlap");
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, ENS_MAX_BLOCKS);
-    return zlaunch(ensemble_rows_kernel, dim3(blocks), 256, 0, st, "ensemble_rows", m, K, (int)N, (int)V, mode, out, (long)ld_out, rows);
+    return zlaunch(ensemble_rows_kernel, dim3(wave_rows_grid(N)), 256, 0, st, "ensemble_rows", m, K, (int)N, (int)V, mode, out, (long)ld_out, rows);
 }
 
 }  // namespace slnlp

@@ -11,7 +11,7 @@
 // over the M rows that hold no NaN and have a finite maximum.  Everything but z itself is fp64.
 //
 // HOW IT RUNS.  The call queues a FIXED sequence of 3 (max_iter + 1) + 2 launches and never waits for the host.  Iteration t:
-//   prior_rows     one wave per row, four rows per block, rows over a grid-stride loop (calibration.hip's shape): lanes stride the
+//   prior_rows     one wave per row, four rows per block, rows over a grid-stride loop (wave_rows, common.hpp): lanes stride the
 //                  columns; the maximum of a and the sum of exp(a - max) are wave reductions in a fixed order; lane 0 writes lse_i
 //                  (NaN for an excluded row) into scratch.  Iteration 0 runs at lw = 0 and keeps its lse_i for the gain.
 //   prior_classes  one block of 256 threads per class c (ranking.hip's grid): thread t adds exp(a_ic - lse_i) over rows t, t + 256,
@@ -37,10 +37,9 @@
 #include <limits.h>
 #include <math.h>
 
-#include <algorithm>
-
 #include "block_reduce.hpp"
 #include "common.hpp"
+#include "fit_state.hpp"
 #include "launch.hpp"
 #include "logp_row.hpp"
 #include "spans.hpp"
@@ -51,30 +50,19 @@
 
 namespace slnlp {
 
-constexpr int PRIOR_MAX_BLOCKS = 2048;                   // x 4 rows: more than 8192 rows wrap the stride loop
 constexpr double PRIOR_FLOOR = 2.2250738585072014e-308;  // 2^-1022: ln of it is finite, so is every lw
-// state: 8 doubles, then 8 int64 (include/slnlp.h)
+// state (fit_state.hpp): this fit's own doubles; FIT_BAD counts the rows that hold a NaN or have no finite maximum
 enum { PRIOR_GAIN = 0, PRIOR_D = 1 };
-enum { PRIOR_REASON = 0, PRIOR_ITERATIONS = 1, PRIOR_ROWS = 2, PRIOR_NAN = 3 };
 // the evaluation a launch belongs to: 0 .. max_iter are the iterations, PRIOR_FINAL the one at the result
 constexpr int PRIOR_FINAL = -1;
-
-// whether iteration `eval` has nothing left to do (iteration 0 initialises the state and the final evaluation always runs:
-// neither reads the flag)
-__device__ __forceinline__ bool prior_settled(const double* state, int eval) {
-    return eval > 0 && ((const int64_t*)(state + 8))[PRIOR_REASON] != 0;
-}
 
 // lse_i at lw (null: lw = 0) for every row, NaN for an excluded one
 __device__ __forceinline__ void prior_rows_body(const float* __restrict__ logp, long ld, int N, int V, const double* __restrict__ beta_dev,
                                                 const double* __restrict__ lw, const double* __restrict__ state,
                                                 double* __restrict__ lse, int eval) {
-    if (prior_settled(state, eval)) return;
+    if (fit_settled(state, eval, 0, PRIOR_FINAL)) return;
     const double beta = beta_dev ? beta_dev[0] : 1.0;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
-    for (long r = wave; r < N; r += nwaves) {            // r: the same in every lane, so every lane reaches the reductions
+    wave_rows(N, [&](long r, int lane) {
         const float* row = logp + r * ld;
         const LogpRowMax m = logp_row_argmax(row, V, lane);
         double amax = -INFINITY;
@@ -84,7 +72,7 @@ __device__ __forceinline__ void prior_rows_body(const float* __restrict__ logp, 
         for (int j = lane; j < V; j += 64) s += exp((beta * (double)row[j] + (lw ? lw[j] : 0.0)) - amax);
         s = wave_sum_d(s);
         if (lane == 0) lse[r] = m.finite ? amax + log(s) : NAN;
-    }
+    });
 }
 SLNLP_ZKERNEL(prior_rows_kernel, 256, prior_rows_body)
 
@@ -92,19 +80,16 @@ SLNLP_ZKERNEL(prior_rows_kernel, 256, prior_rows_body)
 __device__ __forceinline__ void prior_classes_body(const float* __restrict__ logp, long ld, int N, const double* __restrict__ beta_dev,
                                                    const double* __restrict__ lw, const double* __restrict__ state,
                                                    const double* __restrict__ lse, double* __restrict__ S, int eval) {
-    if (prior_settled(state, eval)) return;              // (every thread reads the same flag: the block returns as one)
+    if (fit_settled(state, eval, 0, PRIOR_FINAL)) return;              // (every thread reads the same flag: the block returns as one)
     __shared__ double red[256];
     const double beta = beta_dev ? beta_dev[0] : 1.0;
     const int tid = threadIdx.x;
     const long c = blockIdx.x;
     const double lwc = lw ? lw[c] : 0.0;
-    double s = 0.0;
-    for (long r = tid; r < N; r += 256) {
+    block_sum_rows<1>(&red, tid, N, [&](long r, double* s) {
         const double l = lse[r];
-        if (l == l) s += exp((beta * (double)logp[r * ld + c] + lwc) - l);
-    }
-    red[tid] = s;
-    block_tree<1>(&red, tid, TreeSum{});
+        if (l == l) s[0] += exp((beta * (double)logp[r * ld + c] + lwc) - l);
+    });
     if (tid == 0) S[c] = red[0];
 }
 SLNLP_ZKERNEL(prior_classes_kernel, 256, prior_classes_body)
@@ -113,20 +98,15 @@ SLNLP_ZKERNEL(prior_classes_kernel, 256, prior_classes_body)
 __device__ __forceinline__ void prior_update_body(const double* __restrict__ S, const double* __restrict__ lse0,
                                                   const double* __restrict__ log_source, int N, int V, int max_iter, double tol,
                                                   double* __restrict__ table, double* __restrict__ state, int eval) {
-    if (prior_settled(state, eval)) return;
+    if (fit_settled(state, eval, 0, PRIOR_FINAL)) return;
     __shared__ double red[256];
     __shared__ int bad_red[256];
-    int64_t* q = (int64_t*)(state + 8);
+    int64_t* q = fit_words(state);
     const int tid = threadIdx.x;
-    long M;
+    long M = q[FIT_ROWS];
     if (eval == 0) {                                     // count the rows prior_rows excluded
-        int bad = 0;
-        for (long r = tid; r < N; r += 256) bad += lse0[r] != lse0[r] ? 1 : 0;
-        bad_red[tid] = bad;
-        block_tree<1>(&bad_red, tid, TreeSum{});
+        block_sum_rows<1>(&bad_red, tid, N, [&](long r, int* bad) { bad[0] += lse0[r] != lse0[r] ? 1 : 0; });
         M = (long)N - bad_red[0];
-    } else {
-        M = q[PRIOR_ROWS];
     }
     double* mean = table;
     double* pi = table + V;
@@ -145,20 +125,17 @@ __device__ __forceinline__ void prior_update_body(const double* __restrict__ S, 
     block_tree<1>(&red, tid, [](double m, double o) { return o > m || o != o ? o : m; });   // the larger, or a NaN, wins
     if (tid != 0) return;
     if (eval == 0) {
-        for (int k = 0; k < 8; ++k) state[k] = 0.0;
-        for (int k = 0; k < 8; ++k) q[k] = 0;
-        q[PRIOR_ROWS] = M;
-        q[PRIOR_NAN] = (long)N - M;
+        fit_state_reset(state, M, (long)N - M);
         if (M == 0) {
-            q[PRIOR_REASON] = SLNLP_PRIOR_EMPTY;
+            q[FIT_REASON] = SLNLP_PRIOR_EMPTY;
             return;
         }
     }
     d = red[0];
     state[PRIOR_D] = d;
-    q[PRIOR_ITERATIONS] = eval + 1;
-    if (d <= tol) q[PRIOR_REASON] = SLNLP_PRIOR_TOL;
-    else if (eval == max_iter) q[PRIOR_REASON] = SLNLP_PRIOR_CAP;
+    q[FIT_ITERATIONS] = eval + 1;
+    if (d <= tol) q[FIT_REASON] = SLNLP_PRIOR_TOL;
+    else if (eval == max_iter) q[FIT_REASON] = SLNLP_PRIOR_CAP;
 }
 SLNLP_ZKERNEL(prior_update_kernel, 256, prior_update_body)
 
@@ -167,15 +144,12 @@ __device__ __forceinline__ void prior_gain_body(const double* __restrict__ lse, 
                                                 double* __restrict__ state) {
     __shared__ double red[256];
     const int tid = threadIdx.x;
-    double s = 0.0;
-    for (long r = tid; r < N; r += 256) {
+    block_sum_rows<1>(&red, tid, N, [&](long r, double* s) {
         const double l0 = lse0[r];
-        if (l0 == l0) s += lse[r] - l0;
-    }
-    red[tid] = s;
-    block_tree<1>(&red, tid, TreeSum{});
+        if (l0 == l0) s[0] += lse[r] - l0;
+    });
     if (tid != 0) return;
-    const int64_t M = ((const int64_t*)(state + 8))[PRIOR_ROWS];
+    const int64_t M = fit_words(state)[FIT_ROWS];
     state[PRIOR_GAIN] = M > 0 ? red[0] / (double)M : 0.0;
 }
 SLNLP_ZKERNEL(prior_gain_kernel, 256, prior_gain_body)
@@ -184,10 +158,7 @@ SLNLP_ZKERNEL(prior_gain_kernel, 256, prior_gain_body)
 __device__ __forceinline__ void shift_logp_body(const float* logp, long ld, int N, int V, const double* __restrict__ beta_dev,
                                                 const double* __restrict__ lw, float* out, long ld_out) {
     const double beta = beta_dev ? beta_dev[0] : 1.0;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
-    for (long r = wave; r < N; r += nwaves) {
+    wave_rows(N, [&](long r, int lane) {
         const float* row = logp + r * ld;
         float* dst = out + r * ld_out;
         const LogpRowMax m = logp_row_argmax(row, V, lane);
@@ -204,7 +175,7 @@ __device__ __forceinline__ void shift_logp_body(const float* logp, long ld, int 
         const bool ok = m.finite && fabs(amax) < INFINITY;           // a row without a softmax: NaN in every column
         for (int j = lane; j < V; j += 64)                           // re-read, then stored, by its own lane
             dst[j] = ok ? (float)(((beta * (double)row[j] + lw[j]) - amax) - l) : NAN;
-    }
+    });
 }
 SLNLP_ZKERNEL(shift_logp_kernel, 256, shift_logp_body)
 
@@ -226,8 +197,7 @@ int fit_priors(const float* logp, int64_t ld, int64_t N, int64_t V, const double
     SLNLP_CHECK_ARG(max_iter >= 0 && max_iter <= SLNLP_PRIOR_MAX_ITER, "fit_priors: max_iter=%d outside 0..%d", max_iter, SLNLP_PRIOR_MAX_ITER);
     SLNLP_CHECK_ARG(tol >= 0.0 && tol < INFINITY, "fit_priors: tol=%g is not a finite number >= 0", tol);
     const size_t need = prior_scratch_bytes(N, V);
-    SLNLP_CHECK_ARG(scratch_bytes >= 0 && (size_t)scratch_bytes >= need, "fit_priors: scratch of %ld bytes is too small, %ld rows of %ld classes need %ld",
-                    (long)scratch_bytes, (long)N, (long)V, (long)need);
+    SLNLP_TRY(check_scratch("fit_priors", scratch, scratch_bytes, need, N, V, 0));
     SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0, "fit_priors: misaligned pointer (logp: 4 bytes)");
     SLNLP_CHECK_ARG((((uintptr_t)beta_dev | (uintptr_t)log_source | (uintptr_t)table | (uintptr_t)state | (uintptr_t)scratch) & 7) == 0,
                     "fit_priors: misaligned pointer (beta, log_source, table, state, scratch: 8 bytes)");
@@ -238,7 +208,7 @@ int fit_priors(const float* logp, int64_t ld, int64_t N, int64_t V, const double
     double* lse = lse0 + N;
     double* S = lse + N;
     const double* lw = table + 2 * V;
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, PRIOR_MAX_BLOCKS);
+    const int blocks = wave_rows_grid(N);
     for (int t = 0; t <= max_iter; ++t) {
         SLNLP_TRY(zlaunch(prior_rows_kernel, dim3(blocks), 256, 0, st, "fit_priors_rows", logp, (long)ld, (int)N, (int)V, beta_dev,
                           t == 0 ? (const double*)nullptr : lw, (const double*)state, t == 0 ? lse0 : lse, t));
@@ -255,19 +225,15 @@ int fit_priors(const float* logp, int64_t ld, int64_t N, int64_t V, const double
 int shift_logp(const float* logp, int64_t ld, int64_t N, int64_t V, const double* beta_dev, const double* log_w, float* out,
                int64_t ld_out, hipStream_t st) {
     SLNLP_CHECK_ARG(logp && log_w && out, "shift_logp: null pointer");
-    Span z;
+    Span z, o;
     SLNLP_TRY(check_logp_matrix("shift_logp", logp, N, INT_MAX, V, INT_MAX, ld, &z));
-    SLNLP_CHECK_ARG(ld_out >= V, "shift_logp: ld_out=%ld is less than V=%ld", (long)ld_out, (long)V);
-    SLNLP_CHECK_ARG(ld_out <= INT64_MAX / 8 / N, "shift_logp: ld_out=%ld times N=%ld is no addressable matrix", (long)ld_out, (long)N);
+    SLNLP_TRY(check_out_matrix("shift_logp", out, N, "N", V, ld_out, &o));
     SLNLP_CHECK_ARG((((uintptr_t)logp | (uintptr_t)out) & 3) == 0 && (((uintptr_t)beta_dev | (uintptr_t)log_w) & 7) == 0,
                     "shift_logp: misaligned pointer (logp, out: 4 bytes; beta, log_w: 8 bytes)");
-    const Span o = {out, matrix_bytes(N, ld_out, V), "out"};
-    const bool in_place = (const float*)out == logp && ld_out == ld;
-    SLNLP_CHECK_ARG(in_place || !spans_overlap(o, z),
-                    "shift_logp: out overlaps logp without being logp itself (in place means the same pointer and the same row stride)");
+    SLNLP_TRY(check_in_place("shift_logp", o, ld_out, z, ld));
     SLNLP_CHECK_ARG(!spans_overlap(o, Span{beta_dev, 8, "beta"}) && !spans_overlap(o, Span{log_w, (size_t)V * 8, "log_w"}),
                     "shift_logp: out overlaps beta or log_w");
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, PRIOR_MAX_BLOCKS);
+    const int blocks = wave_rows_grid(N);
     return zlaunch(shift_logp_kernel, dim3(blocks), 256, 0, st, "shift_logp", logp, (long)ld, (int)N, (int)V, beta_dev, log_w, out, (long)ld_out);
 }
 

@@ -16,7 +16,7 @@
 // three terms are NaN).  table [B + 1, 4]: row b < B = (count, sum conf, sum correct, 0) over the scored rows of bin b; row B =
 // (sum brier, sum nll, n_bad_label, n_nan) -- the two sums over the scored rows only.  tests/reliability_ref.py restates both.
 //
-// HOW IT RUNS.  Two launches, no atomics, nothing that depends on the grid.  reliability_rows: score.hip's / fit_rows' shape -- one
+// HOW IT RUNS.  Two launches, no atomics, nothing that depends on the grid.  reliability_rows: wave_rows' shape (common.hpp) -- one
 // wave per row, four rows per block, rows over a grid-stride loop, lanes stride the columns; the arg-max and the three sums are
 // wave reductions in the fixed DPP / v_readlane order (common.hpp); lane 0 stores the row's four doubles; no LDS.
 // reliability_table: B + 1 blocks of 256 threads, block b reduces bin b and block B the totals: thread t adds rows t, t + 256, ...
@@ -25,8 +25,6 @@
 #include <limits.h>
 #include <math.h>
 
-#include <algorithm>
-
 #include "common.hpp"
 #include "launch.hpp"
 #include "logp_row.hpp"
@@ -34,11 +32,11 @@
 
 namespace slnlp {
 
-constexpr int REL_MAX_BLOCKS = 2048;   // x 4 rows: more than 8192 rows wrap the stride loop
-
 __device__ __forceinline__ void reliability_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
                                                       int bins, const double* __restrict__ beta_dev, double* __restrict__ rows) {
     const double beta = beta_dev ? beta_dev[0] : 1.0;
+    // (wave_rows' loop, written out: through the helper two of six figures timed above the parent's spread, twice, with no cause
+    // in the instruction stream -- profiles/judging_shell_ab.json)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     const int nwaves = gridDim.x * 4;
@@ -112,7 +110,7 @@ int reliability_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N,
     const Span in[3] = {z, {y, n * 8, "y"}, {beta_dev, 8, "beta"}};
     const Span out[2] = {{rows, n * 32, "rows"}, {table, ((size_t)bins + 1) * 32, "table"}};
     SLNLP_TRY(check_no_overlap("reliability_rows", out, in));
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, REL_MAX_BLOCKS);
+    const int blocks = wave_rows_grid(N);
     SLNLP_TRY(zlaunch(reliability_rows_kernel, dim3(blocks), 256, 0, st, "reliability_rows", logp, (long)ld, y, (int)N, (int)V, bins, beta_dev,
                       rows));
     return zlaunch(reliability_table_kernel, dim3(bins + 1), 256, 0, st, "reliability_table", (const double*)rows, (int)N, bins, table);

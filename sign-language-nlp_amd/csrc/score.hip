@@ -14,7 +14,7 @@
 // A label outside [0, V) is never used as an index: its row gets picked = NaN and rank = V, counts as one n_bad and enters
 // pred_sum only.  tests/score_ref.py is the numpy restatement.
 //
-// One wave per row, four rows per block, rows over a grid-stride loop: lanes stride the columns (coalesced), v is read first,
+// One wave per row, four rows per block, rows over a grid-stride loop (wave_rows, common.hpp): lanes stride the columns (coalesced), v is read first,
 // so the maximum, its index and the two rank counts come out of the same pass.  The wave-level combines are DPP exchanges and
 // v_readlane over all 64 lanes (common.hpp); the arg-max rule -- larger value wins, equal values: lower index, NaN beats all -- is
 // a total order on (value, index), so every lane of a pair computes the same winner.  The class counts are integer atomics, one
@@ -30,7 +30,7 @@
 
 namespace slnlp {
 
-constexpr int SCORE_MAX_BLOCKS = 2048;  // x 4 rows: epochs past 8192 rows wrap the stride loop
+constexpr int SCORE_ZERO_MAX_BLOCKS = 2048;  // x 256 entries: more counts wrap score_zero's stride loop
 
 // (the arg-max order score_beats, its wave reduction wave_best and wave_sum_i: common.hpp)
 
@@ -42,11 +42,8 @@ SLNLP_ZKERNEL(score_zero_kernel, 256, score_zero_body)
 __device__ __forceinline__ void score_rows_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
                                                 int* __restrict__ pred, float* __restrict__ picked, int* __restrict__ rank,
                                                 int* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int nwaves = gridDim.x * 4;
     const float qnan = __builtin_bit_cast(float, 0x7fc00000);
-    for (long r = wave; r < N; r += nwaves) {
+    wave_rows(N, [&](long r, int lane) {
         const float* row = logp + r * ld;
         const int64_t label = y[r];
         const bool ok = label >= 0 && label < V;
@@ -76,7 +73,7 @@ __device__ __forceinline__ void score_rows_body(const float* __restrict__ logp, 
                 atomicAdd(&counts[3L * V], 1);
             }
         }
-    }
+    });
 }
 SLNLP_ZKERNEL(score_rows_kernel, 256, score_rows_body)
 
@@ -92,10 +89,9 @@ int score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V
     const Span in[2] = {z, {y, n * 8, "y"}};
     const Span out[4] = {{pred, n * 4, "pred"}, {picked, n * 4, "picked"}, {rank, n * 4, "rank"}, {counts, n_counts * 4, "counts"}};
     SLNLP_TRY(check_no_overlap("score_rows", out, in));
-    const int zero_blocks = (int)std::min<size_t>((n_counts + 255) / 256, SCORE_MAX_BLOCKS);
+    const int zero_blocks = (int)std::min<size_t>((n_counts + 255) / 256, SCORE_ZERO_MAX_BLOCKS);
     SLNLP_TRY(zlaunch(score_zero_kernel, dim3(zero_blocks), 256, 0, st, "score_zero", counts, (int)n_counts));
-    const int blocks = (int)std::min<int64_t>((N + 3) / 4, SCORE_MAX_BLOCKS);
-    return zlaunch(score_rows_kernel, dim3(blocks), 256, 0, st, "score_rows", logp, (long)ld, y, (int)N, V, pred, picked, rank, counts);
+    return zlaunch(score_rows_kernel, dim3(wave_rows_grid(N)), 256, 0, st, "score_rows", logp, (long)ld, y, (int)N, V, pred, picked, rank, counts);
 }
 
 }  // namespace slnlp

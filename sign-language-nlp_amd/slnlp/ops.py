@@ -456,8 +456,8 @@ def score_rows(logp, y, out=None):
             out = score_buffers(N, V, logp.device)
         pred, picked, rank, counts = out
         for t, dt, n in ((pred, torch.int32, N), (picked, torch.float32, N), (rank, torch.int32, N), (counts, torch.int32, 3 * V + 1)):
-            if not (t.device == logp.device and t.dtype == dt and t.dim() == 1 and t.numel() == n and t.is_contiguous()):
-                raise ValueError(f"score_rows: out must be (int32 [{N}], float32 [{N}], int32 [{N}], int32 [{3 * V + 1}]) on {logp.device}")
+            _tensor("score_rows", "out", t, logp.device, dt, n,
+                    f"(int32 [{N}], float32 [{N}], int32 [{N}], int32 [{3 * V + 1}]) on {logp.device}")
         check(load().slnlp_score_rows(ptr(logp), ld, ptr(y), N, V, ptr(pred), ptr(picked), ptr(rank), ptr(counts), stream_ptr()),
               "score_rows")
     return out
@@ -474,15 +474,38 @@ def _logp_matrix(what, logp):
     return N, V, (int(logp.stride(0)) if N > 1 else max(V, int(logp.stride(0))))
 
 
+def _tensor(what, name, t, device, dtype, shape, must_be=None):
+    """The tensor contract of the judging wrappers: ``t`` on ``device``, of ``dtype``, contiguous, of ``shape`` -- a tuple, an int
+    n for (n,), None for one dimension of any length.  ``must_be``: the message's wording of it where that is not the default."""
+    dims = shape if isinstance(shape, tuple) else (shape,)
+    if not (t.device == device and t.dtype == dtype and t.is_contiguous() and (t.dim() == 1 if shape is None else tuple(t.shape) == dims)):
+        text = must_be or f"a contiguous {str(dtype)[6:]} [{', '.join(map(str, dims))}] tensor on {device}"
+        raise ValueError(f"{what}: {name} must be {text}")
+
+
 def _labels(what, y, device, N, or_none=""):
-    if not (y.device == device and y.dtype == torch.int64 and y.dim() == 1 and y.numel() == N and y.is_contiguous()):
-        raise ValueError(f"{what}: y must be a contiguous int64 [{N}] tensor on {device}{or_none}")
+    _tensor(what, "y", y, device, torch.int64, N, f"a contiguous int64 [{N}] tensor on {device}{or_none}")
 
 
 def _cal_state(what, state, device):
-    if not (state.device == device and state.dtype == torch.float64 and state.dim() == 1 and state.numel() == CAL_STATE_DOUBLES
-            and state.is_contiguous()):
-        raise ValueError(f"{what}: state must be a contiguous float64 [{CAL_STATE_DOUBLES}] tensor on {device}")
+    _tensor(what, "state", state, device, torch.float64, CAL_STATE_DOUBLES)
+
+
+def _scratch(what, scratch, device, doubles=None):
+    """A fit's scratch: float64, one dimension (the library checks its length; ``doubles``: what the message says it takes)"""
+    _tensor(what, "scratch", scratch, device, torch.float64, None,
+            f"a contiguous float64 {'' if doubles is None else f'[>= {doubles}] '}tensor on {device}")
+
+
+def _out_like(what, logp, out):
+    """-> (out, its row stride): ``out`` -- None: a new tensor; ``logp`` itself: in place -- as a float32 matrix of ``logp``'s shape
+    on its device"""
+    N, V = int(logp.shape[0]), int(logp.shape[1])
+    if out is None:
+        out = torch.empty(N, V, dtype=torch.float32, device=logp.device)
+    if out.device != logp.device or tuple(out.shape) != (N, V):
+        raise ValueError(f"{what}: out must be a float32 [{N}, {V}] tensor on {logp.device}")
+    return out, _logp_matrix(f"{what} (out)", out)[2]
 
 
 def fit_temperature(logp, y, state=None, scratch=None):
@@ -499,8 +522,7 @@ def fit_temperature(logp, y, state=None, scratch=None):
         _cal_state("fit_temperature", state, logp.device)
         if scratch is None:
             scratch = torch.empty(4 * N, dtype=torch.float64, device=logp.device)
-        if not (scratch.device == logp.device and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.is_contiguous()):
-            raise ValueError(f"fit_temperature: scratch must be a contiguous float64 [>= {4 * N}] tensor on {logp.device}")
+        _scratch("fit_temperature", scratch, logp.device, 4 * N)
         check(load().slnlp_fit_temperature(ptr(logp), ld, ptr(y), N, V, ptr(state), ptr(scratch), scratch.numel() * 8, stream_ptr()),
               "fit_temperature")
     return state
@@ -555,8 +577,7 @@ def fit_bias_temperature(logp, y, bias_sd=2.0, tol=1e-10, state=None, bias=None,
             need = load().slnlp_fit_bias_temperature_scratch_bytes(N, V)
             check(0 if need >= 0 else 1, "fit_bias_temperature_scratch_bytes")
             scratch = torch.empty(need // 8, dtype=torch.float64, device=logp.device)
-        if not (scratch.device == logp.device and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.is_contiguous()):
-            raise ValueError(f"fit_bias_temperature: scratch must be a contiguous float64 tensor on {logp.device}")
+        _scratch("fit_bias_temperature", scratch, logp.device)
         check(load().slnlp_fit_bias_temperature(ptr(logp), ld, ptr(y), N, V, bias_sd, tol, ptr(state), ptr(bias), ptr(scratch),
                                                 scratch.numel() * 8, stream_ptr()), "fit_bias_temperature")
     return state, bias
@@ -589,11 +610,7 @@ def scale_logp(logp, state, out=None):
     N, V, ld = _logp_matrix("scale_logp", logp)
     _cal_state("scale_logp", state, logp.device)
     with torch.cuda.device(logp.device):
-        if out is None:
-            out = torch.empty(N, V, dtype=torch.float32, device=logp.device)
-        if out.device != logp.device or tuple(out.shape) != (N, V):
-            raise ValueError(f"scale_logp: out must be a float32 [{N}, {V}] tensor on {logp.device}")
-        _, _, ld_out = _logp_matrix("scale_logp (out)", out)
+        out, ld_out = _out_like("scale_logp", logp, out)
         check(load().slnlp_scale_logp(ptr(logp), ld, N, V, ptr(state), ptr(out), ld_out, stream_ptr()), "scale_logp")
     return out
 
@@ -602,8 +619,7 @@ PRIOR_STATE_DOUBLES = 16                     # SLNLP_PRIOR_STATE_BYTES / 8: eigh
 
 
 def _prior_vector(what, name, t, device, V):
-    if not (t.device == device and t.dtype == torch.float64 and t.dim() == 1 and t.numel() == V and t.is_contiguous()):
-        raise ValueError(f"{what}: {name} must be a contiguous float64 [{V}] tensor on {device}")
+    _tensor(what, name, t, device, torch.float64, V)
 
 
 def fit_priors(logp, log_source, state=None, max_iter=200, tol=1e-6, out=None, scratch=None):
@@ -629,11 +645,9 @@ def fit_priors(logp, log_source, state=None, max_iter=200, tol=1e-6, out=None, s
         _prior_vector("fit_priors", "out", out, logp.device, 3 * V + PRIOR_STATE_DOUBLES)
         if scratch is None:
             scratch = torch.empty(2 * N + V, dtype=torch.float64, device=logp.device)
-        if not (scratch.device == logp.device and scratch.dtype == torch.float64 and scratch.dim() == 1 and scratch.is_contiguous()):
-            raise ValueError(f"fit_priors: scratch must be a contiguous float64 [>= {2 * N + V}] tensor on {logp.device}")
-        check(load().slnlp_fit_priors(ptr(logp), ld, N, V, ptr(state) if state is not None else None, ptr(log_source), max_iter,
-                                      float(tol), ptr(out), ptr(out[3 * V:]), ptr(scratch), scratch.numel() * 8, stream_ptr()),
-              "fit_priors")
+        _scratch("fit_priors", scratch, logp.device, 2 * N + V)
+        check(load().slnlp_fit_priors(ptr(logp), ld, N, V, ptr(state), ptr(log_source), max_iter, float(tol), ptr(out), ptr(out[3 * V:]),
+                                      ptr(scratch), scratch.numel() * 8, stream_ptr()), "fit_priors")
     return out
 
 
@@ -659,13 +673,8 @@ def shift_logp(logp, log_w, state=None, out=None):
     if state is not None:
         _cal_state("shift_logp", state, logp.device)
     with torch.cuda.device(logp.device):
-        if out is None:
-            out = torch.empty(N, V, dtype=torch.float32, device=logp.device)
-        if out.device != logp.device or tuple(out.shape) != (N, V):
-            raise ValueError(f"shift_logp: out must be a float32 [{N}, {V}] tensor on {logp.device}")
-        _, _, ld_out = _logp_matrix("shift_logp (out)", out)
-        check(load().slnlp_shift_logp(ptr(logp), ld, N, V, ptr(state) if state is not None else None, ptr(log_w), ptr(out), ld_out,
-                                      stream_ptr()), "shift_logp")
+        out, ld_out = _out_like("shift_logp", logp, out)
+        check(load().slnlp_shift_logp(ptr(logp), ld, N, V, ptr(state), ptr(log_w), ptr(out), ld_out, stream_ptr()), "shift_logp")
     return out
 
 
@@ -695,10 +704,9 @@ def reliability_rows(logp, y, bins=15, state=None, out=None):
             out = reliability_buffers(N, bins, logp.device)
         rows, table = out
         for t, shape in ((rows, (N, 4)), (table, (bins + 1, 4))):
-            if not (t.device == logp.device and t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f"reliability_rows: out must be (float64 [{N}, 4], float64 [{bins + 1}, 4]) on {logp.device}")
-        check(load().slnlp_reliability_rows(ptr(logp), ld, ptr(y), N, V, bins, ptr(state) if state is not None else None, ptr(rows),
-                                            ptr(table), stream_ptr()), "reliability_rows")
+            _tensor("reliability_rows", "out", t, logp.device, torch.float64, shape, f"(float64 [{N}, 4], float64 [{bins + 1}, 4]) on {logp.device}")
+        check(load().slnlp_reliability_rows(ptr(logp), ld, ptr(y), N, V, bins, ptr(state), ptr(rows), ptr(table), stream_ptr()),
+              "reliability_rows")
     return out
 
 
@@ -734,13 +742,11 @@ def ranking_rows(logp, y, out=None, per_row=True):
         if out is None:
             out = ranking_buffers(N, V, logp.device, per_row=bool(per_row))
         rows, table = out
-        ok = table.device == logp.device and table.dtype == torch.float64 and tuple(table.shape) == (V + 1, 4) and table.is_contiguous()
+        must_be = f"(int32 [{N}, 4] or None, float64 [{V + 1}, 4]) on {logp.device}"
+        _tensor("ranking_rows", "out", table, logp.device, torch.float64, (V + 1, 4), must_be)
         if rows is not None:
-            ok = ok and rows.device == logp.device and rows.dtype == torch.int32 and tuple(rows.shape) == (N, 4) and rows.is_contiguous()
-        if not ok:
-            raise ValueError(f"ranking_rows: out must be (int32 [{N}, 4] or None, float64 [{V + 1}, 4]) on {logp.device}")
-        check(load().slnlp_ranking_rows(ptr(logp), ld, ptr(y), N, V, ptr(rows) if rows is not None else None, ptr(table), stream_ptr()),
-              "ranking_rows")
+            _tensor("ranking_rows", "out", rows, logp.device, torch.int32, (N, 4), must_be)
+        check(load().slnlp_ranking_rows(ptr(logp), ld, ptr(y), N, V, ptr(rows), ptr(table), stream_ptr()), "ranking_rows")
     return out
 
 
@@ -790,8 +796,7 @@ def _conformal_buf(what, buf, logp_or_device, N, V):
 
 
 def _conformal_state(what, name, t, device):
-    if not (t.device == device and t.dtype == torch.float64 and t.dim() == 1 and t.numel() == 4 and t.is_contiguous()):
-        raise ValueError(f"{what}: {name} must be a contiguous float64 [4] tensor on {device}")
+    _tensor(what, name, t, device, torch.float64, 4)
 
 
 def conformal_rows(logp, y=None, buf=None, *, method="aps", lam=0.0, k_reg=0, randomized=True, seed=0, draw=0, state=None, qhat=None):
@@ -823,10 +828,9 @@ def conformal_rows(logp, y=None, buf=None, *, method="aps", lam=0.0, k_reg=0, ra
             buf = conformal_buffers(N, V, logp.device, sets=qhat is not None)
         _conformal_buf(what, buf, logp.device, N, V)
         sets = buf["sets"] if qhat is not None else None
-        check(load().slnlp_conformal_rows(ptr(logp), ld, ptr(y) if y is not None else None, N, V, ptr(state) if state is not None else None,
-                                          _lib.CONFORMAL_METHODS[method], float(lam), k_reg, 1 if randomized else 0, seed, draw,
-                                          ptr(qhat) if qhat is not None else None, ptr(buf["score"]) if y is not None else None,
-                                          ptr(buf["rows"]), ptr(sets) if sets is not None else None, stream_ptr()), what)
+        check(load().slnlp_conformal_rows(ptr(logp), ld, ptr(y), N, V, ptr(state), _lib.CONFORMAL_METHODS[method], float(lam), k_reg,
+                                          1 if randomized else 0, seed, draw, ptr(qhat), ptr(buf["score"]) if y is not None else None,
+                                          ptr(buf["rows"]), ptr(sets), stream_ptr()), what)
     return buf
 
 
@@ -933,9 +937,8 @@ def selective_rows(logp, y=None, buf=None, *, score="max_prob", state=None, tau=
         if buf is None:
             buf = selective_buffers(N, logp.device)
         _selective_buf(what, buf, logp.device, N)
-        check(load().slnlp_selective_rows(ptr(logp), ld, ptr(y) if y is not None else None, N, V, _lib.SEL_SCORES[score],
-                                          ptr(state) if state is not None else None, ptr(tau) if tau is not None else None,
-                                          ptr(buf["kappa"]), ptr(buf["rows"]), stream_ptr()), what)
+        check(load().slnlp_selective_rows(ptr(logp), ld, ptr(y), N, V, _lib.SEL_SCORES[score], ptr(state), ptr(tau), ptr(buf["kappa"]),
+                                          ptr(buf["rows"]), stream_ptr()), what)
     return buf
 
 
@@ -1070,10 +1073,8 @@ def topk_rows(logp, k, state=None, out=None):
             out = topk_buffers(N, k, logp.device)
         idx, prob = out
         for t, dt in ((idx, torch.int32), (prob, torch.float64)):
-            if not (t.device == logp.device and t.dtype == dt and tuple(t.shape) == (N, k) and t.is_contiguous()):
-                raise ValueError(f"topk_rows: out must be (int32 [{N}, {k}], float64 [{N}, {k}]) on {logp.device}")
-        check(load().slnlp_topk_rows(ptr(logp), ld, N, V, k, ptr(state) if state is not None else None, ptr(idx), ptr(prob),
-                                     stream_ptr()), "topk_rows")
+            _tensor("topk_rows", "out", t, logp.device, dt, (N, k), f"(int32 [{N}, {k}], float64 [{N}, {k}]) on {logp.device}")
+        check(load().slnlp_topk_rows(ptr(logp), ld, N, V, k, ptr(state), ptr(idx), ptr(prob), stream_ptr()), "topk_rows")
     return out
 
 
@@ -1092,8 +1093,7 @@ def confusion_matrix(pred, y, V, out=None):
     with torch.cuda.device(pred.device):
         if out is None:
             out = torch.empty(V * V + 1, dtype=torch.int32, device=pred.device)
-        if not (out.device == pred.device and out.dtype == torch.int32 and out.dim() == 1 and out.numel() == V * V + 1 and out.is_contiguous()):
-            raise ValueError(f"confusion_matrix: out must be a contiguous int32 [{V * V + 1}] tensor on {pred.device}")
+        _tensor("confusion_matrix", "out", out, pred.device, torch.int32, V * V + 1)
         check(load().slnlp_confusion_matrix(ptr(pred), ptr(y), N, V, ptr(out), stream_ptr()), "confusion_matrix")
     return out
 
@@ -1114,12 +1114,10 @@ def confusion_pairs(counts, V, M, out=None, work=None):
     with torch.cuda.device(counts.device):
         if out is None:
             out = torch.empty(M, 3, dtype=torch.int32, device=counts.device)
-        if not (out.device == counts.device and out.dtype == torch.int32 and tuple(out.shape) == (M, 3) and out.is_contiguous()):
-            raise ValueError(f"confusion_pairs: out must be a contiguous int32 [{M}, 3] tensor on {counts.device}")
+        _tensor("confusion_pairs", "out", out, counts.device, torch.int32, (M, 3))
         if work is None:
             work = torch.empty(load().slnlp_confusion_pairs_workspace_bytes(V, M), dtype=torch.uint8, device=counts.device)
-        if not (work.device == counts.device and work.dtype == torch.uint8 and work.dim() == 1 and work.is_contiguous()):
-            raise ValueError(f"confusion_pairs: work must be a contiguous uint8 tensor on {counts.device}")
+        _tensor("confusion_pairs", "work", work, counts.device, torch.uint8, None, f"a contiguous uint8 tensor on {counts.device}")
         check(load().slnlp_confusion_pairs(ptr(counts), V, M, ptr(out), ptr(work), work.numel(), stream_ptr()), "confusion_pairs")
     return out
 
@@ -1182,8 +1180,8 @@ def label_audit_rows(logp, y, buf=None, *, state=None, pairs=20):
             buf = label_audit_buffers(N, V, pairs, logp.device)
         if not (isinstance(buf, dict) and buf.get("shape", (0, 0, 0))[:2] == (N, V) and buf["flat"].device == logp.device):
             raise ValueError(f"{what}: buf must be label_audit_buffers({N}, {V}, pairs, {logp.device!r})")
-        check(load().slnlp_label_audit(ptr(logp), ld, ptr(y), N, V, ptr(state) if state is not None else None, buf["shape"][2],
-                                       ptr(buf["flat"]), buf["flat"].numel() * 4, stream_ptr()), what)
+        check(load().slnlp_label_audit(ptr(logp), ld, ptr(y), N, V, ptr(state), buf["shape"][2], ptr(buf["flat"]),
+                                       buf["flat"].numel() * 4, stream_ptr()), what)
     return buf
 
 
@@ -1217,16 +1215,14 @@ def scatter_logp(logp, rows, out, state=None):
     _lib.require_gpu()
     what = "scatter_logp"
     n, V, ld = _logp_matrix(what, logp)
-    if not (rows.device == logp.device and rows.dtype == torch.int64 and rows.dim() == 1 and rows.numel() == n and rows.is_contiguous()):
-        raise ValueError(f"{what}: rows must be a contiguous int64 [{n}] tensor on {logp.device}")
+    _tensor(what, "rows", rows, logp.device, torch.int64, n)
     if state is not None:
         _cal_state(what, state, logp.device)
     if not (torch.is_tensor(out) and out.device == logp.device and out.dim() == 2 and out.shape[1] == V and out.shape[0] >= 1):
         raise ValueError(f"{what}: out must be a float32 [N_out, {V}] tensor on {logp.device}")
     N_out, _, ld_out = _logp_matrix(what + " (out)", out)
     with torch.cuda.device(logp.device):
-        check(load().slnlp_scatter_logp(ptr(logp), ld, n, V, ptr(state) if state is not None else None, ptr(rows), ptr(out), ld_out, N_out,
-                                        stream_ptr()), what)
+        check(load().slnlp_scatter_logp(ptr(logp), ld, n, V, ptr(state), ptr(rows), ptr(out), ld_out, N_out, stream_ptr()), what)
     return out
 
 
@@ -1278,8 +1274,9 @@ def bootstrap_scores(y, pred, rank, values=None, *, n_classes, top_k=0, replicat
     for name, t in (("pred", pred), ("rank", rank)):
         if t is None and name == "rank" and top_k == 0:
             continue
-        if t is None or not (t.device == y.device and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == N and t.is_contiguous()):
+        if t is None:
             raise ValueError(f"{what}: {name} must be a contiguous int32 [{N}] tensor on {y.device}")
+        _tensor(what, name, t, y.device, torch.int32, N)
     Q, ldv = 0, 0
     if values is not None:
         if not (values.device == y.device and values.dtype == torch.float64 and values.dim() == 2 and values.shape[0] == N
@@ -1293,11 +1290,10 @@ def bootstrap_scores(y, pred, rank, values=None, *, n_classes, top_k=0, replicat
         if out is None:
             out = bootstrap_buffers(B, V, Q, bool(counts), y.device)
         stats, cnt = out
-        ok = stats.device == y.device and stats.dtype == torch.float64 and tuple(stats.shape) == (B, _lib.BOOT_FIXED + Q) and stats.is_contiguous()
+        must_be = f"(float64 [{B}, {_lib.BOOT_FIXED + Q}], int32 [{B}, {3 * V + 1}] or None) on {y.device}"
+        _tensor(what, "out", stats, y.device, torch.float64, (B, _lib.BOOT_FIXED + Q), must_be)
         if cnt is not None:
-            ok = ok and cnt.device == y.device and cnt.dtype == torch.int32 and tuple(cnt.shape) == (B, 3 * V + 1) and cnt.is_contiguous()
-        if not ok:
-            raise ValueError(f"{what}: out must be (float64 [{B}, {_lib.BOOT_FIXED + Q}], int32 [{B}, {3 * V + 1}] or None) on {y.device}")
+            _tensor(what, "out", cnt, y.device, torch.int32, (B, 3 * V + 1), must_be)
         check(load().slnlp_bootstrap_scores(ptr(y), ptr(pred), ptr(rank) if top_k else None, ptr(values), ldv, Q, N, V, top_k, B, seed,
                                             ptr(stats), ptr(cnt), stream_ptr()), what)
     return out
@@ -1389,11 +1385,7 @@ def ensemble_rows(logps, states=None, weights=None, voting="soft", diagnostics=T
         if len(weights) != K or not all(0.0 < w < float("inf") for w in weights):
             raise ValueError(f"{what}: weights={weights!r}, expected {K} finite numbers above 0")
     with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(N, V, dtype=torch.float32, device=dev)
-        if out.device != dev or tuple(out.shape) != (N, V):
-            raise ValueError(f"{what}: out must be a float32 [{N}, {V}] tensor on {dev}")
-        _, _, ld_out = _logp_matrix(f"{what} (out)", out)
+        out, ld_out = _out_like(what, logps[0], out)
         rows = torch.empty(N, 4, dtype=torch.float64, device=dev) if diagnostics else None
         check(load().slnlp_ensemble_rows((C.c_void_p * K)(*[ptr(z) for z in logps]), (C.c_int64 * K)(*lds),
                                          (C.c_void_p * K)(*[ptr(st) for st in states]),

@@ -3,11 +3,14 @@
 build of the library on ONE box: each feature's existing timer (tools/time_reliability.py, time_error_analysis.py, time_conformal.py,
 time_ranking.py, time_selective.py, time_prior_shift.py, time_calibration.py: their own shapes, samples and HIP events) and, for
 the ensemble, HIP events around ``ops.ensemble_rows`` at 4000 x 202 with K = 5 -- every one in a fresh child process, the two
-libraries alternating, `--rounds` times.
+libraries alternating, `--rounds` times.  Three more workloads stand for the kernels that share the wave-per-row loop and the
+queued fits' state (csrc/common.hpp: wave_rows, csrc/fit_state.hpp): `bias_calibration` (tools/time_bias_calibration.py: the whole
+queued fit), `label_audit` (tools/time_label_audit.py: the audit's eight launches, its joint stages, scatter_logp and scale_logp)
+and `epoch_scoring` (tools/time_epoch_scoring.py: the wall clock of an epoch end on score_rows, in microseconds like the rest).
 
     python tools/ab_logp_row.py --variant parent [--rounds 5] [--workloads ranking selective ...] [--out profiles/logp_row_ab.json]
         parent = lib/libslnlp_probeparent.so (make VARIANT=parent in a checkout of the old tree)
-        --workloads: a subset of the eight (default: all)
+        --workloads: a subset of the eleven (default: all)
 
 Per figure (median microseconds of one child): every round's value for both builds, the parent's min..max over its rounds, the new
 build's median over its rounds and whether that lies inside the parent's spread -- the only yardstick there is for kernels nobody
@@ -23,7 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "sign-language-nlp_amd"), os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
-WORKLOADS = ("reliability", "topk", "conformal", "ensemble", "ranking", "selective", "prior_shift", "calibration")
+WORKLOADS = ("reliability", "topk", "conformal", "ensemble", "ranking", "selective", "prior_shift", "calibration", "bias_calibration",
+             "label_audit", "epoch_scoring")
 
 
 def child(workload):
@@ -65,6 +69,23 @@ def child(workload):
     if workload == "calibration":
         import time_calibration as t
         return {f"{k}_{N}x{V}": t.time_shape(N, V)[k]["median_us"] for N, V in t.SHAPES for k in ("fit_temperature",)}
+    if workload == "bias_calibration":
+        import time_bias_calibration as t
+        return {f"fit_bias_temperature_{N}x{V}": t.time_shape(N, V)["fit_bias_temperature"]["median_us"] for N, V in t.SHAPES}
+    if workload == "label_audit":
+        import time_label_audit as t
+        out = {}
+        for N in t.SIZES:
+            res = t.time_size(N)
+            out.update({f"label_audit_{k}_{N}x{t.V}": res[k]["median_us"] for k in ("kernel", "kernel_batched", "joint_stages")})
+        out.update({k: v["median_us"] for k, v in t.time_scatter().items() if isinstance(v, dict)})
+        return out
+    if workload == "epoch_scoring":
+        import time_epoch_scoring as t
+        from slnlp.data import synthetic_dataset
+        ds = synthetic_dataset(t.ROWS, seq_len=12, src_vocab=64, n_labels=t.CLASSES, seed=6, min_len=3)
+        return {f"end_epoch_{name}": 1e3 * t.time_case(ds, k, scoring)["after"]["median_ms"]
+                for name, k, scoring in (("lockstep15_five_names", 15, t.FIVE), ("solo_macro_names", 1, t.MACRO))}
     from slnlp import ops
     from time_error_analysis import make_logp, timed
     zs = [make_logp(4000, 202, 1 + k)[0] for k in range(5)]
@@ -101,19 +122,20 @@ def main():
                     sys.exit(f"ab_logp_row: {wl} with {lib or 'the product library'} failed ({got.returncode}):\n{got.stderr[-2000:]}")
                 for k, v in json.loads(got.stdout.strip().splitlines()[-1]).items():
                     us.setdefault(k, {"parent": [], "new": []})["parent" if lib else "new"].append(round(v, 3))
-                print(f"round {r} {wl:12s} {lib or 'new'}", flush=True)
+                print(f"round {r} {wl:16s} {lib or 'new'}", flush=True)
+        for s in us.values():
+            s.update(parent_min=min(s["parent"]), parent_max=max(s["parent"]), parent_median=statistics.median(s["parent"]),
+                     new_median=statistics.median(s["new"]))
+            s["new_median_within_parent_spread"] = s["parent_min"] <= s["new_median"] <= s["parent_max"]
+        if a.out:                                            # after every round: a run that is cut short leaves the rounds it finished
+            command = f"python tools/ab_logp_row.py --variant {a.variant} --rounds {a.rounds} --workloads {' '.join(a.workloads)}"
+            with open(a.out, "w") as f:
+                json.dump({"command": command, "rounds": r + 1,
+                           "unit": "us: the median of one fresh process's samples, per round", "figures": us}, f, indent=1)
+                f.write("\n")
     for k, s in us.items():
-        s.update(parent_min=min(s["parent"]), parent_max=max(s["parent"]), parent_median=statistics.median(s["parent"]),
-                 new_median=statistics.median(s["new"]))
-        s["new_median_within_parent_spread"] = s["parent_min"] <= s["new_median"] <= s["parent_max"]
         print(f"{k:44s} parent {s['parent_min']:9.2f} .. {s['parent_max']:9.2f} (median {s['parent_median']:9.2f})   new median {s['new_median']:9.2f}"
               f"   {'within' if s['new_median_within_parent_spread'] else 'below' if s['new_median'] < s['parent_min'] else 'ABOVE'}")
-    if a.out:
-        command = f"python tools/ab_logp_row.py --variant {a.variant} --rounds {a.rounds} --workloads {' '.join(a.workloads)}"
-        with open(a.out, "w") as f:
-            json.dump({"command": command, "rounds": a.rounds,
-                       "unit": "us: the median of one fresh process's samples, per round", "figures": us}, f, indent=1)
-            f.write("\n")
     return 0
 
 

@@ -8,7 +8,7 @@ Per kernel (matched by substring of the mangled name; a name that matches severa
 base name, e.g. sgd_kernel does not match sgd_groups_kernel):
   (a) resources: next_free_vgpr / next_free_sgpr / group_segment_fixed_size / private_segment_fixed_size / scratch lines;
   (b) the instruction stream between the kernel's label and the function's end (every exit, not only the first s_endpgm),
-      `.LBB<n>_<k>` function numbers normalised;
+      `.LBB<n>_<k>` labels renamed by the order in which the kernel defines them;
   (c) the multiset of opcodes.
 Exit status 0: (a) equal for every kernel; 1 otherwise.  A differing stream with equal resources is reported, not an error.
 """
@@ -56,6 +56,13 @@ def parse(path):
             desc = None
         elif desc and s.split()[0] in RES:
             out[desc]["res"][s.split()[0]] = s.split()[1]
+    for v in out.values():                          # a block's number shifts with every block in front of it: name the labels
+        if "stream" in v:                           # of a kernel by the order in which it defines them
+            names = {}
+            for l in v["stream"]:
+                if l.startswith(".LBB_") and l.endswith(":"):
+                    names[l[:-1]] = f".L{len(names)}"
+            v["stream"] = [re.sub(r"\.LBB_\d+", lambda m: names.get(m.group(0), m.group(0)), l) for l in v["stream"]]
     return {k: v for k, v in out.items() if "stream" in v and "res" in v}
 
 

@@ -19,6 +19,15 @@ fit_temperature (state) where beta is absent; selective_rows for each of the thr
 selective_counts with two risk and two coverage levels (counts and table), conformal_quantile (state) and fit_priors (table and
 state, 5 iterations) at every beta.  Then ranking_rows and selective_counts alone at N = 2049 and N = 4133 with V = 3
 (make_chunked): more members than one LDS chunk of 2048 holds, ties across the chunk boundaries.
+
+The kernels that share the wave-per-row loop, the queued fits' state and the row sums (csrc/common.hpp: wave_rows, csrc/fit_state.hpp,
+csrc/block_reduce.hpp) add, on the same grid: fit_bias_temperature (state and bias) where beta is absent; shift_logp out of place and
+in place, label_audit_rows (a zero-filled buffer, all of it but the pairs workspace) and scatter_logp (a zero-filled target of
+N + 2 rows; the row table holds -1 and N + 2 among valid targets where N >= 3) at every beta.  augment_rows and gather_batch (with and
+without an order) run on id matrices of their own (make_ids).  Then ONE block at N = 8197, V = 3, stride 6 (make_wrapped) -- the
+wave-per-row loop has 2048 x 4 waves, so it first wraps at row 8192, a size nothing above reaches: score_rows, reliability_rows,
+topk_rows, scale_logp, shift_logp, scatter_logp, fit_temperature, fit_bias_temperature, fit_priors (max_iter 2), label_audit_rows
+and ensemble_rows (K = 3).  An op that refuses its arguments puts the message in its place (the same for every build).
 """
 import json
 import os
@@ -88,6 +97,71 @@ def make_chunked(torch, N):
     return z, y, kappa, rows
 
 
+def make_wrapped(torch, N=8197):
+    """-> (three logp float32 [N, 3] with row stride 6, y int64 [N]) on the host: more rows than the 8192 waves of a wave-per-row
+    launch.  The special rows sit on both sides of the wrap: a NaN, a +inf maximum, a -inf column, a tie, labels out of range."""
+    g = torch.Generator().manual_seed(8197)
+    zs = []
+    for k in range(3):
+        z = torch.full((N, 6), 7.0)
+        z[:, :3] = torch.log_softmax(3.0 * torch.randn(N, 3, generator=g, dtype=torch.float64), dim=1).float()
+        zs.append(z)
+    y = torch.randint(0, 3, (N,), generator=g)
+    z = zs[0]
+    for base in (3, 8190):                                   # rows 3 .. 7 and 8190 .. 8194
+        z[base, 1] = float("nan")
+        z[base + 1, 2] = float("inf")
+        z[base + 2, 0] = -float("inf")
+        z[base + 3, 0] = z[base + 3, 2] = z[base + 3].max() + 0.25
+        y[base + 4] = (-1, 3)[base > 3]
+    return zs, y
+
+
+def make_ids(torch, n, S, seed):
+    """-> (X int64 [n, S], L int64 [n], y int64 [n]) on the host: token ids, lengths in 0 .. S + 1 (one past the row: clamped), labels"""
+    g = torch.Generator().manual_seed(31 * seed + 7 * n + S)
+    return torch.randint(2, 900, (n, S), generator=g), torch.randint(0, S + 2, (n,), generator=g), torch.randint(0, 9, (n,), generator=g)
+
+
+def attempt(fn):
+    """fn()'s CRC, or the message of the ValueError / RuntimeError with which the op refused its arguments"""
+    try:
+        return fn()
+    except (ValueError, RuntimeError) as e:
+        return f"{type(e).__name__}: {e}"
+
+
+def judged(torch, ops, z, y, state, fresh):
+    """the ops this tool reached last: shift_logp, label_audit_rows, scatter_logp -> {name: crc}.  fresh(): a new device copy of z"""
+    N, V = z.shape
+    dev = z.device
+    log_w = torch.log_softmax(torch.arange(V, dtype=torch.float64, device=dev) / 3.0, dim=0)
+    out = {"shift_logp": attempt(lambda: crc(ops.shift_logp(z, log_w, state)))}
+
+    def in_place():
+        zc = fresh()
+        ops.shift_logp(zc, log_w, state, out=zc)
+        return crc(zc)
+    out["shift_logp_in_place"] = attempt(in_place)
+
+    def audit():
+        buf = ops.label_audit_buffers(N, V, 5, dev)
+        buf["flat"].zero_()
+        ops.label_audit_rows(z, y, buf, state=state)
+        return crc(buf["flat"][:buf["at"]["work"]])
+    out["label_audit_rows"] = attempt(audit)
+
+    def scatter():
+        rows = torch.arange(N - 1, -1, -1, dtype=torch.int64)           # distinct targets, descending
+        if N >= 3:
+            rows[0], rows[N // 2] = -1, N + 2
+        dst = torch.zeros(N + 2, V + 3, dtype=torch.float32, device=dev)[:, :V]
+        ops.scatter_logp(z, rows.to(dev), dst, state=state)
+        return crc(dst)
+    out["scatter_logp"] = attempt(scatter)
+    return out
+
+
 def crc(*tensors):
     c = 0
     for t in tensors:
@@ -126,6 +200,8 @@ def lines():
                     out["score_rows"] = crc(*ops.score_rows(z, y))
                     out["ranking_rows"] = crc(*ops.ranking_rows(z, y))
                     out["fit_temperature"] = crc(ops.fit_temperature(z, y))
+                    out["fit_bias_temperature"] = attempt(lambda: crc(*ops.fit_bias_temperature(z, y)))
+                out.update(judged(torch, ops, z, y, state, lambda: mats[0][0].to(dev)[:, :V]))
                 tau = torch.tensor([0.4, 0.0, 0.0, 0.0], dtype=torch.float64, device=dev)
                 for score in ("max_prob", "margin", "neg_entropy"):
                     for name, t in ((score, None), (score + "_tau", tau)):
@@ -139,6 +215,35 @@ def lines():
                 out["fit_priors"] = crc(ops.fit_priors(z, source, state=state, max_iter=5))
                 torch.cuda.synchronize()
                 yield {"V": V, "N": N, "beta": beta, **out}
+    for n in NS:
+        for S in (1, 48, 130):
+            X, L, y = (t.to(dev) for t in make_ids(torch, n, S, 5))
+            order = torch.randperm(n, generator=torch.Generator().manual_seed(n)).to(dev)
+            out = {f"augment_rows_{k}": crc(*ops.augment_rows(X, L, 0, 1, pd, pm, seed=11, epoch=3))
+                   for k, (pd, pm) in enumerate(((0.3, 0.2), (0.0, 0.5), (0.9, 0.0)))}
+            B = max(1, n - 1)
+            out["gather_batch"] = crc(*ops.gather_batch(X, L, y, None, n - B, B))
+            out["gather_batch_order"] = crc(*ops.gather_batch(X, L, y, order, n - B, B))
+            torch.cuda.synchronize()
+            yield {"n": n, "S": S, **out}
+    zs, y = make_wrapped(torch)
+    zs, y = [t.to(dev)[:, :3] for t in zs], y.to(dev)
+    z = zs[0]
+    for beta in (None, 1.0 / 6.0):
+        state = None if beta is None else ops.temperature_state(beta, dev)
+        out = {"reliability_rows": crc(*ops.reliability_rows(z, y, bins=15, state=state)), "topk_rows": crc(*ops.topk_rows(z, 2, state=state)),
+               "ensemble_rows": crc(*ops.ensemble_rows(zs, states=None if state is None else [state] * 3, weights=[3.0, 1.0, 2.0]))}
+        source = torch.log_softmax(torch.arange(3, dtype=torch.float64, device=dev) / 3, dim=0)
+        out["fit_priors"] = crc(ops.fit_priors(z, source, state=state, max_iter=2))
+        if state is not None:
+            out["scale_logp"] = crc(ops.scale_logp(z, state))
+        else:
+            out["score_rows"] = crc(*ops.score_rows(z, y))
+            out["fit_temperature"] = crc(ops.fit_temperature(z, y))
+            out["fit_bias_temperature"] = crc(*ops.fit_bias_temperature(z, y))
+        out.update(judged(torch, ops, z, y, state, lambda: make_wrapped(torch)[0][0].to(dev)[:, :3]))
+        torch.cuda.synchronize()
+        yield {"V": 3, "N": z.shape[0], "beta": beta, **out}
     for N in CHUNK_NS:
         z, y, kappa, rows = (t.to(dev) for t in make_chunked(torch, N))
         sel = ops.selective_buffers(N, dev)
@@ -170,8 +275,11 @@ def compare(variant, dest):
             json.dump(res, f, indent=0)
             f.write("\n")
     print(f"logp_bits: {len(a)} lines of the product library, {len(b)} of {variant}: " + ("all equal" if res["equal"] else f"{len(differing)} DIFFER"))
+    refused = sorted({k for x in a for k, v in x.items() if isinstance(v, str)})
+    if refused:
+        print(f"logp_bits: ops that refused their arguments on some line: {', '.join(refused)}")
     for x, y in differing[:10]:
-        print("  ", {k: (x[k], y.get(k)) for k in x if x[k] != y.get(k)}, {k: x[k] for k in ("V", "N", "beta")})
+        print("  ", {k: (x[k], y.get(k)) for k in x if x[k] != y.get(k)}, {k: x[k] for k in ("V", "N", "beta", "n", "S") if k in x})
     return 0 if res["equal"] else 1
 
 
