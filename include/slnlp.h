@@ -895,6 +895,79 @@ int slnlp_augment_rows(const int64_t* X, const int64_t* L, int64_t n, int64_t S,
                        float p_mask, uint64_t seed, int64_t epoch, int64_t* X_out /* [n, S] */, int64_t* L_out /* [n] */,
                        void* stream);
 
+/* --------------------------------------------------------- occlusion attribution --
+ * What in the input a prediction rests on (LogProbJudge.attribute; slnlp/metrics.py's attribution_report): hide one UNIT of a row
+ * -- a window of frames, or one phonological field in every frame -- run the forward passes again and measure how far the
+ * log-probability of the class falls.  tests/attribution_ref.py restates everything below in numpy.
+ *
+ * THE VARIANT TABLE (slnlp.ops.occlusion_variants builds it on the host): variants int32 [M, 3] = (row, unit, bin), sorted by
+ * (row, unit); row_start int32 [N + 1], the offset of each row's first variant.  bin in [0, n_bins) keys the summary's table.
+ *
+ * slnlp_occlude_rows builds the variants' inputs.  X int64 [n, S], L int64 [n], y int64 [n]; row i has len = clamp(L[i], 0, S).
+ * Variant j = (row, unit, .) writes X_out[j, :], L_out[j], y_out[j] = y[row] (the Transformer's decoder consumes it):
+ *   SLNLP_OCCLUDE_MASK        the window [lo, hi) = [unit stride, min(unit stride + width, len)) becomes unk; positions below len
+ *                             outside it are copied, X_out[j, len .. S) = pad, L_out[j] = len
+ *   SLNLP_OCCLUDE_DROP        the window's positions are deleted and the rest closes up in ascending order; the tail is pad,
+ *                             L_out[j] = len - (hi - lo).  A window that covers the whole row (lo = 0, hi = len) is MASKED
+ *                             instead: a row never loses all of its frames
+ *   SLNLP_OCCLUDE_SUBSTITUTE  every position t < len takes sub[X[row, t] F + unit] when 0 <= X[row, t] < Vx, else X[row, t] itself;
+ *                             the tail is pad, L_out[j] = len.  sub int64 [Vx, F] (slnlp.ingest.field_substitutions); width and
+ *                             stride are not read
+ * Positions >= len of X are never read.  A variant is INVALID when its row lies outside [0, n), or its unit is invalid for that
+ * row -- unit < 0; a window starting at or behind len (so every unit of a row of length 0); a field outside [0, F) or a row of
+ * length 0 under SUBSTITUTE: it reads nothing and writes an all-pad row with L_out = 0 and y_out = 0.  One wave per variant,
+ * integers only, no LDS, no atomics: a function of the arguments alone.  One launch on stream, no host wait.
+ *
+ * slnlp_attribution_rows judges M variant rows var float32 [M, ld_v] against their base rows base float32 [N, ld_b] (V columns
+ * used of each, padding never read).  variants, vals and ints are the WHOLE table's arrays: row j of var is variant off + j, and
+ * entries off .. off + M - 1 are read and written (the caller has room for off + M).  beta = state ? state[0] : 1.  Both rows go
+ * through slnlp_topk_rows' / slnlp_reliability_rows' fp64 row head: zmax, a = beta zmax, rest = sum e - 1, s0 = 1 + rest, and
+ *   p(k) = 1 / s0 at the maximum, exp(beta z_k - a) / s0 elsewhere;    lp(k) = (beta z_k - a) - log1p(rest)
+ * The target c is y[row] (target 0; y may be null with target 1) or the base row's arg-max (target 1).  At variant off + j:
+ *   vals double [., 3]   drop = lp_b(c) - lp_v(c);  dp = p_b(c) - p_v(c);  kl = sum_k p_b(k) (lp_b(k) - lp_v(k)), terms with
+ *                        p_b(k) == 0 count as 0; lane l adds its columns l, l + 64, ... ascending, then the wave's fixed order
+ *   ints int32 [., 2]    the variant row's arg-max (slnlp_score_rows' order), and a code: 0 usable; -3 the variant's row lies
+ *                        outside [0, N) (looked at first; arg-max -1, nothing else is read); -2 the base or the variant row holds
+ *                        a NaN or has no finite maximum; -1 the label lies outside [0, V) (never used as an index)
+ * A row with a non-zero code stores NaN in all three values.  A usable variant may still have a drop of +-inf or NaN (-inf at the
+ * target in one or both rows) and a kl of +inf: IEEE arithmetic on the definitions above.  One launch, a wave per variant.
+ *
+ * slnlp_attribution_summary reduces a finished table; four launches, no host wait, no floating-point atomics.
+ *   rows_i int32 [N, 6]   per row: the base arg-max, the target c (-1 when there is none), the base row's code (0, -1, -2 as
+ *                         above), the number of usable variants, the number of flips (usable variants whose arg-max is not the
+ *                         base's), top_unit (-1 for none)
+ *   rows_d double [N, 4]  lp_b(c) (NaN without a target); top_drop, the largest finite drop of the row's usable variants -- ties to the
+ *                         smaller unit -- and min_drop, the least (NaN for none); sum_drop over the finite drops (lane l of the
+ *                         row's wave adds entries l, l + 64, ... of the row's segment, then the wave's fixed order)
+ *                         A row's segment is row_start[r] .. row_start[r + 1] clamped into [0, M]; entries of another row are skipped.
+ *   cell int32 [M]        scratch: ((c n_bins + bin) << 1) | flip of a usable variant whose bin lies in [0, n_bins), else -1
+ *   table_i int64 [V, n_bins, 3], table_d double [V, n_bins, 2], keyed by (target class, bin): count -- the usable variants whose
+ *                         drop and kl are both finite, the ones in the sums --, flips over all usable variants of the cell,
+ *                         nonfinite -- the usable variants with a drop or kl that is not finite, counted here and kept out of the
+ *                         sums --; the sums of drop and of kl.  One block per cell: thread t adds variants t, t + 256, ...
+ *                         ascending, a fixed binary tree adds the 256 threads, so a cell's bits depend on M alone.
+ *   head int64 [8]        usable, bad-label (-1), non-finite (-2) and invalid (-3) variants, total flips, 0, 0, 0
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer (sub only under SUBSTITUTE, y only
+ * with target 0, state never); n, N, S or M outside 1..INT32_MAX (M, off + M: INT32_MAX / 3); a kind or target that is none of the
+ * above; width or stride outside 1..S; F or n_bins outside 1..SLNLP_ATTR_MAX_BINS; V outside 1..SLNLP_CONFUSION_MAX_V; ld < V; a
+ * misaligned pointer; an output overlapping an input or another output. */
+#define SLNLP_OCCLUDE_MASK 0
+#define SLNLP_OCCLUDE_DROP 1
+#define SLNLP_OCCLUDE_SUBSTITUTE 2
+#define SLNLP_ATTR_MAX_BINS 64
+#define SLNLP_ATTR_HEAD_BYTES 64
+int slnlp_occlude_rows(const int64_t* X, const int64_t* L, const int64_t* y, int64_t n, int64_t S, const int32_t* variants, int64_t M,
+                       int kind, int64_t width, int64_t stride, int64_t pad, int64_t unk, const int64_t* sub, int64_t Vx, int64_t F,
+                       int64_t* X_out /* [M, S] */, int64_t* L_out /* [M] */, int64_t* y_out /* [M] */, void* stream);
+int slnlp_attribution_rows(const float* base, int64_t ld_b, const float* var, int64_t ld_v, const int64_t* y, const int32_t* variants,
+                           int64_t N, int64_t M, int64_t V, int target, const double* state, int64_t off, double* vals, int32_t* ints,
+                           void* stream);
+int slnlp_attribution_summary(const float* base, int64_t ld_b, const int64_t* y, const int32_t* variants, const int32_t* row_start,
+                              int64_t N, int64_t M, int64_t V, int n_bins, int target, const double* state, const double* vals,
+                              const int32_t* ints, int32_t* cell, int64_t* head, int64_t* table_i, double* table_d, int32_t* rows_i,
+                              double* rows_d, void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);

@@ -27,11 +27,6 @@
 
 namespace slnlp {
 
-// kept lanes below this one
-__device__ __forceinline__ int lanes_below(unsigned long long ballot) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
-}
-
 __device__ __forceinline__ void augment_rows_body(const int64_t* __restrict__ X, const int64_t* __restrict__ L, int n, int S, int64_t pad,
                                                   int64_t unk, unsigned thr_drop, unsigned thr_mask, unsigned long long seed,
                                                   unsigned epoch, int64_t* __restrict__ X_out, int64_t* __restrict__ L_out) {

@@ -119,6 +119,11 @@ __device__ __forceinline__ void wave_rows(Count n, F f) {
 constexpr int WAVE_ROWS_MAX_BLOCKS = 2048;   // x 4 rows: more than 8192 rows wrap the stride loop
 // the blocks of 256 threads of a wave_rows launch over n rows
 static inline int wave_rows_grid(int64_t n) { return (int)((n + 3) / 4 < WAVE_ROWS_MAX_BLOCKS ? (n + 3) / 4 : WAVE_ROWS_MAX_BLOCKS); }
+// the lanes below this one whose bit is set in a wave's ballot: a kept position's slot within its chunk of 64 (augment.hip,
+// attribution.hip)
+__device__ __forceinline__ int lanes_below(unsigned long long ballot) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+}
 
 // ------------------------------------------------------------- dropout ------
 // Counter-based Threefry4x32-12 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11 -- the

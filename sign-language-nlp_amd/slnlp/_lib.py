@@ -148,6 +148,9 @@ SIGNATURES = {
     "slnlp_selective_counts": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp]),
     "slnlp_label_audit": (i32, [vp, i64, vp, i64, i64, vp, i32, vp, i64, vp]),
     "slnlp_scatter_logp": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp]),
+    "slnlp_occlude_rows": (i32, [vp, vp, vp, i64, i64, vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
+    "slnlp_attribution_rows": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
+    "slnlp_attribution_summary": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -303,6 +306,10 @@ SEL_MAX_LEVELS = 8                              # SLNLP_SEL_MAX_LEVELS
 SEL_TABLE_HEAD = 40                             # SLNLP_SEL_TABLE_HEAD
 SEL_MAX_ROWS = 1048576                          # SLNLP_SEL_MAX_ROWS
 AUDIT_HEAD_BYTES = 64                           # SLNLP_AUDIT_HEAD_BYTES
+OCCLUDE_KINDS = ("mask", "drop", "substitute")  # SLNLP_OCCLUDE_MASK / _DROP / _SUBSTITUTE
+ATTR_MAX_BINS = 64                              # SLNLP_ATTR_MAX_BINS
+ATTR_HEAD_BYTES = 64                            # SLNLP_ATTR_HEAD_BYTES
+ATTR_TARGETS = ("label", "pred")                # target 0: the label; 1: the base row's arg-max
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

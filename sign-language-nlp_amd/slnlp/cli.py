@@ -91,7 +91,21 @@ which train labels are probably wrong, by confident learning:
 
 (For the Transformer, whose decoder reads the gold label, this is a statement about its log-probs, not about the labels.)
 
-Without the eight keys the workdir holds exactly the files listed above.
+A top-level ``attribution: {by: frame, mode: mask, width: 1, stride: 1, bins: 8, target: label}`` (all optional, these defaults;
+``by``: frame, window or field; ``mode``: mask or drop; ``target``: label or pred) makes rank 0 write, next to test_output.json,
+what the refit's ``attribute`` finds on the test split -- which frames of a sign, or which phonological fields, its predictions rest
+on, by occlusion.  ``by: field`` builds the substitution table from the config's own ``dataset_args.fields`` and
+``composition_strategy`` (``slnlp.ingest.field_substitutions``) and names the units after the fields:
+
+    test_attribution.json          rows, variants, usable, bad_labels, nonfinite_rows, invalid, total_flips, temperature, the options,
+                                   unit_names, the ranking (bin, name, mean drop: largest first) and per bin mean_drop, mean_kl,
+                                   flip_rate, count, nonfinite
+    test_attribution_classes.csv   class, name, bin, unit, count, nonfinite, mean_drop, mean_kl and flip_rate per (class, bin) with a
+                                   usable variant
+
+(For the Transformer, whose decoder reads the gold label, the drops are conditional on that label.)
+
+Without the nine keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -105,7 +119,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -394,6 +408,56 @@ def save_selective(est, test_data, opts, workdir):
     return res
 
 
+def attribution_options(setting):
+    """The ``attribution`` key with its defaults filled in -- {by frame, mode mask, width 1, stride 1, bins 8, target label} -- or
+    None when the key is absent.  Anything but a dict over these six keys ({}: all defaults) with ``by`` frame / window / field,
+    ``mode`` mask / drop, ``width`` and ``stride`` integers >= 1 (``by: frame``: width 1), ``bins`` an integer in 1..64 and
+    ``target`` label / pred raises ValueError (the estimator's own check: slnlp/judge.py)."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"attribution={setting!r}: expected a dict with keys among ('by', 'mode', 'width', 'stride', 'bins', 'target')")
+    from .judge import attribution_options as checked
+    return checked(setting)
+
+
+def save_attribution(est, test_data, opts, dataset_args, workdir):
+    """``est.attribute(test_data, **opts)`` as ``test_attribution.json`` (the counts, the options, the ranking and the per-bin table)
+    and ``test_attribution_classes.csv`` (class, name, bin, unit, count, nonfinite, mean_drop, mean_kl, flip_rate per (class, bin)
+    with a usable variant) in ``workdir``; floats are written with ``repr``, a NaN as null / an empty cell.  ``by: field`` builds
+    the substitution table from ``dataset_args``' ``fields`` and ``composition_strategy``.  Returns the result."""
+    names = test_data.vocab_y.itos if getattr(test_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    extra = {}
+    if opts["by"] == "field":
+        from .ingest import field_substitutions
+        fields = list((dataset_args or {}).get("fields") or [])
+        if not fields or getattr(test_data, "vocab_X", None) is None or not hasattr(test_data.vocab_X, "itos"):
+            raise ValueError("attribution: by='field' needs dataset_args.fields and a dataset built from them (its vocabulary names the tokens)")
+        extra = {"substitutions": field_substitutions(test_data.vocab_X, fields, (dataset_args or {}).get("composition_strategy", "as_words")),
+                 "unit_names": fields}
+    res = est.attribute(test_data, **opts, **extra)
+    num = lambda v: None if v != v else float(v)
+    cell = lambda v: "" if v != v else repr(float(v))
+    pb, pc = res["per_bin"], res["per_class"]
+    out = {k: int(res[k]) for k in ("rows", "variants", "usable", "bad_labels", "nonfinite_rows", "invalid", "total_flips")}
+    out.update(temperature=float(res["temperature"]), options=dict(opts), unit_names=list(res["unit_names"]),
+               ranking=[[int(b), n, num(d)] for b, n, d in res["ranking"]],
+               per_bin=[{"bin": b, "unit": res["unit_names"][b], "count": int(pb["count"][b]), "nonfinite": int(pb["nonfinite"][b]),
+                         "mean_drop": num(pb["mean_drop"][b]), "mean_kl": num(pb["mean_kl"][b]), "flip_rate": num(pb["flip_rate"][b])}
+                        for b in range(len(res["unit_names"]))])
+    save_json(out, os.path.join(workdir, "test_attribution.json"))
+    with open(os.path.join(workdir, "test_attribution_classes.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["class", "name", "bin", "unit", "count", "nonfinite", "mean_drop", "mean_kl", "flip_rate"])
+        for i, c in enumerate(res["classes"]):
+            for b in range(len(res["unit_names"])):
+                if pc["count"][i, b] + pc["nonfinite"][i, b] > 0:
+                    w.writerow([int(c), name(c), b, res["unit_names"][b], int(pc["count"][i, b]), int(pc["nonfinite"][i, b]),
+                                cell(pc["mean_drop"][i, b]), cell(pc["mean_kl"][i, b]), cell(pc["flip_rate"][i, b])])
+    return res
+
+
 LABEL_AUDIT_DEFAULTS = {"cv": 5, "rank_by": "normalized_margin", "pairs": 20, "top": 200}
 LABEL_AUDIT_RANKINGS = ("normalized_margin", "self_confidence")                 # slnlp/metrics.py: LABEL_RANKINGS
 LABEL_AUDIT_MAX_CV, LABEL_AUDIT_MAX_PAIRS = 32, 64                              # SLNLP_ENSEMBLE_MAX_MEMBERS, SLNLP_PAIRS_MAX
@@ -652,6 +716,7 @@ def run(args):
     prior_shift = prior_shift_options(args.get("prior_shift"))
     selective = selective_options(args.get("selective"))
     label_audit = label_audit_options(args.get("label_audit"))
+    attribution = attribution_options(args.get("attribution"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -699,6 +764,8 @@ def run(args):
             save_conformal(est, test_data, workdir)
         if selective is not None:
             save_selective(est, test_data, selective, workdir)
+        if attribution is not None:
+            save_attribution(est, test_data, attribution, args.get("dataset_args"), workdir)
         if ensemble is not None:
             save_ensemble(gs, factory, train_data, test_data, ensemble, intervals, metrics, seed, workdir)
         if prior_shift is not None:

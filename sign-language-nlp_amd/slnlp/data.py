@@ -75,6 +75,24 @@ class TokenDataset:
         return self[perm[:n_test]], self[perm[n_test:]]
 
 
+class DeviceRows:
+    """Rows that are already on the device -- ``ids`` int64 [n, S], ``lengths`` int64 [n], ``y`` int64 [n], contiguous tensors on
+    one device -- for the forward passes of a fitted estimator: ``NeuralNetClassifier._device_data`` hands the three tensors on as
+    they are instead of uploading a ``TokenDataset`` (``LogProbJudge.attribute`` builds its occluded variants on the device)."""
+
+    def __init__(self, ids, lengths, y):
+        import torch
+        for name, t, dim in (("ids", ids, 2), ("lengths", lengths, 1), ("y", y, 1)):
+            if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == dim and t.is_contiguous() and t.device == ids.device):
+                raise ValueError(f"DeviceRows: {name} must be a contiguous int64 tensor of {dim} dimension(s) on the device of ids")
+        if not len(ids) == len(lengths) == len(y):
+            raise ValueError(f"DeviceRows: {len(ids)} rows of ids, {len(lengths)} lengths and {len(y)} labels")
+        self.ids, self.lengths, self.y = ids, lengths, y
+
+    def __len__(self):
+        return int(self.y.shape[0])
+
+
 def collate_data(data):
     """helper.py:293-304: list of ((ids, len), label) -> ({"X","lengths","y"}, y) int64 tensors."""
     import torch

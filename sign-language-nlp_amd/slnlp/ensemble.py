@@ -5,7 +5,7 @@ member runs its own forward passes (``NeuralNetClassifier._forward_logp``: under
 weights where it predicts with them), ONE ``ops.ensemble_rows`` launch combines the members' device log-probs, each at its own
 temperature, into one set of float32 log-probs, and everything that judges one fit's log-probs -- ``predict_proba``,
 ``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare``, ``conformalize``, ``predict_set``,
-``coverage``, ``risk_coverage``, ``fit_rejection``, ``predict_selective``, ``label_issues`` -- then works on the ensemble through the
+``coverage``, ``risk_coverage``, ``fit_rejection``, ``predict_selective``, ``label_issues``, ``attribute`` -- then works on the ensemble through the
 same ``_forward_logp(ds, then)`` hook: both classes inherit those methods from ``slnlp.judge.LogProbJudge``.  The
 same launch gives, per sample, how much the members disagree (``uncertainty``): the entropy of the mixture, the expected entropy
 of a member and their difference, the mutual information.  Nothing is averaged on the host and no torch arithmetic runs on the

@@ -120,3 +120,40 @@ def build_dataset(dataset_dir, fields, samples_min_freq=1, composition_strategy=
     ds = TokenDataset(ids, lengths, y, vocab_X, vocab_y)
     ds.files = [f for f, _, _ in samples]
     return ds
+
+
+def _split_token(word, F, composition_strategy):
+    """The F field parts of a composed token, or None when it does not split into F parts."""
+    if composition_strategy == "as_sep_feat":
+        import ast
+        try:
+            parts = ast.literal_eval(word)
+        except (ValueError, SyntaxError):
+            return None
+        return list(parts) if isinstance(parts, list) and len(parts) == F and all(isinstance(q, str) for q in parts) else None
+    parts = word.split("-")
+    return parts if len(parts) == F else None
+
+
+def field_substitutions(vocab_X, fields, composition_strategy):
+    """The substitution table of a field occlusion (``LogProbJudge.attribute(by="field")``): int64 [len(vocab_X), F] whose entry
+    (v, f) is the id of token v with field f replaced by what ``composition_strategy`` writes for a NULL field -- composed by the
+    strategy's own function and looked up in ``vocab_X.stoi``, so a word the vocabulary has not seen maps to ``<unk>``.
+    ``<unk>``, ``<pad>`` and every token that does not split into F parts map to themselves."""
+    if composition_strategy not in STRATEGIES:
+        raise ValueError(f"Unknown composition strategy: '{composition_strategy}'")
+    fields = list(fields)
+    F = len(fields)
+    if F < 1:
+        raise ValueError("field_substitutions: no fields")
+    compose = STRATEGIES[composition_strategy]
+    null = _split_token(compose([{f: None for f in fields}], fields)[0], F, composition_strategy)     # the parts of an all-null frame
+    join = (lambda parts: str(parts)) if composition_strategy == "as_sep_feat" else "-".join
+    table = np.repeat(np.arange(len(vocab_X), dtype=np.int64)[:, None], F, axis=1)
+    for v, word in enumerate(vocab_X.itos):
+        parts = None if word in (UNK_WORD, PAD_WORD) else _split_token(word, F, composition_strategy)
+        if parts is None:
+            continue
+        for f in range(F):
+            table[v, f] = vocab_X.stoi[join(parts[:f] + [null[f]] + parts[f + 1:])]
+    return table

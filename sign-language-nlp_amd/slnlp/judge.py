@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import metrics, ops
-from .data import TokenDataset
+from .data import DeviceRows, TokenDataset
 
 
 CONFORMAL_DEFAULTS = {"alpha": 0.1, "method": "aps", "randomized": True, "lam": 0.0, "k_reg": 0, "seed": 0}
@@ -64,6 +64,41 @@ def conformal_least_rows(alpha):
     while math.ceil(float(n + 1) * (1.0 - alpha)) > n:
         n += 1
     return n
+
+
+ATTRIBUTION_DEFAULTS = {"by": "frame", "mode": "mask", "width": 1, "stride": 1, "bins": 8, "target": "label"}
+ATTRIBUTION_BY = ("frame", "window", "field")
+ATTRIBUTION_MODES = ("mask", "drop")
+ATTRIBUTION_TARGETS = tuple(ops._lib.ATTR_TARGETS)
+
+
+def attribution_options(setting):
+    """The ``attribution`` setting with its defaults filled in -- {by "frame", mode "mask", width 1, stride 1, bins 8, target
+    "label"} -- or None (off).  ``by``: "frame" (windows of width 1; ``width`` must be 1), "window" or "field" (one unit per
+    phonological field; ``mode``, ``width``, ``stride`` and ``bins`` are not used).  Anything else raises ValueError here."""
+    if setting is None or setting is False:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"attribution={setting!r}: expected a dict with keys among {tuple(ATTRIBUTION_DEFAULTS)} or None")
+    unknown = sorted(set(setting) - set(ATTRIBUTION_DEFAULTS))
+    if unknown:
+        raise ValueError(f"attribution: unknown keys {unknown} (known: {tuple(ATTRIBUTION_DEFAULTS)})")
+    o = {**ATTRIBUTION_DEFAULTS, **setting}
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if o["by"] not in ATTRIBUTION_BY:
+        raise ValueError(f"attribution: by={o['by']!r}, expected one of {ATTRIBUTION_BY}")
+    if o["mode"] not in ATTRIBUTION_MODES:
+        raise ValueError(f"attribution: mode={o['mode']!r}, expected one of {ATTRIBUTION_MODES}")
+    if o["target"] not in ATTRIBUTION_TARGETS:
+        raise ValueError(f"attribution: target={o['target']!r}, expected one of {ATTRIBUTION_TARGETS}")
+    for k in ("width", "stride"):
+        if not whole(o[k]) or not 1 <= o[k] < 2 ** 31:
+            raise ValueError(f"attribution: {k}={o[k]!r}, expected an integer >= 1")
+    if not whole(o["bins"]) or not 1 <= o["bins"] <= ops._lib.ATTR_MAX_BINS:
+        raise ValueError(f"attribution: bins={o['bins']!r}, expected an integer in 1..{ops._lib.ATTR_MAX_BINS}")
+    if o["by"] == "frame" and o["width"] != 1:
+        raise ValueError(f"attribution: by='frame' occludes one frame at a time, width={o['width']!r}; use by='window'")
+    return {"by": o["by"], "mode": o["mode"], "width": int(o["width"]), "stride": int(o["stride"]), "bins": int(o["bins"]), "target": o["target"]}
 
 
 CONFORMAL_DRAW_CALIBRATE, CONFORMAL_DRAW_PREDICT = 0, 1    # the u of a row at prediction time is independent of the calibration draws
@@ -634,4 +669,107 @@ class LogProbJudge:
         self._report_calibration(res, use)
         if per_row:
             res["per_row"] = {q: got[q] for q in ("k", "code", "flags", "pred", "s", "m", "other", "p_pred")}
+        return res
+
+    # ----------------------------------------------------------- attribution
+    def attribute(self, X, y=None, by="frame", mode="mask", width=1, stride=1, bins=8, substitutions=None, unit_names=None,
+                  target="label", calibrated=True, per_variant=False, max_variants=65536):
+        """What in the input this fit's predictions on ``X`` rest on, by occlusion: hide one unit of a row, run the forward passes
+        again and measure how far the log-probability of the class falls.  ``by`` "frame": the units are the frames, one at a
+        time (``width`` 1; ``stride`` > 1 takes every stride-th); "window": windows of ``width`` frames every ``stride``; ``mode``
+        "mask" replaces the window's tokens by ``<unk>``, "drop" deletes them and closes the row up (a window over the whole row
+        is masked).  ``by`` "field": the units are the phonological fields a token is composed from; ``substitutions`` int64
+        [len(vocab_X), F] (``slnlp.ingest.field_substitutions``) maps every token to itself with one field nulled.  ``target``:
+        the class whose log-probability is followed, "label" (``y``, or the dataset's) or "pred" (the base row's arg-max).
+
+        One base pass, its calibrated log-probs kept on the device; then the rows of ``X`` in chunks of at most
+        ``max_variants`` variants: ``ops.occlude_rows`` builds the chunk's inputs ON THE DEVICE, the forward passes take them as
+        ``slnlp.data.DeviceRows`` through the same hook every consumer uses, and ``ops.attribution_rows`` reduces each variant row
+        against its base row under the same calibration; one ``ops.attribution_summary`` and ONE download -- the M x V variant
+        log-probs never leave the device.  Returns ``metrics.attribution_report``'s dict -- per row top_unit, top_drop, min_drop,
+        sum_drop, flips, units, base_pred, target, base_logp; per_bin and per_class {mean_drop, mean_kl, flip_rate, count,
+        nonfinite} (a bin is the relative position of the window's centre in ``bins`` equal parts of the row, or the field);
+        ranking; unit_names; the head's counts -- with ``base_pred`` and ``target`` as indices into ``classes`` (target -1: the row
+        has none), plus ``classes``, ``temperature``, ``rows`` and ``by`` / ``mode`` / ``width`` / ``stride`` / ``target_kind``.  ``per_variant=True`` adds ``per_variant``:
+        variants int32 [M, 3] = (row, unit, bin), row_start, drop / dp / kl float64 [M], pred and code int32 [M].
+
+        drop = lp_base(c) - lp_variant(c), so a POSITIVE drop says the unit supports class c.  Occlusion measures what THIS model
+        uses, not what is in the signal, and ``<unk>`` / the null field are themselves tokens the model has a reaction to.  The
+        statement is as asked for the two RNN models only: the reference Transformer feeds the gold label to its decoder, so its
+        drops are conditional on that label (every variant carries its row's label).  Raises ValueError when a label lies outside
+        the classes (``target="label"``) or when no row has a frame to occlude."""
+        self._require_initialized()
+        what = "attribute"
+        o = attribution_options({"by": by, "mode": mode, "width": width, "stride": stride, "bins": bins, "target": target})
+        cap = ops._int_in(what, "max_variants", max_variants, 1, (2 ** 31 - 1) // 3)
+        V = len(self.classes_)
+        if V > ops._lib.CONFUSION_MAX_V:
+            raise ValueError(f"{what}: {V} classes, the table is formed for at most {ops._lib.CONFUSION_MAX_V}")
+        ds = self._as_dataset(X)
+        S = int(ds.ids.shape[1])
+        if o["by"] == "field":
+            if substitutions is None:
+                raise ValueError(f"{what}: by='field' needs substitutions, the table of slnlp.ingest.field_substitutions")
+            sub_host = np.ascontiguousarray(np.asarray(substitutions), dtype=np.int64)
+            if sub_host.ndim != 2 or not 1 <= sub_host.shape[1] <= ops._lib.ATTR_MAX_BINS or sub_host.shape[0] < 1:
+                raise ValueError(f"{what}: substitutions of shape {sub_host.shape}, expected int64 [vocabulary, F] with F in 1..{ops._lib.ATTR_MAX_BINS}")
+            kind = "substitute"
+            variants, row_start, n_bins = ops.occlusion_variants(ds.lengths, S, "field", n_fields=int(sub_host.shape[1]))
+        else:
+            if substitutions is not None:
+                raise ValueError(f"{what}: substitutions are read with by='field' only")
+            if o["width"] > S or o["stride"] > S:
+                raise ValueError(f"{what}: width={o['width']} and stride={o['stride']} must lie in 1..{S}, the rows' padded length")
+            sub_host, kind = None, o["mode"]
+            variants, row_start, n_bins = ops.occlusion_variants(ds.lengths, S, o["mode"], o["width"], o["stride"], o["bins"])
+        if unit_names is not None and len(list(unit_names)) != n_bins:
+            raise ValueError(f"{what}: {len(list(unit_names))} unit_names for {n_bins} bins")
+        M = int(variants.shape[0])
+        if M < 1:
+            raise ValueError(f"{what}: no row of X has a frame to occlude")
+        if M > (2 ** 31 - 1) // 3:
+            raise ValueError(f"{what}: {M} variants, at most {(2 ** 31 - 1) // 3} fit one table")
+        use = self._uses_temperature(calibrated)
+        _, on_device = self._labels(what, ds, y, check=o["target"] == "label")
+        pad, unk = 1, 0                                      # the vocabularies' specials: <unk> 0, <pad> 1 (slnlp/ingest.py)
+        if getattr(ds, "vocab_X", None) is not None and hasattr(ds.vocab_X, "stoi"):
+            pad, unk = int(ds.vocab_X.stoi["<pad>"]), int(ds.vocab_X.stoi["<unk>"])
+
+        def base_rows(logp, yd):                             # the calibrated base log-probs stay on the device
+            logp, state = self._calibrated_logp(logp, use)
+            return logp, on_device(logp, yd), state
+        base, yd, state = self._judge(ds, base_rows)
+        dev = base.device
+        with torch.cuda.device(dev):
+            Xd, Ld = torch.from_numpy(ds.ids).to(dev), torch.from_numpy(ds.lengths).to(dev)
+            sub = None if sub_host is None else torch.from_numpy(sub_host).to(dev)
+            buf = ops.attribution_buffers(len(ds), V, variants, row_start, n_bins, dev)
+        first = 0                                            # whole rows per chunk (one row alone where it has more variants than the cap)
+        while first < len(ds):
+            last = first + 1
+            while last < len(ds) and int(row_start[last + 1]) - int(row_start[first]) <= cap:
+                last += 1
+            off, m = int(row_start[first]), int(row_start[last]) - int(row_start[first])
+            first = last
+            if m == 0:
+                continue
+            with torch.cuda.device(dev):
+                rows = DeviceRows(*ops.occlude_rows(Xd, Ld, yd, buf["variants"][off:off + m], kind, width=o["width"], stride=o["stride"],
+                                                    pad=pad, unk=unk, sub=sub))
+
+            def variant_rows(logp, _, off=off):
+                logp, st = self._calibrated_logp(logp, use)
+                return ops.attribution_rows(base, logp, yd, buf, off, target=o["target"], state=st)
+            self._judge(rows, variant_rows)
+        with torch.cuda.device(dev):
+            ops.attribution_summary(base, yd, buf, target=o["target"], state=state)
+            got = ops.attribution_download(buf, per_variant=bool(per_variant))
+        self._refuse_labels(what, got["head"][1], M, V)
+        res = metrics.attribution_report(got, unit_names)
+        res.update(classes=self.classes_, temperature=float(self.temperature_) if use else 1.0, by=o["by"], mode=o["mode"], width=o["width"],
+                   stride=o["stride"], target_kind=o["target"], rows=len(ds))
+        self._report_calibration(res, use)
+        if per_variant:
+            res["per_variant"] = {"variants": variants, "row_start": row_start, "drop": got["vals"][:, 0], "dp": got["vals"][:, 1],
+                                  "kl": got["vals"][:, 2], "pred": got["ints"][:, 0], "code": got["ints"][:, 1]}
         return res

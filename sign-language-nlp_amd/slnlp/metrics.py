@@ -788,3 +788,42 @@ def uncertainty_summary(rows):
     mean = (lambda v: float(np.sum(v) / n)) if n else (lambda v: float("nan"))
     return {"total_entropy": mean(rows[ok, 0]), "expected_entropy": mean(rows[ok, 1]), "mutual_information": mean(rows[ok, 2]),
             "disagreement_rate": mean(rows[ok, 3] > 0), "mean_disagreement": mean(rows[ok, 3]), "rows": n, "nan_rows": int((~ok).sum())}
+
+
+def attribution_report(rec, unit_names=None):
+    """``ops.attribution_download``'s dict (``slnlp_attribution_summary``, include/slnlp.h) as the report of an occlusion
+    attribution, in fp64 from the device's exact counts and fixed-order sums:
+
+    * per row, arrays [N]: ``top_unit`` (the unit whose occlusion lowers the target's log-prob most, -1 for none), ``top_drop``,
+      ``min_drop``, ``sum_drop``, ``flips`` (variants whose arg-max is not the base's), ``units`` (usable variants), ``base_pred``,
+      ``target`` (-1 for none), ``base_logp`` (the base log-prob of the target);
+    * ``per_bin`` over all classes and ``per_class`` per (class, bin), each {mean_drop, mean_kl, flip_rate, count, nonfinite}:
+      arrays [n_bins] and [V, n_bins].  ``count`` holds the usable variants whose drop and kl are finite -- the ones in the means --,
+      ``nonfinite`` the other usable ones; ``flip_rate`` = flips / (count + nonfinite); a cell with count 0 has NaN means, one
+      without a usable variant a NaN flip rate.  The bins' sums over the classes are ``math.fsum``s of the cells;
+    * ``ranking``: the bins with a count by mean drop, largest first (ties by ascending bin), as (bin, name, mean_drop);
+    * ``unit_names``: the bins' names (``unit_names``, default their numbers as strings), and the head's counts ``variants``,
+      ``usable``, ``bad_labels``, ``nonfinite_rows``, ``invalid``, ``flips``."""
+    ti, td = np.asarray(rec["table_i"], dtype=np.int64), np.asarray(rec["table_d"], dtype=np.float64)
+    ri, rd, head = np.asarray(rec["rows_i"]), np.asarray(rec["rows_d"], dtype=np.float64), np.asarray(rec["head"], dtype=np.int64)
+    V, nb = ti.shape[:2]
+    names = [str(b) for b in range(nb)] if unit_names is None else [str(u) for u in unit_names]
+    if len(names) != nb:
+        raise ValueError(f"attribution_report: {len(names)} unit_names for {nb} bins")
+
+    def cells(count, flips, nonfinite, drop, kl):
+        count, seen = np.asarray(count, dtype=np.float64), np.asarray(count + nonfinite, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return {"mean_drop": np.where(count > 0, drop / count, np.nan), "mean_kl": np.where(count > 0, kl / count, np.nan),
+                    "flip_rate": np.where(seen > 0, flips / seen, np.nan), "count": np.asarray(count, dtype=np.int64),
+                    "nonfinite": np.asarray(nonfinite, dtype=np.int64)}
+    per_class = cells(ti[:, :, 0], ti[:, :, 1], ti[:, :, 2], td[:, :, 0], td[:, :, 1])
+    over = lambda a: np.array([math.fsum(a[:, b]) for b in range(nb)], dtype=np.float64)
+    per_bin = cells(ti[:, :, 0].sum(axis=0), ti[:, :, 1].sum(axis=0), ti[:, :, 2].sum(axis=0), over(td[:, :, 0]), over(td[:, :, 1]))
+    ranked = sorted((b for b in range(nb) if per_bin["count"][b] > 0), key=lambda b: (-per_bin["mean_drop"][b], b))
+    return {"top_unit": ri[:, 5].astype(np.int64), "top_drop": rd[:, 1], "min_drop": rd[:, 2], "sum_drop": rd[:, 3],
+            "flips": ri[:, 4].astype(np.int64), "units": ri[:, 3].astype(np.int64), "base_pred": ri[:, 0].astype(np.int64),
+            "target": ri[:, 1].astype(np.int64), "base_logp": rd[:, 0], "per_bin": per_bin, "per_class": per_class,
+            "ranking": [(b, names[b], float(per_bin["mean_drop"][b])) for b in ranked], "unit_names": names,
+            "variants": int(head[:4].sum()), "usable": int(head[0]), "bad_labels": int(head[1]), "nonfinite_rows": int(head[2]),
+            "invalid": int(head[3]), "total_flips": int(head[4])}

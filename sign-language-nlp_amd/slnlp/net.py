@@ -54,6 +54,7 @@ import numpy as np
 import torch
 
 from . import metrics, ops, param_groups, sampler, schedule
+from .data import DeviceRows
 from .judge import CONFORMAL_DEFAULTS, LogProbJudge, conformal_least_rows, conformal_options  # noqa: F401  (part of this module's names)
 
 
@@ -900,6 +901,8 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         self._stream.wait_stream(torch.cuda.current_stream(self._stream.device))
 
     def _device_data(self, ds):
+        if isinstance(ds, DeviceRows):                       # built on the device (LogProbJudge.attribute): handed on as they are
+            return ds.ids, ds.lengths, ds.y
         dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
         return (torch.from_numpy(ds.ids).to(dev), torch.from_numpy(ds.lengths).to(dev), torch.from_numpy(ds.y).to(dev))
 

@@ -1205,6 +1205,197 @@ def label_audit_download(buf, per_row=False):
     return out
 
 
+def occlusion_variants(lengths, S, by, width=1, stride=1, bins=8, n_fields=None):
+    """The variant table of an occlusion attribution over rows of ``lengths`` (host integers [N]) padded to ``S`` positions
+    (include/slnlp.h): ``(variants int32 [M, 3] = (row, unit, bin) sorted by (row, unit), row_start int32 [N + 1], n_bins)``.
+    With len = clamp(L[i], 0, S): ``by`` "mask" / "drop": the units are the windows [u stride, min(u stride + width, len)) with
+    u stride < len -- a row of length 0 has none -- and the bin is the relative position of the window's centre,
+    min(bins - 1, (bins (lo + hi)) // (2 len)) in integers; ``n_bins = bins``.  ``by`` "field": one unit per field u in
+    0..n_fields - 1 for a row with len >= 1, the bin is u and ``n_bins = n_fields``.  ``bins`` and ``n_fields`` lie in 1..64,
+    ``width`` and ``stride`` in 1..S, M in 0..2^31 - 1.  Host arithmetic: no GPU is needed."""
+    import numpy as np
+    what = "occlusion_variants"
+    L = np.asarray(lengths)
+    if L.ndim != 1 or L.dtype.kind not in "iu":
+        raise ValueError(f"{what}: lengths must be one dimension of integers, got {L.dtype} {L.shape}")
+    S = _int_in(what, "S", S, 1, 2 ** 31 - 1)
+    if by not in ("mask", "drop", "field"):
+        raise ValueError(f"{what}: by={by!r}, expected 'mask', 'drop' or 'field'")
+    ln = np.clip(L.astype(np.int64), 0, S)
+    if by == "field":
+        n_bins = _int_in(what, "n_fields", n_fields, 1, _lib.ATTR_MAX_BINS)
+        counts = np.where(ln >= 1, n_bins, 0)
+    else:
+        width, stride = _int_in(what, "width", width, 1, S), _int_in(what, "stride", stride, 1, S)
+        n_bins = _int_in(what, "bins", bins, 1, _lib.ATTR_MAX_BINS)
+        counts = (ln + stride - 1) // stride                 # the units u with u stride < len
+    row_start = np.zeros(ln.size + 1, dtype=np.int64)
+    np.cumsum(counts, out=row_start[1:])
+    M = int(row_start[-1])
+    if M > 2 ** 31 - 1:
+        raise ValueError(f"{what}: {M} variants, at most {2 ** 31 - 1} fit a table")
+    rows = np.repeat(np.arange(ln.size, dtype=np.int64), counts)
+    unit = np.arange(M, dtype=np.int64) - row_start[rows]
+    if by == "field":
+        bin_ = unit
+    else:
+        lo = unit * stride
+        hi = np.minimum(lo + width, ln[rows])
+        bin_ = np.minimum(n_bins - 1, (n_bins * (lo + hi)) // (2 * ln[rows]))
+    return np.stack([rows, unit, bin_], axis=1).astype(np.int32).reshape(M, 3), row_start.astype(np.int32), n_bins
+
+
+def occlude_rows(X, L, y, variants, kind, *, width=1, stride=1, pad=1, unk=0, sub=None, out=None):
+    """The variants' inputs, built on the device (``slnlp_occlude_rows``, csrc/attribution.hip): for each entry (row, unit, .) of
+    ``variants`` int32 [m, 3] -- a device tensor, or a slice of the table's rows -- a copy of row ``row`` of ``X`` int64 [n, S] /
+    ``L`` / ``y`` int64 [n] with the unit hidden: ``kind`` "mask" (the window becomes ``unk``), "drop" (the window is deleted and
+    the rest closes up; a window over the whole row is masked) or "substitute" (every token goes through ``sub`` int64 [Vx, F],
+    column ``unit``).  Returns ``(X_out [m, S], L_out [m], y_out [m])``; ``out``: that triple to fill.  One launch on the current
+    stream of ``X``'s device; no host wait."""
+    _lib.require_gpu()
+    what = "occlude_rows"
+    if kind not in _lib.OCCLUDE_KINDS:
+        raise ValueError(f"{what}: kind={kind!r}, expected one of {_lib.OCCLUDE_KINDS}")
+    if not (X.is_cuda and X.dtype == torch.int64 and X.dim() == 2 and X.is_contiguous()):
+        raise ValueError(f"{what}: X must be a contiguous int64 [n, S] device tensor")
+    n, S = int(X.shape[0]), int(X.shape[1])
+    _tensor(what, "L", L, X.device, torch.int64, n)
+    _tensor(what, "y", y, X.device, torch.int64, n)
+    if not (variants.device == X.device and variants.dtype == torch.int32 and variants.dim() == 2 and variants.shape[1] == 3
+            and variants.is_contiguous() and variants.shape[0] >= 1):
+        raise ValueError(f"{what}: variants must be a contiguous int32 [m >= 1, 3] tensor on {X.device}")
+    m = int(variants.shape[0])
+    Vx = F = 0
+    if kind == "substitute":
+        if not (torch.is_tensor(sub) and sub.device == X.device and sub.dtype == torch.int64 and sub.dim() == 2 and sub.is_contiguous()):
+            raise ValueError(f"{what}: substitute needs sub, a contiguous int64 [Vx, F] tensor on {X.device}")
+        Vx, F = int(sub.shape[0]), int(sub.shape[1])
+    else:
+        sub = None
+    with torch.cuda.device(X.device):
+        if out is None:
+            out = (torch.empty(m, S, dtype=torch.int64, device=X.device), torch.empty(m, dtype=torch.int64, device=X.device),
+                   torch.empty(m, dtype=torch.int64, device=X.device))
+        Xo, Lo, yo = out
+        _tensor(what, "X_out", Xo, X.device, torch.int64, (m, S))
+        _tensor(what, "L_out", Lo, X.device, torch.int64, m)
+        _tensor(what, "y_out", yo, X.device, torch.int64, m)
+        check(load().slnlp_occlude_rows(ptr(X), ptr(L), ptr(y), n, S, ptr(variants), m, _lib.OCCLUDE_KINDS.index(kind), int(width), int(stride),
+                                        int(pad), int(unk), ptr(sub), Vx, F, ptr(Xo), ptr(Lo), ptr(yo), stream_ptr()), what)
+    return Xo, Lo, yo
+
+
+_ATTR_PIECES = ("head", "table_i", "table_d", "rows_d", "rows_i", "vals", "ints", "cell", "variants", "row_start")
+
+
+def attribution_buffers(N, V, variants, row_start, n_bins, device):
+    """The device buffer of one attribution of N rows of V classes under a variant table (``occlusion_variants``' host arrays,
+    uploaded here), ONE int32 allocation, every piece 8-byte aligned (int32 pieces padded to an even length):
+
+        head int64 [8] | table_i int64 [V, n_bins, 3] | table_d float64 [V, n_bins, 2] | rows_d float64 [N, 4] | rows_i [N, 6] |
+        vals float64 [M, 3] | ints [M, 2] | cell [M] | variants [M, 3] | row_start [N + 1]
+
+    What a report needs ends with rows_i and the per-variant values follow, so ``attribution_download`` copies one contiguous
+    piece either way.  ``buf[name]`` is the piece as a tensor view."""
+    import numpy as np
+    what = "attribution_buffers"
+    N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
+    nb = _int_in(what, "n_bins", n_bins, 1, _lib.ATTR_MAX_BINS)
+    variants = np.ascontiguousarray(variants, dtype=np.int32)
+    row_start = np.ascontiguousarray(row_start, dtype=np.int32)
+    if variants.ndim != 2 or variants.shape[1] != 3 or not 1 <= variants.shape[0] <= (2 ** 31 - 1) // 3 or row_start.shape != (N + 1,):
+        raise ValueError(f"{what}: variants int32 [M, 3] with M in 1..{(2 ** 31 - 1) // 3} and row_start int32 [{N + 1}] expected, got "
+                         f"{variants.shape} and {row_start.shape}")
+    M = int(variants.shape[0])
+    even = lambda n: n + (n & 1)
+    sizes = {"head": _lib.ATTR_HEAD_BYTES // 4, "table_i": 6 * V * nb, "table_d": 4 * V * nb, "rows_d": 8 * N, "rows_i": even(6 * N),
+             "vals": 6 * M, "ints": 2 * M, "cell": even(M), "variants": even(3 * M), "row_start": even(N + 1)}
+    at, off = {}, 0
+    for name in _ATTR_PIECES:
+        at[name] = off
+        off += sizes[name]
+    flat = torch.empty(off, dtype=torch.int32, device=device)
+    piece = lambda name, n, dtype=torch.int32: flat[at[name]:at[name] + n].view(dtype)
+    buf = {"flat": flat, "at": at, "end": off, "shape": (N, V, M, nb),
+           "head": piece("head", 16, torch.int64), "table_i": piece("table_i", 6 * V * nb, torch.int64),
+           "table_d": piece("table_d", 4 * V * nb, torch.float64), "rows_d": piece("rows_d", 8 * N, torch.float64),
+           "rows_i": piece("rows_i", 6 * N), "vals": piece("vals", 6 * M, torch.float64), "ints": piece("ints", 2 * M),
+           "cell": piece("cell", M), "variants": piece("variants", 3 * M).view(M, 3), "row_start": piece("row_start", N + 1)}
+    buf["variants"].copy_(torch.from_numpy(variants))
+    buf["row_start"].copy_(torch.from_numpy(row_start))
+    return buf
+
+
+def _attribution_args(what, base, y, buf, target, state):
+    N, V, ld = _logp_matrix(what, base)
+    if not (isinstance(buf, dict) and buf.get("shape", (0, 0))[:2] == (N, V) and buf["flat"].device == base.device):
+        raise ValueError(f"{what}: buf must be attribution_buffers({N}, {V}, ...) on {base.device}")
+    if target not in _lib.ATTR_TARGETS:
+        raise ValueError(f"{what}: target={target!r}, expected one of {_lib.ATTR_TARGETS}")
+    if y is not None or target == "label":
+        if y is None:
+            raise ValueError(f"{what}: target 'label' needs the labels y")
+        _labels(what, y, base.device, N)
+    if state is not None:
+        _cal_state(what, state, base.device)
+    return N, V, ld
+
+
+def attribution_rows(base, var, y, buf, off, *, target="label", state=None):
+    """Judge the variant rows ``var`` float32 [m, V] -- variants ``off .. off + m - 1`` of ``buf``'s table -- against their base
+    rows in ``base`` float32 [N, V] (``slnlp_attribution_rows``, include/slnlp.h): drop, dp and kl into ``buf["vals"]``, the
+    variant's arg-max and code into ``buf["ints"]``.  ``y``: int64 [N] labels (may be None with ``target="pred"``, the base
+    row's arg-max); ``state``: a calibration state whose beta is read on the device (None: beta = 1).  One launch on the current
+    stream of ``base``'s device; no host wait.  Returns ``buf``."""
+    _lib.require_gpu()
+    what = "attribution_rows"
+    N, V, ld = _attribution_args(what, base, y, buf, target, state)
+    m, Vv, ld_v = _logp_matrix(what + " (var)", var)
+    M = buf["shape"][2]
+    off = _int_in(what, "off", off, 0, M)
+    if Vv != V or var.device != base.device or off + m > M:
+        raise ValueError(f"{what}: var must hold at most {M - off} rows of {V} classes on {base.device} at off={off}, got {tuple(var.shape)}")
+    with torch.cuda.device(base.device):
+        check(load().slnlp_attribution_rows(ptr(base), ld, ptr(var), ld_v, ptr(y), ptr(buf["variants"]), N, m, V, _lib.ATTR_TARGETS.index(target),
+                                            ptr(state), off, ptr(buf["vals"]), ptr(buf["ints"]), stream_ptr()), what)
+    return buf
+
+
+def attribution_summary(base, y, buf, *, target="label", state=None):
+    """Reduce ``buf``'s finished table on the device (``slnlp_attribution_summary``): per row the base arg-max, the target, its
+    log-probability, the usable variants, the flips, top_unit / top_drop, min_drop and sum_drop; the [V, n_bins] table keyed by
+    (target class, bin); the head.  ``base``, ``y``, ``target`` and ``state`` as for ``attribution_rows``.  Four queued launches on
+    the current stream of ``base``'s device; no host wait.  Returns ``buf``."""
+    _lib.require_gpu()
+    what = "attribution_summary"
+    N, V, ld = _attribution_args(what, base, y, buf, target, state)
+    M, nb = buf["shape"][2:]
+    with torch.cuda.device(base.device):
+        check(load().slnlp_attribution_summary(ptr(base), ld, ptr(y), ptr(buf["variants"]), ptr(buf["row_start"]), N, M, V, nb,
+                                               _lib.ATTR_TARGETS.index(target), ptr(state), ptr(buf["vals"]), ptr(buf["ints"]), ptr(buf["cell"]),
+                                               ptr(buf["head"]), ptr(buf["table_i"]), ptr(buf["table_d"]), ptr(buf["rows_i"]), ptr(buf["rows_d"]),
+                                               stream_ptr()), what)
+    return buf
+
+
+def attribution_download(buf, per_variant=False):
+    """What an attribution hands to the host in ONE device-to-host copy -- the log-probs stay on the device: {head int64 [8] =
+    (usable, bad_labels, nonfinite, invalid, flips, 0, 0, 0), table_i int64 [V, n_bins, 3] = (count, flips, nonfinite), table_d
+    float64 [V, n_bins, 2] = (sum drop, sum kl), rows_d float64 [N, 4] = (base log-prob of the target, top_drop, min_drop,
+    sum_drop), rows_i int32 [N, 6] = (base_pred, target, code, units, flips, top_unit)}: what ``metrics.attribution_report`` reads.
+    ``per_variant=True`` extends the copy by vals float64 [M, 3] = (drop, dp, kl) and ints int32 [M, 2] = (arg-max, code)."""
+    import numpy as np
+    N, V, M, nb = buf["shape"]
+    at = buf["at"]
+    h = buf["flat"][:at["cell"] if per_variant else at["vals"]].cpu().numpy()
+    out = {"head": h[:at["table_i"]].view(np.int64), "table_i": h[at["table_i"]:at["table_d"]].view(np.int64).reshape(V, nb, 3),
+           "table_d": h[at["table_d"]:at["rows_d"]].view(np.float64).reshape(V, nb, 2),
+           "rows_d": h[at["rows_d"]:at["rows_i"]].view(np.float64).reshape(N, 4), "rows_i": h[at["rows_i"]:at["rows_i"] + 6 * N].reshape(N, 6)}
+    if per_variant:
+        out.update(vals=h[at["vals"]:at["ints"]].view(np.float64).reshape(M, 3), ints=h[at["ints"]:at["cell"]].reshape(M, 2))
+    return out
+
+
 def scatter_logp(logp, rows, out, state=None):
     """``out[rows[i], :] = `` row i of ``logp`` float32 [n, V] (``slnlp_scatter_logp``): with ``state`` (a calibration state whose beta
     is read on the device) the row ``scale_logp`` would write, bit for bit; with None the float32 values themselves.  ``rows``: a

@@ -73,6 +73,10 @@ class OutOfFold(LogProbJudge, ClassifierMixin, BaseEstimator):
         """``VotingEnsemble(members, **kw)``: what to predict NEW rows with."""
         return VotingEnsemble(self.members, **kw)
 
+    def attribute(self, *args, **kwargs):
+        raise NotImplementedError("OutOfFold.attribute: out-of-fold log-probs exist only for the cross-fitted rows themselves, not for "
+                                  "occluded variants of them; attribute with a member or with ensemble()")
+
     def _refuse_other_data(self, ds):
         own = self.dataset
         same = len(ds) == self.rows_ and (own is None or ds is own or (np.array_equal(ds.y, own.y) and np.array_equal(ds.lengths, own.lengths)

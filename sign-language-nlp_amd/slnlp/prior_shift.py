@@ -8,7 +8,7 @@ Saerens, Latinne and Decaestecker (2002) (``ops.fit_priors``: the maximum-likeli
 method to beat, Alexandari et al. 2020, so the base's fitted temperature is folded in) and re-weights the base's device log-probs
 in place (``ops.shift_logp``) before they reach whatever judges them: the wrapper is a ``slnlp.judge.LogProbJudge``, so
 ``predict_proba``, ``predict``, ``reliability``, ``ranking``, ``predict_topk``, ``error_analysis``, ``score_interval``, ``compare``,
-``conformalize``, ``predict_set``, ``coverage``, ``risk_coverage``, ``fit_rejection``, ``predict_selective`` and ``label_issues`` all see the adapted
+``conformalize``, ``predict_set``, ``coverage``, ``risk_coverage``, ``fit_rejection``, ``predict_selective``, ``label_issues`` and ``attribute`` all see the adapted
 predictions.  No torch arithmetic runs on the device.
 
 "Unlabelled" is honest for the two RNN models only: the reference Transformer feeds the gold label to its decoder (SURVEY.md
