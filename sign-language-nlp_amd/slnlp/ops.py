@@ -2,11 +2,12 @@
 parity tests and by the RNN host code).  Every function launches on torch's
 current stream and fails loudly without a GPU / without the built library."""
 import ctypes as C
+import math
 import numbers
 
 import torch
 
-from . import _lib
+from . import _lib, _packed
 from ._lib import GemmArgs, check, load, ptr, stream_ptr
 
 
@@ -425,23 +426,17 @@ def swap_arenas(a, b):
 
 def score_buffers(N, V, device):
     """The four output tensors of ``score_rows`` for an [N, V] epoch: slices of ONE allocation, so ``score_download`` is one copy."""
-    flat = torch.empty(3 * N + 3 * V + 1, dtype=torch.int32, device=device)
-    return flat[:N], flat[N:2 * N].view(torch.float32), flat[2 * N:3 * N], flat[3 * N:]
+    return _packed.Packed(torch.int32, _score_pieces(N, V), device).views()
+
+
+def _score_pieces(N, V):
+    return (("pred", torch.int32, N, 4), ("picked", torch.float32, N, 4), ("rank", torch.int32, N, 4), ("counts", torch.int32, 3 * V + 1, 4))
 
 
 def score_download(out):
     """``score_rows``' four tensors as numpy arrays: one device-to-host copy when they are ``score_buffers``' slices of one
     allocation, four otherwise."""
-    import numpy as np
-    pred, picked, rank, counts = out
-    N, base = pred.numel(), pred._base
-    if (base is not None and base.dtype == torch.int32 and base.dim() == 1 and base.is_contiguous()
-            and base.numel() == 3 * N + counts.numel() and pred.data_ptr() == base.data_ptr()
-            and picked.data_ptr() == base.data_ptr() + 4 * N and rank.data_ptr() == base.data_ptr() + 8 * N
-            and counts.data_ptr() == base.data_ptr() + 12 * N):
-        h = base.cpu().numpy()
-        return h[:N], h[N:2 * N].view(np.float32), h[2 * N:3 * N], h[3 * N:]
-    return tuple(t.cpu().numpy() for t in out)
+    return _packed.download(out, torch.int32)
 
 
 def score_rows(logp, y, out=None):
@@ -635,8 +630,7 @@ def fit_priors(logp, log_source, state=None, max_iter=200, tol=1e-6, out=None, s
     N, V, ld = _logp_matrix("fit_priors", logp)
     _prior_vector("fit_priors", "log_source", log_source, logp.device, V)
     max_iter = _int_in("fit_priors", "max_iter", max_iter, 0, _lib.PRIOR_MAX_ITER)
-    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not 0.0 <= float(tol) < float("inf"):
-        raise ValueError(f"fit_priors: tol={tol!r}, expected a finite number >= 0")
+    tol = _positive("fit_priors", "tol", tol, zero_ok=True)
     if state is not None:
         _cal_state("fit_priors", state, logp.device)
     with torch.cuda.device(logp.device):
@@ -646,7 +640,7 @@ def fit_priors(logp, log_source, state=None, max_iter=200, tol=1e-6, out=None, s
         if scratch is None:
             scratch = torch.empty(2 * N + V, dtype=torch.float64, device=logp.device)
         _scratch("fit_priors", scratch, logp.device, 2 * N + V)
-        check(load().slnlp_fit_priors(ptr(logp), ld, N, V, ptr(state), ptr(log_source), max_iter, float(tol), ptr(out), ptr(out[3 * V:]),
+        check(load().slnlp_fit_priors(ptr(logp), ld, N, V, ptr(state), ptr(log_source), max_iter, tol, ptr(out), ptr(out[3 * V:]),
                                       ptr(scratch), scratch.numel() * 8, stream_ptr()), "fit_priors")
     return out
 
@@ -681,8 +675,7 @@ def shift_logp(logp, log_w, state=None, out=None):
 def reliability_buffers(N, bins, device):
     """The two output tensors of ``reliability_rows`` for N rows and ``bins`` bins -- rows float64 [N, 4], table float64
     [bins + 1, 4] -- as slices of ONE allocation, so ``reliability_download`` is one copy."""
-    flat = torch.empty(4 * (N + bins + 1), dtype=torch.float64, device=device)
-    return flat[:4 * N].view(N, 4), flat[4 * N:].view(bins + 1, 4)
+    return _packed.Packed(torch.float64, (("rows", torch.float64, (N, 4), 8), ("table", torch.float64, (bins + 1, 4), 8)), device).views()
 
 
 def reliability_rows(logp, y, bins=15, state=None, out=None):
@@ -722,9 +715,8 @@ def ranking_buffers(N, V, device, per_row=True):
     """The two output tensors of ``ranking_rows`` for an [N, V] set of log-probs -- rows int32 [N, 4] (None with
     ``per_row=False``), table float64 [V + 1, 4] -- as slices of ONE allocation: the table comes first, so it is 32-byte aligned
     and ``ranking_download`` copies it alone."""
-    flat = torch.empty(4 * (V + 1) + (2 * N if per_row else 0), dtype=torch.float64, device=device)
-    table = flat[:4 * (V + 1)].view(V + 1, 4)
-    return (flat[4 * (V + 1):].view(torch.int32).view(N, 4) if per_row else None), table
+    p = _packed.Packed(torch.float64, (("table", torch.float64, (V + 1, 4), 8),) + ((("rows", torch.int32, (N, 4), 8),) if per_row else ()), device)
+    return (p.view("rows") if per_row else None), p.view("table")
 
 
 def ranking_rows(logp, y, out=None, per_row=True):
@@ -779,20 +771,28 @@ def conformal_buffers(N, V, device, sets=True):
     the table come first, so ``conformal_download`` copies them alone; the set words are uint32 bit masks held in int32."""
     what = "conformal_buffers"
     N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFORMAL_MAX_V)
-    W = (V + 31) // 32
-    head = 4 + 4 * (V + 1)
-    at_rows = head + N + (N & 1)
-    at_sets = at_rows + 2 * N
-    flat = torch.empty(at_sets + ((N * W + 1) // 2 if sets else 0), dtype=torch.int64, device=device)
-    return {"flat": flat, "shape": (N, V), "state": flat[:4].view(torch.float64), "table": flat[4:head].view(V + 1, 4),
-            "score": flat[head:head + N].view(torch.float64), "rows": flat[at_rows:at_sets].view(torch.int32).view(N, 4),
-            "sets": flat[at_sets:].view(torch.int32)[:N * W].view(N, W) if sets else None}
+    pieces = [("state", torch.float64, 4, 8), ("table", torch.int64, (V + 1, 4), 8), ("score", torch.float64, N, 8),
+              ("rows", torch.int32, (N, 4), 16)] + ([("sets", torch.int32, (N, (V + 31) // 32), 4)] if sets else [])
+    return _packed_dict(_packed.Packed(torch.int64, pieces, device), (N, V), sets=None)
 
 
-def _conformal_buf(what, buf, logp_or_device, N, V):
-    device = logp_or_device
-    if not (isinstance(buf, dict) and buf.get("shape") == (N, V) and buf["flat"].device == device):
-        raise ValueError(f"{what}: buf must be conformal_buffers({N}, {V}, {device!r})")
+def _packed_dict(p, shape, shaped=True, **more):
+    """What a dict-returning ``*_buffers`` hands out: the allocation, the shape it was made for, ``packed`` (the table that laid it
+    out and cuts its downloads), the keys ``more`` and every piece as a device view"""
+    return {"flat": p.flat, "shape": shape, "packed": p, **more, **dict(zip(p.at, p.views(shaped=shaped)))}
+
+
+def _even_ints(name, *shape):
+    """An int32 piece of a buffer whose pieces are all 8-byte aligned: padded to an even length"""
+    n = math.prod(shape)
+    return name, torch.int32, shape, 8, n + (n & 1)
+
+
+def _packed_buf(what, buf, maker, shape, device, more=0):
+    """``buf`` is ``maker``'s dict for a shape that begins with ``shape`` (``more`` further entries), on ``device`` (None: any)"""
+    if not (isinstance(buf, dict) and len(buf.get("shape", ())) == len(shape) + more and buf["shape"][:len(shape)] == shape
+            and (device is None or buf["flat"].device == device)):
+        raise ValueError(f"{what}: buf must be {maker}")
 
 
 def _conformal_state(what, name, t, device):
@@ -826,7 +826,7 @@ def conformal_rows(logp, y=None, buf=None, *, method="aps", lam=0.0, k_reg=0, ra
     with torch.cuda.device(logp.device):
         if buf is None:
             buf = conformal_buffers(N, V, logp.device, sets=qhat is not None)
-        _conformal_buf(what, buf, logp.device, N, V)
+        _packed_buf(what, buf, f"conformal_buffers({N}, {V}, {logp.device!r})", (N, V), logp.device)
         sets = buf["sets"] if qhat is not None else None
         check(load().slnlp_conformal_rows(ptr(logp), ld, ptr(y), N, V, ptr(state), _lib.CONFORMAL_METHODS[method], float(lam), k_reg,
                                           1 if randomized else 0, seed, draw, ptr(qhat), ptr(buf["score"]) if y is not None else None,
@@ -865,10 +865,9 @@ def conformal_download(buf, rows=False, sets=False, score=False):
     state float64 [4], table int64 [V + 1, 4]} (a piece no call has written yet holds whatever the allocation held) -- and, only
     on request, one further copy each for ``rows`` int32 [N, 4], ``sets`` uint32 [N, W] and ``score`` float64 [N]."""
     import numpy as np
-    N, V = buf["shape"]
-    h = buf["flat"][:4 + 4 * (V + 1)].cpu().numpy()
-    st = h[:4].view(np.float64)
-    out = {"state": st, "table": h[4:].reshape(V + 1, 4), "qhat": float(st[0]), "n": st[1], "k": st[2], "excluded": st[3]}
+    out = buf["packed"].cut("state", "table")
+    st = out["state"]
+    out.update(qhat=float(st[0]), n=st[1], k=st[2], excluded=st[3])
     if rows:
         out["rows"] = buf["rows"].cpu().numpy()
     if sets:
@@ -889,17 +888,9 @@ def selective_buffers(N, device):
     over in one copy."""
     N = _int_in("selective_buffers", "N", N, 1, _lib.SEL_MAX_ROWS)
     head = _lib.SEL_TABLE_HEAD + (N + _lib.SEL_CHUNK - 1) // _lib.SEL_CHUNK
-    at_rows = head + N + ((head + N) & 1)
-    at_counts = at_rows + 2 * N
-    flat = torch.empty(at_counts + N, dtype=torch.float64, device=device)
-    return {"flat": flat, "shape": (N,), "at": (head, at_rows, at_counts), "table": flat[:head], "kappa": flat[head:head + N],
-            "rows": flat[at_rows:at_counts].view(torch.int32).view(N, 4), "counts": flat[at_counts:].view(torch.int32).view(N, 2),
-            "levels": None}
-
-
-def _selective_buf(what, buf, device, N):
-    if not (isinstance(buf, dict) and buf.get("shape") == (N,) and buf["flat"].device == device):
-        raise ValueError(f"{what}: buf must be selective_buffers({N}, {device!r})")
+    p = _packed.Packed(torch.float64, (("table", torch.float64, head, 8), ("kappa", torch.float64, N, 8), ("rows", torch.int32, (N, 4), 16),
+                                       ("counts", torch.int32, (N, 2), 4)), device)
+    return _packed_dict(p, (N,), at=(p.begin("kappa"), p.begin("rows"), p.begin("counts")), levels=None)
 
 
 def _selective_levels(what, name, values):
@@ -936,7 +927,7 @@ def selective_rows(logp, y=None, buf=None, *, score="max_prob", state=None, tau=
     with torch.cuda.device(logp.device):
         if buf is None:
             buf = selective_buffers(N, logp.device)
-        _selective_buf(what, buf, logp.device, N)
+        _packed_buf(what, buf, f"selective_buffers({N}, {logp.device!r})", (N,), logp.device)
         check(load().slnlp_selective_rows(ptr(logp), ld, ptr(y), N, V, _lib.SEL_SCORES[score], ptr(state), ptr(tau), ptr(buf["kappa"]),
                                           ptr(buf["rows"]), stream_ptr()), what)
     return buf
@@ -949,8 +940,7 @@ def selective_counts(buf, risks=(), coverages=()):
     each; ``slnlp_selective_counts``, include/slnlp.h).  Returns the table.  Three queued launches; no host wait."""
     _lib.require_gpu()
     what = "selective_counts"
-    if not (isinstance(buf, dict) and "kappa" in buf and "counts" in buf):
-        raise ValueError(f"{what}: buf must be selective_buffers(N, device)")
+    _packed_buf(what, buf, "selective_buffers(N, device)", (), None, more=1)
     N, = buf["shape"]
     risks, coverages = _selective_levels(what, "risks", risks), _selective_levels(what, "coverages", coverages)
     r, c = (C.c_double * max(1, len(risks)))(*risks), (C.c_double * max(1, len(coverages)))(*coverages)
@@ -966,16 +956,10 @@ def selective_download(buf, counts=True):
     device: {kappa float64 [N], rows int32 [N, 4], counts int32 [N, 2], table float64 [40 + chunks], risks, coverages} (a piece no
     call has written yet holds whatever the allocation held).  ``counts=False``: kappa and rows alone, 24 bytes a row (what
     ``selective_rows`` by itself writes)."""
-    import numpy as np
-    N, = buf["shape"]
-    head, at_rows, at_counts = buf["at"]
     if not counts:
-        h = buf["flat"][head:at_counts].cpu().numpy()
-        return {"kappa": h[:N], "rows": h[at_rows - head:].view(np.int32).reshape(N, 4)}
-    h = buf["flat"].cpu().numpy()
+        return buf["packed"].cut("kappa", "rows")
     risks, coverages = buf["levels"] if buf["levels"] is not None else ([], [])
-    return {"table": h[:head], "kappa": h[head:head + N], "rows": h[at_rows:at_counts].view(np.int32).reshape(N, 4),
-            "counts": h[at_counts:].view(np.int32).reshape(N, 2), "risks": list(risks), "coverages": list(coverages)}
+    return {**buf["packed"].cut("table", "counts"), "risks": list(risks), "coverages": list(coverages)}
 
 
 def error_analysis_buffers(N, V, k, M, device):
@@ -992,24 +976,14 @@ def error_analysis_buffers(N, V, k, M, device):
     what = "error_analysis_buffers"
     N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
     k, M = _int_in(what, "k", k or 0, 0, min(V, _lib.TOPK_MAX)), _int_in(what, "M", M, 1, _lib.PAIRS_MAX)
-    work_bytes = load().slnlp_confusion_pairs_workspace_bytes(V, M)
-    at, off = {}, 0
-    for name, n, align8 in (("confusion", V * V + 1, False), ("pairs", 3 * M, False), ("counts", 3 * V + 1, False),
-                            ("topk_idx", N * k, True), ("topk_prob", 2 * N * k, True), ("pred", N, False), ("picked", N, False),
-                            ("rank", N, False), ("work", work_bytes // 4, True)):
-        if align8:                                           # an even int32 offset: 8-byte aligned (one pad entry where needed)
-            off += off & 1
-        at[name] = (off, n)
-        off += n
-    flat = torch.empty(off, dtype=torch.int32, device=device)
-    buf = {name: flat[begin:begin + n] for name, (begin, n) in at.items()}
-    buf["pairs"] = buf["pairs"].view(M, 3)
-    buf["picked"] = buf["picked"].view(torch.float32)
-    buf["topk_idx"] = buf["topk_idx"].view(N, k) if k else None
-    buf["topk_prob"] = buf["topk_prob"].view(torch.float64).view(N, k) if k else None
-    buf["work"] = buf["work"].view(torch.uint8)
-    buf.update(flat=flat, at=at, score=(buf["pred"], buf["picked"], buf["rank"], buf["counts"]),
-               topk=(buf["topk_idx"], buf["topk_prob"]) if k else None, shape=(N, V, k, M))
+    pred, picked, rank, counts = _score_pieces(N, V)
+    p = _packed.Packed(torch.int32, (("confusion", torch.int32, V * V + 1, 4), ("pairs", torch.int32, (M, 3), 4), counts,
+                                     ("topk_idx", torch.int32, (N, k), 8), ("topk_prob", torch.float64, (N, k), 8), pred, picked, rank,
+                                     ("work", torch.uint8, load().slnlp_confusion_pairs_workspace_bytes(V, M), 8)), device)
+    buf = _packed_dict(p, (N, V, k, M), at={name: (p.begin(name), p.end(name) - p.begin(name)) for name in p.at})
+    if not k:
+        buf["topk_idx"] = buf["topk_prob"] = None
+    buf.update(score=(buf["pred"], buf["picked"], buf["rank"], buf["counts"]), topk=(buf["topk_idx"], buf["topk_prob"]) if k else None)
     return buf
 
 
@@ -1020,40 +994,24 @@ def error_analysis_download(buf, matrix=True, topk=False):
     ``topk_idx`` int32 [N, k] and ``topk_prob`` float64 [N, k] or None."""
     import numpy as np
     N, V, k, M = buf["shape"]
-    at = buf["at"]
-    begin = at["confusion"][0] if matrix else at["pairs"][0]
-    end = sum(at["topk_prob"]) if topk and k else sum(at["counts"])
-    h = buf["flat"][begin:end].cpu().numpy()
-    piece = lambda name: h[at[name][0] - begin:at[name][0] - begin + at[name][1]]
-    out = {"pairs": piece("pairs").reshape(M, 3), "counts": piece("counts").astype(np.int64), "confusion": None, "skipped": None,
-           "topk_idx": None, "topk_prob": None}
+    h = buf["packed"].cut("confusion" if matrix else "pairs", "topk_prob" if topk and k else "counts")
+    out = {"pairs": h["pairs"], "counts": h["counts"].astype(np.int64), "confusion": None, "skipped": None,
+           "topk_idx": h.get("topk_idx"), "topk_prob": h.get("topk_prob")}
     if matrix:
-        out["confusion"], out["skipped"] = piece("confusion")[:V * V].reshape(V, V).astype(np.int64), int(piece("confusion")[V * V])
-    if topk and k:
-        out["topk_idx"] = piece("topk_idx").reshape(N, k)
-        out["topk_prob"] = piece("topk_prob").copy().view(np.float64).reshape(N, k)    # (the copy: 8-byte aligned on the host too)
+        out["confusion"], out["skipped"] = h["confusion"][:V * V].reshape(V, V).astype(np.int64), int(h["confusion"][V * V])
     return out
 
 
 def topk_buffers(N, k, device):
     """The two output tensors of ``topk_rows`` -- idx int32 [N, k], prob float64 [N, k] -- as slices of ONE allocation (the
     probabilities first: they need the 8-byte alignment), so ``topk_download`` is one copy."""
-    flat = torch.empty(3 * N * k, dtype=torch.int32, device=device)
-    return flat[2 * N * k:].view(N, k), flat[:2 * N * k].view(torch.float64).view(N, k)
+    return _packed.Packed(torch.int32, (("prob", torch.float64, (N, k), 8), ("idx", torch.int32, (N, k), 4)), device).views("idx", "prob")
 
 
 def topk_download(out):
     """``topk_rows``' two tensors as numpy arrays (idx int32 [N, k], prob float64 [N, k]): one device-to-host copy when they are
     ``topk_buffers``' slices of one allocation, two otherwise."""
-    import numpy as np
-    idx, prob = out
-    n = idx.numel()
-    if (idx.is_contiguous() and prob.is_contiguous() and idx.untyped_storage().data_ptr() == prob.untyped_storage().data_ptr()
-            and idx.storage_offset() == 2 * prob.storage_offset() + 2 * n):
-        flat = torch.empty(0, dtype=torch.int32, device=idx.device).set_(idx.untyped_storage(), 2 * prob.storage_offset(), (3 * n,))
-        h = flat.cpu().numpy()
-        return h[2 * n:].reshape(idx.shape), h[:2 * n].view(np.float64).reshape(prob.shape)
-    return idx.cpu().numpy(), prob.cpu().numpy()
+    return _packed.download(out[::-1], torch.int32)[::-1]
 
 
 def topk_rows(logp, k, state=None, out=None):
@@ -1135,9 +1093,6 @@ def error_analysis_rows(logp, y, buf, state=None):
     return buf
 
 
-_AUDIT_PIECES = ("t", "s", "m", "n", "joint", "pairs", "k", "code", "flags", "pred", "other", "p_pred", "work")
-
-
 def label_audit_buffers(N, V, pairs, device):
     """The device buffer of one label audit of an [N, V] set of log-probs with ``pairs`` likely label swaps, ONE int32 allocation
     laid out as include/slnlp.h states (every piece 8-byte aligned, int32 pieces padded to an even length):
@@ -1149,16 +1104,12 @@ def label_audit_buffers(N, V, pairs, device):
     what = "label_audit_buffers"
     N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
     M = _int_in(what, "pairs", pairs, 1, _lib.PAIRS_MAX)
-    even = lambda n: n + (n & 1)
-    sizes = {"t": 2 * V, "s": 2 * N, "m": 2 * N, "n": even(V), "joint": even(V * V + 1), "pairs": even(3 * M), "k": even(N),
-             "code": even(N), "flags": even(N), "pred": even(N), "other": 2 * N, "p_pred": 2 * N,
-             "work": load().slnlp_confusion_pairs_workspace_bytes(V, M) // 4}
-    at, off = {}, _lib.AUDIT_HEAD_BYTES // 4                 # in int32 entries
-    for name in _AUDIT_PIECES:
-        at[name] = off
-        off += sizes[name]
-    flat = torch.empty(off, dtype=torch.int32, device=device)
-    return {"flat": flat, "at": at, "end": off, "shape": (N, V, M)}
+    reals = lambda name, n: (name, torch.float64, n, 8)
+    p = _packed.Packed(torch.int32, (("head", torch.int64, _lib.AUDIT_HEAD_BYTES // 8, 8), reals("t", V), reals("s", N), reals("m", N),
+                                     _even_ints("n", V), _even_ints("joint", V * V + 1), _even_ints("pairs", M, 3), _even_ints("k", N),
+                                     _even_ints("code", N), _even_ints("flags", N), _even_ints("pred", N), reals("other", N), reals("p_pred", N),
+                                     ("work", torch.uint8, load().slnlp_confusion_pairs_workspace_bytes(V, M), 8)), device)
+    return {"flat": p.flat, "at": {name: p.begin(name) for name in p.at if name != "head"}, "end": p.flat.numel(), "shape": (N, V, M), "packed": p}
 
 
 def label_audit_rows(logp, y, buf=None, *, state=None, pairs=20):
@@ -1178,8 +1129,7 @@ def label_audit_rows(logp, y, buf=None, *, state=None, pairs=20):
     with torch.cuda.device(logp.device):
         if buf is None:
             buf = label_audit_buffers(N, V, pairs, logp.device)
-        if not (isinstance(buf, dict) and buf.get("shape", (0, 0, 0))[:2] == (N, V) and buf["flat"].device == logp.device):
-            raise ValueError(f"{what}: buf must be label_audit_buffers({N}, {V}, pairs, {logp.device!r})")
+        _packed_buf(what, buf, f"label_audit_buffers({N}, {V}, pairs, {logp.device!r})", (N, V), logp.device, more=1)
         check(load().slnlp_label_audit(ptr(logp), ld, ptr(y), N, V, ptr(state), buf["shape"][2], ptr(buf["flat"]),
                                        buf["flat"].numel() * 4, stream_ptr()), what)
     return buf
@@ -1191,17 +1141,9 @@ def label_audit_download(buf, per_row=False):
     [V, V], overflow, pairs int32 [M, 3], k / code / flags int32 [N], s / m float64 [N]}: what ``metrics.label_audit_report`` reads.
     ``per_row=True`` extends the copy by pred int32 [N], other and p_pred float64 [N]."""
     import numpy as np
-    N, V, M = buf["shape"]
-    at = buf["at"]
-    end = at["work"] if per_row else at["pred"]
-    h = buf["flat"][:end].cpu().numpy()
-    ints = lambda name, n: h[at[name]:at[name] + n]
-    reals = lambda name, n: h[at[name]:at[name] + 2 * n].view(np.float64)
-    out = {"head": h[:_lib.AUDIT_HEAD_BYTES // 4].view(np.int64), "t": reals("t", V), "s": reals("s", N), "m": reals("m", N),
-           "n": ints("n", V), "joint": ints("joint", V * V).reshape(V, V).astype(np.int64), "overflow": int(ints("joint", V * V + 1)[-1]),
-           "pairs": ints("pairs", 3 * M).reshape(M, 3), "k": ints("k", N), "code": ints("code", N), "flags": ints("flags", N)}
-    if per_row:
-        out.update(pred=ints("pred", N), other=reals("other", N), p_pred=reals("p_pred", N))
+    V = buf["shape"][1]
+    out = buf["packed"].cut("head", "p_pred" if per_row else "flags")
+    out.update(joint=out["joint"][:V * V].reshape(V, V).astype(np.int64), overflow=int(out["joint"][V * V]))
     return out
 
 
@@ -1285,9 +1227,6 @@ def occlude_rows(X, L, y, variants, kind, *, width=1, stride=1, pad=1, unk=0, su
     return Xo, Lo, yo
 
 
-_ATTR_PIECES = ("head", "table_i", "table_d", "rows_d", "rows_i", "vals", "ints", "cell", "variants", "row_start")
-
-
 def attribution_buffers(N, V, variants, row_start, n_bins, device):
     """The device buffer of one attribution of N rows of V classes under a variant table (``occlusion_variants``' host arrays,
     uploaded here), ONE int32 allocation, every piece 8-byte aligned (int32 pieces padded to an even length):
@@ -1307,20 +1246,12 @@ def attribution_buffers(N, V, variants, row_start, n_bins, device):
         raise ValueError(f"{what}: variants int32 [M, 3] with M in 1..{(2 ** 31 - 1) // 3} and row_start int32 [{N + 1}] expected, got "
                          f"{variants.shape} and {row_start.shape}")
     M = int(variants.shape[0])
-    even = lambda n: n + (n & 1)
-    sizes = {"head": _lib.ATTR_HEAD_BYTES // 4, "table_i": 6 * V * nb, "table_d": 4 * V * nb, "rows_d": 8 * N, "rows_i": even(6 * N),
-             "vals": 6 * M, "ints": 2 * M, "cell": even(M), "variants": even(3 * M), "row_start": even(N + 1)}
-    at, off = {}, 0
-    for name in _ATTR_PIECES:
-        at[name] = off
-        off += sizes[name]
-    flat = torch.empty(off, dtype=torch.int32, device=device)
-    piece = lambda name, n, dtype=torch.int32: flat[at[name]:at[name] + n].view(dtype)
-    buf = {"flat": flat, "at": at, "end": off, "shape": (N, V, M, nb),
-           "head": piece("head", 16, torch.int64), "table_i": piece("table_i", 6 * V * nb, torch.int64),
-           "table_d": piece("table_d", 4 * V * nb, torch.float64), "rows_d": piece("rows_d", 8 * N, torch.float64),
-           "rows_i": piece("rows_i", 6 * N), "vals": piece("vals", 6 * M, torch.float64), "ints": piece("ints", 2 * M),
-           "cell": piece("cell", M), "variants": piece("variants", 3 * M).view(M, 3), "row_start": piece("row_start", N + 1)}
+    p = _packed.Packed(torch.int32, (("head", torch.int64, _lib.ATTR_HEAD_BYTES // 8, 8), ("table_i", torch.int64, (V, nb, 3), 8),
+                                     ("table_d", torch.float64, (V, nb, 2), 8), ("rows_d", torch.float64, (N, 4), 8),
+                                     _even_ints("rows_i", N, 6), ("vals", torch.float64, (M, 3), 8), _even_ints("ints", M, 2),
+                                     _even_ints("cell", M), _even_ints("variants", M, 3), _even_ints("row_start", N + 1)), device)
+    buf = _packed_dict(p, (N, V, M, nb), shaped=False, at={name: p.begin(name) for name in p.at}, end=p.flat.numel())
+    buf["variants"] = buf["variants"].view(M, 3)             # (the other pieces in one dimension, as the kernels index them)
     buf["variants"].copy_(torch.from_numpy(variants))
     buf["row_start"].copy_(torch.from_numpy(row_start))
     return buf
@@ -1328,8 +1259,7 @@ def attribution_buffers(N, V, variants, row_start, n_bins, device):
 
 def _attribution_args(what, base, y, buf, target, state):
     N, V, ld = _logp_matrix(what, base)
-    if not (isinstance(buf, dict) and buf.get("shape", (0, 0))[:2] == (N, V) and buf["flat"].device == base.device):
-        raise ValueError(f"{what}: buf must be attribution_buffers({N}, {V}, ...) on {base.device}")
+    _packed_buf(what, buf, f"attribution_buffers({N}, {V}, ...) on {base.device}", (N, V), base.device, more=2)
     if target not in _lib.ATTR_TARGETS:
         raise ValueError(f"{what}: target={target!r}, expected one of {_lib.ATTR_TARGETS}")
     if y is not None or target == "label":
@@ -1384,16 +1314,7 @@ def attribution_download(buf, per_variant=False):
     float64 [V, n_bins, 2] = (sum drop, sum kl), rows_d float64 [N, 4] = (base log-prob of the target, top_drop, min_drop,
     sum_drop), rows_i int32 [N, 6] = (base_pred, target, code, units, flips, top_unit)}: what ``metrics.attribution_report`` reads.
     ``per_variant=True`` extends the copy by vals float64 [M, 3] = (drop, dp, kl) and ints int32 [M, 2] = (arg-max, code)."""
-    import numpy as np
-    N, V, M, nb = buf["shape"]
-    at = buf["at"]
-    h = buf["flat"][:at["cell"] if per_variant else at["vals"]].cpu().numpy()
-    out = {"head": h[:at["table_i"]].view(np.int64), "table_i": h[at["table_i"]:at["table_d"]].view(np.int64).reshape(V, nb, 3),
-           "table_d": h[at["table_d"]:at["rows_d"]].view(np.float64).reshape(V, nb, 2),
-           "rows_d": h[at["rows_d"]:at["rows_i"]].view(np.float64).reshape(N, 4), "rows_i": h[at["rows_i"]:at["rows_i"] + 6 * N].reshape(N, 6)}
-    if per_variant:
-        out.update(vals=h[at["vals"]:at["ints"]].view(np.float64).reshape(M, 3), ints=h[at["ints"]:at["cell"]].reshape(M, 2))
-    return out
+    return buf["packed"].cut("head", "ints" if per_variant else "rows_i")
 
 
 def scatter_logp(logp, rows, out, state=None):
@@ -1421,26 +1342,17 @@ def bootstrap_buffers(B, V, Q, counts, device):
     """The output tensors of ``bootstrap_scores`` for ``B`` replicates over ``V`` classes with ``Q`` value columns -- stats
     float64 [B, 9 + Q] and, with ``counts``, counts int32 [B, 3 V + 1] (else None) -- as slices of ONE allocation, so
     ``bootstrap_download`` is one copy."""
-    n_stats, n_counts = B * (_lib.BOOT_FIXED + Q), B * (3 * V + 1) if counts else 0
-    flat = torch.empty(n_stats + (n_counts + 1) // 2, dtype=torch.float64, device=device)
-    return flat[:n_stats].view(B, _lib.BOOT_FIXED + Q), (flat[n_stats:].view(torch.int32)[:n_counts].view(B, 3 * V + 1) if counts else None)
+    p = _packed.Packed(torch.float64, (("stats", torch.float64, (B, _lib.BOOT_FIXED + Q), 8),)
+                       + ((("counts", torch.int32, (B, 3 * V + 1), 4),) if counts else ()), device)
+    return p.view("stats"), (p.view("counts") if counts else None)
 
 
 def bootstrap_download(out):
     """``bootstrap_scores``' result as numpy arrays ``(stats float64 [B, 9 + Q], counts int32 [B, 3 V + 1] or None)``: one
     device-to-host copy when they are ``bootstrap_buffers``' slices of one allocation (it waits for the launch), two otherwise."""
-    import numpy as np
-    stats, counts = out
-    if counts is None:
-        return stats.cpu().numpy(), None
-    n, words = stats.numel(), (counts.numel() + 1) // 2
-    if (stats.is_contiguous() and counts.is_contiguous() and stats.untyped_storage().data_ptr() == counts.untyped_storage().data_ptr()
-            and counts.storage_offset() == 2 * (stats.storage_offset() + n)
-            and stats.untyped_storage().nbytes() >= 8 * (stats.storage_offset() + n + words)):
-        flat = torch.empty(0, dtype=torch.float64, device=stats.device).set_(stats.untyped_storage(), stats.storage_offset(), (n + words,))
-        h = flat.cpu().numpy()
-        return h[:n].reshape(stats.shape), h[n:].view(np.int32)[:counts.numel()].reshape(counts.shape)
-    return stats.cpu().numpy(), counts.cpu().numpy()
+    if out[1] is None:
+        return out[0].cpu().numpy(), None
+    return _packed.download(out, torch.float64)
 
 
 def bootstrap_scores(y, pred, rank, values=None, *, n_classes, top_k=0, replicates, seed, counts=False, out=None):
@@ -1502,17 +1414,10 @@ def score_interval_buffers(N, V, B, device, bins=15):
     what = "score_interval_buffers"
     N, V = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "V", V, 1, _lib.CONFUSION_MAX_V)
     B, bins = _int_in(what, "B", B, 1, _lib.BOOT_MAX_REPLICATES), _int_in(what, "bins", bins, 1, _lib.REL_MAX_BINS)
-    pad4 = lambda n: (n + 3) // 4 * 4
-    n_stats, n_ints = B * (_lib.BOOT_FIXED + 3), 3 * N + 3 * V + 1
-    o_table = pad4(n_stats)
-    o_ints = o_table + 4 * (bins + 1)
-    o_rows = pad4(o_ints + (n_ints + 1) // 2)
-    flat = torch.empty(o_rows + 4 * N, dtype=torch.float64, device=device)
-    ints = flat[o_ints:o_rows].view(torch.int32)
-    score = (ints[:N], ints[N:2 * N].view(torch.float32), ints[2 * N:3 * N], ints[3 * N:n_ints])
-    return {"flat": flat, "shape": (N, V, B, bins), "head": o_ints + (n_ints + 1) // 2, "at": (o_table, o_ints), "score": score,
-            "reliability": (flat[o_rows:].view(N, 4), flat[o_table:o_ints].view(bins + 1, 4)),
-            "boot": (flat[:n_stats].view(B, _lib.BOOT_FIXED + 3), None)}
+    p = _packed.Packed(torch.float64, (("stats", torch.float64, (B, _lib.BOOT_FIXED + 3), 8), ("table", torch.float64, (bins + 1, 4), 32),
+                                       *_score_pieces(N, V), ("rows", torch.float64, (N, 4), 32)), device)
+    return {"flat": p.flat, "shape": (N, V, B, bins), "head": p.end("counts"), "at": (p.begin("table"), p.begin("pred")), "packed": p,
+            "score": p.views("pred", "picked", "rank", "counts"), "reliability": p.views("rows", "table"), "boot": (p.view("stats"), None)}
 
 
 def score_interval_rows(logp, y, buf, *, top_k=0, seed=0, state=None):
@@ -1531,12 +1436,8 @@ def score_interval_download(buf):
     arrays -- ``stats`` float64 [B, 12], ``table`` float64 [bins + 1, 4], ``pred`` int32 [N], ``rank`` int32 [N], ``counts`` int64
     [3 V + 1]."""
     import numpy as np
-    N, V, B, bins = buf["shape"]
-    o_table, o_ints = buf["at"]
-    h = buf["flat"][:buf["head"]].cpu().numpy()
-    ints = h[o_ints:].view(np.int32)
-    return {"stats": h[:B * (_lib.BOOT_FIXED + 3)].reshape(B, _lib.BOOT_FIXED + 3), "table": h[o_table:o_ints].reshape(bins + 1, 4),
-            "pred": ints[:N], "rank": ints[2 * N:3 * N], "counts": ints[3 * N:3 * N + 3 * V + 1].astype(np.int64)}
+    h = buf["packed"].cut("stats", "counts")
+    return {"stats": h["stats"], "table": h["table"], "pred": h["pred"], "rank": h["rank"], "counts": h["counts"].astype(np.int64)}
 
 
 def ensemble_rows(logps, states=None, weights=None, voting="soft", diagnostics=True, out=None):
