@@ -837,6 +837,67 @@ int slnlp_label_audit(const float* logp, int64_t ld, const int64_t* y, int64_t N
 int slnlp_scatter_logp(const float* logp, int64_t ld, int64_t n, int64_t V, const double* beta_dev, const int64_t* rows, float* out,
                        int64_t ld_out, int64_t N_out, void* stream);
 
+/* ---------------------------------------------------------- training dynamics --
+ * What happened to every train row DURING a fit, kept on the device epoch by epoch (NeuralNetClassifier(train_dynamics=True);
+ * slnlp/metrics.py's train_dynamics_report): dataset cartography (Swayamdipta et al. 2020: confidence, variability, correctness),
+ * forgetting events (Toneva et al. 2019) and the area under the margin, AUM (Pleiss et al. 2020).  The statistics describe the
+ * memorisation itself, so -- unlike the label audit -- they are meant for a fit's own train rows.  tests/train_dynamics_ref.py
+ * restates everything below in numpy.
+ *
+ * One call takes ONE epoch's train log-probs: logp float32 [n_visit, ld], V <= ld columns used (padding is never read), in VISIT
+ * order; y int64 [n_visit] the labels in visit order; order int64 [n_visit] the dataset row r of visit i (NULL: r = i); N the rows
+ * of the dataset; epoch >= 1 its number.  ALL PER-ROW STATE IS INTEGER, so the result is a pure function of the arguments: it
+ * depends neither on the order of the visits within the epoch nor on the order in which atomics land, and no floating-point atomic
+ * is involved (under a balanced resample a row is visited several times per epoch: visits to one row do collide).  Per visit i:
+ *   code     -3: r lies outside [0, N) (never used as an address); -2: the row holds a NaN or its maximum is not finite (looked at
+ *            before the label, as in slnlp_label_audit); -1: the label lies outside [0, V) (never used as an index); else 0.  Only a
+ *            visit with code 0 is USABLE: the others enter no sum and no count but the head's three skipped counts.
+ *   pred     the arg-max in slnlp_score_rows' order (a NaN first, larger values first, equal values by ascending column); written
+ *            for every code.  correct = (pred == y_i), 0 for an unusable visit
+ *   q        uint64 rint(min(p, 1) 2^20) with p = p_{i, y_i}, slnlp_label_audit's self-confidence at beta = 1 bit for bit
+ *            (1 / s0 for a label at the maximum, exp(z_iy - a) / s0 otherwise, on slnlp_topk_rows' fp64 row head); 0 if unusable
+ *   mq       int64 rint(clamp((double)z_iy - (double)z_i,other, -1024, 1024) 2^20), `other` the first column other than y_i in
+ *            the arg-max's order; 0 for V = 1 and for an unusable visit.  Both operands are float32, so the difference is exact
+ *            in fp64 and mq restatable bit for bit; a label at -inf gives -1024 2^20, a label that is the only finite column
+ *            +1024 2^20.  No exp is involved
+ * and a usable visit adds into row r with integer atomics: v_e += 1, c_e += correct (the epoch's scratch), sum_q += q,
+ * sum_q2 += q q, sum_mq += mq (two's complement).  Then THE FOLD, per dataset row with v_e > 0:
+ *   a = (c_e == v_e), the row was right at EVERY visit of the epoch;
+ *   visits += v_e; correct_visits += c_e; epochs_seen += 1; epochs_correct += a; forgetting += (last == 1 && !a);
+ *   first_learned = epoch if it is still -1 and a holds; last = a (-1: never seen); v_e = c_e = 0.
+ * With one visit per epoch that is Toneva's forgetting event at epoch granularity.  A row whose visits reach 2^23
+ * (SLNLP_DYN_VISIT_BITS) sets the head's overflow flag: q q <= 2^40, so sum_q2 < 2^63 up to 2^23 visits; |mq| <= 2^30, so
+ * |sum_mq| < 2^53.  Beyond it the sums wrap.
+ *
+ * state, in bytes from its start, with e(x) = x rounded up to an even number (every piece is 8-byte aligned):
+ *   head     int64 [8]: epochs folded, usable visits, bad labels (code -1), NaN rows (-2), bad row indices (-3), rows seen so far,
+ *            overflow (0 / 1), 0 -- all cumulative over the calls since the reset
+ *   sum_q    uint64 [N]         sum_q2         uint64 [N]        sum_mq         int64 [N]
+ *   visits   uint32 [e(N)]      correct_visits uint32 [e(N)]     epochs_seen    int32 [e(N)]
+ *   epochs_correct int32 [e(N)] forgetting     int32 [e(N)]      first_learned  int32 [e(N)]      last  int32 [e(N)]
+ *   v_e      uint32 [e(N)]      c_e            uint32 [e(N)]
+ * in this order, SLNLP_DYN_HEAD_BYTES first: slnlp_train_dynamics_state_bytes(N) in all (-1 and a message for N outside
+ * 1..INT32_MAX).  What a report needs ends with last.  visits, the per-visit scratch of ONE call (overwritten by the next):
+ *   q uint64 [n]    mq int64 [n]    code int32 [e(n)]    correct int32 [e(n)]    pred int32 [e(n)]      with n = n_visit:
+ * 16 n + 12 e(n) bytes, which visits_bytes must cover.
+ *
+ * slnlp_train_dynamics_reset: one launch of the library's own that zeroes the state and sets first_learned and last to -1.
+ * slnlp_train_dynamics_epoch: a fixed sequence of two launches on the stream, no host wait: the visits (a wave per visit
+ * position), the fold (a thread per dataset row and per visit position; the head's counts are integer sums over a fixed tree per
+ * block and one integer atomic per block and count).
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null logp, y, state or visits; N, n_visit or epoch
+ * outside 1..INT32_MAX; V outside 1..INT32_MAX; ld < V; state_bytes or visits_bytes too small; a misaligned pointer (logp 4 bytes;
+ * y, order, state, visits 8); state or visits overlapping an input or each other. */
+#define SLNLP_DYN_HEAD_BYTES 64
+#define SLNLP_DYN_FRAC_BITS 20          /* q and mq are fixed point with this many fraction bits */
+#define SLNLP_DYN_VISIT_BITS 23         /* a row at 2^23 visits sets the overflow flag */
+int64_t slnlp_train_dynamics_state_bytes(int64_t N);
+int slnlp_train_dynamics_reset(void* state, int64_t state_bytes, int64_t N, void* stream);
+int slnlp_train_dynamics_epoch(const float* logp, int64_t ld, const int64_t* y, const int64_t* order, int64_t n_visit, int64_t V,
+                               int64_t N, int64_t epoch, void* state, int64_t state_bytes, void* visits, int64_t visits_bytes,
+                               void* stream);
+
 /* -------------------------------------------------------------- batch gather --
  * One train batch in visit order (a shuffled epoch, iterator_train__shuffle): row i of the outputs is row
  * order[row0 + i] of the dataset X int64 [rows, S] / lengths int64 [rows] / y int64 [rows]; order == NULL: row row0 + i.

@@ -6,7 +6,7 @@
 //
 // z float32 log-probs [N, ld] (V columns used), y int64 [N], beta = beta_dev ? beta_dev[0] : 1; everything but z is fp64.  A row is
 // USABLE when logp_row_argmax(...).finite holds (no NaN, a finite maximum: looked at first, code -2 otherwise) and its label lies in
-// [0, V) (code -1 otherwise).  The probability of column c of row i is audit_prob() below on the row head of logp_row.hpp:
+// [0, V) (code -1 otherwise).  The probability of column c of row i is audit_prob() (logp_prob.hpp) on the row head of logp_row.hpp:
 // 1 / s0 for a column at the maximum, exp(beta z_ic - a) / s0 for another -- topk_rows' and reliability_rows' bits.
 //
 // slnlp_label_audit queues a FIXED sequence of eight launches and never waits for the host:
@@ -34,21 +34,13 @@
 #include "block_reduce.hpp"
 #include "common.hpp"
 #include "launch.hpp"
+#include "logp_prob.hpp"
 #include "logp_row.hpp"
 #include "scale_row.hpp"
 #include "spans.hpp"
 
-namespace slnlp {
-
-// The probability of a column with float32 log-prob zf, given the row head (zmax, a, s0) of logp_row.hpp.  It stands IN FRONT of
-// the pragma below on purpose: topk_rows forms `exp(beta * (double)v - a) / s0` under the compiler's default contraction, and
-// this is that expression under that setting (tests/test_label_audit_gpu.py compares the bits).  Passes 1 and 3 both call it.
-__device__ __forceinline__ double audit_prob(float zf, float zmax, double beta, double a, double s0) {
-    return zf == zmax ? 1.0 / s0 : exp(beta * (double)zf - a) / s0;
-}
-
-}  // namespace slnlp
-
+// (audit_prob, the probability of a column given the row head, comes from logp_prob.hpp, included IN FRONT of the pragma below on
+// purpose: it is formed under the compiler's default contraction, as topk_rows forms it.  Passes 1 and 3 both call it.)
 // this file's own arithmetic (s - other, sum / n) is rounded operation by operation, as the restatement's numpy expressions are
 #pragma clang fp contract(off)
 

@@ -148,6 +148,9 @@ SIGNATURES = {
     "slnlp_selective_counts": (i32, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp]),
     "slnlp_label_audit": (i32, [vp, i64, vp, i64, i64, vp, i32, vp, i64, vp]),
     "slnlp_scatter_logp": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp]),
+    "slnlp_train_dynamics_state_bytes": (i64, [i64]),
+    "slnlp_train_dynamics_reset": (i32, [vp, i64, i64, vp]),
+    "slnlp_train_dynamics_epoch": (i32, [vp, i64, vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp]),
     "slnlp_occlude_rows": (i32, [vp, vp, vp, i64, i64, vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
     "slnlp_attribution_rows": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
     "slnlp_attribution_summary": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -306,6 +309,9 @@ SEL_MAX_LEVELS = 8                              # SLNLP_SEL_MAX_LEVELS
 SEL_TABLE_HEAD = 40                             # SLNLP_SEL_TABLE_HEAD
 SEL_MAX_ROWS = 1048576                          # SLNLP_SEL_MAX_ROWS
 AUDIT_HEAD_BYTES = 64                           # SLNLP_AUDIT_HEAD_BYTES
+DYN_HEAD_BYTES = 64                             # SLNLP_DYN_HEAD_BYTES
+DYN_FRAC_BITS = 20                              # SLNLP_DYN_FRAC_BITS
+DYN_VISIT_BITS = 23                             # SLNLP_DYN_VISIT_BITS
 OCCLUDE_KINDS = ("mask", "drop", "substitute")  # SLNLP_OCCLUDE_MASK / _DROP / _SUBSTITUTE
 ATTR_MAX_BINS = 64                              # SLNLP_ATTR_MAX_BINS
 ATTR_HEAD_BYTES = 64                            # SLNLP_ATTR_HEAD_BYTES

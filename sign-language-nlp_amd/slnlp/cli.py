@@ -105,7 +105,20 @@ on, by occlusion.  ``by: field`` builds the substitution table from the config's
 
 (For the Transformer, whose decoder reads the gold label, the drops are conditional on that label.)
 
-Without the nine keys the workdir holds exactly the files listed above.
+A top-level ``train_dynamics: {top: 50}`` (optional, this default) goes to the estimator as ``train_dynamics=True``: every fit folds
+its epochs' train log-probs into per-row integer counts on the device (csrc/train_dynamics.hip), and rank 0 writes what the
+refit's ``train_dynamics()`` holds -- which train rows it never learned, learned and forgot, wavers on:
+
+    train_dynamics.json            rows, rows_seen, unforgettable, never_learned_rows, forgetting_events, epochs, visits, bad_labels,
+                                   nan_rows, bad_rows, overflow, top, the first ``top`` row indices of hard / ambiguous / forgotten /
+                                   low_aum and per class support, confidence, variability, correctness, aum, never_learned, forgetting
+    train_dynamics_rows.csv        row, label, name, confidence, variability, correctness, forgetting, first_learned and aum of every
+                                   train row the refit has seen, by row
+
+(The probabilities are the training pass's -- dropout on, each visit under the weights of its own step -- and for the Transformer,
+whose decoder reads the gold label, conditional on that label.  The refit's checkpoints then hold train_dynamics.npz too.)
+
+Without the ten keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -119,7 +132,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -202,6 +215,8 @@ def build_net_params(args, dataset, device):
     for k in ("lr", "max_epochs", "batch_size", "verbose", "calibration", "conformal"):     # (calibration: {method: temperature}, conformal: {alpha: ...}, slnlp/net.py)
         if args.get(k) is not None:
             p[k] = args[k]
+    if train_dynamics_options(args.get("train_dynamics")) is not None:
+        p["train_dynamics"] = True                                              # (the key's ``top`` shapes the files, not the fit)
     if isinstance(p.get("scoring"), str):
         p["scoring"] = [p["scoring"]]
     p.update(prefix_args("module", batch_first=True, src_vocab=dataset.vocab_X, tgt_vocab=dataset.vocab_y, **model_args))
@@ -514,6 +529,56 @@ def save_label_audit(gs, factory, train_data, opts, seed, workdir):
     return oof, res
 
 
+TRAIN_DYNAMICS_DEFAULTS = {"top": 50}
+
+
+def train_dynamics_options(setting):
+    """The ``train_dynamics`` key with its default filled in -- {top 50} -- or None when the key is absent.  Anything but a dict over
+    this one key ({}: the default) with ``top`` an integer >= 0 raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"train_dynamics={setting!r}: expected a dict with keys among {tuple(TRAIN_DYNAMICS_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(TRAIN_DYNAMICS_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"train_dynamics: unknown keys {unknown} (known: {tuple(TRAIN_DYNAMICS_DEFAULTS)})")
+    opts = dict(TRAIN_DYNAMICS_DEFAULTS, **setting)
+    if isinstance(opts["top"], bool) or not isinstance(opts["top"], int) or not 0 <= opts["top"] <= 2 ** 31 - 1:
+        raise ValueError(f"train_dynamics: top={opts['top']!r}, expected an integer >= 0")
+    return opts
+
+
+def save_train_dynamics(est, train_data, opts, workdir):
+    """The refit's ``train_dynamics(top=opts["top"], per_row=True)`` as ``train_dynamics.json`` (the totals, the ranked lists' row
+    indices and the per-class table) and ``train_dynamics_rows.csv`` (row, label, name, confidence, variability, correctness,
+    forgetting, first_learned, aum: one line per train row the fit has seen, by row) in ``workdir``; floats are written with
+    ``repr``.  Returns the result."""
+    res = est.train_dynamics(top=opts["top"], per_row=True)
+    names = train_data.vocab_y.itos if getattr(train_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    cell = lambda v: None if v != v else float(v)            # NaN: a class without a seen row
+    per = res["per_class"]
+    out = {k: int(res[k]) for k in ("rows", "rows_seen", "unforgettable", "never_learned_rows", "forgetting_events", "epochs", "visits",
+                                    "bad_labels", "nan_rows", "bad_rows")}
+    out.update(overflow=bool(res["overflow"]), top=opts["top"],
+               **{k: [int(r) for r in res[k]["row"]] for k in ("hard", "ambiguous", "forgotten", "low_aum")},
+               per_class=[{"class": int(c), "name": name(c), "support": int(per["support"][i]),
+                           **{k: cell(per[k][i]) for k in ("confidence", "variability", "correctness", "aum")},
+                           "never_learned": int(per["never_learned"][i]), "forgetting": int(per["forgetting"][i])}
+                          for i, c in enumerate(per["label"])])
+    save_json(out, os.path.join(workdir, "train_dynamics.json"))
+    rows = res["per_row"]
+    with open(os.path.join(workdir, "train_dynamics_rows.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["row", "label", "name", "confidence", "variability", "correctness", "forgetting", "first_learned", "aum"])
+        for i in np.argsort(rows["row"], kind="stable"):
+            if rows["visits"][i] > 0:
+                w.writerow([int(rows["row"][i]), int(rows["label"][i]), name(rows["label"][i]), repr(float(rows["confidence"][i])),
+                            repr(float(rows["variability"][i])), repr(float(rows["correctness"][i])), int(rows["forgetting"][i]),
+                            int(rows["first_learned"][i]), repr(float(rows["aum"][i]))])
+    return res
+
+
 PRIOR_SHIFT_DEFAULTS = {"max_iter": 200, "tol": 1e-6, "source": "train"}
 PRIOR_SHIFT_MAX_ITER = 1024                                                     # SLNLP_PRIOR_MAX_ITER
 PRIOR_SHIFT_SOURCES = ("train", "train_labels")
@@ -717,6 +782,7 @@ def run(args):
     selective = selective_options(args.get("selective"))
     label_audit = label_audit_options(args.get("label_audit"))
     attribution = attribution_options(args.get("attribution"))
+    dynamics = train_dynamics_options(args.get("train_dynamics"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -772,6 +838,8 @@ def run(args):
             save_prior_shift(est, train_data, test_data, prior_shift, workdir)
         if label_audit is not None:
             save_label_audit(gs, factory, train_data, label_audit, seed, workdir)
+        if dynamics is not None:
+            save_train_dynamics(est, train_data, dynamics, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

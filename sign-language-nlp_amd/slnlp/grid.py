@@ -89,7 +89,7 @@ def build_tasks(param_grid, y, cv, seq_len=48, defaults=None):
 # threshold: slnlp/lockstep.py)
 SHAPE_KEYS_EXCLUDED = ("lr", "module__dropout", "criterion__label_smoothing", "optimizer__weight_decay", "optimizer__dampening",
                        "optimizer__nesterov", "lr_scheduler", "iterator_train__shuffle", "optimizer__param_groups",
-                       "iterator_train__augment", "calibration", "conformal")
+                       "iterator_train__augment", "calibration", "conformal", "train_dynamics")
 
 
 def estimate_fit_bytes(params, seq_len, defaults=None, lockstep=1):

@@ -503,6 +503,83 @@ def label_audit_report(rec, y, rank_by="normalized_margin"):
             "rows": head[0], "bad_labels": head[1], "nan_rows": head[2], "unconfident": head[3], "argmax_disagrees": head[5]}
 
 
+DYN_FRAC_BITS = 20                                         # SLNLP_DYN_FRAC_BITS: q and mq are fixed point with 20 fraction bits
+TRAIN_DYNAMICS_FIELDS = ("confidence", "variability", "correctness", "aum", "forgetting", "first_learned", "epochs_seen")
+
+
+def train_dynamics_report(got, labels, rows=None, top=50):
+    """``ops.train_dynamics_download``'s dict (``slnlp_train_dynamics_epoch``, include/slnlp.h) as the report of a fit's training
+    dynamics, on the host from the exact integers, in fp64.  ``labels`` [N]: the label of every train row (any dtype); ``rows`` int
+    [N]: the dataset index of every train row (None: 0 .. N - 1); ``top``: the length of the ranked lists.  Per row, over its
+    ``visits`` usable visits, with F = 2^20 (``DYN_FRAC_BITS``):
+
+        confidence = sum_q / (visits F)          the mean probability of the gold class (Swayamdipta et al. 2020)
+        variability = sqrt(max(0, sum_q2 / (visits F^2) - confidence^2))           its standard deviation
+        correctness = correct_visits / visits    aum = sum_mq / (visits F), the area under the margin (Pleiss et al. 2020)
+        forgetting: the epochs the row was right at every visit of the epoch before and not in this one (Toneva et al. 2019)
+        first_learned: the first epoch it was right at every visit (-1: never); epochs_seen: the epochs that visited it
+
+    Returned: ``hard`` (lowest confidence first), ``ambiguous`` (highest variability first), ``forgotten`` (most forgetting events
+    first, only rows with at least one) and ``low_aum`` (lowest AUM first), each cut at ``top``, ties by row index; ``never_learned``:
+    ALL seen rows with first_learned == -1, by row index.  Each is a dict of arrays ``row`` (the dataset index), ``label`` and the
+    seven statistics above.  A row no usable visit has reached is in none of them.  Totals: ``rows``, ``rows_seen``,
+    ``unforgettable`` (learned, no forgetting event), ``never_learned_rows``, ``forgetting_events``, ``epochs``, ``visits``,
+    ``bad_labels``, ``nan_rows``, ``bad_rows`` (the head's skipped visits) and ``overflow`` (a row reached the visit limit: its sums
+    may have wrapped).  ``per_class``: arrays over the sorted distinct labels -- ``label``, ``support`` (all its train rows), the
+    means of confidence, variability, correctness and aum over its SEEN rows (NaN without one), ``never_learned``,
+    ``forgetting``.  ``per_row``: the statistics of every train row as arrays [N] (NaN for an unseen row's four means), with
+    ``row``, ``label`` and ``visits``."""
+    what = "train_dynamics_report"
+    if isinstance(top, (bool, np.bool_)) or not isinstance(top, (int, np.integer)) or top < 0:
+        raise ValueError(f"{what}: top={top!r}, expected an integer >= 0")
+    visits = np.asarray(got["visits"]).astype(np.int64)
+    N = visits.size
+    labels = np.asarray(labels)
+    rows = np.arange(N, dtype=np.int64) if rows is None else np.asarray(rows).astype(np.int64)
+    if labels.shape != (N,) or rows.shape != (N,):
+        raise ValueError(f"{what}: labels has shape {tuple(labels.shape)} and rows {tuple(rows.shape)}, the state {N} rows")
+    F = float(1 << DYN_FRAC_BITS)
+    seen = visits > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        v = np.where(seen, visits, 0).astype(np.float64)
+        conf = np.asarray(got["sum_q"]).astype(np.float64) / (v * F)
+        var = np.asarray(got["sum_q2"]).astype(np.float64) / (v * (F * F)) - conf * conf
+        stats = {"confidence": conf, "variability": np.sqrt(np.maximum(0.0, var)),
+                 "correctness": np.asarray(got["correct_visits"]).astype(np.float64) / v,
+                 "aum": np.asarray(got["sum_mq"]).astype(np.float64) / (v * F)}
+    for name in ("confidence", "variability", "correctness", "aum"):
+        stats[name] = np.where(seen, stats[name], np.nan)
+    for name in ("forgetting", "first_learned", "epochs_seen"):
+        stats[name] = np.asarray(got[name]).astype(np.int64)
+    at = np.flatnonzero(seen)
+
+    def entries(which):
+        return {"row": rows[which], "label": labels[which], **{name: stats[name][which] for name in TRAIN_DYNAMICS_FIELDS}}
+
+    def ranked(key, among=at):
+        return entries(among[np.lexsort((rows[among], key[among]))][:int(top)])
+    never = at[stats["first_learned"][at] == -1]
+    never = never[np.argsort(rows[never], kind="stable")]
+    classes, cls = np.unique(labels, return_inverse=True)
+    C = classes.size
+    n_seen = np.bincount(cls[at], minlength=C).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        means = {name: np.bincount(cls[at], weights=stats[name][at], minlength=C) / n_seen
+                 for name in ("confidence", "variability", "correctness", "aum")}
+    head = [int(x) for x in got["head"]]
+    return {"hard": ranked(stats["confidence"]), "ambiguous": ranked(-stats["variability"]),
+            "forgotten": ranked(-stats["forgetting"], at[stats["forgetting"][at] > 0]), "low_aum": ranked(stats["aum"]),
+            "never_learned": entries(never),
+            "rows": N, "rows_seen": int(at.size), "never_learned_rows": int(never.size),
+            "unforgettable": int(np.count_nonzero((stats["first_learned"][at] != -1) & (stats["forgetting"][at] == 0))),
+            "forgetting_events": int(stats["forgetting"][at].sum()), "epochs": head[0], "visits": head[1], "bad_labels": head[2],
+            "nan_rows": head[3], "bad_rows": head[4], "overflow": bool(head[6]),
+            "per_class": {"label": classes, "support": np.bincount(cls, minlength=C), **means,
+                          "never_learned": np.bincount(cls[never], minlength=C),
+                          "forgetting": np.bincount(cls[at], weights=stats["forgetting"][at], minlength=C).astype(np.int64)},
+            "per_row": {"row": rows, "label": labels, "visits": visits, **stats}}
+
+
 _LOG_FACTORIAL = [0.0]                                     # ln i!, grown on demand with math.lgamma
 
 

@@ -33,7 +33,12 @@ semantics:
   (LAC / APS / RAPS, csrc/conformal.hip) is taken on the valid split's log-probs, on the device; ``predict_set`` then returns per
   sample the set of classes that holds the true one with probability about 1 - alpha.  About: the valid split also chose the
   temperature and the stopping epoch, so the guarantee is approximate there; it is exact only with ``conformalize`` on rows the
-  fit never saw (``coverage`` reports what the sets achieve on labelled data).
+  fit never saw (``coverage`` reports what the sets achieve on labelled data);
+* ``train_dynamics=True``: every epoch's train log-probs are folded, on the device, into per-row integer counts
+  (csrc/train_dynamics.hip: two queued launches per epoch, no host wait), and ``train_dynamics()`` reports which train rows the
+  fit never learned, learned and forgot, wavers on, or fits only against a large negative margin (confidence / variability /
+  correctness, forgetting events, AUM).  The probabilities are the training pass's: dropout on, augmented inputs under
+  ``iterator_train__augment``, each visit under the weights of its own step.  Off (the default), nothing is allocated or queued.
 
 Beyond skorch: ``reliability`` (ECE / MCE / Brier, csrc/reliability.hip), ``predict_topk`` and ``error_analysis`` (top-k classes,
 confusion matrix, most-confused pairs, per-class report: csrc/confusion.hip) and ``ranking`` (one-vs-rest ROC AUC and average
@@ -474,6 +479,7 @@ class _FitRun:
         labels = net.labels if net.labels is not None else ds.labels()
         idx_tr, idx_va = net._train_split(ds)
         self.tr, self.va = ds[idx_tr], (ds[idx_va] if idx_va is not None else None)
+        self.idx_tr = idx_tr
         self.Xtr, self.Ltr, self.ytr = net._device_data(self.tr)
         if self.va is not None:
             self.Xva, self.Lva, self.yva = net._device_data(self.va)
@@ -545,6 +551,9 @@ class _FitRun:
             self._aug_ids = net._augment_ids()
             self._aug_src = (self.Xtr, self.Ltr)
             self.Xtr, self.Ltr = torch.empty_like(self.Xtr), torch.empty_like(self.Ltr)
+        # train_dynamics: the per-row integer state (ops.train_dynamics_buffers) lives on the net, so that partial_fit / a warm
+        # start goes on adding to it; with the option off nothing is allocated and end_epoch queues nothing
+        self.dynamics = net._train_dynamics_state(self) if net._train_dynamics_on() else None
         self.epochs_left = int(net.max_epochs)
         self.done = self.epochs_left <= 0
 
@@ -598,6 +607,12 @@ class _FitRun:
             return self.ytr[:self.n_visit], self.tr.y[:self.n_visit]
         return self.ytr, self.tr.y
 
+    def train_labels_dev(self):
+        """``train_labels``' device half alone: no host copy is taken (a balanced epoch's labels exist on the device only)."""
+        if self.epoch_order is not None or self.balance is not None:
+            return self.y_visit_dev
+        return self.ytr[:self.n_visit] if self.n_visit != len(self.tr) else self.ytr
+
     def _reduced_scores(self, names, split, logp, y_dev, y_host):
         """``metrics.epoch_scores`` into this fit's own device buffers for ``split`` (allocated once, not every epoch)."""
         if logp.is_cuda and split not in self._score_out:
@@ -617,6 +632,10 @@ class _FitRun:
         net = self.net
         tr_loss, tr_logp, tr_batches = tr
         epoch = len(net.history) + 1
+        if self.dynamics is not None:
+            # the epoch's train log-probs, folded into the per-row state: two launches queued on the fit's stream, no host wait --
+            # in front of the history row and of the checkpoint, which saves the state with this epoch in it
+            ops.train_dynamics_epoch(tr_logp, self.train_labels_dev(), self.order_dev, epoch, self.dynamics["buf"])
         if self.schedule is not None:
             # what the reference's lr scoring reads at epoch end: with batch stepping the rate after the epoch's last step
             net._set_lr(self.schedule.rates)
@@ -688,13 +707,15 @@ class _FitRun:
 class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
     _OWN = ("module", "criterion", "optimizer", "lr", "max_epochs", "batch_size", "device", "warm_start", "verbose",
             "predict_nonlinearity", "scoring", "labels", "early_stopping", "gradient_clipping", "lr_scheduler",
-            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging", "calibration", "conformal")
+            "checkpoint_dir", "train_split", "use_graph", "callbacks", "dataset", "weight_averaging", "calibration", "conformal",
+            "train_dynamics")
 
     def __init__(self, module, criterion="torch.nn.CrossEntropyLoss", optimizer="torch.optim.SGD", lr=0.01,
                  max_epochs=10, batch_size=128, device="cuda", warm_start=False, verbose=0,
                  predict_nonlinearity="auto", scoring=None, labels=None, early_stopping=None,
                  gradient_clipping=None, lr_scheduler=None, checkpoint_dir=None, train_split=5, use_graph="auto",
-                 callbacks=None, dataset=None, weight_averaging=None, calibration=None, conformal=None, **kwargs):
+                 callbacks=None, dataset=None, weight_averaging=None, calibration=None, conformal=None, train_dynamics=False,
+                 **kwargs):
         loc = locals()
         self._params = {k: loc[k] for k in self._OWN}
         for k, v in kwargs.items():
@@ -828,6 +849,8 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         if conf_opts is not None and not self.train_split:
             raise ValueError(f"conformal: the threshold is taken on the fit's internal valid split, and train_split={self.train_split!r} "
                              "holds nothing out (conformalize(X, y) takes it on data of yours)")
+        if not isinstance(self._params.get("train_dynamics", False), (bool, np.bool_)):
+            raise ValueError(f"train_dynamics={self._params['train_dynamics']!r}: expected True or False")
         ok, pairs = optimizer_kwargs(self._sub("optimizer"))
         if not pairs:
             schedule.check_setting(self.lr_scheduler, self.lr)  # a setting the loop cannot honour: here, not in the middle of a fit
@@ -861,6 +884,7 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         self._conf_opts = conf_opts
         self._set_conformal(None)
         self._set_rejection(None)
+        self._dyn = None                                 # the training dynamics of an earlier fit do not describe the one to come
         self._opt_defaults = optimizer_defaults(self._opt_cls, {"lr": float(self.lr), **ok}) if self._fused else None
         # the criterion the library evaluates (train and eval forwards): the configured one, on both paths, when it can
         self._crit_opts = criterion_options(self.criterion_) if hasattr(mod_cls, "engine") else None
@@ -1245,10 +1269,68 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         elif "lr" in groups[0]:
             self._set_lr(groups[0]["lr"])
 
+    # ------------------------------------------------------- training dynamics
+    def _train_dynamics_on(self):
+        return bool(self.__dict__.get("_params", {}).get("train_dynamics", False))
+
+    def _train_dynamics_state(self, run):
+        """The per-row state a ``train_dynamics=True`` fit adds to (``_FitRun.__init__``): new and reset, or -- ``partial_fit`` / a
+        warm start / a loaded checkpoint -- the one this net already holds for the same train rows.  {buf:
+        ``ops.train_dynamics_buffers``' dict, idx_tr: the train split's dataset indices, y: its labels}.  Runs on the fit's stream."""
+        idx = np.asarray(run.idx_tr, dtype=np.int64)
+        dev, N, n_visit = run.ytr.device, len(run.tr), int(run.n_visit)
+        dyn = getattr(self, "_dyn", None)
+        if dyn is not None and not np.array_equal(dyn["idx_tr"], idx):
+            raise ValueError(f"train_dynamics: the state describes {len(dyn['idx_tr'])} train rows of an earlier fit and this fit's train "
+                             f"split has {len(idx)} rows with other dataset indices; initialize() (or fit without warm_start) starts anew")
+        if dyn is not None and dyn["buf"]["shape"] == (N, n_visit) and dyn["buf"]["flat"].device == dev:
+            return dyn
+        buf = ops.train_dynamics_buffers(N, n_visit, dev)
+        words = buf["state_bytes"] // 4
+        if dyn is None:
+            ops.train_dynamics_reset(buf)
+        else:                                                # the epoch length changed between two partial fits (or the state came
+            buf["flat"][:words].copy_(dyn["buf"]["flat"][:words])       # from a checkpoint, which does not know it): the state moves
+        self._dyn = {"buf": buf, "idx_tr": idx, "y": np.asarray(run.tr.y).astype(np.int64)}
+        return self._dyn
+
+    def train_dynamics(self, top=50, per_row=False):
+        """What happened to every row of the fit's train split DURING training (``train_dynamics=True``): dataset cartography
+        (Swayamdipta et al. 2020), forgetting events (Toneva et al. 2019) and the area under the margin (Pleiss et al. 2020), kept
+        on the device epoch by epoch from the train pass's own log-probs (csrc/train_dynamics.hip: all per-row state is integer,
+        so the numbers are a pure function of the fit) -- no extra forward pass, ONE download here.
+        ``metrics.train_dynamics_report``'s dict: ``hard`` / ``ambiguous`` / ``forgotten`` / ``low_aum`` (at most ``top`` rows
+        each) and ``never_learned``, whose ``row`` entries are indices into the dataset the fit was given and whose ``label``
+        entries are ``classes_`` entries; the totals; ``per_class``; plus ``classes``.  ``per_row=True`` keeps ``per_row``, the
+        arrays over all train rows.  Unlike ``label_issues`` it is honest on the fit's own train rows by construction: what it
+        measures is the memorisation itself.
+
+        The probabilities are the TRAINING pass's: dropout on, augmented inputs under ``iterator_train__augment``, and every
+        visit under the weights of its own step (an epoch's first batch saw older weights than its last).  Under
+        ``iterator_train__balance`` a row is visited several times per epoch (or not at all), and forgetting is epoch-granular:
+        a row counts as right in an epoch when it was right at EVERY visit of it, and an epoch that does not visit it leaves
+        its record alone.  For the reference Transformer, whose decoder is fed the gold label, the statistics are conditional
+        on that label -- the caveat of ``label_issues`` and ``attribute``.  Raises when the option was off or no epoch has run."""
+        if not self._train_dynamics_on():
+            raise ValueError("train_dynamics: the estimator was built with train_dynamics=False, nothing was recorded")
+        dyn = self.__dict__.get("_dyn")
+        if dyn is None:
+            raise ValueError("train_dynamics: no epoch has run yet (fit first)")
+        got = ops.train_dynamics_download(dyn["buf"])
+        if int(got["head"][0]) < 1:
+            raise ValueError("train_dynamics: no epoch has run yet (fit first)")
+        classes = self.__dict__.get("classes_")              # (a state loaded from a checkpoint, no fit yet: the class ids themselves)
+        res = metrics.train_dynamics_report(got, dyn["y"] if classes is None else classes[dyn["y"]], rows=dyn["idx_tr"], top=top)
+        res["classes"] = classes
+        if not per_row:
+            del res["per_row"]
+        return res
+
     def save_params(self, dirname):
         """skorch ``Checkpoint`` artefacts: params.pt (state_dict), optimizer.pt (a torch.optim state_dict in either
         mode), criterion.pt, history.json; calibration.json, conformal.json and rejection.json when the fit has a temperature / a conformal threshold /
-        a rejection threshold."""
+        a rejection threshold; train_dynamics.npz (the integer state with its head, the train split's dataset indices and labels)
+        when the fit keeps training dynamics."""
         os.makedirs(dirname, exist_ok=True)
         torch.save({k: v.detach().cpu() for k, v in self.module_.state_dict().items()}, os.path.join(dirname, "params.pt"))
         torch.save(self._sgd_state_dict() if self._fused else self.optimizer_.state_dict(), os.path.join(dirname, "optimizer.pt"))
@@ -1265,6 +1347,10 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         if getattr(self, "rejection_", None) is not None:
             with open(os.path.join(dirname, "rejection.json"), "w") as f:
                 json.dump(self.rejection_, f, indent=1)      # (repr round-trips the threshold bit for bit; Infinity and NaN as above)
+        if self.__dict__.get("_dyn") is not None:         # the training dynamics so far: a resumed fit goes on adding to them
+            buf = self._dyn["buf"]                       # (one device-to-host copy of the state's 4-byte words)
+            np.savez(os.path.join(dirname, "train_dynamics.npz"), state=buf["flat"][:buf["state_bytes"] // 4].cpu().numpy(),
+                     idx_tr=self._dyn["idx_tr"], y=self._dyn["y"])
         if getattr(self, "_avg_opts", None) is not None:  # the running average and how many models it holds: a resumed fit goes on
             torch.save({"state_dict": {k: v.detach().cpu() for k, v in self.averaged_state_dict().items()}, "n_averaged": self.n_averaged_},
                        os.path.join(dirname, "averaged.pt"))
@@ -1306,6 +1392,17 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         if os.path.exists(rej_file):
             with open(rej_file) as f:
                 self._set_rejection(json.load(f))            # the threshold goes back to the device
+        dyn_file = os.path.join(dirname, "train_dynamics.npz")
+        if self._train_dynamics_on() and os.path.exists(dyn_file):
+            with np.load(dyn_file) as saved:             # the integers go back to the device; the fit that continues them checks
+                words, idx, y = saved["state"], saved["idx_tr"].astype(np.int64), saved["y"].astype(np.int64)       # its train rows
+            dev = self.module_._arena.device if hasattr(self.module_, "_arena") else torch.device(self.device)
+            buf = ops.train_dynamics_buffers(len(idx), len(idx), dev)       # (the epoch length is the next fit's to say)
+            if words.dtype != np.int32 or words.shape != (buf["state_bytes"] // 4,):
+                raise ValueError(f"{dyn_file}: a state of {words.dtype} {words.shape}, {len(idx)} train rows take int32 "
+                                 f"({buf['state_bytes'] // 4},)")
+            buf["flat"][:words.size].copy_(torch.from_numpy(words))
+            self._dyn = {"buf": buf, "idx_tr": idx, "y": y}
         hist = os.path.join(dirname, "history.json")
         if os.path.exists(hist):
             with open(hist) as f:

@@ -1147,6 +1147,81 @@ def label_audit_download(buf, per_row=False):
     return out
 
 
+TRAIN_DYNAMICS_ROW_INTS = ("visits", "correct_visits", "epochs_seen", "epochs_correct", "forgetting", "first_learned", "last")
+
+
+def train_dynamics_buffers(N, n_visit, device):
+    """The device buffer of a fit's training dynamics over ``N`` dataset rows, fed ``n_visit`` visit positions per epoch: ONE int32
+    allocation laid out as include/slnlp.h states (every piece 8-byte aligned, int32 pieces padded to an even length) -- the state
+
+        head int64 [8] | sum_q int64 [N] | sum_q2 int64 [N] | sum_mq int64 [N] | visits [N] | correct_visits [N] | epochs_seen [N] |
+        epochs_correct [N] | forgetting [N] | first_learned [N] | last [N] | v_e [N] | c_e [N]
+
+    and behind it the per-visit scratch of one epoch: ``q int64 [n_visit] | mq int64 [n_visit] | code | correct | pred [n_visit]``.
+    What a report needs ends with last, so ``train_dynamics_download`` copies one contiguous piece; ``state_bytes`` is where the
+    scratch begins.  (The unsigned pieces are held as signed ones: below the visit limit no value reaches a sign bit.)  The state is
+    NOT zeroed: ``train_dynamics_reset`` does that."""
+    what = "train_dynamics_buffers"
+    N, n = _int_in(what, "N", N, 1, 2 ** 31 - 1), _int_in(what, "n_visit", n_visit, 1, 2 ** 31 - 1)
+    longs = lambda name, k: (name, torch.int64, k, 8)
+    p = _packed.Packed(torch.int32, (("head", torch.int64, _lib.DYN_HEAD_BYTES // 8, 8), longs("sum_q", N), longs("sum_q2", N), longs("sum_mq", N),
+                                     *(_even_ints(name, N) for name in TRAIN_DYNAMICS_ROW_INTS), _even_ints("v_e", N), _even_ints("c_e", N),
+                                     longs("q", n), longs("mq", n), _even_ints("code", n), _even_ints("correct", n), _even_ints("pred", n)), device)
+    state_bytes = p.at["q"][0]
+    if state_bytes != load().slnlp_train_dynamics_state_bytes(N):
+        raise RuntimeError(f"{what}: the state of {N} rows is laid out in {state_bytes} bytes here and in "
+                           f"{load().slnlp_train_dynamics_state_bytes(N)} by the library")
+    return _packed_dict(p, (N, n), state_bytes=state_bytes)
+
+
+def _dyn_buf(what, buf, device=None):
+    _packed_buf(what, buf, "train_dynamics_buffers(N, n_visit, device)", (), device, more=2)
+    return buf["flat"], buf["state_bytes"], buf["flat"].numel() * 4 - buf["state_bytes"]
+
+
+def train_dynamics_reset(buf):
+    """Zero the state of ``train_dynamics_buffers`` (first_learned and last: -1) with one launch of the library's own
+    (``slnlp_train_dynamics_reset``) on the current stream of the buffer's device; no host wait.  Returns ``buf``."""
+    _lib.require_gpu()
+    what = "train_dynamics_reset"
+    flat, state_bytes, _ = _dyn_buf(what, buf)
+    with torch.cuda.device(flat.device):
+        check(load().slnlp_train_dynamics_reset(ptr(flat), state_bytes, buf["shape"][0], stream_ptr()), what)
+    return buf
+
+
+def train_dynamics_epoch(logp, y, order, epoch, buf):
+    """Fold ONE epoch's train log-probs into the training-dynamics state ``buf`` (``train_dynamics_buffers``):
+    ``slnlp_train_dynamics_epoch``, include/slnlp.h.  ``logp`` float32 [n_visit, V] in visit order (rows may be padded:
+    ``stride(0) >= V``), ``y`` int64 [n_visit] the labels in visit order, ``order`` int64 [n_visit] the dataset row of every visit
+    or None (visit i is row i), ``epoch`` >= 1 its number.  Two queued launches on the current stream of ``logp``'s device; no host
+    wait.  Returns ``buf``, whose per-visit scratch holds this epoch's values until the next call."""
+    _lib.require_gpu()
+    what = "train_dynamics_epoch"
+    n, V, ld = _logp_matrix(what, logp)
+    _labels(what, y, logp.device, n)
+    if order is not None:
+        _tensor(what, "order", order, logp.device, torch.int64, n, f"a contiguous int64 [{n}] tensor on {logp.device} or None")
+    epoch = _int_in(what, "epoch", epoch, 1, 2 ** 31 - 1)
+    flat, state_bytes, visits_bytes = _dyn_buf(what, buf, logp.device)
+    if buf["shape"][1] != n:
+        raise ValueError(f"{what}: buf was made for {buf['shape'][1]} visits per epoch, logp has {n} rows")
+    with torch.cuda.device(logp.device):
+        check(load().slnlp_train_dynamics_epoch(ptr(logp), ld, ptr(y), ptr(order), n, V, buf["shape"][0], epoch, ptr(flat), state_bytes,
+                                                ptr(flat) + state_bytes, visits_bytes, stream_ptr()), what)
+    return buf
+
+
+def train_dynamics_download(buf, per_visit=False):
+    """What the training dynamics hand to the host in ONE device-to-host copy: {head int64 [8] = (epochs, usable visits, bad_labels,
+    nan_rows, bad_rows, rows seen, overflow, 0), sum_q / sum_q2 / sum_mq int64 [N], visits / correct_visits / epochs_seen /
+    epochs_correct / forgetting / first_learned / last int32 [N]}: what ``metrics.train_dynamics_report`` reads.
+    ``per_visit=True`` extends the copy through the last epoch's per-visit scratch: q / mq int64, code / correct / pred int32
+    [n_visit] (and the fold's v_e / c_e, which are 0 between epochs)."""
+    _dyn_buf("train_dynamics_download", buf)
+    return buf["packed"].cut("head", "pred" if per_visit else "last")
+
+
 def occlusion_variants(lengths, S, by, width=1, stride=1, bins=8, n_fields=None):
     """The variant table of an occlusion attribution over rows of ``lengths`` (host integers [N]) padded to ``S`` positions
     (include/slnlp.h): ``(variants int32 [M, 3] = (row, unit, bin) sorted by (row, unit), row_start int32 [N + 1], n_bins)``.
