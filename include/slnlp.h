@@ -1029,6 +1029,62 @@ int slnlp_attribution_summary(const float* base, int64_t ld_b, const int64_t* y,
                               const int32_t* ints, int32_t* cell, int64_t* head, int64_t* table_i, double* table_d, int32_t* rows_i,
                               double* rows_d, void* stream);
 
+/* ------------------------------------------- edit-distance nearest neighbours (csrc/edit_knn.hip) --
+ * All-pairs unit-cost Levenshtein distances between two sets of token rows and the k nearest references of every query: the
+ * non-neural baseline (slnlp.EditKNN) and the audit of a split (slnlp.split_audit).  Everything is integer until the votes, there
+ * are no floating-point atomics, and every result is a pure function of the arguments: the same bytes on every run, on any stream,
+ * beside other kernels.
+ *
+ * Xq int64 [nq, .] with row stride ldq (in tokens, >= 1), Lq int64 [nq]; Xr / ldr / Lr [nr] the references.  A row is USABLE when
+ * its length L lies in 0..min(SLNLP_EDIT_MAX_LEN, its row stride); only the first L tokens of a usable row are read, tokens are
+ * compared as full int64 values, and nothing past L -- and nothing of an unusable row -- influences anything.  Rows longer than 64
+ * tokens are REFUSED (flagged and counted), never truncated: the kernel is Myers' bit-vector recurrence with the query in one
+ * 64-bit word.
+ *
+ * slnlp_edit_distances: dist uint8 [nq, nr], the distance of every (query, reference) pair (at most 64), 255 where either row is
+ * unusable.  One launch.
+ *
+ * slnlp_edit_knn_rows: distances into scratch (slnlp_edit_knn_scratch_bytes: one byte per pair; nq nr <= SLNLP_EDIT_MAX_PAIRS,
+ * -1 with a message otherwise), then the selection and the head: three queued launches, no host wait.  Per query the k
+ * (1..SLNLP_EDIT_MAX_K) usable references of smallest distance, ordered by (distance, reference index) ascending -- ties at the k-th
+ * distance go to the lower index.  exclude int64 [nq] or null: the one reference index query i skips (leave-one-out), -1 none; any
+ * other value outside 0..nr-1 skips nothing and sets SLNLP_EDIT_CODE_EXCLUDE.  An unusable reference is never a neighbour; an
+ * unusable query gets none and SLNLP_EDIT_CODE_QUERY.
+ *   nbr  int32 [nq, k, 2]   (distance, reference index), (-1, -1) past found
+ *   rows int32 [nq, 4]      found, the usable references (but the excluded one) with distance <= radius (0..64), the nearest
+ *                           distance or -1, the code bits
+ *   head int64 [8]          unusable queries, unusable references, then 0 (the third is written by the votes)
+ *
+ * slnlp_edit_knn_logp: neighbours to float32 log-probs [nq, V] with row stride ld, one wave per query in fp64, neighbours in list
+ * order: w_j = 1 (SLNLP_EDIT_UNIFORM) or exp(-d_j / (tau n_j)) (SLNLP_EDIT_DISTANCE), n_j = max(Lq, Lr_j, 1) when normalize, else 1;
+ * s_c = the sum of w_j over the neighbours with label yr[index_j] = c, W the sum of all w_j; p_c = (s_c + lam prior_c) / (W + lam)
+ * with prior float64 [V]; logp_c = (float) log(p_c).  A neighbour whose label lies outside 0..V-1 is skipped, out of W as well, and
+ * counted in head[2].  found = 0: the log of the prior.  A query with SLNLP_EDIT_CODE_QUERY: a row of NaN -- reported, not patched.
+ * Two queued launches.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message, before anything is launched): a null pointer (exclude may be null); nq or nr
+ * outside 1..SLNLP_EDIT_MAX_ROWS (2^30: the kernels' 32-bit row loops step past the end by less than a block), V outside 1..INT32_MAX; more than SLNLP_EDIT_MAX_PAIRS pairs; a row stride < 1; k outside 1..SLNLP_EDIT_MAX_K; radius outside
+ * 0..64; weights or normalize that is none of the above; tau or lam not finite and > 0; ld < V; a scratch that is too small; a
+ * misaligned pointer; an output overlapping an input or another output. */
+#define SLNLP_EDIT_MAX_LEN 64
+#define SLNLP_EDIT_MAX_K 64
+#define SLNLP_EDIT_MAX_ROWS 1073741824
+#define SLNLP_EDIT_MAX_PAIRS 2147483648LL
+#define SLNLP_EDIT_HEAD_BYTES 64
+#define SLNLP_EDIT_CODE_QUERY 1
+#define SLNLP_EDIT_CODE_EXCLUDE 2
+#define SLNLP_EDIT_UNIFORM 0
+#define SLNLP_EDIT_DISTANCE 1
+int slnlp_edit_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                         int64_t nr, uint8_t* dist /* [nq, nr] */, void* stream);
+int64_t slnlp_edit_knn_scratch_bytes(int64_t nq, int64_t nr);
+int slnlp_edit_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                        int64_t nr, const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes,
+                        int64_t* head /* [8] */, int32_t* rows /* [nq, 4] */, int32_t* nbr /* [nq, k, 2] */, void* stream);
+int slnlp_edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq,
+                        int64_t nr, int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior,
+                        float* logp, int64_t ld, int64_t* head, void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);

@@ -154,6 +154,10 @@ SIGNATURES = {
     "slnlp_occlude_rows": (i32, [vp, vp, vp, i64, i64, vp, i64, i32, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp]),
     "slnlp_attribution_rows": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
     "slnlp_attribution_summary": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "slnlp_edit_distances": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
+    "slnlp_edit_knn_scratch_bytes": (i64, [i64, i64]),
+    "slnlp_edit_knn_rows": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "slnlp_edit_knn_logp": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, C.c_double, i32, C.c_double, vp, vp, i64, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -316,6 +320,12 @@ OCCLUDE_KINDS = ("mask", "drop", "substitute")  # SLNLP_OCCLUDE_MASK / _DROP / _
 ATTR_MAX_BINS = 64                              # SLNLP_ATTR_MAX_BINS
 ATTR_HEAD_BYTES = 64                            # SLNLP_ATTR_HEAD_BYTES
 ATTR_TARGETS = ("label", "pred")                # target 0: the label; 1: the base row's arg-max
+EDIT_MAX_LEN = 64                               # SLNLP_EDIT_MAX_LEN
+EDIT_MAX_K = 64                                 # SLNLP_EDIT_MAX_K
+EDIT_MAX_ROWS = 2 ** 30                         # SLNLP_EDIT_MAX_ROWS
+EDIT_MAX_PAIRS = 2 ** 31                        # SLNLP_EDIT_MAX_PAIRS
+EDIT_HEAD_BYTES = 64                            # SLNLP_EDIT_HEAD_BYTES
+EDIT_WEIGHTS = ("uniform", "distance")          # SLNLP_EDIT_UNIFORM / _DISTANCE
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

@@ -118,7 +118,22 @@ refit's ``train_dynamics()`` holds -- which train rows it never learned, learned
 (The probabilities are the training pass's -- dropout on, each visit under the weights of its own step -- and for the Transformer,
 whose decoder reads the gold label, conditional on that label.  The refit's checkpoints then hold train_dynamics.npz too.)
 
-Without the ten keys the workdir holds exactly the files listed above.
+A top-level ``baseline: {k: 5, weights: distance, tau: 1.0, normalize: true, smoothing: 1.0, radius: 2, top: 50}`` (all optional,
+these defaults) fits ``slnlp.EditKNN`` -- k nearest train rows under Levenshtein distance, csrc/edit_knn.hip: the method that needs
+no network -- on the train split and audits the split with ``slnlp.split_audit``; rank 0 writes
+
+    test_baseline.json             the baseline's test_<metric> scores (the metrics of test_output.json, through the same score
+                                   path), its options, the neighbour summary (nearest-distance histogram, 1-NN accuracy, flagged
+                                   rows) and ``refit_vs_baseline``: ``compare`` of the refit against it on the test split
+    test_split_audit.json          rows, radius, exact / near duplicates of test rows in train, the ones whose twin carries another
+                                   label, the nearest-distance histogram, the per-class table, the ``top`` closest pairs and the
+                                   refit's accuracy on the duplicated and on the clean rows
+    test_split_audit_rows.csv      row, label, name, nearest train row, its label, its name, distance, duplicated and whether the
+                                   refit is right, for every test row with a neighbour
+
+(Rows longer than 64 frames are refused, not truncated: the baseline then raises before the grid search's results are written.)
+
+Without the eleven keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -132,7 +147,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics", "baseline")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -579,6 +594,81 @@ def save_train_dynamics(est, train_data, opts, workdir):
     return res
 
 
+BASELINE_DEFAULTS = {"k": 5, "weights": "distance", "tau": 1.0, "normalize": True, "smoothing": 1.0, "radius": 2, "top": 50}
+BASELINE_WEIGHTS = ("uniform", "distance")                                      # SLNLP_EDIT_UNIFORM / _DISTANCE
+BASELINE_MAX_K, BASELINE_MAX_RADIUS = 64, 64                                    # SLNLP_EDIT_MAX_K, SLNLP_EDIT_MAX_LEN
+
+
+def baseline_options(setting):
+    """The ``baseline`` key with its defaults filled in -- {k 5, weights distance, tau 1.0, normalize true, smoothing 1.0, radius 2,
+    top 50} -- or None when the key is absent.  Anything but a dict over these seven keys ({}: all defaults) with ``k`` an integer
+    in 1..64, ``weights`` uniform or distance, ``tau`` and ``smoothing`` finite numbers > 0, ``normalize`` a bool, ``radius`` an
+    integer in 0..64 and ``top`` an integer >= 0 raises ValueError."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"baseline={setting!r}: expected a dict with keys among {tuple(BASELINE_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(BASELINE_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"baseline: unknown keys {unknown} (known: {tuple(BASELINE_DEFAULTS)})")
+    opts = dict(BASELINE_DEFAULTS, **setting)
+    whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    if not whole(opts["k"], 1, BASELINE_MAX_K):
+        raise ValueError(f"baseline: k={opts['k']!r}, expected an integer in 1..{BASELINE_MAX_K}")
+    if opts["weights"] not in BASELINE_WEIGHTS:
+        raise ValueError(f"baseline: weights={opts['weights']!r}, expected one of {BASELINE_WEIGHTS}")
+    for name in ("tau", "smoothing"):
+        v = opts[name]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) < float("inf"):
+            raise ValueError(f"baseline: {name}={v!r}, expected a finite number > 0")
+    if not isinstance(opts["normalize"], bool):
+        raise ValueError(f"baseline: normalize={opts['normalize']!r}, expected true or false")
+    if not whole(opts["radius"], 0, BASELINE_MAX_RADIUS):
+        raise ValueError(f"baseline: radius={opts['radius']!r}, expected an integer in 0..{BASELINE_MAX_RADIUS}")
+    if not whole(opts["top"], 0, 2 ** 31 - 1):
+        raise ValueError(f"baseline: top={opts['top']!r}, expected an integer >= 0")
+    return opts
+
+
+def save_baseline(est, train_data, test_data, opts, intervals, metrics, device, workdir):
+    """``slnlp.EditKNN`` fitted on ``train_data`` and scored on ``test_data`` as ``test_baseline.json``, and ``slnlp.split_audit`` of
+    the split with the refit ``est`` as the judge as ``test_split_audit.json`` / ``test_split_audit_rows.csv`` in ``workdir``.
+    Returns (the ``EditKNN``, the audit)."""
+    from . import metrics as M
+    from .edit_knn import EditKNN, split_audit
+    from .net import ScoringWrapper
+    knn = EditKNN(k=opts["k"], weights=opts["weights"], tau=float(opts["tau"]), normalize=opts["normalize"], smoothing=float(opts["smoothing"]),
+                  device=device).fit(train_data)
+    scores = {f"test_{m}": float(ScoringWrapper(m, test_data.labels())(knn, test_data, test_data.y)) for m in metrics}
+    dist, idx = knn.kneighbors(test_data)
+    rows = np.stack([(idx >= 0).sum(1), np.zeros(len(idx), dtype=np.int64), dist[:, 0], np.zeros(len(idx), dtype=np.int64)], axis=1)
+    summary = M.knn_report(rows, np.stack([dist, idx], axis=2), test_data.y, train_data.y)
+    save_json({"options": {k: opts[k] for k in ("k", "weights", "tau", "normalize", "smoothing")}, "train_rows": len(train_data), "scores": scores,
+               "neighbours": _jsonable(summary), "refit_vs_baseline": _jsonable(est.compare(knn, test_data, **(intervals or {})))},
+              os.path.join(workdir, "test_baseline.json"))
+    audit = split_audit(train_data, test_data, radius=opts["radius"], top=opts["top"], judge=est, device=device)
+    per = audit["per_class"]
+    names = train_data.vocab_y.itos if getattr(train_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    out = {k: audit[k] for k in ("rows", "radius", "exact_duplicates", "near_duplicates", "conflicting", "conflicting_exact", "flagged_queries",
+                                 "flagged_references", "rows_duplicated", "rows_clean", "accuracy", "accuracy_duplicated", "accuracy_clean")}
+    cell = lambda v: None if isinstance(v, float) and v != v else v
+    out = {k: cell(v) for k, v in out.items()}
+    out.update(top=opts["top"], nearest_hist=[int(c) for c in audit["nearest_hist"]], pairs=[list(p) for p in audit["pairs"]],
+               per_class=[{"class": int(c), "name": name(c), "support": int(per["support"][i]), "duplicated": int(per["duplicated"][i]),
+                           "conflicting": int(per["conflicting"][i])} for i, c in enumerate(per["label"])])
+    save_json(out, os.path.join(workdir, "test_split_audit.json"))
+    right = np.asarray(est.predict(test_data)) == np.asarray(test_data.y)
+    with open(os.path.join(workdir, "test_split_audit_rows.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["row", "label", "name", "nearest", "nearest_label", "nearest_name", "distance", "duplicated", "refit_right"])
+        for i in range(len(test_data)):
+            if idx[i, 0] >= 0:
+                yq, yr = int(test_data.y[i]), int(train_data.y[idx[i, 0]])
+                w.writerow([i, yq, name(yq), int(idx[i, 0]), yr, name(yr), int(dist[i, 0]), int(bool(audit["duplicated"][i])), int(bool(right[i]))])
+    return knn, audit
+
+
 PRIOR_SHIFT_DEFAULTS = {"max_iter": 200, "tol": 1e-6, "source": "train"}
 PRIOR_SHIFT_MAX_ITER = 1024                                                     # SLNLP_PRIOR_MAX_ITER
 PRIOR_SHIFT_SOURCES = ("train", "train_labels")
@@ -783,6 +873,7 @@ def run(args):
     label_audit = label_audit_options(args.get("label_audit"))
     attribution = attribution_options(args.get("attribution"))
     dynamics = train_dynamics_options(args.get("train_dynamics"))
+    baseline = baseline_options(args.get("baseline"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -840,6 +931,8 @@ def run(args):
             save_label_audit(gs, factory, train_data, label_audit, seed, workdir)
         if dynamics is not None:
             save_train_dynamics(est, train_data, dynamics, workdir)
+        if baseline is not None:
+            save_baseline(est, train_data, test_data, baseline, intervals, metrics, device, workdir)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

@@ -1,0 +1,268 @@
+"""The non-neural baseline and the audit of a split: k nearest neighbours under Levenshtein distance, on the device.
+
+A row of this data is a short sequence of composite phonology tokens, and the obvious method that needs no network is "look up the
+most similar training signs".  ``EditKNN`` is that method as one more ``LogProbJudge`` host beside ``VotingEnsemble``, ``PriorShift``
+and ``OutOfFold``: ``fit`` uploads the train rows once, and ``_forward_logp(ds, then)`` -- the one hook every consumer goes through
+-- forms all-pairs edit distances, the k nearest references of every query and their vote as float32 log-probs [N, V], library
+launches only (csrc/edit_knn.hip; no torch arithmetic runs on the device).  ``reliability``, ``ranking``,
+``score_interval``, ``label_issues``, ``attribute`` and ``compare`` then work on it unchanged: ``net.compare(knn, X)`` says whether
+a network beats the trivial method.  ``leave_one_out()`` gives out-of-sample log-probs of the train rows themselves with no fit at
+all.
+
+``split_audit`` asks the other question the same distances answer: do the held-out rows have twins in train?  ASL-Phono holds the
+same gloss signed several times; identical or near-identical token sequences on both sides of a split inflate every score, and a
+twin with ANOTHER gloss is irreducible error or a label problem no model-based audit can see.
+
+Rows longer than 64 frames are REFUSED -- ``fit`` raises, a query is flagged and gets a row of NaN -- never truncated: the kernel
+is Myers' bit-vector recurrence with the query in one 64-bit word; longer rows (the multi-word form) are out of scope here."""
+import copy
+
+import numpy as np
+import torch
+from sklearn.base import BaseEstimator, ClassifierMixin
+
+from . import _lib, metrics, ops
+from .data import DeviceRows, TokenDataset
+from .judge import LogProbJudge
+
+WEIGHTS = _lib.EDIT_WEIGHTS
+SCRATCH_PAIRS = 1 << 28                      # (query, reference) pairs per launch sequence: one byte each, 256 MiB of scratch
+
+
+def knn_options(what, k, weights, tau, normalize, smoothing):
+    """The options of ``EditKNN`` checked: (k, weights, tau, normalize, smoothing); anything else raises ValueError"""
+    k = ops._int_in(what, "k", k, 1, _lib.EDIT_MAX_K)
+    if weights not in WEIGHTS:
+        raise ValueError(f"{what}: weights={weights!r}, expected one of {WEIGHTS}")
+    if not isinstance(normalize, (bool, np.bool_)):
+        raise ValueError(f"{what}: normalize={normalize!r}, expected True or False")
+    return k, weights, ops._positive(what, "tau", tau), bool(normalize), ops._positive(what, "smoothing", smoothing)
+
+
+def query_chunks(nq, nr, cap=SCRATCH_PAIRS):
+    """The query rows of one pass in chunks ``[(start, stop), ...]`` that keep ``(stop - start) * nr`` under ``cap`` pairs (a single
+    query where ``nr`` alone exceeds it): every row exactly once, in order."""
+    nq, nr, cap = ops._int_in("query_chunks", "nq", nq, 1, _lib.EDIT_MAX_ROWS), ops._int_in("query_chunks", "nr", nr, 1, _lib.EDIT_MAX_ROWS), \
+        ops._int_in("query_chunks", "cap", cap, 1, _lib.EDIT_MAX_PAIRS)
+    step = max(1, min(nq, cap // nr))
+    return [(a, min(a + step, nq)) for a in range(0, nq, step)]
+
+
+def _check_rows(what, ds):
+    """A TokenDataset whose every row the kernel takes: lengths in 0..min(64, S)"""
+    if not isinstance(ds, TokenDataset):
+        raise TypeError(f"{what}: expected a slnlp.data.TokenDataset, got {type(ds).__name__}")
+    if len(ds) < 1:
+        raise ValueError(f"{what}: the dataset has no rows")
+    top = min(_lib.EDIT_MAX_LEN, int(ds.ids.shape[1]))
+    bad = (ds.lengths < 0) | (ds.lengths > top)
+    if bad.any():
+        raise ValueError(f"{what}: {int(bad.sum())} of {len(ds)} rows have a length outside 0..{top} (first: row {int(np.flatnonzero(bad)[0])}, "
+                         f"length {int(ds.lengths[bad][0])}); rows longer than {_lib.EDIT_MAX_LEN} frames are refused, not truncated")
+
+
+def _cuda_device(device):
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError(f"device={device!r}: the HIP path is the only compute path, expected a cuda device")
+    return dev
+
+
+def _on_stream(dev, body):
+    """``body()`` under the device's gate held shared, on this thread's fit stream; returns once the stream has drained"""
+    from .net import device_gate, device_stream, stream_sync
+    gate = device_gate(dev)
+    gate.enter(False)
+    try:
+        stream = device_stream(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.device(dev), torch.cuda.stream(stream), torch.no_grad():
+            res = body()
+        stream_sync(stream)
+    finally:
+        gate.leave(False)
+    return res
+
+
+def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None):
+    """``ops.edit_knn_rows`` over the queries in ``query_chunks``; ``each(start, stop, buf)`` runs behind every chunk on the same
+    stream.  One scratch and one buffer serve the chunks of equal size."""
+    nq, nr = int(Xq.shape[0]), int(Xr.shape[0])
+    chunks = query_chunks(nq, nr, SCRATCH_PAIRS if cap is None else cap)
+    scratch = torch.empty((chunks[0][1] - chunks[0][0]) * nr, dtype=torch.uint8, device=Xq.device)
+    buf = None
+    for a, b in chunks:
+        if buf is None or buf["shape"][0] != b - a:
+            buf = ops.edit_knn_buffers(b - a, k, Xq.device)
+        ops.edit_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius=radius, exclude=None if exclude is None else exclude[a:b], buf=buf, scratch=scratch)
+        each(a, b, buf)
+
+
+class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
+    """``k`` nearest train rows under unit-cost Levenshtein distance (1..64; ties at the k-th distance go to the lower train row),
+    voting with ``weights`` "uniform" or "distance": w = exp(-d / (tau n)), n = max(len(query), len(neighbour), 1) when
+    ``normalize``, else 1.  p_c = (sum of the weights of the neighbours with label c + smoothing prior_c) / (sum of all weights +
+    smoothing) with ``prior_`` = (n_c + 1) / (N + V) of the train labels, so no class is at 0 and a query without a neighbour gets
+    the prior.  It has no temperature: ``calibration_`` is None, ``temperature_`` 1.0."""
+    calibration_ = None
+    temperature_ = 1.0
+    predict_nonlinearity = "auto"
+    initialized_ = False
+    _loo = False
+    _cap = None                                              # pairs per launch sequence (None: SCRATCH_PAIRS)
+
+    def __init__(self, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None):
+        knn_options("EditKNN", k, weights, tau, normalize, smoothing)
+        if device is not None:
+            _cuda_device(device)
+        self.k, self.weights, self.tau, self.normalize, self.smoothing, self.device = k, weights, tau, normalize, smoothing, device
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, X, y=None):
+        """Check ``X`` (a ``TokenDataset``: lengths in 0..64, labels inside the classes -- ValueError otherwise, before anything
+        touches the GPU) and upload its ids, lengths and labels once.  ``classes_`` as ``NeuralNetClassifier`` sets them: the
+        target vocabulary's indices, or 0..max(y) without one."""
+        knn_options("EditKNN", self.k, self.weights, self.tau, self.normalize, self.smoothing)
+        ds = self._as_dataset(X, y)
+        _check_rows("EditKNN.fit", ds)
+        classes = np.arange(len(ds.vocab_y)) if ds.vocab_y is not None else np.arange(int(ds.y.max()) + 1)
+        V = len(classes)
+        self._refuse_labels("EditKNN.fit", ((ds.y < 0) | (ds.y >= V)).sum(), len(ds), V)
+        dev = _cuda_device(self.device)
+        _lib.require_gpu()
+        self.classes_, self.rows_, self.dataset_ = classes, len(ds), ds
+        self.prior_ = (np.bincount(np.asarray(ds.y), minlength=V).astype(np.float64) + 1.0) / (len(ds) + V)
+        with torch.cuda.device(dev):
+            self._ids, self._lengths, self._y = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (ds.ids, ds.lengths, np.asarray(ds.y)))
+            self._prior = torch.from_numpy(self.prior_).to(dev)
+        self._self_index = None
+        self.initialized_ = True
+        return self
+
+    def leave_one_out(self):
+        """A sibling that shares the device rows and judges the FITTED rows themselves: query i skips reference i, so its
+        log-probs are out of sample with no fit at all.  It refuses every other dataset (length, labels, lengths and ids are
+        compared); the fitted ``EditKNN`` predicts new rows."""
+        self._require_initialized()
+        sib = copy.copy(self)
+        sib._loo = True
+        with torch.cuda.device(self._ids.device):
+            sib._self_index = torch.from_numpy(np.arange(self.rows_, dtype=np.int64)).to(self._ids.device)
+        return sib
+
+    def attribute(self, *args, **kwargs):
+        if self._loo:
+            raise NotImplementedError("EditKNN.leave_one_out: leave-one-out log-probs exist only for the fitted rows themselves, not for "
+                                      "occluded variants of them; attribute with the fitted EditKNN")
+        return super().attribute(*args, **kwargs)
+
+    def _refuse_other_data(self, ds):
+        own = self.dataset_
+        same = isinstance(ds, TokenDataset) and len(ds) == self.rows_ and (ds is own or (np.array_equal(ds.y, own.y) and np.array_equal(ds.lengths, own.lengths)
+                                                                                       and np.array_equal(ds.ids, own.ids)))
+        if not same:
+            raise ValueError(f"EditKNN.leave_one_out: leave-one-out log-probs exist only for the {self.rows_} rows that were fitted on, in their "
+                             f"order; got a dataset of {len(ds)} rows" + ("" if len(ds) != self.rows_ else " with other contents")
+                             + " (the fitted EditKNN predicts new rows)")
+
+    # ------------------------------------------------------------- the hook
+    def _queries(self, ds):
+        """(ids, lengths, labels) of the queries on the fitted rows' device, and the exclusion list"""
+        if self._loo:
+            self._refuse_other_data(ds)
+            return self._ids, self._lengths, self._y, self._self_index
+        if isinstance(ds, DeviceRows):                       # built on the device (LogProbJudge.attribute): taken as they are
+            if ds.ids.device != self._ids.device:
+                raise ValueError(f"EditKNN: the rows are on {ds.ids.device}, the fitted rows on {self._ids.device}")
+            return ds.ids, ds.lengths, ds.y, None
+        if not isinstance(ds, TokenDataset) or len(ds) < 1:
+            raise TypeError("EditKNN: expected a non-empty slnlp.data.TokenDataset or slnlp.data.DeviceRows")
+        dev = self._ids.device
+        return (*(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (ds.ids, ds.lengths, np.asarray(ds.y))), None)
+
+    def _on_stream(self, body):
+        return _on_stream(self._ids.device, body)
+
+    def _forward_logp(self, ds, then):
+        """The float32 log-probs [len(ds), V] of ``ds`` (a ``TokenDataset`` or ``DeviceRows``) on the device, handed to
+        ``then(logp, y_dev)``: the hook every consumer of ``LogProbJudge`` goes through.  The queries go in ``query_chunks``; per
+        chunk ``ops.edit_knn_rows`` and ``ops.edit_knn_logp`` -- five queued launches, nothing waits for the host.  A flagged query shows as a row of NaN."""
+        self._require_initialized()
+        if self._loo:
+            self._refuse_other_data(ds)                      # before anything touches the device
+        k, weights, tau, normalize, lam = knn_options("EditKNN", self.k, self.weights, self.tau, self.normalize, self.smoothing)
+
+        def body():
+            Xq, Lq, yq, exclude = self._queries(ds)
+            out = torch.empty(int(Xq.shape[0]), len(self.classes_), dtype=torch.float32, device=Xq.device)
+
+            def vote(a, b, buf):
+                ops.edit_knn_logp(buf, Lq[a:b], self._lengths, self._y, self._prior, weights=weights, tau=tau, normalize=normalize, lam=lam,
+                                  out=out[a:b])
+            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap)
+            return then(out, yq)
+        return self._on_stream(body)
+
+    # ------------------------------------------------------------ neighbours
+    def kneighbors(self, X, k=None):
+        """``(distances int32 [N, k], indices int64 [N, k])`` of the ``k`` (None: the estimator's) nearest train rows of every row
+        of ``X``, ordered by (distance, train row); (-1, -1) where fewer than k exist or the query's length is outside 0..64.  One
+        download per chunk of queries."""
+        self._require_initialized()
+        k = ops._int_in("EditKNN.kneighbors", "k", self.k if k is None else k, 1, _lib.EDIT_MAX_K)
+        ds = self._as_dataset(X)
+        if self._loo:
+            self._refuse_other_data(ds)
+        got = []
+
+        def body():
+            Xq, Lq, _, exclude = self._queries(ds)
+            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, lambda a, b, buf: got.append(ops.edit_knn_download(buf)["nbr"].copy()), self._cap)
+        self._on_stream(body)
+        nbr = np.concatenate(got, axis=0)
+        return nbr[:, :, 0].astype(np.int32), nbr[:, :, 1].astype(np.int64)
+
+
+def split_audit(train, test, radius=2, top=50, judge=None, device=None):
+    """Do the rows of ``test`` have twins in ``train``?  One ``ops.edit_knn_rows`` pass with k = 1 (the held-out rows as queries, the
+    train rows as references; in chunks where the pairs exceed the scratch cap), one download, then
+    ``metrics.split_audit_report``: exact and near (<= ``radius`` edits, 0..64) duplicates, the ones whose twin carries ANOTHER
+    label, the histogram of nearest distances, a per-class table and the ``top`` closest pairs.  Labels are the datasets' class
+    indices, those of ``classes_`` (the target vocabulary's where there is one).  ``split_audit(train, train)`` -- the same object, or equal
+    contents -- skips every row's own copy and audits the training set's own redundancy.  ``judge`` (any ``LogProbJudge``): adds
+    ``accuracy_duplicated`` / ``accuracy_clean`` and ``rows_duplicated`` / ``rows_clean`` from ``judge.predict(test)``: how much
+    of a reported accuracy sits on rows that have a twin in train (NaN where a side is empty).  Rows whose length lies outside
+    0..64 are not audited: ``flagged_queries`` / ``flagged_references`` count them."""
+    what = "split_audit"
+    for name, ds in (("train", train), ("test", test)):
+        if not isinstance(ds, TokenDataset) or len(ds) < 1:
+            raise TypeError(f"{what}: {name} must be a non-empty slnlp.data.TokenDataset")
+    radius = ops._int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN)
+    top = ops._int_in(what, "top", top, 0, 2 ** 31 - 1)
+    if judge is not None and not isinstance(judge, LogProbJudge):
+        raise TypeError(f"{what}: judge must be a LogProbJudge (a fit, an ensemble, an EditKNN), got {type(judge).__name__}")
+    dev = _cuda_device(device)
+    _lib.require_gpu()
+    own = test is train or (len(test) == len(train) and np.array_equal(test.ids, train.ids) and np.array_equal(test.lengths, train.lengths)
+                            and np.array_equal(test.y, train.y))
+    got = []
+
+    def body():
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        Xr, Lr = up(train.ids), up(train.lengths)
+        Xq, Lq = (Xr, Lr) if own else (up(test.ids), up(test.lengths))
+        exclude = up(np.arange(len(train), dtype=np.int64)) if own else None
+        _search(Xq, Lq, Xr, Lr, 1, radius, exclude, lambda a, b, buf: got.append({n: v.copy() for n, v in ops.edit_knn_download(buf).items()}))
+    _on_stream(dev, body)
+    rows, nbr = np.concatenate([g["rows"] for g in got]), np.concatenate([g["nbr"] for g in got])
+    head = got[0]["head"].copy()
+    head[0] = sum(int(g["head"][0]) for g in got)            # the queries of every chunk; the references are the same in each
+    res = metrics.split_audit_report(rows, nbr, np.asarray(test.y), np.asarray(train.y), radius, top, head=head)
+    res["self"] = bool(own)
+    if judge is not None:
+        right = np.asarray(judge.predict(test)) == np.asarray(test.y)
+        dup = res["duplicated"]
+        res.update(rows_duplicated=int(dup.sum()), rows_clean=int((~dup).sum()),
+                   accuracy_duplicated=float(right[dup].mean()) if dup.any() else float("nan"),
+                   accuracy_clean=float(right[~dup].mean()) if (~dup).any() else float("nan"), accuracy=float(right.mean()))
+    return res

@@ -580,6 +580,91 @@ def train_dynamics_report(got, labels, rows=None, top=50):
             "per_row": {"row": rows, "label": labels, "visits": visits, **stats}}
 
 
+EDIT_BINS = 65                                             # the distances 0 .. SLNLP_EDIT_MAX_LEN
+
+
+def _edit_tables(what, rows, nbr, y_query, y_ref):
+    rows, nbr = np.asarray(rows), np.asarray(nbr)
+    if rows.ndim != 2 or rows.shape[1] != 4 or nbr.ndim != 3 or nbr.shape[0] != rows.shape[0] or nbr.shape[1] < 1 or nbr.shape[2] != 2:
+        raise ValueError(f"{what}: rows int32 [nq, 4] and nbr int32 [nq, k >= 1, 2] expected (ops.edit_knn_download), got {rows.shape} and {nbr.shape}")
+    y_query, y_ref = np.asarray(y_query), np.asarray(y_ref)
+    if y_query.shape != (rows.shape[0],) or y_ref.ndim != 1:
+        raise ValueError(f"{what}: y_query has shape {tuple(y_query.shape)} and y_ref {tuple(y_ref.shape)}, the tables hold {rows.shape[0]} queries")
+    listed = (nbr[:, :, 1] >= 0) & (nbr[:, :, 1] < y_ref.size) & (np.arange(nbr.shape[1])[None, :] < rows[:, :1])
+    return rows.astype(np.int64), nbr.astype(np.int64), y_query, y_ref, listed
+
+
+def _nearest_hist(nearest):
+    hist = np.zeros(EDIT_BINS + 1, dtype=np.int64)
+    hist[:EDIT_BINS] = np.bincount(nearest[(nearest >= 0) & (nearest < EDIT_BINS)], minlength=EDIT_BINS)
+    hist[EDIT_BINS] = np.count_nonzero(nearest < 0)
+    return hist
+
+
+def knn_report(rows, nbr, y_query, y_ref, head=None):
+    """``ops.edit_knn_download``'s tables (``slnlp_edit_knn_rows``, include/slnlp.h) as a summary of a neighbour search, on the host:
+    ``rows`` (queries), ``k``, ``flagged_queries`` (a length outside 0..64: no neighbours), ``no_neighbour`` (unflagged, none found),
+    ``nearest_hist`` int64 [66] (the nearest distance 0..64, last bin: none), ``mean_nearest``, ``mean_found``, and per rank
+    j < k: ``agreement`` (the share of the queries with a j-th neighbour whose label it carries), ``mean_distance`` and ``listed``
+    (how many queries have one); ``accuracy_1nn`` = agreement[0] over ALL unflagged queries (a query without a neighbour is wrong).
+    ``head``: the download's head, for ``flagged_references`` and ``bad_labels`` (None: not reported).  Labels of any dtype."""
+    rows, nbr, yq, yr, listed = _edit_tables("knn_report", rows, nbr, y_query, y_ref)
+    flagged = (rows[:, 3] & 1) != 0
+    nearest = np.where(flagged, -1, rows[:, 2])
+    same = np.zeros(listed.shape, dtype=bool)
+    same[listed] = yr[nbr[:, :, 1][listed]] == np.broadcast_to(yq[:, None], listed.shape)[listed]
+    n_listed = listed.sum(axis=0)
+    usable = int((~flagged).sum())
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res = {"rows": int(rows.shape[0]), "k": int(nbr.shape[1]), "flagged_queries": int(flagged.sum()),
+               "no_neighbour": int(((rows[:, 0] == 0) & ~flagged).sum()), "nearest_hist": _nearest_hist(nearest),
+               "mean_nearest": float(nearest[nearest >= 0].mean()) if (nearest >= 0).any() else float("nan"),
+               "mean_found": float(rows[~flagged, 0].mean()) if usable else float("nan"),
+               "agreement": same.sum(axis=0) / n_listed, "mean_distance": np.where(listed, nbr[:, :, 0], 0).sum(axis=0) / n_listed,
+               "listed": n_listed, "accuracy_1nn": float(same[:, 0].sum() / usable) if usable else float("nan")}
+    if head is not None:
+        res.update(flagged_references=int(head[1]), bad_labels=int(head[2]))
+    return res
+
+
+def split_audit_report(rows, nbr, y_query, y_ref, radius, top, head=None):
+    """Whether held-out rows have twins among the references (``slnlp.split_audit``), from ``ops.edit_knn_download``'s tables of a
+    search of the held-out rows (queries) in the train rows (references), on the host.  A query's NEAREST reference is its first
+    listed neighbour (smallest distance, then lowest row).  Returned: ``rows``; ``exact_duplicates`` (nearest distance 0) and
+    ``near_duplicates`` (<= ``radius``, the exact ones included); ``conflicting``: near duplicates whose nearest reference carries
+    ANOTHER label -- irreducible error, or a label problem no model-based audit sees -- and ``conflicting_exact``;
+    ``nearest_hist`` int64 [66]: the nearest distances 0..64 and a last bin for "none"; ``per_class``: arrays over the sorted
+    distinct query labels -- ``label``, ``support``, ``duplicated``, ``conflicting``; ``pairs``: up to ``top`` tuples (query row,
+    reference row, distance, query label, reference label) of the LISTED neighbours within the radius, smallest distance first,
+    ties by query then reference row; ``duplicated`` bool [rows]; ``radius``; ``flagged_queries`` (a length outside 0..64: not
+    audited) and ``flagged_references`` (``head``: the download's head; None: 0).  Labels of any dtype."""
+    what = "split_audit_report"
+    for name, v, hi in (("radius", radius, EDIT_BINS - 1), ("top", top, 2 ** 31 - 1)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
+            raise ValueError(f"{what}: {name}={v!r}, expected an integer in 0..{hi}")
+    rows, nbr, yq, yr, listed = _edit_tables(what, rows, nbr, y_query, y_ref)
+    flagged = (rows[:, 3] & 1) != 0
+    has = listed[:, 0] & ~flagged
+    nearest = np.where(has, nbr[:, 0, 0], -1)
+    near = has & (nearest <= radius)
+    exact = has & (nearest == 0)
+    other = np.zeros(rows.shape[0], dtype=bool)
+    other[has] = yr[nbr[has, 0, 1]] != yq[has]
+    classes, cls = np.unique(yq, return_inverse=True)
+    C = classes.size
+    q, j = np.nonzero(listed & ~flagged[:, None] & (nbr[:, :, 0] <= radius))
+    d, r = nbr[q, j, 0], nbr[q, j, 1]
+    order = np.lexsort((r, q, d))[:int(top)]
+    plain = lambda v: v.item() if hasattr(v, "item") else v        # (an object array of names hands out the names themselves)
+    pairs = [(int(q[o]), int(r[o]), int(d[o]), plain(yq[q[o]]), plain(yr[r[o]])) for o in order]
+    return {"rows": int(rows.shape[0]), "radius": int(radius), "exact_duplicates": int(exact.sum()), "near_duplicates": int(near.sum()),
+            "conflicting": int((near & other).sum()), "conflicting_exact": int((exact & other).sum()), "nearest_hist": _nearest_hist(nearest),
+            "per_class": {"label": classes, "support": np.bincount(cls, minlength=C), "duplicated": np.bincount(cls[near], minlength=C),
+                          "conflicting": np.bincount(cls[near & other], minlength=C)},
+            "pairs": pairs, "duplicated": near, "flagged_queries": int(flagged.sum()),
+            "flagged_references": int(head[1]) if head is not None else 0}
+
+
 _LOG_FACTORIAL = [0.0]                                     # ln i!, grown on demand with math.lgamma
 
 

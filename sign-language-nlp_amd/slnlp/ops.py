@@ -1392,6 +1392,133 @@ def attribution_download(buf, per_variant=False):
     return buf["packed"].cut("head", "ints" if per_variant else "rows_i")
 
 
+def _edit_side(what, side, X, L):
+    """One side of the edit-distance entry points: ``X`` int64 [n, S] with unit column stride (rows may be padded: ``stride(0) >=
+    S``), ``L`` int64 [n] on its device -> (n, row stride)"""
+    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == torch.int64 and X.dim() == 2 and X.shape[0] >= 1 and X.shape[1] >= 1
+            and (X.stride(1) == 1 or X.shape[1] == 1) and X.stride(0) >= X.shape[1]):
+        raise ValueError(f"{what}: the {side} rows must be an int64 [n >= 1, S >= 1] device tensor with unit column stride")
+    n = int(X.shape[0])
+    if not torch.is_tensor(L):
+        raise ValueError(f"{what}: the {side} lengths must be a contiguous int64 [{n}] tensor on {X.device}")
+    _tensor(what, f"the {side} lengths", L, X.device, torch.int64, n)
+    return n, int(X.stride(0)) if n > 1 else max(int(X.shape[1]), int(X.stride(0)))
+
+
+def _edit_pairs(what, nq, nr):
+    if nq * nr > _lib.EDIT_MAX_PAIRS:
+        raise ValueError(f"{what}: {nq} x {nr} pairs, at most {_lib.EDIT_MAX_PAIRS} (one byte each) are formed per call: pass the queries in chunks")
+
+
+def edit_distances(Xq, Lq, Xr, Lr, out=None):
+    """The unit-cost Levenshtein distance of every (query, reference) pair (``slnlp_edit_distances``, csrc/edit_knn.hip): ``Xq`` int64
+    [nq, S] / ``Lq`` int64 [nq] against ``Xr`` int64 [nr, S'] / ``Lr`` int64 [nr] -> uint8 [nq, nr]; 255 where either row's length
+    lies outside 0..64 (or beyond its row).  Only the first L tokens of a row are read.  ``out``: the matrix to fill.  One launch on
+    the current stream of ``Xq``'s device; no host wait."""
+    _lib.require_gpu()
+    what = "edit_distances"
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    _edit_pairs(what, nq, nr)
+    with torch.cuda.device(Xq.device):
+        if out is None:
+            out = torch.empty(nq, nr, dtype=torch.uint8, device=Xq.device)
+        _tensor(what, "out", out, Xq.device, torch.uint8, (nq, nr))
+        check(load().slnlp_edit_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(out), stream_ptr()), what)
+    return out
+
+
+def edit_knn_buffers(nq, k, device):
+    """The outputs of ``edit_knn_rows`` for ``nq`` queries and ``k`` neighbours as slices of ONE int32 allocation, so that
+    ``edit_knn_download`` is one copy:
+
+        head int64 [8] | rows int32 [nq, 4] | nbr int32 [nq, k, 2]"""
+    what = "edit_knn_buffers"
+    nq, k = _int_in(what, "nq", nq, 1, _lib.EDIT_MAX_ROWS), _int_in(what, "k", k, 1, _lib.EDIT_MAX_K)
+    p = _packed.Packed(torch.int32, (("head", torch.int64, _lib.EDIT_HEAD_BYTES // 8, 8), ("rows", torch.int32, (nq, 4), 8),
+                                     ("nbr", torch.int32, (nq, k, 2), 8)), device)
+    return _packed_dict(p, (nq, k))
+
+
+def edit_knn_rows(Xq, Lq, Xr, Lr, k, *, radius=0, exclude=None, buf=None, scratch=None):
+    """The ``k`` (1..64) nearest references of every query under Levenshtein distance (``slnlp_edit_knn_rows``): per query the
+    usable references of smallest distance ordered by (distance, reference index) -- ties at the k-th distance go to the lower
+    index -- into ``buf`` (``edit_knn_buffers(nq, k, device)``; None: a new one).  ``exclude``: int64 [nq] on the device, the one
+    reference index query i skips (leave-one-out; -1: none), or None.  ``radius`` (0..64): ``rows[:, 1]`` counts the usable
+    references within it.  ``scratch``: a uint8 tensor of at least nq nr elements to hold the distances (None: a new one; it holds
+    the uint8 [nq, nr] matrix afterwards).  Three queued launches on the current stream of ``Xq``'s device; no host wait.
+    Returns ``buf``."""
+    what = "edit_knn_rows"
+    k, radius = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K), _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN)
+    _lib.require_gpu()
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    _edit_pairs(what, nq, nr)
+    dev = Xq.device
+    if exclude is not None:
+        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
+    with torch.cuda.device(dev):
+        if buf is None:
+            buf = edit_knn_buffers(nq, k, dev)
+        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
+        if scratch is None:
+            scratch = torch.empty(nq * nr, dtype=torch.uint8, device=dev)
+        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {nq * nr}] tensor on {dev}")
+        check(load().slnlp_edit_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(exclude), k, radius, ptr(scratch),
+                                         scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
+    return buf
+
+
+def edit_knn_logp(buf, Lq, Lr, yr, prior, *, weights="distance", tau=1.0, normalize=True, lam=1.0, out=None):
+    """The neighbours of ``buf`` (``edit_knn_rows``) as float32 log-probs [nq, V] (``slnlp_edit_knn_logp``, include/slnlp.h states the
+    vote): ``Lq`` int64 [nq] and ``Lr`` / ``yr`` int64 [nr] the lengths and the references' labels, ``prior`` float64 [V] on the
+    device; ``weights`` "uniform" or "distance" (w = exp(-d / (tau n)), n = max(Lq, Lr, 1) when ``normalize``), ``lam`` > 0 the
+    weight of the prior.  A flagged query gets a row of NaN; ``buf["head"][2]`` counts the neighbours whose label lies outside the
+    V classes.  ``out``: a float32 [nq, V] tensor to fill (rows may be padded).  Two queued launches on the current stream of
+    ``buf``'s device; no host wait.  Returns ``out``."""
+    what = "edit_knn_logp"
+    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
+    nq, k = buf["shape"]
+    dev = buf["flat"].device
+    if weights not in _lib.EDIT_WEIGHTS:
+        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
+    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
+    _lib.require_gpu()
+    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
+    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
+    _tensor(what, "Lr", Lr, dev, torch.int64, None)
+    nr = int(Lr.shape[0])
+    _tensor(what, "yr", yr, dev, torch.int64, nr)
+    _tensor(what, "prior", prior, dev, torch.float64, None)
+    V = int(prior.shape[0])
+    if nr < 1 or V < 1:
+        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
+        if out.device != dev or tuple(out.shape) != (nq, V):
+            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
+        ld = _logp_matrix(f"{what} (out)", out)[2]
+        check(load().slnlp_edit_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, _lib.EDIT_WEIGHTS.index(weights),
+                                         tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]), stream_ptr()), what)
+    return out
+
+
+def edit_knn_download(buf, neighbours=True):
+    """What a neighbour search hands to the host in ONE device-to-host copy: {head int64 [8] = (flagged queries, flagged references,
+    neighbours with a label outside the classes, 0, ...), rows int32 [nq, 4] = (found, references within the radius, nearest
+    distance or -1, code bits: 1 the query's length is outside 0..64, 2 its ``exclude`` entry names no reference), nbr int32 [nq, k,
+    2] = (distance, reference index), (-1, -1) past found}; ``neighbours=False`` stops behind rows."""
+    _packed_buf("edit_knn_download", buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
+    return buf["packed"].cut("head", "nbr" if neighbours else "rows")
+
+
 def scatter_logp(logp, rows, out, state=None):
     """``out[rows[i], :] = `` row i of ``logp`` float32 [n, V] (``slnlp_scatter_logp``): with ``state`` (a calibration state whose beta
     is read on the device) the row ``scale_logp`` would write, bit for bit; with None the float32 values themselves.  ``rows``: a
