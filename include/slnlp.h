@@ -220,6 +220,39 @@ int slnlp_attn_cross_bwd(const float* q, const float* kv, int64_t ld_kv, const f
                          float* dq, float* dkv, int64_t ld_dkv,
                          float drop_p, int drop_site, const unsigned long long* rng, void* stream);
 
+/* The same attention WITHOUT projecting the memory (csrc/attention_mem.hip; what the Transformer plan's decoder runs): with one
+ * query per sequence, k_s = Wk mem_s + bk and v_s = Wv mem_s + bv re-associate into per-head B-row products around kernels that
+ * read the memory rows themselves.  mem [S*B, E], rows m = s*B + b; per (sequence, head) row bh = b*H + h:
+ *   forward   qk [B*H, E] = Wk_h^T q_h (the caller's product)  ->  probs [B*H, S] = softmax_s(qk . mem_s / sqrt(dh)) (before
+ *             dropout), pd = dropout(probs) at site element (bh, s), psum [B*H] = sum_s pd, mbar [B*H, E] = sum_s pd mem_s,
+ *             ctx0 [B, E] = bv_h psum (the caller's product Wv_h mbar adds onto it: that is ctx)
+ *   backward  dmbar [B*H, E] = Wv_h^T d ctx_h (the caller's product), dctx [B, E]  ->  dsc [B*H, S] = d score_s =
+ *             probs (t - sum_s probs t) / sqrt(dh) with t = dropout(dmbar . mem_s + dctx_h . bv_h), dqk [B*H, E] = sum_s dsc
+ *             mem_s, dcp [B, E] = dctx_h psum; then, unless dmem is NULL, dmem [S*B, E] (= or, accumulate != 0, +=) sum_h (pd
+ *             dmbar + dsc qk) and dbv [E] = the column sums of dcp.  d bk is exactly zero and is not written.
+ * slnlp_attn_mem_dmem_all: dmem and every layer's dbv of N layers in ONE launch, from a DEVICE table of their buffers (all
+ * written by slnlp_attn_mem_bwd calls with dmem NULL): dmem = the bits of N accumulating calls for layers N-1 ... 0.
+ * H <= 64, dh a multiple of 4 and <= 256, H * dh <= 1024, S <= 5000. */
+int slnlp_attn_mem_fwd(const float* qk, const float* mem, const float* bv, int B, int S, int H, int dh, float* mbar, float* psum,
+                       float* probs, float* ctx0, float drop_p, int drop_site, const unsigned long long* rng, void* stream);
+int slnlp_attn_mem_bwd(const float* mem, const float* bv, const float* probs, const float* psum, const float* qk,
+                       const float* dmbar, const float* dctx, int B, int S, int H, int dh, float* dsc, float* dqk, float* dcp,
+                       float* dbv, float* dmem /* or NULL */, int accumulate, float drop_p, int drop_site,
+                       const unsigned long long* rng, void* stream);
+typedef struct slnlp_xmem_dmem_layer {
+    const float *probs, *dsc, *dmbar, *qk, *dcp;
+    float* dbv;
+    int32_t drop_site;
+    int32_t pad;
+} slnlp_xmem_dmem_layer;
+int slnlp_attn_mem_dmem_all(const slnlp_xmem_dmem_layer* table_dev, int N, int B, int S, int H, int dh, float* dmem, float drop_p,
+                            const unsigned long long* rng, void* stream);
+/* Heads of one sequence that a workgroup of the two kernels above serves from one pass over the memory rows: 0 = automatic
+ * (two, or what the environment variable SLNLP_XMEM_HEADS names), 1 / 2 / 4 forced; a value that does not divide H or whose
+ * LDS does not fit falls back to the next smaller one.  A tuning / test knob: per output element the arithmetic and its
+ * order are the same, so results do not depend on it. */
+int slnlp_set_xmem_heads(int hp);
+
 /* -------------------------------------------------------------- layernorm --
  * y = (x - mean) * rstd * gamma + beta, eps added to the biased variance
  * (torch.nn.LayerNorm as used by nn.Transformer, eps 1e-5).  stats [rows,2] =

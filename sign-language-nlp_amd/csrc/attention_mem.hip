@@ -16,6 +16,8 @@
 //
 // One workgroup per (sequence, head), fp32 FMA arithmetic; every global read is a coalesced row (weights [row][E],
 // memory rows [E]).  The dropout element of p_s is (row b*H + h, column s), as in attention.hip's cross kernels.
+#include <stddef.h>
+
 #include "common.hpp"
 #include "launch.hpp"
 
@@ -579,9 +581,12 @@ static int xmem_init() {                  // dynamic LDS beyond 64 KiB is only n
     });
 }
 
-// heads per workgroup (1: the kernels above).  env SLNLP_XMEM_HEADS = 1 / 2 / 4 forces it (A / B runs).
+// heads per workgroup (1: the kernels above).  env SLNLP_XMEM_HEADS = 1 / 2 / 4 forces it (A / B runs), and so does
+// slnlp_set_xmem_heads (tests: 0 = back to the environment's choice), which is looked at first.
+static std::atomic<int> g_xmem_heads{0};
 static int xmem_heads_per_wg(int B, int S, int H, int dh) {
-    static const int forced = [] { const char* e = getenv("SLNLP_XMEM_HEADS"); return e ? atoi(e) : 0; }();
+    static const int env = [] { const char* e = getenv("SLNLP_XMEM_HEADS"); return e ? atoi(e) : 0; }();
+    const int set = g_xmem_heads.load(std::memory_order_relaxed), forced = set ? set : env;
     const int want = forced ? forced : 2;
     for (int hp = want; hp >= 2; hp >>= 1)
         if (H % hp == 0 && (size_t)hp * (H * dh + ((S + 3) & ~3) + 4) * sizeof(float) <= 65536) return hp;
@@ -653,4 +658,41 @@ int xmem_dmem_all(const XmemDmemLayer* tab, int N, int B, int S, int H, int dh, 
                    dmem, drop_p, dropout_threshold(drop_p), rng);
 }
 
+static_assert(sizeof(slnlp_xmem_dmem_layer) == 56 && sizeof(XmemDmemLayer) == sizeof(slnlp_xmem_dmem_layer) &&
+                  offsetof(XmemDmemLayer, probs) == offsetof(slnlp_xmem_dmem_layer, probs) &&
+                  offsetof(XmemDmemLayer, dsc) == offsetof(slnlp_xmem_dmem_layer, dsc) &&
+                  offsetof(XmemDmemLayer, dmbar) == offsetof(slnlp_xmem_dmem_layer, dmbar) &&
+                  offsetof(XmemDmemLayer, qk) == offsetof(slnlp_xmem_dmem_layer, qk) &&
+                  offsetof(XmemDmemLayer, dcp) == offsetof(slnlp_xmem_dmem_layer, dcp) &&
+                  offsetof(XmemDmemLayer, dbv) == offsetof(slnlp_xmem_dmem_layer, dbv) &&
+                  offsetof(XmemDmemLayer, drop_site) == offsetof(slnlp_xmem_dmem_layer, drop_site) &&
+                  offsetof(XmemDmemLayer, pad) == offsetof(slnlp_xmem_dmem_layer, pad),
+              "slnlp_xmem_dmem_layer (slnlp.h) is the layout of XmemDmemLayer");
+
 }  // namespace slnlp
+
+extern "C" {
+int slnlp_attn_mem_fwd(const float* qk, const float* mem, const float* bv, int B, int S, int H, int dh, float* mbar, float* psum,
+                       float* probs, float* ctx0, float drop_p, int drop_site, const unsigned long long* rng, void* stream) {
+    return slnlp::xmem_fwd(qk, mem, bv, B, S, H, dh, mbar, psum, probs, ctx0, drop_p, drop_site, rng, (hipStream_t)stream);
+}
+int slnlp_attn_mem_bwd(const float* mem, const float* bv, const float* probs, const float* psum, const float* qk, const float* dmbar,
+                       const float* dctx, int B, int S, int H, int dh, float* dsc, float* dqk, float* dcp, float* dbv, float* dmem,
+                       int accumulate, float drop_p, int drop_site, const unsigned long long* rng, void* stream) {
+    return slnlp::xmem_bwd(mem, bv, probs, psum, qk, dmbar, dctx, B, S, H, dh, dsc, dqk, dcp, dbv, dmem, accumulate, drop_p, drop_site,
+                           rng, (hipStream_t)stream);
+}
+int slnlp_attn_mem_dmem_all(const slnlp_xmem_dmem_layer* table_dev, int N, int B, int S, int H, int dh, float* dmem, float drop_p,
+                            const unsigned long long* rng, void* stream) {
+    return slnlp::xmem_dmem_all(reinterpret_cast<const slnlp::XmemDmemLayer*>(table_dev), N, B, S, H, dh, dmem, drop_p, rng,
+                                (hipStream_t)stream);
+}
+int slnlp_set_xmem_heads(int hp) {
+    if (hp != 0 && hp != 1 && hp != 2 && hp != 4) {
+        slnlp::set_error("set_xmem_heads: %d (0 = automatic, 1 / 2 / 4 heads per workgroup)", hp);
+        return SLNLP_ERR_INVALID_ARG;
+    }
+    slnlp::g_xmem_heads.store(hp, std::memory_order_relaxed);
+    return 0;
+}
+}

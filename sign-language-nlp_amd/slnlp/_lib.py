@@ -82,6 +82,10 @@ class LnReduceEntry(C.Structure):
     _fields_ = [("partial", vp), ("dgamma", vp), ("dbeta", vp), ("nblk", i32), ("E", i32)]
 
 
+class XmemDmemLayer(C.Structure):
+    _fields_ = [("probs", vp), ("dsc", vp), ("dmbar", vp), ("qk", vp), ("dcp", vp), ("dbv", vp), ("drop_site", i32), ("pad", i32)]
+
+
 # name -> (restype, argtypes).  Every symbol include/slnlp.h declares is listed;
 # tests/test_abi.py checks the header and this table agree.
 SIGNATURES = {
@@ -108,6 +112,10 @@ SIGNATURES = {
     "slnlp_attn_self_bwd_long": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]),
     "slnlp_attn_cross_fwd": (i32, [vp, vp, i64, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]),
     "slnlp_attn_cross_bwd": (i32, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, i64, f32, i32, vp, vp]),
+    "slnlp_attn_mem_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, f32, i32, vp, vp]),
+    "slnlp_attn_mem_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp]),
+    "slnlp_attn_mem_dmem_all": (i32, [vp, i32, i32, i32, i32, i32, vp, f32, vp, vp]),
+    "slnlp_set_xmem_heads": (i32, [i32]),
     "slnlp_layernorm_fwd": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),
     "slnlp_layernorm_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32), vp]),
     "slnlp_ln_param_reduce": (i32, [vp, i32, i32, vp]),

@@ -298,6 +298,59 @@ def attn_cross_bwd(q, kv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, 
     return dq, dkv
 
 
+def attn_mem_fwd(qk, mem, bv, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None, out=None):
+    """Cross-attention over the unprojected memory, forward (``slnlp_attn_mem_fwd``): qk [B*H, E], mem [S*B, E], bv [E] ->
+    (mbar [B*H, E], psum [B*H], probs [B*H, S], ctx0 [B, E]); ``out``: those four tensors to write into, or None."""
+    _lib.require_gpu()
+    E = H * dh
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=qk.device)
+    mbar, psum, probs, ctx0 = out if out is not None else (new(B * H, E), new(B * H), new(B * H, S), new(B, E))
+    check(load().slnlp_attn_mem_fwd(ptr(qk), ptr(mem), ptr(bv), B, S, H, dh, ptr(mbar), ptr(psum), ptr(probs), ptr(ctx0), drop_p,
+                                    drop_site, ptr(rng), stream_ptr()), "attn_mem_fwd")
+    return mbar, psum, probs, ctx0
+
+
+def attn_mem_bwd(mem, bv, probs, psum, qk, dmbar, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None, want_dmem=True, dmem=None,
+                 accumulate=False, out=None):
+    """Its backward (``slnlp_attn_mem_bwd``) -> (dsc [B*H, S], dqk [B*H, E], dcp [B, E], dbv [E], dmem [S*B, E] | None).
+    ``want_dmem`` False passes a null d memory: the launch that writes it and dbv is left to ``attn_mem_dmem_all``.  ``dmem``
+    None allocates it; ``accumulate`` adds onto the ``dmem`` given.  ``out``: (dsc, dqk, dcp, dbv) to write into, or None."""
+    _lib.require_gpu()
+    E = H * dh
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=mem.device)
+    dsc, dqk, dcp, dbv = out if out is not None else (new(B * H, S), new(B * H, E), new(B, E), new(E))
+    if not want_dmem:
+        dmem = None
+    elif dmem is None:
+        assert not accumulate, "attn_mem_bwd: accumulate needs the d memory to add onto"
+        dmem = new(S * B, E)
+    check(load().slnlp_attn_mem_bwd(ptr(mem), ptr(bv), ptr(probs), ptr(psum), ptr(qk), ptr(dmbar), ptr(dctx), B, S, H, dh, ptr(dsc),
+                                    ptr(dqk), ptr(dcp), ptr(dbv), ptr(dmem), int(bool(accumulate)), drop_p, drop_site, ptr(rng),
+                                    stream_ptr()), "attn_mem_bwd")
+    return dsc, dqk, dcp, dbv, dmem
+
+
+def attn_mem_dmem_all(layers, *, B, S, H, dh, drop_p=0.0, rng=None, dmem=None):
+    """d memory of all decoder layers and every layer's d bv in one launch (``slnlp_attn_mem_dmem_all``).  ``layers``: per layer
+    a dict of the tensors probs, dsc, dmbar, qk, dcp, dbv (dbv is written) and the int drop_site.  -> (dmem [S*B, E], table): the
+    device table of the layers' pointers, which the caller keeps until the launch has run."""
+    _lib.require_gpu()
+    n = len(layers)
+    host = (_lib.XmemDmemLayer * n)(*[_lib.XmemDmemLayer(*[ptr(L[k]) for k in ("probs", "dsc", "dmbar", "qk", "dcp", "dbv")],
+                                                         int(L["drop_site"]), 0) for L in layers])
+    device = layers[0]["probs"].device
+    table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
+    if dmem is None:
+        dmem = torch.empty(S * B, H * dh, dtype=torch.float32, device=device)
+    check(load().slnlp_attn_mem_dmem_all(ptr(table), n, B, S, H, dh, ptr(dmem), drop_p, ptr(rng), stream_ptr()), "attn_mem_dmem_all")
+    return dmem, table
+
+
+def set_xmem_heads(hp):
+    """Heads per workgroup of the two kernels above: 0 automatic, 1 / 2 / 4 forced (``slnlp_set_xmem_heads``)."""
+    check(load().slnlp_set_xmem_heads(int(hp)), "set_xmem_heads")
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
     _lib.require_gpu()
     rows, E = x.shape

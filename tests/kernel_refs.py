@@ -1,7 +1,8 @@
 """Plain restatements of the recurrent and attention kernels' arithmetic for the kernel parity tests (test_rnn_kernels_gpu.py,
-test_attn_long_gpu.py).  Everything is dtype-generic torch on the CPU: the tests run it in float64, take backward references
-from autograd through these forward functions, and rerun it in float32 / with format-rounded products as yardsticks of what a
-chain of timesteps may differ by.  test_kernel_refs_cpu.py pins this module to torch.nn.LSTM / GRU and to oracle.rnn_ref."""
+test_attn_long_gpu.py, test_attn_mem_gpu.py).  Everything is dtype-generic torch on the CPU: the tests run it in float64, take
+backward references from autograd through these forward functions, and rerun it in float32 / with format-rounded products as
+yardsticks of what a chain of timesteps may differ by.  test_kernel_refs_cpu.py pins this module to torch.nn.LSTM / GRU, to
+oracle.rnn_ref and, for the re-associated cross-attention (xmem_ref), to autograd through the projected form (cross_ref)."""
 import math
 
 import torch
@@ -185,3 +186,81 @@ def cross_ref(q, kv, B, S, H, dh, mask=None, p=0.0):
     pr = torch.softmax(qh @ k.transpose(-1, -2) / math.sqrt(dh), -1)       # [B,H,1,S]
     pd = pr if mask is None else pr * mask.view(B, H, 1, S) / (1 - p)
     return (pd @ v).reshape(B, E), pr.view(B, H, S)
+
+
+def xmem_ref(qk, mem, bv, dmbar, dctx, B, S, H, dh, mask=None, p=0.0):
+    """Cross-attention over the unprojected memory (csrc/attention_mem.hip, header comment), every kernel output by name.
+    qk [B*H, E] = Wk_h^T q_h, mem [S*B, E] (rows time-major), bv [E], dmbar [B*H, E] = Wv_h^T d ctx_h, dctx [B, E]; mask
+    [B*H, S]: dropout keep-mask (0 / 1) on the probabilities, row b*H + h.  -> dict: probs, psum, mbar, ctx0 (forward; ctx =
+    Wv_h mbar + ctx0), dsc, dqk, dcp, dbv, dmem (backward), and sc, pd, t (intermediates)."""
+    E = H * dh
+    m = mem.view(S, B, E).transpose(0, 1)                                  # [B,S,E]
+    q3, g3 = qk.view(B, H, E), dmbar.view(B, H, E)
+    keep = torch.ones(B, H, S, dtype=qk.dtype) if mask is None else mask.view(B, H, S).to(qk.dtype) / (1 - p)
+    sc = torch.einsum("bhe,bse->bhs", q3, m) / math.sqrt(dh)
+    probs = torch.softmax(sc, -1)
+    pd = probs * keep
+    psum = pd.sum(-1)                                                      # [B,H]
+    mbar = torch.einsum("bhs,bse->bhe", pd, m)
+    ctx0 = (bv.view(1, H, dh) * psum.unsqueeze(-1)).reshape(B, E)
+    c = (dctx.view(B, H, dh) * bv.view(1, H, dh)).sum(-1)                  # d ctx_h . bv_h
+    t = (torch.einsum("bhe,bse->bhs", g3, m) + c.unsqueeze(-1)) * keep
+    dsc = probs * (t - (probs * t).sum(-1, keepdim=True)) / math.sqrt(dh)
+    dqk = torch.einsum("bhs,bse->bhe", dsc, m)
+    dcp = (dctx.view(B, H, dh) * psum.unsqueeze(-1)).reshape(B, E)
+    dbv = dcp.sum(0)
+    dmem = (torch.einsum("bhs,bhe->sbe", pd, g3) + torch.einsum("bhs,bhe->sbe", dsc, q3)).reshape(S * B, E)
+    return dict(sc=sc.reshape(B * H, S), probs=probs.reshape(B * H, S), pd=pd.reshape(B * H, S), psum=psum.reshape(B * H),
+                mbar=mbar.reshape(B * H, E), ctx0=ctx0, t=t.reshape(B * H, S), dsc=dsc.reshape(B * H, S),
+                dqk=dqk.reshape(B * H, E), dcp=dcp, dbv=dbv, dmem=dmem)
+
+
+XMEM_SHAPES = [(3, 13, 3, 8), (5, 70, 4, 16), (2, 1, 2, 4), (4, 27, 1, 64)]   # (B, S, H, dh) the CPU pins and the GPU parity tests share
+
+
+def xmem_inputs(B, S, H, dh, seed=0):
+    """float32 inputs of the memory cross-attention kernels as the parity tests draw them: everything at unit scale, bv
+    included, but qk at sqrt(dh / E) per element, so that the scores are roughly N(0, 1): a softmax neither flat nor one-hot."""
+    E = H * dh
+    g = torch.Generator().manual_seed(1000 * seed + 97 * B + 13 * S + 7 * H + dh)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    return dict(qk=rnd(B * H, E) * math.sqrt(dh / E), mem=rnd(S * B, E), bv=rnd(E), dmbar=rnd(B * H, E), dctx=rnd(B, E))
+
+
+def xmem_block_inputs(B, S, H, dh, seed=0):
+    """float32 inputs of the whole block in its standard form: q [B, E], mem [S*B, E], the K and V blocks of in_proj (Wk, Wv
+    [E, E] at 1 / sqrt(E), the scale that keeps q . k / sqrt(dh) near N(0, 1)), unit-scale biases bk, bv [E] and dctx [B, E]."""
+    E = H * dh
+    g = torch.Generator().manual_seed(2000 * seed + 97 * B + 13 * S + 7 * H + dh)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    return dict(q=rnd(B, E), mem=rnd(S * B, E), Wk=rnd(E, E) / math.sqrt(E), Wv=rnd(E, E) / math.sqrt(E), bk=rnd(E), bv=rnd(E),
+                dctx=rnd(B, E))
+
+
+def xmem_block_standard(inp, B, S, H, dh, mask=None, p=0.0):
+    """The block as nn.MultiheadAttention computes it, in float64: cross_ref on kv = [mem Wk^T + bk | mem Wv^T + bv] and autograd
+    of sum(ctx * dctx).  -> dict: ctx, probs, dq, dmem, dWk, dWv, dbk, dbv."""
+    E = H * dh
+    leaf = {k: inp[k].double().clone().requires_grad_(True) for k in ("q", "mem", "Wk", "Wv", "bk", "bv")}
+    kv = torch.cat([leaf["mem"] @ leaf["Wk"].T + leaf["bk"], leaf["mem"] @ leaf["Wv"].T + leaf["bv"]], 1)
+    ctx, probs = cross_ref(leaf["q"], kv, B, S, H, dh, None if mask is None else mask.double().view(B, H, S), p)
+    grads = torch.autograd.grad((ctx * inp["dctx"].double()).sum(), [leaf[k] for k in ("q", "mem", "Wk", "Wv", "bk", "bv")])
+    out = dict(zip(("dq", "dmem", "dWk", "dWv", "dbk", "dbv"), grads))
+    out.update(ctx=ctx.detach(), probs=probs.detach().reshape(B * H, S))
+    return out
+
+
+def xmem_block_reassociated(inp, B, S, H, dh, mask=None, p=0.0):
+    """The same block the way the plan runs it, in float64: the per-head products as einsums around xmem_ref.  -> dict as
+    xmem_block_standard's (no dbk: the re-associated form has none), plus qk, dmbar and xmem_ref's own outputs under "x"."""
+    E = H * dh
+    d = {k: v.double() for k, v in inp.items()}
+    Wk, Wv = d["Wk"].view(H, dh, E), d["Wv"].view(H, dh, E)
+    qk = torch.einsum("bhd,hde->bhe", d["q"].view(B, H, dh), Wk).reshape(B * H, E)
+    dmbar = torch.einsum("bhd,hde->bhe", d["dctx"].view(B, H, dh), Wv).reshape(B * H, E)
+    x = xmem_ref(qk, d["mem"], d["bv"], dmbar, d["dctx"], B, S, H, dh, None if mask is None else mask.double(), p)
+    ctx = torch.einsum("bhe,hde->bhd", x["mbar"].view(B, H, E), Wv).reshape(B, E) + x["ctx0"]
+    dq = torch.einsum("bhe,hde->bhd", x["dqk"].view(B, H, E), Wk).reshape(B, E)
+    dWk = torch.einsum("bhd,bhe->hde", d["q"].view(B, H, dh), x["dqk"].view(B, H, E)).reshape(E, E)
+    dWv = torch.einsum("bhd,bhe->hde", d["dctx"].view(B, H, dh), x["mbar"].view(B, H, E)).reshape(E, E)
+    return dict(ctx=ctx, probs=x["probs"], dq=dq, dmem=x["dmem"], dWk=dWk, dWv=dWv, dbv=x["dbv"], qk=qk, dmbar=dmbar, x=x)

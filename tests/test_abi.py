@@ -79,6 +79,46 @@ def test_argument_validation_returns_codes_not_aborts(lib):
     assert lib.slnlp_gemm(None, None) == 1
 
 
+def test_attn_mem_entry_points_validate_before_they_touch_a_device(lib):
+    """slnlp_attn_mem_fwd / _bwd / _dmem_all check shapes and pointers first: codes and messages, no launch, no GPU needed."""
+    from slnlp import _lib
+    buf = (C.c_float * 16)()
+    p = C.cast(buf, C.c_void_p).value                           # any non-null address: nothing below gets as far as reading it
+    INVALID = 1                                                  # SLNLP_ERR_INVALID_ARG
+
+    def fwd(B, S, H, dh, qk=p):
+        return lib.slnlp_attn_mem_fwd(qk, p, p, B, S, H, dh, p, p, p, p, 0.0, 0, None, None)
+
+    def bwd(B, S, H, dh, dsc=p):
+        return lib.slnlp_attn_mem_bwd(p, p, p, p, p, p, p, B, S, H, dh, dsc, p, p, p, None, 0, 0.0, 0, None, None)
+
+    def dmem_all(B, S, H, dh, tab=p, N=1):
+        return lib.slnlp_attn_mem_dmem_all(tab, N, B, S, H, dh, p, 0.0, None, None)
+
+    for call in (fwd, bwd, dmem_all):
+        assert call(2, 3, 65, 4) == INVALID and b"heads" in lib.slnlp_last_error()          # H = 65 > the 64 the LDS tables hold
+        assert call(2, 3, 2, 6) == INVALID and b"head_dim" in lib.slnlp_last_error()        # dh not a multiple of 4
+        assert call(2, 3, 8, 256) == INVALID and b"2048" in lib.slnlp_last_error()          # H * dh = 2048 > 1024
+        assert call(2, 0, 2, 4) == INVALID and call(0, 3, 2, 4) == INVALID and call(2, 5001, 2, 4) == INVALID
+    assert fwd(2, 3, 2, 4, qk=None) == INVALID and b"null" in lib.slnlp_last_error()
+    assert bwd(2, 3, 2, 4, dsc=None) == INVALID and b"null" in lib.slnlp_last_error()
+    assert dmem_all(2, 3, 2, 4, tab=None) == INVALID and b"null" in lib.slnlp_last_error()
+    assert dmem_all(2, 3, 2, 4, N=0) == INVALID
+    assert lib.slnlp_attn_mem_fwd(p, p, p, 2, 3, 2, 4, p, p, p, p, 0.25, 0, None, None) == INVALID      # dropout without its rng
+    assert b"dropout" in lib.slnlp_last_error()
+    assert C.sizeof(_lib.XmemDmemLayer) == 56                    # slnlp_xmem_dmem_layer: six pointers, drop_site, pad
+
+
+def test_set_xmem_heads_takes_0_1_2_4_only(lib):
+    try:
+        for hp in (3, -1, 8, 5):
+            assert lib.slnlp_set_xmem_heads(hp) == 1 and b"set_xmem_heads" in lib.slnlp_last_error()
+        for hp in (1, 2, 4, 0):
+            assert lib.slnlp_set_xmem_heads(hp) == 0
+    finally:
+        assert lib.slnlp_set_xmem_heads(0) == 0
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -114,3 +114,53 @@ def test_chain_yardsticks_are_small_ordered_and_finite(rnn_type):
     for k, v in ref.items():
         assert torch.isfinite(v).all() and float(v.abs().max()) > 0, k
         assert e32[k] < 1e-5 and e3[k] < 1e-4 and e3[k] < e1[k] < 1e-1, (k, e32[k], e3[k], e1[k])
+
+
+def _keep_mask(B, S, H, p, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(B * H, S, generator=g) >= p).double()
+
+
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("B,S,H,dh", kr.XMEM_SHAPES)
+def test_xmem_ref_equals_the_projected_cross_attention_and_its_autograd(B, S, H, dh, p):
+    """xmem_ref, with the per-head products around it, is nn.MultiheadAttention's arithmetic re-associated: forward and every
+    gradient agree with cross_ref on the projected memory to 1e-12, under a dropout mask too, and d bk is zero."""
+    inp = kr.xmem_block_inputs(B, S, H, dh)
+    mask = _keep_mask(B, S, H, p, 31 + S) if p > 0 else None
+    std = kr.xmem_block_standard(inp, B, S, H, dh, mask, p)
+    got = kr.xmem_block_reassociated(inp, B, S, H, dh, mask, p)
+    for k in ("ctx", "probs", "dq", "dmem", "dWk", "dWv", "dbv"):
+        if S == 1 and k in ("dq", "dWk"):                               # a softmax over one element passes no gradient
+            assert float(std[k].abs().max()) < 1e-12 and float(got[k].abs().max()) < 1e-12, k
+            continue
+        assert float(std[k].abs().max()) > 0, k
+        e = kr.rel(got[k], std[k])
+        print(f"xmem_ref vs standard form {(B, S, H, dh)} p={p} {k}: {e:.2e}")
+        assert e < 1e-12, (k, e)
+    assert float(std["dbk"].abs().max()) < 1e-12 * float(std["dbv"].abs().max())      # the kernels write no d bk: there is none
+    x = got["x"]
+    if p > 0:
+        assert float((x["psum"] - 1).abs().max()) > 0.05                 # the mask is live: sum_s p_s != 1
+    else:
+        assert float((x["psum"] - 1).abs().max()) < 1e-14
+    if S == 1:
+        assert torch.equal(x["probs"], torch.ones_like(x["probs"])) and torch.equal(x["dsc"], torch.zeros_like(x["dsc"]))
+
+
+@pytest.mark.parametrize("B,S,H,dh", [s for s in kr.XMEM_SHAPES if s[1] > 1])
+def test_xmem_parity_inputs_see_the_bias_term_under_dropout(B, S, H, dh):
+    """The GPU parity tests' inputs (xmem_inputs: unit-scale bv) must keep  d ctx_h . bv_h  visible: at p = 0.25, d score
+    without that term differs by more than 1e-2 of its scale.  Without dropout the term cancels exactly."""
+    inp = {k: v.double() for k, v in kr.xmem_inputs(B, S, H, dh).items()}
+    mask = _keep_mask(B, S, H, 0.25, 5 + S)
+    nobias = dict(inp, bv=torch.zeros_like(inp["bv"]))                   # bv reaches d score through that term alone
+    full = kr.xmem_ref(B=B, S=S, H=H, dh=dh, mask=mask, p=0.25, **inp)
+    cut = kr.xmem_ref(B=B, S=S, H=H, dh=dh, mask=mask, p=0.25, **nobias)
+    e = kr.rel(cut["dsc"], full["dsc"])
+    print(f"d score without d ctx . bv {(B, S, H, dh)}: {e:.3f} of its scale")
+    assert e > 1e-2
+    assert float((full["psum"] - 1).abs().max()) > 0.05
+    assert kr.rel(kr.xmem_ref(B=B, S=S, H=H, dh=dh, **nobias)["dsc"], kr.xmem_ref(B=B, S=S, H=H, dh=dh, **inp)["dsc"]) < 1e-12
+    sc = full["sc"]
+    assert 0.5 < float(sc.std()) < 2.0                                   # scores near N(0, 1): neither flat nor one-hot
