@@ -1118,6 +1118,49 @@ int slnlp_edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* 
                         int64_t nr, int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior,
                         float* logp, int64_t ld, int64_t* head, void* stream);
 
+/* ------------------------------------- phonology-weighted edit-distance neighbours (csrc/field_knn.hip) --
+ * The same search under a WEIGHTED edit distance (slnlp.PhonoKNN, slnlp.split_audit(field_codes=...)): a token of this data is a
+ * composition of F phonological fields, and substituting one frame for another costs the number of fields in which they differ.
+ * Everything is an integer until the votes; every result is a pure function of the arguments, as above.
+ *
+ * codes   int32 [Vt, F] on the device, 1 <= F <= SLNLP_FIELD_MAX_FIELDS, 1 <= Vt <= INT32_MAX: row v holds the per-field value
+ *         ids of token id v.
+ * sub(a, b) for int64 tokens a, b: 0 if a == b (compared as whole int64 values); otherwise F if either token lies outside
+ *         0..Vt-1 (the table is never read for such a token); otherwise #{f : codes[a, f] != codes[b, f]} -- which may be 0:
+ *         the table defines which tokens are equivalent.
+ * gap     in 1..F: the cost of inserting or deleting one frame.
+ * d(q, r) the minimum total cost of substitutions, insertions and deletions that turn q into r;
+ *         d <= F max(len q, len r) <= 64 F <= 1024.  With F = 1, codes[v, 0] = v and gap = 1 it is the unit Levenshtein distance.
+ * Rows are USABLE exactly as above: a length in 0..min(SLNLP_EDIT_MAX_LEN, row stride); only the first L tokens of a usable row are
+ * read, nothing of an unusable one is.
+ *
+ * slnlp_field_distances: dist uint16 [nq, nr], 65535 where either row is unusable.  One launch.
+ *
+ * slnlp_field_knn_rows: distances into scratch (slnlp_field_knn_scratch_bytes: TWO bytes per pair, 2-byte aligned), then the
+ * selection and the head as slnlp_edit_knn_rows: the k (1..SLNLP_EDIT_MAX_K) usable references of smallest distance ordered by
+ * (distance, index), ties at the k-th distance to the lower index, exclude as above, radius in 0..64 F.  It writes the same head /
+ * rows / nbr buffers (nbr distances are int32).  Three queued launches, no host wait.
+ *
+ * slnlp_field_knn_logp: the vote of slnlp_edit_knn_logp with w_j = exp(-d_j / (tau n_j)), n_j = F (normalize ? max(Lq, Lr_j, 1) :
+ * 1) -- tau is in frames in both metrics, and at F = 1 the vote is the unit-cost one operation for operation.  A neighbour is
+ * listed when 0 <= d <= 64 F.  Two queued launches.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message that names the entry point, before anything is launched): those of the
+ * slnlp_edit_* entry points, and: F outside 1..SLNLP_FIELD_MAX_FIELDS, Vt outside 1..INT32_MAX, gap outside 1..F, radius outside
+ * 0..64 F, a null or misaligned codes (4 bytes) or dist (2 bytes), codes overlapping any output. */
+#define SLNLP_FIELD_MAX_FIELDS 16
+int slnlp_field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                          int64_t nr, const int32_t* codes /* [Vt, F] */, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist /* [nq, nr] */,
+                          void* stream);
+int64_t slnlp_field_knn_scratch_bytes(int64_t nq, int64_t nr);
+int slnlp_field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                         int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k,
+                         int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head /* [8] */, int32_t* rows /* [nq, 4] */,
+                         int32_t* nbr /* [nq, k, 2] */, void* stream);
+int slnlp_field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq,
+                         int64_t nr, int64_t k, int64_t V, int64_t F, int weights, double tau, int normalize, double lam,
+                         const double* prior, float* logp, int64_t ld, int64_t* head, void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);

@@ -14,13 +14,15 @@
 //                 t then runs Myers' single-word recurrence (edit_myers.hpp, the bit-63 note is there) over references t,
 //                 t + 256, ...: per reference token one hash lookup of its mask and one column step.  uint8 [nq, nr]; 255 where
 //                 either row is unusable.
-//   edit_select   a wave per query over its row of the distance matrix: a 65-bin count in LDS (integer atomics) gives the cut-off
+//   edit_select   (the body is edit_shared.hpp's, shared with field_knn.hip; here over uint8 with its 65 bins a compile-time constant)
+//                 a wave per query over its row of the distance matrix: a 65-bin count in LDS (integer atomics) gives the cut-off
 //                 distance T, the count below it and how many rows AT T are still wanted; a second sweep in ascending reference
 //                 index keeps the rows below T and the first wanted ones at T by ordered ballot compaction (lanes_below, as
 //                 augment.hip and attribution.hip close rows up) -- ties at the k-th distance go to the lower index; the <= 64
 //                 kept pairs are ranked by (distance, index) by counting.  The sweep stops once the list is full.
 //   edit_head     one block: the unusable queries and references, summed over the fixed tree.
-//   edit_logp     a wave per query: the neighbours' weights in fp64 and per class their sum IN LIST ORDER.
+//   edit_logp     a wave per query: the neighbours' weights in fp64 and per class their sum IN LIST ORDER.  The distance bound and
+//                 the unit are arguments (64 and 1 here; 64 F and F for field_knn.hip, which launches these kernels too).
 //   edit_bad      one block: the neighbours whose reference label lies outside the classes.
 #include <limits.h>
 #include <math.h>
@@ -28,6 +30,7 @@
 #include "block_reduce.hpp"
 #include "common.hpp"
 #include "edit_myers.hpp"
+#include "edit_shared.hpp"
 #include "launch.hpp"
 #include "spans.hpp"
 
@@ -36,19 +39,9 @@
 
 namespace slnlp {
 
-enum { EDIT_HEAD_QUERIES = 0, EDIT_HEAD_REFERENCES = 1, EDIT_HEAD_BAD_LABELS = 2 };
-constexpr int EDIT_BINS = SLNLP_EDIT_MAX_LEN + 1;        // the distances 0 .. 64
-constexpr int EDIT_NONE = 255;                           // the matrix entry of a pair with an unusable row
 constexpr int EDIT_SLOTS = 128;                          // of the query's token hash: at most 64 are taken, a probe always ends
-constexpr int EDIT_MAX_BLOCKS = 65536;
 
 __device__ __forceinline__ unsigned edit_hash(int64_t c) { return (unsigned)(((uint64_t)c * 0x9E3779B97F4A7C15ull) >> 57); }
-
-// a wave's LDS stores and atomics, done and visible to its other lanes' loads behind this point
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // ------------------------------------------------------------------------------------------------------- distances ----
 __device__ __forceinline__ void edit_dist_body(const int64_t* __restrict__ Xq, long ldq, const int64_t* __restrict__ Lq, int nq,
@@ -123,77 +116,11 @@ __device__ __forceinline__ void edit_dist_body(const int64_t* __restrict__ Xq, l
 SLNLP_ZKERNEL(edit_dist_kernel, 256, edit_dist_body)
 
 // ------------------------------------------------------------------------------------------------------- selection ----
+// the shared body (edit_shared.hpp) over the uint8 matrix, its 65 bins a compile-time constant
 __device__ __forceinline__ void edit_select_body(const unsigned char* __restrict__ dist, const int64_t* __restrict__ Lq,
                                                  const int64_t* __restrict__ exclude, int nq, int nr, int max_q, int k, int radius,
                                                  int* __restrict__ rows, int* __restrict__ nbr) {
-    __shared__ int hist[4][EDIT_BINS];
-    __shared__ int cand_d[4][64];
-    __shared__ int cand_i[4][64];
-    const int w = threadIdx.x >> 6;
-    wave_rows<int>(nq, [&](int q, int lane) {                // q, code, ex and every count below: the same in every lane
-        const int64_t lq = Lq[q];
-        int code = (lq < 0 || lq > max_q) ? SLNLP_EDIT_CODE_QUERY : 0;
-        int ex = -1;
-        if (exclude) {
-            const int64_t e = exclude[q];
-            if (e >= 0 && e < nr) ex = (int)e;
-            else if (e != -1) code |= SLNLP_EDIT_CODE_EXCLUDE;
-        }
-        const bool usable = !(code & SLNLP_EDIT_CODE_QUERY);
-        const unsigned char* row = dist + (long)q * nr;
-        for (int b = lane; b < EDIT_BINS; b += 64) hist[w][b] = 0;
-        wave_lds_sync();
-        if (usable) {
-            for (int j0 = 0; j0 < nr; j0 += 64) {
-                const int j = j0 + lane;
-                if (j < nr && j != ex) {
-                    const int d = row[j];
-                    if (d < EDIT_BINS) atomicAdd(&hist[w][d], 1);
-                }
-            }
-        }
-        wave_lds_sync();
-        int total = 0, cut = EDIT_BINS, below = 0, within = 0, nearest = -1;
-        for (int b = 0; b < EDIT_BINS; ++b) {
-            const int c = hist[w][b];
-            if (c > 0 && nearest < 0) nearest = b;
-            if (cut == EDIT_BINS && total + c >= k) { cut = b; below = total; }
-            total += c;
-            if (b <= radius) within = total;
-        }
-        const int found = total < k ? total : k;
-        const int need = cut < EDIT_BINS ? k - below : 0;    // rows AT the cut-off distance still wanted (cut == 65: every row is below)
-        int base = 0, ties = 0;
-        for (int j0 = 0; j0 < nr && base < found; j0 += 64) {
-            const int j = j0 + lane;
-            int d = EDIT_NONE;
-            if (j < nr && j != ex) d = row[j];
-            const bool tie = d == cut;
-            const unsigned long long tie_ballot = __ballot(tie);
-            const bool take = d < cut && d < EDIT_BINS ? true : (tie && ties + lanes_below(tie_ballot) < need);
-            const unsigned long long take_ballot = __ballot(take);
-            const int slot = base + lanes_below(take_ballot);
-            if (take && slot < 64) { cand_d[w][slot] = d; cand_i[w][slot] = j; }
-            base += __popcll(take_ballot);
-            ties += __popcll(tie_ballot);
-        }
-        wave_lds_sync();
-        const bool mine = lane < found;
-        const int my_d = mine ? cand_d[w][lane] : INT_MAX, my_i = mine ? cand_i[w][lane] : INT_MAX;
-        int pos = 0;                                         // the pairs in front of mine in (distance, index) order: indices are distinct
-        for (int t = 0; t < found; ++t) {
-            const int od = cand_d[w][t], oi = cand_i[w][t];
-            pos += (od < my_d || (od == my_d && oi < my_i)) ? 1 : 0;
-        }
-        int* out = nbr + (long)q * k * 2;
-        if (mine) { out[2 * pos] = my_d; out[2 * pos + 1] = my_i; }
-        else if (lane < k) { out[2 * lane] = -1; out[2 * lane + 1] = -1; }
-        if (lane == 0) {
-            int* r = rows + 4 * (long)q;
-            r[0] = found; r[1] = within; r[2] = nearest; r[3] = code;
-        }
-        wave_lds_sync();                                     // the wave's next query rewrites hist and cand
-    });
+    edit_select_generic<unsigned char, EDIT_NONE, EDIT_BINS, true>(dist, Lq, exclude, nq, nr, max_q, k, radius, EDIT_BINS, rows, nbr);
 }
 SLNLP_ZKERNEL(edit_select_kernel, 256, edit_select_body)
 
@@ -212,12 +139,12 @@ SLNLP_ZKERNEL(edit_head_kernel, 256, edit_head_body)
 
 // ----------------------------------------------------------------------------------------------------------- votes ----
 // the reference label of neighbour j of query q, or -1: outside the list, an index or a distance no selection writes (never used
-// as an address), a label outside the classes.  *d and *idx: the pair
+// as an address), a label outside the classes.  *d and *idx: the pair.  bound: the largest distance of the metric (64, or 64 F)
 __device__ __forceinline__ int edit_neighbour_label(const int* __restrict__ nbr, const int64_t* __restrict__ yr, long q, int j, int k, int nr, int V,
-                                                    int* d, int* idx, bool* listed) {
+                                                    int bound, int* d, int* idx, bool* listed) {
     *d = nbr[(q * k + j) * 2];
     *idx = nbr[(q * k + j) * 2 + 1];
-    *listed = *idx >= 0 && *idx < nr && *d >= 0 && *d < EDIT_BINS;
+    *listed = *idx >= 0 && *idx < nr && *d >= 0 && *d <= bound;
     if (!*listed) return -1;
     const int64_t y = yr[*idx];
     return (y >= 0 && y < V) ? (int)y : -1;
@@ -230,7 +157,7 @@ __device__ __forceinline__ int edit_found(const int* __restrict__ rows, long q, 
 __device__ __forceinline__ void edit_logp_body(const int* __restrict__ nbr, const int* __restrict__ rows, const int64_t* __restrict__ Lq,
                                                const int64_t* __restrict__ Lr, const int64_t* __restrict__ yr, int nq, int nr, int k, int V,
                                                int weights, double tau, int normalize, double lam, const double* __restrict__ prior,
-                                               float* __restrict__ logp, long ld) {
+                                               float* __restrict__ logp, long ld, int bound, int unit) {
     __shared__ double wj[4][64];
     __shared__ int lab[4][64];
     const int w = threadIdx.x >> 6;
@@ -246,16 +173,17 @@ __device__ __forceinline__ void edit_logp_body(const int* __restrict__ nbr, cons
         if (lane < found) {
             int d, idx;
             bool listed;
-            y = edit_neighbour_label(nbr, yr, q, lane, k, nr, V, &d, &idx, &listed);
+            y = edit_neighbour_label(nbr, yr, q, lane, k, nr, V, bound, &d, &idx, &listed);
             if (y >= 0) {
                 wt = 1.0;
                 if (weights == SLNLP_EDIT_DISTANCE) {
-                    double n = 1.0;
+                    int64_t frames = 1;                      // n = unit * frames: tau is in frames in both metrics (unit 1: n as ever)
                     if (normalize) {
                         const int64_t a = Lq[q], b = Lr[idx];
                         const int64_t mx = a > b ? a : b;
-                        n = (double)(mx > 1 ? mx : 1);
+                        frames = mx > 1 ? mx : 1;
                     }
+                    const double n = (double)(frames * unit);
                     wt = exp(-(double)d / (tau * n));
                 }
             }
@@ -282,7 +210,7 @@ __device__ __forceinline__ void edit_logp_body(const int* __restrict__ nbr, cons
 SLNLP_ZKERNEL(edit_logp_kernel, 256, edit_logp_body)
 
 __device__ __forceinline__ void edit_bad_body(const int* __restrict__ nbr, const int* __restrict__ rows, const int64_t* __restrict__ yr, int nq,
-                                              int nr, int k, int V, int64_t* __restrict__ head) {
+                                              int nr, int k, int V, int bound, int64_t* __restrict__ head) {
     __shared__ long long part[256];
     const int tid = threadIdx.x;
     block_sum_rows<1>(&part, tid, (long)nq * k, [&](long g, long long* acc) {
@@ -291,7 +219,7 @@ __device__ __forceinline__ void edit_bad_body(const int* __restrict__ nbr, const
         if ((rows[4 * q + 3] & SLNLP_EDIT_CODE_QUERY) || j >= edit_found(rows, q, k)) return;
         int d, idx;
         bool listed;
-        const int y = edit_neighbour_label(nbr, yr, q, j, k, nr, V, &d, &idx, &listed);
+        const int y = edit_neighbour_label(nbr, yr, q, j, k, nr, V, bound, &d, &idx, &listed);
         acc[0] += (listed && y < 0) ? 1 : 0;
     });
     if (tid == 0) head[EDIT_HEAD_BAD_LABELS] = (int64_t)part[0];
@@ -299,39 +227,21 @@ __device__ __forceinline__ void edit_bad_body(const int* __restrict__ nbr, const
 SLNLP_ZKERNEL(edit_bad_kernel, 256, edit_bad_body)
 
 // ------------------------------------------------------------------------------------------------------- host side ----
-struct EditSide {
-    Span x, l;
-    int max_len;
-};
-// one side's rows: n in 1..INT_MAX, ld >= 1 and addressable, alignment; the bytes that may be read
-static int edit_check_side(const char* what, const char* side, const int64_t* X, int64_t ld, const int64_t* L, int64_t n, EditSide* out) {
-    SLNLP_CHECK_ARG(X && L, "%s: null pointer (%s rows)", what, side);
-    SLNLP_CHECK_ARG(n >= 1 && n <= SLNLP_EDIT_MAX_ROWS, "%s: %s rows n=%ld outside 1..%d", what, side, (long)n, SLNLP_EDIT_MAX_ROWS);
-    SLNLP_CHECK_ARG(ld >= 1 && ld <= INT64_MAX / 8 / n, "%s: %s row stride %ld times %ld rows is no addressable matrix", what, side, (long)ld, (long)n);
-    SLNLP_CHECK_ARG((((uintptr_t)X | (uintptr_t)L) & 7) == 0, "%s: misaligned pointer (%s rows: 8 bytes)", what, side);
-    out->max_len = ld < SLNLP_EDIT_MAX_LEN ? (int)ld : SLNLP_EDIT_MAX_LEN;
-    out->x = Span{X, ((size_t)(n - 1) * (size_t)ld + (size_t)out->max_len) * 8, side};
-    out->l = Span{L, (size_t)n * 8, side};
-    return 0;
-}
 static int edit_check_pairs(const char* what, int64_t nq, int64_t nr) {
     SLNLP_CHECK_ARG(nq <= SLNLP_EDIT_MAX_PAIRS / nr, "%s: %ld x %ld pairs, at most %ld (one byte each) are formed per call", what, (long)nq, (long)nr,
                     (long)SLNLP_EDIT_MAX_PAIRS);
     return 0;
 }
-static inline int edit_blocks(int64_t n) { return (int)(n < EDIT_MAX_BLOCKS ? n : EDIT_MAX_BLOCKS); }
-// the distance launch: a block per query, and with fewer than EDIT_FILL queries the references in y tiles (a multiple of 256, as many
-// tiles as bring the launch to about EDIT_FILL blocks, every tile with work); each tile's block forms the query's hash again
-constexpr int EDIT_FILL = 8192;
+// the distance launch (edit_dist_grid: a block per query, few queries in reference tiles); each tile's block forms the query's hash again
 static int launch_edit_dist(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Xr, int64_t ldr,
                             const int64_t* Lr, int64_t nr, int max_r, unsigned char* dist, hipStream_t st) {
-    int64_t tiles = (EDIT_FILL + nq - 1) / nq;
-    const int64_t most = (nr + 255) / 256;
-    tiles = tiles < 1 ? 1 : (tiles > most ? most : tiles);
-    const int64_t tile = ((nr + tiles - 1) / tiles + 255) / 256 * 256;
-    tiles = (nr + tile - 1) / tile;                          // <= EDIT_FILL
-    return zlaunch(edit_dist_kernel, dim3(edit_blocks(nq), (unsigned)tiles), 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q,
-                   max_r, (int)tile, dist);
+    int tile;
+    const dim3 grid = edit_dist_grid(nq, nr, &tile);
+    return zlaunch(edit_dist_kernel, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, dist);
+}
+
+int edit_launch_head(const char* what, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Lr, int64_t nr, int max_r, int64_t* head, hipStream_t st) {
+    return zlaunch(edit_head_kernel, dim3(1), 256, 0, st, what, Lq, (int)nq, max_q, Lr, (int)nr, max_r, head);
 }
 
 int edit_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
@@ -371,13 +281,12 @@ int edit_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq,
     SLNLP_TRY(launch_edit_dist("edit_knn_distances", Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, dist, st));
     SLNLP_TRY(zlaunch(edit_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, "edit_knn_select", (const unsigned char*)dist, Lq, exclude, (int)nq,
                       (int)nr, Q.max_len, (int)k, (int)radius, (int*)rows, (int*)nbr));
-    return zlaunch(edit_head_kernel, dim3(1), 256, 0, st, "edit_knn_head", Lq, (int)nq, Q.max_len, Lr, (int)nr, R.max_len, head);
+    return edit_launch_head("edit_knn_head", Lq, nq, Q.max_len, Lr, nr, R.max_len, head, st);
 }
 
-int edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
-                  int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior, float* logp, int64_t ld,
-                  int64_t* head, hipStream_t st) {
-    const char* what = "edit_knn_logp";
+int edit_launch_logp(const char* what, const char* what_head, int bound, int unit, const int32_t* nbr, const int32_t* rows, const int64_t* Lq,
+                     const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr, int64_t k, int64_t V, int weights, double tau, int normalize,
+                     double lam, const double* prior, float* logp, int64_t ld, int64_t* head, hipStream_t st) {
     SLNLP_CHECK_ARG(nbr && rows && Lq && Lr && yr && prior && logp && head, "%s: null pointer", what);
     SLNLP_CHECK_ARG(nq >= 1 && nq <= SLNLP_EDIT_MAX_ROWS, "%s: nq=%ld outside 1..%d", what, (long)nq, SLNLP_EDIT_MAX_ROWS);
     SLNLP_CHECK_ARG(nr >= 1 && nr <= SLNLP_EDIT_MAX_ROWS, "%s: nr=%ld outside 1..%d", what, (long)nr, SLNLP_EDIT_MAX_ROWS);
@@ -398,8 +307,15 @@ int edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, co
     const Span out[2] = {z, {head, SLNLP_EDIT_HEAD_BYTES, "head"}};
     SLNLP_TRY(check_no_overlap(what, out, in));
     SLNLP_TRY(zlaunch(edit_logp_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, what, (const int*)nbr, (const int*)rows, Lq, Lr, yr, (int)nq, (int)nr, (int)k,
-                      (int)V, weights, tau, normalize, lam, prior, logp, (long)ld));
-    return zlaunch(edit_bad_kernel, dim3(1), 256, 0, st, "edit_knn_logp_head", (const int*)nbr, (const int*)rows, yr, (int)nq, (int)nr, (int)k, (int)V, head);
+                      (int)V, weights, tau, normalize, lam, prior, logp, (long)ld, bound, unit));
+    return zlaunch(edit_bad_kernel, dim3(1), 256, 0, st, what_head, (const int*)nbr, (const int*)rows, yr, (int)nq, (int)nr, (int)k, (int)V, bound, head);
+}
+
+int edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
+                  int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior, float* logp, int64_t ld,
+                  int64_t* head, hipStream_t st) {
+    return edit_launch_logp("edit_knn_logp", "edit_knn_logp_head", SLNLP_EDIT_MAX_LEN, 1, nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau, normalize, lam,
+                            prior, logp, ld, head, st);
 }
 
 }  // namespace slnlp

@@ -1,0 +1,235 @@
+// field_knn.hip -- the phonology-weighted edit distance between two sets of token rows and the k nearest references of every query,
+// on the device (slnlp.PhonoKNN, slnlp.split_audit(field_codes=...)).  A token of this data is a composition
+// of F phonological fields; substituting one frame for another costs the number of fields in which they differ, inserting or
+// deleting a frame costs gap.  include/slnlp.h states the definitions; tests/field_knn_ref.py restates them in numpy.
+//
+// Rows, usability and the buffers are those of edit_knn.hip; codes int32 [Vt, F] holds the per-field value ids of token id v in row
+// v.  EVERYTHING IS INTEGER until the votes and there are no atomics on global memory: each result is a pure function of the
+// arguments, whatever the grid, the stream or the kernels beside it.
+//
+//   field_dist    a block per query (queries over a grid-stride loop; with few queries the references in tiles over grid.y, as
+//                 edit_dist).  The query's tokens, their "outside the table" flags and their code vectors -- padded with zeros to 16
+//                 entries -- go to LDS once per block and query.  Thread t then runs the weighted recurrence (field_edit.hpp) over
+//                 the references t, t + 256, ...: per reference token its code vector into 4 G registers (fixed indices: the kernel
+//                 is built for G = (F + 3) / 4 = 1, 2, 3 and 4 groups of four fields, so a cell is straight-line code and its
+//                 LDS reads are all in flight before the first compare) and one column step.  THE COLUMN lives transposed in LDS,
+//                 col[word][thread] with two uint16 positions per dword: 32 x 256 dwords = 32 KiB, 37.6 KiB a block with the query.
+//                 A wave's 64 lanes read and write 64 consecutive dwords (every bank once: no conflict), the query's entries are
+//                 read at one address by all lanes (a broadcast).  uint16 [nq, nr]; 65535 where either row is unusable.
+//   field_select  edit_shared.hpp's selection body over the uint16 matrix with 64 F + 1 <= 1025 bins.
+//   the head and the votes are edit_knn.hip's kernels with the bound 64 F and the unit F.
+#include <limits.h>
+
+#include "common.hpp"
+#include "edit_shared.hpp"
+#include "field_edit.hpp"
+#include "launch.hpp"
+#include "spans.hpp"
+
+namespace slnlp {
+
+constexpr int FIELD_NONE = 65535;                                            // the matrix entry of a pair with an unusable row
+constexpr int FIELD_BINS_CAP = SLNLP_EDIT_MAX_LEN * SLNLP_FIELD_MAX_FIELDS + 1;   // the distances 0 .. 1024
+static_assert(FIELD_MAX == SLNLP_FIELD_MAX_FIELDS && FIELD_WORDS * 2 == SLNLP_EDIT_MAX_LEN, "field_edit.hpp and slnlp.h disagree");
+
+// a thread's column: word p of thread t at col[p][t]
+struct FieldLdsColumn {
+    unsigned* base;
+    __device__ __forceinline__ unsigned load(int p) const { return base[p * 256]; }
+    __device__ __forceinline__ void store(int p, unsigned w) const { base[p * 256] = w; }
+};
+
+// ------------------------------------------------------------------------------------------------------- distances ----
+template <int G>
+__device__ __forceinline__ void field_dist_impl(const int64_t* __restrict__ Xq, long ldq, const int64_t* __restrict__ Lq, int nq,
+                                                const int64_t* __restrict__ Xr, long ldr, const int64_t* __restrict__ Lr, int nr, int max_q,
+                                                int max_r, int tile, const int* __restrict__ codes, int F, int Vt, int gap,
+                                                unsigned short* __restrict__ dist) {                 // (F + 3) / 4 == G
+    __shared__ int64_t qtok[SLNLP_EDIT_MAX_LEN];
+    __shared__ int qout[SLNLP_EDIT_MAX_LEN];
+    __shared__ __attribute__((aligned(16))) int qcode[SLNLP_EDIT_MAX_LEN][FIELD_MAX];
+    __shared__ unsigned col[FIELD_WORDS][256];
+    const int tid = threadIdx.x;
+    const FieldLdsColumn column{&col[0][tid]};
+    const long j_begin = (long)blockIdx.y * tile;
+    const int j_end = (int)(j_begin + tile < nr ? j_begin + tile : nr);
+    for (int q = blockIdx.x; q < nq; q += gridDim.x) {       // q, lq, m: the same in every thread, so is every branch on them
+        const int64_t lq = Lq[q];
+        unsigned short* out = dist + (long)q * nr;
+        if (lq < 0 || lq > max_q) {                          // reads nothing more
+            for (int j = (int)j_begin + tid; j < j_end; j += 256) out[j] = (unsigned short)FIELD_NONE;
+            continue;
+        }
+        const int m = (int)lq;
+        const int words = (m + 1) >> 1;
+        __syncthreads();                                     // the reads of the block's previous query are over
+        // 64 positions x 16 entries: zeros behind the query's length, behind F and for a token outside the table (never looked up)
+        for (int i = tid; i < SLNLP_EDIT_MAX_LEN * FIELD_MAX; i += 256) {
+            const int j = i >> 4, f = i & (FIELD_MAX - 1);
+            int v = 0;
+            if (j < m && f < F) {
+                const int64_t c = Xq[(long)q * ldq + j];
+                if (c >= 0 && c < Vt) v = codes[c * F + f];
+            }
+            qcode[j][f] = v;
+        }
+        if (tid < SLNLP_EDIT_MAX_LEN) {
+            const int64_t c = tid < m ? Xq[(long)q * ldq + tid] : 0;
+            qtok[tid] = c;
+            qout[tid] = (c >= 0 && c < Vt) ? 0 : 1;
+        }
+        __syncthreads();
+        for (int j = (int)j_begin + tid; j < j_end; j += 256) {
+            const int64_t lr = Lr[j];
+            int d;
+            if (lr < 0 || lr > max_r) {
+                d = FIELD_NONE;
+            } else {
+                const int64_t* row = Xr + (long)j * ldr;
+                const int n = (int)lr;
+                field_column_begin(column, words, gap);
+                for (int t = 0; t < n; ++t) {
+                    const int64_t c = row[t];
+                    const bool inside = c >= 0 && c < Vt;
+                    int rc[4 * G];
+#pragma unroll
+                    for (int f = 0; f < 4 * G; ++f) rc[f] = (inside && f < F) ? codes[c * F + f] : 0;
+                    field_column_step(column, words, t + 1, gap, [&](int p) {
+                        return field_sub(qtok[p] == c, (qout[p] != 0) | !inside, field_differ_groups<G>(qcode[p], rc), F);
+                    });
+                }
+                d = field_column_score(column, m, n, gap);
+            }
+            out[j] = (unsigned short)d;
+        }
+    }
+}
+#define SLNLP_FIELD_DIST(G)                                                                                                                \
+    __device__ __forceinline__ void field_dist_body_g##G(const int64_t* __restrict__ Xq, long ldq, const int64_t* __restrict__ Lq, int nq,  \
+                                                         const int64_t* __restrict__ Xr, long ldr, const int64_t* __restrict__ Lr, int nr,  \
+                                                         int max_q, int max_r, int tile, const int* __restrict__ codes, int F, int Vt,      \
+                                                         int gap, unsigned short* __restrict__ dist) {                                      \
+        field_dist_impl<G>(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, max_q, max_r, tile, codes, F, Vt, gap, dist);                                  \
+    }                                                                                                                                      \
+    SLNLP_ZKERNEL(field_dist_kernel_g##G, 256, field_dist_body_g##G)
+SLNLP_FIELD_DIST(1)
+SLNLP_FIELD_DIST(2)
+SLNLP_FIELD_DIST(3)
+SLNLP_FIELD_DIST(4)
+#undef SLNLP_FIELD_DIST
+
+// ------------------------------------------------------------------------------------------------------- selection ----
+__device__ __forceinline__ void field_select_body(const unsigned short* __restrict__ dist, const int64_t* __restrict__ Lq,
+                                                  const int64_t* __restrict__ exclude, int nq, int nr, int max_q, int k, int radius, int bins,
+                                                  int* __restrict__ rows, int* __restrict__ nbr) {
+    edit_select_generic<unsigned short, FIELD_NONE, FIELD_BINS_CAP, false>(dist, Lq, exclude, nq, nr, max_q, k, radius, bins, rows, nbr);
+}
+SLNLP_ZKERNEL(field_select_kernel, 256, field_select_body)
+
+// ------------------------------------------------------------------------------------------------------- host side ----
+// the table and the gap: F in 1..16, Vt in 1..INT32_MAX, gap in 1..F, codes 4-byte aligned; the bytes that are read
+static int field_check_table(const char* what, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, Span* out) {
+    SLNLP_CHECK_ARG(codes, "%s: null pointer (codes)", what);
+    SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
+    SLNLP_CHECK_ARG(Vt >= 1 && Vt <= INT_MAX, "%s: Vt=%ld outside 1..%d", what, (long)Vt, INT_MAX);
+    SLNLP_CHECK_ARG(gap >= 1 && gap <= F, "%s: gap=%ld outside 1..F=%ld", what, (long)gap, (long)F);
+    SLNLP_CHECK_ARG(((uintptr_t)codes & 3) == 0, "%s: misaligned pointer (codes: 4 bytes)", what);
+    *out = Span{codes, (size_t)Vt * (size_t)F * 4, "codes"};
+    return 0;
+}
+static int field_check_pairs(const char* what, int64_t nq, int64_t nr) {
+    SLNLP_CHECK_ARG(nq <= SLNLP_EDIT_MAX_PAIRS / nr, "%s: %ld x %ld pairs, at most %ld (two bytes each) are formed per call", what, (long)nq, (long)nr,
+                    (long)SLNLP_EDIT_MAX_PAIRS);
+    return 0;
+}
+static int launch_field_dist(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Xr, int64_t ldr,
+                             const int64_t* Lr, int64_t nr, int max_r, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, unsigned short* dist,
+                             hipStream_t st) {
+    int tile;
+    const dim3 grid = edit_dist_grid(nq, nr, &tile);
+    const int groups = (int)(F + 3) / 4;                     // 1..4: the kernel built for that many groups of four fields
+    auto kern = groups == 1 ? field_dist_kernel_g1 : groups == 2 ? field_dist_kernel_g2 : groups == 3 ? field_dist_kernel_g3 : field_dist_kernel_g4;
+    return zlaunch(kern, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, (const int*)codes, (int)F,
+                   (int)Vt, (int)gap, dist);
+}
+
+int field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
+                    const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, hipStream_t st) {
+    const char* what = "field_distances";
+    EditSide Q, R;
+    Span table;
+    SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
+    SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
+    SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
+    SLNLP_CHECK_ARG(dist, "%s: null pointer (dist)", what);
+    SLNLP_CHECK_ARG(((uintptr_t)dist & 1) == 0, "%s: misaligned pointer (dist: 2 bytes)", what);
+    SLNLP_TRY(field_check_pairs(what, nq, nr));
+    const Span in[5] = {Q.x, Q.l, R.x, R.l, table};
+    const Span out[1] = {{dist, (size_t)nq * (size_t)nr * 2, "dist"}};
+    SLNLP_TRY(check_no_overlap(what, out, in));
+    return launch_field_dist(what, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, (unsigned short*)dist, st);
+}
+
+int field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
+                   const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k, int64_t radius, void* scratch,
+                   int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
+    const char* what = "field_knn_rows";
+    EditSide Q, R;
+    Span table;
+    SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
+    SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
+    SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
+    SLNLP_CHECK_ARG(scratch && head && rows && nbr, "%s: null pointer (scratch, head, rows or nbr)", what);
+    SLNLP_TRY(field_check_pairs(what, nq, nr));
+    SLNLP_CHECK_ARG(k >= 1 && k <= SLNLP_EDIT_MAX_K, "%s: k=%ld outside 1..%d", what, (long)k, SLNLP_EDIT_MAX_K);
+    const int64_t bound = SLNLP_EDIT_MAX_LEN * F;
+    SLNLP_CHECK_ARG(radius >= 0 && radius <= bound, "%s: radius=%ld outside 0..64 F=%ld", what, (long)radius, (long)bound);
+    const size_t pairs = (size_t)nq * (size_t)nr;
+    SLNLP_TRY(check_scratch(what, scratch, scratch_bytes, pairs * 2, nq, 0, 2));
+    SLNLP_CHECK_ARG((((uintptr_t)head | (uintptr_t)exclude) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)nbr) & 3) == 0,
+                    "%s: misaligned pointer (head, exclude: 8 bytes; rows, nbr: 4 bytes)", what);
+    const Span in[6] = {Q.x, Q.l, R.x, R.l, {exclude, (size_t)nq * 8, "exclude"}, table};
+    const Span out[4] = {{scratch, pairs * 2, "scratch"}, {head, SLNLP_EDIT_HEAD_BYTES, "head"}, {rows, (size_t)nq * 16, "rows"},
+                         {nbr, (size_t)nq * (size_t)k * 8, "nbr"}};
+    SLNLP_TRY(check_no_overlap(what, out, in));
+    unsigned short* dist = (unsigned short*)scratch;
+    SLNLP_TRY(launch_field_dist("field_knn_distances", Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, dist, st));
+    SLNLP_TRY(zlaunch(field_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, "field_knn_select", (const unsigned short*)dist, Lq, exclude, (int)nq,
+                      (int)nr, Q.max_len, (int)k, (int)radius, (int)bound + 1, (int*)rows, (int*)nbr));
+    return edit_launch_head("field_knn_head", Lq, nq, Q.max_len, Lr, nr, R.max_len, head, st);
+}
+
+int field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
+                   int64_t k, int64_t V, int64_t F, int weights, double tau, int normalize, double lam, const double* prior, float* logp, int64_t ld,
+                   int64_t* head, hipStream_t st) {
+    const char* what = "field_knn_logp";
+    SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
+    return edit_launch_logp(what, "field_knn_logp_head", (int)(SLNLP_EDIT_MAX_LEN * F), (int)F, nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau, normalize,
+                            lam, prior, logp, ld, head, st);
+}
+
+}  // namespace slnlp
+
+extern "C" int slnlp_field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                                     int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, void* stream) {
+    return slnlp::field_distances(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, gap, dist, (hipStream_t)stream);
+}
+extern "C" int64_t slnlp_field_knn_scratch_bytes(int64_t nq, int64_t nr) {
+    if (nq < 1 || nq > SLNLP_EDIT_MAX_ROWS || nr < 1 || nr > SLNLP_EDIT_MAX_ROWS || nq > SLNLP_EDIT_MAX_PAIRS / nr) {
+        slnlp::set_error("field_knn_scratch_bytes: %ld x %ld pairs: both counts lie in 1..%d and at most %ld pairs are formed per call", (long)nq,
+                         (long)nr, SLNLP_EDIT_MAX_ROWS, (long)SLNLP_EDIT_MAX_PAIRS);
+        return -1;
+    }
+    return nq * nr * 2;
+}
+extern "C" int slnlp_field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                                    int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k,
+                                    int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, void* stream) {
+    return slnlp::field_knn_rows(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr,
+                                 (hipStream_t)stream);
+}
+extern "C" int slnlp_field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
+                                    int64_t k, int64_t V, int64_t F, int weights, double tau, int normalize, double lam, const double* prior, float* logp,
+                                    int64_t ld, int64_t* head, void* stream) {
+    return slnlp::field_knn_logp(nbr, rows, Lq, Lr, yr, nq, nr, k, V, F, weights, tau, normalize, lam, prior, logp, ld, head, (hipStream_t)stream);
+}

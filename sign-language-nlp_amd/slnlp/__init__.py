@@ -1,7 +1,7 @@
 """slnlp: the MI355X path of the sign-language gloss classifier.  The submodules are imported on demand (``slnlp.net``,
-``slnlp.ops``, ...); ``slnlp.VotingEnsemble``, ``slnlp.PriorShift``, ``slnlp.OutOfFold``, ``slnlp.cross_fit``, ``slnlp.EditKNN`` and
-``slnlp.split_audit`` are resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
-__all__ = ["VotingEnsemble", "PriorShift", "OutOfFold", "cross_fit", "EditKNN", "split_audit"]
+``slnlp.ops``, ...); ``slnlp.VotingEnsemble``, ``slnlp.PriorShift``, ``slnlp.OutOfFold``, ``slnlp.cross_fit``, ``slnlp.EditKNN``,
+``slnlp.PhonoKNN`` and ``slnlp.split_audit`` are resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
+__all__ = ["VotingEnsemble", "PriorShift", "OutOfFold", "cross_fit", "EditKNN", "PhonoKNN", "split_audit"]
 
 
 def __getattr__(name):
@@ -14,7 +14,7 @@ def __getattr__(name):
     if name in ("OutOfFold", "cross_fit"):
         from . import out_of_fold
         return getattr(out_of_fold, name)
-    if name in ("EditKNN", "split_audit"):
+    if name in ("EditKNN", "PhonoKNN", "split_audit"):
         from . import edit_knn
         return getattr(edit_knn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -133,7 +133,19 @@ no network -- on the train split and audits the split with ``slnlp.split_audit``
 
 (Rows longer than 64 frames are refused, not truncated: the baseline then raises before the grid search's results are written.)
 
-Without the eleven keys the workdir holds exactly the files listed above.
+A top-level ``phono_baseline: {k: 5, weights: distance, tau: 1.0, normalize: true, smoothing: 1.0, gap: null, radius: null, top: 50}``
+(all optional, these defaults) does the same under the PHONOLOGY-WEIGHTED edit distance (``slnlp.PhonoKNN``, csrc/field_knn.hip):
+substituting one frame for another costs the number of fields in which they differ, inserting or deleting one costs ``gap`` (null:
+the number of fields F), and ``radius`` (null: F, one frame) is in field units.  The code table comes from the config's own
+``dataset_args.fields`` and ``composition_strategy`` (``slnlp.ingest.field_codes``); rank 0 writes
+
+    test_phono_baseline.json         as test_baseline.json, with ``refit_vs_phono`` -- and, when ``baseline`` is set too,
+                                     ``baseline_vs_phono``: ``compare`` of the unit-cost baseline against this one on paired
+                                     resamples of the test split, i.e. whether the field metric beats the unit metric on this data
+    test_phono_split_audit.json      as test_split_audit.json in field units (the histogram has 64 F + 2 bins), with gap and fields
+    test_phono_split_audit_rows.csv  as test_split_audit_rows.csv
+
+Without the twelve keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -147,7 +159,7 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics", "baseline")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics", "baseline", "phono_baseline")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -669,6 +681,107 @@ def save_baseline(est, train_data, test_data, opts, intervals, metrics, device, 
     return knn, audit
 
 
+PHONO_BASELINE_DEFAULTS = {"k": 5, "weights": "distance", "tau": 1.0, "normalize": True, "smoothing": 1.0, "gap": None, "radius": None, "top": 50}
+PHONO_MAX_FIELDS = 16                                                           # SLNLP_FIELD_MAX_FIELDS
+
+
+def phono_baseline_options(setting):
+    """The ``phono_baseline`` key with its defaults filled in -- {k 5, weights distance, tau 1.0, normalize true, smoothing 1.0, gap
+    null (-> F), radius null (-> F), top 50} -- or None when the key is absent.  Anything but a dict over these eight keys ({}: all
+    defaults) raises ValueError: the five voting options as ``baseline``'s, ``gap`` null or an integer in 1..16, ``radius`` null or
+    an integer in 0..1024 (both are held to the F of the config's fields once the table is built), ``top`` an integer >= 0."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"phono_baseline={setting!r}: expected a dict with keys among {tuple(PHONO_BASELINE_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(PHONO_BASELINE_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"phono_baseline: unknown keys {unknown} (known: {tuple(PHONO_BASELINE_DEFAULTS)})")
+    opts = dict(PHONO_BASELINE_DEFAULTS, **setting)
+    whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    if not whole(opts["k"], 1, BASELINE_MAX_K):
+        raise ValueError(f"phono_baseline: k={opts['k']!r}, expected an integer in 1..{BASELINE_MAX_K}")
+    if opts["weights"] not in BASELINE_WEIGHTS:
+        raise ValueError(f"phono_baseline: weights={opts['weights']!r}, expected one of {BASELINE_WEIGHTS}")
+    for name in ("tau", "smoothing"):
+        v = opts[name]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) < float("inf"):
+            raise ValueError(f"phono_baseline: {name}={v!r}, expected a finite number > 0")
+    if not isinstance(opts["normalize"], bool):
+        raise ValueError(f"phono_baseline: normalize={opts['normalize']!r}, expected true or false")
+    if opts["gap"] is not None and not whole(opts["gap"], 1, PHONO_MAX_FIELDS):
+        raise ValueError(f"phono_baseline: gap={opts['gap']!r}, expected null (the number of fields) or an integer in 1..{PHONO_MAX_FIELDS}")
+    if opts["radius"] is not None and not whole(opts["radius"], 0, BASELINE_MAX_RADIUS * PHONO_MAX_FIELDS):
+        raise ValueError(f"phono_baseline: radius={opts['radius']!r}, expected null (the number of fields) or an integer in "
+                         f"0..{BASELINE_MAX_RADIUS * PHONO_MAX_FIELDS}")
+    if not whole(opts["top"], 0, 2 ** 31 - 1):
+        raise ValueError(f"phono_baseline: top={opts['top']!r}, expected an integer >= 0")
+    return opts
+
+
+def phono_field_codes(dataset, dataset_args):
+    """The code table of ``phono_baseline`` from the config's own ``dataset_args.fields`` and ``composition_strategy``
+    (``slnlp.ingest.field_codes``); ValueError without fields or without a source vocabulary that names the tokens"""
+    from .ingest import field_codes
+    fields = list((dataset_args or {}).get("fields") or [])
+    if not fields or getattr(dataset, "vocab_X", None) is None or not hasattr(dataset.vocab_X, "itos"):
+        raise ValueError("phono_baseline: needs dataset_args.fields and a dataset built from them (its vocabulary names the tokens)")
+    if len(fields) > PHONO_MAX_FIELDS:
+        raise ValueError(f"phono_baseline: {len(fields)} fields, at most {PHONO_MAX_FIELDS} are taken")
+    return field_codes(dataset.vocab_X, fields, (dataset_args or {}).get("composition_strategy", "as_words"))
+
+
+def save_phono_baseline(est, train_data, test_data, opts, dataset_args, intervals, metrics, device, workdir, unit=None, field_codes=None):
+    """``slnlp.PhonoKNN`` fitted on ``train_data`` and scored on ``test_data`` as ``test_phono_baseline.json``, and
+    ``slnlp.split_audit(field_codes=...)`` of the split with the refit ``est`` as the judge as ``test_phono_split_audit.json`` /
+    ``test_phono_split_audit_rows.csv`` in ``workdir``.  ``field_codes``: the table (None: ``phono_field_codes``).  ``unit``: the
+    fitted ``EditKNN`` of the ``baseline`` key when that is set too -- ``baseline_vs_phono`` is its ``compare`` against the field
+    metric on paired resamples.  Returns (the ``PhonoKNN``, the audit)."""
+    from . import metrics as M
+    from .edit_knn import PhonoKNN, split_audit
+    from .net import ScoringWrapper
+    codes = phono_field_codes(train_data, dataset_args) if field_codes is None else np.asarray(field_codes)
+    F = int(codes.shape[1])
+    gap = F if opts["gap"] is None else opts["gap"]
+    radius = F if opts["radius"] is None else opts["radius"]
+    if not 1 <= gap <= F:
+        raise ValueError(f"phono_baseline: gap={gap!r}, expected null or an integer in 1..{F} (the number of fields)")
+    if not 0 <= radius <= BASELINE_MAX_RADIUS * F:
+        raise ValueError(f"phono_baseline: radius={radius!r}, expected null or an integer in 0..{BASELINE_MAX_RADIUS * F} (64 frames of {F} fields)")
+    knn = PhonoKNN(codes, gap=gap, k=opts["k"], weights=opts["weights"], tau=float(opts["tau"]), normalize=opts["normalize"],
+                   smoothing=float(opts["smoothing"]), device=device).fit(train_data)
+    scores = {f"test_{m}": float(ScoringWrapper(m, test_data.labels())(knn, test_data, test_data.y)) for m in metrics}
+    dist, idx = knn.kneighbors(test_data)
+    rows = np.stack([(idx >= 0).sum(1), np.zeros(len(idx), dtype=np.int64), dist[:, 0], np.zeros(len(idx), dtype=np.int64)], axis=1)
+    summary = M.knn_report(rows, np.stack([dist, idx], axis=2), test_data.y, train_data.y, max_distance=BASELINE_MAX_RADIUS * F)
+    base = {"options": {**{k: opts[k] for k in ("k", "weights", "tau", "normalize", "smoothing")}, "gap": gap, "fields": F}, "train_rows": len(train_data),
+            "scores": scores, "neighbours": _jsonable(summary), "refit_vs_phono": _jsonable(est.compare(knn, test_data, **(intervals or {})))}
+    if unit is not None:
+        base["baseline_vs_phono"] = _jsonable(unit.compare(knn, test_data, **(intervals or {})))
+    save_json(base, os.path.join(workdir, "test_phono_baseline.json"))
+    audit = split_audit(train_data, test_data, radius=radius, top=opts["top"], judge=est, device=device, field_codes=codes, gap=gap)
+    per = audit["per_class"]
+    names = train_data.vocab_y.itos if getattr(train_data, "vocab_y", None) is not None else None
+    name = lambda c: names[int(c)] if names is not None else str(int(c))
+    out = {k: audit[k] for k in ("rows", "radius", "exact_duplicates", "near_duplicates", "conflicting", "conflicting_exact", "flagged_queries",
+                                 "flagged_references", "rows_duplicated", "rows_clean", "accuracy", "accuracy_duplicated", "accuracy_clean")}
+    cell = lambda v: None if isinstance(v, float) and v != v else v
+    out = {k: cell(v) for k, v in out.items()}
+    out.update(top=opts["top"], gap=gap, fields=F, nearest_hist=[int(c) for c in audit["nearest_hist"]], pairs=[list(p) for p in audit["pairs"]],
+               per_class=[{"class": int(c), "name": name(c), "support": int(per["support"][i]), "duplicated": int(per["duplicated"][i]),
+                           "conflicting": int(per["conflicting"][i])} for i, c in enumerate(per["label"])])
+    save_json(out, os.path.join(workdir, "test_phono_split_audit.json"))
+    right = np.asarray(est.predict(test_data)) == np.asarray(test_data.y)
+    with open(os.path.join(workdir, "test_phono_split_audit_rows.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["row", "label", "name", "nearest", "nearest_label", "nearest_name", "distance", "duplicated", "refit_right"])
+        for i in range(len(test_data)):
+            if idx[i, 0] >= 0:
+                yq, yr = int(test_data.y[i]), int(train_data.y[idx[i, 0]])
+                w.writerow([i, yq, name(yq), int(idx[i, 0]), yr, name(yr), int(dist[i, 0]), int(bool(audit["duplicated"][i])), int(bool(right[i]))])
+    return knn, audit
+
+
 PRIOR_SHIFT_DEFAULTS = {"max_iter": 200, "tol": 1e-6, "source": "train"}
 PRIOR_SHIFT_MAX_ITER = 1024                                                     # SLNLP_PRIOR_MAX_ITER
 PRIOR_SHIFT_SOURCES = ("train", "train_labels")
@@ -874,6 +987,7 @@ def run(args):
     attribution = attribution_options(args.get("attribution"))
     dynamics = train_dynamics_options(args.get("train_dynamics"))
     baseline = baseline_options(args.get("baseline"))
+    phono = phono_baseline_options(args.get("phono_baseline"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -888,6 +1002,7 @@ def run(args):
     if (args.get("dataset_args") or {}).get("balance_dataset") is True:
         dataset = balance_dataset(dataset, seed)
     test_data, train_data = dataset.split(float(args.get("test_size", 0.15)), seed)
+    phono_codes = phono_field_codes(dataset, args.get("dataset_args")) if phono is not None else None      # fails before the grid search
 
     net_params = build_net_params(args, dataset, device)
     factory = lambda: NeuralNetClassifier(**net_params)
@@ -931,8 +1046,12 @@ def run(args):
             save_label_audit(gs, factory, train_data, label_audit, seed, workdir)
         if dynamics is not None:
             save_train_dynamics(est, train_data, dynamics, workdir)
+        unit = None
         if baseline is not None:
-            save_baseline(est, train_data, test_data, baseline, intervals, metrics, device, workdir)
+            unit, _ = save_baseline(est, train_data, test_data, baseline, intervals, metrics, device, workdir)
+        if phono is not None:
+            save_phono_baseline(est, train_data, test_data, phono, args.get("dataset_args"), intervals, metrics, device, workdir, unit=unit,
+                                field_codes=phono_codes)
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

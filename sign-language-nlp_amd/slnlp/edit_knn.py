@@ -14,7 +14,11 @@ same gloss signed several times; identical or near-identical token sequences on 
 twin with ANOTHER gloss is irreducible error or a label problem no model-based audit can see.
 
 Rows longer than 64 frames are REFUSED -- ``fit`` raises, a query is flagged and gets a row of NaN -- never truncated: the kernel
-is Myers' bit-vector recurrence with the query in one 64-bit word; longer rows (the multi-word form) are out of scope here."""
+is Myers' bit-vector recurrence with the query in one 64-bit word; longer rows (the multi-word form) are out of scope here.
+
+``PhonoKNN`` and ``split_audit(field_codes=...)`` answer both questions under the PHONOLOGY-WEIGHTED edit distance instead
+(csrc/field_knn.hip): a token is a composition of F fields, and substituting one frame for another costs the number of fields in
+which they differ.  Only the search and the vote differ; the unit-cost surface keeps its bytes, messages and defaults."""
 import copy
 
 import numpy as np
@@ -84,18 +88,41 @@ def _on_stream(dev, body):
     return res
 
 
-def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None):
-    """``ops.edit_knn_rows`` over the queries in ``query_chunks``; ``each(start, stop, buf)`` runs behind every chunk on the same
-    stream.  One scratch and one buffer serve the chunks of equal size."""
+def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None):
+    """``ops.edit_knn_rows`` -- or, with ``metric`` = (codes on the device, gap), ``ops.field_knn_rows`` -- over the queries in
+    ``query_chunks``; ``each(start, stop, buf)`` runs behind every chunk on the same stream.  One scratch and one buffer serve the
+    chunks of equal size.  The field metric keeps two bytes a pair and is chunked at half the pairs: the scratch stays at 256 MiB."""
     nq, nr = int(Xq.shape[0]), int(Xr.shape[0])
-    chunks = query_chunks(nq, nr, SCRATCH_PAIRS if cap is None else cap)
-    scratch = torch.empty((chunks[0][1] - chunks[0][0]) * nr, dtype=torch.uint8, device=Xq.device)
+    cap = SCRATCH_PAIRS if cap is None else cap
+    width = 1 if metric is None else 2
+    chunks = query_chunks(nq, nr, max(1, cap // width))
+    scratch = torch.empty(width * (chunks[0][1] - chunks[0][0]) * nr, dtype=torch.uint8, device=Xq.device)
     buf = None
     for a, b in chunks:
         if buf is None or buf["shape"][0] != b - a:
             buf = ops.edit_knn_buffers(b - a, k, Xq.device)
-        ops.edit_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius=radius, exclude=None if exclude is None else exclude[a:b], buf=buf, scratch=scratch)
+        ex = None if exclude is None else exclude[a:b]
+        if metric is None:
+            ops.edit_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius=radius, exclude=ex, buf=buf, scratch=scratch)
+        else:
+            ops.field_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, metric[0], k, gap=metric[1], radius=radius, exclude=ex, buf=buf, scratch=scratch)
         each(a, b, buf)
+
+
+def field_table(what, field_codes, gap):
+    """The code table of the phonology-weighted metric checked, on the host: ``field_codes`` a 2-D integer array [Vt >= 1, F in
+    1..16] whose values fit int32, ``gap`` an integer in 1..F (None: F) -> (contiguous int32 array, gap); anything else raises
+    ValueError"""
+    if torch.is_tensor(field_codes):
+        field_codes = field_codes.detach().cpu().numpy()
+    codes = np.asarray(field_codes)
+    if codes.ndim != 2 or codes.dtype.kind not in "iu" or codes.shape[0] < 1 or not 1 <= codes.shape[1] <= _lib.FIELD_MAX_FIELDS:
+        raise ValueError(f"{what}: field_codes must be a 2-D integer array [Vt >= 1, F in 1..{_lib.FIELD_MAX_FIELDS}] (slnlp.ingest.field_codes), "
+                         f"got {codes.dtype} {tuple(codes.shape)}")
+    if codes.size and (codes.min() < -2 ** 31 or codes.max() >= 2 ** 31):
+        raise ValueError(f"{what}: field_codes holds values outside int32")
+    F = int(codes.shape[1])
+    return np.ascontiguousarray(codes, dtype=np.int32), ops._int_in(what, "gap", F if gap is None else gap, 1, F)
 
 
 class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
@@ -183,6 +210,13 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
     def _on_stream(self, body):
         return _on_stream(self._ids.device, body)
 
+    def _metric(self):
+        """What ``_search`` measures with: None, the unit-cost distance"""
+        return None
+
+    def _vote(self, buf, Lq, **options):
+        ops.edit_knn_logp(buf, Lq, self._lengths, self._y, self._prior, **options)
+
     def _forward_logp(self, ds, then):
         """The float32 log-probs [len(ds), V] of ``ds`` (a ``TokenDataset`` or ``DeviceRows``) on the device, handed to
         ``then(logp, y_dev)``: the hook every consumer of ``LogProbJudge`` goes through.  The queries go in ``query_chunks``; per
@@ -197,9 +231,8 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
             out = torch.empty(int(Xq.shape[0]), len(self.classes_), dtype=torch.float32, device=Xq.device)
 
             def vote(a, b, buf):
-                ops.edit_knn_logp(buf, Lq[a:b], self._lengths, self._y, self._prior, weights=weights, tau=tau, normalize=normalize, lam=lam,
-                                  out=out[a:b])
-            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap)
+                self._vote(buf, Lq[a:b], weights=weights, tau=tau, normalize=normalize, lam=lam, out=out[a:b])
+            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._metric())
             return then(out, yq)
         return self._on_stream(body)
 
@@ -217,13 +250,51 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
 
         def body():
             Xq, Lq, _, exclude = self._queries(ds)
-            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, lambda a, b, buf: got.append(ops.edit_knn_download(buf)["nbr"].copy()), self._cap)
+            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, lambda a, b, buf: got.append(ops.edit_knn_download(buf)["nbr"].copy()), self._cap,
+                    self._metric())
         self._on_stream(body)
         nbr = np.concatenate(got, axis=0)
         return nbr[:, :, 0].astype(np.int32), nbr[:, :, 1].astype(np.int64)
 
 
-def split_audit(train, test, radius=2, top=50, judge=None, device=None):
+class PhonoKNN(EditKNN):
+    """``EditKNN`` under the PHONOLOGY-WEIGHTED edit distance (csrc/field_knn.hip): a token of this data is a composition of F
+    fields, and substituting one frame for another costs the number of fields in which they differ -- ``field_codes`` int [Vt, F]
+    (``slnlp.ingest.field_codes``) holds token v's per-field value ids in row v; a token outside the table costs F against every
+    other -- while inserting or deleting a frame costs ``gap`` (1..F; None: F).  Distances are integers in field units, at most
+    64 F; the vote's w = exp(-d / (tau n)) takes n = F max(len(query), len(neighbour), 1) when ``normalize``, else F, so ``tau``
+    is in frames as in ``EditKNN``.  ``fit``, ``leave_one_out``, ``kneighbors`` and every ``LogProbJudge`` method are ``EditKNN``'s:
+    only the search and the vote differ.  With F = 1, ``field_codes[v, 0] = v`` and ``gap = 1`` it is ``EditKNN``."""
+
+    def __init__(self, field_codes, gap=None, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None):
+        field_table("PhonoKNN", field_codes, gap)
+        super().__init__(k=k, weights=weights, tau=tau, normalize=normalize, smoothing=smoothing, device=device)
+        self.field_codes, self.gap = field_codes, gap
+
+    def fit(self, X, y=None):
+        """``EditKNN.fit`` after the table is checked -- again, as ``set_params`` goes past ``__init__`` -- and held to the
+        dataset: with a source vocabulary it has a row for every token id (ValueError otherwise, before anything touches the
+        GPU).  The table is uploaded once."""
+        codes, gap = field_table("PhonoKNN", self.field_codes, self.gap)
+        ds = self._as_dataset(X, y)
+        vocab = getattr(ds, "vocab_X", None)
+        if vocab is not None and codes.shape[0] < len(vocab):
+            raise ValueError(f"PhonoKNN.fit: field_codes has {codes.shape[0]} rows, the dataset's source vocabulary {len(vocab)} tokens: "
+                             "the table must cover the vocabulary")
+        super().fit(ds)
+        with torch.cuda.device(self._ids.device):
+            self._codes = torch.from_numpy(codes).to(self._ids.device)
+        self._gap, self.fields_ = gap, int(codes.shape[1])
+        return self
+
+    def _metric(self):
+        return self._codes, self._gap
+
+    def _vote(self, buf, Lq, **options):
+        ops.field_knn_logp(buf, Lq, self._lengths, self._y, self._prior, self.fields_, **options)
+
+
+def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field_codes=None, gap=None):
     """Do the rows of ``test`` have twins in ``train``?  One ``ops.edit_knn_rows`` pass with k = 1 (the held-out rows as queries, the
     train rows as references; in chunks where the pairs exceed the scratch cap), one download, then
     ``metrics.split_audit_report``: exact and near (<= ``radius`` edits, 0..64) duplicates, the ones whose twin carries ANOTHER
@@ -232,12 +303,26 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None):
     contents -- skips every row's own copy and audits the training set's own redundancy.  ``judge`` (any ``LogProbJudge``): adds
     ``accuracy_duplicated`` / ``accuracy_clean`` and ``rows_duplicated`` / ``rows_clean`` from ``judge.predict(test)``: how much
     of a reported accuracy sits on rows that have a twin in train (NaN where a side is empty).  Rows whose length lies outside
-    0..64 are not audited: ``flagged_queries`` / ``flagged_references`` count them."""
+    0..64 are not audited: ``flagged_queries`` / ``flagged_references`` count them.  ``field_codes`` int [Vt, F] (with ``gap``,
+    1..F; None: F): the audit runs under ``PhonoKNN``'s phonology-weighted distance instead -- distances and ``radius`` (0..64 F)
+    are in field units, ``nearest_hist`` has 64 F + 2 bins, and a row that differs from a train row in one field of one frame is a
+    near duplicate at ``radius=1``."""
     what = "split_audit"
     for name, ds in (("train", train), ("test", test)):
         if not isinstance(ds, TokenDataset) or len(ds) < 1:
             raise TypeError(f"{what}: {name} must be a non-empty slnlp.data.TokenDataset")
-    radius = ops._int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN)
+    codes = None
+    if field_codes is not None:
+        codes, gap = field_table(what, field_codes, gap)
+        for name, ds in (("train", train), ("test", test)):
+            vocab = getattr(ds, "vocab_X", None)
+            if vocab is not None and codes.shape[0] < len(vocab):
+                raise ValueError(f"{what}: field_codes has {codes.shape[0]} rows, the source vocabulary of {name} {len(vocab)} tokens: the table "
+                                 "must cover the vocabulary")
+    elif gap is not None:
+        raise ValueError(f"{what}: gap={gap!r} without field_codes: the unit-cost distance has no gap cost")
+    bound = _lib.EDIT_MAX_LEN * (1 if codes is None else int(codes.shape[1]))
+    radius = ops._int_in(what, "radius", radius, 0, bound)
     top = ops._int_in(what, "top", top, 0, 2 ** 31 - 1)
     if judge is not None and not isinstance(judge, LogProbJudge):
         raise TypeError(f"{what}: judge must be a LogProbJudge (a fit, an ensemble, an EditKNN), got {type(judge).__name__}")
@@ -252,12 +337,13 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None):
         Xr, Lr = up(train.ids), up(train.lengths)
         Xq, Lq = (Xr, Lr) if own else (up(test.ids), up(test.lengths))
         exclude = up(np.arange(len(train), dtype=np.int64)) if own else None
-        _search(Xq, Lq, Xr, Lr, 1, radius, exclude, lambda a, b, buf: got.append({n: v.copy() for n, v in ops.edit_knn_download(buf).items()}))
+        _search(Xq, Lq, Xr, Lr, 1, radius, exclude, lambda a, b, buf: got.append({n: v.copy() for n, v in ops.edit_knn_download(buf).items()}),
+                metric=None if codes is None else (up(codes), gap))
     _on_stream(dev, body)
     rows, nbr = np.concatenate([g["rows"] for g in got]), np.concatenate([g["nbr"] for g in got])
     head = got[0]["head"].copy()
     head[0] = sum(int(g["head"][0]) for g in got)            # the queries of every chunk; the references are the same in each
-    res = metrics.split_audit_report(rows, nbr, np.asarray(test.y), np.asarray(train.y), radius, top, head=head)
+    res = metrics.split_audit_report(rows, nbr, np.asarray(test.y), np.asarray(train.y), radius, top, head=head, max_distance=bound)
     res["self"] = bool(own)
     if judge is not None:
         right = np.asarray(judge.predict(test)) == np.asarray(test.y)

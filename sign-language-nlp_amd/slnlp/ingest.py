@@ -157,3 +157,26 @@ def field_substitutions(vocab_X, fields, composition_strategy):
         for f in range(F):
             table[v, f] = vocab_X.stoi[join(parts[:f] + [null[f]] + parts[f + 1:])]
     return table
+
+
+def field_codes(vocab_X, fields, composition_strategy):
+    """The code table of the phonology-weighted edit distance (``slnlp.PhonoKNN``, ``split_audit(field_codes=...)``): int32
+    [len(vocab_X), F] whose entry (v, f) is the index of token v's part string of field f among that field's DISTINCT part strings,
+    in vocabulary order of first appearance -- two tokens differ in a field exactly when their entries do.  ``<unk>``, ``<pad>`` and
+    every token that does not split into F parts (``_split_token``, as ``field_substitutions``) get -(v + 1) in every field: such a
+    token equals only itself."""
+    if composition_strategy not in STRATEGIES:
+        raise ValueError(f"Unknown composition strategy: '{composition_strategy}'")
+    F = len(list(fields))
+    if F < 1:
+        raise ValueError("field_codes: no fields")
+    table = np.zeros((len(vocab_X), F), dtype=np.int32)
+    seen = [{} for _ in range(F)]
+    for v, word in enumerate(vocab_X.itos):
+        parts = None if word in (UNK_WORD, PAD_WORD) else _split_token(word, F, composition_strategy)
+        if parts is None:
+            table[v, :] = -(v + 1)
+            continue
+        for f in range(F):
+            table[v, f] = seen[f].setdefault(parts[f], len(seen[f]))
+    return table

@@ -581,6 +581,13 @@ def train_dynamics_report(got, labels, rows=None, top=50):
 
 
 EDIT_BINS = 65                                             # the distances 0 .. SLNLP_EDIT_MAX_LEN
+EDIT_MAX_DISTANCE = 64 * 16                                # SLNLP_EDIT_MAX_LEN * SLNLP_FIELD_MAX_FIELDS: the field metric's bound at F = 16
+
+
+def _max_distance(what, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= v <= EDIT_MAX_DISTANCE:
+        raise ValueError(f"{what}: max_distance={v!r}, expected an integer in 1..{EDIT_MAX_DISTANCE}")
+    return int(v) + 1
 
 
 def _edit_tables(what, rows, nbr, y_query, y_ref):
@@ -594,20 +601,23 @@ def _edit_tables(what, rows, nbr, y_query, y_ref):
     return rows.astype(np.int64), nbr.astype(np.int64), y_query, y_ref, listed
 
 
-def _nearest_hist(nearest):
-    hist = np.zeros(EDIT_BINS + 1, dtype=np.int64)
-    hist[:EDIT_BINS] = np.bincount(nearest[(nearest >= 0) & (nearest < EDIT_BINS)], minlength=EDIT_BINS)
-    hist[EDIT_BINS] = np.count_nonzero(nearest < 0)
+def _nearest_hist(nearest, bins=EDIT_BINS):
+    hist = np.zeros(bins + 1, dtype=np.int64)
+    hist[:bins] = np.bincount(nearest[(nearest >= 0) & (nearest < bins)], minlength=bins)
+    hist[bins] = np.count_nonzero(nearest < 0)
     return hist
 
 
-def knn_report(rows, nbr, y_query, y_ref, head=None):
+def knn_report(rows, nbr, y_query, y_ref, head=None, max_distance=64):
     """``ops.edit_knn_download``'s tables (``slnlp_edit_knn_rows``, include/slnlp.h) as a summary of a neighbour search, on the host:
     ``rows`` (queries), ``k``, ``flagged_queries`` (a length outside 0..64: no neighbours), ``no_neighbour`` (unflagged, none found),
     ``nearest_hist`` int64 [66] (the nearest distance 0..64, last bin: none), ``mean_nearest``, ``mean_found``, and per rank
     j < k: ``agreement`` (the share of the queries with a j-th neighbour whose label it carries), ``mean_distance`` and ``listed``
     (how many queries have one); ``accuracy_1nn`` = agreement[0] over ALL unflagged queries (a query without a neighbour is wrong).
-    ``head``: the download's head, for ``flagged_references`` and ``bad_labels`` (None: not reported).  Labels of any dtype."""
+    ``head``: the download's head, for ``flagged_references`` and ``bad_labels`` (None: not reported).  Labels of any dtype.
+    ``max_distance``: the metric's largest distance -- 64, or 64 F for the tables of ``ops.field_knn_rows`` -- ``nearest_hist`` has
+    ``max_distance + 2`` bins."""
+    bins = _max_distance("knn_report", max_distance)
     rows, nbr, yq, yr, listed = _edit_tables("knn_report", rows, nbr, y_query, y_ref)
     flagged = (rows[:, 3] & 1) != 0
     nearest = np.where(flagged, -1, rows[:, 2])
@@ -617,7 +627,7 @@ def knn_report(rows, nbr, y_query, y_ref, head=None):
     usable = int((~flagged).sum())
     with np.errstate(invalid="ignore", divide="ignore"):
         res = {"rows": int(rows.shape[0]), "k": int(nbr.shape[1]), "flagged_queries": int(flagged.sum()),
-               "no_neighbour": int(((rows[:, 0] == 0) & ~flagged).sum()), "nearest_hist": _nearest_hist(nearest),
+               "no_neighbour": int(((rows[:, 0] == 0) & ~flagged).sum()), "nearest_hist": _nearest_hist(nearest, bins),
                "mean_nearest": float(nearest[nearest >= 0].mean()) if (nearest >= 0).any() else float("nan"),
                "mean_found": float(rows[~flagged, 0].mean()) if usable else float("nan"),
                "agreement": same.sum(axis=0) / n_listed, "mean_distance": np.where(listed, nbr[:, :, 0], 0).sum(axis=0) / n_listed,
@@ -627,7 +637,7 @@ def knn_report(rows, nbr, y_query, y_ref, head=None):
     return res
 
 
-def split_audit_report(rows, nbr, y_query, y_ref, radius, top, head=None):
+def split_audit_report(rows, nbr, y_query, y_ref, radius, top, head=None, max_distance=64):
     """Whether held-out rows have twins among the references (``slnlp.split_audit``), from ``ops.edit_knn_download``'s tables of a
     search of the held-out rows (queries) in the train rows (references), on the host.  A query's NEAREST reference is its first
     listed neighbour (smallest distance, then lowest row).  Returned: ``rows``; ``exact_duplicates`` (nearest distance 0) and
@@ -637,9 +647,12 @@ def split_audit_report(rows, nbr, y_query, y_ref, radius, top, head=None):
     distinct query labels -- ``label``, ``support``, ``duplicated``, ``conflicting``; ``pairs``: up to ``top`` tuples (query row,
     reference row, distance, query label, reference label) of the LISTED neighbours within the radius, smallest distance first,
     ties by query then reference row; ``duplicated`` bool [rows]; ``radius``; ``flagged_queries`` (a length outside 0..64: not
-    audited) and ``flagged_references`` (``head``: the download's head; None: 0).  Labels of any dtype."""
+    audited) and ``flagged_references`` (``head``: the download's head; None: 0).  Labels of any dtype.  ``max_distance``: the
+    metric's largest distance -- 64, or 64 F for the tables of ``ops.field_knn_rows``: ``radius`` lies in 0..max_distance and
+    ``nearest_hist`` has ``max_distance + 2`` bins."""
     what = "split_audit_report"
-    for name, v, hi in (("radius", radius, EDIT_BINS - 1), ("top", top, 2 ** 31 - 1)):
+    bins = _max_distance(what, max_distance)
+    for name, v, hi in (("radius", radius, bins - 1), ("top", top, 2 ** 31 - 1)):
         if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
             raise ValueError(f"{what}: {name}={v!r}, expected an integer in 0..{hi}")
     rows, nbr, yq, yr, listed = _edit_tables(what, rows, nbr, y_query, y_ref)
@@ -658,7 +671,7 @@ def split_audit_report(rows, nbr, y_query, y_ref, radius, top, head=None):
     plain = lambda v: v.item() if hasattr(v, "item") else v        # (an object array of names hands out the names themselves)
     pairs = [(int(q[o]), int(r[o]), int(d[o]), plain(yq[q[o]]), plain(yr[r[o]])) for o in order]
     return {"rows": int(rows.shape[0]), "radius": int(radius), "exact_duplicates": int(exact.sum()), "near_duplicates": int(near.sum()),
-            "conflicting": int((near & other).sum()), "conflicting_exact": int((exact & other).sum()), "nearest_hist": _nearest_hist(nearest),
+            "conflicting": int((near & other).sum()), "conflicting_exact": int((exact & other).sum()), "nearest_hist": _nearest_hist(nearest, bins),
             "per_class": {"label": classes, "support": np.bincount(cls, minlength=C), "duplicated": np.bincount(cls[near], minlength=C),
                           "conflicting": np.bincount(cls[near & other], minlength=C)},
             "pairs": pairs, "duplicated": near, "flagged_queries": int(flagged.sum()),

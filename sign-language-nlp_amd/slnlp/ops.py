@@ -1572,6 +1572,104 @@ def edit_knn_download(buf, neighbours=True):
     return buf["packed"].cut("head", "nbr" if neighbours else "rows")
 
 
+def _field_table(what, codes, gap, dev):
+    """The code table of the weighted edit distance: ``codes`` a contiguous int32 [Vt >= 1, F in 1..16] tensor on ``dev``, ``gap``
+    an integer in 1..F (None: F) -> (Vt, F, gap)"""
+    if not (torch.is_tensor(codes) and codes.dtype == torch.int32 and codes.dim() == 2 and codes.shape[0] >= 1
+            and 1 <= codes.shape[1] <= _lib.FIELD_MAX_FIELDS and codes.is_contiguous() and codes.device == dev):
+        raise ValueError(f"{what}: codes must be a contiguous int32 [Vt >= 1, F in 1..{_lib.FIELD_MAX_FIELDS}] tensor on {dev}")
+    Vt, F = int(codes.shape[0]), int(codes.shape[1])
+    return Vt, F, _int_in(what, "gap", F if gap is None else gap, 1, F)
+
+
+def field_distances(Xq, Lq, Xr, Lr, codes, gap=None, out=None):
+    """The phonology-weighted edit distance of every (query, reference) pair (``slnlp_field_distances``, csrc/field_knn.hip):
+    substituting a frame costs the number of fields in which the two tokens' rows of ``codes`` (int32 [Vt, F] on the device)
+    differ -- F for a token outside the table, 0 for the same token -- inserting or deleting one costs ``gap`` (1..F; None: F).
+    Rows as ``edit_distances`` -> uint16 [nq, nr]; 65535 where either row's length lies outside 0..64 (or beyond its row).  ``out``:
+    the matrix to fill.  One launch on the current stream of ``Xq``'s device; no host wait."""
+    _lib.require_gpu()
+    what = "field_distances"
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    _edit_pairs(what, nq, nr)
+    Vt, F, gap = _field_table(what, codes, gap, Xq.device)
+    with torch.cuda.device(Xq.device):
+        if out is None:
+            out = torch.empty(nq, nr, dtype=torch.uint16, device=Xq.device)
+        _tensor(what, "out", out, Xq.device, torch.uint16, (nq, nr))
+        check(load().slnlp_field_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, gap, ptr(out), stream_ptr()), what)
+    return out
+
+
+def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None, buf=None, scratch=None):
+    """``edit_knn_rows`` under the phonology-weighted distance of ``field_distances`` (``slnlp_field_knn_rows``): the same selection
+    into the same ``buf`` (``edit_knn_buffers(nq, k, device)``; None: a new one), distances in field units, ``radius`` in 0..64 F.
+    ``scratch``: a uint8 tensor of at least 2 nq nr bytes, 2-byte aligned (None: a new one; it holds the uint16 [nq, nr] matrix
+    afterwards).  Three queued launches on the current stream of ``Xq``'s device; no host wait.  Returns ``buf``."""
+    what = "field_knn_rows"
+    k = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K)
+    _lib.require_gpu()
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    _edit_pairs(what, nq, nr)
+    dev = Xq.device
+    Vt, F, gap = _field_table(what, codes, gap, dev)
+    radius = _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * F)
+    if exclude is not None:
+        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
+    with torch.cuda.device(dev):
+        if buf is None:
+            buf = edit_knn_buffers(nq, k, dev)
+        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
+        if scratch is None:
+            scratch = torch.empty(2 * nq * nr, dtype=torch.uint8, device=dev)
+        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {2 * nq * nr}] tensor on {dev}")
+        check(load().slnlp_field_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, gap, ptr(exclude), k, radius,
+                                          ptr(scratch), scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
+    return buf
+
+
+def field_knn_logp(buf, Lq, Lr, yr, prior, F, *, weights="distance", tau=1.0, normalize=True, lam=1.0, out=None):
+    """``edit_knn_logp`` for the neighbours of ``field_knn_rows`` (``slnlp_field_knn_logp``): distances are in units of ``F`` fields
+    (1..16), so w = exp(-d / (tau n)) with n = F max(Lq, Lr, 1) when ``normalize``, else F -- ``tau`` is in frames in both metrics,
+    and at F = 1 the vote is ``edit_knn_logp``'s bit for bit.  Two queued launches on the current stream of ``buf``'s device; no host
+    wait.  Returns ``out``."""
+    what = "field_knn_logp"
+    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
+    nq, k = buf["shape"]
+    dev = buf["flat"].device
+    F = _int_in(what, "F", F, 1, _lib.FIELD_MAX_FIELDS)
+    if weights not in _lib.EDIT_WEIGHTS:
+        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
+    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
+    _lib.require_gpu()
+    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
+    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
+    _tensor(what, "Lr", Lr, dev, torch.int64, None)
+    nr = int(Lr.shape[0])
+    _tensor(what, "yr", yr, dev, torch.int64, nr)
+    _tensor(what, "prior", prior, dev, torch.float64, None)
+    V = int(prior.shape[0])
+    if nr < 1 or V < 1:
+        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
+        if out.device != dev or tuple(out.shape) != (nq, V):
+            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
+        ld = _logp_matrix(f"{what} (out)", out)[2]
+        check(load().slnlp_field_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, F, _lib.EDIT_WEIGHTS.index(weights),
+                                          tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]), stream_ptr()), what)
+    return out
+
+
 def scatter_logp(logp, rows, out, state=None):
     """``out[rows[i], :] = `` row i of ``logp`` float32 [n, V] (``slnlp_scatter_logp``): with ``state`` (a calibration state whose beta
     is read on the device) the row ``scale_logp`` would write, bit for bit; with None the float32 values themselves.  ``rows``: a
