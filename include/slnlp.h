@@ -1161,6 +1161,43 @@ int slnlp_field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t*
                          int64_t nr, int64_t k, int64_t V, int64_t F, int weights, double tau, int normalize, double lam,
                          const double* prior, float* logp, int64_t ld, int64_t* head, void* stream);
 
+/* ------------------------------------------- per-field integer weights (csrc/field_knn.hip, csrc/score.hip) --
+ * The same metric with a WEIGHT per field (slnlp.PhonoKNN(field_weights=...), slnlp.fit_field_weights).  All integers.
+ *
+ * fweights int32 [F] ON THE HOST (the weights reach the kernel by value, among its arguments), each in 0..SLNLP_FIELD_MAX_WEIGHT;
+ *         their sum W lies in 1..SLNLP_FIELD_MAX_WEIGHT.  A field of weight 0 is ignored.
+ * sub(a, b) 0 if a == b as int64 values; otherwise W (not F) if either token lies outside 0..Vt-1; otherwise the sum of
+ *         fweights[f] over the fields with codes[a, f] != codes[b, f] -- which may be 0 for distinct tokens.
+ * gap     in 1..W.
+ * d(q, r) as above, at most 64 W <= 1024: the uint16 matrix, its 65535, the bins and the selection are those of the unweighted
+ *         search with the bound 64 W.  With every weight 1 it IS the unweighted metric (W = F), value for value.
+ * The vote is slnlp_field_knn_logp called with W where it takes F: its unit becomes W, so tau stays in frames.
+ *
+ * slnlp_field_distances_w / slnlp_field_knn_rows_w: slnlp_field_distances / slnlp_field_knn_rows under this metric; radius in
+ * 0..64 W; the same scratch, head, rows and nbr.  Errors (SLNLP_ERR_INVALID_ARG, before anything is launched): those of the
+ * unweighted entries, and a null fweights, a weight outside 0..16, W outside 1..16, gap outside 1..W, radius outside 0..64 W.
+ *
+ * slnlp_loo_objective: what a search over candidate weights ranks by.  logp float32 [N, ld] (V columns), y int64 [N]; slot
+ * `slot` of the device table of C slots of SLNLP_LOO_SLOT_BYTES bytes gets
+ *     int64 rows whose arg-max (the lowest index on a tie) is the label | fp64 sum of -logp[i, y_i] | int64 rows that hold a NaN
+ *     | int64 rows whose label lies outside 0..V-1
+ * A NaN row and a row with such a label count as wrong and add nothing to the sum.  The sum is taken in a fixed order that
+ * depends on N alone: cell t of 256 adds the rows t, t + 256, ... in increasing order, then a binary tree (cells t and t + w for
+ * w = 128, 64, .. 1) adds the cells.  One launch of one block, no atomics.  Errors: a null or misaligned pointer, N or V outside
+ * 1..INT32_MAX, ld < V, C outside 1..SLNLP_LOO_MAX_SLOTS, slot outside 0..C-1, the table overlapping an input. */
+#define SLNLP_FIELD_MAX_WEIGHT 16
+#define SLNLP_LOO_SLOT_BYTES 32
+#define SLNLP_LOO_MAX_SLOTS 65536
+int slnlp_field_distances_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                            int64_t nr, const int32_t* codes /* [Vt, F] */, int64_t Vt, int64_t F, const int32_t* fweights /* host [F] */,
+                            int64_t gap, uint16_t* dist /* [nq, nr] */, void* stream);
+int slnlp_field_knn_rows_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                           int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights /* host [F] */, int64_t gap,
+                           const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head /* [8] */,
+                           int32_t* rows /* [nq, 4] */, int32_t* nbr /* [nq, k, 2] */, void* stream);
+int slnlp_loo_objective(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, void* table /* [C] slots */, int64_t C,
+                        int64_t slot, void* stream);
+
 /* debug / test helper: materialise the keep mask (1.0 / 0.0) of a dropout site */
 int slnlp_dropout_mask(float* out, int R, int C, float p, int site,
                        const unsigned long long* rng, void* stream);

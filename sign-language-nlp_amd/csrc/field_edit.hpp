@@ -50,6 +50,32 @@ SLNLP_HD int field_differ(const A& a, const B& b, int groups) {
 // sub(a, b): 0 for the same int64 token; F when either lies outside the table; else the fields in which their codes differ (may be 0)
 SLNLP_HD int field_sub(bool same, bool outside, int differ, int F) { return same ? 0 : (outside ? F : differ); }
 
+// ------------------------------------------------------------------------------------------------ per-field weights ----
+// The weighted metric (slnlp_field_distances_w): field f counts w[f] (0..16, their sum W in 1..16) instead of 1, a token outside
+// the table costs W, gap lies in 1..W.  Sixteen ints, zeros behind F as the code vectors: the kernel takes the struct BY VALUE among
+// its arguments, so the weights are uniform values in scalar registers and no table is read for them.
+struct FieldWeights {
+    int w[FIELD_MAX];
+};
+
+// the sum of w[e] over the entries in which two padded code vectors differ, over the first G groups of four
+template <int G, class A, class B>
+SLNLP_HD int field_weigh_groups(const A& a, const B& b, const FieldWeights& fw) {
+    int n = 0;
+#pragma unroll
+    for (int e = 0; e < 4 * G; ++e) n += a[e] != b[e] ? fw.w[e] : 0;
+    return n;
+}
+template <class A, class B>
+SLNLP_HD int field_weigh(const A& a, const B& b, const FieldWeights& fw, int groups) {
+    switch (groups) {
+        case 1: return field_weigh_groups<1>(a, b, fw);
+        case 2: return field_weigh_groups<2>(a, b, fw);
+        case 3: return field_weigh_groups<3>(a, b, fw);
+        default: return field_weigh_groups<4>(a, b, fw);
+    }
+}
+
 SLNLP_HD int field_cell(int up, int left, int diag, int sub, int gap) {
     const int a = (up < left ? up : left) + gap, b = diag + sub;
     return a < b ? a : b;

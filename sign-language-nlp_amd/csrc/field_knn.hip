@@ -16,6 +16,10 @@
 //                 col[word][thread] with two uint16 positions per dword: 32 x 256 dwords = 32 KiB, 37.6 KiB a block with the query.
 //                 A wave's 64 lanes read and write 64 consecutive dwords (every bank once: no conflict), the query's entries are
 //                 read at one address by all lanes (a broadcast).  uint16 [nq, nr]; 65535 where either row is unusable.
+//   field_dist_w  the same body under PER-FIELD WEIGHTS (slnlp_field_distances_w / _knn_rows_w): field f counts w[f] (0..16, their
+//                 sum W in 1..16), a token outside the table costs W, gap lies in 1..W, d <= 64 W.  The weights travel BY VALUE among
+//                 the kernel's arguments (FieldWeights, 16 ints): uniform values in scalar registers, no table read for them.  The
+//                 unweighted kernels are not routed through it: the cost policy is a template argument of the one body.
 //   field_select  edit_shared.hpp's selection body over the uint16 matrix with 64 F + 1 <= 1025 bins.
 //   the head and the votes are edit_knn.hip's kernels with the bound 64 F and the unit F.
 #include <limits.h>
@@ -40,11 +44,27 @@ struct FieldLdsColumn {
 };
 
 // ------------------------------------------------------------------------------------------------------- distances ----
-template <int G>
+// what a substitution between two tokens of the table costs, and what a token outside it costs: the unit metric counts the
+// differing fields (F outside), the weighted one adds their weights (W outside).  The body below is written once over the two.
+struct FieldUnitCost {
+    int F;
+    template <int G, class A, class B>
+    __device__ __forceinline__ int differ(const A& a, const B& b) const { return field_differ_groups<G>(a, b); }
+    __device__ __forceinline__ int outside() const { return F; }
+};
+struct FieldWeightedCost {
+    FieldWeights fw;
+    int W;
+    template <int G, class A, class B>
+    __device__ __forceinline__ int differ(const A& a, const B& b) const { return field_weigh_groups<G>(a, b, fw); }
+    __device__ __forceinline__ int outside() const { return W; }
+};
+
+template <int G, class Cost>
 __device__ __forceinline__ void field_dist_impl(const int64_t* __restrict__ Xq, long ldq, const int64_t* __restrict__ Lq, int nq,
                                                 const int64_t* __restrict__ Xr, long ldr, const int64_t* __restrict__ Lr, int nr, int max_q,
                                                 int max_r, int tile, const int* __restrict__ codes, int F, int Vt, int gap,
-                                                unsigned short* __restrict__ dist) {                 // (F + 3) / 4 == G
+                                                unsigned short* __restrict__ dist, const Cost cost) { // (F + 3) / 4 == G
     __shared__ int64_t qtok[SLNLP_EDIT_MAX_LEN];
     __shared__ int qout[SLNLP_EDIT_MAX_LEN];
     __shared__ __attribute__((aligned(16))) int qcode[SLNLP_EDIT_MAX_LEN][FIELD_MAX];
@@ -95,7 +115,7 @@ __device__ __forceinline__ void field_dist_impl(const int64_t* __restrict__ Xq, 
 #pragma unroll
                     for (int f = 0; f < 4 * G; ++f) rc[f] = (inside && f < F) ? codes[c * F + f] : 0;
                     field_column_step(column, words, t + 1, gap, [&](int p) {
-                        return field_sub(qtok[p] == c, (qout[p] != 0) | !inside, field_differ_groups<G>(qcode[p], rc), F);
+                        return field_sub(qtok[p] == c, (qout[p] != 0) | !inside, cost.template differ<G>(qcode[p], rc), cost.outside());
                     });
                 }
                 d = field_column_score(column, m, n, gap);
@@ -109,9 +129,16 @@ __device__ __forceinline__ void field_dist_impl(const int64_t* __restrict__ Xq, 
                                                          const int64_t* __restrict__ Xr, long ldr, const int64_t* __restrict__ Lr, int nr,  \
                                                          int max_q, int max_r, int tile, const int* __restrict__ codes, int F, int Vt,      \
                                                          int gap, unsigned short* __restrict__ dist) {                                      \
-        field_dist_impl<G>(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, max_q, max_r, tile, codes, F, Vt, gap, dist);                                  \
+        field_dist_impl<G>(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, max_q, max_r, tile, codes, F, Vt, gap, dist, FieldUnitCost{F});                \
     }                                                                                                                                      \
-    SLNLP_ZKERNEL(field_dist_kernel_g##G, 256, field_dist_body_g##G)
+    SLNLP_ZKERNEL(field_dist_kernel_g##G, 256, field_dist_body_g##G)                                                                       \
+    __device__ __forceinline__ void field_dist_w_body_g##G(const int64_t* __restrict__ Xq, long ldq, const int64_t* __restrict__ Lq, int nq, \
+                                                           const int64_t* __restrict__ Xr, long ldr, const int64_t* __restrict__ Lr, int nr, \
+                                                           int max_q, int max_r, int tile, const int* __restrict__ codes, int F, int Vt,    \
+                                                           int gap, unsigned short* __restrict__ dist, FieldWeights fw, int W) {            \
+        field_dist_impl<G>(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, max_q, max_r, tile, codes, F, Vt, gap, dist, FieldWeightedCost{fw, W});        \
+    }                                                                                                                                      \
+    SLNLP_ZKERNEL(field_dist_w_kernel_g##G, 256, field_dist_w_body_g##G)
 SLNLP_FIELD_DIST(1)
 SLNLP_FIELD_DIST(2)
 SLNLP_FIELD_DIST(3)
@@ -137,6 +164,28 @@ static int field_check_table(const char* what, const int32_t* codes, int64_t Vt,
     *out = Span{codes, (size_t)Vt * (size_t)F * 4, "codes"};
     return 0;
 }
+// the weighted metric's table, weights and gap: fweights a HOST array of F ints in 0..16 whose sum W lies in 1..16, gap in 1..W
+static int field_check_weighted(const char* what, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, Span* out,
+                                FieldWeights* fw, int* W_out) {
+    SLNLP_CHECK_ARG(codes, "%s: null pointer (codes)", what);
+    SLNLP_CHECK_ARG(fweights, "%s: null pointer (fweights: a host array of F weights)", what);
+    SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
+    SLNLP_CHECK_ARG(Vt >= 1 && Vt <= INT_MAX, "%s: Vt=%ld outside 1..%d", what, (long)Vt, INT_MAX);
+    int W = 0;
+    *fw = FieldWeights{};
+    for (int f = 0; f < F; ++f) {
+        SLNLP_CHECK_ARG(fweights[f] >= 0 && fweights[f] <= SLNLP_FIELD_MAX_WEIGHT, "%s: fweights[%d]=%d outside 0..%d", what, f, (int)fweights[f],
+                        SLNLP_FIELD_MAX_WEIGHT);
+        fw->w[f] = fweights[f];
+        W += fweights[f];
+    }
+    SLNLP_CHECK_ARG(W >= 1 && W <= SLNLP_FIELD_MAX_WEIGHT, "%s: the weights sum to W=%d outside 1..%d", what, W, SLNLP_FIELD_MAX_WEIGHT);
+    SLNLP_CHECK_ARG(gap >= 1 && gap <= W, "%s: gap=%ld outside 1..W=%d", what, (long)gap, W);
+    SLNLP_CHECK_ARG(((uintptr_t)codes & 3) == 0, "%s: misaligned pointer (codes: 4 bytes)", what);
+    *out = Span{codes, (size_t)Vt * (size_t)F * 4, "codes"};
+    *W_out = W;
+    return 0;
+}
 static int field_check_pairs(const char* what, int64_t nq, int64_t nr) {
     SLNLP_CHECK_ARG(nq <= SLNLP_EDIT_MAX_PAIRS / nr, "%s: %ld x %ld pairs, at most %ld (two bytes each) are formed per call", what, (long)nq, (long)nr,
                     (long)SLNLP_EDIT_MAX_PAIRS);
@@ -144,46 +193,68 @@ static int field_check_pairs(const char* what, int64_t nq, int64_t nr) {
 }
 static int launch_field_dist(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Xr, int64_t ldr,
                              const int64_t* Lr, int64_t nr, int max_r, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, unsigned short* dist,
-                             hipStream_t st) {
+                             hipStream_t st, const FieldWeights* fw = nullptr, int W = 0) {
     int tile;
     const dim3 grid = edit_dist_grid(nq, nr, &tile);
     const int groups = (int)(F + 3) / 4;                     // 1..4: the kernel built for that many groups of four fields
+    if (fw) {                                                // the weighted sibling: the weights by value behind the same arguments
+        auto kern = groups == 1 ? field_dist_w_kernel_g1 : groups == 2 ? field_dist_w_kernel_g2 : groups == 3 ? field_dist_w_kernel_g3 : field_dist_w_kernel_g4;
+        return zlaunch(kern, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, (const int*)codes,
+                       (int)F, (int)Vt, (int)gap, dist, *fw, W);
+    }
     auto kern = groups == 1 ? field_dist_kernel_g1 : groups == 2 ? field_dist_kernel_g2 : groups == 3 ? field_dist_kernel_g3 : field_dist_kernel_g4;
     return zlaunch(kern, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, (const int*)codes, (int)F,
                    (int)Vt, (int)gap, dist);
 }
 
-int field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                    const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, hipStream_t st) {
-    const char* what = "field_distances";
+// weighted false: the unit metric and its kernels (fweights unused); true: the weighted sibling (fweights a host array)
+static int field_distances_any(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr,
+                               const int64_t* Lr, int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, bool weighted,
+                               int64_t gap, uint16_t* dist, hipStream_t st) {
     EditSide Q, R;
     Span table;
+    FieldWeights fw;
+    int W = 0;
     SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
     SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
-    SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
+    if (weighted) SLNLP_TRY(field_check_weighted(what, codes, Vt, F, fweights, gap, &table, &fw, &W));
+    else SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
     SLNLP_CHECK_ARG(dist, "%s: null pointer (dist)", what);
     SLNLP_CHECK_ARG(((uintptr_t)dist & 1) == 0, "%s: misaligned pointer (dist: 2 bytes)", what);
     SLNLP_TRY(field_check_pairs(what, nq, nr));
     const Span in[5] = {Q.x, Q.l, R.x, R.l, table};
     const Span out[1] = {{dist, (size_t)nq * (size_t)nr * 2, "dist"}};
     SLNLP_TRY(check_no_overlap(what, out, in));
-    return launch_field_dist(what, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, (unsigned short*)dist, st);
+    return launch_field_dist(what, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, (unsigned short*)dist, st,
+                             weighted ? &fw : nullptr, W);
+}
+int field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
+                    const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, hipStream_t st) {
+    return field_distances_any("field_distances", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, nullptr, false, gap, dist, st);
+}
+int field_distances_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
+                      const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, uint16_t* dist, hipStream_t st) {
+    return field_distances_any("field_distances_w", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, true, gap, dist, st);
 }
 
-int field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                   const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k, int64_t radius, void* scratch,
-                   int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
-    const char* what = "field_knn_rows";
+// the search under either metric: `unit` is F, or W with weights, and names itself in the radius message
+static int field_knn_rows_any(const char* what, const char* what_dist, const char* what_select, const char* what_head, const int64_t* Xq, int64_t ldq,
+                              const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr, const int32_t* codes,
+                              int64_t Vt, int64_t F, const int32_t* fweights, bool weighted, int64_t gap, const int64_t* exclude, int64_t k,
+                              int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
     EditSide Q, R;
     Span table;
+    FieldWeights fw;
+    int W = 0;
     SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
     SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
-    SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
+    if (weighted) SLNLP_TRY(field_check_weighted(what, codes, Vt, F, fweights, gap, &table, &fw, &W));
+    else SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
     SLNLP_CHECK_ARG(scratch && head && rows && nbr, "%s: null pointer (scratch, head, rows or nbr)", what);
     SLNLP_TRY(field_check_pairs(what, nq, nr));
     SLNLP_CHECK_ARG(k >= 1 && k <= SLNLP_EDIT_MAX_K, "%s: k=%ld outside 1..%d", what, (long)k, SLNLP_EDIT_MAX_K);
-    const int64_t bound = SLNLP_EDIT_MAX_LEN * F;
-    SLNLP_CHECK_ARG(radius >= 0 && radius <= bound, "%s: radius=%ld outside 0..64 F=%ld", what, (long)radius, (long)bound);
+    const int64_t bound = SLNLP_EDIT_MAX_LEN * (weighted ? (int64_t)W : F);
+    SLNLP_CHECK_ARG(radius >= 0 && radius <= bound, "%s: radius=%ld outside 0..64 %s=%ld", what, (long)radius, weighted ? "W" : "F", (long)bound);
     const size_t pairs = (size_t)nq * (size_t)nr;
     SLNLP_TRY(check_scratch(what, scratch, scratch_bytes, pairs * 2, nq, 0, 2));
     SLNLP_CHECK_ARG((((uintptr_t)head | (uintptr_t)exclude) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)nbr) & 3) == 0,
@@ -193,10 +264,22 @@ int field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq
                          {nbr, (size_t)nq * (size_t)k * 8, "nbr"}};
     SLNLP_TRY(check_no_overlap(what, out, in));
     unsigned short* dist = (unsigned short*)scratch;
-    SLNLP_TRY(launch_field_dist("field_knn_distances", Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, dist, st));
-    SLNLP_TRY(zlaunch(field_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, "field_knn_select", (const unsigned short*)dist, Lq, exclude, (int)nq,
+    SLNLP_TRY(launch_field_dist(what_dist, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, dist, st, weighted ? &fw : nullptr, W));
+    SLNLP_TRY(zlaunch(field_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, what_select, (const unsigned short*)dist, Lq, exclude, (int)nq,
                       (int)nr, Q.max_len, (int)k, (int)radius, (int)bound + 1, (int*)rows, (int*)nbr));
-    return edit_launch_head("field_knn_head", Lq, nq, Q.max_len, Lr, nr, R.max_len, head, st);
+    return edit_launch_head(what_head, Lq, nq, Q.max_len, Lr, nr, R.max_len, head, st);
+}
+int field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
+                   const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k, int64_t radius, void* scratch,
+                   int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
+    return field_knn_rows_any("field_knn_rows", "field_knn_distances", "field_knn_select", "field_knn_head", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F,
+                              nullptr, false, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, st);
+}
+int field_knn_rows_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
+                     const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, const int64_t* exclude, int64_t k, int64_t radius,
+                     void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
+    return field_knn_rows_any("field_knn_rows_w", "field_knn_distances_w", "field_knn_select_w", "field_knn_head_w", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes,
+                              Vt, F, fweights, true, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, st);
 }
 
 int field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
@@ -213,6 +296,18 @@ int field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, c
 extern "C" int slnlp_field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
                                      int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, void* stream) {
     return slnlp::field_distances(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, gap, dist, (hipStream_t)stream);
+}
+extern "C" int slnlp_field_distances_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                                       int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, uint16_t* dist,
+                                       void* stream) {
+    return slnlp::field_distances_w(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, gap, dist, (hipStream_t)stream);
+}
+extern "C" int slnlp_field_knn_rows_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                                      int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap,
+                                      const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head,
+                                      int32_t* rows, int32_t* nbr, void* stream) {
+    return slnlp::field_knn_rows_w(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, gap, exclude, k, radius, scratch, scratch_bytes, head, rows,
+                                   nbr, (hipStream_t)stream);
 }
 extern "C" int64_t slnlp_field_knn_scratch_bytes(int64_t nq, int64_t nr) {
     if (nq < 1 || nq > SLNLP_EDIT_MAX_ROWS || nr < 1 || nr > SLNLP_EDIT_MAX_ROWS || nq > SLNLP_EDIT_MAX_PAIRS / nr) {

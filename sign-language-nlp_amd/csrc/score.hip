@@ -24,6 +24,7 @@
 
 #include <algorithm>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
 #include "launch.hpp"
 #include "spans.hpp"
@@ -94,8 +95,77 @@ int score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V
     return zlaunch(score_rows_kernel, dim3(wave_rows_grid(N)), 256, 0, st, "score_rows", logp, (long)ld, y, (int)N, V, pred, picked, rank, counts);
 }
 
+// ---------------------------------------------------------------------------------------------- leave-one-out objective ----
+// What a search over candidate metrics ranks by (slnlp.fit_field_weights): the rows whose arg-max is the label and the fp64 sum
+// of -logp[i, y_i], into slot `slot` of a device table of 32-byte slots -- int64 right | fp64 sum | int64 NaN rows | int64 labels
+// outside 0..V-1 -- so the candidates of a step fill one table and the host downloads it once.  ONE block: thread t takes the rows
+// t, t + 256, ... in increasing order (a row's columns in order, the first maximum wins: the lowest index on a tie, as
+// score_rows), then block_tree adds the 256 threads -- an order that depends on N alone, so the sum's bits are a function of the
+// log-probs.  A row that holds a NaN is wrong, adds nothing and is counted; so is a row whose label lies outside the classes.
+__device__ __forceinline__ void loo_objective_body(const float* __restrict__ logp, long ld, const int64_t* __restrict__ y, int N, int V,
+                                                   int64_t* __restrict__ slot) {
+    __shared__ double sum[256];
+    __shared__ int cnt[3][256];
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    int right = 0, nans = 0, bad = 0;
+    for (long r = tid; r < N; r += 256) {
+        const float* row = logp + r * ld;
+        float bv = row[0];
+        int bi = 0;
+        bool nan = bv != bv;
+        for (int j = 1; j < V; ++j) {
+            const float x = row[j];
+            nan |= x != x;
+            if (x > bv) { bv = x; bi = j; }
+        }
+        const int64_t label = y[r];
+        if (nan) {
+            ++nans;
+        } else if (label < 0 || label >= V) {
+            ++bad;
+        } else {
+            right += bi == label ? 1 : 0;
+            acc += -(double)row[label];
+        }
+    }
+    sum[tid] = acc;
+    cnt[0][tid] = right;
+    cnt[1][tid] = nans;
+    cnt[2][tid] = bad;
+    block_tree<1>(&sum, tid, TreeSum{});
+    block_tree<3>(cnt, tid, TreeSum{});
+    if (tid == 0) {
+        slot[0] = cnt[0][0];
+        slot[1] = __builtin_bit_cast(int64_t, sum[0]);
+        slot[2] = cnt[1][0];
+        slot[3] = cnt[2][0];
+    }
+}
+SLNLP_ZKERNEL(loo_objective_kernel, 256, loo_objective_body)
+
+int loo_objective(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, void* table, int64_t C, int64_t slot, hipStream_t st) {
+    const char* what = "loo_objective";
+    SLNLP_CHECK_ARG(logp && y && table, "%s: null pointer", what);
+    Span z;
+    SLNLP_TRY(check_logp_matrix(what, logp, N, INT_MAX, V, INT_MAX, ld, &z));
+    SLNLP_CHECK_ARG(C >= 1 && C <= SLNLP_LOO_MAX_SLOTS, "%s: C=%ld slots outside 1..%d", what, (long)C, SLNLP_LOO_MAX_SLOTS);
+    SLNLP_CHECK_ARG(slot >= 0 && slot < C, "%s: slot=%ld outside 0..C-1=%ld", what, (long)slot, (long)(C - 1));
+    SLNLP_CHECK_ARG(((uintptr_t)logp & 3) == 0 && (((uintptr_t)y | (uintptr_t)table) & 7) == 0, "%s: misaligned pointer (logp: 4 bytes; y, table: 8 bytes)",
+                    what);
+    const Span in[2] = {z, {y, (size_t)N * 8, "y"}};
+    const Span out[1] = {{table, (size_t)C * SLNLP_LOO_SLOT_BYTES, "table"}};
+    SLNLP_TRY(check_no_overlap(what, out, in));
+    return zlaunch(loo_objective_kernel, dim3(1), 256, 0, st, what, logp, (long)ld, y, (int)N, (int)V,
+                   (int64_t*)((char*)table + slot * SLNLP_LOO_SLOT_BYTES));
+}
+
 }  // namespace slnlp
 
+extern "C" int slnlp_loo_objective(const float* logp, int64_t ld, const int64_t* y, int64_t N, int64_t V, void* table, int64_t C, int64_t slot,
+                                   void* stream) {
+    return slnlp::loo_objective(logp, ld, y, N, V, table, C, slot, (hipStream_t)stream);
+}
 extern "C" int slnlp_score_rows(const float* logp, int64_t ld, const int64_t* y, int64_t N, int V, int32_t* pred, float* picked,
                                 int32_t* rank, int32_t* counts, void* stream) {
     return slnlp::score_rows(logp, ld, y, N, V, pred, picked, rank, counts, (hipStream_t)stream);

@@ -170,6 +170,9 @@ SIGNATURES = {
     "slnlp_field_knn_scratch_bytes": (i64, [i64, i64]),
     "slnlp_field_knn_rows": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "slnlp_field_knn_logp": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, C.c_double, i32, C.c_double, vp, vp, i64, vp, vp]),
+    "slnlp_field_distances_w": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp]),
+    "slnlp_field_knn_rows_w": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "slnlp_loo_objective": (i32, [vp, i64, vp, i64, i64, vp, i64, i64, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -339,6 +342,9 @@ EDIT_MAX_PAIRS = 2 ** 31                        # SLNLP_EDIT_MAX_PAIRS
 EDIT_HEAD_BYTES = 64                            # SLNLP_EDIT_HEAD_BYTES
 EDIT_WEIGHTS = ("uniform", "distance")          # SLNLP_EDIT_UNIFORM / _DISTANCE
 FIELD_MAX_FIELDS = 16                           # SLNLP_FIELD_MAX_FIELDS
+FIELD_MAX_WEIGHT = 16                           # SLNLP_FIELD_MAX_WEIGHT
+LOO_SLOT_BYTES = 32                             # SLNLP_LOO_SLOT_BYTES
+LOO_MAX_SLOTS = 65536                           # SLNLP_LOO_MAX_SLOTS
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

@@ -145,6 +145,16 @@ the number of fields F), and ``radius`` (null: F, one frame) is in field units. 
     test_phono_split_audit.json      as test_split_audit.json in field units (the histogram has 64 F + 2 bins), with gap and fields
     test_phono_split_audit_rows.csv  as test_split_audit_rows.csv
 
+Its sub-key ``fit_weights: {levels: [0, 1, 2, 4], sweeps: 2, scoring: neg_log_loss}`` (null or absent: nothing changes) fits
+per-field integer weights first (``slnlp.fit_field_weights``: a coordinate search on the leave-one-out objective of the train split,
+on the device) and builds the phono baseline and the phono split audit with them -- distances, ``gap`` and ``radius`` are then
+in units of W, the sum of the weights.  Rank 0 also writes
+
+    train_phono_weights.json         the search's report with the field NAMES of ``dataset_args.fields`` next to the weights.  Its
+                                     objective is leave-one-out on the TRAIN split, which this data's repeated glosses flatter;
+    test_phono_baseline.json         gains ``phono_vs_weighted``: ``compare`` of the unit-weight ``PhonoKNN`` against the weighted
+                                     one on paired resamples of the TEST split -- the number to judge the weights by
+
 Without the twelve keys the workdir holds exactly the files listed above.
 """
 import argparse
@@ -685,6 +695,34 @@ PHONO_BASELINE_DEFAULTS = {"k": 5, "weights": "distance", "tau": 1.0, "normalize
 PHONO_MAX_FIELDS = 16                                                           # SLNLP_FIELD_MAX_FIELDS
 
 
+PHONO_FIT_WEIGHTS_DEFAULTS = {"levels": [0, 1, 2, 4], "sweeps": 2, "scoring": "neg_log_loss"}
+PHONO_MAX_WEIGHT = 16                                                           # SLNLP_FIELD_MAX_WEIGHT
+
+
+def phono_fit_weights_options(setting):
+    """The sub-key ``phono_baseline.fit_weights`` with its defaults filled in -- {levels [0, 1, 2, 4], sweeps 2, scoring
+    neg_log_loss} -- or None when it is null.  Anything but a dict over these three keys raises ValueError: ``levels`` a non-empty
+    list of distinct integers in 0..16, ``sweeps`` an integer in 1..64, ``scoring`` neg_log_loss or accuracy."""
+    if setting is None:
+        return None
+    if not isinstance(setting, dict):
+        raise ValueError(f"phono_baseline: fit_weights={setting!r}, expected null or a dict with keys among {tuple(PHONO_FIT_WEIGHTS_DEFAULTS)}")
+    unknown = sorted(set(setting) - set(PHONO_FIT_WEIGHTS_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"phono_baseline: fit_weights: unknown keys {unknown} (known: {tuple(PHONO_FIT_WEIGHTS_DEFAULTS)})")
+    opts = dict(PHONO_FIT_WEIGHTS_DEFAULTS, **setting)
+    whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    lv = opts["levels"]
+    if not isinstance(lv, (list, tuple)) or not lv or not all(whole(v, 0, PHONO_MAX_WEIGHT) for v in lv) or len(set(lv)) != len(lv):
+        raise ValueError(f"phono_baseline: fit_weights: levels={lv!r}, expected a list of distinct integers in 0..{PHONO_MAX_WEIGHT}")
+    if not whole(opts["sweeps"], 1, 64):
+        raise ValueError(f"phono_baseline: fit_weights: sweeps={opts['sweeps']!r}, expected an integer in 1..64")
+    if opts["scoring"] not in ("neg_log_loss", "accuracy"):
+        raise ValueError(f"phono_baseline: fit_weights: scoring={opts['scoring']!r}, expected neg_log_loss or accuracy")
+    opts["levels"] = list(lv)
+    return opts
+
+
 def phono_baseline_options(setting):
     """The ``phono_baseline`` key with its defaults filled in -- {k 5, weights distance, tau 1.0, normalize true, smoothing 1.0, gap
     null (-> F), radius null (-> F), top 50} -- or None when the key is absent.  Anything but a dict over these eight keys ({}: all
@@ -694,6 +732,8 @@ def phono_baseline_options(setting):
         return None
     if not isinstance(setting, dict):
         raise ValueError(f"phono_baseline={setting!r}: expected a dict with keys among {tuple(PHONO_BASELINE_DEFAULTS)}")
+    fit_weights = phono_fit_weights_options(setting.get("fit_weights"))          # the one sub-key: present in the result only when set
+    setting = {k: v for k, v in setting.items() if k != "fit_weights"}
     unknown = sorted(set(setting) - set(PHONO_BASELINE_DEFAULTS), key=str)
     if unknown:
         raise ValueError(f"phono_baseline: unknown keys {unknown} (known: {tuple(PHONO_BASELINE_DEFAULTS)})")
@@ -716,6 +756,8 @@ def phono_baseline_options(setting):
                          f"0..{BASELINE_MAX_RADIUS * PHONO_MAX_FIELDS}")
     if not whole(opts["top"], 0, 2 ** 31 - 1):
         raise ValueError(f"phono_baseline: top={opts['top']!r}, expected an integer >= 0")
+    if fit_weights is not None:
+        opts["fit_weights"] = fit_weights
     return opts
 
 
@@ -736,20 +778,40 @@ def save_phono_baseline(est, train_data, test_data, opts, dataset_args, interval
     ``slnlp.split_audit(field_codes=...)`` of the split with the refit ``est`` as the judge as ``test_phono_split_audit.json`` /
     ``test_phono_split_audit_rows.csv`` in ``workdir``.  ``field_codes``: the table (None: ``phono_field_codes``).  ``unit``: the
     fitted ``EditKNN`` of the ``baseline`` key when that is set too -- ``baseline_vs_phono`` is its ``compare`` against the field
-    metric on paired resamples.  Returns (the ``PhonoKNN``, the audit)."""
+    metric on paired resamples.  With ``opts["fit_weights"]`` the weights are fitted on ``train_data`` first
+    (``train_phono_weights.json``), the baseline and the audit run under them (units of W) and ``phono_vs_weighted`` compares the
+    unit-weight ``PhonoKNN`` against the weighted one.  Returns (the ``PhonoKNN``, the audit)."""
     from . import metrics as M
     from .edit_knn import PhonoKNN, split_audit
     from .net import ScoringWrapper
     codes = phono_field_codes(train_data, dataset_args) if field_codes is None else np.asarray(field_codes)
     F = int(codes.shape[1])
+    fit, fweights, unit_knn = opts.get("fit_weights"), None, None
     gap = F if opts["gap"] is None else opts["gap"]
-    radius = F if opts["radius"] is None else opts["radius"]
     if not 1 <= gap <= F:
         raise ValueError(f"phono_baseline: gap={gap!r}, expected null or an integer in 1..{F} (the number of fields)")
+    vote = dict(k=opts["k"], weights=opts["weights"], tau=float(opts["tau"]), normalize=opts["normalize"], smoothing=float(opts["smoothing"]), device=device)
+    if fit is not None:
+        from .field_weights import fit_field_weights
+        if opts["radius"] is not None and not 0 <= opts["radius"] <= BASELINE_MAX_RADIUS * PHONO_MAX_WEIGHT:
+            raise ValueError(f"phono_baseline: radius={opts['radius']!r}, expected null or an integer in 0..{BASELINE_MAX_RADIUS * PHONO_MAX_WEIGHT}")
+        report = fit_field_weights(train_data, codes, levels=fit["levels"], sweeps=fit["sweeps"], scoring=fit["scoring"], gap=opts["gap"], **vote)
+        fweights = [int(v) for v in report["weights"]]
+        names = list((dataset_args or {}).get("fields") or [])
+        names = names if len(names) == F else [f"field{f}" for f in range(F)]
+        save_json(_jsonable({**report, "fields": dict(zip(names, fweights)), "field_names": names, "options": {**fit, "gap": opts["gap"]},
+                             "note": "leave-one-out on the train split: repeated glosses flatter it; judge the weights by phono_vs_weighted "
+                                     "in test_phono_baseline.json"}), os.path.join(workdir, "train_phono_weights.json"))
+        unit_knn = PhonoKNN(codes, gap=gap, **vote).fit(train_data)
+        F_unit, F = F, sum(fweights)                             # from here on the unit is W
+        gap = F if opts["gap"] is None else opts["gap"]
+    radius = F if opts["radius"] is None else opts["radius"]
     if not 0 <= radius <= BASELINE_MAX_RADIUS * F:
         raise ValueError(f"phono_baseline: radius={radius!r}, expected null or an integer in 0..{BASELINE_MAX_RADIUS * F} (64 frames of {F} fields)")
-    knn = PhonoKNN(codes, gap=gap, k=opts["k"], weights=opts["weights"], tau=float(opts["tau"]), normalize=opts["normalize"],
-                   smoothing=float(opts["smoothing"]), device=device).fit(train_data)
+    if fweights is None:
+        knn = PhonoKNN(codes, gap=gap, **vote).fit(train_data)
+    else:
+        knn = PhonoKNN(codes, gap=gap, field_weights=fweights, **vote).fit(train_data)
     scores = {f"test_{m}": float(ScoringWrapper(m, test_data.labels())(knn, test_data, test_data.y)) for m in metrics}
     dist, idx = knn.kneighbors(test_data)
     rows = np.stack([(idx >= 0).sum(1), np.zeros(len(idx), dtype=np.int64), dist[:, 0], np.zeros(len(idx), dtype=np.int64)], axis=1)
@@ -758,8 +820,12 @@ def save_phono_baseline(est, train_data, test_data, opts, dataset_args, interval
             "scores": scores, "neighbours": _jsonable(summary), "refit_vs_phono": _jsonable(est.compare(knn, test_data, **(intervals or {})))}
     if unit is not None:
         base["baseline_vs_phono"] = _jsonable(unit.compare(knn, test_data, **(intervals or {})))
+    if fweights is not None:
+        base["options"].update(fields=F_unit, field_weights=fweights, unit=F)
+        base["phono_vs_weighted"] = _jsonable(unit_knn.compare(knn, test_data, **(intervals or {})))
     save_json(base, os.path.join(workdir, "test_phono_baseline.json"))
-    audit = split_audit(train_data, test_data, radius=radius, top=opts["top"], judge=est, device=device, field_codes=codes, gap=gap)
+    audit = split_audit(train_data, test_data, radius=radius, top=opts["top"], judge=est, device=device, field_codes=codes, gap=gap,
+                        **({} if fweights is None else {"field_weights": fweights}))
     per = audit["per_class"]
     names = train_data.vocab_y.itos if getattr(train_data, "vocab_y", None) is not None else None
     name = lambda c: names[int(c)] if names is not None else str(int(c))
@@ -770,6 +836,8 @@ def save_phono_baseline(est, train_data, test_data, opts, dataset_args, interval
     out.update(top=opts["top"], gap=gap, fields=F, nearest_hist=[int(c) for c in audit["nearest_hist"]], pairs=[list(p) for p in audit["pairs"]],
                per_class=[{"class": int(c), "name": name(c), "support": int(per["support"][i]), "duplicated": int(per["duplicated"][i]),
                            "conflicting": int(per["conflicting"][i])} for i, c in enumerate(per["label"])])
+    if fweights is not None:
+        out.update(fields=F_unit, field_weights=fweights, unit=F)
     save_json(out, os.path.join(workdir, "test_phono_split_audit.json"))
     right = np.asarray(est.predict(test_data)) == np.asarray(test_data.y)
     with open(os.path.join(workdir, "test_phono_split_audit_rows.csv"), "w", newline="") as f:

@@ -18,7 +18,9 @@ is Myers' bit-vector recurrence with the query in one 64-bit word; longer rows (
 
 ``PhonoKNN`` and ``split_audit(field_codes=...)`` answer both questions under the PHONOLOGY-WEIGHTED edit distance instead
 (csrc/field_knn.hip): a token is a composition of F fields, and substituting one frame for another costs the number of fields in
-which they differ.  Only the search and the vote differ; the unit-cost surface keeps its bytes, messages and defaults."""
+which they differ.  Only the search and the vote differ; the unit-cost surface keeps its bytes, messages and defaults.
+``field_weights=`` gives every field an integer weight of its own (``slnlp.fit_field_weights`` fits them, slnlp/field_weights.py);
+without it every call is the one it was."""
 import copy
 
 import numpy as np
@@ -89,7 +91,7 @@ def _on_stream(dev, body):
 
 
 def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None):
-    """``ops.edit_knn_rows`` -- or, with ``metric`` = (codes on the device, gap), ``ops.field_knn_rows`` -- over the queries in
+    """``ops.edit_knn_rows`` -- or, with ``metric`` = (codes on the device, gap[, field weights or None]), ``ops.field_knn_rows`` -- over the queries in
     ``query_chunks``; ``each(start, stop, buf)`` runs behind every chunk on the same stream.  One scratch and one buffer serve the
     chunks of equal size.  The field metric keeps two bytes a pair and is chunked at half the pairs: the scratch stays at 256 MiB."""
     nq, nr = int(Xq.shape[0]), int(Xr.shape[0])
@@ -105,7 +107,8 @@ def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None):
         if metric is None:
             ops.edit_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius=radius, exclude=ex, buf=buf, scratch=scratch)
         else:
-            ops.field_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, metric[0], k, gap=metric[1], radius=radius, exclude=ex, buf=buf, scratch=scratch)
+            ops.field_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, metric[0], k, gap=metric[1], radius=radius, exclude=ex, buf=buf, scratch=scratch,
+                               field_weights=metric[2] if len(metric) > 2 else None)
         each(a, b, buf)
 
 
@@ -123,6 +126,13 @@ def field_table(what, field_codes, gap):
         raise ValueError(f"{what}: field_codes holds values outside int32")
     F = int(codes.shape[1])
     return np.ascontiguousarray(codes, dtype=np.int32), ops._int_in(what, "gap", F if gap is None else gap, 1, F)
+
+
+def field_weights_of(what, field_weights, F, gap):
+    """The per-field weights of the weighted metric checked, on the host: ``field_weights`` F integers in 0..16 whose sum W lies
+    in 1..16, ``gap`` an integer in 1..W (None: W) -> (tuple of ints, W, gap); anything else raises ValueError"""
+    _, W, gap = ops._field_weights(what, field_weights, F, gap)
+    return tuple(int(v) for v in field_weights), W, gap
 
 
 class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
@@ -227,14 +237,18 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
         k, weights, tau, normalize, lam = knn_options("EditKNN", self.k, self.weights, self.tau, self.normalize, self.smoothing)
 
         def body():
-            Xq, Lq, yq, exclude = self._queries(ds)
-            out = torch.empty(int(Xq.shape[0]), len(self.classes_), dtype=torch.float32, device=Xq.device)
-
-            def vote(a, b, buf):
-                self._vote(buf, Lq[a:b], weights=weights, tau=tau, normalize=normalize, lam=lam, out=out[a:b])
-            _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._metric())
-            return then(out, yq)
+            return then(*self._queue_logp(ds, k, weights, tau, normalize, lam))
         return self._on_stream(body)
+
+    def _queue_logp(self, ds, k, weights, tau, normalize, lam):
+        """``_forward_logp``'s launches queued on the current stream: (log-probs [len(ds), V], labels), both on the device"""
+        Xq, Lq, yq, exclude = self._queries(ds)
+        out = torch.empty(int(Xq.shape[0]), len(self.classes_), dtype=torch.float32, device=Xq.device)
+
+        def vote(a, b, buf):
+            self._vote(buf, Lq[a:b], weights=weights, tau=tau, normalize=normalize, lam=lam, out=out[a:b])
+        _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._metric())
+        return out, yq
 
     # ------------------------------------------------------------ neighbours
     def kneighbors(self, X, k=None):
@@ -264,18 +278,45 @@ class PhonoKNN(EditKNN):
     other -- while inserting or deleting a frame costs ``gap`` (1..F; None: F).  Distances are integers in field units, at most
     64 F; the vote's w = exp(-d / (tau n)) takes n = F max(len(query), len(neighbour), 1) when ``normalize``, else F, so ``tau``
     is in frames as in ``EditKNN``.  ``fit``, ``leave_one_out``, ``kneighbors`` and every ``LogProbJudge`` method are ``EditKNN``'s:
-    only the search and the vote differ.  With F = 1, ``field_codes[v, 0] = v`` and ``gap = 1`` it is ``EditKNN``."""
+    only the search and the vote differ.  With F = 1, ``field_codes[v, 0] = v`` and ``gap = 1`` it is ``EditKNN``.
 
-    def __init__(self, field_codes, gap=None, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None):
-        field_table("PhonoKNN", field_codes, gap)
+    ``field_weights`` (None: the metric above, the calls and the bytes it always had): F integers in 0..16 whose sum W lies in
+    1..16 -- field f counts ``field_weights[f]`` instead of 1, a field of weight 0 is ignored, a token outside the table costs W,
+    ``gap`` lies in 1..W (None: W), distances are at most 64 W and the vote's unit is W (``unit_``), so ``tau`` stays in frames.
+    ``slnlp.fit_field_weights`` fits them.  ``get_params`` lists ``field_weights`` only when it is set, so the parameter list of
+    the unweighted estimator is what it was; ``set_params(field_weights=...)`` is taken either way."""
+
+    def __init__(self, field_codes, gap=None, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None, field_weights=None):
+        self._check_metric(field_codes, gap, field_weights)
         super().__init__(k=k, weights=weights, tau=tau, normalize=normalize, smoothing=smoothing, device=device)
-        self.field_codes, self.gap = field_codes, gap
+        self.field_codes, self.gap, self.field_weights = field_codes, gap, field_weights
+
+    @staticmethod
+    def _check_metric(field_codes, gap, field_weights):
+        """-> (the table, gap, the weights as a tuple or None, the vote's unit: W, or F without weights)"""
+        if field_weights is None:
+            codes, gap = field_table("PhonoKNN", field_codes, gap)
+            return codes, gap, None, int(codes.shape[1])
+        codes, _ = field_table("PhonoKNN", field_codes, None)
+        w, W, gap = field_weights_of("PhonoKNN", field_weights, int(codes.shape[1]), gap)
+        return codes, gap, w, W
+
+    def get_params(self, deep=True):
+        params = super().get_params(deep=deep)
+        if params.get("field_weights") is None:
+            params.pop("field_weights", None)
+        return params
+
+    def set_params(self, **params):
+        if "field_weights" in params:
+            self.field_weights = params.pop("field_weights")
+        return super().set_params(**params)
 
     def fit(self, X, y=None):
         """``EditKNN.fit`` after the table is checked -- again, as ``set_params`` goes past ``__init__`` -- and held to the
         dataset: with a source vocabulary it has a row for every token id (ValueError otherwise, before anything touches the
         GPU).  The table is uploaded once."""
-        codes, gap = field_table("PhonoKNN", self.field_codes, self.gap)
+        codes, gap, fweights, unit = self._check_metric(self.field_codes, self.gap, self.field_weights)
         ds = self._as_dataset(X, y)
         vocab = getattr(ds, "vocab_X", None)
         if vocab is not None and codes.shape[0] < len(vocab):
@@ -284,17 +325,17 @@ class PhonoKNN(EditKNN):
         super().fit(ds)
         with torch.cuda.device(self._ids.device):
             self._codes = torch.from_numpy(codes).to(self._ids.device)
-        self._gap, self.fields_ = gap, int(codes.shape[1])
+        self._gap, self.fields_, self._fweights, self.unit_ = gap, int(codes.shape[1]), fweights, unit
         return self
 
     def _metric(self):
-        return self._codes, self._gap
+        return self._codes, self._gap, self._fweights
 
     def _vote(self, buf, Lq, **options):
-        ops.field_knn_logp(buf, Lq, self._lengths, self._y, self._prior, self.fields_, **options)
+        ops.field_knn_logp(buf, Lq, self._lengths, self._y, self._prior, self.unit_, **options)
 
 
-def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field_codes=None, gap=None):
+def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field_codes=None, gap=None, field_weights=None):
     """Do the rows of ``test`` have twins in ``train``?  One ``ops.edit_knn_rows`` pass with k = 1 (the held-out rows as queries, the
     train rows as references; in chunks where the pairs exceed the scratch cap), one download, then
     ``metrics.split_audit_report``: exact and near (<= ``radius`` edits, 0..64) duplicates, the ones whose twin carries ANOTHER
@@ -306,14 +347,24 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
     0..64 are not audited: ``flagged_queries`` / ``flagged_references`` count them.  ``field_codes`` int [Vt, F] (with ``gap``,
     1..F; None: F): the audit runs under ``PhonoKNN``'s phonology-weighted distance instead -- distances and ``radius`` (0..64 F)
     are in field units, ``nearest_hist`` has 64 F + 2 bins, and a row that differs from a train row in one field of one frame is a
-    near duplicate at ``radius=1``."""
+    near duplicate at ``radius=1``.  ``field_weights`` (with ``field_codes``; F integers in 0..16, their sum W in 1..16): the
+    audit runs under ``PhonoKNN(field_weights=...)``'s metric -- ``gap`` in 1..W (None: W), ``radius`` (0..64 W) and
+    ``nearest_hist`` (64 W + 2 bins) in units of W, ``max_distance`` 64 W -- so a row that differs from a train row only in fields
+    of weight 0 is an exact duplicate."""
     what = "split_audit"
     for name, ds in (("train", train), ("test", test)):
         if not isinstance(ds, TokenDataset) or len(ds) < 1:
             raise TypeError(f"{what}: {name} must be a non-empty slnlp.data.TokenDataset")
-    codes = None
+    codes, fweights, unit = None, None, 1
+    if field_codes is None and field_weights is not None:
+        raise ValueError(f"{what}: field_weights={field_weights!r} without field_codes: the unit-cost distance has no fields")
     if field_codes is not None:
-        codes, gap = field_table(what, field_codes, gap)
+        if field_weights is None:
+            codes, gap = field_table(what, field_codes, gap)
+            unit = int(codes.shape[1])
+        else:
+            codes, _ = field_table(what, field_codes, None)
+            fweights, unit, gap = field_weights_of(what, field_weights, int(codes.shape[1]), gap)
         for name, ds in (("train", train), ("test", test)):
             vocab = getattr(ds, "vocab_X", None)
             if vocab is not None and codes.shape[0] < len(vocab):
@@ -321,7 +372,7 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
                                  "must cover the vocabulary")
     elif gap is not None:
         raise ValueError(f"{what}: gap={gap!r} without field_codes: the unit-cost distance has no gap cost")
-    bound = _lib.EDIT_MAX_LEN * (1 if codes is None else int(codes.shape[1]))
+    bound = _lib.EDIT_MAX_LEN * unit
     radius = ops._int_in(what, "radius", radius, 0, bound)
     top = ops._int_in(what, "top", top, 0, 2 ** 31 - 1)
     if judge is not None and not isinstance(judge, LogProbJudge):
@@ -338,7 +389,7 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
         Xq, Lq = (Xr, Lr) if own else (up(test.ids), up(test.lengths))
         exclude = up(np.arange(len(train), dtype=np.int64)) if own else None
         _search(Xq, Lq, Xr, Lr, 1, radius, exclude, lambda a, b, buf: got.append({n: v.copy() for n, v in ops.edit_knn_download(buf).items()}),
-                metric=None if codes is None else (up(codes), gap))
+                metric=None if codes is None else (up(codes), gap, fweights))
     _on_stream(dev, body)
     rows, nbr = np.concatenate([g["rows"] for g in got]), np.concatenate([g["nbr"] for g in got])
     head = got[0]["head"].copy()

@@ -1582,12 +1582,30 @@ def _field_table(what, codes, gap, dev):
     return Vt, F, _int_in(what, "gap", F if gap is None else gap, 1, F)
 
 
-def field_distances(Xq, Lq, Xr, Lr, codes, gap=None, out=None):
+def _field_weights(what, field_weights, F, gap):
+    """The per-field weights of the weighted metric checked on the host: ``field_weights`` a sequence of F integers in 0..16 whose
+    sum W lies in 1..16, ``gap`` an integer in 1..W (None: W) -> (ctypes int32 [F] array, W, gap); anything else raises ValueError"""
+    try:
+        w = list(field_weights)
+    except TypeError:
+        w = None
+    whole = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if w is None or len(w) != F or not all(whole(v) and 0 <= v <= _lib.FIELD_MAX_WEIGHT for v in w):
+        raise ValueError(f"{what}: field_weights={field_weights!r}, expected {F} integers in 0..{_lib.FIELD_MAX_WEIGHT} (one per field)")
+    W = int(sum(int(v) for v in w))
+    if not 1 <= W <= _lib.FIELD_MAX_WEIGHT:
+        raise ValueError(f"{what}: field_weights={tuple(int(v) for v in w)} sum to W={W}, expected 1..{_lib.FIELD_MAX_WEIGHT}")
+    return (C.c_int32 * F)(*(int(v) for v in w)), W, _int_in(what, "gap", W if gap is None else gap, 1, W)
+
+
+def field_distances(Xq, Lq, Xr, Lr, codes, gap=None, out=None, field_weights=None):
     """The phonology-weighted edit distance of every (query, reference) pair (``slnlp_field_distances``, csrc/field_knn.hip):
     substituting a frame costs the number of fields in which the two tokens' rows of ``codes`` (int32 [Vt, F] on the device)
     differ -- F for a token outside the table, 0 for the same token -- inserting or deleting one costs ``gap`` (1..F; None: F).
     Rows as ``edit_distances`` -> uint16 [nq, nr]; 65535 where either row's length lies outside 0..64 (or beyond its row).  ``out``:
-    the matrix to fill.  One launch on the current stream of ``Xq``'s device; no host wait."""
+    the matrix to fill.  One launch on the current stream of ``Xq``'s device; no host wait.  ``field_weights`` (None: the call
+    above, unchanged): F integers in 0..16 with sum W in 1..16 -- field f counts ``field_weights[f]``, a token outside the table
+    costs W, ``gap`` lies in 1..W (None: W) and distances are at most 64 W (``slnlp_field_distances_w``)."""
     _lib.require_gpu()
     what = "field_distances"
     nq, ldq = _edit_side(what, "query", Xq, Lq)
@@ -1595,20 +1613,30 @@ def field_distances(Xq, Lq, Xr, Lr, codes, gap=None, out=None):
         raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
     nr, ldr = _edit_side(what, "reference", Xr, Lr)
     _edit_pairs(what, nq, nr)
-    Vt, F, gap = _field_table(what, codes, gap, Xq.device)
+    if field_weights is not None:
+        Vt, F, _ = _field_table(what, codes, None, Xq.device)
+        fw, W, gap = _field_weights(what, field_weights, F, gap)
+    else:
+        Vt, F, gap = _field_table(what, codes, gap, Xq.device)
     with torch.cuda.device(Xq.device):
         if out is None:
             out = torch.empty(nq, nr, dtype=torch.uint16, device=Xq.device)
         _tensor(what, "out", out, Xq.device, torch.uint16, (nq, nr))
+        if field_weights is not None:
+            check(load().slnlp_field_distances_w(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, fw, gap, ptr(out), stream_ptr()),
+                  what)
+            return out
         check(load().slnlp_field_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, gap, ptr(out), stream_ptr()), what)
     return out
 
 
-def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None, buf=None, scratch=None):
+def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None, buf=None, scratch=None, field_weights=None):
     """``edit_knn_rows`` under the phonology-weighted distance of ``field_distances`` (``slnlp_field_knn_rows``): the same selection
     into the same ``buf`` (``edit_knn_buffers(nq, k, device)``; None: a new one), distances in field units, ``radius`` in 0..64 F.
     ``scratch``: a uint8 tensor of at least 2 nq nr bytes, 2-byte aligned (None: a new one; it holds the uint16 [nq, nr] matrix
-    afterwards).  Three queued launches on the current stream of ``Xq``'s device; no host wait.  Returns ``buf``."""
+    afterwards).  Three queued launches on the current stream of ``Xq``'s device; no host wait.  Returns ``buf``.
+    ``field_weights`` (None: the call above, unchanged): the weighted metric of ``field_distances(field_weights=...)`` --
+    ``gap`` in 1..W, ``radius`` in 0..64 W, distances in units of W (``slnlp_field_knn_rows_w``)."""
     what = "field_knn_rows"
     k = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K)
     _lib.require_gpu()
@@ -1618,8 +1646,13 @@ def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None
     nr, ldr = _edit_side(what, "reference", Xr, Lr)
     _edit_pairs(what, nq, nr)
     dev = Xq.device
-    Vt, F, gap = _field_table(what, codes, gap, dev)
-    radius = _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * F)
+    if field_weights is not None:
+        Vt, F, _ = _field_table(what, codes, None, dev)
+        fw, W, gap = _field_weights(what, field_weights, F, gap)
+        radius = _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * W)
+    else:
+        Vt, F, gap = _field_table(what, codes, gap, dev)
+        radius = _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * F)
     if exclude is not None:
         _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
     with torch.cuda.device(dev):
@@ -1629,6 +1662,10 @@ def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None
         if scratch is None:
             scratch = torch.empty(2 * nq * nr, dtype=torch.uint8, device=dev)
         _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {2 * nq * nr}] tensor on {dev}")
+        if field_weights is not None:
+            check(load().slnlp_field_knn_rows_w(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, fw, gap, ptr(exclude), k, radius,
+                                                ptr(scratch), scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
+            return buf
         check(load().slnlp_field_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, gap, ptr(exclude), k, radius,
                                           ptr(scratch), scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
     return buf
@@ -1668,6 +1705,40 @@ def field_knn_logp(buf, Lq, Lr, yr, prior, F, *, weights="distance", tau=1.0, no
         check(load().slnlp_field_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, F, _lib.EDIT_WEIGHTS.index(weights),
                                           tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]), stream_ptr()), what)
     return out
+
+
+def loo_objective_table(slots, device):
+    """The table ``loo_objective`` fills: an int64 [slots, 4] device tensor of zeros, one 32-byte slot a candidate"""
+    slots = _int_in("loo_objective_table", "slots", slots, 1, _lib.LOO_MAX_SLOTS)
+    return torch.zeros(slots, _lib.LOO_SLOT_BYTES // 8, dtype=torch.int64, device=device)
+
+
+def loo_objective(logp, y, table, slot):
+    """What a search over candidate metrics ranks by (``slnlp_loo_objective``, csrc/score.hip): of the float32 log-probs ``logp``
+    [N, V] and the labels ``y`` int64 [N], into slot ``slot`` of ``table`` (``loo_objective_table``) the number of rows whose
+    arg-max -- the lowest index on a tie -- is the label, the fp64 sum of -logp[i, y_i] in a fixed order that depends on N alone,
+    the rows that hold a NaN and the rows whose label lies outside the classes (both count as wrong and add nothing).  One launch
+    on the current stream of ``logp``'s device; no host wait.  Returns ``table``."""
+    what = "loo_objective"
+    N, V, ld = _logp_matrix(what, logp)
+    _labels(what, y, logp.device, N)
+    if not (torch.is_tensor(table) and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == _lib.LOO_SLOT_BYTES // 8
+            and 1 <= table.shape[0] <= _lib.LOO_MAX_SLOTS and table.is_contiguous() and table.device == logp.device):
+        raise ValueError(f"{what}: table must be loo_objective_table(slots, device) on {logp.device}: a contiguous int64 [slots, 4] tensor")
+    C = int(table.shape[0])
+    slot = _int_in(what, "slot", slot, 0, C - 1)
+    _lib.require_gpu()
+    with torch.cuda.device(logp.device):
+        check(load().slnlp_loo_objective(ptr(logp), ld, ptr(y), N, V, ptr(table), C, slot, stream_ptr()), what)
+    return table
+
+
+def loo_objective_download(table):
+    """``loo_objective``'s table on the host in ONE device-to-host copy: {right int64 [C], sum float64 [C], nan_rows int64 [C],
+    bad_labels int64 [C]}"""
+    t = table.cpu()
+    return {"right": t[:, 0].numpy().copy(), "sum": t[:, 1].contiguous().view(torch.float64).numpy().copy(), "nan_rows": t[:, 2].numpy().copy(),
+            "bad_labels": t[:, 3].numpy().copy()}
 
 
 def scatter_logp(logp, rows, out, state=None):
