@@ -105,10 +105,15 @@ int slnlp_gemm(const slnlp_gemm_args* args, void* stream);
 int64_t slnlp_gemm_group_scratch_bytes(const slnlp_gemm_args* jobs, const int32_t* split_k, int njobs);
 /* Output tile of the plane-GEMM launches: 0 = automatic (128 x 128 once a launch holds >= 200 of them -- merged lockstep
  * launches, the configs[4] shapes, cfg2's in_proj gradients -- 256 x 256 for forward launches with K >= 1024 that fill the
- * chip's rounds, else 64 x 64); forced: 64, 128 (128 x 128, 64-k stages), 12832 (128 x 128, 32-k stages), 256 (256 x 256,
- * 32-k stages).  A tuning / test knob: results do not depend on it (the K partition, hence every element's accumulation
- * order, is the same for every geometry). */
+ * chip's rounds; 96 x 64 for a launch of ONE job with k-major A and no split-K that is more than one workgroup per CU at
+ * 64 x 64 and at most one at 96 x 64 -- cfg2's 2400-row products with N = 512; else 64 x 64); forced: 64, 128 (128 x 128,
+ * 64-k stages), 12832 (128 x 128, 32-k stages), 256 (256 x 256, 32-k stages), 96 (96 x 64 wherever it can run -- one job,
+ * k-major A, no split-K -- and 64 x 64 for every other launch).  A tuning / test knob: results do not depend on it (the K
+ * partition, hence every element's accumulation order, is the same for every geometry). */
 int slnlp_set_plane_tile(int tile);
+/* The geometry a launch of these plane jobs takes (slnlp_gemm / slnlp_gemm_group; split_k may be NULL): index into
+ * {64 x 64, 128 x 128 64-k, 128 x 128 32-k, 256 x 256 32-k, 96 x 64}.  Reads shapes, layouts and the knob above only: no device. */
+int slnlp_plane_geo(const slnlp_gemm_args* jobs, const int32_t* split_k, int njobs);
 /* Thread groups per workgroup of the fp32-operand GEMM launches (slnlp_gemm, fp32 jobs of slnlp_gemm_group, the plans' 50-row
  * products): 0 = automatic (two -- each walks one half of the K tiles -- for launches of <= 128 workgroups with at least four K
  * tiles; one for everything larger, merged lockstep launches included), 1 or 2 forced.  A tuning / test knob: the K sum is

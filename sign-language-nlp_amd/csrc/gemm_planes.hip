@@ -9,7 +9,9 @@
 // of 64 in both dimensions, so a K-step is: 4 x global_load_lds_dwordx4 per wave (global -> LDS
 // DMA, no VGPRs, no VALU, no ds_write), one counted s_waitcnt, two barriers, fragment reads, MFMA.
 //
-//  * tile 64x64x64, 8 waves (4x2, each 16x32), two LDS stages of {Ahi, Alo, Bhi, Blo} x 8 KiB;
+//  * tile 64x64x64, 8 waves (4x2, each 16x32), two LDS stages of {Ahi, Alo, Bhi, Blo} x 8 KiB -- the base geometry; the others
+//    (GEO below: 128x128 with 64-k or 32-k stages, 256x256x32, and 96x64x64 with a 2x4 wave grid and three stages) reuse its
+//    plane images, swizzles and fragment reads, and the host picks one per launch (plane_geo_auto);
 //  * LDS-DMA writes lane-linearly, so the bank-conflict swizzle is applied to the SOURCE address
 //    and undone with the same XOR on the fragment read (both are involutions):
 //      k-major image [row][64 k]  : 16-B slot ^= (row & 7)            -> conflict-free ds_read_b128
@@ -141,6 +143,26 @@ __device__ unsigned g_ts_n;
 #define TS_EPI(slot) do { } while (0)
 #endif
 
+// How a tile's eight waves share it: 4 (M) x 2 (N) for every BM that is a multiple of 64; the 96-row tile -- 96 / 4 is no
+// multiple of the 16-row MFMA block -- takes 2 (M) x 4 (N): 48 rows x (BN / 4) columns per wave.  A compile-time property of
+// the geometry: the 4 x 2 tiles compile to the code they had before the 96-row tile existed.
+template <int BM, int BN>
+struct WaveGrid {
+    static constexpr int WN = BM % 64 == 0 ? 2 : 4, WM = 8 / WN, WN_SH = WN == 2 ? 1 : 2;
+    static constexpr int MT = BM / WM / 16, NT = BN / WN / 16;       // 16 x 16 MFMA tiles per wave
+    static constexpr int SUBM = (BM + PT - 1) / PT;                   // 64-row plane images an A panel touches (the last may be partial)
+    static_assert(BM % (16 * WM) == 0 && BN % (16 * WN) == 0, "whole MFMA tiles per wave");
+    static __device__ __forceinline__ int wm0(int wave) { return (wave >> WN_SH) * (BM / WM); }
+    static __device__ __forceinline__ int wn0(int wave) { return (wave & (WN - 1)) * (BN / WN); }
+};
+
+// lane term of a k-major A piece of the 96-row tile: its rows start on multiples of 32, so a piece may reach past the plane's
+// last padded row -- those lanes read that row again (their products land in rows >= M, which no epilogue stores)
+__device__ __forceinline__ unsigned plane_lane_off_clamped(long ld, int row0, int row_max, int wave, int lane) {   // bytes
+    const int line = 8 * wave + (lane >> 3), ps = lane & 7;
+    return (unsigned)(((long)min(row0 + line, row_max) * ld + ((ps ^ (line & 7)) << 3)) * 2);
+}
+
 // The K loop of one (passes, operand layouts) variant: accumulators (and A's row sums) of output tile (bm0, bn0) over ring steps
 // [kt0, kt1).  Inlined once per variant into plane_tile, whose tile decoding, split-K meeting and epilogue are the same code for all.
 //
@@ -154,37 +176,50 @@ __device__ unsigned g_ts_n;
 //   128 x 128 x 32, 2 stages : the same tile in 64 KiB -- two workgroups per CU again, each other's cover during prologue / epilogue.
 //   256 x 256 x 32, 2 stages : 64 x 128 per wave -- 24 fragment reads for 96 MFMAs, half the operand bytes per FLOP again; 128 KiB,
 //                              one workgroup per CU: launches of many K-steps per tile and several tiles per CU.
+//   96 x 64 x 64, 3 stages   : 8 waves as 2 (M) x 4 (N), 48 x 16 per wave (WaveGrid above) -- 8 fragment reads for 9 MFMAs per 32-k;
+//                              a k-major A panel is one plane image + 32 lines; 120 KiB, one workgroup per CU on purpose: solo
+//                              launches of 257 .. 512 tiles of 64 x 64 that fit one workgroup per CU at 96 x 64 (plane_geo_auto).
 // The K partition (in units of 64) does not depend on the geometry, so every geometry accumulates every output element in the
 // same order: identical bits.
 template <int NSPLIT, bool AK, bool BK, int BM, int BN, int BKS, int NST>
 __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned short* smem, int bm0, int bn0, int kt0, int kt1,
-                                            bool do_rowsum, f32x4 (&acc)[BM / 64][BN / 32], float (&rowsum)[BM / PT],
-                                            unsigned long long* ts) {
+                                            bool do_rowsum, f32x4 (&acc)[WaveGrid<BM, BN>::MT][WaveGrid<BM, BN>::NT],
+                                            float (&rowsum)[WaveGrid<BM, BN>::SUBM], unsigned long long* ts) {
     // planes per operand: NSPLIT 3 = A_lo B_hi + A_hi B_lo + A_hi B_hi; NSPLIT 2 = A_hi (B_hi + B_lo) -- the A operand (the dY of a
     // gradient product) contributes its bf16 head only, a third less MFMA work and a quarter less staging; NSPLIT 1 = A_hi B_hi
     constexpr int NPA = NSPLIT == 3 ? 2 : 1, NPB = NSPLIT >= 2 ? 2 : 1;
-    constexpr int SUBM = BM / PT, SUBN = BN / PT;            // 64-row plane images per operand panel
-    constexpr int MT = BM / 64, NT = BN / 32;                // 16 x 16 MFMA tiles per wave: (BM/4)/16 x (BN/2)/16
+    using WG = WaveGrid<BM, BN>;
+    constexpr int SUBM = WG::SUBM, SUBN = BN / PT;           // 64-row plane images per operand panel
+    constexpr int MT = WG::MT, NT = WG::NT;                  // 16 x 16 MFMA tiles per wave
     constexpr int IMG_E = PT * BKS;                          // elements of one image (8 KiB at 64 k, 4 KiB at 32 k)
-    constexpr int A_IMGS = NPA * SUBM, B_IMGS = NPB * SUBN;
-    constexpr int STAGE = (A_IMGS + B_IMGS) * IMG_E;         // A planes then B planes
-    constexpr int PIECES = (A_IMGS + B_IMGS) * BKS / 64;     // DMA instructions per wave and stage
+    constexpr int A_E = BM * BKS, B_E = BN * BKS;            // elements of one plane's panel: whole images, but for the 96-row tile's 1.5
+    constexpr int A_LO = A_E, B_HI = NPA * A_E, B_LO = B_HI + B_E;     // A_hi (at 0), A_lo, B_hi, B_lo inside a stage
+    constexpr int STAGE = NPA * A_E + NPB * B_E;
+    constexpr bool HALF_A = BM % PT != 0;                    // the 96-row tile: a k-major A panel is a whole image + 32 lines
+    // DMA instructions per wave and stage.  The 32 extra lines of the 96-row tile are four waves' work per plane: A_hi's go to
+    // waves 0-3 and A_lo's to waves 4-7, one instruction each; a two-pass job has no A_lo, so its waves 4-7 issue one fewer
+    constexpr int PIECES = HALF_A ? NPA + 1 + NPB * SUBN : (NPA * SUBM + NPB * SUBN) * BKS / 64;
+    constexpr int PIECES_HI = HALF_A && NPA == 1 ? PIECES - 1 : PIECES;      // (waves 4-7)
     static_assert(BKS == 64 || (BM % 128 == 0 && BN % 128 == 0), "32-k stages move 128-row slabs");
+    static_assert(!HALF_A || (AK && BKS == 64 && BM == PT + PT / 2), "the 96-row panel is built for k-major A and 64-k stages");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm0 = (wave >> 1) * (BM / 4), wn0 = (wave & 1) * (BN / 2);
+    const int wm0 = WG::wm0(wave), wn0 = WG::wn0(wave);
     // planes are zero-padded to multiples of 64 rows; a wider panel may reach further: read the last padded block again
     // instead (its products land in rows >= M / columns >= N, which no epilogue stores)
     const int am_last = ((g.M + PT - 1) / PT - 1) * PT, bn_last = ((g.N + PT - 1) / PT - 1) * PT;
 
     // this wave's DMA pieces of a stage: per operand panel piece a loop-invariant lane offset (bytes inside the plane; planes
     // are far below 4 GiB); the hi and the lo plane of an operand share it
-    constexpr int APC = BKS == 64 ? SUBM : SUBM / 2, BPC = BKS == 64 ? SUBN : SUBN / 2;      // pieces per plane and stage
+    constexpr int APC = HALF_A ? 1 : BKS == 64 ? SUBM : SUBM / 2, BPC = BKS == 64 ? SUBN : SUBN / 2;      // (whole) pieces per plane and stage
     unsigned aoff[APC], boff[BPC];
+    unsigned aoff_half = 0;                                  // 96-row tile: lines 64 + 8 * (wave & 3) ... of the panel
 #pragma unroll
     for (int q = 0; q < APC; ++q) {
-        if constexpr (BKS == 64) aoff[q] = plane_lane_off<AK>(g.lda_p, BM > PT ? min(bm0 + q * PT, am_last) : bm0, wave, lane);
+        if constexpr (HALF_A) aoff[q] = plane_lane_off_clamped(g.lda_p, bm0, am_last + PT - 1, wave, lane);
+        else if constexpr (BKS == 64) aoff[q] = plane_lane_off<AK>(g.lda_p, BM > PT ? min(bm0 + q * PT, am_last) : bm0, wave, lane);
         else aoff[q] = slab32_lane_off<AK>(g.lda_p, bm0 + 2 * q * PT, am_last, wave, lane);
     }
+    if constexpr (HALF_A) aoff_half = plane_lane_off_clamped(g.lda_p, bm0 + PT, am_last + PT - 1, wave & 3, lane);
 #pragma unroll
     for (int q = 0; q < BPC; ++q) {
         if constexpr (BKS == 64) boff[q] = plane_lane_off<BK>(g.ldb_p, BN > PT ? min(bn0 + q * PT, bn_last) : bn0, wave, lane);
@@ -198,12 +233,17 @@ __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned s
 #pragma unroll
         for (int q = 0; q < APC; ++q) {
             dma_piece(g.A_hi, ka, aoff[q], s + q * PSTEP * IMG_E);
-            if (NPA == 2) dma_piece(g.A_lo, ka, aoff[q], s + (SUBM + q * PSTEP) * IMG_E);
+            if (NPA == 2) dma_piece(g.A_lo, ka, aoff[q], s + (A_LO + q * PSTEP * IMG_E));
+        }
+        if constexpr (HALF_A) {                              // (wave-uniform branches)
+            unsigned short* sh = smem + stage * STAGE + IMG_E + (wave & 3) * 512;
+            if (wave < 4) dma_piece(g.A_hi, ka, aoff_half, sh);
+            else if (NPA == 2) dma_piece(g.A_lo, ka, aoff_half, sh + A_LO);
         }
 #pragma unroll
         for (int q = 0; q < BPC; ++q) {
-            dma_piece(g.B_hi, kb, boff[q], s + (A_IMGS + q * PSTEP) * IMG_E);
-            if (NPB == 2) dma_piece(g.B_lo, kb, boff[q], s + (A_IMGS + SUBN + q * PSTEP) * IMG_E);
+            dma_piece(g.B_hi, kb, boff[q], s + (B_HI + q * PSTEP * IMG_E));
+            if (NPB == 2) dma_piece(g.B_lo, kb, boff[q], s + (B_LO + q * PSTEP * IMG_E));
         }
     };
 
@@ -214,7 +254,8 @@ __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned s
     for (int kt = kt0; kt < kt1; ++kt) {
         const int it = kt - kt0;
         // this wave's DMA of step kt has landed once only the (NST-2) newer steps' pieces are outstanding
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"((NST - 2) * PIECES) : "memory");
+        if (PIECES_HI == PIECES || wave < 4) asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"((NST - 2) * PIECES) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"((NST - 2) * PIECES_HI) : "memory");
         __builtin_amdgcn_s_barrier();                      // ... and so has every other wave's part
         asm volatile("" ::: "memory");
 #if SLNLP_PROBE_FENCES == 128
@@ -232,10 +273,10 @@ __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned s
                 const int row = wm0 + 16 * i;              // a 16-row MFMA tile never straddles two 64-row images
                 if constexpr (BKS == 64) {
                     ah[i] = pfrag<AK>(s + (row / PT) * IMG_E, row % PT, kk, lane);
-                    if (NPA == 2) al[i] = pfrag<AK>(s + (SUBM + row / PT) * IMG_E, row % PT, kk, lane);
+                    if (NPA == 2) al[i] = pfrag<AK>(s + (A_LO + (row / PT) * IMG_E), row % PT, kk, lane);
                 } else {
                     ah[i] = pfrag32<AK>(s + (row / PT) * IMG_E, row % PT, lane);
-                    if (NPA == 2) al[i] = pfrag32<AK>(s + (SUBM + row / PT) * IMG_E, row % PT, lane);
+                    if (NPA == 2) al[i] = pfrag32<AK>(s + (A_LO + (row / PT) * IMG_E), row % PT, lane);
                 }
             }
 #pragma unroll
@@ -245,11 +286,11 @@ __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned s
                 for (int j = 0; j < JB; ++j) {
                     const int row = wn0 + 16 * (j0 + j);
                     if constexpr (BKS == 64) {
-                        bh[j] = pfrag<BK>(s + (A_IMGS + row / PT) * IMG_E, row % PT, kk, lane);
-                        if (NPB == 2) bl[j] = pfrag<BK>(s + (A_IMGS + SUBN + row / PT) * IMG_E, row % PT, kk, lane);
+                        bh[j] = pfrag<BK>(s + (B_HI + (row / PT) * IMG_E), row % PT, kk, lane);
+                        if (NPB == 2) bl[j] = pfrag<BK>(s + (B_LO + (row / PT) * IMG_E), row % PT, kk, lane);
                     } else {
-                        bh[j] = pfrag32<BK>(s + (A_IMGS + row / PT) * IMG_E, row % PT, lane);
-                        if (NPB == 2) bl[j] = pfrag32<BK>(s + (A_IMGS + SUBN + row / PT) * IMG_E, row % PT, lane);
+                        bh[j] = pfrag32<BK>(s + (B_HI + (row / PT) * IMG_E), row % PT, lane);
+                        if (NPB == 2) bl[j] = pfrag32<BK>(s + (B_LO + (row / PT) * IMG_E), row % PT, lane);
                     }
                 }
 #pragma unroll
@@ -273,12 +314,15 @@ __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned s
 #pragma unroll
             for (int sm = 0; sm < SUBM; sm += 8 / OCT) {
                 const int im = sm + sub0;
+                if constexpr (HALF_A) {
+                    if (im * PT + row >= BM) continue;         // (the rows the partial image does not have)
+                }
                 float t = 0.f;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int off = BKS == 64 ? img_off<AK>(row, kq + k) : img32_off<AK>(row, kq + k);
                     t += pbf2f(s[im * IMG_E + off]);
-                    if (NPA == 2) t += pbf2f(s[(SUBM + im) * IMG_E + off]);
+                    if (NPA == 2) t += pbf2f(s[A_LO + im * IMG_E + off]);
                 }
                 if (BKS == 64) rowsum[sm] += t;
                 else if (kt & 1) rowsum[sm + 1] += t;          // (kt0 is even: a split starts on a 64-k tile)
@@ -314,12 +358,13 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
     tsp = ts;
     TS_MARK(0);
 #endif
-    constexpr int SUBM = BM / PT;                            // 64-row plane images per A panel
-    constexpr int MT = BM / 64, NT = BN / 32;                // 16 x 16 MFMA tiles per wave: (BM/4)/16 x (BN/2)/16
+    using WG = WaveGrid<BM, BN>;
+    constexpr int SUBM = WG::SUBM;                           // 64-row plane images per A panel
+    constexpr int MT = WG::MT, NT = WG::NT;                  // 16 x 16 MFMA tiles per wave
     constexpr int KSUB = PT / BKS;                           // ring steps per 64-k tile
     const slnlp_gemm_args& g = job.a;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm0 = (wave >> 1) * (BM / 4), wn0 = (wave & 1) * (BN / 2);
+    const int wm0 = WG::wm0(wave), wn0 = WG::wn0(wave);
     const int nks = job.nks;
     int bx, by, ks, tile;
     {   // XCD-aware order (see gemm.hip): each XCD owns a contiguous run of (tile, split) units
@@ -359,12 +404,21 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
 
     // variants 3, 4 (launches of the split-bf16 family only): the gradient products of one dY with its bf16 head alone (precision 2)
     // (a two-pass stage is 3/4 of a three-pass one: THREE of them fit where two of those do -- a prefetch distance of two K-steps)
-    if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-    else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-    else if (job.variant == 2) plane_kloop<NSPLIT, false, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-    else if constexpr (NSPLIT == 3) {
-        if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-        else plane_kloop<2, false, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+    if constexpr (BM % PT != 0) {
+        // the 96-row tile takes k-major A only (forward products and data gradients: plane_geo_auto never gives it another job)
+        if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        else if constexpr (NSPLIT == 3) {
+            if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        }
+    } else {
+        if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        else if (job.variant == 2) plane_kloop<NSPLIT, false, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        else if constexpr (NSPLIT == 3) {
+            if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            else plane_kloop<2, false, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+        }
     }
     TS_MARK(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // drain the dummy prefetches before LDS is reused / freed
@@ -490,7 +544,41 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
 #if defined(SLNLP_PROBE_EPI) && SLNLP_PROBE_EPI == 2
             if (ch == 0) TS_EPI(6);
 #endif
-            if (early) {
+            if constexpr (NT % 2 != 0) {
+                // (2 x 4 wave grid: ONE column tile per wave, so the two columns a Philox call serves -- c and c + 16, c % 32 < 16 --
+                // belong to two waves; each draws the call of its pair and takes its own half of the lots: the mask is a function
+                // of the element's global (row, column) alone.  Otherwise the loop below, one tile at a time.)
+                static_assert(NT == 1, "one column tile per wave");
+                if (early) {
+#pragma unroll 1
+                    for (int t = 0; t < MT; ++t) {
+                        const int lm0 = lr0 + 16 * t, gm0 = bm0 + ch * ER + lm0, gn0 = bn0 + lc0;
+                        if (gn0 >= N || gm0 >= M) continue;      // (never stored)
+                        float v[4], gt[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            v[r] = stg[(lm0 + r) * SLD + lc0];
+                            gt[r] = 1.f;
+                            if (g.gate && gm0 + r < M) gt[r] = g.gate[(long)(gm0 + r) * g.ldg + gn0];
+                        }
+                        const float bias = sbias[lc0];
+                        uint4 bits = make_uint4(0, 0, 0, 0);
+                        if (g.drop_p > 0.f) bits = dropout_bits8(dkey, (unsigned)gm0 >> 2, drop_cc((unsigned)gn0));
+                        const int h = drop_half((unsigned)gn0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float x = v[r] + bias;
+                            if (g.relu == 1) x = fmaxf(x, 0.f);
+                            else if (g.relu == 2) x = tanhf(x);
+                            if (g.gate) x = g.gate_mode == 1 ? x * (1.f - gt[r] * gt[r]) : (gt[r] > 0.f ? x * g.gate_scale : 0.f);
+                            if (g.drop_p > 0.f) x = (pick_lot(bits, h, r) >= job.drop_thr) ? x * job.drop_scale : 0.f;
+                            v[r] = x;
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) stg[(lm0 + r) * SLD + lc0] = v[r];
+                    }
+                }
+            } else if (early) {
                 // a lane's column tiles come in pairs 16 columns apart (wn0 and bn0 are multiples of 32): the 4 rows x 2 columns ONE
                 // Philox call serves (common.hpp).  The pair's eight values (and gate values) are READ FIRST, then taken through the
                 // chain, then written: element by element the compiler must keep every image read behind the previous image write
@@ -823,8 +911,10 @@ constexpr int PLACE_JOB_BITS = 12, PLACE_JOBS = 1 << PLACE_JOB_BITS;
 
 // GEO: the launch's tile geometry (table below); every job of a launch uses it (the host picks it per launch: plane_geo_for()).
 struct GeoInfo { int bm, bn, bks, nst; };
-constexpr int NGEO = 4;
-constexpr GeoInfo GEO[NGEO] = {{64, 64, 64, 2}, {128, 128, 64, 2}, {128, 128, 32, 2}, {256, 256, 32, 2}};
+// Geometry 4 (96 x 64) is a SOLO geometry: one job with k-major A, no split-K (plane_geo_auto); grouped, batched and merged launches
+// never take it, and their tables (split-K scratch regions, arrival counters, block maps) are sized for geometries 0 .. 3.
+constexpr int NGEO = 5, GEO_SOLO96 = 4;
+constexpr GeoInfo GEO[NGEO] = {{64, 64, 64, 2}, {128, 128, 64, 2}, {128, 128, 32, 2}, {256, 256, 32, 2}, {96, 64, 64, 3}};
 
 template <int NSPLIT, int G>
 __global__ __launch_bounds__(PTHREADS) void gemm_planes_kernel(const PlaneGroupParams P, const PlaneJob* __restrict__ tab,
@@ -858,7 +948,10 @@ __global__ __launch_bounds__(PTHREADS) void gemm_planes_kernel(const PlaneGroupP
 
 // ring bytes: stages x (A + B panels) x (hi, lo) x bks k x 2 B -- 64 KiB, 128 KiB, 64 KiB for three-pass jobs; 72 / 144 / 72 KiB for
 // two-pass jobs (three stages of A_hi + B_hi + B_lo); the epilogue's fp32 image of the tile (bm x (bn + 4) floats: 17 KiB / 66 KiB)
-// lives in the same memory.  A launch asks for the largest (one workgroup size per launch): two workgroups per CU still fit
+// lives in the same memory.  A launch asks for the largest (one workgroup size per launch): two workgroups per CU still fit.
+// The 96 x 64 tile: THREE stages of 40 KiB (four of 28 KiB for two-pass jobs), 120 / 112 KiB -- it is there to run ONE workgroup
+// per CU (gemm_planes_init checks that the runtime agrees), so nothing but its own ring covers a DMA round trip: with two stages
+// (80 / 84 KiB) it lost to the 64 x 64 tile's two workgroups per CU what it won in bytes.
 constexpr size_t plane_lds(int geo) {
     const size_t ring3 = (size_t)GEO[geo].nst * 2 * (GEO[geo].bm + GEO[geo].bn) * GEO[geo].bks * sizeof(unsigned short);
     const size_t ring2 = (size_t)(GEO[geo].nst + 1) * (GEO[geo].bm + 2 * GEO[geo].bn) * GEO[geo].bks * sizeof(unsigned short);   // two-pass jobs: one stage more
@@ -881,6 +974,7 @@ constexpr Q8GeoInfo QGEO[NQGEO] = {{64, 64, 4}, {128, 128, 2}};
 // the same sums, bit for bit -- on every CU: one (tile, 16 x 16-per-wave slab) per workgroup, all slices' loads in flight at once.
 template <int G>
 __global__ __launch_bounds__(PTHREADS) void plane_splitk_reduce_kernel(const PlaneJob job_in) {
+    static_assert(GEO[G].bm % 64 == 0, "split-K geometries only (4 x 2 wave grid)");
     constexpr int BM = GEO[G].bm, BN = GEO[G].bn, MT = BM / 64, NT = BN / 32, TILE_FLOATS = BM * BN, SC = 17;
     PlaneJob job = job_in;
     launder(job.a);
@@ -914,7 +1008,7 @@ __global__ __launch_bounds__(PTHREADS) void plane_splitk_reduce_kernel(const Pla
         if (by * BM + tid < g.M) g.rowsum_a[by * BM + tid] = rs_row;
     }
 }
-static const void* splitk_reduce_kernel_ptr(int geo) {
+static const void* splitk_reduce_kernel_ptr(int geo) {      // (geometries 0 .. 3: the 96 x 64 tile never splits K)
     switch (geo) {
         case 0: return (const void*)plane_splitk_reduce_kernel<0>;
         case 1: return (const void*)plane_splitk_reduce_kernel<1>;
@@ -974,7 +1068,7 @@ static int splitk_mode() {
 }
 
 // ---- which geometry a launch uses.  -1 = automatic (plane_geo_for), 0 .. NGEO-1 = forced (slnlp_set_plane_tile: tuning, tests)
-static int geo_of_knob(int knob) { return knob == 64 ? 0 : knob == 128 ? 1 : knob == 12832 ? 2 : knob == 256 ? 3 : -1; }
+static int geo_of_knob(int knob) { return knob == 64 ? 0 : knob == 128 ? 1 : knob == 12832 ? 2 : knob == 256 ? 3 : knob == 96 ? GEO_SOLO96 : -1; }
 static std::atomic<int> g_plane_geo{[] { const char* e = getenv("SLNLP_PLANE_TILE"); return geo_of_knob(e ? atoi(e) : 0); }()};
 constexpr int BIG_TILE_MIN_UNITS = 200;    // a launch takes 128 x 128 tiles when it still has at least this many of them
 
@@ -997,23 +1091,38 @@ constexpr int TWO_PER_CU_UNITS = 300;    // (a 4-fit lockstep step, 496- and 320
 //     previous kernel (step 15.00 -> 14.90 ms without it).  Not below: at K = 512 the tile's longer fill / drain is not paid back (846 tiles:
 //     185 against 183 us; 282 tiles: 88 against 67), half-empty rounds lose outright (128 tiles: 77 against 52 us), and the merged
 //     gradient groups (split-K partial tiles of 256 KiB, two-pass rings) stay 7 % ahead on the 128 x 128 x 32 ring.
+//   * 96 x 64 x 64, 3 stages (120 / 112 KiB: ONE workgroup per CU) for a solo launch -- one job, k-major A, no split-K -- that would be MORE than one
+//     workgroup per CU and at most two at 64 x 64 and is at most one at 96 x 64: cfg2's 2400-row products with N = 512 (encoder
+//     out_proj / linear1 / linear2 forward, the encoder data gradients) are 304 workgroups of 256 KB (K = 512) on 256 CUs, two of them
+//     on 48 CUs; at 96 x 64 they are 200 of 320 KB, one per CU.  These launches sit on the per-CU load path,
+//     so the launch lasts as long as its busiest CU loads.  Never a grouped, batched or merged launch: `solo` is set by
+//     plane_geo_for alone, for one job.
 struct LaunchShape {
     long units128 = 0, units256 = 0;     // workgroups the launch would have at 128 x 128 / 256 x 256 tiles
+    long units64 = 0, units96 = 0;       // ... at 64 x 64 / 96 x 64
     int min_k = 1 << 30;                 // shortest K loop (per split)
     bool forward = true;                 // every job: both operands k-major, no split-K
+    bool a_rows = true;                  // every job: A k-major, no split-K (what the 96 x 64 tile is built for)
+    bool solo = false;                   // a launch of its own for ONE job (plane_geo_for), not a merged or batched one
     int njobs = 0;
 };
 static void shape_add(LaunchShape& s, const slnlp_gemm_args& a, int nks) {
     if (nks < 1) nks = 1;
     s.units128 += (long)ceil_div(a.M, 128) * ceil_div(a.N, 128) * nks;
     s.units256 += (long)ceil_div(a.M, 256) * ceil_div(a.N, 256) * nks;
+    s.units64 += (long)ceil_div(a.M, 64) * ceil_div(a.N, 64) * nks;
+    s.units96 += (long)ceil_div(a.M, 96) * ceil_div(a.N, 64) * nks;
     s.min_k = std::min(s.min_k, a.K / nks);
     s.forward = s.forward && a.a_kmajor && a.b_kmajor && nks == 1 && a.precision != 2;
+    s.a_rows = s.a_rows && a.a_kmajor && nks == 1;
     ++s.njobs;
 }
+constexpr int CUS = 256;
 static int plane_geo_auto(const LaunchShape& s) {
     const int forced = g_plane_geo.load(std::memory_order_relaxed);
-    if (forced >= 0) return forced;
+    const bool can96 = s.solo && s.njobs == 1 && s.a_rows;
+    if (forced >= 0) return forced == GEO_SOLO96 && !can96 ? 0 : forced;      // (forced 96 x 64: where it can run; 64 x 64 elsewhere)
+    if (can96 && s.units64 > CUS && s.units64 <= 2 * CUS && s.units96 <= CUS) return GEO_SOLO96;
     if (s.units128 < BIG_TILE_MIN_UNITS) return 0;
     if (s.forward && s.min_k >= 1024 && (s.units256 >= 512 || s.min_k >= 2048) && s.units256 * 100 >= (s.units256 + 255) / 256 * 256 * 85) return 3;
     // ... and for a gradient product launched ALONE (gemm_planes_wd below: the data and the weight gradient of a large dY take a
@@ -1028,6 +1137,7 @@ int plane_geo_for(const slnlp_gemm_args* jobs, const int* split_k, int njobs) {
         if (jobs[i].precision == 8) return 0;                // (fp8 launches have their own geometries: q8_geo_auto)
         shape_add(s, jobs[i], split_k ? split_k[i] : 1);
     }
+    s.solo = njobs == 1;
     return plane_geo_auto(s);
 }
 
@@ -1044,6 +1154,19 @@ int gemm_planes_init() {
         if (!ok) {
             set_error("gemm_planes_init: cannot raise dynamic LDS limit: %s", hipGetErrorString(hipGetLastError()));
             return SLNLP_ERR_LAUNCH;
+        }
+        // the 96 x 64 tile is chosen for launches of one workgroup per CU: two of them on a CU would put the 64 x 64 tile's
+        // double load back on it.  Its LDS request is what holds it to one; ask the runtime here, outside any capture.
+        for (int prec = 1; prec <= 3; prec += 2) {
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_planes_kernel_ptr(prec, GEO_SOLO96), PTHREADS, plane_lds(GEO_SOLO96)) != hipSuccess) {
+                (void)hipGetLastError();                     // (no answer: 120 KiB of a CU's 160 KiB still fit once only)
+                continue;
+            }
+            if (per_cu > 1) {
+                set_error("gemm_planes_init: the 96 x 64 tile must run one workgroup per CU, the runtime reports %d", per_cu);
+                return SLNLP_ERR_LAUNCH;
+            }
         }
         return 0;
     });
@@ -1441,6 +1564,7 @@ static const void* kernel_of(int geo) {
         case 1: return (const void*)gemm_planes_kernel<NSPLIT, 1>;
         case 2: return (const void*)gemm_planes_kernel<NSPLIT, 2>;
         case 3: return (const void*)gemm_planes_kernel<NSPLIT, 3>;
+        case 4: return (const void*)gemm_planes_kernel<NSPLIT, 4>;
         default: return (const void*)gemm_planes_kernel<NSPLIT, 0>;
     }
 }
@@ -1520,11 +1644,17 @@ extern "C" int slnlp_quant_rows_fp8(const float* x, int64_t ld, int R, int K, ui
 
 extern "C" int slnlp_set_plane_tile(int tile) {
     if (tile != 0 && slnlp::geo_of_knob(tile) < 0) {
-        slnlp::set_error("set_plane_tile: %d (0 = automatic, 64, 128, 12832 = 128 x 128 with 32-k stages, 256 = 256 x 256 with 32-k stages)", tile);
+        slnlp::set_error("set_plane_tile: %d (0 = automatic, 64, 128, 12832 = 128 x 128 with 32-k stages, 256 = 256 x 256 with 32-k stages, "
+                         "96 = 96 x 64 for solo launches with k-major A)", tile);
         return SLNLP_ERR_INVALID_ARG;
     }
     slnlp::g_plane_geo.store(slnlp::geo_of_knob(tile), std::memory_order_relaxed);
     return 0;
+}
+
+extern "C" int slnlp_plane_geo(const slnlp_gemm_args* jobs, const int32_t* split_k, int njobs) {
+    if (!jobs || njobs < 1) return 0;
+    return slnlp::plane_geo_for(jobs, split_k, njobs);
 }
 
 extern "C" int slnlp_set_fp8_tile(int tile) {

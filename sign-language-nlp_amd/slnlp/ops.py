@@ -113,6 +113,14 @@ def gemm_group(jobs, split_k=None, scratch=None):
     return scratch
 
 
+def plane_geo(jobs, split_k=None):
+    """Tile geometry (0 .. 4: 64x64, 128x128 64-k, 128x128 32-k, 256x256 32-k, 96x64) a launch of these plane jobs takes; no device."""
+    n = len(jobs)
+    arr = (GemmArgs * n)(*jobs)
+    sk = (C.c_int32 * n)(*(split_k or [1] * n))
+    return int(load().slnlp_plane_geo(arr, sk, n))
+
+
 def gemm_wd_plan(jw, jd):
     """(split, separate, geometry of the wgrad launch, of the dgrad launch) the library picks for this gradient pair."""
     v = [C.c_int32(0) for _ in range(4)]
