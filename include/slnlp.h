@@ -181,7 +181,7 @@ int slnlp_embed_fwd(const int64_t* ids, int64_t ld_ids, int B, int S, int E, int
                     const float* table, const float* pe /* NULL: no positional term */, float* out,
                     float scale /* sqrt(E) for the Transformer, 1 for the RNN models (bkp.py:49) */,
                     float drop_p, int drop_site, const unsigned long long* rng,
-                    int64_t nan_idx /* id whose rows become NaN (decoder <pad> target), or -1 */, void* stream);
+                    int64_t nan_idx /* id whose rows become NaN (decoder <pad> target), or -1: none (an id of -1 is a zero row like any id outside [0, V)) */, void* stream);
 /* dtable[v,:] = sqrt(E) * sum_{tokens with id v} dropout_bwd(dx[token,:]);
  * rows with no token are zeroed.  Deterministic (fixed summation tree, no
  * float atomics).  scratch: slnlp_embed_bwd_scratch_bytes(B,S,E) bytes. */
@@ -280,6 +280,42 @@ typedef struct slnlp_ln_reduce_entry {
     const float* partial; float* dgamma; float* dbeta; int32_t nblk; int32_t E;
 } slnlp_ln_reduce_entry;
 int slnlp_ln_param_reduce(const slnlp_ln_reduce_entry* table_dev, int n, int max_E, void* stream);
+
+/* The embedding and LayerNorm launchers with the arguments the plans pass (host code around the same kernels; what
+ * tests/test_elementwise_edges_gpu.py calls).  Every one returns SLNLP_ERR_INVALID_ARG with a message before anything is launched
+ * for a null required pointer, a bad shape (E % 4 != 0; E > 1024 for LayerNorm; more than 65536 tokens for the embedding
+ * backward), dropout without its rng, or one plane of a pair without the other.
+ *   hi / lo (optional, both or neither): the fp32 output also as bf16 planes of the same shape -- hi = bf16(v) rounded to
+ *     nearest, lo = bf16(v - hi).
+ *   keep_mask (optional, [B*S*E/4] bytes): under dropout slnlp_embed_fwd_ex records the keep bits of each float4 (bit e = column
+ *     c + e kept), and slnlp_embed_bwd_ex reads them instead of drawing the lots again.  A keep_mask also sends a batch of at most
+ *     64 tokens through the chunk + combine launches instead of the single launch: same bits.
+ *   full_rows (0: rows): the rows of the caller's FULL batch.  The chunks of the (dgamma, dbeta) partial sums follow it, so a
+ *     shorter last batch writes the same nblk = ceil(full_rows / chunk) chunks, the trailing ones zero.  partial (with
+ *     nblk_out) and dx_drop may be NULL: no column sums / no fp32 dropout copy (drop_hi / drop_lo alone still get it).
+ *   slnlp_ln_param_partial: the (dgamma, dbeta) chunk sums of n LayerNorms in one launch from a DEVICE table; entry.dec picks the
+ *     row class (rows_dec / full_rows_dec or rows_enc / full_rows_enc).  Chunks are 16 rows (more past 16384 full rows); an entry
+ *     writes partial[chunk][2][E] for every chunk of its class's FULL batch, zeros past its last row.  Encoder entries are
+ *     skipped when full_rows_enc >= 1024: slnlp_layernorm_bwd(_ex) summed those chunks itself. */
+int slnlp_embed_fwd_ex(const int64_t* ids, int64_t ld_ids, int B, int S, int E, int V, const float* table, const float* pe,
+                       float* out, float scale, float drop_p, int drop_site, const unsigned long long* rng, int64_t nan_idx,
+                       uint16_t* hi, uint16_t* lo, unsigned char* keep_mask, void* stream);
+int slnlp_embed_bwd_ex(const int64_t* ids, int64_t ld_ids, int B, int S, int E, int V, const float* dx, float* dtable, float scale,
+                       int64_t zero_row, float drop_p, int drop_site, const unsigned long long* rng, void* scratch,
+                       const unsigned char* keep_mask, void* stream);
+int slnlp_layernorm_fwd_ex(const float* x, const float* gamma, const float* beta, int rows, int E, float eps, float* y,
+                           float* stats, uint16_t* hi, uint16_t* lo, void* stream);
+int slnlp_layernorm_bwd_ex(const float* dy, const float* x, const float* gamma, const float* stats, int rows, int E,
+                           const float* add_to_dx, float* dx, float* dx_drop, float drop_p, int drop_site,
+                           const unsigned long long* rng, float* partial, int* nblk_out, int full_rows, uint16_t* dx_hi,
+                           uint16_t* dx_lo, uint16_t* drop_hi, uint16_t* drop_lo, void* stream);
+typedef struct slnlp_ln_partial_entry {
+    const float* dy; const float* x; const float* stats; float* partial;
+    int32_t dec;   /* 1: a decoder LayerNorm (rows_dec), 0: an encoder one (rows_enc) */
+    int32_t pad;
+} slnlp_ln_partial_entry;
+int slnlp_ln_param_partial(const slnlp_ln_partial_entry* table_dev, int n, int E, int rows_enc, int rows_dec, int full_rows_enc,
+                           int full_rows_dec, void* stream);
 
 /* ------------------------------------------------------------------ loss --
  * logp = log_softmax(logits) (transformer.py:88-89 / bkp.py:75-76) and

@@ -36,7 +36,8 @@ __device__ __forceinline__ void embed_fwd_body(const long* __restrict__ ids, lon
         }
         // decoder input token == <pad>: its single self-attention key is masked
         // (transformer.py:72-73) -> softmax over an empty set -> NaN row in torch.
-        if (id == nan_idx) v = make_float4(NAN, NAN, NAN, NAN);
+        // (nan_idx < 0 means "no such id": an id of -1 is outside the table -- a zero row -- and not a match for that -1)
+        if (nan_idx >= 0 && id == nan_idx) v = make_float4(NAN, NAN, NAN, NAN);
         *reinterpret_cast<float4*>(out + (long)m * E + c) = v;
         store_planes4(po, (long)m * E + c, v);
     }
@@ -946,6 +947,65 @@ int slnlp_layernorm_bwd(const float* dy, const float* x, const float* gamma, con
 }
 int slnlp_ln_param_reduce(const slnlp_ln_reduce_entry* table_dev, int n, int max_E, void* stream) {
     return slnlp::ln_param_reduce(table_dev, n, max_E, (hipStream_t)stream);
+}
+
+// ---- the same launchers with the arguments only plans pass (output planes, the keep record, the full batch's rows, the
+// table-driven column sums): host code, no kernel of their own.  Everything is checked before the first launch.
+static_assert(sizeof(slnlp_ln_partial_entry) == sizeof(slnlp::LnPartialEntry) && sizeof(slnlp_ln_partial_entry) == 40 &&
+                  offsetof(slnlp_ln_partial_entry, dy) == offsetof(slnlp::LnPartialEntry, dy) &&
+                  offsetof(slnlp_ln_partial_entry, x) == offsetof(slnlp::LnPartialEntry, x) &&
+                  offsetof(slnlp_ln_partial_entry, stats) == offsetof(slnlp::LnPartialEntry, stats) &&
+                  offsetof(slnlp_ln_partial_entry, partial) == offsetof(slnlp::LnPartialEntry, partial) &&
+                  offsetof(slnlp_ln_partial_entry, dec) == offsetof(slnlp::LnPartialEntry, dec) &&
+                  offsetof(slnlp_ln_partial_entry, pad) == offsetof(slnlp::LnPartialEntry, pad),
+              "slnlp_ln_partial_entry is the published layout of LnPartialEntry");
+static bool plane_pair(const uint16_t* hi, const uint16_t* lo) { return (hi == nullptr) == (lo == nullptr); }
+static slnlp::PlaneOut planes(uint16_t* hi, uint16_t* lo) {
+    slnlp::PlaneOut po;
+    po.hi = hi;
+    po.lo = lo;
+    return po;                                 // (q8 stays null)
+}
+int slnlp_embed_fwd_ex(const int64_t* ids, int64_t ld_ids, int B, int S, int E, int V, const float* table, const float* pe,
+                       float* out, float scale, float drop_p, int drop_site, const unsigned long long* rng, int64_t nan_idx,
+                       uint16_t* hi, uint16_t* lo, unsigned char* keep_mask, void* stream) {
+    SLNLP_CHECK_ARG(plane_pair(hi, lo), "embed_fwd_ex: the hi and lo planes go together");
+    SLNLP_CHECK_ARG(S <= 0 || ld_ids >= S, "embed_fwd_ex: ld_ids %ld < S %d", (long)ld_ids, S);
+    return slnlp::embed_fwd(ids, ld_ids, B, S, E, V, table, pe, out, scale, drop_p, drop_site, rng, nan_idx, (hipStream_t)stream,
+                            planes(hi, lo), keep_mask);
+}
+int slnlp_embed_bwd_ex(const int64_t* ids, int64_t ld_ids, int B, int S, int E, int V, const float* dx, float* dtable, float scale,
+                       int64_t zero_row, float drop_p, int drop_site, const unsigned long long* rng, void* scratch,
+                       const unsigned char* keep_mask, void* stream) {
+    SLNLP_CHECK_ARG(S <= 0 || ld_ids >= S, "embed_bwd_ex: ld_ids %ld < S %d", (long)ld_ids, S);
+    return slnlp::embed_bwd(ids, ld_ids, B, S, E, V, dx, dtable, scale, zero_row, drop_p, drop_site, rng, scratch,
+                            (hipStream_t)stream, keep_mask);
+}
+int slnlp_layernorm_fwd_ex(const float* x, const float* gamma, const float* beta, int rows, int E, float eps, float* y,
+                           float* stats, uint16_t* hi, uint16_t* lo, void* stream) {
+    SLNLP_CHECK_ARG(plane_pair(hi, lo), "layernorm_fwd_ex: the hi and lo planes go together");
+    return slnlp::layernorm_fwd(x, gamma, beta, rows, E, eps, y, stats, (hipStream_t)stream, planes(hi, lo));
+}
+int slnlp_layernorm_bwd_ex(const float* dy, const float* x, const float* gamma, const float* stats, int rows, int E,
+                           const float* add_to_dx, float* dx, float* dx_drop, float drop_p, int drop_site,
+                           const unsigned long long* rng, float* partial, int* nblk_out, int full_rows, uint16_t* dx_hi,
+                           uint16_t* dx_lo, uint16_t* drop_hi, uint16_t* drop_lo, void* stream) {
+    SLNLP_CHECK_ARG(plane_pair(dx_hi, dx_lo) && plane_pair(drop_hi, drop_lo), "layernorm_bwd_ex: the hi and lo planes go together");
+    SLNLP_CHECK_ARG(full_rows >= 0, "layernorm_bwd_ex: full_rows %d < 0", full_rows);
+    return slnlp::layernorm_bwd(dy, x, gamma, stats, rows, E, add_to_dx, dx, dx_drop, drop_p, drop_site, rng, partial, nblk_out,
+                                full_rows, (hipStream_t)stream, planes(dx_hi, dx_lo), planes(drop_hi, drop_lo));
+}
+int slnlp_ln_param_partial(const slnlp_ln_partial_entry* table_dev, int n, int E, int rows_enc, int rows_dec, int full_rows_enc,
+                           int full_rows_dec, void* stream) {
+    SLNLP_CHECK_ARG(table_dev, "ln_param_partial: null table");
+    SLNLP_CHECK_ARG(n > 0 && n <= 65535, "ln_param_partial: %d entries (1 .. 65535)", n);
+    SLNLP_CHECK_ARG(E > 0 && E % 4 == 0 && E <= slnlp::LN_MAXU * 256, "ln_param_partial: need E %% 4 == 0 and E <= %d, got %d",
+                    slnlp::LN_MAXU * 256, E);
+    SLNLP_CHECK_ARG(rows_enc >= 0 && rows_dec >= 0 && full_rows_enc >= rows_enc && full_rows_dec >= rows_dec,
+                    "ln_param_partial: rows (%d, %d) must be >= 0 and within the full batch's (%d, %d)", rows_enc, rows_dec,
+                    full_rows_enc, full_rows_dec);
+    return slnlp::ln_param_partial(reinterpret_cast<const slnlp::LnPartialEntry*>(table_dev), nullptr, n, E, rows_enc, rows_dec,
+                                   full_rows_enc, full_rows_dec, (hipStream_t)stream);
 }
 int slnlp_lsm_nll(const float* logits, int64_t ld_logits, const int64_t* y, int B, int V, int64_t ignore_index,
                   float* logp, float* loss, float* dlogits, int64_t ld_dlogits, float* row_scratch, void* stream) {

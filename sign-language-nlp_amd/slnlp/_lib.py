@@ -82,6 +82,10 @@ class LnReduceEntry(C.Structure):
     _fields_ = [("partial", vp), ("dgamma", vp), ("dbeta", vp), ("nblk", i32), ("E", i32)]
 
 
+class LnPartialEntry(C.Structure):
+    _fields_ = [("dy", vp), ("x", vp), ("stats", vp), ("partial", vp), ("dec", i32), ("pad", i32)]
+
+
 class XmemDmemLayer(C.Structure):
     _fields_ = [("probs", vp), ("dsc", vp), ("dmbar", vp), ("qk", vp), ("dcp", vp), ("dbv", vp), ("drop_site", i32), ("pad", i32)]
 
@@ -106,6 +110,8 @@ SIGNATURES = {
     "slnlp_embed_fwd": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp, f32, f32, i32, vp, i64, vp]),
     "slnlp_embed_bwd_scratch_bytes": (i64, [i32, i32, i32]),
     "slnlp_embed_bwd": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, f32, i64, f32, i32, vp, vp, vp]),
+    "slnlp_embed_fwd_ex": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, vp, f32, f32, i32, vp, i64, vp, vp, vp, vp]),
+    "slnlp_embed_bwd_ex": (i32, [vp, i64, i32, i32, i32, i32, vp, vp, f32, i64, f32, i32, vp, vp, vp, vp]),
     "slnlp_attn_self_fwd": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]),
     "slnlp_attn_self_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, f32, i32, vp, vp]),
     "slnlp_attn_long_scratch_bytes": (i64, [i32, i32, i32]),
@@ -119,6 +125,9 @@ SIGNATURES = {
     "slnlp_layernorm_fwd": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp]),
     "slnlp_layernorm_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32), vp]),
     "slnlp_ln_param_reduce": (i32, [vp, i32, i32, vp]),
+    "slnlp_layernorm_fwd_ex": (i32, [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "slnlp_layernorm_bwd_ex": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, i32, vp, vp, C.POINTER(i32), i32, vp, vp, vp, vp, vp]),
+    "slnlp_ln_param_partial": (i32, [vp, i32, i32, i32, i32, i32, i32, vp]),
     "slnlp_lsm_nll": (i32, [vp, i64, vp, i32, i32, i64, vp, vp, vp, i64, vp, vp]),
     "slnlp_lsm_nll_ex": (i32, [vp, i64, vp, i32, i32, i64, vp, f32, i32, vp, vp, vp, i64, vp, vp]),
     "slnlp_lsm_bwd": (i32, [vp, vp, i32, i32, vp, i64, vp]),

@@ -260,6 +260,40 @@ def embed_bwd(ids, dx, *, B, S, V, scale=None, zero_row=-1, drop_p=0.0, drop_sit
     return dt
 
 
+def _plane_pair(like):
+    """Two int16 tensors of ``like``'s shape: the bf16 hi / lo planes a kernel writes beside its fp32 output."""
+    return torch.empty_like(like, dtype=torch.int16), torch.empty_like(like, dtype=torch.int16)
+
+
+def embed_fwd_ex(ids, table, pe, *, B, S, scale=None, drop_p=0.0, drop_site=0, rng=None, nan_idx=-1, want_planes=False,
+                 want_keep=False):
+    """``embed_fwd`` as the plans call it (``slnlp_embed_fwd_ex``) -> (out, (hi, lo) | None, keep_mask | None): the bf16 planes
+    of the output (int16 bit patterns) and, under dropout, the keep bits of each float4 ([S*B*E/4] uint8)."""
+    _lib.require_gpu()
+    V, E = table.shape
+    out = torch.empty(S * B, E, dtype=torch.float32, device=table.device)
+    planes = _plane_pair(out) if want_planes else None
+    keep = torch.zeros(S * B * E // 4, dtype=torch.uint8, device=table.device) if want_keep else None
+    hi, lo = planes if planes else (None, None)
+    check(load().slnlp_embed_fwd_ex(ptr(ids), ids.stride(0) if ids.ndim == 2 else 1, B, S, E, V, ptr(table), ptr(pe), ptr(out),
+                                    float(E ** 0.5 if scale is None else scale), drop_p, drop_site, ptr(rng), nan_idx, ptr(hi), ptr(lo),
+                                    ptr(keep), stream_ptr()), "embed_fwd_ex")
+    return out, planes, keep
+
+
+def embed_bwd_ex(ids, dx, *, B, S, V, scale=None, zero_row=-1, drop_p=0.0, drop_site=0, rng=None, keep_mask=None, out=None):
+    """``embed_bwd`` with the keep bits ``embed_fwd_ex`` recorded (``slnlp_embed_bwd_ex``; None: the lots are drawn again) ->
+    dtable [V, E], written into ``out`` when given."""
+    _lib.require_gpu()
+    E = dx.shape[1]
+    dt = torch.empty(V, E, dtype=torch.float32, device=dx.device) if out is None else out
+    scratch = torch.empty(int(load().slnlp_embed_bwd_scratch_bytes(B, S, E)), dtype=torch.uint8, device=dx.device)
+    check(load().slnlp_embed_bwd_ex(ptr(ids), ids.stride(0) if ids.ndim == 2 else 1, B, S, E, V, ptr(dx), ptr(dt),
+                                    float(E ** 0.5 if scale is None else scale), zero_row, drop_p, drop_site, ptr(rng), ptr(scratch),
+                                    ptr(keep_mask), stream_ptr()), "embed_bwd_ex")
+    return dt
+
+
 def attn_self_fwd(qkv, ids, pad_idx, *, B, S, H, dh, causal=True, drop_p=0.0, drop_site=0, rng=None):
     _lib.require_gpu()
     E = H * dh
@@ -389,39 +423,108 @@ def layernorm_bwd(dy, x, gamma, stats, *, add_to_dx=None, want_drop=False, drop_
     return dx, dxd, dg, db
 
 
-def lsm_nll(logits, y, ignore_index, *, want_grad=True):
+def layernorm_fwd_ex(x, gamma, beta, eps=1e-5, *, want_planes=False):
+    """``layernorm_fwd`` with the output's bf16 planes (``slnlp_layernorm_fwd_ex``) -> (y, stats, (hi, lo) | None)"""
+    _lib.require_gpu()
+    rows, E = x.shape
+    y = torch.empty_like(x)
+    stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device)
+    hi, lo = planes = _plane_pair(y) if want_planes else (None, None)
+    check(load().slnlp_layernorm_fwd_ex(ptr(x), ptr(gamma), ptr(beta), rows, E, eps, ptr(y), ptr(stats), ptr(hi), ptr(lo), stream_ptr()),
+          "layernorm_fwd_ex")
+    return y, stats, (planes if want_planes else None)
+
+
+def layernorm_bwd_ex(dy, x, gamma, stats, *, add_to_dx=None, want_drop=False, drop_p=0.0, drop_site=0, rng=None, full_rows=0,
+                     partial=None, want_planes=False, want_drop_planes=False):
+    """``slnlp_layernorm_bwd_ex``: the row kernel alone, as the plans launch it -> dict of dx, dx_drop | None (``want_drop``),
+    planes / drop_planes ((hi, lo) int16 | None) and nblk.  ``partial`` ([>= nblk, 2, E] fp32, or None: no column sums) receives the
+    (dgamma, dbeta) chunk sums, whose chunks follow ``full_rows`` (0: this call's rows); ``ln_param_reduce`` adds them."""
+    _lib.require_gpu()
+    rows, E = x.shape
+    dx = torch.empty_like(x)
+    dxd = torch.empty_like(x) if want_drop else None
+    planes = _plane_pair(dx) if want_planes else None
+    dplanes = _plane_pair(dx) if want_drop_planes else None
+    nblk = C.c_int32(0)
+    check(load().slnlp_layernorm_bwd_ex(ptr(dy), ptr(x), ptr(gamma), ptr(stats), rows, E, ptr(add_to_dx), ptr(dx), ptr(dxd), drop_p,
+                                        drop_site, ptr(rng), ptr(partial), C.byref(nblk), int(full_rows),
+                                        *[ptr(t) for t in (planes or (None, None))], *[ptr(t) for t in (dplanes or (None, None))],
+                                        stream_ptr()), "layernorm_bwd_ex")
+    return dict(dx=dx, dx_drop=dxd, planes=planes, drop_planes=dplanes, nblk=nblk.value)
+
+
+def _device_table(structs, device):
+    """A ctypes array of table entries, uploaded; the caller keeps the tensor until the launch that reads it has run."""
+    return torch.frombuffer(bytearray(bytes(structs)), dtype=torch.uint8).to(device)
+
+
+def ln_param_partial(entries, *, E, rows_enc=0, rows_dec=0, full_rows_enc=0, full_rows_dec=0):
+    """The (dgamma, dbeta) chunk sums of several LayerNorms in one table-driven launch (``slnlp_ln_param_partial``).
+    ``entries``: per LayerNorm a dict of the tensors dy, x, stats, partial (written) and the flag dec."""
+    _lib.require_gpu()
+    n = len(entries)
+    host = (_lib.LnPartialEntry * n)(*[_lib.LnPartialEntry(ptr(e["dy"]), ptr(e["x"]), ptr(e["stats"]), ptr(e["partial"]),
+                                                           int(bool(e["dec"])), 0) for e in entries])
+    table = _device_table(host, entries[0]["dy"].device)
+    check(load().slnlp_ln_param_partial(ptr(table), n, E, rows_enc, rows_dec, full_rows_enc, full_rows_dec, stream_ptr()), "ln_param_partial")
+    torch.cuda.current_stream().synchronize()  # `table` must outlive the launch
+
+
+def ln_param_reduce(entries, max_E):
+    """(dgamma, dbeta) of several LayerNorms from their chunk sums in one launch (``slnlp_ln_param_reduce``).  ``entries``: per
+    LayerNorm a dict of the tensors partial [nblk, 2, E], dgamma, dbeta (written) and the ints nblk, E."""
+    _lib.require_gpu()
+    n = len(entries)
+    host = (_lib.LnReduceEntry * n)(*[_lib.LnReduceEntry(ptr(e["partial"]), ptr(e["dgamma"]), ptr(e["dbeta"]), int(e["nblk"]), int(e["E"]))
+                                      for e in entries])
+    table = _device_table(host, entries[0]["partial"].device)
+    check(load().slnlp_ln_param_reduce(ptr(table), n, max_E, stream_ptr()), "ln_param_reduce")
+    torch.cuda.current_stream().synchronize()  # `table` must outlive the launch
+
+
+def _dlogits(dlogits, want_grad, B, V, device):
+    """The gradient output of the criterion: a [B, >= V] fp32 view to write into (its row stride is ld_dlogits), a new [B, V], or None."""
+    if dlogits is not None:
+        assert dlogits.shape == (B, V) and dlogits.stride(1) == 1, "dlogits: a [B, V] view with unit column stride"
+        return dlogits
+    return torch.empty(B, V, dtype=torch.float32, device=device) if want_grad else None
+
+
+def lsm_nll(logits, y, ignore_index, *, want_grad=True, dlogits=None):
     """-> (logp [B,V], loss [1], dlogits [B,V] | None)"""
     _lib.require_gpu()
     B, V = logits.shape
     logp = torch.empty(B, V, dtype=torch.float32, device=logits.device)
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-    dl = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_grad else None
+    dl = _dlogits(dlogits, want_grad, B, V, logits.device)
     rows = torch.empty(B, dtype=torch.float32, device=logits.device)
     check(load().slnlp_lsm_nll(ptr(logits), logits.stride(0), ptr(y), B, V, ignore_index, ptr(logp), ptr(loss),
-                               ptr(dl), V, ptr(rows), stream_ptr()), "lsm_nll")
+                               ptr(dl), V if dl is None else dl.stride(0), ptr(rows), stream_ptr()), "lsm_nll")
     return logp, loss, dl
 
 
-def lsm_nll_ex(logits, y, ignore_index, *, weight=None, label_smoothing=0.0, reduction="mean", want_grad=True):
+def lsm_nll_ex(logits, y, ignore_index, *, weight=None, label_smoothing=0.0, reduction="mean", want_grad=True, dlogits=None):
     """``lsm_nll`` with CrossEntropyLoss's ``weight`` ([V] fp32 on the device, or None), ``label_smoothing`` and
     ``reduction`` ("mean" / "sum") -> (logp [B,V], loss [1], dlogits [B,V] | None)"""
     _lib.require_gpu()
     B, V = logits.shape
     logp = torch.empty(B, V, dtype=torch.float32, device=logits.device)
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
-    dl = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_grad else None
+    dl = _dlogits(dlogits, want_grad, B, V, logits.device)
     rows = torch.empty(B, dtype=torch.float32, device=logits.device)
     w = None if weight is None else weight.to(logits.device, torch.float32).contiguous()
     check(load().slnlp_lsm_nll_ex(ptr(logits), logits.stride(0), ptr(y), B, V, ignore_index, ptr(w), float(label_smoothing),
-                                  _lib.REDUCTIONS[reduction], ptr(logp), ptr(loss), ptr(dl), V, ptr(rows), stream_ptr()), "lsm_nll_ex")
+                                  _lib.REDUCTIONS[reduction], ptr(logp), ptr(loss), ptr(dl), V if dl is None else dl.stride(0), ptr(rows),
+                                  stream_ptr()), "lsm_nll_ex")
     return logp, loss, dl
 
 
-def lsm_bwd(logp, dlogp):
+def lsm_bwd(logp, dlogp, *, dlogits=None):
     _lib.require_gpu()
     B, V = logp.shape
-    out = torch.empty_like(logp)
-    check(load().slnlp_lsm_bwd(ptr(logp), ptr(dlogp), B, V, ptr(out), V, stream_ptr()), "lsm_bwd")
+    out = _dlogits(dlogits, True, B, V, logp.device)
+    check(load().slnlp_lsm_bwd(ptr(logp), ptr(dlogp), B, V, ptr(out), out.stride(0), stream_ptr()), "lsm_bwd")
     return out
 
 
