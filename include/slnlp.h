@@ -1113,7 +1113,7 @@ int slnlp_attribution_summary(const float* base, int64_t ld_b, const int64_t* y,
  * its length L lies in 0..min(SLNLP_EDIT_MAX_LEN, its row stride); only the first L tokens of a usable row are read, tokens are
  * compared as full int64 values, and nothing past L -- and nothing of an unusable row -- influences anything.  Rows longer than 64
  * tokens are REFUSED (flagged and counted), never truncated: the kernel is Myers' bit-vector recurrence with the query in one
- * 64-bit word.
+ * 64-bit word.  The slnlp_edit_long_* entry points below run the multi-word recurrence and take rows of up to 512 tokens.
  *
  * slnlp_edit_distances: dist uint8 [nq, nr], the distance of every (query, reference) pair (at most 64), 255 where either row is
  * unusable.  One launch.
@@ -1158,6 +1158,46 @@ int slnlp_edit_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64
 int slnlp_edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq,
                         int64_t nr, int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior,
                         float* logp, int64_t ld, int64_t* head, void* stream);
+
+/* ------------------------------------------- edit-distance neighbours of long rows (csrc/edit_long.hip) --
+ * The same search for rows of up to SLNLP_EDIT_LONG_MAX_LEN = 512 tokens (slnlp.EditKNN(max_len=...), slnlp.split_audit(max_len=...)):
+ * the unit-cost Levenshtein distance by Myers' recurrence in its MULTI-WORD form, the query in ceil(L / 64) = 1..8 64-bit words
+ * (csrc/edit_myers_multi.hpp).  Everything is an integer until the votes; every result is a pure function of the arguments, as
+ * above.  The slnlp_edit_* entry points above are untouched by it: their limit, bytes and messages are what they were.
+ *
+ * max_len in 1..SLNLP_EDIT_LONG_MAX_LEN is an argument of every entry point.  A row is USABLE when its length L lies in
+ * 0..min(max_len, its row stride); only the first L tokens of a usable row are read, tokens are compared as full int64 values, and
+ * nothing past L -- and nothing of an unusable row -- influences anything.  A row longer than max_len is REFUSED (flagged and
+ * counted) although it may fit its row stride, never truncated.  d(q, r) <= max(len q, len r) <= max_len.  Where every row has at most
+ * 64 tokens the distances are those of slnlp_edit_distances, value for value.
+ *
+ * slnlp_edit_long_distances: dist uint16 [nq, nr], 65535 where either row is unusable.  One launch.
+ *
+ * slnlp_edit_long_knn_rows: distances into scratch (slnlp_edit_long_knn_scratch_bytes: TWO bytes per pair, 2-byte aligned; nq nr <=
+ * SLNLP_EDIT_MAX_PAIRS, -1 with a message otherwise), then the selection and the head as slnlp_edit_knn_rows: the k
+ * (1..SLNLP_EDIT_MAX_K) usable references of smallest distance ordered by (distance, index), ties at the k-th distance to the lower
+ * index, exclude as above, radius in 0..max_len.  It writes the same head / rows / nbr buffers; the code bit SLNLP_EDIT_CODE_QUERY
+ * says that the query's length lies outside 0..min(max_len, ldq).  Three queued launches, no host wait.
+ *
+ * slnlp_edit_long_knn_logp: the vote of slnlp_edit_knn_logp, operation for operation, but a neighbour is listed when 0 <= d <=
+ * max_len (slnlp_edit_knn_logp lists none beyond 64).  Two queued launches.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message that names the entry point, before anything is launched): those of the
+ * slnlp_edit_* entry points, and: max_len outside 1..SLNLP_EDIT_LONG_MAX_LEN, radius outside 0..max_len, a null or misaligned dist
+ * (2 bytes), a scratch that is too small or not 2-byte aligned.
+ *
+ * The phonology-weighted search below has no long form: its rows stay at SLNLP_EDIT_MAX_LEN = 64 tokens. */
+#define SLNLP_EDIT_LONG_MAX_LEN 512
+int slnlp_edit_long_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                              int64_t nr, int64_t max_len, uint16_t* dist /* [nq, nr] */, void* stream);
+int64_t slnlp_edit_long_knn_scratch_bytes(int64_t nq, int64_t nr);
+int slnlp_edit_long_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                             int64_t nr, int64_t max_len, const int64_t* exclude, int64_t k, int64_t radius, void* scratch,
+                             int64_t scratch_bytes, int64_t* head /* [8] */, int32_t* rows /* [nq, 4] */, int32_t* nbr /* [nq, k, 2] */,
+                             void* stream);
+int slnlp_edit_long_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq,
+                             int64_t nr, int64_t k, int64_t V, int64_t max_len, int weights, double tau, int normalize, double lam,
+                             const double* prior, float* logp, int64_t ld, int64_t* head, void* stream);
 
 /* ------------------------------------- phonology-weighted edit-distance neighbours (csrc/field_knn.hip) --
  * The same search under a WEIGHTED edit distance (slnlp.PhonoKNN, slnlp.split_audit(field_codes=...)): a token of this data is a

@@ -175,6 +175,10 @@ SIGNATURES = {
     "slnlp_edit_knn_scratch_bytes": (i64, [i64, i64]),
     "slnlp_edit_knn_rows": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "slnlp_edit_knn_logp": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, C.c_double, i32, C.c_double, vp, vp, i64, vp, vp]),
+    "slnlp_edit_long_distances": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp]),
+    "slnlp_edit_long_knn_scratch_bytes": (i64, [i64, i64]),
+    "slnlp_edit_long_knn_rows": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "slnlp_edit_long_knn_logp": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, C.c_double, i32, C.c_double, vp, vp, i64, vp, vp]),
     "slnlp_field_distances": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp, vp]),
     "slnlp_field_knn_scratch_bytes": (i64, [i64, i64]),
     "slnlp_field_knn_rows": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
@@ -346,6 +350,7 @@ ATTR_MAX_BINS = 64                              # SLNLP_ATTR_MAX_BINS
 ATTR_HEAD_BYTES = 64                            # SLNLP_ATTR_HEAD_BYTES
 ATTR_TARGETS = ("label", "pred")                # target 0: the label; 1: the base row's arg-max
 EDIT_MAX_LEN = 64                               # SLNLP_EDIT_MAX_LEN
+EDIT_LONG_MAX_LEN = 512                         # SLNLP_EDIT_LONG_MAX_LEN
 EDIT_MAX_K = 64                                 # SLNLP_EDIT_MAX_K
 EDIT_MAX_ROWS = 2 ** 30                         # SLNLP_EDIT_MAX_ROWS
 EDIT_MAX_PAIRS = 2 ** 31                        # SLNLP_EDIT_MAX_PAIRS

@@ -131,7 +131,11 @@ no network -- on the train split and audits the split with ``slnlp.split_audit``
     test_split_audit_rows.csv      row, label, name, nearest train row, its label, its name, distance, duplicated and whether the
                                    refit is right, for every test row with a neighbour
 
-(Rows longer than 64 frames are refused, not truncated: the baseline then raises before the grid search's results are written.)
+(Rows longer than 64 frames are refused, not truncated: the baseline then raises before the grid search's results are written --
+unless the key names a larger limit: ``baseline: {..., max_len: 128}``, an integer in 65..512, runs the baseline and the audit on the
+multi-word search (``EditKNN(max_len=...)``, ``split_audit(..., max_len=...)``, csrc/edit_long.hip), which takes rows of up to
+``max_len`` frames and refuses longer ones in the same way; ``radius`` then lies in 0..max_len and ``nearest_hist`` has max_len + 2
+bins.  ``phono_baseline`` has no such key: the phonology-weighted search stays at 64 frames.)
 
 A top-level ``phono_baseline: {k: 5, weights: distance, tau: 1.0, normalize: true, smoothing: 1.0, gap: null, radius: null, top: 50}``
 (all optional, these defaults) does the same under the PHONOLOGY-WEIGHTED edit distance (``slnlp.PhonoKNN``, csrc/field_knn.hip):
@@ -619,22 +623,31 @@ def save_train_dynamics(est, train_data, opts, workdir):
 BASELINE_DEFAULTS = {"k": 5, "weights": "distance", "tau": 1.0, "normalize": True, "smoothing": 1.0, "radius": 2, "top": 50}
 BASELINE_WEIGHTS = ("uniform", "distance")                                      # SLNLP_EDIT_UNIFORM / _DISTANCE
 BASELINE_MAX_K, BASELINE_MAX_RADIUS = 64, 64                                    # SLNLP_EDIT_MAX_K, SLNLP_EDIT_MAX_LEN
+BASELINE_LONG_MAX_LEN = 512                                                     # SLNLP_EDIT_LONG_MAX_LEN
 
 
 def baseline_options(setting):
     """The ``baseline`` key with its defaults filled in -- {k 5, weights distance, tau 1.0, normalize true, smoothing 1.0, radius 2,
     top 50} -- or None when the key is absent.  Anything but a dict over these seven keys ({}: all defaults) with ``k`` an integer
     in 1..64, ``weights`` uniform or distance, ``tau`` and ``smoothing`` finite numbers > 0, ``normalize`` a bool, ``radius`` an
-    integer in 0..64 and ``top`` an integer >= 0 raises ValueError."""
+    integer in 0..64 and ``top`` an integer >= 0 raises ValueError.  An eighth key, ``max_len`` (an integer in 65..512: rows of up to
+    that many frames, ``radius`` then in 0..max_len), is in the result only when it was given."""
     if setting is None:
         return None
+    known = tuple(BASELINE_DEFAULTS) + ("max_len",)
     if not isinstance(setting, dict):
-        raise ValueError(f"baseline={setting!r}: expected a dict with keys among {tuple(BASELINE_DEFAULTS)}")
-    unknown = sorted(set(setting) - set(BASELINE_DEFAULTS), key=str)
+        raise ValueError(f"baseline={setting!r}: expected a dict with keys among {known}")
+    unknown = sorted(set(setting) - set(known), key=str)
     if unknown:
-        raise ValueError(f"baseline: unknown keys {unknown} (known: {tuple(BASELINE_DEFAULTS)})")
+        raise ValueError(f"baseline: unknown keys {unknown} (known: {known})")
     opts = dict(BASELINE_DEFAULTS, **setting)
     whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    max_radius = BASELINE_MAX_RADIUS
+    if "max_len" in opts:
+        if not whole(opts["max_len"], BASELINE_MAX_RADIUS + 1, BASELINE_LONG_MAX_LEN):
+            raise ValueError(f"baseline: max_len={opts['max_len']!r}, expected an integer in {BASELINE_MAX_RADIUS + 1}..{BASELINE_LONG_MAX_LEN} "
+                             "(leave the key out for rows of at most 64 frames)")
+        max_radius = opts["max_len"]
     if not whole(opts["k"], 1, BASELINE_MAX_K):
         raise ValueError(f"baseline: k={opts['k']!r}, expected an integer in 1..{BASELINE_MAX_K}")
     if opts["weights"] not in BASELINE_WEIGHTS:
@@ -645,8 +658,8 @@ def baseline_options(setting):
             raise ValueError(f"baseline: {name}={v!r}, expected a finite number > 0")
     if not isinstance(opts["normalize"], bool):
         raise ValueError(f"baseline: normalize={opts['normalize']!r}, expected true or false")
-    if not whole(opts["radius"], 0, BASELINE_MAX_RADIUS):
-        raise ValueError(f"baseline: radius={opts['radius']!r}, expected an integer in 0..{BASELINE_MAX_RADIUS}")
+    if not whole(opts["radius"], 0, max_radius):
+        raise ValueError(f"baseline: radius={opts['radius']!r}, expected an integer in 0..{max_radius}")
     if not whole(opts["top"], 0, 2 ** 31 - 1):
         raise ValueError(f"baseline: top={opts['top']!r}, expected an integer >= 0")
     return opts
@@ -659,16 +672,17 @@ def save_baseline(est, train_data, test_data, opts, intervals, metrics, device, 
     from . import metrics as M
     from .edit_knn import EditKNN, split_audit
     from .net import ScoringWrapper
+    max_len = opts.get("max_len")
     knn = EditKNN(k=opts["k"], weights=opts["weights"], tau=float(opts["tau"]), normalize=opts["normalize"], smoothing=float(opts["smoothing"]),
-                  device=device).fit(train_data)
+                  device=device, max_len=max_len).fit(train_data)
     scores = {f"test_{m}": float(ScoringWrapper(m, test_data.labels())(knn, test_data, test_data.y)) for m in metrics}
     dist, idx = knn.kneighbors(test_data)
     rows = np.stack([(idx >= 0).sum(1), np.zeros(len(idx), dtype=np.int64), dist[:, 0], np.zeros(len(idx), dtype=np.int64)], axis=1)
-    summary = M.knn_report(rows, np.stack([dist, idx], axis=2), test_data.y, train_data.y)
-    save_json({"options": {k: opts[k] for k in ("k", "weights", "tau", "normalize", "smoothing")}, "train_rows": len(train_data), "scores": scores,
+    summary = M.knn_report(rows, np.stack([dist, idx], axis=2), test_data.y, train_data.y, **({} if max_len is None else {"max_distance": max_len}))
+    save_json({"options": {k: opts[k] for k in ("k", "weights", "tau", "normalize", "smoothing") + (() if max_len is None else ("max_len",))}, "train_rows": len(train_data), "scores": scores,
                "neighbours": _jsonable(summary), "refit_vs_baseline": _jsonable(est.compare(knn, test_data, **(intervals or {})))},
               os.path.join(workdir, "test_baseline.json"))
-    audit = split_audit(train_data, test_data, radius=opts["radius"], top=opts["top"], judge=est, device=device)
+    audit = split_audit(train_data, test_data, radius=opts["radius"], top=opts["top"], judge=est, device=device, max_len=max_len)
     per = audit["per_class"]
     names = train_data.vocab_y.itos if getattr(train_data, "vocab_y", None) is not None else None
     name = lambda c: names[int(c)] if names is not None else str(int(c))

@@ -13,12 +13,17 @@ all.
 same gloss signed several times; identical or near-identical token sequences on both sides of a split inflate every score, and a
 twin with ANOTHER gloss is irreducible error or a label problem no model-based audit can see.
 
-Rows longer than 64 frames are REFUSED -- ``fit`` raises, a query is flagged and gets a row of NaN -- never truncated: the kernel
-is Myers' bit-vector recurrence with the query in one 64-bit word; longer rows (the multi-word form) are out of scope here.
+Rows longer than 64 frames are REFUSED by default -- ``fit`` raises, a query is flagged and gets a row of NaN -- never truncated:
+the default kernel is Myers' bit-vector recurrence with the query in one 64-bit word.  ``EditKNN(max_len=...)`` and
+``split_audit(..., max_len=...)`` with ``max_len`` in 65..512 run the MULTI-WORD recurrence instead (csrc/edit_long.hip: the query
+in up to 8 words, a uint16 distance matrix, two bytes a pair): every call of that estimator takes rows of up to ``max_len`` frames
+and refuses longer ones in the same way.  It is opt-in: with nothing set every call is the one it was, launch for launch.
 
 ``PhonoKNN`` and ``split_audit(field_codes=...)`` answer both questions under the PHONOLOGY-WEIGHTED edit distance instead
 (csrc/field_knn.hip): a token is a composition of F fields, and substituting one frame for another costs the number of fields in
-which they differ.  Only the search and the vote differ; the unit-cost surface keeps its bytes, messages and defaults.
+which they differ.  Only the search and the vote differ; the unit-cost surface keeps its bytes, messages and defaults.  THE ONE
+LIMIT THAT REMAINS: the phonology-weighted search stays at 64 frames (its kernel keeps a thread's column of the dynamic program in
+LDS, which does not stretch to 512 positions) -- ``PhonoKNN`` and ``split_audit(field_codes=...)`` refuse ``max_len``.
 ``field_weights=`` gives every field an integer weight of its own (``slnlp.fit_field_weights`` fits them, slnlp/field_weights.py);
 without it every call is the one it was."""
 import copy
@@ -54,17 +59,26 @@ def query_chunks(nq, nr, cap=SCRATCH_PAIRS):
     return [(a, min(a + step, nq)) for a in range(0, nq, step)]
 
 
-def _check_rows(what, ds):
-    """A TokenDataset whose every row the kernel takes: lengths in 0..min(64, S)"""
+def long_max_len(what, max_len):
+    """``max_len`` checked: None (the 64-frame search) or an integer in 65..512 (the multi-word search); anything else raises
+    ValueError"""
+    if max_len is None:
+        return None
+    return ops._int_in(what, "max_len", max_len, _lib.EDIT_MAX_LEN + 1, _lib.EDIT_LONG_MAX_LEN)
+
+
+def _check_rows(what, ds, max_len=None):
+    """A TokenDataset whose every row the kernel takes: lengths in 0..min(64, S) -- or 0..min(max_len, S)"""
     if not isinstance(ds, TokenDataset):
         raise TypeError(f"{what}: expected a slnlp.data.TokenDataset, got {type(ds).__name__}")
     if len(ds) < 1:
         raise ValueError(f"{what}: the dataset has no rows")
-    top = min(_lib.EDIT_MAX_LEN, int(ds.ids.shape[1]))
+    limit = _lib.EDIT_MAX_LEN if max_len is None else max_len
+    top = min(limit, int(ds.ids.shape[1]))
     bad = (ds.lengths < 0) | (ds.lengths > top)
     if bad.any():
         raise ValueError(f"{what}: {int(bad.sum())} of {len(ds)} rows have a length outside 0..{top} (first: row {int(np.flatnonzero(bad)[0])}, "
-                         f"length {int(ds.lengths[bad][0])}); rows longer than {_lib.EDIT_MAX_LEN} frames are refused, not truncated")
+                         f"length {int(ds.lengths[bad][0])}); rows longer than {limit} frames are refused, not truncated")
 
 
 def _cuda_device(device):
@@ -90,13 +104,15 @@ def _on_stream(dev, body):
     return res
 
 
-def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None):
-    """``ops.edit_knn_rows`` -- or, with ``metric`` = (codes on the device, gap[, field weights or None]), ``ops.field_knn_rows`` -- over the queries in
+def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None, max_len=None):
+    """``ops.edit_knn_rows`` -- or, with ``metric`` = (codes on the device, gap[, field weights or None]), ``ops.field_knn_rows``; or, with
+    ``max_len`` (65..512, never beside ``metric``), ``ops.edit_long_knn_rows`` -- over the queries in
     ``query_chunks``; ``each(start, stop, buf)`` runs behind every chunk on the same stream.  One scratch and one buffer serve the
-    chunks of equal size.  The field metric keeps two bytes a pair and is chunked at half the pairs: the scratch stays at 256 MiB."""
+    chunks of equal size.  The field metric and the long rows keep two bytes a pair and are chunked at half the pairs: the scratch
+    stays at 256 MiB."""
     nq, nr = int(Xq.shape[0]), int(Xr.shape[0])
     cap = SCRATCH_PAIRS if cap is None else cap
-    width = 1 if metric is None else 2
+    width = 1 if metric is None and max_len is None else 2
     chunks = query_chunks(nq, nr, max(1, cap // width))
     scratch = torch.empty(width * (chunks[0][1] - chunks[0][0]) * nr, dtype=torch.uint8, device=Xq.device)
     buf = None
@@ -104,7 +120,9 @@ def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None):
         if buf is None or buf["shape"][0] != b - a:
             buf = ops.edit_knn_buffers(b - a, k, Xq.device)
         ex = None if exclude is None else exclude[a:b]
-        if metric is None:
+        if max_len is not None:
+            ops.edit_long_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, max_len=max_len, radius=radius, exclude=ex, buf=buf, scratch=scratch)
+        elif metric is None:
             ops.edit_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius=radius, exclude=ex, buf=buf, scratch=scratch)
         else:
             ops.field_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, metric[0], k, gap=metric[1], radius=radius, exclude=ex, buf=buf, scratch=scratch,
@@ -140,28 +158,50 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
     voting with ``weights`` "uniform" or "distance": w = exp(-d / (tau n)), n = max(len(query), len(neighbour), 1) when
     ``normalize``, else 1.  p_c = (sum of the weights of the neighbours with label c + smoothing prior_c) / (sum of all weights +
     smoothing) with ``prior_`` = (n_c + 1) / (N + V) of the train labels, so no class is at 0 and a query without a neighbour gets
-    the prior.  It has no temperature: ``calibration_`` is None, ``temperature_`` 1.0."""
+    the prior.  It has no temperature: ``calibration_`` is None, ``temperature_`` 1.0.
+
+    ``max_len`` (None: rows of at most 64 frames, the calls and the bytes it always had): an integer in 65..512 -- every call of
+    the estimator (``fit``'s row check, the log-probs, ``kneighbors``, ``leave_one_out``, ``attribute``) takes rows of up to
+    ``max_len`` frames through the multi-word search (csrc/edit_long.hip); a longer row is refused as a row beyond 64 is without
+    it, and where every row has at most 64 frames the log-probs are bit for bit the ones of ``max_len=None``.  ``get_params``
+    lists ``max_len`` only when it is set, so the parameter list of the default estimator is what it was;
+    ``set_params(max_len=...)`` is taken either way."""
     calibration_ = None
     temperature_ = 1.0
     predict_nonlinearity = "auto"
     initialized_ = False
     _loo = False
     _cap = None                                              # pairs per launch sequence (None: SCRATCH_PAIRS)
+    _max_len = None                                          # what fit checked max_len to: None, the 64-frame search
 
-    def __init__(self, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None):
+    def __init__(self, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None, max_len=None):
         knn_options("EditKNN", k, weights, tau, normalize, smoothing)
+        long_max_len("EditKNN", max_len)
         if device is not None:
             _cuda_device(device)
         self.k, self.weights, self.tau, self.normalize, self.smoothing, self.device = k, weights, tau, normalize, smoothing, device
+        self.max_len = max_len
+
+    def get_params(self, deep=True):
+        params = super().get_params(deep=deep)
+        if params.get("max_len") is None:
+            params.pop("max_len", None)
+        return params
+
+    def set_params(self, **params):
+        if "max_len" in params:
+            self.max_len = params.pop("max_len")
+        return super().set_params(**params)
 
     # ------------------------------------------------------------------ fit
     def fit(self, X, y=None):
-        """Check ``X`` (a ``TokenDataset``: lengths in 0..64, labels inside the classes -- ValueError otherwise, before anything
-        touches the GPU) and upload its ids, lengths and labels once.  ``classes_`` as ``NeuralNetClassifier`` sets them: the
-        target vocabulary's indices, or 0..max(y) without one."""
+        """Check ``X`` (a ``TokenDataset``: lengths in 0..64 -- 0..``max_len`` where that is set --, labels inside the classes:
+        ValueError otherwise, before anything touches the GPU) and upload its ids, lengths and labels once.  ``classes_`` as
+        ``NeuralNetClassifier`` sets them: the target vocabulary's indices, or 0..max(y) without one."""
         knn_options("EditKNN", self.k, self.weights, self.tau, self.normalize, self.smoothing)
+        self._max_len = long_max_len("EditKNN", self.max_len)    # again: set_params goes past __init__
         ds = self._as_dataset(X, y)
-        _check_rows("EditKNN.fit", ds)
+        _check_rows("EditKNN.fit", ds, self._max_len)
         classes = np.arange(len(ds.vocab_y)) if ds.vocab_y is not None else np.arange(int(ds.y.max()) + 1)
         V = len(classes)
         self._refuse_labels("EditKNN.fit", ((ds.y < 0) | (ds.y >= V)).sum(), len(ds), V)
@@ -225,12 +265,16 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
         return None
 
     def _vote(self, buf, Lq, **options):
+        if self._max_len is not None:
+            ops.edit_long_knn_logp(buf, Lq, self._lengths, self._y, self._prior, max_len=self._max_len, **options)
+            return
         ops.edit_knn_logp(buf, Lq, self._lengths, self._y, self._prior, **options)
 
     def _forward_logp(self, ds, then):
         """The float32 log-probs [len(ds), V] of ``ds`` (a ``TokenDataset`` or ``DeviceRows``) on the device, handed to
         ``then(logp, y_dev)``: the hook every consumer of ``LogProbJudge`` goes through.  The queries go in ``query_chunks``; per
-        chunk ``ops.edit_knn_rows`` and ``ops.edit_knn_logp`` -- five queued launches, nothing waits for the host.  A flagged query shows as a row of NaN."""
+        chunk ``ops.edit_knn_rows`` and ``ops.edit_knn_logp`` (with ``max_len``: their ``edit_long_`` siblings) -- five queued launches,
+        nothing waits for the host.  A flagged query shows as a row of NaN."""
         self._require_initialized()
         if self._loo:
             self._refuse_other_data(ds)                      # before anything touches the device
@@ -247,14 +291,14 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
 
         def vote(a, b, buf):
             self._vote(buf, Lq[a:b], weights=weights, tau=tau, normalize=normalize, lam=lam, out=out[a:b])
-        _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._metric())
+        _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._metric(), self._max_len)
         return out, yq
 
     # ------------------------------------------------------------ neighbours
     def kneighbors(self, X, k=None):
         """``(distances int32 [N, k], indices int64 [N, k])`` of the ``k`` (None: the estimator's) nearest train rows of every row
-        of ``X``, ordered by (distance, train row); (-1, -1) where fewer than k exist or the query's length is outside 0..64.  One
-        download per chunk of queries."""
+        of ``X``, ordered by (distance, train row); (-1, -1) where fewer than k exist or the query's length is outside 0..64
+        (0..``max_len`` where that is set).  One download per chunk of queries."""
         self._require_initialized()
         k = ops._int_in("EditKNN.kneighbors", "k", self.k if k is None else k, 1, _lib.EDIT_MAX_K)
         ds = self._as_dataset(X)
@@ -265,7 +309,7 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
         def body():
             Xq, Lq, _, exclude = self._queries(ds)
             _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, lambda a, b, buf: got.append(ops.edit_knn_download(buf)["nbr"].copy()), self._cap,
-                    self._metric())
+                    self._metric(), self._max_len)
         self._on_stream(body)
         nbr = np.concatenate(got, axis=0)
         return nbr[:, :, 0].astype(np.int32), nbr[:, :, 1].astype(np.int64)
@@ -284,7 +328,10 @@ class PhonoKNN(EditKNN):
     1..16 -- field f counts ``field_weights[f]`` instead of 1, a field of weight 0 is ignored, a token outside the table costs W,
     ``gap`` lies in 1..W (None: W), distances are at most 64 W and the vote's unit is W (``unit_``), so ``tau`` stays in frames.
     ``slnlp.fit_field_weights`` fits them.  ``get_params`` lists ``field_weights`` only when it is set, so the parameter list of
-    the unweighted estimator is what it was; ``set_params(field_weights=...)`` is taken either way."""
+    the unweighted estimator is what it was; ``set_params(field_weights=...)`` is taken either way.
+
+    It takes no ``max_len``: the phonology-weighted search is limited to 64 frames, and ``fit`` raises where the attribute was
+    set all the same."""
 
     def __init__(self, field_codes, gap=None, k=5, weights="distance", tau=1.0, normalize=True, smoothing=1.0, device=None, field_weights=None):
         self._check_metric(field_codes, gap, field_weights)
@@ -316,6 +363,9 @@ class PhonoKNN(EditKNN):
         """``EditKNN.fit`` after the table is checked -- again, as ``set_params`` goes past ``__init__`` -- and held to the
         dataset: with a source vocabulary it has a row for every token id (ValueError otherwise, before anything touches the
         GPU).  The table is uploaded once."""
+        if getattr(self, "max_len", None) is not None:
+            raise ValueError(f"PhonoKNN.fit: max_len={self.max_len!r}: the phonology-weighted search is limited to {_lib.EDIT_MAX_LEN} frames "
+                             "(only EditKNN and the unit-cost split_audit take max_len)")
         codes, gap, fweights, unit = self._check_metric(self.field_codes, self.gap, self.field_weights)
         ds = self._as_dataset(X, y)
         vocab = getattr(ds, "vocab_X", None)
@@ -335,7 +385,7 @@ class PhonoKNN(EditKNN):
         ops.field_knn_logp(buf, Lq, self._lengths, self._y, self._prior, self.unit_, **options)
 
 
-def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field_codes=None, gap=None, field_weights=None):
+def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field_codes=None, gap=None, field_weights=None, max_len=None):
     """Do the rows of ``test`` have twins in ``train``?  One ``ops.edit_knn_rows`` pass with k = 1 (the held-out rows as queries, the
     train rows as references; in chunks where the pairs exceed the scratch cap), one download, then
     ``metrics.split_audit_report``: exact and near (<= ``radius`` edits, 0..64) duplicates, the ones whose twin carries ANOTHER
@@ -350,8 +400,15 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
     near duplicate at ``radius=1``.  ``field_weights`` (with ``field_codes``; F integers in 0..16, their sum W in 1..16): the
     audit runs under ``PhonoKNN(field_weights=...)``'s metric -- ``gap`` in 1..W (None: W), ``radius`` (0..64 W) and
     ``nearest_hist`` (64 W + 2 bins) in units of W, ``max_distance`` 64 W -- so a row that differs from a train row only in fields
-    of weight 0 is an exact duplicate."""
+    of weight 0 is an exact duplicate.  ``max_len`` (None: the audit above, unchanged; an integer in 65..512): the unit-cost audit
+    of rows of up to ``max_len`` frames through the multi-word search (csrc/edit_long.hip) -- ``radius`` lies in 0..max_len,
+    ``nearest_hist`` has max_len + 2 bins, ``max_distance`` is max_len and only rows beyond max_len frames are flagged.  The
+    phonology-weighted search is limited to 64 frames: ``max_len`` beside ``field_codes`` raises ValueError."""
     what = "split_audit"
+    max_len = long_max_len(what, max_len)
+    if max_len is not None and field_codes is not None:
+        raise ValueError(f"{what}: max_len={max_len} with field_codes: the phonology-weighted search is limited to {_lib.EDIT_MAX_LEN} frames "
+                         "(only the unit-cost audit takes max_len)")
     for name, ds in (("train", train), ("test", test)):
         if not isinstance(ds, TokenDataset) or len(ds) < 1:
             raise TypeError(f"{what}: {name} must be a non-empty slnlp.data.TokenDataset")
@@ -372,7 +429,7 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
                                  "must cover the vocabulary")
     elif gap is not None:
         raise ValueError(f"{what}: gap={gap!r} without field_codes: the unit-cost distance has no gap cost")
-    bound = _lib.EDIT_MAX_LEN * unit
+    bound = _lib.EDIT_MAX_LEN * unit if max_len is None else max_len
     radius = ops._int_in(what, "radius", radius, 0, bound)
     top = ops._int_in(what, "top", top, 0, 2 ** 31 - 1)
     if judge is not None and not isinstance(judge, LogProbJudge):
@@ -389,7 +446,7 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
         Xq, Lq = (Xr, Lr) if own else (up(test.ids), up(test.lengths))
         exclude = up(np.arange(len(train), dtype=np.int64)) if own else None
         _search(Xq, Lq, Xr, Lr, 1, radius, exclude, lambda a, b, buf: got.append({n: v.copy() for n, v in ops.edit_knn_download(buf).items()}),
-                metric=None if codes is None else (up(codes), gap, fweights))
+                metric=None if codes is None else (up(codes), gap, fweights), max_len=max_len)
     _on_stream(dev, body)
     rows, nbr = np.concatenate([g["rows"] for g in got]), np.concatenate([g["nbr"] for g in got])
     head = got[0]["head"].copy()

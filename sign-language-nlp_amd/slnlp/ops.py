@@ -1683,6 +1683,98 @@ def edit_knn_download(buf, neighbours=True):
     return buf["packed"].cut("head", "nbr" if neighbours else "rows")
 
 
+def _edit_long_pairs(what, nq, nr):
+    if nq * nr > _lib.EDIT_MAX_PAIRS:
+        raise ValueError(f"{what}: {nq} x {nr} pairs, at most {_lib.EDIT_MAX_PAIRS} (two bytes each) are formed per call: pass the queries in chunks")
+
+
+def edit_long_distances(Xq, Lq, Xr, Lr, *, max_len, out=None):
+    """``edit_distances`` for rows of up to ``max_len`` (1..512) frames (``slnlp_edit_long_distances``, csrc/edit_long.hip: Myers'
+    recurrence in its multi-word form) -> uint16 [nq, nr]; 65535 where either row's length lies outside 0..max_len (or beyond its
+    row): a longer row is refused, never truncated.  Where both apply the values are ``edit_distances``'s.  ``out``: the matrix to
+    fill.  One launch on the current stream of ``Xq``'s device; no host wait."""
+    what = "edit_long_distances"
+    max_len = _int_in(what, "max_len", max_len, -2 ** 63, 2 ** 63 - 1)          # the library holds it to 1..512
+    _lib.require_gpu()
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    _edit_long_pairs(what, nq, nr)
+    with torch.cuda.device(Xq.device):
+        if out is None:
+            out = torch.empty(nq, nr, dtype=torch.uint16, device=Xq.device)
+        _tensor(what, "out", out, Xq.device, torch.uint16, (nq, nr))
+        check(load().slnlp_edit_long_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, max_len, ptr(out), stream_ptr()), what)
+    return out
+
+
+def edit_long_knn_rows(Xq, Lq, Xr, Lr, k, *, max_len, radius=0, exclude=None, buf=None, scratch=None):
+    """``edit_knn_rows`` for rows of up to ``max_len`` (1..512) frames (``slnlp_edit_long_knn_rows``): the same selection into the
+    same ``buf`` (``edit_knn_buffers(nq, k, device)``; None: a new one), ``radius`` in 0..max_len; the code bit 1 of ``rows[:, 3]``
+    says that the query's length lies outside 0..max_len.  ``scratch``: a uint8 tensor of at least 2 nq nr bytes, 2-byte aligned
+    (None: a new one; it holds the uint16 [nq, nr] matrix afterwards).  Three queued launches on the current stream of ``Xq``'s
+    device; no host wait.  Returns ``buf``."""
+    what = "edit_long_knn_rows"
+    max_len = _int_in(what, "max_len", max_len, -2 ** 63, 2 ** 63 - 1)          # the library holds it to 1..512 and the radius to 0..max_len
+    k, radius = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K), _int_in(what, "radius", radius, -2 ** 63, 2 ** 63 - 1)
+    _lib.require_gpu()
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    _edit_long_pairs(what, nq, nr)
+    dev = Xq.device
+    if exclude is not None:
+        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
+    with torch.cuda.device(dev):
+        if buf is None:
+            buf = edit_knn_buffers(nq, k, dev)
+        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
+        if scratch is None:
+            scratch = torch.empty(2 * nq * nr, dtype=torch.uint8, device=dev)
+        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {2 * nq * nr}] tensor on {dev}")
+        check(load().slnlp_edit_long_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, max_len, ptr(exclude), k, radius, ptr(scratch),
+                                              scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
+    return buf
+
+
+def edit_long_knn_logp(buf, Lq, Lr, yr, prior, *, max_len, weights="distance", tau=1.0, normalize=True, lam=1.0, out=None):
+    """``edit_knn_logp`` for the neighbours of ``edit_long_knn_rows`` (``slnlp_edit_long_knn_logp``): the same vote, operation for
+    operation, but a neighbour is listed up to the distance ``max_len`` (1..512) where ``edit_knn_logp`` lists none beyond 64.  Two
+    queued launches on the current stream of ``buf``'s device; no host wait.  Returns ``out``."""
+    what = "edit_long_knn_logp"
+    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
+    nq, k = buf["shape"]
+    dev = buf["flat"].device
+    max_len = _int_in(what, "max_len", max_len, -2 ** 63, 2 ** 63 - 1)          # the library holds it to 1..512
+    if weights not in _lib.EDIT_WEIGHTS:
+        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
+    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
+    _lib.require_gpu()
+    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
+    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
+    _tensor(what, "Lr", Lr, dev, torch.int64, None)
+    nr = int(Lr.shape[0])
+    _tensor(what, "yr", yr, dev, torch.int64, nr)
+    _tensor(what, "prior", prior, dev, torch.float64, None)
+    V = int(prior.shape[0])
+    if nr < 1 or V < 1:
+        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
+        if out.device != dev or tuple(out.shape) != (nq, V):
+            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
+        ld = _logp_matrix(f"{what} (out)", out)[2]
+        check(load().slnlp_edit_long_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, max_len,
+                                              _lib.EDIT_WEIGHTS.index(weights), tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]),
+                                              stream_ptr()), what)
+    return out
+
+
 def _field_table(what, codes, gap, dev):
     """The code table of the weighted edit distance: ``codes`` a contiguous int32 [Vt >= 1, F in 1..16] tensor on ``dev``, ``gap``
     an integer in 1..F (None: F) -> (Vt, F, gap)"""
