@@ -152,13 +152,15 @@ struct RngState {
 // operations.  Kernels that draw in a loop make it once in front of the loop: written inside, the load sits in every iteration
 // with a full wait behind it (the loop's LDS stores may alias the state as far as the compiler knows).
 struct DropKey { unsigned ks[5]; };
-__device__ __forceinline__ DropKey dropout_key(const unsigned long long* rng, int site) {
-    const unsigned long long k = rng[0] + 0x9E3779B97F4A7C15ull * rng[1];
+// (from the two rng words: a kernel that loads them ahead of time makes the key where it needs it)
+__device__ __forceinline__ DropKey dropout_key(unsigned long long seed, unsigned long long step, int site) {
+    const unsigned long long k = seed + 0x9E3779B97F4A7C15ull * step;
     DropKey K;
     K.ks[0] = (unsigned)k; K.ks[1] = (unsigned)(k >> 32); K.ks[2] = (unsigned)site; K.ks[3] = 0u;
     K.ks[4] = 0x1BD11BDAu ^ K.ks[0] ^ K.ks[1] ^ K.ks[2] ^ K.ks[3];
     return K;
 }
+__device__ __forceinline__ DropKey dropout_key(const unsigned long long* rng, int site) { return dropout_key(rng[0], rng[1], site); }
 
 #ifndef SLNLP_THREEFRY_ROUNDS
 #define SLNLP_THREEFRY_ROUNDS 12

@@ -18,6 +18,7 @@
 //      m-major image [k][64 rows] : 16-B slot ^= 2*(k>>1 & 1 | k>>3 & 1 << 1) -> ds_read_b64_tr_b16
 //  * padding makes every tile interior: no bounds logic anywhere in the loop.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -181,7 +182,7 @@ __device__ __forceinline__ unsigned plane_lane_off_clamped(long ld, int row0, in
 //                              launches of 257 .. 512 tiles of 64 x 64 that fit one workgroup per CU at 96 x 64 (plane_geo_auto).
 // The K partition (in units of 64) does not depend on the geometry, so every geometry accumulates every output element in the
 // same order: identical bits.
-template <int NSPLIT, bool AK, bool BK, int BM, int BN, int BKS, int NST>
+template <int NSPLIT, bool AK, bool BK, int BM, int BN, int BKS, int NST, int PART>
 __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned short* smem, int bm0, int bn0, int kt0, int kt1,
                                             bool do_rowsum, f32x4 (&acc)[WaveGrid<BM, BN>::MT][WaveGrid<BM, BN>::NT],
                                             float (&rowsum)[WaveGrid<BM, BN>::SUBM], unsigned long long* ts) {
@@ -250,7 +251,15 @@ __device__ __forceinline__ void plane_kloop(const slnlp_gemm_args& g, unsigned s
     // NST-deep LDS ring: steps kt+1 .. kt+NST-1 are in flight while step kt is consumed (a K-step's MFMA work is
     // ~0.2 - 0.6 us, one DMA round trip ~1 us).  ONE barrier per step: the stage refilled at step kt was consumed at
     // step kt-1, which every wave has finished once it passes this step's barrier.
-    for (int t = 0; t < NST - 1; ++t) issue(kt0 + t, t);
+    // PART 0 is the ring's prologue alone, PART 1 the loop behind it: what plane_tile puts between the two (the 96 x 64 tile's
+    // dropout decisions) runs while the first stages are on their way.  It must not issue vector memory requests of its own
+    // carelessly: they join the DMA's in-order counter.  (`s_waitcnt vmcnt(n)` returns once all but the n NEWEST requests have
+    // landed, and stage kt is always older than the NST - 2 stages the wait below leaves in flight: a request queued between the
+    // stages can make a wait longer, never too short.)
+    if constexpr (PART == 0) {
+        for (int t = 0; t < NST - 1; ++t) issue(kt0 + t, t);
+        return;
+    }
     for (int kt = kt0; kt < kt1; ++kt) {
         const int it = kt - kt0;
         // this wave's DMA of step kt has landed once only the (NST-2) newer steps' pieces are outstanding
@@ -365,7 +374,9 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
     const slnlp_gemm_args& g = job.a;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = WG::wm0(wave), wn0 = WG::wn0(wave);
-    const int nks = job.nks;
+    // (the 96-row tile is a solo geometry that never splits K -- plane_geo_auto -- so its kernels carry no meeting code and hold
+    // none of its scalar registers across the K loop)
+    const int nks = BM % PT != 0 ? 1 : job.nks;
     int bx, by, ks, tile;
     {   // XCD-aware order (see gemm.hip): each XCD owns a contiguous run of (tile, split) units
         const int nwg = job.tiles_x * job.tiles_y * nks;
@@ -402,24 +413,52 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
 #pragma unroll
     for (int i = 0; i < SUBM; ++i) rowsum[i] = 0.f;
 
-    // variants 3, 4 (launches of the split-bf16 family only): the gradient products of one dY with its bf16 head alone (precision 2)
-    // (a two-pass stage is 3/4 of a three-pass one: THREE of them fit where two of those do -- a prefetch distance of two K-steps)
-    if constexpr (BM % PT != 0) {
-        // the 96-row tile takes k-major A only (forward products and data gradients: plane_geo_auto never gives it another job)
-        if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-        else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-        else if constexpr (NSPLIT == 3) {
-            if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+    auto kloop = [&](auto part) {
+        constexpr int PART = decltype(part)::value;
+        // variants 3, 4 (launches of the split-bf16 family only): the gradient products of one dY with its bf16 head alone (precision 2)
+        // (a two-pass stage is 3/4 of a three-pass one: THREE of them fit where two of those do -- a prefetch distance of two K-steps)
+        if constexpr (BM % PT != 0) {
+            // the 96-row tile takes k-major A only (forward products and data gradients: plane_geo_auto never gives it another job)
+            if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            else if constexpr (NSPLIT == 3) {
+                if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            }
+        } else {
+            if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            else if (job.variant == 2) plane_kloop<NSPLIT, false, false, BM, BN, BKS, NST, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            else if constexpr (NSPLIT == 3) {
+                if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+                else plane_kloop<2, false, false, BM, BN, BKS, NST + 1, PART>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+            }
         }
-    } else {
-        if (job.variant == 0) plane_kloop<NSPLIT, true, true, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-        else if (job.variant == 1) plane_kloop<NSPLIT, true, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-        else if (job.variant == 2) plane_kloop<NSPLIT, false, false, BM, BN, BKS, NST>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-        else if constexpr (NSPLIT == 3) {
-            if (job.variant == 3) plane_kloop<2, true, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
-            else plane_kloop<2, false, false, BM, BN, BKS, NST + 1>(g, smem, bm0, bn0, kt0, kt1, do_rowsum, acc, rowsum, tsp);
+    };
+    kloop(std::integral_constant<int, 0>{});               // the ring's prologue
+    // The 96 x 64 tile's dropout decisions, made HERE, while the ring's first stages are on their way: a lane's MT Threefry calls
+    // -- a function of its global (rows, column) and the key alone -- were a third of what phases 1a + 1b cost behind the K loop
+    // (timeline, back to back: 2.00 us with them there, 1.36 us with them here, 0.20 us for a job without dropout): the 2 x 4 wave
+    // grid draws every call in two waves, and a workgroup that has its CU to itself has no other to fill its vector unit behind
+    // the loop.  Under the loop the vector unit is idle: the loop waits for the DMA.  Kept as one bit per element (bit 4 i + r).
+    // The rng words come through the scalar cache -- a wait on lgkmcnt, which the DMA's vmcnt queue does not enter.
+    unsigned keep = 0;
+    if constexpr (NT == 1) {
+        if (g.drop_p > 0.f) {
+            typedef const __attribute__((address_space(4))) unsigned long long* const_words;
+            const const_words rw = (const_words)g.rng;
+            const DropKey key = dropout_key(rw[0], rw[1], g.drop_site);
+            const int gn0 = bn0 + wn0 + (lane & 15), h = drop_half((unsigned)gn0);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                const int gm0 = bm0 + wm0 + ((lane >> 4) << 2) + 16 * i;
+                const uint4 bits = dropout_bits8(key, (unsigned)gm0 >> 2, drop_cc((unsigned)gn0));
+#pragma unroll
+                for (int r = 0; r < 4; ++r) keep |= (pick_lot(bits, h, r) >= job.drop_thr ? 1u : 0u) << (4 * i + r);
+            }
+            asm volatile("" : "+v"(keep));                   // (made here, not where it is used)
         }
     }
+    kloop(std::integral_constant<int, 1>{});
     TS_MARK(2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // drain the dummy prefetches before LDS is reused / freed
     __builtin_amdgcn_s_barrier();
@@ -517,24 +556,78 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
     //  (1b) jobs with dropout (or tanh) only: in the accumulator layout still -- a lane holds 4 rows x 1 column of a 16 x 16 tile,
     //       and one Philox call serves those 4 rows -- every lane takes its own values through bias, activation, gate and dropout
     //       IN the image, one ROLLED loop over its MT x NT tiles (its own words: no barrier between 1a and 1b; the bias comes from
-    //       an LDS copy, a global load per iteration would put its latency on every one of them);
+    //       an LDS copy, a global load per iteration would put its latency on every one of them).  The 96 x 64 tile (NT == 1, 12
+    //       accumulators per lane) does the same arithmetic on the accumulators themselves, AHEAD of 1a, and writes the image
+    //       once; its dropout decisions are there already, made under the K loop (`keep` above);
     //  (2)  row-major: a thread takes 4 consecutive columns of a row -- bias, ReLU and gate here for the jobs that skipped 1b,
     //       residual -- and writes ONE 16-byte fp32 store and two 8-byte plane stores (scalar pieces when the job's pointers /
     //       strides do not allow vectors); gate and residual pieces of eight passes are requested up front.
     // The element-wise arithmetic and its order are those of a plain per-element epilogue: results do not depend on the route.
+    // Per-workgroup timeline of the 96 x 64 tile at M = 2400, N = K = 512 (profiles/plane_epilogue_timeline.txt, p50 of 200 workgroups
+    // x 6 launches, back to back / behind evicted caches), parent -> this code: forward product with bias, dropout, residual and
+    // planes -- 1a + 1b 2.12 / 2.40 -> 0.80 / 1.16 us, everything behind the K loop 4.08 / 4.56 -> 2.36 / 2.96 us of a workgroup
+    // life of 11.7 / 14.1 -> 10.5 / 12.0 us.  (Residual, gate and bias requested under the K loop as well were built and measured:
+    // they take a data gradient's phase 2 from 1.4 to 0.5 us behind evicted caches and give the K loop 0.2 - 0.4 us more to
+    // carry, and in the train step, where the residual was written two launches ago, they measured as nothing -- DESIGN.md
+    // section 7 -- so those requests stay where they were.)
     constexpr int SLD = BN + 4, ER = BM > 128 ? 128 : BM, ECH = BM / ER;
     const int crow = (lane >> 4) << 2, ccol = lane & 15;
     float* stg = reinterpret_cast<float*>(smem);
     float* sbias = stg + ER * SLD;                           // [BN] behind the image (and behind the row-sum table / flag above)
     const bool early = g.drop_p > 0.f || g.relu == 2;        // block-uniform
-    if (early && tid < BN) sbias[tid] = (g.bias && bn0 + tid < N) ? g.bias[bn0 + tid] : 0.f;
+    float bias1 = 0.f;                                       // NT == 1: the bias of the lane's ONE column
+    if constexpr (NT == 1) {
+        if (early && g.bias && bn0 + wn0 + ccol < N) bias1 = g.bias[bn0 + wn0 + ccol];
+    } else {
+        if (early && tid < BN) sbias[tid] = (g.bias && bn0 + tid < N) ? g.bias[bn0 + tid] : 0.f;
+    }
     DropKey dkey = {};                                       // the step's Threefry key, made ONCE (common.hpp: dropout_key)
-    if (g.drop_p > 0.f) dkey = dropout_key(g.rng, g.drop_site);
+    if (NT != 1 && g.drop_p > 0.f) dkey = dropout_key(g.rng, g.drop_site);
 #pragma unroll 1
     for (int ch = 0; ch < ECH; ++ch) {
         __syncthreads();                                     // every thread is done with the K-loop stages / the split-K flag / the last chunk
         if (ECH == 1 || wm0 / ER == ch) {                    // (wave-uniform)
             const int lr0 = wm0 - ch * ER + crow, lc0 = wn0 + ccol;     // this lane's rows / column inside the chunk's image, tile (0, 0)
+            if constexpr (NT == 1) {
+                // (1b) of the 2 x 4 wave grid, IN REGISTERS ahead of (1a): ONE column tile per wave, so a lane's MT x 4 values share a
+                // column and its bias, and the two columns a Threefry call serves -- c and c + 16, c % 32 < 16 -- belong to two waves;
+                // each draws the call of its pair and takes its own half of the lots: the mask is a function of the element's
+                // global (row, column) alone.  Unrolled over MT = 3 (static accumulator indices; 12 values, not the wide tiles'
+                // 64 or 128): the gate values of all MT tiles are one round trip, and the image is written once instead of
+                // written, read back and written again per tile.
+                static_assert(ECH == 1, "one chunk");
+                const int gn0 = bn0 + lc0;
+                if (early && gn0 < N) {
+                    float gt[MT][4];
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int gm = bm0 + lr0 + 16 * i + r;
+                            gt[i][r] = 1.f;
+                            if (g.gate && gm < M) gt[i][r] = g.gate[(long)gm * g.ldg + gn0];
+                        }
+                    // One step of the chain at a time over the lane's 12 values, each block-uniform condition tested ONCE: written
+                    // element by element (as the rolled loop below is) every element branches around the steps its job does not
+                    // take -- some sixty scalar branches, and a taken branch refills the wave's instruction buffer: phases 1a + 1b
+                    // 1.36 -> 0.76 us (timeline, back to back).  Element by element the operations and their order are the same.
+                    // (Rows >= M are computed like the others and never stored.)
+                    auto each = [&](auto&& step) {
+#pragma unroll
+                        for (int i = 0; i < MT; ++i)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) acc[i][0][r] = step(acc[i][0][r], i, r);
+                    };
+                    each([&](float x, int, int) { return x + bias1; });
+                    if (g.relu == 1) each([&](float x, int, int) { return fmaxf(x, 0.f); });
+                    else if (g.relu == 2) each([&](float x, int, int) { return tanhf(x); });
+                    if (g.gate) {
+                        if (g.gate_mode == 1) each([&](float x, int i, int r) { return x * (1.f - gt[i][r] * gt[i][r]); });
+                        else each([&](float x, int i, int r) { return gt[i][r] > 0.f ? x * g.gate_scale : 0.f; });
+                    }
+                    if (g.drop_p > 0.f) each([&](float x, int i, int r) { return (keep >> (4 * i + r) & 1u) ? x * job.drop_scale : 0.f; });
+                }
+            }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -545,39 +638,7 @@ __device__ __forceinline__ void plane_tile(const PlaneJob& job, int lid, bool pl
             if (ch == 0) TS_EPI(6);
 #endif
             if constexpr (NT % 2 != 0) {
-                // (2 x 4 wave grid: ONE column tile per wave, so the two columns a Philox call serves -- c and c + 16, c % 32 < 16 --
-                // belong to two waves; each draws the call of its pair and takes its own half of the lots: the mask is a function
-                // of the element's global (row, column) alone.  Otherwise the loop below, one tile at a time.)
-                static_assert(NT == 1, "one column tile per wave");
-                if (early) {
-#pragma unroll 1
-                    for (int t = 0; t < MT; ++t) {
-                        const int lm0 = lr0 + 16 * t, gm0 = bm0 + ch * ER + lm0, gn0 = bn0 + lc0;
-                        if (gn0 >= N || gm0 >= M) continue;      // (never stored)
-                        float v[4], gt[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            v[r] = stg[(lm0 + r) * SLD + lc0];
-                            gt[r] = 1.f;
-                            if (g.gate && gm0 + r < M) gt[r] = g.gate[(long)(gm0 + r) * g.ldg + gn0];
-                        }
-                        const float bias = sbias[lc0];
-                        uint4 bits = make_uint4(0, 0, 0, 0);
-                        if (g.drop_p > 0.f) bits = dropout_bits8(dkey, (unsigned)gm0 >> 2, drop_cc((unsigned)gn0));
-                        const int h = drop_half((unsigned)gn0);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float x = v[r] + bias;
-                            if (g.relu == 1) x = fmaxf(x, 0.f);
-                            else if (g.relu == 2) x = tanhf(x);
-                            if (g.gate) x = g.gate_mode == 1 ? x * (1.f - gt[r] * gt[r]) : (gt[r] > 0.f ? x * g.gate_scale : 0.f);
-                            if (g.drop_p > 0.f) x = (pick_lot(bits, h, r) >= job.drop_thr) ? x * job.drop_scale : 0.f;
-                            v[r] = x;
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) stg[(lm0 + r) * SLD + lc0] = v[r];
-                    }
-                }
+                static_assert(NT == 1, "one column tile per wave: phase 1b ran in registers, above");
             } else if (early) {
                 // a lane's column tiles come in pairs 16 columns apart (wn0 and bn0 are multiples of 32): the 4 rows x 2 columns ONE
                 // Philox call serves (common.hpp).  The pair's eight values (and gate values) are READ FIRST, then taken through the
