@@ -1,19 +1,20 @@
 // edit_knn.hip -- all-pairs Levenshtein distances between two sets of token rows and the k nearest references of every query, on the
 // device (slnlp.EditKNN, slnlp.split_audit): the non-neural baseline of a sign data set -- "look up the most
 // similar training sign" -- and the audit of a split -- "does this held-out row have a twin in train".  include/slnlp.h states the
-// definitions and the buffers; tests/edit_knn_ref.py restates them in numpy, line by line.
+// definitions and the buffers; tests/edit_knn_ref.py restates them in numpy, line by line.  This file owns the 64-frame search's
+// kernels and entry points, and the head, vote and bad-label kernels that all three searches launch (edit_launch_head /
+// edit_launch_logp); the checks and the launch order of a search are edit_shared.hpp's shell.
 //
 // Xq int64 [nq, .] with row stride ldq, Lq int64 [nq]; Xr / Lr the references.  A row is USABLE when its length lies in
 // 0 .. min(64, its row stride): only the first L tokens of a usable row are read, nothing of an unusable one is, tokens are compared
 // as full int64 values.  EVERYTHING IS INTEGER until the votes and there are no floating-point atomics: each result is a pure
 // function of the arguments, whatever the grid, the stream or the kernels beside it.
 //
-//   edit_dist     a block per query (queries over a grid-stride loop; with few queries the references in tiles over grid.y).  The
-//                 query's tokens go to LDS; thread j < m forms the match mask of position j's token over all positions, the first occurrence of a token claims a slot of a 128-slot open
-//                 hash (an integer compare-and-swap on LDS; which slot it lands in is a race, what a lookup finds is not).  Thread
-//                 t then runs Myers' single-word recurrence (edit_myers.hpp, the bit-63 note is there) over references t,
-//                 t + 256, ...: per reference token one hash lookup of its mask and one column step.  uint8 [nq, nr]; 255 where
-//                 either row is unusable.
+//   edit_dist     edit_dist.hpp's body -- written once for this search and edit_long.hip's -- for queries of up to 64 frames: a block
+//                 per query (queries over a grid-stride loop; with few queries the references in tiles over grid.y), the query's
+//                 match masks in ONE 64-bit word per position behind a 128-slot open hash in LDS (1536 bytes a block), and per
+//                 reference token one lookup and one column step of Myers' recurrence (edit_myers_multi.hpp at one word, which is
+//                 edit_myers.hpp's step; the bit-63 note is there).  uint8 [nq, nr]; 255 where either row is unusable.
 //   edit_select   (the body is edit_shared.hpp's, shared with field_knn.hip; here over uint8 with its 65 bins a compile-time constant)
 //                 a wave per query over its row of the distance matrix: a 65-bin count in LDS (integer atomics) gives the cut-off
 //                 distance T, the count below it and how many rows AT T are still wanted; a second sweep in ascending reference
@@ -29,7 +30,7 @@
 
 #include "block_reduce.hpp"
 #include "common.hpp"
-#include "edit_myers.hpp"
+#include "edit_dist.hpp"
 #include "edit_shared.hpp"
 #include "launch.hpp"
 #include "spans.hpp"
@@ -39,79 +40,12 @@
 
 namespace slnlp {
 
-constexpr int EDIT_SLOTS = 128;                          // of the query's token hash: at most 64 are taken, a probe always ends
-
-__device__ __forceinline__ unsigned edit_hash(int64_t c) { return (unsigned)(((uint64_t)c * 0x9E3779B97F4A7C15ull) >> 57); }
-
 // ------------------------------------------------------------------------------------------------------- distances ----
+// the shared body (edit_dist.hpp) for queries of up to 64 frames over the uint8 matrix: one mask word, a 128-slot hash, 1536 bytes of LDS
 __device__ __forceinline__ void edit_dist_body(const int64_t* __restrict__ Xq, long ldq, const int64_t* __restrict__ Lq, int nq,
                                                const int64_t* __restrict__ Xr, long ldr, const int64_t* __restrict__ Lr, int nr, int max_q,
                                                int max_r, int tile, unsigned char* __restrict__ dist) {
-    __shared__ int64_t pat[SLNLP_EDIT_MAX_LEN];
-    __shared__ uint64_t eqm[SLNLP_EDIT_MAX_LEN];
-    __shared__ int owner[EDIT_SLOTS];
-    const int tid = threadIdx.x;
-    // block (x, y) takes the references [y tile, (y + 1) tile) of the queries x, x + gridDim.x, ...: few queries still fill the device
-    const long j_begin = (long)blockIdx.y * tile;
-    const int j_end = (int)(j_begin + tile < nr ? j_begin + tile : nr);
-    for (int q = blockIdx.x; q < nq; q += gridDim.x) {       // q, lq, m: the same in every thread, so is every branch on them
-        const int64_t lq = Lq[q];
-        unsigned char* out = dist + (long)q * nr;
-        if (lq < 0 || lq > max_q) {                          // reads nothing more
-            for (int j = (int)j_begin + tid; j < j_end; j += 256) out[j] = (unsigned char)EDIT_NONE;
-            continue;
-        }
-        const int m = (int)lq;
-        __syncthreads();                                     // the lookups of the block's previous query are over
-        if (tid < EDIT_SLOTS) owner[tid] = -1;
-        if (tid < m) pat[tid] = Xq[(long)q * ldq + tid];
-        __syncthreads();
-        if (tid < m) {
-            const int64_t c = pat[tid];
-            uint64_t mask = 0;
-            int first = tid;
-            for (int j = 0; j < m; ++j) {
-                if (pat[j] == c) {
-                    mask |= (uint64_t)1 << j;                // j <= 63
-                    first = j < first ? j : first;
-                }
-            }
-            eqm[tid] = mask;
-            if (first == tid) {                              // one claim per distinct token
-                unsigned h = edit_hash(c);
-                while (atomicCAS(&owner[h], -1, tid) != -1) h = (h + 1) & (EDIT_SLOTS - 1);
-            }
-        }
-        __syncthreads();
-        const uint64_t top = m > 0 ? (uint64_t)1 << (m - 1) : 0;
-        for (int j = (int)j_begin + tid; j < j_end; j += 256) {
-            const int64_t lr = Lr[j];
-            int d;
-            if (lr < 0 || lr > max_r) {
-                d = EDIT_NONE;
-            } else if (m == 0) {
-                d = (int)lr;
-            } else {
-                MyersState s = myers_begin(m);
-                const int64_t* row = Xr + (long)j * ldr;
-                const int n = (int)lr;
-                for (int t = 0; t < n; ++t) {
-                    const int64_t c = row[t];
-                    unsigned h = edit_hash(c);
-                    uint64_t Eq = 0;
-                    for (;;) {
-                        const int o = owner[h];
-                        if (o < 0) break;
-                        if (pat[o] == c) { Eq = eqm[o]; break; }
-                        h = (h + 1) & (EDIT_SLOTS - 1);
-                    }
-                    myers_step(s, Eq, top);
-                }
-                d = s.score;
-            }
-            out[j] = (unsigned char)d;
-        }
-    }
+    edit_dist_generic<SLNLP_EDIT_MAX_LEN, unsigned char, EDIT_NONE>(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, max_q, max_r, tile, dist);
 }
 SLNLP_ZKERNEL(edit_dist_kernel, 256, edit_dist_body)
 
@@ -227,61 +161,13 @@ __device__ __forceinline__ void edit_bad_body(const int* __restrict__ nbr, const
 SLNLP_ZKERNEL(edit_bad_kernel, 256, edit_bad_body)
 
 // ------------------------------------------------------------------------------------------------------- host side ----
-static int edit_check_pairs(const char* what, int64_t nq, int64_t nr) {
-    SLNLP_CHECK_ARG(nq <= SLNLP_EDIT_MAX_PAIRS / nr, "%s: %ld x %ld pairs, at most %ld (one byte each) are formed per call", what, (long)nq, (long)nr,
-                    (long)SLNLP_EDIT_MAX_PAIRS);
-    return 0;
-}
-// the distance launch (edit_dist_grid: a block per query, few queries in reference tiles); each tile's block forms the query's hash again
-static int launch_edit_dist(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Xr, int64_t ldr,
-                            const int64_t* Lr, int64_t nr, int max_r, unsigned char* dist, hipStream_t st) {
-    int tile;
-    const dim3 grid = edit_dist_grid(nq, nr, &tile);
-    return zlaunch(edit_dist_kernel, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, dist);
-}
-
 int edit_launch_head(const char* what, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Lr, int64_t nr, int max_r, int64_t* head, hipStream_t st) {
     return zlaunch(edit_head_kernel, dim3(1), 256, 0, st, what, Lq, (int)nq, max_q, Lr, (int)nr, max_r, head);
 }
 
-int edit_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                   uint8_t* dist, hipStream_t st) {
-    const char* what = "edit_distances";
-    EditSide Q, R;
-    SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
-    SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
-    SLNLP_CHECK_ARG(dist, "%s: null pointer (dist)", what);
-    SLNLP_TRY(edit_check_pairs(what, nq, nr));
-    const Span in[4] = {Q.x, Q.l, R.x, R.l};
-    const Span out[1] = {{dist, (size_t)nq * (size_t)nr, "dist"}};
-    SLNLP_TRY(check_no_overlap(what, out, in));
-    return launch_edit_dist(what, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, (unsigned char*)dist, st);
-}
-
-int edit_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                  const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows,
-                  int32_t* nbr, hipStream_t st) {
-    const char* what = "edit_knn_rows";
-    EditSide Q, R;
-    SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
-    SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
-    SLNLP_CHECK_ARG(scratch && head && rows && nbr, "%s: null pointer (scratch, head, rows or nbr)", what);
-    SLNLP_TRY(edit_check_pairs(what, nq, nr));
-    SLNLP_CHECK_ARG(k >= 1 && k <= SLNLP_EDIT_MAX_K, "%s: k=%ld outside 1..%d", what, (long)k, SLNLP_EDIT_MAX_K);
-    SLNLP_CHECK_ARG(radius >= 0 && radius <= SLNLP_EDIT_MAX_LEN, "%s: radius=%ld outside 0..%d", what, (long)radius, SLNLP_EDIT_MAX_LEN);
-    const size_t pairs = (size_t)nq * (size_t)nr;
-    SLNLP_TRY(check_scratch(what, scratch, scratch_bytes, pairs, nq, 0, 0));
-    SLNLP_CHECK_ARG((((uintptr_t)head | (uintptr_t)exclude) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)nbr) & 3) == 0,
-                    "%s: misaligned pointer (head, exclude: 8 bytes; rows, nbr: 4 bytes)", what);
-    const Span in[5] = {Q.x, Q.l, R.x, R.l, {exclude, (size_t)nq * 8, "exclude"}};
-    const Span out[4] = {{scratch, pairs, "scratch"}, {head, SLNLP_EDIT_HEAD_BYTES, "head"}, {rows, (size_t)nq * 16, "rows"},
-                         {nbr, (size_t)nq * (size_t)k * 8, "nbr"}};
-    SLNLP_TRY(check_no_overlap(what, out, in));
-    unsigned char* dist = (unsigned char*)scratch;
-    SLNLP_TRY(launch_edit_dist("edit_knn_distances", Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, dist, st));
-    SLNLP_TRY(zlaunch(edit_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, "edit_knn_select", (const unsigned char*)dist, Lq, exclude, (int)nq,
-                      (int)nr, Q.max_len, (int)k, (int)radius, (int*)rows, (int*)nbr));
-    return edit_launch_head("edit_knn_head", Lq, nq, Q.max_len, Lr, nr, R.max_len, head, st);
+// what this search states: a uint8 matrix, the distances 0 .. 64
+static EditSearch edit_search(const char* what) {
+    return EditSearch{what, "edit_knn_distances", "edit_knn_select", "edit_knn_head", 1, SLNLP_EDIT_MAX_LEN, "64", Span{}};
 }
 
 int edit_launch_logp(const char* what, const char* what_head, int bound, int unit, const int32_t* nbr, const int32_t* rows, const int64_t* Lq,
@@ -311,34 +197,40 @@ int edit_launch_logp(const char* what, const char* what_head, int bound, int uni
     return zlaunch(edit_bad_kernel, dim3(1), 256, 0, st, what_head, (const int*)nbr, (const int*)rows, yr, (int)nq, (int)nr, (int)k, (int)V, bound, head);
 }
 
-int edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
-                  int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior, float* logp, int64_t ld,
-                  int64_t* head, hipStream_t st) {
-    return edit_launch_logp("edit_knn_logp", "edit_knn_logp_head", SLNLP_EDIT_MAX_LEN, 1, nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau, normalize, lam,
-                            prior, logp, ld, head, st);
-}
-
 }  // namespace slnlp
 
 extern "C" int slnlp_edit_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
                                     int64_t nr, uint8_t* dist, void* stream) {
-    return slnlp::edit_distances(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, dist, (hipStream_t)stream);
+    using namespace slnlp;
+    const hipStream_t st = (hipStream_t)stream;
+    const EditSearch s = edit_search("edit_distances");
+    EditSide Q, R;
+    SLNLP_TRY(edit_check_side(s.what, "query", Xq, ldq, Lq, nq, SLNLP_EDIT_MAX_LEN, &Q));
+    SLNLP_TRY(edit_check_side(s.what, "reference", Xr, ldr, Lr, nr, SLNLP_EDIT_MAX_LEN, &R));
+    return edit_search_distances(s, Q, R, dist,
+                                 [&](const char* what, void* d) { return edit_launch_dist(edit_dist_kernel, what, Q, R, (unsigned char*)d, st); });
 }
-extern "C" int64_t slnlp_edit_knn_scratch_bytes(int64_t nq, int64_t nr) {
-    if (nq < 1 || nq > SLNLP_EDIT_MAX_ROWS || nr < 1 || nr > SLNLP_EDIT_MAX_ROWS || nq > SLNLP_EDIT_MAX_PAIRS / nr) {
-        slnlp::set_error("edit_knn_scratch_bytes: %ld x %ld pairs: both counts lie in 1..%d and at most %ld pairs are formed per call", (long)nq,
-                         (long)nr, SLNLP_EDIT_MAX_ROWS, (long)SLNLP_EDIT_MAX_PAIRS);
-        return -1;
-    }
-    return nq * nr;
-}
+extern "C" int64_t slnlp_edit_knn_scratch_bytes(int64_t nq, int64_t nr) { return slnlp::edit_scratch_bytes("edit_knn_scratch_bytes", nq, nr, 1); }
 extern "C" int slnlp_edit_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
                                    int64_t nr, const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head,
                                    int32_t* rows, int32_t* nbr, void* stream) {
-    return slnlp::edit_knn_rows(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, (hipStream_t)stream);
+    using namespace slnlp;
+    const hipStream_t st = (hipStream_t)stream;
+    const EditSearch s = edit_search("edit_knn_rows");
+    EditSide Q, R;
+    SLNLP_TRY(edit_check_side(s.what, "query", Xq, ldq, Lq, nq, SLNLP_EDIT_MAX_LEN, &Q));
+    SLNLP_TRY(edit_check_side(s.what, "reference", Xr, ldr, Lr, nr, SLNLP_EDIT_MAX_LEN, &R));
+    return edit_search_rows(
+        s, Q, R, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, st,
+        [&](const char* what, void* d) { return edit_launch_dist(edit_dist_kernel, what, Q, R, (unsigned char*)d, st); },
+        [&](const char* what, void* d) {
+            return zlaunch(edit_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, what, (const unsigned char*)d, Lq, exclude, (int)nq, (int)nr,
+                           Q.max_len, (int)k, (int)radius, (int*)rows, (int*)nbr);
+        });
 }
 extern "C" int slnlp_edit_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
                                    int64_t k, int64_t V, int weights, double tau, int normalize, double lam, const double* prior, float* logp, int64_t ld,
                                    int64_t* head, void* stream) {
-    return slnlp::edit_knn_logp(nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau, normalize, lam, prior, logp, ld, head, (hipStream_t)stream);
+    return slnlp::edit_launch_logp("edit_knn_logp", "edit_knn_logp_head", SLNLP_EDIT_MAX_LEN, 1, nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau,
+                                   normalize, lam, prior, logp, ld, head, (hipStream_t)stream);
 }

@@ -1,7 +1,11 @@
-// edit_shared.hpp -- what the two neighbour searches share: edit_knn.hip (unit-cost Levenshtein, a uint8 matrix, the distances
-// 0 .. 64) and field_knn.hip (the phonology-weighted distance, a uint16 matrix, the distances 0 .. 64 F).  The selection body is
-// generic over the matrix element, its "none" value and the number of bins; the head and the votes live in edit_knn.hip and take
-// the distance bound and the unit as arguments.  include/slnlp.h states the definitions.
+// edit_shared.hpp -- what the three neighbour searches share: edit_knn.hip (unit-cost Levenshtein over rows of up to 64 frames, a
+// uint8 matrix), edit_long.hip (the same distance over rows of up to 512 frames, a uint16 matrix) and field_knn.hip (the
+// phonology-weighted distance, a uint16 matrix, the distances 0 .. 64 F).  Device side: the selection body, generic over the matrix
+// element, its "none" value and the number of bins.  Host side: the checks of a side, of the pairs and of the scratch size, the grid
+// of a distance launch (and the launch itself of the two unit-cost ones), and THE SHELL of the two kinds of call --
+// edit_search_distances and edit_search_rows hold every check behind the sides and the order of the launches; a search states its
+// names, its element width and its distance bound (EditSearch) and hands in the callables that launch its own kernels.  The head and
+// the votes live in edit_knn.hip and take the distance bound and the unit as arguments.  include/slnlp.h states the definitions.
 #pragma once
 #include <limits.h>
 
@@ -103,19 +107,37 @@ __device__ __forceinline__ void edit_select_generic(const T* __restrict__ dist, 
 
 // ------------------------------------------------------------------------------------------------------- host side ----
 struct EditSide {
+    const int64_t *X, *L;
+    int64_t ld, n;
     Span x, l;
     int max_len;
 };
-// one side's rows: n in 1..INT_MAX, ld >= 1 and addressable, alignment; the bytes that may be read
-static inline int edit_check_side(const char* what, const char* side, const int64_t* X, int64_t ld, const int64_t* L, int64_t n, EditSide* out) {
+// one side's rows: n in 1..INT_MAX, ld >= 1 and addressable, alignment; a usable row has at most min(bound, ld) tokens, and only
+// they are read: the bytes that may be
+static inline int edit_check_side(const char* what, const char* side, const int64_t* X, int64_t ld, const int64_t* L, int64_t n, int64_t bound,
+                                  EditSide* out) {
     SLNLP_CHECK_ARG(X && L, "%s: null pointer (%s rows)", what, side);
     SLNLP_CHECK_ARG(n >= 1 && n <= SLNLP_EDIT_MAX_ROWS, "%s: %s rows n=%ld outside 1..%d", what, side, (long)n, SLNLP_EDIT_MAX_ROWS);
     SLNLP_CHECK_ARG(ld >= 1 && ld <= INT64_MAX / 8 / n, "%s: %s row stride %ld times %ld rows is no addressable matrix", what, side, (long)ld, (long)n);
     SLNLP_CHECK_ARG((((uintptr_t)X | (uintptr_t)L) & 7) == 0, "%s: misaligned pointer (%s rows: 8 bytes)", what, side);
-    out->max_len = ld < SLNLP_EDIT_MAX_LEN ? (int)ld : SLNLP_EDIT_MAX_LEN;
-    out->x = Span{X, ((size_t)(n - 1) * (size_t)ld + (size_t)out->max_len) * 8, side};
-    out->l = Span{L, (size_t)n * 8, side};
+    const int max_len = (int)(ld < bound ? ld : bound);
+    *out = EditSide{X, L, ld, n, Span{X, ((size_t)(n - 1) * (size_t)ld + (size_t)max_len) * 8, side}, Span{L, (size_t)n * 8, side}, max_len};
     return 0;
+}
+// width: the bytes of a matrix element, 1 or 2
+static inline int edit_check_pairs(const char* what, int64_t nq, int64_t nr, int width) {
+    SLNLP_CHECK_ARG(nq <= SLNLP_EDIT_MAX_PAIRS / nr, "%s: %ld x %ld pairs, at most %ld (%s each) are formed per call", what, (long)nq, (long)nr,
+                    (long)SLNLP_EDIT_MAX_PAIRS, width == 1 ? "one byte" : "two bytes");
+    return 0;
+}
+// the body of the three slnlp_*_knn_scratch_bytes
+static inline int64_t edit_scratch_bytes(const char* what, int64_t nq, int64_t nr, int width) {
+    if (nq < 1 || nq > SLNLP_EDIT_MAX_ROWS || nr < 1 || nr > SLNLP_EDIT_MAX_ROWS || nq > SLNLP_EDIT_MAX_PAIRS / nr) {
+        set_error("%s: %ld x %ld pairs: both counts lie in 1..%d and at most %ld pairs are formed per call", what, (long)nq, (long)nr,
+                  SLNLP_EDIT_MAX_ROWS, (long)SLNLP_EDIT_MAX_PAIRS);
+        return -1;
+    }
+    return nq * nr * width;
 }
 static inline int edit_blocks(int64_t n) { return (int)(n < EDIT_MAX_BLOCKS ? n : EDIT_MAX_BLOCKS); }
 // the grid of a distance launch: a block per query, and with fewer than EDIT_FILL queries the references in y tiles (a multiple of
@@ -131,9 +153,66 @@ static inline dim3 edit_dist_grid(int64_t nq, int64_t nr, int* tile_out) {
     return dim3(edit_blocks(nq), (unsigned)tiles);
 }
 
+// the distance launch of the two unit-cost searches (edit_dist.hpp's body over T); each tile's block forms the query's hash again
+template <class Kernel, class T>
+static inline int edit_launch_dist(Kernel kernel, const char* what, const EditSide& Q, const EditSide& R, T* dist, hipStream_t st) {
+    int tile;
+    const dim3 grid = edit_dist_grid(Q.n, R.n, &tile);
+    return zlaunch(kernel, grid, 256, 0, st, what, Q.X, (long)Q.ld, Q.L, (int)Q.n, R.X, (long)R.ld, R.L, (int)R.n, Q.max_len, R.max_len, tile, dist);
+}
+
+// ----------------------------------------------------------------------------------------------------------- shell ----
+int edit_launch_head(const char* what, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Lr, int64_t nr, int max_r, int64_t* head, hipStream_t st);
+
+// what a search states about itself: its name in every refusal and the names of its three launches, the bytes of a matrix element
+// (1 or 2), its largest distance and how the radius refusal words it, and one more input span (the code table; {}: none)
+struct EditSearch {
+    const char *what, *what_dist, *what_select, *what_head;
+    int width;
+    int64_t bound;
+    const char* bound_says;
+    Span extra;
+};
+
+// *_distances behind the sides (and the table): dist, the pairs, the overlaps; then launch(what, dist) fills the matrix
+template <class Launch>
+static inline int edit_search_distances(const EditSearch& s, const EditSide& Q, const EditSide& R, void* dist, Launch launch) {
+    const char* what = s.what;
+    SLNLP_CHECK_ARG(dist, "%s: null pointer (dist)", what);
+    SLNLP_CHECK_ARG(((uintptr_t)dist & (uintptr_t)(s.width - 1)) == 0, "%s: misaligned pointer (dist: %d bytes)", what, s.width);
+    SLNLP_TRY(edit_check_pairs(what, Q.n, R.n, s.width));
+    const Span in[5] = {Q.x, Q.l, R.x, R.l, s.extra};
+    const Span out[1] = {{dist, (size_t)Q.n * (size_t)R.n * s.width, "dist"}};
+    SLNLP_TRY(check_no_overlap(what, out, in));
+    return launch(what, dist);
+}
+
+// *_knn_rows behind the sides (and the table): null pointers, pairs, k, radius, scratch, alignment, overlaps; then
+// distances(what_dist, matrix) into the scratch, select(what_select, matrix) and the head
+template <class Distances, class Select>
+static inline int edit_search_rows(const EditSearch& s, const EditSide& Q, const EditSide& R, const int64_t* exclude, int64_t k, int64_t radius,
+                                   void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st,
+                                   Distances distances, Select select) {
+    const char* what = s.what;
+    SLNLP_CHECK_ARG(scratch && head && rows && nbr, "%s: null pointer (scratch, head, rows or nbr)", what);
+    SLNLP_TRY(edit_check_pairs(what, Q.n, R.n, s.width));
+    SLNLP_CHECK_ARG(k >= 1 && k <= SLNLP_EDIT_MAX_K, "%s: k=%ld outside 1..%d", what, (long)k, SLNLP_EDIT_MAX_K);
+    SLNLP_CHECK_ARG(radius >= 0 && radius <= s.bound, "%s: radius=%ld outside 0..%s", what, (long)radius, s.bound_says);
+    const size_t bytes = (size_t)Q.n * (size_t)R.n * s.width;
+    SLNLP_TRY(check_scratch(what, scratch, scratch_bytes, bytes, Q.n, 0, s.width));
+    SLNLP_CHECK_ARG((((uintptr_t)head | (uintptr_t)exclude) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)nbr) & 3) == 0,
+                    "%s: misaligned pointer (head, exclude: 8 bytes; rows, nbr: 4 bytes)", what);
+    const Span in[6] = {Q.x, Q.l, R.x, R.l, {exclude, (size_t)Q.n * 8, "exclude"}, s.extra};
+    const Span out[4] = {{scratch, bytes, "scratch"}, {head, SLNLP_EDIT_HEAD_BYTES, "head"}, {rows, (size_t)Q.n * 16, "rows"},
+                         {nbr, (size_t)Q.n * (size_t)k * 8, "nbr"}};
+    SLNLP_TRY(check_no_overlap(what, out, in));
+    SLNLP_TRY(distances(s.what_dist, scratch));
+    SLNLP_TRY(select(s.what_select, scratch));
+    return edit_launch_head(s.what_head, Q.L, Q.n, Q.max_len, R.L, R.n, R.max_len, head, st);
+}
+
 // edit_knn.hip: the head of a search, and the votes with their head, for distances 0 .. bound in units of `unit` fields (the
 // unit-cost search: 64 and 1).  `what` names the entry point in every message, what_head the second launch.
-int edit_launch_head(const char* what, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Lr, int64_t nr, int max_r, int64_t* head, hipStream_t st);
 int edit_launch_logp(const char* what, const char* what_head, int bound, int unit, const int32_t* nbr, const int32_t* rows, const int64_t* Lq,
                      const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr, int64_t k, int64_t V, int weights, double tau, int normalize,
                      double lam, const double* prior, float* logp, int64_t ld, int64_t* head, hipStream_t st);

@@ -22,7 +22,10 @@
 //                 unweighted kernels are not routed through it: the cost policy is a template argument of the one body.
 //   field_select  edit_shared.hpp's selection body over the uint16 matrix with 64 F + 1 <= 1025 bins.
 //   the head and the votes are edit_knn.hip's kernels with the bound 64 F and the unit F.
+// Host side: this file checks the table and the weights (field_check_metric) and states the search (its names, two bytes a pair, the
+// bound 64 F or 64 W, the table as one more input); every other check and the launch order are edit_shared.hpp's shell.
 #include <limits.h>
+#include <stdio.h>
 
 #include "common.hpp"
 #include "edit_shared.hpp"
@@ -154,177 +157,125 @@ __device__ __forceinline__ void field_select_body(const unsigned short* __restri
 SLNLP_ZKERNEL(field_select_kernel, 256, field_select_body)
 
 // ------------------------------------------------------------------------------------------------------- host side ----
-// the table and the gap: F in 1..16, Vt in 1..INT32_MAX, gap in 1..F, codes 4-byte aligned; the bytes that are read
-static int field_check_table(const char* what, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, Span* out) {
+// what a field search checks behind its sides and then states: the table -- codes 4-byte aligned, F in 1..16, Vt in 1..INT32_MAX --
+// and the metric's unit, which bounds the gap (1..unit) and the distances (0..64 unit).  Unweighted (fweights unused) the unit is F;
+// weighted, fweights is a HOST array of F ints in 0..16 and the unit their sum W in 1..16.
+struct FieldMetric {
+    const int32_t* codes;
+    int64_t Vt, F, gap;
+    bool weighted;
+    FieldWeights fw;
+    int unit;
+    char says[32];                                           // of the radius refusal: "64 F=384"
+};
+static int field_check_metric(const char* what, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, bool weighted, int64_t gap,
+                              FieldMetric* out, Span* table) {
     SLNLP_CHECK_ARG(codes, "%s: null pointer (codes)", what);
+    if (weighted) SLNLP_CHECK_ARG(fweights, "%s: null pointer (fweights: a host array of F weights)", what);
     SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
     SLNLP_CHECK_ARG(Vt >= 1 && Vt <= INT_MAX, "%s: Vt=%ld outside 1..%d", what, (long)Vt, INT_MAX);
-    SLNLP_CHECK_ARG(gap >= 1 && gap <= F, "%s: gap=%ld outside 1..F=%ld", what, (long)gap, (long)F);
-    SLNLP_CHECK_ARG(((uintptr_t)codes & 3) == 0, "%s: misaligned pointer (codes: 4 bytes)", what);
-    *out = Span{codes, (size_t)Vt * (size_t)F * 4, "codes"};
-    return 0;
-}
-// the weighted metric's table, weights and gap: fweights a HOST array of F ints in 0..16 whose sum W lies in 1..16, gap in 1..W
-static int field_check_weighted(const char* what, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, Span* out,
-                                FieldWeights* fw, int* W_out) {
-    SLNLP_CHECK_ARG(codes, "%s: null pointer (codes)", what);
-    SLNLP_CHECK_ARG(fweights, "%s: null pointer (fweights: a host array of F weights)", what);
-    SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
-    SLNLP_CHECK_ARG(Vt >= 1 && Vt <= INT_MAX, "%s: Vt=%ld outside 1..%d", what, (long)Vt, INT_MAX);
-    int W = 0;
-    *fw = FieldWeights{};
-    for (int f = 0; f < F; ++f) {
-        SLNLP_CHECK_ARG(fweights[f] >= 0 && fweights[f] <= SLNLP_FIELD_MAX_WEIGHT, "%s: fweights[%d]=%d outside 0..%d", what, f, (int)fweights[f],
-                        SLNLP_FIELD_MAX_WEIGHT);
-        fw->w[f] = fweights[f];
-        W += fweights[f];
+    *out = FieldMetric{codes, Vt, F, gap, weighted, FieldWeights{}, (int)F, ""};
+    if (weighted) {
+        int W = 0;
+        for (int f = 0; f < F; ++f) {
+            SLNLP_CHECK_ARG(fweights[f] >= 0 && fweights[f] <= SLNLP_FIELD_MAX_WEIGHT, "%s: fweights[%d]=%d outside 0..%d", what, f, (int)fweights[f],
+                            SLNLP_FIELD_MAX_WEIGHT);
+            out->fw.w[f] = fweights[f];
+            W += fweights[f];
+        }
+        SLNLP_CHECK_ARG(W >= 1 && W <= SLNLP_FIELD_MAX_WEIGHT, "%s: the weights sum to W=%d outside 1..%d", what, W, SLNLP_FIELD_MAX_WEIGHT);
+        out->unit = W;
     }
-    SLNLP_CHECK_ARG(W >= 1 && W <= SLNLP_FIELD_MAX_WEIGHT, "%s: the weights sum to W=%d outside 1..%d", what, W, SLNLP_FIELD_MAX_WEIGHT);
-    SLNLP_CHECK_ARG(gap >= 1 && gap <= W, "%s: gap=%ld outside 1..W=%d", what, (long)gap, W);
+    const char* unit_name = weighted ? "W" : "F";
+    SLNLP_CHECK_ARG(gap >= 1 && gap <= out->unit, "%s: gap=%ld outside 1..%s=%d", what, (long)gap, unit_name, out->unit);
     SLNLP_CHECK_ARG(((uintptr_t)codes & 3) == 0, "%s: misaligned pointer (codes: 4 bytes)", what);
-    *out = Span{codes, (size_t)Vt * (size_t)F * 4, "codes"};
-    *W_out = W;
+    snprintf(out->says, sizeof out->says, "64 %s=%d", unit_name, SLNLP_EDIT_MAX_LEN * out->unit);
+    *table = Span{codes, (size_t)Vt * (size_t)F * 4, "codes"};
     return 0;
 }
-static int field_check_pairs(const char* what, int64_t nq, int64_t nr) {
-    SLNLP_CHECK_ARG(nq <= SLNLP_EDIT_MAX_PAIRS / nr, "%s: %ld x %ld pairs, at most %ld (two bytes each) are formed per call", what, (long)nq, (long)nr,
-                    (long)SLNLP_EDIT_MAX_PAIRS);
-    return 0;
-}
-static int launch_field_dist(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, int max_q, const int64_t* Xr, int64_t ldr,
-                             const int64_t* Lr, int64_t nr, int max_r, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, unsigned short* dist,
-                             hipStream_t st, const FieldWeights* fw = nullptr, int W = 0) {
+static int launch_field_dist(const char* what, const EditSide& Q, const EditSide& R, const FieldMetric& m, unsigned short* dist, hipStream_t st) {
     int tile;
-    const dim3 grid = edit_dist_grid(nq, nr, &tile);
-    const int groups = (int)(F + 3) / 4;                     // 1..4: the kernel built for that many groups of four fields
-    if (fw) {                                                // the weighted sibling: the weights by value behind the same arguments
+    const dim3 grid = edit_dist_grid(Q.n, R.n, &tile);
+    const int groups = (int)(m.F + 3) / 4;                   // 1..4: the kernel built for that many groups of four fields
+    if (m.weighted) {                                        // the weighted sibling: the weights by value behind the same arguments
         auto kern = groups == 1 ? field_dist_w_kernel_g1 : groups == 2 ? field_dist_w_kernel_g2 : groups == 3 ? field_dist_w_kernel_g3 : field_dist_w_kernel_g4;
-        return zlaunch(kern, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, (const int*)codes,
-                       (int)F, (int)Vt, (int)gap, dist, *fw, W);
+        return zlaunch(kern, grid, 256, 0, st, what, Q.X, (long)Q.ld, Q.L, (int)Q.n, R.X, (long)R.ld, R.L, (int)R.n, Q.max_len, R.max_len, tile,
+                       (const int*)m.codes, (int)m.F, (int)m.Vt, (int)m.gap, dist, m.fw, m.unit);
     }
     auto kern = groups == 1 ? field_dist_kernel_g1 : groups == 2 ? field_dist_kernel_g2 : groups == 3 ? field_dist_kernel_g3 : field_dist_kernel_g4;
-    return zlaunch(kern, grid, 256, 0, st, what, Xq, (long)ldq, Lq, (int)nq, Xr, (long)ldr, Lr, (int)nr, max_q, max_r, tile, (const int*)codes, (int)F,
-                   (int)Vt, (int)gap, dist);
+    return zlaunch(kern, grid, 256, 0, st, what, Q.X, (long)Q.ld, Q.L, (int)Q.n, R.X, (long)R.ld, R.L, (int)R.n, Q.max_len, R.max_len, tile,
+                   (const int*)m.codes, (int)m.F, (int)m.Vt, (int)m.gap, dist);
 }
 
-// weighted false: the unit metric and its kernels (fweights unused); true: the weighted sibling (fweights a host array)
-static int field_distances_any(const char* what, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr,
+// the two kinds of call under either metric; names: the entry point and its three launches (*_distances: the entry point alone)
+struct FieldNames {
+    const char *what, *dist, *select, *head;
+};
+static int field_distances_any(const FieldNames& nm, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr,
                                const int64_t* Lr, int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, bool weighted,
                                int64_t gap, uint16_t* dist, hipStream_t st) {
     EditSide Q, R;
+    FieldMetric m;
     Span table;
-    FieldWeights fw;
-    int W = 0;
-    SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
-    SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
-    if (weighted) SLNLP_TRY(field_check_weighted(what, codes, Vt, F, fweights, gap, &table, &fw, &W));
-    else SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
-    SLNLP_CHECK_ARG(dist, "%s: null pointer (dist)", what);
-    SLNLP_CHECK_ARG(((uintptr_t)dist & 1) == 0, "%s: misaligned pointer (dist: 2 bytes)", what);
-    SLNLP_TRY(field_check_pairs(what, nq, nr));
-    const Span in[5] = {Q.x, Q.l, R.x, R.l, table};
-    const Span out[1] = {{dist, (size_t)nq * (size_t)nr * 2, "dist"}};
-    SLNLP_TRY(check_no_overlap(what, out, in));
-    return launch_field_dist(what, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, (unsigned short*)dist, st,
-                             weighted ? &fw : nullptr, W);
-}
-int field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                    const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, hipStream_t st) {
-    return field_distances_any("field_distances", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, nullptr, false, gap, dist, st);
-}
-int field_distances_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                      const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, uint16_t* dist, hipStream_t st) {
-    return field_distances_any("field_distances_w", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, true, gap, dist, st);
+    SLNLP_TRY(edit_check_side(nm.what, "query", Xq, ldq, Lq, nq, SLNLP_EDIT_MAX_LEN, &Q));
+    SLNLP_TRY(edit_check_side(nm.what, "reference", Xr, ldr, Lr, nr, SLNLP_EDIT_MAX_LEN, &R));
+    SLNLP_TRY(field_check_metric(nm.what, codes, Vt, F, fweights, weighted, gap, &m, &table));
+    const EditSearch s{nm.what, nm.dist, nm.select, nm.head, 2, SLNLP_EDIT_MAX_LEN * (int64_t)m.unit, m.says, table};
+    return edit_search_distances(s, Q, R, dist, [&](const char* what, void* d) { return launch_field_dist(what, Q, R, m, (unsigned short*)d, st); });
 }
 
-// the search under either metric: `unit` is F, or W with weights, and names itself in the radius message
-static int field_knn_rows_any(const char* what, const char* what_dist, const char* what_select, const char* what_head, const int64_t* Xq, int64_t ldq,
-                              const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr, const int32_t* codes,
-                              int64_t Vt, int64_t F, const int32_t* fweights, bool weighted, int64_t gap, const int64_t* exclude, int64_t k,
-                              int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
+static int field_knn_rows_any(const FieldNames& nm, const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr,
+                              const int64_t* Lr, int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, bool weighted,
+                              int64_t gap, const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head,
+                              int32_t* rows, int32_t* nbr, hipStream_t st) {
     EditSide Q, R;
+    FieldMetric m;
     Span table;
-    FieldWeights fw;
-    int W = 0;
-    SLNLP_TRY(edit_check_side(what, "query", Xq, ldq, Lq, nq, &Q));
-    SLNLP_TRY(edit_check_side(what, "reference", Xr, ldr, Lr, nr, &R));
-    if (weighted) SLNLP_TRY(field_check_weighted(what, codes, Vt, F, fweights, gap, &table, &fw, &W));
-    else SLNLP_TRY(field_check_table(what, codes, Vt, F, gap, &table));
-    SLNLP_CHECK_ARG(scratch && head && rows && nbr, "%s: null pointer (scratch, head, rows or nbr)", what);
-    SLNLP_TRY(field_check_pairs(what, nq, nr));
-    SLNLP_CHECK_ARG(k >= 1 && k <= SLNLP_EDIT_MAX_K, "%s: k=%ld outside 1..%d", what, (long)k, SLNLP_EDIT_MAX_K);
-    const int64_t bound = SLNLP_EDIT_MAX_LEN * (weighted ? (int64_t)W : F);
-    SLNLP_CHECK_ARG(radius >= 0 && radius <= bound, "%s: radius=%ld outside 0..64 %s=%ld", what, (long)radius, weighted ? "W" : "F", (long)bound);
-    const size_t pairs = (size_t)nq * (size_t)nr;
-    SLNLP_TRY(check_scratch(what, scratch, scratch_bytes, pairs * 2, nq, 0, 2));
-    SLNLP_CHECK_ARG((((uintptr_t)head | (uintptr_t)exclude) & 7) == 0 && (((uintptr_t)rows | (uintptr_t)nbr) & 3) == 0,
-                    "%s: misaligned pointer (head, exclude: 8 bytes; rows, nbr: 4 bytes)", what);
-    const Span in[6] = {Q.x, Q.l, R.x, R.l, {exclude, (size_t)nq * 8, "exclude"}, table};
-    const Span out[4] = {{scratch, pairs * 2, "scratch"}, {head, SLNLP_EDIT_HEAD_BYTES, "head"}, {rows, (size_t)nq * 16, "rows"},
-                         {nbr, (size_t)nq * (size_t)k * 8, "nbr"}};
-    SLNLP_TRY(check_no_overlap(what, out, in));
-    unsigned short* dist = (unsigned short*)scratch;
-    SLNLP_TRY(launch_field_dist(what_dist, Xq, ldq, Lq, nq, Q.max_len, Xr, ldr, Lr, nr, R.max_len, codes, Vt, F, gap, dist, st, weighted ? &fw : nullptr, W));
-    SLNLP_TRY(zlaunch(field_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, what_select, (const unsigned short*)dist, Lq, exclude, (int)nq,
-                      (int)nr, Q.max_len, (int)k, (int)radius, (int)bound + 1, (int*)rows, (int*)nbr));
-    return edit_launch_head(what_head, Lq, nq, Q.max_len, Lr, nr, R.max_len, head, st);
-}
-int field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                   const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k, int64_t radius, void* scratch,
-                   int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
-    return field_knn_rows_any("field_knn_rows", "field_knn_distances", "field_knn_select", "field_knn_head", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F,
-                              nullptr, false, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, st);
-}
-int field_knn_rows_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr, int64_t nr,
-                     const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, const int64_t* exclude, int64_t k, int64_t radius,
-                     void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, hipStream_t st) {
-    return field_knn_rows_any("field_knn_rows_w", "field_knn_distances_w", "field_knn_select_w", "field_knn_head_w", Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes,
-                              Vt, F, fweights, true, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, st);
+    SLNLP_TRY(edit_check_side(nm.what, "query", Xq, ldq, Lq, nq, SLNLP_EDIT_MAX_LEN, &Q));
+    SLNLP_TRY(edit_check_side(nm.what, "reference", Xr, ldr, Lr, nr, SLNLP_EDIT_MAX_LEN, &R));
+    SLNLP_TRY(field_check_metric(nm.what, codes, Vt, F, fweights, weighted, gap, &m, &table));
+    const EditSearch s{nm.what, nm.dist, nm.select, nm.head, 2, SLNLP_EDIT_MAX_LEN * (int64_t)m.unit, m.says, table};
+    return edit_search_rows(
+        s, Q, R, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, st,
+        [&](const char* what, void* d) { return launch_field_dist(what, Q, R, m, (unsigned short*)d, st); },
+        [&](const char* what, void* d) {
+            return zlaunch(field_select_kernel, dim3(wave_rows_grid(nq)), 256, 0, st, what, (const unsigned short*)d, Lq, exclude, (int)nq, (int)nr,
+                           Q.max_len, (int)k, (int)radius, (int)s.bound + 1, (int*)rows, (int*)nbr);
+        });
 }
 
-int field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
-                   int64_t k, int64_t V, int64_t F, int weights, double tau, int normalize, double lam, const double* prior, float* logp, int64_t ld,
-                   int64_t* head, hipStream_t st) {
-    const char* what = "field_knn_logp";
-    SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
-    return edit_launch_logp(what, "field_knn_logp_head", (int)(SLNLP_EDIT_MAX_LEN * F), (int)F, nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau, normalize,
-                            lam, prior, logp, ld, head, st);
-}
 
 }  // namespace slnlp
 
 extern "C" int slnlp_field_distances(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
                                      int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, uint16_t* dist, void* stream) {
-    return slnlp::field_distances(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, gap, dist, (hipStream_t)stream);
+    return slnlp::field_distances_any({"field_distances"}, Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, nullptr, false, gap, dist, (hipStream_t)stream);
 }
 extern "C" int slnlp_field_distances_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
                                        int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap, uint16_t* dist,
                                        void* stream) {
-    return slnlp::field_distances_w(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, gap, dist, (hipStream_t)stream);
+    return slnlp::field_distances_any({"field_distances_w"}, Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, true, gap, dist, (hipStream_t)stream);
+}
+extern "C" int64_t slnlp_field_knn_scratch_bytes(int64_t nq, int64_t nr) { return slnlp::edit_scratch_bytes("field_knn_scratch_bytes", nq, nr, 2); }
+extern "C" int slnlp_field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
+                                    int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k,
+                                    int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, void* stream) {
+    return slnlp::field_knn_rows_any({"field_knn_rows", "field_knn_distances", "field_knn_select", "field_knn_head"}, Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes,
+                                     Vt, F, nullptr, false, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr, (hipStream_t)stream);
 }
 extern "C" int slnlp_field_knn_rows_w(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
                                       int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, const int32_t* fweights, int64_t gap,
                                       const int64_t* exclude, int64_t k, int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head,
                                       int32_t* rows, int32_t* nbr, void* stream) {
-    return slnlp::field_knn_rows_w(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, fweights, gap, exclude, k, radius, scratch, scratch_bytes, head, rows,
-                                   nbr, (hipStream_t)stream);
-}
-extern "C" int64_t slnlp_field_knn_scratch_bytes(int64_t nq, int64_t nr) {
-    if (nq < 1 || nq > SLNLP_EDIT_MAX_ROWS || nr < 1 || nr > SLNLP_EDIT_MAX_ROWS || nq > SLNLP_EDIT_MAX_PAIRS / nr) {
-        slnlp::set_error("field_knn_scratch_bytes: %ld x %ld pairs: both counts lie in 1..%d and at most %ld pairs are formed per call", (long)nq,
-                         (long)nr, SLNLP_EDIT_MAX_ROWS, (long)SLNLP_EDIT_MAX_PAIRS);
-        return -1;
-    }
-    return nq * nr * 2;
-}
-extern "C" int slnlp_field_knn_rows(const int64_t* Xq, int64_t ldq, const int64_t* Lq, int64_t nq, const int64_t* Xr, int64_t ldr, const int64_t* Lr,
-                                    int64_t nr, const int32_t* codes, int64_t Vt, int64_t F, int64_t gap, const int64_t* exclude, int64_t k,
-                                    int64_t radius, void* scratch, int64_t scratch_bytes, int64_t* head, int32_t* rows, int32_t* nbr, void* stream) {
-    return slnlp::field_knn_rows(Xq, ldq, Lq, nq, Xr, ldr, Lr, nr, codes, Vt, F, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr,
-                                 (hipStream_t)stream);
+    return slnlp::field_knn_rows_any({"field_knn_rows_w", "field_knn_distances_w", "field_knn_select_w", "field_knn_head_w"}, Xq, ldq, Lq, nq, Xr, ldr, Lr,
+                                     nr, codes, Vt, F, fweights, true, gap, exclude, k, radius, scratch, scratch_bytes, head, rows, nbr,
+                                     (hipStream_t)stream);
 }
 extern "C" int slnlp_field_knn_logp(const int32_t* nbr, const int32_t* rows, const int64_t* Lq, const int64_t* Lr, const int64_t* yr, int64_t nq, int64_t nr,
                                     int64_t k, int64_t V, int64_t F, int weights, double tau, int normalize, double lam, const double* prior, float* logp,
                                     int64_t ld, int64_t* head, void* stream) {
-    return slnlp::field_knn_logp(nbr, rows, Lq, Lr, yr, nq, nr, k, V, F, weights, tau, normalize, lam, prior, logp, ld, head, (hipStream_t)stream);
+    const char* what = "field_knn_logp";
+    SLNLP_CHECK_ARG(F >= 1 && F <= SLNLP_FIELD_MAX_FIELDS, "%s: F=%ld outside 1..%d", what, (long)F, SLNLP_FIELD_MAX_FIELDS);
+    return slnlp::edit_launch_logp(what, "field_knn_logp_head", (int)(SLNLP_EDIT_MAX_LEN * F), (int)F, nbr, rows, Lq, Lr, yr, nq, nr, k, V, weights, tau,
+                                   normalize, lam, prior, logp, ld, head, (hipStream_t)stream);
 }

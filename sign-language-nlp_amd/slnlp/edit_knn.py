@@ -26,6 +26,7 @@ LIMIT THAT REMAINS: the phonology-weighted search stays at 64 frames (its kernel
 LDS, which does not stretch to 512 positions) -- ``PhonoKNN`` and ``split_audit(field_codes=...)`` refuse ``max_len``.
 ``field_weights=`` gives every field an integer weight of its own (``slnlp.fit_field_weights`` fits them, slnlp/field_weights.py);
 without it every call is the one it was."""
+import collections
 import copy
 
 import numpy as np
@@ -104,29 +105,41 @@ def _on_stream(dev, body):
     return res
 
 
-def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, metric=None, max_len=None):
-    """``ops.edit_knn_rows`` -- or, with ``metric`` = (codes on the device, gap[, field weights or None]), ``ops.field_knn_rows``; or, with
-    ``max_len`` (65..512, never beside ``metric``), ``ops.edit_long_knn_rows`` -- over the queries in
-    ``query_chunks``; ``each(start, stop, buf)`` runs behind every chunk on the same stream.  One scratch and one buffer serve the
-    chunks of equal size.  The field metric and the long rows keep two bytes a pair and are chunked at half the pairs: the scratch
-    stays at 256 MiB."""
+# What ``_search`` needs of a neighbour search: ``width``, the bytes a pair takes in its distance matrix, and
+# ``rows(Xq, Lq, Xr, Lr, k, radius, exclude, buf, scratch)``, its ``ops.*_knn_rows`` bound to its metric's arguments
+Search = collections.namedtuple("Search", "width rows")
+
+
+def _bound(width, fn, *metric, **options):
+    def rows(Xq, Lq, Xr, Lr, k, radius, exclude, buf, scratch):
+        return fn(Xq, Lq, Xr, Lr, *metric, k, radius=radius, exclude=exclude, buf=buf, scratch=scratch, **options)
+    return Search(width, rows)
+
+
+def unit_search(max_len=None):
+    """``ops.edit_knn_rows``: one byte a pair -- with ``max_len`` (65..512) ``ops.edit_long_knn_rows``: two"""
+    return _bound(1, ops.edit_knn_rows) if max_len is None else _bound(2, ops.edit_long_knn_rows, max_len=max_len)
+
+
+def field_search(codes, gap, field_weights=None):
+    """``ops.field_knn_rows`` over ``codes`` (on the device): two bytes a pair"""
+    return _bound(2, ops.field_knn_rows, codes, gap=gap, field_weights=field_weights)
+
+
+def _search(Xq, Lq, Xr, Lr, k, radius, exclude, each, cap=None, search=None):
+    """``search.rows`` (a ``Search``; None: the unit-cost one) over the queries in ``query_chunks``; ``each(start, stop, buf)`` runs
+    behind every chunk on the same stream.  One scratch and one buffer serve the chunks of equal size.  A search of two bytes a pair
+    (the field metric, the long rows) is chunked at half the pairs: the scratch stays at 256 MiB."""
+    search = unit_search() if search is None else search
     nq, nr = int(Xq.shape[0]), int(Xr.shape[0])
     cap = SCRATCH_PAIRS if cap is None else cap
-    width = 1 if metric is None and max_len is None else 2
-    chunks = query_chunks(nq, nr, max(1, cap // width))
-    scratch = torch.empty(width * (chunks[0][1] - chunks[0][0]) * nr, dtype=torch.uint8, device=Xq.device)
+    chunks = query_chunks(nq, nr, max(1, cap // search.width))
+    scratch = torch.empty(search.width * (chunks[0][1] - chunks[0][0]) * nr, dtype=torch.uint8, device=Xq.device)
     buf = None
     for a, b in chunks:
         if buf is None or buf["shape"][0] != b - a:
             buf = ops.edit_knn_buffers(b - a, k, Xq.device)
-        ex = None if exclude is None else exclude[a:b]
-        if max_len is not None:
-            ops.edit_long_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, max_len=max_len, radius=radius, exclude=ex, buf=buf, scratch=scratch)
-        elif metric is None:
-            ops.edit_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius=radius, exclude=ex, buf=buf, scratch=scratch)
-        else:
-            ops.field_knn_rows(Xq[a:b], Lq[a:b], Xr, Lr, metric[0], k, gap=metric[1], radius=radius, exclude=ex, buf=buf, scratch=scratch,
-                               field_weights=metric[2] if len(metric) > 2 else None)
+        search.rows(Xq[a:b], Lq[a:b], Xr, Lr, k, radius, None if exclude is None else exclude[a:b], buf, scratch)
         each(a, b, buf)
 
 
@@ -260,9 +273,9 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
     def _on_stream(self, body):
         return _on_stream(self._ids.device, body)
 
-    def _metric(self):
-        """What ``_search`` measures with: None, the unit-cost distance"""
-        return None
+    def _searcher(self):
+        """What ``_search`` runs: the unit-cost search of the fitted ``max_len``"""
+        return unit_search(self._max_len)
 
     def _vote(self, buf, Lq, **options):
         if self._max_len is not None:
@@ -291,7 +304,7 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
 
         def vote(a, b, buf):
             self._vote(buf, Lq[a:b], weights=weights, tau=tau, normalize=normalize, lam=lam, out=out[a:b])
-        _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._metric(), self._max_len)
+        _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, vote, self._cap, self._searcher())
         return out, yq
 
     # ------------------------------------------------------------ neighbours
@@ -309,7 +322,7 @@ class EditKNN(LogProbJudge, ClassifierMixin, BaseEstimator):
         def body():
             Xq, Lq, _, exclude = self._queries(ds)
             _search(Xq, Lq, self._ids, self._lengths, k, 0, exclude, lambda a, b, buf: got.append(ops.edit_knn_download(buf)["nbr"].copy()), self._cap,
-                    self._metric(), self._max_len)
+                    self._searcher())
         self._on_stream(body)
         nbr = np.concatenate(got, axis=0)
         return nbr[:, :, 0].astype(np.int32), nbr[:, :, 1].astype(np.int64)
@@ -378,8 +391,8 @@ class PhonoKNN(EditKNN):
         self._gap, self.fields_, self._fweights, self.unit_ = gap, int(codes.shape[1]), fweights, unit
         return self
 
-    def _metric(self):
-        return self._codes, self._gap, self._fweights
+    def _searcher(self):
+        return field_search(self._codes, self._gap, self._fweights)
 
     def _vote(self, buf, Lq, **options):
         ops.field_knn_logp(buf, Lq, self._lengths, self._y, self._prior, self.unit_, **options)
@@ -446,7 +459,7 @@ def split_audit(train, test, radius=2, top=50, judge=None, device=None, *, field
         Xq, Lq = (Xr, Lr) if own else (up(test.ids), up(test.lengths))
         exclude = up(np.arange(len(train), dtype=np.int64)) if own else None
         _search(Xq, Lq, Xr, Lr, 1, radius, exclude, lambda a, b, buf: got.append({n: v.copy() for n, v in ops.edit_knn_download(buf).items()}),
-                metric=None if codes is None else (up(codes), gap, fweights), max_len=max_len)
+                search=unit_search(max_len) if codes is None else field_search(up(codes), gap, fweights))
     _on_stream(dev, body)
     rows, nbr = np.concatenate([g["rows"] for g in got]), np.concatenate([g["nbr"] for g in got])
     head = got[0]["head"].copy()

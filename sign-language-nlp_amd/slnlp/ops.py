@@ -1569,9 +1569,89 @@ def _edit_side(what, side, X, L):
     return n, int(X.stride(0)) if n > 1 else max(int(X.shape[1]), int(X.stride(0)))
 
 
-def _edit_pairs(what, nq, nr):
+def _edit_pairs(what, nq, nr, width):
+    says = "one byte" if width == 1 else "two bytes"
     if nq * nr > _lib.EDIT_MAX_PAIRS:
-        raise ValueError(f"{what}: {nq} x {nr} pairs, at most {_lib.EDIT_MAX_PAIRS} (one byte each) are formed per call: pass the queries in chunks")
+        raise ValueError(f"{what}: {nq} x {nr} pairs, at most {_lib.EDIT_MAX_PAIRS} ({says} each) are formed per call: pass the queries in chunks")
+
+
+def _knn_sides(what, Xq, Lq, Xr, Lr):
+    """Both sides of a neighbour search, the references on the queries' device -> (nq, ldq, nr, ldr, device)"""
+    nq, ldq = _edit_side(what, "query", Xq, Lq)
+    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
+        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
+    nr, ldr = _edit_side(what, "reference", Xr, Lr)
+    return nq, ldq, nr, ldr, Xq.device
+
+
+def _knn_distances(what, dtype, says, Xq, Lq, Xr, Lr, out, metric):
+    """The body of the three ``*_distances``: sides, pairs (refused as ``says`` bytes each), then ``metric(device)`` -> (entry point,
+    its arguments between ``nr`` and the matrix) with the metric's own checks, then ``out`` of ``dtype`` and the call"""
+    _lib.require_gpu()
+    nq, ldq, nr, ldr, dev = _knn_sides(what, Xq, Lq, Xr, Lr)
+    _edit_pairs(what, nq, nr, says)
+    entry, args = metric(dev)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nq, nr, dtype=dtype, device=dev)
+        _tensor(what, "out", out, dev, dtype, (nq, nr))
+        check(entry(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, *args, ptr(out), stream_ptr()), what)
+    return out
+
+
+def _knn_rows(what, width, says, Xq, Lq, Xr, Lr, k, exclude, buf, scratch, metric):
+    """The body of the three ``*_knn_rows`` behind their integer checks: sides, pairs (refused as ``says`` bytes each), then
+    ``metric(device)`` -> (entry point, its arguments between ``nr`` and ``exclude``, radius) with the metric's own checks, then
+    ``exclude``, ``buf``, the scratch of ``width`` bytes a pair and the call"""
+    _lib.require_gpu()
+    nq, ldq, nr, ldr, dev = _knn_sides(what, Xq, Lq, Xr, Lr)
+    _edit_pairs(what, nq, nr, says)
+    entry, args, radius = metric(dev)
+    if exclude is not None:
+        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
+    with torch.cuda.device(dev):
+        if buf is None:
+            buf = edit_knn_buffers(nq, k, dev)
+        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
+        if scratch is None:
+            scratch = torch.empty(width * nq * nr, dtype=torch.uint8, device=dev)
+        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {width * nq * nr}] tensor on {dev}")
+        check(entry(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, *args, ptr(exclude), k, radius, ptr(scratch), scratch.numel(),
+                    ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
+    return buf
+
+
+def _knn_logp(what, entry, buf, Lq, Lr, yr, prior, extra, weights, tau, normalize, lam, out):
+    """The body of the three ``*_knn_logp``; ``extra``: None, or (name, value, lowest, highest) of the one integer that the entry
+    point takes behind ``V``, checked where it always was (behind ``buf``)"""
+    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
+    nq, k = buf["shape"]
+    dev = buf["flat"].device
+    extra = () if extra is None else (_int_in(what, *extra),)
+    if weights not in _lib.EDIT_WEIGHTS:
+        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
+    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
+    _lib.require_gpu()
+    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
+    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
+    _tensor(what, "Lr", Lr, dev, torch.int64, None)
+    nr = int(Lr.shape[0])
+    _tensor(what, "yr", yr, dev, torch.int64, nr)
+    _tensor(what, "prior", prior, dev, torch.float64, None)
+    V = int(prior.shape[0])
+    if nr < 1 or V < 1:
+        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
+        if out.device != dev or tuple(out.shape) != (nq, V):
+            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
+        ld = _logp_matrix(f"{what} (out)", out)[2]
+        check(getattr(load(), entry)(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, *extra, _lib.EDIT_WEIGHTS.index(weights),
+                                     tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]), stream_ptr()), what)
+    return out
 
 
 def edit_distances(Xq, Lq, Xr, Lr, out=None):
@@ -1579,19 +1659,7 @@ def edit_distances(Xq, Lq, Xr, Lr, out=None):
     [nq, S] / ``Lq`` int64 [nq] against ``Xr`` int64 [nr, S'] / ``Lr`` int64 [nr] -> uint8 [nq, nr]; 255 where either row's length
     lies outside 0..64 (or beyond its row).  Only the first L tokens of a row are read.  ``out``: the matrix to fill.  One launch on
     the current stream of ``Xq``'s device; no host wait."""
-    _lib.require_gpu()
-    what = "edit_distances"
-    nq, ldq = _edit_side(what, "query", Xq, Lq)
-    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
-        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
-    nr, ldr = _edit_side(what, "reference", Xr, Lr)
-    _edit_pairs(what, nq, nr)
-    with torch.cuda.device(Xq.device):
-        if out is None:
-            out = torch.empty(nq, nr, dtype=torch.uint8, device=Xq.device)
-        _tensor(what, "out", out, Xq.device, torch.uint8, (nq, nr))
-        check(load().slnlp_edit_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(out), stream_ptr()), what)
-    return out
+    return _knn_distances("edit_distances", torch.uint8, 1, Xq, Lq, Xr, Lr, out, lambda dev: (load().slnlp_edit_distances, ()))
 
 
 def edit_knn_buffers(nq, k, device):
@@ -1606,6 +1674,8 @@ def edit_knn_buffers(nq, k, device):
     return _packed_dict(p, (nq, k))
 
 
+
+
 def edit_knn_rows(Xq, Lq, Xr, Lr, k, *, radius=0, exclude=None, buf=None, scratch=None):
     """The ``k`` (1..64) nearest references of every query under Levenshtein distance (``slnlp_edit_knn_rows``): per query the
     usable references of smallest distance ordered by (distance, reference index) -- ties at the k-th distance go to the lower
@@ -1616,25 +1686,7 @@ def edit_knn_rows(Xq, Lq, Xr, Lr, k, *, radius=0, exclude=None, buf=None, scratc
     Returns ``buf``."""
     what = "edit_knn_rows"
     k, radius = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K), _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN)
-    _lib.require_gpu()
-    nq, ldq = _edit_side(what, "query", Xq, Lq)
-    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
-        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
-    nr, ldr = _edit_side(what, "reference", Xr, Lr)
-    _edit_pairs(what, nq, nr)
-    dev = Xq.device
-    if exclude is not None:
-        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
-    with torch.cuda.device(dev):
-        if buf is None:
-            buf = edit_knn_buffers(nq, k, dev)
-        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
-        if scratch is None:
-            scratch = torch.empty(nq * nr, dtype=torch.uint8, device=dev)
-        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {nq * nr}] tensor on {dev}")
-        check(load().slnlp_edit_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(exclude), k, radius, ptr(scratch),
-                                         scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
-    return buf
+    return _knn_rows(what, 1, 1, Xq, Lq, Xr, Lr, k, exclude, buf, scratch, lambda dev: (load().slnlp_edit_knn_rows, (), radius))
 
 
 def edit_knn_logp(buf, Lq, Lr, yr, prior, *, weights="distance", tau=1.0, normalize=True, lam=1.0, out=None):
@@ -1644,34 +1696,7 @@ def edit_knn_logp(buf, Lq, Lr, yr, prior, *, weights="distance", tau=1.0, normal
     weight of the prior.  A flagged query gets a row of NaN; ``buf["head"][2]`` counts the neighbours whose label lies outside the
     V classes.  ``out``: a float32 [nq, V] tensor to fill (rows may be padded).  Two queued launches on the current stream of
     ``buf``'s device; no host wait.  Returns ``out``."""
-    what = "edit_knn_logp"
-    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
-    nq, k = buf["shape"]
-    dev = buf["flat"].device
-    if weights not in _lib.EDIT_WEIGHTS:
-        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
-    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
-    _lib.require_gpu()
-    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
-        if not torch.is_tensor(t):
-            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
-    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
-    _tensor(what, "Lr", Lr, dev, torch.int64, None)
-    nr = int(Lr.shape[0])
-    _tensor(what, "yr", yr, dev, torch.int64, nr)
-    _tensor(what, "prior", prior, dev, torch.float64, None)
-    V = int(prior.shape[0])
-    if nr < 1 or V < 1:
-        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
-        if out.device != dev or tuple(out.shape) != (nq, V):
-            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
-        ld = _logp_matrix(f"{what} (out)", out)[2]
-        check(load().slnlp_edit_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, _lib.EDIT_WEIGHTS.index(weights),
-                                         tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]), stream_ptr()), what)
-    return out
+    return _knn_logp("edit_knn_logp", "slnlp_edit_knn_logp", buf, Lq, Lr, yr, prior, None, weights, tau, normalize, lam, out)
 
 
 def edit_knn_download(buf, neighbours=True):
@@ -1683,9 +1708,6 @@ def edit_knn_download(buf, neighbours=True):
     return buf["packed"].cut("head", "nbr" if neighbours else "rows")
 
 
-def _edit_long_pairs(what, nq, nr):
-    if nq * nr > _lib.EDIT_MAX_PAIRS:
-        raise ValueError(f"{what}: {nq} x {nr} pairs, at most {_lib.EDIT_MAX_PAIRS} (two bytes each) are formed per call: pass the queries in chunks")
 
 
 def edit_long_distances(Xq, Lq, Xr, Lr, *, max_len, out=None):
@@ -1695,18 +1717,7 @@ def edit_long_distances(Xq, Lq, Xr, Lr, *, max_len, out=None):
     fill.  One launch on the current stream of ``Xq``'s device; no host wait."""
     what = "edit_long_distances"
     max_len = _int_in(what, "max_len", max_len, -2 ** 63, 2 ** 63 - 1)          # the library holds it to 1..512
-    _lib.require_gpu()
-    nq, ldq = _edit_side(what, "query", Xq, Lq)
-    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
-        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
-    nr, ldr = _edit_side(what, "reference", Xr, Lr)
-    _edit_long_pairs(what, nq, nr)
-    with torch.cuda.device(Xq.device):
-        if out is None:
-            out = torch.empty(nq, nr, dtype=torch.uint16, device=Xq.device)
-        _tensor(what, "out", out, Xq.device, torch.uint16, (nq, nr))
-        check(load().slnlp_edit_long_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, max_len, ptr(out), stream_ptr()), what)
-    return out
+    return _knn_distances(what, torch.uint16, 2, Xq, Lq, Xr, Lr, out, lambda dev: (load().slnlp_edit_long_distances, (max_len,)))
 
 
 def edit_long_knn_rows(Xq, Lq, Xr, Lr, k, *, max_len, radius=0, exclude=None, buf=None, scratch=None):
@@ -1718,61 +1729,15 @@ def edit_long_knn_rows(Xq, Lq, Xr, Lr, k, *, max_len, radius=0, exclude=None, bu
     what = "edit_long_knn_rows"
     max_len = _int_in(what, "max_len", max_len, -2 ** 63, 2 ** 63 - 1)          # the library holds it to 1..512 and the radius to 0..max_len
     k, radius = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K), _int_in(what, "radius", radius, -2 ** 63, 2 ** 63 - 1)
-    _lib.require_gpu()
-    nq, ldq = _edit_side(what, "query", Xq, Lq)
-    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
-        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
-    nr, ldr = _edit_side(what, "reference", Xr, Lr)
-    _edit_long_pairs(what, nq, nr)
-    dev = Xq.device
-    if exclude is not None:
-        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
-    with torch.cuda.device(dev):
-        if buf is None:
-            buf = edit_knn_buffers(nq, k, dev)
-        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
-        if scratch is None:
-            scratch = torch.empty(2 * nq * nr, dtype=torch.uint8, device=dev)
-        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {2 * nq * nr}] tensor on {dev}")
-        check(load().slnlp_edit_long_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, max_len, ptr(exclude), k, radius, ptr(scratch),
-                                              scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
-    return buf
+    return _knn_rows(what, 2, 2, Xq, Lq, Xr, Lr, k, exclude, buf, scratch, lambda dev: (load().slnlp_edit_long_knn_rows, (max_len,), radius))
 
 
 def edit_long_knn_logp(buf, Lq, Lr, yr, prior, *, max_len, weights="distance", tau=1.0, normalize=True, lam=1.0, out=None):
     """``edit_knn_logp`` for the neighbours of ``edit_long_knn_rows`` (``slnlp_edit_long_knn_logp``): the same vote, operation for
     operation, but a neighbour is listed up to the distance ``max_len`` (1..512) where ``edit_knn_logp`` lists none beyond 64.  Two
     queued launches on the current stream of ``buf``'s device; no host wait.  Returns ``out``."""
-    what = "edit_long_knn_logp"
-    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
-    nq, k = buf["shape"]
-    dev = buf["flat"].device
-    max_len = _int_in(what, "max_len", max_len, -2 ** 63, 2 ** 63 - 1)          # the library holds it to 1..512
-    if weights not in _lib.EDIT_WEIGHTS:
-        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
-    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
-    _lib.require_gpu()
-    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
-        if not torch.is_tensor(t):
-            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
-    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
-    _tensor(what, "Lr", Lr, dev, torch.int64, None)
-    nr = int(Lr.shape[0])
-    _tensor(what, "yr", yr, dev, torch.int64, nr)
-    _tensor(what, "prior", prior, dev, torch.float64, None)
-    V = int(prior.shape[0])
-    if nr < 1 or V < 1:
-        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
-        if out.device != dev or tuple(out.shape) != (nq, V):
-            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
-        ld = _logp_matrix(f"{what} (out)", out)[2]
-        check(load().slnlp_edit_long_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, max_len,
-                                              _lib.EDIT_WEIGHTS.index(weights), tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]),
-                                              stream_ptr()), what)
-    return out
+    return _knn_logp("edit_long_knn_logp", "slnlp_edit_long_knn_logp", buf, Lq, Lr, yr, prior, ("max_len", max_len, -2 ** 63, 2 ** 63 - 1),
+                     weights, tau, normalize, lam, out)             # the library holds max_len to 1..512
 
 
 def _field_table(what, codes, gap, dev):
@@ -1801,6 +1766,18 @@ def _field_weights(what, field_weights, F, gap):
     return (C.c_int32 * F)(*(int(v) for v in w)), W, _int_in(what, "gap", W if gap is None else gap, 1, W)
 
 
+
+def _field_metric(what, codes, gap, field_weights, dev):
+    """The table, the weights and the gap of either field metric checked -> (arguments of the entry point behind ``nr``, unit: F or
+    W, "_w" where the weighted entry point takes them)"""
+    if field_weights is None:
+        Vt, F, gap = _field_table(what, codes, gap, dev)
+        return (ptr(codes), Vt, F, gap), F, ""
+    Vt, F, _ = _field_table(what, codes, None, dev)
+    fw, W, gap = _field_weights(what, field_weights, F, gap)
+    return (ptr(codes), Vt, F, fw, gap), W, "_w"
+
+
 def field_distances(Xq, Lq, Xr, Lr, codes, gap=None, out=None, field_weights=None):
     """The phonology-weighted edit distance of every (query, reference) pair (``slnlp_field_distances``, csrc/field_knn.hip):
     substituting a frame costs the number of fields in which the two tokens' rows of ``codes`` (int32 [Vt, F] on the device)
@@ -1809,28 +1786,12 @@ def field_distances(Xq, Lq, Xr, Lr, codes, gap=None, out=None, field_weights=Non
     the matrix to fill.  One launch on the current stream of ``Xq``'s device; no host wait.  ``field_weights`` (None: the call
     above, unchanged): F integers in 0..16 with sum W in 1..16 -- field f counts ``field_weights[f]``, a token outside the table
     costs W, ``gap`` lies in 1..W (None: W) and distances are at most 64 W (``slnlp_field_distances_w``)."""
-    _lib.require_gpu()
     what = "field_distances"
-    nq, ldq = _edit_side(what, "query", Xq, Lq)
-    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
-        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
-    nr, ldr = _edit_side(what, "reference", Xr, Lr)
-    _edit_pairs(what, nq, nr)
-    if field_weights is not None:
-        Vt, F, _ = _field_table(what, codes, None, Xq.device)
-        fw, W, gap = _field_weights(what, field_weights, F, gap)
-    else:
-        Vt, F, gap = _field_table(what, codes, gap, Xq.device)
-    with torch.cuda.device(Xq.device):
-        if out is None:
-            out = torch.empty(nq, nr, dtype=torch.uint16, device=Xq.device)
-        _tensor(what, "out", out, Xq.device, torch.uint16, (nq, nr))
-        if field_weights is not None:
-            check(load().slnlp_field_distances_w(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, fw, gap, ptr(out), stream_ptr()),
-                  what)
-            return out
-        check(load().slnlp_field_distances(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, gap, ptr(out), stream_ptr()), what)
-    return out
+
+    def metric(dev):
+        args, _, w = _field_metric(what, codes, gap, field_weights, dev)
+        return getattr(load(), "slnlp_field_distances" + w), args
+    return _knn_distances(what, torch.uint16, 1, Xq, Lq, Xr, Lr, out, metric)
 
 
 def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None, buf=None, scratch=None, field_weights=None):
@@ -1842,36 +1803,11 @@ def field_knn_rows(Xq, Lq, Xr, Lr, codes, k, *, gap=None, radius=0, exclude=None
     ``gap`` in 1..W, ``radius`` in 0..64 W, distances in units of W (``slnlp_field_knn_rows_w``)."""
     what = "field_knn_rows"
     k = _int_in(what, "k", k, 1, _lib.EDIT_MAX_K)
-    _lib.require_gpu()
-    nq, ldq = _edit_side(what, "query", Xq, Lq)
-    if not (torch.is_tensor(Xr) and Xr.device == Xq.device):
-        raise ValueError(f"{what}: the reference rows must be a tensor on {Xq.device}")
-    nr, ldr = _edit_side(what, "reference", Xr, Lr)
-    _edit_pairs(what, nq, nr)
-    dev = Xq.device
-    if field_weights is not None:
-        Vt, F, _ = _field_table(what, codes, None, dev)
-        fw, W, gap = _field_weights(what, field_weights, F, gap)
-        radius = _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * W)
-    else:
-        Vt, F, gap = _field_table(what, codes, gap, dev)
-        radius = _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * F)
-    if exclude is not None:
-        _tensor(what, "exclude", exclude, dev, torch.int64, nq, f"a contiguous int64 [{nq}] tensor on {dev} or None")
-    with torch.cuda.device(dev):
-        if buf is None:
-            buf = edit_knn_buffers(nq, k, dev)
-        _packed_buf(what, buf, f"edit_knn_buffers({nq}, {k}, device) on {dev}", (nq, k), dev)
-        if scratch is None:
-            scratch = torch.empty(2 * nq * nr, dtype=torch.uint8, device=dev)
-        _tensor(what, "scratch", scratch, dev, torch.uint8, None, f"a contiguous uint8 [>= {2 * nq * nr}] tensor on {dev}")
-        if field_weights is not None:
-            check(load().slnlp_field_knn_rows_w(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, fw, gap, ptr(exclude), k, radius,
-                                                ptr(scratch), scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
-            return buf
-        check(load().slnlp_field_knn_rows(ptr(Xq), ldq, ptr(Lq), nq, ptr(Xr), ldr, ptr(Lr), nr, ptr(codes), Vt, F, gap, ptr(exclude), k, radius,
-                                          ptr(scratch), scratch.numel(), ptr(buf["head"]), ptr(buf["rows"]), ptr(buf["nbr"]), stream_ptr()), what)
-    return buf
+
+    def metric(dev):
+        args, unit, w = _field_metric(what, codes, gap, field_weights, dev)
+        return getattr(load(), "slnlp_field_knn_rows" + w), args, _int_in(what, "radius", radius, 0, _lib.EDIT_MAX_LEN * unit)
+    return _knn_rows(what, 2, 1, Xq, Lq, Xr, Lr, k, exclude, buf, scratch, metric)
 
 
 def field_knn_logp(buf, Lq, Lr, yr, prior, F, *, weights="distance", tau=1.0, normalize=True, lam=1.0, out=None):
@@ -1879,35 +1815,8 @@ def field_knn_logp(buf, Lq, Lr, yr, prior, F, *, weights="distance", tau=1.0, no
     (1..16), so w = exp(-d / (tau n)) with n = F max(Lq, Lr, 1) when ``normalize``, else F -- ``tau`` is in frames in both metrics,
     and at F = 1 the vote is ``edit_knn_logp``'s bit for bit.  Two queued launches on the current stream of ``buf``'s device; no host
     wait.  Returns ``out``."""
-    what = "field_knn_logp"
-    _packed_buf(what, buf, "edit_knn_buffers(nq, k, device)", (), None, more=2)
-    nq, k = buf["shape"]
-    dev = buf["flat"].device
-    F = _int_in(what, "F", F, 1, _lib.FIELD_MAX_FIELDS)
-    if weights not in _lib.EDIT_WEIGHTS:
-        raise ValueError(f"{what}: weights={weights!r}, expected one of {_lib.EDIT_WEIGHTS}")
-    tau, lam = _positive(what, "tau", tau), _positive(what, "lam", lam)
-    _lib.require_gpu()
-    for name, t in (("Lq", Lq), ("Lr", Lr), ("yr", yr), ("prior", prior)):
-        if not torch.is_tensor(t):
-            raise ValueError(f"{what}: {name} must be a tensor on {dev}")
-    _tensor(what, "Lq", Lq, dev, torch.int64, nq)
-    _tensor(what, "Lr", Lr, dev, torch.int64, None)
-    nr = int(Lr.shape[0])
-    _tensor(what, "yr", yr, dev, torch.int64, nr)
-    _tensor(what, "prior", prior, dev, torch.float64, None)
-    V = int(prior.shape[0])
-    if nr < 1 or V < 1:
-        raise ValueError(f"{what}: {nr} references and {V} classes: at least one of each")
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(nq, V, dtype=torch.float32, device=dev)
-        if out.device != dev or tuple(out.shape) != (nq, V):
-            raise ValueError(f"{what}: out must be a float32 [{nq}, {V}] tensor on {dev}")
-        ld = _logp_matrix(f"{what} (out)", out)[2]
-        check(load().slnlp_field_knn_logp(ptr(buf["nbr"]), ptr(buf["rows"]), ptr(Lq), ptr(Lr), ptr(yr), nq, nr, k, V, F, _lib.EDIT_WEIGHTS.index(weights),
-                                          tau, int(bool(normalize)), lam, ptr(prior), ptr(out), ld, ptr(buf["head"]), stream_ptr()), what)
-    return out
+    return _knn_logp("field_knn_logp", "slnlp_field_knn_logp", buf, Lq, Lr, yr, prior, ("F", F, 1, _lib.FIELD_MAX_FIELDS), weights, tau,
+                     normalize, lam, out)
 
 
 def loo_objective_table(slots, device):

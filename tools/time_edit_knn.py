@@ -2,6 +2,7 @@
 ``slnlp_edit_knn_logp``: ``slnlp.EditKNN``, ``slnlp.split_audit``).
 
     python tools/time_edit_knn.py [--out profiles/edit_knn_timing.json] [--host-queries 8]
+    python tools/time_edit_knn.py --ab parent [--out profiles/knn_shell_timing.json]
 
 Rows of S = 48 positions from ``synthetic_dataset`` (3000 source tokens, 200 labels, lengths 8..48), k = 5, at three shapes (queries
 x references): 800 x 3200 (a grid's test split against its train split), 4000 x 4000 (leave-one-out over a train split) and
@@ -20,6 +21,12 @@ x references): 800 x 3200 (a grid's test split against its train split), 4000 x 
 * ``gru_forward``: wall clock of ONE forward pass (``predict_proba``) of a cfg3 GRU (bench.py: cfg3gru -- embedding 512, hidden
   512, 4 layers, batch 50) with untrained weights over the same query rows (2 warm-up, 5 samples).
 
+``--ab NAME`` (a run of its own, whose parent process never opens the GPU; with ``--out`` it is merged into that file under
+``edit_knn_rows_<shape>_vs_parent``): ``ops.edit_knn_rows`` at 4000 x 4000 and at 16384 x 4000 under the product library and under
+lib/libslnlp_probeNAME.so (the parent commit's tree built with ``make VARIANT=NAME``), in fresh child processes, interleaved,
+``--ab-rounds`` times on this box (tools/knn_ab.py): each child's batched median, and per build the spread between its repeated
+medians.  The margin is the parent's own spread.
+
 No pass / fail: the numbers are recorded."""
 import argparse
 import json
@@ -35,6 +42,8 @@ for p in (ROOT, os.path.join(ROOT, "sign-language-nlp_amd"), os.path.join(ROOT, 
 
 import numpy as np
 import torch
+
+from time_field_knn import emit
 
 S, K, SRC_VOCAB, LABELS = 48, 5, 3000, 200
 SHAPES = (("test_vs_train_800x3200", 800, 3200), ("leave_one_out_4000x4000", 4000, 4000), ("large_16384x4000", 16384, 4000))
@@ -115,14 +124,42 @@ def time_shape(name, nq, nr, data, host_queries, gru):
     return res
 
 
+def ab_child(nq, nr):
+    """One child of the A / B: edit_knn_rows at nq x nr, batched medians of its own repeats"""
+    from slnlp import ops
+    from slnlp.data import synthetic_dataset
+    data = synthetic_dataset(nq + nr, seq_len=S, src_vocab=SRC_VOCAB, n_labels=LABELS, seed=1, min_len=8)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    Xr, Lr, Xq, Lq = dev(data.ids[:nr]), dev(data.lengths[:nr]), dev(data.ids[nr:]), dev(data.lengths[nr:])
+    buf = ops.edit_knn_buffers(nq, K, "cuda")
+    scratch = torch.empty(nq * nr, dtype=torch.uint8, device="cuda")
+    fn = lambda: ops.edit_knn_rows(Xq, Lq, Xr, Lr, K, buf=buf, scratch=scratch)
+    batched = stats([timed_us(fn, 4) for _ in range(2 + 9)][2:], "us")
+    got = ops.edit_knn_download(buf)
+    print(json.dumps({"knn_rows_batched": batched, "checksum": int(got["nbr"].astype(np.int64).sum())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--host-queries", type=int, default=8)
     ap.add_argument("--shapes", default=None, help="comma-separated indices into SHAPES (default: all)")
+    ap.add_argument("--ab", default=None, help="NAME of lib/libslnlp_probeNAME.so, the parent commit's library")
+    ap.add_argument("--ab-rounds", type=int, default=4)
+    ap.add_argument("--ab-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.ab:                                              # children only: this process stays off the GPU
+        from knn_ab import ab
+        res = json.load(open(args.out)) if args.out and os.path.exists(args.out) else {}
+        for name, nq, nr in SHAPES[1:]:
+            what = (f"ops.edit_knn_rows (distances, selection, head) at {nq} x {nr}, S = {S}, k = {K}; 4 calls between one pair of events, median of 9 "
+                    "repeats per child process; children interleaved on one box")
+            res[f"edit_knn_rows_{nq}x{nr}_vs_parent"] = ab(HERE, ["--ab-child", f"{nq}x{nr}"], args.ab, args.ab_rounds, what, "time_edit_knn")
+        return emit(res, args.out)
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_edit_knn.py: no GPU -- nothing is measured without one")
+    if args.ab_child:
+        return ab_child(*(int(v) for v in args.ab_child.split("x")))
     from slnlp.data import synthetic_dataset
     from slnlp.net import NeuralNetClassifier
     which = [SHAPES[int(i)] for i in args.shapes.split(",")] if args.shapes else list(SHAPES)
@@ -143,12 +180,7 @@ def main():
                     f"{SAMPLES} samples after {WARMUP} warm-up; *_batched: {BATCH} calls between one pair of events, per call; predict_proba and "
                     "gru_forward: wall clock between two device synchronisations; host: the numpy restatement on a stated subset of the "
                     "queries, host_extrapolated_ms scaled linearly and NOT measured at the full size")}
-    line = json.dumps(res, indent=1)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

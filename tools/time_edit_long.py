@@ -4,6 +4,7 @@
 
     python tools/time_edit_long.py [--out profiles/edit_long_timing.json] [--host-queries 8]
     python tools/time_edit_long.py --registers [--out profiles/edit_long_timing.json]        (no GPU: hipcc alone)
+    python tools/time_edit_long.py --ab parent [--out profiles/knn_shell_timing.json]
 
 Rows from ``synthetic_dataset`` (3000 source tokens, 200 labels, lengths 8..S), k = 5.  Event-timed as tools/time_edit_knn.py: one
 ``ops`` call between two HIP events, the second one waited for, into buffers allocated once; 5 warm-up calls, 30 samples;
@@ -25,7 +26,11 @@ Rows from ``synthetic_dataset`` (3000 source tokens, 200 labels, lengths 8..S), 
   ``same_integers``: whether the device's neighbours of those queries equal it.  Not scaled to a claim about the full size.
 * ``registers`` (``--registers``, merged into ``--out``): the register allocation, scratch and LDS bytes of ``edit_long_dist_kernel``
   from the code object's metadata -- of the built library, and of csrc/edit_long.hip compiled with one W alone
-  (``-DSLNLP_EDIT_LONG_ONLY_W=W``) for each W the kernel instantiates."""
+  (``-DSLNLP_EDIT_LONG_ONLY_W=W``) for each W the kernel instantiates.
+* ``--ab NAME`` (a run of its own, whose parent process never opens the GPU; with ``--out`` it is merged into that file under
+  ``edit_long_knn_rows_vs_parent``): ``ops.edit_long_knn_rows`` at 4000 x 4000, S = max_len = 128 -- a ``long_rows`` shape above --
+  under the product library and under lib/libslnlp_probeNAME.so, in fresh child processes, interleaved, ``--ab-rounds`` times
+  (tools/knn_ab.py): each child's batched median, per build the spread between its repeated medians; the margin is the parent's."""
 import argparse
 import json
 import os
@@ -182,6 +187,21 @@ def time_long(name, nq, nr, S, max_len, data, host_queries=0):
     return res
 
 
+def ab_child():
+    """One child of the A / B: edit_long_knn_rows at 4000 x 4000, S = max_len = 128, batched medians of its own repeats"""
+    import torch
+    from slnlp import ops
+    S, n = LONG_S[0], SHORT_N
+    data = rows_of(S, 2 * n)
+    Xr, Lr, Xq, Lq = dev(data.ids[:n]), dev(data.lengths[:n]), dev(data.ids[n:]), dev(data.lengths[n:])
+    buf = ops.edit_knn_buffers(n, K, "cuda")
+    scratch = torch.empty(2 * n * n, dtype=torch.uint8, device="cuda")
+    fn = lambda: ops.edit_long_knn_rows(Xq, Lq, Xr, Lr, K, max_len=S, buf=buf, scratch=scratch)
+    batched = stats([timed_us(fn, 4) for _ in range(2 + 9)][2:], "us")
+    got = ops.edit_knn_download(buf)
+    print(json.dumps({"knn_rows_batched": batched, "checksum": int(got["nbr"].astype(np.int64).sum())}))
+
+
 # --------------------------------------------------------------------------------------------------------- registers ----
 def kernel_metadata(path, match="edit_long"):
     import msgpack
@@ -233,10 +253,21 @@ def main():
     ap.add_argument("--host-queries", type=int, default=8)
     ap.add_argument("--registers", action="store_true", help="only the register record (no GPU), merged into --out")
     ap.add_argument("--short-path-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--ab", default=None, help="NAME of lib/libslnlp_probeNAME.so, the parent commit's library")
+    ap.add_argument("--ab-rounds", type=int, default=4)
+    ap.add_argument("--ab-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.short_path_child:
         return short_path_child()
-    if args.registers:
+    if args.ab_child:
+        return ab_child()
+    if args.ab:                                              # children only: this process stays off the GPU
+        from knn_ab import ab
+        res = json.load(open(args.out)) if args.out and os.path.exists(args.out) else {}
+        what = (f"ops.edit_long_knn_rows (distances, selection, head) at {SHORT_N} x {SHORT_N}, S = max_len = {LONG_S[0]}, k = {K}; 4 calls between one "
+                "pair of events, median of 9 repeats per child process; children interleaved on one box")
+        res["edit_long_knn_rows_vs_parent"] = ab(HERE, ["--ab-child"], args.ab, args.ab_rounds, what, "time_edit_long")
+    elif args.registers:
         res = json.load(open(args.out)) if args.out and os.path.exists(args.out) else {}
         res["registers"] = registers()
     else:

@@ -27,7 +27,6 @@ key ``phono_baseline.fit_weights``) tells a user on their own data.  No pass / f
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
@@ -106,29 +105,11 @@ def ab_child():
 
 
 def ab(name, rounds):
-    res = {"product": [], name: []}
-    for r in range(rounds):
-        for variant in (name, "product"):
-            env = dict(os.environ)
-            env.pop("SLNLP_PROBE_LIB", None)
-            if variant != "product":
-                env["SLNLP_PROBE_LIB"] = variant
-            out = subprocess.run([sys.executable, HERE, "--ab-child"], env=env, capture_output=True, text=True, timeout=300)
-            if out.returncode != 0:
-                raise SystemExit(f"time_field_weights --ab: the {variant} child failed ({out.returncode}): {out.stderr[-600:]}")
-            res[variant].append(json.loads(out.stdout.strip().splitlines()[-1]))
-            print(f"[time_field_weights] ab round {r} {variant}: {res[variant][-1]['knn_rows_batched']['median_us']:.1f} us", file=sys.stderr, flush=True)
-    out = {"what": "ops.field_knn_rows WITHOUT weights (distances, selection, head) at 4000 x 4000, S = 48, F = 6, k = 5; 4 calls between one pair of "
-                   "events, median of 9 repeats per child process; children interleaved on one box", "rounds": rounds}
-    for variant, runs in res.items():
-        med = [c["knn_rows_batched"]["median_us"] for c in runs]
-        out[variant] = {"medians_us": med, "median_of_medians_us": float(np.median(med)), "spread_us": float(max(med) - min(med)),
-                        "checksums": [c["checksum"] for c in runs]}
-    out["difference_us"] = out["product"]["median_of_medians_us"] - out[name]["median_of_medians_us"]
-    out["margin_us"] = out[name]["spread_us"]
-    out["within_margin"] = bool(abs(out["difference_us"]) <= out["margin_us"])
-    out["same_neighbours"] = len({c for v in ("product", name) for c in out[v]["checksums"]}) == 1
-    return out
+    """tools/knn_ab.py: the children interleaved, each build's medians and spread"""
+    from knn_ab import ab as ab_children
+    what = ("ops.field_knn_rows WITHOUT weights (distances, selection, head) at 4000 x 4000, S = 48, F = 6, k = 5; 4 calls between one pair of "
+            "events, median of 9 repeats per child process; children interleaved on one box")
+    return ab_children(HERE, ["--ab-child"], name, rounds, what, "time_field_weights")
 
 
 def main():
