@@ -1199,6 +1199,44 @@ int slnlp_edit_long_knn_logp(const int32_t* nbr, const int32_t* rows, const int6
                              int64_t nr, int64_t k, int64_t V, int64_t max_len, int weights, double tau, int normalize, double lam,
                              const double* prior, float* logp, int64_t ld, int64_t* head, void* stream);
 
+/* ------------------------------------------- near-duplicate groups of one data set (csrc/dup_groups.hip) --
+ * The connected components of "rows within radius edits of each other" (slnlp.duplicate_groups): the undirected graph over the N
+ * rows of ONE data set whose edges are the pairs {i, j}, i != j, with d(i, j) <= radius; every row is labelled with the LOWEST row
+ * index of its component.  That labelling is unique, so the result is a pure function of the arguments: the same bytes on every
+ * run, on any stream, beside other kernels.  Integers only, integer atomics only.
+ *
+ * The distances are what slnlp_edit_distances (width 1: uint8, 255 for a pair with an unusable row), slnlp_edit_long_distances and
+ * slnlp_field_distances[_w] (width 2: uint16, 65535) write, with the data set on both sides.  The N x N matrix need not be
+ * resident: the caller forms the rows q0 .. q0 + nq - 1 against all N rows, links them, and reuses the memory for the next chunk.
+ * Every row is linked exactly once; the chunks may come in any order.  Three entry points, all queued, no host wait:
+ *
+ * slnlp_dup_groups_begin: parent[i] = i, degree[i] = 0, head zeroed.  One launch.
+ *
+ * slnlp_dup_groups_link: dist [nq, N] of `width` bytes an element, row qi the distances of row i = q0 + qi.  A wave per row:
+ * degree[i] = #{j != i : dist[qi, j] <= radius}, and for every such j < i the trees of i and j are joined by hooking the LARGER
+ * root under the SMALLER (a 32-bit compare-and-swap on parent) -- the distance is symmetric, so j < i sees every edge once.  A row
+ * whose own entry dist[qi, q0 + qi] is the sentinel is UNUSABLE: it links to nothing, keeps degree 0 and is counted in head[2].
+ * One launch.
+ *
+ * slnlp_dup_groups_finish: group[i] = the root of i = the lowest row index of its component; head[0] = the groups (rows with
+ * group[i] == i), head[1] = the edges = the degree sum halved.  Two launches.  It may be called again after further links.
+ *
+ *   head int64 [8]    groups | edges within the radius | unusable rows | code | the degree sum | 0 0 0
+ *
+ * code is 0.  Every loop of these kernels counts its rounds to N + 1 although none can need them (a walk to the root descends
+ * strictly; a failed compare-and-swap means another hook completed, and at most N - 1 exist); a thread that ran out sets code to 1
+ * and leaves, and the result is then not to be used.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message that names the entry point, before anything is launched): a null pointer; N or nq
+ * outside 1..SLNLP_EDIT_MAX_ROWS; q0 < 0 or q0 + nq > N; more than SLNLP_EDIT_MAX_PAIRS pairs; width not 1 or 2; radius outside
+ * 0..254 (width 1) or 0..65534 (width 2); a misaligned pointer (dist: width bytes; parent, degree, group: 4; head: 8); an output
+ * overlapping an input or another output. */
+#define SLNLP_DUP_HEAD_BYTES 64
+int slnlp_dup_groups_begin(int32_t* parent /* [N] */, int32_t* degree /* [N] */, int64_t N, int64_t* head /* [8] */, void* stream);
+int slnlp_dup_groups_link(const void* dist /* [nq, N] */, int width, int64_t nq, int64_t N, int64_t q0, int64_t radius,
+                          int32_t* parent /* [N] */, int32_t* degree /* [N] */, int64_t* head /* [8] */, void* stream);
+int slnlp_dup_groups_finish(const int32_t* parent /* [N] */, int64_t N, int32_t* group /* [N] */, int64_t* head /* [8] */, void* stream);
+
 /* ------------------------------------- phonology-weighted edit-distance neighbours (csrc/field_knn.hip) --
  * The same search under a WEIGHTED edit distance (slnlp.PhonoKNN, slnlp.split_audit(field_codes=...)): a token of this data is a
  * composition of F phonological fields, and substituting one frame for another costs the number of fields in which they differ.

@@ -1,7 +1,7 @@
 """slnlp: the MI355X path of the sign-language gloss classifier.  The submodules are imported on demand (``slnlp.net``,
 ``slnlp.ops``, ...); ``slnlp.VotingEnsemble``, ``slnlp.PriorShift``, ``slnlp.OutOfFold``, ``slnlp.cross_fit``, ``slnlp.EditKNN``,
-``slnlp.PhonoKNN``, ``slnlp.split_audit`` and ``slnlp.fit_field_weights`` are resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
-__all__ = ["VotingEnsemble", "PriorShift", "OutOfFold", "cross_fit", "EditKNN", "PhonoKNN", "split_audit", "fit_field_weights"]
+``slnlp.PhonoKNN``, ``slnlp.split_audit``, ``slnlp.fit_field_weights`` and ``slnlp.duplicate_groups`` are resolved on first use, so that ``import slnlp`` stays free of torch and sklearn."""
+__all__ = ["VotingEnsemble", "PriorShift", "OutOfFold", "cross_fit", "EditKNN", "PhonoKNN", "split_audit", "fit_field_weights", "duplicate_groups"]
 
 
 def __getattr__(name):
@@ -20,4 +20,7 @@ def __getattr__(name):
     if name == "fit_field_weights":
         from .field_weights import fit_field_weights
         return fit_field_weights
+    if name == "duplicate_groups":
+        from .dup_groups import duplicate_groups
+        return duplicate_groups
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -159,7 +159,20 @@ in units of W, the sum of the weights.  Rank 0 also writes
     test_phono_baseline.json         gains ``phono_vs_weighted``: ``compare`` of the unit-weight ``PhonoKNN`` against the weighted
                                      one on paired resamples of the TEST split -- the number to judge the weights by
 
-Without the twelve keys the workdir holds exactly the files listed above.
+A top-level ``grouped_splits: {radius: 0, metric: unit, max_len: null}`` (all optional, these defaults) makes the run's splits
+LEAK-FREE: ``slnlp.duplicate_groups`` (csrc/dup_groups.hip) forms the connected components of "rows within ``radius`` edits of each
+other" once, on the loaded dataset, BEFORE ``balance_dataset`` and the test split; the dataset carries the group ids and the test
+split, the grid's folds and every fit's internal valid split keep a group on one side (a row ``balance_dataset`` over-samples keeps
+its original's group).  ``metric: unit`` is ``baseline``'s distance (``max_len``: 65..512 for longer rows), ``metric: phono``
+``phono_baseline``'s, from ``dataset_args.fields``, ``radius`` in field units; it takes no ``max_len``.  Rank 0 writes
+
+    duplicate_groups.json          the options, rows, radius, max_distance, n_groups, largest, rows_in_groups, pairs, flagged,
+                                   mixed_label_groups and the histogram of group sizes
+
+Where ``baseline`` is set too, ``test_split_audit.json`` is the end-to-end proof: at a radius up to this one it reports no twin of
+a test row in train.
+
+Without the thirteen keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -173,7 +186,8 @@ import numpy as np
 
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
-             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics", "baseline", "phono_baseline")
+             "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics", "baseline", "phono_baseline",
+             "grouped_splits")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -775,16 +789,76 @@ def phono_baseline_options(setting):
     return opts
 
 
-def phono_field_codes(dataset, dataset_args):
-    """The code table of ``phono_baseline`` from the config's own ``dataset_args.fields`` and ``composition_strategy``
-    (``slnlp.ingest.field_codes``); ValueError without fields or without a source vocabulary that names the tokens"""
+def phono_field_codes(dataset, dataset_args, what="phono_baseline"):
+    """The code table of ``phono_baseline`` (or of the key ``what``) from the config's own ``dataset_args.fields`` and
+    ``composition_strategy`` (``slnlp.ingest.field_codes``); ValueError without fields or without a source vocabulary that names the
+    tokens"""
     from .ingest import field_codes
     fields = list((dataset_args or {}).get("fields") or [])
     if not fields or getattr(dataset, "vocab_X", None) is None or not hasattr(dataset.vocab_X, "itos"):
-        raise ValueError("phono_baseline: needs dataset_args.fields and a dataset built from them (its vocabulary names the tokens)")
+        raise ValueError(f"{what}: needs dataset_args.fields and a dataset built from them (its vocabulary names the tokens)")
     if len(fields) > PHONO_MAX_FIELDS:
-        raise ValueError(f"phono_baseline: {len(fields)} fields, at most {PHONO_MAX_FIELDS} are taken")
+        raise ValueError(f"{what}: {len(fields)} fields, at most {PHONO_MAX_FIELDS} are taken")
     return field_codes(dataset.vocab_X, fields, (dataset_args or {}).get("composition_strategy", "as_words"))
+
+
+GROUPED_SPLITS_DEFAULTS = {"radius": 0, "metric": "unit", "max_len": None}
+GROUPED_SPLITS_METRICS = ("unit", "phono")
+GROUPED_SPLITS_REPORT = ("rows", "radius", "max_distance", "n_groups", "largest", "rows_in_groups", "pairs", "flagged", "mixed_label_groups")
+
+
+def grouped_splits_options(setting):
+    """The ``grouped_splits`` key with its defaults filled in -- {radius 0, metric unit, max_len null} -- or None when the key is
+    absent.  Anything but a dict over these three keys ({}: all defaults) raises ValueError: ``metric`` "unit" (Levenshtein distance,
+    as ``baseline``) or "phono" (the phonology-weighted distance of ``phono_baseline``, from ``dataset_args.fields``); ``max_len``
+    null or an integer in 65..512, with the unit metric only (the phonology-weighted search stays at 64 frames); ``radius`` an
+    integer in 0..64 -- 0..max_len with ``max_len``, 0..64 x 16 in field units under "phono" (held to 64 F once the fields are
+    known)."""
+    if setting is None:
+        return None
+    known = tuple(GROUPED_SPLITS_DEFAULTS)
+    if not isinstance(setting, dict):
+        raise ValueError(f"grouped_splits={setting!r}: expected a dict with keys among {known}")
+    unknown = sorted(set(setting) - set(known), key=str)
+    if unknown:
+        raise ValueError(f"grouped_splits: unknown keys {unknown} (known: {known})")
+    opts = dict(GROUPED_SPLITS_DEFAULTS, **setting)
+    whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    if opts["metric"] not in GROUPED_SPLITS_METRICS:
+        raise ValueError(f"grouped_splits: metric={opts['metric']!r}, expected one of {GROUPED_SPLITS_METRICS}")
+    max_radius = BASELINE_MAX_RADIUS * (PHONO_MAX_FIELDS if opts["metric"] == "phono" else 1)
+    if opts["max_len"] is not None:
+        if opts["metric"] == "phono":
+            raise ValueError(f"grouped_splits: max_len={opts['max_len']!r} with metric phono: the phonology-weighted search is limited to "
+                             f"{BASELINE_MAX_RADIUS} frames (only the unit metric takes max_len)")
+        if not whole(opts["max_len"], BASELINE_MAX_RADIUS + 1, BASELINE_LONG_MAX_LEN):
+            raise ValueError(f"grouped_splits: max_len={opts['max_len']!r}, expected null or an integer in {BASELINE_MAX_RADIUS + 1}.."
+                             f"{BASELINE_LONG_MAX_LEN} (null: rows of at most 64 frames)")
+        max_radius = opts["max_len"]
+    if not whole(opts["radius"], 0, max_radius):
+        raise ValueError(f"grouped_splits: radius={opts['radius']!r}, expected an integer in 0..{max_radius}")
+    return opts
+
+
+def apply_grouped_splits(dataset, opts, dataset_args, device, workdir=None):
+    """``dataset`` carrying the near-duplicate groups of the ``grouped_splits`` key (``slnlp.duplicate_groups``), formed once on
+    the device; with ``workdir`` the report without its per-row arrays goes to ``duplicate_groups.json`` there.  Every split
+    downstream -- the test split, the grid's folds, each fit's valid split -- then keeps a group on one side."""
+    from .dup_groups import duplicate_groups
+    metric = {}
+    if opts["metric"] == "phono":
+        codes = phono_field_codes(dataset, dataset_args, "grouped_splits")
+        F = int(np.asarray(codes).shape[1])
+        if opts["radius"] > BASELINE_MAX_RADIUS * F:
+            raise ValueError(f"grouped_splits: radius={opts['radius']!r}, expected an integer in 0..{BASELINE_MAX_RADIUS * F} (64 frames of {F} "
+                             "fields)")
+        metric = {"field_codes": codes}
+    res = duplicate_groups(dataset, opts["radius"], max_len=opts["max_len"], device=device, **metric)
+    if workdir is not None:
+        sizes = np.bincount(res["sizes"])
+        save_json({"options": dict(opts), **{k: int(res[k]) for k in GROUPED_SPLITS_REPORT},
+                   "size_hist": {str(s): int(c) for s, c in enumerate(sizes) if c}}, os.path.join(workdir, "duplicate_groups.json"))
+    return dataset.with_groups(res)
 
 
 def save_phono_baseline(est, train_data, test_data, opts, dataset_args, intervals, metrics, device, workdir, unit=None, field_codes=None):
@@ -1070,6 +1144,7 @@ def run(args):
     dynamics = train_dynamics_options(args.get("train_dynamics"))
     baseline = baseline_options(args.get("baseline"))
     phono = phono_baseline_options(args.get("phono_baseline"))
+    grouped = grouped_splits_options(args.get("grouped_splits"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -1081,6 +1156,8 @@ def run(args):
         dataset = G.broadcast_dataset(dataset, device)
     if args.get("debug"):
         dataset = dataset.truncated(int(args.get("cv", 5)) * 10)
+    if grouped is not None:                                  # before the rows are over-sampled and split: a copy keeps its original's group
+        dataset = apply_grouped_splits(dataset, grouped, args.get("dataset_args"), device, workdir if rank == 0 else None)
     if (args.get("dataset_args") or {}).get("balance_dataset") is True:
         dataset = balance_dataset(dataset, seed)
     test_data, train_data = dataset.split(float(args.get("test_size", 0.15)), seed)

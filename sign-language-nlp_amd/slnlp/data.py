@@ -23,14 +23,39 @@ class LabelArray(np.ndarray):
         return np.asarray(self)
 
 
+def group_ids(what, groups, n):
+    """``groups`` checked: an integer array [n] (or the dict ``slnlp.duplicate_groups`` returns: its ``"groups"``) -> a contiguous
+    int64 copy; anything else raises ValueError"""
+    if isinstance(groups, dict):
+        if "groups" not in groups:
+            raise ValueError(f"{what}: a dict without \"groups\" (expected what slnlp.duplicate_groups returns)")
+        groups = groups["groups"]
+    g = np.asarray(groups)
+    if g.dtype.kind not in "iu" or g.shape != (n,):
+        raise ValueError(f"{what}: groups must be an integer array [{n}] (one id per row), got {g.dtype} {tuple(g.shape)}")
+    return np.array(g, dtype=np.int64)
+
+
 class TokenDataset:
-    def __init__(self, X, lengths, y, vocab_X=None, vocab_y=None):
+    """``groups`` (None: no groups, every split is the one it always was): int64 [N], rows with one id are near-duplicates of each
+    other (``slnlp.duplicate_groups``) and every splitter -- ``split``, the grid's and ``cross_fit``'s folds, a fit's internal
+    valid split -- keeps them on one side.  Slicing carries them with the rows."""
+    groups = None                                            # (a dataset unpickled from before the attribute existed has none)
+
+    def __init__(self, X, lengths, y, vocab_X=None, vocab_y=None, groups=None):
         self.ids = np.ascontiguousarray(X, dtype=np.int64)
         self.lengths = np.ascontiguousarray(lengths, dtype=np.int64)
         self.y = np.ascontiguousarray(y, dtype=np.int64).view(LabelArray)
         assert self.ids.ndim == 2 and len(self.ids) == len(self.lengths) == len(self.y)
         self.vocab_X, self.vocab_y = vocab_X, vocab_y
         self.batch_first = True
+        self.groups = None if groups is None else group_ids("TokenDataset", groups, len(self.y))
+
+    def with_groups(self, groups):
+        """This dataset carrying ``groups``: an integer array [N], or the dict ``slnlp.duplicate_groups`` returns (None: without
+        any).  The rows are shared, not copied."""
+        return TokenDataset(self.ids, self.lengths, self.y, self.vocab_X, self.vocab_y,
+                            None if groups is None else group_ids("with_groups", groups, len(self)))
 
     def __len__(self):
         return len(self.y)
@@ -45,7 +70,9 @@ class TokenDataset:
         if isinstance(idx, tuple):        # sklearn's _array_indexing passes (indices, Ellipsis)
             idx = idx[0]
         idx = np.asarray(idx) if not isinstance(idx, slice) else idx
-        return TokenDataset(self.ids[idx], self.lengths[idx], self.y[idx], self.vocab_X, self.vocab_y)
+        if self.groups is None:
+            return TokenDataset(self.ids[idx], self.lengths[idx], self.y[idx], self.vocab_X, self.vocab_y)
+        return TokenDataset(self.ids[idx], self.lengths[idx], self.y[idx], self.vocab_X, self.vocab_y, self.groups[idx])
 
     def X(self):
         return self
@@ -67,12 +94,62 @@ class TokenDataset:
     def split(self, test_size=0.15, seed=1):
         """(test, train) like ``AslDataset.split(lengths=0.15, seed)`` (asl_dataset.py:220-253): that is
         ``torch.utils.data.random_split`` with ``Generator().manual_seed(seed)``, i.e. one ``torch.randperm`` whose
-        first ``round(test_size * N)`` entries are the test set and the rest the train set, both in permutation order."""
+        first ``round(test_size * N)`` entries are the test set and the rest the train set, both in permutation order.
+
+        With ``groups`` the same permutation is walked: while the test side holds fewer than ``n_test`` rows, a row whose group is
+        not yet placed brings its WHOLE group to the test side (members in permutation order); everything else goes to train, in
+        permutation order.  No group straddles the sides, the test side overshoots ``n_test`` by less than the largest group, and
+        all-singleton groups give exactly the ungrouped split."""
         import torch
         n_test = int(round(len(self) * test_size)) if isinstance(test_size, float) else int(test_size)
         gen = torch.Generator().manual_seed(seed) if seed else None
         perm = torch.randperm(len(self), generator=gen).numpy()
-        return self[perm[:n_test]], self[perm[n_test:]]
+        if self.groups is None:
+            return self[perm[:n_test]], self[perm[n_test:]]
+        test, train = grouped_split(perm, self.groups, n_test)
+        return self[test], self[train]
+
+
+def grouped_split(perm, groups, n_test):
+    """``TokenDataset.split``'s walk over ``perm`` with ``groups`` -> (test indices, train indices), both in permutation order"""
+    perm, groups = np.asarray(perm), np.asarray(groups)
+    members = {}
+    for i in perm.tolist():
+        members.setdefault(int(groups[i]), []).append(i)
+    side, test = {}, []                                      # group id -> True: on the test side
+    for i in perm.tolist():
+        g = int(groups[i])
+        if g not in side:
+            side[g] = len(test) < n_test
+            if side[g]:
+                test.extend(members[g])
+    train = [i for i in perm.tolist() if not side[int(groups[i])]]
+    return np.asarray(test, dtype=np.int64), np.asarray(train, dtype=np.int64)
+
+
+def group_folds(what, option, y, groups, n_splits):
+    """The folds of every splitter that honours groups, ``[(train indices, held-out indices), ...]``: ``StratifiedGroupKFold(
+    n_splits)`` without shuffle on (``y``, ``groups``); where that raises ValueError (no class has as many members as there are
+    folds) ``GroupKFold(n_splits)``; where there are fewer groups than folds a ValueError that names ``option`` and the counts --
+    never an ungrouped split."""
+    from sklearn.model_selection import GroupKFold, StratifiedGroupKFold
+    y, groups = np.asarray(y), np.asarray(groups)
+    n_groups = len(np.unique(groups))
+
+    def refuse(why):
+        return ValueError(f"{what}: {option}={n_splits} folds over {n_groups} groups of near-duplicate rows ({len(y)} rows): {why}; "
+                          f"lower {option}, lower the radius of the groups or drop them (with_groups(None))")
+    if n_groups < n_splits:
+        raise refuse("a group stays on one side, so there cannot be more folds than groups")
+    idx = np.zeros(len(y))
+    try:
+        return list(StratifiedGroupKFold(n_splits=n_splits).split(idx, y, groups))
+    except ValueError:
+        pass
+    try:
+        return list(GroupKFold(n_splits=n_splits).split(idx, y, groups))
+    except ValueError as e:
+        raise refuse(str(e)) from None
 
 
 class DeviceRows:

@@ -70,10 +70,16 @@ def estimate_cost(params, seq_len=48, n_samples=1, defaults=None):
     return float(n_samples) * float(epochs) * (COST_PER_STEP + float(N) * (COST_PER_LAYER + arith))
 
 
-def build_tasks(param_grid, y, cv, seq_len=48, defaults=None):
+def build_tasks(param_grid, y, cv, seq_len=48, defaults=None, groups=None):
+    """``groups`` (None: the stratified folds, unchanged): the dataset's near-duplicate groups, int64 [len(y)] -- the folds keep
+    each on one side (``data.group_folds``: ``StratifiedGroupKFold(cv)`` without shuffle)."""
     from sklearn.model_selection import StratifiedKFold
     cands = parameter_grid(param_grid)
-    folds = list(StratifiedKFold(n_splits=cv).split(np.zeros(len(y)), y))
+    if groups is None:
+        folds = list(StratifiedKFold(n_splits=cv).split(np.zeros(len(y)), y))
+    else:
+        from .data import group_folds, group_ids
+        folds = group_folds("build_tasks", "cv", y, group_ids("build_tasks", groups, len(y)), cv)
     tasks = [(ci, fi) for ci in range(len(cands)) for fi in range(len(folds))]
     cost = lambda t: estimate_cost(cands[tasks[t][0]], seq_len, len(folds[tasks[t][1]][0]), defaults)
     order = sorted(range(len(tasks)), key=lambda t: (-cost(t), t))
@@ -204,6 +210,9 @@ def comm_device(device="cpu"):
     return "cpu"
 
 
+GROUPS_FOLLOW = 1 << 40      # added to the fourth meta word when the dataset carries groups: without them the four words are what they were
+
+
 def broadcast_dataset(ds, device="cpu", src=0, force=False):
     """Rank ``src`` holds the dataset; everyone else receives it (ONE broadcast of a packed int64 buffer
     over RCCL/xGMI on GPUs: ~4 MB at N=10k, latency-bound).  ``force``: run the collectives even in a
@@ -215,22 +224,25 @@ def broadcast_dataset(ds, device="cpu", src=0, force=False):
     device = comm_device(device)
     meta = torch.zeros(4, dtype=torch.int64, device=device)
     if rank == src:
+        has_groups = getattr(ds, "groups", None) is not None
         meta[:] = torch.tensor([len(ds), ds.ids.shape[1], len(ds.vocab_X) if ds.vocab_X else 0,
-                                len(ds.vocab_y) if ds.vocab_y else 0])
+                                (len(ds.vocab_y) if ds.vocab_y else 0) + (GROUPS_FOLLOW if has_groups else 0)])
     dist.broadcast(meta, src)
     n, s, vx, vy = [int(v) for v in meta.cpu()]
-    buf = torch.empty(n * (s + 2), dtype=torch.int64, device=device)
+    has_groups, vy = vy >= GROUPS_FOLLOW, vy % GROUPS_FOLLOW
+    buf = torch.empty(n * (s + 2 + has_groups), dtype=torch.int64, device=device)
     if rank == src:
-        buf[:] = torch.from_numpy(np.concatenate([ds.ids.ravel(), ds.lengths, ds.y])).to(device)
+        buf[:] = torch.from_numpy(np.concatenate([ds.ids.ravel(), ds.lengths, ds.y] + ([ds.groups] if has_groups else []))).to(device)
     dist.broadcast(buf, src)
     if rank == src and not force:
         return ds
     from model.util import Vocab
     b = buf.cpu().numpy()
     keep = ds if rank == src else None
-    return TokenDataset(b[:n * s].reshape(n, s), b[n * s:n * s + n], b[n * s + n:],
+    return TokenDataset(b[:n * s].reshape(n, s), b[n * s:n * s + n], b[n * s + n:n * s + 2 * n],
                         keep.vocab_X if keep else (Vocab(vx) if vx else None),
-                        keep.vocab_y if keep else (Vocab(vy) if vy else None))
+                        keep.vocab_y if keep else (Vocab(vy) if vy else None),
+                        groups=b[n * s + 2 * n:] if has_groups else None)
 
 
 class WorkCounter:
@@ -461,7 +473,8 @@ class ShardedGridSearchCV:
         dist, rank, world = _dist()
         ds = broadcast_dataset(dataset, self.device, force=self.force_collectives)
         self._defaults_cache = self._defaults()
-        cands, folds, tasks, order = build_tasks(self.param_grid, ds.y, self.cv, ds.ids.shape[1], self._defaults_cache)
+        cands, folds, tasks, order = build_tasks(self.param_grid, ds.y, self.cv, ds.ids.shape[1], self._defaults_cache,
+                                                 groups=getattr(ds, "groups", None))
         group_fn = self.fit_and_score_group
         if self.lockstep > 1 and group_fn is None:
             from .lockstep import fit_and_score_group as group_fn

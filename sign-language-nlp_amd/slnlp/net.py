@@ -1080,6 +1080,9 @@ class NeuralNetClassifier(LogProbJudge, ClassifierMixin, BaseEstimator):
         ts = self.train_split
         if not ts:
             return np.arange(len(ds)), None
+        if getattr(ds, "groups", None) is not None:          # near-duplicate groups stay on one side: slnlp/data.py
+            from .data import group_folds
+            return group_folds("NeuralNetClassifier", "train_split", ds.y, ds.groups, int(ts))[0]
         from sklearn.model_selection import KFold, StratifiedKFold
         idx = np.arange(len(ds))
         try:

@@ -1819,6 +1819,75 @@ def field_knn_logp(buf, Lq, Lr, yr, prior, F, *, weights="distance", tau=1.0, no
                      normalize, lam, out)
 
 
+DUP_WIDTHS = {torch.uint8: 1, torch.uint16: 2}             # the bytes of a distance: edit_distances | edit_long_ / field_distances
+
+
+def dup_groups_buffers(N, device):
+    """The state and the outputs of one near-duplicate grouping of ``N`` rows (csrc/dup_groups.hip) as slices of ONE int32
+    allocation, so that ``dup_groups_download`` is one copy:
+
+        head int64 [8] | group int32 [N] | degree int32 [N] | parent int32 [N]
+
+    and the forest begun (``slnlp_dup_groups_begin``: parent[i] = i, degree 0, head 0) on the current stream of ``device``; no host
+    wait.  ``parent`` is the device-resident forest the chunks are linked into; it is never downloaded."""
+    _lib.require_gpu()
+    N = _int_in("dup_groups_buffers", "N", N, 1, _lib.EDIT_MAX_ROWS)
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        p = _packed.Packed(torch.int32, (("head", torch.int64, _lib.DUP_HEAD_BYTES // 8, 8), ("group", torch.int32, N, 4),
+                                         ("degree", torch.int32, N, 4), ("parent", torch.int32, N, 4)), device)
+        buf = _packed_dict(p, (N,))
+        check(load().slnlp_dup_groups_begin(ptr(buf["parent"]), ptr(buf["degree"]), N, ptr(buf["head"]), stream_ptr()), "dup_groups_buffers")
+    return buf
+
+
+def dup_groups_link(dist, q0, radius, buf):
+    """Link one chunk of distances into ``buf``'s forest (``slnlp_dup_groups_link``): ``dist`` a contiguous uint8 or uint16 [nq, N]
+    device tensor, what ``edit_distances`` / ``edit_long_distances`` / ``field_distances`` write for the data set's rows ``q0 .. q0 +
+    nq - 1`` against all N of them; ``radius`` in 0..254 (uint8) or 0..65534 (uint16).  Every row of the data set is linked exactly
+    once.  One launch on the current stream of ``dist``'s device; no host wait.  Returns ``buf``."""
+    what = "dup_groups_link"
+    _packed_buf(what, buf, "dup_groups_buffers(N, device)", (), None, more=1)
+    N, = buf["shape"]
+    dev = buf["flat"].device
+    if not (torch.is_tensor(dist) and dist.dtype in DUP_WIDTHS and dist.dim() == 2 and dist.shape[1] == N and dist.shape[0] >= 1
+            and dist.is_contiguous() and dist.device == dev):
+        raise ValueError(f"{what}: dist must be a contiguous uint8 or uint16 [nq >= 1, {N}] tensor on {dev}")
+    width, nq = DUP_WIDTHS[dist.dtype], int(dist.shape[0])
+    q0 = _int_in(what, "q0", q0, 0, N - 1)
+    radius = _int_in(what, "radius", radius, 0, 254 if width == 1 else 65534)
+    _lib.require_gpu()
+    with torch.cuda.device(dev):
+        check(load().slnlp_dup_groups_link(ptr(dist), width, nq, N, q0, radius, ptr(buf["parent"]), ptr(buf["degree"]), ptr(buf["head"]),
+                                           stream_ptr()), what)
+    return buf
+
+
+def dup_groups_finish(buf):
+    """Resolve ``buf``'s forest (``slnlp_dup_groups_finish``): ``buf["group"]`` = every row's root, the lowest row index of its
+    component; the head gets the groups and the edges.  Two launches on the current stream of ``buf``'s device; no host wait.
+    Returns ``buf``."""
+    what = "dup_groups_finish"
+    _packed_buf(what, buf, "dup_groups_buffers(N, device)", (), None, more=1)
+    N, = buf["shape"]
+    _lib.require_gpu()
+    with torch.cuda.device(buf["flat"].device):
+        check(load().slnlp_dup_groups_finish(ptr(buf["parent"]), N, ptr(buf["group"]), ptr(buf["head"]), stream_ptr()), what)
+    return buf
+
+
+def dup_groups_download(buf):
+    """What a grouping hands to the host in ONE device-to-host copy: {head int64 [8] = (groups, edges within the radius, unusable
+    rows, code, the degree sum, 0, 0, 0), group int32 [N], degree int32 [N]}.  A code other than 0 -- a kernel loop ran out of its N +
+    1 rounds, which the forest's invariants rule out -- raises RuntimeError."""
+    _packed_buf("dup_groups_download", buf, "dup_groups_buffers(N, device)", (), None, more=1)
+    out = buf["packed"].cut("head", "degree")
+    if int(out["head"][3]) != 0:
+        raise RuntimeError(f"dup_groups_download: the device reports code {int(out['head'][3])}: a union-find loop exhausted its bound of N + 1 "
+                           "rounds; the groups are not to be used")
+    return out
+
+
 def loo_objective_table(slots, device):
     """The table ``loo_objective`` fills: an int64 [slots, 4] device tensor of zeros, one 32-byte slot a candidate"""
     slots = _int_in("loo_objective_table", "slots", slots, 1, _lib.LOO_MAX_SLOTS)

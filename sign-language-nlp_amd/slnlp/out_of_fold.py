@@ -115,21 +115,32 @@ class OutOfFold(LogProbJudge, ClassifierMixin, BaseEstimator):
         return res
 
 
+def cross_fit_folds(dataset, cv):
+    """``cross_fit``'s folds ``[(train, held_out), ...]``: ``StratifiedKFold(cv)`` without shuffle on the labels -- with ``groups`` on
+    the dataset ``data.group_folds`` (``StratifiedGroupKFold(cv)`` without shuffle), as ``grid.build_tasks`` cuts them"""
+    y = np.asarray(dataset.y)
+    if getattr(dataset, "groups", None) is not None:
+        from .data import group_folds
+        return group_folds("cross_fit", "cv", y, dataset.groups, cv)
+    from sklearn.model_selection import StratifiedKFold
+    return list(StratifiedKFold(n_splits=cv).split(np.zeros(len(y)), y))
+
+
 def cross_fit(estimator, dataset, cv=5, seed=None, calibrated=True):
     """Cross-fit ``estimator`` on ``dataset`` and return the ``OutOfFold``: ``StratifiedKFold(cv)`` without shuffle on the dataset's
     labels -- ``grid.build_tasks``' splitter, so the folds are the grid search's -- and per fold a ``sklearn.base.clone`` of the
     estimator fitted on the other folds, one after the other.  ``seed``: ``torch.manual_seed(seed + f)`` before fold f's clone
-    initialises (None: torch's generator as it stands).  ``calibrated``: as in ``OutOfFold``."""
+    initialises (None: torch's generator as it stands).  ``calibrated``: as in ``OutOfFold``.  A dataset that carries ``groups``
+    (``with_groups``) is cut by ``cross_fit_folds`` instead: no group of near-duplicates straddles a fold, and each clone's internal
+    valid split keeps them whole too (the slices carry the groups)."""
     from sklearn.base import clone
-    from sklearn.model_selection import StratifiedKFold
     if not isinstance(dataset, TokenDataset):
         raise TypeError("cross_fit: dataset must be a slnlp.data.TokenDataset")
     cv = ops._int_in("cross_fit", "cv", cv, 2, ops._lib.ENSEMBLE_MAX_MEMBERS)
     if seed is not None:
         seed = ops._int_in("cross_fit", "seed", seed, 0, 2 ** 63 - 1 - cv)
-    y = np.asarray(dataset.y)
     members, folds = [], []
-    for f, (train, held_out) in enumerate(StratifiedKFold(n_splits=cv).split(np.zeros(len(y)), y)):
+    for f, (train, held_out) in enumerate(cross_fit_folds(dataset, cv)):
         if seed is not None:
             torch.manual_seed(seed + f)
         members.append(clone(estimator).fit(dataset[train]))
