@@ -224,6 +224,21 @@ int slnlp_attn_cross_bwd(const float* q, const float* kv, int64_t ld_kv, const f
                          const float* dctx, int B, int S, int H, int dh,
                          float* dq, float* dkv, int64_t ld_dkv,
                          float drop_p, int drop_site, const unsigned long long* rng, void* stream);
+/* The three launchers above with the arguments the plans pass: the output also (or only) as bf16 hi / lo planes, uint16 bit
+ * patterns with the row stride of the fp32 tensor (E for ctx, 3E for dqkv, ld_dkv for dkv), hi = bf16(x) rounded to nearest,
+ * lo = bf16(x - hi); q8 adds ctx as OCP e4m3 bytes (saturating at +-448).  hi and lo go together, q8 needs them.  ctx / dqkv
+ * may be NULL with both planes and S <= 64: then only the planes are written (16-byte row pieces when dh % 8 == 0, the planes
+ * are 16-byte aligned and there is no q8; element stores otherwise -- the same bits).  long_scratch: as for
+ * slnlp_attn_self_bwd_long, required for S > 64.  SLNLP_ERR_INVALID_ARG with a message before any launch otherwise. */
+int slnlp_attn_self_fwd_ex(const float* qkv, const int64_t* ids, int64_t ld_ids, int64_t pad_idx, int causal, int B, int S, int H,
+                           int dh, float* ctx /* or NULL */, float* probs, float drop_p, int drop_site,
+                           const unsigned long long* rng, uint16_t* hi, uint16_t* lo, uint8_t* q8, void* stream);
+int slnlp_attn_self_bwd_ex(const float* qkv, const float* probs, const float* dctx, int B, int S, int H, int dh,
+                           float* dqkv /* or NULL */, float drop_p, int drop_site, const unsigned long long* rng,
+                           float* long_scratch, uint16_t* hi, uint16_t* lo, void* stream);
+int slnlp_attn_cross_bwd_ex(const float* q, const float* kv, int64_t ld_kv, const float* probs, const float* dctx, int B, int S,
+                            int H, int dh, float* dq, float* dkv, int64_t ld_dkv, float drop_p, int drop_site,
+                            const unsigned long long* rng, uint16_t* hi, uint16_t* lo, void* stream);
 
 /* The same attention WITHOUT projecting the memory (csrc/attention_mem.hip; what the Transformer plan's decoder runs): with one
  * query per sequence, k_s = Wk mem_s + bk and v_s = Wv mem_s + bv re-associate into per-head B-row products around kernels that

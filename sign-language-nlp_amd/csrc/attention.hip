@@ -735,4 +735,38 @@ int slnlp_attn_cross_bwd(const float* q, const float* kv, int64_t ld_kv, const f
     return slnlp::attn_cross_bwd(q, kv, ld_kv, probs, dctx, B, S, H, dh, dq, dkv, ld_dkv, drop_p, drop_site, rng,
                                  (hipStream_t)stream);
 }
+
+// The same launchers with the arguments the plans pass (tf_plan.hip): output planes, and no fp32 output at all where the
+// consumers read the planes.  Everything is refused here, before any launch.
+static int check_plane_args(const char* who, const void* fp32_out, const char* out_name, const uint16_t* hi, const uint16_t* lo,
+                            const uint8_t* q8, int S) {
+    SLNLP_CHECK_ARG((hi != nullptr) == (lo != nullptr), "%s: the hi and lo planes go together", who);
+    SLNLP_CHECK_ARG(!q8 || hi, "%s: a q8 plane needs the hi and lo planes", who);
+    SLNLP_CHECK_ARG(fp32_out || (hi && S <= slnlp::SMAX), "%s: null pointer (%s may be NULL only with output planes, S <= %d)", who,
+                    out_name, slnlp::SMAX);
+    return 0;
+}
+int slnlp_attn_self_fwd_ex(const float* qkv, const int64_t* ids, int64_t ld_ids, int64_t pad_idx, int causal, int B, int S, int H,
+                           int dh, float* ctx, float* probs, float drop_p, int drop_site, const unsigned long long* rng,
+                           uint16_t* hi, uint16_t* lo, uint8_t* q8, void* stream) {
+    SLNLP_TRY(check_plane_args("attn_self_fwd_ex", ctx, "ctx", hi, lo, q8, S));
+    SLNLP_CHECK_ARG(!ids || S <= 0 || ld_ids >= S, "attn_self_fwd_ex: ld_ids %ld < S %d", (long)ld_ids, S);
+    return slnlp::attn_self_fwd(qkv, ids, ld_ids, pad_idx, causal, B, S, H, dh, ctx, probs, drop_p, drop_site, rng,
+                                (hipStream_t)stream, slnlp::PlaneOut{hi, lo, q8});
+}
+int slnlp_attn_self_bwd_ex(const float* qkv, const float* probs, const float* dctx, int B, int S, int H, int dh, float* dqkv,
+                           float drop_p, int drop_site, const unsigned long long* rng, float* long_scratch, uint16_t* hi,
+                           uint16_t* lo, void* stream) {
+    SLNLP_TRY(check_plane_args("attn_self_bwd_ex", dqkv, "dqkv", hi, lo, nullptr, S));
+    SLNLP_CHECK_ARG(S <= slnlp::SMAX || long_scratch, "attn_self_bwd_ex: S=%d > %d needs long_scratch", S, slnlp::SMAX);
+    return slnlp::attn_self_bwd(qkv, probs, dctx, B, S, H, dh, dqkv, drop_p, drop_site, rng, (hipStream_t)stream,
+                                slnlp::PlaneOut{hi, lo, nullptr}, long_scratch);
+}
+int slnlp_attn_cross_bwd_ex(const float* q, const float* kv, int64_t ld_kv, const float* probs, const float* dctx, int B, int S,
+                            int H, int dh, float* dq, float* dkv, int64_t ld_dkv, float drop_p, int drop_site,
+                            const unsigned long long* rng, uint16_t* hi, uint16_t* lo, void* stream) {
+    SLNLP_CHECK_ARG((hi != nullptr) == (lo != nullptr), "attn_cross_bwd_ex: the hi and lo planes go together");
+    return slnlp::attn_cross_bwd(q, kv, ld_kv, probs, dctx, B, S, H, dh, dq, dkv, ld_dkv, drop_p, drop_site, rng,
+                                 (hipStream_t)stream, slnlp::PlaneOut{hi, lo, nullptr});
+}
 }

@@ -254,7 +254,7 @@ __device__ __forceinline__ bool dropout_keep(const unsigned long long* rng, int 
 // ------------------------------------------------------- bf16 plane sinks ----
 // Producers of GEMM operands also emit the value as bf16 hi / lo planes (same row stride as the fp32
 // tensor) so the consuming GEMM can stage them by LDS-DMA with no conversion (gemm_planes.hip).
-// hi = truncated upper half of the fp32 word, lo = rne_bf16(x - hi): hi + lo == x to ~2^-16.
+// hi = bf16(x) rounded to nearest, lo = bf16(x - hi) (split_bf16 below): hi + lo == x to ~2^-16.
 struct PlaneOut {
     unsigned short* hi = nullptr;
     unsigned short* lo = nullptr;

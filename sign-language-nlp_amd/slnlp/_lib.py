@@ -118,6 +118,9 @@ SIGNATURES = {
     "slnlp_attn_self_bwd_long": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]),
     "slnlp_attn_cross_fwd": (i32, [vp, vp, i64, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp]),
     "slnlp_attn_cross_bwd": (i32, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, i64, f32, i32, vp, vp]),
+    "slnlp_attn_self_fwd_ex": (i32, [vp, vp, i64, i64, i32, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp]),
+    "slnlp_attn_self_bwd_ex": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, f32, i32, vp, vp, vp, vp, vp]),
+    "slnlp_attn_cross_bwd_ex": (i32, [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, i64, f32, i32, vp, vp, vp, vp]),
     "slnlp_attn_mem_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, f32, i32, vp, vp]),
     "slnlp_attn_mem_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp]),
     "slnlp_attn_mem_dmem_all": (i32, [vp, i32, i32, i32, i32, i32, vp, f32, vp, vp]),

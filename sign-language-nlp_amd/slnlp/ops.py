@@ -340,6 +340,79 @@ def attn_cross_bwd(q, kv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, 
     return dq, dkv
 
 
+def _attn_ex_outputs(what, like_shape, device, want_planes, planes_only, want_q8, out, key):
+    """The fp32 output (None under ``planes_only``), its planes and its q8 plane for the ``attn_*_ex`` wrappers; ``out`` may hold
+    any of them pre-allocated (``key``, "planes" = (hi, lo), "q8"), e.g. pre-filled or padded buffers of a test."""
+    out = dict(out or {})
+    want_planes = want_planes or planes_only or want_q8 or "planes" in out
+    fp32 = None if planes_only else out.get(key)
+    if fp32 is None and not planes_only:
+        fp32 = torch.empty(*like_shape, dtype=torch.float32, device=device)
+    planes = out.get("planes")
+    if planes is None and want_planes:
+        planes = (torch.empty(*like_shape, dtype=torch.int16, device=device), torch.empty(*like_shape, dtype=torch.int16, device=device))
+    q8 = out.get("q8")
+    if q8 is None and want_q8:
+        q8 = torch.empty(*like_shape, dtype=torch.uint8, device=device)
+    for t in (fp32,) + tuple(planes or ()) + (q8,):
+        assert t is None or (t.stride(-1) == 1 and t.stride(0) == like_shape[-1]), f"{what}: outputs have the fp32 tensor's row stride"
+    return fp32, planes, q8
+
+
+def attn_self_fwd_ex(qkv, ids, pad_idx, *, B, S, H, dh, causal=True, drop_p=0.0, drop_site=0, rng=None, want_planes=False,
+                     planes_only=False, want_q8=False, out=None):
+    """``attn_self_fwd`` as the plans call it (``slnlp_attn_self_fwd_ex``) -> dict of ctx (None under ``planes_only``: the call
+    passes a null fp32 output), probs, planes ((hi, lo) int16 bit patterns | None) and q8 (uint8 e4m3 | None).  ``ids`` may be a
+    view whose row stride is not S.  ``out``: a dict with any of ctx / probs / planes / q8 to write into."""
+    _lib.require_gpu()
+    E = H * dh
+    ctx, planes, q8 = _attn_ex_outputs("attn_self_fwd_ex", (S * B, E), qkv.device, want_planes, planes_only, want_q8, out, "ctx")
+    probs = (out or {}).get("probs")
+    if probs is None:
+        probs = torch.empty(B, H, S, S, dtype=torch.float32, device=qkv.device)
+    hi, lo = planes or (None, None)
+    check(load().slnlp_attn_self_fwd_ex(ptr(qkv), ptr(ids), ids.stride(0) if ids is not None else 0, pad_idx, int(causal), B, S, H, dh,
+                                        ptr(ctx), ptr(probs), drop_p, drop_site, ptr(rng), ptr(hi), ptr(lo), ptr(q8), stream_ptr()),
+          "attn_self_fwd_ex")
+    return dict(ctx=ctx, probs=probs, planes=planes, q8=q8)
+
+
+def attn_self_bwd_ex(qkv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None, want_planes=False, planes_only=False,
+                     out=None):
+    """``attn_self_bwd`` as the plans call it (``slnlp_attn_self_bwd_ex``) -> dict of dqkv (None under ``planes_only``) and planes
+    ((hi, lo) int16 | None), row stride 3E.  ``out``: a dict with dqkv / planes to write into."""
+    _lib.require_gpu()
+    dqkv, planes, _ = _attn_ex_outputs("attn_self_bwd_ex", (S * B, 3 * H * dh), qkv.device, want_planes, planes_only, False, out, "dqkv")
+    scratch = None
+    if S > 64:
+        scratch = torch.empty(int(load().slnlp_attn_long_scratch_bytes(B, S, H)), dtype=torch.uint8, device=qkv.device)
+    hi, lo = planes or (None, None)
+    check(load().slnlp_attn_self_bwd_ex(ptr(qkv), ptr(probs), ptr(dctx), B, S, H, dh, ptr(dqkv), drop_p, drop_site, ptr(rng),
+                                        ptr(scratch), ptr(hi), ptr(lo), stream_ptr()), "attn_self_bwd_ex")
+    return dict(dqkv=dqkv, planes=planes)
+
+
+def attn_cross_bwd_ex(q, kv, probs, dctx, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None, want_planes=False, out=None):
+    """``attn_cross_bwd`` with the planes of dkv (``slnlp_attn_cross_bwd_ex``) -> dict of dq, dkv and planes ((hi, lo) int16 | None).
+    ``out``: a dict with dkv / planes to write into; the planes have dkv's row stride (column views of wider buffers are fine)."""
+    _lib.require_gpu()
+    out = dict(out or {})
+    dq = torch.empty_like(q)
+    dkv = out.get("dkv")
+    if dkv is None:
+        dkv = torch.empty(kv.shape, dtype=torch.float32, device=kv.device)
+    planes = out.get("planes")
+    if planes is None and want_planes:
+        planes = (torch.empty(dkv.shape, dtype=torch.int16, device=kv.device), torch.empty(dkv.shape, dtype=torch.int16, device=kv.device))
+    for t in planes or ():
+        assert t.stride(0) == dkv.stride(0) and t.stride(1) == 1, "attn_cross_bwd_ex: the planes have dkv's row stride"
+    hi, lo = planes or (None, None)
+    check(load().slnlp_attn_cross_bwd_ex(ptr(q), ptr(kv), kv.stride(0), ptr(probs), ptr(dctx), B, S, H, dh, ptr(dq), ptr(dkv),
+                                         dkv.stride(0), drop_p, drop_site, ptr(rng), ptr(hi), ptr(lo), stream_ptr()),
+          "attn_cross_bwd_ex")
+    return dict(dq=dq, dkv=dkv, planes=planes)
+
+
 def attn_mem_fwd(qk, mem, bv, *, B, S, H, dh, drop_p=0.0, drop_site=0, rng=None, out=None):
     """Cross-attention over the unprojected memory, forward (``slnlp_attn_mem_fwd``): qk [B*H, E], mem [S*B, E], bv [E] ->
     (mbar [B*H, E], psum [B*H], probs [B*H, S], ctx0 [B, E]); ``out``: those four tensors to write into, or None."""

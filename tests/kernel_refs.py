@@ -105,6 +105,13 @@ def fmt_product(precision):
     return lambda h, w: _FmtProduct.apply(h, w, precision)
 
 
+def planes_are_the_split_of(planes, x):
+    """hi / lo planes (int16 bit patterns) == bf16_split(x), as bf16 bit patterns."""
+    hi, lo = bf16_split(x.detach().cpu())
+    return (torch.equal(planes[0].cpu(), hi.to(torch.bfloat16).view(torch.int16))
+            and torch.equal(planes[1].cpu(), lo.to(torch.bfloat16).view(torch.int16)))
+
+
 def rel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
@@ -157,14 +164,15 @@ def chain_yardsticks(rnn_type, inp, precision):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def _mha_ref(qkv, ids, pad, B, S, H, dh, causal, mask=None, p=0.0):
+def _mha_ref(qkv, ids, pad, B, S, H, dh, causal, mask=None, p=0.0, product=torch.matmul):
     """Self-attention core of one layer for any S: qkv [S*B, 3E] (q | k | v, rows time-major) -> (ctx [S*B, E], probs
     [B, H, S, S] before dropout); key j is blocked for query i where j > i (causal) or ids[b, j] == pad (ids may be None);
-    mask [B, H, S, S]: dropout keep-mask on the probabilities."""
+    mask [B, H, S, S]: dropout keep-mask on the probabilities.  ``product(a, b)`` stands for a @ b in the two contractions
+    (and, through autograd, in their gradients): tests/attention_ref.py runs them on format-rounded operands."""
     E = H * dh
     x = qkv.view(S, B, 3, H, dh)
     q, k, v = [x[:, :, i].permute(1, 2, 0, 3) for i in range(3)]           # [B,H,S,dh]
-    sc = q @ k.transpose(-1, -2) / math.sqrt(dh)
+    sc = product(q, k.transpose(-1, -2)) / math.sqrt(dh)
     blocked = torch.zeros(B, 1, S, S, dtype=torch.bool)
     if causal:
         blocked = blocked | torch.triu(torch.ones(S, S, dtype=torch.bool), 1)
@@ -172,7 +180,7 @@ def _mha_ref(qkv, ids, pad, B, S, H, dh, causal, mask=None, p=0.0):
         blocked = blocked | (ids == pad).view(B, 1, 1, S)
     pr = torch.softmax(sc.masked_fill(blocked, float("-inf")), -1)
     pd = pr if mask is None else pr * mask / (1 - p)
-    ctx = (pd @ v).permute(2, 0, 1, 3).reshape(S * B, E)
+    ctx = product(pd, v).permute(2, 0, 1, 3).reshape(S * B, E)
     return ctx, pr
 
 

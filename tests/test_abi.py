@@ -77,6 +77,38 @@ def test_argument_validation_returns_codes_not_aborts(lib):
     a = _lib.GemmArgs()
     assert lib.slnlp_gemm(C.byref(a), None) == 1                  # null operands -> SLNLP_ERR_INVALID_ARG
     assert lib.slnlp_gemm(None, None) == 1
+    # the attention launchers that take output planes: every refusal comes before a launch, so none needs a device
+    buf = (C.c_float * 16)()
+    p = C.cast(buf, C.c_void_p).value                             # any non-null address: nothing below gets as far as reading it
+    INVALID = 1
+
+    def fwd(S=20, dh=8, ctx=p, hi=None, lo=None, q8=None, drop=0.0, ld_ids=None, B=2):
+        return lib.slnlp_attn_self_fwd_ex(p, p, S if ld_ids is None else ld_ids, 1, 1, B, S, 2, dh, ctx, p, drop, 0, None, hi, lo, q8, None)
+
+    def bwd(S=20, dh=8, dqkv=p, hi=None, lo=None, scratch=None, drop=0.0, B=2):
+        return lib.slnlp_attn_self_bwd_ex(p, p, p, B, S, 2, dh, dqkv, drop, 0, None, scratch, hi, lo, None)
+
+    def xbwd(S=20, dh=8, hi=None, lo=None, ld=32, drop=0.0, dkv=p):
+        return lib.slnlp_attn_cross_bwd_ex(p, p, ld, p, p, 2, S, 2, dh, p, dkv, ld, drop, 0, None, hi, lo, None)
+
+    for call in (fwd, bwd, xbwd):
+        for kw in (dict(hi=p), dict(lo=p)):                       # one plane of a pair without the other
+            assert call(**kw) == INVALID and b"go together" in lib.slnlp_last_error(), (call.__name__, kw)
+        assert call(dh=6, hi=p, lo=p) == INVALID and b"head_dim" in lib.slnlp_last_error()       # the existing shape checks
+        assert call(S=0, hi=p, lo=p) == INVALID
+        assert call(drop=0.25, hi=p, lo=p) == INVALID and b"dropout" in lib.slnlp_last_error()   # dropout without its rng
+        assert call(drop=1.0, hi=p, lo=p) == INVALID and b"dropout" in lib.slnlp_last_error()
+    assert fwd(q8=p) == INVALID and b"q8" in lib.slnlp_last_error()                              # q8 without hi / lo
+    assert fwd(ctx=None) == INVALID and b"null" in lib.slnlp_last_error()                        # no fp32 output and no planes
+    assert bwd(dqkv=None) == INVALID and b"null" in lib.slnlp_last_error()
+    assert fwd(S=65, ctx=None, hi=p, lo=p) == INVALID and b"S <= 64" in lib.slnlp_last_error()   # planes only: one-tile kernels
+    assert bwd(S=65, dqkv=None, hi=p, lo=p, scratch=p) == INVALID and b"S <= 64" in lib.slnlp_last_error()
+    assert bwd(S=65, hi=p, lo=p) == INVALID and b"scratch" in lib.slnlp_last_error()             # S > 64 without long_scratch
+    assert fwd(ld_ids=19) == INVALID and b"ld_ids" in lib.slnlp_last_error()
+    assert fwd(B=0, hi=p, lo=p) == INVALID and bwd(B=0, hi=p, lo=p) == INVALID
+    assert xbwd(ld=31, hi=p, lo=p) == INVALID and b"ld" in lib.slnlp_last_error()                # ld_kv / ld_dkv: multiples of 4, >= 2E
+    assert xbwd(ld=28, hi=p, lo=p) == INVALID
+    assert xbwd(dkv=None, hi=p, lo=p) == INVALID and b"null" in lib.slnlp_last_error()           # the cross backward always writes fp32
 
 
 def test_attn_mem_entry_points_validate_before_they_touch_a_device(lib):

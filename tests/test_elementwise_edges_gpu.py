@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import elementwise_ref as er
-import kernel_refs as kr
+from kernel_refs import planes_are_the_split_of
 
 pytestmark = pytest.mark.gpu
 
@@ -57,13 +57,6 @@ def bits(t):
 
 def same_bits(a, b):
     return torch.equal(bits(a), bits(b))
-
-
-def planes_are_the_split_of(planes, x):
-    """hi / lo planes == kernel_refs.bf16_split(x), as bf16 bit patterns."""
-    hi, lo = kr.bf16_split(x.detach().cpu())
-    return (torch.equal(planes[0].cpu(), hi.to(torch.bfloat16).view(torch.int16))
-            and torch.equal(planes[1].cpu(), lo.to(torch.bfloat16).view(torch.int16)))
 
 
 def exactly_zero(t):
