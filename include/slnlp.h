@@ -1252,6 +1252,69 @@ int slnlp_dup_groups_link(const void* dist /* [nq, N] */, int width, int64_t nq,
                           int32_t* parent /* [N] */, int32_t* degree /* [N] */, int64_t* head /* [8] */, void* stream);
 int slnlp_dup_groups_finish(const int32_t* parent /* [N] */, int64_t N, int32_t* group /* [N] */, int64_t* head /* [8] */, void* stream);
 
+/* ------------------------------------------- gloss structure of one data set (csrc/gloss_structure.hip) --
+ * What the LABELS of a data set look like under one of the edit distances above (slnlp.gloss_structure): a silhouette per row, a
+ * medoid per class, and the class-to-class distance table.  The device forms the integers; the host divides.  Integers only,
+ * integer atomics only: the result is a pure function of the arguments -- the same bytes on every run, on any stream, and for any
+ * chunking of the rows.
+ *
+ * The data set has N rows; label[i] is in 0..C-1, or -1 for a row LEFT OUT (the host gives -1 to the rows the metric refuses).  d is
+ * the N x N matrix slnlp_edit_distances (width 1: uint8, sentinel 255), slnlp_edit_long_distances or slnlp_field_distances[_w]
+ * (width 2: uint16, sentinel 65535) writes with the data set on both sides; d <= max_distance.
+ *
+ *   n_c               #{j : label[j] = c}
+ *   T[i, c]           for a labelled row i: the sum of d(i, j) over j != i with label[j] = c.  Exact; below 2^32, since begin refuses
+ *                     max_distance N >= 2^32.
+ *   own[i]            T[i, label[i]]
+ *   other_class[i]    among the classes c != label[i] with n_c > 0 the one that minimises T[i, c] / n_c.  The comparison is exact:
+ *                     T[i, a] n_b < T[i, b] n_a in 64-bit integers; ties go to the LOWER class.  -1 if there is no such class.
+ *   other[i]          T[i, other_class[i]], 0 where other_class is -1.
+ *   class_sum[a, b]   the sum over the rows i of class a of T[i, b]: int64, symmetric; the diagonal counts every within-class pair
+ *                     twice.
+ *   medoid[c]         the row of class c with the smallest own[i], ties to the LOWEST row; -1 for an empty class.
+ *   A row left out writes own = other = 0 and other_class = -1, and is no column of anybody's sum.
+ *
+ * The host's values, in fp64 from those integers (sklearn's silhouette_samples conventions): a = own / (n - 1), b = other / n_other,
+ * s = (b - a) / max(a, b), and s = 0 where the row's class has one member, where there is no other class, or where max(a, b) = 0;
+ * the mean distance of classes a != b is class_sum[a, b] / (n_a n_b), of a class to itself class_sum[a, a] / (n_a (n_a - 1)).
+ *
+ * The N x N matrix need not be resident: the caller forms the rows q0 .. q0 + nq - 1 against all N rows, hands them to
+ * slnlp_gloss_structure_rows and reuses the memory for the next chunk.  Every row arrives exactly once; the chunks may come in any
+ * order.  Three entry points, all queued, no host wait:
+ *
+ * slnlp_gloss_structure_begin: count = the n_c (integer atomics), class_sum = 0, med_sum = UINT64_MAX, medoid = "none", head zeroed
+ * but for the labelled rows and the rows left out.  Two launches.
+ *
+ * slnlp_gloss_structure_rows: dist [nq, N] of `width` bytes an element, row qi the distances of row i = q0 + qi.  A wave per row
+ * adds every element into a table of C uint32 sums in LDS (LDS integer adds; four waves a block: 16 C bytes), then takes own,
+ * other and other_class from the table, adds T[i, c] to class_sum[label[i], c] (64-bit atomic adds) and takes a 64-bit atomic
+ * minimum of own[i] into med_sum[label[i]].  The sentinel at a pair of two labelled rows is a breach of the contract, not data:
+ * it sets code bit 0 and adds nothing.  One launch.
+ *
+ * slnlp_gloss_structure_finish: every row with own[i] == med_sum[label[i]] takes a 32-bit atomic minimum of i into
+ * medoid[label[i]]; then "none" becomes -1 and head[1] = the classes that have a medoid.  Two launches.
+ *
+ *   head int64 [8]    labelled rows | non-empty classes | rows left out | code | the sum of own | 0 0 0
+ *
+ * code is 0, or: bit 0 (1) the sentinel met at a labelled pair; bit 1 (2) a label outside -1..C-1 (such a row is treated as left
+ * out by every kernel: no index is formed from its label).  With a code the result is not to be used.
+ *
+ * Errors (SLNLP_ERR_INVALID_ARG with a message that names the entry point, before anything is launched): a null pointer; N or nq
+ * outside 1..SLNLP_EDIT_MAX_ROWS; C outside 1..SLNLP_GLOSS_MAX_CLASSES; max_distance outside 1..65534 or max_distance N >= 2^32;
+ * q0 < 0 or q0 + nq > N; more than SLNLP_EDIT_MAX_PAIRS pairs; width not 1 or 2; a misaligned pointer (dist: width bytes; label,
+ * count, own, other, other_class, medoid: 4; class_sum, med_sum, head: 8); an output overlapping an input or another output. */
+#define SLNLP_GLOSS_HEAD_BYTES 64
+#define SLNLP_GLOSS_MAX_CLASSES 1024
+int slnlp_gloss_structure_begin(const int32_t* label /* [N] */, int64_t N, int64_t C, int64_t max_distance, int32_t* count /* [C] */,
+                                int64_t* class_sum /* [C, C] */, int64_t* med_sum /* [C] */, int32_t* medoid /* [C] */, int64_t* head /* [8] */,
+                                void* stream);
+int slnlp_gloss_structure_rows(const void* dist /* [nq, N] */, int width, int64_t nq, int64_t N, int64_t q0, const int32_t* label /* [N] */,
+                               int64_t C, const int32_t* count /* [C] */, uint32_t* own /* [N] */, uint32_t* other /* [N] */,
+                               int32_t* other_class /* [N] */, int64_t* class_sum /* [C, C] */, int64_t* med_sum /* [C] */,
+                               int64_t* head /* [8] */, void* stream);
+int slnlp_gloss_structure_finish(const int32_t* label /* [N] */, const uint32_t* own /* [N] */, const int64_t* med_sum /* [C] */, int64_t N,
+                                 int64_t C, int32_t* medoid /* [C] */, int64_t* head /* [8] */, void* stream);
+
 /* ------------------------------------- phonology-weighted edit-distance neighbours (csrc/field_knn.hip) --
  * The same search under a WEIGHTED edit distance (slnlp.PhonoKNN, slnlp.split_audit(field_codes=...)): a token of this data is a
  * composition of F phonological fields, and substituting one frame for another costs the number of fields in which they differ.

@@ -192,6 +192,9 @@ SIGNATURES = {
     "slnlp_dup_groups_begin": (i32, [vp, vp, i64, vp, vp]),
     "slnlp_dup_groups_link": (i32, [vp, i32, i64, i64, i64, i64, vp, vp, vp, vp]),
     "slnlp_dup_groups_finish": (i32, [vp, i64, vp, vp, vp]),
+    "slnlp_gloss_structure_begin": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+    "slnlp_gloss_structure_rows": (i32, [vp, i32, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "slnlp_gloss_structure_finish": (i32, [vp, vp, vp, i64, i64, vp, vp, vp]),
     "slnlp_dropout_mask": (i32, [vp, i32, i32, f32, i32, vp, vp]),
     "slnlp_balance_plan_create": (i32, [vp, i64, i32, vp, C.POINTER(vp)]),
     "slnlp_balance_plan_rows": (i64, [vp]),
@@ -367,6 +370,8 @@ FIELD_MAX_WEIGHT = 16                           # SLNLP_FIELD_MAX_WEIGHT
 LOO_SLOT_BYTES = 32                             # SLNLP_LOO_SLOT_BYTES
 LOO_MAX_SLOTS = 65536                           # SLNLP_LOO_MAX_SLOTS
 DUP_HEAD_BYTES = 64                             # SLNLP_DUP_HEAD_BYTES
+GLOSS_HEAD_BYTES = 64                           # SLNLP_GLOSS_HEAD_BYTES
+GLOSS_MAX_CLASSES = 1024                        # SLNLP_GLOSS_MAX_CLASSES
 CONFUSION_MAX_V = 4096                          # SLNLP_CONFUSION_MAX_V
 PAIRS_MAX = 64                                  # SLNLP_PAIRS_MAX
 BOOT_MAX_REPLICATES = 65536                     # SLNLP_BOOT_MAX_REPLICATES

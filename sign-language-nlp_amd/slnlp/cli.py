@@ -172,7 +172,20 @@ its original's group).  ``metric: unit`` is ``baseline``'s distance (``max_len``
 Where ``baseline`` is set too, ``test_split_audit.json`` is the end-to-end proof: at a radius up to this one it reports no twin of
 a test row in train.
 
-Without the thirteen keys the workdir holds exactly the files listed above.
+A top-level ``gloss_structure: {metric: unit, max_len: null, top: 50}`` (all optional, these defaults) reports, before anything is
+read off a model, what the glosses of the TRAIN split look like under the metric (``slnlp.gloss_structure``,
+csrc/gloss_structure.hip): ``metric: unit`` is ``baseline``'s distance (``max_len``: 65..512 for longer rows), ``metric: phono``
+``phono_baseline``'s, from ``dataset_args.fields``; it takes no ``max_len``.  Rank 0 writes
+
+    train_gloss_structure.json        the options, rows, flagged, max_distance, mean_silhouette, misplaced_share, per class its name,
+                                      support, silhouette and medoid row, the ``top`` closest pairs of glosses (joinable against
+                                      ``test_confused_pairs.csv``) and the ``top`` misplaced rows.  With ``metric: phono`` and
+                                      ``phono_baseline.fit_weights`` set: ``mean_silhouette_unit`` and ``mean_silhouette_weighted``
+                                      side by side, the report itself under the fitted weights
+    train_gloss_structure_rows.csv    row, label, name, a, b, silhouette, nearest gloss, its name, whether the row is its gloss's medoid
+    train_gloss_distance.csv          the C x C mean distances between glosses, a header row and column of gloss names
+
+Without the fourteen keys the workdir holds exactly the files listed above.
 """
 import argparse
 import copy
@@ -187,7 +200,7 @@ import numpy as np
 DICT_ARGS = ("early_stopping", "gradient_clipping", "lr_scheduler", "dataset_args", "model_args", "optimizer_args",
              "criterion_args", "iterator_train_args", "grid_args", "calibration", "error_analysis", "confidence_intervals",
              "ensemble", "ranking", "conformal", "prior_shift", "selective", "label_audit", "attribution", "train_dynamics", "baseline", "phono_baseline",
-             "grouped_splits")
+             "grouped_splits", "gloss_structure")
 SCALAR_ARGS = {"model": str, "optimizer": str, "criterion": str, "cv": int, "scoring": str, "verbose": int, "n_jobs": int,
                "workdir": str, "debug": lambda s: s.lower() in ("1", "true", "yes"),
                "cuda": lambda s: s.lower() in ("1", "true", "yes"), "seed": int, "lr": float, "max_epochs": int,
@@ -861,6 +874,79 @@ def apply_grouped_splits(dataset, opts, dataset_args, device, workdir=None):
     return dataset.with_groups(res)
 
 
+GLOSS_STRUCTURE_DEFAULTS = {"metric": "unit", "max_len": None, "top": 50}
+
+
+def gloss_structure_options(setting):
+    """The ``gloss_structure`` key with its defaults filled in -- {metric unit, max_len null, top 50} -- or None when the key is
+    absent.  Anything but a dict over these three keys ({}: all defaults) raises ValueError: ``metric`` "unit" or "phono" as in
+    ``grouped_splits``; ``max_len`` null or an integer in 65..512, with the unit metric only; ``top`` an integer in 0..10000."""
+    if setting is None:
+        return None
+    known = tuple(GLOSS_STRUCTURE_DEFAULTS)
+    if not isinstance(setting, dict):
+        raise ValueError(f"gloss_structure={setting!r}: expected a dict with keys among {known}")
+    unknown = sorted(set(setting) - set(known), key=str)
+    if unknown:
+        raise ValueError(f"gloss_structure: unknown keys {unknown} (known: {known})")
+    opts = dict(GLOSS_STRUCTURE_DEFAULTS, **setting)
+    whole = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi
+    if opts["metric"] not in GROUPED_SPLITS_METRICS:
+        raise ValueError(f"gloss_structure: metric={opts['metric']!r}, expected one of {GROUPED_SPLITS_METRICS}")
+    if opts["max_len"] is not None:
+        if opts["metric"] == "phono":
+            raise ValueError(f"gloss_structure: max_len={opts['max_len']!r} with metric phono: the phonology-weighted search is limited to "
+                             f"{BASELINE_MAX_RADIUS} frames (only the unit metric takes max_len)")
+        if not whole(opts["max_len"], BASELINE_MAX_RADIUS + 1, BASELINE_LONG_MAX_LEN):
+            raise ValueError(f"gloss_structure: max_len={opts['max_len']!r}, expected null or an integer in {BASELINE_MAX_RADIUS + 1}.."
+                             f"{BASELINE_LONG_MAX_LEN} (null: rows of at most 64 frames)")
+    if not whole(opts["top"], 0, 10000):
+        raise ValueError(f"gloss_structure: top={opts['top']!r}, expected an integer in 0..10000")
+    return opts
+
+
+def save_gloss_structure(train_data, opts, dataset_args, device, workdir, field_codes=None, field_weights=None):
+    """``slnlp.gloss_structure`` of ``train_data`` under the ``gloss_structure`` key's metric as ``train_gloss_structure.json``,
+    ``train_gloss_structure_rows.csv`` and ``train_gloss_distance.csv`` in ``workdir``.  ``field_codes``: the table of the phono
+    metric (None: ``phono_field_codes``); ``field_weights``: the weights ``phono_baseline.fit_weights`` fitted -- the report is
+    then the weighted metric's, and the mean silhouette under unit weights is recorded beside it.  Returns the report."""
+    from .gloss_structure import gloss_structure
+    metric = {}
+    if opts["metric"] == "phono":
+        codes = phono_field_codes(train_data, dataset_args, "gloss_structure") if field_codes is None else np.asarray(field_codes)
+        metric = {"field_codes": codes}
+    res = gloss_structure(train_data, max_len=opts["max_len"], device=device, top=opts["top"], **metric)
+    out = {"options": dict(opts)}
+    if metric and field_weights is not None:
+        out["mean_silhouette_unit"] = res["mean_silhouette"]
+        res = gloss_structure(train_data, device=device, top=opts["top"], field_weights=[int(w) for w in field_weights], **metric)
+        out.update(mean_silhouette_weighted=res["mean_silhouette"], field_weights=[int(w) for w in field_weights])
+    names = train_data.vocab_y.itos if getattr(train_data, "vocab_y", None) is not None else None
+    name = lambda c: str(c) if names is None or c is None else names[int(c)]
+    cell = lambda v: None if isinstance(v, float) and v != v else v
+    out.update({k: cell(res[k]) for k in ("rows", "flagged", "max_distance", "mean_silhouette", "misplaced_share")})
+    out["per_class"] = [{"class": c.item(), "name": name(c), "support": int(res["counts"][k]), "silhouette": cell(float(res["class_silhouette"][k])),
+                         "medoid": int(res["medoids"][k])} for k, c in enumerate(res["classes"])]
+    out["closest_pairs"] = [[a, b, name(a), name(b), d, na, nb] for a, b, d, na, nb in res["closest_pairs"]]
+    out["misplaced"] = [dict(m, name=name(m["label"]), nearest_name=name(m["nearest_class"])) for m in res["misplaced"]]
+    save_json(out, os.path.join(workdir, "train_gloss_structure.json"))
+    medoids = set(int(m) for m in res["medoids"] if m >= 0)
+    y = np.asarray(train_data.y)
+    with open(os.path.join(workdir, "train_gloss_structure_rows.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["row", "label", "name", "a", "b", "silhouette", "nearest_class", "nearest_name", "medoid"])
+        for i in range(len(train_data)):
+            near = res["nearest_class"][i]
+            w.writerow([i, int(y[i]), name(y[i]), res["a"][i], res["b"][i], res["silhouette"][i], "" if near is None else near,
+                        "" if near is None else name(near), int(i in medoids)])
+    with open(os.path.join(workdir, "train_gloss_distance.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["", *[name(c) for c in res["classes"]]])
+        for k, c in enumerate(res["classes"]):
+            w.writerow([name(c), *res["class_distance"][k].tolist()])
+    return res
+
+
 def save_phono_baseline(est, train_data, test_data, opts, dataset_args, intervals, metrics, device, workdir, unit=None, field_codes=None):
     """``slnlp.PhonoKNN`` fitted on ``train_data`` and scored on ``test_data`` as ``test_phono_baseline.json``, and
     ``slnlp.split_audit(field_codes=...)`` of the split with the refit ``est`` as the judge as ``test_phono_split_audit.json`` /
@@ -1145,6 +1231,7 @@ def run(args):
     baseline = baseline_options(args.get("baseline"))
     phono = phono_baseline_options(args.get("phono_baseline"))
     grouped = grouped_splits_options(args.get("grouped_splits"))
+    structure = gloss_structure_options(args.get("gloss_structure"))
     if rank == 0:
         os.makedirs(workdir, exist_ok=True)
         import yaml
@@ -1162,6 +1249,8 @@ def run(args):
         dataset = balance_dataset(dataset, seed)
     test_data, train_data = dataset.split(float(args.get("test_size", 0.15)), seed)
     phono_codes = phono_field_codes(dataset, args.get("dataset_args")) if phono is not None else None      # fails before the grid search
+    if structure is not None and structure["metric"] == "phono" and phono_codes is None:
+        phono_codes = phono_field_codes(dataset, args.get("dataset_args"), "gloss_structure")
 
     net_params = build_net_params(args, dataset, device)
     factory = lambda: NeuralNetClassifier(**net_params)
@@ -1208,9 +1297,13 @@ def run(args):
         unit = None
         if baseline is not None:
             unit, _ = save_baseline(est, train_data, test_data, baseline, intervals, metrics, device, workdir)
+        phono_knn = None
         if phono is not None:
-            save_phono_baseline(est, train_data, test_data, phono, args.get("dataset_args"), intervals, metrics, device, workdir, unit=unit,
-                                field_codes=phono_codes)
+            phono_knn, _ = save_phono_baseline(est, train_data, test_data, phono, args.get("dataset_args"), intervals, metrics, device, workdir,
+                                               unit=unit, field_codes=phono_codes)
+        if structure is not None:
+            save_gloss_structure(train_data, structure, args.get("dataset_args"), device, workdir, field_codes=phono_codes,
+                                 field_weights=getattr(phono_knn, "field_weights", None))
         # workdir/{params,optimizer,criterion}.pt + history.json are the refit's best-valid-loss checkpoint (skorch
         # Checkpoint(monitor="valid_loss_best", dirname=workdir), helper.py:211-213) and stay untouched; the weights
         # after the last epoch (not kept by the reference) go to a directory of their own

@@ -5,6 +5,7 @@ import ctypes as C
 import math
 import numbers
 
+import numpy as np
 import torch
 
 from . import _lib, _packed
@@ -1958,6 +1959,101 @@ def dup_groups_download(buf):
     if int(out["head"][3]) != 0:
         raise RuntimeError(f"dup_groups_download: the device reports code {int(out['head'][3])}: a union-find loop exhausted its bound of N + 1 "
                            "rounds; the groups are not to be used")
+    return out
+
+
+GLOSS_MAKER = "gloss_structure_buffers(N, C, labels, max_distance, device)"
+
+
+def gloss_structure_buffers(N, C, labels, max_distance, device):
+    """The state and the outputs of one gloss-structure pass over ``N`` rows of ``C`` classes (csrc/gloss_structure.hip) as slices
+    of ONE int64 allocation, so that ``gloss_structure_download`` is one copy:
+
+        head int64 [8] | own uint32 [N] | other uint32 [N] | other_class int32 [N] | count int32 [C] | medoid int32 [C]
+                       | class_sum int64 [C, C] | med_sum int64 [C]
+
+    (``own`` and ``other`` are held as int32 tensors: the same bits).  ``labels``: N integers in -1..C-1 (-1: the row is left
+    out), a host array or a tensor; they are uploaded as int32 (``buf["label"]``) and the pass begun
+    (``slnlp_gloss_structure_begin``: the class counts taken, the sums zeroed) on the current stream of ``device``; no host wait.
+    ``max_distance``: the metric's bound -- 64, ``max_len``, 64 F or 64 W; ``max_distance * N`` must stay below 2^32.  A label
+    outside -1..C-1 is found on the device and raised by ``gloss_structure_download``."""
+    what = "gloss_structure_buffers"
+    _lib.require_gpu()
+    N = _int_in(what, "N", N, 1, _lib.EDIT_MAX_ROWS)
+    C = _int_in(what, "C", C, 1, _lib.GLOSS_MAX_CLASSES)
+    max_distance = _int_in(what, "max_distance", max_distance, 1, 65534)
+    if max_distance * N >= 2 ** 32:
+        raise ValueError(f"{what}: max_distance={max_distance} times N={N} reaches 2^32: a row's sum over one class must fit 32 bits")
+    device = torch.device(device)
+    lab = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    if lab.dim() != 1 or lab.shape[0] != N or lab.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: labels must be {N} int32 or int64 values in -1..{C - 1}")
+    with torch.cuda.device(device):
+        label = lab.to(device=device, dtype=torch.int32).contiguous()
+        p = _packed.Packed(torch.int64, (("head", torch.int64, _lib.GLOSS_HEAD_BYTES // 8, 8), ("own", torch.int32, N, 4),
+                                         ("other", torch.int32, N, 4), ("other_class", torch.int32, N, 4), ("count", torch.int32, C, 4),
+                                         ("medoid", torch.int32, C, 4), ("class_sum", torch.int64, (C, C), 8), ("med_sum", torch.int64, C, 8)),
+                           device)
+        buf = _packed_dict(p, (N, C), label=label, max_distance=max_distance)
+        check(load().slnlp_gloss_structure_begin(ptr(label), N, C, max_distance, ptr(buf["count"]), ptr(buf["class_sum"]), ptr(buf["med_sum"]),
+                                                 ptr(buf["medoid"]), ptr(buf["head"]), stream_ptr()), what)
+    return buf
+
+
+def _gloss_buf(what, buf):
+    _packed_buf(what, buf, GLOSS_MAKER, (), None, more=2)
+    if "label" not in buf or "class_sum" not in buf:
+        raise ValueError(f"{what}: buf must be {GLOSS_MAKER}")
+    return buf["shape"]
+
+
+def gloss_structure_rows(dist, q0, buf):
+    """One chunk of distances into ``buf``'s sums (``slnlp_gloss_structure_rows``): ``dist`` a contiguous uint8 or uint16 [nq, N]
+    device tensor, what ``edit_distances`` / ``edit_long_distances`` / ``field_distances`` write for the data set's rows ``q0 .. q0
+    + nq - 1`` against all N of them.  Every row of the data set arrives exactly once, in any order.  One launch on the current
+    stream of ``dist``'s device; no host wait.  Returns ``buf``."""
+    what = "gloss_structure_rows"
+    N, C = _gloss_buf(what, buf)
+    dev = buf["flat"].device
+    if not (torch.is_tensor(dist) and dist.dtype in DUP_WIDTHS and dist.dim() == 2 and dist.shape[1] == N and dist.shape[0] >= 1
+            and dist.is_contiguous() and dist.device == dev):
+        raise ValueError(f"{what}: dist must be a contiguous uint8 or uint16 [nq >= 1, {N}] tensor on {dev}")
+    width, nq = DUP_WIDTHS[dist.dtype], int(dist.shape[0])
+    q0 = _int_in(what, "q0", q0, 0, N - 1)
+    _lib.require_gpu()
+    with torch.cuda.device(dev):
+        check(load().slnlp_gloss_structure_rows(ptr(dist), width, nq, N, q0, ptr(buf["label"]), C, ptr(buf["count"]), ptr(buf["own"]),
+                                                ptr(buf["other"]), ptr(buf["other_class"]), ptr(buf["class_sum"]), ptr(buf["med_sum"]),
+                                                ptr(buf["head"]), stream_ptr()), what)
+    return buf
+
+
+def gloss_structure_finish(buf):
+    """The medoids of ``buf``'s classes and the head's class count (``slnlp_gloss_structure_finish``).  Two launches on the current
+    stream of ``buf``'s device; no host wait.  Returns ``buf``."""
+    what = "gloss_structure_finish"
+    N, C = _gloss_buf(what, buf)
+    _lib.require_gpu()
+    with torch.cuda.device(buf["flat"].device):
+        check(load().slnlp_gloss_structure_finish(ptr(buf["label"]), ptr(buf["own"]), ptr(buf["med_sum"]), N, C, ptr(buf["medoid"]),
+                                                  ptr(buf["head"]), stream_ptr()), what)
+    return buf
+
+
+def gloss_structure_download(buf):
+    """What a gloss-structure pass hands to the host in ONE device-to-host copy: {head int64 [8] = (labelled rows, non-empty
+    classes, rows left out, code, the sum of own, 0, 0, 0), own uint32 [N], other uint32 [N], other_class int32 [N], count int32
+    [C], medoid int32 [C], class_sum int64 [C, C]}.  A code other than 0 raises RuntimeError: bit 0 -- the sentinel of an
+    unusable row met at a pair of two LABELLED rows (the caller labels such rows -1); bit 1 -- a label outside -1..C-1."""
+    what = "gloss_structure_download"
+    _gloss_buf(what, buf)
+    out = buf["packed"].cut("head", "class_sum")
+    code = int(out["head"][3])
+    if code != 0:
+        why = [w for bit, w in ((1, "a distance sentinel at a pair of labelled rows (a row the metric refuses must be labelled -1)"),
+                                (2, f"a label outside -1..{buf['shape'][1] - 1}")) if code & bit]
+        raise RuntimeError(f"{what}: the device reports code {code}: {'; '.join(why)}; the result is not to be used")
+    out["own"], out["other"] = out["own"].view(np.uint32), out["other"].view(np.uint32)
     return out
 
 
