@@ -38,7 +38,10 @@ __device__ __forceinline__ float clip_coef(const float* __restrict__ partials, f
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
-    return max_norm > 0.f ? fminf(max_norm / (norm + 1e-6f), 1.f) : 1.f;
+    // a NaN norm (one NaN gradient element) gives a NaN coefficient, as torch's clamp does: fminf alone would return its other
+    // operand, 1, and every finite element would take an unclipped step.  An infinite norm gives 0
+    const float coef = norm != norm ? norm : fminf(max_norm / (norm + 1e-6f), 1.f);
+    return max_norm > 0.f ? coef : 1.f;
 }
 
 __device__ __forceinline__ void update_done(float norm, float* __restrict__ norm_out, unsigned long long* __restrict__ rng) {

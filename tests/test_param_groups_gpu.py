@@ -291,16 +291,17 @@ def test_set_param_groups_drops_captured_graphs():
         eng.set_param_groups({"seg_begin": [0, 2046], "seg_group": [0, 1], "weight_decay": [0.0, 0.0]}, lr)
 
 
-def weight_planes(eng):
-    """The bf16 hi / lo planes of the encoder layers' weights -- the range the update writes and the plane GEMMs read -- as int16
-    views of the plan's workspace (``slnlp_tf_debug_layout`` names the offsets)."""
+def weight_planes(eng, lo=None, hi=None):
+    """The bf16 hi / lo planes of the encoder layers' weights -- the range the update writes and the plane GEMMs read at B <= 64 --
+    or of arena floats [lo, hi), as int16 views of the plan's workspace (``slnlp_tf_debug_layout`` names the offsets)."""
     import ctypes as C
     from slnlp import _lib
     buf = C.create_string_buffer(1 << 16)
     _lib.check(_lib.load().slnlp_tf_debug_layout(C.byref(eng.cfg), buf, len(buf)), "layout")
     at = dict((k, int(v)) for k, v in (line.split() for line in buf.value.decode().splitlines()))
     off = {name: o for name, _, o in eng.entries}
-    lo, hi = off["transformer.encoder.layers.0.self_attn.in_proj_weight"], off["transformer.encoder.norm.weight"]
+    lo = off["transformer.encoder.layers.0.self_attn.in_proj_weight"] if lo is None else lo
+    hi = off["transformer.encoder.norm.weight"] if hi is None else hi
     planes = []
     for which in ("wp.hi", "wp.lo"):
         plane = eng.workspace[at[which]:at[which] + 2 * eng.arena_floats].view(torch.int16)
