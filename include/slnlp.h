@@ -71,7 +71,10 @@ typedef struct slnlp_gemm_args {
     /* Optional PRE-SPLIT operands (bf16 hi / lo planes, row-major, rows and columns zero-padded to
      * multiples of 64, row stride ld*_p elements).  When A_hi and B_hi are set the GEMM stages them by
      * LDS-DMA and does no conversion (A, B, lda, ldb are then ignored; *_lo required for precision 3).
-     * C_hi / C_lo (optional): also emit the result as planes for the next GEMM. C may then be NULL. */
+     * C_hi / C_lo (optional): also emit the result as planes for the next GEMM. C may then be NULL.
+     * Every GEMM (slnlp_gemm, slnlp_gemm_group, slnlp_gemm_rows, slnlp_gemm_rows_bwd) stores plane words (m < M, n < N) only:
+     * the words past (M, N) -- inside the 64-aligned box and beyond -- are left as they are, never zeroed.  The zero padding the
+     * next GEMM reads therefore comes from the planes' allocation, and survives every producer. */
     const uint16_t* A_hi; const uint16_t* A_lo; int64_t lda_p;
     const uint16_t* B_hi; const uint16_t* B_lo; int64_t ldb_p;
     uint16_t* C_hi; uint16_t* C_lo; int64_t ldc_p;
